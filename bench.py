@@ -262,6 +262,38 @@ def bench_bf16x3(args, cfg, ds, od, ad, B, torch):
     return res
 
 
+DUMP_CAP_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, info, params, cap_bytes=DUMP_CAP_BYTES):
+    """--dump-outputs: what the timed path hands its caller after its last step - the 13 info scalars and the updated parameter tree -
+    as float32 .npy files, `info__<key>.npy` and `params__<leaf path>.npy` ('/' -> '__').  Past `cap_bytes` every leaf is cut to the same
+    fraction of its elements at fixed, seeded positions (flattened), so two builds stay comparable file for file."""
+    os.makedirs(out_dir, exist_ok=True)
+    leaves = []
+
+    def walk(node, path):
+        for k in sorted(node):
+            if isinstance(node[k], dict):
+                walk(node[k], path + [k])
+            else:
+                leaves.append(('__'.join(path + [k]), np.asarray(node[k], dtype=np.float32)))
+    walk(params, [])
+    total = sum(a.nbytes for _, a in leaves) + 4 * len(info)
+    frac = min(1.0, (cap_bytes - 4 * len(info)) / total)
+    written = 0
+    for k, v in info.items():
+        np.save(os.path.join(out_dir, 'info__' + k.replace('/', '__') + '.npy'), np.asarray(v, dtype=np.float32))
+        written += 4
+    for i, (name, a) in enumerate(leaves):
+        if frac < 1.0:
+            n = max(1, int(a.size * frac))
+            a = a.reshape(-1)[np.sort(np.random.default_rng(i).choice(a.size, size=n, replace=False))]
+        np.save(os.path.join(out_dir, 'params__' + name + '.npy'), a)
+        written += a.nbytes
+    return {'dir': out_dir, 'files': len(info) + len(leaves), 'bytes': written, 'sampled': frac < 1.0}
+
+
 def spawn_ranks(n):
     """`python bench.py --gpus N` without a launcher: start N fresh ranks of this script (one per GPU, RCCL over xGMI) with the
     torch.distributed environment the launcher would have set, relay rank 0's ONE json line on stdout, return the worst exit code.
@@ -302,6 +334,8 @@ def main():
     ap.add_argument('--precision', choices=['fp32', 'bf16x3'], default=os.environ.get('FQL_BENCH_PRECISION', 'fp32'),
                     help="fp32 = fp32 matrix cores (the headline); bf16x3 = split-bf16 products on the bf16 matrix cores, fp32 accumulate "
                          "(fql_config.precision = 2; reported against the bf16 peak / 3)")
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps write the last step\'s info scalars and updated parameters as DIR/<name>.npy (float32, <= 64 MB)')
     args = ap.parse_args()
 
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
@@ -391,6 +425,8 @@ def main():
         dt = float(t.item())
     info = agent.read_info()
     st = agent.stats()
+    # before any later pass (kernel profile, host batches) steps the agent again
+    dumped = dump_outputs(args.dump_outputs, info, agent.get_params()) if args.dump_outputs and rank == 0 else None
 
     if rank == 0:
         steps_per_s = args.steps / dt
@@ -418,6 +454,8 @@ def main():
                              'kernel_launches_per_update': st['launches_per_update']},
             'last_info': {k: round(v, 5) for k, v in info.items()},
         }
+        if dumped:
+            out['dumped_outputs'] = dumped
         roof = {'bound': 'mfma', 'achieved': round(whole, 3), 'peak': peak_tf, 'unit': 'TFLOP/s',
                 'frac': round(whole / peak_tf, 4), 'traffic': None, 'kernel': 'whole update (per-kernel pass skipped)'}
         if world == 1 and not args.no_extras:

@@ -41,3 +41,29 @@ def test_committed_pmc_summary_belongs_to_this_tree_and_bench_reads_it():
         import warnings
         warnings.warn('fql_amd/csrc changed after profiles/%s was measured: re-run tools/profile.sh' % bench.PMC_FILE)
     assert bench.pmc_counters('no_such_file.json', 'fql_side_kernel') == {}
+
+
+def test_dump_outputs_writes_float32_leaves_and_samples_past_the_cap(tmp_path):
+    import numpy as np
+    bench = _load('bench_mod', os.path.join(ROOT, 'bench.py'))
+    rng = np.random.default_rng(0)
+    params = {'modules_critic': {'Dense_0': {'kernel': rng.standard_normal((64, 32)), 'bias': rng.standard_normal(32).astype(np.float32)}},
+              'modules_actor': {'Dense_0': {'kernel': rng.standard_normal((16, 8)).astype(np.float32)}}}
+    info = {'critic/critic_loss': 1.5, 'grad/norm': 2.25}
+    full = bench.dump_outputs(str(tmp_path / 'full'), info, params)
+    assert full['files'] == 5 and not full['sampled']
+    k = np.load(tmp_path / 'full' / 'params__modules_critic__Dense_0__kernel.npy')
+    assert k.dtype == np.float32 and k.shape == (64, 32)
+    np.testing.assert_array_equal(k, params['modules_critic']['Dense_0']['kernel'].astype(np.float32))
+    assert float(np.load(tmp_path / 'full' / 'info__grad__norm.npy')) == 2.25
+    # past the cap: a fixed, seeded subset of every leaf, the same on every call, within the byte budget
+    cap = 4 * 1000
+    a = bench.dump_outputs(str(tmp_path / 'a'), info, params, cap_bytes=cap)
+    b = bench.dump_outputs(str(tmp_path / 'b'), info, params, cap_bytes=cap)
+    assert a['sampled'] and a['bytes'] <= cap and a['files'] == 5
+    for f in sorted(os.listdir(tmp_path / 'a')):
+        x, y = np.load(tmp_path / 'a' / f), np.load(tmp_path / 'b' / f)
+        assert x.dtype == np.float32
+        np.testing.assert_array_equal(x, y)
+    s = np.load(tmp_path / 'a' / 'params__modules_critic__Dense_0__kernel.npy')
+    assert 0 < s.size < 64 * 32 and np.isin(s, params['modules_critic']['Dense_0']['kernel'].astype(np.float32)).all()
