@@ -2,10 +2,10 @@
 
 `agents` mirrors the reference registry (agents/__init__.py:10-19) for the one agent on the built path.
 """
-from .agent import FQLAgent, INFO_KEYS, NOISE_KEYS
+from .agent import FQLAgent, FQLAgentGroup, INFO_KEYS, NOISE_KEYS
 from .config import get_config
 from .datasets import Dataset, ReplayBuffer
 
 agents = dict(fql=FQLAgent)
 
-__all__ = ['FQLAgent', 'get_config', 'agents', 'INFO_KEYS', 'NOISE_KEYS', 'Dataset', 'ReplayBuffer']
+__all__ = ['FQLAgent', 'FQLAgentGroup', 'get_config', 'agents', 'INFO_KEYS', 'NOISE_KEYS', 'Dataset', 'ReplayBuffer']

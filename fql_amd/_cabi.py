@@ -87,6 +87,10 @@ SYMBOLS = {
     'fql_synchronize': (_I, [_VP, C.POINTER(_I)]),
     'fql_stats': (_I, [_VP, C.POINTER(_I64), C.POINTER(_I64), C.POINTER(_I64)]),
     'fql_stream': (_VP, [_VP]),
+    'fql_group_create': (_I, [_VP, _I, C.POINTER(_VP)]),
+    'fql_group_destroy': (_I, [_VP]),
+    'fql_group_update_from_dataset': (_I, [_VP, _VP, _I, _VP, _VP]),
+    'fql_group_synchronize': (_I, [_VP]),
 }
 
 _lib = None

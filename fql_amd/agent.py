@@ -222,7 +222,9 @@ class FQLAgent:
 
     def close(self):
         if getattr(self, '_h', None):
-            self._lib.fql_destroy(self._h)
+            rc = self._lib.fql_destroy(self._h)
+            if rc == _cabi.FQL_E_STATE:   # a member of an agent group: the handle stays valid until the group is closed
+                self._check(rc)
             self._h = None
 
     def __del__(self):
@@ -651,3 +653,107 @@ class FQLAgent:
         a, b, c = C.c_int64(), C.c_int64(), C.c_int64()
         self._check(self._lib.fql_stats(self._h, C.byref(a), C.byref(b), C.byref(c)))
         return {'launches_per_update': int(a.value), 'macs_per_update': int(b.value), 'param_count': int(c.value)}
+
+
+class FQLAgentGroup:
+    """K agents of one structure - the same config except `seed` and `alpha` - trained side by side by ONE fused update program
+    (include/fql_amd.h, fql_group_*): every launch of the update carries all K members' tasks.  The seed / alpha sweeps the reference
+    recommends (README "Tips for hyperparameter tuning") on one device:
+
+        group = FQLAgentGroup.create([0, 1, 2], ex_obs, ex_act, config, alphas=[0.3, 3, 30])
+        group.upload_dataset(train_dataset)
+        for step in range(n):
+            infos = group.update_from_dataset(want_info=(step % log_every == 0))
+
+    `members` are ordinary FQLAgent objects (sample_actions, total_loss, get/set_params, checkpoints, ...); a member's trajectory is
+    bitwise the one it has when trained alone with the same seed, alpha, rows and noise.  Members are state agents with precision 'fp32'
+    and the engine's device RNG; while grouped their batch size is fixed."""
+
+    def __init__(self, handle, members):
+        self._lib = _cabi.load()
+        self._g = handle
+        self.members = members
+        self.batch_size = int(members[0].config['batch_size'])
+        self._keep = None
+
+    @classmethod
+    def create(cls, seeds, ex_observations, ex_actions, config, alphas=None):
+        seeds = [int(s) for s in seeds]
+        if not seeds:
+            raise ValueError('an agent group needs at least one seed')
+        cfg = get_config()
+        cfg.update(dict(config))
+        alphas = [float(cfg['alpha'])] * len(seeds) if alphas is None else [float(a) for a in alphas]
+        if len(alphas) != len(seeds):
+            raise ValueError(f'{len(seeds)} seeds but {len(alphas)} alphas')
+        if cfg.get('encoder') is not None:
+            raise NotImplementedError('agent groups take state agents only (encoder=None)')
+        if cfg.get('precision', 'fp32') not in ('fp32', 0):
+            raise NotImplementedError("agent groups take precision='fp32' members only")
+        if cfg.get('rng') is not None and cfg.get('rng') != 'engine':
+            raise NotImplementedError(f"agent groups draw rows and noise from the engine's device RNG; rng={cfg.get('rng')!r} is not supported")
+        lib = _cabi.load()
+        members = []
+        for s, a in zip(seeds, alphas):
+            c = dict(cfg)
+            c['alpha'] = a
+            members.append(FQLAgent.create(s, ex_observations, ex_actions, c))
+        arr = (C.c_void_p * len(members))(*[m._h for m in members])
+        g = C.c_void_p()
+        _cabi.check(lib, None, lib.fql_group_create(arr, len(members), C.byref(g)))
+        return cls(g, members)
+
+    def _check(self, rc):
+        _cabi.check(self._lib, None, rc)
+
+    def upload_dataset(self, dataset, capacity: Optional[int] = None):
+        """Every member gets its own device copy of `dataset` (FQLAgent.upload_dataset)."""
+        for m in self.members:
+            m.upload_dataset(dataset, capacity=capacity)
+
+    def update_from_dataset(self, batch_size=None, idxs=None, want_info=False):
+        """One fused update of every member: rows from each member's dataset (`idxs` [K, B] int, host or device, or None = each member's
+        device RNG), noise from each member's device RNG.  Returns a list of K LazyInfo (want_info) or None."""
+        K, B = len(self.members), int(batch_size or self.batch_size)
+        if B != self.batch_size:
+            raise ValueError(f'batch_size {B}: the members of a group keep the batch size they were grouped with ({self.batch_size})')
+        ip, keep, stream = None, None, None
+        if idxs is not None:
+            if hasattr(idxs, 'data_ptr'):
+                keep = idxs.long().contiguous()
+                if tuple(keep.shape) != (K, B):
+                    raise ValueError(f'idxs must be [{K}, {B}], got {tuple(keep.shape)}')
+                if keep.is_cuda:
+                    h = _torch().cuda.current_stream().cuda_stream
+                    stream = h if h else _cabi.FQL_STREAM_LEGACY
+                ip = keep.data_ptr()
+            else:
+                keep = np.ascontiguousarray(idxs, dtype=np.int64)
+                if keep.shape != (K, B):
+                    raise ValueError(f'idxs must be [{K}, {B}], got {keep.shape}')
+                ip = keep.ctypes.data
+            if not (hasattr(keep, 'is_cuda') and keep.is_cuda):
+                a = keep.numpy() if hasattr(keep, 'numpy') else keep
+                for i, m in enumerate(self.members):
+                    n = m.dataset_size()[0]
+                    if B and (a[i].min() < 0 or a[i].max() >= n):
+                        raise ValueError(f'idxs[{i}] out of range: [{int(a[i].min())}, {int(a[i].max())}] for {n} rows')
+        self._check(self._lib.fql_group_update_from_dataset(self._g, ip, B, None, stream))
+        self._keep = keep
+        return [m._lazy_info(None) for m in self.members] if want_info else None
+
+    def synchronize(self):
+        """Host wait for the group's last update."""
+        self._check(self._lib.fql_group_synchronize(self._g))
+
+    def close(self):
+        """Destroy the fused program; the members stay usable as standalone agents."""
+        if getattr(self, '_g', None):
+            self._lib.fql_group_destroy(self._g)
+            self._g = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

@@ -356,7 +356,7 @@ struct Dgrad0Args {
     GemmTask t[4];
     int ntasks, col0;
 };
-__global__ __launch_bounds__(FQL_THREADS) void fql_dgrad0_kernel(const Dgrad0Args P) {
+__device__ __forceinline__ void fql_dgrad0_body(const Dgrad0Args& P) {
     __shared__ __attribute__((aligned(16))) float red[4 * 64 * 4];
     const int tid = threadIdx.x, kp = tid >> 6, lane = tid & 63, c = lane & 15, q = lane >> 4;
     const int ntm = P.t[0].M >> 4;
@@ -386,6 +386,9 @@ __global__ __launch_bounds__(FQL_THREADS) void fql_dgrad0_kernel(const Dgrad0Arg
     for (int p = 0; p < 4; ++p) v += red[(p * 64 + lane) * 4 + kp];      // wave kp finishes row 4q + kp, column c
     stg(T.C + (size_t)(row0 + 4 * q + kp) * T.ldc + P.col0 + c, v);
 }
+__global__ __launch_bounds__(FQL_THREADS) void fql_dgrad0_kernel(const Dgrad0Args P) { fql_dgrad0_body(P); }
+// multi-instance entry point (agent groups): blockIdx.y picks the member, its argument struct comes from a device array
+__global__ __launch_bounds__(FQL_THREADS) void fql_dgrad0_multi_kernel(const Dgrad0Args* __restrict__ args) { fql_dgrad0_body(args[blockIdx.y]); }
 
 // The one-step actor's head dgrad (agents/fql.py:62-79 through utils/networks.py:53-58) as a launch of its own on the critical lane, between the Euler
 // chain and the three tail dgrads: dX = (dA W_head^T) * GELU'(z_3) with dA = d(actor loss)/d(one-step actions) built in the prologue (GF_A_LOSSACT: distillation
@@ -393,7 +396,7 @@ __global__ __launch_bounds__(FQL_THREADS) void fql_dgrad0_kernel(const Dgrad0Arg
 // partials, same loads and summation order as fql_euler_finish_kernel).  The contraction is 16 wide - four MFMAs a wave - so the launch is its loads: the task
 // arrives as the kernel argument (no table hop), one thread builds one dA element, a wave owns a 16 x 16 output tile.  It replaces the generic 16-row kernel's
 // instantiation for this task (216 registers and 192 spilled scalars there: every other flag combination's state was live through it).
-__global__ __launch_bounds__(FQL_THREADS) void fql_head_dgrad_kernel(const GemmTask T) {
+__device__ __forceinline__ void fql_head_dgrad_body(const GemmTask& T) {
     __shared__ __attribute__((aligned(16))) float da[16 * 20];
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, c = lane & 15, q = lane >> 4;
     const int ntn = T.N >> 6;
@@ -437,6 +440,9 @@ __global__ __launch_bounds__(FQL_THREADS) void fql_head_dgrad_kernel(const GemmT
 #pragma unroll
     for (int i = 0; i < 4; ++i) stg(T.C + (size_t)(row0 + 4 * q + i) * T.ldc + n0 + c, acc[i] * zp[i]);
 }
+__global__ __launch_bounds__(FQL_THREADS) void fql_head_dgrad_kernel(const GemmTask T) { fql_head_dgrad_body(T); }
+// multi-instance entry point (agent groups): blockIdx.y picks the member, its argument struct comes from a device array
+__global__ __launch_bounds__(FQL_THREADS) void fql_head_dgrad_multi_kernel(const GemmTask* __restrict__ args) { const GemmTask T = ((const FQL_CONST_AS GemmTask*)args)[blockIdx.y]; fql_head_dgrad_body(T); }
 
 template <int H, int V>
 __global__ __launch_bounds__(FQL_CHAIN_THREADS, FQL_CHAIN_WAVES) void fql_chain_kernel(const ChainArgs P) { chain_body<H, V>(P); }
@@ -444,6 +450,9 @@ __global__ __launch_bounds__(FQL_CHAIN_THREADS, FQL_CHAIN_WAVES) void fql_chain_
 struct ChainPair { ChainArgs t[2]; };
 template <int H, int V>
 __global__ __launch_bounds__(FQL_CHAIN_THREADS, FQL_CHAIN_WAVES) void fql_chain_pair_kernel(const ChainPair P) { chain_body<H, V>(P.t[blockIdx.y]); }
+// one chain task per member of an agent group (blockIdx.y = member), argument structs in a device array
+template <int H, int V>
+__global__ __launch_bounds__(FQL_CHAIN_THREADS, FQL_CHAIN_WAVES) void fql_chain_multi_kernel(const ChainArgs* __restrict__ args) { const ChainArgs P = args[blockIdx.y]; chain_body<H, V>(P); }
 // ------------------------------------------------------------------------------------------------
 // precision = 2: the same three variants with split-bf16 operands (fql_kernels.h, top).  Weights arrive pre-split from
 // fql_wfrag_kernel (modes 1 / 2: one 16-byte hi and one 16-byte lo load per lane and 32-deep MFMA step, the bytes of the fp32

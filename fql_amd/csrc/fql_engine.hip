@@ -235,6 +235,7 @@ struct EncBuf {
 
 }  // namespace
 
+struct fql_group_s;
 struct fql_engine {
     fql_config cfg{};
     uint64_t seed = 0;
@@ -362,6 +363,19 @@ struct fql_engine {
     unsigned long long* x_stamps = nullptr;
 
     int64_t launches_per_update = 0;
+    // agent groups (fql_group_*): the group this engine is a member of, the event behind that group's last update and whether an entry
+    // point of this engine has run since (then the next group update orders itself behind this engine's stream)
+    fql_group_s* group = nullptr;
+    hipEvent_t grp_done = nullptr;
+    bool grp_pending = false, grp_touched = true;
+    void group_fence() {   // host wait for the group's last update (every entry point: it may read or write what that update writes)
+        grp_touched = true;
+        if (grp_pending) { HIP_CHECK(hipEventSynchronize(grp_done)); grp_pending = false; }
+    }
+    void group_order(hipStream_t s) {   // the same as a stream dependency, for entry points that only enqueue on `s`
+        grp_touched = true;
+        if (grp_pending) HIP_CHECK(hipStreamWaitEvent(s, grp_done, 0));
+    }
     // lazily read infos (the reference returns device scalars that are only read at log time, main.py:276): a ring of pinned host
     // slots, one asynchronous 52-byte copy + event per ticket
     static constexpr int kInfoRing = 64;
@@ -3254,8 +3268,8 @@ struct fql_engine {
 // ================================================================================================
 // FQL_TRY: every entry point that may use HIP on the engine's buffers - updates still on the engine's AQL queues finish first.
 // FQL_TRY_FAST: the update entry points that can go to those queues themselves (run_full decides).
-#define FQL_TRY(h, ...) FQL_TRY_(h, (h)->hip_touch(), __VA_ARGS__)
-#define FQL_TRY_FAST(h, ...) FQL_TRY_(h, (void)0, __VA_ARGS__)
+#define FQL_TRY(h, ...) FQL_TRY_(h, ((h)->group_fence(), (h)->hip_touch()), __VA_ARGS__)
+#define FQL_TRY_FAST(h, ...) FQL_TRY_(h, (h)->group_fence(), __VA_ARGS__)
 #define FQL_TRY_(h, pre, ...)                              \
     try {                                                  \
         pre;                                               \
@@ -3416,6 +3430,7 @@ int fql_create(const fql_config* cfg, uint64_t seed, fql_handle* out) {
 
 int fql_destroy(fql_handle h) {
     if (!h) return FQL_OK;
+    if (h->group) { h->err = "fql_destroy: the handle is a member of an agent group (fql_group_destroy first)"; return FQL_E_STATE; }
     h->stop_workers();
     try { h->aql_drain(); } catch (...) {}
     if (h->stream) hipStreamSynchronize(h->stream);
@@ -3445,6 +3460,7 @@ int fql_destroy(fql_handle h) {
 
 int fql_set_batch_size(fql_handle h, int batch_size) {
     if (!h) return FQL_E_INVALID;
+    if (h->group) { h->err = "fql_set_batch_size: the handle is a member of an agent group (fql_group_destroy first)"; return FQL_E_STATE; }
     FQL_TRY(h, { if (batch_size != h->B) h->build_workspace(batch_size); });
 }
 
@@ -3464,6 +3480,7 @@ int fql_leaf_info(fql_handle h, int index, char* name, int name_cap, int* ndim, 
 static int leaf_rw(fql_handle h, const char* leaf, float* host, size_t n, int which, bool to_device) {
     if (!h) return FQL_E_INVALID;
     try {
+        h->group_fence();
         if (!leaf || !host) invalid("leaf/host pointer must not be NULL");
         const Leaf* l = h->find_leaf(leaf);
         if (!l) { h->err = std::string("unknown leaf: ") + leaf; return FQL_E_NOTFOUND; }
@@ -3871,7 +3888,7 @@ int fql_update_from_dataset(fql_handle h, const int64_t* idx, int batch_size, in
 
 int fql_info_enqueue(fql_handle h, void* stream, uint64_t* ticket) {
     if (!h || !ticket) return FQL_E_INVALID;
-    FQL_TRY(h, {
+    FQL_TRY_(h, ((h)->group_order(pick(h, stream)), (h)->hip_touch()), {
         hipStream_t s = pick(h, stream);
         const uint64_t k = h->info_seq++;
         const int slot = (int)(k % fql_engine::kInfoRing);
@@ -4137,3 +4154,350 @@ int fql_update_from_frames(fql_handle h, const int64_t* idx, const int32_t* crop
         h->finish_info(info13, FQL_NUM_INFO, s);
     });
 }
+
+// ================================================================================================
+// Agent groups: K members of one structure advanced by ONE fused update program.
+// The members' prog_full are zipped launch by launch.  A table-driven launch becomes one launch over the concatenation of the members'
+// task tables (tile0 and the side kernel's sub-table offsets rebased, grid = the sum); an argument-struct launch becomes one launch of the
+// kernel's multi-instance entry point with blockIdx.y = member, reading the member's argument struct from a device array.  Every task keeps
+// the tile shape and arguments its member's program gave it, so each member computes exactly what it computes alone.
+// ================================================================================================
+namespace {
+
+typedef void (*MultiLaunch)(dim3 g, dim3 b, size_t lds, hipStream_t s, const void* args);
+struct MultiEntry {
+    MultiLaunch launch;
+    size_t arg_bytes;
+};
+// single-instance kernel -> its multi-instance entry point
+const std::map<const void*, MultiEntry>& multi_entries() {
+    static const std::map<const void*, MultiEntry> m = [] {
+        std::map<const void*, MultiEntry> e;
+#define FQL_MULTI(single, multi, A) \
+    e[(const void*)(single)] = MultiEntry{[](dim3 g, dim3 b, size_t l, hipStream_t s, const void* a) { hipLaunchKernelGGL(multi, g, b, l, s, (const A*)a); }, sizeof(A)}
+        FQL_MULTI(fql_prep_kernel, fql_prep_multi_kernel, PrepArgs);
+        FQL_MULTI(fql_post_onestep_kernel, fql_post_onestep_multi_kernel, PostOsArgs);
+        FQL_MULTI(fql_loss_critic_kernel, fql_loss_critic_multi_kernel, LossCriticArgs);
+        FQL_MULTI(fql_loss_q_kernel, fql_loss_q_multi_kernel, LossQArgs);
+        FQL_MULTI(fql_loss_bc_kernel, fql_loss_bc_multi_kernel, LossBcArgs);
+        FQL_MULTI(fql_loss_actor_kernel, fql_loss_actor_multi_kernel, LossActorArgs);
+        FQL_MULTI(fql_euler_finish_kernel, fql_euler_finish_multi_kernel, EulerFinishArgs);
+        FQL_MULTI(fql_head_dgrad_kernel, fql_head_dgrad_multi_kernel, GemmTask);
+        FQL_MULTI(fql_dgrad0_kernel, fql_dgrad0_multi_kernel, Dgrad0Args);
+        FQL_MULTI(fql_adam_kernel, fql_adam_multi_kernel, AdamArgs);
+        FQL_MULTI(fql_finalize_kernel, fql_finalize_multi_kernel, FinalizeArgs);
+        FQL_MULTI((fql_chain_kernel<512, 0>), (fql_chain_multi_kernel<512, 0>), ChainArgs);
+        FQL_MULTI((fql_chain_kernel<512, 1>), (fql_chain_multi_kernel<512, 1>), ChainArgs);
+        FQL_MULTI((fql_chain_kernel<512, 2>), (fql_chain_multi_kernel<512, 2>), ChainArgs);
+        FQL_MULTI((fql_chain_kernel<512, 3>), (fql_chain_multi_kernel<512, 3>), ChainArgs);
+        FQL_MULTI((fql_chain_kernel<256, 0>), (fql_chain_multi_kernel<256, 0>), ChainArgs);
+        FQL_MULTI((fql_chain_kernel<256, 1>), (fql_chain_multi_kernel<256, 1>), ChainArgs);
+        FQL_MULTI((fql_chain_kernel<256, 2>), (fql_chain_multi_kernel<256, 2>), ChainArgs);
+        FQL_MULTI((fql_chain_kernel<256, 3>), (fql_chain_multi_kernel<256, 3>), ChainArgs);
+#undef FQL_MULTI
+        return e;
+    }();
+    return m;
+}
+
+bool is_table_launch(OpType t) { return t == OP_GEMM || t == OP_GEMM64 || t == OP_WGRAD || t == OP_LNBWD || t == OP_WFRAG; }
+
+struct GLaunch {
+    int lane = 0;
+    std::vector<int> waits;
+    bool record_after = false;
+    hipEvent_t ev = nullptr;
+    bool table = false;
+    Launch L;                   // table-driven: the fused launch (tables, counts, grid), issued like a member's own
+    MultiLaunch multi = nullptr;   // argument-struct: the multi-instance kernel, its grid (y = member), LDS and [K] argument structs
+    dim3 grid, block;
+    size_t lds = 0;
+    void* args = nullptr;
+};
+
+}  // namespace
+
+struct fql_group_s {
+    std::vector<fql_handle> m;
+    int K = 0, B = 0;
+    hipStream_t lanes[FQL_LANES] = {};   // lane 0 = the group's own stream
+    std::vector<GLaunch> launches;
+    bool lane_used[FQL_LANES] = {};
+    hipEvent_t ev_fork = nullptr, ev_join[FQL_LANES] = {}, ev_in = nullptr, ev_done = nullptr;
+    hipGraph_t graph = nullptr;
+    hipGraphExec_t exec = nullptr;
+    std::vector<void*> allocs;
+    int64_t* d_idx = nullptr;   // [K][B] staging of host row indices
+
+    void* upload(const void* src, size_t bytes) {
+        void* d = nullptr;
+        HIP_CHECK(hipMalloc(&d, std::max<size_t>(bytes, 16)));
+        allocs.push_back(d);
+        if (bytes) HIP_CHECK(hipMemcpy(d, src, bytes, hipMemcpyHostToDevice));
+        return d;
+    }
+    // the members' task tables one after the other, each member's tile0 shifted by `shift[member]` (MiscTask: no tile0, no shift)
+    template <typename T>
+    void* fuse(const std::vector<const void*>& tables, const std::vector<int>& counts, const std::vector<int>& shift, bool rebase = true) {
+        std::vector<T> all;
+        for (size_t i = 0; i < tables.size(); ++i) {
+            std::vector<T> h((size_t)counts[i]);
+            if (counts[i]) HIP_CHECK(hipMemcpy(h.data(), tables[i], (size_t)counts[i] * sizeof(T), hipMemcpyDeviceToHost));
+            if (rebase) for (T& t : h) rebase_tile0(t, shift[i]);
+            all.insert(all.end(), h.begin(), h.end());
+        }
+        return upload(all.data(), all.size() * sizeof(T));
+    }
+    template <typename T> static void rebase_tile0(T& t, int d) { t.tile0 += d; }
+    static void rebase_tile0(MiscTask&, int) {}   // (indexed by workgroup - tile_m: concatenation is the rebase)
+
+    // one fused launch from launch `li` of every member's prog_full; `rec[k]` = what member k's issue() would dispatch
+    GLaunch zip(int li, const std::vector<AqlDispatch>& rec) {
+        const Launch& L0 = m[0]->prog_full.launches[li];
+        GLaunch G;
+        G.lane = L0.lane; G.waits = L0.waits; G.record_after = L0.record_after;
+        if (is_table_launch(L0.type)) {
+            G.table = true;
+            Launch F = L0;
+            F.ev = nullptr; F.waits.clear();
+            std::vector<const void*> tg, tw, tl, tm;
+            std::vector<int> ng, nw, nl, nm, sg, sw, sl, sm;
+            int cg = 0, cw = 0, cl = 0, cm = 0, ntot = 0;
+            for (int k = 0; k < K; ++k) {
+                const Launch& L = m[k]->prog_full.launches[li];
+                if (L0.type == OP_WFRAG) {
+                    tg.push_back(m[k]->d_wfrag); ng.push_back(m[k]->wfrag_n); sg.push_back(cg); cg += m[k]->wfrag_grid; ntot += m[k]->wfrag_n;
+                } else if (L.side) {
+                    tg.push_back(L.table); ng.push_back(L.ntasks); sg.push_back(cg); cg += L.tile_w;
+                    tw.push_back(L.table_w); nw.push_back(L.n_w); sw.push_back(cw); cw += L.tile_l - L.tile_w;
+                    tl.push_back(L.table_l); nl.push_back(L.n_l); sl.push_back(cl); cl += L.tile_m - L.tile_l;
+                    tm.push_back(L.table_m); nm.push_back(L.grid - L.tile_m); sm.push_back(0); cm += L.grid - L.tile_m;
+                } else {
+                    tg.push_back(L.table); ng.push_back(L.ntasks); sg.push_back(cg); cg += L.grid; ntot += L.ntasks;
+                }
+            }
+            if (L0.type == OP_WFRAG) {
+                F.table = fuse<WfragTask>(tg, ng, sg); F.ntasks = ntot; F.grid = cg;
+            } else if (L0.side) {
+                F.table = fuse<GemmTask>(tg, ng, sg);
+                F.table_w = fuse<WgradTask>(tw, nw, sw);
+                F.table_l = fuse<LnBwdTask>(tl, nl, sl);
+                F.table_m = fuse<MiscTask>(tm, nm, sm, false);
+                F.ntasks = F.n_w = F.n_l = 0;
+                for (int k = 0; k < K; ++k) { F.ntasks += ng[k]; F.n_w += nw[k]; F.n_l += nl[k]; }
+                F.tile_w = cg; F.tile_l = cg + cw; F.tile_m = cg + cw + cl; F.grid = F.tile_m + cm;
+            } else {
+                if (L0.type == OP_WGRAD) F.table = fuse<WgradTask>(tg, ng, sg);
+                else if (L0.type == OP_LNBWD) F.table = fuse<LnBwdTask>(tg, ng, sg);
+                else F.table = fuse<GemmTask>(tg, ng, sg);
+                F.ntasks = ntot; F.grid = cg;
+            }
+            G.L = F;
+            return G;
+        }
+        auto it = multi_entries().find(rec[0].fn);
+        if (it == multi_entries().end()) invalid("agent groups: launch %d (op type %d) has no multi-instance kernel", li, (int)L0.type);
+        std::vector<uint8_t> args;
+        for (int k = 0; k < K; ++k) {
+            if (rec[k].args.size() != it->second.arg_bytes) invalid("internal: launch %d records %zu argument bytes, its struct has %zu", li, rec[k].args.size(), it->second.arg_bytes);
+            args.insert(args.end(), rec[k].args.begin(), rec[k].args.end());
+        }
+        G.multi = it->second.launch;
+        G.grid = dim3(rec[0].grid[0], K);
+        G.block = dim3(rec[0].block[0], rec[0].block[1], rec[0].block[2]);
+        G.lds = rec[0].lds;
+        G.args = upload(args.data(), args.size());
+        return G;
+    }
+
+    void issue(GLaunch& G, hipStream_t s) {
+        if (!G.table) { G.multi(G.grid, G.block, G.lds, s, G.args); return; }
+        if (G.L.type == OP_WFRAG) hipLaunchKernelGGL(fql_wfrag_kernel, dim3(G.L.grid), dim3(FQL_THREADS), 0, s, (const WfragTask*)G.L.table, G.L.ntasks, -1);
+        else m[0]->issue(G.L, s, -1);   // (reads the launch and the members' shared config only)
+    }
+
+    // the fused program as ONE graph with the lanes, forks, joins and cross-lane events of a member's own
+    void capture() {
+        hipStream_t s0 = lanes[0];
+        HIP_CHECK(hipStreamBeginCapture(s0, hipStreamCaptureModeThreadLocal));
+        try {
+            HIP_CHECK(hipEventRecord(ev_fork, s0));
+            for (int l = 1; l < FQL_LANES; ++l) if (lane_used[l]) HIP_CHECK(hipStreamWaitEvent(lanes[l], ev_fork, 0));
+            for (GLaunch& G : launches) {
+                hipStream_t s = lanes[G.lane];
+                for (int w : G.waits) HIP_CHECK(hipStreamWaitEvent(s, launches[w].ev, 0));
+                issue(G, s);
+                if (G.record_after) HIP_CHECK(hipEventRecord(G.ev, s));
+            }
+            for (int l = 1; l < FQL_LANES; ++l)
+                if (lane_used[l]) { HIP_CHECK(hipEventRecord(ev_join[l], lanes[l])); HIP_CHECK(hipStreamWaitEvent(s0, ev_join[l], 0)); }
+            HIP_CHECK(hipGetLastError());
+        } catch (...) {
+            hipGraph_t g = nullptr;
+            hipStreamEndCapture(s0, &g);
+            if (g) hipGraphDestroy(g);
+            throw;
+        }
+        HIP_CHECK(hipStreamEndCapture(s0, &graph));
+        HIP_CHECK(hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0));
+    }
+
+    void release() {
+        if (lanes[0]) hipStreamSynchronize(lanes[0]);
+        if (ev_done) hipEventSynchronize(ev_done);
+        for (fql_handle h : m) { h->group = nullptr; h->grp_pending = false; h->grp_done = nullptr; h->grp_touched = true; }
+        if (exec) hipGraphExecDestroy(exec);
+        if (graph) hipGraphDestroy(graph);
+        for (GLaunch& G : launches) if (G.ev) hipEventDestroy(G.ev);
+        for (hipEvent_t e : {ev_fork, ev_in, ev_done}) if (e) hipEventDestroy(e);
+        for (hipEvent_t e : ev_join) if (e) hipEventDestroy(e);
+        for (void* p : allocs) hipFree(p);
+        if (d_idx) hipFree(d_idx);
+        for (hipStream_t s : lanes) if (s) hipStreamDestroy(s);
+    }
+};
+
+namespace {
+// the members' restrictions and the structural identity of their programs (fql_group_create)
+void group_check(const fql_handle* members, int k) {
+    if (!members || k <= 0) invalid("fql_group_create: members must be a non-empty array (k = %d)", k);
+    for (int i = 0; i < k; ++i) {
+        fql_handle h = members[i];
+        if (!h) invalid("fql_group_create: member %d is NULL", i);
+        for (int j = 0; j < i; ++j) if (members[j] == h) invalid("fql_group_create: member %d appears twice", i);
+        if (h->group) invalid("fql_group_create: member %d already belongs to a group", i);
+        if (h->visual) invalid("fql_group_create: member %d has an encoder (groups take state agents only)", i);
+        if (h->cfg.precision != 0) invalid("fql_group_create: member %d has precision %d (groups take fp32 members only)", i, h->cfg.precision);
+        if (h->began) invalid("fql_group_create: member %d is between fql_update_begin and fql_update_end", i);
+        if (!h->prog_full.exec) invalid("fql_group_create: member %d has no single-graph update program", i);
+        if (h->use_pec || h->use_xchain) invalid("fql_group_create: member %d runs a persistent Euler chain (FQL_PEC / FQL_XCHAIN): not groupable", i);
+        fql_config a = h->cfg, b = members[0]->cfg;
+        a.alpha = b.alpha = 0.f;
+        a.batch_size = b.batch_size = 0;
+        if (std::memcmp(&a, &b, sizeof a) != 0)
+            invalid("fql_group_create: member %d's config differs from member 0's in more than seed and alpha", i);
+        if (h->B != members[0]->B) invalid("fql_group_create: member %d has batch size %d, member 0 has %d", i, h->B, members[0]->B);
+        const Program& p = h->prog_full, &p0 = members[0]->prog_full;
+        if (p.launches.size() != p0.launches.size()) invalid("fql_group_create: member %d's update has %zu launches, member 0's %zu", i, p.launches.size(), p0.launches.size());
+        for (size_t li = 0; li < p.launches.size(); ++li) {
+            const Launch &L = p.launches[li], &L0 = p0.launches[li];
+            if (L.type != L0.type || L.lane != L0.lane || L.grid != L0.grid || L.waits != L0.waits || L.side != L0.side || L.tmt2 != L0.tmt2 ||
+                L.kbig != L0.kbig || L.euler != L0.euler || L.record_after != L0.record_after || L.lds != L0.lds)
+                invalid("fql_group_create: launch %zu of member %d differs from member 0's (type %d/%d, lane %d/%d, grid %d/%d)", li, i, (int)L.type,
+                        (int)L0.type, L.lane, L0.lane, L.grid, L0.grid);
+            if (L.type == OP_WFRAG && h->wfrag_grid != members[0]->wfrag_grid) invalid("fql_group_create: member %d's weight-copy launch differs", i);
+        }
+    }
+}
+std::vector<AqlDispatch> record_program(fql_handle h) {
+    std::vector<AqlDispatch> rec;
+    h->aql_rec = &rec;
+    try {
+        for (const Launch& L : h->prog_full.launches) h->issue(L, nullptr, (int)(&L - h->prog_full.launches.data()));
+    } catch (...) { h->aql_rec = nullptr; throw; }
+    h->aql_rec = nullptr;
+    if (rec.size() != h->prog_full.launches.size()) invalid("internal: a launch did not record exactly one dispatch");
+    return rec;
+}
+}  // namespace
+
+extern "C" {
+
+int fql_group_create(const fql_handle* members, int k, fql_group* out) {
+    if (!out) { g_create_error = "fql_group_create: out must not be NULL"; return FQL_E_INVALID; }
+    *out = nullptr;
+    auto* g = new fql_group_s();
+    try {
+        group_check(members, k);
+        g->m.assign(members, members + k);
+        g->K = k;
+        g->B = members[0]->B;
+        for (fql_handle h : g->m) { h->aql_drain(); HIP_CHECK(hipStreamSynchronize(h->stream)); }
+        std::vector<std::vector<AqlDispatch>> rec;
+        for (fql_handle h : g->m) rec.push_back(record_program(h));
+        const size_t n = g->m[0]->prog_full.launches.size();
+        for (size_t li = 0; li < n; ++li)
+            for (int i = 1; i < k; ++i) {
+                const AqlDispatch &a = rec[i][li], &b = rec[0][li];
+                if (a.fn != b.fn || std::memcmp(a.grid, b.grid, sizeof a.grid) || std::memcmp(a.block, b.block, sizeof a.block) || a.lds != b.lds)
+                    invalid("fql_group_create: launch %zu of member %d runs another kernel or shape than member 0's", li, i);
+            }
+        for (size_t li = 0; li < n; ++li) {
+            if (rec[0][li].grid[1] != 1 || rec[0][li].grid[2] != 1) invalid("fql_group_create: launch %zu has a 2-D grid: not groupable", li);
+            std::vector<AqlDispatch> col;
+            for (int i = 0; i < k; ++i) col.push_back(rec[i][li]);
+            g->launches.push_back(g->zip((int)li, col));
+            g->lane_used[g->launches.back().lane] = true;
+        }
+        for (int l = 0; l < FQL_LANES; ++l) HIP_CHECK(hipStreamCreateWithFlags(&g->lanes[l], hipStreamNonBlocking));
+        for (GLaunch& G : g->launches) if (G.record_after) HIP_CHECK(hipEventCreateWithFlags(&G.ev, hipEventDisableTiming));
+        for (hipEvent_t* e : {&g->ev_fork, &g->ev_in, &g->ev_done}) HIP_CHECK(hipEventCreateWithFlags(e, hipEventDisableTiming));
+        for (int l = 1; l < FQL_LANES; ++l) HIP_CHECK(hipEventCreateWithFlags(&g->ev_join[l], hipEventDisableTiming));
+        HIP_CHECK(hipMalloc((void**)&g->d_idx, (size_t)k * g->B * sizeof(int64_t)));
+        g->capture();
+    } catch (const Invalid& e) {
+        g_create_error = e.msg; g->release(); delete g; return FQL_E_INVALID;
+    } catch (const HipError& e) {
+        g_create_error = e.msg; g->release(); delete g; return FQL_E_HIP;
+    }
+    for (fql_handle h : g->m) { h->group = g; h->grp_done = g->ev_done; h->grp_pending = false; h->grp_touched = true; }
+    *out = g;
+    return FQL_OK;
+}
+
+int fql_group_destroy(fql_group g) {
+    if (!g) return FQL_OK;
+    g->release();
+    delete g;
+    return FQL_OK;
+}
+
+int fql_group_update_from_dataset(fql_group g, const int64_t* idx, int batch_size, float* info13xk, void* stream) {
+    if (!g) { g_create_error = "fql_group_update_from_dataset: NULL group"; return FQL_E_INVALID; }
+    try {
+        if (batch_size != g->B) invalid("fql_group_update_from_dataset: batch_size %d does not match the members' %d", batch_size, g->B);
+        for (int i = 0; i < g->K; ++i)
+            if (g->m[i]->began) { g_create_error = "fql_group_update_from_dataset: a member is between fql_update_begin and fql_update_end"; return FQL_E_STATE; }
+        const hipStream_t s = stream ? (hipStream_t)stream : g->lanes[0];
+        // ordering rule 1: behind everything submitted through a member since the last group update
+        for (fql_handle h : g->m) {
+            if (!h->grp_touched) continue;
+            h->aql_drain();
+            HIP_CHECK(hipEventRecord(g->ev_in, h->stream));
+            HIP_CHECK(hipStreamWaitEvent(s, g->ev_in, 0));
+            h->grp_touched = false;
+        }
+        const int64_t* rows = idx;
+        if (idx && !fql_engine::is_device_ptr(idx)) {
+            HIP_CHECK(hipMemcpyAsync(g->d_idx, idx, (size_t)g->K * g->B * sizeof(int64_t), hipMemcpyHostToDevice, s));
+            HIP_CHECK(hipStreamSynchronize(s));   // (host indices are borrowed for the call only)
+            rows = g->d_idx;
+        }
+        for (int i = 0; i < g->K; ++i) g->m[i]->source_from_dataset(rows ? rows + (size_t)i * g->B : nullptr, g->B, 0, 0, nullptr, s);
+        HIP_CHECK(hipGraphLaunch(g->exec, s));
+        if (info13xk) {
+            for (int i = 0; i < g->K; ++i)
+                HIP_CHECK(hipMemcpyAsync(info13xk + (size_t)i * FQL_NUM_INFO, &g->m[i]->d_state->info[0], FQL_NUM_INFO * sizeof(float), hipMemcpyDefault, s));
+        }
+        HIP_CHECK(hipEventRecord(g->ev_done, s));
+        for (fql_handle h : g->m) { h->grp_pending = true; h->grp_touched = false; }
+        if (info13xk && !fql_engine::is_device_ptr(info13xk)) HIP_CHECK(hipEventSynchronize(g->ev_done));
+    } catch (const Invalid& e) {
+        g_create_error = e.msg; return FQL_E_INVALID;
+    } catch (const HipError& e) {
+        g_create_error = e.msg; return FQL_E_HIP;
+    }
+    return FQL_OK;
+}
+
+int fql_group_synchronize(fql_group g) {
+    if (!g) { g_create_error = "fql_group_synchronize: NULL group"; return FQL_E_INVALID; }
+    if (hipEventSynchronize(g->ev_done) != hipSuccess || hipStreamSynchronize(g->lanes[0]) != hipSuccess) {
+        g_create_error = std::string("fql_group_synchronize: ") + hipGetErrorString(hipGetLastError());
+        return FQL_E_HIP;
+    }
+    for (fql_handle h : g->m) h->grp_pending = false;
+    return FQL_OK;
+}
+
+}  // extern "C"

@@ -1899,7 +1899,14 @@ struct PrepArgs {
 
 // agents/fql.py:52-56 (x_t, vel), :144-150 (noise), utils/datasets.py:64-100 (index draw + gather),
 // utils/networks.py:191,229-231 (concatenate) -- one pass builds every network input of the step.
-__global__ __launch_bounds__(FQL_THREADS) void fql_prep_kernel(PrepArgs P) {
+// Multi-instance entry points read their member's argument struct through the constant address space: scalar loads into SGPRs, as from
+// the kernel-argument segment of the single-instance kernel (same registers, no VGPR copies of the fields)
+#if defined(__HIP_DEVICE_COMPILE__)
+#define FQL_CONST_AS __attribute__((address_space(4)))
+#else
+#define FQL_CONST_AS
+#endif
+__device__ __forceinline__ void fql_prep_body(const PrepArgs& P) {
     tl_enter(P.tl);
     if (P.xsync && blockIdx.x == 0 && P.part != 2)
         for (int i = threadIdx.x; i < 16 * 32; i += FQL_THREADS) P.xsync[i] = 0u;
@@ -1970,6 +1977,9 @@ __global__ __launch_bounds__(FQL_THREADS) void fql_prep_kernel(PrepArgs P) {
         P.w_mask[b] = (second ? S.mask2 : S.mask)[src];
     }
 }
+__global__ __launch_bounds__(FQL_THREADS) void fql_prep_kernel(PrepArgs P) { fql_prep_body(P); }
+// multi-instance entry point (agent groups): blockIdx.y picks the member, its argument struct comes from a device array
+__global__ __launch_bounds__(FQL_THREADS) void fql_prep_multi_kernel(const PrepArgs* __restrict__ args) { const PrepArgs P = ((const FQL_CONST_AS PrepArgs*)args)[blockIdx.y]; fql_prep_body(P); }
 
 // ------------------------------------------------------------------------------------------------
 // single-workgroup loss / bookkeeping kernels (B <= a few thousand rows: latency, not bandwidth)
@@ -2141,6 +2151,12 @@ __global__ __launch_bounds__(FQL_THREADS) void fql_loss_critic_kernel(LossCritic
 __global__ __launch_bounds__(FQL_THREADS) void fql_loss_q_kernel(LossQArgs P) { __shared__ float sh[4]; fql_loss_q_body(P, sh); }
 __global__ __launch_bounds__(FQL_THREADS) void fql_loss_bc_kernel(LossBcArgs P) { __shared__ float sh[4]; fql_loss_bc_body(P, sh); }
 __global__ __launch_bounds__(FQL_THREADS) void fql_loss_actor_kernel(LossActorArgs P) { __shared__ float sh[4]; fql_loss_actor_body(P, sh); }
+// multi-instance entry point (agent groups): blockIdx.y picks the member, its argument struct comes from a device array
+__global__ __launch_bounds__(FQL_THREADS) void fql_post_onestep_multi_kernel(const PostOsArgs* __restrict__ args) { __shared__ float sh[4]; const PostOsArgs P = args[blockIdx.y]; fql_post_onestep_body(P, sh); }
+__global__ __launch_bounds__(FQL_THREADS) void fql_loss_critic_multi_kernel(const LossCriticArgs* __restrict__ args) { __shared__ float sh[4]; const LossCriticArgs P = args[blockIdx.y]; fql_loss_critic_body(P, sh); }
+__global__ __launch_bounds__(FQL_THREADS) void fql_loss_q_multi_kernel(const LossQArgs* __restrict__ args) { __shared__ float sh[4]; const LossQArgs P = args[blockIdx.y]; fql_loss_q_body(P, sh); }
+__global__ __launch_bounds__(FQL_THREADS) void fql_loss_bc_multi_kernel(const LossBcArgs* __restrict__ args) { __shared__ float sh[4]; const LossBcArgs P = args[blockIdx.y]; fql_loss_bc_body(P, sh); }
+__global__ __launch_bounds__(FQL_THREADS) void fql_loss_actor_multi_kernel(const LossActorArgs* __restrict__ args) { __shared__ float sh[4]; const LossActorArgs P = args[blockIdx.y]; fql_loss_actor_body(P, sh); }
 
 // single-workgroup loss / metric tasks that ride in a side-lane launch
 enum : int { MISC_POSTOS = 0, MISC_LOSS_CRITIC, MISC_LOSS_Q, MISC_LOSS_BC };
@@ -2178,7 +2194,7 @@ __device__ __forceinline__ int f2ord(float f) {
 }
 __device__ __forceinline__ float ord2f(int i) { return __int_as_float(i >= 0 ? i : i ^ 0x7FFFFFFF); }
 
-__global__ __launch_bounds__(FQL_THREADS) void fql_adam_kernel(AdamArgs A) {
+__device__ __forceinline__ void fql_adam_body(const AdamArgs& A) {
     __shared__ float sh[4];
     tl_enter(A.tl);
     if (A.err && __hip_atomic_load(A.err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) return;   // (null unless FQL_PEC=1)
@@ -2228,6 +2244,9 @@ __global__ __launch_bounds__(FQL_THREADS) void fql_adam_kernel(AdamArgs A) {
     }
     tl_exit(A.tl);
 }
+__global__ __launch_bounds__(FQL_THREADS) void fql_adam_kernel(AdamArgs A) { fql_adam_body(A); }
+// multi-instance entry point (agent groups): blockIdx.y picks the member, its argument struct comes from a device array
+__global__ __launch_bounds__(FQL_THREADS) void fql_adam_multi_kernel(const AdamArgs* __restrict__ args) { const AdamArgs A = ((const FQL_CONST_AS AdamArgs*)args)[blockIdx.y]; fql_adam_body(A); }
 
 struct FinalizeArgs {
     DevState* st;
@@ -2239,7 +2258,7 @@ struct FinalizeArgs {
 };
 // grad/max, grad/min, grad/norm = sum over leaves of ||g_leaf||_2 (utils/flax_utils.py:139-157); target-critic leaves
 // contribute zeros, which bound grad/max >= 0 >= grad/min (F5).  Also advances optax count / TrainState.step / RNG step.
-__global__ __launch_bounds__(FQL_THREADS) void fql_finalize_kernel(FinalizeArgs A) {
+__device__ __forceinline__ void fql_finalize_body(const FinalizeArgs& A) {
     __shared__ float sh[4];
     __shared__ float leafn[256];
     DevState* st = A.st;
@@ -2279,6 +2298,9 @@ __global__ __launch_bounds__(FQL_THREADS) void fql_finalize_kernel(FinalizeArgs 
         st->b2pow *= 0.999;
     }
 }
+__global__ __launch_bounds__(FQL_THREADS) void fql_finalize_kernel(FinalizeArgs A) { fql_finalize_body(A); }
+// multi-instance entry point (agent groups): blockIdx.y picks the member, its argument struct comes from a device array
+__global__ __launch_bounds__(FQL_THREADS) void fql_finalize_multi_kernel(const FinalizeArgs* __restrict__ args) { const FinalizeArgs A = args[blockIdx.y]; fql_finalize_body(A); }
 
 // fused Euler chain, last step: target = clip(a_{n-1} + (sum of head partials + bias) / flow_steps)  (agents/fql.py:169-170)
 struct EulerFinishArgs {
@@ -2289,7 +2311,7 @@ struct EulerFinishArgs {
     int M, ad, ap, ntp, a_ld;
     float scale;
 };
-__global__ __launch_bounds__(FQL_THREADS) void fql_euler_finish_kernel(EulerFinishArgs P) {
+__device__ __forceinline__ void fql_euler_finish_body(const EulerFinishArgs& P) {
     const int e = blockIdx.x * FQL_THREADS + threadIdx.x;
     if (e >= P.M * P.ad) return;
     const int r = sdiv(e, frcp(P.ad)), j = e - r * P.ad;
@@ -2301,6 +2323,9 @@ __global__ __launch_bounds__(FQL_THREADS) void fql_euler_finish_kernel(EulerFini
     for (int tp = 0; tp < 32; ++tp) sum += (tp < P.ntp) ? pv[tp] : 0.f;
     stg(P.tgt + (size_t)r * P.ap + j, clip1(ldg(P.a_in + (size_t)r * P.a_ld + j) + (sum + ldg(P.eb + j)) * P.scale));
 }
+__global__ __launch_bounds__(FQL_THREADS) void fql_euler_finish_kernel(EulerFinishArgs P) { fql_euler_finish_body(P); }
+// multi-instance entry point (agent groups): blockIdx.y picks the member, its argument struct comes from a device array
+__global__ __launch_bounds__(FQL_THREADS) void fql_euler_finish_multi_kernel(const EulerFinishArgs* __restrict__ args) { const EulerFinishArgs P = args[blockIdx.y]; fql_euler_finish_body(P); }
 
 // ------------------------------------------------------------------------------------------------
 // Persistent Euler chain (agents/fql.py:155-171): the whole 10-step x (layers 0..3 + head) chain in ONE launch.

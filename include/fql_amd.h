@@ -52,6 +52,7 @@ extern "C" {
 #define FQL_NUM_INFO 13
 
 typedef struct fql_engine* fql_handle;
+typedef struct fql_group_s* fql_group;
 
 /* agents/fql.py:249-270 get_config() -- same keys, same defaults (see fql_default_config). */
 typedef struct fql_config {
@@ -261,6 +262,32 @@ int fql_synchronize(fql_handle h, int* mode);
  * out.  A ticket expires (FQL_E_STATE) once 64 later tickets have been taken. */
 int fql_info_enqueue(fql_handle h, void* stream, uint64_t* ticket);
 int fql_info_wait(fql_handle h, uint64_t ticket, float* info13_host);
+
+/* ---- agent groups: K agents of one structure trained side by side (seed / alpha sweeps, README "Tips for hyperparameter tuning") ----
+ * A group advances its members with ONE fused update program: every launch of a member's update carries the tasks of all K members
+ * (concatenated task tables, or blockIdx.y = member), captured as one graph with a single agent's lanes.  Each task keeps its arguments
+ * and tile shapes, so a member's trajectory is bitwise the one it has alone (same seed, alpha, rows and noise).  Members stay ordinary
+ * handles: every entry point above works on them.  Errors of the fql_group_* calls are reported by fql_last_error(NULL).
+ *
+ * fql_group_create: `members` [k], k >= 1, distinct, in no other group.  Members are state agents (encoder 0) with precision 0, the same
+ * config except alpha (and the create seed), the same batch size, and structurally identical update programs (launch count, kernels,
+ * grids, lanes, waits); the persistent Euler-chain variants (FQL_PEC / FQL_XCHAIN) are not groupable.  Anything else: FQL_E_INVALID.
+ * Out of scope and refused: visual or bf16x3 members, members that differ in anything but seed and alpha.  Data-parallel halves,
+ * balanced sampling, replay rings and the engine's own queues (stream = NULL updates of a single agent) are not group paths.
+ * While a handle belongs to a group, fql_set_batch_size and fql_destroy on it return FQL_E_STATE. */
+int fql_group_create(const fql_handle* members, int k, fql_group* out);
+/* Waits for the group's last update and releases the members (they are plain handles again; nothing is freed of them). */
+int fql_group_destroy(fql_group g);
+/* fql_update_from_dataset of every member in one fused update: member i samples its rows from ITS OWN uploaded dataset, idx + i * B
+ * ([k][B] int64, device or host) or NULL = each member's device RNG; the noise always comes from each member's device RNG.
+ * info13xk: [k][13] (device or host; host = synchronous) or NULL.  `stream` as elsewhere: NULL = the group's own stream.
+ * Ordering: (1) the update is ordered after all work submitted earlier through any member: a member's queued engine-queue updates are
+ * drained and the group's stream waits for the member's stream (work the caller enqueued on streams of its own is the caller's to order).
+ * (2) every member entry point called afterwards sees this update's results without an explicit synchronise (fql_get_param /
+ * fql_set_param included): it waits for the group's update first (fql_info_enqueue: a stream dependency, no host wait). */
+int fql_group_update_from_dataset(fql_group g, const int64_t* idx, int batch_size, float* info13xk, void* stream);
+/* Host wait for the group's last update. */
+int fql_group_synchronize(fql_group g);
 
 /* Introspection for tests / bench: per-update kernel-launch count, algorithmic MAC count per update
  * (SURVEY.md section 8d figure), and the engine's HIP stream. */
