@@ -14,6 +14,7 @@ LIB_PATH = os.environ.get('FQL_AMD_LIB') or os.path.join(_HERE, 'libfql_amd.so')
 FQL_MAX_HIDDEN = 8
 FQL_STREAM_LEGACY = 1   # (void*)1 == hipStreamLegacy: the legacy default stream (torch's default stream)
 FQL_NUM_INFO = 13
+FQL_IFQL_NUM_INFO = 12
 FQL_OK, FQL_E_INVALID, FQL_E_NODEVICE, FQL_E_HIP, FQL_E_STATE, FQL_E_NOTFOUND = 0, -1, -2, -3, -4, -5
 
 
@@ -28,6 +29,10 @@ class FqlConfig(C.Structure):
         ('batch_size', C.c_int32), ('precision', C.c_int32), ('encoder', C.c_int32), ('img_h', C.c_int32),
         ('img_w', C.c_int32), ('img_c', C.c_int32), ('reserved', C.c_int32 * 3),
     ]
+
+
+class FqlIfqlConfig(C.Structure):
+    _fields_ = [('expectile', C.c_float), ('num_samples', C.c_int32), ('reserved', C.c_int32 * 6)]
 
 
 class FqlNoise(C.Structure):
@@ -91,6 +96,10 @@ SYMBOLS = {
     'fql_group_destroy': (_I, [_VP]),
     'fql_group_update_from_dataset': (_I, [_VP, _VP, _I, _VP, _VP]),
     'fql_group_synchronize': (_I, [_VP]),
+    'fql_ifql_default_config': (None, [C.POINTER(FqlIfqlConfig)]),
+    'fql_ifql_create': (_I, [C.POINTER(FqlConfig), C.POINTER(FqlIfqlConfig), _U64, C.POINTER(_VP)]),
+    'fql_num_info': (_I, [_VP]),
+    'fql_handle_info_name': (C.c_char_p, [_VP, _I]),
 }
 
 _lib = None

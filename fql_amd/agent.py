@@ -140,9 +140,10 @@ class LazyInfo(dict):
     default=float)); pickling and copy() give a plain dict of floats.  Holding it across more than 64 later lazy updates without reading it
     raises on first use (the engine keeps 64 snapshots)."""
 
-    def __init__(self, agent, ticket):
+    def __init__(self, agent, ticket, keys=None):
         p = _Pending(agent, ticket)
-        super().__init__((k, LazyScalar(p, i)) for i, k in enumerate(INFO_KEYS))
+        keys = keys if keys is not None else getattr(agent, '_info_keys', INFO_KEYS)
+        super().__init__((k, LazyScalar(p, i)) for i, k in enumerate(keys))
 
     def to_dict(self):
         return {k: float(v) for k, v in self.items()}
@@ -157,9 +158,14 @@ class LazyInfo(dict):
 class FQLAgent:
     """Flow Q-learning agent backed by the MI355X step engine."""
 
+    _loss_infos = 10          # infos fql_total_loss writes (the total-loss probe has no gradient statistics)
+    _jax_sample_noise = True  # sample_actions(seed=<JAX key>) draws the reference's noise on the host
+
     def __init__(self, handle, config, seed):
         self._lib = _cabi.load()
         self._h = handle
+        # the info keys of this handle's updates, in order (fql_handle_info_name)
+        self._info_keys = tuple(self._lib.fql_handle_info_name(handle, i).decode() for i in range(self._lib.fql_num_info(handle)))
         self.config = config
         self._seed = seed
         self._keep = []
@@ -175,6 +181,17 @@ class FQLAgent:
         lib = _cabi.load()
         cfg = get_config()
         cfg.update(dict(config))
+        c, ob_dims, action_dim = cls._engine_config(lib, cfg, ex_observations, ex_actions)
+        h = C.c_void_p()
+        rc = lib.fql_create(C.byref(c), int(seed) & 0xFFFFFFFFFFFFFFFF, C.byref(h))
+        _cabi.check(lib, None, rc)
+        cfg['ob_dims'] = ob_dims
+        cfg['action_dim'] = action_dim
+        return cls(h, cfg, int(seed))
+
+    @staticmethod
+    def _engine_config(lib, cfg, ex_observations, ex_actions):
+        """(fql_config, ob_dims, action_dim) for the networks `cfg` describes."""
         ex_observations = np.asarray(ex_observations) if not hasattr(ex_observations, 'shape') else ex_observations
         ob_dims = tuple(int(d) for d in ex_observations.shape[1:])
         action_dim = int(ex_actions.shape[-1])
@@ -202,23 +219,20 @@ class FQLAgent:
         for i, v in enumerate(vh):
             c.value_hidden[i] = int(v)
         c.layer_norm, c.actor_layer_norm = int(bool(cfg['layer_norm'])), int(bool(cfg['actor_layer_norm']))
-        c.lr, c.discount, c.tau, c.alpha = float(cfg['lr']), float(cfg['discount']), float(cfg['tau']), float(cfg['alpha'])
-        if cfg['q_agg'] not in ('mean', 'min'):
-            raise ValueError(f"q_agg must be 'mean' or 'min', got {cfg['q_agg']!r}")
-        c.q_agg = 1 if cfg['q_agg'] == 'min' else 0
+        c.lr, c.discount, c.tau = float(cfg['lr']), float(cfg['discount']), float(cfg['tau'])
+        c.alpha = float(cfg.get('alpha', c.alpha))
+        q_agg = cfg.get('q_agg', 'mean')
+        if q_agg not in ('mean', 'min'):
+            raise ValueError(f"q_agg must be 'mean' or 'min', got {q_agg!r}")
+        c.q_agg = 1 if q_agg == 'min' else 0
         c.flow_steps = int(cfg['flow_steps'])
-        c.normalize_q_loss = int(bool(cfg['normalize_q_loss']))
+        c.normalize_q_loss = int(bool(cfg.get('normalize_q_loss', False)))
         c.batch_size = int(cfg['batch_size'])
         prec = cfg.get('precision', 'fp32')
         if prec not in ('fp32', 'bf16x3', 0, 2):
             raise ValueError(f"precision must be 'fp32' or 'bf16x3', got {prec!r}")
         c.precision = 2 if prec in ('bf16x3', 2) else 0
-        h = C.c_void_p()
-        rc = lib.fql_create(C.byref(c), int(seed) & 0xFFFFFFFFFFFFFFFF, C.byref(h))
-        _cabi.check(lib, None, rc)
-        cfg['ob_dims'] = ob_dims
-        cfg['action_dim'] = action_dim
-        return cls(h, cfg, int(seed))
+        return c, ob_dims, action_dim
 
     def close(self):
         if getattr(self, '_h', None):
@@ -350,7 +364,7 @@ class FQLAgent:
         """The 13 info scalars of the last update (blocks until that update has run)."""
         buf = (C.c_float * _cabi.FQL_NUM_INFO)()
         self._check(self._lib.fql_read_info(self._h, buf))
-        return {k: float(buf[i]) for i, k in enumerate(INFO_KEYS)}
+        return {k: float(buf[i]) for i, k in enumerate(self._info_keys)}
 
     def synchronize(self) -> str:
         """Host wait for every update enqueued so far (jax.block_until_ready(agent)): the engine's HIP stream and the hardware queues of
@@ -375,7 +389,7 @@ class FQLAgent:
         stream = self._stream(args + nargs)
         self._check(self._lib.fql_total_loss(self._h, *[a.ptr for a in args], B, C.byref(nz) if nz else None,
                                              C.byref(loss), info, stream))
-        return float(loss.value), {k: float(info[i]) for i, k in enumerate(INFO_KEYS[:10])}
+        return float(loss.value), {k: float(info[i]) for i, k in enumerate(self._info_keys[:self._loss_infos])}
 
     def sample_actions(self, observations, seed=None, temperature=1.0, noises=None):
         """agents/fql.py:135-153: clip(onestep(obs, N(0, I))).  `temperature` is accepted and ignored,
@@ -386,6 +400,9 @@ class FQLAgent:
         """agents/fql.py:155-171."""
         return self._eval(observations, noises, None, flow=True)
 
+    def _sample_noise_shape(self, n, flow):
+        return (n, self.config['action_dim'])
+
     def _eval(self, observations, noises, seed, flow):
         obd, ad = tuple(self.config['ob_dims']), self.config['action_dim']
         vis = len(obd) == 3
@@ -394,14 +411,14 @@ class FQLAgent:
         if vis and tuple(observations.shape[-3:]) != obd:
             raise ValueError(f'observations must end in {obd}, got {tuple(observations.shape)}')
         lead = tuple(observations.shape[:-3]) if vis else tuple(observations.shape[:-1])
-        if not flow and noises is None and seed is not None and np.ndim(seed) == 1 and np.size(seed) == 2:
+        if self._jax_sample_noise and not flow and noises is None and seed is not None and np.ndim(seed) == 1 and np.size(seed) == 2:
             # a JAX key (what main.py:225 / utils/evaluation.py:98-101 pass): draw exactly the noise the reference draws
             noises = jax_prng.sample_actions_noise(np.asarray(seed), lead, ad, partitionable=bool(self._jax_mode()))
         if not vis and int(observations.shape[-1]) != od:
             raise ValueError(f'observations last dim must be {od}, got {tuple(observations.shape)}')
         n = int(np.prod(lead)) if lead else 1
         o = _Arg(observations, (n,) + obd, u8=vis)
-        z = _Arg(noises, (n, ad))
+        z = _Arg(noises, self._sample_noise_shape(n, flow))
         if is_torch and observations.is_cuda:
             torch = _torch()
             out = torch.empty(lead + (ad,), dtype=torch.float32, device=observations.device)

@@ -15,6 +15,7 @@
 #include "fql_chain.h"
 #include "fql_aux.h"
 #include "fql_xchain.h"
+#include "fql_ifql.h"
 #include <hip/hip_ext.h>
 #include "fql_aql.h"
 
@@ -125,7 +126,9 @@ struct Leaf {
 // ------------------------------------------------------------------------------------------------
 enum OpType { OP_GEMM, OP_GEMM64, OP_WGRAD, OP_LNBWD, OP_PREP, OP_POSTOS, OP_EULER_FIN, OP_PEC, OP_LOSS_CRITIC, OP_LOSS_Q, OP_LOSS_BC,
               OP_LOSS_ACTOR, OP_CONV_WPREP, OP_CONV, OP_CONV_U8, OP_POOL, OP_POOL_BWD, OP_CONV_WGRAD, OP_CONV_WRED, OP_ENC_DZ, OP_CHAIN, OP_WFRAG, OP_XCHAIN, OP_HEAD_DGRAD, OP_DGRAD0, OP_ADAM,
-              OP_FINALIZE };
+              OP_FINALIZE,
+              // IFQL (agents/ifql.py) only: after every FQL type, so FQL programs keep their launch order
+              OP_IFQL_PREP, OP_IFQL_LOSS_V, OP_IFQL_LOSS_C, OP_IFQL_FIN, OP_NUM_TYPES };
 
 struct Op {
     OpType type;
@@ -147,6 +150,9 @@ struct Op {
     ConvWgradArgs cw;
     ConvWredArgs cwr;
     EncDzArgs edz;
+    IfqlPrepArgs iprep;
+    IfqlValueArgs iv;
+    IfqlCriticArgs ic;
     ChainArgs chain;
     XChainArgs xchain;
     const ConvWprepTask* wprep_tasks = nullptr;
@@ -238,6 +244,13 @@ struct EncBuf {
 struct fql_group_s;
 struct fql_engine {
     fql_config cfg{};
+    // IFQL agent (agents/ifql.py; fql_ifql_create): the arena's NET_OS slot holds the value net (obs -> 1, LayerNorm like the critic),
+    // NET_BC is actor_flow; critic, target and their place in the arena are FQL's.  The update is build_ifql_program.
+    bool ifql = false;
+    float expectile = 0.9f;
+    int num_samples = 32;
+    float* X_v = nullptr;   // [2B, value in_p]: [obs ; next_obs]
+    PassBuf p_v;            // value pass over X_v (backward over the obs half only)
     uint64_t seed = 0;
     int device = 0;
     hipStream_t stream = nullptr, stream2 = nullptr, stream3 = nullptr, stream4 = nullptr;
@@ -352,6 +365,10 @@ struct fql_engine {
         unsigned char* st_img = nullptr;
         EncBuf eb_os, eb_bc;
         Program prog_enc_os, prog_enc_bc;
+        // IFQL best-of-N: the critic pair on [obs | clip(flow action)] of every sample row
+        float* Xq = nullptr;
+        PassBuf p_q[2];
+        Program prog_q;
     };
     std::map<int, std::unique_ptr<Eval>> evals;
 
@@ -413,7 +430,8 @@ struct fql_engine {
         nets[NET_C0] = make(od + ad, cfg.value_hidden, cfg.num_value_hidden, 1, cfg.layer_norm != 0);
         nets[NET_C1] = nets[NET_C0];
         nets[NET_BC] = make(od + ad + 1, cfg.actor_hidden, cfg.num_actor_hidden, ad, cfg.actor_layer_norm != 0);
-        nets[NET_OS] = make(od + ad, cfg.actor_hidden, cfg.num_actor_hidden, ad, cfg.actor_layer_norm != 0);
+        nets[NET_OS] = ifql ? make(od, cfg.value_hidden, cfg.num_value_hidden, 1, cfg.layer_norm != 0)   // value (agents/ifql.py:188-193)
+                            : make(od + ad, cfg.actor_hidden, cfg.num_actor_hidden, ad, cfg.actor_layer_norm != 0);
         nets[NET_T0] = nets[NET_C0];
         nets[NET_T1] = nets[NET_C0];
         size_t off = 0;
@@ -517,7 +535,7 @@ struct fql_engine {
         const Net& n = nets[NET_BC];
         const int nh = n.nl() - 1;
         const int H = n.layers[0].out_p;
-        bool ok = !cfg.actor_layer_norm && cfg.act_dim <= 15 && nh >= 3 && (H == 256 || H == 512);
+        bool ok = !ifql && !cfg.actor_layer_norm && cfg.act_dim <= 15 && nh >= 3 && (H == 256 || H == 512);   // (IFQL has no Euler chain in its update)
         for (int l = 0; l < nh && ok; ++l) ok = n.layers[l].out == H && n.layers[l].out_p == H;
         use_chain = ok;
         if (!ok) return;
@@ -551,12 +569,19 @@ struct fql_engine {
     void build_leaves() {
         leaves.clear();
         struct Mod { const char* name; const char* sub; int n0, n1; bool train; int enc; };
-        const Mod mods[4] = {{"modules_actor_bc_flow", "mlp", NET_BC, -1, true, ENC_BC},
-                             {"modules_actor_onestep_flow", "mlp", NET_OS, -1, true, ENC_OS},
-                             {"modules_critic", "value_net", NET_C0, NET_C1, true, ENC_C},
-                             {"modules_target_critic", "value_net", NET_T0, NET_T1, false, ENC_T}};
+        const Mod fql_mods[4] = {{"modules_actor_bc_flow", "mlp", NET_BC, -1, true, ENC_BC},
+                                 {"modules_actor_onestep_flow", "mlp", NET_OS, -1, true, ENC_OS},
+                                 {"modules_critic", "value_net", NET_C0, NET_C1, true, ENC_C},
+                                 {"modules_target_critic", "value_net", NET_T0, NET_T1, false, ENC_T}};
+        // IFQL (agents/ifql.py:215-225): the value net is a 1-member Value, so its leaves are unstacked
+        const Mod ifql_mods[4] = {{"modules_actor_flow", "mlp", NET_BC, -1, true, ENC_BC},
+                                  {"modules_critic", "value_net", NET_C0, NET_C1, true, ENC_C},
+                                  {"modules_target_critic", "value_net", NET_T0, NET_T1, false, ENC_T},
+                                  {"modules_value", "value_net", NET_OS, -1, true, ENC_OS}};
+        const Mod* mods = ifql ? ifql_mods : fql_mods;
         int tid = 0;
-        for (const Mod& m : mods) {
+        for (int mi = 0; mi < 4; ++mi) {
+            const Mod& m = mods[mi];
             const Net& n0 = nets[m.n0];
             const bool ens = m.n1 >= 0;
             if (visual) {
@@ -634,7 +659,9 @@ struct fql_engine {
         for (const AdamChunk& c : ch) range[c.leaf + 1]++;
         for (int i = 0; i < n_train_leaves; ++i) range[i + 1] += range[i];
         {   // leaves (and so chunks) are ordered module by module: actor_bc_flow, actor_onestep_flow, critic
-            const char* mods[3] = {"modules_actor_bc_flow/", "modules_actor_onestep_flow/", "modules_critic/"};
+            const char* fmods[3] = {"modules_actor_bc_flow/", "modules_actor_onestep_flow/", "modules_critic/"};
+            const char* imods[3] = {"modules_actor_flow/", "modules_value/", "modules_critic/"};
+            const char* const* mods = ifql ? imods : fmods;
             for (int m = 0; m < 3; ++m) {
                 int lo = 1 << 30, hi = -1;
                 for (const Leaf& lf : leaves)
@@ -1479,7 +1506,7 @@ struct fql_engine {
         std::vector<int> launch_of(pr.ops.size(), -1);
         for (int lv = 0; lv <= maxlv; ++lv) {
           for (int lane = 0; lane < FQL_LANES; ++lane) {
-            for (int ty = 0; ty <= OP_FINALIZE; ++ty) {
+            for (int ty = 0; ty < OP_NUM_TYPES; ++ty) {
                 std::vector<const Op*> sel;
                 for (int oi = 0; oi < (int)pr.ops.size(); ++oi) {
                     const Op& op = pr.ops[oi];
@@ -2063,6 +2090,21 @@ struct fql_engine {
             case OP_FINALIZE:
                 FQL_LAUNCH(fql_finalize_kernel, dim3(1), dim3(FQL_THREADS), 0, s,
                                    FinalizeArgs{d_state, d_chunks, d_partials, d_leaf_range, n_chunks, n_train_leaves, L.op.fin_mode, tl});
+                break;
+            case OP_IFQL_PREP:
+                FQL_LAUNCH(fql_ifql_prep_kernel, dim3((L.op.iprep.B + 3) / 4), dim3(FQL_THREADS), 0, s, L.op.iprep);
+                break;
+            case OP_IFQL_LOSS_V:
+                FQL_LAUNCH(fql_ifql_loss_value_kernel, dim3(1), dim3(FQL_THREADS), 0, s, L.op.iv);
+                break;
+            case OP_IFQL_LOSS_C:
+                FQL_LAUNCH(fql_ifql_loss_critic_kernel, dim3(1), dim3(FQL_THREADS), 0, s, L.op.ic);
+                break;
+            case OP_IFQL_FIN:
+                FQL_LAUNCH(fql_ifql_finalize_kernel, dim3(1), dim3(FQL_THREADS), 0, s,
+                                   FinalizeArgs{d_state, d_chunks, d_partials, d_leaf_range, n_chunks, n_train_leaves, L.op.fin_mode, tl});
+                break;
+            case OP_NUM_TYPES:
                 break;
         }
     }
@@ -2816,10 +2858,114 @@ struct fql_engine {
         push(pr, f);
     }
 
+    // ---------------------------------------------------------------------------------------
+    // the IFQL update as a program (agents/ifql.py:79-120).  No Euler chain: every level is throughput work on the side lanes.
+    //   lane 0: batch assembly; Adam + Polyak over every chunk and the finalize, behind both side lanes
+    //   lane 1: value on [obs ; next_obs] (2B rows) -> target pair -> value loss -> value backward (obs half); actor_flow forward, BC loss, backward
+    //   lane 2: critic pair forward -> critic loss (waits for value(next_obs) on lane 1) -> critic backward (parameter gradients only)
+    // Edges between the forked lanes run 1 -> 2 only (see schedule()).
+    // ---------------------------------------------------------------------------------------
+    void build_ifql_program(Program& pr, bool with_grads) {
+        const int od = cfg.obs_dim, ad = cfg.act_dim, ap = pad16(ad);
+        DevState* st = d_state;
+        const void *I_V = &st->info[IFQL_I_VALUE], *I_C = &st->info[IFQL_I_CRITIC], *I_A = &st->info[IFQL_I_ACTOR];
+        wide_tiles = true;
+        allow64 = true;
+        emit_lane = 0;
+        {
+            Op op{};
+            op.type = OP_IFQL_PREP;
+            op.iprep = IfqlPrepArgs{d_src, st, seed, B, od, ad, nets[NET_OS].in_p(), nets[NET_C0].in_p(), nets[NET_BC].in_p(), ap,
+                                    X_v, X_c1, X_bc, vel, w_rew, w_mask};
+            op.writes = {X_v, X_c1, X_bc, vel, w_rew, w_mask};
+            push(pr, op);
+        }
+        emit_lane = 1;
+        emit_forward(pr, p_v, with_grads);                        // value(obs) ifql.py:34, value(next_obs) ifql.py:47
+        for (int e = 0; e < 2; ++e) emit_forward(pr, p_ct[e], false);   // target_critic(obs, actions) ifql.py:33
+        {
+            Op op{};
+            op.type = OP_IFQL_LOSS_V;
+            op.iv = IfqlValueArgs{p_v.out, p_ct[0].out, p_ct[1].out, with_grads ? p_v.dz.back() : nullptr, st, B, expectile};
+            op.reads = {p_v.out, p_ct[0].out, p_ct[1].out};
+            op.writes = {I_V};
+            if (with_grads) op.writes.push_back(p_v.dz.back());
+            push(pr, op);
+        }
+        if (with_grads) emit_backward(pr, p_v, 0, B, true, false);
+        emit_forward(pr, p_bc, with_grads);                       // actor_flow(obs, x_t, t) ifql.py:71
+        {
+            Op op{};
+            op.type = OP_LOSS_BC;
+            op.lb = LossBcArgs{p_bc.out, vel, with_grads ? p_bc.dz.back() : nullptr, st, B, ad, ap, with_grads ? 1 : 0};
+            op.reads = {p_bc.out, vel};
+            op.writes = {I_A};
+            if (with_grads) op.writes.push_back(p_bc.dz.back());
+            push(pr, op);
+        }
+        if (with_grads) emit_backward(pr, p_bc, 0, B, true, false);
+        emit_lane = 2;
+        for (int e = 0; e < 2; ++e) emit_forward(pr, p_c1[e], with_grads);   // critic(obs, actions) ifql.py:50
+        {
+            Op op{};
+            op.type = OP_IFQL_LOSS_C;
+            op.ic = IfqlCriticArgs{p_v.out + (size_t)B * nets[NET_OS].layers.back().out_p, p_c1[0].out, p_c1[1].out, w_rew, w_mask,
+                                   with_grads ? p_c1[0].dz.back() : nullptr, with_grads ? p_c1[1].dz.back() : nullptr, st, B, cfg.discount};
+            op.reads = {p_v.out, p_c1[0].out, p_c1[1].out, w_rew, w_mask};
+            op.writes = {I_C};
+            if (with_grads) { op.writes.push_back(p_c1[0].dz.back()); op.writes.push_back(p_c1[1].dz.back()); }
+            push(pr, op);
+        }
+        if (with_grads)
+            for (int e = 0; e < 2; ++e) emit_backward(pr, p_c1[e], 0, B, true, false);
+        if (with_grads) adam_for(pr, 2, {NET_C0, NET_C1, NET_BC, NET_OS}, 0, -2);   // every chunk, one launch; Polyak from the pre-step critic
+        Op f{};
+        f.type = OP_IFQL_FIN;
+        f.fin_mode = with_grads ? 1 : 0;
+        f.reads = {I_V, I_C, I_A};
+        if (with_grads) for (int m = 0; m < 3; ++m) f.reads.push_back(d_partials + mod_chunk0[m] * 4);
+        f.writes = {&st->info[8], st};
+        emit_lane = 0;
+        push(pr, f);
+    }
+
+    void build_ifql_workspace() {
+        const int ap = pad16(cfg.act_dim);
+        auto& W = ws_allocs;
+        X_v = dalloc(W, (size_t)2 * B * nets[NET_OS].in_p());
+        X_c1 = dalloc(W, (size_t)B * nets[NET_C0].in_p());
+        X_bc = dalloc(W, (size_t)B * nets[NET_BC].in_p());
+        vel = dalloc(W, (size_t)B * ap);
+        w_rew = dalloc(W, B); w_mask = dalloc(W, B);
+        X_os = X_eu = X_c2 = X_ct = X_e0 = C0 = Vpart = w_act = tgt = nullptr;
+        fused_euler = use_pec = use_xchain = euler_finish_fused = false;
+        p_v = make_pass(W, NET_OS, 2 * B, X_v, true, false);
+        p_bc = make_pass(W, NET_BC, B, X_bc, true, false);
+        for (int e = 0; e < 2; ++e) {
+            p_c1[e] = make_pass(W, NET_C0 + e, B, X_c1, true, false);
+            p_ct[e] = make_pass(W, NET_T0 + e, B, X_c1, false, false);
+        }
+        build_ifql_program(prog_full, true);
+        build_ifql_program(prog_loss, false);
+        schedule(prog_full, W);
+        schedule(prog_loss, W);
+        capture(prog_full);
+        capture(prog_loss);
+        aql_tried = false;
+        split_ok = false;
+        launches_per_update = (int64_t)prog_full.launches.size();
+        src_valid = false;
+    }
+
     int64_t macs_per_update() const {
         auto macs = [&](const Net& n) { int64_t m = 0; for (const Layer& L : n.layers) m += (int64_t)L.in * L.out; return m; };
         auto first = [&](const Net& n) { return (int64_t)n.layers[0].in * n.layers[0].out; };
         const int64_t os = macs(nets[NET_OS]), bc = macs(nets[NET_BC]), cr = macs(nets[NET_C0]);
+        if (ifql) {   // value on 2B rows + its backward on B; target pair; critic pair forward + backward (no input gradient); actor_flow forward + backward
+            const int64_t fwd = 2 * os + 4 * cr + bc;
+            const int64_t bwd = (2 * os - first(nets[NET_OS])) + 2 * (2 * cr - first(nets[NET_C0])) + (2 * bc - first(nets[NET_BC]));
+            return (fwd + bwd) * (int64_t)B;
+        }
         const int64_t fwd = 3 * os + (cfg.flow_steps + 1) * bc + 6 * cr;
         const int64_t bwd = 2 * (2 * cr - first(nets[NET_C0])) + (2 * bc - first(nets[NET_BC])) + (2 * os - first(nets[NET_OS])) + 2 * cr;
         int64_t total = (fwd + bwd) * (int64_t)B;
@@ -2871,6 +3017,7 @@ struct fql_engine {
         in_act = dalloc(W, (size_t)B * ad); in_rew = dalloc(W, B); in_mask = dalloc(W, B);
         for (int i = 0; i < 5; ++i) in_noise[i] = dalloc(W, (size_t)B * ad);
         in_idx = (int64_t*)dalloc(W, (size_t)B * 4);   // [2][B]: indices in use, staging of host indices (frames path)
+        if (ifql) { build_ifql_workspace(); return; }
         X_os = dalloc(W, (size_t)3 * B * inp_c); X_bc = dalloc(W, (size_t)B * inp_b); X_eu = dalloc(W, (size_t)B * inp_b);
         X_c1 = dalloc(W, (size_t)B * inp_c); X_c2 = dalloc(W, (size_t)B * inp_c); X_ct = dalloc(W, (size_t)B * inp_c);
         const int ap = pad16(ad);
@@ -3062,6 +3209,7 @@ struct fql_engine {
     void fill_noise(SrcDesc& d, const fql_noise* nz, hipStream_t s) {
         const int ad = cfg.act_dim;
         if (!nz) return;
+        if (ifql && (nz->eps1 || nz->z || nz->eps2)) invalid("IFQL reads only x0 and t of fql_noise (eps1, z and eps2 must be NULL)");
         d.eps1 = stage(nz->eps1, in_noise[0], (size_t)B * ad, s);
         d.x0 = stage(nz->x0, in_noise[1], (size_t)B * ad, s);
         d.t = stage(nz->t, in_noise[2], B, s);
@@ -3205,6 +3353,14 @@ struct fql_engine {
                          1.0f / (float)fs, (float)(s + 1) / (float)fs);
         schedule(ev->prog_os, W);
         schedule(ev->prog_flow, W);
+        if (ifql) {   // best-of-N scoring: the critic pair on every sample row
+            ev->Xq = dalloc(W, (size_t)n_pad * nets[NET_C0].in_p());
+            for (int e = 0; e < 2; ++e) {
+                ev->p_q[e] = make_pass(W, NET_C0 + e, n_pad, ev->Xq, false, false);
+                emit_forward(ev->prog_q, ev->p_q[e], false);
+            }
+            schedule(ev->prog_q, W);
+        }
         if (visual) {
             const size_t ib = (size_t)cfg.img_h * cfg.img_w * cfg.img_c;
             ev->st_img = (unsigned char*)dalloc(W, ((size_t)n_pad * ib + 3) / 4 + 4);
@@ -3261,11 +3417,48 @@ struct fql_engine {
             }
         }
     }
+    // IFQL sample_actions (agents/ifql.py:123-155), per observation: num_samples noises through the Euler flow of actor_flow, clip, score by
+    // min(q1, q2) of the critic, keep the first argmax.  [n, od] is a batched extension of the reference's single observation: row by row
+    // equal to n calls with the same noises.  Chunks of <= 4096 sample rows, as eval_rows.
+    void ifql_sample(const float* obs, const float* noise, uint64_t sd, int n, float* out, hipStream_t s, bool own_stream) {
+        if (n <= 0) invalid("n must be positive (got %d)", n);
+        if (!obs || !out) invalid("observations/out must not be NULL");
+        const int od = cfg.obs_dim, ad = cfg.act_dim, ap = pad16(ad), N = num_samples;
+        const int per = std::max(1, 4096 / N);
+        for (int start = 0; start < n; start += per) {
+            const int m = std::min(per, n - start);
+            Eval& ev = get_eval(pad16(m * N));
+            const float* o = stage(obs + (size_t)start * od, ev.st_obs, (size_t)m * od, s);
+            const float* z = noise ? stage(noise + (size_t)start * N * ad, ev.st_noise, (size_t)m * N * ad, s) : nullptr;
+            drain_staging(s);
+            IfqlRepeatArgs ra{o, z, ev.Xf, seed, sd, m, N, ev.n_pad, od, ad, nets[NET_BC].in_p(), start * N};
+            hipLaunchKernelGGL(fql_ifql_repeat_kernel, dim3((ev.n_pad + 3) / 4), dim3(FQL_THREADS), 0, s, ra);
+            run_launches(ev.prog_flow, s);
+            IfqlQinArgs qa{o, ev.tgt, ev.Xq, m, N, ev.n_pad, od, ad, ap, nets[NET_C0].in_p()};
+            hipLaunchKernelGGL(fql_ifql_qin_kernel, dim3((ev.n_pad + 3) / 4), dim3(FQL_THREADS), 0, s, qa);
+            run_launches(ev.prog_q, s);
+            float* dst = out + (size_t)start * ad;
+            const bool dev_out = is_device_ptr(dst);
+            IfqlSelectArgs sa{ev.p_q[0].out, ev.p_q[1].out, ev.tgt, dev_out ? dst : ev.st_out, m, N, ad, ap};
+            hipLaunchKernelGGL(fql_ifql_select_kernel, dim3((m + 3) / 4), dim3(FQL_THREADS), 0, s, sa);
+            HIP_CHECK(hipGetLastError());
+            if (!dev_out) {
+                HIP_CHECK(hipMemcpyAsync(dst, ev.st_out, (size_t)m * ad * sizeof(float), hipMemcpyDeviceToHost, s));
+                HIP_CHECK(hipStreamSynchronize(s));
+            } else if (own_stream) {
+                HIP_CHECK(hipStreamSynchronize(s));
+            }
+        }
+    }
 };
 
 // ================================================================================================
 // C ABI
 // ================================================================================================
+#define FQL_IFQL_REFUSES(h, what)                                                                          \
+    do {                                                                                                \
+        if ((h) && (h)->ifql) { (h)->err = what " is not available on an IFQL handle"; return FQL_E_STATE; } \
+    } while (0)
 // FQL_TRY: every entry point that may use HIP on the engine's buffers - updates still on the engine's AQL queues finish first.
 // FQL_TRY_FAST: the update entry points that can go to those queues themselves (run_full decides).
 #define FQL_TRY(h, ...) FQL_TRY_(h, ((h)->group_fence(), (h)->hip_touch()), __VA_ARGS__)
@@ -3345,9 +3538,36 @@ void fql_default_config(fql_config* c) {
 
 const char* fql_last_error(fql_handle h) { return h ? h->err.c_str() : g_create_error.c_str(); }
 
-int fql_create(const fql_config* cfg, uint64_t seed, fql_handle* out) {
+static int create_engine(const fql_config* cfg, const fql_ifql_config* icfg, uint64_t seed, fql_handle* out);
+int fql_create(const fql_config* cfg, uint64_t seed, fql_handle* out) { return create_engine(cfg, nullptr, seed, out); }
+
+void fql_ifql_default_config(fql_ifql_config* c) {   // agents/ifql.py:231-250
+    std::memset(c, 0, sizeof *c);
+    c->expectile = 0.9f;
+    c->num_samples = 32;
+}
+int fql_ifql_create(const fql_config* cfg, const fql_ifql_config* icfg, uint64_t seed, fql_handle* out) {
+    if (!icfg) { g_create_error = "icfg must not be NULL"; if (out) *out = nullptr; return FQL_E_INVALID; }
+    return create_engine(cfg, icfg, seed, out);
+}
+static const char* k_ifql_info_names[FQL_IFQL_NUM_INFO] = {
+    "value/value_loss", "value/v_mean", "value/v_max", "value/v_min", "critic/critic_loss", "critic/q_mean", "critic/q_max",
+    "critic/q_min", "actor/actor_loss", "grad/max", "grad/min", "grad/norm"};
+int fql_num_info(fql_handle h) { return !h ? FQL_E_INVALID : h->ifql ? FQL_IFQL_NUM_INFO : FQL_NUM_INFO; }
+const char* fql_handle_info_name(fql_handle h, int i) {
+    if (!h || i < 0 || i >= fql_num_info(h)) return nullptr;
+    return h->ifql ? k_ifql_info_names[i] : k_info_names[i];
+}
+
+static int create_engine(const fql_config* cfg, const fql_ifql_config* icfg, uint64_t seed, fql_handle* out) {
     if (!cfg || !out) { g_create_error = "cfg/out must not be NULL"; return FQL_E_INVALID; }
     *out = nullptr;
+    if (icfg) {   // IFQL: state observations and fp32 only
+        if (cfg->encoder != 0) { g_create_error = "fql_ifql_create: visual encoders are not available for IFQL (encoder must be 0)"; return FQL_E_INVALID; }
+        if (cfg->precision != 0) { g_create_error = "fql_ifql_create: IFQL runs in fp32 only (precision must be 0)"; return FQL_E_INVALID; }
+        if (!(icfg->expectile > 0.0f && icfg->expectile < 1.0f)) { g_create_error = "fql_ifql_create: expectile must be in (0, 1)"; return FQL_E_INVALID; }
+        if (icfg->num_samples < 1 || icfg->num_samples > 4096) { g_create_error = "fql_ifql_create: num_samples must be in [1, 4096]"; return FQL_E_INVALID; }
+    }
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
         (void)hipGetLastError();
@@ -3358,6 +3578,7 @@ int fql_create(const fql_config* cfg, uint64_t seed, fql_handle* out) {
     try {
         h->cfg = *cfg;
         h->seed = seed;
+        if (icfg) { h->ifql = true; h->expectile = icfg->expectile; h->num_samples = icfg->num_samples; }
         if (cfg->encoder != 0) {   // visual agent (agents/fql.py:196-202): the MLPs see the 512-wide encoding instead of obs
             if (cfg->encoder != 1 && cfg->encoder != 2) invalid("encoder %d not available (0 = none, 1 = impala_small, 2 = impala)", cfg->encoder);
             if (cfg->img_h <= 0 || cfg->img_w <= 0 || cfg->img_h % 32 || cfg->img_w % 32 || cfg->img_w > 128 || cfg->img_c <= 0 || cfg->img_c > 16)
@@ -3573,6 +3794,7 @@ static void run_full(fql_handle h, hipStream_t s, bool own_stream) {
 
 int fql_update_begin(fql_handle h, const float* obs, const float* act, const float* rew, const float* mask,
                      const float* nobs, int batch_size, const fql_noise* noise, void* stream) {
+    FQL_IFQL_REFUSES(h, "fql_update_begin");
     if (!h) return FQL_E_INVALID;
     FQL_TRY(h, {
         hipStream_t s = pick(h, stream);
@@ -3583,6 +3805,7 @@ int fql_update_begin(fql_handle h, const float* obs, const float* act, const flo
     });
 }
 int fql_update_end(fql_handle h, float* info13, void* stream) {
+    FQL_IFQL_REFUSES(h, "fql_update_end");
     if (!h) return FQL_E_INVALID;
     if (!h->began) { h->err = "fql_update_end without fql_update_begin"; return FQL_E_STATE; }
     FQL_TRY(h, {
@@ -3638,13 +3861,19 @@ int fql_total_loss(fql_handle h, const float* obs, const float* act, const float
         float tmp[10];
         HIP_CHECK(hipMemcpyAsync(tmp, &h->d_state->info[0], sizeof tmp, hipMemcpyDeviceToHost, s));
         HIP_CHECK(hipStreamSynchronize(s));
+        if (h->ifql) {   // agents/ifql.py:79-98: value + critic + actor; nine infos
+            if (loss) *loss = tmp[0] + tmp[4] + tmp[8];
+            if (info10) std::memcpy(info10, tmp, 9 * sizeof(float));
+        } else {
         if (loss) *loss = tmp[0] + tmp[4];
         if (info10) std::memcpy(info10, tmp, sizeof tmp);
+        }
     });
 }
 
 int fql_sample_actions(fql_handle h, const float* obs, int n, const float* noise, uint64_t seed, float* out, void* stream) {
     if (!h) return FQL_E_INVALID;
+    if (h->ifql) FQL_TRY(h, h->ifql_sample(obs, noise, seed, n, out, pick(h, stream), stream == nullptr));
     FQL_TRY(h, h->eval_rows(false, obs, noise, seed, n, out, pick(h, stream), stream == nullptr));
 }
 int fql_flow_actions(fql_handle h, const float* obs, const float* noises, int n, float* out, void* stream) {
@@ -3703,6 +3932,7 @@ int fql_dataset_size(fql_handle h, int64_t* size, int64_t* pointer) {
 }
 // ---- online fine-tuning: ring capacity, uint8 ring insert, the replay ring of balanced sampling (helpers above extern "C")
 int fql_noise_from_jax_keys(fql_handle h, const uint32_t* keys10, int partitionable, int batch_size, fql_noise* out, void* stream) {
+    FQL_IFQL_REFUSES(h, "fql_noise_from_jax_keys");
     if (!h || !keys10 || !out) return FQL_E_INVALID;
     FQL_TRY(h, {
         if (batch_size != h->B) invalid("batch_size %d does not match the engine's workspace (%d); call fql_set_batch_size", batch_size, h->B);
@@ -3753,6 +3983,7 @@ int fql_dataset_reserve(fql_handle h, int64_t capacity) {
     });
 }
 int fql_dataset_add_frames(fql_handle h, const uint8_t* frame, const uint8_t* next_frame, const float* ac, float reward, float mask) {
+    FQL_IFQL_REFUSES(h, "fql_dataset_add_frames");
     if (!h) return FQL_E_INVALID;
     FQL_TRY(h, {
         if (!h->visual || !h->ds_frames) throw Invalid{"no frames dataset allocated (fql_dataset_upload_frames)"};
@@ -3764,6 +3995,7 @@ int fql_dataset_add_frames(fql_handle h, const uint8_t* frame, const uint8_t* ne
     });
 }
 int fql_replay_create(fql_handle h, int64_t capacity) {
+    FQL_IFQL_REFUSES(h, "fql_replay_create");
     if (!h) return FQL_E_INVALID;
     FQL_TRY(h, {
         if (capacity < 1) invalid("fql_replay_create: capacity %lld", (long long)capacity);
@@ -3783,6 +4015,7 @@ int fql_replay_create(fql_handle h, int64_t capacity) {
     });
 }
 int fql_replay_add(fql_handle h, const float* ob, const float* ac, float reward, float mask, const float* nob) {
+    FQL_IFQL_REFUSES(h, "fql_replay_add");
     if (!h) return FQL_E_INVALID;
     FQL_TRY(h, {
         if (h->rb_cap <= 0 || h->visual) throw Invalid{"fql_replay_add: no state replay ring (fql_replay_create; frames agents use fql_replay_add_frames)"};
@@ -3793,6 +4026,7 @@ int fql_replay_add(fql_handle h, const float* ob, const float* ac, float reward,
     });
 }
 int fql_replay_add_frames(fql_handle h, const uint8_t* frame, const uint8_t* next_frame, const float* ac, float reward, float mask) {
+    FQL_IFQL_REFUSES(h, "fql_replay_add_frames");
     if (!h) return FQL_E_INVALID;
     FQL_TRY(h, {
         if (h->rb_cap <= 0 || !h->visual) throw Invalid{"fql_replay_add_frames: no frames replay ring (fql_replay_create on a frames agent)"};
@@ -3804,6 +4038,7 @@ int fql_replay_add_frames(fql_handle h, const uint8_t* frame, const uint8_t* nex
     });
 }
 int fql_replay_size(fql_handle h, int64_t* size, int64_t* pointer) {
+    FQL_IFQL_REFUSES(h, "fql_replay_size");
     if (!h) return FQL_E_INVALID;
     if (size) *size = h->rb_size;
     if (pointer) *pointer = h->rb_ptr;
@@ -3811,6 +4046,7 @@ int fql_replay_size(fql_handle h, int64_t* size, int64_t* pointer) {
 }
 int fql_update_balanced(fql_handle h, const int64_t* idx_dataset, const int64_t* idx_replay, const int32_t* crop_froms, int batch_size,
                         const fql_noise* noise, float* info13, void* stream) {
+    FQL_IFQL_REFUSES(h, "fql_update_balanced");
     if (!h) return FQL_E_INVALID;
     if (h->began) { h->err = "fql_update_balanced between fql_update_begin and fql_update_end"; return FQL_E_STATE; }
     FQL_TRY_FAST(h, {
@@ -3824,6 +4060,7 @@ int fql_update_balanced(fql_handle h, const int64_t* idx_dataset, const int64_t*
 
 int fql_update_from_dataset_begin(fql_handle h, const int64_t* idx, int batch_size, int64_t lo, int64_t hi,
                                   const fql_noise* noise, void* stream) {
+    FQL_IFQL_REFUSES(h, "fql_update_from_dataset_begin");
     if (!h) return FQL_E_INVALID;
     FQL_TRY(h, {
         hipStream_t s = pick(h, stream);
@@ -3835,6 +4072,7 @@ int fql_update_from_dataset_begin(fql_handle h, const int64_t* idx, int batch_si
 }
 int fql_update_from_dataset_begin_split(fql_handle h, const int64_t* idx, int batch_size, int64_t lo, int64_t hi,
                                         const fql_noise* noise, void* stream0, void* stream1) {
+    FQL_IFQL_REFUSES(h, "fql_update_from_dataset_begin_split");
     if (!h) return FQL_E_INVALID;
     if (!h->split_ok || !stream0 || !stream1 || stream0 == stream1) { h->err = "split update unavailable (needs two distinct streams and a two-lane program)"; return FQL_E_STATE; }
     FQL_TRY(h, {
@@ -3845,6 +4083,7 @@ int fql_update_from_dataset_begin_split(fql_handle h, const int64_t* idx, int ba
 }
 int fql_update_begin_split(fql_handle h, const float* obs, const float* act, const float* rew, const float* mask, const float* nobs,
                            int batch_size, const fql_noise* noise, void* stream0, void* stream1) {
+    FQL_IFQL_REFUSES(h, "fql_update_begin_split");
     if (!h) return FQL_E_INVALID;
     if (!h->split_ok || !stream0 || !stream1 || stream0 == stream1) { h->err = "split update unavailable (needs two distinct streams and a two-lane program)"; return FQL_E_STATE; }
     FQL_TRY(h, {
@@ -3854,6 +4093,7 @@ int fql_update_begin_split(fql_handle h, const float* obs, const float* act, con
     });
 }
 int fql_update_end_split(fql_handle h, float* info13, void* stream0, void* stream1) {
+    FQL_IFQL_REFUSES(h, "fql_update_end_split");
     if (!h) return FQL_E_INVALID;
     if (!h->began) { h->err = "fql_update_end_split without fql_update_begin"; return FQL_E_STATE; }
     if (!stream0 || !stream1 || stream0 == stream1) { h->err = "fql_update_end_split needs two distinct streams"; return FQL_E_STATE; }
@@ -3864,6 +4104,7 @@ int fql_update_end_split(fql_handle h, float* info13, void* stream0, void* strea
     });
 }
 int fql_grad_buckets(fql_handle h, size_t offsets[2], size_t lengths[2]) {
+    FQL_IFQL_REFUSES(h, "fql_grad_buckets");
     if (!h || !offsets || !lengths) return FQL_E_INVALID;
     // bucket 0: both critic members + the BC flow actor (all produced on lane 1); bucket 1: the one-step actor (lane 0's tail)
     offsets[0] = 0; lengths[0] = h->nets[NET_OS].off;
@@ -4103,6 +4344,7 @@ extern "C" int fql_debug_enc(fql_handle h, int enc, int code, void* out, size_t 
 
 int fql_dataset_upload_frames(fql_handle h, int64_t n, const uint8_t* frames, const uint8_t* next_frames, const float* act,
                               const float* rew, const float* mask, const float* terminals, int frame_stack, float p_aug) {
+    FQL_IFQL_REFUSES(h, "fql_dataset_upload_frames");
     if (!h) return FQL_E_INVALID;
     FQL_TRY(h, {
         if (!h->visual) throw Invalid{"fql_dataset_upload_frames needs an agent created with an encoder"};
@@ -4145,6 +4387,7 @@ int fql_dataset_upload_frames(fql_handle h, int64_t n, const uint8_t* frames, co
 }
 int fql_update_from_frames(fql_handle h, const int64_t* idx, const int32_t* crop_froms, int batch_size, int64_t lo, int64_t hi,
                            const fql_noise* noise, float* info13, void* stream) {
+    FQL_IFQL_REFUSES(h, "fql_update_from_frames");
     if (!h) return FQL_E_INVALID;
     FQL_TRY(h, {
         hipStream_t s = pick(h, stream);
@@ -4406,6 +4649,11 @@ extern "C" {
 int fql_group_create(const fql_handle* members, int k, fql_group* out) {
     if (!out) { g_create_error = "fql_group_create: out must not be NULL"; return FQL_E_INVALID; }
     *out = nullptr;
+    for (int i = 0; members && i < k; ++i)
+        if (members[i] && members[i]->ifql) {
+            g_create_error = "fql_group_create: member " + std::to_string(i) + " is an IFQL handle (groups take FQL agents only)";
+            return FQL_E_STATE;
+        }
     auto* g = new fql_group_s();
     try {
         group_check(members, k);

@@ -294,6 +294,35 @@ int fql_group_synchronize(fql_group g);
 int fql_stats(fql_handle h, int64_t* launches_per_update, int64_t* macs_per_update, int64_t* param_count);
 void* fql_stream(fql_handle h);
 
+/* ---- IFQL: implicit flow Q-learning (agents/ifql.py), the flow variant of IDQL, on the same engine ----
+ * State observations and fp32 only.  Networks (agents/ifql.py:188-225): "modules_value/value_net/..." (a 1-member Value: leaves are
+ * UNSTACKED [in, out]), "modules_critic/value_net/..." and "modules_target_critic/value_net/..." (stacked [2, ...] as in FQL),
+ * "modules_actor_flow/mlp/..." (FQL's BC flow network).  Glorot-uniform kernels, zero biases, target := critic.
+ * An IFQL handle is an ordinary fql_handle: destroy, set_batch_size, leaf / param / opt-state / step access, fql_update,
+ * fql_update_from_dataset (device-drawn and explicit rows), dataset upload / add / reserve / size, fql_total_loss (writes 9 infos:
+ * loss = value + critic + actor), fql_sample_actions, fql_flow_actions, info enqueue / wait, fql_read_info, fql_synchronize, fql_stats
+ * and fql_stream work on it.  Differences:
+ *   - info buffers stay 13 floats: slots 0-11 hold the 12 IFQL infos (fql_handle_info_name), slot 12 is 0;
+ *   - fql_noise: only x0 [B, act] and t [B] are read; any other non-NULL pointer is FQL_E_INVALID;
+ *   - fql_sample_actions: per observation, num_samples noises through the Euler flow of actor_flow, clipped to [-1, 1], scored by
+ *     min(q1, q2) of the critic, the first argmax kept (agents/ifql.py:123-155).  noise is [n, num_samples, act] or NULL (engine RNG).
+ *     n > 1 is an extension (the reference takes one observation): row by row equal to n single calls with the same noises;
+ *   - alpha, q_agg and normalize_q_loss of fql_config are ignored.
+ * Refused: encoder != 0 or precision != 0 at create (FQL_E_INVALID); on an IFQL handle fql_update_begin* / _end*, fql_grad_buckets, frame
+ * uploads / updates, fql_noise_from_jax_keys, the replay ring and balanced sampling return FQL_E_STATE, and fql_group_create with an IFQL
+ * member returns FQL_E_STATE. */
+#define FQL_IFQL_NUM_INFO 12
+typedef struct fql_ifql_config {
+    float expectile;      /* IQL expectile (0.9) */
+    int32_t num_samples;  /* best-of-N sample count (32) */
+    int32_t reserved[6];
+} fql_ifql_config;
+void fql_ifql_default_config(fql_ifql_config* c);
+int fql_ifql_create(const fql_config* cfg, const fql_ifql_config* icfg, uint64_t seed, fql_handle* out);
+/* infos per update of this handle: 13 (FQL) or 12 (IFQL); their names, NULL past fql_num_info */
+int fql_num_info(fql_handle h);
+const char* fql_handle_info_name(fql_handle h, int i);
+
 #ifdef __cplusplus
 }
 #endif
