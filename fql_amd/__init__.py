@@ -1,13 +1,14 @@
 """fql_amd: MI355X-native (gfx950) Flow Q-Learning gradient step behind the reference's FQLAgent API.
 
-`agents` mirrors the reference registry (agents/__init__.py:10-19) for the agents on the built path: FQL and IFQL.
+`agents` mirrors the reference registry (agents/__init__.py:10-19) for the agents on the built path: FQL, IFQL and ReBRAC.
 """
 from .agent import FQLAgent, FQLAgentGroup, INFO_KEYS, NOISE_KEYS
 from .config import get_config
 from .datasets import Dataset, ReplayBuffer
 from .ifql import IFQLAgent, IFQL_INFO_KEYS
+from .rebrac import ReBRACAgent, REBRAC_INFO_KEYS, REBRAC_CRITIC_INFO_KEYS
 
-agents = dict(fql=FQLAgent, ifql=IFQLAgent)
+agents = dict(fql=FQLAgent, ifql=IFQLAgent, rebrac=ReBRACAgent)
 
-__all__ = ['FQLAgent', 'FQLAgentGroup', 'IFQLAgent', 'get_config', 'agents', 'INFO_KEYS', 'IFQL_INFO_KEYS', 'NOISE_KEYS', 'Dataset',
-           'ReplayBuffer']
+__all__ = ['FQLAgent', 'FQLAgentGroup', 'IFQLAgent', 'ReBRACAgent', 'get_config', 'agents', 'INFO_KEYS', 'IFQL_INFO_KEYS',
+           'REBRAC_INFO_KEYS', 'REBRAC_CRITIC_INFO_KEYS', 'NOISE_KEYS', 'Dataset', 'ReplayBuffer']

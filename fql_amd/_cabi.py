@@ -15,6 +15,8 @@ FQL_MAX_HIDDEN = 8
 FQL_STREAM_LEGACY = 1   # (void*)1 == hipStreamLegacy: the legacy default stream (torch's default stream)
 FQL_NUM_INFO = 13
 FQL_IFQL_NUM_INFO = 12
+FQL_REBRAC_NUM_INFO = 12
+FQL_REBRAC_CRITIC_NUM_INFO = 7
 FQL_OK, FQL_E_INVALID, FQL_E_NODEVICE, FQL_E_HIP, FQL_E_STATE, FQL_E_NOTFOUND = 0, -1, -2, -3, -4, -5
 
 
@@ -33,6 +35,11 @@ class FqlConfig(C.Structure):
 
 class FqlIfqlConfig(C.Structure):
     _fields_ = [('expectile', C.c_float), ('num_samples', C.c_int32), ('reserved', C.c_int32 * 6)]
+
+
+class FqlRebracConfig(C.Structure):
+    _fields_ = [('alpha_actor', C.c_float), ('alpha_critic', C.c_float), ('actor_noise', C.c_float), ('actor_noise_clip', C.c_float),
+                ('tanh_squash', C.c_int32), ('actor_fc_scale', C.c_float), ('reserved', C.c_int32 * 6)]
 
 
 class FqlNoise(C.Structure):
@@ -100,6 +107,13 @@ SYMBOLS = {
     'fql_ifql_create': (_I, [C.POINTER(FqlConfig), C.POINTER(FqlIfqlConfig), _U64, C.POINTER(_VP)]),
     'fql_num_info': (_I, [_VP]),
     'fql_handle_info_name': (C.c_char_p, [_VP, _I]),
+    'fql_rebrac_default_config': (None, [C.POINTER(FqlRebracConfig)]),
+    'fql_rebrac_create': (_I, [C.POINTER(FqlConfig), C.POINTER(FqlRebracConfig), _U64, C.POINTER(_VP)]),
+    'fql_rebrac_update': (_I, [_VP] + _BATCH[:5] + [_VP, _I, C.POINTER(FqlNoise), _I, _VP, _VP]),
+    'fql_rebrac_update_from_dataset': (_I, [_VP, _VP, _I, _I64, _I64, C.POINTER(FqlNoise), _I, _VP, _VP]),
+    'fql_rebrac_total_loss': (_I, [_VP] + _BATCH[:5] + [_VP, _I, C.POINTER(FqlNoise), _I, C.POINTER(_F), C.POINTER(_F), _VP]),
+    'fql_rebrac_sample_actions': (_I, [_VP, _VP, _I, _VP, _U64, _F, _VP, _VP]),
+    'fql_rebrac_stats': (_I, [_VP, _I, C.POINTER(_I64), C.POINTER(_I64)]),
 }
 
 _lib = None

@@ -16,6 +16,7 @@
 #include "fql_aux.h"
 #include "fql_xchain.h"
 #include "fql_ifql.h"
+#include "fql_rebrac.h"
 #include <hip/hip_ext.h>
 #include "fql_aql.h"
 
@@ -84,7 +85,8 @@ struct Net {
     int in_p() const { return layers.front().in_p; }
     int nl() const { return (int)layers.size(); }
 };
-enum { NET_C0 = 0, NET_C1, NET_BC, NET_OS, NET_T0, NET_T1, NUM_NETS };
+// NET_TA: ReBRAC's target actor (empty, zero-sized, in every other agent: their arena is unchanged)
+enum { NET_C0 = 0, NET_C1, NET_BC, NET_OS, NET_T0, NET_T1, NET_TA, NUM_NETS };
 
 // IMPALA encoder in the arena (utils/encoders.py:61-100): per stack 1 + 2 num_blocks convolutions, then Dense + GELU.
 // A convolution leaf is stored exactly as flax lays it out, [3][3][cin][cout] = [tap][cin][cout], bias [cout].
@@ -128,7 +130,9 @@ enum OpType { OP_GEMM, OP_GEMM64, OP_WGRAD, OP_LNBWD, OP_PREP, OP_POSTOS, OP_EUL
               OP_LOSS_ACTOR, OP_CONV_WPREP, OP_CONV, OP_CONV_U8, OP_POOL, OP_POOL_BWD, OP_CONV_WGRAD, OP_CONV_WRED, OP_ENC_DZ, OP_CHAIN, OP_WFRAG, OP_XCHAIN, OP_HEAD_DGRAD, OP_DGRAD0, OP_ADAM,
               OP_FINALIZE,
               // IFQL (agents/ifql.py) only: after every FQL type, so FQL programs keep their launch order
-              OP_IFQL_PREP, OP_IFQL_LOSS_V, OP_IFQL_LOSS_C, OP_IFQL_FIN, OP_NUM_TYPES };
+              OP_IFQL_PREP, OP_IFQL_LOSS_V, OP_IFQL_LOSS_C, OP_IFQL_FIN,
+              // ReBRAC (agents/rebrac.py) only: after IFQL's
+              OP_REBRAC_PREP, OP_REBRAC_ACT, OP_REBRAC_LOSS_C, OP_REBRAC_LOSS_A, OP_REBRAC_AGRAD, OP_REBRAC_FIN, OP_NUM_TYPES };
 
 struct Op {
     OpType type;
@@ -153,6 +157,11 @@ struct Op {
     IfqlPrepArgs iprep;
     IfqlValueArgs iv;
     IfqlCriticArgs ic;
+    RebracPrepArgs rprep;
+    RebracActArgs ract;
+    RebracCriticArgs rc;
+    RebracActorArgs ra;
+    RebracActorGradArgs rag;
     ChainArgs chain;
     XChainArgs xchain;
     const ConvWprepTask* wprep_tasks = nullptr;
@@ -160,6 +169,7 @@ struct Op {
     int cw_grid = 0;
     int adam_c0 = 0, adam_n = -1;  // chunk range of an Adam op (-1: all chunks)
     int adam_c1 = 0, adam_n1 = 0;  // second chunk range of the same launch (two modules merged), adam_n1 = 0: none
+    int adam_polyak = -1;          // Polyak range of an Adam op in floats from offset 0 (-1: critic_size; 0: no Polyak step)
     int fin_mode = 0;
     int level = 0;
     int lane = 0;            // 0 = critical lane (Euler chain, one-step backward), 1 = side lane
@@ -251,6 +261,16 @@ struct fql_engine {
     int num_samples = 32;
     float* X_v = nullptr;   // [2B, value in_p]: [obs ; next_obs]
     PassBuf p_v;            // value pass over X_v (backward over the obs half only)
+    // ReBRAC agent (agents/rebrac.py; fql_rebrac_create): NET_BC holds the actor (obs -> mean), NET_OS is empty and NET_TA, the target
+    // actor, follows the target critic, so the Polyak range [0, critic_size = n_train) of fql_adam_kernel covers critic and actor.
+    // Two update programs: prog_full (full_update=True) and prog_critic (critic-only step: no actor passes, zero actor gradient, no Polyak).
+    bool rebrac = false;
+    fql_rebrac_config rcfg{};
+    float *X_a = nullptr, *X_ta = nullptr, *X_t = nullptr, *X_q = nullptr;   // actor inputs [B, inp_a] (obs, next_obs); critic inputs [B, inp_c]
+    float *w_nact = nullptr, *w_noise = nullptr;                            // [B, ap]: next_actions, raw N(0, 1) of the target-policy noise
+    PassBuf p_a, p_ta, p_q[2];                                               // actor, target actor, critic pair on [obs | actor actions]
+    Program prog_critic;
+    AqlProgram aql_critic;
     uint64_t seed = 0;
     int device = 0;
     hipStream_t stream = nullptr, stream2 = nullptr, stream3 = nullptr, stream4 = nullptr;
@@ -287,7 +307,7 @@ struct fql_engine {
     // workspace (per batch size)
     int B = 0;
     std::vector<void*> ws_allocs;
-    float *in_obs = nullptr, *in_act = nullptr, *in_rew = nullptr, *in_mask = nullptr, *in_nobs = nullptr;
+    float *in_obs = nullptr, *in_act = nullptr, *in_rew = nullptr, *in_mask = nullptr, *in_nobs = nullptr, *in_nact = nullptr;
     float* in_noise[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
     int64_t* in_idx = nullptr;
     float *X_os = nullptr, *X_bc = nullptr, *X_eu = nullptr, *X_c1 = nullptr, *X_c2 = nullptr, *X_ct = nullptr;
@@ -429,11 +449,13 @@ struct fql_engine {
         };
         nets[NET_C0] = make(od + ad, cfg.value_hidden, cfg.num_value_hidden, 1, cfg.layer_norm != 0);
         nets[NET_C1] = nets[NET_C0];
-        nets[NET_BC] = make(od + ad + 1, cfg.actor_hidden, cfg.num_actor_hidden, ad, cfg.actor_layer_norm != 0);
-        nets[NET_OS] = ifql ? make(od, cfg.value_hidden, cfg.num_value_hidden, 1, cfg.layer_norm != 0)   // value (agents/ifql.py:188-193)
+        nets[NET_BC] = rebrac ? make(od, cfg.actor_hidden, cfg.num_actor_hidden, ad, cfg.actor_layer_norm != 0)   // actor (utils/networks.py:82-150)
+                              : make(od + ad + 1, cfg.actor_hidden, cfg.num_actor_hidden, ad, cfg.actor_layer_norm != 0);
+        nets[NET_OS] = rebrac ? Net{} : ifql ? make(od, cfg.value_hidden, cfg.num_value_hidden, 1, cfg.layer_norm != 0)   // value (agents/ifql.py:188-193)
                             : make(od + ad, cfg.actor_hidden, cfg.num_actor_hidden, ad, cfg.actor_layer_norm != 0);
         nets[NET_T0] = nets[NET_C0];
         nets[NET_T1] = nets[NET_C0];
+        nets[NET_TA] = rebrac ? nets[NET_BC] : Net{};
         size_t off = 0;
         auto place_enc = [&](int ei) {
             if (!visual) return;
@@ -484,10 +506,11 @@ struct fql_engine {
             if (ni == NET_T1) place_enc(ENC_T);
         }
         n_total = off;
+        if (rebrac) critic_size = n_train;   // Polyak moves the critic pair and the actor (rebrac.py:131-133)
         for (int ni = 0; ni < NUM_NETS; ++ni)
             for (const Layer& L : nets[ni].layers)
                 if (L.in_p > 1024 || L.out_p > 1024) invalid("layer widths above 1024 are not supported (got %d -> %d)", L.in, L.out);
-        if (nets[NET_T0].off - n_train != 0 || nets[NET_T0].size + nets[NET_T1].size + (visual ? encs[ENC_T].size : 0) != critic_size)
+        if (nets[NET_T0].off - n_train != 0 || nets[NET_T0].size + nets[NET_T1].size + nets[NET_TA].size + (visual ? encs[ENC_T].size : 0) != critic_size)
             invalid("internal: target arena layout mismatch");
     }
 
@@ -535,7 +558,7 @@ struct fql_engine {
         const Net& n = nets[NET_BC];
         const int nh = n.nl() - 1;
         const int H = n.layers[0].out_p;
-        bool ok = !ifql && !cfg.actor_layer_norm && cfg.act_dim <= 15 && nh >= 3 && (H == 256 || H == 512);   // (IFQL has no Euler chain in its update)
+        bool ok = !ifql && !rebrac && !cfg.actor_layer_norm && cfg.act_dim <= 15 && nh >= 3 && (H == 256 || H == 512);   // (IFQL has no Euler chain in its update)
         for (int l = 0; l < nh && ok; ++l) ok = n.layers[l].out == H && n.layers[l].out_p == H;
         use_chain = ok;
         if (!ok) return;
@@ -568,7 +591,7 @@ struct fql_engine {
 
     void build_leaves() {
         leaves.clear();
-        struct Mod { const char* name; const char* sub; int n0, n1; bool train; int enc; };
+        struct Mod { const char* name; const char* sub; int n0, n1; bool train; int enc; bool actor = false; };
         const Mod fql_mods[4] = {{"modules_actor_bc_flow", "mlp", NET_BC, -1, true, ENC_BC},
                                  {"modules_actor_onestep_flow", "mlp", NET_OS, -1, true, ENC_OS},
                                  {"modules_critic", "value_net", NET_C0, NET_C1, true, ENC_C},
@@ -578,7 +601,12 @@ struct fql_engine {
                                   {"modules_critic", "value_net", NET_C0, NET_C1, true, ENC_C},
                                   {"modules_target_critic", "value_net", NET_T0, NET_T1, false, ENC_T},
                                   {"modules_value", "value_net", NET_OS, -1, true, ENC_OS}};
-        const Mod* mods = ifql ? ifql_mods : fql_mods;
+        // ReBRAC (agents/rebrac.py:199-213): Actor modules hold actor_net/Dense_0..nh-1 (+ LayerNorm_i) and mean_net (the last layer)
+        const Mod rebrac_mods[4] = {{"modules_actor", "actor_net", NET_BC, -1, true, ENC_BC, true},
+                                    {"modules_critic", "value_net", NET_C0, NET_C1, true, ENC_C},
+                                    {"modules_target_actor", "actor_net", NET_TA, -1, false, ENC_BC, true},
+                                    {"modules_target_critic", "value_net", NET_T0, NET_T1, false, ENC_T}};
+        const Mod* mods = rebrac ? rebrac_mods : ifql ? ifql_mods : fql_mods;
         int tid = 0;
         for (int mi = 0; mi < 4; ++mi) {
             const Mod& m = mods[mi];
@@ -625,8 +653,8 @@ struct fql_engine {
                 leaves.push_back(lf);
             };
             const std::string base = std::string(m.name) + "/" + m.sub + "/";
-            // jax dict order: Dense_0..Dense_L (bias, kernel), then LayerNorm_0.. (bias, scale)
-            for (int i = 0; i < n0.nl(); ++i) {
+            // jax dict order: Dense_0..Dense_L (bias, kernel), then LayerNorm_0.. (bias, scale); an Actor's last layer is mean_net, after actor_net
+            for (int i = 0; i < (m.actor ? n0.nl() - 1 : n0.nl()); ++i) {
                 const Layer& a = n0.layers[i];
                 const Layer* b = ens ? &nets[m.n1].layers[i] : nullptr;
                 add(base + "Dense_" + std::to_string(i) + "/bias", false, 1, a.out, a.b, b ? b->b : 0, 1, a.out_p);
@@ -638,6 +666,12 @@ struct fql_engine {
                 const Layer* b = ens ? &nets[m.n1].layers[i] : nullptr;
                 add(base + "LayerNorm_" + std::to_string(i) + "/bias", false, 1, a.out, a.be, b ? b->be : 0, 1, a.out_p);
                 add(base + "LayerNorm_" + std::to_string(i) + "/scale", false, 1, a.out, a.g, b ? b->g : 0, 1, a.out_p);
+            }
+            if (m.actor) {
+                const Layer& a = n0.layers.back();
+                const std::string hb = std::string(m.name) + "/mean_net/";
+                add(hb + "bias", false, 1, a.out, a.b, 0, 1, a.out_p);
+                add(hb + "kernel", true, a.in, a.out, a.w, 0, a.in_p, a.out_p);
             }
         }
         n_train_leaves = tid;
@@ -661,7 +695,8 @@ struct fql_engine {
         {   // leaves (and so chunks) are ordered module by module: actor_bc_flow, actor_onestep_flow, critic
             const char* fmods[3] = {"modules_actor_bc_flow/", "modules_actor_onestep_flow/", "modules_critic/"};
             const char* imods[3] = {"modules_actor_flow/", "modules_value/", "modules_critic/"};
-            const char* const* mods = ifql ? imods : fmods;
+            const char* rmods[3] = {"modules_actor/", "modules_critic/", "modules_critic/"};   // (two trained modules: the critic's range twice)
+            const char* const* mods = rebrac ? rmods : ifql ? imods : fmods;
             for (int m = 0; m < 3; ++m) {
                 int lo = 1 << 30, hi = -1;
                 for (const Leaf& lf : leaves)
@@ -705,7 +740,9 @@ struct fql_engine {
         std::mt19937_64 gen(seed * 0x9E3779B97F4A7C15ull + 0x1234567ull);
         for (int ni = 0; ni <= NET_OS; ++ni)
             for (const Layer& L : nets[ni].layers) {
-                const double lim = std::sqrt(6.0 / (double)(L.in + L.out));
+                // ReBRAC's mean_net: variance_scaling(actor_fc_scale, fan_avg, uniform) (utils/networks.py:9-11,117)
+                const double scale = (rebrac && ni == NET_BC && &L == &nets[ni].layers.back()) ? (double)rcfg.actor_fc_scale : 1.0;
+                const double lim = std::sqrt(6.0 * scale / (double)(L.in + L.out));
                 std::uniform_real_distribution<double> U(-lim, lim);
                 for (int r = 0; r < L.in; ++r)
                     for (int c = 0; c < L.out; ++c) h[L.w + (size_t)r * L.out_p + c] = (float)U(gen);
@@ -2081,7 +2118,7 @@ struct fql_engine {
                 FQL_LAUNCH(fql_xchain_kernel, dim3(XCH_NGRP * XCH_NMEM), dim3(256), x_lds, s, L.op.xchain);
                 break;
             case OP_ADAM: {
-                AdamArgs a{P, G, Mu, Nu, P + n_train, d_chunks, d_state, d_partials, L.op.adam_c0, (int)critic_size, cfg.lr, cfg.tau, tl,
+                AdamArgs a{P, G, Mu, Nu, P + n_train, d_chunks, d_state, d_partials, L.op.adam_c0, L.op.adam_polyak >= 0 ? L.op.adam_polyak : (int)critic_size, cfg.lr, cfg.tau, tl,
                            use_pec ? (const unsigned*)(pec_epoch + pec_teams) : (xsync ? (const unsigned*)(xsync + 16 * 32) : nullptr),
                            L.op.adam_n1 > 0 ? L.op.adam_n : -1, L.op.adam_c1};
                 FQL_LAUNCH(fql_adam_kernel, dim3(L.op.adam_n < 0 ? n_chunks : L.op.adam_n + L.op.adam_n1), dim3(FQL_THREADS), 0, s, a);
@@ -2103,6 +2140,26 @@ struct fql_engine {
             case OP_IFQL_FIN:
                 FQL_LAUNCH(fql_ifql_finalize_kernel, dim3(1), dim3(FQL_THREADS), 0, s,
                                    FinalizeArgs{d_state, d_chunks, d_partials, d_leaf_range, n_chunks, n_train_leaves, L.op.fin_mode, tl});
+                break;
+            case OP_REBRAC_PREP:
+                FQL_LAUNCH(fql_rebrac_prep_kernel, dim3((L.op.rprep.B + 3) / 4), dim3(FQL_THREADS), 0, s, L.op.rprep);
+                break;
+            case OP_REBRAC_ACT:
+                FQL_LAUNCH(fql_rebrac_act_kernel, dim3((L.op.ract.n * L.op.ract.ad + FQL_THREADS - 1) / FQL_THREADS), dim3(FQL_THREADS), 0, s, L.op.ract);
+                break;
+            case OP_REBRAC_LOSS_C:
+                FQL_LAUNCH(fql_rebrac_loss_critic_kernel, dim3(1), dim3(FQL_THREADS), 0, s, L.op.rc);
+                break;
+            case OP_REBRAC_LOSS_A:
+                FQL_LAUNCH(fql_rebrac_loss_actor_kernel, dim3(1), dim3(FQL_THREADS), 0, s, L.op.ra);
+                break;
+            case OP_REBRAC_AGRAD:
+                FQL_LAUNCH(fql_rebrac_actor_grad_kernel, dim3((L.op.rag.B * L.op.rag.ad + FQL_THREADS - 1) / FQL_THREADS), dim3(FQL_THREADS), 0, s, L.op.rag);
+                break;
+            case OP_REBRAC_FIN:
+                FQL_LAUNCH(fql_rebrac_finalize_kernel, dim3(1), dim3(FQL_THREADS), 0, s,
+                                   FinalizeArgs{d_state, d_chunks, d_partials, d_leaf_range, n_chunks, n_train_leaves, L.op.fin_mode & 1, tl},
+                                   (L.op.fin_mode >> 1) & 1);
                 break;
             case OP_NUM_TYPES:
                 break;
@@ -2957,9 +3014,151 @@ struct fql_engine {
         src_valid = false;
     }
 
+    // ---------------------------------------------------------------------------------------
+    // the ReBRAC update as a program (agents/rebrac.py:86-134).  No Euler chain: throughput work on the side lanes.
+    //   lane 0: batch assembly; Adam over every chunk (+ Polyak of critic and actor on a full step) and the finalize, behind both side lanes
+    //   lane 1: target actor -> target action -> target critic pair; full steps: actor -> critic pair on [obs | a] -> actor loss ->
+    //           the pair's input gradient -> dL/dmean -> actor backward
+    //   lane 2: critic pair forward -> critic loss (waits for the target pair on lane 1) -> critic backward (parameter gradients only)
+    // Edges between the forked lanes run 1 -> 2 only (see schedule()).  with_grads = false: the loss probe (no backward, no finalize).
+    // ---------------------------------------------------------------------------------------
+    void build_rebrac_program(Program& pr, bool full_update, bool with_grads) {
+        const int od = cfg.obs_dim, ad = cfg.act_dim, ap = pad16(ad);
+        const int inp_a = nets[NET_BC].in_p(), inp_c = nets[NET_C0].in_p();
+        DevState* st = d_state;
+        const void *I_C = &st->info[REBRAC_I_CRITIC], *I_A = &st->info[REBRAC_I_ACTOR];
+        const bool zero_actor = with_grads && !full_update;
+        const Net& na = nets[NET_BC];
+        wide_tiles = true;
+        allow64 = true;
+        emit_lane = 0;
+        {
+            Op op{};
+            op.type = OP_REBRAC_PREP;
+            op.rprep = RebracPrepArgs{d_src, st, seed, B, od, ad, inp_a, inp_c, ap, X_c1, X_t, X_q, X_a, X_ta, w_act, w_nact, w_noise,
+                                      w_rew, w_mask, zero_actor ? G + na.off : nullptr, zero_actor ? (int64_t)na.size : 0};
+            op.writes = {X_c1, X_t, X_q, X_a, X_ta, w_act, w_nact, w_noise, w_rew, w_mask};
+            if (zero_actor)   // critic-only step: the actor's gradient is zero (rebrac.py:104-106), not the last full step's
+                for (const Layer& L : na.layers) {
+                    op.writes.push_back(G + L.w); op.writes.push_back(G + L.b);
+                    if (L.ln) { op.writes.push_back(G + L.g); op.writes.push_back(G + L.be); }
+                }
+            push(pr, op);
+        }
+        auto act_op = [&](const PassBuf& p, const float* noise, float* X, bool target) {
+            Op op{};
+            op.type = OP_REBRAC_ACT;
+            op.ract = RebracActArgs{p.out, noise, X, 0, 0, B, ad, ap, ap, inp_c, od, 0, target ? 1 : 0, rcfg.tanh_squash, target ? 1 : 0,
+                                    rcfg.actor_noise, rcfg.actor_noise_clip};
+            op.reads = {p.out};
+            if (noise) op.reads.push_back(noise);
+            op.writes = {X};
+            push(pr, op);
+        };
+        emit_lane = 1;
+        emit_forward(pr, p_ta, false);                                  // target_actor(next_obs)  rebrac.py:28
+        act_op(p_ta, w_noise, X_t, true);                               // a' = clip(mode + clip(noise), -1, 1)  rebrac.py:29-34
+        for (int e = 0; e < 2; ++e) emit_forward(pr, p_ct[e], false);   // target_critic(next_obs, a')  rebrac.py:36
+        if (full_update) {
+            emit_forward(pr, p_a, with_grads);                          // actor(obs)  rebrac.py:57
+            act_op(p_a, nullptr, X_q, false);                           // a = mode  rebrac.py:58
+            for (int e = 0; e < 2; ++e) emit_forward(pr, p_q[e], with_grads);   // critic(obs, a), stored params  rebrac.py:61
+            {
+                Op op{};
+                op.type = OP_REBRAC_LOSS_A;
+                op.ra = RebracActorArgs{p_q[0].out, p_q[1].out, X_q, w_act, with_grads ? p_q[0].dz.back() : nullptr,
+                                        with_grads ? p_q[1].dz.back() : nullptr, st, B, od, ad, inp_c, ap, rcfg.alpha_actor};
+                op.reads = {p_q[0].out, p_q[1].out, X_q, w_act};
+                op.writes = {I_A};
+                if (with_grads) { op.writes.push_back(p_q[0].dz.back()); op.writes.push_back(p_q[1].dz.back()); }
+                push(pr, op);
+            }
+            if (with_grads) {
+                for (int e = 0; e < 2; ++e) emit_backward(pr, p_q[e], 0, B, false, true);   // dQ/da only: the critic's params get no gradient
+                Op op{};
+                op.type = OP_REBRAC_AGRAD;
+                op.rag = RebracActorGradArgs{p_q[0].dx0, p_q[1].dx0, X_q, w_act, p_a.dz.back(), B, od, ad, inp_c, ap,
+                                             rcfg.alpha_actor * 2.0f / (float)B, rcfg.tanh_squash};
+                op.reads = {p_q[0].dx0, p_q[1].dx0, X_q, w_act};
+                op.writes = {p_a.dz.back()};
+                push(pr, op);
+                emit_backward(pr, p_a, 0, B, true, false);
+            }
+        }
+        emit_lane = 2;
+        for (int e = 0; e < 2; ++e) emit_forward(pr, p_c1[e], with_grads);   // critic(obs, actions)  rebrac.py:44
+        {
+            Op op{};
+            op.type = OP_REBRAC_LOSS_C;
+            op.rc = RebracCriticArgs{p_c1[0].out, p_c1[1].out, p_ct[0].out, p_ct[1].out, X_t, w_nact, w_rew, w_mask,
+                                     with_grads ? p_c1[0].dz.back() : nullptr, with_grads ? p_c1[1].dz.back() : nullptr, st, B, od, ad, inp_c, ap,
+                                     cfg.discount, rcfg.alpha_critic};
+            op.reads = {p_c1[0].out, p_c1[1].out, p_ct[0].out, p_ct[1].out, X_t, w_nact, w_rew, w_mask};
+            op.writes = {I_C};
+            if (with_grads) { op.writes.push_back(p_c1[0].dz.back()); op.writes.push_back(p_c1[1].dz.back()); }
+            push(pr, op);
+        }
+        if (!with_grads) return;
+        for (int e = 0; e < 2; ++e) emit_backward(pr, p_c1[e], 0, B, true, false);
+        // every chunk in one launch (the actor's too: on a critic-only step Adam still moves it with a zero gradient); Polyak from the
+        // pre-step critic and actor on full steps only (rebrac.py:112-120,131-133)
+        adam_for(pr, 0, {NET_C0, NET_C1, NET_BC}, 0, -2);
+        Op& a = pr.ops.back();
+        if (full_update) for (const Layer& L : na.layers) a.writes.push_back(P + n_train + L.w);   // the target actor
+        else a.adam_polyak = 0;
+        Op f{};
+        f.type = OP_REBRAC_FIN;
+        f.fin_mode = 1 | (full_update ? 2 : 0);
+        f.reads = {I_C, I_A};
+        for (int m = 0; m < 3; ++m) f.reads.push_back(d_partials + mod_chunk0[m] * 4);
+        f.writes = {&st->info[8], st};
+        emit_lane = 0;
+        push(pr, f);
+    }
+
+    void build_rebrac_workspace() {
+        const int ap = pad16(cfg.act_dim);
+        const int inp_a = nets[NET_BC].in_p(), inp_c = nets[NET_C0].in_p();
+        auto& W = ws_allocs;
+        X_c1 = dalloc(W, (size_t)B * inp_c); X_t = dalloc(W, (size_t)B * inp_c); X_q = dalloc(W, (size_t)B * inp_c);
+        X_a = dalloc(W, (size_t)B * inp_a); X_ta = dalloc(W, (size_t)B * inp_a);
+        w_act = dalloc(W, (size_t)B * ap); w_nact = dalloc(W, (size_t)B * ap); w_noise = dalloc(W, (size_t)B * ap);
+        w_rew = dalloc(W, B); w_mask = dalloc(W, B);
+        X_os = X_bc = X_eu = X_c2 = X_ct = X_e0 = C0 = Vpart = vel = tgt = X_v = nullptr;
+        fused_euler = use_pec = use_xchain = euler_finish_fused = false;
+        p_a = make_pass(W, NET_BC, B, X_a, true, false);
+        p_ta = make_pass(W, NET_TA, B, X_ta, false, false);
+        for (int e = 0; e < 2; ++e) {
+            p_c1[e] = make_pass(W, NET_C0 + e, B, X_c1, true, false);
+            p_ct[e] = make_pass(W, NET_T0 + e, B, X_t, false, false);
+            p_q[e] = make_pass(W, NET_C0 + e, B, X_q, true, true);
+        }
+        build_rebrac_program(prog_full, true, true);
+        build_rebrac_program(prog_critic, false, true);
+        build_rebrac_program(prog_loss, true, false);
+        for (Program* pr : {&prog_full, &prog_critic, &prog_loss}) schedule(*pr, W);
+        for (Program* pr : {&prog_full, &prog_critic, &prog_loss}) capture(*pr);
+        aql_tried = false;
+        split_ok = false;
+        launches_per_update = (int64_t)prog_full.launches.size();
+        src_valid = false;
+    }
+    // multiply-accumulates of one ReBRAC update per batch row, algorithmic (full GEMM shapes)
+    int64_t rebrac_macs(bool full_update) const {
+        auto macs = [&](const Net& n) { int64_t m = 0; for (const Layer& L : n.layers) m += (int64_t)L.in * L.out; return m; };
+        auto first = [&](const Net& n) { return (int64_t)n.layers[0].in * n.layers[0].out; };
+        const int64_t ac = macs(nets[NET_BC]), cr = macs(nets[NET_C0]);
+        // target actor + target pair forward; critic pair forward + backward without the input gradient
+        int64_t m = ac + 2 * cr + 2 * cr + 2 * (2 * cr - first(nets[NET_C0]));
+        // actor forward; the pair on [obs | a] forward + input gradient; actor backward without the input gradient
+        if (full_update) m += ac + 2 * cr + 2 * cr + (2 * ac - first(nets[NET_BC]));
+        return m * (int64_t)B;
+    }
+
     int64_t macs_per_update() const {
         auto macs = [&](const Net& n) { int64_t m = 0; for (const Layer& L : n.layers) m += (int64_t)L.in * L.out; return m; };
         auto first = [&](const Net& n) { return (int64_t)n.layers[0].in * n.layers[0].out; };
+        if (rebrac) return rebrac_macs(true);
         const int64_t os = macs(nets[NET_OS]), bc = macs(nets[NET_BC]), cr = macs(nets[NET_C0]);
         if (ifql) {   // value on 2B rows + its backward on B; target pair; critic pair forward + backward (no input gradient); actor_flow forward + backward
             const int64_t fwd = 2 * os + 4 * cr + bc;
@@ -2996,9 +3195,12 @@ struct fql_engine {
         free_program(prog_loss);
         free_program(prog_split);
         free_program(prog_full);
+        free_program(prog_critic);
         aql_drain();
         if (aql_full.kernargs) { hipFree(aql_full.kernargs); }
         aql_full = AqlProgram{};
+        if (aql_critic.kernargs) { hipFree(aql_critic.kernargs); }
+        aql_critic = AqlProgram{};
         use_xchain = false; xsync = nullptr; xvp = nullptr; x_stamps = nullptr;
         free_split();
         for (void* p : ws_allocs) hipFree(p);
@@ -3011,13 +3213,14 @@ struct fql_engine {
         free_workspace();
         B = batch;
         const int od = cfg.obs_dim, ad = cfg.act_dim;
-        const int inp_c = nets[NET_OS].in_p(), inp_b = nets[NET_BC].in_p();
         auto& W = ws_allocs;
         in_obs = dalloc(W, (size_t)B * od); in_nobs = dalloc(W, (size_t)B * od);
         in_act = dalloc(W, (size_t)B * ad); in_rew = dalloc(W, B); in_mask = dalloc(W, B);
         for (int i = 0; i < 5; ++i) in_noise[i] = dalloc(W, (size_t)B * ad);
         in_idx = (int64_t*)dalloc(W, (size_t)B * 4);   // [2][B]: indices in use, staging of host indices (frames path)
         if (ifql) { build_ifql_workspace(); return; }
+        if (rebrac) { in_nact = dalloc(W, (size_t)B * ad); build_rebrac_workspace(); return; }
+        const int inp_c = nets[NET_OS].in_p(), inp_b = nets[NET_BC].in_p();
         X_os = dalloc(W, (size_t)3 * B * inp_c); X_bc = dalloc(W, (size_t)B * inp_b); X_eu = dalloc(W, (size_t)B * inp_b);
         X_c1 = dalloc(W, (size_t)B * inp_c); X_c2 = dalloc(W, (size_t)B * inp_c); X_ct = dalloc(W, (size_t)B * inp_c);
         const int ap = pad16(ad);
@@ -3210,6 +3413,7 @@ struct fql_engine {
         const int ad = cfg.act_dim;
         if (!nz) return;
         if (ifql && (nz->eps1 || nz->z || nz->eps2)) invalid("IFQL reads only x0 and t of fql_noise (eps1, z and eps2 must be NULL)");
+        if (rebrac && (nz->x0 || nz->t || nz->z || nz->eps2)) invalid("ReBRAC reads only eps1 of fql_noise (x0, t, z and eps2 must be NULL)");
         d.eps1 = stage(nz->eps1, in_noise[0], (size_t)B * ad, s);
         d.x0 = stage(nz->x0, in_noise[1], (size_t)B * ad, s);
         d.t = stage(nz->t, in_noise[2], B, s);
@@ -3337,6 +3541,19 @@ struct fql_engine {
         ev->n_pad = n_pad;
         auto& W = ev->allocs;
         const int od = cfg.obs_dim, ad = cfg.act_dim;
+        if (rebrac) {   // sample_actions: the actor's forward over the rows (prog_os on p_os; NET_OS is empty here)
+            ev->X = dalloc(W, (size_t)n_pad * nets[NET_BC].in_p());
+            ev->st_obs = dalloc(W, (size_t)n_pad * od);
+            ev->st_noise = dalloc(W, (size_t)n_pad * ad);
+            ev->st_out = dalloc(W, (size_t)n_pad * ad);
+            ev->p_os = make_pass(W, NET_BC, n_pad, ev->X, false, false);
+            emit_lane = 0;
+            emit_forward(ev->prog_os, ev->p_os, false);
+            schedule(ev->prog_os, W);
+            Eval& ref = *ev;
+            evals[n_pad] = std::move(ev);
+            return ref;
+        }
         ev->X = dalloc(W, (size_t)n_pad * nets[NET_OS].in_p());
         ev->Xf = dalloc(W, (size_t)n_pad * nets[NET_BC].in_p());
         ev->tgt = dalloc(W, (size_t)n_pad * pad16(ad));
@@ -3417,6 +3634,78 @@ struct fql_engine {
             }
         }
     }
+    // ReBRAC sample_actions (agents/rebrac.py:136-152): clip(mode(actor(obs)) + clip(N(0, 1) actor_noise temperature, +-actor_noise_clip), -1, 1).
+    // noise: [n, act] raw N(0, 1) or null (Philox keyed by (seed, sd), row numbers of the call: chunking does not change the draw)
+    void rebrac_sample(const float* obs, const float* noise, uint64_t sd, float temperature, int n, float* out, hipStream_t s, bool own_stream) {
+        if (n <= 0) invalid("n must be positive (got %d)", n);
+        if (!obs || !out) invalid("observations/out must not be NULL");
+        if (!(temperature >= 0.0f)) invalid("temperature must be >= 0");
+        const int od = cfg.obs_dim, ad = cfg.act_dim, ap = pad16(ad);
+        for (int start = 0; start < n; start += 4096) {
+            const int m = std::min(4096, n - start);
+            Eval& ev = get_eval(pad16(m));
+            const float* o = stage(obs + (size_t)start * od, ev.st_obs, (size_t)m * od, s);
+            const float* z = noise ? stage(noise + (size_t)start * ad, ev.st_noise, (size_t)m * ad, s) : nullptr;
+            drain_staging(s);
+            AssembleArgs aa{o, nullptr, ev.X, seed, sd, m, ev.n_pad, od, 0, nets[NET_BC].in_p()};   // [obs | 0]
+            hipLaunchKernelGGL(fql_assemble_kernel, dim3((ev.n_pad + 3) / 4), dim3(FQL_THREADS), 0, s, aa);
+            run_launches(ev.prog_os, s);
+            float* dst = out + (size_t)start * ad;
+            const bool dev_out = is_device_ptr(dst);
+            RebracActArgs ra{ev.p_os.out, z, dev_out ? dst : ev.st_out, seed, sd, m, ad, ap, ad, ad, 0, start, z ? 1 : 2, rcfg.tanh_squash, 1,
+                             rcfg.actor_noise * temperature, rcfg.actor_noise_clip};
+            hipLaunchKernelGGL(fql_rebrac_act_kernel, dim3((m * ad + FQL_THREADS - 1) / FQL_THREADS), dim3(FQL_THREADS), 0, s, ra);
+            HIP_CHECK(hipGetLastError());
+            if (!dev_out) {
+                HIP_CHECK(hipMemcpyAsync(dst, ev.st_out, (size_t)m * ad * sizeof(float), hipMemcpyDeviceToHost, s));
+                HIP_CHECK(hipStreamSynchronize(s));
+            } else if (own_stream) {
+                HIP_CHECK(hipStreamSynchronize(s));
+            }
+        }
+    }
+    // ReBRAC batch sources: the FQL ones plus next_actions (explicit [B, act], or the dataset's actions one row on)
+    void rebrac_source_from_batch(const float* obs, const float* act, const float* rew, const float* mask, const float* nobs, const float* nact,
+                                  int batch, const fql_noise* nz, int advance, hipStream_t s) {
+        if (batch != B) invalid("batch_size %d does not match the engine's workspace (%d); call fql_set_batch_size", batch, B);
+        if (!obs || !act || !rew || !mask || !nobs || !nact) invalid("batch pointers must not be NULL (ReBRAC batches carry next_actions)");
+        const int od = cfg.obs_dim, ad = cfg.act_dim;
+        SrcDesc d{};
+        d.obs = stage(obs, in_obs, (size_t)B * od, s);
+        d.nobs = stage(nobs, in_nobs, (size_t)B * od, s);
+        d.act = stage(act, in_act, (size_t)B * ad, s);
+        d.rew = stage(rew, in_rew, B, s);
+        d.mask = stage(mask, in_mask, B, s);
+        d.nact = stage(nact, in_nact, (size_t)B * ad, s);
+        fill_noise(d, nz, s);
+        d.advance = advance;
+        drain_staging(s);
+        set_source(d, s);
+    }
+    void rebrac_source_from_dataset(const int64_t* idx, int batch, int64_t lo, int64_t hi, const fql_noise* nz, hipStream_t s) {
+        if (batch != B) invalid("batch_size %d does not match the engine's workspace (%d)", batch, B);
+        if (!ds_obs || ds_size <= 0) throw Invalid{"no dataset uploaded (fql_dataset_upload)"};
+        if (lo == 0 && hi == 0) hi = ds_size;
+        if (lo < 0 || hi > ds_size || lo >= hi) invalid("bad sampling range [%lld, %lld) for dataset of %lld rows", (long long)lo, (long long)hi, (long long)ds_size);
+        SrcDesc d{};
+        d.obs = ds_obs; d.act = ds_act; d.rew = ds_rew; d.mask = ds_mask; d.nobs = ds_nobs;
+        d.nact = ds_act; d.nact_rows = ds_size;   // utils/datasets.py:96-100: actions[min(idx + 1, size - 1)], the whole dataset's size
+        if (idx) {
+            if (is_device_ptr(idx)) d.idx = idx;
+            else {
+                hip_touch();
+                HIP_CHECK(hipMemcpyAsync(in_idx, idx, (size_t)B * sizeof(int64_t), hipMemcpyHostToDevice, s));
+                staged_host = true;
+                d.idx = in_idx;
+            }
+        } else {
+            d.use_rng_idx = 1; d.lo = lo; d.span = hi - lo;
+        }
+        fill_noise(d, nz, s);
+        d.advance = 1;
+        drain_staging(s);
+        set_source(d, s);
+    }
     // IFQL sample_actions (agents/ifql.py:123-155), per observation: num_samples noises through the Euler flow of actor_flow, clip, score by
     // min(q1, q2) of the critic, keep the first argmax.  [n, od] is a batched extension of the reference's single observation: row by row
     // equal to n calls with the same noises.  Chunks of <= 4096 sample rows, as eval_rows.
@@ -3458,6 +3747,11 @@ struct fql_engine {
 #define FQL_IFQL_REFUSES(h, what)                                                                          \
     do {                                                                                                \
         if ((h) && (h)->ifql) { (h)->err = what " is not available on an IFQL handle"; return FQL_E_STATE; } \
+        if ((h) && (h)->rebrac) { (h)->err = what " is not available on a ReBRAC handle"; return FQL_E_STATE; } \
+    } while (0)
+#define FQL_REBRAC_REFUSES(h, what, why)                                                                                  \
+    do {                                                                                                               \
+        if ((h) && (h)->rebrac) { (h)->err = what " is not available on a ReBRAC handle (" why ")"; return FQL_E_STATE; } \
     } while (0)
 // FQL_TRY: every entry point that may use HIP on the engine's buffers - updates still on the engine's AQL queues finish first.
 // FQL_TRY_FAST: the update entry points that can go to those queues themselves (run_full decides).
@@ -3538,8 +3832,8 @@ void fql_default_config(fql_config* c) {
 
 const char* fql_last_error(fql_handle h) { return h ? h->err.c_str() : g_create_error.c_str(); }
 
-static int create_engine(const fql_config* cfg, const fql_ifql_config* icfg, uint64_t seed, fql_handle* out);
-int fql_create(const fql_config* cfg, uint64_t seed, fql_handle* out) { return create_engine(cfg, nullptr, seed, out); }
+static int create_engine(const fql_config* cfg, const fql_ifql_config* icfg, const fql_rebrac_config* rcfg, uint64_t seed, fql_handle* out);
+int fql_create(const fql_config* cfg, uint64_t seed, fql_handle* out) { return create_engine(cfg, nullptr, nullptr, seed, out); }
 
 void fql_ifql_default_config(fql_ifql_config* c) {   // agents/ifql.py:231-250
     std::memset(c, 0, sizeof *c);
@@ -3548,18 +3842,34 @@ void fql_ifql_default_config(fql_ifql_config* c) {   // agents/ifql.py:231-250
 }
 int fql_ifql_create(const fql_config* cfg, const fql_ifql_config* icfg, uint64_t seed, fql_handle* out) {
     if (!icfg) { g_create_error = "icfg must not be NULL"; if (out) *out = nullptr; return FQL_E_INVALID; }
-    return create_engine(cfg, icfg, seed, out);
+    return create_engine(cfg, icfg, nullptr, seed, out);
 }
+void fql_rebrac_default_config(fql_rebrac_config* c) {   // agents/rebrac.py:222-244
+    std::memset(c, 0, sizeof *c);
+    c->alpha_actor = 0.0f;
+    c->alpha_critic = 0.0f;
+    c->actor_noise = 0.2f;
+    c->actor_noise_clip = 0.5f;
+    c->tanh_squash = 1;
+    c->actor_fc_scale = 0.01f;
+}
+int fql_rebrac_create(const fql_config* cfg, const fql_rebrac_config* rcfg, uint64_t seed, fql_handle* out) {
+    if (!rcfg) { g_create_error = "rcfg must not be NULL"; if (out) *out = nullptr; return FQL_E_INVALID; }
+    return create_engine(cfg, nullptr, rcfg, seed, out);
+}
+static const char* k_rebrac_info_names[FQL_REBRAC_NUM_INFO] = {
+    "critic/critic_loss", "critic/q_mean", "critic/q_max", "critic/q_min", "actor/total_loss", "actor/actor_loss", "actor/bc_loss",
+    "actor/std", "actor/mse", "grad/max", "grad/min", "grad/norm"};
 static const char* k_ifql_info_names[FQL_IFQL_NUM_INFO] = {
     "value/value_loss", "value/v_mean", "value/v_max", "value/v_min", "critic/critic_loss", "critic/q_mean", "critic/q_max",
     "critic/q_min", "actor/actor_loss", "grad/max", "grad/min", "grad/norm"};
-int fql_num_info(fql_handle h) { return !h ? FQL_E_INVALID : h->ifql ? FQL_IFQL_NUM_INFO : FQL_NUM_INFO; }
+int fql_num_info(fql_handle h) { return !h ? FQL_E_INVALID : h->ifql ? FQL_IFQL_NUM_INFO : h->rebrac ? FQL_REBRAC_NUM_INFO : FQL_NUM_INFO; }
 const char* fql_handle_info_name(fql_handle h, int i) {
     if (!h || i < 0 || i >= fql_num_info(h)) return nullptr;
-    return h->ifql ? k_ifql_info_names[i] : k_info_names[i];
+    return h->ifql ? k_ifql_info_names[i] : h->rebrac ? k_rebrac_info_names[i] : k_info_names[i];
 }
 
-static int create_engine(const fql_config* cfg, const fql_ifql_config* icfg, uint64_t seed, fql_handle* out) {
+static int create_engine(const fql_config* cfg, const fql_ifql_config* icfg, const fql_rebrac_config* rcfg, uint64_t seed, fql_handle* out) {
     if (!cfg || !out) { g_create_error = "cfg/out must not be NULL"; return FQL_E_INVALID; }
     *out = nullptr;
     if (icfg) {   // IFQL: state observations and fp32 only
@@ -3567,6 +3877,14 @@ static int create_engine(const fql_config* cfg, const fql_ifql_config* icfg, uin
         if (cfg->precision != 0) { g_create_error = "fql_ifql_create: IFQL runs in fp32 only (precision must be 0)"; return FQL_E_INVALID; }
         if (!(icfg->expectile > 0.0f && icfg->expectile < 1.0f)) { g_create_error = "fql_ifql_create: expectile must be in (0, 1)"; return FQL_E_INVALID; }
         if (icfg->num_samples < 1 || icfg->num_samples > 4096) { g_create_error = "fql_ifql_create: num_samples must be in [1, 4096]"; return FQL_E_INVALID; }
+    }
+    if (rcfg) {   // ReBRAC: state observations and fp32 only
+        if (cfg->encoder != 0) { g_create_error = "fql_rebrac_create: visual encoders are not available for ReBRAC (encoder must be 0)"; return FQL_E_INVALID; }
+        if (cfg->precision != 0) { g_create_error = "fql_rebrac_create: ReBRAC runs in fp32 only (precision must be 0)"; return FQL_E_INVALID; }
+        if (!(rcfg->actor_noise >= 0.0f) || !(rcfg->actor_noise_clip >= 0.0f)) { g_create_error = "fql_rebrac_create: actor_noise and actor_noise_clip must be >= 0"; return FQL_E_INVALID; }
+        if (!(rcfg->actor_fc_scale > 0.0f)) { g_create_error = "fql_rebrac_create: actor_fc_scale must be > 0"; return FQL_E_INVALID; }
+        if (!std::isfinite(rcfg->alpha_actor) || !std::isfinite(rcfg->alpha_critic)) { g_create_error = "fql_rebrac_create: alpha_actor and alpha_critic must be finite"; return FQL_E_INVALID; }
+        if (rcfg->tanh_squash != 0 && rcfg->tanh_squash != 1) { g_create_error = "fql_rebrac_create: tanh_squash must be 0 or 1"; return FQL_E_INVALID; }
     }
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
@@ -3579,6 +3897,7 @@ static int create_engine(const fql_config* cfg, const fql_ifql_config* icfg, uin
         h->cfg = *cfg;
         h->seed = seed;
         if (icfg) { h->ifql = true; h->expectile = icfg->expectile; h->num_samples = icfg->num_samples; }
+        if (rcfg) { h->rebrac = true; h->rcfg = *rcfg; }
         if (cfg->encoder != 0) {   // visual agent (agents/fql.py:196-202): the MLPs see the 512-wide encoding instead of obs
             if (cfg->encoder != 1 && cfg->encoder != 2) invalid("encoder %d not available (0 = none, 1 = impala_small, 2 = impala)", cfg->encoder);
             if (cfg->img_h <= 0 || cfg->img_w <= 0 || cfg->img_h % 32 || cfg->img_w % 32 || cfg->img_w > 128 || cfg->img_c <= 0 || cfg->img_c > 16)
@@ -3817,6 +4136,7 @@ int fql_update_end(fql_handle h, float* info13, void* stream) {
 }
 int fql_update(fql_handle h, const float* obs, const float* act, const float* rew, const float* mask, const float* nobs,
                int batch_size, const fql_noise* noise, float* info13, void* stream) {
+    FQL_REBRAC_REFUSES(h, "fql_update", "its batch has no next_actions: fql_rebrac_update");
     if (h && h->prog_full.exec && !h->began) {
         FQL_TRY_FAST(h, {
             hipStream_t s = pick(h, stream);
@@ -3853,6 +4173,7 @@ int fql_set_rng_stream(fql_handle h, uint64_t stream_id) {
 
 int fql_total_loss(fql_handle h, const float* obs, const float* act, const float* rew, const float* mask, const float* nobs,
                    int batch_size, const fql_noise* noise, float* loss, float* info10, void* stream) {
+    FQL_REBRAC_REFUSES(h, "fql_total_loss", "its batch has no next_actions: fql_rebrac_total_loss");
     if (!h) return FQL_E_INVALID;
     FQL_TRY(h, {
         hipStream_t s = pick(h, stream);
@@ -3873,10 +4194,12 @@ int fql_total_loss(fql_handle h, const float* obs, const float* act, const float
 
 int fql_sample_actions(fql_handle h, const float* obs, int n, const float* noise, uint64_t seed, float* out, void* stream) {
     if (!h) return FQL_E_INVALID;
+    if (h->rebrac) FQL_TRY(h, h->rebrac_sample(obs, noise, seed, 1.0f, n, out, pick(h, stream), stream == nullptr));
     if (h->ifql) FQL_TRY(h, h->ifql_sample(obs, noise, seed, n, out, pick(h, stream), stream == nullptr));
     FQL_TRY(h, h->eval_rows(false, obs, noise, seed, n, out, pick(h, stream), stream == nullptr));
 }
 int fql_flow_actions(fql_handle h, const float* obs, const float* noises, int n, float* out, void* stream) {
+    FQL_REBRAC_REFUSES(h, "fql_flow_actions", "the actor is deterministic, there is no flow");
     if (!h) return FQL_E_INVALID;
     FQL_TRY(h, h->eval_rows(true, obs, noises, 0, n, out, pick(h, stream), stream == nullptr));
 }
@@ -4113,6 +4436,7 @@ int fql_grad_buckets(fql_handle h, size_t offsets[2], size_t lengths[2]) {
 }
 int fql_update_from_dataset(fql_handle h, const int64_t* idx, int batch_size, int64_t lo, int64_t hi, const fql_noise* noise,
                             float* info13, void* stream) {
+    FQL_REBRAC_REFUSES(h, "fql_update_from_dataset", "the step kind is an argument: fql_rebrac_update_from_dataset");
     if (h && h->visual) return fql_update_from_frames(h, idx, nullptr, batch_size, lo, hi, noise, info13, stream);
     if (h && h->prog_full.exec && !h->began) {
         FQL_TRY_FAST(h, {
@@ -4189,6 +4513,81 @@ int fql_stats(fql_handle h, int64_t* launches_per_update, int64_t* macs_per_upda
 }
 void* fql_stream(fql_handle h) { return h ? (void*)h->stream : nullptr; }
 
+// ---- ReBRAC (agents/rebrac.py) ---------------------------------------------------------------------------------------------------
+// One update: the full program (full_update != 0) or the critic-only one, on the engine's AQL queues when the caller left the stream to
+// the engine, else the captured graph on `s` (both bitwise equal).
+static void run_rebrac(fql_handle h, hipStream_t s, bool own_stream, bool full_update) {
+    static const int no_graph = getenv("FQL_NO_GRAPH") ? atoi(getenv("FQL_NO_GRAPH")) : 0;
+    if (own_stream && !no_graph && !h->aql_tried) {
+        h->aql_tried = true;
+        h->hip_touch();
+        h->build_aql(h->prog_full, h->aql_full);
+        if (h->aql_full.ok) h->build_aql(h->prog_critic, h->aql_critic);
+    }
+    const AqlProgram& ap = full_update ? h->aql_full : h->aql_critic;
+    if (own_stream && ap.ok && !no_graph) {
+        if (h->hip_dirty) { HIP_CHECK(hipStreamSynchronize(s)); h->hip_dirty = false; }
+        try { h->aql.submit(ap); } catch (const AqlError& e) { throw HipError{e.msg}; }
+        h->last_update_aql = true;
+        return;
+    }
+    h->last_update_aql = false;
+    h->hip_touch();
+    run_program(h, full_update ? h->prog_full : h->prog_critic, s);
+}
+#define FQL_REBRAC_ONLY(h, what)                                                                           \
+    do {                                                                                                \
+        if (!(h)) return FQL_E_INVALID;                                                                 \
+        if (!(h)->rebrac) { (h)->err = what " needs a ReBRAC handle (fql_rebrac_create)"; return FQL_E_STATE; } \
+    } while (0)
+int fql_rebrac_update(fql_handle h, const float* obs, const float* act, const float* rew, const float* masks, const float* next_obs,
+                      const float* next_actions, int batch_size, const fql_noise* noise, int full_update, float* info13, void* stream) {
+    FQL_REBRAC_ONLY(h, "fql_rebrac_update");
+    FQL_TRY_FAST(h, {
+        hipStream_t s = pick(h, stream);
+        h->rebrac_source_from_batch(obs, act, rew, masks, next_obs, next_actions, batch_size, noise, 1, s);
+        run_rebrac(h, s, stream == nullptr, full_update != 0);
+        h->finish_info(info13, FQL_NUM_INFO, s);
+    });
+}
+int fql_rebrac_update_from_dataset(fql_handle h, const int64_t* idx, int batch_size, int64_t lo, int64_t hi, const fql_noise* noise,
+                                   int full_update, float* info13, void* stream) {
+    FQL_REBRAC_ONLY(h, "fql_rebrac_update_from_dataset");
+    FQL_TRY_FAST(h, {
+        hipStream_t s = pick(h, stream);
+        h->rebrac_source_from_dataset(idx, batch_size, lo, hi, noise, s);
+        run_rebrac(h, s, stream == nullptr, full_update != 0);
+        h->finish_info(info13, FQL_NUM_INFO, s);
+    });
+}
+int fql_rebrac_total_loss(fql_handle h, const float* obs, const float* act, const float* rew, const float* masks, const float* next_obs,
+                          const float* next_actions, int batch_size, const fql_noise* noise, int full_update, float* loss, float* info10,
+                          void* stream) {
+    FQL_REBRAC_ONLY(h, "fql_rebrac_total_loss");
+    FQL_TRY(h, {
+        hipStream_t s = pick(h, stream);
+        h->rebrac_source_from_batch(obs, act, rew, masks, next_obs, next_actions, batch_size, noise, 0, s);
+        run_program(h, h->prog_loss, s);
+        float tmp[9];
+        HIP_CHECK(hipMemcpyAsync(tmp, &h->d_state->info[0], sizeof tmp, hipMemcpyDeviceToHost, s));
+        HIP_CHECK(hipStreamSynchronize(s));
+        // rebrac.py:86-108: critic_loss (+ the actor's total_loss on a full step); 9 infos, or the 4 critic ones
+        if (loss) *loss = full_update ? tmp[0] + tmp[4] : tmp[0];
+        if (info10) std::memcpy(info10, tmp, (full_update ? 9 : 4) * sizeof(float));
+    });
+}
+int fql_rebrac_sample_actions(fql_handle h, const float* obs, int n, const float* noise, uint64_t seed, float temperature, float* out,
+                              void* stream) {
+    FQL_REBRAC_ONLY(h, "fql_rebrac_sample_actions");
+    FQL_TRY(h, h->rebrac_sample(obs, noise, seed, temperature, n, out, pick(h, stream), stream == nullptr));
+}
+int fql_rebrac_stats(fql_handle h, int full_update, int64_t* launches_per_update, int64_t* macs_per_update) {
+    FQL_REBRAC_ONLY(h, "fql_rebrac_stats");
+    if (launches_per_update) *launches_per_update = (int64_t)(full_update ? h->prog_full : h->prog_critic).launches.size();
+    if (macs_per_update) *macs_per_update = h->rebrac_macs(full_update != 0);
+    return FQL_OK;
+}
+
 }  // extern "C"
 
 // Per-launch device times of ONE update, measured with HIP events on the engine's stream (used by bench.py for the per-kernel
@@ -4199,6 +4598,7 @@ void* fql_stream(fql_handle h) { return h ? (void*)h->stream : nullptr; }
 // one-workgroup kernel that returns at once (median of 32), which the caller subtracts (minus the ~1.4 us such a kernel itself shows
 // in a rocprofv3 trace) to compare with rocprofv3's per-kernel durations.
 extern "C" int fql_profile_update(fql_handle h, int batch_size, int cap, int* type, int* lane, int* grid, float* us, double* macs, float* null_us) {
+    FQL_REBRAC_REFUSES(h, "fql_profile_update", "FQL batch sources only");
     if (!h || !type || !us) return FQL_E_INVALID;
     if (!h->prog_full.exec) { h->err = "no single-graph update program"; return FQL_E_STATE; }
     try {
@@ -4234,6 +4634,7 @@ extern "C" int fql_profile_update(fql_handle h, int batch_size, int cap, int* ty
 // 4 X_c1 [B, inp_c], 5 w_rew [B], 6 w_mask [B], 7 in_idx (int64 [B], frames path), 8 in_crop (int32 [B][2], frames path),
 // 9 X_eu [B, inp_b].  *dims receives {rows, row stride in elements}.
 extern "C" int fql_debug_workspace(fql_handle h, int which, void* out, size_t bytes, int* dims) {
+    FQL_REBRAC_REFUSES(h, "fql_debug_workspace", "FQL workspaces only");
     if (!h || !out) return FQL_E_INVALID;
     const int B = h->B, ic = h->nets[NET_OS].in_p(), ib = h->nets[NET_BC].in_p(), ap = pad16(h->cfg.act_dim);
     const void* src = nullptr;
@@ -4650,8 +5051,9 @@ int fql_group_create(const fql_handle* members, int k, fql_group* out) {
     if (!out) { g_create_error = "fql_group_create: out must not be NULL"; return FQL_E_INVALID; }
     *out = nullptr;
     for (int i = 0; members && i < k; ++i)
-        if (members[i] && members[i]->ifql) {
-            g_create_error = "fql_group_create: member " + std::to_string(i) + " is an IFQL handle (groups take FQL agents only)";
+        if (members[i] && (members[i]->ifql || members[i]->rebrac)) {
+            g_create_error = "fql_group_create: member " + std::to_string(i) + (members[i]->ifql ? " is an IFQL handle" : " is a ReBRAC handle") +
+                             " (groups take FQL agents only)";
             return FQL_E_STATE;
         }
     auto* g = new fql_group_s();

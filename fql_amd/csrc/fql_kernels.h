@@ -1876,6 +1876,9 @@ struct SrcDesc {  // where the batch comes from; rewritten by the host only when
     int split;
     const float *obs2, *act2, *rew2, *mask2, *nobs2;
     int64_t lo2, span2;
+    // ReBRAC only (fql_rebrac.h): next_actions.  nact_rows > 0: the dataset's actions, row min(idx + 1, nact_rows - 1); 0: row b of nact
+    const float* nact;
+    int64_t nact_rows;
 };
 
 struct PrepArgs {

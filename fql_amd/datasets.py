@@ -40,6 +40,7 @@ class Dataset(dict):
         self._agent = None
         self.frame_stack = None   # number of frames to stack; set outside the class (utils/datasets.py:54, main.py:120)
         self.p_aug = None         # image augmentation probability; set outside the class (utils/datasets.py:55, main.py:121)
+        self.return_next_actions = False   # also return next_actions (ReBRAC); set outside the class (utils/datasets.py:58)
         if 'terminals' in self:   # utils/datasets.py:58-62
             self.terminal_locs = np.nonzero(np.asarray(self['terminals']) > 0)[0]
             self.initial_locs = np.concatenate([[0], self.terminal_locs[:-1] + 1]).astype(np.int64)
@@ -49,8 +50,12 @@ class Dataset(dict):
         return np.random.randint(self.size, size=num_idxs)
 
     def get_subset(self, idxs):
-        """utils/datasets.py:94-100."""
-        return {k: v[idxs] for k, v in self.items()}
+        """utils/datasets.py:94-100.  With return_next_actions: next_actions = actions[min(idxs + 1, size - 1)], which (as the reference
+        warns) is the NEXT episode's first action at the end of a trajectory."""
+        result = {k: v[idxs] for k, v in self.items()}
+        if self.return_next_actions:
+            result['next_actions'] = self['actions'][np.minimum(np.asarray(idxs) + 1, self.size - 1)]
+        return result
 
     def sample(self, batch_size: int, idxs=None):
         """utils/datasets.py:68-92."""

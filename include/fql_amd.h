@@ -323,6 +323,63 @@ int fql_ifql_create(const fql_config* cfg, const fql_ifql_config* icfg, uint64_t
 int fql_num_info(fql_handle h);
 const char* fql_handle_info_name(fql_handle h, int i);
 
+/* ---- ReBRAC: revisited behavior-regularized actor-critic (agents/rebrac.py), TD3+BC with LayerNorm, on the same engine ----
+ * State observations and fp32 only.  Networks (agents/rebrac.py:182-213): "modules_critic/value_net/..." and
+ * "modules_target_critic/value_net/..." (FQL's stacked [2, ...] critic), "modules_actor/actor_net/Dense_0..n-1" (+ "LayerNorm_i" with
+ * actor_layer_norm) and "modules_actor/mean_net/{bias,kernel}" (utils/networks.py:82-150, const_std: no log-std leaves), and the same
+ * under "modules_target_actor".  Glorot-uniform kernels except mean_net's, variance_scaling(actor_fc_scale, fan_avg, uniform); zero
+ * biases; both targets are copies at create.
+ *
+ * Two kinds of update (main.py:207-208): full_update != 0 = critic + actor loss, Adam, Polyak of both targets from the PRE-step critic
+ * and actor; full_update == 0 = the critic-only step: the actor's gradient is zero, Adam still runs over every leaf (mu / nu decay, the
+ * actor still moves when mu != 0, count and step advance), no Polyak.  Info buffers stay 13 floats:
+ *   full step (fql_handle_info_name, 12 keys): 0 critic/critic_loss 1 critic/q_mean 2 critic/q_max 3 critic/q_min 4 actor/total_loss
+ *     5 actor/actor_loss 6 actor/bc_loss 7 actor/std 8 actor/mse 9 grad/max 10 grad/min 11 grad/norm; 12 is 0;
+ *   critic-only step (7 keys): 0-3 the critic keys, 4 grad/max 5 grad/min 6 grad/norm; 7-12 are 0.
+ * The grad statistics run over the whole tree: target leaves, and the actor's on critic-only steps, count with zero gradients.
+ * fql_noise: only eps1 is read, the raw N(0, 1) [B, act] of the target-policy noise before actor_noise scaling (agents/rebrac.py:30-34);
+ * any other non-NULL pointer is FQL_E_INVALID.  NULL = the engine's Philox stream.
+ * next_actions: explicit [B, act] in fql_rebrac_update / fql_rebrac_total_loss; fql_rebrac_update_from_dataset gathers
+ * actions[min(idx + 1, size - 1)] with `size` the dataset's current row count (utils/datasets.py:96-100, including its end-of-episode quirk).
+ * A ReBRAC handle is an ordinary fql_handle for destroy, set_batch_size, leaf / param / opt-state / step access, dataset upload / add /
+ * reserve / size, fql_sample_actions (temperature 1), info enqueue / wait, fql_read_info, fql_synchronize, fql_stats (the full step)
+ * and fql_stream.  Refused: encoder != 0 or precision != 0 at create (FQL_E_INVALID); on a ReBRAC handle fql_update,
+ * fql_update_from_dataset and fql_total_loss (no next_actions / step kind), fql_update_begin* / _end*, fql_grad_buckets, frame uploads /
+ * updates, fql_noise_from_jax_keys, the replay ring, balanced sampling and fql_flow_actions return FQL_E_STATE, and fql_group_create
+ * with a ReBRAC member returns FQL_E_STATE.  The fql_rebrac_* calls on another handle return FQL_E_STATE. */
+#define FQL_REBRAC_NUM_INFO 12
+#define FQL_REBRAC_CRITIC_NUM_INFO 7
+typedef struct fql_rebrac_config {
+    float alpha_actor;       /* actor BC coefficient (0.0)                     */
+    float alpha_critic;      /* critic BC coefficient (0.0)                    */
+    float actor_noise;       /* target-policy / sampling noise scale (0.2)     */
+    float actor_noise_clip;  /* noise clip (0.5)                               */
+    int32_t tanh_squash;     /* mode = tanh(mean) (1) or mean (0)              */
+    float actor_fc_scale;    /* mean_net kernel init scale (0.01)              */
+    int32_t reserved[6];
+} fql_rebrac_config;
+void fql_rebrac_default_config(fql_rebrac_config* c);
+int fql_rebrac_create(const fql_config* cfg, const fql_rebrac_config* rcfg, uint64_t seed, fql_handle* out);
+/* ReBRACAgent.update(batch, full_update)  agents/rebrac.py:122-134.  info13 as fql_update's (layout above). */
+int fql_rebrac_update(fql_handle h, const float* observations, const float* actions, const float* rewards, const float* masks,
+                      const float* next_observations, const float* next_actions, int batch_size, const fql_noise* noise,
+                      int full_update, float* info13, void* stream);
+/* train_dataset.sample(B) + update(batch, full_update) on the device; idx / lo / hi as fql_update_from_dataset's. */
+int fql_rebrac_update_from_dataset(fql_handle h, const int64_t* idx, int batch_size, int64_t lo, int64_t hi, const fql_noise* noise,
+                                   int full_update, float* info13, void* stream);
+/* ReBRACAgent.total_loss(batch, full_update)  agents/rebrac.py:86-108: pure forward, no state change.  loss = critic_loss (+ the actor's
+ * total_loss when full_update); info10 receives the first 9 infos of the full layout (4 when !full_update).  Synchronous. */
+int fql_rebrac_total_loss(fql_handle h, const float* observations, const float* actions, const float* rewards, const float* masks,
+                          const float* next_observations, const float* next_actions, int batch_size, const fql_noise* noise,
+                          int full_update, float* loss, float* info10, void* stream);
+/* ReBRACAgent.sample_actions(observations, seed, temperature)  agents/rebrac.py:136-152:
+ * clip(mode + clip(N(0, 1) actor_noise temperature, +-actor_noise_clip), -1, 1).  noise [n, act] raw N(0, 1) or NULL (engine RNG keyed
+ * by `seed`); rows of one call equal single calls with the same noise rows.  fql_sample_actions == this with temperature 1. */
+int fql_rebrac_sample_actions(fql_handle h, const float* observations, int n, const float* noise, uint64_t seed, float temperature,
+                              float* out, void* stream);
+/* launches and algorithmic MACs of one full (full_update != 0) or critic-only update */
+int fql_rebrac_stats(fql_handle h, int full_update, int64_t* launches_per_update, int64_t* macs_per_update);
+
 #ifdef __cplusplus
 }
 #endif
