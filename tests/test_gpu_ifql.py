@@ -6,7 +6,7 @@ import pytest
 
 from oracle import fql_oracle as O
 from tests import ifql_oracle as IO
-from tests.util import assert_info_close, leaf_dict, make_problem, randomize_params
+from tests.util import assert_info_close, leaf_dict, make_problem, randomize_params, sync_restatement
 
 pytestmark = pytest.mark.gpu
 OD, AD = 29, 8
@@ -69,13 +69,9 @@ def test_leaves_match_reference_layout_and_init():
             np.testing.assert_array_equal(v, p[k.replace('modules_target_critic/', 'modules_critic/')])
 
 
-@pytest.mark.parametrize('H,B', [(64, 64), (512, 256)])
-def test_one_update_matches_fp64_restatement(H, B):
-    cfg, _, batch, noise = _problem(H, B, seed=1)
-    a = _agent(cfg, batch)
-    params = _randomized(a.get_params(), 5)
-    a.set_params(params)
-    ref = IO.OracleIFQL(params, dict(cfg), OD, AD, np.float64)
+def _check_first_update(a, ref, cfg, params, batch, noise):
+    """One update from zero moments on both sides: the 12 infos, every leaf's gradient (Adam mu / 0.1), nu, post-step params, and Polyak
+    from the pre-step critic.  Returns the worst max|g_gpu - g_ref| / max|g_ref| over the leaves."""
     _, _, g_ref = ref.grads(batch, noise)
     _, info = a.update(batch, noise=noise)
     info = info.to_dict()
@@ -87,8 +83,10 @@ def test_one_update_matches_fp64_restatement(H, B):
     assert opt['count'] == 1 and opt['step'] == 2
     mu, nu = leaf_dict(opt['mu']), leaf_dict(opt['nu'])
     new, new_ref = leaf_dict(a.get_params()), leaf_dict(ref.params)
+    worst = (0.0, None)
     for p, g in leaf_dict(g_ref).items():
         tol = 2e-5 * np.abs(g).max() + 1e-9
+        worst = max(worst, (float(np.abs(mu[p] / 0.1 - g).max() / max(np.abs(g).max(), 1e-30)), p))
         np.testing.assert_allclose(mu[p] / 0.1, g, rtol=0, atol=tol, err_msg=f'grad {p}')
         np.testing.assert_allclose(nu[p] / 0.001, g * g, rtol=1e-4, atol=tol * np.abs(g).max() + 1e-12, err_msg=f'nu {p}')
         d = np.abs(new[p] - new_ref[p])
@@ -100,14 +98,11 @@ def test_one_update_matches_fp64_restatement(H, B):
             stable = np.abs(g) > 50 * tol
             assert d[stable].max(initial=0) <= 2e-6, (p, d[stable].max())
             assert d.max() <= 2 * cfg['lr'] + 1e-6, p
+    return worst
 
 
-def test_total_loss_matches_and_changes_no_state():
-    cfg, _, batch, noise = _problem(seed=2)
-    a = _agent(cfg, batch)
-    params = _randomized(a.get_params(), 6)
-    a.set_params(params)
-    ref = IO.OracleIFQL(params, dict(cfg), OD, AD, np.float64)
+def _check_total_loss(a, ref, params, batch, noise):
+    """total_loss on both sides (9 infos, the loss); no parameter or optimizer state changes."""
     loss, info = a.total_loss(batch, noise=noise)
     want_loss, want = ref.total_loss(batch, noise)
     assert tuple(info) == IO.INFO_KEYS[:9]
@@ -118,6 +113,25 @@ def test_total_loss_matches_and_changes_no_state():
     for k, v in leaf_dict(params).items():
         np.testing.assert_array_equal(after[k], v, err_msg=k)
     assert a.get_opt_state()['count'] == 0
+
+
+@pytest.mark.parametrize('H,B', [(64, 64), (512, 256)])
+def test_one_update_matches_fp64_restatement(H, B):
+    cfg, _, batch, noise = _problem(H, B, seed=1)
+    a = _agent(cfg, batch)
+    params = _randomized(a.get_params(), 5)
+    a.set_params(params)
+    ref = IO.OracleIFQL(params, dict(cfg), OD, AD, np.float64)
+    _check_first_update(a, ref, cfg, params, batch, noise)
+
+
+def test_total_loss_matches_and_changes_no_state():
+    cfg, _, batch, noise = _problem(seed=2)
+    a = _agent(cfg, batch)
+    params = _randomized(a.get_params(), 6)
+    a.set_params(params)
+    ref = IO.OracleIFQL(params, dict(cfg), OD, AD, np.float64)
+    _check_total_loss(a, ref, params, batch, noise)
 
 
 def test_trajectory_100_updates_tracks_restatement():
@@ -296,3 +310,142 @@ def test_refusals_return_documented_codes():
     assert lib.fql_ifql_create(C.byref(c), C.byref(ic), 0, C.byref(out)) == _cabi.FQL_E_INVALID
     a.update(batch, noise=noise)   # the handle still works after the refusals
     a.synchronize()
+
+
+# ---- shapes, configs, chunked sampling and batch-size switches -------------------------------------------------------------------------
+
+SHAPE_CASES = [
+    # od, ad, B, actor hidden, value hidden, cfg overrides
+    pytest.param(7, 3, 16, (32,) * 4, (32,) * 4, {}, id='small'),
+    pytest.param(29, 8, 32, (64, 64), (48, 80, 64), {}, id='ragged_depths'),
+    pytest.param(11, 5, 48, (64,) * 4, (64,) * 4, dict(layer_norm=False), id='no_layer_norm'),
+    pytest.param(17, 6, 64, (64,) * 4, (64,) * 4, dict(actor_layer_norm=True, expectile=0.7, discount=0.995), id='actor_ln_expectile'),
+    pytest.param(69, 21, 256, (512,) * 4, (512,) * 4, dict(discount=0.995), id='humanoidmaze'),
+    pytest.param(40, 4, 1024, (512,) * 4, (512,) * 4, {}, id='b1024'),   # the value pass runs at M = 2048
+]
+
+
+def _problem_at(od, ad, B, actor, value, seed, **kw):
+    import fql_amd
+    _, ds, batch, noise = make_problem(od, ad, B, value, seed=seed)
+    cfg = fql_amd.ifql.get_config()
+    cfg.update(actor_hidden_dims=tuple(actor), value_hidden_dims=tuple(value), batch_size=B)
+    cfg.update(kw)
+    return cfg, ds, batch, {'x0': noise['x0'], 't': noise['t']}
+
+
+@pytest.mark.parametrize('od,ad,B,actor,value,kw', SHAPE_CASES)
+def test_total_loss_and_update_across_shapes_and_configs(od, ad, B, actor, value, kw):
+    cfg, _, batch, noise = _problem_at(od, ad, B, actor, value, seed=11, **kw)
+    a = _agent(cfg, batch)
+    params = _randomized(a.get_params(), 12)
+    a.set_params(params)
+    ref = IO.OracleIFQL(params, dict(cfg), od, ad, np.float64)
+    _check_total_loss(a, ref, params, batch, noise)
+    worst = _check_first_update(a, ref, cfg, params, batch, noise)
+    print(f'worst relative gradient error {worst[0]:.3e} ({worst[1]})')
+
+
+def _best_of_n(ref, obs, noises):
+    """OracleIFQL.sample_actions for every row of obs [n, od] at once: the flow of each of the N noises, min(q1, q2), the first argmax.
+    Returns the chosen actions [n, act], every candidate [n, N, act] and their scores [n, N]."""
+    n, N, ad = noises.shape
+    rep = np.repeat(obs, N, axis=0)
+    acts = ref.compute_flow_actions(rep, noises.reshape(n * N, ad))
+    q = ref._critic('modules_critic', rep, acts, stored=True).min(axis=0).reshape(n, N)
+    acts = acts.reshape(n, N, ad)
+    return acts[np.arange(n), np.argmax(q, axis=1)], acts, q
+
+
+@pytest.mark.parametrize('N,n', [(1, 4097), (7, 590), (65, 64), (100, 42)])
+def test_sample_actions_across_the_row_chunk(N, n):
+    """n x N sample rows cross the 4096-row chunk (4096 // N observations per chunk; at N = 65 the select kernel's lanes loop).  Rows with a
+    clear winner (top two scores more than 1e-2 apart, the margin of test_sample_actions_best_of_n_and_flow_actions) must pick the
+    restatement's action; the others one of the candidates within 1e-2 of the best score.  Then the seeded draw's chunk keying."""
+    od, ad = 69, 21
+    cfg, _, batch, _ = _problem_at(od, ad, 64, (64,) * 4, (64,) * 4, seed=13, num_samples=N)
+    params = _randomized(IO.init_params(8, od, ad, cfg), 8)
+    a = _agent(cfg, batch, params=params)
+    ref = IO.OracleIFQL(params, dict(cfg), od, ad, np.float64)
+    rng = np.random.default_rng(N)
+    obs = rng.standard_normal((n, od)).astype(np.float32)
+    noises = (2.0 * rng.standard_normal((n, N, ad))).astype(np.float32)
+    want, cand, q = _best_of_n(ref, obs, noises)
+    for i in (0, n - 1):   # the batched restatement is OracleIFQL.sample_actions row by row
+        w, qi = ref.sample_actions(obs[i], noises[i])
+        np.testing.assert_allclose(want[i], w, rtol=0, atol=1e-12)
+        np.testing.assert_allclose(q[i], qi, rtol=0, atol=1e-12)
+    got = a.sample_actions(obs, noises=noises)
+    assert got.shape == (n, ad) and np.abs(got).max() <= 1.0
+    qs = np.sort(q, axis=1)
+    clear = qs[:, -1] - qs[:, -2] > 1e-2 if N > 1 else np.ones(n, bool)
+    assert clear.mean() >= 0.5, clear.mean()
+    np.testing.assert_allclose(got[clear], want[clear], atol=2e-5)
+    for i in np.nonzero(~clear)[0]:
+        near = q[i] >= q[i].max() - 1e-2
+        assert np.abs(cand[i][near] - got[i]).max(axis=1).min() <= 2e-5, i
+    np.testing.assert_array_equal(got[n - 1], a.sample_actions(obs[n - 1], noises=noises[n - 1]))   # the second chunk's last row
+    per = 4096 // N
+    same = np.repeat(obs[:1], per + 1, axis=0)
+    drawn = a.sample_actions(same, seed=5)
+    assert np.abs(drawn).max() <= 1.0
+    assert np.abs(drawn[per] - drawn[0]).max() > 1e-3   # the second chunk's first observation draws its own noises
+    np.testing.assert_array_equal(drawn[:per], a.sample_actions(same[:per], seed=5))
+
+
+def _check_step(a, ref, cfg, batch, noise, pre):
+    """One more update, moments carried from earlier steps: test_gpu_rebrac._check_step's bounds.  The gradient is (mu - 0.9 mu0) / 0.1;
+    the targets are Polyak of the engine's own pre-step critic and target."""
+    _, _, g_ref = ref.grads(batch, noise)
+    mu0 = leaf_dict(a.get_opt_state()['mu'])
+    pre_ref = leaf_dict(O.tree_map(np.copy, ref.params))
+    _, info = a.update(batch, noise=noise)
+    info = info.to_dict()
+    assert tuple(info) == IO.INFO_KEYS
+    _, want = ref.update(batch, noise)
+    assert_info_close(info, want, rtol=5e-5, atol=5e-6, keys=IO.INFO_KEYS)
+    a.synchronize()
+    opt = a.get_opt_state()
+    mu, nu, mu_ref, nu_ref = leaf_dict(opt['mu']), leaf_dict(opt['nu']), leaf_dict(ref.mu), leaf_dict(ref.nu)
+    new, new_ref = leaf_dict(a.get_params()), leaf_dict(ref.params)
+    for p, g in leaf_dict(g_ref).items():
+        if p.startswith('modules_target_critic/'):
+            np.testing.assert_allclose(new[p], 0.005 * pre[p.replace('target_critic', 'critic')] + 0.995 * pre[p], atol=1e-6, err_msg=p)
+            continue
+        tol = 2e-5 * np.abs(g).max() + 1e-5 * np.abs(mu0[p]).max() + 1e-9
+        np.testing.assert_allclose((mu[p] - np.float32(0.9) * mu0[p]) / 0.1, g, rtol=0, atol=tol, err_msg=f'grad {p}')
+        np.testing.assert_allclose(nu[p], nu_ref[p], rtol=1e-4, atol=1e-4 * np.abs(nu_ref[p]).max() + 1e-20, err_msg=f'nu {p}')
+        d = np.abs((new[p] - pre[p]) - (new_ref[p] - pre_ref[p]))
+        stable = (np.abs(g) > 50 * tol) & (np.abs(mu_ref[p]) > 5 * tol)
+        assert d[stable].max(initial=0) <= 2e-6, (p, d[stable].max())
+        assert d.max() <= 2 * cfg['lr'] + 1e-6, p
+
+
+def test_batch_size_switches_track_restatement():
+    """B = 64, 32, 64: each switch rebuilds the workspace and programs; every step is compared after the rebuild, from the engine's own
+    pre-step state (sync_restatement).  Then update_from_dataset after a switch equals update on the same rows, bitwise."""
+    cfg, ds, batch, _ = _problem_at(OD, AD, 64, (64,) * 4, (64,) * 4, seed=14)
+    a = _agent(cfg, batch)
+    params = _randomized(a.get_params(), 15)
+    a.set_params(params)
+    ref = IO.OracleIFQL(params, dict(cfg), OD, AD, np.float64)
+    rng = np.random.default_rng(14)
+    steps = []
+    for i, B in enumerate((64, 32, 64)):
+        idx = rng.integers(0, len(ds['observations']), size=B)
+        noise = {'x0': rng.standard_normal((B, AD)).astype(np.float32), 't': rng.random(B).astype(np.float32)}
+        steps.append((idx, noise))
+        print('step at B', B)
+        assert a.get_opt_state()['count'] == i
+        sync_restatement(ref, a)
+        _check_step(a, ref, cfg, O.sample_batch(ds, idx), noise, leaf_dict(a.get_params()))
+    opt = a.get_opt_state()
+    assert opt['count'] == 3 and opt['step'] == 4
+    x, y = _agent(cfg, ds, params=params), _agent(cfg, ds, params=params)
+    x.upload_dataset(ds)
+    for idx, noise in steps:
+        x.update_from_dataset(batch_size=len(idx), idxs=idx, noise=noise)
+        y.update(O.sample_batch(ds, idx), noise=noise)
+    x.synchronize(); y.synchronize()
+    _same_state(x, y)
+    assert x.read_info() == y.read_info()

@@ -10,7 +10,8 @@ import numpy as np
 import pytest
 
 from oracle import fql_oracle as O
-from tests.util import assert_info_close, leaf_dict, make_problem, randomize_params
+from tests.util import (assert_info_close, assert_step_matches, assert_total_loss_matches, assert_trajectory_tracks_oracle, leaf_dict,
+                        make_problem, randomize_params)
 
 pytestmark = pytest.mark.gpu
 
@@ -45,35 +46,8 @@ def test_total_loss_and_update_match_oracle(od, ad, B, hidden, kw):
         np.testing.assert_array_equal(got_back[p], a, err_msg=p)   # set/get round trip is exact
 
     ref = O.OracleFQL(params, dict(cfg), od, ad, np.float64)
-    loss_ref, info_ref = ref.total_loss(batch, noise)
-    loss, info = agent.total_loss(batch, noise=noise)
-    assert abs(loss - float(loss_ref)) <= 2e-6 + 2e-5 * abs(float(loss_ref))
-    assert_info_close(info, info_ref, keys=O.INFO_KEYS[:10])
-    # total_loss must not change any state
-    for p, a in leaf_dict(agent.get_params()).items():
-        np.testing.assert_array_equal(a, leaf_dict(params)[p], err_msg=p)
-
-    _, _, g_ref = ref.grads(batch, noise)
-    _, info_u = agent.update(batch, noise=noise)
-    _, info_ru = ref.update(batch, noise)
-    assert_info_close(info_u, info_ru, rtol=5e-5, atol=5e-6)
-    opt = agent.get_opt_state()
-    assert opt['count'] == 1 and opt['step'] == 2
-    mu = leaf_dict(opt['mu']); nu = leaf_dict(opt['nu'])
-    new = leaf_dict(agent.get_params()); new_ref = leaf_dict(ref.params)
-    lr = cfg['lr']
-    for p, g in leaf_dict(g_ref).items():
-        scale = np.abs(g).max()
-        tol = 2e-5 * scale + 1e-9
-        np.testing.assert_allclose(mu[p] / 0.1, g, rtol=0, atol=tol, err_msg=f'grad {p}')
-        np.testing.assert_allclose(nu[p] / 0.001, g * g, rtol=1e-4, atol=tol * scale + 1e-12, err_msg=f'nu {p}')
-        d = np.abs(new[p] - new_ref[p])
-        stable = np.abs(g) > 50 * tol
-        if 'target' in p:
-            assert d.max() <= 1e-6, p
-        else:
-            assert d[stable].max(initial=0) <= 2e-6, (p, d[stable].max())
-            assert d.max() <= 2 * lr + 1e-6, p
+    assert_total_loss_matches(agent, ref, params, batch, noise)
+    assert_step_matches(agent, ref, cfg, batch, noise)
 
 
 def test_polyak_reads_pre_step_critic():
@@ -89,21 +63,7 @@ def test_polyak_reads_pre_step_critic():
 
 
 def test_multi_step_trajectory_tracks_oracle():
-    od, ad, B = 29, 8, 64
-    cfg, ds, batch, noise = make_problem(od, ad, B, (64, 64, 64, 64), seed=21)
-    agent = _agent(cfg, batch)
-    params = agent.get_params()
-    ref = O.OracleFQL(params, dict(cfg), od, ad, np.float32)
-    rng = np.random.default_rng(0)
-    for s in range(20):
-        idx = rng.integers(0, len(ds['observations']), size=B)
-        b = O.sample_batch(ds, idx)
-        nz = O.make_noise(B, ad, 100 + s)
-        _, ig = agent.update(b, noise=nz)
-        _, ir = ref.update(b, nz)
-        assert_info_close(ig, ir, rtol=2e-3, atol=2e-4)
-    opt = agent.get_opt_state()
-    assert opt['count'] == 20 and opt['step'] == 21
+    assert_trajectory_tracks_oracle(29, 8, 64, (64, 64, 64, 64), seed=21)
 
 
 def test_full_size_config_one_update():

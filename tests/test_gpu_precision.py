@@ -49,10 +49,12 @@ CASES = [
     (29, 8, 64, (64, 64, 64, 64), 10.0, {}),                            # single-chunk tiles, generic Euler path
     (17, 6, 32, (80, 48, 64, 32), 10.0, {}),                            # ragged widths
     (29, 8, 64, (128, 128, 128, 128), 10.0, dict(q_agg='min', actor_layer_norm=True, normalize_q_loss=True)),
+    (69, 21, 256, (512, 512, 512, 512), 30.0, dict(discount=0.995)),   # humanoidmaze: no Euler chain, generic dgrad, ap = 32
 ]
 
 
-@pytest.mark.parametrize('od,ad,B,hidden,alpha,kw', CASES, ids=['configs1', 'configs2', 'h256', 'h64', 'ragged', 'ln_min_norm'])
+@pytest.mark.parametrize('od,ad,B,hidden,alpha,kw', CASES, ids=['configs1', 'configs2', 'h256', 'h64', 'ragged', 'ln_min_norm',
+                                                                     'humanoidmaze'])
 def test_bf16x3_update_within_the_loss_bound_of_the_oracle(od, ad, B, hidden, alpha, kw):
     worst, deltas = _one_update(od, ad, B, hidden, alpha, 'bf16x3', **kw)
     assert max(deltas.values()) <= 1e-4, deltas          # north_star: losses within 1e-4 (relative to max(1, |ref|))

@@ -6,7 +6,7 @@ import pytest
 
 from oracle import fql_oracle as O
 from tests import rebrac_oracle as RO
-from tests.util import assert_info_close, leaf_dict
+from tests.util import assert_info_close, leaf_dict, sync_restatement
 
 pytestmark = pytest.mark.gpu
 OD, AD = 29, 8
@@ -95,6 +95,7 @@ def _check_step(a, ref, batch, noise, full, cfg, pre):
     opt = a.get_opt_state()
     mu, nu, mu_ref, nu_ref = leaf_dict(opt['mu']), leaf_dict(opt['nu']), leaf_dict(ref.mu), leaf_dict(ref.nu)
     new, new_ref = leaf_dict(a.get_params()), leaf_dict(ref.params)
+    worst = (0.0, None)
     for p, g in leaf_dict(g_ref).items():
         if p.startswith('modules_target_'):
             if full:   # Polyak from the PRE-step online module
@@ -103,6 +104,8 @@ def _check_step(a, ref, batch, noise, full, cfg, pre):
                 np.testing.assert_array_equal(new[p], pre[p], err_msg=p)
             continue
         tol = 2e-5 * np.abs(g).max() + 1e-5 * np.abs(mu0[p]).max() + 1e-9   # (mu0's fp32 decay rounds at ~1e-7 relative)
+        if np.abs(g).max() > 0:
+            worst = max(worst, (float(np.abs((mu[p] - np.float32(0.9) * mu0[p]) / 0.1 - g).max() / np.abs(g).max()), p))
         np.testing.assert_allclose((mu[p] - np.float32(0.9) * mu0[p]) / 0.1, g, rtol=0, atol=tol, err_msg=f'grad {p}')
         np.testing.assert_allclose(nu[p], nu_ref[p], rtol=1e-4, atol=1e-4 * np.abs(nu_ref[p]).max() + 1e-20, err_msg=f'nu {p}')
         d = np.abs((new[p] - pre[p]) - (new_ref[p] - pre_ref[p]))   # this step's increment (an earlier ill-conditioned step's difference stays)
@@ -111,6 +114,7 @@ def _check_step(a, ref, batch, noise, full, cfg, pre):
         stable = (np.abs(g) > 50 * tol) & (np.abs(mu_ref[p]) > 5 * tol)
         assert d[stable].max(initial=0) <= 2e-6, (p, d[stable].max())
         assert d.max() <= 2 * cfg['lr'] + 1e-6, p
+    return worst
 
 
 @pytest.mark.parametrize('H,B', [(64, 64), (512, 256)])
@@ -132,12 +136,8 @@ def test_full_then_critic_only_update_match_fp64_restatement(H, B):
     assert moved, 'a critic-only step moves the actor through Adam momentum'
 
 
-def test_total_loss_matches_and_changes_no_state():
-    cfg, _, batch, noise = _problem(seed=2)
-    a = _agent(cfg, batch)
-    params = _randomized(a.get_params(), 6)
-    a.set_params(params)
-    ref = RO.OracleReBRAC(params, dict(cfg), OD, AD, np.float64)
+def _check_total_loss(a, ref, params, batch, noise):
+    """total_loss of both step kinds on both sides (infos, the loss); no parameter or optimizer state changes."""
     for full in (True, False):
         loss, info = a.total_loss(batch, noise=noise, full_update=full)
         want_loss, want = ref.total_loss(batch, noise, full_update=full)
@@ -150,6 +150,15 @@ def test_total_loss_matches_and_changes_no_state():
     for k, v in leaf_dict(params).items():
         np.testing.assert_array_equal(after[k], v, err_msg=k)
     assert a.get_opt_state()['count'] == 0
+
+
+def test_total_loss_matches_and_changes_no_state():
+    cfg, _, batch, noise = _problem(seed=2)
+    a = _agent(cfg, batch)
+    params = _randomized(a.get_params(), 6)
+    a.set_params(params)
+    ref = RO.OracleReBRAC(params, dict(cfg), OD, AD, np.float64)
+    _check_total_loss(a, ref, params, batch, noise)
 
 
 def test_trajectory_100_updates_on_actor_freq_schedule():
@@ -352,3 +361,92 @@ def test_refusals_return_documented_codes():
     a.update(batch, noise=noise)   # the handle still works after the refusals
     a.update(batch, full_update=False, noise=noise)
     a.synchronize()
+
+
+# ---- shapes, configs, chunked sampling and batch-size switches -------------------------------------------------------------------------
+
+SHAPE_CASES = [
+    # od, ad, B, actor hidden, value hidden, cfg overrides (on top of _cfg's alpha_actor 0.5, alpha_critic 0.3)
+    pytest.param(7, 3, 16, (32,) * 4, (32,) * 4, {}, id='small'),
+    pytest.param(29, 8, 32, (64, 64), (48, 80, 64), {}, id='ragged_depths'),
+    pytest.param(11, 5, 48, (64,) * 4, (64,) * 4, dict(tanh_squash=False), id='no_tanh'),
+    pytest.param(17, 6, 64, (64,) * 4, (64,) * 4, dict(actor_layer_norm=True, layer_norm=False), id='actor_ln_no_critic_ln'),
+    pytest.param(69, 21, 256, (512,) * 4, (512,) * 4, dict(alpha_actor=0.01, alpha_critic=0.01, discount=0.995), id='humanoidmaze'),
+    pytest.param(29, 16, 256, (512,) * 4, (512,) * 4, {}, id='act16'),               # OP_DGRAD0 with a full 16-column action block
+    # the reference's default alphas; obs + 16 > in_p = 48: the generic first-layer dgrad at H 512
+    pytest.param(40, 4, 1024, (512,) * 4, (512,) * 4, dict(alpha_actor=0.0, alpha_critic=0.0), id='b1024'),
+]
+
+
+def _problem_at(od, ad, B, actor, value, seed, **kw):
+    ds = O.make_synthetic_dataset(max(4 * B, 64), od, ad, seed=seed)
+    idx = np.random.default_rng(seed + 1).integers(0, len(ds['observations']), size=B)
+    cfg = _cfg(64, B, actor_hidden_dims=tuple(actor), value_hidden_dims=tuple(value), **kw)
+    return cfg, ds, RO.make_batch(ds, idx), RO.make_noise(B, ad, seed + 2)
+
+
+@pytest.mark.parametrize('od,ad,B,actor,value,kw', SHAPE_CASES)
+def test_total_loss_and_both_step_kinds_across_shapes_and_configs(od, ad, B, actor, value, kw):
+    """total_loss, a full step, then a critic-only step from the engine's post-step state (sync_restatement)."""
+    cfg, _, batch, noise = _problem_at(od, ad, B, actor, value, seed=21, **kw)
+    a = _agent(cfg, batch)
+    params = _randomized(a.get_params(), 22)
+    a.set_params(params)
+    ref = RO.OracleReBRAC(params, dict(cfg), od, ad, np.float64)
+    _check_total_loss(a, ref, params, batch, noise)
+    w_full = _check_step(a, ref, batch, noise, True, cfg, leaf_dict(params))
+    assert a.get_opt_state()['count'] == 1
+    sync_restatement(ref, a)
+    w_crit = _check_step(a, ref, batch, RO.make_noise(B, ad, 23), False, cfg, leaf_dict(a.get_params()))
+    print(f'worst relative gradient error: full step {w_full[0]:.3e} ({w_full[1]}), critic-only step {w_crit[0]:.3e} ({w_crit[1]})')
+
+
+def test_sample_actions_across_the_row_chunk():
+    """n = 4097 rows (one past the 4096-row chunk) with explicit noises at temperatures 1 and 0.3, then the seeded draw's chunk keying."""
+    od, ad, n = 69, 21, 4097
+    cfg, _, batch, _ = _problem_at(od, ad, 64, (512,) * 4, (512,) * 4, seed=24)
+    params = _randomized(RO.init_params(9, od, ad, cfg), 9, scale=0.05)
+    a = _agent(cfg, batch, params=params)
+    ref = RO.OracleReBRAC(params, dict(cfg), od, ad, np.float64)
+    rng = np.random.default_rng(24)
+    obs = rng.standard_normal((n, od)).astype(np.float32)
+    z = (3.0 * rng.standard_normal((n, ad))).astype(np.float32)
+    for temp in (1.0, 0.3):
+        got = a.sample_actions(obs, noises=z, temperature=temp)
+        assert got.shape == (n, ad) and np.abs(got).max() <= 1.0
+        np.testing.assert_allclose(got, ref.sample_actions(obs, z, temp), atol=2e-5, err_msg=str(temp))
+    same = np.repeat(obs[:1], n, axis=0)
+    drawn = a.sample_actions(same, seed=5)
+    assert np.abs(drawn).max() <= 1.0
+    assert np.abs(drawn[4096] - drawn[0]).max() > 1e-3   # the second chunk's first row draws its own noise
+    np.testing.assert_array_equal(drawn[:4096], a.sample_actions(same[:4096], seed=5))
+
+
+def test_batch_size_switches_track_restatement():
+    """B = 64, 32, 64: each switch rebuilds the workspace and both programs; every step is compared after the rebuild, from the engine's
+    own pre-step state (sync_restatement).  Then update_from_dataset after a switch equals update on the same rows, bitwise."""
+    cfg, ds, batch, _ = _problem(seed=25)
+    a = _agent(cfg, batch)
+    params = _randomized(a.get_params(), 26)
+    a.set_params(params)
+    ref = RO.OracleReBRAC(params, dict(cfg), OD, AD, np.float64)
+    rng = np.random.default_rng(25)
+    steps = []
+    for i, (B, full) in enumerate(((64, True), (32, False), (64, True))):
+        idx = rng.integers(0, len(ds['observations']), size=B)
+        noise = {'eps1': rng.standard_normal((B, AD)).astype(np.float32)}
+        steps.append((idx, noise, full))
+        print('step at B', B)
+        assert a.get_opt_state()['count'] == i
+        sync_restatement(ref, a)
+        _check_step(a, ref, RO.make_batch(ds, idx), noise, full, cfg, leaf_dict(a.get_params()))
+    opt = a.get_opt_state()
+    assert opt['count'] == 3 and opt['step'] == 4
+    x, y = _agent(cfg, ds, params=params), _agent(cfg, ds, params=params)
+    x.upload_dataset(ds)
+    for idx, noise, full in steps:
+        x.update_from_dataset(batch_size=len(idx), idxs=idx, noise=noise, full_update=full)
+        y.update(RO.make_batch(ds, idx), full_update=full, noise=noise)
+    x.synchronize(); y.synchronize()
+    _same_state(x, y)
+    assert x.read_info() == y.read_info()

@@ -11,9 +11,19 @@ from tests import ifql_oracle as IO
 OD, AD, B, H = 5, 3, 8, (8, 8)
 
 
-def _setup(seed=0):
+# the configurations of the GPU matrix (tests/test_gpu_ifql.py SHAPE_CASES) beside the default one
+CONFIGS = {
+    'no_layer_norm': dict(layer_norm=False),
+    'actor_ln': dict(actor_layer_norm=True),
+    'ragged_depths': dict(actor_hidden_dims=(9, 7), value_hidden_dims=(6, 10, 8)),
+    'expectile': dict(expectile=0.7, discount=0.995),
+}
+
+
+def _setup(seed=0, **kw):
     cfg = IO.get_config()
     cfg.update(actor_hidden_dims=H, value_hidden_dims=H)
+    cfg.update(kw)
     params = IO.init_params(seed, OD, AD, cfg, np.float64)
     rng = np.random.default_rng(seed + 1)
     for _, leaf in O.tree_leaves_with_path(params):
@@ -24,12 +34,25 @@ def _setup(seed=0):
     return cfg, params, batch, noise
 
 
-@pytest.mark.parametrize('path', ['modules_value/value_net/Dense_0/kernel', 'modules_value/value_net/LayerNorm_1/scale',
-                                  'modules_critic/value_net/Dense_1/kernel', 'modules_critic/value_net/Dense_2/bias',
-                                  'modules_actor_flow/mlp/Dense_0/kernel', 'modules_actor_flow/mlp/Dense_2/bias'])
-def test_gradients_match_finite_differences(path):
+FD_PATHS = {
+    None: ['modules_value/value_net/Dense_0/kernel', 'modules_value/value_net/LayerNorm_1/scale', 'modules_critic/value_net/Dense_1/kernel',
+           'modules_critic/value_net/Dense_2/bias', 'modules_actor_flow/mlp/Dense_0/kernel', 'modules_actor_flow/mlp/Dense_2/bias'],
+    'no_layer_norm': ['modules_value/value_net/Dense_1/kernel', 'modules_value/value_net/Dense_2/bias',
+                      'modules_critic/value_net/Dense_0/kernel', 'modules_critic/value_net/Dense_1/bias'],
+    'actor_ln': ['modules_actor_flow/mlp/LayerNorm_0/scale', 'modules_actor_flow/mlp/LayerNorm_1/bias', 'modules_actor_flow/mlp/Dense_1/kernel',
+                 'modules_actor_flow/mlp/Dense_2/kernel'],
+    'ragged_depths': ['modules_value/value_net/Dense_3/kernel', 'modules_value/value_net/LayerNorm_2/scale',
+                      'modules_critic/value_net/Dense_2/kernel', 'modules_critic/value_net/LayerNorm_0/bias',
+                      'modules_actor_flow/mlp/Dense_1/kernel', 'modules_actor_flow/mlp/Dense_2/bias'],
+    'expectile': ['modules_value/value_net/Dense_0/kernel', 'modules_value/value_net/Dense_2/bias', 'modules_value/value_net/LayerNorm_0/scale',
+                  'modules_critic/value_net/Dense_2/kernel'],
+}
+
+
+@pytest.mark.parametrize('conf,path', [pytest.param(c, p, id=p if c is None else f'{c}-{p}') for c, ps in FD_PATHS.items() for p in ps])
+def test_gradients_match_finite_differences(conf, path):
     """jax.grad of total_loss: value(next_obs) and the target critic are stored parameters (no gradient flows through them)."""
-    cfg, params, batch, noise = _setup()
+    cfg, params, batch, noise = _setup(**CONFIGS.get(conf, {}))
     ref = IO.OracleIFQL(params, cfg, OD, AD, np.float64)
     ref.frozen = O.tree_map(np.copy, ref.params)
     _, _, g = ref.grads(batch, noise)
@@ -110,12 +133,14 @@ def test_leaf_layout_value_unstacked_critic_stacked():
     assert 'modules_value/value_net/LayerNorm_3/scale' in p
 
 
-@pytest.mark.parametrize('dtype,rtol', [('float64', 1e-10), ('float32', 1e-6)])
-def test_numpy_and_torch_restatements_agree(dtype, rtol):
+@pytest.mark.parametrize('dtype,rtol,conf', [pytest.param('float64', 1e-10, None, id='float64-1e-10'),
+                                              pytest.param('float32', 1e-6, None, id='float32-1e-06')] +
+                         [pytest.param('float64', 1e-10, c, id=f'float64-1e-10-{c}') for c in CONFIGS])
+def test_numpy_and_torch_restatements_agree(dtype, rtol, conf):
     """tests/ifql_oracle.py (hand-derived backward) == tests/ifql_oracle_torch.py (autograd): infos, gradients, two updates."""
     import torch
     from tests import ifql_oracle_torch as IT
-    cfg, params, batch, noise = _setup(4)
+    cfg, params, batch, noise = _setup(4, **CONFIGS.get(conf, {}))
     npd, tdt = np.dtype(dtype), getattr(torch, dtype)
     params = O.tree_map(lambda a: a.astype(npd), params)
     batch = {k: v.astype(npd) for k, v in batch.items()}

@@ -30,13 +30,22 @@ def _setup(seed=0, **kw):
 PATHS = ['modules_critic/value_net/Dense_0/kernel', 'modules_critic/value_net/LayerNorm_1/scale', 'modules_critic/value_net/Dense_2/bias',
          'modules_actor/actor_net/Dense_0/kernel', 'modules_actor/actor_net/LayerNorm_1/bias', 'modules_actor/mean_net/kernel',
          'modules_actor/mean_net/bias']
+# the configurations of the GPU matrix (tests/test_gpu_rebrac.py SHAPE_CASES) beside the default one, with the leaves they add
+CONFIGS = {
+    'no_layer_norm': (dict(layer_norm=False), ['modules_critic/value_net/Dense_1/kernel']),
+    'ragged_depths': (dict(actor_hidden_dims=(9, 7), value_hidden_dims=(6, 10, 8)),
+                      ['modules_critic/value_net/Dense_3/kernel', 'modules_critic/value_net/LayerNorm_2/bias',
+                       'modules_actor/actor_net/Dense_1/kernel']),
+}
+CASES = [pytest.param(full, tanh, conf, id=f'{full}-{tanh}' if conf is None else f'{conf}-{full}-{tanh}')
+         for conf in [None] + list(CONFIGS) for tanh in (True, False) for full in (True, False)]
 
 
-@pytest.mark.parametrize('tanh_squash', [True, False])
-@pytest.mark.parametrize('full', [True, False])
-def test_gradients_match_finite_differences(full, tanh_squash):
+@pytest.mark.parametrize('full,tanh_squash,conf', CASES)
+def test_gradients_match_finite_differences(full, tanh_squash, conf):
     """jax.grad of total_loss: targets and the actor loss's critic are stored parameters; lam is a stop_gradient (held fixed here)."""
-    cfg, params, batch, noise = _setup(tanh_squash=tanh_squash)
+    kw, extra = CONFIGS.get(conf, ({}, []))
+    cfg, params, batch, noise = _setup(tanh_squash=tanh_squash, **kw)
     ref = RO.OracleReBRAC(params, cfg, OD, AD, np.float64)
     ref.frozen = O.tree_map(np.copy, ref.params)
     _, info, g = ref._losses(batch, noise, want_grads=True, full_update=full)
@@ -44,7 +53,7 @@ def test_gradients_match_finite_differences(full, tanh_squash):
         ref.lam_override = info['_lam']
     leaves, grads = dict(O.tree_leaves_with_path(ref.params)), dict(O.tree_leaves_with_path(g))
     rng = np.random.default_rng(3)
-    for path in PATHS:
+    for path in [p for p in PATHS + extra if p in leaves]:
         leaf, want = leaves[path], grads[path]
         if not full and path.startswith('modules_actor/'):
             assert not want.any(), path   # critic-only step: the actor's gradient is zero
@@ -62,11 +71,10 @@ def test_gradients_match_finite_differences(full, tanh_squash):
             assert not gg.any()
 
 
-@pytest.mark.parametrize('tanh_squash', [True, False])
-@pytest.mark.parametrize('full', [True, False])
-def test_numpy_and_torch_restatements_agree(full, tanh_squash):
+@pytest.mark.parametrize('full,tanh_squash,conf', CASES)
+def test_numpy_and_torch_restatements_agree(full, tanh_squash, conf):
     from tests import rebrac_oracle_torch as RT
-    cfg, params, batch, noise = _setup(tanh_squash=tanh_squash)
+    cfg, params, batch, noise = _setup(tanh_squash=tanh_squash, **CONFIGS.get(conf, ({}, []))[0])
     ref = RO.OracleReBRAC(params, cfg, OD, AD, np.float64)
     l1, i1, g1 = ref._losses(batch, noise, want_grads=True, full_update=full)
     l2, i2, g2 = RT.losses(params, cfg, batch, noise, full_update=full)

@@ -42,6 +42,17 @@ def assert_info_close(got, want, rtol=2e-5, atol=2e-6, keys=None):
         assert abs(g - w) <= atol + rtol * abs(w), (k, g, w)
 
 
+def assert_total_loss_matches(agent, ref, params, batch, noise):
+    """total_loss on both sides: the loss and the first 10 infos; the engine's state is unchanged afterwards."""
+    loss_ref, info_ref = ref.total_loss(batch, noise)
+    loss, info = agent.total_loss(batch, noise=noise)
+    assert abs(loss - float(loss_ref)) <= 2e-6 + 2e-5 * abs(float(loss_ref))
+    assert_info_close(info, info_ref, keys=O.INFO_KEYS[:10])
+    # total_loss must not change any state
+    for p, a in leaf_dict(agent.get_params()).items():
+        np.testing.assert_array_equal(a, leaf_dict(params)[p], err_msg=p)
+
+
 def assert_step_matches(agent, ref, cfg, batch, noise, step=None):
     """One update on both sides: 13 infos, every leaf's gradient (Adam mu / 0.1 after the first step from zero moments), nu, post-step
     parameters.  `step(agent, batch, noise)` runs the GPU side (default: agent.update) and returns the infos or None (then read_info)."""
@@ -72,3 +83,33 @@ def assert_step_matches(agent, ref, cfg, batch, noise, step=None):
             assert d[stable].max(initial=0) <= 2e-6, (p, d[stable].max())
             assert d.max() <= 2 * lr + 1e-6, p
     return worst
+
+
+def assert_trajectory_tracks_oracle(od, ad, B, hidden, seed, steps=20, **cfgkw):
+    """`steps` updates from the engine's own init on fresh rows and noise, against the fp32 oracle on the same sequence: the infos of
+    every step within 2e-3 relative.  The optimizer counters advance once per update."""
+    import fql_amd
+    cfg, ds, batch, noise = make_problem(od, ad, B, hidden, seed=seed, **cfgkw)
+    agent = fql_amd.FQLAgent.create(0, batch['observations'][:1], batch['actions'][:1], cfg)
+    params = agent.get_params()
+    ref = O.OracleFQL(params, dict(cfg), od, ad, np.float32)
+    rng = np.random.default_rng(0)
+    for s in range(steps):
+        idx = rng.integers(0, len(ds['observations']), size=B)
+        b = O.sample_batch(ds, idx)
+        nz = O.make_noise(B, ad, 100 + s)
+        _, ig = agent.update(b, noise=nz)
+        _, ir = ref.update(b, nz)
+        assert_info_close(ig, ir, rtol=2e-3, atol=2e-4)
+    opt = agent.get_opt_state()
+    assert opt['count'] == steps and opt['step'] == steps + 1
+
+
+def sync_restatement(ref, agent):
+    """Continue the restatement from the engine's state: parameters, Adam moments and counters, cast to the restatement's dtype.  Two
+    trajectories part after one step where |g| is within fp32 error (Adam's first step is lr sign(g) there), and the next step's gradient
+    then differs by more than its per-step bound allows; after this call the next step is compared on identical inputs."""
+    cast = lambda t: O.tree_map(lambda a: np.array(a, dtype=ref.dtype), t)   # noqa: E731
+    opt = agent.get_opt_state()
+    ref.params, ref.mu, ref.nu = cast(agent.get_params()), cast(opt['mu']), cast(opt['nu'])
+    ref.count, ref.step = opt['count'], opt['step']
