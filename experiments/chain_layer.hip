@@ -14,7 +14,7 @@ int main(int argc, char** argv) {
     const int M = argc > 1 ? atoi(argv[1]) : 256, N = argc > 2 ? atoi(argv[2]) : 512, K = argc > 3 ? atoi(argv[3]) : 512;
     const int wk = argc > 4 ? atoi(argv[4]) : 2;
     const int mode = argc > 5 ? atoi(argv[5]) : 0;
-    const int tmt = argc > 6 ? atoi(argv[6]) : 1;  // 1: A never written (C to a third buffer), 2: same W for all layers
+    const int tmt = 1;   // (argv[6] = 2 ran two row tiles per workgroup: that path of fql_gemm16_kernel was removed)
     hipStream_t s; CK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
     float *A0, *A1, *W, *b; GemmTask* tb;
     CK(hipMalloc(&A0, (size_t)M * 1024 * 4)); CK(hipMalloc(&A1, (size_t)M * 1024 * 4)); CK(hipMalloc(&W, (size_t)8 * K * N * 4)); CK(hipMalloc(&b, 4096 * 4));
@@ -37,7 +37,7 @@ int main(int argc, char** argv) {
     const size_t lds = ((size_t)16 * tmt * (K + 4) + 1024 * tmt) * 4;
     hipGraph_t g; hipGraphExec_t ge;
     CK(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-    for (int i = 0; i < 96; ++i) hipLaunchKernelGGL((fql_gemm16_kernel<true, false>), dim3(grid), dim3(256), lds, s, tb + (i % 8), 1, -1);
+    for (int i = 0; i < 96; ++i) hipLaunchKernelGGL((fql_gemm16_kernel<false>), dim3(grid), dim3(256), lds, s, tb + (i % 8), 1, -1);
     CK(hipStreamEndCapture(s, &g)); CK(hipGraphInstantiate(&ge, g, nullptr, nullptr, 0));
     for (int i = 0; i < 20; ++i) CK(hipGraphLaunch(ge, s));
     CK(hipStreamSynchronize(s));

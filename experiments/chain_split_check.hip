@@ -97,7 +97,7 @@ int main() {
             a.A = variant == 0 ? (v ? C0r : C0) : (v ? As : A); a.Wf = Wf[v]; a.bias = bias; a.C = Cout[v];
             a.ea_in = ea_in; a.ea_out = ea_out[v]; a.W0f = W0f[v]; a.evp_in = evp_in; a.eb = eb;
             a.W4f = W4f[v]; a.evp_out = evp_out[v];
-            a.M = M; a.ad = ad; a.ap = ap; a.ea_ld = 48; a.inv_steps = 0.1f; a.t_s = 0.3f; a.variant = variant; a.tl = -1; a.prio = 0; a.stamps = nullptr;
+            a.M = M; a.ad = ad; a.ap = ap; a.ea_ld = 48; a.inv_steps = 0.1f; a.t_s = 0.3f; a.variant = variant; a.tl = -1; a.stamps = nullptr;
             if (v == 0) { if (variant == 0) hipLaunchKernelGGL((fql_chain_kernel<512, 0>), dim3((M / 16) * 16), dim3(FQL_CHAIN_THREADS), FQL_CHAIN_LDS_BYTES(512), s, a); else if (variant == 1) hipLaunchKernelGGL((fql_chain_kernel<512, 1>), dim3((M / 16) * 16), dim3(FQL_CHAIN_THREADS), FQL_CHAIN_LDS_BYTES(512), s, a); else hipLaunchKernelGGL((fql_chain_kernel<512, 2>), dim3((M / 16) * 16), dim3(FQL_CHAIN_THREADS), FQL_CHAIN_LDS_BYTES(512), s, a); }
             else if (variant == 0) hipLaunchKernelGGL((fql_chain_split_kernel<512, 0>), dim3((M / 16) * 16), dim3(FQL_CHAIN_THREADS), FQL_CHAIN_LDS_BYTES(512), s, a);
             else if (variant == 1) hipLaunchKernelGGL((fql_chain_split_kernel<512, 1>), dim3((M / 16) * 16), dim3(FQL_CHAIN_THREADS), FQL_CHAIN_LDS_BYTES(512), s, a);

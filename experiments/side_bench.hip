@@ -62,11 +62,11 @@ int main(int argc, char** argv) {
     CK(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
     for (int i = 0; i < 48; ++i)
         if (shape == 4) hipLaunchKernelGGL(fql_side_big_kernel, dim3(grid), dim3(256), lds, s, (const GemmTask*)(tb + (i % 2) * 4), 4, (const WgradTask*)nullptr, 0,
-                           (const LnBwdTask*)nullptr, 0, grid, grid, (const MiscTask*)nullptr, grid, 0, -1);
+                           (const LnBwdTask*)nullptr, 0, grid, grid, (const MiscTask*)nullptr, grid, -1);
         else if (split) hipLaunchKernelGGL(fql_side_split_kernel, dim3(grid), dim3(256), lds, s, (const GemmTask*)(tb + (i % 2) * 4), 4, (const WgradTask*)nullptr, 0,
-                           (const LnBwdTask*)nullptr, 0, grid, grid, (const MiscTask*)nullptr, grid, 0, -1);
+                           (const LnBwdTask*)nullptr, 0, grid, grid, (const MiscTask*)nullptr, grid, -1);
         else hipLaunchKernelGGL(fql_side_kernel, dim3(grid), dim3(256), lds, s, (const GemmTask*)(tb + (i % 2) * 4), 4, (const WgradTask*)nullptr, 0,
-                           (const LnBwdTask*)nullptr, 0, grid, grid, (const MiscTask*)nullptr, grid, 0, -1);
+                           (const LnBwdTask*)nullptr, 0, grid, grid, (const MiscTask*)nullptr, grid, -1);
     CK(hipStreamEndCapture(s, &g)); CK(hipGraphInstantiate(&ge, g, nullptr, nullptr, 0));
     for (int i = 0; i < 10; ++i) CK(hipGraphLaunch(ge, s));
     CK(hipStreamSynchronize(s));

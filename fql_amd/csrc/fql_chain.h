@@ -71,7 +71,6 @@ struct ChainArgs {
     int xg;               // XCD-aware tile order (xcd_tile) with xg row groups; 0 = row-major
     int hw;               // variant E: hidden width of THIS launch's layers (the critic's; the other variants use the BC flow's)
     int tl;               // timeline id (diagnostics build)
-    int prio;             // s_setprio level of the chain's waves (they are latency-critical and light: 0.85 us of MFMA per launch)
     unsigned long long* stamps;   // diagnostics build only (FQL_STAMPS): [grid][8] wall-clock stamps
 };
 
@@ -147,9 +146,6 @@ __device__ __forceinline__ void chain_body(const ChainArgs& P) {
     if (P.xg) xcd_tile((int)blockIdx.x, P.M >> 4, ntc, P.xg, tm, tn);
     const int row0 = tm * 16, n0 = tn * 32 + nt * 16;
     tl_enter(P.tl);
-    if (P.prio == 3) __builtin_amdgcn_s_setprio(3);
-    else if (P.prio == 2) __builtin_amdgcn_s_setprio(2);
-    else if (P.prio == 1) __builtin_amdgcn_s_setprio(1);
 #ifdef FQL_STAMPS
     unsigned long long stamp[8];
     int nst = 0;

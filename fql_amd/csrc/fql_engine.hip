@@ -14,7 +14,6 @@
 #include "fql_conv.h"
 #include "fql_chain.h"
 #include "fql_aux.h"
-#include "fql_xchain.h"
 #include "fql_ifql.h"
 #include "fql_rebrac.h"
 #include <hip/hip_ext.h>
@@ -126,6 +125,8 @@ struct Leaf {
 // ------------------------------------------------------------------------------------------------
 // program = ordered ops with read/write sets -> levels -> launches
 // ------------------------------------------------------------------------------------------------
+// OP_WGRAD, OP_LNBWD, OP_POSTOS and the OP_LOSS_{CRITIC,Q,BC} ops ride in OP_GEMM64 (side-lane) launches, never in launches of their own.
+// OP_PEC and OP_XCHAIN are reserved (retired persistent Euler chains): the values index profile labels (bench.py OP_NAMES) and order launches.
 enum OpType { OP_GEMM, OP_GEMM64, OP_WGRAD, OP_LNBWD, OP_PREP, OP_POSTOS, OP_EULER_FIN, OP_PEC, OP_LOSS_CRITIC, OP_LOSS_Q, OP_LOSS_BC,
               OP_LOSS_ACTOR, OP_CONV_WPREP, OP_CONV, OP_CONV_U8, OP_POOL, OP_POOL_BWD, OP_CONV_WGRAD, OP_CONV_WRED, OP_ENC_DZ, OP_CHAIN, OP_WFRAG, OP_XCHAIN, OP_HEAD_DGRAD, OP_DGRAD0, OP_ADAM,
               OP_FINALIZE,
@@ -147,7 +148,6 @@ struct Op {
     LossBcArgs lb;
     LossActorArgs la;
     EulerFinishArgs ef;
-    PecArgs pec;
     ConvArgs conv;
     PoolArgs pool;
     PoolBwdArgs poolb;
@@ -163,7 +163,6 @@ struct Op {
     RebracActorArgs ra;
     RebracActorGradArgs rag;
     ChainArgs chain;
-    XChainArgs xchain;
     const ConvWprepTask* wprep_tasks = nullptr;
     int wprep_n = 0;
     int cw_grid = 0;
@@ -180,13 +179,13 @@ struct Launch {
     OpType type;
     int grid = 0, ntasks = 0;
     size_t lds = 0;
-    void* table = nullptr;  // device task table (GEMM/WGRAD/LNBWD)
+    void* table = nullptr;  // device task table (GEMM / GEMM64 / convolution families)
     Op op;                  // arg-struct kernels
     bool pool_fused = false; // OP_CONV_U8: the stack's max-pool runs inside the convolution kernel (fql_conv3x3_pool_kernel)
     int lane = 0;
-    bool tmt2 = false, kbig = false, euler = false;
+    bool tmt2 = false, kbig = false, euler = false;   // tmt2: OP_GEMM64 launch with 64 x 64 tile tasks (fql_side_big_kernel)
     double macs = 0.0;           // algorithmic multiply-accumulates of the GEMM-shaped tasks of this launch (roofline accounting)
-    bool side = false;           // merged gemm64 + wgrad + lnbwd launch
+    // OP_GEMM64 (side-lane) launches: gemm64 tiles, then weight-gradient, LayerNorm-backward and loss / metric tasks of the level
     void *table_w = nullptr, *table_l = nullptr, *table_m = nullptr;
     int n_w = 0, n_l = 0, tile_w = 0, tile_l = 0, tile_m = 0;
     std::vector<GemmTask> dg_tasks;   // OP_DGRAD0: the (<= 4) tasks of this launch, handed over as the kernel argument
@@ -313,7 +312,7 @@ struct fql_engine {
     float *X_os = nullptr, *X_bc = nullptr, *X_eu = nullptr, *X_c1 = nullptr, *X_c2 = nullptr, *X_ct = nullptr;
     float *vel = nullptr, *w_rew = nullptr, *w_mask = nullptr, *w_act = nullptr, *tgt = nullptr;
     float *X_e0 = nullptr, *C0 = nullptr, *Abuf[2] = {nullptr, nullptr}, *Vpart = nullptr;  // fused Euler chain
-    bool fused_euler = false, use_pec = false;
+    bool fused_euler = false;
     // Euler-chain kernel (fql_chain.h): fragment-major copies of the BC flow's hidden kernels (layers 1..nh-1), of the 16 rows of
     // W0 that start at the action block and of the head kernel, refreshed behind every Adam step of that module
     bool use_chain = false;
@@ -327,9 +326,6 @@ struct fql_engine {
     bool wide_tiles = false;    // three-lane programs: 32 x 64 side tiles everywhere (the other lanes fill the CUs a launch leaves idle; +1 %)
     bool split_ok = false;
     int vp_tiles = 0;
-    int pec_teams = 0;               // teams of the persistent chain (H/32 workgroups each, one workgroup per CU)
-    unsigned* pec_epoch = nullptr;   // [teams] launch epochs of the persistent chain + 1 error word at the end
-    fql_u64 *pec_g[2] = {nullptr, nullptr}, *pec_vg = nullptr;  // granule buffers: activations [B][H] x 2, head partials [T][B][16]
     int num_cus = 0;
     PassBuf p_os, p_os_bwd, p_bc, p_eu, p_c1[2], p_c2[2], p_ct[2];
     Program prog_fwdbwd, prog_opt, prog_loss;
@@ -391,13 +387,6 @@ struct fql_engine {
         Program prog_q;
     };
     std::map<int, std::unique_ptr<Eval>> evals;
-
-    // XCD-resident Euler chain (fql_xchain.h): the whole chain as one persistent launch on the critical lane
-    bool use_xchain = false;
-    unsigned* xsync = nullptr;      // [17][32] words: arrival flags, tickets (zeroed by the prep launch), sticky error word
-    float* xvp = nullptr;           // head partials [32][B][16]
-    size_t x_lds = 0;
-    unsigned long long* x_stamps = nullptr;
 
     int64_t launches_per_update = 0;
     // agent groups (fql_group_*): the group this engine is a member of, the event behind that group's last update and whether an entry
@@ -516,16 +505,13 @@ struct fql_engine {
 
     // can the first convolution of a stack run fused with the stack's max-pool (fql_conv3x3_pool_kernel)?  first_stack: it reads the uint8 images
     // Measured (visual update, one box): the uint8 layer fused +2.8 % (fp32) and more in bf16x3; the float layers of stacks 1 / 2 fused too: bf16x3 370.5 -> 373.9, fp32
-    // 311.7 -> 308.3 (their 5-row tiles redo a quarter of the rows, which fp32 MFMAs pay for) - so those are fused under precision = 2 only (FQL_FUSE_POOL_FLOAT=0/1 overrides).
+    // 311.7 -> 308.3 (their 5-row tiles redo a quarter of the rows, which fp32 MFMAs pay for) - so those are fused under precision = 2 only.
     bool pool_fusable(const EncStack& st, const ConvL& c, bool first_stack) const {
-        constexpr bool on = true;
-        constexpr int float_env = -1;
-        const bool on_float = float_env >= 0 ? float_env != 0 : cfg.precision == 2;
         const int Ci = pad16c(c.cin);
-        if (!on || st.W % 16 || st.W < 16 || st.W > 128 || st.H % 2 || (c.cout != 16 && c.cout != 32)) return false;
+        if (st.W % 16 || st.W < 16 || st.W > 128 || st.H % 2 || (c.cout != 16 && c.cout != 32)) return false;
         if ((size_t)FQL_CONV_POOL_LDS_FLOATS(st.W, Ci, c.cout) * sizeof(float) > 65536) return false;
         if (first_stack) return c.cout == 16 && Ci == 16 && 7 * st.W * c.cin <= 4 * 4 * FQL_THREADS && (st.W * c.cin) % 4 == 0;   // seven uint8 rows: <= 4 dwords per thread
-        return on_float && (Ci == 16 || Ci == 32) && Ci == c.cin && 7 * (st.W + 2) * (Ci / 4) <= 4 * FQL_THREADS;               // seven float rows: <= 4 float4 per thread
+        return cfg.precision == 2 && (Ci == 16 || Ci == 32) && Ci == c.cin && 7 * (st.W + 2) * (Ci / 4) <= 4 * FQL_THREADS;               // seven float rows: <= 4 float4 per thread
     }
     // LDS-layout weight copies of every convolution + the task tables of fql_conv_wprep_kernel (needs P)
     void build_enc_weights() {
@@ -937,8 +923,8 @@ struct fql_engine {
         if (in_mode == 2 && (a.Ci != 16 || a.Co != 16)) invalid("uint8 convolution weight gradient: <= 16 input channels and 16 output channels expected (got %d -> %d)", c.cin, c.cout);
         a.R = conv_rows(H, W, a.Ci, a.Co, true);
         a.nblocks = n * (H / a.R);
-        constexpr int cwg_env = 256;   // persistent workgroups per weight-gradient task
-        op.cw_grid = std::min(a.nblocks, cwg_env);
+        constexpr int cwg_grid = 256;   // persistent workgroups per weight-gradient task
+        op.cw_grid = std::min(a.nblocks, cwg_grid);
         op.reads = {in_id, dout_id};
         op.writes = {wp};
         push(pr, op);
@@ -1046,8 +1032,7 @@ struct fql_engine {
 
     // throughput-lane tasks with 64-aligned shapes go to the 64x64 LDS-tiled kernel
     bool want64(int M, int N, int K, int flags) const {
-        constexpr bool off = false;
-        if (off || emit_lane == 0 || !allow64) return false;
+        if (emit_lane == 0 || !allow64) return false;
         if (M % 64 || N % 64 || K % 64) return false;
         if (flags & (GF_EULER | GF_CLIP_OUT)) return false;
         return true;
@@ -1131,38 +1116,6 @@ struct fql_engine {
             }
             push(pr, op);
         }
-    }
-
-    // The whole Euler chain in one persistent launch (fql_euler_persistent_kernel): C0 GEMM, then teams of H/32
-    // workgroups hand 16-row activation tiles to each other through L2.
-    void emit_euler_persistent(Program& pr) {
-        const Net& n = nets[NET_BC];
-        const int od = cfg.obs_dim, ad = cfg.act_dim, ap = pad16(ad), inp_b = n.in_p();
-        const Layer& l0 = n.layers[0];
-        {
-            Op op{};
-            op.type = OP_GEMM;
-            GemmTask& t = op.gemm;
-            t.A = X_e0; t.lda = l0.in_p; t.B = P + l0.w; t.ldb = l0.out_p; t.bias = P + l0.b; t.C = C0; t.ldc = l0.out_p;
-            t.M = B; t.N = l0.out_p; t.K = l0.in_p; t.flags = GF_BIAS;
-            op.reads = {X_e0, t.B};
-            op.writes = {C0};
-            push(pr, op);
-        }
-        Op op{};
-        op.type = OP_PEC;
-        PecArgs& a = op.pec;
-        a.C0 = C0; a.a0 = X_eu + od; a.lda0 = inp_b;
-        a.W0act = P + l0.w + (size_t)od * l0.out_p;
-        for (int l = 0; l < 3; ++l) { a.W[l] = P + n.layers[l + 1].w; a.b[l] = P + n.layers[l + 1].b; }
-        a.W4 = P + n.layers[4].w; a.b4 = P + n.layers[4].b;
-        a.G[0] = pec_g[0]; a.G[1] = pec_g[1]; a.Vg = pec_vg; a.tgt = tgt;
-        a.epoch = pec_epoch; a.err = pec_epoch + pec_teams;
-        a.M = B; a.ad = ad; a.ap = ap; a.flow_steps = cfg.flow_steps;
-        a.nteams = pec_teams; a.ntile = B / 16 / pec_teams;
-        op.reads = {C0, X_eu};
-        op.writes = {tgt, pec_g[0], pec_g[1], pec_vg};
-        push(pr, op);
     }
 
     // Euler chain with 3 launches per step instead of 5 (agents/fql.py:155-171): [fold head partials -> a_s; layer 0 as a
@@ -1260,8 +1213,6 @@ struct fql_engine {
                 a.M = B; a.ad = ad; a.ap = ap;
                 a.inv_steps = 1.0f / (float)fs; a.t_s = (float)s / (float)fs;
                 a.variant = 1;
-                constexpr int chain_prio = 0;
-                a.prio = chain_prio;
                 op.reads = {a.Wf, P + ly.w};
                 if (l == 1) {
                     a.variant = 0;
@@ -1302,45 +1253,6 @@ struct fql_engine {
         op.writes = {tgt};
         push(pr, op);
     }
-    // The whole chain as ONE persistent XCD-resident launch (fql_xchain.h): 8 row blocks x 32 column slices, activations exchanged through
-    // each XCD's own L2, hidden kernels resident in LDS.
-    bool xchain_eligible() const {
-        // opt-in (FQL_XCHAIN=1).  Measured at B = 256, H = 512 (profiles/r03_xcd_resident.txt): the update takes 352-359 us with this ONE launch in place of
-        // the chain's 30 against 344-345 us with the launches (each member re-reads its XCD's whole activation panel and its slice of the layer's kernel
-        // every phase: 3 MB through an XCD's L2 per phase).
-        if (!getenv("FQL_XCHAIN") || atoi(getenv("FQL_XCHAIN")) == 0) return false;
-        if (visual || cfg.precision != 0 || cfg.actor_layer_norm || cfg.act_dim > 15) return false;
-        if (num_cus != XCH_NGRP * XCH_NMEM || B % 128 != 0 || B / 128 > XCH_MAXRT) return false;
-        const Net& n = nets[NET_BC];
-        const int nh = n.nl() - 1;
-        if (nh < 2 || nh - 1 > 7) return false;
-        const int H = n.layers[0].out;
-        if (H % 16 || H > 512 || n.layers[0].in_p > 128 || n.layers[nh].out_p != 16) return false;
-        for (int l = 0; l < nh; ++l) if (n.layers[l].out != H || n.layers[l].out_p != H) return false;
-        return use_chain;   // (the kernel reads the fragment-major copies the chain launches read)
-    }
-    void emit_euler_xcd(Program& pr) {
-        const Net& n = nets[NET_BC];
-        const int nh = n.nl() - 1;
-        Op op{};
-        op.type = OP_XCHAIN;
-        XChainArgs& a = op.xchain;
-        a.B = B; a.R = B / 8; a.RT = B / 128;
-        a.H = n.layers[0].out_p; a.nl = nh - 1;
-        a.od = cfg.obs_dim; a.ad = cfg.act_dim; a.ap = pad16(cfg.act_dim); a.in_p = n.in_p(); a.fs = cfg.flow_steps;
-        a.x_e0 = X_eu; a.x_eu = X_eu;   // (C0 masks the action / t rows of the first kernel: the Euler input serves as its observation-only input too)
-        a.w0 = P + n.layers[0].w; a.b0 = P + n.layers[0].b;
-        for (int l = 1; l < nh; ++l) { a.b[l - 1] = P + n.layers[l].b; a.wf[l - 1] = wf_bc[l - 1]; }
-        a.w4 = P + n.layers[nh].w; a.b4 = P + n.layers[nh].b;
-        a.hc[0] = p_eu.g[0]; a.hc[1] = p_eu.g[1];
-        a.vp = xvp; a.tgt = tgt; a.sync = xsync;
-        a.stamps = x_stamps;
-        op.reads = {X_eu};
-        for (const Layer& L : n.layers) op.reads.push_back(P + L.w);
-        for (float* w : wf_bc) op.reads.push_back(w);
-        op.writes = {tgt, xvp, p_eu.g[0], p_eu.g[1]};
-        push(pr, op);
-    }
     // refresh of the fragment-major copies inside a program, behind the Adam launch that rewrites the BC flow's kernels
     void emit_wfrag(Program& pr) {
         if (!use_chain) return;
@@ -1378,13 +1290,11 @@ struct fql_engine {
                 w.M = M; w.Kin = ly.in_p; w.N = ly.out_p;
                 op.reads = {xin_id, dz};
                 op.writes = {w.dW, w.db};
-                // weight gradients feed nothing but the optimizer: background lane
                 // weight gradients feed nothing but the optimizer: those of a chain that runs on the critical lane are
-                // issued on the side lane so they never sit between two links of that chain
+                // issued on the side lane so they never sit between two links of that chain (a separate wgrad lane was measured
+                // slower than sharing launches)
                 const int keep = emit_lane;
-                constexpr bool wlane = false;  // (a separate wgrad lane is worse than sharing launches)
-                if (wlane) emit_lane = 2;
-                else if (emit_lane == 0 && !split_build) emit_lane = 1;
+                if (emit_lane == 0 && !split_build) emit_lane = 1;
                 if (defer_wgrads) { op.lane = emit_lane; defer_wgrads->push_back(op); }
                 else push(pr, op);
                 emit_lane = keep;
@@ -1464,8 +1374,7 @@ struct fql_engine {
                 if (want64(t.M, t.N, t.K, t.flags)) op.type = OP_GEMM64;
                 // a square hidden layer on the latency lane (the one-step actor's backward tail behind the Euler chain): the chain
                 // kernel's variant D does it in about half the time of the generic 16-row kernel
-                constexpr bool chain_dgrad = true;
-                if (chain_dgrad && op.type == OP_GEMM && use_chain && t.N == t.K && t.N == cfg.actor_hidden[0] && t.M % 16 == 0 &&
+                if (op.type == OP_GEMM && use_chain && t.N == t.K && t.N == cfg.actor_hidden[0] && t.M % 16 == 0 &&
                     t.lda == t.K && t.ldb == t.K && t.ldc == t.N && prev.out_p == t.N) {
                     Op co{};
                     co.type = OP_CHAIN;
@@ -1488,8 +1397,6 @@ struct fql_engine {
     // ---------------------------------------------------------------------------------------
     // scheduling + launch tables + graph capture
     // ---------------------------------------------------------------------------------------
-    static bool is_table(OpType t) { return t == OP_GEMM || t == OP_GEMM64 || t == OP_WGRAD || t == OP_LNBWD; }
-
     void schedule(Program& pr, std::vector<void*>& owner) {
         // list scheduling: level = 1 + max level of every op this one conflicts with (RAW, WAW, WAR)
         std::map<const void*, int> last_writer;               // buffer -> op index of last writer
@@ -1549,10 +1456,10 @@ struct fql_engine {
                     const Op& op = pr.ops[oi];
                     if (op.level == lv && op.type == ty && op.lane == lane) sel.push_back(&op);
                 }
-                constexpr bool merge_side = true;
-                if (merge_side && (ty == OP_WGRAD || ty == OP_LNBWD || ty == OP_POSTOS || ty == OP_LOSS_CRITIC || ty == OP_LOSS_Q ||
-                                   ty == OP_LOSS_BC)) continue;  // folded into the OP_GEMM64 iteration
-                if (merge_side && ty == OP_GEMM64) {
+                // the side-lane families of a level share ONE launch with its gemm64 tiles (fql_side_kernel)
+                if (ty == OP_WGRAD || ty == OP_LNBWD || ty == OP_POSTOS || ty == OP_LOSS_CRITIC || ty == OP_LOSS_Q || ty == OP_LOSS_BC)
+                    continue;  // folded into the OP_GEMM64 iteration
+                if (ty == OP_GEMM64) {
                     std::vector<const Op*> selw, sell, selm;
                     for (const Op& op : pr.ops) {
                         if (op.level != lv || op.lane != lane) continue;
@@ -1565,7 +1472,6 @@ struct fql_engine {
                     pr.lane_used[lane] = true;
                     Launch L;
                     L.type = OP_GEMM64;
-                    L.side = true;
                     L.lane = lane;
                     const int li = (int)pr.launches.size();
                     for (const Op* o : sel) launch_of[o - pr.ops.data()] = li;
@@ -1574,21 +1480,18 @@ struct fql_engine {
                     for (const Op* o : selm) launch_of[o - pr.ops.data()] = li;
                     // 32 x 64 tiles while a level is a latency chain (B = 256: 1.5 workgroups per CU), 64 x 64 once a task alone
                     // brings >= 128 of them (M >= 1024: +2 % at B = 1024)
-                    constexpr int ri_env = 0;
-                    constexpr bool xcd_order = true;
                     int ri = 1;
                     int tile = 0;
                     std::vector<GemmTask> tg;
                     // tile shape of the 32-row tasks of this launch: 32 x 64 unless 32 x 32 tiles deal out more evenly over the CUs
                     // (e.g. 384 tiles of 32 x 64 = two tile times on half the CUs; 768 of 32 x 32 = three half-size tiles everywhere)
-                    constexpr int nj_env = 0;
                     int nj = 2;
                     {
                         int t64 = 0;
                         double other = 0.0;   // in units of a 32 x 32 x 512 tile
                         for (const Op* o : sel) {
                             const GemmTask& t = o->gemm;
-                            const bool big = cfg.precision == 2 ? false : ri_env ? ri_env == 2 : (t.M >= 1024 && t.M % 64 == 0);
+                            const bool big = cfg.precision != 2 && t.M >= 1024 && t.M % 64 == 0;
                             if (big) other += 4.0 * (t.M / 64) * (t.N / 64) * t.K / 512.0;
                             else t64 += (t.M / 32) * (t.N / 64);
                         }
@@ -1597,26 +1500,24 @@ struct fql_engine {
                         const int ncu = std::max(1, num_cus);
                         const double m64 = 2.0 * ((t64 + ncu - 1) / ncu) + other / ncu, m32 = 1.0 * ((2 * t64 + ncu - 1) / ncu) + other / ncu;
                         if (t64 > 0 && m32 < m64 && !wide_tiles) nj = 1;
-                        if (nj_env == 1 || nj_env == 2) nj = nj_env;
                     }
                     for (const Op* o : sel) {
                         GemmTask t = o->gemm;
-                        const int ri_t = cfg.precision == 2 ? 1 : ri_env ? ri_env : (t.M >= 1024 && t.M % 64 == 0 ? 2 : 1);   // split bodies are 32-row tiles
+                        const int ri_t = cfg.precision != 2 && t.M >= 1024 && t.M % 64 == 0 ? 2 : 1;   // split bodies are 32-row tiles
                         ri = std::max(ri, ri_t);
                         if (ri_t == 2) L.tmt2 = true;
                         t.tmt = ri_t;
                         t.wk = ri_t == 2 ? 2 : nj;          // MFMA column tiles per wave: tile = 32 x (32 wk)
                         t.ntn = t.N / (32 * t.wk); t.tile0 = tile;
                         t.xg = 0;
-                        if (ri_t == 1 && xcd_order && tile % 8 == 0) {   // XCD-aware tile order: gm x gn = 8 blocks of the tile grid, fewest panel fetches
+                        if (ri_t == 1 && tile % 8 == 0) {   // XCD-aware tile order: gm x gn = 8 blocks of the tile grid, fewest panel fetches
                             const int ntm = t.M / 32;
                             // gm row groups x gn column groups: an A row panel is fetched by gn XCDs, a B column panel by gm -> fewest panel bytes
-                            // (FQL_XCD_GM forces gm; measured on the whole update: the rule's choice 3075, forced 4: 3001-3061, 8: 2864-3026, 1: 2967-3040, off: 3025)
-                            constexpr int gm_env = 0;
+                            // (measured on the whole update: the rule's choice 3075, gm forced to 4: 3001-3061, 8: 2864-3026, 1: 2967-3040, no XCD order: 3025)
                             double best = 1e30;
                             for (int gm : {1, 2, 4, 8}) {
                                 const int gn = 8 / gm;
-                                if (ntm % gm || t.ntn % gn || (gm_env && gm != gm_env)) continue;
+                                if (ntm % gm || t.ntn % gn) continue;
                                 const double cost = (double)gn * t.M + (double)gm * t.N;
                                 if (cost < best) { best = cost; t.xg = gm; }
                             }
@@ -1702,10 +1603,8 @@ struct fql_engine {
                             ConvArgs a = o->conv;
                             const int nb = a.N * (a.H / a.R);
                             a.tile0 = tile;
-                            // float layers: a workgroup per row block by default; FQL_CONV_WGS_PER_CU=k makes them persistent too (measured: +-1 %)
-                            constexpr int conv_per_cu = 0;
-                            const int per_cu = ty == OP_CONV_U8 ? u8_per_cu : conv_per_cu;
-                            a.nwg = per_cu > 0 ? std::min(nb, std::max(1, (int)(((long long)per_cu * num_cus * nb) / nb_all))) : nb;
+                            // float layers: a workgroup per row block (persistent float layers were measured at +-1 %)
+                            a.nwg = ty == OP_CONV_U8 ? std::min(nb, std::max(1, (int)(((long long)u8_per_cu * num_cus * nb) / nb_all))) : nb;
                             if (a.parg) {   // convolution + max-pool in one kernel: a workgroup per (image, pooled row pair)
                                 a.nwg = a.N * ((a.H + 3) / 4);
                                 L.pool_fused = true;
@@ -1775,7 +1674,7 @@ struct fql_engine {
                     pr.launches.push_back(L);
                     continue;
                 }
-                if (!is_table((OpType)ty)) {
+                if (ty != OP_GEMM) {
                     for (const Op* o : sel) {
                         Launch L;
                         L.type = (OpType)ty;
@@ -1787,68 +1686,27 @@ struct fql_engine {
                     continue;
                 }
                 Launch L;
-                L.type = (OpType)ty;
+                L.type = OP_GEMM;
                 L.lane = lane;
                 for (const Op* o : sel) launch_of[o - pr.ops.data()] = (int)pr.launches.size();
                 L.ntasks = (int)sel.size();
                 int tile = 0;
-                if (ty == OP_GEMM) {
-                    std::vector<GemmTask> tb;
-                    for (const Op* o : sel) {
-                        GemmTask t = o->gemm;
-                        constexpr int tmt_side = 1;
-                        t.wk = (t.N <= 16) ? 4 : 2;
-                        // throughput lane: two 16-row tiles per workgroup share each B fragment
-                        t.tmt = (lane == 1 && tmt_side == 2 && t.M % 32 == 0 && t.M >= 256 && t.N >= 32) ? 2 : 1;
-                        t.ntn = (t.N / 16 + (4 / t.wk) - 1) / (4 / t.wk);
-                        t.tile0 = tile;
-                        tile += (t.M / (16 * t.tmt)) * t.ntn;
-                        if (t.tmt == 2) L.tmt2 = true;
-                        if (t.K > 512) L.kbig = true;
-                        if (t.flags & (GF_A_EULER0 | GF_HEAD_PART | GF_A_LOSSACT)) L.euler = true;
-                        L.lds = std::max(L.lds, ((size_t)16 * t.tmt * (t.K + 4) + 1024 * t.tmt + 1280) * sizeof(float));
-                        tb.push_back(t);
-                    }
-                    L.table = dalloc(owner, tb.size() * sizeof(GemmTask) / sizeof(float) + 4);
-                    HIP_CHECK(hipMemcpy(L.table, tb.data(), tb.size() * sizeof(GemmTask), hipMemcpyHostToDevice));
-                } else if (ty == OP_GEMM64) {
-                    std::vector<GemmTask> tb;
-                    for (const Op* o : sel) {
-                        GemmTask t = o->gemm;
-                        constexpr int ri_env = 0;
-                        const int ri = ri_env ? ri_env : (t.M >= 1024 && t.M % 64 == 0 ? 2 : 1);
-                        t.wk = 2; t.tmt = ri;  // row tiles per wave: workgroup tile (32 ri) x 64
-                        t.ntn = t.N / 64;
-                        t.tile0 = tile;
-                        tile += (t.M / (32 * ri)) * t.ntn;
-                        tb.push_back(t);
-                    }
-                    L.lds = (size_t)(4 * 64 * 68 + 256) * sizeof(float);
-                    L.table = dalloc(owner, tb.size() * sizeof(GemmTask) / sizeof(float) + 4);
-                    HIP_CHECK(hipMemcpy(L.table, tb.data(), tb.size() * sizeof(GemmTask), hipMemcpyHostToDevice));
-                } else if (ty == OP_WGRAD) {
-                    std::vector<WgradTask> tb;
-                    for (const Op* o : sel) {
-                        WgradTask t = o->wgrad;
-                        t.ntn = (t.N + 63) / 64;
-                        t.tile0 = tile;
-                        tile += ((t.Kin + FQL_WGRAD_KT - 1) / FQL_WGRAD_KT) * t.ntn;
-                        tb.push_back(t);
-                    }
-                    L.table = dalloc(owner, tb.size() * sizeof(WgradTask) / sizeof(float) + 4);
-                    HIP_CHECK(hipMemcpy(L.table, tb.data(), tb.size() * sizeof(WgradTask), hipMemcpyHostToDevice));
-                } else {
-                    std::vector<LnBwdTask> tb;
-                    for (const Op* o : sel) {
-                        LnBwdTask t = o->ln;
-                        t.ntiles_rows = (t.M + 3) / 4;
-                        t.tile0 = tile;
-                        tile += t.ntiles_rows + (t.dgamma ? t.H / 16 : 0);
-                        tb.push_back(t);
-                    }
-                    L.table = dalloc(owner, tb.size() * sizeof(LnBwdTask) / sizeof(float) + 4);
-                    HIP_CHECK(hipMemcpy(L.table, tb.data(), tb.size() * sizeof(LnBwdTask), hipMemcpyHostToDevice));
+                std::vector<GemmTask> tb;
+                for (const Op* o : sel) {
+                    GemmTask t = o->gemm;
+                    t.wk = (t.N <= 16) ? 4 : 2;
+                    // (two 16-row tiles per workgroup sharing each B fragment were tried on the throughput lane: not kept)
+                    t.tmt = 1;
+                    t.ntn = (t.N / 16 + (4 / t.wk) - 1) / (4 / t.wk);
+                    t.tile0 = tile;
+                    tile += (t.M / 16) * t.ntn;
+                    if (t.K > 512) L.kbig = true;
+                    if (t.flags & (GF_A_EULER0 | GF_HEAD_PART | GF_A_LOSSACT)) L.euler = true;
+                    L.lds = std::max(L.lds, ((size_t)16 * (t.K + 4) + 1024 + 1280) * sizeof(float));
+                    tb.push_back(t);
                 }
+                L.table = dalloc(owner, tb.size() * sizeof(GemmTask) / sizeof(float) + 4);
+                HIP_CHECK(hipMemcpy(L.table, tb.data(), tb.size() * sizeof(GemmTask), hipMemcpyHostToDevice));
                 L.grid = tile;
                 pr.launches.push_back(L);
             }
@@ -1889,11 +1747,6 @@ struct fql_engine {
             else if (o.type == OP_CHAIN) {
                 const double H = cfg.actor_hidden[0];
                 m = (double)o.chain.M * H * H + (o.chain.variant == 0 ? (double)o.chain.M * 16.0 * H : 0.0) + (o.chain.variant == 2 ? (double)o.chain.M * H * o.chain.ap : 0.0);
-            }
-            else if (o.type == OP_XCHAIN) {
-                const Net& nb = nets[NET_BC];
-                for (const Layer& L : nb.layers) m += (double)B * L.in * L.out;
-                m = m * cfg.flow_steps - (double)B * cfg.obs_dim * nb.layers[0].out * (cfg.flow_steps - 1);   // (the obs part of layer 0 is computed once)
             }
             else if (o.type == OP_CONV || o.type == OP_CONV_U8) m = (double)o.conv.N * o.conv.H * o.conv.W * 9.0 * (o.conv.transposed ? o.conv.Ci : o.conv.Ci_real) * o.conv.Co;
             else if (o.type == OP_CONV_WGRAD) m = (double)o.cw.N * o.cw.H * o.cw.W * 9.0 * o.cw.Ci_real * o.cw.Co;
@@ -1966,64 +1819,32 @@ struct fql_engine {
         else hipLaunchKernelGGL(k, g, b, l, st, __VA_ARGS__);                                     \
     } while (0)
     void issue(const Launch& L, hipStream_t s, int tl) {
-        constexpr bool u8_split = true;
-        constexpr int side_prio = 0;
         switch (L.type) {
             case OP_GEMM:
                 if (L.euler && L.kbig) FQL_LAUNCH((fql_gemm16_euler_kernel<true>), dim3(L.grid), dim3(FQL_THREADS), L.lds, s, (const GemmTask*)L.table, L.ntasks, tl);
                 else if (L.euler) FQL_LAUNCH((fql_gemm16_euler_kernel<false>), dim3(L.grid), dim3(FQL_THREADS), L.lds, s, (const GemmTask*)L.table, L.ntasks, tl);
-                else if (L.tmt2 && L.kbig) FQL_LAUNCH((fql_gemm16_kernel<true, true>), dim3(L.grid), dim3(FQL_THREADS), L.lds, s, (const GemmTask*)L.table, L.ntasks, tl);
-                else if (L.tmt2) FQL_LAUNCH((fql_gemm16_kernel<true, false>), dim3(L.grid), dim3(FQL_THREADS), L.lds, s, (const GemmTask*)L.table, L.ntasks, tl);
-                else if (L.kbig) FQL_LAUNCH((fql_gemm16_kernel<false, true>), dim3(L.grid), dim3(FQL_THREADS), L.lds, s, (const GemmTask*)L.table, L.ntasks, tl);
-                else FQL_LAUNCH((fql_gemm16_kernel<false, false>), dim3(L.grid), dim3(FQL_THREADS), L.lds, s, (const GemmTask*)L.table, L.ntasks, tl);
+                else if (L.kbig) FQL_LAUNCH((fql_gemm16_kernel<true>), dim3(L.grid), dim3(FQL_THREADS), L.lds, s, (const GemmTask*)L.table, L.ntasks, tl);
+                else FQL_LAUNCH((fql_gemm16_kernel<false>), dim3(L.grid), dim3(FQL_THREADS), L.lds, s, (const GemmTask*)L.table, L.ntasks, tl);
                 break;
-            case OP_GEMM64:
-                if (L.side && L.tmt2)
+            case OP_GEMM64:   // the level's side-lane launch (schedule())
+                if (L.tmt2)
                     FQL_LAUNCH(fql_side_big_kernel, dim3(L.grid), dim3(FQL_THREADS), L.lds, s, (const GemmTask*)L.table, L.ntasks,
                                        (const WgradTask*)L.table_w, L.n_w, (const LnBwdTask*)L.table_l, L.n_l, L.tile_w, L.tile_l,
-                                       (const MiscTask*)L.table_m, L.tile_m, 0, tl);
-                else if (L.side && cfg.precision == 2)
+                                       (const MiscTask*)L.table_m, L.tile_m, tl);
+                else if (cfg.precision == 2)
                     FQL_LAUNCH(fql_side_split_kernel, dim3(L.grid), dim3(FQL_THREADS), L.lds, s, (const GemmTask*)L.table, L.ntasks,
                                        (const WgradTask*)L.table_w, L.n_w, (const LnBwdTask*)L.table_l, L.n_l, L.tile_w, L.tile_l,
-                                       (const MiscTask*)L.table_m, L.tile_m, side_prio, tl);
-                else if (L.side)
+                                       (const MiscTask*)L.table_m, L.tile_m, tl);
+                else
                     FQL_LAUNCH(fql_side_kernel, dim3(L.grid), dim3(FQL_THREADS), L.lds, s, (const GemmTask*)L.table, L.ntasks,
                                        (const WgradTask*)L.table_w, L.n_w, (const LnBwdTask*)L.table_l, L.n_l, L.tile_w, L.tile_l,
-                                       (const MiscTask*)L.table_m, L.tile_m, side_prio, tl);
-                else
-                    FQL_LAUNCH(fql_gemm64_kernel, dim3(L.grid), dim3(FQL_THREADS), L.lds, s, (const GemmTask*)L.table, L.ntasks);
-                break;
-            case OP_WGRAD:
-                FQL_LAUNCH(fql_wgrad_kernel, dim3(L.grid), dim3(FQL_THREADS), 0, s, (const WgradTask*)L.table, L.ntasks);
-                break;
-            case OP_LNBWD:
-                FQL_LAUNCH(fql_lnbwd_kernel, dim3(L.grid), dim3(FQL_THREADS), 0, s, (const LnBwdTask*)L.table, L.ntasks);
+                                       (const MiscTask*)L.table_m, L.tile_m, tl);
                 break;
             case OP_PREP:
                 { PrepArgs pa = L.op.prep; pa.tl = tl; FQL_LAUNCH(fql_prep_kernel, dim3((pa.B + 3) / 4), dim3(FQL_THREADS), 0, s, pa); }
                 break;
-            case OP_POSTOS:
-                FQL_LAUNCH(fql_post_onestep_kernel, dim3(1), dim3(FQL_THREADS), 0, s, L.op.postos);
-                break;
-            case OP_PEC: {
-                const PecArgs& a = L.op.pec;
-                const int T = cfg.actor_hidden[0] / 32;
-                const size_t lds = ((size_t)16 * (cfg.actor_hidden[0] + 4) + 1024 + 576 + 512 * (size_t)a.ntile) * sizeof(float);
-                if (cfg.actor_hidden[0] == 512) FQL_LAUNCH((fql_euler_persistent_kernel<512>), dim3(a.nteams * T), dim3(FQL_THREADS), lds, s, a);
-                else FQL_LAUNCH((fql_euler_persistent_kernel<256>), dim3(a.nteams * T), dim3(FQL_THREADS), lds, s, a);
-                break;
-            }
             case OP_EULER_FIN:
                 FQL_LAUNCH(fql_euler_finish_kernel, dim3((L.op.ef.M * L.op.ef.ad + FQL_THREADS - 1) / FQL_THREADS), dim3(FQL_THREADS), 0, s, L.op.ef);
-                break;
-            case OP_LOSS_CRITIC:
-                FQL_LAUNCH(fql_loss_critic_kernel, dim3(1), dim3(FQL_THREADS), 0, s, L.op.lc);
-                break;
-            case OP_LOSS_Q:
-                FQL_LAUNCH(fql_loss_q_kernel, dim3(1), dim3(FQL_THREADS), 0, s, L.op.lq);
-                break;
-            case OP_LOSS_BC:
-                FQL_LAUNCH(fql_loss_bc_kernel, dim3(1), dim3(FQL_THREADS), 0, s, L.op.lb);
                 break;
             case OP_LOSS_ACTOR:
                 FQL_LAUNCH(fql_loss_actor_kernel, dim3(1), dim3(FQL_THREADS), 0, s, L.op.la);
@@ -2041,7 +1862,7 @@ struct fql_engine {
             case OP_CONV_U8:
                 if (L.pool_fused && cfg.precision == 2) FQL_LAUNCH(fql_conv3x3_pool_split_kernel, dim3(L.grid), dim3(FQL_THREADS), L.lds, s, (const ConvArgs*)L.table, L.ntasks);
                 else if (L.pool_fused) FQL_LAUNCH(fql_conv3x3_pool_kernel, dim3(L.grid), dim3(FQL_THREADS), L.lds, s, (const ConvArgs*)L.table, L.ntasks);
-                else if (cfg.precision == 2 && u8_split) FQL_LAUNCH(fql_conv3x3_u8_split_kernel, dim3(L.grid), dim3(FQL_THREADS), L.lds, s, (const ConvArgs*)L.table, L.ntasks);
+                else if (cfg.precision == 2) FQL_LAUNCH(fql_conv3x3_u8_split_kernel, dim3(L.grid), dim3(FQL_THREADS), L.lds, s, (const ConvArgs*)L.table, L.ntasks);
                 else
                 FQL_LAUNCH(fql_conv3x3_u8_kernel, dim3(L.grid), dim3(FQL_THREADS), L.lds, s, (const ConvArgs*)L.table, L.ntasks);
                 break;
@@ -2073,18 +1894,14 @@ struct fql_engine {
             case OP_CHAIN: {
                 ChainArgs ca = L.op.chain; ca.tl = tl;
                 {   // XCD-aware tile order of the chain launches (16-row tiles x 32-column tiles)
-                    constexpr bool xcd_order = true;
                     const int ntm = ca.M / 16, ntn = cfg.actor_hidden[0] / 32;
                     ca.xg = 0;
-                    if (xcd_order) {
-                        constexpr int gm_env = 0;
-                        double best = 1e30;
-                        for (int gm : {1, 2, 4, 8}) {
-                            const int gn = 8 / gm;
-                            if (ntm % gm || ntn % gn || (gm_env && gm != gm_env)) continue;
-                            const double cost = (double)gn * ca.M + (double)gm * cfg.actor_hidden[0];
-                            if (cost < best) { best = cost; ca.xg = gm; }
-                        }
+                    double best = 1e30;
+                    for (int gm : {1, 2, 4, 8}) {
+                        const int gn = 8 / gm;
+                        if (ntm % gm || ntn % gn) continue;
+                        const double cost = (double)gn * ca.M + (double)gm * cfg.actor_hidden[0];
+                        if (cost < best) { best = cost; ca.xg = gm; }
                     }
                 }
                 if (cfg.precision == 2 && ca.variant != 3) {   // (variant D keeps fp32 operands: its dZ / W arrive as fp32 and splitting both in the kernel costs what the MFMAs save)
@@ -2114,12 +1931,8 @@ struct fql_engine {
             case OP_HEAD_DGRAD:
                 FQL_LAUNCH(fql_head_dgrad_kernel, dim3((L.op.gemm.M / 16) * (L.op.gemm.N / 64)), dim3(FQL_THREADS), 0, s, L.op.gemm);
                 break;
-            case OP_XCHAIN:   // one workgroup per CU: 8 XCDs x 32 members
-                FQL_LAUNCH(fql_xchain_kernel, dim3(XCH_NGRP * XCH_NMEM), dim3(256), x_lds, s, L.op.xchain);
-                break;
             case OP_ADAM: {
                 AdamArgs a{P, G, Mu, Nu, P + n_train, d_chunks, d_state, d_partials, L.op.adam_c0, L.op.adam_polyak >= 0 ? L.op.adam_polyak : (int)critic_size, cfg.lr, cfg.tau, tl,
-                           use_pec ? (const unsigned*)(pec_epoch + pec_teams) : (xsync ? (const unsigned*)(xsync + 16 * 32) : nullptr),
                            L.op.adam_n1 > 0 ? L.op.adam_n : -1, L.op.adam_c1};
                 FQL_LAUNCH(fql_adam_kernel, dim3(L.op.adam_n < 0 ? n_chunks : L.op.adam_n + L.op.adam_n1), dim3(FQL_THREADS), 0, s, a);
                 break;
@@ -2161,8 +1974,9 @@ struct fql_engine {
                                    FinalizeArgs{d_state, d_chunks, d_partials, d_leaf_range, n_chunks, n_train_leaves, L.op.fin_mode & 1, tl},
                                    (L.op.fin_mode >> 1) & 1);
                 break;
-            case OP_NUM_TYPES:
-                break;
+            case OP_WGRAD: case OP_LNBWD: case OP_POSTOS: case OP_LOSS_CRITIC: case OP_LOSS_Q: case OP_LOSS_BC:   // (inside OP_GEMM64 launches)
+            case OP_PEC: case OP_XCHAIN: case OP_NUM_TYPES:
+                throw HipError{"internal: op type " + std::to_string((int)L.type) + " has no launch of its own"};
         }
     }
 
@@ -2534,16 +2348,15 @@ struct fql_engine {
             op.type = OP_PREP;
             op.prep = PrepArgs{d_src, st, seed, B, od, ad, inp_c, inp_b, ap, X_os, X_bc, X_eu, X_c1, X_c2, X_ct, vel, w_rew, w_mask, w_act,
                                fused_euler ? X_e0 : nullptr, nullptr, nullptr, nullptr, nullptr};
-            op.prep.tl = -1; op.prep.part = 0; op.prep.xsync = use_xchain ? xsync : nullptr;
+            op.prep.tl = -1; op.prep.part = 0;
             // One batch-assembly launch per lane (state agents): the side lane then has no dependency on the critical lane at the
             // start of the update.  (On this runtime a graph branch whose first node waits for a node of the other branch starts
             // only ~16 launches of that branch later: profiles/r02_timeline_concurrent.txt.)
-            constexpr bool split_prep = true;
             if (visual) {
                 op.prep.E_c = eb_c.E; op.prep.E_t = eb_t.E; op.prep.E_bc = eb_bc.E; op.prep.E_os = eb_os.E;
                 op.reads = {eb_c.E, eb_t.E, eb_bc.E, eb_os.E};
             }
-            if (split_prep && !visual && !split_build) {
+            if (!visual && !split_build) {
                 Op a = op, b = op;
                 a.prep.part = 1;
                 a.writes = {X_eu};
@@ -2564,8 +2377,7 @@ struct fql_engine {
         // the critic-loss passes, the BC pass, every weight gradient and Adam go to lane 2.  Edges between the two forked
         // lanes run 1 -> 2 only: torch's bundled HIP runtime recurses forever in hipStreamEndCapture when two forked streams wait
         // on each other in BOTH directions (hip::Stream::EndCapture walks the cycle; the system ROCm 7.2 runtime does not).
-        constexpr bool lanes3_env = true;
-        const bool lanes3 = lanes3_env && !visual && !split_build;
+        const bool lanes3 = !visual && !split_build;
         const int fill_lane = lanes3 ? 2 : 1;
         if (!split_build) fill_lane_full = fill_lane;
         wide_tiles = lanes3;
@@ -2585,8 +2397,7 @@ struct fql_engine {
         for (int e = 0; e < 2; ++e) emit_forward(pr, p_c1[e], with_grads);
         // three lanes: the target-critic pass rides on lane 1 (its action block comes from the one-step forward there, and lane 1 is otherwise
         // idle once the Q-gradient path has ended): 2500 -> 2580 updates/s in steady state
-        constexpr int ct_lane3 = -1;   // (three-lane programs only: the others have no lane 2)
-        place("ct", lanes3 ? (ct_lane3 >= 0 ? ct_lane3 : 1) : fill_lane, true);
+        place("ct", lanes3 ? 1 : fill_lane, true);
         for (int e = 0; e < 2; ++e) emit_forward(pr, p_ct[e], false);
         place("c1", fill_lane, true);
         {
@@ -2602,11 +2413,10 @@ struct fql_engine {
         }
         // The critic's weight gradients gate nothing but Adam: they are emitted after the Q-gradient chain, whose levels on lane 1
         // then carry fewer tiles and finish earlier - and with them the one-step actor's backward tail (2127 -> 2170 updates/s;
-        // deferring the BC flow's too: 2161, the critic's whole backward chain: 2050).  FQL_LATE_WGRAD: 0 off, 1 both, 2 critic, 3 bc.
-        constexpr int late_wgrad_env = -1;
-        const int late_wgrad = late_wgrad_env >= 0 ? late_wgrad_env : (lanes3 ? 0 : 2);   // (three lanes: they are on lane 2, out of the Q-gradient path's launches anyway)
+        // deferring the BC flow's too: 2161, the critic's whole backward chain: 2050).  Not in three-lane programs: there they are on lane 2, out of
+        // the Q-gradient path's launches anyway.
         std::vector<Op> late_ops;
-        if ((late_wgrad == 1 || late_wgrad == 2) && with_grads) defer_wgrads = &late_ops;
+        if (!lanes3 && with_grads) defer_wgrads = &late_ops;
         if (with_grads)
             for (int e = 0; e < 2; ++e) emit_backward(pr, p_c1[e], 0, B, true, visual);
         // (not in the data-parallel split program: there lane 1 must finish bucket 0 without waiting for lane 0's tail)
@@ -2615,16 +2425,14 @@ struct fql_engine {
             place("enc", 1, true);
             emit_encoder_backward(pr, eb_c, 0, B, p_c1[0].dx0, p_c1[1].dx0, nets[NET_C0].in_p());
         }
-        // BC flow-matching pass (fql.py:52-59).  FQL_BC_LATE=<lane> (three-lane programs): emitted BEHIND the Q-gradient path on that lane instead of
-        // on lane 2 in front of it - lane 1 idles from the end of the Q-gradient path to the end of the update while lane 2 carries the longest tail.
-        constexpr int bc_late_env = 0;
-        const int bc_late = (lanes3 && with_grads) ? bc_late_env : 0;
-        auto emit_bc = [&](int bc_lane) {
+        // BC flow-matching pass (fql.py:52-59), on lane 2 in front of the Q-gradient path.  (Three lanes: emitting it BEHIND the Q-gradient path
+        // instead - lane 1 idles from the end of that path to the end of the update while lane 2 carries the longest tail - was tried and not kept.)
+        {
             // (three lanes: the BC flow's FORWARD on lane 1 in front of the one-step pass, its loss and backward stay on lane 2 - -0.5 .. -1.0 % per
             // fp32 update in three in-process A/Bs under AQL dispatch, nothing in bf16x3; experiments/lane_sweep.sh)
-            place("bcf", lanes3 ? 1 : bc_lane, true);
+            place("bcf", lanes3 ? 1 : fill_lane, true);
             emit_forward(pr, p_bc, with_grads);
-            place("bc", bc_lane, true);
+            place("bc", fill_lane, true);
             {
                 Op op{};
                 op.type = OP_LOSS_BC;
@@ -2634,14 +2442,13 @@ struct fql_engine {
                 if (with_grads) op.writes.push_back(p_bc.dz.back());
                 push(pr, op);
             }
-            defer_wgrads = ((late_wgrad == 1 || late_wgrad == 3) && with_grads) ? &late_ops : nullptr;
+            defer_wgrads = nullptr;
             if (with_grads) emit_backward(pr, p_bc, 0, B, true, visual);
             if (with_grads && visual && !enc_align) {
                 place("enc", 1, true);
                 emit_encoder_backward(pr, eb_bc, 0, B, p_bc.dx0, nullptr, nets[NET_BC].in_p());
             }
-        };
-        if (!bc_late) emit_bc(fill_lane);
+        }
         // Q term: critic(obs, clip(actor_actions)) with stored params, input-differentiable (fql.py:69-76)
         place("c2", 1, true);
         for (int e = 0; e < 2; ++e) emit_forward(pr, p_c2[e], with_grads);
@@ -2661,27 +2468,22 @@ struct fql_engine {
         defer_wgrads = nullptr;
         if (with_grads) {
             // two lanes: in phase with the c1 chain (shared launches); three lanes: on its own, as early as its inputs exist
-            constexpr bool c2_align = true;
-            for (int e = 0; e < 2; ++e) emit_backward(pr, p_c2[e], 0, B, false, true, (c2_align && !lanes3) ? I_CR : nullptr);
+            for (int e = 0; e < 2; ++e) emit_backward(pr, p_c2[e], 0, B, false, true, !lanes3 ? I_CR : nullptr);
         }
         for (Op& w : late_ops) {   // the critic's and the BC flow's weight gradients only after the Q-gradient chain (they gate nothing)
             w.reads.push_back(p_c2[0].dx0); w.reads.push_back(p_c2[1].dx0);
             emit_lane = w.lane;
             push(pr, w);
         }
-        if (bc_late) emit_bc(bc_late);
         // Euler chain through the BC flow (fql.py:155-171): flow_steps sequential forwards
         place("eu", 0, false);
         const int fs = cfg.flow_steps;
         // The last Euler step's target is finished inside the one-step head dgrad's prologue (GF_A_EULFIN: one launch less on the critical lane,
         // bit-identical target).  The 16 partial loads per element lengthen the prologue of all 256 workgroups by most of what the launch boundary
         // saves: -0.45 % per update in both orders of an in-process A/B (experiments/ab_inproc.py; round 2, under the graph's host cost, saw nothing).
-        constexpr bool fuse_ef_env = true;
-        euler_finish_fused = fuse_ef_env && with_grads && !cfg.actor_layer_norm && !use_pec && !use_xchain && fused_euler && use_chain &&
-                             fs > 1 && vp_tiles <= 32;
-        if (use_xchain) emit_euler_xcd(pr);
-        else if (use_pec) emit_euler_persistent(pr);
-        else if (fused_euler && use_chain) emit_euler_chain(pr);
+        // (A persistent one-launch chain was measured slower than these launches at every batch size: DESIGN.md section 9.)
+        euler_finish_fused = with_grads && !cfg.actor_layer_norm && fused_euler && use_chain && fs > 1 && vp_tiles <= 32;
+        if (fused_euler && use_chain) emit_euler_chain(pr);
         else if (fused_euler) emit_euler_fused(pr);
         else
         for (int s = 0; s < fs; ++s)
@@ -2689,8 +2491,7 @@ struct fql_engine {
                          (float)(s + 1) / (float)fs);
         // The actor-loss gradient is built inside the one-step actor's head dgrad (GF_A_LOSSACT), so the loss kernel only
         // reports scalars and leaves the critical path (it rides on lane 1): 2083 -> 2130 updates/s.
-        constexpr bool fuse_la_env = true;
-        const bool fuse_la = with_grads && fuse_la_env && !cfg.actor_layer_norm;
+        const bool fuse_la = with_grads && !cfg.actor_layer_norm;
         Op la_op{};
         int la_lane = 0;
         {
@@ -2706,10 +2507,9 @@ struct fql_engine {
                 op.reads.push_back(p_c2[0].dx0); op.reads.push_back(p_c2[1].dx0);
                 op.writes.push_back(p_os_bwd.dz.back());
             }
-            // FQL_TAIL_MERGE (see adam_for; default on): this kernel, first of lane 2's tail, also takes the edge to the end of lane 1's Q-gradient chain that
-            // the critic's Adam behind it needs (write after read of the critic's kernels) - both cross-lane waits of the tail on ONE launch
-            constexpr bool tail_merge = true;   // default on
-            if (tail_merge && with_grads && !kgrad) { op.reads.push_back(p_c2[0].dx0); op.reads.push_back(p_c2[1].dx0); }
+            // this kernel, first of lane 2's tail, also takes the edge to the end of lane 1's Q-gradient chain that the critic's Adam
+            // behind it needs (write after read of the critic's kernels) - both cross-lane waits of the tail on ONE launch (as in adam_for)
+            if (with_grads && !kgrad) { op.reads.push_back(p_c2[0].dx0); op.reads.push_back(p_c2[1].dx0); }
             const int keep = emit_lane;
             if (fuse_la && !split_build) emit_lane = fill_lane;
             if (euler_finish_fused) { la_op = op; la_lane = emit_lane; }   // pushed behind the head dgrad, which now WRITES the target
@@ -2719,10 +2519,9 @@ struct fql_engine {
         if (with_grads) {
             // The one-step actor's weight gradients gate the last Adam launch.  On lane 1 they would queue behind the deferred critic
             // weight gradients and the other two Adam launches; emitted here as ONE launch on lane 0 behind the last dgrad they
-            // cost ~10 us of tail instead.  (FQL_OS_WGRAD_SIDE=1: the old placement.)
-            constexpr bool os_w_side = false;
+            // cost ~10 us of tail instead.  (Lane 1 was the earlier placement.)
             std::vector<Op> os_w;
-            if (!os_w_side) defer_wgrads = &os_w;
+            defer_wgrads = &os_w;
             const size_t first = pr.ops.size();
             emit_backward(pr, p_os_bwd, B, B, true, visual);
             defer_wgrads = nullptr;
@@ -2766,13 +2565,11 @@ struct fql_engine {
                 push(pr, la_op);
                 emit_lane = keep;
             }
-            // Three lanes: lane 2 is idle by the time the tail runs, so each layer's weight gradient goes there as soon as its dz exists
-            // (beside the remaining dgrads of the tail); only the first layer's small one is left behind the last dgrad.
-            constexpr int os_w_l2_env = -1;
-            const bool os_w_l2 = lanes3 && (os_w_l2_env >= 0 ? os_w_l2_env != 0 : false);
+            // (Three lanes: sending each layer's weight gradient to lane 2, idle by the time the tail runs, as soon as its dz exists was
+            // tried and not kept.)
             for (Op& w : os_w) {
-                if (!os_w_l2) w.reads.push_back(p_os_bwd.dz[0]);   // after the last dgrad: all five in one launch
-                emit_lane = os_w_l2 ? 2 : 0;
+                w.reads.push_back(p_os_bwd.dz[0]);   // after the last dgrad: all five in one launch
+                emit_lane = 0;
                 push(pr, w);
             }
             emit_lane = 0;
@@ -2809,10 +2606,9 @@ struct fql_engine {
                 a.adam_c0 = 0; a.adam_n = -1;
                 for (int mm = 0; mm < 3; ++mm) a.writes.push_back(d_partials + mod_chunk0[mm] * 4);
             }
-            // FQL_TAIL_MERGE (default on; =0 off): the critic's Adam, the first launch of lane 2's tail, also waits for the Euler target the actor-loss kernel behind it reads -
+            // the critic's Adam, the first launch of lane 2's tail, also waits for the Euler target the actor-loss kernel behind it reads -
             // one launch with two cross-lane edges instead of two launches with one each (every such edge costs the waiting lane ~10 us)
-            constexpr bool tail_merge = true;   // default on
-            if (tail_merge && m == 2 && tgt) a.reads.push_back(tgt);
+            if (m == 2 && tgt) a.reads.push_back(tgt);
             for (int mm : {m, m2}) if (visual && mm >= 0) {
                 const int m = mm;
                 const int ei = m == 2 ? ENC_C : (m == 0 ? ENC_BC : ENC_OS);
@@ -2895,14 +2691,9 @@ struct fql_engine {
     void build_full_program(Program& pr) {
         build_step_program(pr, true);
         DevState* st = d_state;
-        // the critic's and the BC flow's Adam as ONE launch (FQL_ADAM_MERGE=0: two): both sit at the end of the same lane behind the same
+        // the critic's and the BC flow's Adam as ONE launch (rather than two): both sit at the end of the same lane behind the same
         // dependencies, and every graph node costs the host 3-4 us
-        constexpr bool adam_merge = true;
-        if (adam_merge) adam_for(pr, 2, {NET_C0, NET_C1, NET_BC}, fill_lane_full, 0);
-        else {
-            adam_for(pr, 2, {NET_C0, NET_C1}, fill_lane_full);
-            adam_for(pr, 0, {NET_BC}, fill_lane_full);
-        }
+        adam_for(pr, 2, {NET_C0, NET_C1, NET_BC}, fill_lane_full, 0);
         emit_wfrag(pr);   // lane 1, behind the BC flow's Adam: the next update's chain reads the copies
         adam_for(pr, 1, {NET_OS}, 0);
         Op f{};
@@ -2995,7 +2786,7 @@ struct fql_engine {
         vel = dalloc(W, (size_t)B * ap);
         w_rew = dalloc(W, B); w_mask = dalloc(W, B);
         X_os = X_eu = X_c2 = X_ct = X_e0 = C0 = Vpart = w_act = tgt = nullptr;
-        fused_euler = use_pec = use_xchain = euler_finish_fused = false;
+        fused_euler = euler_finish_fused = false;
         p_v = make_pass(W, NET_OS, 2 * B, X_v, true, false);
         p_bc = make_pass(W, NET_BC, B, X_bc, true, false);
         for (int e = 0; e < 2; ++e) {
@@ -3125,7 +2916,7 @@ struct fql_engine {
         w_act = dalloc(W, (size_t)B * ap); w_nact = dalloc(W, (size_t)B * ap); w_noise = dalloc(W, (size_t)B * ap);
         w_rew = dalloc(W, B); w_mask = dalloc(W, B);
         X_os = X_bc = X_eu = X_c2 = X_ct = X_e0 = C0 = Vpart = vel = tgt = X_v = nullptr;
-        fused_euler = use_pec = use_xchain = euler_finish_fused = false;
+        fused_euler = euler_finish_fused = false;
         p_a = make_pass(W, NET_BC, B, X_a, true, false);
         p_ta = make_pass(W, NET_TA, B, X_ta, false, false);
         for (int e = 0; e < 2; ++e) {
@@ -3201,7 +2992,6 @@ struct fql_engine {
         aql_full = AqlProgram{};
         if (aql_critic.kernargs) { hipFree(aql_critic.kernargs); }
         aql_critic = AqlProgram{};
-        use_xchain = false; xsync = nullptr; xvp = nullptr; x_stamps = nullptr;
         free_split();
         for (void* p : ws_allocs) hipFree(p);
         ws_allocs.clear();
@@ -3237,57 +3027,6 @@ struct fql_engine {
                 vp_tiles = (nb.layers[nh - 1].out_p / 16 + 1) / 2;
                 if (vp_tiles > 32) fused_euler = false;
                 Vpart = dalloc(W, (size_t)std::max(vp_tiles, 1) * B * ap);
-                // persistent chain: one launch for all flow_steps x layers; needs every workgroup resident (1 per CU)
-                const int H = nb.layers[0].out_p;
-                bool same = nh == 4 && (H == 512 || H == 256);
-                for (int l = 0; l < nh; ++l) same = same && nb.layers[l].out_p == H && nb.layers[l].out == H;
-                // opt-in (FQL_PEC=1): alone the chain drops from 331 to 220 us, but beside the other lanes the update time is
-                // unchanged on this box (the lanes barely overlap), so the default stays with plain launches
-                // teams: as many as fit one workgroup per CU; each takes B / 16 / teams row tiles
-                pec_teams = std::min(B / 16, num_cus / (H / 32));
-                while (pec_teams > 1 && (B / 16) % pec_teams) --pec_teams;
-                // default: on when every team has >= 4 row tiles to walk per phase (B >= 1024: +5 %); at B = 256 / 512 the chain
-                // is shorter but the update is not.  FQL_PEC=1 / 0 forces it on / off.
-                const int pec_tiles = pec_teams >= 1 ? B / 16 / pec_teams : 0;
-                // opt-in only (FQL_PEC=1): since round 2 the launch-based chain on fql_chain_kernel is faster at every batch size
-                // measured (B = 1024: 989 against 970 updates/s), and a persistent kernel that needs co-residency stays off by default
-                const bool pec_want = getenv("FQL_PEC") ? atoi(getenv("FQL_PEC")) != 0 : false;
-                use_pec = fused_euler && same && pec_want && pec_teams >= 1 && pec_tiles <= PEC_MAX_TILES && cfg.flow_steps <= 20;
-                if (use_pec) {
-                    // every workgroup of the persistent chain spins on its team mates: all of them must be resident at once
-                    const size_t lds = ((size_t)16 * (H + 4) + 1024 + 576 + 512 * (size_t)pec_tiles) * sizeof(float);
-                    int per_cu = 0;
-                    const hipError_t oe = H == 512 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fql_euler_persistent_kernel<512>, FQL_THREADS, lds)
-                                                   : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fql_euler_persistent_kernel<256>, FQL_THREADS, lds);
-                    if (oe != hipSuccess || per_cu < 1 || pec_teams * (H / 32) > num_cus) {   // one workgroup per CU: never rely on a second slot
-                        (void)hipGetLastError();
-                        use_pec = false;
-                    }
-                }
-                if (use_pec) {
-                    pec_epoch = (unsigned*)dalloc(W, (size_t)pec_teams + 1);
-                    for (int i = 0; i < 2; ++i) pec_g[i] = (fql_u64*)dalloc(W, (size_t)B * H * 2);
-                    pec_vg = (fql_u64*)dalloc(W, (size_t)(H / 32) * B * 16 * 2);
-                }
-            }
-        }
-        use_xchain = xchain_eligible();
-        if (use_xchain) {
-            const Net& nb = nets[NET_BC];
-            x_lds = (size_t)FQL_XCHAIN_LDS_FLOATS * sizeof(float);
-            int per_cu = 0;   // every workgroup waits for its XCD's other 31: all 256 must be resident, one per CU
-            const void* kf = (const void*)fql_xchain_kernel;
-            hipError_t oe = hipFuncSetAttribute(kf, hipFuncAttributeMaxDynamicSharedMemorySize, (int)x_lds);
-            if (oe == hipSuccess) oe = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fql_xchain_kernel, 256, x_lds);
-            if (oe != hipSuccess || per_cu < 1) {
-                (void)hipGetLastError();
-                use_xchain = false;
-            } else {
-                xsync = (unsigned*)dalloc(W, 17 * 32);
-                xvp = dalloc(W, (size_t)XCH_NMEM * B * 16);
-#ifdef FQL_XSTAMPS
-                x_stamps = (unsigned long long*)dalloc(W, (size_t)256 * 64 * 2 * 2);
-#endif
             }
         }
         if (visual) {
@@ -4470,11 +4209,6 @@ int fql_info_wait(fql_handle h, uint64_t ticket, float* info13_host) {
         const int slot = (int)(ticket % fql_engine::kInfoRing);
         HIP_CHECK(hipEventSynchronize(h->info_ev[slot]));
         std::memcpy(info13_host, h->h_info_ring[slot], FQL_NUM_INFO * sizeof(float));
-        if (h->use_pec) {   // (opt-in persistent chain) a hand-off time-out makes the optimizer skip the update: say so at the first read
-            unsigned e = 0;
-            HIP_CHECK(hipMemcpy(&e, h->pec_epoch + h->pec_teams, sizeof e, hipMemcpyDeviceToHost));
-            if (e) throw HipError{"persistent Euler chain: a team hand-off timed out (that update and every later one were not applied)"};
-        }
     });
 }
 
@@ -4492,11 +4226,6 @@ int fql_read_info(fql_handle h, float* info13_host) {
     FQL_TRY(h, {
         HIP_CHECK(hipDeviceSynchronize());
         HIP_CHECK(hipMemcpy(info13_host, &h->d_state->info[0], FQL_NUM_INFO * sizeof(float), hipMemcpyDeviceToHost));
-        if (h->use_pec) {
-            unsigned e = 0;
-            HIP_CHECK(hipMemcpy(&e, h->pec_epoch + h->pec_teams, sizeof e, hipMemcpyDeviceToHost));
-            if (e) throw HipError{"persistent Euler chain: a team hand-off timed out (results of this update are invalid)"};
-        }
     });
 }
 
@@ -4820,10 +4549,6 @@ const std::map<const void*, MultiEntry>& multi_entries() {
 #define FQL_MULTI(single, multi, A) \
     e[(const void*)(single)] = MultiEntry{[](dim3 g, dim3 b, size_t l, hipStream_t s, const void* a) { hipLaunchKernelGGL(multi, g, b, l, s, (const A*)a); }, sizeof(A)}
         FQL_MULTI(fql_prep_kernel, fql_prep_multi_kernel, PrepArgs);
-        FQL_MULTI(fql_post_onestep_kernel, fql_post_onestep_multi_kernel, PostOsArgs);
-        FQL_MULTI(fql_loss_critic_kernel, fql_loss_critic_multi_kernel, LossCriticArgs);
-        FQL_MULTI(fql_loss_q_kernel, fql_loss_q_multi_kernel, LossQArgs);
-        FQL_MULTI(fql_loss_bc_kernel, fql_loss_bc_multi_kernel, LossBcArgs);
         FQL_MULTI(fql_loss_actor_kernel, fql_loss_actor_multi_kernel, LossActorArgs);
         FQL_MULTI(fql_euler_finish_kernel, fql_euler_finish_multi_kernel, EulerFinishArgs);
         FQL_MULTI(fql_head_dgrad_kernel, fql_head_dgrad_multi_kernel, GemmTask);
@@ -4844,7 +4569,7 @@ const std::map<const void*, MultiEntry>& multi_entries() {
     return m;
 }
 
-bool is_table_launch(OpType t) { return t == OP_GEMM || t == OP_GEMM64 || t == OP_WGRAD || t == OP_LNBWD || t == OP_WFRAG; }
+bool is_table_launch(OpType t) { return t == OP_GEMM || t == OP_GEMM64 || t == OP_WFRAG; }
 
 struct GLaunch {
     int lane = 0;
@@ -4911,7 +4636,7 @@ struct fql_group_s {
                 const Launch& L = m[k]->prog_full.launches[li];
                 if (L0.type == OP_WFRAG) {
                     tg.push_back(m[k]->d_wfrag); ng.push_back(m[k]->wfrag_n); sg.push_back(cg); cg += m[k]->wfrag_grid; ntot += m[k]->wfrag_n;
-                } else if (L.side) {
+                } else if (L0.type == OP_GEMM64) {
                     tg.push_back(L.table); ng.push_back(L.ntasks); sg.push_back(cg); cg += L.tile_w;
                     tw.push_back(L.table_w); nw.push_back(L.n_w); sw.push_back(cw); cw += L.tile_l - L.tile_w;
                     tl.push_back(L.table_l); nl.push_back(L.n_l); sl.push_back(cl); cl += L.tile_m - L.tile_l;
@@ -4922,7 +4647,7 @@ struct fql_group_s {
             }
             if (L0.type == OP_WFRAG) {
                 F.table = fuse<WfragTask>(tg, ng, sg); F.ntasks = ntot; F.grid = cg;
-            } else if (L0.side) {
+            } else if (L0.type == OP_GEMM64) {
                 F.table = fuse<GemmTask>(tg, ng, sg);
                 F.table_w = fuse<WgradTask>(tw, nw, sw);
                 F.table_l = fuse<LnBwdTask>(tl, nl, sl);
@@ -4931,9 +4656,7 @@ struct fql_group_s {
                 for (int k = 0; k < K; ++k) { F.ntasks += ng[k]; F.n_w += nw[k]; F.n_l += nl[k]; }
                 F.tile_w = cg; F.tile_l = cg + cw; F.tile_m = cg + cw + cl; F.grid = F.tile_m + cm;
             } else {
-                if (L0.type == OP_WGRAD) F.table = fuse<WgradTask>(tg, ng, sg);
-                else if (L0.type == OP_LNBWD) F.table = fuse<LnBwdTask>(tg, ng, sg);
-                else F.table = fuse<GemmTask>(tg, ng, sg);
+                F.table = fuse<GemmTask>(tg, ng, sg);
                 F.ntasks = ntot; F.grid = cg;
             }
             G.L = F;
@@ -5014,7 +4737,6 @@ void group_check(const fql_handle* members, int k) {
         if (h->cfg.precision != 0) invalid("fql_group_create: member %d has precision %d (groups take fp32 members only)", i, h->cfg.precision);
         if (h->began) invalid("fql_group_create: member %d is between fql_update_begin and fql_update_end", i);
         if (!h->prog_full.exec) invalid("fql_group_create: member %d has no single-graph update program", i);
-        if (h->use_pec || h->use_xchain) invalid("fql_group_create: member %d runs a persistent Euler chain (FQL_PEC / FQL_XCHAIN): not groupable", i);
         fql_config a = h->cfg, b = members[0]->cfg;
         a.alpha = b.alpha = 0.f;
         a.batch_size = b.batch_size = 0;
@@ -5025,7 +4747,7 @@ void group_check(const fql_handle* members, int k) {
         if (p.launches.size() != p0.launches.size()) invalid("fql_group_create: member %d's update has %zu launches, member 0's %zu", i, p.launches.size(), p0.launches.size());
         for (size_t li = 0; li < p.launches.size(); ++li) {
             const Launch &L = p.launches[li], &L0 = p0.launches[li];
-            if (L.type != L0.type || L.lane != L0.lane || L.grid != L0.grid || L.waits != L0.waits || L.side != L0.side || L.tmt2 != L0.tmt2 ||
+            if (L.type != L0.type || L.lane != L0.lane || L.grid != L0.grid || L.waits != L0.waits || L.tmt2 != L0.tmt2 ||
                 L.kbig != L0.kbig || L.euler != L0.euler || L.record_after != L0.record_after || L.lds != L0.lds)
                 invalid("fql_group_create: launch %zu of member %d differs from member 0's (type %d/%d, lane %d/%d, grid %d/%d)", li, i, (int)L.type,
                         (int)L0.type, L.lane, L0.lane, L.grid, L0.grid);

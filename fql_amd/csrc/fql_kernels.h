@@ -808,27 +808,21 @@ __device__ __forceinline__ void gemm16_body(const GemmTask& T, float* lds) {
 #endif
 }
 
-// TMT2: the launch contains tasks with two row tiles per workgroup; KBIG: some task has K > 512.  Separate
-// kernels so the common case (K <= 512) keeps its register count (and with it two workgroups per CU).
+// KBIG: some task has K > 512.  Separate kernels so the common case (K <= 512) keeps its register count (and with it
+// two workgroups per CU).
 #ifndef FQL_GEMM_WAVES
 #define FQL_GEMM_WAVES 1
 #endif
 // (Passing the task by value in the kernel-argument segment was tried for single-task launches: slower -- the
 // kernarg segment is host-visible memory and a 200-byte struct costs more than one hop through the HBM table.)
-template <bool TMT2, bool KBIG>
+template <bool KBIG>
 __global__ __launch_bounds__(FQL_THREADS, FQL_GEMM_WAVES) void fql_gemm16_kernel(const GemmTask* __restrict__ tasks, int ntasks, int tl) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     tl_enter(tl);
     const GemmTask& T = tasks[find_task(tasks, ntasks, blockIdx.x)];
-    if (TMT2 && T.tmt == 2) {
-        if (T.K <= 128) gemm16_body<2, 2, false>(T, lds);
-        else if (!KBIG || T.K <= 512) gemm16_body<8, 2, false>(T, lds);
-        else gemm16_body<16, 2, false>(T, lds);
-    } else {
-        if (T.K <= 128) gemm16_body<2, 1, false>(T, lds);
-        else if (!KBIG || T.K <= 512) gemm16_body<8, 1, false>(T, lds);
-        else gemm16_body<16, 1, false>(T, lds);
-    }
+    if (T.K <= 128) gemm16_body<2, 1, false>(T, lds);
+    else if (!KBIG || T.K <= 512) gemm16_body<8, 1, false>(T, lds);
+    else gemm16_body<16, 1, false>(T, lds);
     tl_exit(tl);
 }
 // Euler-chain launches (fused layer-0 build / head partial): own kernel so their registers do not tax the others
@@ -1558,12 +1552,6 @@ __device__ __forceinline__ void gemm_tile_dispatch(const GemmTask& T, float* lds
     }
 }
 
-__global__ __launch_bounds__(FQL_THREADS, 2) void fql_gemm64_kernel(const GemmTask* __restrict__ tasks, int ntasks) {
-    extern __shared__ __attribute__((aligned(16))) float lds[];
-    const int ti = find_task(tasks, ntasks, blockIdx.x);
-    gemm_tile_dispatch<true>(tasks[ti], lds);
-}
-
 // ------------------------------------------------------------------------------------------------
 // K9 wgrad: dW[Kin, N] = X^T dZ (contraction over the batch), db[n] = sum_m dZ[m, n]
 //   implied by jax.grad, utils/flax_utils.py:137.
@@ -1734,10 +1722,6 @@ __device__ __forceinline__ void wgrad_split_body(const WgradTask& T, int bid, fl
     }
     wgrad_finish<1>(T, lds, acc, bs, tk, k0, n0, ntv, true);
 }
-__global__ __launch_bounds__(FQL_THREADS) void fql_wgrad_kernel(const WgradTask* __restrict__ tasks, int ntasks) {
-    __shared__ __attribute__((aligned(16))) float lds_w[FQL_WGRAD_LDS_FLOATS];
-    wgrad_body(tasks[find_task(tasks, ntasks, blockIdx.x)], blockIdx.x, lds_w);
-}
 
 // ------------------------------------------------------------------------------------------------
 // LayerNorm backward fused with GELU' (critic, utils/networks.py:56-58 reversed):
@@ -1839,13 +1823,6 @@ __device__ __forceinline__ void lnbwd_body(const LnBwdTask& T, int bid, float (*
         }
     }
 }
-__global__ __launch_bounds__(FQL_THREADS) void fql_lnbwd_kernel(const LnBwdTask* __restrict__ tasks, int ntasks) {
-    __shared__ float red[2][16][16];
-    const int ti = find_task(tasks, ntasks, blockIdx.x);
-    const LnBwdTask& T = tasks[ti];
-    if (T.dq) lnbwd_body<true>(T, blockIdx.x, red);
-    else lnbwd_body<false>(T, blockIdx.x, red);
-}
 
 // ------------------------------------------------------------------------------------------------
 // step state + batch assembly
@@ -1896,8 +1873,6 @@ struct PrepArgs {
     int tl;   // timeline id (diagnostics)
     int part; // 0: every output; 1: the critical lane's inputs only (X_eu, X_e0); 2: everything else (one launch per lane: neither lane
               //    then waits for the other at the start of the update)
-    unsigned* xsync;  // the XCD-resident Euler chain behind this launch (fql_xchain.h): its arrival flags and tickets (32-word slots 0..15; slot 16 is the
-                      // sticky error word) are zeroed here, or null
 };
 
 // agents/fql.py:52-56 (x_t, vel), :144-150 (noise), utils/datasets.py:64-100 (index draw + gather),
@@ -1911,8 +1886,6 @@ struct PrepArgs {
 #endif
 __device__ __forceinline__ void fql_prep_body(const PrepArgs& P) {
     tl_enter(P.tl);
-    if (P.xsync && blockIdx.x == 0 && P.part != 2)
-        for (int i = threadIdx.x; i < 16 * 32; i += FQL_THREADS) P.xsync[i] = 0u;
     const SrcDesc& S = *P.src;
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int b = blockIdx.x * 4 + wave;
@@ -2149,16 +2122,8 @@ __device__ __forceinline__ void fql_loss_actor_body(const LossActorArgs& P, floa
     }
 }
 
-__global__ __launch_bounds__(FQL_THREADS) void fql_post_onestep_kernel(PostOsArgs P) { __shared__ float sh[4]; fql_post_onestep_body(P, sh); }
-__global__ __launch_bounds__(FQL_THREADS) void fql_loss_critic_kernel(LossCriticArgs P) { __shared__ float sh[4]; fql_loss_critic_body(P, sh); }
-__global__ __launch_bounds__(FQL_THREADS) void fql_loss_q_kernel(LossQArgs P) { __shared__ float sh[4]; fql_loss_q_body(P, sh); }
-__global__ __launch_bounds__(FQL_THREADS) void fql_loss_bc_kernel(LossBcArgs P) { __shared__ float sh[4]; fql_loss_bc_body(P, sh); }
 __global__ __launch_bounds__(FQL_THREADS) void fql_loss_actor_kernel(LossActorArgs P) { __shared__ float sh[4]; fql_loss_actor_body(P, sh); }
 // multi-instance entry point (agent groups): blockIdx.y picks the member, its argument struct comes from a device array
-__global__ __launch_bounds__(FQL_THREADS) void fql_post_onestep_multi_kernel(const PostOsArgs* __restrict__ args) { __shared__ float sh[4]; const PostOsArgs P = args[blockIdx.y]; fql_post_onestep_body(P, sh); }
-__global__ __launch_bounds__(FQL_THREADS) void fql_loss_critic_multi_kernel(const LossCriticArgs* __restrict__ args) { __shared__ float sh[4]; const LossCriticArgs P = args[blockIdx.y]; fql_loss_critic_body(P, sh); }
-__global__ __launch_bounds__(FQL_THREADS) void fql_loss_q_multi_kernel(const LossQArgs* __restrict__ args) { __shared__ float sh[4]; const LossQArgs P = args[blockIdx.y]; fql_loss_q_body(P, sh); }
-__global__ __launch_bounds__(FQL_THREADS) void fql_loss_bc_multi_kernel(const LossBcArgs* __restrict__ args) { __shared__ float sh[4]; const LossBcArgs P = args[blockIdx.y]; fql_loss_bc_body(P, sh); }
 __global__ __launch_bounds__(FQL_THREADS) void fql_loss_actor_multi_kernel(const LossActorArgs* __restrict__ args) { __shared__ float sh[4]; const LossActorArgs P = args[blockIdx.y]; fql_loss_actor_body(P, sh); }
 
 // single-workgroup loss / metric tasks that ride in a side-lane launch
@@ -2188,7 +2153,6 @@ struct AdamArgs {
     int critic_size;
     float lr, tau;
     int tl;
-    const unsigned* err;   // persistent Euler chain only: its time-out word; set => the update's targets are invalid, leave the parameters alone
     int n0, chunk1;        // two modules in one launch: workgroups [0, n0) take chunks chunk0 + b, the rest chunk1 + (b - n0); n0 < 0: one range
 };
 __device__ __forceinline__ int f2ord(float f) {
@@ -2200,7 +2164,6 @@ __device__ __forceinline__ float ord2f(int i) { return __int_as_float(i >= 0 ? i
 __device__ __forceinline__ void fql_adam_body(const AdamArgs& A) {
     __shared__ float sh[4];
     tl_enter(A.tl);
-    if (A.err && __hip_atomic_load(A.err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) return;   // (null unless FQL_PEC=1)
     const int cidx = (A.n0 < 0 || (int)blockIdx.x < A.n0) ? (int)blockIdx.x + A.chunk0 : (int)blockIdx.x - A.n0 + A.chunk1;
     const AdamChunk ch = A.chunks[cidx];  // <= 4096 elements, offset and length multiples of 4
     // optax bias correction with count = adam_count + 1 (the counters advance in the finalize kernel afterwards)
@@ -2330,308 +2293,6 @@ __global__ __launch_bounds__(FQL_THREADS) void fql_euler_finish_kernel(EulerFini
 // multi-instance entry point (agent groups): blockIdx.y picks the member, its argument struct comes from a device array
 __global__ __launch_bounds__(FQL_THREADS) void fql_euler_finish_multi_kernel(const EulerFinishArgs* __restrict__ args) { const EulerFinishArgs P = args[blockIdx.y]; fql_euler_finish_body(P); }
 
-// ------------------------------------------------------------------------------------------------
-// Persistent Euler chain (agents/fql.py:155-171): the whole 10-step x (layers 0..3 + head) chain in ONE launch.
-//
-// A kernel boundary costs ~1.6 us plus ~2.5 us of cold first loads (the per-XCD L2s are written back and
-// invalidated at every boundary), 30 times per update.  Here the H/32 workgroups that own one 16-row tile of the
-// batch (a "team": one 32-column slice of every hidden layer each) hand their 16 x 32 output tiles to each other
-// as 8-byte {tag, value} granules (CDNA4 guide, Guideline 16 form R2: the data is the flag):
-//   producer: one naturally aligned 8-byte agent-scope relaxed atomic store per value, straight from the MFMA
-//             accumulator layout -- no drain, no flag, no counter;
-//   consumer: every thread sweeps its granules of the team's 16 x H tile with 8-byte agent-scope relaxed atomic
-//             loads until every tag equals the phase tag (wall-clock bounded), then stages the values in LDS.
-// Tags never repeat: tag = (launch epoch of the team << 6) + phase index + 1, the epoch living in device memory and
-// advanced by member 0 when it has consumed the team's last phase (every member has read it by then), so neither
-// a memset node nor a per-launch argument is needed and a graph replay is safe.  A buffer is rewritten only after
-// every member has passed the phase that read it (the phase order implies it: a member can publish phase p + 2
-// only after it has gathered phase p + 1 from all members, each of which gathered phase p before publishing).
-// Results do not depend on placement; teams are mapped to one XCD only for speed.  A sweep that times out sets
-// an error word and falls through, so the grid always drains.
-// ------------------------------------------------------------------------------------------------
-typedef unsigned long long fql_u64;
-struct PecArgs {
-    const float* C0;      // [M, H]  obs W0 + b0 (loop invariant)
-    const float* a0;      // [M, lda0] initial actions (noise z): X_eu + obs_dim
-    const float* W0act;   // W0 rows of (action block, t): [ad + 1 (+ zero rows)][H]
-    const float* W[3];    // hidden kernels of layers 1..3, [H][H]
-    const float* b[3];    // their biases
-    const float* W4;      // head kernel [H][ap]
-    const float* b4;      // head bias [ap]
-    fql_u64* G[2];        // [M][H] activation granules, ping-pong
-    fql_u64* Vg;          // [T][M][16] head-partial granules
-    float* tgt;           // [M, ap] out: clip(a_n)
-    unsigned* epoch;      // [teams] launch epochs (device resident, advanced by the kernel)
-    unsigned* err;        // set to 1 if a sweep timed out
-    int M, ad, ap, lda0, flow_steps, nteams, ntile;  // nteams teams, each owning ntile 16-row tiles (team + nteams j)
-};
-
-__device__ __forceinline__ fql_u64 ld_granule(const fql_u64* p) {
-    return __hip_atomic_load((const FQL_GAS fql_u64*)p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ void st_granule(fql_u64* p, unsigned tag, float v) {
-    __hip_atomic_store((FQL_GAS fql_u64*)p, ((fql_u64)tag << 32) | (fql_u64)__float_as_uint(v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-// wave-uniform: true when a spin has lasted 200 ms of wall clock (100 MHz ticks): something is badly wrong, drain the grid
-__device__ __forceinline__ bool pec_spin_fail(fql_u64& t0, unsigned* err) {
-    const fql_u64 now = __builtin_amdgcn_s_memrealtime();
-    if (t0 == 0) { t0 = now; return false; }
-    if (now - t0 > 20000000ull) {
-        __hip_atomic_store((FQL_GAS unsigned*)err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        return true;
-    }
-    return false;
-}
-
-#define PEC_MAX_TILES 8
-template <int H>  // hidden width (all four hidden layers), multiple of 256; T = H / 32 members per team
-__global__ __launch_bounds__(FQL_THREADS) void fql_euler_persistent_kernel(const PecArgs P) {
-    constexpr int T = H / 32, S = H + 4, G2 = H / 32;  // G2 = k-groups (of 16) per K-half
-    constexpr int CT = H / 64;                          // layer-0 column tiles per wave
-    constexpr int KPR = H / FQL_THREADS;                // granule sweeps per row of the activation tile
-    extern __shared__ __attribute__((aligned(16))) float lds[];
-    float* red = lds + 16 * S;   // [2 column tiles][64] float4: K-split partials
-    float* hs = red + 1024;      // [16][36] staging: last-hidden tile for the head partial
-    float* eas = hs + 576;       // [ntile][16][32] current actions a_s of every row tile (persistent across steps)
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    const int c = lane & 15, q = lane >> 4;
-    const int nt = wave & 1, kp = wave >> 1;
-    // team / member mapping: members of a team share blockIdx % 8 (one XCD under round-robin placement: speed only)
-    int team, mem;
-    if (P.nteams % 8 == 0) {
-        const int x = blockIdx.x & 7, qq = blockIdx.x >> 3;
-        mem = qq % T; team = x + 8 * (qq / T);
-    } else {
-        team = blockIdx.x / T; mem = blockIdx.x % T;
-    }
-    // a team owns the 16-row tiles team, team + nteams, ...: every phase runs over all of them in turn, so the
-    // granules a tile needs were published a whole round earlier and their flight time hides behind the other tiles
-    const int ntile = P.ntile;
-    const int n0 = mem * 32 + nt * 16;
-    const int M = P.M, ad = P.ad, ap = P.ap;
-    const unsigned ep = __hip_atomic_load((FQL_GAS unsigned*)(P.epoch + team), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const unsigned tag0 = ep << 6;  // phase tags of this launch: tag0 + 1 .. tag0 + 3 flow_steps (< 64)
-
-    // ---- operands.  The hidden-layer B fragments (K-half x 16 columns = 4 G2 VGPRs) are fetched once per phase (for
-    // all row tiles), BEFORE the sweep for the team's tile (they do not depend on it) and from an L2 that is never
-    // invalidated inside this launch; keeping all three layers resident instead (192 VGPRs) would push the kernel
-    // to 450 VGPRs and evict every other lane's waves from the CUs for the length of the chain.
-    float wb[4 * G2];  // element (k = 16 (kp G2 + g) + 4 q + s, n0 + c) of the current layer
-    auto load_w = [&](const float* Wl) {
-        // the per-lane base is made opaque so the 4 G2 load addresses are formed here, next to the loads: hoisted
-        // out of the step loop they would occupy >100 VGPR pairs for the whole kernel
-        const float* base = Wl + (size_t)(16 * kp * G2 + 4 * q) * H + n0 + c;
-        asm volatile("" : "+v"(base));
-#pragma unroll
-        for (int g = 0; g < G2; ++g)
-#pragma unroll
-            for (int s4 = 0; s4 < 4; ++s4) wb[4 * g + s4] = ldg(base + (size_t)(16 * g + s4) * H);
-    };
-    float bias[3];
-#pragma unroll
-    for (int l = 0; l < 3; ++l) bias[l] = ldg(P.b[l] + n0 + c);
-    float bw4[8];       // head kernel rows of this workgroup's 32 hidden columns (used by wave 0)
-#pragma unroll
-    for (int g = 0; g < 2; ++g)
-#pragma unroll
-        for (int s4 = 0; s4 < 4; ++s4) bw4[4 * g + s4] = ldg(P.W4 + (size_t)(mem * 32 + 16 * g + 4 * q + s4) * ap + c);
-    // a_0 (+ zero fill of the [16][32] blocks); column ad carries t_s
-    for (int e = tid; e < ntile * 512; e += FQL_THREADS) {
-        const int j = e >> 9, r = (e >> 5) & 15, col = e & 31;
-        eas[e] = (col < ad) ? ldg(P.a0 + (size_t)((team + P.nteams * j) * 16 + r) * P.lda0 + col) : 0.f;
-    }
-    const float inv_steps = 1.0f / (float)P.flow_steps;
-
-    auto gemm_phase = [&](const float (&wl)[4 * G2]) -> f32x4 {  // A tile in LDS -> 16 x 16 accumulator (kp 0 holds the sum)
-        f32x4 acc = {0.f, 0.f, 0.f, 0.f}, acc2 = {0.f, 0.f, 0.f, 0.f};
-        const float* arow = lds + c * S + 4 * q + 16 * kp * G2;
-#pragma unroll
-        for (int g = 0; g < G2; g += 2) {
-            const f32x4 a = *reinterpret_cast<const f32x4*>(arow + 16 * g);
-            const f32x4 a2 = *reinterpret_cast<const f32x4*>(arow + 16 * g + 16);
-#pragma unroll
-            for (int s4 = 0; s4 < 4; ++s4) {
-                acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a[s4], wl[4 * g + s4], acc, 0, 0, 0);
-                acc2 = __builtin_amdgcn_mfma_f32_16x16x4f32(a2[s4], wl[4 * g + 4 + s4], acc2, 0, 0, 0);
-            }
-        }
-        acc += acc2;
-        if (kp == 1) *reinterpret_cast<f32x4*>(&red[(nt * 64 + lane) * 4]) = acc;
-        __syncthreads();
-        if (kp == 0) acc += *reinterpret_cast<const f32x4*>(&red[(nt * 64 + lane) * 4]);
-        return acc;
-    };
-    // GELU tile -> granules, straight from the accumulator layout (col = c, rows 4 q + i): 16 lanes = 128 contiguous bytes
-    auto publish_tile = [&](const f32x4& acc, float bl, fql_u64* dst, int row0, unsigned tag) {
-        if (kp == 0) {
-            fql_u64* d = dst + (size_t)(row0 + 4 * q) * H + n0 + c;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) st_granule(d + (size_t)i * H, tag, gelu_f(acc[i] + bl));
-        }
-    };
-    // a 16 x H tile: thread t sweeps granules t + 256 k (row k / KPR) until all carry `tag`, then stages them in LDS
-    auto gather_tile = [&](const fql_u64* src, int row0, unsigned tag) {
-#ifndef FQL_PEC_NO_SENTINEL
-        // hint poll (guide: one idle wave polls, with s_sleep): lanes 0..T-1 of wave 0 watch the LAST granule each member
-        // stores (row 15, last column of its slice) before anybody sweeps; the sweep below still checks every tag, so this
-        // only keeps 64 KB sweeps of a tile that is not there yet off the CU's memory pipe while other kernels share it
-        // (with >= 4 row tiles per team the tile was published a whole round ago and the hint only costs a barrier: skipped)
-        if (ntile < 4 && wave == 0) {
-            const fql_u64* sp = src + (size_t)(row0 + 15) * H + min(lane, T - 1) * 32 + 31;
-            fql_u64 t1 = 0;
-            for (;;) {
-                const bool ok = lane >= T || (unsigned)(ld_granule(sp) >> 32) == tag;
-                if (__all(ok)) break;
-                __builtin_amdgcn_s_sleep(8);
-                if (pec_spin_fail(t1, P.err)) break;
-            }
-        }
-        if (ntile < 4) __syncthreads();
-#endif
-        const fql_u64* sb = src + (size_t)row0 * H + tid;
-        asm volatile("" : "+v"(sb));
-        constexpr int NG = 16 * KPR;
-        fql_u64 v[NG];
-        fql_u64 t0 = 0;
-        for (;;) {
-            bool ok = true;
-#pragma unroll
-            for (int i = 0; i < NG; ++i) {
-                v[i] = ld_granule(sb + (size_t)i * FQL_THREADS);
-                ok &= (unsigned)(v[i] >> 32) == tag;
-            }
-            if (__all(ok)) break;
-            __builtin_amdgcn_s_sleep(1);
-            if (pec_spin_fail(t0, P.err)) break;
-        }
-#pragma unroll
-        for (int i = 0; i < NG; ++i) lds[(i / KPR) * S + tid + FQL_THREADS * (i % KPR)] = __uint_as_float((unsigned)v[i]);
-    };
-    // fold the T head partials of the previous phase C in fixed order: thread (r, j) owns action element (row0 + r, j)
-    auto gather_head = [&](int row0, unsigned tag) -> float {
-        const int r = tid >> 4, j = tid & 15;
-        const bool act = j < ad;
-        const fql_u64* vb = P.Vg + ((size_t)row0 + r) * 16 + (act ? j : 0);
-        fql_u64 v[T];
-        fql_u64 t0 = 0;
-        for (;;) {
-            bool ok = true;
-#pragma unroll
-            for (int tp = 0; tp < T; ++tp) {
-                v[tp] = ld_granule(vb + (size_t)tp * M * 16);
-                ok &= (unsigned)(v[tp] >> 32) == tag;
-            }
-            if (__all(ok || !act)) break;
-            __builtin_amdgcn_s_sleep(1);
-            if (pec_spin_fail(t0, P.err)) break;
-        }
-        float sum = 0.f;
-#pragma unroll
-        for (int tp = 0; tp < T; ++tp) sum += __uint_as_float((unsigned)v[tp]);
-        return sum;
-    };
-
-#pragma clang loop unroll(disable)
-    for (int s = 0; s < P.flow_steps; ++s) {
-        const unsigned tagA = tag0 + 3 * s + 1, tagB = tagA + 1, tagC = tagA + 2;
-        // ---------------- phase A: fold head partials -> a_s ; layer 0 (rank update of C0) ; layer 1
-        load_w(P.W[0]);
-        float wf[CT][4];    // W0 action/t rows for this wave's layer-0 column tiles (wave + 4 t)
-        {
-            const float* wb0 = P.W0act + (size_t)(4 * q) * H + 16 * wave + c;
-            asm volatile("" : "+v"(wb0));
-#pragma unroll
-            for (int t = 0; t < CT; ++t)
-#pragma unroll
-                for (int s4 = 0; s4 < 4; ++s4) wf[t][s4] = ldg(wb0 + (size_t)s4 * H + 64 * t);
-        }
-#pragma clang loop unroll(disable)
-        for (int j = 0; j < ntile; ++j) {
-            const int row0 = (team + P.nteams * j) * 16;
-            float* ea = eas + 512 * j;
-            f32x4 c0f[CT];      // C0 in C layout for the same column tiles
-            {
-                const float* cb = P.C0 + (size_t)(row0 + 4 * q) * H + 16 * wave + c;
-                asm volatile("" : "+v"(cb));
-#pragma unroll
-                for (int t = 0; t < CT; ++t)
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) c0f[t][i] = ldg(cb + (size_t)i * H + 64 * t);
-            }
-            if (s > 0) {
-                const float sum = gather_head(row0, tagA - 1);  // phase C of step s - 1
-                const int r = tid >> 4, jj = tid & 15;
-                if (jj < ad) ea[r * 32 + jj] += (sum + ldg(P.b4 + jj)) * inv_steps;
-            }
-            if (tid < 16) ea[tid * 32 + ad] = (float)s * inv_steps;  // t_s
-            __syncthreads();
-            {
-                const f32x4 af = *reinterpret_cast<const f32x4*>(&ea[c * 32 + 4 * q]);
-#pragma unroll
-                for (int t = 0; t < CT; ++t) {
-                    f32x4 h = c0f[t];
-#pragma unroll
-                    for (int s4 = 0; s4 < 4; ++s4) h = __builtin_amdgcn_mfma_f32_16x16x4f32(af[s4], wf[t][s4], h, 0, 0, 0);
-                    const int ct = wave + 4 * t;
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) lds[(4 * q + i) * S + 16 * ct + c] = gelu_f(h[i]);
-                }
-            }
-            __syncthreads();
-            const f32x4 acc = gemm_phase(wb);
-            publish_tile(acc, bias[0], P.G[0], row0, tagA);
-        }
-        // ---------------- phase B: layer 2
-        load_w(P.W[1]);
-#pragma clang loop unroll(disable)
-        for (int j = 0; j < ntile; ++j) {
-            const int row0 = (team + P.nteams * j) * 16;
-            gather_tile(P.G[0], row0, tagA);
-            __syncthreads();
-            const f32x4 acc = gemm_phase(wb);
-            publish_tile(acc, bias[1], P.G[1], row0, tagB);
-        }
-        // ---------------- phase C: layer 3 + head partial
-        load_w(P.W[2]);
-#pragma clang loop unroll(disable)
-        for (int j = 0; j < ntile; ++j) {
-            const int row0 = (team + P.nteams * j) * 16;
-            gather_tile(P.G[1], row0, tagB);
-            __syncthreads();
-            const f32x4 acc = gemm_phase(wb);
-            if (kp == 0) {
-#pragma unroll
-                for (int i = 0; i < 4; ++i) hs[(4 * q + i) * 36 + 16 * nt + c] = gelu_f(acc[i] + bias[2]);
-            }
-            __syncthreads();
-            if (wave == 0) {
-                f32x4 pa = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                for (int g = 0; g < 2; ++g) {
-                    const f32x4 a4 = *reinterpret_cast<const f32x4*>(&hs[c * 36 + 16 * g + 4 * q]);
-#pragma unroll
-                    for (int s4 = 0; s4 < 4; ++s4) pa = __builtin_amdgcn_mfma_f32_16x16x4f32(a4[s4], bw4[4 * g + s4], pa, 0, 0, 0);
-                }
-                if (c < ad) {
-                    fql_u64* d = P.Vg + ((size_t)mem * M + row0 + 4 * q) * 16 + c;
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) st_granule(d + (size_t)i * 16, tagC, pa[i]);
-                }
-            }
-        }
-    }
-    // ---------------- final: member 0 folds the last partials, writes clip(a_n) and advances the team's epoch
-    if (mem == 0) {
-        for (int j = 0; j < ntile; ++j) {
-            const int row0 = (team + P.nteams * j) * 16;
-            const float sum = gather_head(row0, tag0 + 3 * P.flow_steps);
-            const int r = tid >> 4, jj = tid & 15;
-            if (jj < ad) stg(P.tgt + (size_t)(row0 + r) * ap + jj, clip1(eas[512 * j + r * 32 + jj] + (sum + ldg(P.b4 + jj)) * inv_steps));
-        }
-        if (tid == 0) __hip_atomic_store((FQL_GAS unsigned*)(P.epoch + team), ep + 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-}
-
 // Encoder head backward entry (utils/encoders.py:98, MLP with activate_final): dZ = (dXa[:, :n] (+ dXb[:, :n])) GELU'(z),
 // dXa / dXb = the layer-0 input gradients of the module's MLP(s) ([M, ld], encoding in the first n columns)
 struct EncDzArgs {
@@ -2700,12 +2361,9 @@ __global__ void fql_dataset_add_kernel(float* obs, float* act, float* rew, float
 #endif
 template <bool BIG, bool SPLIT = false>   // BIG: the launch contains 64 x 64 tile tasks (batches >= 1024); SPLIT: precision = 2 (bf16 x 3)
 __device__ __forceinline__ void side_body(const GemmTask* __restrict__ gt, int ngt, const WgradTask* __restrict__ wt, int nwt, const LnBwdTask* __restrict__ lt,
-                                          int nlt, int tile_w, int tile_l, const MiscTask* __restrict__ mt, int tile_m, int prio) {
+                                          int nlt, int tile_w, int tile_l, const MiscTask* __restrict__ mt, int tile_m) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int b = blockIdx.x;
-    if (prio == 1) __builtin_amdgcn_s_setprio(1);
-    else if (prio == 2) __builtin_amdgcn_s_setprio(2);
-    else if (prio == 3) __builtin_amdgcn_s_setprio(3);
     if (b < tile_w) {
         gemm_tile_dispatch<BIG, SPLIT>(gt[find_task(gt, ngt, b)], lds);
     } else if (b < tile_l) {
@@ -2732,23 +2390,23 @@ __device__ __forceinline__ void side_body(const GemmTask* __restrict__ gt, int n
 // workgroup (2 x 104 registers per SIMD) fit a CU together; the 64 x 64 tile body needs twice that
 __global__ __launch_bounds__(FQL_THREADS, FQL_SIDE_WAVES) void fql_side_kernel(
     const GemmTask* __restrict__ gt, int ngt, const WgradTask* __restrict__ wt, int nwt, const LnBwdTask* __restrict__ lt, int nlt, int tile_w, int tile_l,
-    const MiscTask* __restrict__ mt, int tile_m, int prio, int tl) {
+    const MiscTask* __restrict__ mt, int tile_m, int tl) {
     tl_enter(tl);
-    side_body<false>(gt, ngt, wt, nwt, lt, nlt, tile_w, tile_l, mt, tile_m, prio);
+    side_body<false>(gt, ngt, wt, nwt, lt, nlt, tile_w, tile_l, mt, tile_m);
     tl_exit(tl);
 }
 // precision = 2: same launch contract, split-bf16 tile and weight-gradient bodies (32-row tiles only)
 __global__ __launch_bounds__(FQL_THREADS, FQL_SIDE_WAVES) void fql_side_split_kernel(
     const GemmTask* __restrict__ gt, int ngt, const WgradTask* __restrict__ wt, int nwt, const LnBwdTask* __restrict__ lt, int nlt, int tile_w, int tile_l,
-    const MiscTask* __restrict__ mt, int tile_m, int prio, int tl) {
+    const MiscTask* __restrict__ mt, int tile_m, int tl) {
     tl_enter(tl);
-    side_body<false, true>(gt, ngt, wt, nwt, lt, nlt, tile_w, tile_l, mt, tile_m, prio);
+    side_body<false, true>(gt, ngt, wt, nwt, lt, nlt, tile_w, tile_l, mt, tile_m);
     tl_exit(tl);
 }
 __global__ __launch_bounds__(FQL_THREADS, 2) void fql_side_big_kernel(
     const GemmTask* __restrict__ gt, int ngt, const WgradTask* __restrict__ wt, int nwt, const LnBwdTask* __restrict__ lt, int nlt, int tile_w, int tile_l,
-    const MiscTask* __restrict__ mt, int tile_m, int prio, int tl) {
+    const MiscTask* __restrict__ mt, int tile_m, int tl) {
     tl_enter(tl);
-    side_body<true>(gt, ngt, wt, nwt, lt, nlt, tile_w, tile_l, mt, tile_m, prio);
+    side_body<true>(gt, ngt, wt, nwt, lt, nlt, tile_w, tile_l, mt, tile_m);
     tl_exit(tl);
 }

@@ -271,7 +271,7 @@ int fql_info_wait(fql_handle h, uint64_t ticket, float* info13_host);
  *
  * fql_group_create: `members` [k], k >= 1, distinct, in no other group.  Members are state agents (encoder 0) with precision 0, the same
  * config except alpha (and the create seed), the same batch size, and structurally identical update programs (launch count, kernels,
- * grids, lanes, waits); the persistent Euler-chain variants (FQL_PEC / FQL_XCHAIN) are not groupable.  Anything else: FQL_E_INVALID.
+ * grids, lanes, waits).  Anything else: FQL_E_INVALID.
  * Out of scope and refused: visual or bf16x3 members, members that differ in anything but seed and alpha.  Data-parallel halves,
  * balanced sampling, replay rings and the engine's own queues (stream = NULL updates of a single agent) are not group paths.
  * While a handle belongs to a group, fql_set_batch_size and fql_destroy on it return FQL_E_STATE. */

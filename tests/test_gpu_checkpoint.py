@@ -1,12 +1,10 @@
-"""GPU: checkpoint round trip in the reference's state-dict layout (utils/flax_utils.py:162-202) and the opt-in
-persistent Euler-chain kernel against the oracle."""
-import os
+"""GPU: checkpoint round trip in the reference's state-dict layout (utils/flax_utils.py:162-202)."""
 
 import numpy as np
 import pytest
 
 from oracle import fql_oracle as O
-from tests.util import assert_info_close, leaf_dict, make_problem, randomize_params
+from tests.util import assert_info_close, leaf_dict, make_problem
 
 pytestmark = pytest.mark.gpu
 
@@ -35,29 +33,6 @@ def test_checkpoint_roundtrip_resumes_bit_identically(tmp_path):
     _, ib = b.update(batch, noise=nz)
     assert ia == ib                                     # same state, same kernels: bitwise equal infos
     assert b.get_opt_state()['count'] == 4
-
-
-@pytest.mark.parametrize('B', [256, 512])
-def test_persistent_euler_chain_matches_oracle(B):
-    """FQL_PEC=1: the whole Euler chain in one persistent launch (team hand-offs as {tag, value} granules);
-    B=512 gives every team two row tiles, which it runs through each phase in turn."""
-    import fql_amd
-    od, ad = 29, 8
-    os.environ['FQL_PEC'] = '1'
-    try:
-        cfg, ds, batch, noise = make_problem(od, ad, B, (512, 512, 512, 512), seed=17)
-        agent = fql_amd.FQLAgent.create(0, batch['observations'][:1], batch['actions'][:1], cfg)
-    finally:
-        del os.environ['FQL_PEC']
-    params = randomize_params(agent.get_params(), seed=4, scale=0.05)
-    agent.set_params(params)
-    ref = O.OracleFQL(params, dict(cfg), od, ad, np.float64)
-    for s in range(3):
-        nz = O.make_noise(B, ad, 90 + s)
-        _, ig = agent.update(batch, noise=nz)
-        _, ir = ref.update(batch, nz)
-        assert_info_close(ig, ir, rtol=1e-4, atol=1e-5)
-    assert agent.stats()['launches_per_update'] < 60     # the chain is one launch on this path (30 in the default program)
 
 
 def test_jax_key_paths_match_oracle_with_host_threefry_noise():
