@@ -31,7 +31,7 @@ for enc, name, n in [(1, 'modules_actor_bc_flow', 32), (2, 'modules_actor_oneste
         pool_ref, arg_ref = E.max_pool(c0_ref)
         pool = rd(enc, 100 * s + 1, (n, res // 2, res // 2, C_))
         arg = rd(enc, 100 * s + 4, (n, res // 2, res // 2, C_), np.uint8)
-        inp, c1_ref = sc['blocks'][0]
+        inp, c1_ref = sc['blocks'][0][:2]
         c1 = rd(enc, 100 * s + 2, (n, res // 2, res // 2, C_))
         y = rd(enc, 100 * s + 3, (n, res // 2, res // 2, C_))
         y_ref = cache['stacks'][s + 1]['x0'] if s < 2 else cache['final']

@@ -246,6 +246,7 @@ struct EncBuf {
     float *dz = nullptr, *dA = nullptr, *dB = nullptr, *dC = nullptr;
     std::map<const void*, float*> wpart;   // per convolution (keyed by its arena weight pointer): weight-gradient partials, so the
                                             // wgrads of a pass are independent and their folds share launches
+    std::map<const void*, size_t> bytes;   // allocated size of every activation / scratch buffer above (fql_debug_enc's bound)
 };
 
 }  // namespace
@@ -791,40 +792,54 @@ struct fql_engine {
         const EncNet& en = encs[enc];
         EncBuf b;
         b.enc = enc; b.n = n; b.img = img;
+        auto al = [&](size_t nfloats) {
+            float* p = dalloc(owner, nfloats);
+            b.bytes[p] = std::max<size_t>(nfloats, 4) * sizeof(float);
+            return p;
+        };
         size_t maxel = 0;
         for (const EncStack& st : en.stacks) {
             EncBuf::St s;
             const int C = st.conv[0].cout;
             const size_t full = (size_t)n * st.H * st.W * C, quarter = full / 4;
             maxel = std::max(maxel, full);
-            s.c0 = dalloc(owner, full);
-            s.pool = dalloc(owner, quarter);
-            s.arg = (unsigned char*)dalloc(owner, quarter / 4 + 4);
+            s.c0 = al(full);
+            s.pool = al(quarter);
+            s.arg = (unsigned char*)al(quarter / 4 + 4);
             for (size_t j = 1; j + 1 < st.conv.size(); j += 2) {
-                s.c1.push_back(dalloc(owner, quarter));
-                s.y.push_back(dalloc(owner, quarter));
+                s.c1.push_back(al(quarter));
+                s.y.push_back(al(quarter));
             }
             b.st.push_back(s);
         }
-        b.frelu = dalloc(owner, (size_t)n * en.flat);
-        b.z = dalloc(owner, (size_t)n * enc_dim);
-        b.E = dalloc(owner, (size_t)n * enc_dim);
+        b.frelu = al((size_t)n * en.flat);
+        b.z = al((size_t)n * enc_dim);
+        b.E = al((size_t)n * enc_dim);
         if (bwd) {
-            b.dz = dalloc(owner, (size_t)n * enc_dim);
-            b.dA = dalloc(owner, maxel); b.dB = dalloc(owner, maxel); b.dC = dalloc(owner, maxel);
+            b.dz = al((size_t)n * enc_dim);
+            b.dA = al(maxel); b.dB = al(maxel); b.dC = al(maxel);
             for (const EncStack& st : en.stacks)
                 for (const ConvL& c : st.conv) b.wpart[P + c.w] = dalloc(owner, (size_t)256 * (9 * pad16c(c.cin) + 1) * c.cout);
         }
         return b;
     }
     // image rows per workgroup: <= 8 MFMA row tiles of 16 pixels, whole rows, LDS within 64 KB
-    static int conv_rows(int H, int W, int Ci, int Co, bool wgrad) {
-        for (int R = std::min(H, std::max(1, 128 / W)); R >= 1; R >>= 1) {
-            if (H % R || (R * W) % 16) continue;
+    // The halving sequence from the cap is the planner's choice wherever it finds a fit (every tiling it picks stays as it is); only when it
+    // finds none (12-pixel rows: 10, 5, 2, 1 never try 8 or 4) the largest fitting R below the cap is taken.  The weight gradient of a float
+    // input stages its (R + 2) halo rows through ConvTile's NF float4 per thread: a tile beyond that would leave LDS rows unwritten.
+    static int conv_rows(int H, int W, int Ci, int Co, bool wgrad, bool u8 = false) {
+        const int cap = std::min(H, std::max(1, 128 / W));
+        auto fits = [&](int R) {
+            if (H % R || (R * W) % 16) return false;
+            if (wgrad && !u8 && (R + 2) * (W + 2) * (Ci / 4) > ConvTile::NF * FQL_THREADS) return false;
             const size_t fl = wgrad ? (size_t)(R + 2) * (W + 2) * (Ci + 4) + (size_t)R * W * (Co + 4)
                                     : (size_t)(R + 2) * (W + 2) * (Ci + 4) + (size_t)Co * (9 * Ci + 4);
-            if (fl * sizeof(float) <= 65536) return R;
-        }
+            return fl * sizeof(float) <= 65536;
+        };
+        for (int R = cap; R >= 1; R >>= 1)
+            if (fits(R)) return R;
+        for (int R = cap; R >= 1; --R)
+            if (fits(R)) return R;
         invalid("convolution tile does not fit (H %d, W %d, channels %d -> %d)", H, W, Ci, Co);
     }
     void emit_conv(Program& pr, const void* in, const void* in_id, int in_mode, int n, int H, int W, const ConvL& c, bool transposed,
@@ -921,7 +936,7 @@ struct fql_engine {
         a.in = in; a.dout = dout; a.partial = wp;
         a.N = n; a.H = H; a.W = W; a.Ci = pad16c(c.cin); a.Ci_real = c.cin; a.Co = c.cout; a.in_mode = in_mode;
         if (in_mode == 2 && (a.Ci != 16 || a.Co != 16)) invalid("uint8 convolution weight gradient: <= 16 input channels and 16 output channels expected (got %d -> %d)", c.cin, c.cout);
-        a.R = conv_rows(H, W, a.Ci, a.Co, true);
+        a.R = conv_rows(H, W, a.Ci, a.Co, true, in_mode == 2);
         a.nblocks = n * (H / a.R);
         constexpr int cwg_grid = 256;   // persistent workgroups per weight-gradient task
         op.cw_grid = std::min(a.nblocks, cwg_grid);
@@ -4449,25 +4464,45 @@ extern "C" int fql_debug_timeline(fql_handle h, int reset, int cap, int* lane, i
 }
 
 // Diagnostic only (not in include/fql_amd.h): copy an encoder-pass buffer to the host.  enc: 0 critic, 1 bc_flow, 2 onestep, 3 target;
-// code: 100 s + {0: c0, 1: pool, 2: c1[0], 3: y[0], 4: arg (bytes)}, 900: frelu, 901: z, 902: E, 903: dz, 904: dA, 905: dB, 906: dC
+// code: 100 s + {0: c0, 1: pool, 10 k + 2: c1[k], 10 k + 3: y[k], 4: arg (bytes)}, 900: frelu, 901: z, 902: E, 903: dz, 904: dA, 905: dB, 906: dC;
+// 100 s + 50: stack s's plan as int32 [pool_fused, then per convolution j: split, R forward, R data gradient, R weight gradient]
+// (split: the layer runs bf16 x 3; R: image rows per workgroup that conv_rows chose; 0 where that form never runs).
+// A request larger than the buffer is refused (FQL_E_INVALID); an unknown code is FQL_E_NOTFOUND.
 extern "C" int fql_debug_enc(fql_handle h, int enc, int code, void* out, size_t bytes) {
-    if (!h || !h->visual) return FQL_E_INVALID;
+    if (!h || !h->visual || enc < 0 || enc >= NUM_ENC || code < 0 || (bytes && !out)) return FQL_E_INVALID;
     EncBuf* b = enc == 0 ? &h->eb_c : enc == 1 ? &h->eb_bc : enc == 2 ? &h->eb_os : &h->eb_t;
     const void* src = nullptr;
     if (code >= 900) {
         const void* tab[] = {b->frelu, b->z, b->E, b->dz, b->dA, b->dB, b->dC};
-        src = tab[code - 900];
-    } else {
-        EncBuf::St& s = b->st[code / 100];
-        switch (code % 100) {
-            case 0: src = s.c0; break;
-            case 1: src = s.pool; break;
-            case 2: src = s.c1[0]; break;
-            case 3: src = s.y[0]; break;
-            default: src = s.arg; break;
+        if (code - 900 < 7) src = tab[code - 900];
+    } else if ((size_t)(code / 100) < b->st.size()) {
+        const int si = code / 100, k = code % 100;
+        EncBuf::St& s = b->st[si];
+        if (k == 50) {   // the plan: computed on the host, no device copy
+            const EncStack& st = h->encs[enc].stacks[si];
+            std::vector<int32_t> plan{st.conv[0].pool_fused ? 1 : 0};
+            for (size_t j = 0; j < st.conv.size(); ++j) {
+                const ConvL& c = st.conv[j];
+                const int H = j == 0 ? st.H : st.H / 2, W = j == 0 ? st.W : st.W / 2, Ci = pad16c(c.cin);
+                const bool u8 = si == 0 && j == 0;
+                plan.push_back(u8 ? (h->cfg.precision == 2 ? 1 : 0) : (c.split ? 1 : 0));
+                plan.push_back(fql_engine::conv_rows(H, W, Ci, c.cout, false));
+                plan.push_back(u8 ? 0 : fql_engine::conv_rows(H, W, c.cout, Ci, false));
+                plan.push_back(fql_engine::conv_rows(H, W, Ci, c.cout, true, u8));
+            }
+            if (bytes > plan.size() * sizeof(int32_t)) return FQL_E_INVALID;
+            std::memcpy(out, plan.data(), bytes);
+            return FQL_OK;
         }
+        if (k == 0) src = s.c0;
+        else if (k == 1) src = s.pool;
+        else if (k == 4) src = s.arg;
+        else if (k % 10 == 2 && (size_t)(k / 10) < s.c1.size()) src = s.c1[k / 10];
+        else if (k % 10 == 3 && (size_t)(k / 10) < s.y.size()) src = s.y[k / 10];
     }
     if (!src) return FQL_E_NOTFOUND;
+    auto it = b->bytes.find(src);
+    if (it == b->bytes.end() || bytes > it->second) return FQL_E_INVALID;
     hipDeviceSynchronize();
     return hipMemcpy(out, src, bytes, hipMemcpyDeviceToHost) == hipSuccess ? FQL_OK : FQL_E_HIP;
 }

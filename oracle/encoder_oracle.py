@@ -73,14 +73,19 @@ def conv3x3_bwd(x, kernel, dy):
     return dx, dk, db
 
 
-def max_pool(x):
-    """3x3 / stride 2 / SAME on even extents.  Returns (y, arg) with arg = winning offset 3*i + j per output."""
+def max_pool(x, arg=None):
+    """3x3 / stride 2 / SAME on even extents.  Returns (y, arg) with arg = winning offset 3*i + j per output.
+    A given ``arg`` routes each window to that offset instead of its first maximum."""
     n, h, w, c = x.shape
     assert h % 2 == 0 and w % 2 == 0
     xp = np.pad(x, ((0, 0), (0, 1), (0, 1), (0, 0)), constant_values=-np.inf)
     win = np.lib.stride_tricks.sliding_window_view(xp, (3, 3), axis=(1, 2))[:, ::2, ::2]  # [N,H/2,W/2,C,3,3]
     flat = win.reshape(n, h // 2, w // 2, c, 9)
-    arg = flat.argmax(axis=-1)  # first maximum in row-major window order
+    if arg is None:
+        arg = flat.argmax(axis=-1)  # first maximum in row-major window order
+    else:
+        arg = np.asarray(arg).astype(np.int64)
+        assert arg.shape == flat.shape[:-1] and arg.min(initial=0) >= 0 and arg.max(initial=0) < 9, arg.shape
     return np.take_along_axis(flat, arg[..., None], axis=-1)[..., 0], arg.astype(np.uint8)
 
 
@@ -133,8 +138,43 @@ def encoder_out_dim(name='impala_small') -> int:
 # ----------------------------------------------------------------------------------------
 # forward / backward
 # ----------------------------------------------------------------------------------------
-def impala_forward(p: dict, x_u8, keep=False, dtype=np.float32):
-    """utils/encoders.py:83-100.  x_u8: [N,H,W,C] uint8 (or float already in 0..255)."""
+def _pick(routing, key, s, b=None):
+    """A decision array from ``routing`` (None where the routing or its entry is absent)."""
+    if routing is None:
+        return None
+    v = routing.get(key)
+    if v is None or s is None:
+        return v
+    v = v[s]
+    return v if b is None or v is None else v[b]
+
+
+def _mask(v, x):
+    if v is None:
+        return None
+    v = np.asarray(v, bool)
+    assert v.shape == x.shape, (v.shape, x.shape)
+    return v
+
+
+def _relu(x, pos):
+    """ReLU, or x where the routed mask ``pos`` is set (None: decided here)."""
+    return np.maximum(x, 0) if pos is None else np.where(pos, x, 0)
+
+
+def _pos(x, pos):
+    return x > 0 if pos is None else pos
+
+
+def impala_forward(p: dict, x_u8, keep=False, dtype=np.float32, routing=None):
+    """utils/encoders.py:83-100.  x_u8: [N,H,W,C] uint8 (or float already in 0..255).
+
+    ``routing`` (optional) pins the pass's discrete decisions to given ones instead of deciding them here: a dict with
+    'arg' (per stack: max-pool winner codes 3 i + j, shaped like the pool output), 'c1' and 'inp' (per stack, per block:
+    boolean masks of ``c1 > 0`` and of the block input ``> 0``) and 'final' (boolean mask of the last stack's output ``> 0``).
+    A pool then outputs the routed element and a ReLU passes x where the mask is set; ``impala_backward`` follows the
+    same decisions.  Any entry may be None (decided here).  Given the decisions this pass would make itself, the result
+    is bitwise that of the default."""
     x = np.asarray(x_u8).astype(dtype) / dtype(255.0) if np.dtype(dtype) != np.float64 else np.asarray(x_u8).astype(np.float64) / 255.0
     cache = {'stacks': []}
     ns = sum(1 for k in p if k.startswith('stack_blocks_'))
@@ -144,21 +184,25 @@ def impala_forward(p: dict, x_u8, keep=False, dtype=np.float32):
         sc = {'x0': x}
         y = conv3x3(x, st['Conv_0']['kernel'], st['Conv_0']['bias'])
         sc['pre_pool_hw'] = y.shape[1:3]
-        y, arg = max_pool(y)
+        y, arg = max_pool(y, _pick(routing, 'arg', s))
         sc['arg'] = arg
         sc['blocks'] = []
         for b in range(nb):
             inp = y
-            r1 = np.maximum(inp, 0)
+            inp_pos = _mask(_pick(routing, 'inp', s, b), inp)
+            r1 = _relu(inp, inp_pos)
             c1 = conv3x3(r1, st[f'Conv_{1 + 2 * b}']['kernel'], st[f'Conv_{1 + 2 * b}']['bias'])
-            r2 = np.maximum(c1, 0)
+            c1_pos = _mask(_pick(routing, 'c1', s, b), c1)
+            r2 = _relu(c1, c1_pos)
             c2 = conv3x3(r2, st[f'Conv_{2 + 2 * b}']['kernel'], st[f'Conv_{2 + 2 * b}']['bias'])
             y = c2 + inp
-            sc['blocks'].append((inp, c1))
+            sc['blocks'].append((inp, c1, inp_pos, c1_pos))
         cache['stacks'].append(sc)
         x = y
     cache['final'] = x
-    f = np.maximum(x, 0).reshape(x.shape[0], -1)
+    final_pos = _mask(_pick(routing, 'final', None), x)
+    cache['final_pos'] = final_pos
+    f = _relu(x, final_pos).reshape(x.shape[0], -1)
     cache['flat'] = f
     mlp = p['MLP_0']
     zs = []
@@ -172,7 +216,8 @@ def impala_forward(p: dict, x_u8, keep=False, dtype=np.float32):
 
 
 def impala_backward(p: dict, cache: dict, dout):
-    """Gradient of ``impala_forward`` w.r.t. its parameters (input images carry no gradient)."""
+    """Gradient of ``impala_forward`` w.r.t. its parameters (input images carry no gradient).  It follows the decisions
+    the forward pass recorded in ``cache`` (its own, or the routing it was given)."""
     g = {}
     mlp = p['MLP_0']
     gm = {}
@@ -184,28 +229,37 @@ def impala_backward(p: dict, cache: dict, dout):
         dh = dz @ mlp[f'Dense_{i}']['kernel'].T
     g['MLP_0'] = gm
     x = cache['final']
-    dy = dh.reshape(x.shape) * (x > 0)
+    dy = dh.reshape(x.shape) * _pos(x, cache['final_pos'])
     ns = len(cache['stacks'])
     for s in reversed(range(ns)):
         st = p[f'stack_blocks_{s}']
         sc = cache['stacks'][s]
         gs = {}
         for b in reversed(range(len(sc['blocks']))):
-            inp, c1 = sc['blocks'][b]
-            r2 = np.maximum(c1, 0)
+            inp, c1, inp_pos, c1_pos = sc['blocks'][b]
+            r2 = _relu(c1, c1_pos)
             d_r2, dk, db = conv3x3_bwd(r2, st[f'Conv_{2 + 2 * b}']['kernel'], dy)
             gs[f'Conv_{2 + 2 * b}'] = {'kernel': dk, 'bias': db}
-            d_c1 = d_r2 * (c1 > 0)
-            r1 = np.maximum(inp, 0)
+            d_c1 = d_r2 * _pos(c1, c1_pos)
+            r1 = _relu(inp, inp_pos)
             d_r1, dk, db = conv3x3_bwd(r1, st[f'Conv_{1 + 2 * b}']['kernel'], d_c1)
             gs[f'Conv_{1 + 2 * b}'] = {'kernel': dk, 'bias': db}
-            dy = dy + d_r1 * (inp > 0)
+            dy = dy + d_r1 * _pos(inp, inp_pos)
         d_conv = max_pool_bwd(sc['arg'], dy, sc['pre_pool_hw'])
         dx, dk, db = conv3x3_bwd(sc['x0'], st['Conv_0']['kernel'], d_conv)
         gs['Conv_0'] = {'kernel': dk, 'bias': db}
         g[f'stack_blocks_{s}'] = gs
         dy = dx
     return g
+
+
+def routing_of(cache: dict) -> dict:
+    """The decisions a forward pass made (``impala_forward(..., keep=True)``'s cache), in the ``routing`` format."""
+    st = cache['stacks']
+    return {'arg': [sc['arg'] for sc in st],
+            'c1': [[_pos(c1, c1p) for _, c1, _, c1p in sc['blocks']] for sc in st],
+            'inp': [[_pos(inp, ip) for inp, _, ip, _ in sc['blocks']] for sc in st],
+            'final': _pos(cache['final'], cache['final_pos'])}
 
 
 # ----------------------------------------------------------------------------------------

@@ -260,7 +260,7 @@ def tree_map(f, *trees):
 class OracleFQL:
     """Restatement of FQLAgent (agents/fql.py:15-246) with explicit noise."""
 
-    def __init__(self, params: dict, config: dict, obs_dim: int, act_dim: int, dtype=np.float32):
+    def __init__(self, params: dict, config: dict, obs_dim: int, act_dim: int, dtype=np.float32, routing=None):
         self.dtype = np.dtype(dtype)
         self.config = dict(config)
         self.enc_name = self.config.get('encoder')
@@ -277,6 +277,10 @@ class OracleFQL:
         # utils/flax_utils.py:90-118) reads this tree instead of self.params, so finite differences of total_loss w.r.t.
         # self.params see exactly the dependence jax.grad differentiates
         self.frozen = None
+        # test hook (visual agents): {module name: encoder routing (encoder_oracle.impala_forward)} pins the discrete decisions of
+        # that module's differentiated encoder pass over batch['observations'] (pool winners, ReLU signs) to given ones, e.g. the
+        # engine's, so that a near-tie decided the other way does not move the gradients below it.  None: decided here.
+        self.routing = dict(routing) if routing else {}
 
     def _P(self, stored=False):
         return self.frozen if (stored and self.frozen is not None) else self.params
@@ -293,7 +297,8 @@ class OracleFQL:
         """Module `name`'s encoder applied to raw observations (identity for state-based agents)."""
         if self.enc_name is None:
             return (self._c(obs), None) if keep else self._c(obs)
-        return ENC.impala_forward(self._P(stored)[name]['encoder'], obs, keep=keep, dtype=self.dtype.type)
+        routing = self.routing.get(name) if keep else None
+        return ENC.impala_forward(self._P(stored)[name]['encoder'], obs, keep=keep, dtype=self.dtype.type, routing=routing)
 
     def _actor(self, name, obs, act, t=None, keep=False, stored=False):
         """`obs` is already encoded (utils/networks.py:221-222 with the encoder applied by the caller)."""

@@ -1,4 +1,6 @@
 """CPU: the numpy encoder oracle against an independent torch-autograd restatement (conv2d / max_pool2d / gelu)."""
+import math
+
 import numpy as np
 import pytest
 import torch
@@ -180,3 +182,122 @@ def test_visual_numpy_oracle_equals_torch_autograd_restatement():
         _, ib = tref.update(batch, nz)
         for k in ia:
             assert abs(ia[k] - ib[k]) <= 1e-8 * (1 + abs(ia[k])), k
+
+
+def _random_encoder(name, hw, c, seed):
+    rng = np.random.default_rng(seed)
+    p = E.init_encoder_params(rng, hw + (c,), name, np.float64)
+    for path, leaf in flat(p).items():
+        if path.endswith('bias'):
+            leaf[...] = rng.normal(size=leaf.shape) * 0.1
+    x = rng.integers(0, 256, size=(3,) + hw + (c,), dtype=np.uint8)
+    return rng, p, x
+
+
+@pytest.mark.parametrize('name,hw,c', [('impala_small', (16, 24), 5), ('impala', (16, 16), 3)])
+def test_routing_with_own_decisions_is_bitwise_the_default(name, hw, c):
+    rng, p, x = _random_encoder(name, hw, c, 3)
+    out, cache = E.impala_forward(p, x, keep=True, dtype=np.float64)
+    routing = E.routing_of(cache)
+    assert len(routing['arg']) == 3 and len(routing['c1'][0]) == (2 if name == 'impala' else 1)
+    out_r, cache_r = E.impala_forward(p, x, keep=True, dtype=np.float64, routing=routing)
+    np.testing.assert_array_equal(out_r, out)
+    dout = rng.normal(size=out.shape)
+    g, g_r = flat(E.impala_backward(p, cache, dout)), flat(E.impala_backward(p, cache_r, dout))
+    for path in g:
+        np.testing.assert_array_equal(g_r[path], g[path], err_msg=path)
+
+
+def test_oracle_fql_routing_with_own_decisions_is_bitwise_the_default():
+    O, cfg, agent, batch, noise = make_visual_problem(enc='impala_small', hw=16)
+    _, _, g = agent.grads(batch, noise)
+    routing = {}
+    for m in ('modules_critic', 'modules_actor_bc_flow', 'modules_actor_onestep_flow'):
+        _, cache = E.impala_forward(agent.params[m]['encoder'], batch['observations'], keep=True, dtype=np.float64)
+        routing[m] = E.routing_of(cache)
+    pinned = O.OracleFQL(agent.params, cfg, (16, 16, 3), 4, np.float64, routing=routing)
+    loss_p, info_p, g_p = pinned.grads(batch, noise)
+    loss, info, _ = agent.grads(batch, noise)
+    assert loss_p == loss and info_p == info
+    for path, leaf in O.tree_leaves_with_path(g):
+        np.testing.assert_array_equal(dict(O.tree_leaves_with_path(g_p))[path], leaf, err_msg=path)
+
+
+def test_pool_routing_sends_the_gradient_to_the_named_input_at_a_tie():
+    """A window whose maximum sits at two offsets: by default the first wins (row-major); routed, the named one does."""
+    rng = np.random.default_rng(4)
+    x = rng.normal(size=(2, 6, 8, 3))
+    x[0, 2, 3, 1] = x[0, 2, 4, 1] = x[0, 2:5, 2:5, 1].max() + 1.0          # window (1, 1): offsets 3 * 0 + 1 and 3 * 0 + 2
+    y, arg = E.max_pool(x)
+    assert arg[0, 1, 1, 1] == 1
+    routed = arg.copy()
+    routed[0, 1, 1, 1] = 2
+    y_r, arg_r = E.max_pool(x, routed)
+    np.testing.assert_array_equal(y_r, y)                                  # same value either way: it is a tie
+    np.testing.assert_array_equal(arg_r, routed)
+    dy = rng.normal(size=y.shape)
+    # hand scatter with torch: every window's gradient to input (2 oh + a // 3, 2 ow + a % 3), added up
+    n, ho, wo, c = dy.shape
+    idx = np.zeros(dy.shape, np.int64)
+    for o in np.ndindex(*dy.shape):
+        a = int(routed[o])
+        idx[o] = (2 * o[1] + a // 3) * (x.shape[2] + 1) + 2 * o[2] + a % 3
+    t = torch.zeros(n, c, (x.shape[1] + 1) * (x.shape[2] + 1), dtype=torch.float64)
+    t.scatter_add_(2, torch.as_tensor(idx).permute(0, 3, 1, 2).reshape(n, c, -1),
+                   torch.as_tensor(dy).permute(0, 3, 1, 2).reshape(n, c, -1))
+    want = t.reshape(n, c, x.shape[1] + 1, x.shape[2] + 1).permute(0, 2, 3, 1).numpy()[:, :-1, :-1]
+    got = E.max_pool_bwd(arg_r, dy, x.shape[1:3])
+    np.testing.assert_allclose(got, want, rtol=0, atol=1e-15)             # overlapping windows: another order of adds
+    moved = got - E.max_pool_bwd(arg, dy, x.shape[1:3])                      # only window (1, 1)'s gradient moved: (2, 3) -> (2, 4)
+    want_moved = np.zeros_like(moved)
+    want_moved[0, 2, 4, 1], want_moved[0, 2, 3, 1] = dy[0, 1, 1, 1], -dy[0, 1, 1, 1]
+    np.testing.assert_allclose(moved, want_moved, rtol=0, atol=1e-15)
+
+
+def test_relu_routing_passes_the_gradient_where_the_mask_is_set():
+    """One decision of each ReLU kind (block input, c1, final output) flipped against its sign: forward and every leaf's
+    gradient follow the given masks, checked against torch autograd through x * mask and a gather at the routed pool offsets."""
+    rng, p, x = _random_encoder('impala_debug', (8, 8), 3, 5)
+    _, cache = E.impala_forward(p, x, keep=True, dtype=np.float64)
+    routing = E.routing_of(cache)
+    # flip one decision of each kind (value need not be a tie: routing is followed as given)
+    for key, where in (('inp', (0, 1, 2, 0)), ('c1', (1, 0, 1, 3))):
+        m = routing[key][0][0].copy()
+        m[where] = ~m[where]
+        routing[key][0][0] = m
+    fm = routing['final'].copy()
+    fm[2, 0, 1, 2] = ~fm[2, 0, 1, 2]
+    routing['final'] = fm
+    out_r, cache_r = E.impala_forward(p, x, keep=True, dtype=np.float64, routing=routing)
+    dout = rng.normal(size=out_r.shape)
+    g_r = flat(E.impala_backward(p, cache_r, dout))
+    # torch restatement of the same masked network: relu replaced by x * mask, pool by a gather at the routed offsets
+    tp = to_torch(p)
+
+    def conv(x, k, b):
+        return torch.nn.functional.conv2d(x.permute(0, 3, 1, 2), k.permute(3, 2, 0, 1), b, padding=1).permute(0, 2, 3, 1)
+
+    def pool(x, arg):
+        n, h, w, c = x.shape
+        xp = torch.nn.functional.pad(x, (0, 0, 0, 1, 0, 1), value=-float('inf'))
+        win = xp.unfold(1, 3, 2).unfold(2, 3, 2)                            # [N, H/2, W/2, C, 3, 3]
+        return torch.gather(win.reshape(*win.shape[:4], 9), -1, torch.as_tensor(arg, dtype=torch.int64)[..., None])[..., 0]
+
+    h = torch.as_tensor(x, dtype=torch.float64) / 255.0
+    for s in range(2):
+        st = tp[f'stack_blocks_{s}']
+        h = pool(conv(h, st['Conv_0']['kernel'], st['Conv_0']['bias']), routing['arg'][s])
+        inp = h
+        c1 = conv(inp * torch.as_tensor(routing['inp'][s][0]), st['Conv_1']['kernel'], st['Conv_1']['bias'])
+        h = conv(c1 * torch.as_tensor(routing['c1'][s][0]), st['Conv_2']['kernel'], st['Conv_2']['bias']) + inp
+    f = (h * torch.as_tensor(routing['final'])).reshape(h.shape[0], -1)
+    d = tp['MLP_0']['Dense_0']
+    z = f @ d['kernel'] + d['bias']
+    out_t = 0.5 * z * (1 + torch.tanh(math.sqrt(2 / math.pi) * (z + 0.044715 * z ** 3)))
+    np.testing.assert_allclose(out_r, out_t.detach().numpy(), rtol=1e-10, atol=1e-12)
+    (out_t * torch.as_tensor(dout)).sum().backward()
+    ft = flat(tp)
+    for path in g_r:
+        np.testing.assert_allclose(g_r[path], ft[path].grad.numpy(), rtol=1e-9, atol=1e-11, err_msg=path)
+    g = flat(E.impala_backward(p, cache, dout))
+    assert any(np.abs(g[k] - g_r[k]).max() > 1e-9 for k in g)                # the flips moved some gradient
