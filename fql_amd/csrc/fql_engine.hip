@@ -3775,6 +3775,7 @@ static int leaf_rw(fql_handle h, const char* leaf, float* host, size_t n, int wh
     if (!h) return FQL_E_INVALID;
     try {
         h->group_fence();
+        h->hip_touch();   // stream-less updates still on the AQL queues read and write P / Mu / Nu; a chain-weight refresh must precede the next submit
         if (!leaf || !host) invalid("leaf/host pointer must not be NULL");
         const Leaf* l = h->find_leaf(leaf);
         if (!l) { h->err = std::string("unknown leaf: ") + leaf; return FQL_E_NOTFOUND; }
