@@ -20,10 +20,6 @@
 #include "fql_aql.h"
 
 #include <algorithm>
-#include <atomic>
-#include <condition_variable>
-#include <mutex>
-#include <thread>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -197,31 +193,86 @@ struct Launch {
 struct Program {
     std::vector<Op> ops;
     std::vector<Launch> launches;
-    bool two_lanes = false;  // more than one lane in use
     bool lane_used[FQL_LANES] = {};
     hipEvent_t ev_fork = nullptr, ev_join[FQL_LANES] = {};
     hipGraph_t graph = nullptr;
     hipGraphExec_t exec = nullptr;
     int64_t macs = 0;
-    // threaded eager issue (run_threaded): sequence number of the run whose event record of launch i has been enqueued
-    std::unique_ptr<std::atomic<uint64_t>[]> rec;
-    size_t rec_n = 0;
-    uint64_t run_seq = 0;
+    AqlProgram aql;            // the program as AQL packets (fql_aql.h): built by its first update on the engine's own stream
+    bool aql_tried = false;    // build_aql has run for it (lazily: data-parallel and graph-only users never start the HSA side)
 };
 
-// One host thread per extra lane for the threaded eager executor: spins for a short while after a job (back-to-back updates find it
-// hot), then sleeps on a condition variable.
-struct LaneWorker {
-    std::thread th;
-    std::mutex m;
-    std::condition_variable cv;
-    std::atomic<uint64_t> job{0}, done{0};
-    std::atomic<bool> stop{false};
-    Program* pr = nullptr;
-    hipStream_t s = nullptr;
-    int lane = 0;
-    std::string err;     // set by the worker when a HIP call failed during the job
-};
+// Puts a launch list (a Program's, or an agent group's) onto streams; the only copy of the lane loop.  ls == nullptr: every launch on
+// s0 in list order, which is a topological order of the program.  Otherwise lane 0 runs on s0 and lane l >= 1 on ls[l]: a launch first
+// waits for the events of the launches in its `waits`, a launch that another lane waits on records its event (created on first use),
+// and every used lane >= 1 is joined back into s0 at the end.  fork: those lanes first start behind what s0 holds (else the caller
+// orders them).  issue(launch, stream) enqueues one launch.
+template <typename P, typename IssueFn>
+void issue_lanes(P& pr, hipStream_t s0, const hipStream_t* ls, bool fork, IssueFn&& issue) {
+    auto lazy = [](hipEvent_t& e) { if (!e) HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming)); };
+    bool side = false;   // a lane >= 1 runs on a stream of its own
+    if (ls) for (int l = 1; l < FQL_LANES; ++l) side |= pr.lane_used[l];
+    if (side && fork) {
+        lazy(pr.ev_fork);
+        HIP_CHECK(hipEventRecord(pr.ev_fork, s0));
+        for (int l = 1; l < FQL_LANES; ++l) if (pr.lane_used[l]) HIP_CHECK(hipStreamWaitEvent(ls[l], pr.ev_fork, 0));
+    }
+    for (auto& L : pr.launches) {
+        const hipStream_t s = side && L.lane != 0 ? ls[L.lane] : s0;
+        if (side)
+            for (int w : L.waits) if (pr.launches[w].ev) HIP_CHECK(hipStreamWaitEvent(s, pr.launches[w].ev, 0));
+        issue(L, s);
+        if (side && L.record_after) {
+            lazy(L.ev);
+            HIP_CHECK(hipEventRecord(L.ev, s));
+        }
+    }
+    if (side)
+        for (int l = 1; l < FQL_LANES; ++l) {
+            if (!pr.lane_used[l]) continue;
+            lazy(pr.ev_join[l]);
+            HIP_CHECK(hipEventRecord(pr.ev_join[l], ls[l]));
+            HIP_CHECK(hipStreamWaitEvent(s0, pr.ev_join[l], 0));
+        }
+    HIP_CHECK(hipGetLastError());
+}
+// the events issue_lanes created for a launch list
+template <typename P>
+void destroy_lane_events(P& pr) {
+    for (auto& L : pr.launches) if (L.ev) { hipEventDestroy(L.ev); L.ev = nullptr; }
+    if (pr.ev_fork) { hipEventDestroy(pr.ev_fork); pr.ev_fork = nullptr; }
+    for (hipEvent_t& e : pr.ev_join) if (e) { hipEventDestroy(e); e = nullptr; }
+}
+
+// what `body` enqueues on `s` (and on the streams it forks from `s`) as an instantiated graph; a body that throws ends the capture first
+template <typename Body>
+void capture_graph(hipStream_t s, Body&& body, hipGraph_t& graph, hipGraphExec_t& exec) {
+    static const bool trace = getenv("FQL_TRACE") != nullptr;
+    HIP_CHECK(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
+    try {
+        body();
+    } catch (...) {
+        hipGraph_t g = nullptr;
+        hipStreamEndCapture(s, &g);
+        if (g) hipGraphDestroy(g);
+        throw;
+    }
+    if (trace) fprintf(stderr, "[fql] end capture\n");
+    HIP_CHECK(hipStreamEndCapture(s, &graph));
+    if (trace) {
+        size_t nn = 0;
+        hipGraphGetNodes(graph, nullptr, &nn);
+        fprintf(stderr, "[fql] instantiate (%zu nodes)\n", nn);
+    }
+    HIP_CHECK(hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0));
+    if (trace) fprintf(stderr, "[fql] instantiated\n");
+}
+
+// Every update program holds its captured graph once build_workspace has returned: only a rebuild that failed halfway (and freed the
+// old programs) leaves one without.  The update entry points report that instead of launching a null graph.
+void require_graph(const Program& pr) {
+    if (!pr.exec) throw HipError{"no update program: the last workspace rebuild (fql_set_batch_size) failed halfway"};
+}
 
 struct PassBuf {
     int net = 0, M = 0;
@@ -270,10 +321,10 @@ struct fql_engine {
     float *w_nact = nullptr, *w_noise = nullptr;                            // [B, ap]: next_actions, raw N(0, 1) of the target-policy noise
     PassBuf p_a, p_ta, p_q[2];                                               // actor, target actor, critic pair on [obs | actor actions]
     Program prog_critic;
-    AqlProgram aql_critic;
     uint64_t seed = 0;
     int device = 0;
-    hipStream_t stream = nullptr, stream2 = nullptr, stream3 = nullptr, stream4 = nullptr;
+    hipStream_t stream = nullptr;
+    hipStream_t lane_streams[FQL_LANES] = {};   // lanes >= 1 of the engine's programs (lane 0 runs on the stream a program is issued on)
     bool allow64 = true;
     int emit_lane = 0;
     std::vector<Op>* defer_wgrads = nullptr;   // when set, emit_backward collects weight-gradient ops here instead of emitting them in place
@@ -343,10 +394,8 @@ struct fql_engine {
     bool began = false;
     // the single-GPU update as AQL packets on the engine's own HSA queues (fql_aql.h); everything else stays on HIP streams
     AqlRuntime aql;
-    AqlProgram aql_full;
     std::vector<AqlDispatch>* aql_rec = nullptr;   // issue() records instead of launching while this is set
     bool last_update_aql = false;
-    bool aql_tried = false;                        // build_aql has run for the current programs (lazily: data-parallel and graph-only users never start the HSA side)
     bool hip_dirty = true;                         // HIP work may be pending on the engine's stream: drain it before the next AQL submit
     void aql_drain() {                             // every AQL update submitted so far has finished (host wait)
         if (!aql.up) return;
@@ -389,7 +438,6 @@ struct fql_engine {
     };
     std::map<int, std::unique_ptr<Eval>> evals;
 
-    int64_t launches_per_update = 0;
     // agent groups (fql_group_*): the group this engine is a member of, the event behind that group's last update and whether an entry
     // point of this engine has run since (then the next group update orders itself behind this engine's stream)
     fql_group_s* group = nullptr;
@@ -1459,8 +1507,6 @@ struct fql_engine {
         int maxlv = 0;
         for (const Op& op : pr.ops) maxlv = std::max(maxlv, op.level);
         pr.launches.clear();
-        pr.rec_n = 0;
-        pr.two_lanes = false;
         for (bool& b : pr.lane_used) b = false;
         std::vector<int> launch_of(pr.ops.size(), -1);
         for (int lv = 0; lv <= maxlv; ++lv) {
@@ -1483,7 +1529,6 @@ struct fql_engine {
                         if (op.type == OP_POSTOS || op.type == OP_LOSS_CRITIC || op.type == OP_LOSS_Q || op.type == OP_LOSS_BC) selm.push_back(&op);
                     }
                     if (sel.empty() && selw.empty() && sell.empty() && selm.empty()) continue;
-                    if (lane >= 1) pr.two_lanes = true;
                     pr.lane_used[lane] = true;
                     Launch L;
                     L.type = OP_GEMM64;
@@ -1590,7 +1635,6 @@ struct fql_engine {
                     continue;
                 }
                 if (sel.empty()) continue;
-                if (lane >= 1) pr.two_lanes = true;
                 pr.lane_used[lane] = true;
                 if (ty == OP_CONV || ty == OP_CONV_U8 || ty == OP_CONV_WGRAD || ty == OP_CONV_WRED) {
                     // every convolution-family op of this level and lane shares ONE launch (e.g. the same layer of the four
@@ -1996,172 +2040,49 @@ struct fql_engine {
     }
 
 #undef FQL_LAUNCH
-    // ---- threaded eager executor ---------------------------------------------------------------------------------------------
-    // The lanes of a program issued as plain launches, each lane's stream fed by a host thread of its own (lane 0 by the caller).
-    // Cross-lane dependencies: the producer records its event and then publishes the run's sequence number for that launch; the
-    // consumer's thread waits for the number (so the event it makes its stream wait on is THIS run's record), then
-    // hipStreamWaitEvent.  Nothing is captured, so the lane graph may hold edges in both directions.
-    std::unique_ptr<LaneWorker> workers[FQL_LANES];
-    std::atomic<bool> lanes_abort{false};
-
-    void run_lane(Program& pr, int lane, hipStream_t s, uint64_t seq) {
-        const bool diag = (&pr == &prog_full);
-        if (lane != 0) HIP_CHECK(hipStreamWaitEvent(s, pr.ev_fork, 0));
-        for (size_t i = 0; i < pr.launches.size(); ++i) {
-            const Launch& L = pr.launches[i];
-            if (L.lane != lane) continue;
-            for (int w : L.waits) {
-                if (!pr.launches[w].ev) continue;
-                int spins = 0;
-                while (pr.rec[w].load(std::memory_order_acquire) < seq) {
-                    if (lanes_abort.load(std::memory_order_relaxed)) throw HipError{"threaded lanes: aborted after an error on another lane"};
-                    if (++spins > 64) { __builtin_ia32_pause(); }
-                }
-                HIP_CHECK(hipStreamWaitEvent(s, pr.launches[w].ev, 0));
-            }
-            issue(L, s, diag ? (int)i : -1);
-            if (L.record_after) {
-                HIP_CHECK(hipEventRecord(L.ev, s));
-                pr.rec[i].store(seq, std::memory_order_release);
-            }
-        }
-        if (lane != 0) HIP_CHECK(hipEventRecord(pr.ev_join[lane], s));
-        HIP_CHECK(hipGetLastError());
+    // issue() of a launch of `pr` (timeline ids, diagnostics build only: the launches of prog_full)
+    void issue_of(const Program& pr, const Launch& L, hipStream_t s) {
+        issue(L, s, &pr == &prog_full ? (int)(&L - pr.launches.data()) : -1);
     }
-
-    void worker_main(LaneWorker* w) {
-        hipSetDevice(device);
-        uint64_t last = 0;
-        for (;;) {
-            uint64_t j = last;
-            for (int spin = 0; spin < 40000 && (j = w->job.load(std::memory_order_acquire)) == last && !w->stop.load(std::memory_order_relaxed); ++spin)
-                __builtin_ia32_pause();
-            if (j == last && !w->stop.load()) {
-                std::unique_lock<std::mutex> lk(w->m);
-                w->cv.wait(lk, [&] { return w->job.load(std::memory_order_acquire) != last || w->stop.load(); });
-                j = w->job.load(std::memory_order_acquire);
-            }
-            if (w->stop.load()) return;
-            try {
-                run_lane(*w->pr, w->lane, w->s, w->pr->run_seq);
-            } catch (const HipError& e) {
-                w->err = e.msg;
-                lanes_abort.store(true);
-            }
-            last = j;
-            w->done.store(j, std::memory_order_release);
-        }
-    }
-
-    void stop_workers() {
-        for (auto& w : workers) {
-            if (!w) continue;
-            w->stop.store(true);
-            { std::lock_guard<std::mutex> lk(w->m); }
-            w->cv.notify_one();
-            if (w->th.joinable()) w->th.join();
-            w.reset();
-        }
-    }
-
-    void run_threaded(Program& pr, hipStream_t s0) {
-        if (!pr.two_lanes) { run_launches(pr, s0); return; }
-        hipStream_t ls[FQL_LANES] = {s0, stream2, stream3, stream4};
-        if (pr.rec_n != pr.launches.size()) {      // first run of this program: events and sequence slots
-            pr.rec.reset(new std::atomic<uint64_t>[pr.launches.size()]);
-            for (size_t i = 0; i < pr.launches.size(); ++i) pr.rec[i].store(0);
-            pr.rec_n = pr.launches.size();
-            pr.run_seq = 0;
-            for (Launch& L : pr.launches)
-                if (L.record_after && !L.ev) HIP_CHECK(hipEventCreateWithFlags(&L.ev, hipEventDisableTiming));
-            if (!pr.ev_fork) HIP_CHECK(hipEventCreateWithFlags(&pr.ev_fork, hipEventDisableTiming));
-            for (int l = 1; l < FQL_LANES; ++l)
-                if (pr.lane_used[l] && !pr.ev_join[l]) HIP_CHECK(hipEventCreateWithFlags(&pr.ev_join[l], hipEventDisableTiming));
-        }
-        const uint64_t seq = ++pr.run_seq;
-        lanes_abort.store(false);
-        HIP_CHECK(hipEventRecord(pr.ev_fork, s0));
-        for (int l = 1; l < FQL_LANES; ++l) {
-            if (!pr.lane_used[l]) continue;
-            if (!workers[l]) {
-                workers[l].reset(new LaneWorker);
-                workers[l]->lane = l;
-                workers[l]->th = std::thread([this, w = workers[l].get()] { worker_main(w); });
-            }
-            LaneWorker* w = workers[l].get();
-            w->pr = &pr; w->s = ls[l]; w->err.clear();
-            // job numbers are per worker (programs alternate), the run's sequence number travels in the program
-            w->job.store(w->job.load(std::memory_order_relaxed) + 1, std::memory_order_release);
-            { std::lock_guard<std::mutex> lk(w->m); }
-            w->cv.notify_one();
-        }
-        std::string err0;
-        try { run_lane(pr, 0, s0, seq); } catch (const HipError& e) { err0 = e.msg; lanes_abort.store(true); }
-        for (int l = 1; l < FQL_LANES; ++l) {
-            if (!pr.lane_used[l]) continue;
-            LaneWorker* w = workers[l].get();
-            const uint64_t want = w->job.load(std::memory_order_relaxed);
-            while (w->done.load(std::memory_order_acquire) != want) __builtin_ia32_pause();
-            if (err0.empty() && !w->err.empty()) err0 = w->err;
-            if (err0.empty()) HIP_CHECK(hipStreamWaitEvent(s0, pr.ev_join[l], 0));
-        }
-        if (!err0.empty()) throw HipError{err0};
-    }
-
-    // fork = true: the lanes of a multi-lane program on the lane streams (graph capture, or eager issue with FQL_NO_GRAPH=2); otherwise
-    // everything goes to `s0` in emission order, which is a topological order of the program.
-    void run_launches(Program& pr, hipStream_t s0, bool fork = false) {
-        const bool par = fork && pr.two_lanes;
-        hipStream_t ls[FQL_LANES] = {s0, stream2, stream3, stream4};
-        if (par) {
-            if (!pr.ev_fork) HIP_CHECK(hipEventCreateWithFlags(&pr.ev_fork, hipEventDisableTiming));
-            HIP_CHECK(hipEventRecord(pr.ev_fork, s0));
-            for (int l = 1; l < FQL_LANES; ++l) if (pr.lane_used[l]) HIP_CHECK(hipStreamWaitEvent(ls[l], pr.ev_fork, 0));
-        }
+    // a program's launches through issue_lanes (ls == nullptr: every launch on s0), logged under FQL_TRACE
+    void run_launches(Program& pr, hipStream_t s0, const hipStream_t* ls = nullptr, bool fork = true) {
         static const bool trace_l = getenv("FQL_TRACE") != nullptr;
-        for (Launch& L : pr.launches) {
-            hipStream_t s = par ? ls[L.lane] : s0;
+        issue_lanes(pr, s0, ls, fork, [&](const Launch& L, hipStream_t s) {
             if (trace_l) {
                 fprintf(stderr, "[fql] launch %d type %d lane %d grid %d waits %zu:", (int)(&L - pr.launches.data()), (int)L.type, L.lane, L.grid, L.waits.size());
                 for (int w : L.waits) fprintf(stderr, " %d(lane %d)", w, pr.launches[w].lane);
                 fprintf(stderr, "\n");
             }
-            if (par)
-                for (int w : L.waits) if (pr.launches[w].ev) HIP_CHECK(hipStreamWaitEvent(s, pr.launches[w].ev, 0));
-            issue(L, s, (&pr == &prog_full) ? (int)(&L - pr.launches.data()) : -1);
-            if (par && L.record_after) {
-                if (!L.ev) HIP_CHECK(hipEventCreateWithFlags(&L.ev, hipEventDisableTiming));
-                HIP_CHECK(hipEventRecord(L.ev, s));
-            }
-        }
-        if (par)
-            for (int l = 1; l < FQL_LANES; ++l) {
-                if (!pr.lane_used[l]) continue;
-                if (!pr.ev_join[l]) HIP_CHECK(hipEventCreateWithFlags(&pr.ev_join[l], hipEventDisableTiming));
-                HIP_CHECK(hipEventRecord(pr.ev_join[l], ls[l]));
-                HIP_CHECK(hipStreamWaitEvent(s0, pr.ev_join[l], 0));
-            }
-        HIP_CHECK(hipGetLastError());
+            issue_of(pr, L, s);
+        });
+    }
+    // what issue() dispatches for each launch of `pr`, in order, recorded instead of launched
+    std::vector<AqlDispatch> record_dispatches(const Program& pr) {
+        std::vector<AqlDispatch> rec;
+        aql_rec = &rec;
+        try {
+            for (const Launch& L : pr.launches) issue_of(pr, L, nullptr);
+        } catch (...) { aql_rec = nullptr; throw; }
+        aql_rec = nullptr;
+        if (rec.size() != pr.launches.size()) throw HipError{"internal: a launch did not record exactly one dispatch"};
+        return rec;
     }
 
     // The program as AQL packet templates for the engine's own HSA queues (fql_aql.h): one queue per lane, the barrier bit inside a lane,
-    // completion signal -> barrier-AND packet across lanes.  Left off (ap.ok = false, the captured graph runs) when the HSA runtime does not
-    // come up or FQL_AQL=0.
-    void build_aql(Program& pr, AqlProgram& ap) {
+    // completion signal -> barrier-AND packet across lanes, into pr.aql.  Left off (pr.aql.ok = false, the captured graph runs) when the HSA
+    // runtime does not come up or FQL_AQL=0.
+    void build_aql(Program& pr) {
         static const bool off = getenv("FQL_AQL") && atoi(getenv("FQL_AQL")) == 0;
         static const bool trace_a = getenv("FQL_TRACE") != nullptr;
+        AqlProgram& ap = pr.aql;
         ap = AqlProgram{};
         if (off || visual) return;   // (visual updates gather their frames with HIP launches in front of the program and are device-bound anyway)
         void* kargs = nullptr;
         try {
             if (!aql.up && aql.why.empty()) aql.init(device, (const void*)&fql_create);
             if (!aql.up) throw AqlError{aql.why};
-            std::vector<AqlDispatch> rec;
-            aql_rec = &rec;
-            try { for (const Launch& L : pr.launches) issue(L, nullptr, (&pr == &prog_full) ? (int)(&L - pr.launches.data()) : -1); } catch (...) { aql_rec = nullptr; throw; }   // (timeline ids: diagnostics build only)
-            aql_rec = nullptr;
+            const std::vector<AqlDispatch> rec = record_dispatches(pr);
             const size_t n = pr.launches.size();
-            if (rec.size() != n) throw AqlError{"a launch did not record exactly one dispatch"};
 
             std::vector<const AqlKernelInfo*> ki(n);
             std::vector<size_t> koff(n);
@@ -2231,7 +2152,6 @@ struct fql_engine {
             if (trace_a) fprintf(stderr, "[fql] AQL program: %zu launches, packets per lane %zu %zu %zu %zu, %d signals, %zu bytes of kernargs\n", n,
                                  ap.lane[0].size(), ap.lane[1].size(), ap.lane[2].size(), ap.lane[3].size(), nsig, tot);
         } catch (const AqlError& e) {
-            aql_rec = nullptr;
             if (kargs) hipFree(kargs);
             ap = AqlProgram{};
             if (aql.why.empty()) aql.why = e.msg;
@@ -2243,25 +2163,7 @@ struct fql_engine {
         if (pr.exec) { hipGraphExecDestroy(pr.exec); pr.exec = nullptr; }
         if (pr.graph) { hipGraphDestroy(pr.graph); pr.graph = nullptr; }
         HIP_CHECK(hipStreamSynchronize(stream));
-        HIP_CHECK(hipStreamBeginCapture(stream, hipStreamCaptureModeThreadLocal));
-        try {
-            run_launches(pr, stream, true);
-        } catch (...) {
-            hipGraph_t g = nullptr;
-            hipStreamEndCapture(stream, &g);
-            if (g) hipGraphDestroy(g);
-            throw;
-        }
-        static const bool trace_c = getenv("FQL_TRACE") != nullptr;
-        if (trace_c) fprintf(stderr, "[fql] end capture\n");
-        HIP_CHECK(hipStreamEndCapture(stream, &pr.graph));
-        if (trace_c) {
-            size_t nn = 0;
-            hipGraphGetNodes(pr.graph, nullptr, &nn);
-            fprintf(stderr, "[fql] instantiate (%zu nodes)\n", nn);
-        }
-        HIP_CHECK(hipGraphInstantiate(&pr.exec, pr.graph, nullptr, nullptr, 0));
-        if (trace_c) fprintf(stderr, "[fql] instantiated\n");
+        capture_graph(stream, [&] { run_launches(pr, stream, lane_streams); }, pr.graph, pr.exec);
     }
 
     // one graph per segment: seg 0 = lane-0 launches up to the last one lane 1 waits on, seg 1 = lane 1, seg 2 = lane 0 up to
@@ -2289,17 +2191,7 @@ struct fql_engine {
                 if (seg_of(li) == seg) { Launch L = pr.launches[li]; L.waits.clear(); L.record_after = false; L.ev = nullptr; L.lane = 0; sub.launches.push_back(L); }
             if (sub.launches.empty()) return false;
             HIP_CHECK(hipStreamSynchronize(stream));
-            HIP_CHECK(hipStreamBeginCapture(stream, hipStreamCaptureModeThreadLocal));
-            try {
-                run_launches(sub, stream, false);
-            } catch (...) {
-                hipGraph_t g = nullptr;
-                hipStreamEndCapture(stream, &g);
-                if (g) hipGraphDestroy(g);
-                throw;
-            }
-            HIP_CHECK(hipStreamEndCapture(stream, &split_graph[seg]));
-            HIP_CHECK(hipGraphInstantiate(&split_exec[seg], split_graph[seg], nullptr, nullptr, 0));
+            capture_graph(stream, [&] { run_launches(sub, stream); }, split_graph[seg], split_exec[seg]);
         }
         if (!ev_a) HIP_CHECK(hipEventCreateWithFlags(&ev_a, hipEventDisableTiming));
         if (!ev_b) HIP_CHECK(hipEventCreateWithFlags(&ev_b, hipEventDisableTiming));
@@ -2328,12 +2220,16 @@ struct fql_engine {
         split_begun = true;
     }
 
-    void free_program(Program& pr) {
+    // Never throws (fql_destroy runs it, often from a garbage collector): updates of the program's AQL form still on the queues finish
+    // first; a queue that has failed was reported by the call that met it, and its buffers are released all the same.
+    void free_program(Program& pr) noexcept {
+        if (pr.aql.kernargs) {
+            try { aql_drain(); } catch (...) {}
+            hipFree(pr.aql.kernargs);
+        }
         if (pr.exec) hipGraphExecDestroy(pr.exec);
         if (pr.graph) hipGraphDestroy(pr.graph);
-        for (Launch& L : pr.launches) if (L.ev) hipEventDestroy(L.ev);
-        if (pr.ev_fork) hipEventDestroy(pr.ev_fork);
-        for (hipEvent_t e : pr.ev_join) if (e) hipEventDestroy(e);
+        destroy_lane_events(pr);
         pr = Program{};
     }
 
@@ -2677,28 +2573,14 @@ struct fql_engine {
     }
     // the optimizer program as plain launches on two caller streams (no capture: five launches)
     void run_opt_split(hipStream_t s0, hipStream_t s1) {
-        Program& pr = prog_opt_split;
         // lane 1 rewrites the critic's and the BC flow's parameters (and the chain's weight copies): it must not pass lane 0's last
         // reader of them, the Euler chain.  After a split begin that point is ev_c; otherwise everything enqueued on s0 so far.
         if (!ev_c) HIP_CHECK(hipEventCreateWithFlags(&ev_c, hipEventDisableTiming));
         if (!split_begun) HIP_CHECK(hipEventRecord(ev_c, s0));
         HIP_CHECK(hipStreamWaitEvent(s1, ev_c, 0));
         split_begun = false;
-        for (Launch& L : pr.launches) {
-            hipStream_t s = L.lane == 0 ? s0 : s1;
-            for (int w : L.waits) if (pr.launches[w].ev) HIP_CHECK(hipStreamWaitEvent(s, pr.launches[w].ev, 0));
-            issue(L, s, -1);
-            if (L.record_after) {
-                if (!L.ev) HIP_CHECK(hipEventCreateWithFlags(&L.ev, hipEventDisableTiming));
-                HIP_CHECK(hipEventRecord(L.ev, s));
-            }
-        }
-        if (pr.lane_used[1]) {   // s0 ends behind everything of the update
-            if (!pr.ev_join[1]) HIP_CHECK(hipEventCreateWithFlags(&pr.ev_join[1], hipEventDisableTiming));
-            HIP_CHECK(hipEventRecord(pr.ev_join[1], s1));
-            HIP_CHECK(hipStreamWaitEvent(s0, pr.ev_join[1], 0));
-        }
-        HIP_CHECK(hipGetLastError());
+        const hipStream_t ls[FQL_LANES] = {s0, s1, s1, s1};
+        run_launches(prog_opt_split, s0, ls, false);   // s0 ends behind everything of the update
     }
 
     // fwd + bwd + optimizer in one graph (single-GPU calls): Adam of a module is issued on the lane that produced its
@@ -2814,9 +2696,7 @@ struct fql_engine {
         schedule(prog_loss, W);
         capture(prog_full);
         capture(prog_loss);
-        aql_tried = false;
         split_ok = false;
-        launches_per_update = (int64_t)prog_full.launches.size();
         src_valid = false;
     }
 
@@ -2944,9 +2824,7 @@ struct fql_engine {
         build_rebrac_program(prog_loss, true, false);
         for (Program* pr : {&prog_full, &prog_critic, &prog_loss}) schedule(*pr, W);
         for (Program* pr : {&prog_full, &prog_critic, &prog_loss}) capture(*pr);
-        aql_tried = false;
         split_ok = false;
-        launches_per_update = (int64_t)prog_full.launches.size();
         src_valid = false;
     }
     // multiply-accumulates of one ReBRAC update per batch row, algorithmic (full GEMM shapes)
@@ -2994,7 +2872,7 @@ struct fql_engine {
         return total;
     }
 
-    void free_workspace() {
+    void free_workspace() noexcept {
         free_program(prog_fwdbwd);
         free_program(prog_opt);
         free_program(prog_opt_split);
@@ -3002,11 +2880,6 @@ struct fql_engine {
         free_program(prog_split);
         free_program(prog_full);
         free_program(prog_critic);
-        aql_drain();
-        if (aql_full.kernargs) { hipFree(aql_full.kernargs); }
-        aql_full = AqlProgram{};
-        if (aql_critic.kernargs) { hipFree(aql_critic.kernargs); }
-        aql_critic = AqlProgram{};
         free_split();
         for (void* p : ws_allocs) hipFree(p);
         ws_allocs.clear();
@@ -3092,7 +2965,6 @@ struct fql_engine {
             FQL_TR("scheduled full");
             capture(prog_full);
             FQL_TR("captured full");
-            aql_tried = false;   // (the AQL form of this program is built by the first update that can use it: run_full)
         }
         {
             split_build = true;
@@ -3101,8 +2973,6 @@ struct fql_engine {
             schedule(prog_split, W);
             split_ok = capture_split(prog_split);
         }
-        launches_per_update = prog_full.exec ? (int64_t)prog_full.launches.size()
-                                             : (int64_t)prog_fwdbwd.launches.size() + (int64_t)prog_opt.launches.size();
         src_valid = false;
     }
 
@@ -3508,7 +3378,7 @@ struct fql_engine {
         if ((h) && (h)->rebrac) { (h)->err = what " is not available on a ReBRAC handle (" why ")"; return FQL_E_STATE; } \
     } while (0)
 // FQL_TRY: every entry point that may use HIP on the engine's buffers - updates still on the engine's AQL queues finish first.
-// FQL_TRY_FAST: the update entry points that can go to those queues themselves (run_full decides).
+// FQL_TRY_FAST: the update entry points that can go to those queues themselves (run_update decides).
 #define FQL_TRY(h, ...) FQL_TRY_(h, ((h)->group_fence(), (h)->hip_touch()), __VA_ARGS__)
 #define FQL_TRY_FAST(h, ...) FQL_TRY_(h, (h)->group_fence(), __VA_ARGS__)
 #define FQL_TRY_(h, pre, ...)                              \
@@ -3685,9 +3555,7 @@ static int create_engine(const fql_config* cfg, const fql_ifql_config* icfg, con
         h->num_cus = prop.multiProcessorCount;
         // (stream priorities and CU masks were tried for the graph lanes in rounds 1-2: no gain with two streams, a 4x slowdown with three)
         HIP_CHECK(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-        HIP_CHECK(hipStreamCreateWithFlags(&h->stream2, hipStreamNonBlocking));
-        HIP_CHECK(hipStreamCreateWithFlags(&h->stream3, hipStreamNonBlocking));
-        HIP_CHECK(hipStreamCreateWithFlags(&h->stream4, hipStreamNonBlocking));
+        for (int l = 1; l < FQL_LANES; ++l) HIP_CHECK(hipStreamCreateWithFlags(&h->lane_streams[l], hipStreamNonBlocking));
         h->build_nets();
         HIP_CHECK(hipMalloc((void**)&h->P, h->n_total * sizeof(float)));
         HIP_CHECK(hipMalloc((void**)&h->G, h->n_train * sizeof(float)));
@@ -3725,7 +3593,6 @@ static int create_engine(const fql_config* cfg, const fql_ifql_config* icfg, con
 int fql_destroy(fql_handle h) {
     if (!h) return FQL_OK;
     if (h->group) { h->err = "fql_destroy: the handle is a member of an agent group (fql_group_destroy first)"; return FQL_E_STATE; }
-    h->stop_workers();
     try { h->aql_drain(); } catch (...) {}
     if (h->stream) hipStreamSynchronize(h->stream);
     hipDeviceSynchronize();
@@ -3745,9 +3612,7 @@ int fql_destroy(fql_handle h) {
     for (void* q : h->enc_allocs) hipFree(q);
     for (void* q : h->chain_allocs) hipFree(q);
     if (h->stream) hipStreamDestroy(h->stream);
-    if (h->stream2) hipStreamDestroy(h->stream2);
-    if (h->stream3) hipStreamDestroy(h->stream3);
-    if (h->stream4) hipStreamDestroy(h->stream4);
+    for (hipStream_t s : h->lane_streams) if (s) hipStreamDestroy(s);
     delete h;
     return FQL_OK;
 }
@@ -3835,35 +3700,40 @@ int fql_set_step(fql_handle h, int64_t adam_count, int64_t train_step) {
 // torch's *default* stream maps to (its handle reads 0, which cannot be told from "no stream" here); anything else is a hipStream_t.
 static hipStream_t pick(fql_handle h, void* s) { return s ? (hipStream_t)s : h->stream; }
 
+// FQL_NO_GRAPH (diagnostics; the captured graph is the product path): 1 = eager launches on one stream, 2 = eager launches on the lane
+// streams (tests/test_gpu_streams.py runs the parity suite under it); any other non-zero value acts as 1
+static int no_graph() {
+    static const int v = getenv("FQL_NO_GRAPH") ? atoi(getenv("FQL_NO_GRAPH")) : 0;
+    return v;
+}
+
 static void run_program(fql_handle h, Program& pr, hipStream_t s) {
-    // FQL_NO_GRAPH (diagnostics; the captured graph is the product path): 1 = eager launches on one stream, 2 = eager launches on the lane
-    // streams, 3 = one host thread per lane (run_threaded; tests/test_gpu_streams.py runs the parity suite under it)
-    static const int no_graph = getenv("FQL_NO_GRAPH") ? atoi(getenv("FQL_NO_GRAPH")) : 0;
-    if (no_graph == 3) h->run_threaded(pr, s);
-    else if (no_graph == 2) h->run_launches(pr, s, true);
-    else if (no_graph) h->run_launches(pr, s);
+    if (no_graph() == 2) h->run_launches(pr, s, h->lane_streams);
+    else if (no_graph()) h->run_launches(pr, s);
     else HIP_CHECK(hipGraphLaunch(pr.exec, s));
 }
 
-// The whole update (prog_full).  The caller left the stream to the engine: pre-built AQL packets on the engine's own queues (fql_aql.h; the
-// stream is drained first if HIP work may be pending on it).  Otherwise, or when that path is off: the captured graph on `s`.
-static void run_full(fql_handle h, hipStream_t s, bool own_stream) {
-    static const int no_graph = getenv("FQL_NO_GRAPH") ? atoi(getenv("FQL_NO_GRAPH")) : 0;
-    if (own_stream && !no_graph && h->prog_full.exec && !h->aql_tried) {
-        h->aql_tried = true;
-        h->hip_touch();
-        h->build_aql(h->prog_full, h->aql_full);
-    }
-    if (own_stream && h->aql_full.ok && !no_graph && h->prog_full.exec) {
-        if (h->hip_dirty) { HIP_CHECK(hipStreamSynchronize(s)); h->hip_dirty = false; }
-        try { h->aql.submit(h->aql_full); } catch (const AqlError& e) { throw HipError{e.msg}; }
-        h->last_update_aql = true;
-        return;
+// One update: `pr` is prog_full (FQL, IFQL, a full ReBRAC step) or prog_critic (a critic-only ReBRAC step).  The caller left the stream to
+// the engine: the program's AQL form on the engine's own queues (fql_aql.h; built by the first such update, the stream drained first if
+// HIP work may be pending on it).  Otherwise, or when that path is off: the captured graph on `s`.
+static void run_update(fql_handle h, Program& pr, hipStream_t s, bool own_stream) {
+    require_graph(pr);
+    if (own_stream && !no_graph()) {
+        if (!pr.aql_tried) {
+            pr.aql_tried = true;
+            h->hip_touch();
+            h->build_aql(pr);
+        }
+        if (pr.aql.ok) {
+            if (h->hip_dirty) { HIP_CHECK(hipStreamSynchronize(s)); h->hip_dirty = false; }
+            try { h->aql.submit(pr.aql); } catch (const AqlError& e) { throw HipError{e.msg}; }
+            h->last_update_aql = true;
+            return;
+        }
     }
     h->last_update_aql = false;
     h->hip_touch();
-    if (h->prog_full.exec) run_program(h, h->prog_full, s);
-    else { run_program(h, h->prog_fwdbwd, s); run_program(h, h->prog_opt, s); }
+    run_program(h, pr, s);
 }
 
 int fql_update_begin(fql_handle h, const float* obs, const float* act, const float* rew, const float* mask,
@@ -3892,11 +3762,11 @@ int fql_update_end(fql_handle h, float* info13, void* stream) {
 int fql_update(fql_handle h, const float* obs, const float* act, const float* rew, const float* mask, const float* nobs,
                int batch_size, const fql_noise* noise, float* info13, void* stream) {
     FQL_REBRAC_REFUSES(h, "fql_update", "its batch has no next_actions: fql_rebrac_update");
-    if (h && h->prog_full.exec && !h->began) {
+    if (h && !h->began) {
         FQL_TRY_FAST(h, {
             hipStream_t s = pick(h, stream);
             h->source_from_batch(obs, act, rew, mask, nobs, batch_size, noise, 1, s);
-            run_full(h, s, stream == nullptr);
+            run_update(h, h->prog_full, s, stream == nullptr);
             h->finish_info(info13, FQL_NUM_INFO, s);
         });
     }
@@ -4131,7 +4001,7 @@ int fql_update_balanced(fql_handle h, const int64_t* idx_dataset, const int64_t*
         hipStream_t s = pick(h, stream);
         if (h->visual) h->hip_touch();
         h->source_balanced(idx_dataset, idx_replay, crop_froms, batch_size, noise, s);
-        run_full(h, s, stream == nullptr);
+        run_update(h, h->prog_full, s, stream == nullptr);
         h->finish_info(info13, FQL_NUM_INFO, s);
     });
 }
@@ -4193,11 +4063,11 @@ int fql_update_from_dataset(fql_handle h, const int64_t* idx, int batch_size, in
                             float* info13, void* stream) {
     FQL_REBRAC_REFUSES(h, "fql_update_from_dataset", "the step kind is an argument: fql_rebrac_update_from_dataset");
     if (h && h->visual) return fql_update_from_frames(h, idx, nullptr, batch_size, lo, hi, noise, info13, stream);
-    if (h && h->prog_full.exec && !h->began) {
+    if (h && !h->began) {
         FQL_TRY_FAST(h, {
             hipStream_t s = pick(h, stream);
             h->source_from_dataset(idx, batch_size, lo, hi, noise, s);
-            run_full(h, s, stream == nullptr);
+            run_update(h, h->prog_full, s, stream == nullptr);
             h->finish_info(info13, FQL_NUM_INFO, s);
         });
     }
@@ -4247,7 +4117,7 @@ int fql_read_info(fql_handle h, float* info13_host) {
 
 int fql_stats(fql_handle h, int64_t* launches_per_update, int64_t* macs_per_update, int64_t* param_count) {
     if (!h) return FQL_E_INVALID;
-    if (launches_per_update) *launches_per_update = h->launches_per_update;
+    if (launches_per_update) *launches_per_update = (int64_t)h->prog_full.launches.size();
     if (macs_per_update) *macs_per_update = h->macs_per_update();
     if (param_count) {
         int64_t n = 0;
@@ -4259,27 +4129,7 @@ int fql_stats(fql_handle h, int64_t* launches_per_update, int64_t* macs_per_upda
 void* fql_stream(fql_handle h) { return h ? (void*)h->stream : nullptr; }
 
 // ---- ReBRAC (agents/rebrac.py) ---------------------------------------------------------------------------------------------------
-// One update: the full program (full_update != 0) or the critic-only one, on the engine's AQL queues when the caller left the stream to
-// the engine, else the captured graph on `s` (both bitwise equal).
-static void run_rebrac(fql_handle h, hipStream_t s, bool own_stream, bool full_update) {
-    static const int no_graph = getenv("FQL_NO_GRAPH") ? atoi(getenv("FQL_NO_GRAPH")) : 0;
-    if (own_stream && !no_graph && !h->aql_tried) {
-        h->aql_tried = true;
-        h->hip_touch();
-        h->build_aql(h->prog_full, h->aql_full);
-        if (h->aql_full.ok) h->build_aql(h->prog_critic, h->aql_critic);
-    }
-    const AqlProgram& ap = full_update ? h->aql_full : h->aql_critic;
-    if (own_stream && ap.ok && !no_graph) {
-        if (h->hip_dirty) { HIP_CHECK(hipStreamSynchronize(s)); h->hip_dirty = false; }
-        try { h->aql.submit(ap); } catch (const AqlError& e) { throw HipError{e.msg}; }
-        h->last_update_aql = true;
-        return;
-    }
-    h->last_update_aql = false;
-    h->hip_touch();
-    run_program(h, full_update ? h->prog_full : h->prog_critic, s);
-}
+// One update: the full program (full_update != 0) or the critic-only one, through run_update (the AQL form and the graph are bitwise equal).
 #define FQL_REBRAC_ONLY(h, what)                                                                           \
     do {                                                                                                \
         if (!(h)) return FQL_E_INVALID;                                                                 \
@@ -4291,7 +4141,7 @@ int fql_rebrac_update(fql_handle h, const float* obs, const float* act, const fl
     FQL_TRY_FAST(h, {
         hipStream_t s = pick(h, stream);
         h->rebrac_source_from_batch(obs, act, rew, masks, next_obs, next_actions, batch_size, noise, 1, s);
-        run_rebrac(h, s, stream == nullptr, full_update != 0);
+        run_update(h, full_update ? h->prog_full : h->prog_critic, s, stream == nullptr);
         h->finish_info(info13, FQL_NUM_INFO, s);
     });
 }
@@ -4301,7 +4151,7 @@ int fql_rebrac_update_from_dataset(fql_handle h, const int64_t* idx, int batch_s
     FQL_TRY_FAST(h, {
         hipStream_t s = pick(h, stream);
         h->rebrac_source_from_dataset(idx, batch_size, lo, hi, noise, s);
-        run_rebrac(h, s, stream == nullptr, full_update != 0);
+        run_update(h, full_update ? h->prog_full : h->prog_critic, s, stream == nullptr);
         h->finish_info(info13, FQL_NUM_INFO, s);
     });
 }
@@ -4345,8 +4195,8 @@ int fql_rebrac_stats(fql_handle h, int full_update, int64_t* launches_per_update
 extern "C" int fql_profile_update(fql_handle h, int batch_size, int cap, int* type, int* lane, int* grid, float* us, double* macs, float* null_us) {
     FQL_REBRAC_REFUSES(h, "fql_profile_update", "FQL batch sources only");
     if (!h || !type || !us) return FQL_E_INVALID;
-    if (!h->prog_full.exec) { h->err = "no single-graph update program"; return FQL_E_STATE; }
     try {
+        require_graph(h->prog_full);
         hipStream_t s = h->stream;
         if (null_us) *null_us = 0.f;   // (no calibration needed: the events ride on the dispatches)
         h->source_from_dataset(nullptr, batch_size, 0, 0, nullptr, s);
@@ -4558,8 +4408,7 @@ int fql_update_from_frames(fql_handle h, const int64_t* idx, const int32_t* crop
     FQL_TRY(h, {
         hipStream_t s = pick(h, stream);
         h->source_from_frames(idx, crop_froms, batch_size, lo, hi, noise, s);
-        if (h->prog_full.exec) run_program(h, h->prog_full, s);
-        else { run_program(h, h->prog_fwdbwd, s); run_program(h, h->prog_opt, s); }
+        run_update(h, h->prog_full, s, stream == nullptr);
         h->finish_info(info13, FQL_NUM_INFO, s);
     });
 }
@@ -4721,28 +4570,7 @@ struct fql_group_s {
 
     // the fused program as ONE graph with the lanes, forks, joins and cross-lane events of a member's own
     void capture() {
-        hipStream_t s0 = lanes[0];
-        HIP_CHECK(hipStreamBeginCapture(s0, hipStreamCaptureModeThreadLocal));
-        try {
-            HIP_CHECK(hipEventRecord(ev_fork, s0));
-            for (int l = 1; l < FQL_LANES; ++l) if (lane_used[l]) HIP_CHECK(hipStreamWaitEvent(lanes[l], ev_fork, 0));
-            for (GLaunch& G : launches) {
-                hipStream_t s = lanes[G.lane];
-                for (int w : G.waits) HIP_CHECK(hipStreamWaitEvent(s, launches[w].ev, 0));
-                issue(G, s);
-                if (G.record_after) HIP_CHECK(hipEventRecord(G.ev, s));
-            }
-            for (int l = 1; l < FQL_LANES; ++l)
-                if (lane_used[l]) { HIP_CHECK(hipEventRecord(ev_join[l], lanes[l])); HIP_CHECK(hipStreamWaitEvent(s0, ev_join[l], 0)); }
-            HIP_CHECK(hipGetLastError());
-        } catch (...) {
-            hipGraph_t g = nullptr;
-            hipStreamEndCapture(s0, &g);
-            if (g) hipGraphDestroy(g);
-            throw;
-        }
-        HIP_CHECK(hipStreamEndCapture(s0, &graph));
-        HIP_CHECK(hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0));
+        capture_graph(lanes[0], [&] { issue_lanes(*this, lanes[0], lanes, true, [&](GLaunch& G, hipStream_t s) { issue(G, s); }); }, graph, exec);
     }
 
     void release() {
@@ -4751,9 +4579,8 @@ struct fql_group_s {
         for (fql_handle h : m) { h->group = nullptr; h->grp_pending = false; h->grp_done = nullptr; h->grp_touched = true; }
         if (exec) hipGraphExecDestroy(exec);
         if (graph) hipGraphDestroy(graph);
-        for (GLaunch& G : launches) if (G.ev) hipEventDestroy(G.ev);
-        for (hipEvent_t e : {ev_fork, ev_in, ev_done}) if (e) hipEventDestroy(e);
-        for (hipEvent_t e : ev_join) if (e) hipEventDestroy(e);
+        destroy_lane_events(*this);
+        for (hipEvent_t e : {ev_in, ev_done}) if (e) hipEventDestroy(e);
         for (void* p : allocs) hipFree(p);
         if (d_idx) hipFree(d_idx);
         for (hipStream_t s : lanes) if (s) hipStreamDestroy(s);
@@ -4772,7 +4599,7 @@ void group_check(const fql_handle* members, int k) {
         if (h->visual) invalid("fql_group_create: member %d has an encoder (groups take state agents only)", i);
         if (h->cfg.precision != 0) invalid("fql_group_create: member %d has precision %d (groups take fp32 members only)", i, h->cfg.precision);
         if (h->began) invalid("fql_group_create: member %d is between fql_update_begin and fql_update_end", i);
-        if (!h->prog_full.exec) invalid("fql_group_create: member %d has no single-graph update program", i);
+        require_graph(h->prog_full);
         fql_config a = h->cfg, b = members[0]->cfg;
         a.alpha = b.alpha = 0.f;
         a.batch_size = b.batch_size = 0;
@@ -4790,16 +4617,6 @@ void group_check(const fql_handle* members, int k) {
             if (L.type == OP_WFRAG && h->wfrag_grid != members[0]->wfrag_grid) invalid("fql_group_create: member %d's weight-copy launch differs", i);
         }
     }
-}
-std::vector<AqlDispatch> record_program(fql_handle h) {
-    std::vector<AqlDispatch> rec;
-    h->aql_rec = &rec;
-    try {
-        for (const Launch& L : h->prog_full.launches) h->issue(L, nullptr, (int)(&L - h->prog_full.launches.data()));
-    } catch (...) { h->aql_rec = nullptr; throw; }
-    h->aql_rec = nullptr;
-    if (rec.size() != h->prog_full.launches.size()) invalid("internal: a launch did not record exactly one dispatch");
-    return rec;
 }
 }  // namespace
 
@@ -4822,7 +4639,7 @@ int fql_group_create(const fql_handle* members, int k, fql_group* out) {
         g->B = members[0]->B;
         for (fql_handle h : g->m) { h->aql_drain(); HIP_CHECK(hipStreamSynchronize(h->stream)); }
         std::vector<std::vector<AqlDispatch>> rec;
-        for (fql_handle h : g->m) rec.push_back(record_program(h));
+        for (fql_handle h : g->m) rec.push_back(h->record_dispatches(h->prog_full));
         const size_t n = g->m[0]->prog_full.launches.size();
         for (size_t li = 0; li < n; ++li)
             for (int i = 1; i < k; ++i) {
@@ -4838,9 +4655,7 @@ int fql_group_create(const fql_handle* members, int k, fql_group* out) {
             g->lane_used[g->launches.back().lane] = true;
         }
         for (int l = 0; l < FQL_LANES; ++l) HIP_CHECK(hipStreamCreateWithFlags(&g->lanes[l], hipStreamNonBlocking));
-        for (GLaunch& G : g->launches) if (G.record_after) HIP_CHECK(hipEventCreateWithFlags(&G.ev, hipEventDisableTiming));
-        for (hipEvent_t* e : {&g->ev_fork, &g->ev_in, &g->ev_done}) HIP_CHECK(hipEventCreateWithFlags(e, hipEventDisableTiming));
-        for (int l = 1; l < FQL_LANES; ++l) HIP_CHECK(hipEventCreateWithFlags(&g->ev_join[l], hipEventDisableTiming));
+        for (hipEvent_t* e : {&g->ev_in, &g->ev_done}) HIP_CHECK(hipEventCreateWithFlags(e, hipEventDisableTiming));
         HIP_CHECK(hipMalloc((void**)&g->d_idx, (size_t)k * g->B * sizeof(int64_t)));
         g->capture();
     } catch (const Invalid& e) {

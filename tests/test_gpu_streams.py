@@ -107,14 +107,15 @@ def test_uncapturable_lane_placement_is_refused_not_crashed():
     assert agent.stats()['launches_per_update'] > 0
 
 
-def test_threaded_eager_lane_executor_passes_the_parity_cases():
-    """FQL_NO_GRAPH=3 (run_threaded: one host thread per extra lane, cross-lane order through per-launch sequence numbers + events, nothing
-    captured): the same parity cases as the captured graph, in a process of its own (the mode is read once per process)."""
+def test_eager_lane_streams_pass_the_parity_cases():
+    """FQL_NO_GRAPH=2 (each lane's launches eagerly on its own stream, forked from and joined into the caller's stream, cross-lane order
+    through per-launch events, nothing captured): the same parity cases as the captured graph, in a process of its own (the mode is
+    read once per process)."""
     import os
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    env = dict(os.environ, FQL_NO_GRAPH='3')
+    env = dict(os.environ, FQL_NO_GRAPH='2')
     r = subprocess.run([sys.executable, '-m', 'pytest', 'tests/test_gpu_parity.py', '-q', '-m', 'gpu', '-x', '-k',
                         'test_total_loss_and_update_match_oracle or test_full_size_config_one_update'],
                        cwd=root, env=env, capture_output=True, text=True, timeout=300)
