@@ -1,14 +1,15 @@
 """fql_amd: MI355X-native (gfx950) Flow Q-Learning gradient step behind the reference's FQLAgent API.
 
-`agents` mirrors the reference registry (agents/__init__.py:10-19) for the agents on the built path: FQL, IFQL and ReBRAC.
+`agents` mirrors the reference registry (agents/__init__.py:10-19) for the agents on the built path: FQL, IFQL, ReBRAC and SAC (RLPD's learner).
 """
 from .agent import FQLAgent, FQLAgentGroup, INFO_KEYS, NOISE_KEYS
 from .config import get_config
 from .datasets import Dataset, ReplayBuffer
 from .ifql import IFQLAgent, IFQL_INFO_KEYS
 from .rebrac import ReBRACAgent, REBRAC_INFO_KEYS, REBRAC_CRITIC_INFO_KEYS
+from .sac import SACAgent, SAC_INFO_KEYS
 
-agents = dict(fql=FQLAgent, ifql=IFQLAgent, rebrac=ReBRACAgent)
+agents = dict(fql=FQLAgent, ifql=IFQLAgent, rebrac=ReBRACAgent, sac=SACAgent)
 
-__all__ = ['FQLAgent', 'FQLAgentGroup', 'IFQLAgent', 'ReBRACAgent', 'get_config', 'agents', 'INFO_KEYS', 'IFQL_INFO_KEYS',
-           'REBRAC_INFO_KEYS', 'REBRAC_CRITIC_INFO_KEYS', 'NOISE_KEYS', 'Dataset', 'ReplayBuffer']
+__all__ = ['FQLAgent', 'FQLAgentGroup', 'IFQLAgent', 'ReBRACAgent', 'SACAgent', 'get_config', 'agents', 'INFO_KEYS', 'IFQL_INFO_KEYS',
+           'REBRAC_INFO_KEYS', 'REBRAC_CRITIC_INFO_KEYS', 'SAC_INFO_KEYS', 'NOISE_KEYS', 'Dataset', 'ReplayBuffer']

@@ -17,6 +17,7 @@ FQL_NUM_INFO = 13
 FQL_IFQL_NUM_INFO = 12
 FQL_REBRAC_NUM_INFO = 12
 FQL_REBRAC_CRITIC_NUM_INFO = 7
+FQL_SAC_NUM_INFO = 14
 FQL_OK, FQL_E_INVALID, FQL_E_NODEVICE, FQL_E_HIP, FQL_E_STATE, FQL_E_NOTFOUND = 0, -1, -2, -3, -4, -5
 
 
@@ -40,6 +41,12 @@ class FqlIfqlConfig(C.Structure):
 class FqlRebracConfig(C.Structure):
     _fields_ = [('alpha_actor', C.c_float), ('alpha_critic', C.c_float), ('actor_noise', C.c_float), ('actor_noise_clip', C.c_float),
                 ('tanh_squash', C.c_int32), ('actor_fc_scale', C.c_float), ('reserved', C.c_int32 * 6)]
+
+
+class FqlSacConfig(C.Structure):
+    _fields_ = [('target_entropy', C.c_float), ('target_entropy_multiplier', C.c_float), ('tanh_squash', C.c_int32),
+                ('state_dependent_std', C.c_int32), ('actor_fc_scale', C.c_float), ('backup_entropy', C.c_int32),
+                ('reserved', C.c_int32 * 6)]
 
 
 class FqlNoise(C.Structure):
@@ -114,6 +121,16 @@ SYMBOLS = {
     'fql_rebrac_total_loss': (_I, [_VP] + _BATCH[:5] + [_VP, _I, C.POINTER(FqlNoise), _I, C.POINTER(_F), C.POINTER(_F), _VP]),
     'fql_rebrac_sample_actions': (_I, [_VP, _VP, _I, _VP, _U64, _F, _VP, _VP]),
     'fql_rebrac_stats': (_I, [_VP, _I, C.POINTER(_I64), C.POINTER(_I64)]),
+    'fql_sac_default_config': (None, [C.POINTER(FqlSacConfig)]),
+    'fql_sac_create': (_I, [C.POINTER(FqlConfig), C.POINTER(FqlSacConfig), _U64, C.POINTER(_VP)]),
+    'fql_sac_update': (_I, [_VP] + _BATCH + [C.POINTER(FqlNoise), _VP, _VP]),
+    'fql_sac_update_from_dataset': (_I, [_VP, _VP, _I, _I64, _I64, C.POINTER(FqlNoise), _VP, _VP]),
+    'fql_sac_update_balanced': (_I, [_VP, _VP, _VP, _I, C.POINTER(FqlNoise), _VP, _VP]),
+    'fql_sac_total_loss': (_I, [_VP] + _BATCH + [C.POINTER(FqlNoise), C.POINTER(_F), C.POINTER(_F), _VP]),
+    'fql_sac_sample_actions': (_I, [_VP, _VP, _I, _VP, _U64, _F, _VP, _VP]),
+    'fql_sac_stats': (_I, [_VP, C.POINTER(_I64), C.POINTER(_I64)]),
+    'fql_read_info_n': (_I, [_VP, _VP, _I]),
+    'fql_info_wait_n': (_I, [_VP, _U64, _VP, _I]),
 }
 
 _lib = None

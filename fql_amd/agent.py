@@ -141,7 +141,7 @@ class LazyInfo(dict):
     raises on first use (the engine keeps 64 snapshots)."""
 
     def __init__(self, agent, ticket, keys=None):
-        p = _Pending(agent, ticket)
+        p = getattr(agent, '_pending_cls', _Pending)(agent, ticket)
         keys = keys if keys is not None else getattr(agent, '_info_keys', INFO_KEYS)
         super().__init__((k, LazyScalar(p, i)) for i, k in enumerate(keys))
 
@@ -703,6 +703,8 @@ class FQLAgentGroup:
         alphas = [float(cfg['alpha'])] * len(seeds) if alphas is None else [float(a) for a in alphas]
         if len(alphas) != len(seeds):
             raise ValueError(f'{len(seeds)} seeds but {len(alphas)} alphas')
+        if cfg.get('agent_name') == 'sac':
+            raise NotImplementedError('agent groups take FQL agents only (SAC groups are not available)')
         if cfg.get('encoder') is not None:
             raise NotImplementedError('agent groups take state agents only (encoder=None)')
         if cfg.get('precision', 'fp32') not in ('fp32', 0):

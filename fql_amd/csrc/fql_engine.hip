@@ -16,6 +16,7 @@
 #include "fql_aux.h"
 #include "fql_ifql.h"
 #include "fql_rebrac.h"
+#include "fql_sac.h"
 #include <hip/hip_ext.h>
 #include "fql_aql.h"
 
@@ -108,6 +109,7 @@ inline int pad16c(int c) { return (c + 15) & ~15; }
 struct Segment {  // one contiguous padded block of a leaf
     size_t off;
     int rows, cols, rows_p, cols_p;  // logical and padded 2-D shape (vectors: rows = 1)
+    int chunk_w = 0;                 // > 0: a column block of a wider layer (SAC's actor heads): Adam chunks of chunk_w floats per padded row
 };
 struct Leaf {
     std::string name;
@@ -129,7 +131,9 @@ enum OpType { OP_GEMM, OP_GEMM64, OP_WGRAD, OP_LNBWD, OP_PREP, OP_POSTOS, OP_EUL
               // IFQL (agents/ifql.py) only: after every FQL type, so FQL programs keep their launch order
               OP_IFQL_PREP, OP_IFQL_LOSS_V, OP_IFQL_LOSS_C, OP_IFQL_FIN,
               // ReBRAC (agents/rebrac.py) only: after IFQL's
-              OP_REBRAC_PREP, OP_REBRAC_ACT, OP_REBRAC_LOSS_C, OP_REBRAC_LOSS_A, OP_REBRAC_AGRAD, OP_REBRAC_FIN, OP_NUM_TYPES };
+              OP_REBRAC_PREP, OP_REBRAC_ACT, OP_REBRAC_LOSS_C, OP_REBRAC_LOSS_A, OP_REBRAC_AGRAD, OP_REBRAC_FIN,
+              // SAC (agents/sac.py) only: after ReBRAC's
+              OP_SAC_PREP, OP_SAC_ACT, OP_SAC_LOSS_C, OP_SAC_LOSS_A, OP_SAC_AGRAD, OP_SAC_FIN, OP_NUM_TYPES };
 
 struct Op {
     OpType type;
@@ -158,6 +162,11 @@ struct Op {
     RebracCriticArgs rc;
     RebracActorArgs ra;
     RebracActorGradArgs rag;
+    SacPrepArgs sprep;
+    SacActArgs sact;
+    SacCriticArgs sc;
+    SacActorArgs sa;
+    SacActorGradArgs sag;
     ChainArgs chain;
     const ConvWprepTask* wprep_tasks = nullptr;
     int wprep_n = 0;
@@ -321,6 +330,15 @@ struct fql_engine {
     float *w_nact = nullptr, *w_noise = nullptr;                            // [B, ap]: next_actions, raw N(0, 1) of the target-policy noise
     PassBuf p_a, p_ta, p_q[2];                                               // actor, target actor, critic pair on [obs | actor actions]
     Program prog_critic;
+    // SAC agent (agents/sac.py; fql_sac_create): NET_BC holds the actor, whose last layer is both heads as one [H, 2 ap] layer (mean
+    // columns [0, ap), raw log-std [ap, 2 ap)); modules_alpha/log_value sits in the NET_OS slot (4 floats at alpha_off), so the trained
+    // region is critic pair, actor, log_value and the Polyak range [0, critic_size) is the critic pair's.  p_a runs over X_a = [obs ;
+    // next_obs] (2B rows; backward over the obs rows), p_q[] is the critic pair on [obs | a], p_ct[] the target pair on [next_obs | a'].
+    bool sac = false;
+    fql_sac_config scfg{};
+    float target_entropy = 0.f;
+    size_t alpha_off = 0;
+    float *w_eps = nullptr, *lp_buf = nullptr;   // [2B, ap]: eps_c rows then eps_n rows; [2B]: log-probabilities of a, then of a'
     uint64_t seed = 0;
     int device = 0;
     hipStream_t stream = nullptr;
@@ -488,8 +506,9 @@ struct fql_engine {
         nets[NET_C0] = make(od + ad, cfg.value_hidden, cfg.num_value_hidden, 1, cfg.layer_norm != 0);
         nets[NET_C1] = nets[NET_C0];
         nets[NET_BC] = rebrac ? make(od, cfg.actor_hidden, cfg.num_actor_hidden, ad, cfg.actor_layer_norm != 0)   // actor (utils/networks.py:82-150)
+                     : sac ? make(od, cfg.actor_hidden, cfg.num_actor_hidden, 2 * pad16(ad), cfg.actor_layer_norm != 0)   // actor_net + [mean_net | log_std_net]
                               : make(od + ad + 1, cfg.actor_hidden, cfg.num_actor_hidden, ad, cfg.actor_layer_norm != 0);
-        nets[NET_OS] = rebrac ? Net{} : ifql ? make(od, cfg.value_hidden, cfg.num_value_hidden, 1, cfg.layer_norm != 0)   // value (agents/ifql.py:188-193)
+        nets[NET_OS] = (rebrac || sac) ? Net{} : ifql ? make(od, cfg.value_hidden, cfg.num_value_hidden, 1, cfg.layer_norm != 0)   // value (agents/ifql.py:188-193)
                             : make(od + ad, cfg.actor_hidden, cfg.num_actor_hidden, ad, cfg.actor_layer_norm != 0);
         nets[NET_T0] = nets[NET_C0];
         nets[NET_T1] = nets[NET_C0];
@@ -540,7 +559,11 @@ struct fql_engine {
             // every module's encoder follows its MLP(s); the critic's sits inside the Polyak-averaged region
             if (ni == NET_C1) { place_enc(ENC_C); critic_size = off; }
             if (ni == NET_BC) place_enc(ENC_BC);
-            if (ni == NET_OS) { place_enc(ENC_OS); n_train = off; }
+            if (ni == NET_OS) {
+                place_enc(ENC_OS);
+                if (sac) { alpha_off = off; off += 4; }   // modules_alpha/log_value: one float, padded to an Adam quad
+                n_train = off;
+            }
             if (ni == NET_T1) place_enc(ENC_T);
         }
         n_total = off;
@@ -593,7 +616,7 @@ struct fql_engine {
         const Net& n = nets[NET_BC];
         const int nh = n.nl() - 1;
         const int H = n.layers[0].out_p;
-        bool ok = !ifql && !rebrac && !cfg.actor_layer_norm && cfg.act_dim <= 15 && nh >= 3 && (H == 256 || H == 512);   // (IFQL has no Euler chain in its update)
+        bool ok = !ifql && !rebrac && !sac && !cfg.actor_layer_norm && cfg.act_dim <= 15 && nh >= 3 && (H == 256 || H == 512);   // (IFQL has no Euler chain in its update)
         for (int l = 0; l < nh && ok; ++l) ok = n.layers[l].out == H && n.layers[l].out_p == H;
         use_chain = ok;
         if (!ok) return;
@@ -641,10 +664,26 @@ struct fql_engine {
                                     {"modules_critic", "value_net", NET_C0, NET_C1, true, ENC_C},
                                     {"modules_target_actor", "actor_net", NET_TA, -1, false, ENC_BC, true},
                                     {"modules_target_critic", "value_net", NET_T0, NET_T1, false, ENC_T}};
-        const Mod* mods = rebrac ? rebrac_mods : ifql ? ifql_mods : fql_mods;
+        // SAC (agents/sac.py:170-196): Actor (actor_net, log_std_net, mean_net), the 0-d LogParam (n0 = -1), critic, target critic
+        const Mod sac_mods[4] = {{"modules_actor", "actor_net", NET_BC, -1, true, ENC_BC, true},
+                                 {"modules_alpha", "", -1, -1, true, ENC_BC},
+                                 {"modules_critic", "value_net", NET_C0, NET_C1, true, ENC_C},
+                                 {"modules_target_critic", "value_net", NET_T0, NET_T1, false, ENC_T}};
+        const Mod* mods = sac ? sac_mods : rebrac ? rebrac_mods : ifql ? ifql_mods : fql_mods;
         int tid = 0;
         for (int mi = 0; mi < 4; ++mi) {
             const Mod& m = mods[mi];
+            if (m.n0 < 0) {   // modules_alpha/log_value: shape ()
+                Leaf lf;
+                lf.name = std::string(m.name) + "/log_value";
+                lf.ndim = 0;
+                for (int k = 0; k < 4; ++k) lf.shape[k] = 1;
+                lf.segs.push_back(Segment{alpha_off, 1, 1, 1, 4});
+                lf.trainable = true;
+                lf.train_id = tid++;
+                leaves.push_back(lf);
+                continue;
+            }
             const Net& n0 = nets[m.n0];
             const bool ens = m.n1 >= 0;
             if (visual) {
@@ -702,7 +741,17 @@ struct fql_engine {
                 add(base + "LayerNorm_" + std::to_string(i) + "/bias", false, 1, a.out, a.be, b ? b->be : 0, 1, a.out_p);
                 add(base + "LayerNorm_" + std::to_string(i) + "/scale", false, 1, a.out, a.g, b ? b->g : 0, 1, a.out_p);
             }
-            if (m.actor) {
+            if (m.actor && sac) {   // the two heads: column blocks [0, ap) and [ap, 2 ap) of the last layer, each read back as [H, act] / [act]
+                const Layer& a = n0.layers.back();
+                const int ad = cfg.act_dim, ap = pad16(ad);
+                for (const char* head : {"log_std_net", "mean_net"}) {
+                    const size_t c0 = std::strcmp(head, "mean_net") == 0 ? 0 : (size_t)ap;
+                    const std::string hb = std::string(m.name) + "/" + head + "/";
+                    add(hb + "bias", false, 1, ad, a.b + c0, 0, 1, ap);
+                    add(hb + "kernel", true, a.in, ad, a.w + c0, 0, a.in_p, a.out_p);
+                    leaves.back().segs[0].chunk_w = ap;
+                }
+            } else if (m.actor) {
                 const Layer& a = n0.layers.back();
                 const std::string hb = std::string(m.name) + "/mean_net/";
                 add(hb + "bias", false, 1, a.out, a.b, 0, 1, a.out_p);
@@ -716,6 +765,10 @@ struct fql_engine {
         for (const Leaf& lf : leaves) {
             if (!lf.trainable) continue;
             for (const Segment& s : lf.segs) {
+                if (s.chunk_w > 0) {   // a column block of a wider layer: one chunk per padded row
+                    for (int r = 0; r < s.rows_p; ++r) ch.push_back(AdamChunk{(int)(s.off + (size_t)r * s.cols_p), s.chunk_w, lf.train_id});
+                    continue;
+                }
                 const size_t len = (size_t)s.rows_p * s.cols_p;
                 for (size_t o = 0; o < len; o += 4096)
                     ch.push_back(AdamChunk{(int)(s.off + o), (int)std::min<size_t>(4096, len - o), lf.train_id});
@@ -731,7 +784,8 @@ struct fql_engine {
             const char* fmods[3] = {"modules_actor_bc_flow/", "modules_actor_onestep_flow/", "modules_critic/"};
             const char* imods[3] = {"modules_actor_flow/", "modules_value/", "modules_critic/"};
             const char* rmods[3] = {"modules_actor/", "modules_critic/", "modules_critic/"};   // (two trained modules: the critic's range twice)
-            const char* const* mods = rebrac ? rmods : ifql ? imods : fmods;
+            const char* smods[3] = {"modules_actor/", "modules_alpha/", "modules_critic/"};
+            const char* const* mods = sac ? smods : rebrac ? rmods : ifql ? imods : fmods;
             for (int m = 0; m < 3; ++m) {
                 int lo = 1 << 30, hi = -1;
                 for (const Leaf& lf : leaves)
@@ -777,6 +831,16 @@ struct fql_engine {
             for (const Layer& L : nets[ni].layers) {
                 // ReBRAC's mean_net: variance_scaling(actor_fc_scale, fan_avg, uniform) (utils/networks.py:9-11,117)
                 const double scale = (rebrac && ni == NET_BC && &L == &nets[ni].layers.back()) ? (double)rcfg.actor_fc_scale : 1.0;
+                if (sac && ni == NET_BC && &L == &nets[ni].layers.back()) {
+                    // SAC's mean_net and log_std_net: variance_scaling(actor_fc_scale, fan_avg, uniform), [H, act] each (utils/networks.py:9-11,111-113)
+                    const int ad = cfg.act_dim, ap = pad16(ad);
+                    const double lim = std::sqrt(6.0 * (double)scfg.actor_fc_scale / (double)(L.in + ad));
+                    std::uniform_real_distribution<double> U(-lim, lim);
+                    for (int c0 : {0, ap})
+                        for (int r = 0; r < L.in; ++r)
+                            for (int c = 0; c < ad; ++c) h[L.w + (size_t)r * L.out_p + c0 + c] = (float)U(gen);
+                    continue;
+                }
                 const double lim = std::sqrt(6.0 * scale / (double)(L.in + L.out));
                 std::uniform_real_distribution<double> U(-lim, lim);
                 for (int r = 0; r < L.in; ++r)
@@ -2033,6 +2097,25 @@ struct fql_engine {
                                    FinalizeArgs{d_state, d_chunks, d_partials, d_leaf_range, n_chunks, n_train_leaves, L.op.fin_mode & 1, tl},
                                    (L.op.fin_mode >> 1) & 1);
                 break;
+            case OP_SAC_PREP:
+                FQL_LAUNCH(fql_sac_prep_kernel, dim3((L.op.sprep.B + 3) / 4), dim3(FQL_THREADS), 0, s, L.op.sprep);
+                break;
+            case OP_SAC_ACT:
+                FQL_LAUNCH(fql_sac_act_kernel, dim3((L.op.sact.n + FQL_THREADS - 1) / FQL_THREADS), dim3(FQL_THREADS), 0, s, L.op.sact);
+                break;
+            case OP_SAC_LOSS_C:
+                FQL_LAUNCH(fql_sac_loss_critic_kernel, dim3(1), dim3(FQL_THREADS), 0, s, L.op.sc);
+                break;
+            case OP_SAC_LOSS_A:
+                FQL_LAUNCH(fql_sac_loss_actor_kernel, dim3(1), dim3(FQL_THREADS), 0, s, L.op.sa);
+                break;
+            case OP_SAC_AGRAD:
+                FQL_LAUNCH(fql_sac_actor_grad_kernel, dim3((L.op.sag.B * L.op.sag.ad + FQL_THREADS - 1) / FQL_THREADS), dim3(FQL_THREADS), 0, s, L.op.sag);
+                break;
+            case OP_SAC_FIN:
+                FQL_LAUNCH(fql_sac_finalize_kernel, dim3(1), dim3(FQL_THREADS), 0, s,
+                                   FinalizeArgs{d_state, d_chunks, d_partials, d_leaf_range, n_chunks, n_train_leaves, L.op.fin_mode & 1, tl});
+                break;
             case OP_WGRAD: case OP_LNBWD: case OP_POSTOS: case OP_LOSS_CRITIC: case OP_LOSS_Q: case OP_LOSS_BC:   // (inside OP_GEMM64 launches)
             case OP_PEC: case OP_XCHAIN: case OP_NUM_TYPES:
                 throw HipError{"internal: op type " + std::to_string((int)L.type) + " has no launch of its own"};
@@ -2827,6 +2910,131 @@ struct fql_engine {
         split_ok = false;
         src_valid = false;
     }
+    // ---------------------------------------------------------------------------------------
+    // the SAC update as a program (agents/sac.py:23-122).  No Euler chain: throughput work on the side lanes.
+    //   lane 0: batch assembly (+ eps_c, eps_n); Adam over every chunk (Polyak of the critic) and the finalize, behind both side lanes
+    //   lane 1: actor over [obs ; next_obs] -> sample + log-prob (a' into the target pair's input, a into [obs | a]) -> critic pair on
+    //           [obs | a] -> actor / temperature loss -> the pair's input gradient -> dL/d(heads) -> actor backward (obs rows)
+    //   lane 2: critic pair forward -> target pair forward (waits for a' on lane 1) -> critic loss -> critic backward (parameter gradients)
+    // Edges between the forked lanes run 1 -> 2 only (see schedule()).  with_grads = false: the loss probe (no backward, no finalize).
+    // ---------------------------------------------------------------------------------------
+    void build_sac_program(Program& pr, bool with_grads) {
+        const int od = cfg.obs_dim, ad = cfg.act_dim, ap = pad16(ad);
+        const int inp_a = nets[NET_BC].in_p(), inp_c = nets[NET_C0].in_p();
+        DevState* st = d_state;
+        const void *I_C = &st->info[SAC_I_CRITIC], *I_A = &st->info[SAC_I_ACTOR], *I_Q = &st->info[SAC_I_Q];
+        const float* la = P + alpha_off;
+        wide_tiles = true;
+        allow64 = true;
+        emit_lane = 0;
+        {
+            Op op{};
+            op.type = OP_SAC_PREP;
+            op.sprep = SacPrepArgs{d_src, st, seed, B, od, ad, inp_a, inp_c, ap, X_c1, X_t, X_q, X_a, w_eps, w_rew, w_mask};
+            op.writes = {X_c1, X_t, X_q, X_a, w_eps, w_rew, w_mask};
+            push(pr, op);
+        }
+        emit_lane = 1;
+        emit_forward(pr, p_a, with_grads);   // actor(obs), actor(next_obs)  sac.py:26,61
+        {
+            Op op{};
+            op.type = OP_SAC_ACT;   // a, lp (obs rows) and a', lp' (next rows)  sac.py:27,62
+            op.sact = SacActArgs{p_a.out, w_eps, X_q, X_t, lp_buf, 0, 0, 2 * B, ad, ap, ap, inp_c, od, 0, B, 1, scfg.tanh_squash, 0, 1.0f};
+            op.reads = {p_a.out, w_eps};
+            op.writes = {X_q, X_t, lp_buf};
+            push(pr, op);
+        }
+        for (int e = 0; e < 2; ++e) emit_forward(pr, p_q[e], with_grads);   // critic(obs, a), stored params  sac.py:65
+        {
+            Op op{};
+            op.type = OP_SAC_LOSS_A;
+            op.sa = SacActorArgs{p_q[0].out, p_q[1].out, lp_buf, p_a.out, la, with_grads ? G + alpha_off : nullptr,
+                                 with_grads ? p_q[0].dz.back() : nullptr, with_grads ? p_q[1].dz.back() : nullptr, st, B, ad, ap, target_entropy};
+            op.reads = {p_q[0].out, p_q[1].out, lp_buf, p_a.out, la};
+            op.writes = {I_A, I_Q};
+            if (with_grads) { op.writes.push_back(G + alpha_off); op.writes.push_back(p_q[0].dz.back()); op.writes.push_back(p_q[1].dz.back()); }
+            push(pr, op);
+        }
+        if (with_grads) {
+            for (int e = 0; e < 2; ++e) emit_backward(pr, p_q[e], 0, B, false, true);   // dQ/da only: the critic's params get no gradient
+            Op op{};
+            op.type = OP_SAC_AGRAD;
+            op.sag = SacActorGradArgs{p_q[0].dx0, p_q[1].dx0, X_q, p_a.out, w_eps, la, p_a.dz.back(), B, od, ad, inp_c, ap, scfg.tanh_squash};
+            op.reads = {p_q[0].dx0, p_q[1].dx0, X_q, p_a.out, w_eps, la};
+            op.writes = {p_a.dz.back()};
+            push(pr, op);
+            emit_backward(pr, p_a, 0, B, true, false);
+        }
+        emit_lane = 2;
+        for (int e = 0; e < 2; ++e) emit_forward(pr, p_c1[e], with_grads);   // critic(obs, actions)  sac.py:46
+        for (int e = 0; e < 2; ++e) emit_forward(pr, p_ct[e], false);         // target_critic(next_obs, a')  sac.py:30
+        {
+            Op op{};
+            op.type = OP_SAC_LOSS_C;
+            op.sc = SacCriticArgs{p_c1[0].out, p_c1[1].out, p_ct[0].out, p_ct[1].out, lp_buf + B, w_rew, w_mask, la,
+                                  with_grads ? p_c1[0].dz.back() : nullptr, with_grads ? p_c1[1].dz.back() : nullptr, st, B,
+                                  cfg.q_agg == 1 ? 1 : 0, scfg.backup_entropy ? 1 : 0, cfg.discount};
+            op.reads = {p_c1[0].out, p_c1[1].out, p_ct[0].out, p_ct[1].out, lp_buf, w_rew, w_mask, la};
+            op.writes = {I_C};
+            if (with_grads) { op.writes.push_back(p_c1[0].dz.back()); op.writes.push_back(p_c1[1].dz.back()); }
+            push(pr, op);
+        }
+        if (!with_grads) return;
+        for (int e = 0; e < 2; ++e) emit_backward(pr, p_c1[e], 0, B, true, false);
+        // every chunk in one launch (log_value's too); Polyak of the target critic from the pre-step critic (sac.py:113)
+        adam_for(pr, 0, {NET_C0, NET_C1, NET_BC}, 0, -2);
+        Op& a = pr.ops.back();
+        a.reads.push_back(G + alpha_off);
+        a.writes.push_back(P + alpha_off);
+        Op f{};
+        f.type = OP_SAC_FIN;
+        f.fin_mode = 1;
+        f.reads = {I_C, I_A, I_Q};
+        for (int m = 0; m < 3; ++m) f.reads.push_back(d_partials + mod_chunk0[m] * 4);
+        f.writes = {&st->info[10], st};
+        emit_lane = 0;
+        push(pr, f);
+    }
+
+    void build_sac_workspace() {
+        const int ap = pad16(cfg.act_dim);
+        const int inp_a = nets[NET_BC].in_p(), inp_c = nets[NET_C0].in_p();
+        auto& W = ws_allocs;
+        X_c1 = dalloc(W, (size_t)B * inp_c); X_t = dalloc(W, (size_t)B * inp_c); X_q = dalloc(W, (size_t)B * inp_c);
+        X_a = dalloc(W, (size_t)2 * B * inp_a);
+        w_eps = dalloc(W, (size_t)2 * B * ap); lp_buf = dalloc(W, (size_t)2 * B);
+        w_rew = dalloc(W, B); w_mask = dalloc(W, B);
+        X_os = X_bc = X_eu = X_c2 = X_ct = X_e0 = C0 = Vpart = vel = tgt = X_v = X_ta = w_act = nullptr;
+        fused_euler = euler_finish_fused = false;
+        p_a = make_pass(W, NET_BC, 2 * B, X_a, true, false);
+        for (int e = 0; e < 2; ++e) {
+            p_c1[e] = make_pass(W, NET_C0 + e, B, X_c1, true, false);
+            p_ct[e] = make_pass(W, NET_T0 + e, B, X_t, false, false);
+            p_q[e] = make_pass(W, NET_C0 + e, B, X_q, true, true);
+        }
+        build_sac_program(prog_full, true);
+        build_sac_program(prog_loss, false);
+        for (Program* pr : {&prog_full, &prog_loss}) schedule(*pr, W);
+        for (Program* pr : {&prog_full, &prog_loss}) capture(*pr);
+        split_ok = false;
+        src_valid = false;
+    }
+    // multiply-accumulates of one SAC update per batch row, algorithmic (full GEMM shapes at the logical widths; the heads are H x 2 act)
+    int64_t sac_macs() const {
+        auto macs = [&](const Net& n) {
+            int64_t m = 0;
+            for (const Layer& L : n.layers) m += (int64_t)L.in * (&L == &n.layers.back() && &n == &nets[NET_BC] ? 2 * cfg.act_dim : L.out);
+            return m;
+        };
+        auto first = [&](const Net& n) { return (int64_t)n.layers[0].in * n.layers[0].out; };
+        const int64_t ac = macs(nets[NET_BC]), cr = macs(nets[NET_C0]);
+        // actor on 2B rows; target pair; critic pair forward + backward without the input gradient
+        int64_t m = 2 * ac + 2 * cr + 2 * cr + 2 * (2 * cr - first(nets[NET_C0]));
+        // the pair on [obs | a] forward + input gradient; actor backward on the obs rows without the input gradient
+        m += 2 * cr + 2 * cr + (2 * ac - first(nets[NET_BC]));
+        return m * (int64_t)B;
+    }
+
     // multiply-accumulates of one ReBRAC update per batch row, algorithmic (full GEMM shapes)
     int64_t rebrac_macs(bool full_update) const {
         auto macs = [&](const Net& n) { int64_t m = 0; for (const Layer& L : n.layers) m += (int64_t)L.in * L.out; return m; };
@@ -2843,6 +3051,7 @@ struct fql_engine {
         auto macs = [&](const Net& n) { int64_t m = 0; for (const Layer& L : n.layers) m += (int64_t)L.in * L.out; return m; };
         auto first = [&](const Net& n) { return (int64_t)n.layers[0].in * n.layers[0].out; };
         if (rebrac) return rebrac_macs(true);
+        if (sac) return sac_macs();
         const int64_t os = macs(nets[NET_OS]), bc = macs(nets[NET_BC]), cr = macs(nets[NET_C0]);
         if (ifql) {   // value on 2B rows + its backward on B; target pair; critic pair forward + backward (no input gradient); actor_flow forward + backward
             const int64_t fwd = 2 * os + 4 * cr + bc;
@@ -2898,6 +3107,7 @@ struct fql_engine {
         in_idx = (int64_t*)dalloc(W, (size_t)B * 4);   // [2][B]: indices in use, staging of host indices (frames path)
         if (ifql) { build_ifql_workspace(); return; }
         if (rebrac) { in_nact = dalloc(W, (size_t)B * ad); build_rebrac_workspace(); return; }
+        if (sac) { build_sac_workspace(); return; }
         const int inp_c = nets[NET_OS].in_p(), inp_b = nets[NET_BC].in_p();
         X_os = dalloc(W, (size_t)3 * B * inp_c); X_bc = dalloc(W, (size_t)B * inp_b); X_eu = dalloc(W, (size_t)B * inp_b);
         X_c1 = dalloc(W, (size_t)B * inp_c); X_c2 = dalloc(W, (size_t)B * inp_c); X_ct = dalloc(W, (size_t)B * inp_c);
@@ -3038,6 +3248,7 @@ struct fql_engine {
         if (!nz) return;
         if (ifql && (nz->eps1 || nz->z || nz->eps2)) invalid("IFQL reads only x0 and t of fql_noise (eps1, z and eps2 must be NULL)");
         if (rebrac && (nz->x0 || nz->t || nz->z || nz->eps2)) invalid("ReBRAC reads only eps1 of fql_noise (x0, t, z and eps2 must be NULL)");
+        if (sac && (nz->x0 || nz->t || nz->z)) invalid("SAC reads only eps1 and eps2 of fql_noise (x0, t and z must be NULL)");
         d.eps1 = stage(nz->eps1, in_noise[0], (size_t)B * ad, s);
         d.x0 = stage(nz->x0, in_noise[1], (size_t)B * ad, s);
         d.t = stage(nz->t, in_noise[2], B, s);
@@ -3165,7 +3376,7 @@ struct fql_engine {
         ev->n_pad = n_pad;
         auto& W = ev->allocs;
         const int od = cfg.obs_dim, ad = cfg.act_dim;
-        if (rebrac) {   // sample_actions: the actor's forward over the rows (prog_os on p_os; NET_OS is empty here)
+        if (rebrac || sac) {   // sample_actions: the actor's forward over the rows (prog_os on p_os; NET_OS is empty here)
             ev->X = dalloc(W, (size_t)n_pad * nets[NET_BC].in_p());
             ev->st_obs = dalloc(W, (size_t)n_pad * od);
             ev->st_noise = dalloc(W, (size_t)n_pad * ad);
@@ -3288,6 +3499,37 @@ struct fql_engine {
             }
         }
     }
+    // SAC sample_actions (agents/sac.py:125-136): clip(tanh(mean + exp(ls) temperature eps), -1, 1) (no tanh without tanh_squash).
+    // noise: [n, act] raw N(0, 1) or null (Philox keyed by (seed, sd), row numbers of the call: chunking does not change the draw)
+    void sac_sample(const float* obs, const float* noise, uint64_t sd, float temperature, int n, float* out, hipStream_t s, bool own_stream) {
+        if (n <= 0) invalid("n must be positive (got %d)", n);
+        if (!obs || !out) invalid("observations/out must not be NULL");
+        if (!(temperature >= 0.0f)) invalid("temperature must be >= 0");
+        const int od = cfg.obs_dim, ad = cfg.act_dim, ap = pad16(ad);
+        for (int start = 0; start < n; start += 4096) {
+            const int m = std::min(4096, n - start);
+            Eval& ev = get_eval(pad16(m));
+            const float* o = stage(obs + (size_t)start * od, ev.st_obs, (size_t)m * od, s);
+            const float* z = noise ? stage(noise + (size_t)start * ad, ev.st_noise, (size_t)m * ad, s) : nullptr;
+            drain_staging(s);
+            AssembleArgs aa{o, nullptr, ev.X, seed, sd, m, ev.n_pad, od, 0, nets[NET_BC].in_p()};   // [obs | 0]
+            hipLaunchKernelGGL(fql_assemble_kernel, dim3((ev.n_pad + 3) / 4), dim3(FQL_THREADS), 0, s, aa);
+            run_launches(ev.prog_os, s);
+            float* dst = out + (size_t)start * ad;
+            const bool dev_out = is_device_ptr(dst);
+            float* o_rows = dev_out ? dst : ev.st_out;
+            SacActArgs sa{ev.p_os.out, z, o_rows, o_rows, nullptr, seed, sd, m, ad, ap, ad, ad, 0, start, m, z ? 1 : 2, scfg.tanh_squash, 1,
+                          temperature};
+            hipLaunchKernelGGL(fql_sac_act_kernel, dim3((m + FQL_THREADS - 1) / FQL_THREADS), dim3(FQL_THREADS), 0, s, sa);
+            HIP_CHECK(hipGetLastError());
+            if (!dev_out) {
+                HIP_CHECK(hipMemcpyAsync(dst, ev.st_out, (size_t)m * ad * sizeof(float), hipMemcpyDeviceToHost, s));
+                HIP_CHECK(hipStreamSynchronize(s));
+            } else if (own_stream) {
+                HIP_CHECK(hipStreamSynchronize(s));
+            }
+        }
+    }
     // ReBRAC batch sources: the FQL ones plus next_actions (explicit [B, act], or the dataset's actions one row on)
     void rebrac_source_from_batch(const float* obs, const float* act, const float* rew, const float* mask, const float* nobs, const float* nact,
                                   int batch, const fql_noise* nz, int advance, hipStream_t s) {
@@ -3373,6 +3615,10 @@ struct fql_engine {
         if ((h) && (h)->ifql) { (h)->err = what " is not available on an IFQL handle"; return FQL_E_STATE; } \
         if ((h) && (h)->rebrac) { (h)->err = what " is not available on a ReBRAC handle"; return FQL_E_STATE; } \
     } while (0)
+#define FQL_SAC_REFUSES(h, what)                                                                          \
+    do {                                                                                                \
+        if ((h) && (h)->sac) { (h)->err = what " is not available on a SAC handle"; return FQL_E_STATE; } \
+    } while (0)
 #define FQL_REBRAC_REFUSES(h, what, why)                                                                                  \
     do {                                                                                                               \
         if ((h) && (h)->rebrac) { (h)->err = what " is not available on a ReBRAC handle (" why ")"; return FQL_E_STATE; } \
@@ -3456,8 +3702,9 @@ void fql_default_config(fql_config* c) {
 
 const char* fql_last_error(fql_handle h) { return h ? h->err.c_str() : g_create_error.c_str(); }
 
-static int create_engine(const fql_config* cfg, const fql_ifql_config* icfg, const fql_rebrac_config* rcfg, uint64_t seed, fql_handle* out);
-int fql_create(const fql_config* cfg, uint64_t seed, fql_handle* out) { return create_engine(cfg, nullptr, nullptr, seed, out); }
+static int create_engine(const fql_config* cfg, const fql_ifql_config* icfg, const fql_rebrac_config* rcfg, const fql_sac_config* scfg,
+                         uint64_t seed, fql_handle* out);
+int fql_create(const fql_config* cfg, uint64_t seed, fql_handle* out) { return create_engine(cfg, nullptr, nullptr, nullptr, seed, out); }
 
 void fql_ifql_default_config(fql_ifql_config* c) {   // agents/ifql.py:231-250
     std::memset(c, 0, sizeof *c);
@@ -3466,7 +3713,7 @@ void fql_ifql_default_config(fql_ifql_config* c) {   // agents/ifql.py:231-250
 }
 int fql_ifql_create(const fql_config* cfg, const fql_ifql_config* icfg, uint64_t seed, fql_handle* out) {
     if (!icfg) { g_create_error = "icfg must not be NULL"; if (out) *out = nullptr; return FQL_E_INVALID; }
-    return create_engine(cfg, icfg, nullptr, seed, out);
+    return create_engine(cfg, icfg, nullptr, nullptr, seed, out);
 }
 void fql_rebrac_default_config(fql_rebrac_config* c) {   // agents/rebrac.py:222-244
     std::memset(c, 0, sizeof *c);
@@ -3479,7 +3726,7 @@ void fql_rebrac_default_config(fql_rebrac_config* c) {   // agents/rebrac.py:222
 }
 int fql_rebrac_create(const fql_config* cfg, const fql_rebrac_config* rcfg, uint64_t seed, fql_handle* out) {
     if (!rcfg) { g_create_error = "rcfg must not be NULL"; if (out) *out = nullptr; return FQL_E_INVALID; }
-    return create_engine(cfg, nullptr, rcfg, seed, out);
+    return create_engine(cfg, nullptr, rcfg, nullptr, seed, out);
 }
 static const char* k_rebrac_info_names[FQL_REBRAC_NUM_INFO] = {
     "critic/critic_loss", "critic/q_mean", "critic/q_max", "critic/q_min", "actor/total_loss", "actor/actor_loss", "actor/bc_loss",
@@ -3487,13 +3734,32 @@ static const char* k_rebrac_info_names[FQL_REBRAC_NUM_INFO] = {
 static const char* k_ifql_info_names[FQL_IFQL_NUM_INFO] = {
     "value/value_loss", "value/v_mean", "value/v_max", "value/v_min", "critic/critic_loss", "critic/q_mean", "critic/q_max",
     "critic/q_min", "actor/actor_loss", "grad/max", "grad/min", "grad/norm"};
-int fql_num_info(fql_handle h) { return !h ? FQL_E_INVALID : h->ifql ? FQL_IFQL_NUM_INFO : h->rebrac ? FQL_REBRAC_NUM_INFO : FQL_NUM_INFO; }
+void fql_sac_default_config(fql_sac_config* c) {   // agents/sac.py get_config
+    std::memset(c, 0, sizeof *c);
+    c->target_entropy = NAN;
+    c->target_entropy_multiplier = 0.5f;
+    c->tanh_squash = 1;
+    c->state_dependent_std = 1;
+    c->actor_fc_scale = 0.01f;
+    c->backup_entropy = 0;
+}
+int fql_sac_create(const fql_config* cfg, const fql_sac_config* scfg, uint64_t seed, fql_handle* out) {
+    if (!scfg) { g_create_error = "scfg must not be NULL"; if (out) *out = nullptr; return FQL_E_INVALID; }
+    return create_engine(cfg, nullptr, nullptr, scfg, seed, out);
+}
+static const char* k_sac_info_names[FQL_SAC_NUM_INFO] = {
+    "critic/critic_loss", "critic/q_mean", "critic/q_max", "critic/q_min", "actor/total_loss", "actor/actor_loss", "actor/alpha_loss",
+    "actor/alpha", "actor/entropy", "actor/std", "actor/q", "grad/max", "grad/min", "grad/norm"};
+int fql_num_info(fql_handle h) {
+    return !h ? FQL_E_INVALID : h->ifql ? FQL_IFQL_NUM_INFO : h->rebrac ? FQL_REBRAC_NUM_INFO : h->sac ? FQL_SAC_NUM_INFO : FQL_NUM_INFO;
+}
 const char* fql_handle_info_name(fql_handle h, int i) {
     if (!h || i < 0 || i >= fql_num_info(h)) return nullptr;
-    return h->ifql ? k_ifql_info_names[i] : h->rebrac ? k_rebrac_info_names[i] : k_info_names[i];
+    return h->ifql ? k_ifql_info_names[i] : h->rebrac ? k_rebrac_info_names[i] : h->sac ? k_sac_info_names[i] : k_info_names[i];
 }
 
-static int create_engine(const fql_config* cfg, const fql_ifql_config* icfg, const fql_rebrac_config* rcfg, uint64_t seed, fql_handle* out) {
+static int create_engine(const fql_config* cfg, const fql_ifql_config* icfg, const fql_rebrac_config* rcfg, const fql_sac_config* scfg,
+                         uint64_t seed, fql_handle* out) {
     if (!cfg || !out) { g_create_error = "cfg/out must not be NULL"; return FQL_E_INVALID; }
     *out = nullptr;
     if (icfg) {   // IFQL: state observations and fp32 only
@@ -3510,6 +3776,15 @@ static int create_engine(const fql_config* cfg, const fql_ifql_config* icfg, con
         if (!std::isfinite(rcfg->alpha_actor) || !std::isfinite(rcfg->alpha_critic)) { g_create_error = "fql_rebrac_create: alpha_actor and alpha_critic must be finite"; return FQL_E_INVALID; }
         if (rcfg->tanh_squash != 0 && rcfg->tanh_squash != 1) { g_create_error = "fql_rebrac_create: tanh_squash must be 0 or 1"; return FQL_E_INVALID; }
     }
+    if (scfg) {   // SAC: state observations and fp32 only
+        if (cfg->encoder != 0) { g_create_error = "fql_sac_create: visual encoders are not available for SAC (encoder must be 0)"; return FQL_E_INVALID; }
+        if (cfg->precision != 0) { g_create_error = "fql_sac_create: SAC runs in fp32 only (precision must be 0)"; return FQL_E_INVALID; }
+        if (scfg->state_dependent_std != 1) { g_create_error = "fql_sac_create: only state_dependent_std = 1 is available (the const_std=False vector form is not)"; return FQL_E_INVALID; }
+        if (scfg->tanh_squash != 0 && scfg->tanh_squash != 1) { g_create_error = "fql_sac_create: tanh_squash must be 0 or 1"; return FQL_E_INVALID; }
+        if (!(scfg->actor_fc_scale > 0.0f)) { g_create_error = "fql_sac_create: actor_fc_scale must be > 0"; return FQL_E_INVALID; }
+        if (!std::isnan(scfg->target_entropy) && !std::isfinite(scfg->target_entropy)) { g_create_error = "fql_sac_create: target_entropy must be finite or NaN (automatic)"; return FQL_E_INVALID; }
+        if (std::isnan(scfg->target_entropy) && !std::isfinite(scfg->target_entropy_multiplier)) { g_create_error = "fql_sac_create: target_entropy_multiplier must be finite"; return FQL_E_INVALID; }
+    }
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
         (void)hipGetLastError();
@@ -3522,6 +3797,10 @@ static int create_engine(const fql_config* cfg, const fql_ifql_config* icfg, con
         h->seed = seed;
         if (icfg) { h->ifql = true; h->expectile = icfg->expectile; h->num_samples = icfg->num_samples; }
         if (rcfg) { h->rebrac = true; h->rcfg = *rcfg; }
+        if (scfg) {   // sac.py create: target_entropy = -target_entropy_multiplier * action_dim when None
+            h->sac = true; h->scfg = *scfg;
+            h->target_entropy = std::isnan(scfg->target_entropy) ? -scfg->target_entropy_multiplier * (float)cfg->act_dim : scfg->target_entropy;
+        }
         if (cfg->encoder != 0) {   // visual agent (agents/fql.py:196-202): the MLPs see the 512-wide encoding instead of obs
             if (cfg->encoder != 1 && cfg->encoder != 2) invalid("encoder %d not available (0 = none, 1 = impala_small, 2 = impala)", cfg->encoder);
             if (cfg->img_h <= 0 || cfg->img_w <= 0 || cfg->img_h % 32 || cfg->img_w % 32 || cfg->img_w > 128 || cfg->img_c <= 0 || cfg->img_c > 16)
@@ -3739,6 +4018,7 @@ static void run_update(fql_handle h, Program& pr, hipStream_t s, bool own_stream
 int fql_update_begin(fql_handle h, const float* obs, const float* act, const float* rew, const float* mask,
                      const float* nobs, int batch_size, const fql_noise* noise, void* stream) {
     FQL_IFQL_REFUSES(h, "fql_update_begin");
+    FQL_SAC_REFUSES(h, "fql_update_begin");
     if (!h) return FQL_E_INVALID;
     FQL_TRY(h, {
         hipStream_t s = pick(h, stream);
@@ -3750,6 +4030,7 @@ int fql_update_begin(fql_handle h, const float* obs, const float* act, const flo
 }
 int fql_update_end(fql_handle h, float* info13, void* stream) {
     FQL_IFQL_REFUSES(h, "fql_update_end");
+    FQL_SAC_REFUSES(h, "fql_update_end");
     if (!h) return FQL_E_INVALID;
     if (!h->began) { h->err = "fql_update_end without fql_update_begin"; return FQL_E_STATE; }
     FQL_TRY(h, {
@@ -3762,6 +4043,7 @@ int fql_update_end(fql_handle h, float* info13, void* stream) {
 int fql_update(fql_handle h, const float* obs, const float* act, const float* rew, const float* mask, const float* nobs,
                int batch_size, const fql_noise* noise, float* info13, void* stream) {
     FQL_REBRAC_REFUSES(h, "fql_update", "its batch has no next_actions: fql_rebrac_update");
+    FQL_SAC_REFUSES(h, "fql_update");
     if (h && !h->began) {
         FQL_TRY_FAST(h, {
             hipStream_t s = pick(h, stream);
@@ -3799,6 +4081,7 @@ int fql_set_rng_stream(fql_handle h, uint64_t stream_id) {
 int fql_total_loss(fql_handle h, const float* obs, const float* act, const float* rew, const float* mask, const float* nobs,
                    int batch_size, const fql_noise* noise, float* loss, float* info10, void* stream) {
     FQL_REBRAC_REFUSES(h, "fql_total_loss", "its batch has no next_actions: fql_rebrac_total_loss");
+    FQL_SAC_REFUSES(h, "fql_total_loss");
     if (!h) return FQL_E_INVALID;
     FQL_TRY(h, {
         hipStream_t s = pick(h, stream);
@@ -3820,11 +4103,13 @@ int fql_total_loss(fql_handle h, const float* obs, const float* act, const float
 int fql_sample_actions(fql_handle h, const float* obs, int n, const float* noise, uint64_t seed, float* out, void* stream) {
     if (!h) return FQL_E_INVALID;
     if (h->rebrac) FQL_TRY(h, h->rebrac_sample(obs, noise, seed, 1.0f, n, out, pick(h, stream), stream == nullptr));
+    if (h->sac) FQL_TRY(h, h->sac_sample(obs, noise, seed, 1.0f, n, out, pick(h, stream), stream == nullptr));
     if (h->ifql) FQL_TRY(h, h->ifql_sample(obs, noise, seed, n, out, pick(h, stream), stream == nullptr));
     FQL_TRY(h, h->eval_rows(false, obs, noise, seed, n, out, pick(h, stream), stream == nullptr));
 }
 int fql_flow_actions(fql_handle h, const float* obs, const float* noises, int n, float* out, void* stream) {
     FQL_REBRAC_REFUSES(h, "fql_flow_actions", "the actor is deterministic, there is no flow");
+    FQL_SAC_REFUSES(h, "fql_flow_actions");
     if (!h) return FQL_E_INVALID;
     FQL_TRY(h, h->eval_rows(true, obs, noises, 0, n, out, pick(h, stream), stream == nullptr));
 }
@@ -3881,6 +4166,7 @@ int fql_dataset_size(fql_handle h, int64_t* size, int64_t* pointer) {
 // ---- online fine-tuning: ring capacity, uint8 ring insert, the replay ring of balanced sampling (helpers above extern "C")
 int fql_noise_from_jax_keys(fql_handle h, const uint32_t* keys10, int partitionable, int batch_size, fql_noise* out, void* stream) {
     FQL_IFQL_REFUSES(h, "fql_noise_from_jax_keys");
+    FQL_SAC_REFUSES(h, "fql_noise_from_jax_keys");
     if (!h || !keys10 || !out) return FQL_E_INVALID;
     FQL_TRY(h, {
         if (batch_size != h->B) invalid("batch_size %d does not match the engine's workspace (%d); call fql_set_batch_size", batch_size, h->B);
@@ -3932,6 +4218,7 @@ int fql_dataset_reserve(fql_handle h, int64_t capacity) {
 }
 int fql_dataset_add_frames(fql_handle h, const uint8_t* frame, const uint8_t* next_frame, const float* ac, float reward, float mask) {
     FQL_IFQL_REFUSES(h, "fql_dataset_add_frames");
+    FQL_SAC_REFUSES(h, "fql_dataset_add_frames");
     if (!h) return FQL_E_INVALID;
     FQL_TRY(h, {
         if (!h->visual || !h->ds_frames) throw Invalid{"no frames dataset allocated (fql_dataset_upload_frames)"};
@@ -3975,6 +4262,7 @@ int fql_replay_add(fql_handle h, const float* ob, const float* ac, float reward,
 }
 int fql_replay_add_frames(fql_handle h, const uint8_t* frame, const uint8_t* next_frame, const float* ac, float reward, float mask) {
     FQL_IFQL_REFUSES(h, "fql_replay_add_frames");
+    FQL_SAC_REFUSES(h, "fql_replay_add_frames");
     if (!h) return FQL_E_INVALID;
     FQL_TRY(h, {
         if (h->rb_cap <= 0 || !h->visual) throw Invalid{"fql_replay_add_frames: no frames replay ring (fql_replay_create on a frames agent)"};
@@ -3995,6 +4283,7 @@ int fql_replay_size(fql_handle h, int64_t* size, int64_t* pointer) {
 int fql_update_balanced(fql_handle h, const int64_t* idx_dataset, const int64_t* idx_replay, const int32_t* crop_froms, int batch_size,
                         const fql_noise* noise, float* info13, void* stream) {
     FQL_IFQL_REFUSES(h, "fql_update_balanced");
+    FQL_SAC_REFUSES(h, "fql_update_balanced");
     if (!h) return FQL_E_INVALID;
     if (h->began) { h->err = "fql_update_balanced between fql_update_begin and fql_update_end"; return FQL_E_STATE; }
     FQL_TRY_FAST(h, {
@@ -4009,6 +4298,7 @@ int fql_update_balanced(fql_handle h, const int64_t* idx_dataset, const int64_t*
 int fql_update_from_dataset_begin(fql_handle h, const int64_t* idx, int batch_size, int64_t lo, int64_t hi,
                                   const fql_noise* noise, void* stream) {
     FQL_IFQL_REFUSES(h, "fql_update_from_dataset_begin");
+    FQL_SAC_REFUSES(h, "fql_update_from_dataset_begin");
     if (!h) return FQL_E_INVALID;
     FQL_TRY(h, {
         hipStream_t s = pick(h, stream);
@@ -4021,6 +4311,7 @@ int fql_update_from_dataset_begin(fql_handle h, const int64_t* idx, int batch_si
 int fql_update_from_dataset_begin_split(fql_handle h, const int64_t* idx, int batch_size, int64_t lo, int64_t hi,
                                         const fql_noise* noise, void* stream0, void* stream1) {
     FQL_IFQL_REFUSES(h, "fql_update_from_dataset_begin_split");
+    FQL_SAC_REFUSES(h, "fql_update_from_dataset_begin_split");
     if (!h) return FQL_E_INVALID;
     if (!h->split_ok || !stream0 || !stream1 || stream0 == stream1) { h->err = "split update unavailable (needs two distinct streams and a two-lane program)"; return FQL_E_STATE; }
     FQL_TRY(h, {
@@ -4032,6 +4323,7 @@ int fql_update_from_dataset_begin_split(fql_handle h, const int64_t* idx, int ba
 int fql_update_begin_split(fql_handle h, const float* obs, const float* act, const float* rew, const float* mask, const float* nobs,
                            int batch_size, const fql_noise* noise, void* stream0, void* stream1) {
     FQL_IFQL_REFUSES(h, "fql_update_begin_split");
+    FQL_SAC_REFUSES(h, "fql_update_begin_split");
     if (!h) return FQL_E_INVALID;
     if (!h->split_ok || !stream0 || !stream1 || stream0 == stream1) { h->err = "split update unavailable (needs two distinct streams and a two-lane program)"; return FQL_E_STATE; }
     FQL_TRY(h, {
@@ -4042,6 +4334,7 @@ int fql_update_begin_split(fql_handle h, const float* obs, const float* act, con
 }
 int fql_update_end_split(fql_handle h, float* info13, void* stream0, void* stream1) {
     FQL_IFQL_REFUSES(h, "fql_update_end_split");
+    FQL_SAC_REFUSES(h, "fql_update_end_split");
     if (!h) return FQL_E_INVALID;
     if (!h->began) { h->err = "fql_update_end_split without fql_update_begin"; return FQL_E_STATE; }
     if (!stream0 || !stream1 || stream0 == stream1) { h->err = "fql_update_end_split needs two distinct streams"; return FQL_E_STATE; }
@@ -4053,6 +4346,7 @@ int fql_update_end_split(fql_handle h, float* info13, void* stream0, void* strea
 }
 int fql_grad_buckets(fql_handle h, size_t offsets[2], size_t lengths[2]) {
     FQL_IFQL_REFUSES(h, "fql_grad_buckets");
+    FQL_SAC_REFUSES(h, "fql_grad_buckets");
     if (!h || !offsets || !lengths) return FQL_E_INVALID;
     // bucket 0: both critic members + the BC flow actor (all produced on lane 1); bucket 1: the one-step actor (lane 0's tail)
     offsets[0] = 0; lengths[0] = h->nets[NET_OS].off;
@@ -4062,6 +4356,7 @@ int fql_grad_buckets(fql_handle h, size_t offsets[2], size_t lengths[2]) {
 int fql_update_from_dataset(fql_handle h, const int64_t* idx, int batch_size, int64_t lo, int64_t hi, const fql_noise* noise,
                             float* info13, void* stream) {
     FQL_REBRAC_REFUSES(h, "fql_update_from_dataset", "the step kind is an argument: fql_rebrac_update_from_dataset");
+    FQL_SAC_REFUSES(h, "fql_update_from_dataset");
     if (h && h->visual) return fql_update_from_frames(h, idx, nullptr, batch_size, lo, hi, noise, info13, stream);
     if (h && !h->began) {
         FQL_TRY_FAST(h, {
@@ -4082,19 +4377,30 @@ int fql_info_enqueue(fql_handle h, void* stream, uint64_t* ticket) {
         hipStream_t s = pick(h, stream);
         const uint64_t k = h->info_seq++;
         const int slot = (int)(k % fql_engine::kInfoRing);
-        HIP_CHECK(hipMemcpyAsync(h->h_info_ring[slot], &h->d_state->info[0], FQL_NUM_INFO * sizeof(float), hipMemcpyDeviceToHost, s));
+        HIP_CHECK(hipMemcpyAsync(h->h_info_ring[slot], &h->d_state->info[0], (h->sac ? FQL_SAC_NUM_INFO : FQL_NUM_INFO) * sizeof(float),
+                                 hipMemcpyDeviceToHost, s));
         HIP_CHECK(hipEventRecord(h->info_ev[slot], s));
         *ticket = k;
     });
 }
+static int info_wait(fql_handle h, uint64_t ticket, float* info13_host, int n);
 int fql_info_wait(fql_handle h, uint64_t ticket, float* info13_host) {
+    FQL_SAC_REFUSES(h, "fql_info_wait (14 infos: fql_info_wait_n)");
+    return info_wait(h, ticket, info13_host, FQL_NUM_INFO);
+}
+int fql_info_wait_n(fql_handle h, uint64_t ticket, float* out, int n) {
+    if (!h || !out) return FQL_E_INVALID;
+    if (n < fql_num_info(h)) { h->err = "fql_info_wait_n: the buffer holds fewer floats than fql_num_info(h)"; return FQL_E_INVALID; }
+    return info_wait(h, ticket, out, fql_num_info(h));   // exactly the handle's info count (12 on IFQL / ReBRAC handles)
+}
+static int info_wait(fql_handle h, uint64_t ticket, float* info13_host, int n) {
     if (!h || !info13_host) return FQL_E_INVALID;
     if (ticket >= h->info_seq) { h->err = "unknown info ticket"; return FQL_E_INVALID; }
     if (h->info_seq - ticket > (uint64_t)fql_engine::kInfoRing) { h->err = "info ticket expired (more than 64 later tickets were taken before it was read)"; return FQL_E_STATE; }
     FQL_TRY(h, {
         const int slot = (int)(ticket % fql_engine::kInfoRing);
         HIP_CHECK(hipEventSynchronize(h->info_ev[slot]));
-        std::memcpy(info13_host, h->h_info_ring[slot], FQL_NUM_INFO * sizeof(float));
+        std::memcpy(info13_host, h->h_info_ring[slot], n * sizeof(float));
     });
 }
 
@@ -4108,10 +4414,19 @@ int fql_synchronize(fql_handle h, int* mode) {
 }
 
 int fql_read_info(fql_handle h, float* info13_host) {
+    FQL_SAC_REFUSES(h, "fql_read_info (14 infos: fql_read_info_n)");
     if (!h || !info13_host) return FQL_E_INVALID;
     FQL_TRY(h, {
         HIP_CHECK(hipDeviceSynchronize());
         HIP_CHECK(hipMemcpy(info13_host, &h->d_state->info[0], FQL_NUM_INFO * sizeof(float), hipMemcpyDeviceToHost));
+    });
+}
+int fql_read_info_n(fql_handle h, float* out, int n) {
+    if (!h || !out) return FQL_E_INVALID;
+    if (n < fql_num_info(h)) { h->err = "fql_read_info_n: the buffer holds fewer floats than fql_num_info(h)"; return FQL_E_INVALID; }
+    FQL_TRY(h, {
+        HIP_CHECK(hipDeviceSynchronize());
+        HIP_CHECK(hipMemcpy(out, &h->d_state->info[0], (size_t)fql_num_info(h) * sizeof(float), hipMemcpyDeviceToHost));   // exactly fql_num_info(h)
     });
 }
 
@@ -4183,6 +4498,74 @@ int fql_rebrac_stats(fql_handle h, int full_update, int64_t* launches_per_update
     return FQL_OK;
 }
 
+// ---- SAC (agents/sac.py; RLPD = SAC online with balanced sampling) ----------------------------------------------------------------
+// One update through run_update (the AQL form and the graph are bitwise equal); 14 infos.
+#define FQL_SAC_ONLY(h, what)                                                                           \
+    do {                                                                                             \
+        if (!(h)) return FQL_E_INVALID;                                                              \
+        if (!(h)->sac) { (h)->err = what " needs a SAC handle (fql_sac_create)"; return FQL_E_STATE; } \
+    } while (0)
+int fql_sac_update(fql_handle h, const float* obs, const float* act, const float* rew, const float* masks, const float* next_obs,
+                   int batch_size, const fql_noise* noise, float* info14, void* stream) {
+    FQL_SAC_ONLY(h, "fql_sac_update");
+    FQL_TRY_FAST(h, {
+        hipStream_t s = pick(h, stream);
+        h->source_from_batch(obs, act, rew, masks, next_obs, batch_size, noise, 1, s);
+        run_update(h, h->prog_full, s, stream == nullptr);
+        h->finish_info(info14, FQL_SAC_NUM_INFO, s);
+    });
+}
+int fql_sac_update_from_dataset(fql_handle h, const int64_t* idx, int batch_size, int64_t lo, int64_t hi, const fql_noise* noise,
+                                float* info14, void* stream) {
+    FQL_SAC_ONLY(h, "fql_sac_update_from_dataset");
+    FQL_TRY_FAST(h, {
+        hipStream_t s = pick(h, stream);
+        h->source_from_dataset(idx, batch_size, lo, hi, noise, s);
+        run_update(h, h->prog_full, s, stream == nullptr);
+        h->finish_info(info14, FQL_SAC_NUM_INFO, s);
+    });
+}
+int fql_sac_update_balanced(fql_handle h, const int64_t* idx_dataset, const int64_t* idx_replay, int batch_size, const fql_noise* noise,
+                            float* info14, void* stream) {
+    FQL_SAC_ONLY(h, "fql_sac_update_balanced");
+    FQL_TRY_FAST(h, {
+        hipStream_t s = pick(h, stream);
+        h->source_balanced(idx_dataset, idx_replay, nullptr, batch_size, noise, s);
+        run_update(h, h->prog_full, s, stream == nullptr);
+        h->finish_info(info14, FQL_SAC_NUM_INFO, s);
+    });
+}
+int fql_sac_total_loss(fql_handle h, const float* obs, const float* act, const float* rew, const float* masks, const float* next_obs,
+                       int batch_size, const fql_noise* noise, float* loss, float* info11, void* stream) {
+    FQL_SAC_ONLY(h, "fql_sac_total_loss");
+    FQL_TRY(h, {
+        hipStream_t s = pick(h, stream);
+        h->source_from_batch(obs, act, rew, masks, next_obs, batch_size, noise, 0, s);
+        // the probe writes info slots 0-10 and 14: keep the last update's infos (fql_read_info_n after the probe still reads them)
+        float keep[16], tmp[SAC_I_Q + 1];
+        HIP_CHECK(hipMemcpyAsync(keep, &h->d_state->info[0], sizeof keep, hipMemcpyDeviceToHost, s));
+        run_program(h, h->prog_loss, s);
+        HIP_CHECK(hipMemcpyAsync(tmp, &h->d_state->info[0], sizeof tmp, hipMemcpyDeviceToHost, s));
+        HIP_CHECK(hipMemcpyAsync(&h->d_state->info[0], keep, sizeof keep, hipMemcpyHostToDevice, s));
+        HIP_CHECK(hipStreamSynchronize(s));
+        tmp[10] = tmp[SAC_I_Q];   // actor/q (scratch slot while no finalize runs)
+        // sac.py:94-112: loss = critic_loss + the actor's total_loss; infos 0-10
+        if (loss) *loss = tmp[0] + tmp[4];
+        if (info11) std::memcpy(info11, tmp, 11 * sizeof(float));
+    });
+}
+int fql_sac_sample_actions(fql_handle h, const float* obs, int n, const float* noise, uint64_t seed, float temperature, float* out,
+                           void* stream) {
+    FQL_SAC_ONLY(h, "fql_sac_sample_actions");
+    FQL_TRY(h, h->sac_sample(obs, noise, seed, temperature, n, out, pick(h, stream), stream == nullptr));
+}
+int fql_sac_stats(fql_handle h, int64_t* launches_per_update, int64_t* macs_per_update) {
+    FQL_SAC_ONLY(h, "fql_sac_stats");
+    if (launches_per_update) *launches_per_update = (int64_t)h->prog_full.launches.size();
+    if (macs_per_update) *macs_per_update = h->sac_macs();
+    return FQL_OK;
+}
+
 }  // extern "C"
 
 // Per-launch device times of ONE update, measured with HIP events on the engine's stream (used by bench.py for the per-kernel
@@ -4194,6 +4577,7 @@ int fql_rebrac_stats(fql_handle h, int full_update, int64_t* launches_per_update
 // in a rocprofv3 trace) to compare with rocprofv3's per-kernel durations.
 extern "C" int fql_profile_update(fql_handle h, int batch_size, int cap, int* type, int* lane, int* grid, float* us, double* macs, float* null_us) {
     FQL_REBRAC_REFUSES(h, "fql_profile_update", "FQL batch sources only");
+    FQL_SAC_REFUSES(h, "fql_profile_update");
     if (!h || !type || !us) return FQL_E_INVALID;
     try {
         require_graph(h->prog_full);
@@ -4230,6 +4614,7 @@ extern "C" int fql_profile_update(fql_handle h, int batch_size, int cap, int* ty
 // 9 X_eu [B, inp_b].  *dims receives {rows, row stride in elements}.
 extern "C" int fql_debug_workspace(fql_handle h, int which, void* out, size_t bytes, int* dims) {
     FQL_REBRAC_REFUSES(h, "fql_debug_workspace", "FQL workspaces only");
+    FQL_SAC_REFUSES(h, "fql_debug_workspace");
     if (!h || !out) return FQL_E_INVALID;
     const int B = h->B, ic = h->nets[NET_OS].in_p(), ib = h->nets[NET_BC].in_p(), ap = pad16(h->cfg.act_dim);
     const void* src = nullptr;
@@ -4361,6 +4746,7 @@ extern "C" int fql_debug_enc(fql_handle h, int enc, int code, void* out, size_t 
 int fql_dataset_upload_frames(fql_handle h, int64_t n, const uint8_t* frames, const uint8_t* next_frames, const float* act,
                               const float* rew, const float* mask, const float* terminals, int frame_stack, float p_aug) {
     FQL_IFQL_REFUSES(h, "fql_dataset_upload_frames");
+    FQL_SAC_REFUSES(h, "fql_dataset_upload_frames");
     if (!h) return FQL_E_INVALID;
     FQL_TRY(h, {
         if (!h->visual) throw Invalid{"fql_dataset_upload_frames needs an agent created with an encoder"};
@@ -4404,6 +4790,7 @@ int fql_dataset_upload_frames(fql_handle h, int64_t n, const uint8_t* frames, co
 int fql_update_from_frames(fql_handle h, const int64_t* idx, const int32_t* crop_froms, int batch_size, int64_t lo, int64_t hi,
                            const fql_noise* noise, float* info13, void* stream) {
     FQL_IFQL_REFUSES(h, "fql_update_from_frames");
+    FQL_SAC_REFUSES(h, "fql_update_from_frames");
     if (!h) return FQL_E_INVALID;
     FQL_TRY(h, {
         hipStream_t s = pick(h, stream);
@@ -4626,8 +5013,9 @@ int fql_group_create(const fql_handle* members, int k, fql_group* out) {
     if (!out) { g_create_error = "fql_group_create: out must not be NULL"; return FQL_E_INVALID; }
     *out = nullptr;
     for (int i = 0; members && i < k; ++i)
-        if (members[i] && (members[i]->ifql || members[i]->rebrac)) {
-            g_create_error = "fql_group_create: member " + std::to_string(i) + (members[i]->ifql ? " is an IFQL handle" : " is a ReBRAC handle") +
+        if (members[i] && (members[i]->ifql || members[i]->rebrac || members[i]->sac)) {
+            g_create_error = "fql_group_create: member " + std::to_string(i) +
+                             (members[i]->ifql ? " is an IFQL handle" : members[i]->rebrac ? " is a ReBRAC handle" : " is a SAC handle") +
                              " (groups take FQL agents only)";
             return FQL_E_STATE;
         }

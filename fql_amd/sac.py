@@ -1,0 +1,250 @@
+"""Host-side mirror of the reference's SACAgent (agents/sac.py) over the C ABI: soft actor-critic with a squashed Gaussian actor and a
+learned temperature.  RLPD is this agent run online from an empty replay ring with balanced sampling
+(main.py --offline_steps=0 --online_steps=1000000 --agent=agents/sac.py --balanced_sampling=1):
+
+    agent = SACAgent.create(seed, ex_observations, ex_actions, config)
+    agent.upload_dataset(train_dataset)          # the offline half of every balanced batch
+    agent.create_replay_buffer(size)             # starts empty
+    action = agent.sample_actions(observations=ob, seed=key, temperature=1.0)
+    agent.add_transition(dict(observations=ob, actions=action, rewards=r, masks=m, next_observations=nob), replay=True)
+    agent, info = agent.update_balanced(batch_size)   # concat(dataset.sample(B / 2), replay.sample(B / 2)) -> update; 14 keys
+
+State observations and fp32 only: `encoder`, precision 'bf16x3', JAX-key noise, compute_flow_actions, the data-parallel begin / end
+halves, gradient buckets and agent groups are refused here, before the library is called.  Everything else (datasets, the replay
+ring, checkpoints, get/set_params, synchronize) is FQLAgent's plumbing on a SAC handle.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import math
+
+import numpy as np
+
+from . import _cabi
+from .agent import FQLAgent, LazyInfo, _Arg, _Pending, _seed_to_u64
+from .config import ConfigDict
+
+SAC_INFO_KEYS = (
+    'critic/critic_loss', 'critic/q_mean', 'critic/q_max', 'critic/q_min',
+    'actor/total_loss', 'actor/actor_loss', 'actor/alpha_loss', 'actor/alpha', 'actor/entropy', 'actor/std', 'actor/q',
+    'grad/max', 'grad/min', 'grad/norm',
+)
+# eps1: the raw N(0, 1) [B, act] of the next-observation actions of the critic loss (agents/sac.py:27); eps2: of the actor loss's
+# actions (agents/sac.py:62)
+SAC_NOISE_KEYS = ('eps1', 'eps2')
+
+
+def get_config():
+    """agents/sac.py get_config (same keys and defaults), plus the engine's own 'rng' and 'precision' keys."""
+    return ConfigDict(
+        agent_name='sac',
+        ob_dims=None,  # set automatically by create()
+        action_dim=None,  # set automatically by create()
+        lr=3e-4,
+        batch_size=256,
+        actor_hidden_dims=(512, 512, 512, 512),
+        value_hidden_dims=(512, 512, 512, 512),
+        layer_norm=True,
+        actor_layer_norm=False,
+        discount=0.99,
+        tau=0.005,
+        target_entropy=None,
+        target_entropy_multiplier=0.5,
+        tanh_squash=True,
+        state_dependent_std=True,
+        actor_fc_scale=0.01,
+        q_agg='min',
+        backup_entropy=False,
+        encoder=None,
+        rng='engine',  # not a reference key: device Philox noise or explicit tensors (the only sources SAC supports)
+        precision='fp32',  # not a reference key: SAC runs in fp32 only
+    )
+
+
+class _PendingN(_Pending):
+    """_Pending over fql_info_wait_n: all fql_num_info(h) scalars of one update."""
+
+    def get(self):
+        if self.vals is None:
+            n = len(self.agent._info_keys)
+            buf = (C.c_float * n)()
+            self.agent._check(self.agent._lib.fql_info_wait_n(self.agent._h, self.ticket, buf, n))
+            self.vals = [float(buf[i]) for i in range(n)]
+            self.agent = None
+        return self.vals
+
+
+class SACAgent(FQLAgent):
+    """SAC agent (RLPD's learner) backed by the MI355X step engine."""
+
+    _loss_infos = 11
+    _jax_sample_noise = False
+    _pending_cls = _PendingN
+
+    @classmethod
+    def create(cls, seed, ex_observations, ex_actions, config):
+        """agents/sac.py create.  `config`: dict-like with the keys of get_config()."""
+        cfg = get_config()
+        cfg.update(dict(config))
+        if cfg.get('encoder') is not None:
+            raise NotImplementedError('SAC: visual encoders are not available (state observations only)')
+        if cfg.get('precision', 'fp32') not in ('fp32', 0):
+            raise NotImplementedError(f"SAC runs in fp32 only (precision {cfg['precision']!r})")
+        if cfg.get('rng', 'engine') != 'engine':
+            raise NotImplementedError(f"SAC draws its noise from the engine's RNG or explicit tensors only (rng {cfg['rng']!r})")
+        if not cfg['state_dependent_std']:
+            raise NotImplementedError('SAC: only state_dependent_std=True is available')
+        cfg.setdefault('flow_steps', 10)   # (an fql_config field SAC does not read)
+        lib = _cabi.load()
+        c, ob_dims, action_dim = cls._engine_config(lib, cfg, ex_observations, ex_actions)
+        sc = _cabi.FqlSacConfig()
+        lib.fql_sac_default_config(C.byref(sc))
+        sc.target_entropy = math.nan if cfg['target_entropy'] is None else float(cfg['target_entropy'])
+        sc.target_entropy_multiplier = float(cfg['target_entropy_multiplier'])
+        sc.tanh_squash, sc.state_dependent_std = int(bool(cfg['tanh_squash'])), 1
+        sc.actor_fc_scale, sc.backup_entropy = float(cfg['actor_fc_scale']), int(bool(cfg['backup_entropy']))
+        h = C.c_void_p()
+        _cabi.check(lib, None, lib.fql_sac_create(C.byref(c), C.byref(sc), int(seed) & 0xFFFFFFFFFFFFFFFF, C.byref(h)))
+        cfg['ob_dims'] = ob_dims
+        cfg['action_dim'] = action_dim
+        if cfg['target_entropy'] is None:   # sac.py create: -target_entropy_multiplier * action_dim
+            cfg['target_entropy'] = -cfg['target_entropy_multiplier'] * action_dim
+        return cls(h, cfg, int(seed))
+
+    def _noise_args(self, noise, B):
+        """Explicit eps1 / eps2 [B, act] (raw N(0, 1)); other keys are refused."""
+        if noise is None:
+            return None, []
+        extra = set(noise) - set(SAC_NOISE_KEYS)
+        if extra:
+            raise ValueError(f'SAC reads only {SAC_NOISE_KEYS} of the noise dict, got {sorted(extra)}')
+        ad = self.config['action_dim']
+        e1, e2 = _Arg(noise.get('eps1'), (B, ad)), _Arg(noise.get('eps2'), (B, ad))
+        return _cabi.FqlNoise(e1.ptr, None, None, None, e2.ptr), [e1, e2]
+
+    def _info(self, stream):
+        t = C.c_uint64()
+        self._check(self._lib.fql_info_enqueue(self._h, stream, C.byref(t)))
+        return LazyInfo(self, int(t.value), SAC_INFO_KEYS)
+
+    # -- reference API ----------------------------------------------------------------------
+    def update(self, batch, noise=None, want_info=True):
+        """agents/sac.py update.  Returns (agent, info); info is a LazyInfo with SAC_INFO_KEYS, or None with want_info=False."""
+        B, args = self._batch_args(batch)
+        self._ensure_batch(B)
+        nz, nargs = self._noise_args(noise, B)
+        stream = self._stream(args + nargs)
+        self._check(self._lib.fql_sac_update(self._h, *[a.ptr for a in args], B, C.byref(nz) if nz else None, None, stream))
+        self._keep = (args, nargs)
+        return self, (self._info(stream) if want_info else None)
+
+    def update_from_dataset(self, batch_size=None, idxs=None, noise=None, shard=(0, 0), want_info=False, stream=None):
+        """train_dataset.sample(B) + update(batch) without leaving the device."""
+        B = int(batch_size or self.config['batch_size'])
+        self._ensure_batch(B)
+        nz, nargs = self._noise_args(noise, B)
+        ip, keep = None, None
+        if idxs is not None:
+            keep, ip = self._host_idx(idxs, B, self.dataset_size()[0], 'idxs')
+        self._check(self._lib.fql_sac_update_from_dataset(self._h, ip, B, int(shard[0]), int(shard[1]), C.byref(nz) if nz else None,
+                                                          None, stream))
+        self._keep = (keep, nargs)
+        return self, (self._info(stream) if want_info else None)
+
+    def update_balanced(self, batch_size=None, idxs=None, noise=None, want_info=False, stream=None):
+        """RLPD's step (main.py:255-259) on the device: concat(train_dataset.sample(B // 2), replay_buffer.sample(B // 2)) -> update.
+        `idxs` = (dataset_idxs, replay_idxs), B // 2 each, or None (engine RNG)."""
+        B = int(batch_size or self.config['batch_size'])
+        self._ensure_batch(B)
+        nz, nargs = self._noise_args(noise, B)
+        ia = ib = None
+        keep = None
+        if idxs is not None:
+            ka, ia = self._host_idx(idxs[0], B // 2, self.dataset_size()[0], 'dataset idxs')
+            kb, ib = self._host_idx(idxs[1], B // 2, self.replay_size()[0], 'replay idxs')
+            keep = (ka, kb)
+        self._check(self._lib.fql_sac_update_balanced(self._h, ia, ib, B, C.byref(nz) if nz else None, None, stream))
+        self._keep = (keep, nargs)
+        return self, (self._info(stream) if want_info else None)
+
+    def read_info(self):
+        """The 14 infos of the last update (blocks until it has run)."""
+        n = len(SAC_INFO_KEYS)
+        buf = (C.c_float * n)()
+        self._check(self._lib.fql_read_info_n(self._h, buf, n))
+        return {k: float(buf[i]) for i, k in enumerate(SAC_INFO_KEYS)}
+
+    def total_loss(self, batch, grad_params=None, rng=None, noise=None):
+        """agents/sac.py total_loss with grad_params=None (the validation probe, main.py:284): (loss, info) with the 11 critic and
+        actor infos.  No state changes."""
+        if grad_params is not None:
+            raise NotImplementedError('total_loss with traced grad_params is jax.grad plumbing; use update()')
+        if rng is not None:
+            raise NotImplementedError('SAC draws its noise from the engine RNG or explicit tensors (noise=), not JAX keys')
+        B, args = self._batch_args(batch)
+        self._ensure_batch(B)
+        nz, nargs = self._noise_args(noise, B)
+        loss = C.c_float()
+        info = (C.c_float * 11)()
+        stream = self._stream(args + nargs)
+        self._check(self._lib.fql_sac_total_loss(self._h, *[a.ptr for a in args], B, C.byref(nz) if nz else None, C.byref(loss), info,
+                                                 stream))
+        return float(loss.value), {k: float(info[i]) for i, k in enumerate(SAC_INFO_KEYS[:11])}
+
+    def sample_actions(self, observations, seed=None, temperature=1.0, noises=None):
+        """agents/sac.py sample_actions: clip(tanh(mean + exp(log_std) temperature N(0, 1)), -1, 1).  [od] -> [act]; [n, od] -> [n, act].
+        `noises`: the raw N(0, 1) with the actions' shape, or None = engine RNG keyed by `seed`."""
+        od, ad = self.config['ob_dims'][0], self.config['action_dim']
+        is_torch = hasattr(observations, 'data_ptr')
+        if int(observations.shape[-1]) != od:
+            raise ValueError(f'observations last dim must be {od}, got {tuple(observations.shape)}')
+        lead = tuple(observations.shape[:-1])
+        n = int(np.prod(lead)) if lead else 1
+        o = _Arg(observations, (n, od))
+        z = _Arg(noises, (n, ad))
+        if is_torch and observations.is_cuda:
+            torch = __import__('torch')
+            out = torch.empty(lead + (ad,), dtype=torch.float32, device=observations.device)
+            optr = out.data_ptr()
+        else:
+            out = np.empty(lead + (ad,), dtype=np.float32)
+            optr = out.ctypes.data
+        if seed is None and noises is None:
+            self._sample_calls += 1
+            sd = (self._seed << 20) ^ self._sample_calls
+        else:
+            sd = _seed_to_u64(seed)
+        self._check(self._lib.fql_sac_sample_actions(self._h, o.ptr, n, z.ptr, sd & 0xFFFFFFFFFFFFFFFF, float(temperature), optr,
+                                                     self._stream([o, z])))
+        return out
+
+    def sac_stats(self):
+        """(launches, MACs) of one update."""
+        la, ma = C.c_int64(), C.c_int64()
+        self._check(self._lib.fql_sac_stats(self._h, C.byref(la), C.byref(ma)))
+        return int(la.value), int(ma.value)
+
+    # -- FQL-only paths, refused before the library is called ----------------------------------
+    def _refuse(self, what):
+        raise NotImplementedError(f'SAC: {what} is not available (FQL agents only)')
+
+    def compute_flow_actions(self, observations, noises):
+        self._refuse('compute_flow_actions (the actor is a Gaussian, there is no flow)')
+
+    def update_begin(self, *a, **k):
+        self._refuse('the data-parallel update halves')
+
+    def update_begin_split(self, *a, **k):
+        self._refuse('the data-parallel update halves')
+
+    def update_end(self, *a, **k):
+        self._refuse('the data-parallel update halves')
+
+    def update_end_split(self, *a, **k):
+        self._refuse('the data-parallel update halves')
+
+    def grad_buckets(self):
+        self._refuse('gradient buckets')
+
+
+__all__ = ['SACAgent', 'SAC_INFO_KEYS', 'SAC_NOISE_KEYS', 'get_config']

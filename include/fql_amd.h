@@ -380,6 +380,65 @@ int fql_rebrac_sample_actions(fql_handle h, const float* observations, int n, co
 /* launches and algorithmic MACs of one full (full_update != 0) or critic-only update */
 int fql_rebrac_stats(fql_handle h, int full_update, int64_t* launches_per_update, int64_t* macs_per_update);
 
+/* ---- SAC (agents/sac.py): soft actor-critic with a squashed Gaussian actor and a learned temperature; RLPD is this agent run online
+ * from an empty replay ring with balanced sampling (main.py --offline_steps=0 --balanced_sampling=1).  State observations, fp32 only.
+ * Networks (agents/sac.py, utils/networks.py Actor / Value / LogParam): "modules_critic/value_net/..." and
+ * "modules_target_critic/value_net/..." (FQL's stacked [2, ...] critic), "modules_actor/actor_net/Dense_0..n-1" (GELU, + "LayerNorm_i"
+ * with actor_layer_norm), "modules_actor/mean_net/{bias,kernel}" and "modules_actor/log_std_net/{bias,kernel}" ([H, act] / [act]; kernels
+ * variance_scaling(actor_fc_scale, fan_avg, uniform)) and "modules_alpha/log_value" (shape (), initial 0).  Adam over the whole tree,
+ * Polyak of the target critic from the PRE-step critic.
+ * Infos: 14 floats (FQL_SAC_NUM_INFO, fql_handle_info_name): 0 critic/critic_loss 1 critic/q_mean 2 critic/q_max 3 critic/q_min
+ *   4 actor/total_loss 5 actor/actor_loss 6 actor/alpha_loss 7 actor/alpha 8 actor/entropy 9 actor/std 10 actor/q 11 grad/max
+ *   12 grad/min 13 grad/norm.  The update calls write 14 floats to info14 (NULL: read later with fql_read_info_n / fql_info_wait_n);
+ *   fql_read_info and fql_info_wait return FQL_E_STATE on a SAC handle rather than overrun a 13-float buffer.
+ * fql_noise: only eps1 (eps_n: the next-observation actions of the critic loss) and eps2 (eps_c: the actor loss's actions) are read,
+ * each the raw N(0, 1) [B, act]; any other non-NULL pointer is FQL_E_INVALID.  NULL = the engine's Philox tensors 1 and 5.
+ * A SAC handle is an ordinary fql_handle for destroy, set_batch_size, leaf / param / opt-state / step access, dataset upload / add /
+ * reserve / size, replay create / add / size, fql_sample_actions (temperature 1), info enqueue / fql_info_wait_n / fql_read_info_n,
+ * fql_synchronize, fql_stats and fql_stream.  Refused: encoder != 0, precision != 0 or state_dependent_std == 0 at create
+ * (FQL_E_INVALID); on a SAC handle fql_update*, fql_update_begin* / _end*, fql_total_loss, fql_grad_buckets, frame uploads / updates,
+ * fql_noise_from_jax_keys and fql_flow_actions return FQL_E_STATE, and fql_group_create with a SAC member returns FQL_E_STATE.  The
+ * fql_sac_* calls on another handle return FQL_E_STATE. */
+#define FQL_SAC_NUM_INFO 14
+typedef struct fql_sac_config {
+    float target_entropy;             /* NaN = automatic: -target_entropy_multiplier * act_dim (NaN)  */
+    float target_entropy_multiplier;  /* (0.5)                                                          */
+    int32_t tanh_squash;              /* a = tanh(x) (1) or x (0)                                       */
+    int32_t state_dependent_std;      /* log_std_net on the hidden features (1); 0 is refused           */
+    float actor_fc_scale;             /* mean_net / log_std_net kernel init scale (0.01)                */
+    int32_t backup_entropy;           /* subtract discount mask alpha log_prob' in the target (0)      */
+    int32_t reserved[6];
+} fql_sac_config;
+void fql_sac_default_config(fql_sac_config* c);
+/* fql_config.q_agg is read (0 mean, 1 min; SAC's default is min); alpha, flow_steps and normalize_q_loss are ignored. */
+int fql_sac_create(const fql_config* cfg, const fql_sac_config* scfg, uint64_t seed, fql_handle* out);
+/* SACAgent.update(batch)  agents/sac.py. */
+int fql_sac_update(fql_handle h, const float* observations, const float* actions, const float* rewards, const float* masks,
+                   const float* next_observations, int batch_size, const fql_noise* noise, float* info14, void* stream);
+/* train_dataset.sample(B) + update(batch) on the device; idx / lo / hi as fql_update_from_dataset's. */
+int fql_sac_update_from_dataset(fql_handle h, const int64_t* idx, int batch_size, int64_t lo, int64_t hi, const fql_noise* noise,
+                                float* info14, void* stream);
+/* RLPD's balanced step (main.py:255-259): concat(dataset.sample(B / 2), replay.sample(B / 2)) -> update, gathered on the device.
+ * Indices as fql_update_balanced's (both or neither); B must be even; FQL_E_INVALID while the replay ring is empty. */
+int fql_sac_update_balanced(fql_handle h, const int64_t* idx_dataset, const int64_t* idx_replay, int batch_size, const fql_noise* noise,
+                            float* info14, void* stream);
+/* SACAgent.total_loss(batch): pure forward, no state change (parameters, moments, counters and the info slots that fql_read_info_n
+ * reads are as the last update left them).  loss = critic_loss + actor total_loss; info11 receives infos 0-10.  Synchronous. */
+int fql_sac_total_loss(fql_handle h, const float* observations, const float* actions, const float* rewards, const float* masks,
+                       const float* next_observations, int batch_size, const fql_noise* noise, float* loss, float* info11,
+                       void* stream);
+/* SACAgent.sample_actions(observations, seed, temperature): clip(tanh(mean + exp(log_std) temperature eps), -1, 1) (no tanh when
+ * tanh_squash == 0).  noise [n, act] raw N(0, 1) or NULL (engine RNG keyed by `seed`); rows of one call equal single calls with the same
+ * noise rows.  fql_sample_actions == this with temperature 1. */
+int fql_sac_sample_actions(fql_handle h, const float* observations, int n, const float* noise, uint64_t seed, float temperature,
+                           float* out, void* stream);
+/* launches and algorithmic MACs of one update */
+int fql_sac_stats(fql_handle h, int64_t* launches_per_update, int64_t* macs_per_update);
+/* The info calls for any handle: exactly fql_num_info(h) floats into `out` (13 FQL, 12 IFQL / ReBRAC, 14 SAC; nothing past them);
+ * FQL_E_INVALID if n < fql_num_info(h). */
+int fql_read_info_n(fql_handle h, float* out, int n);
+int fql_info_wait_n(fql_handle h, uint64_t ticket, float* out, int n);
+
 #ifdef __cplusplus
 }
 #endif
