@@ -18,6 +18,7 @@ FQL_IFQL_NUM_INFO = 12
 FQL_REBRAC_NUM_INFO = 12
 FQL_REBRAC_CRITIC_NUM_INFO = 7
 FQL_SAC_NUM_INFO = 14
+FQL_BC_NUM_INFO = 4
 FQL_OK, FQL_E_INVALID, FQL_E_NODEVICE, FQL_E_HIP, FQL_E_STATE, FQL_E_NOTFOUND = 0, -1, -2, -3, -4, -5
 
 
@@ -47,6 +48,10 @@ class FqlSacConfig(C.Structure):
     _fields_ = [('target_entropy', C.c_float), ('target_entropy_multiplier', C.c_float), ('tanh_squash', C.c_int32),
                 ('state_dependent_std', C.c_int32), ('actor_fc_scale', C.c_float), ('backup_entropy', C.c_int32),
                 ('reserved', C.c_int32 * 6)]
+
+
+class FqlBcConfig(C.Structure):
+    _fields_ = [('denoise_steps', C.c_int32), ('reserved', C.c_int32 * 7)]
 
 
 class FqlNoise(C.Structure):
@@ -129,6 +134,13 @@ SYMBOLS = {
     'fql_sac_total_loss': (_I, [_VP] + _BATCH + [C.POINTER(FqlNoise), C.POINTER(_F), C.POINTER(_F), _VP]),
     'fql_sac_sample_actions': (_I, [_VP, _VP, _I, _VP, _U64, _F, _VP, _VP]),
     'fql_sac_stats': (_I, [_VP, C.POINTER(_I64), C.POINTER(_I64)]),
+    'fql_bc_default_config': (None, [C.POINTER(FqlBcConfig)]),
+    'fql_bc_create': (_I, [C.POINTER(FqlConfig), C.POINTER(FqlBcConfig), _U64, C.POINTER(_VP)]),
+    'fql_bc_update': (_I, [_VP, _VP, _VP, _I, C.POINTER(FqlNoise), _VP, _VP]),
+    'fql_bc_update_from_dataset': (_I, [_VP, _VP, _I, _I64, _I64, C.POINTER(FqlNoise), _VP, _VP]),
+    'fql_bc_policy_loss': (_I, [_VP, _VP, _VP, _I, C.POINTER(FqlNoise), C.POINTER(_F), _VP]),
+    'fql_bc_sample_actions': (_I, [_VP, _VP, _I, _VP, _U64, _VP, _VP]),
+    'fql_bc_stats': (_I, [_VP, C.POINTER(_I64), C.POINTER(_I64), C.POINTER(_I64)]),
     'fql_read_info_n': (_I, [_VP, _VP, _I]),
     'fql_info_wait_n': (_I, [_VP, _U64, _VP, _I]),
 }

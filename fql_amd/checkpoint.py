@@ -10,6 +10,8 @@ FQLAgent (agents/fql.py:18-20, utils/flax_utils.py:53-88) that state dict is
                  'opt_state': {'0': {'count': int32, 'mu': <params tree>, 'nu': <params tree>}, '1': {}}}}
 
 (optax.adam = chain(scale_by_adam, scale): a 2-tuple of states, tuples serialise with string indices).
+BCAgent (agents/bc.py) holds a bare TrainState named ``policy``: ``{'rng', 'policy': {'step', 'params': {'Dense_0': ..,
+'MLP_0': ..}, 'opt_state': ..}}``; the agent class names its TrainState key (``_train_state_key``).
 This module writes and reads exactly that nesting with numpy leaves.  SURVEY.md 8f N2.
 
 **Parity unpinned**: no checkpoint written by the JAX reference exists in this environment (jax/flax are absent
@@ -126,7 +128,7 @@ def to_state_dict(agent, visual_layout: str = 'nested') -> dict:
         raise ValueError("visual_layout must be 'nested', 'toplevel' or 'toplevel-only'")
     return {
         'rng': rng,
-        'network': {
+        getattr(agent, '_train_state_key', 'network'): {   # BCAgent's TrainState is named 'policy' (agents/bc.py:45)
             'step': np.int64(opt['step']),
             'params': trees[0],
             'opt_state': {'0': {'count': np.int32(opt['count']), 'mu': trees[1], 'nu': trees[2]}, '1': {}},
@@ -172,7 +174,7 @@ def from_state_dict(agent, state: dict, strict: bool = True) -> dict:
     Returns a report: {'visual_layout': 'state'|'nested'|'toplevel'|'both-shared'|'both-distinct', 'dropped': [...],
     'missing': [...], 'unexpected': [...]}.  With strict=True missing / unexpected leaves raise KeyError naming them."""
     report: Dict[str, Any] = {'dropped': [], 'missing': [], 'unexpected': []}
-    net = state['network']
+    net = state[getattr(agent, '_train_state_key', 'network')]
     want = {p for p, _ in agent.leaves()}
 
     def prepare(tree, what):

@@ -17,6 +17,7 @@
 #include "fql_ifql.h"
 #include "fql_rebrac.h"
 #include "fql_sac.h"
+#include "fql_bc.h"
 #include <hip/hip_ext.h>
 #include "fql_aql.h"
 
@@ -133,7 +134,9 @@ enum OpType { OP_GEMM, OP_GEMM64, OP_WGRAD, OP_LNBWD, OP_PREP, OP_POSTOS, OP_EUL
               // ReBRAC (agents/rebrac.py) only: after IFQL's
               OP_REBRAC_PREP, OP_REBRAC_ACT, OP_REBRAC_LOSS_C, OP_REBRAC_LOSS_A, OP_REBRAC_AGRAD, OP_REBRAC_FIN,
               // SAC (agents/sac.py) only: after ReBRAC's
-              OP_SAC_PREP, OP_SAC_ACT, OP_SAC_LOSS_C, OP_SAC_LOSS_A, OP_SAC_AGRAD, OP_SAC_FIN, OP_NUM_TYPES };
+              OP_SAC_PREP, OP_SAC_ACT, OP_SAC_LOSS_C, OP_SAC_LOSS_A, OP_SAC_AGRAD, OP_SAC_FIN,
+              // BC (agents/bc.py) only: after SAC's
+              OP_BC_PREP, OP_BC_FIN, OP_BC_STEPBIAS, OP_BC_LAYER0, OP_NUM_TYPES };
 
 struct Op {
     OpType type;
@@ -167,6 +170,9 @@ struct Op {
     SacCriticArgs sc;
     SacActorArgs sa;
     SacActorGradArgs sag;
+    BcPrepArgs bprep;
+    BcStepBiasArgs bsb;
+    BcLayer0Args bl0;
     ChainArgs chain;
     const ConvWprepTask* wprep_tasks = nullptr;
     int wprep_n = 0;
@@ -339,6 +345,12 @@ struct fql_engine {
     float target_entropy = 0.f;
     size_t alpha_off = 0;
     float *w_eps = nullptr, *lp_buf = nullptr;   // [2B, ap]: eps_c rows then eps_n rows; [2B]: log-probabilities of a, then of a'
+    // BC agent (agents/bc.py; fql_bc_create): the arena holds ONE net, the policy, in the NET_BC slot (input [obs | x_t | emb(t)], every
+    // other net is empty, so critic_size = 0 and Adam has no Polyak range).  One lane: prep, forward, loss, backward, Adam, finalize.
+    bool bc = false;
+    int bc_steps = 16;            // denoise_steps S
+    float* d_emb = nullptr;       // [(S + 1), 16] timestep-embedding table (built on the host at create)
+    bool lane0_64 = false;        // while the BC update program is built: lane 0 takes the 64-column LDS-tiled kernels and keeps its weight gradients
     uint64_t seed = 0;
     int device = 0;
     hipStream_t stream = nullptr;
@@ -503,12 +515,13 @@ struct fql_engine {
             }
             return n;
         };
-        nets[NET_C0] = make(od + ad, cfg.value_hidden, cfg.num_value_hidden, 1, cfg.layer_norm != 0);
+        nets[NET_C0] = bc ? Net{} : make(od + ad, cfg.value_hidden, cfg.num_value_hidden, 1, cfg.layer_norm != 0);
         nets[NET_C1] = nets[NET_C0];
-        nets[NET_BC] = rebrac ? make(od, cfg.actor_hidden, cfg.num_actor_hidden, ad, cfg.actor_layer_norm != 0)   // actor (utils/networks.py:82-150)
+        nets[NET_BC] = bc ? make(od + ad + BC_EMB, cfg.actor_hidden, cfg.num_actor_hidden, ad, cfg.actor_layer_norm != 0)   // policy(obs, x_t, emb(t)) (agents/bc.py:26-44)
+                     : rebrac ? make(od, cfg.actor_hidden, cfg.num_actor_hidden, ad, cfg.actor_layer_norm != 0)   // actor (utils/networks.py:82-150)
                      : sac ? make(od, cfg.actor_hidden, cfg.num_actor_hidden, 2 * pad16(ad), cfg.actor_layer_norm != 0)   // actor_net + [mean_net | log_std_net]
                               : make(od + ad + 1, cfg.actor_hidden, cfg.num_actor_hidden, ad, cfg.actor_layer_norm != 0);
-        nets[NET_OS] = (rebrac || sac) ? Net{} : ifql ? make(od, cfg.value_hidden, cfg.num_value_hidden, 1, cfg.layer_norm != 0)   // value (agents/ifql.py:188-193)
+        nets[NET_OS] = (rebrac || sac || bc) ? Net{} : ifql ? make(od, cfg.value_hidden, cfg.num_value_hidden, 1, cfg.layer_norm != 0)   // value (agents/ifql.py:188-193)
                             : make(od + ad, cfg.actor_hidden, cfg.num_actor_hidden, ad, cfg.actor_layer_norm != 0);
         nets[NET_T0] = nets[NET_C0];
         nets[NET_T1] = nets[NET_C0];
@@ -616,7 +629,7 @@ struct fql_engine {
         const Net& n = nets[NET_BC];
         const int nh = n.nl() - 1;
         const int H = n.layers[0].out_p;
-        bool ok = !ifql && !rebrac && !sac && !cfg.actor_layer_norm && cfg.act_dim <= 15 && nh >= 3 && (H == 256 || H == 512);   // (IFQL has no Euler chain in its update)
+        bool ok = !ifql && !rebrac && !sac && !bc && !cfg.actor_layer_norm && cfg.act_dim <= 15 && nh >= 3 && (H == 256 || H == 512);   // (IFQL has no Euler chain in its update)
         for (int l = 0; l < nh && ok; ++l) ok = n.layers[l].out == H && n.layers[l].out_p == H;
         use_chain = ok;
         if (!ok) return;
@@ -671,7 +684,37 @@ struct fql_engine {
                                  {"modules_target_critic", "value_net", NET_T0, NET_T1, false, ENC_T}};
         const Mod* mods = sac ? sac_mods : rebrac ? rebrac_mods : ifql ? ifql_mods : fql_mods;
         int tid = 0;
-        for (int mi = 0; mi < 4; ++mi) {
+        if (bc) {   // agents/bc.py:26-44: a bare TrainState: Dense_0 (the head), then MLP_0/Dense_i and MLP_0/LayerNorm_i (jax dict order)
+            const Net& n0 = nets[NET_BC];
+            auto add = [&](const std::string& name, bool matrix, int rows, int cols, size_t o0, int rp, int cp) {
+                Leaf lf;
+                lf.name = name;
+                int d = 0;
+                if (matrix) lf.shape[d++] = rows;
+                lf.shape[d++] = cols;
+                lf.ndim = d;
+                for (int k = d; k < 4; ++k) lf.shape[k] = 1;
+                lf.segs.push_back(Segment{o0, matrix ? rows : 1, cols, matrix ? rp : 1, cp});
+                lf.trainable = true;
+                lf.train_id = tid++;
+                leaves.push_back(lf);
+            };
+            const Layer& hd = n0.layers.back();
+            add("Dense_0/bias", false, 1, hd.out, hd.b, 1, hd.out_p);
+            add("Dense_0/kernel", true, hd.in, hd.out, hd.w, hd.in_p, hd.out_p);
+            for (int i = 0; i + 1 < n0.nl(); ++i) {
+                const Layer& a = n0.layers[i];
+                add("MLP_0/Dense_" + std::to_string(i) + "/bias", false, 1, a.out, a.b, 1, a.out_p);
+                add("MLP_0/Dense_" + std::to_string(i) + "/kernel", true, a.in, a.out, a.w, a.in_p, a.out_p);
+            }
+            for (int i = 0; i + 1 < n0.nl(); ++i) {
+                const Layer& a = n0.layers[i];
+                if (!a.ln) continue;
+                add("MLP_0/LayerNorm_" + std::to_string(i) + "/bias", false, 1, a.out, a.be, 1, a.out_p);
+                add("MLP_0/LayerNorm_" + std::to_string(i) + "/scale", false, 1, a.out, a.g, 1, a.out_p);
+            }
+        }
+        for (int mi = 0; mi < (bc ? 0 : 4); ++mi) {
             const Mod& m = mods[mi];
             if (m.n0 < 0) {   // modules_alpha/log_value: shape ()
                 Leaf lf;
@@ -787,6 +830,7 @@ struct fql_engine {
             const char* smods[3] = {"modules_actor/", "modules_alpha/", "modules_critic/"};
             const char* const* mods = sac ? smods : rebrac ? rmods : ifql ? imods : fmods;
             for (int m = 0; m < 3; ++m) {
+                if (bc) { mod_chunk0[m] = 0; mod_chunkn[m] = n_chunks; continue; }   // one module: every chunk
                 int lo = 1 << 30, hi = -1;
                 for (const Leaf& lf : leaves)
                     if (lf.trainable && lf.name.rfind(mods[m], 0) == 0) { lo = std::min(lo, lf.train_id); hi = std::max(hi, lf.train_id); }
@@ -831,6 +875,19 @@ struct fql_engine {
             for (const Layer& L : nets[ni].layers) {
                 // ReBRAC's mean_net: variance_scaling(actor_fc_scale, fan_avg, uniform) (utils/networks.py:9-11,117)
                 const double scale = (rebrac && ni == NET_BC && &L == &nets[ni].layers.back()) ? (double)rcfg.actor_fc_scale : 1.0;
+                if (bc && &L == &nets[ni].layers.back()) {
+                    // BC's Dense_0 is a bare nn.Dense (agents/bc.py:43): flax's default lecun_normal = variance_scaling(1, fan_in,
+                    // truncated_normal): N(0, 1) truncated to [-2, 2], scaled by sqrt(1 / fan_in) / 0.87962566103423978
+                    const double sd = std::sqrt(1.0 / (double)L.in) / 0.87962566103423978;
+                    std::normal_distribution<double> Nd(0.0, 1.0);
+                    for (int r = 0; r < L.in; ++r)
+                        for (int c = 0; c < L.out; ++c) {
+                            double v = Nd(gen);
+                            while (v < -2.0 || v > 2.0) v = Nd(gen);
+                            h[L.w + (size_t)r * L.out_p + c] = (float)(sd * v);
+                        }
+                    continue;
+                }
                 if (sac && ni == NET_BC && &L == &nets[ni].layers.back()) {
                     // SAC's mean_net and log_std_net: variance_scaling(actor_fc_scale, fan_avg, uniform), [H, act] each (utils/networks.py:9-11,111-113)
                     const int ad = cfg.act_dim, ap = pad16(ad);
@@ -1159,7 +1216,7 @@ struct fql_engine {
 
     // throughput-lane tasks with 64-aligned shapes go to the 64x64 LDS-tiled kernel
     bool want64(int M, int N, int K, int flags) const {
-        if (emit_lane == 0 || !allow64) return false;
+        if ((emit_lane == 0 && !lane0_64) || !allow64) return false;
         if (M % 64 || N % 64 || K % 64) return false;
         if (flags & (GF_EULER | GF_CLIP_OUT)) return false;
         return true;
@@ -1180,11 +1237,12 @@ struct fql_engine {
     }
 
     // forward of one pass appended to a program.  final_flags: epilogue of the last layer.
+    // first_layer > 0: the layers before it were run by the caller (BC's sampler builds layer 0's output itself).
     void emit_forward(Program& pr, const PassBuf& p, bool save, int final_flags = 0, float* aux = nullptr,
-                      float* aux2 = nullptr, float f0 = 0.f, float f1 = 0.f) {
+                      float* aux2 = nullptr, float f0 = 0.f, float f1 = 0.f, int first_layer = 0) {
         const Net& n = nets[p.net];
         const int L = n.nl() - 1;
-        for (int l = 0; l <= L; ++l) {
+        for (int l = first_layer; l <= L; ++l) {
             const Layer& ly = n.layers[l];
             Op op{};
             op.type = OP_GEMM;
@@ -1421,7 +1479,7 @@ struct fql_engine {
                 // issued on the side lane so they never sit between two links of that chain (a separate wgrad lane was measured
                 // slower than sharing launches)
                 const int keep = emit_lane;
-                if (emit_lane == 0 && !split_build) emit_lane = 1;
+                if (emit_lane == 0 && !split_build && !lane0_64) emit_lane = 1;
                 if (defer_wgrads) { op.lane = emit_lane; defer_wgrads->push_back(op); }
                 else push(pr, op);
                 emit_lane = keep;
@@ -2096,6 +2154,19 @@ struct fql_engine {
                 FQL_LAUNCH(fql_rebrac_finalize_kernel, dim3(1), dim3(FQL_THREADS), 0, s,
                                    FinalizeArgs{d_state, d_chunks, d_partials, d_leaf_range, n_chunks, n_train_leaves, L.op.fin_mode & 1, tl},
                                    (L.op.fin_mode >> 1) & 1);
+                break;
+            case OP_BC_PREP:
+                FQL_LAUNCH(fql_bc_prep_kernel, dim3((L.op.bprep.B + 3) / 4), dim3(FQL_THREADS), 0, s, L.op.bprep);
+                break;
+            case OP_BC_STEPBIAS:
+                FQL_LAUNCH(fql_bc_stepbias_kernel, dim3((L.op.bsb.S * L.op.bsb.H + FQL_THREADS - 1) / FQL_THREADS), dim3(FQL_THREADS), 0, s, L.op.bsb);
+                break;
+            case OP_BC_LAYER0:
+                FQL_LAUNCH(fql_bc_layer0_kernel, dim3((L.op.bl0.M * L.op.bl0.H + FQL_THREADS - 1) / FQL_THREADS), dim3(FQL_THREADS), 0, s, L.op.bl0);
+                break;
+            case OP_BC_FIN:
+                FQL_LAUNCH(fql_bc_finalize_kernel, dim3(1), dim3(FQL_THREADS), 0, s,
+                                   FinalizeArgs{d_state, d_chunks, d_partials, d_leaf_range, n_chunks, n_train_leaves, L.op.fin_mode & 1, tl});
                 break;
             case OP_SAC_PREP:
                 FQL_LAUNCH(fql_sac_prep_kernel, dim3((L.op.sprep.B + 3) / 4), dim3(FQL_THREADS), 0, s, L.op.sprep);
@@ -3019,6 +3090,71 @@ struct fql_engine {
         split_ok = false;
         src_valid = false;
     }
+    // ---------------------------------------------------------------------------------------
+    // the BC update as a program (agents/bc.py:48-84): ONE lane, no cross-lane edge.  Batch assembly -> policy forward (64-column LDS
+    // tiles where the shapes allow, LayerNorm on the A tile) -> flow-matching loss (rides in the side launch of its level) -> backward
+    // (weight gradients and LayerNorm backward share the dgrad launches) -> Adam over every chunk -> finalize.
+    // with_grads = false: the loss probe (forward and loss only: it writes info slot 5, none of the four slots fql_read_info_n reads).
+    // ---------------------------------------------------------------------------------------
+    void build_bc_program(Program& pr, bool with_grads) {
+        const int od = cfg.obs_dim, ad = cfg.act_dim, ap = pad16(ad);
+        DevState* st = d_state;
+        const void* I_L = &st->info[BC_I_LOSS];
+        wide_tiles = true;
+        allow64 = true;
+        lane0_64 = true;
+        emit_lane = 0;
+        {
+            Op op{};
+            op.type = OP_BC_PREP;
+            op.bprep = BcPrepArgs{d_src, st, seed, d_emb, B, od, ad, nets[NET_BC].in_p(), ap, bc_steps, X_bc, vel};
+            op.writes = {X_bc, vel};
+            push(pr, op);
+        }
+        emit_forward(pr, p_bc, with_grads);   // policy(obs, x_t, t)  bc.py:67
+        {
+            Op op{};
+            op.type = OP_LOSS_BC;              // mean((vel - pred)^2) over B act elements  bc.py:69
+            op.lb = LossBcArgs{p_bc.out, vel, with_grads ? p_bc.dz.back() : nullptr, st, B, ad, ap, with_grads ? 1 : 0};
+            op.reads = {p_bc.out, vel};
+            op.writes = {I_L};
+            if (with_grads) op.writes.push_back(p_bc.dz.back());
+            push(pr, op);
+        }
+        if (with_grads) {
+            emit_backward(pr, p_bc, 0, B, true, false);
+            adam_for(pr, 0, {NET_BC}, 0, -2);   // every chunk in one launch; critic_size = 0: no Polyak range
+            Op f{};
+            f.type = OP_BC_FIN;
+            f.fin_mode = 1;
+            f.reads = {I_L, d_partials};
+            f.writes = {&st->info[0], &st->info[10], st};
+            push(pr, f);
+        }
+        lane0_64 = false;
+    }
+    void build_bc_workspace() {
+        const int ap = pad16(cfg.act_dim);
+        auto& W = ws_allocs;
+        X_bc = dalloc(W, (size_t)B * nets[NET_BC].in_p());
+        vel = dalloc(W, (size_t)B * ap);
+        X_os = X_eu = X_c1 = X_c2 = X_ct = X_e0 = C0 = Vpart = w_act = tgt = w_rew = w_mask = nullptr;
+        fused_euler = euler_finish_fused = false;
+        p_bc = make_pass(W, NET_BC, B, X_bc, true, false);
+        build_bc_program(prog_full, true);
+        build_bc_program(prog_loss, false);
+        for (Program* pr : {&prog_full, &prog_loss}) schedule(*pr, W);
+        for (Program* pr : {&prog_full, &prog_loss}) capture(*pr);
+        split_ok = false;
+        src_valid = false;
+    }
+    // multiply-accumulates of one BC update per batch row, algorithmic: forward + backward without the input gradient
+    int64_t bc_macs() const {
+        int64_t m = 0;
+        for (const Layer& L : nets[NET_BC].layers) m += (int64_t)L.in * L.out;
+        return (3 * m - (int64_t)nets[NET_BC].layers[0].in * nets[NET_BC].layers[0].out) * (int64_t)B;
+    }
+
     // multiply-accumulates of one SAC update per batch row, algorithmic (full GEMM shapes at the logical widths; the heads are H x 2 act)
     int64_t sac_macs() const {
         auto macs = [&](const Net& n) {
@@ -3052,6 +3188,7 @@ struct fql_engine {
         auto first = [&](const Net& n) { return (int64_t)n.layers[0].in * n.layers[0].out; };
         if (rebrac) return rebrac_macs(true);
         if (sac) return sac_macs();
+        if (bc) return bc_macs();
         const int64_t os = macs(nets[NET_OS]), bc = macs(nets[NET_BC]), cr = macs(nets[NET_C0]);
         if (ifql) {   // value on 2B rows + its backward on B; target pair; critic pair forward + backward (no input gradient); actor_flow forward + backward
             const int64_t fwd = 2 * os + 4 * cr + bc;
@@ -3108,6 +3245,7 @@ struct fql_engine {
         if (ifql) { build_ifql_workspace(); return; }
         if (rebrac) { in_nact = dalloc(W, (size_t)B * ad); build_rebrac_workspace(); return; }
         if (sac) { build_sac_workspace(); return; }
+        if (bc) { build_bc_workspace(); return; }
         const int inp_c = nets[NET_OS].in_p(), inp_b = nets[NET_BC].in_p();
         X_os = dalloc(W, (size_t)3 * B * inp_c); X_bc = dalloc(W, (size_t)B * inp_b); X_eu = dalloc(W, (size_t)B * inp_b);
         X_c1 = dalloc(W, (size_t)B * inp_c); X_c2 = dalloc(W, (size_t)B * inp_c); X_ct = dalloc(W, (size_t)B * inp_c);
@@ -3243,12 +3381,31 @@ struct fql_engine {
         drain_staging(s);
         set_source(d, s);
     }
+    // BC batches carry observations and actions only (agents/bc.py:56-69)
+    void bc_source_from_batch(const float* obs, const float* act, int batch, const fql_noise* nz, int advance, hipStream_t s) {
+        if (batch != B) invalid("batch_size %d does not match the engine's workspace (%d); call fql_set_batch_size", batch, B);
+        if (!obs || !act) invalid("batch pointers must not be NULL");
+        SrcDesc d{};
+        d.obs = stage(obs, in_obs, (size_t)B * cfg.obs_dim, s);
+        d.act = stage(act, in_act, (size_t)B * cfg.act_dim, s);
+        fill_noise(d, nz, s);
+        d.advance = advance;
+        drain_staging(s);
+        set_source(d, s);
+    }
     void fill_noise(SrcDesc& d, const fql_noise* nz, hipStream_t s) {
         const int ad = cfg.act_dim;
         if (!nz) return;
         if (ifql && (nz->eps1 || nz->z || nz->eps2)) invalid("IFQL reads only x0 and t of fql_noise (eps1, z and eps2 must be NULL)");
         if (rebrac && (nz->x0 || nz->t || nz->z || nz->eps2)) invalid("ReBRAC reads only eps1 of fql_noise (x0, t, z and eps2 must be NULL)");
         if (sac && (nz->x0 || nz->t || nz->z)) invalid("SAC reads only eps1 and eps2 of fql_noise (x0, t and z must be NULL)");
+        if (bc && (nz->eps1 || nz->z || nz->eps2)) invalid("BC reads only x0 and t of fql_noise (eps1, z and eps2 must be NULL)");
+        if (bc && nz->t && !is_device_ptr(nz->t))   // t = k / S on the grid (device pointers are the caller's to keep on it: read as round(t S))
+            for (int b = 0; b < B; ++b) {
+                const float ts = nz->t[b] * (float)bc_steps;
+                if (!(ts >= -1e-3f && ts <= (float)bc_steps + 1e-3f) || std::fabs(ts - std::nearbyint(ts)) > 1e-3f)
+                    invalid("BC: t[%d] = %g is not on the grid {0, 1/%d, ..., 1}", b, (double)nz->t[b], bc_steps);
+            }
         d.eps1 = stage(nz->eps1, in_noise[0], (size_t)B * ad, s);
         d.x0 = stage(nz->x0, in_noise[1], (size_t)B * ad, s);
         d.t = stage(nz->t, in_noise[2], B, s);
@@ -3376,6 +3533,59 @@ struct fql_engine {
         ev->n_pad = n_pad;
         auto& W = ev->allocs;
         const int od = cfg.obs_dim, ad = cfg.act_dim;
+        if (bc) {   // sample_actions (prog_flow): the step-bias table and the loop-invariant C0 = obs W0 + b0 at the head of the program, then per
+                    // Euler step layer 0 as a rank-act update of C0 plus the step's row, and layers 1.. of the 16-row Dense kernel, whose head
+                    // epilogue adds v / S to the actions in place and on the last step writes the clipped actions (GF_EULER | GF_EULER_BARE)
+            const int S = bc_steps, ap = pad16(ad);
+            const Net& n = nets[NET_BC];
+            const Layer& l0 = n.layers[0];
+            const int H = l0.out_p;
+            ev->X = dalloc(W, (size_t)n_pad * n.in_p());     // [obs | 0]
+            ev->Xf = dalloc(W, (size_t)n_pad * ap);          // the flow's state x
+            ev->Xq = dalloc(W, (size_t)S * H);               // step-bias table c_i
+            float* C0e = dalloc(W, (size_t)n_pad * H);
+            ev->tgt = dalloc(W, (size_t)n_pad * ap);
+            ev->st_obs = dalloc(W, (size_t)n_pad * od);
+            ev->st_noise = dalloc(W, (size_t)n_pad * ad);
+            ev->st_out = dalloc(W, (size_t)n_pad * ad);
+            ev->p_eu = make_pass(W, NET_BC, n_pad, ev->X, false, false);
+            emit_lane = 0;
+            Program& pr = ev->prog_flow;
+            {
+                Op op{};
+                op.type = OP_BC_STEPBIAS;
+                op.bsb = BcStepBiasArgs{d_emb, P + l0.w + (size_t)(od + ad) * H, ev->Xq, S, H};
+                op.reads = {d_emb, P + l0.w};
+                op.writes = {ev->Xq};
+                push(pr, op);
+            }
+            {
+                Op op{};
+                op.type = OP_GEMM;
+                GemmTask& t = op.gemm;
+                t.A = ev->X; t.lda = l0.in_p; t.B = P + l0.w; t.ldb = H; t.bias = P + l0.b; t.C = C0e; t.ldc = H;
+                t.M = n_pad; t.N = H; t.K = l0.in_p; t.flags = GF_BIAS;
+                op.reads = {ev->X, t.B};
+                op.writes = {C0e};
+                push(pr, op);
+            }
+            for (int i = 0; i < S; ++i) {
+                Op op{};
+                op.type = OP_BC_LAYER0;
+                op.bl0 = BcLayer0Args{C0e, ev->Xf, P + l0.w + (size_t)od * H, ev->Xq + (size_t)i * H, ev->p_eu.g[0], n_pad, H, ad, ap};
+                op.reads = {C0e, ev->Xf, ev->Xq, P + l0.w};
+                op.writes = {ev->p_eu.g[0]};
+                push(pr, op);
+                emit_forward(pr, ev->p_eu, false, GF_EULER | (i == S - 1 ? GF_EULER_LAST : 0), ev->Xf, ev->tgt, 1.0f / (float)S, 0.f, 1);
+                GemmTask& hd = pr.ops.back().gemm;   // the actions alone: ld ap, no observation block in front, no time block behind
+                hd.flags |= GF_EULER_BARE;
+                hd.i0 = ap; hd.i1 = 0;
+            }
+            schedule(pr, W);
+            Eval& ref = *ev;
+            evals[n_pad] = std::move(ev);
+            return ref;
+        }
         if (rebrac || sac) {   // sample_actions: the actor's forward over the rows (prog_os on p_os; NET_OS is empty here)
             ev->X = dalloc(W, (size_t)n_pad * nets[NET_BC].in_p());
             ev->st_obs = dalloc(W, (size_t)n_pad * od);
@@ -3530,6 +3740,34 @@ struct fql_engine {
             }
         }
     }
+    // BC sample_actions (agents/bc.py:86-101): x ~ N(0, I); S times x += policy(obs, x, i / S) / S; clip.  Rows are independent (16-row
+    // tiles and per-element kernels, the same at every n), so row j of a call equals the single-observation call on the same noise.
+    // noise: [n, act] or null (Philox keyed by (seed, sd) and the row number of the call: chunking does not change the draw)
+    void bc_sample(const float* obs, const float* noise, uint64_t sd, int n, float* out, hipStream_t s, bool own_stream) {
+        if (n <= 0) invalid("n must be positive (got %d)", n);
+        if (!obs || !out) invalid("observations/out must not be NULL");
+        const int od = cfg.obs_dim, ad = cfg.act_dim, ap = pad16(ad);
+        for (int start = 0; start < n; start += 4096) {
+            const int m = std::min(4096, n - start);
+            Eval& ev = get_eval(pad16(m));
+            const float* o = stage(obs + (size_t)start * od, ev.st_obs, (size_t)m * od, s);
+            const float* z = noise ? stage(noise + (size_t)start * ad, ev.st_noise, (size_t)m * ad, s) : nullptr;
+            drain_staging(s);
+            BcAssembleArgs aa{o, z, ev.X, ev.Xf, seed, sd, m, ev.n_pad, od, ad, nets[NET_BC].in_p(), ap, start};
+            hipLaunchKernelGGL(fql_bc_assemble_kernel, dim3((ev.n_pad + 3) / 4), dim3(FQL_THREADS), 0, s, aa);
+            run_launches(ev.prog_flow, s);
+            float* dst = out + (size_t)start * ad;
+            const bool dev_out = is_device_ptr(dst);
+            hipLaunchKernelGGL(fql_extract_kernel, dim3((m * ad + 255) / 256), dim3(256), 0, s, (const float*)ev.tgt, dev_out ? dst : ev.st_out, m, ad, ap);
+            HIP_CHECK(hipGetLastError());
+            if (!dev_out) {
+                HIP_CHECK(hipMemcpyAsync(dst, ev.st_out, (size_t)m * ad * sizeof(float), hipMemcpyDeviceToHost, s));
+                HIP_CHECK(hipStreamSynchronize(s));
+            } else if (own_stream) {
+                HIP_CHECK(hipStreamSynchronize(s));
+            }
+        }
+    }
     // ReBRAC batch sources: the FQL ones plus next_actions (explicit [B, act], or the dataset's actions one row on)
     void rebrac_source_from_batch(const float* obs, const float* act, const float* rew, const float* mask, const float* nobs, const float* nact,
                                   int batch, const fql_noise* nz, int advance, hipStream_t s) {
@@ -3619,6 +3857,10 @@ struct fql_engine {
     do {                                                                                                \
         if ((h) && (h)->sac) { (h)->err = what " is not available on a SAC handle"; return FQL_E_STATE; } \
     } while (0)
+#define FQL_BC_REFUSES(h, what)                                                                        \
+    do {                                                                                              \
+        if ((h) && (h)->bc) { (h)->err = what " is not available on a BC handle"; return FQL_E_STATE; } \
+    } while (0)
 #define FQL_REBRAC_REFUSES(h, what, why)                                                                                  \
     do {                                                                                                               \
         if ((h) && (h)->rebrac) { (h)->err = what " is not available on a ReBRAC handle (" why ")"; return FQL_E_STATE; } \
@@ -3703,7 +3945,7 @@ void fql_default_config(fql_config* c) {
 const char* fql_last_error(fql_handle h) { return h ? h->err.c_str() : g_create_error.c_str(); }
 
 static int create_engine(const fql_config* cfg, const fql_ifql_config* icfg, const fql_rebrac_config* rcfg, const fql_sac_config* scfg,
-                         uint64_t seed, fql_handle* out);
+                         uint64_t seed, fql_handle* out, const fql_bc_config* bcfg = nullptr);
 int fql_create(const fql_config* cfg, uint64_t seed, fql_handle* out) { return create_engine(cfg, nullptr, nullptr, nullptr, seed, out); }
 
 void fql_ifql_default_config(fql_ifql_config* c) {   // agents/ifql.py:231-250
@@ -3750,16 +3992,17 @@ int fql_sac_create(const fql_config* cfg, const fql_sac_config* scfg, uint64_t s
 static const char* k_sac_info_names[FQL_SAC_NUM_INFO] = {
     "critic/critic_loss", "critic/q_mean", "critic/q_max", "critic/q_min", "actor/total_loss", "actor/actor_loss", "actor/alpha_loss",
     "actor/alpha", "actor/entropy", "actor/std", "actor/q", "grad/max", "grad/min", "grad/norm"};
+static const char* k_bc_info_names[FQL_BC_NUM_INFO] = {"bc_loss", "grad/max", "grad/min", "grad/norm"};
 int fql_num_info(fql_handle h) {
-    return !h ? FQL_E_INVALID : h->ifql ? FQL_IFQL_NUM_INFO : h->rebrac ? FQL_REBRAC_NUM_INFO : h->sac ? FQL_SAC_NUM_INFO : FQL_NUM_INFO;
+    return !h ? FQL_E_INVALID : h->bc ? FQL_BC_NUM_INFO : h->ifql ? FQL_IFQL_NUM_INFO : h->rebrac ? FQL_REBRAC_NUM_INFO : h->sac ? FQL_SAC_NUM_INFO : FQL_NUM_INFO;
 }
 const char* fql_handle_info_name(fql_handle h, int i) {
     if (!h || i < 0 || i >= fql_num_info(h)) return nullptr;
-    return h->ifql ? k_ifql_info_names[i] : h->rebrac ? k_rebrac_info_names[i] : h->sac ? k_sac_info_names[i] : k_info_names[i];
+    return h->bc ? k_bc_info_names[i] : h->ifql ? k_ifql_info_names[i] : h->rebrac ? k_rebrac_info_names[i] : h->sac ? k_sac_info_names[i] : k_info_names[i];
 }
 
 static int create_engine(const fql_config* cfg, const fql_ifql_config* icfg, const fql_rebrac_config* rcfg, const fql_sac_config* scfg,
-                         uint64_t seed, fql_handle* out) {
+                         uint64_t seed, fql_handle* out, const fql_bc_config* bcfg) {
     if (!cfg || !out) { g_create_error = "cfg/out must not be NULL"; return FQL_E_INVALID; }
     *out = nullptr;
     if (icfg) {   // IFQL: state observations and fp32 only
@@ -3785,6 +4028,11 @@ static int create_engine(const fql_config* cfg, const fql_ifql_config* icfg, con
         if (!std::isnan(scfg->target_entropy) && !std::isfinite(scfg->target_entropy)) { g_create_error = "fql_sac_create: target_entropy must be finite or NaN (automatic)"; return FQL_E_INVALID; }
         if (std::isnan(scfg->target_entropy) && !std::isfinite(scfg->target_entropy_multiplier)) { g_create_error = "fql_sac_create: target_entropy_multiplier must be finite"; return FQL_E_INVALID; }
     }
+    if (bcfg) {   // BC: state observations and fp32 only
+        if (cfg->encoder != 0) { g_create_error = "fql_bc_create: visual encoders are not available for BC (encoder must be 0)"; return FQL_E_INVALID; }
+        if (cfg->precision != 0) { g_create_error = "fql_bc_create: BC runs in fp32 only (precision must be 0)"; return FQL_E_INVALID; }
+        if (bcfg->denoise_steps < 1 || bcfg->denoise_steps > 1024) { g_create_error = "fql_bc_create: denoise_steps must be in [1, 1024]"; return FQL_E_INVALID; }
+    }
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
         (void)hipGetLastError();
@@ -3797,6 +4045,7 @@ static int create_engine(const fql_config* cfg, const fql_ifql_config* icfg, con
         h->seed = seed;
         if (icfg) { h->ifql = true; h->expectile = icfg->expectile; h->num_samples = icfg->num_samples; }
         if (rcfg) { h->rebrac = true; h->rcfg = *rcfg; }
+        if (bcfg) { h->bc = true; h->bc_steps = bcfg->denoise_steps; }
         if (scfg) {   // sac.py create: target_entropy = -target_entropy_multiplier * action_dim when None
             h->sac = true; h->scfg = *scfg;
             h->target_entropy = std::isnan(scfg->target_entropy) ? -scfg->target_entropy_multiplier * (float)cfg->act_dim : scfg->target_entropy;
@@ -3836,6 +4085,23 @@ static int create_engine(const fql_config* cfg, const fql_ifql_config* icfg, con
         HIP_CHECK(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
         for (int l = 1; l < FQL_LANES; ++l) HIP_CHECK(hipStreamCreateWithFlags(&h->lane_streams[l], hipStreamNonBlocking));
         h->build_nets();
+        if (h->bc) {   // the timestep-embedding table, rows k = 0..S: freq_i = float32(exp_f64(-ln(10000) i / 8)),
+                       // arg = float32(float32(t 10000) freq_i), [cos | sin] in fp64 of that fp32 argument, rounded to fp32
+            const int S = h->bc_steps;
+            std::vector<float> tab((size_t)(S + 1) * BC_EMB);
+            for (int k = 0; k <= S; ++k) {
+                const float t = (float)k / (float)S;
+                const float ts = t * 10000.0f;
+                for (int i = 0; i < BC_EMB / 2; ++i) {
+                    const float freq = (float)std::exp(-std::log(10000.0) * (double)i / (double)(BC_EMB / 2));
+                    const float arg = ts * freq;
+                    tab[(size_t)k * BC_EMB + i] = (float)std::cos((double)arg);
+                    tab[(size_t)k * BC_EMB + BC_EMB / 2 + i] = (float)std::sin((double)arg);
+                }
+            }
+            HIP_CHECK(hipMalloc((void**)&h->d_emb, tab.size() * sizeof(float)));
+            HIP_CHECK(hipMemcpy(h->d_emb, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice));
+        }
         HIP_CHECK(hipMalloc((void**)&h->P, h->n_total * sizeof(float)));
         HIP_CHECK(hipMalloc((void**)&h->G, h->n_train * sizeof(float)));
         HIP_CHECK(hipMalloc((void**)&h->Mu, h->n_train * sizeof(float)));
@@ -3880,7 +4146,7 @@ int fql_destroy(fql_handle h) {
     for (auto& kv : h->evals) {
         for (void* p : kv.second->allocs) hipFree(p);
     }
-    hipFree(h->P); hipFree(h->G); hipFree(h->Mu); hipFree(h->Nu); hipFree(h->d_chunks); hipFree(h->d_partials); hipFree(h->d_leaf_range); hipFree(h->d_state); hipFree(h->d_src);
+    hipFree(h->P); hipFree(h->G); hipFree(h->Mu); hipFree(h->Nu); hipFree(h->d_chunks); hipFree(h->d_partials); hipFree(h->d_leaf_range); hipFree(h->d_state); hipFree(h->d_src); hipFree(h->d_emb);
     if (h->h_src_ring) hipHostFree(h->h_src_ring);
     if (h->h_info_ring) hipHostFree(h->h_info_ring);
     for (auto& e : h->info_ev) if (e) hipEventDestroy(e);
@@ -4019,6 +4285,7 @@ int fql_update_begin(fql_handle h, const float* obs, const float* act, const flo
                      const float* nobs, int batch_size, const fql_noise* noise, void* stream) {
     FQL_IFQL_REFUSES(h, "fql_update_begin");
     FQL_SAC_REFUSES(h, "fql_update_begin");
+    FQL_BC_REFUSES(h, "fql_update_begin");
     if (!h) return FQL_E_INVALID;
     FQL_TRY(h, {
         hipStream_t s = pick(h, stream);
@@ -4031,6 +4298,7 @@ int fql_update_begin(fql_handle h, const float* obs, const float* act, const flo
 int fql_update_end(fql_handle h, float* info13, void* stream) {
     FQL_IFQL_REFUSES(h, "fql_update_end");
     FQL_SAC_REFUSES(h, "fql_update_end");
+    FQL_BC_REFUSES(h, "fql_update_end");
     if (!h) return FQL_E_INVALID;
     if (!h->began) { h->err = "fql_update_end without fql_update_begin"; return FQL_E_STATE; }
     FQL_TRY(h, {
@@ -4044,6 +4312,7 @@ int fql_update(fql_handle h, const float* obs, const float* act, const float* re
                int batch_size, const fql_noise* noise, float* info13, void* stream) {
     FQL_REBRAC_REFUSES(h, "fql_update", "its batch has no next_actions: fql_rebrac_update");
     FQL_SAC_REFUSES(h, "fql_update");
+    FQL_BC_REFUSES(h, "fql_update");
     if (h && !h->began) {
         FQL_TRY_FAST(h, {
             hipStream_t s = pick(h, stream);
@@ -4082,6 +4351,7 @@ int fql_total_loss(fql_handle h, const float* obs, const float* act, const float
                    int batch_size, const fql_noise* noise, float* loss, float* info10, void* stream) {
     FQL_REBRAC_REFUSES(h, "fql_total_loss", "its batch has no next_actions: fql_rebrac_total_loss");
     FQL_SAC_REFUSES(h, "fql_total_loss");
+    FQL_BC_REFUSES(h, "fql_total_loss");
     if (!h) return FQL_E_INVALID;
     FQL_TRY(h, {
         hipStream_t s = pick(h, stream);
@@ -4101,6 +4371,7 @@ int fql_total_loss(fql_handle h, const float* obs, const float* act, const float
 }
 
 int fql_sample_actions(fql_handle h, const float* obs, int n, const float* noise, uint64_t seed, float* out, void* stream) {
+    FQL_BC_REFUSES(h, "fql_sample_actions (fql_bc_sample_actions)");
     if (!h) return FQL_E_INVALID;
     if (h->rebrac) FQL_TRY(h, h->rebrac_sample(obs, noise, seed, 1.0f, n, out, pick(h, stream), stream == nullptr));
     if (h->sac) FQL_TRY(h, h->sac_sample(obs, noise, seed, 1.0f, n, out, pick(h, stream), stream == nullptr));
@@ -4110,6 +4381,7 @@ int fql_sample_actions(fql_handle h, const float* obs, int n, const float* noise
 int fql_flow_actions(fql_handle h, const float* obs, const float* noises, int n, float* out, void* stream) {
     FQL_REBRAC_REFUSES(h, "fql_flow_actions", "the actor is deterministic, there is no flow");
     FQL_SAC_REFUSES(h, "fql_flow_actions");
+    FQL_BC_REFUSES(h, "fql_flow_actions");
     if (!h) return FQL_E_INVALID;
     FQL_TRY(h, h->eval_rows(true, obs, noises, 0, n, out, pick(h, stream), stream == nullptr));
 }
@@ -4167,6 +4439,7 @@ int fql_dataset_size(fql_handle h, int64_t* size, int64_t* pointer) {
 int fql_noise_from_jax_keys(fql_handle h, const uint32_t* keys10, int partitionable, int batch_size, fql_noise* out, void* stream) {
     FQL_IFQL_REFUSES(h, "fql_noise_from_jax_keys");
     FQL_SAC_REFUSES(h, "fql_noise_from_jax_keys");
+    FQL_BC_REFUSES(h, "fql_noise_from_jax_keys");
     if (!h || !keys10 || !out) return FQL_E_INVALID;
     FQL_TRY(h, {
         if (batch_size != h->B) invalid("batch_size %d does not match the engine's workspace (%d); call fql_set_batch_size", batch_size, h->B);
@@ -4219,6 +4492,7 @@ int fql_dataset_reserve(fql_handle h, int64_t capacity) {
 int fql_dataset_add_frames(fql_handle h, const uint8_t* frame, const uint8_t* next_frame, const float* ac, float reward, float mask) {
     FQL_IFQL_REFUSES(h, "fql_dataset_add_frames");
     FQL_SAC_REFUSES(h, "fql_dataset_add_frames");
+    FQL_BC_REFUSES(h, "fql_dataset_add_frames");
     if (!h) return FQL_E_INVALID;
     FQL_TRY(h, {
         if (!h->visual || !h->ds_frames) throw Invalid{"no frames dataset allocated (fql_dataset_upload_frames)"};
@@ -4231,6 +4505,7 @@ int fql_dataset_add_frames(fql_handle h, const uint8_t* frame, const uint8_t* ne
 }
 int fql_replay_create(fql_handle h, int64_t capacity) {
     FQL_IFQL_REFUSES(h, "fql_replay_create");
+    FQL_BC_REFUSES(h, "fql_replay_create");
     if (!h) return FQL_E_INVALID;
     FQL_TRY(h, {
         if (capacity < 1) invalid("fql_replay_create: capacity %lld", (long long)capacity);
@@ -4251,6 +4526,7 @@ int fql_replay_create(fql_handle h, int64_t capacity) {
 }
 int fql_replay_add(fql_handle h, const float* ob, const float* ac, float reward, float mask, const float* nob) {
     FQL_IFQL_REFUSES(h, "fql_replay_add");
+    FQL_BC_REFUSES(h, "fql_replay_add");
     if (!h) return FQL_E_INVALID;
     FQL_TRY(h, {
         if (h->rb_cap <= 0 || h->visual) throw Invalid{"fql_replay_add: no state replay ring (fql_replay_create; frames agents use fql_replay_add_frames)"};
@@ -4263,6 +4539,7 @@ int fql_replay_add(fql_handle h, const float* ob, const float* ac, float reward,
 int fql_replay_add_frames(fql_handle h, const uint8_t* frame, const uint8_t* next_frame, const float* ac, float reward, float mask) {
     FQL_IFQL_REFUSES(h, "fql_replay_add_frames");
     FQL_SAC_REFUSES(h, "fql_replay_add_frames");
+    FQL_BC_REFUSES(h, "fql_replay_add_frames");
     if (!h) return FQL_E_INVALID;
     FQL_TRY(h, {
         if (h->rb_cap <= 0 || !h->visual) throw Invalid{"fql_replay_add_frames: no frames replay ring (fql_replay_create on a frames agent)"};
@@ -4275,6 +4552,7 @@ int fql_replay_add_frames(fql_handle h, const uint8_t* frame, const uint8_t* nex
 }
 int fql_replay_size(fql_handle h, int64_t* size, int64_t* pointer) {
     FQL_IFQL_REFUSES(h, "fql_replay_size");
+    FQL_BC_REFUSES(h, "fql_replay_size");
     if (!h) return FQL_E_INVALID;
     if (size) *size = h->rb_size;
     if (pointer) *pointer = h->rb_ptr;
@@ -4284,6 +4562,7 @@ int fql_update_balanced(fql_handle h, const int64_t* idx_dataset, const int64_t*
                         const fql_noise* noise, float* info13, void* stream) {
     FQL_IFQL_REFUSES(h, "fql_update_balanced");
     FQL_SAC_REFUSES(h, "fql_update_balanced");
+    FQL_BC_REFUSES(h, "fql_update_balanced");
     if (!h) return FQL_E_INVALID;
     if (h->began) { h->err = "fql_update_balanced between fql_update_begin and fql_update_end"; return FQL_E_STATE; }
     FQL_TRY_FAST(h, {
@@ -4299,6 +4578,7 @@ int fql_update_from_dataset_begin(fql_handle h, const int64_t* idx, int batch_si
                                   const fql_noise* noise, void* stream) {
     FQL_IFQL_REFUSES(h, "fql_update_from_dataset_begin");
     FQL_SAC_REFUSES(h, "fql_update_from_dataset_begin");
+    FQL_BC_REFUSES(h, "fql_update_from_dataset_begin");
     if (!h) return FQL_E_INVALID;
     FQL_TRY(h, {
         hipStream_t s = pick(h, stream);
@@ -4312,6 +4592,7 @@ int fql_update_from_dataset_begin_split(fql_handle h, const int64_t* idx, int ba
                                         const fql_noise* noise, void* stream0, void* stream1) {
     FQL_IFQL_REFUSES(h, "fql_update_from_dataset_begin_split");
     FQL_SAC_REFUSES(h, "fql_update_from_dataset_begin_split");
+    FQL_BC_REFUSES(h, "fql_update_from_dataset_begin_split");
     if (!h) return FQL_E_INVALID;
     if (!h->split_ok || !stream0 || !stream1 || stream0 == stream1) { h->err = "split update unavailable (needs two distinct streams and a two-lane program)"; return FQL_E_STATE; }
     FQL_TRY(h, {
@@ -4324,6 +4605,7 @@ int fql_update_begin_split(fql_handle h, const float* obs, const float* act, con
                            int batch_size, const fql_noise* noise, void* stream0, void* stream1) {
     FQL_IFQL_REFUSES(h, "fql_update_begin_split");
     FQL_SAC_REFUSES(h, "fql_update_begin_split");
+    FQL_BC_REFUSES(h, "fql_update_begin_split");
     if (!h) return FQL_E_INVALID;
     if (!h->split_ok || !stream0 || !stream1 || stream0 == stream1) { h->err = "split update unavailable (needs two distinct streams and a two-lane program)"; return FQL_E_STATE; }
     FQL_TRY(h, {
@@ -4335,6 +4617,7 @@ int fql_update_begin_split(fql_handle h, const float* obs, const float* act, con
 int fql_update_end_split(fql_handle h, float* info13, void* stream0, void* stream1) {
     FQL_IFQL_REFUSES(h, "fql_update_end_split");
     FQL_SAC_REFUSES(h, "fql_update_end_split");
+    FQL_BC_REFUSES(h, "fql_update_end_split");
     if (!h) return FQL_E_INVALID;
     if (!h->began) { h->err = "fql_update_end_split without fql_update_begin"; return FQL_E_STATE; }
     if (!stream0 || !stream1 || stream0 == stream1) { h->err = "fql_update_end_split needs two distinct streams"; return FQL_E_STATE; }
@@ -4347,6 +4630,7 @@ int fql_update_end_split(fql_handle h, float* info13, void* stream0, void* strea
 int fql_grad_buckets(fql_handle h, size_t offsets[2], size_t lengths[2]) {
     FQL_IFQL_REFUSES(h, "fql_grad_buckets");
     FQL_SAC_REFUSES(h, "fql_grad_buckets");
+    FQL_BC_REFUSES(h, "fql_grad_buckets");
     if (!h || !offsets || !lengths) return FQL_E_INVALID;
     // bucket 0: both critic members + the BC flow actor (all produced on lane 1); bucket 1: the one-step actor (lane 0's tail)
     offsets[0] = 0; lengths[0] = h->nets[NET_OS].off;
@@ -4357,6 +4641,7 @@ int fql_update_from_dataset(fql_handle h, const int64_t* idx, int batch_size, in
                             float* info13, void* stream) {
     FQL_REBRAC_REFUSES(h, "fql_update_from_dataset", "the step kind is an argument: fql_rebrac_update_from_dataset");
     FQL_SAC_REFUSES(h, "fql_update_from_dataset");
+    FQL_BC_REFUSES(h, "fql_update_from_dataset");
     if (h && h->visual) return fql_update_from_frames(h, idx, nullptr, batch_size, lo, hi, noise, info13, stream);
     if (h && !h->began) {
         FQL_TRY_FAST(h, {
@@ -4386,6 +4671,7 @@ int fql_info_enqueue(fql_handle h, void* stream, uint64_t* ticket) {
 static int info_wait(fql_handle h, uint64_t ticket, float* info13_host, int n);
 int fql_info_wait(fql_handle h, uint64_t ticket, float* info13_host) {
     FQL_SAC_REFUSES(h, "fql_info_wait (14 infos: fql_info_wait_n)");
+    FQL_BC_REFUSES(h, "fql_info_wait (4 infos: fql_info_wait_n)");
     return info_wait(h, ticket, info13_host, FQL_NUM_INFO);
 }
 int fql_info_wait_n(fql_handle h, uint64_t ticket, float* out, int n) {
@@ -4415,6 +4701,7 @@ int fql_synchronize(fql_handle h, int* mode) {
 
 int fql_read_info(fql_handle h, float* info13_host) {
     FQL_SAC_REFUSES(h, "fql_read_info (14 infos: fql_read_info_n)");
+    FQL_BC_REFUSES(h, "fql_read_info (4 infos: fql_read_info_n)");
     if (!h || !info13_host) return FQL_E_INVALID;
     FQL_TRY(h, {
         HIP_CHECK(hipDeviceSynchronize());
@@ -4566,6 +4853,64 @@ int fql_sac_stats(fql_handle h, int64_t* launches_per_update, int64_t* macs_per_
     return FQL_OK;
 }
 
+// ---- BC (agents/bc.py): flow-matching behavioural cloning -------------------------------------------------------------------------
+// One update through run_update (the AQL form and the graph are bitwise equal); 4 infos.
+#define FQL_BC_ONLY(h, what)                                                                          \
+    do {                                                                                            \
+        if (!(h)) return FQL_E_INVALID;                                                             \
+        if (!(h)->bc) { (h)->err = what " needs a BC handle (fql_bc_create)"; return FQL_E_STATE; } \
+    } while (0)
+void fql_bc_default_config(fql_bc_config* c) {   // agents/bc.py:135-148
+    std::memset(c, 0, sizeof *c);
+    c->denoise_steps = 16;
+}
+int fql_bc_create(const fql_config* cfg, const fql_bc_config* bcfg, uint64_t seed, fql_handle* out) {
+    if (!bcfg) { g_create_error = "bcfg must not be NULL"; if (out) *out = nullptr; return FQL_E_INVALID; }
+    return create_engine(cfg, nullptr, nullptr, nullptr, seed, out, bcfg);
+}
+int fql_bc_update(fql_handle h, const float* obs, const float* act, int batch_size, const fql_noise* noise, float* info4, void* stream) {
+    FQL_BC_ONLY(h, "fql_bc_update");
+    FQL_TRY_FAST(h, {
+        hipStream_t s = pick(h, stream);
+        h->bc_source_from_batch(obs, act, batch_size, noise, 1, s);
+        run_update(h, h->prog_full, s, stream == nullptr);
+        h->finish_info(info4, FQL_BC_NUM_INFO, s);
+    });
+}
+int fql_bc_update_from_dataset(fql_handle h, const int64_t* idx, int batch_size, int64_t lo, int64_t hi, const fql_noise* noise,
+                               float* info4, void* stream) {
+    FQL_BC_ONLY(h, "fql_bc_update_from_dataset");
+    FQL_TRY_FAST(h, {
+        hipStream_t s = pick(h, stream);
+        h->source_from_dataset(idx, batch_size, lo, hi, noise, s);
+        run_update(h, h->prog_full, s, stream == nullptr);
+        h->finish_info(info4, FQL_BC_NUM_INFO, s);
+    });
+}
+int fql_bc_policy_loss(fql_handle h, const float* obs, const float* act, int batch_size, const fql_noise* noise, float* loss, void* stream) {
+    FQL_BC_ONLY(h, "fql_bc_policy_loss");
+    FQL_TRY(h, {
+        hipStream_t s = pick(h, stream);
+        h->bc_source_from_batch(obs, act, batch_size, noise, 0, s);
+        run_program(h, h->prog_loss, s);   // writes info slot 5 only: the four slots fql_read_info_n reads stay the last update's
+        float v = 0.f;
+        HIP_CHECK(hipMemcpyAsync(&v, &h->d_state->info[BC_I_LOSS], sizeof v, hipMemcpyDeviceToHost, s));
+        HIP_CHECK(hipStreamSynchronize(s));
+        if (loss) *loss = v;
+    });
+}
+int fql_bc_sample_actions(fql_handle h, const float* obs, int n, const float* noise, uint64_t seed, float* out, void* stream) {
+    FQL_BC_ONLY(h, "fql_bc_sample_actions");
+    FQL_TRY(h, h->bc_sample(obs, noise, seed, n, out, pick(h, stream), stream == nullptr));
+}
+int fql_bc_stats(fql_handle h, int64_t* launches_per_update, int64_t* macs_per_update, int64_t* launches_per_sample) {
+    FQL_BC_ONLY(h, "fql_bc_stats");
+    if (launches_per_update) *launches_per_update = (int64_t)h->prog_full.launches.size();
+    if (macs_per_update) *macs_per_update = h->bc_macs();
+    if (launches_per_sample) *launches_per_sample = 4 + (int64_t)h->bc_steps * h->nets[NET_BC].nl();   // assemble, step-bias table, C0, S (layer 0 + nh GEMMs), extract
+    return FQL_OK;
+}
+
 }  // extern "C"
 
 // Per-launch device times of ONE update, measured with HIP events on the engine's stream (used by bench.py for the per-kernel
@@ -4578,6 +4923,7 @@ int fql_sac_stats(fql_handle h, int64_t* launches_per_update, int64_t* macs_per_
 extern "C" int fql_profile_update(fql_handle h, int batch_size, int cap, int* type, int* lane, int* grid, float* us, double* macs, float* null_us) {
     FQL_REBRAC_REFUSES(h, "fql_profile_update", "FQL batch sources only");
     FQL_SAC_REFUSES(h, "fql_profile_update");
+    FQL_BC_REFUSES(h, "fql_profile_update");
     if (!h || !type || !us) return FQL_E_INVALID;
     try {
         require_graph(h->prog_full);
@@ -4615,6 +4961,7 @@ extern "C" int fql_profile_update(fql_handle h, int batch_size, int cap, int* ty
 extern "C" int fql_debug_workspace(fql_handle h, int which, void* out, size_t bytes, int* dims) {
     FQL_REBRAC_REFUSES(h, "fql_debug_workspace", "FQL workspaces only");
     FQL_SAC_REFUSES(h, "fql_debug_workspace");
+    FQL_BC_REFUSES(h, "fql_debug_workspace");
     if (!h || !out) return FQL_E_INVALID;
     const int B = h->B, ic = h->nets[NET_OS].in_p(), ib = h->nets[NET_BC].in_p(), ap = pad16(h->cfg.act_dim);
     const void* src = nullptr;
@@ -4747,6 +5094,7 @@ int fql_dataset_upload_frames(fql_handle h, int64_t n, const uint8_t* frames, co
                               const float* rew, const float* mask, const float* terminals, int frame_stack, float p_aug) {
     FQL_IFQL_REFUSES(h, "fql_dataset_upload_frames");
     FQL_SAC_REFUSES(h, "fql_dataset_upload_frames");
+    FQL_BC_REFUSES(h, "fql_dataset_upload_frames");
     if (!h) return FQL_E_INVALID;
     FQL_TRY(h, {
         if (!h->visual) throw Invalid{"fql_dataset_upload_frames needs an agent created with an encoder"};
@@ -4791,6 +5139,7 @@ int fql_update_from_frames(fql_handle h, const int64_t* idx, const int32_t* crop
                            const fql_noise* noise, float* info13, void* stream) {
     FQL_IFQL_REFUSES(h, "fql_update_from_frames");
     FQL_SAC_REFUSES(h, "fql_update_from_frames");
+    FQL_BC_REFUSES(h, "fql_update_from_frames");
     if (!h) return FQL_E_INVALID;
     FQL_TRY(h, {
         hipStream_t s = pick(h, stream);
@@ -5013,9 +5362,9 @@ int fql_group_create(const fql_handle* members, int k, fql_group* out) {
     if (!out) { g_create_error = "fql_group_create: out must not be NULL"; return FQL_E_INVALID; }
     *out = nullptr;
     for (int i = 0; members && i < k; ++i)
-        if (members[i] && (members[i]->ifql || members[i]->rebrac || members[i]->sac)) {
+        if (members[i] && (members[i]->ifql || members[i]->rebrac || members[i]->sac || members[i]->bc)) {
             g_create_error = "fql_group_create: member " + std::to_string(i) +
-                             (members[i]->ifql ? " is an IFQL handle" : members[i]->rebrac ? " is a ReBRAC handle" : " is a SAC handle") +
+                             (members[i]->ifql ? " is an IFQL handle" : members[i]->rebrac ? " is a ReBRAC handle" : members[i]->sac ? " is a SAC handle" : " is a BC handle") +
                              " (groups take FQL agents only)";
             return FQL_E_STATE;
         }

@@ -150,6 +150,7 @@ enum : int {
                             // per tile: [M/16][N/16][q = (n % 16) / 4][c = m % 16][n % 4] (fql_chain_split_kernel variant A: lane (c, q) owns row c, columns 4 q ..)
     GF_C_FRAG = 1 << 18,    // gemm16 epilogue: C (+ bias) stored in accumulator-fragment-major layout [M/4][N][4] (one dwordx4 per lane;
                             // read back as one dwordx4 per MFMA tile by fql_chain_kernel variant A)
+    GF_EULER_BARE = 1 << 19, // with GF_EULER: aux holds the actions alone (no t column is written: BC's time enters through its step-bias table)
 };
 
 struct GemmTask {
@@ -782,7 +783,7 @@ __device__ __forceinline__ void gemm16_body(const GemmTask& T, float* lds) {
                 stg(xr + n, a);
                 if (flags & GF_EULER_LAST) stg(T.aux2 + (size_t)row * T.ldc + n, clip1(a));
             }
-            if (n == 0) stg(xr + T.i2, T.f1);
+            if (n == 0 && !(flags & GF_EULER_BARE)) stg(xr + T.i2, T.f1);
             continue;
         }
         if (flags & GF_SAVE_Z) { float gg, dg; gelu_both(v, gg, dg); stg(T.Zout + o, dg); v = (flags & GF_GELU) ? gg : v; }

@@ -439,6 +439,48 @@ int fql_sac_stats(fql_handle h, int64_t* launches_per_update, int64_t* macs_per_
 int fql_read_info_n(fql_handle h, float* out, int n);
 int fql_info_wait_n(fql_handle h, uint64_t ticket, float* out, int n);
 
+/* ---- BC (agents/bc.py): flow-matching behavioural cloning, the baseline agent and the one utils/train.py::train_bc_agent trains.
+ * State observations, fp32 only.  One network, a bare TrainState: policy(obs, x_t, emb(t)) = MLP(hidden, GELU, LayerNorm) + Dense(act).
+ * Leaves: "MLP_0/Dense_0..n-1/{bias,kernel}" (default_init kernels), "MLP_0/LayerNorm_i/{bias,scale}" with actor_layer_norm, and
+ * "Dense_0/{bias,kernel}" (the head: flax's default lecun_normal).  No target network; Adam over the whole tree.
+ * fql_config mapping: hidden_dims = actor_hidden / num_actor_hidden, use_layer_norm = actor_layer_norm, bc_lr = lr; the value_* fields,
+ * layer_norm, discount, tau, alpha, q_agg, normalize_q_loss and flow_steps are ignored (num_value_hidden must still be in range).
+ * Timestep embedding: t = k / S, k in 0..S (S = denoise_steps); emb = [cos(arg_i) | sin(arg_i)], i = 0..7,
+ * arg_i = float32(float32(t * 10000) * freq_i), freq_i = float32(exp(-ln(10000) * i / 8) in fp64), cos / sin in fp64 of that fp32
+ * argument; the [(S + 1), 16] table is built on the host at create.
+ * Infos: 4 floats (FQL_BC_NUM_INFO, fql_handle_info_name): 0 bc_loss 1 grad/max 2 grad/min 3 grad/norm.  The update calls write 4
+ * floats to info4 (NULL: read later with fql_read_info_n / fql_info_wait_n); fql_read_info and fql_info_wait return FQL_E_STATE.
+ * fql_noise: only x0 [B, act] (raw N(0, 1)) and t [B] are read; t must lie on the grid {0, 1/S, ..., 1} and is read as round(t S)
+ * (a host t off the grid is FQL_E_INVALID); any other non-NULL pointer is FQL_E_INVALID.  NULL = the engine's Philox tensors 2 and 3.
+ * A BC handle is an ordinary fql_handle for destroy, set_batch_size, leaf / param / opt-state / step access, dataset upload / add /
+ * reserve / size, info enqueue / fql_info_wait_n / fql_read_info_n, fql_synchronize, fql_stats and fql_stream.  Refused: encoder != 0
+ * or precision != 0 at create (FQL_E_INVALID); on a BC handle fql_update*, fql_update_begin* / _end*, fql_total_loss,
+ * fql_sample_actions, fql_flow_actions, fql_grad_buckets, frame uploads / updates, fql_replay_*, fql_update_balanced,
+ * fql_noise_from_jax_keys, fql_read_info, fql_info_wait and every fql_rebrac_* / fql_sac_* call return FQL_E_STATE, and
+ * fql_group_create with a BC member returns FQL_E_STATE.  The fql_bc_* calls on another handle return FQL_E_STATE. */
+#define FQL_BC_NUM_INFO 4
+typedef struct fql_bc_config {
+    int32_t denoise_steps;            /* S: grid of t and Euler steps of sample_actions (16) */
+    int32_t reserved[7];
+} fql_bc_config;
+void fql_bc_default_config(fql_bc_config* c);
+int fql_bc_create(const fql_config* cfg, const fql_bc_config* bcfg, uint64_t seed, fql_handle* out);
+/* BCAgent.update(batch)  agents/bc.py:72-84: observations [B, obs], actions [B, act]. */
+int fql_bc_update(fql_handle h, const float* observations, const float* actions, int batch_size, const fql_noise* noise, float* info4,
+                  void* stream);
+/* train_dataset.sample(B) + update(batch) on the device; idx / lo / hi as fql_update_from_dataset's. */
+int fql_bc_update_from_dataset(fql_handle h, const int64_t* idx, int batch_size, int64_t lo, int64_t hi, const fql_noise* noise,
+                               float* info4, void* stream);
+/* BCAgent.policy_loss(batch): pure forward, no state change (parameters, moments, counters and the info slots that fql_read_info_n
+ * reads are as the last update left them).  Synchronous. */
+int fql_bc_policy_loss(fql_handle h, const float* observations, const float* actions, int batch_size, const fql_noise* noise, float* loss,
+                       void* stream);
+/* BCAgent.sample_actions(observations, seed): x ~ N(0, I); S times x += policy(obs, x, i / S) / S; clip to [-1, 1].  noise [n, act] or
+ * NULL (engine RNG keyed by `seed`); rows of one call equal single calls with the same noise rows. */
+int fql_bc_sample_actions(fql_handle h, const float* observations, int n, const float* noise, uint64_t seed, float* out, void* stream);
+/* launches and algorithmic MACs of one update; launches of one sampling call of <= 4096 rows */
+int fql_bc_stats(fql_handle h, int64_t* launches_per_update, int64_t* macs_per_update, int64_t* launches_per_sample);
+
 #ifdef __cplusplus
 }
 #endif
