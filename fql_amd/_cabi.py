@@ -19,6 +19,8 @@ FQL_REBRAC_NUM_INFO = 12
 FQL_REBRAC_CRITIC_NUM_INFO = 7
 FQL_SAC_NUM_INFO = 14
 FQL_BC_NUM_INFO = 4
+FQL_IQL_AWR_NUM_INFO = 16
+FQL_IQL_DDPGBC_NUM_INFO = 19
 FQL_OK, FQL_E_INVALID, FQL_E_NODEVICE, FQL_E_HIP, FQL_E_STATE, FQL_E_NOTFOUND = 0, -1, -2, -3, -4, -5
 
 
@@ -48,6 +50,11 @@ class FqlSacConfig(C.Structure):
     _fields_ = [('target_entropy', C.c_float), ('target_entropy_multiplier', C.c_float), ('tanh_squash', C.c_int32),
                 ('state_dependent_std', C.c_int32), ('actor_fc_scale', C.c_float), ('backup_entropy', C.c_int32),
                 ('reserved', C.c_int32 * 6)]
+
+
+class FqlIqlConfig(C.Structure):
+    _fields_ = [('expectile', C.c_float), ('alpha', C.c_float), ('actor_loss', C.c_int32), ('const_std', C.c_int32),
+                ('reserved', C.c_int32 * 8)]
 
 
 class FqlBcConfig(C.Structure):
@@ -141,6 +148,13 @@ SYMBOLS = {
     'fql_bc_policy_loss': (_I, [_VP, _VP, _VP, _I, C.POINTER(FqlNoise), C.POINTER(_F), _VP]),
     'fql_bc_sample_actions': (_I, [_VP, _VP, _I, _VP, _U64, _VP, _VP]),
     'fql_bc_stats': (_I, [_VP, C.POINTER(_I64), C.POINTER(_I64), C.POINTER(_I64)]),
+    'fql_iql_default_config': (None, [C.POINTER(FqlIqlConfig)]),
+    'fql_iql_create': (_I, [C.POINTER(FqlConfig), C.POINTER(FqlIqlConfig), _U64, C.POINTER(_VP)]),
+    'fql_iql_update': (_I, [_VP] + _BATCH + [C.POINTER(FqlNoise), _VP, _VP]),
+    'fql_iql_update_from_dataset': (_I, [_VP, _VP, _I, _I64, _I64, C.POINTER(FqlNoise), _VP, _VP]),
+    'fql_iql_total_loss': (_I, [_VP] + _BATCH + [C.POINTER(FqlNoise), C.POINTER(_F), C.POINTER(_F), _VP]),
+    'fql_iql_sample_actions': (_I, [_VP, _VP, _I, _VP, _U64, _F, _VP, _VP]),
+    'fql_iql_stats': (_I, [_VP, C.POINTER(_I64), C.POINTER(_I64)]),
     'fql_read_info_n': (_I, [_VP, _VP, _I]),
     'fql_info_wait_n': (_I, [_VP, _U64, _VP, _I]),
 }

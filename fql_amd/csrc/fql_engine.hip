@@ -18,6 +18,7 @@
 #include "fql_rebrac.h"
 #include "fql_sac.h"
 #include "fql_bc.h"
+#include "fql_iql.h"
 #include <hip/hip_ext.h>
 #include "fql_aql.h"
 
@@ -136,7 +137,9 @@ enum OpType { OP_GEMM, OP_GEMM64, OP_WGRAD, OP_LNBWD, OP_PREP, OP_POSTOS, OP_EUL
               // SAC (agents/sac.py) only: after ReBRAC's
               OP_SAC_PREP, OP_SAC_ACT, OP_SAC_LOSS_C, OP_SAC_LOSS_A, OP_SAC_AGRAD, OP_SAC_FIN,
               // BC (agents/bc.py) only: after SAC's
-              OP_BC_PREP, OP_BC_FIN, OP_BC_STEPBIAS, OP_BC_LAYER0, OP_NUM_TYPES };
+              OP_BC_PREP, OP_BC_FIN, OP_BC_STEPBIAS, OP_BC_LAYER0,
+              // IQL (agents/iql.py) only: after BC's
+              OP_IQL_PREP, OP_IQL_HEAD, OP_IQL_LOSS_AWR, OP_IQL_LOSS_DDPGBC, OP_IQL_AGRAD, OP_IQL_FIN, OP_NUM_TYPES };
 
 struct Op {
     OpType type;
@@ -173,6 +176,11 @@ struct Op {
     BcPrepArgs bprep;
     BcStepBiasArgs bsb;
     BcLayer0Args bl0;
+    IqlPrepArgs qprep;
+    IqlHeadArgs qhead;
+    IqlAwrArgs qawr;
+    IqlDdpgArgs qddpg;
+    IqlActorGradArgs qag;
     ChainArgs chain;
     const ConvWprepTask* wprep_tasks = nullptr;
     int wprep_n = 0;
@@ -351,6 +359,15 @@ struct fql_engine {
     int bc_steps = 16;            // denoise_steps S
     float* d_emb = nullptr;       // [(S + 1), 16] timestep-embedding table (built on the host at create)
     bool lane0_64 = false;        // while the BC update program is built: lane 0 takes the 64-column LDS-tiled kernels and keeps its weight gradients
+    // IQL agent (agents/iql.py; fql_iql_create): NET_OS holds the value net and the critic pair and its target sit where IFQL's do; NET_BC
+    // is the Gaussian actor (actor_net + mean_net, obs -> act) and modules_actor/log_stds ([act], const_std = 0 only) follows the value
+    // net at ls_off, padded to ap floats.  p_v, p_c1[], p_ct[] as IFQL's; p_a is the actor on obs; ddpgbc adds p_q[], the critic pair on
+    // [obs | q_actions].  The infos (16 or 19) live in iql_info: [0, 32) of the last update, [32, 64) of the last loss probe.
+    bool iql = false;
+    fql_iql_config qcfg{};
+    size_t ls_off = 0;
+    float *se_buf = nullptr, *ls_part = nullptr;   // [B]: squared error per row; [B, ap]: per-row terms of the log_stds gradient
+    float* iql_info = nullptr;
     uint64_t seed = 0;
     int device = 0;
     hipStream_t stream = nullptr;
@@ -484,7 +501,7 @@ struct fql_engine {
     // lazily read infos (the reference returns device scalars that are only read at log time, main.py:276): a ring of pinned host
     // slots, one asynchronous 52-byte copy + event per ticket
     static constexpr int kInfoRing = 64;
-    float (*h_info_ring)[16] = nullptr;
+    float (*h_info_ring)[32] = nullptr;
     hipEvent_t info_ev[kInfoRing] = {};
     uint64_t info_seq = 0;
 
@@ -518,10 +535,10 @@ struct fql_engine {
         nets[NET_C0] = bc ? Net{} : make(od + ad, cfg.value_hidden, cfg.num_value_hidden, 1, cfg.layer_norm != 0);
         nets[NET_C1] = nets[NET_C0];
         nets[NET_BC] = bc ? make(od + ad + BC_EMB, cfg.actor_hidden, cfg.num_actor_hidden, ad, cfg.actor_layer_norm != 0)   // policy(obs, x_t, emb(t)) (agents/bc.py:26-44)
-                     : rebrac ? make(od, cfg.actor_hidden, cfg.num_actor_hidden, ad, cfg.actor_layer_norm != 0)   // actor (utils/networks.py:82-150)
+                     : (rebrac || iql) ? make(od, cfg.actor_hidden, cfg.num_actor_hidden, ad, cfg.actor_layer_norm != 0)   // actor (utils/networks.py:82-150)
                      : sac ? make(od, cfg.actor_hidden, cfg.num_actor_hidden, 2 * pad16(ad), cfg.actor_layer_norm != 0)   // actor_net + [mean_net | log_std_net]
                               : make(od + ad + 1, cfg.actor_hidden, cfg.num_actor_hidden, ad, cfg.actor_layer_norm != 0);
-        nets[NET_OS] = (rebrac || sac || bc) ? Net{} : ifql ? make(od, cfg.value_hidden, cfg.num_value_hidden, 1, cfg.layer_norm != 0)   // value (agents/ifql.py:188-193)
+        nets[NET_OS] = (rebrac || sac || bc) ? Net{} : (ifql || iql) ? make(od, cfg.value_hidden, cfg.num_value_hidden, 1, cfg.layer_norm != 0)   // value (agents/ifql.py:188-193)
                             : make(od + ad, cfg.actor_hidden, cfg.num_actor_hidden, ad, cfg.actor_layer_norm != 0);
         nets[NET_T0] = nets[NET_C0];
         nets[NET_T1] = nets[NET_C0];
@@ -575,6 +592,7 @@ struct fql_engine {
             if (ni == NET_OS) {
                 place_enc(ENC_OS);
                 if (sac) { alpha_off = off; off += 4; }   // modules_alpha/log_value: one float, padded to an Adam quad
+                if (iql && !qcfg.const_std) { ls_off = off; off += pad16(ad); }   // modules_actor/log_stds: [act], padded to ap
                 n_train = off;
             }
             if (ni == NET_T1) place_enc(ENC_T);
@@ -629,7 +647,7 @@ struct fql_engine {
         const Net& n = nets[NET_BC];
         const int nh = n.nl() - 1;
         const int H = n.layers[0].out_p;
-        bool ok = !ifql && !rebrac && !sac && !bc && !cfg.actor_layer_norm && cfg.act_dim <= 15 && nh >= 3 && (H == 256 || H == 512);   // (IFQL has no Euler chain in its update)
+        bool ok = !ifql && !rebrac && !sac && !bc && !iql && !cfg.actor_layer_norm && cfg.act_dim <= 15 && nh >= 3 && (H == 256 || H == 512);   // (IFQL has no Euler chain in its update)
         for (int l = 0; l < nh && ok; ++l) ok = n.layers[l].out == H && n.layers[l].out_p == H;
         use_chain = ok;
         if (!ok) return;
@@ -682,7 +700,12 @@ struct fql_engine {
                                  {"modules_alpha", "", -1, -1, true, ENC_BC},
                                  {"modules_critic", "value_net", NET_C0, NET_C1, true, ENC_C},
                                  {"modules_target_critic", "value_net", NET_T0, NET_T1, false, ENC_T}};
-        const Mod* mods = sac ? sac_mods : rebrac ? rebrac_mods : ifql ? ifql_mods : fql_mods;
+        // IQL (agents/iql.py:222-227): Actor (actor_net, log_stds with const_std = 0, mean_net), critic, target critic, the 1-member value
+        const Mod iql_mods[4] = {{"modules_actor", "actor_net", NET_BC, -1, true, ENC_BC, true},
+                                 {"modules_critic", "value_net", NET_C0, NET_C1, true, ENC_C},
+                                 {"modules_target_critic", "value_net", NET_T0, NET_T1, false, ENC_T},
+                                 {"modules_value", "value_net", NET_OS, -1, true, ENC_OS}};
+        const Mod* mods = iql ? iql_mods : sac ? sac_mods : rebrac ? rebrac_mods : ifql ? ifql_mods : fql_mods;
         int tid = 0;
         if (bc) {   // agents/bc.py:26-44: a bare TrainState: Dense_0 (the head), then MLP_0/Dense_i and MLP_0/LayerNorm_i (jax dict order)
             const Net& n0 = nets[NET_BC];
@@ -795,6 +818,8 @@ struct fql_engine {
                     leaves.back().segs[0].chunk_w = ap;
                 }
             } else if (m.actor) {
+                if (iql && !qcfg.const_std)   // "log_stds" sorts between actor_net and mean_net
+                    add(std::string(m.name) + "/log_stds", false, 1, cfg.act_dim, ls_off, 0, 1, pad16(cfg.act_dim));
                 const Layer& a = n0.layers.back();
                 const std::string hb = std::string(m.name) + "/mean_net/";
                 add(hb + "bias", false, 1, a.out, a.b, 0, 1, a.out_p);
@@ -828,7 +853,8 @@ struct fql_engine {
             const char* imods[3] = {"modules_actor_flow/", "modules_value/", "modules_critic/"};
             const char* rmods[3] = {"modules_actor/", "modules_critic/", "modules_critic/"};   // (two trained modules: the critic's range twice)
             const char* smods[3] = {"modules_actor/", "modules_alpha/", "modules_critic/"};
-            const char* const* mods = sac ? smods : rebrac ? rmods : ifql ? imods : fmods;
+            const char* qmods[3] = {"modules_actor/", "modules_value/", "modules_critic/"};
+            const char* const* mods = iql ? qmods : sac ? smods : rebrac ? rmods : ifql ? imods : fmods;
             for (int m = 0; m < 3; ++m) {
                 if (bc) { mod_chunk0[m] = 0; mod_chunkn[m] = n_chunks; continue; }   // one module: every chunk
                 int lo = 1 << 30, hi = -1;
@@ -874,7 +900,9 @@ struct fql_engine {
         for (int ni = 0; ni <= NET_OS; ++ni)
             for (const Layer& L : nets[ni].layers) {
                 // ReBRAC's mean_net: variance_scaling(actor_fc_scale, fan_avg, uniform) (utils/networks.py:9-11,117)
-                const double scale = (rebrac && ni == NET_BC && &L == &nets[ni].layers.back()) ? (double)rcfg.actor_fc_scale : 1.0;
+                const double scale = (rebrac && ni == NET_BC && &L == &nets[ni].layers.back()) ? (double)rcfg.actor_fc_scale
+                                     : (iql && ni == NET_BC && &L == &nets[ni].layers.back()) ? 1e-2   // Actor.final_fc_init_scale (utils/networks.py:106)
+                                                                                               : 1.0;
                 if (bc && &L == &nets[ni].layers.back()) {
                     // BC's Dense_0 is a bare nn.Dense (agents/bc.py:43): flax's default lecun_normal = variance_scaling(1, fan_in,
                     // truncated_normal): N(0, 1) truncated to [-2, 2], scaled by sqrt(1 / fan_in) / 0.87962566103423978
@@ -2187,6 +2215,26 @@ struct fql_engine {
                 FQL_LAUNCH(fql_sac_finalize_kernel, dim3(1), dim3(FQL_THREADS), 0, s,
                                    FinalizeArgs{d_state, d_chunks, d_partials, d_leaf_range, n_chunks, n_train_leaves, L.op.fin_mode & 1, tl});
                 break;
+            case OP_IQL_PREP:
+                FQL_LAUNCH(fql_iql_prep_kernel, dim3((L.op.qprep.B + 3) / 4), dim3(FQL_THREADS), 0, s, L.op.qprep);
+                break;
+            case OP_IQL_HEAD:
+                FQL_LAUNCH(fql_iql_head_kernel, dim3((L.op.qhead.B + FQL_THREADS - 1) / FQL_THREADS), dim3(FQL_THREADS), 0, s, L.op.qhead);
+                break;
+            case OP_IQL_LOSS_AWR:
+                FQL_LAUNCH(fql_iql_loss_awr_kernel, dim3(1), dim3(FQL_THREADS), 0, s, L.op.qawr);
+                break;
+            case OP_IQL_LOSS_DDPGBC:
+                FQL_LAUNCH(fql_iql_loss_ddpgbc_kernel, dim3(1), dim3(FQL_THREADS), 0, s, L.op.qddpg);
+                break;
+            case OP_IQL_AGRAD:
+                FQL_LAUNCH(fql_iql_actor_grad_kernel, dim3(1), dim3(FQL_THREADS), 0, s, L.op.qag);
+                break;
+            case OP_IQL_FIN:
+                FQL_LAUNCH(fql_iql_finalize_kernel, dim3(1), dim3(FQL_THREADS), 0, s,
+                                   IqlFinalizeArgs{FinalizeArgs{d_state, d_chunks, d_partials, d_leaf_range, n_chunks, n_train_leaves, L.op.fin_mode & 1, tl},
+                                                   iql_info + ((L.op.fin_mode & 1) ? 0 : IQL_INFO_STRIDE), qcfg.actor_loss == 1 ? IQL_N_DDPGBC : IQL_N_AWR});
+                break;
             case OP_WGRAD: case OP_LNBWD: case OP_POSTOS: case OP_LOSS_CRITIC: case OP_LOSS_Q: case OP_LOSS_BC:   // (inside OP_GEMM64 launches)
             case OP_PEC: case OP_XCHAIN: case OP_NUM_TYPES:
                 throw HipError{"internal: op type " + std::to_string((int)L.type) + " has no launch of its own"};
@@ -3171,6 +3219,172 @@ struct fql_engine {
         return m * (int64_t)B;
     }
 
+    // ---------------------------------------------------------------------------------------
+    // the IQL update as a program (agents/iql.py:28-156).  No Euler chain: throughput work on the side lanes.
+    //   lane 0: batch assembly (+ eps); Adam + Polyak over every chunk and the finalize, behind both side lanes
+    //   lane 1: value on [obs ; next_obs] (2B rows) -> target pair -> value loss -> value backward (obs half); actor forward -> Gaussian head
+    //           (log_prob, squared error; ddpgbc: q_actions into [obs | .]); ddpgbc: critic pair on [obs | q_actions] -> actor loss
+    //   lane 2: critic pair forward -> critic loss (waits for value(next_obs) on lane 1) -> critic backward (parameter gradients only);
+    //           awr: the actor loss on the q1, q2 and v those forward passes left (no second pass); ddpgbc: the pair's input gradient ->
+    //           head gradient; then the actor's backward
+    // Edges between the forked lanes run 1 -> 2 only (see schedule()).  with_grads = false: the loss probe (no backward; its finalize
+    // writes the probe half of iql_info).
+    // ---------------------------------------------------------------------------------------
+    void build_iql_program(Program& pr, bool with_grads) {
+        const int od = cfg.obs_dim, ad = cfg.act_dim, ap = pad16(ad);
+        const int inp_v = nets[NET_OS].in_p(), inp_c = nets[NET_C0].in_p(), inp_a = nets[NET_BC].in_p();
+        const bool ddpg = qcfg.actor_loss == 1, has_ls = !qcfg.const_std;
+        DevState* st = d_state;
+        const void *I_V = &st->info[IFQL_I_VALUE], *I_C = &st->info[IFQL_I_CRITIC];
+        float* out = iql_info + (with_grads ? 0 : IQL_INFO_STRIDE);
+        const void* I_A = out + IQL_I_ACTOR;
+        const float* ls = has_ls ? P + ls_off : nullptr;
+        float* g_ls = has_ls && with_grads ? G + ls_off : nullptr;
+        float* eps = ddpg && has_ls ? w_eps : nullptr;
+        wide_tiles = true;
+        allow64 = true;
+        emit_lane = 0;
+        {
+            Op op{};
+            op.type = OP_IQL_PREP;
+            op.qprep = IqlPrepArgs{d_src, st, seed, B, od, ad, inp_v, inp_c, inp_a, ap, X_v, X_c1, X_a, X_q, w_act, eps, w_rew, w_mask};
+            op.writes = {X_v, X_c1, X_a, w_act, w_rew, w_mask};
+            if (X_q) op.writes.push_back(X_q);
+            if (eps) op.writes.push_back(eps);
+            push(pr, op);
+        }
+        emit_lane = 1;
+        emit_forward(pr, p_v, with_grads);                              // value(obs) iql.py:32, value(next_obs) iql.py:44
+        for (int e = 0; e < 2; ++e) emit_forward(pr, p_ct[e], false);   // target_critic(obs, actions) iql.py:30
+        {
+            Op op{};
+            op.type = OP_IFQL_LOSS_V;
+            op.iv = IfqlValueArgs{p_v.out, p_ct[0].out, p_ct[1].out, with_grads ? p_v.dz.back() : nullptr, st, B, qcfg.expectile};
+            op.reads = {p_v.out, p_ct[0].out, p_ct[1].out};
+            op.writes = {I_V};
+            if (with_grads) op.writes.push_back(p_v.dz.back());
+            push(pr, op);
+        }
+        if (with_grads) emit_backward(pr, p_v, 0, B, true, false);
+        emit_forward(pr, p_a, with_grads);                              // actor(obs) iql.py:69,85
+        {
+            Op op{};
+            op.type = OP_IQL_HEAD;                                      // log_prob(actions) iql.py:70,95; q_actions iql.py:86-89
+            op.qhead = IqlHeadArgs{p_a.out, ls, w_act, eps, lp_buf, se_buf, ddpg ? X_q : nullptr, B, od, ad, ap, inp_c};
+            op.reads = {p_a.out, w_act};
+            if (ls) op.reads.push_back(ls);
+            if (eps) op.reads.push_back(eps);
+            op.writes = {lp_buf, se_buf};
+            if (ddpg) op.writes.push_back(X_q);
+            push(pr, op);
+        }
+        if (ddpg) {
+            for (int e = 0; e < 2; ++e) emit_forward(pr, p_q[e], with_grads);   // critic(obs, q_actions), stored params  iql.py:90
+            Op op{};
+            op.type = OP_IQL_LOSS_DDPGBC;
+            op.qddpg = IqlDdpgArgs{p_q[0].out, p_q[1].out, lp_buf, se_buf, ls, with_grads ? p_q[0].dz.back() : nullptr,
+                                   with_grads ? p_q[1].dz.back() : nullptr, out, B, ad, qcfg.alpha};
+            op.reads = {p_q[0].out, p_q[1].out, lp_buf, se_buf};
+            if (ls) op.reads.push_back(ls);
+            op.writes = {I_A};
+            if (with_grads) { op.writes.push_back(p_q[0].dz.back()); op.writes.push_back(p_q[1].dz.back()); }
+            push(pr, op);
+        }
+        emit_lane = 2;
+        for (int e = 0; e < 2; ++e) emit_forward(pr, p_c1[e], with_grads);   // critic(obs, actions) iql.py:47 (and :62: the same numbers)
+        {
+            Op op{};
+            op.type = OP_IFQL_LOSS_C;
+            op.ic = IfqlCriticArgs{p_v.out + (size_t)B * nets[NET_OS].layers.back().out_p, p_c1[0].out, p_c1[1].out, w_rew, w_mask,
+                                   with_grads ? p_c1[0].dz.back() : nullptr, with_grads ? p_c1[1].dz.back() : nullptr, st, B, cfg.discount};
+            op.reads = {p_v.out, p_c1[0].out, p_c1[1].out, w_rew, w_mask};
+            op.writes = {I_C};
+            if (with_grads) { op.writes.push_back(p_c1[0].dz.back()); op.writes.push_back(p_c1[1].dz.back()); }
+            push(pr, op);
+        }
+        if (with_grads)
+            for (int e = 0; e < 2; ++e) emit_backward(pr, p_c1[e], 0, B, true, false);
+        if (!ddpg) {
+            Op op{};
+            op.type = OP_IQL_LOSS_AWR;
+            op.qawr = IqlAwrArgs{p_c1[0].out, p_c1[1].out, p_v.out, lp_buf, se_buf, p_a.out, w_act, ls, with_grads ? p_a.dz.back() : nullptr,
+                                 ls_part, g_ls, out, B, ad, ap, qcfg.alpha};
+            op.reads = {p_c1[0].out, p_c1[1].out, p_v.out, lp_buf, se_buf, p_a.out, w_act};
+            if (ls) op.reads.push_back(ls);
+            op.writes = {I_A};
+            if (with_grads) op.writes.push_back(p_a.dz.back());
+            if (g_ls) { op.writes.push_back(ls_part); op.writes.push_back(g_ls); }
+            push(pr, op);
+        } else if (with_grads) {
+            for (int e = 0; e < 2; ++e) emit_backward(pr, p_q[e], 0, B, false, true);   // dQ/da only: the critic's params get no gradient here
+            Op op{};
+            op.type = OP_IQL_AGRAD;
+            op.qag = IqlActorGradArgs{p_q[0].dx0, p_q[1].dx0, p_a.out, w_act, eps, ls, p_a.dz.back(), ls_part, g_ls, B, od, ad, ap, inp_c, qcfg.alpha};
+            op.reads = {p_q[0].dx0, p_q[1].dx0, p_a.out, w_act};
+            if (ls) op.reads.push_back(ls);
+            if (eps) op.reads.push_back(eps);
+            op.writes = {p_a.dz.back()};
+            if (g_ls) { op.writes.push_back(ls_part); op.writes.push_back(g_ls); }
+            push(pr, op);
+        }
+        if (with_grads) {
+            emit_backward(pr, p_a, 0, B, true, false);
+            adam_for(pr, 2, {NET_C0, NET_C1, NET_BC, NET_OS}, 0, -2);   // every chunk, one launch; Polyak from the pre-step critic (iql.py:154)
+            if (has_ls) {
+                Op& a = pr.ops.back();
+                a.reads.push_back(G + ls_off);
+                a.writes.push_back(P + ls_off);
+            }
+        }
+        Op f{};
+        f.type = OP_IQL_FIN;
+        f.fin_mode = with_grads ? 1 : 0;
+        f.reads = {I_V, I_C, I_A};
+        if (with_grads) for (int m = 0; m < 3; ++m) f.reads.push_back(d_partials + mod_chunk0[m] * 4);
+        f.writes = {out, st};
+        emit_lane = 0;
+        push(pr, f);
+    }
+
+    void build_iql_workspace() {
+        const int ap = pad16(cfg.act_dim);
+        const int inp_c = nets[NET_C0].in_p();
+        const bool ddpg = qcfg.actor_loss == 1;
+        auto& W = ws_allocs;
+        X_v = dalloc(W, (size_t)2 * B * nets[NET_OS].in_p());
+        X_c1 = dalloc(W, (size_t)B * inp_c);
+        X_a = dalloc(W, (size_t)B * nets[NET_BC].in_p());
+        X_q = ddpg ? dalloc(W, (size_t)B * inp_c) : nullptr;
+        w_act = dalloc(W, (size_t)B * ap); w_eps = dalloc(W, (size_t)B * ap); ls_part = dalloc(W, (size_t)B * ap);
+        lp_buf = dalloc(W, B); se_buf = dalloc(W, B);
+        w_rew = dalloc(W, B); w_mask = dalloc(W, B);
+        X_os = X_bc = X_eu = X_c2 = X_ct = X_e0 = C0 = Vpart = vel = tgt = X_t = X_ta = nullptr;
+        fused_euler = euler_finish_fused = false;
+        p_v = make_pass(W, NET_OS, 2 * B, X_v, true, false);
+        p_a = make_pass(W, NET_BC, B, X_a, true, false);
+        for (int e = 0; e < 2; ++e) {
+            p_c1[e] = make_pass(W, NET_C0 + e, B, X_c1, true, false);
+            p_ct[e] = make_pass(W, NET_T0 + e, B, X_c1, false, false);
+            if (ddpg) p_q[e] = make_pass(W, NET_C0 + e, B, X_q, true, true);
+        }
+        build_iql_program(prog_full, true);
+        build_iql_program(prog_loss, false);
+        for (Program* pr : {&prog_full, &prog_loss}) schedule(*pr, W);
+        for (Program* pr : {&prog_full, &prog_loss}) capture(*pr);
+        split_ok = false;
+        src_valid = false;
+    }
+    // multiply-accumulates of one IQL update per batch row, algorithmic (full GEMM shapes at the logical widths)
+    int64_t iql_macs() const {
+        auto macs = [&](const Net& n) { int64_t m = 0; for (const Layer& L : n.layers) m += (int64_t)L.in * L.out; return m; };
+        auto first = [&](const Net& n) { return (int64_t)n.layers[0].in * n.layers[0].out; };
+        const int64_t va = macs(nets[NET_OS]), ac = macs(nets[NET_BC]), cr = macs(nets[NET_C0]);
+        // value on 2B rows + its backward on B; target pair; critic pair forward + backward (no input gradient); actor forward + backward
+        int64_t m = 2 * va + (2 * va - first(nets[NET_OS])) + 2 * cr + 2 * cr + 2 * (2 * cr - first(nets[NET_C0])) + ac + (2 * ac - first(nets[NET_BC]));
+        if (qcfg.actor_loss == 1) m += 2 * cr + 2 * cr;   // ddpgbc: the pair on [obs | q_actions] forward + input gradient
+        return m * (int64_t)B;
+    }
+
     // multiply-accumulates of one ReBRAC update per batch row, algorithmic (full GEMM shapes)
     int64_t rebrac_macs(bool full_update) const {
         auto macs = [&](const Net& n) { int64_t m = 0; for (const Layer& L : n.layers) m += (int64_t)L.in * L.out; return m; };
@@ -3189,6 +3403,7 @@ struct fql_engine {
         if (rebrac) return rebrac_macs(true);
         if (sac) return sac_macs();
         if (bc) return bc_macs();
+        if (iql) return iql_macs();
         const int64_t os = macs(nets[NET_OS]), bc = macs(nets[NET_BC]), cr = macs(nets[NET_C0]);
         if (ifql) {   // value on 2B rows + its backward on B; target pair; critic pair forward + backward (no input gradient); actor_flow forward + backward
             const int64_t fwd = 2 * os + 4 * cr + bc;
@@ -3246,6 +3461,7 @@ struct fql_engine {
         if (rebrac) { in_nact = dalloc(W, (size_t)B * ad); build_rebrac_workspace(); return; }
         if (sac) { build_sac_workspace(); return; }
         if (bc) { build_bc_workspace(); return; }
+        if (iql) { build_iql_workspace(); return; }
         const int inp_c = nets[NET_OS].in_p(), inp_b = nets[NET_BC].in_p();
         X_os = dalloc(W, (size_t)3 * B * inp_c); X_bc = dalloc(W, (size_t)B * inp_b); X_eu = dalloc(W, (size_t)B * inp_b);
         X_c1 = dalloc(W, (size_t)B * inp_c); X_c2 = dalloc(W, (size_t)B * inp_c); X_ct = dalloc(W, (size_t)B * inp_c);
@@ -3399,6 +3615,7 @@ struct fql_engine {
         if (ifql && (nz->eps1 || nz->z || nz->eps2)) invalid("IFQL reads only x0 and t of fql_noise (eps1, z and eps2 must be NULL)");
         if (rebrac && (nz->x0 || nz->t || nz->z || nz->eps2)) invalid("ReBRAC reads only eps1 of fql_noise (x0, t, z and eps2 must be NULL)");
         if (sac && (nz->x0 || nz->t || nz->z)) invalid("SAC reads only eps1 and eps2 of fql_noise (x0, t and z must be NULL)");
+        if (iql && (nz->x0 || nz->t || nz->z || nz->eps2)) invalid("IQL reads only eps1 of fql_noise (x0, t, z and eps2 must be NULL)");
         if (bc && (nz->eps1 || nz->z || nz->eps2)) invalid("BC reads only x0 and t of fql_noise (eps1, z and eps2 must be NULL)");
         if (bc && nz->t && !is_device_ptr(nz->t))   // t = k / S on the grid (device pointers are the caller's to keep on it: read as round(t S))
             for (int b = 0; b < B; ++b) {
@@ -3512,13 +3729,15 @@ struct fql_engine {
         drain_staging(s);
         set_source(d, s);
     }
+    // where the infos of the last update are: DevState::info, or an IQL handle's own buffer
+    const float* info_src() const { return iql ? iql_info : &d_state->info[0]; }
     void finish_info(float* info, int n, hipStream_t s) {
         if (!info) return;
         hip_touch();
         if (is_device_ptr(info)) {
-            HIP_CHECK(hipMemcpyAsync(info, &d_state->info[0], n * sizeof(float), hipMemcpyDeviceToDevice, s));
+            HIP_CHECK(hipMemcpyAsync(info, info_src(), n * sizeof(float), hipMemcpyDeviceToDevice, s));
         } else {
-            HIP_CHECK(hipMemcpyAsync(info, &d_state->info[0], n * sizeof(float), hipMemcpyDeviceToHost, s));
+            HIP_CHECK(hipMemcpyAsync(info, info_src(), n * sizeof(float), hipMemcpyDeviceToHost, s));
             HIP_CHECK(hipStreamSynchronize(s));
         }
     }
@@ -3586,7 +3805,7 @@ struct fql_engine {
             evals[n_pad] = std::move(ev);
             return ref;
         }
-        if (rebrac || sac) {   // sample_actions: the actor's forward over the rows (prog_os on p_os; NET_OS is empty here)
+        if (rebrac || sac || iql) {   // sample_actions: the actor's forward over the rows (prog_os on p_os; NET_OS is empty here)
             ev->X = dalloc(W, (size_t)n_pad * nets[NET_BC].in_p());
             ev->st_obs = dalloc(W, (size_t)n_pad * od);
             ev->st_noise = dalloc(W, (size_t)n_pad * ad);
@@ -3740,6 +3959,35 @@ struct fql_engine {
             }
         }
     }
+    // IQL sample_actions (agents/iql.py:158-169): clip(mean + exp(clip(log_stds)) temperature eps, -1, 1).
+    // noise: [n, act] raw N(0, 1) or null (Philox keyed by (seed, sd), row numbers of the call: chunking does not change the draw)
+    void iql_sample(const float* obs, const float* noise, uint64_t sd, float temperature, int n, float* out, hipStream_t s, bool own_stream) {
+        if (n <= 0) invalid("n must be positive (got %d)", n);
+        if (!obs || !out) invalid("observations/out must not be NULL");
+        if (!(temperature >= 0.0f)) invalid("temperature must be >= 0");
+        const int od = cfg.obs_dim, ad = cfg.act_dim, ap = pad16(ad);
+        for (int start = 0; start < n; start += 4096) {
+            const int m = std::min(4096, n - start);
+            Eval& ev = get_eval(pad16(m));
+            const float* o = stage(obs + (size_t)start * od, ev.st_obs, (size_t)m * od, s);
+            const float* z = noise ? stage(noise + (size_t)start * ad, ev.st_noise, (size_t)m * ad, s) : nullptr;
+            drain_staging(s);
+            AssembleArgs aa{o, nullptr, ev.X, seed, sd, m, ev.n_pad, od, 0, nets[NET_BC].in_p()};   // [obs | 0]
+            hipLaunchKernelGGL(fql_assemble_kernel, dim3((ev.n_pad + 3) / 4), dim3(FQL_THREADS), 0, s, aa);
+            run_launches(ev.prog_os, s);
+            float* dst = out + (size_t)start * ad;
+            const bool dev_out = is_device_ptr(dst);
+            IqlSampleArgs sa{ev.p_os.out, qcfg.const_std ? nullptr : P + ls_off, z, dev_out ? dst : ev.st_out, seed, sd, m, ad, ap, start, temperature};
+            hipLaunchKernelGGL(fql_iql_sample_kernel, dim3((m * ad + FQL_THREADS - 1) / FQL_THREADS), dim3(FQL_THREADS), 0, s, sa);
+            HIP_CHECK(hipGetLastError());
+            if (!dev_out) {
+                HIP_CHECK(hipMemcpyAsync(dst, ev.st_out, (size_t)m * ad * sizeof(float), hipMemcpyDeviceToHost, s));
+                HIP_CHECK(hipStreamSynchronize(s));
+            } else if (own_stream) {
+                HIP_CHECK(hipStreamSynchronize(s));
+            }
+        }
+    }
     // BC sample_actions (agents/bc.py:86-101): x ~ N(0, I); S times x += policy(obs, x, i / S) / S; clip.  Rows are independent (16-row
     // tiles and per-element kernels, the same at every n), so row j of a call equals the single-observation call on the same noise.
     // noise: [n, act] or null (Philox keyed by (seed, sd) and the row number of the call: chunking does not change the draw)
@@ -3856,6 +4104,7 @@ struct fql_engine {
 #define FQL_SAC_REFUSES(h, what)                                                                          \
     do {                                                                                                \
         if ((h) && (h)->sac) { (h)->err = what " is not available on a SAC handle"; return FQL_E_STATE; } \
+        if ((h) && (h)->iql) { (h)->err = what " is not available on an IQL handle"; return FQL_E_STATE; } \
     } while (0)
 #define FQL_BC_REFUSES(h, what)                                                                        \
     do {                                                                                              \
@@ -3945,7 +4194,7 @@ void fql_default_config(fql_config* c) {
 const char* fql_last_error(fql_handle h) { return h ? h->err.c_str() : g_create_error.c_str(); }
 
 static int create_engine(const fql_config* cfg, const fql_ifql_config* icfg, const fql_rebrac_config* rcfg, const fql_sac_config* scfg,
-                         uint64_t seed, fql_handle* out, const fql_bc_config* bcfg = nullptr);
+                         uint64_t seed, fql_handle* out, const fql_bc_config* bcfg = nullptr, const fql_iql_config* qcfg = nullptr);
 int fql_create(const fql_config* cfg, uint64_t seed, fql_handle* out) { return create_engine(cfg, nullptr, nullptr, nullptr, seed, out); }
 
 void fql_ifql_default_config(fql_ifql_config* c) {   // agents/ifql.py:231-250
@@ -3993,16 +4242,24 @@ static const char* k_sac_info_names[FQL_SAC_NUM_INFO] = {
     "critic/critic_loss", "critic/q_mean", "critic/q_max", "critic/q_min", "actor/total_loss", "actor/actor_loss", "actor/alpha_loss",
     "actor/alpha", "actor/entropy", "actor/std", "actor/q", "grad/max", "grad/min", "grad/norm"};
 static const char* k_bc_info_names[FQL_BC_NUM_INFO] = {"bc_loss", "grad/max", "grad/min", "grad/norm"};
+static const char* k_iql_info_names[2][FQL_IQL_DDPGBC_NUM_INFO] = {
+    {"value/value_loss", "value/v_mean", "value/v_max", "value/v_min", "critic/critic_loss", "critic/q_mean", "critic/q_max", "critic/q_min",
+     "actor/actor_loss", "actor/adv", "actor/bc_log_prob", "actor/mse", "actor/std", "grad/max", "grad/min", "grad/norm", nullptr, nullptr, nullptr},
+    {"value/value_loss", "value/v_mean", "value/v_max", "value/v_min", "critic/critic_loss", "critic/q_mean", "critic/q_max", "critic/q_min",
+     "actor/actor_loss", "actor/q_loss", "actor/bc_loss", "actor/q_mean", "actor/q_abs_mean", "actor/bc_log_prob", "actor/mse", "actor/std",
+     "grad/max", "grad/min", "grad/norm"}};
 int fql_num_info(fql_handle h) {
+    if (h && h->iql) return h->qcfg.actor_loss == 1 ? FQL_IQL_DDPGBC_NUM_INFO : FQL_IQL_AWR_NUM_INFO;
     return !h ? FQL_E_INVALID : h->bc ? FQL_BC_NUM_INFO : h->ifql ? FQL_IFQL_NUM_INFO : h->rebrac ? FQL_REBRAC_NUM_INFO : h->sac ? FQL_SAC_NUM_INFO : FQL_NUM_INFO;
 }
 const char* fql_handle_info_name(fql_handle h, int i) {
     if (!h || i < 0 || i >= fql_num_info(h)) return nullptr;
+    if (h->iql) return k_iql_info_names[h->qcfg.actor_loss == 1 ? 1 : 0][i];
     return h->bc ? k_bc_info_names[i] : h->ifql ? k_ifql_info_names[i] : h->rebrac ? k_rebrac_info_names[i] : h->sac ? k_sac_info_names[i] : k_info_names[i];
 }
 
 static int create_engine(const fql_config* cfg, const fql_ifql_config* icfg, const fql_rebrac_config* rcfg, const fql_sac_config* scfg,
-                         uint64_t seed, fql_handle* out, const fql_bc_config* bcfg) {
+                         uint64_t seed, fql_handle* out, const fql_bc_config* bcfg, const fql_iql_config* qcfg) {
     if (!cfg || !out) { g_create_error = "cfg/out must not be NULL"; return FQL_E_INVALID; }
     *out = nullptr;
     if (icfg) {   // IFQL: state observations and fp32 only
@@ -4033,6 +4290,14 @@ static int create_engine(const fql_config* cfg, const fql_ifql_config* icfg, con
         if (cfg->precision != 0) { g_create_error = "fql_bc_create: BC runs in fp32 only (precision must be 0)"; return FQL_E_INVALID; }
         if (bcfg->denoise_steps < 1 || bcfg->denoise_steps > 1024) { g_create_error = "fql_bc_create: denoise_steps must be in [1, 1024]"; return FQL_E_INVALID; }
     }
+    if (qcfg) {   // IQL: state observations and fp32 only
+        if (cfg->encoder != 0) { g_create_error = "fql_iql_create: visual encoders are not available for IQL (encoder must be 0)"; return FQL_E_INVALID; }
+        if (cfg->precision != 0) { g_create_error = "fql_iql_create: IQL runs in fp32 only (precision must be 0)"; return FQL_E_INVALID; }
+        if (!(qcfg->expectile > 0.0f && qcfg->expectile < 1.0f)) { g_create_error = "fql_iql_create: expectile must be in (0, 1)"; return FQL_E_INVALID; }
+        if (!std::isfinite(qcfg->alpha)) { g_create_error = "fql_iql_create: alpha must be finite"; return FQL_E_INVALID; }
+        if (qcfg->actor_loss != 0 && qcfg->actor_loss != 1) { g_create_error = "fql_iql_create: actor_loss must be 0 (awr) or 1 (ddpgbc)"; return FQL_E_INVALID; }
+        if (qcfg->const_std != 0 && qcfg->const_std != 1) { g_create_error = "fql_iql_create: const_std must be 0 or 1"; return FQL_E_INVALID; }
+    }
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
         (void)hipGetLastError();
@@ -4046,6 +4311,7 @@ static int create_engine(const fql_config* cfg, const fql_ifql_config* icfg, con
         if (icfg) { h->ifql = true; h->expectile = icfg->expectile; h->num_samples = icfg->num_samples; }
         if (rcfg) { h->rebrac = true; h->rcfg = *rcfg; }
         if (bcfg) { h->bc = true; h->bc_steps = bcfg->denoise_steps; }
+        if (qcfg) { h->iql = true; h->qcfg = *qcfg; }
         if (scfg) {   // sac.py create: target_entropy = -target_entropy_multiplier * action_dim when None
             h->sac = true; h->scfg = *scfg;
             h->target_entropy = std::isnan(scfg->target_entropy) ? -scfg->target_entropy_multiplier * (float)cfg->act_dim : scfg->target_entropy;
@@ -4115,9 +4381,13 @@ static int create_engine(const fql_config* cfg, const fql_ifql_config* icfg, con
         h->build_chain_weights();
         h->refresh_chain_weights(h->stream);
         HIP_CHECK(hipMalloc((void**)&h->d_state, sizeof(DevState)));
+        if (h->iql) {
+            HIP_CHECK(hipMalloc((void**)&h->iql_info, 2 * IQL_INFO_STRIDE * sizeof(float)));
+            HIP_CHECK(hipMemset(h->iql_info, 0, 2 * IQL_INFO_STRIDE * sizeof(float)));
+        }
         HIP_CHECK(hipMalloc((void**)&h->d_src, sizeof(SrcDesc)));
         HIP_CHECK(hipHostMalloc((void**)&h->h_src_ring, 64 * sizeof(SrcDesc), hipHostMallocDefault));
-        HIP_CHECK(hipHostMalloc((void**)&h->h_info_ring, fql_engine::kInfoRing * 16 * sizeof(float), hipHostMallocDefault));
+        HIP_CHECK(hipHostMalloc((void**)&h->h_info_ring, fql_engine::kInfoRing * 32 * sizeof(float), hipHostMallocDefault));
         for (auto& e : h->info_ev) HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
         DevState st{};
         st.rng_step = 0; st.adam_count = 0; st.train_step = 1; st.b1pow = 1.0; st.b2pow = 1.0; st.grad_scale = 1.0f; st.lam = 1.0f;
@@ -4146,7 +4416,7 @@ int fql_destroy(fql_handle h) {
     for (auto& kv : h->evals) {
         for (void* p : kv.second->allocs) hipFree(p);
     }
-    hipFree(h->P); hipFree(h->G); hipFree(h->Mu); hipFree(h->Nu); hipFree(h->d_chunks); hipFree(h->d_partials); hipFree(h->d_leaf_range); hipFree(h->d_state); hipFree(h->d_src); hipFree(h->d_emb);
+    hipFree(h->P); hipFree(h->G); hipFree(h->Mu); hipFree(h->Nu); hipFree(h->d_chunks); hipFree(h->d_partials); hipFree(h->d_leaf_range); hipFree(h->d_state); hipFree(h->d_src); hipFree(h->d_emb); hipFree(h->iql_info);
     if (h->h_src_ring) hipHostFree(h->h_src_ring);
     if (h->h_info_ring) hipHostFree(h->h_info_ring);
     for (auto& e : h->info_ev) if (e) hipEventDestroy(e);
@@ -4375,6 +4645,7 @@ int fql_sample_actions(fql_handle h, const float* obs, int n, const float* noise
     if (!h) return FQL_E_INVALID;
     if (h->rebrac) FQL_TRY(h, h->rebrac_sample(obs, noise, seed, 1.0f, n, out, pick(h, stream), stream == nullptr));
     if (h->sac) FQL_TRY(h, h->sac_sample(obs, noise, seed, 1.0f, n, out, pick(h, stream), stream == nullptr));
+    if (h->iql) FQL_TRY(h, h->iql_sample(obs, noise, seed, 1.0f, n, out, pick(h, stream), stream == nullptr));
     if (h->ifql) FQL_TRY(h, h->ifql_sample(obs, noise, seed, n, out, pick(h, stream), stream == nullptr));
     FQL_TRY(h, h->eval_rows(false, obs, noise, seed, n, out, pick(h, stream), stream == nullptr));
 }
@@ -4505,6 +4776,7 @@ int fql_dataset_add_frames(fql_handle h, const uint8_t* frame, const uint8_t* ne
 }
 int fql_replay_create(fql_handle h, int64_t capacity) {
     FQL_IFQL_REFUSES(h, "fql_replay_create");
+    if (h && h->iql) { h->err = "fql_replay_create is not available on an IQL handle"; return FQL_E_STATE; }
     FQL_BC_REFUSES(h, "fql_replay_create");
     if (!h) return FQL_E_INVALID;
     FQL_TRY(h, {
@@ -4526,6 +4798,7 @@ int fql_replay_create(fql_handle h, int64_t capacity) {
 }
 int fql_replay_add(fql_handle h, const float* ob, const float* ac, float reward, float mask, const float* nob) {
     FQL_IFQL_REFUSES(h, "fql_replay_add");
+    if (h && h->iql) { h->err = "fql_replay_add is not available on an IQL handle"; return FQL_E_STATE; }
     FQL_BC_REFUSES(h, "fql_replay_add");
     if (!h) return FQL_E_INVALID;
     FQL_TRY(h, {
@@ -4552,6 +4825,7 @@ int fql_replay_add_frames(fql_handle h, const uint8_t* frame, const uint8_t* nex
 }
 int fql_replay_size(fql_handle h, int64_t* size, int64_t* pointer) {
     FQL_IFQL_REFUSES(h, "fql_replay_size");
+    if (h && h->iql) { h->err = "fql_replay_size is not available on an IQL handle"; return FQL_E_STATE; }
     FQL_BC_REFUSES(h, "fql_replay_size");
     if (!h) return FQL_E_INVALID;
     if (size) *size = h->rb_size;
@@ -4662,14 +4936,15 @@ int fql_info_enqueue(fql_handle h, void* stream, uint64_t* ticket) {
         hipStream_t s = pick(h, stream);
         const uint64_t k = h->info_seq++;
         const int slot = (int)(k % fql_engine::kInfoRing);
-        HIP_CHECK(hipMemcpyAsync(h->h_info_ring[slot], &h->d_state->info[0], (h->sac ? FQL_SAC_NUM_INFO : FQL_NUM_INFO) * sizeof(float),
-                                 hipMemcpyDeviceToHost, s));
+        HIP_CHECK(hipMemcpyAsync(h->h_info_ring[slot], h->info_src(),
+                                 (h->iql ? fql_num_info(h) : h->sac ? FQL_SAC_NUM_INFO : FQL_NUM_INFO) * sizeof(float), hipMemcpyDeviceToHost, s));
         HIP_CHECK(hipEventRecord(h->info_ev[slot], s));
         *ticket = k;
     });
 }
 static int info_wait(fql_handle h, uint64_t ticket, float* info13_host, int n);
 int fql_info_wait(fql_handle h, uint64_t ticket, float* info13_host) {
+    if (h && h->iql) { h->err = "fql_info_wait is not available on an IQL handle (16 or 19 infos: fql_info_wait_n)"; return FQL_E_STATE; }
     FQL_SAC_REFUSES(h, "fql_info_wait (14 infos: fql_info_wait_n)");
     FQL_BC_REFUSES(h, "fql_info_wait (4 infos: fql_info_wait_n)");
     return info_wait(h, ticket, info13_host, FQL_NUM_INFO);
@@ -4700,6 +4975,7 @@ int fql_synchronize(fql_handle h, int* mode) {
 }
 
 int fql_read_info(fql_handle h, float* info13_host) {
+    if (h && h->iql) { h->err = "fql_read_info is not available on an IQL handle (16 or 19 infos: fql_read_info_n)"; return FQL_E_STATE; }
     FQL_SAC_REFUSES(h, "fql_read_info (14 infos: fql_read_info_n)");
     FQL_BC_REFUSES(h, "fql_read_info (4 infos: fql_read_info_n)");
     if (!h || !info13_host) return FQL_E_INVALID;
@@ -4713,7 +4989,7 @@ int fql_read_info_n(fql_handle h, float* out, int n) {
     if (n < fql_num_info(h)) { h->err = "fql_read_info_n: the buffer holds fewer floats than fql_num_info(h)"; return FQL_E_INVALID; }
     FQL_TRY(h, {
         HIP_CHECK(hipDeviceSynchronize());
-        HIP_CHECK(hipMemcpy(out, &h->d_state->info[0], (size_t)fql_num_info(h) * sizeof(float), hipMemcpyDeviceToHost));   // exactly fql_num_info(h)
+        HIP_CHECK(hipMemcpy(out, h->info_src(), (size_t)fql_num_info(h) * sizeof(float), hipMemcpyDeviceToHost));   // exactly fql_num_info(h)
     });
 }
 
@@ -4850,6 +5126,71 @@ int fql_sac_stats(fql_handle h, int64_t* launches_per_update, int64_t* macs_per_
     FQL_SAC_ONLY(h, "fql_sac_stats");
     if (launches_per_update) *launches_per_update = (int64_t)h->prog_full.launches.size();
     if (macs_per_update) *macs_per_update = h->sac_macs();
+    return FQL_OK;
+}
+
+// ---- IQL (agents/iql.py): expectile value, Gaussian actor with the AWR or the DDPG+BC loss -------------------------------------------
+// One update through run_update (the AQL form and the graph are bitwise equal); 16 (awr) or 19 (ddpgbc) infos.
+#define FQL_IQL_ONLY(h, what)                                                                           \
+    do {                                                                                             \
+        if (!(h)) return FQL_E_INVALID;                                                              \
+        if (!(h)->iql) { (h)->err = what " needs an IQL handle (fql_iql_create)"; return FQL_E_STATE; } \
+    } while (0)
+void fql_iql_default_config(fql_iql_config* c) {   // agents/iql.py:242-261
+    std::memset(c, 0, sizeof *c);
+    c->expectile = 0.9f;
+    c->alpha = 1.0f;
+    c->actor_loss = 1;
+    c->const_std = 1;
+}
+int fql_iql_create(const fql_config* cfg, const fql_iql_config* qcfg, uint64_t seed, fql_handle* out) {
+    if (!qcfg) { g_create_error = "qcfg must not be NULL"; if (out) *out = nullptr; return FQL_E_INVALID; }
+    return create_engine(cfg, nullptr, nullptr, nullptr, seed, out, nullptr, qcfg);
+}
+int fql_iql_update(fql_handle h, const float* obs, const float* act, const float* rew, const float* masks, const float* next_obs,
+                   int batch_size, const fql_noise* noise, float* info, void* stream) {
+    FQL_IQL_ONLY(h, "fql_iql_update");
+    FQL_TRY_FAST(h, {
+        hipStream_t s = pick(h, stream);
+        h->source_from_batch(obs, act, rew, masks, next_obs, batch_size, noise, 1, s);
+        run_update(h, h->prog_full, s, stream == nullptr);
+        h->finish_info(info, fql_num_info(h), s);
+    });
+}
+int fql_iql_update_from_dataset(fql_handle h, const int64_t* idx, int batch_size, int64_t lo, int64_t hi, const fql_noise* noise,
+                                float* info, void* stream) {
+    FQL_IQL_ONLY(h, "fql_iql_update_from_dataset");
+    FQL_TRY_FAST(h, {
+        hipStream_t s = pick(h, stream);
+        h->source_from_dataset(idx, batch_size, lo, hi, noise, s);
+        run_update(h, h->prog_full, s, stream == nullptr);
+        h->finish_info(info, fql_num_info(h), s);
+    });
+}
+int fql_iql_total_loss(fql_handle h, const float* obs, const float* act, const float* rew, const float* masks, const float* next_obs,
+                       int batch_size, const fql_noise* noise, float* loss, float* info, void* stream) {
+    FQL_IQL_ONLY(h, "fql_iql_total_loss");
+    FQL_TRY(h, {
+        hipStream_t s = pick(h, stream);
+        h->source_from_batch(obs, act, rew, masks, next_obs, batch_size, noise, 0, s);
+        run_program(h, h->prog_loss, s);   // its finalize writes the probe half of iql_info: the last update's infos stay
+        float tmp[IQL_INFO_STRIDE];
+        HIP_CHECK(hipMemcpyAsync(tmp, h->iql_info + IQL_INFO_STRIDE, sizeof tmp, hipMemcpyDeviceToHost, s));
+        HIP_CHECK(hipStreamSynchronize(s));
+        // iql.py:115-134: loss = value_loss + critic_loss + actor_loss; every info but the grad statistics
+        if (loss) *loss = tmp[0] + tmp[4] + tmp[IQL_I_ACTOR];
+        if (info) std::memcpy(info, tmp, (size_t)(fql_num_info(h) - 3) * sizeof(float));
+    });
+}
+int fql_iql_sample_actions(fql_handle h, const float* obs, int n, const float* noise, uint64_t seed, float temperature, float* out,
+                           void* stream) {
+    FQL_IQL_ONLY(h, "fql_iql_sample_actions");
+    FQL_TRY(h, h->iql_sample(obs, noise, seed, temperature, n, out, pick(h, stream), stream == nullptr));
+}
+int fql_iql_stats(fql_handle h, int64_t* launches_per_update, int64_t* macs_per_update) {
+    FQL_IQL_ONLY(h, "fql_iql_stats");
+    if (launches_per_update) *launches_per_update = (int64_t)h->prog_full.launches.size();
+    if (macs_per_update) *macs_per_update = h->iql_macs();
     return FQL_OK;
 }
 
@@ -5362,9 +5703,9 @@ int fql_group_create(const fql_handle* members, int k, fql_group* out) {
     if (!out) { g_create_error = "fql_group_create: out must not be NULL"; return FQL_E_INVALID; }
     *out = nullptr;
     for (int i = 0; members && i < k; ++i)
-        if (members[i] && (members[i]->ifql || members[i]->rebrac || members[i]->sac || members[i]->bc)) {
+        if (members[i] && (members[i]->ifql || members[i]->rebrac || members[i]->sac || members[i]->bc || members[i]->iql)) {
             g_create_error = "fql_group_create: member " + std::to_string(i) +
-                             (members[i]->ifql ? " is an IFQL handle" : members[i]->rebrac ? " is a ReBRAC handle" : members[i]->sac ? " is a SAC handle" : " is a BC handle") +
+                             (members[i]->ifql ? " is an IFQL handle" : members[i]->rebrac ? " is a ReBRAC handle" : members[i]->sac ? " is a SAC handle" : members[i]->iql ? " is an IQL handle" : " is a BC handle") +
                              " (groups take FQL agents only)";
             return FQL_E_STATE;
         }

@@ -481,6 +481,63 @@ int fql_bc_sample_actions(fql_handle h, const float* observations, int n, const 
 /* launches and algorithmic MACs of one update; launches of one sampling call of <= 4096 rows */
 int fql_bc_stats(fql_handle h, int64_t* launches_per_update, int64_t* macs_per_update, int64_t* launches_per_sample);
 
+/* ---- IQL (agents/iql.py): implicit Q-learning, the classic offline baseline.  State observations, fp32 only.
+ * Networks (utils/networks.py Value / Actor): "modules_value/value_net/..." (one member, unstacked), "modules_critic/value_net/..." and
+ * "modules_target_critic/value_net/..." (FQL's stacked [2, ...] critic), "modules_actor/actor_net/Dense_0..n-1" (GELU, + "LayerNorm_i"
+ * with actor_layer_norm), "modules_actor/mean_net/{bias,kernel}" ([H, act] / [act], kernel variance_scaling(1e-2, fan_avg, uniform)) and,
+ * with const_std == 0 only, "modules_actor/log_stds" ([act], zeros, clipped to [-5, 2] where it is read).  A plain Gaussian: no tanh.
+ * Adam over the whole tree, Polyak of the target critic from the PRE-step critic.
+ * Losses: the value and critic losses are IFQL's (expectile regression onto min of the target pair at (obs, act); TD onto
+ * value(next_obs)).  Actor, actor_loss == 0 (awr): -mean(min(exp(alpha (min(q1, q2) - v)), 100) log_prob(actions)), the weight a
+ * constant; actor_loss == 1 (ddpgbc): a = clip(mean) (const_std) or clip(mean + exp(log_stds) eps), -mean(min(q1, q2)(obs, a)) /
+ * stop_gradient(mean |q|) - alpha mean(log_prob(actions)); minimum and clip pass 1/2 of the gradient at an exact tie / bound.
+ * Infos (fql_num_info, fql_handle_info_name): 0 value/value_loss 1 value/v_mean 2 value/v_max 3 value/v_min 4 critic/critic_loss
+ *   5 critic/q_mean 6 critic/q_max 7 critic/q_min, then
+ *   awr (16, FQL_IQL_AWR_NUM_INFO):       8 actor/actor_loss 9 actor/adv 10 actor/bc_log_prob 11 actor/mse 12 actor/std 13 grad/max
+ *                                         14 grad/min 15 grad/norm
+ *   ddpgbc (19, FQL_IQL_DDPGBC_NUM_INFO): 8 actor/actor_loss 9 actor/q_loss 10 actor/bc_loss 11 actor/q_mean 12 actor/q_abs_mean
+ *                                         13 actor/bc_log_prob 14 actor/mse 15 actor/std 16 grad/max 17 grad/min 18 grad/norm
+ *   The update calls write fql_num_info(h) floats to `info` (NULL: read later with fql_read_info_n / fql_info_wait_n); fql_read_info and
+ *   fql_info_wait return FQL_E_STATE on an IQL handle rather than overrun a 13-float buffer.
+ * fql_noise: only eps1 (the raw N(0, 1) [B, act] of dist.sample in ddpgbc with const_std == 0; ignored otherwise) is read; any other
+ * non-NULL pointer is FQL_E_INVALID.  NULL = the engine's Philox tensor 1.
+ * An IQL handle is an ordinary fql_handle for destroy, set_batch_size, leaf / param / opt-state / step access, dataset upload / add /
+ * reserve / size, fql_sample_actions (temperature 1), info enqueue / fql_info_wait_n / fql_read_info_n, fql_synchronize, fql_stats and
+ * fql_stream.  Refused: encoder != 0 or precision != 0 at create (FQL_E_INVALID); on an IQL handle fql_update*, fql_update_begin* /
+ * _end*, fql_total_loss, fql_flow_actions, fql_grad_buckets, frame uploads / updates, fql_replay_*, fql_update_balanced,
+ * fql_noise_from_jax_keys, fql_read_info and fql_info_wait return FQL_E_STATE, and fql_group_create with an IQL member returns
+ * FQL_E_STATE.  The fql_iql_* calls on another handle return FQL_E_STATE. */
+#define FQL_IQL_AWR_NUM_INFO 16
+#define FQL_IQL_DDPGBC_NUM_INFO 19
+typedef struct fql_iql_config {
+    float expectile;                  /* IQL expectile, in (0, 1) (0.9)                               */
+    float alpha;                      /* temperature in AWR / BC coefficient in DDPG+BC (1.0)          */
+    int32_t actor_loss;               /* 0 = awr, 1 = ddpgbc (1)                                       */
+    int32_t const_std;                /* 1: log-std 0, no log_stds leaf; 0: the learned vector (1)     */
+    int32_t reserved[8];
+} fql_iql_config;
+void fql_iql_default_config(fql_iql_config* c);
+/* fql_config.alpha, q_agg, flow_steps and normalize_q_loss are ignored (alpha is fql_iql_config's). */
+int fql_iql_create(const fql_config* cfg, const fql_iql_config* qcfg, uint64_t seed, fql_handle* out);
+/* IQLAgent.update(batch)  agents/iql.py:145-156. */
+int fql_iql_update(fql_handle h, const float* observations, const float* actions, const float* rewards, const float* masks,
+                   const float* next_observations, int batch_size, const fql_noise* noise, float* info, void* stream);
+/* train_dataset.sample(B) + update(batch) on the device; idx / lo / hi as fql_update_from_dataset's. */
+int fql_iql_update_from_dataset(fql_handle h, const int64_t* idx, int batch_size, int64_t lo, int64_t hi, const fql_noise* noise,
+                                float* info, void* stream);
+/* IQLAgent.total_loss(batch): pure forward, no state change (parameters, moments, counters and the infos that fql_read_info_n reads are
+ * as the last update left them).  loss = value_loss + critic_loss + actor_loss; `info` receives the fql_num_info(h) - 3 infos before the
+ * grad statistics.  Synchronous. */
+int fql_iql_total_loss(fql_handle h, const float* observations, const float* actions, const float* rewards, const float* masks,
+                       const float* next_observations, int batch_size, const fql_noise* noise, float* loss, float* info, void* stream);
+/* IQLAgent.sample_actions(observations, seed, temperature): clip(mean + exp(log_stds) temperature eps, -1, 1); temperature 0 returns
+ * clip(mean) exactly.  noise [n, act] raw N(0, 1) or NULL (engine RNG keyed by `seed`); rows of one call equal single calls with the same
+ * noise rows.  fql_sample_actions == this with temperature 1. */
+int fql_iql_sample_actions(fql_handle h, const float* observations, int n, const float* noise, uint64_t seed, float temperature,
+                           float* out, void* stream);
+/* launches and algorithmic MACs of one update */
+int fql_iql_stats(fql_handle h, int64_t* launches_per_update, int64_t* macs_per_update);
+
 #ifdef __cplusplus
 }
 #endif
