@@ -92,6 +92,19 @@ class _Pending:
         return self.vals
 
 
+class _PendingN(_Pending):
+    """_Pending over fql_info_wait_n: all fql_num_info(h) scalars of one update."""
+
+    def get(self):
+        if self.vals is None:
+            n = len(self.agent._info_keys)
+            buf = (C.c_float * n)()
+            self.agent._check(self.agent._lib.fql_info_wait_n(self.agent._h, self.ticket, buf, n))
+            self.vals = [float(buf[i]) for i in range(n)]
+            self.agent = None
+        return self.vals
+
+
 class LazyScalar:
     """One info value of an update that may not have run yet - what a JAX device scalar is in the reference's info dict (agents/fql.py:39-44;
     main.py:276 reads them at log time).  float(x), arithmetic, comparisons, formatting, numpy conversion all block until the update has run and
@@ -158,6 +171,7 @@ class LazyInfo(dict):
 class FQLAgent:
     """Flow Q-learning agent backed by the MI355X step engine."""
 
+    _name = 'FQL'
     _loss_infos = 10          # infos fql_total_loss writes (the total-loss probe has no gradient statistics)
     _jax_sample_noise = True  # sample_actions(seed=<JAX key>) draws the reference's noise on the host
 
@@ -188,6 +202,16 @@ class FQLAgent:
         cfg['ob_dims'] = ob_dims
         cfg['action_dim'] = action_dim
         return cls(h, cfg, int(seed))
+
+    @classmethod
+    def _refuse_config(cls, cfg):
+        """The create-time refusals of the agents of another kind than FQL (`_name`)."""
+        if cfg.get('encoder') is not None:
+            raise NotImplementedError(f'{cls._name}: visual encoders are not available (state observations only)')
+        if cfg.get('precision', 'fp32') not in ('fp32', 0):
+            raise NotImplementedError(f"{cls._name} runs in fp32 only (precision {cfg['precision']!r})")
+        if cfg.get('rng', 'engine') != 'engine':
+            raise NotImplementedError(f"{cls._name} draws its noise from the engine's RNG or explicit tensors only (rng {cfg['rng']!r})")
 
     @staticmethod
     def _engine_config(lib, cfg, ex_observations, ex_actions):
@@ -407,7 +431,6 @@ class FQLAgent:
         obd, ad = tuple(self.config['ob_dims']), self.config['action_dim']
         vis = len(obd) == 3
         od = obd[0] if not vis else None
-        is_torch = hasattr(observations, 'data_ptr')
         if vis and tuple(observations.shape[-3:]) != obd:
             raise ValueError(f'observations must end in {obd}, got {tuple(observations.shape)}')
         lead = tuple(observations.shape[:-3]) if vis else tuple(observations.shape[:-1])
@@ -419,24 +442,29 @@ class FQLAgent:
         n = int(np.prod(lead)) if lead else 1
         o = _Arg(observations, (n,) + obd, u8=vis)
         z = _Arg(noises, self._sample_noise_shape(n, flow))
-        if is_torch and observations.is_cuda:
-            torch = _torch()
-            out = torch.empty(lead + (ad,), dtype=torch.float32, device=observations.device)
-            optr = out.data_ptr()
-        else:
-            out = np.empty(lead + (ad,), dtype=np.float32)
-            optr = out.ctypes.data
+        out, optr = self._actions_out(observations, lead + (ad,))
         stream = self._stream([o, z])
         if flow:
             self._check(self._lib.fql_flow_actions(self._h, o.ptr, z.ptr, n, optr, stream))
         else:
-            if seed is None and noises is None:
-                self._sample_calls += 1
-                sd = (self._seed << 20) ^ self._sample_calls
-            else:
-                sd = _seed_to_u64(seed)
-            self._check(self._lib.fql_sample_actions(self._h, o.ptr, n, z.ptr, sd & 0xFFFFFFFFFFFFFFFF, optr, stream))
+            self._check(self._lib.fql_sample_actions(self._h, o.ptr, n, z.ptr, self._sample_seed(seed, noises), optr, stream))
         return out
+
+    @staticmethod
+    def _actions_out(observations, shape):
+        """(array, pointer) for sampled actions: a tensor beside CUDA observations, else a NumPy array."""
+        if hasattr(observations, 'data_ptr') and observations.is_cuda:
+            out = _torch().empty(shape, dtype=_torch().float32, device=observations.device)
+            return out, out.data_ptr()
+        out = np.empty(shape, dtype=np.float32)
+        return out, out.ctypes.data
+
+    def _sample_seed(self, seed, noises):
+        """The uint64 that keys the engine's draw: `seed`, or a counter of this agent's own when neither seed nor noises is given."""
+        if seed is None and noises is None:
+            self._sample_calls += 1
+            return ((self._seed << 20) ^ self._sample_calls) & 0xFFFFFFFFFFFFFFFF
+        return _seed_to_u64(seed) & 0xFFFFFFFFFFFFFFFF
 
     # -- device-resident dataset (utils/datasets.py Dataset/ReplayBuffer on the GPU) -------------
     def upload_dataset(self, dataset, capacity: Optional[int] = None, frame_stack: Optional[int] = None, p_aug: Optional[float] = None):
@@ -670,6 +698,81 @@ class FQLAgent:
         a, b, c = C.c_int64(), C.c_int64(), C.c_int64()
         self._check(self._lib.fql_stats(self._h, C.byref(a), C.byref(b), C.byref(c)))
         return {'launches_per_update': int(a.value), 'macs_per_update': int(b.value), 'param_count': int(c.value)}
+
+
+_HALVES = tuple((m, 'the data-parallel update halves') for m in ('update_begin', 'update_begin_split', 'update_end', 'update_end_split'))
+
+
+class KindAgent(FQLAgent):
+    """What the agents of another kind than FQL share: state observations, fp32 and the engine's RNG only, and the FQL-only paths
+    refused before the library is called.  A subclass names itself (`_name`), lists its `_refused` (method, reason) pairs beside the
+    data-parallel halves and gradient buckets, and names the library calls (`_update_fn`, ...) of the shared methods it keeps."""
+
+    _refused = ()
+    _update_fn = _update_dataset_fn = _sample_fn = None
+    _jax_sample_noise = False
+
+    def __init_subclass__(cls, **kw):
+        super().__init_subclass__(**kw)
+        for method, reason in _HALVES + (('grad_buckets', 'gradient buckets'),) + tuple(cls._refused):
+            def refused(self, *a, _reason=reason, **k):
+                raise NotImplementedError(f'{self._name}: {_reason} is not available (FQL agents only)')
+            refused.__name__ = method
+            setattr(cls, method, refused)
+
+    def _probe_guard(self, what, params, rng):
+        """A loss probe takes the stored parameters and the engine's or explicit noise."""
+        if params is not None:
+            raise NotImplementedError(f'{what} is jax.grad plumbing; use update()')
+        if rng is not None:
+            raise NotImplementedError(f'{self._name} draws its noise from the engine RNG or explicit tensors (noise=), not JAX keys')
+
+    # -- reference API: `extra` is what a kind's library call takes between the noise and the info pointer (ReBRAC: the step kind) --
+    def update(self, batch, noise=None, want_info=True, _extra=()):
+        """The agent's update.  Returns (agent, info); info is a LazyInfo with the handle's info keys, or None with want_info=False."""
+        B, args = self._batch_args(batch)
+        self._ensure_batch(B)
+        nz, nargs = self._noise_args(noise, B)
+        stream = self._stream(args + nargs)
+        fn = getattr(self._lib, self._update_fn)
+        self._check(fn(self._h, *[a.ptr for a in args], B, C.byref(nz) if nz else None, *_extra, None, stream))
+        self._keep = (args, nargs)
+        return self, (self._lazy_info(stream) if want_info else None)
+
+    def update_from_dataset(self, batch_size=None, idxs=None, noise=None, shard=(0, 0), want_info=False, stream=None, _extra=()):
+        """train_dataset.sample(B) + update(batch) without leaving the device."""
+        B = int(batch_size or self.config['batch_size'])
+        self._ensure_batch(B)
+        nz, nargs = self._noise_args(noise, B)
+        ip, keep = None, None
+        if idxs is not None:
+            keep, ip = self._host_idx(idxs, B, self.dataset_size()[0], 'idxs')
+        fn = getattr(self._lib, self._update_dataset_fn)
+        self._check(fn(self._h, ip, B, int(shard[0]), int(shard[1]), C.byref(nz) if nz else None, *_extra, None, stream))
+        self._keep = (keep, nargs)
+        return self, (self._lazy_info(stream) if want_info else None)
+
+    def read_info(self):
+        """The infos of the last update (blocks until it has run)."""
+        n = len(self._info_keys)
+        buf = (C.c_float * n)()
+        self._check(self._lib.fql_read_info_n(self._h, buf, n))
+        return {k: float(buf[i]) for i, k in enumerate(self._info_keys)}
+
+    def sample_actions(self, observations, seed=None, temperature=1.0, noises=None):
+        """The kind's sample_actions on its actor's output.  [od] -> [act]; [n, od] -> [n, act].  `noises`: the raw N(0, 1) with the
+        actions' shape, or None = engine RNG keyed by `seed`."""
+        od, ad = self.config['ob_dims'][0], self.config['action_dim']
+        if int(observations.shape[-1]) != od:
+            raise ValueError(f'observations last dim must be {od}, got {tuple(observations.shape)}')
+        lead = tuple(observations.shape[:-1])
+        n = int(np.prod(lead)) if lead else 1
+        o = _Arg(observations, (n, od))
+        z = _Arg(noises, (n, ad))
+        out, optr = self._actions_out(observations, lead + (ad,))
+        fn = getattr(self._lib, self._sample_fn)
+        self._check(fn(self._h, o.ptr, n, z.ptr, self._sample_seed(seed, noises), float(temperature), optr, self._stream([o, z])))
+        return out
 
 
 class FQLAgentGroup:

@@ -20,9 +20,8 @@ import ctypes as C
 import numpy as np
 
 from . import _cabi
-from .agent import FQLAgent, LazyInfo, _Arg, _seed_to_u64
+from .agent import KindAgent, _Arg, _PendingN
 from .config import ConfigDict
-from .sac import _PendingN
 
 BC_INFO_KEYS = ('bc_loss', 'grad/max', 'grad/min', 'grad/norm')
 BC_NOISE_KEYS = ('x0', 't')
@@ -67,11 +66,15 @@ def get_config():
     )
 
 
-class BCAgent(FQLAgent):
-    """Flow-matching BC agent backed by the MI355X step engine."""
+class BCAgent(KindAgent):
+    """Flow-matching BC agent backed by the MI355X step engine.  update: agents/bc.py:72-84, 4 infos (BC_INFO_KEYS)."""
 
+    _name = 'BC'
+    _refused = (('total_loss', 'total_loss (BCAgent has policy_loss)'),
+                ('compute_flow_actions', 'compute_flow_actions (sample_actions(noises=) is the flow)'),
+                ('create_replay_buffer', 'the replay ring'), ('update_balanced', 'balanced sampling'))
+    _update_fn, _update_dataset_fn = 'fql_bc_update', 'fql_bc_update_from_dataset'
     _loss_infos = 1
-    _jax_sample_noise = False
     _pending_cls = _PendingN
     _train_state_key = 'policy'   # agents/bc.py:45: the TrainState's field name (checkpoint layout)
 
@@ -82,12 +85,7 @@ class BCAgent(FQLAgent):
         cfg.update(dict(config))
         if cfg.get('activation', 'gelu') != 'gelu':
             raise NotImplementedError(f"BC: only activation 'gelu' is built (got {cfg['activation']!r})")
-        if cfg.get('encoder') is not None:
-            raise NotImplementedError('BC: visual encoders are not available (state observations only)')
-        if cfg.get('precision', 'fp32') not in ('fp32', 0):
-            raise NotImplementedError(f"BC runs in fp32 only (precision {cfg['precision']!r})")
-        if cfg.get('rng', 'engine') != 'engine':
-            raise NotImplementedError(f"BC draws its noise from the engine's RNG or explicit tensors only (rng {cfg['rng']!r})")
+        cls._refuse_config(cfg)
         if int(cfg['denoise_steps']) < 1:
             raise ValueError('denoise_steps must be >= 1')
         lib = _cabi.load()
@@ -105,7 +103,7 @@ class BCAgent(FQLAgent):
         cfg['action_dim'] = action_dim
         return cls(h, cfg, int(seed))
 
-    def _bc_batch_args(self, batch):
+    def _batch_args(self, batch):   # BC batches carry observations and actions only
         for k in ('observations', 'actions'):
             if k not in batch:
                 raise KeyError(f'batch is missing {k!r}')
@@ -127,50 +125,11 @@ class BCAgent(FQLAgent):
         x0, ta = _Arg(noise.get('x0'), (B, ad)), _Arg(t, (B,))
         return _cabi.FqlNoise(None, x0.ptr, ta.ptr, None, None), [x0, ta]
 
-    def _info(self, stream):
-        t = C.c_uint64()
-        self._check(self._lib.fql_info_enqueue(self._h, stream, C.byref(t)))
-        return LazyInfo(self, int(t.value), BC_INFO_KEYS)
-
-    # -- reference API ----------------------------------------------------------------------
-    def update(self, batch, noise=None, want_info=True):
-        """agents/bc.py:72-84.  Returns (agent, info); info is a LazyInfo with BC_INFO_KEYS, or None with want_info=False."""
-        B, args = self._bc_batch_args(batch)
-        self._ensure_batch(B)
-        nz, nargs = self._noise_args(noise, B)
-        stream = self._stream(args + nargs)
-        self._check(self._lib.fql_bc_update(self._h, args[0].ptr, args[1].ptr, B, C.byref(nz) if nz else None, None, stream))
-        self._keep = (args, nargs)
-        return self, (self._info(stream) if want_info else None)
-
-    def update_from_dataset(self, batch_size=None, idxs=None, noise=None, shard=(0, 0), want_info=False, stream=None):
-        """train_dataset.sample(B) + update(batch) without leaving the device."""
-        B = int(batch_size or self.config['batch_size'])
-        self._ensure_batch(B)
-        nz, nargs = self._noise_args(noise, B)
-        ip, keep = None, None
-        if idxs is not None:
-            keep, ip = self._host_idx(idxs, B, self.dataset_size()[0], 'idxs')
-        self._check(self._lib.fql_bc_update_from_dataset(self._h, ip, B, int(shard[0]), int(shard[1]), C.byref(nz) if nz else None,
-                                                         None, stream))
-        self._keep = (keep, nargs)
-        return self, (self._info(stream) if want_info else None)
-
-    def read_info(self):
-        """The 4 infos of the last update (blocks until it has run)."""
-        n = len(BC_INFO_KEYS)
-        buf = (C.c_float * n)()
-        self._check(self._lib.fql_read_info_n(self._h, buf, n))
-        return {k: float(buf[i]) for i, k in enumerate(BC_INFO_KEYS)}
-
     def policy_loss(self, batch, policy_params=None, rng=None, noise=None):
         """agents/bc.py:48-70 with the stored parameters (the validation probe of train_bc_agent): (loss, {'bc_loss': loss}).
         No state changes."""
-        if policy_params is not None:
-            raise NotImplementedError('policy_loss with traced policy_params is jax.grad plumbing; use update()')
-        if rng is not None:
-            raise NotImplementedError('BC draws its noise from the engine RNG or explicit tensors (noise=), not JAX keys')
-        B, args = self._bc_batch_args(batch)
+        self._probe_guard('policy_loss with traced policy_params', policy_params, rng)
+        B, args = self._batch_args(batch)
         self._ensure_batch(B)
         nz, nargs = self._noise_args(noise, B)
         loss = C.c_float()
@@ -178,15 +137,11 @@ class BCAgent(FQLAgent):
                                                  self._stream(args + nargs)))
         return float(loss.value), {'bc_loss': float(loss.value)}
 
-    def total_loss(self, *a, **k):
-        self._refuse('total_loss (BCAgent has policy_loss)')
-
     def sample_actions(self, observations, seed=None, temperature=1.0, noises=None):
         """agents/bc.py:86-101: x ~ N(0, I), denoise_steps Euler steps, clip.  [od] and [1, od] -> [act] (the reference's squeeze);
         [n, od] -> [n, act], row by row the single-observation result.  `noises`: x with the shape [n, act] (or [act]), or None = engine
         RNG keyed by `seed`.  `temperature` is accepted and ignored, as in the reference."""
         od, ad = self.config['ob_dims'][0], self.config['action_dim']
-        is_torch = hasattr(observations, 'data_ptr')
         if not hasattr(observations, 'shape'):
             observations = np.asarray(observations, dtype=np.float32)
         if int(observations.shape[-1]) != od or len(observations.shape) > 2:
@@ -195,19 +150,8 @@ class BCAgent(FQLAgent):
         shape = (ad,) if n == 1 else (n, ad)
         o = _Arg(observations, (n, od))
         z = _Arg(noises, (n, ad))
-        if is_torch and observations.is_cuda:
-            torch = __import__('torch')
-            out = torch.empty(shape, dtype=torch.float32, device=observations.device)
-            optr = out.data_ptr()
-        else:
-            out = np.empty(shape, dtype=np.float32)
-            optr = out.ctypes.data
-        if seed is None and noises is None:
-            self._sample_calls += 1
-            sd = (self._seed << 20) ^ self._sample_calls
-        else:
-            sd = _seed_to_u64(seed)
-        self._check(self._lib.fql_bc_sample_actions(self._h, o.ptr, n, z.ptr, sd & 0xFFFFFFFFFFFFFFFF, optr, self._stream([o, z])))
+        out, optr = self._actions_out(observations, shape)
+        self._check(self._lib.fql_bc_sample_actions(self._h, o.ptr, n, z.ptr, self._sample_seed(seed, noises), optr, self._stream([o, z])))
         return out
 
     def bc_stats(self):
@@ -215,34 +159,6 @@ class BCAgent(FQLAgent):
         la, ma, ls = C.c_int64(), C.c_int64(), C.c_int64()
         self._check(self._lib.fql_bc_stats(self._h, C.byref(la), C.byref(ma), C.byref(ls)))
         return int(la.value), int(ma.value), int(ls.value)
-
-    # -- FQL-only paths, refused before the library is called ----------------------------------
-    def _refuse(self, what):
-        raise NotImplementedError(f'BC: {what} is not available (FQL agents only)')
-
-    def compute_flow_actions(self, observations, noises):
-        self._refuse('compute_flow_actions (sample_actions(noises=) is the flow)')
-
-    def create_replay_buffer(self, *a, **k):
-        self._refuse('the replay ring')
-
-    def update_balanced(self, *a, **k):
-        self._refuse('balanced sampling')
-
-    def update_begin(self, *a, **k):
-        self._refuse('the data-parallel update halves')
-
-    def update_begin_split(self, *a, **k):
-        self._refuse('the data-parallel update halves')
-
-    def update_end(self, *a, **k):
-        self._refuse('the data-parallel update halves')
-
-    def update_end_split(self, *a, **k):
-        self._refuse('the data-parallel update halves')
-
-    def grad_buckets(self):
-        self._refuse('gradient buckets')
 
 
 def train_bc(agent, dataset, steps, log_every, val_dataset=None, val_batch_size=None, log=None):

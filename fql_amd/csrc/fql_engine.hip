@@ -323,14 +323,74 @@ struct EncBuf {
     std::map<const void*, size_t> bytes;   // allocated size of every activation / scratch buffer above (fql_debug_enc's bound)
 };
 
+// ------------------------------------------------------------------------------------------------
+// agent kinds: what a handle is, and what the engine says about it
+// ------------------------------------------------------------------------------------------------
+enum class AgentKind { FQL, IFQL, REBRAC, SAC, BC, IQL };
+constexpr int kNumKinds = 6;
+
+const char* const k_info_names[FQL_NUM_INFO] = {
+    "critic/critic_loss", "critic/q_mean", "critic/q_max", "critic/q_min", "actor/actor_loss",
+    "actor/bc_flow_loss", "actor/distill_loss", "actor/q_loss", "actor/q", "actor/mse",
+    "grad/max", "grad/min", "grad/norm"};
+const char* const k_ifql_info_names[FQL_IFQL_NUM_INFO] = {
+    "value/value_loss", "value/v_mean", "value/v_max", "value/v_min", "critic/critic_loss", "critic/q_mean", "critic/q_max",
+    "critic/q_min", "actor/actor_loss", "grad/max", "grad/min", "grad/norm"};
+const char* const k_rebrac_info_names[FQL_REBRAC_NUM_INFO] = {
+    "critic/critic_loss", "critic/q_mean", "critic/q_max", "critic/q_min", "actor/total_loss", "actor/actor_loss", "actor/bc_loss",
+    "actor/std", "actor/mse", "grad/max", "grad/min", "grad/norm"};
+const char* const k_sac_info_names[FQL_SAC_NUM_INFO] = {
+    "critic/critic_loss", "critic/q_mean", "critic/q_max", "critic/q_min", "actor/total_loss", "actor/actor_loss", "actor/alpha_loss",
+    "actor/alpha", "actor/entropy", "actor/std", "actor/q", "grad/max", "grad/min", "grad/norm"};
+const char* const k_bc_info_names[FQL_BC_NUM_INFO] = {"bc_loss", "grad/max", "grad/min", "grad/norm"};
+const char* const k_iql_info_names[2][FQL_IQL_DDPGBC_NUM_INFO] = {
+    {"value/value_loss", "value/v_mean", "value/v_max", "value/v_min", "critic/critic_loss", "critic/q_mean", "critic/q_max", "critic/q_min",
+     "actor/actor_loss", "actor/adv", "actor/bc_log_prob", "actor/mse", "actor/std", "grad/max", "grad/min", "grad/norm", nullptr, nullptr, nullptr},
+    {"value/value_loss", "value/v_mean", "value/v_max", "value/v_min", "critic/critic_loss", "critic/q_mean", "critic/q_max", "critic/q_min",
+     "actor/actor_loss", "actor/q_loss", "actor/bc_loss", "actor/q_mean", "actor/q_abs_mean", "actor/bc_log_prob", "actor/mse", "actor/std",
+     "grad/max", "grad/min", "grad/norm"}};
+
+enum { NZ_EPS1 = 1, NZ_X0 = 2, NZ_T = 4, NZ_Z = 8, NZ_EPS2 = 16 };   // the fields of fql_noise
+// One row per kind, indexed by AgentKind.  A new agent adds a row here and a column to k_admission (C ABI, below).
+struct KindDesc {
+    const char* name;               // "IFQL": create-time messages
+    const char* label;              // "an IFQL handle": entry-point messages
+    const char* create;             // its create call
+    const char* const* info_names;  // nullptr: depends on the handle's config (IQL: by actor_loss)
+    int num_info;
+    int noise_reads;                // NZ_* fields of fql_noise the kind reads; any other must be NULL ...
+    const char* noise_refusal;      // ... or fill_noise refuses with this
+};
+const KindDesc k_kinds[kNumKinds] = {
+    {"FQL", "an FQL handle", "fql_create", k_info_names, FQL_NUM_INFO, NZ_EPS1 | NZ_X0 | NZ_T | NZ_Z | NZ_EPS2, nullptr},
+    {"IFQL", "an IFQL handle", "fql_ifql_create", k_ifql_info_names, FQL_IFQL_NUM_INFO, NZ_X0 | NZ_T,
+     "IFQL reads only x0 and t of fql_noise (eps1, z and eps2 must be NULL)"},
+    {"ReBRAC", "a ReBRAC handle", "fql_rebrac_create", k_rebrac_info_names, FQL_REBRAC_NUM_INFO, NZ_EPS1,
+     "ReBRAC reads only eps1 of fql_noise (x0, t, z and eps2 must be NULL)"},
+    {"SAC", "a SAC handle", "fql_sac_create", k_sac_info_names, FQL_SAC_NUM_INFO, NZ_EPS1 | NZ_EPS2,
+     "SAC reads only eps1 and eps2 of fql_noise (x0, t and z must be NULL)"},
+    {"BC", "a BC handle", "fql_bc_create", k_bc_info_names, FQL_BC_NUM_INFO, NZ_X0 | NZ_T,
+     "BC reads only x0 and t of fql_noise (eps1, z and eps2 must be NULL)"},
+    {"IQL", "an IQL handle", "fql_iql_create", nullptr, 0, NZ_EPS1,
+     "IQL reads only eps1 of fql_noise (x0, t, z and eps2 must be NULL)"},
+};
+
 }  // namespace
 
 struct fql_group_s;
 struct fql_engine {
     fql_config cfg{};
+    AgentKind kind = AgentKind::FQL;
+    const KindDesc& desc() const { return k_kinds[(int)kind]; }
+    bool has_value_net() const { return kind == AgentKind::IFQL || kind == AgentKind::IQL; }      // NET_OS holds V(obs)
+    bool actor_on_obs() const { return kind == AgentKind::REBRAC || kind == AgentKind::SAC || kind == AgentKind::IQL; }   // NET_BC is actor(obs), no flow
+    int num_info() const {
+        if (kind == AgentKind::IQL) return qcfg.actor_loss == 1 ? FQL_IQL_DDPGBC_NUM_INFO : FQL_IQL_AWR_NUM_INFO;
+        return desc().num_info;
+    }
+    const char* const* info_names() const { return kind == AgentKind::IQL ? k_iql_info_names[qcfg.actor_loss == 1 ? 1 : 0] : desc().info_names; }
     // IFQL agent (agents/ifql.py; fql_ifql_create): the arena's NET_OS slot holds the value net (obs -> 1, LayerNorm like the critic),
     // NET_BC is actor_flow; critic, target and their place in the arena are FQL's.  The update is build_ifql_program.
-    bool ifql = false;
     float expectile = 0.9f;
     int num_samples = 32;
     float* X_v = nullptr;   // [2B, value in_p]: [obs ; next_obs]
@@ -338,7 +398,6 @@ struct fql_engine {
     // ReBRAC agent (agents/rebrac.py; fql_rebrac_create): NET_BC holds the actor (obs -> mean), NET_OS is empty and NET_TA, the target
     // actor, follows the target critic, so the Polyak range [0, critic_size = n_train) of fql_adam_kernel covers critic and actor.
     // Two update programs: prog_full (full_update=True) and prog_critic (critic-only step: no actor passes, zero actor gradient, no Polyak).
-    bool rebrac = false;
     fql_rebrac_config rcfg{};
     float *X_a = nullptr, *X_ta = nullptr, *X_t = nullptr, *X_q = nullptr;   // actor inputs [B, inp_a] (obs, next_obs); critic inputs [B, inp_c]
     float *w_nact = nullptr, *w_noise = nullptr;                            // [B, ap]: next_actions, raw N(0, 1) of the target-policy noise
@@ -348,14 +407,12 @@ struct fql_engine {
     // columns [0, ap), raw log-std [ap, 2 ap)); modules_alpha/log_value sits in the NET_OS slot (4 floats at alpha_off), so the trained
     // region is critic pair, actor, log_value and the Polyak range [0, critic_size) is the critic pair's.  p_a runs over X_a = [obs ;
     // next_obs] (2B rows; backward over the obs rows), p_q[] is the critic pair on [obs | a], p_ct[] the target pair on [next_obs | a'].
-    bool sac = false;
     fql_sac_config scfg{};
     float target_entropy = 0.f;
     size_t alpha_off = 0;
     float *w_eps = nullptr, *lp_buf = nullptr;   // [2B, ap]: eps_c rows then eps_n rows; [2B]: log-probabilities of a, then of a'
     // BC agent (agents/bc.py; fql_bc_create): the arena holds ONE net, the policy, in the NET_BC slot (input [obs | x_t | emb(t)], every
     // other net is empty, so critic_size = 0 and Adam has no Polyak range).  One lane: prep, forward, loss, backward, Adam, finalize.
-    bool bc = false;
     int bc_steps = 16;            // denoise_steps S
     float* d_emb = nullptr;       // [(S + 1), 16] timestep-embedding table (built on the host at create)
     bool lane0_64 = false;        // while the BC update program is built: lane 0 takes the 64-column LDS-tiled kernels and keeps its weight gradients
@@ -363,7 +420,6 @@ struct fql_engine {
     // is the Gaussian actor (actor_net + mean_net, obs -> act) and modules_actor/log_stds ([act], const_std = 0 only) follows the value
     // net at ls_off, padded to ap floats.  p_v, p_c1[], p_ct[] as IFQL's; p_a is the actor on obs; ddpgbc adds p_q[], the critic pair on
     // [obs | q_actions].  The infos (16 or 19) live in iql_info: [0, 32) of the last update, [32, 64) of the last loss probe.
-    bool iql = false;
     fql_iql_config qcfg{};
     size_t ls_off = 0;
     float *se_buf = nullptr, *ls_part = nullptr;   // [B]: squared error per row; [B, ap]: per-row terms of the log_stds gradient
@@ -532,17 +588,19 @@ struct fql_engine {
             }
             return n;
         };
-        nets[NET_C0] = bc ? Net{} : make(od + ad, cfg.value_hidden, cfg.num_value_hidden, 1, cfg.layer_norm != 0);
-        nets[NET_C1] = nets[NET_C0];
-        nets[NET_BC] = bc ? make(od + ad + BC_EMB, cfg.actor_hidden, cfg.num_actor_hidden, ad, cfg.actor_layer_norm != 0)   // policy(obs, x_t, emb(t)) (agents/bc.py:26-44)
-                     : (rebrac || iql) ? make(od, cfg.actor_hidden, cfg.num_actor_hidden, ad, cfg.actor_layer_norm != 0)   // actor (utils/networks.py:82-150)
-                     : sac ? make(od, cfg.actor_hidden, cfg.num_actor_hidden, 2 * pad16(ad), cfg.actor_layer_norm != 0)   // actor_net + [mean_net | log_std_net]
-                              : make(od + ad + 1, cfg.actor_hidden, cfg.num_actor_hidden, ad, cfg.actor_layer_norm != 0);
-        nets[NET_OS] = (rebrac || sac || bc) ? Net{} : (ifql || iql) ? make(od, cfg.value_hidden, cfg.num_value_hidden, 1, cfg.layer_norm != 0)   // value (agents/ifql.py:188-193)
-                            : make(od + ad, cfg.actor_hidden, cfg.num_actor_hidden, ad, cfg.actor_layer_norm != 0);
-        nets[NET_T0] = nets[NET_C0];
-        nets[NET_T1] = nets[NET_C0];
-        nets[NET_TA] = rebrac ? nets[NET_BC] : Net{};
+        auto actor = [&](int in, int out) { return make(in, cfg.actor_hidden, cfg.num_actor_hidden, out, cfg.actor_layer_norm != 0); };
+        auto value = [&](int in) { return make(in, cfg.value_hidden, cfg.num_value_hidden, 1, cfg.layer_norm != 0); };
+        for (Net& n : nets) n = Net{};
+        if (kind != AgentKind::BC) nets[NET_C0] = value(od + ad);
+        switch (kind) {
+            case AgentKind::FQL: nets[NET_BC] = actor(od + ad + 1, ad); nets[NET_OS] = actor(od + ad, ad); break;
+            case AgentKind::IFQL: nets[NET_BC] = actor(od + ad + 1, ad); nets[NET_OS] = value(od); break;   // value (agents/ifql.py:188-193)
+            case AgentKind::REBRAC: nets[NET_BC] = nets[NET_TA] = actor(od, ad); break;                      // actor (utils/networks.py:82-150)
+            case AgentKind::SAC: nets[NET_BC] = actor(od, 2 * pad16(ad)); break;                             // actor_net + [mean_net | log_std_net]
+            case AgentKind::BC: nets[NET_BC] = actor(od + ad + BC_EMB, ad); break;                           // policy(obs, x_t, emb(t)) (agents/bc.py:26-44)
+            case AgentKind::IQL: nets[NET_BC] = actor(od, ad); nets[NET_OS] = value(od); break;
+        }
+        nets[NET_C1] = nets[NET_T0] = nets[NET_T1] = nets[NET_C0];
         size_t off = 0;
         auto place_enc = [&](int ei) {
             if (!visual) return;
@@ -591,14 +649,14 @@ struct fql_engine {
             if (ni == NET_BC) place_enc(ENC_BC);
             if (ni == NET_OS) {
                 place_enc(ENC_OS);
-                if (sac) { alpha_off = off; off += 4; }   // modules_alpha/log_value: one float, padded to an Adam quad
-                if (iql && !qcfg.const_std) { ls_off = off; off += pad16(ad); }   // modules_actor/log_stds: [act], padded to ap
+                if (kind == AgentKind::SAC) { alpha_off = off; off += 4; }   // modules_alpha/log_value: one float, padded to an Adam quad
+                if (kind == AgentKind::IQL && !qcfg.const_std) { ls_off = off; off += pad16(ad); }   // modules_actor/log_stds: [act], padded to ap
                 n_train = off;
             }
             if (ni == NET_T1) place_enc(ENC_T);
         }
         n_total = off;
-        if (rebrac) critic_size = n_train;   // Polyak moves the critic pair and the actor (rebrac.py:131-133)
+        if (kind == AgentKind::REBRAC) critic_size = n_train;   // Polyak moves the critic pair and the actor (rebrac.py:131-133)
         for (int ni = 0; ni < NUM_NETS; ++ni)
             for (const Layer& L : nets[ni].layers)
                 if (L.in_p > 1024 || L.out_p > 1024) invalid("layer widths above 1024 are not supported (got %d -> %d)", L.in, L.out);
@@ -647,7 +705,7 @@ struct fql_engine {
         const Net& n = nets[NET_BC];
         const int nh = n.nl() - 1;
         const int H = n.layers[0].out_p;
-        bool ok = !ifql && !rebrac && !sac && !bc && !iql && !cfg.actor_layer_norm && cfg.act_dim <= 15 && nh >= 3 && (H == 256 || H == 512);   // (IFQL has no Euler chain in its update)
+        bool ok = kind == AgentKind::FQL && !cfg.actor_layer_norm && cfg.act_dim <= 15 && nh >= 3 && (H == 256 || H == 512);   // (the Euler chain is FQL's)
         for (int l = 0; l < nh && ok; ++l) ok = n.layers[l].out == H && n.layers[l].out_p == H;
         use_chain = ok;
         if (!ok) return;
@@ -705,9 +763,17 @@ struct fql_engine {
                                  {"modules_critic", "value_net", NET_C0, NET_C1, true, ENC_C},
                                  {"modules_target_critic", "value_net", NET_T0, NET_T1, false, ENC_T},
                                  {"modules_value", "value_net", NET_OS, -1, true, ENC_OS}};
-        const Mod* mods = iql ? iql_mods : sac ? sac_mods : rebrac ? rebrac_mods : ifql ? ifql_mods : fql_mods;
+        const Mod* mods = nullptr;   // BC: no modules, the leaves of one bare net
+        switch (kind) {
+            case AgentKind::FQL: mods = fql_mods; break;
+            case AgentKind::IFQL: mods = ifql_mods; break;
+            case AgentKind::REBRAC: mods = rebrac_mods; break;
+            case AgentKind::SAC: mods = sac_mods; break;
+            case AgentKind::BC: break;
+            case AgentKind::IQL: mods = iql_mods; break;
+        }
         int tid = 0;
-        if (bc) {   // agents/bc.py:26-44: a bare TrainState: Dense_0 (the head), then MLP_0/Dense_i and MLP_0/LayerNorm_i (jax dict order)
+        if (!mods) {   // agents/bc.py:26-44: a bare TrainState: Dense_0 (the head), then MLP_0/Dense_i and MLP_0/LayerNorm_i (jax dict order)
             const Net& n0 = nets[NET_BC];
             auto add = [&](const std::string& name, bool matrix, int rows, int cols, size_t o0, int rp, int cp) {
                 Leaf lf;
@@ -737,7 +803,7 @@ struct fql_engine {
                 add("MLP_0/LayerNorm_" + std::to_string(i) + "/scale", false, 1, a.out, a.g, 1, a.out_p);
             }
         }
-        for (int mi = 0; mi < (bc ? 0 : 4); ++mi) {
+        for (int mi = 0; mi < (mods ? 4 : 0); ++mi) {
             const Mod& m = mods[mi];
             if (m.n0 < 0) {   // modules_alpha/log_value: shape ()
                 Leaf lf;
@@ -807,7 +873,7 @@ struct fql_engine {
                 add(base + "LayerNorm_" + std::to_string(i) + "/bias", false, 1, a.out, a.be, b ? b->be : 0, 1, a.out_p);
                 add(base + "LayerNorm_" + std::to_string(i) + "/scale", false, 1, a.out, a.g, b ? b->g : 0, 1, a.out_p);
             }
-            if (m.actor && sac) {   // the two heads: column blocks [0, ap) and [ap, 2 ap) of the last layer, each read back as [H, act] / [act]
+            if (m.actor && kind == AgentKind::SAC) {   // the two heads: column blocks [0, ap) and [ap, 2 ap) of the last layer, each read back as [H, act] / [act]
                 const Layer& a = n0.layers.back();
                 const int ad = cfg.act_dim, ap = pad16(ad);
                 for (const char* head : {"log_std_net", "mean_net"}) {
@@ -818,7 +884,7 @@ struct fql_engine {
                     leaves.back().segs[0].chunk_w = ap;
                 }
             } else if (m.actor) {
-                if (iql && !qcfg.const_std)   // "log_stds" sorts between actor_net and mean_net
+                if (kind == AgentKind::IQL && !qcfg.const_std)   // "log_stds" sorts between actor_net and mean_net
                     add(std::string(m.name) + "/log_stds", false, 1, cfg.act_dim, ls_off, 0, 1, pad16(cfg.act_dim));
                 const Layer& a = n0.layers.back();
                 const std::string hb = std::string(m.name) + "/mean_net/";
@@ -849,14 +915,16 @@ struct fql_engine {
         for (const AdamChunk& c : ch) range[c.leaf + 1]++;
         for (int i = 0; i < n_train_leaves; ++i) range[i + 1] += range[i];
         {   // leaves (and so chunks) are ordered module by module: actor_bc_flow, actor_onestep_flow, critic
-            const char* fmods[3] = {"modules_actor_bc_flow/", "modules_actor_onestep_flow/", "modules_critic/"};
-            const char* imods[3] = {"modules_actor_flow/", "modules_value/", "modules_critic/"};
-            const char* rmods[3] = {"modules_actor/", "modules_critic/", "modules_critic/"};   // (two trained modules: the critic's range twice)
-            const char* smods[3] = {"modules_actor/", "modules_alpha/", "modules_critic/"};
-            const char* qmods[3] = {"modules_actor/", "modules_value/", "modules_critic/"};
-            const char* const* mods = iql ? qmods : sac ? smods : rebrac ? rmods : ifql ? imods : fmods;
+            static const char* const trained[kNumKinds][3] = {
+                {"modules_actor_bc_flow/", "modules_actor_onestep_flow/", "modules_critic/"},
+                {"modules_actor_flow/", "modules_value/", "modules_critic/"},
+                {"modules_actor/", "modules_critic/", "modules_critic/"},   // (ReBRAC, two trained modules: the critic's range twice)
+                {"modules_actor/", "modules_alpha/", "modules_critic/"},
+                {nullptr, nullptr, nullptr},                                // (BC, one module: every chunk)
+                {"modules_actor/", "modules_value/", "modules_critic/"}};
+            const char* const* mods = trained[(int)kind];
             for (int m = 0; m < 3; ++m) {
-                if (bc) { mod_chunk0[m] = 0; mod_chunkn[m] = n_chunks; continue; }   // one module: every chunk
+                if (!mods[m]) { mod_chunk0[m] = 0; mod_chunkn[m] = n_chunks; continue; }
                 int lo = 1 << 30, hi = -1;
                 for (const Leaf& lf : leaves)
                     if (lf.trainable && lf.name.rfind(mods[m], 0) == 0) { lo = std::min(lo, lf.train_id); hi = std::max(hi, lf.train_id); }
@@ -900,10 +968,11 @@ struct fql_engine {
         for (int ni = 0; ni <= NET_OS; ++ni)
             for (const Layer& L : nets[ni].layers) {
                 // ReBRAC's mean_net: variance_scaling(actor_fc_scale, fan_avg, uniform) (utils/networks.py:9-11,117)
-                const double scale = (rebrac && ni == NET_BC && &L == &nets[ni].layers.back()) ? (double)rcfg.actor_fc_scale
-                                     : (iql && ni == NET_BC && &L == &nets[ni].layers.back()) ? 1e-2   // Actor.final_fc_init_scale (utils/networks.py:106)
-                                                                                               : 1.0;
-                if (bc && &L == &nets[ni].layers.back()) {
+                const bool actor_head = ni == NET_BC && &L == &nets[ni].layers.back();
+                const double scale = !actor_head ? 1.0 : kind == AgentKind::REBRAC ? (double)rcfg.actor_fc_scale
+                                     : kind == AgentKind::IQL ? 1e-2   // Actor.final_fc_init_scale (utils/networks.py:106)
+                                                              : 1.0;
+                if (kind == AgentKind::BC && actor_head) {
                     // BC's Dense_0 is a bare nn.Dense (agents/bc.py:43): flax's default lecun_normal = variance_scaling(1, fan_in,
                     // truncated_normal): N(0, 1) truncated to [-2, 2], scaled by sqrt(1 / fan_in) / 0.87962566103423978
                     const double sd = std::sqrt(1.0 / (double)L.in) / 0.87962566103423978;
@@ -916,7 +985,7 @@ struct fql_engine {
                         }
                     continue;
                 }
-                if (sac && ni == NET_BC && &L == &nets[ni].layers.back()) {
+                if (kind == AgentKind::SAC && actor_head) {
                     // SAC's mean_net and log_std_net: variance_scaling(actor_fc_scale, fan_avg, uniform), [H, act] each (utils/networks.py:9-11,111-113)
                     const int ad = cfg.act_dim, ap = pad16(ad);
                     const double lim = std::sqrt(6.0 * (double)scfg.actor_fc_scale / (double)(L.in + ad));
@@ -3400,12 +3469,15 @@ struct fql_engine {
     int64_t macs_per_update() const {
         auto macs = [&](const Net& n) { int64_t m = 0; for (const Layer& L : n.layers) m += (int64_t)L.in * L.out; return m; };
         auto first = [&](const Net& n) { return (int64_t)n.layers[0].in * n.layers[0].out; };
-        if (rebrac) return rebrac_macs(true);
-        if (sac) return sac_macs();
-        if (bc) return bc_macs();
-        if (iql) return iql_macs();
+        switch (kind) {
+            case AgentKind::REBRAC: return rebrac_macs(true);
+            case AgentKind::SAC: return sac_macs();
+            case AgentKind::BC: return bc_macs();
+            case AgentKind::IQL: return iql_macs();
+            default: break;
+        }
         const int64_t os = macs(nets[NET_OS]), bc = macs(nets[NET_BC]), cr = macs(nets[NET_C0]);
-        if (ifql) {   // value on 2B rows + its backward on B; target pair; critic pair forward + backward (no input gradient); actor_flow forward + backward
+        if (kind == AgentKind::IFQL) {   // value on 2B rows + its backward on B; target pair; critic pair forward + backward (no input gradient); actor_flow forward + backward
             const int64_t fwd = 2 * os + 4 * cr + bc;
             const int64_t bwd = (2 * os - first(nets[NET_OS])) + 2 * (2 * cr - first(nets[NET_C0])) + (2 * bc - first(nets[NET_BC]));
             return (fwd + bwd) * (int64_t)B;
@@ -3457,11 +3529,14 @@ struct fql_engine {
         in_act = dalloc(W, (size_t)B * ad); in_rew = dalloc(W, B); in_mask = dalloc(W, B);
         for (int i = 0; i < 5; ++i) in_noise[i] = dalloc(W, (size_t)B * ad);
         in_idx = (int64_t*)dalloc(W, (size_t)B * 4);   // [2][B]: indices in use, staging of host indices (frames path)
-        if (ifql) { build_ifql_workspace(); return; }
-        if (rebrac) { in_nact = dalloc(W, (size_t)B * ad); build_rebrac_workspace(); return; }
-        if (sac) { build_sac_workspace(); return; }
-        if (bc) { build_bc_workspace(); return; }
-        if (iql) { build_iql_workspace(); return; }
+        switch (kind) {
+            case AgentKind::FQL: break;   // below
+            case AgentKind::IFQL: build_ifql_workspace(); return;
+            case AgentKind::REBRAC: in_nact = dalloc(W, (size_t)B * ad); build_rebrac_workspace(); return;
+            case AgentKind::SAC: build_sac_workspace(); return;
+            case AgentKind::BC: build_bc_workspace(); return;
+            case AgentKind::IQL: build_iql_workspace(); return;
+        }
         const int inp_c = nets[NET_OS].in_p(), inp_b = nets[NET_BC].in_p();
         X_os = dalloc(W, (size_t)3 * B * inp_c); X_bc = dalloc(W, (size_t)B * inp_b); X_eu = dalloc(W, (size_t)B * inp_b);
         X_c1 = dalloc(W, (size_t)B * inp_c); X_c2 = dalloc(W, (size_t)B * inp_c); X_ct = dalloc(W, (size_t)B * inp_c);
@@ -3612,12 +3687,9 @@ struct fql_engine {
     void fill_noise(SrcDesc& d, const fql_noise* nz, hipStream_t s) {
         const int ad = cfg.act_dim;
         if (!nz) return;
-        if (ifql && (nz->eps1 || nz->z || nz->eps2)) invalid("IFQL reads only x0 and t of fql_noise (eps1, z and eps2 must be NULL)");
-        if (rebrac && (nz->x0 || nz->t || nz->z || nz->eps2)) invalid("ReBRAC reads only eps1 of fql_noise (x0, t, z and eps2 must be NULL)");
-        if (sac && (nz->x0 || nz->t || nz->z)) invalid("SAC reads only eps1 and eps2 of fql_noise (x0, t and z must be NULL)");
-        if (iql && (nz->x0 || nz->t || nz->z || nz->eps2)) invalid("IQL reads only eps1 of fql_noise (x0, t, z and eps2 must be NULL)");
-        if (bc && (nz->eps1 || nz->z || nz->eps2)) invalid("BC reads only x0 and t of fql_noise (eps1, z and eps2 must be NULL)");
-        if (bc && nz->t && !is_device_ptr(nz->t))   // t = k / S on the grid (device pointers are the caller's to keep on it: read as round(t S))
+        const int given = (nz->eps1 ? NZ_EPS1 : 0) | (nz->x0 ? NZ_X0 : 0) | (nz->t ? NZ_T : 0) | (nz->z ? NZ_Z : 0) | (nz->eps2 ? NZ_EPS2 : 0);
+        if (given & ~desc().noise_reads) invalid("%s", desc().noise_refusal);
+        if (kind == AgentKind::BC && nz->t && !is_device_ptr(nz->t))   // t = k / S on the grid (device pointers are the caller's to keep on it: read as round(t S))
             for (int b = 0; b < B; ++b) {
                 const float ts = nz->t[b] * (float)bc_steps;
                 if (!(ts >= -1e-3f && ts <= (float)bc_steps + 1e-3f) || std::fabs(ts - std::nearbyint(ts)) > 1e-3f)
@@ -3637,6 +3709,7 @@ struct fql_engine {
         if (lo < 0 || hi > ds_size || lo >= hi) invalid("bad sampling range [%lld, %lld) for dataset of %lld rows", (long long)lo, (long long)hi, (long long)ds_size);
         SrcDesc d{};
         d.obs = ds_obs; d.act = ds_act; d.rew = ds_rew; d.mask = ds_mask; d.nobs = ds_nobs;
+        if (kind == AgentKind::REBRAC) { d.nact = ds_act; d.nact_rows = ds_size; }   // utils/datasets.py:96-100: actions[min(idx + 1, size - 1)], the whole dataset's size
         if (idx) {
             if (is_device_ptr(idx)) d.idx = idx;
             else {
@@ -3730,7 +3803,7 @@ struct fql_engine {
         set_source(d, s);
     }
     // where the infos of the last update are: DevState::info, or an IQL handle's own buffer
-    const float* info_src() const { return iql ? iql_info : &d_state->info[0]; }
+    const float* info_src() const { return kind == AgentKind::IQL ? iql_info : &d_state->info[0]; }
     void finish_info(float* info, int n, hipStream_t s) {
         if (!info) return;
         hip_touch();
@@ -3752,7 +3825,7 @@ struct fql_engine {
         ev->n_pad = n_pad;
         auto& W = ev->allocs;
         const int od = cfg.obs_dim, ad = cfg.act_dim;
-        if (bc) {   // sample_actions (prog_flow): the step-bias table and the loop-invariant C0 = obs W0 + b0 at the head of the program, then per
+        if (kind == AgentKind::BC) {   // sample_actions (prog_flow): the step-bias table and the loop-invariant C0 = obs W0 + b0 at the head of the program, then per
                     // Euler step layer 0 as a rank-act update of C0 plus the step's row, and layers 1.. of the 16-row Dense kernel, whose head
                     // epilogue adds v / S to the actions in place and on the last step writes the clipped actions (GF_EULER | GF_EULER_BARE)
             const int S = bc_steps, ap = pad16(ad);
@@ -3805,7 +3878,7 @@ struct fql_engine {
             evals[n_pad] = std::move(ev);
             return ref;
         }
-        if (rebrac || sac || iql) {   // sample_actions: the actor's forward over the rows (prog_os on p_os; NET_OS is empty here)
+        if (actor_on_obs()) {   // sample_actions: the actor's forward over the rows (prog_os on p_os; NET_OS is empty here)
             ev->X = dalloc(W, (size_t)n_pad * nets[NET_BC].in_p());
             ev->st_obs = dalloc(W, (size_t)n_pad * od);
             ev->st_noise = dalloc(W, (size_t)n_pad * ad);
@@ -3834,7 +3907,7 @@ struct fql_engine {
                          1.0f / (float)fs, (float)(s + 1) / (float)fs);
         schedule(ev->prog_os, W);
         schedule(ev->prog_flow, W);
-        if (ifql) {   // best-of-N scoring: the critic pair on every sample row
+        if (kind == AgentKind::IFQL) {   // best-of-N scoring: the critic pair on every sample row
             ev->Xq = dalloc(W, (size_t)n_pad * nets[NET_C0].in_p());
             for (int e = 0; e < 2; ++e) {
                 ev->p_q[e] = make_pass(W, NET_C0 + e, n_pad, ev->Xq, false, false);
@@ -3858,36 +3931,38 @@ struct fql_engine {
         evals[n_pad] = std::move(ev);
         return ref;
     }
-    void eval_rows(bool flow, const float* obs, const float* noise, uint64_t sd, int n, float* out, hipStream_t s, bool own_stream = false) {
+    // The row-chunk loop of every sampling path.  A chunk is <= 4096 rows (256 image rows) of rows_per_obs rows per observation: its
+    // observations and noise are staged, `body` enqueues what differs between the paths - the assemble launch, the program(s) and the
+    // finishing launch that writes the chunk's [m, act] actions to c.out - and the actions are copied out or, on the engine's own stream, waited for.
+    struct SampleSpec { float temperature = 0.f; int rows_per_obs = 1; bool need_noise = false; int enc = ENC_OS; };   // enc: the encoder of a visual agent's rows
+    struct SampleChunk { Eval& ev; const float *o, *z; float* out; int start, m; };   // observations [start, start + m) of the call
+    template <typename Body>
+    void sample_chunks(const float* obs, const float* noise, int n, float* out, hipStream_t s, bool own_stream, const SampleSpec& sp, Body&& body) {
         if (n <= 0) invalid("n must be positive (got %d)", n);
         if (!obs || !out) invalid("observations/out must not be NULL");
-        if (flow && !noise) invalid("noises must not be NULL");
-        const int od = cfg.obs_dim, ad = cfg.act_dim;
-        const int chunk_cap = visual ? 256 : 4096;
-        for (int start = 0; start < n; start += chunk_cap) {
-            const int m = std::min(chunk_cap, n - start);
-            Eval& ev = get_eval(visual ? (m + 63) & ~63 : pad16(m));
+        if (sp.need_noise && !noise) invalid("noises must not be NULL");
+        if (!(sp.temperature >= 0.0f)) invalid("temperature must be >= 0");
+        const int od = cfg.obs_dim, ad = cfg.act_dim, N = sp.rows_per_obs;
+        const int per = std::max(1, (visual ? 256 : 4096) / N);
+        for (int start = 0; start < n; start += per) {
+            const int m = std::min(per, n - start);
+            Eval& ev = get_eval(visual ? (m + 63) & ~63 : pad16(m * N));
             const float* o;
             if (visual) {   // `obs` is uint8 [n, H, W, C]: encode with the module's encoder, then proceed on the encodings
                 const size_t ib = (size_t)cfg.img_h * cfg.img_w * cfg.img_c;
                 const unsigned char* src = reinterpret_cast<const unsigned char*>(obs) + (size_t)start * ib;
                 HIP_CHECK(hipMemcpyAsync(ev.st_img, src, (size_t)m * ib, hipMemcpyDefault, s));
                 if (!is_device_ptr(src)) staged_host = true;
-                run_launches(flow ? ev.prog_enc_bc : ev.prog_enc_os, s);
-                o = flow ? ev.eb_bc.E : ev.eb_os.E;
+                run_launches(sp.enc == ENC_BC ? ev.prog_enc_bc : ev.prog_enc_os, s);
+                o = sp.enc == ENC_BC ? ev.eb_bc.E : ev.eb_os.E;
             } else {
                 o = stage(obs + (size_t)start * od, ev.st_obs, (size_t)m * od, s);
             }
-            const float* z = noise ? stage(noise + (size_t)start * ad, ev.st_noise, (size_t)m * ad, s) : nullptr;
+            const float* z = noise ? stage(noise + (size_t)start * N * ad, ev.st_noise, (size_t)m * N * ad, s) : nullptr;
             drain_staging(s);
-            AssembleArgs a{o, z, flow ? ev.Xf : ev.X, seed, sd + (uint64_t)start, m, ev.n_pad, od, ad,
-                           flow ? nets[NET_BC].in_p() : nets[NET_OS].in_p()};
-            hipLaunchKernelGGL(fql_assemble_kernel, dim3((ev.n_pad + 3) / 4), dim3(FQL_THREADS), 0, s, a);
-            run_launches(flow ? ev.prog_flow : ev.prog_os, s);
             float* dst = out + (size_t)start * ad;
             const bool dev_out = is_device_ptr(dst);
-            const float* src16 = flow ? ev.tgt : ev.p_os.out;
-            hipLaunchKernelGGL(fql_extract_kernel, dim3((m * ad + 255) / 256), dim3(256), 0, s, src16, dev_out ? dst : ev.st_out, m, ad, pad16(ad));
+            body(SampleChunk{ev, o, z, dev_out ? dst : ev.st_out, start, m});
             HIP_CHECK(hipGetLastError());
             if (!dev_out) {
                 HIP_CHECK(hipMemcpyAsync(dst, ev.st_out, (size_t)m * ad * sizeof(float), hipMemcpyDeviceToHost, s));
@@ -3898,125 +3973,84 @@ struct fql_engine {
             }
         }
     }
-    // ReBRAC sample_actions (agents/rebrac.py:136-152): clip(mode(actor(obs)) + clip(N(0, 1) actor_noise temperature, +-actor_noise_clip), -1, 1).
-    // noise: [n, act] raw N(0, 1) or null (Philox keyed by (seed, sd), row numbers of the call: chunking does not change the draw)
-    void rebrac_sample(const float* obs, const float* noise, uint64_t sd, float temperature, int n, float* out, hipStream_t s, bool own_stream) {
-        if (n <= 0) invalid("n must be positive (got %d)", n);
-        if (!obs || !out) invalid("observations/out must not be NULL");
-        if (!(temperature >= 0.0f)) invalid("temperature must be >= 0");
-        const int od = cfg.obs_dim, ad = cfg.act_dim, ap = pad16(ad);
-        for (int start = 0; start < n; start += 4096) {
-            const int m = std::min(4096, n - start);
-            Eval& ev = get_eval(pad16(m));
-            const float* o = stage(obs + (size_t)start * od, ev.st_obs, (size_t)m * od, s);
-            const float* z = noise ? stage(noise + (size_t)start * ad, ev.st_noise, (size_t)m * ad, s) : nullptr;
-            drain_staging(s);
-            AssembleArgs aa{o, nullptr, ev.X, seed, sd, m, ev.n_pad, od, 0, nets[NET_BC].in_p()};   // [obs | 0]
-            hipLaunchKernelGGL(fql_assemble_kernel, dim3((ev.n_pad + 3) / 4), dim3(FQL_THREADS), 0, s, aa);
-            run_launches(ev.prog_os, s);
-            float* dst = out + (size_t)start * ad;
-            const bool dev_out = is_device_ptr(dst);
-            RebracActArgs ra{ev.p_os.out, z, dev_out ? dst : ev.st_out, seed, sd, m, ad, ap, ad, ad, 0, start, z ? 1 : 2, rcfg.tanh_squash, 1,
-                             rcfg.actor_noise * temperature, rcfg.actor_noise_clip};
-            hipLaunchKernelGGL(fql_rebrac_act_kernel, dim3((m * ad + FQL_THREADS - 1) / FQL_THREADS), dim3(FQL_THREADS), 0, s, ra);
-            HIP_CHECK(hipGetLastError());
-            if (!dev_out) {
-                HIP_CHECK(hipMemcpyAsync(dst, ev.st_out, (size_t)m * ad * sizeof(float), hipMemcpyDeviceToHost, s));
-                HIP_CHECK(hipStreamSynchronize(s));
-            } else if (own_stream) {
-                HIP_CHECK(hipStreamSynchronize(s));
-            }
-        }
+    // FQL: the one-step actor, or (flow) the Euler flow of the BC actor on the caller's noises.  A seeded draw is keyed per chunk (sd + start).
+    void eval_rows(bool flow, const float* obs, const float* noise, uint64_t sd, int n, float* out, hipStream_t s, bool own_stream = false) {
+        const int od = cfg.obs_dim, ad = cfg.act_dim;
+        sample_chunks(obs, noise, n, out, s, own_stream, SampleSpec{0.f, 1, flow, flow ? ENC_BC : ENC_OS}, [&](const SampleChunk& c) {
+            AssembleArgs a{c.o, c.z, flow ? c.ev.Xf : c.ev.X, seed, sd + (uint64_t)c.start, c.m, c.ev.n_pad, od, ad,
+                           flow ? nets[NET_BC].in_p() : nets[NET_OS].in_p()};
+            hipLaunchKernelGGL(fql_assemble_kernel, dim3((c.ev.n_pad + 3) / 4), dim3(FQL_THREADS), 0, s, a);
+            run_launches(flow ? c.ev.prog_flow : c.ev.prog_os, s);
+            const float* src16 = flow ? c.ev.tgt : c.ev.p_os.out;
+            hipLaunchKernelGGL(fql_extract_kernel, dim3((c.m * ad + 255) / 256), dim3(256), 0, s, src16, c.out, c.m, ad, pad16(ad));
+        });
     }
-    // SAC sample_actions (agents/sac.py:125-136): clip(tanh(mean + exp(ls) temperature eps), -1, 1) (no tanh without tanh_squash).
-    // noise: [n, act] raw N(0, 1) or null (Philox keyed by (seed, sd), row numbers of the call: chunking does not change the draw)
-    void sac_sample(const float* obs, const float* noise, uint64_t sd, float temperature, int n, float* out, hipStream_t s, bool own_stream) {
-        if (n <= 0) invalid("n must be positive (got %d)", n);
-        if (!obs || !out) invalid("observations/out must not be NULL");
-        if (!(temperature >= 0.0f)) invalid("temperature must be >= 0");
+    // The actors on obs: the actor's forward over the rows, then the kind's own kernel on its output.  noise: [n, act] raw N(0, 1) or null
+    // (Philox keyed by (seed, sd) and the row number of the call: chunking does not change the draw).
+    //   ReBRAC (agents/rebrac.py:136-152): clip(mode(actor(obs)) + clip(N(0, 1) actor_noise temperature, +-actor_noise_clip), -1, 1)
+    //   SAC (agents/sac.py:125-136): clip(tanh(mean + exp(ls) temperature eps), -1, 1) (no tanh without tanh_squash)
+    //   IQL (agents/iql.py:158-169): clip(mean + exp(clip(log_stds)) temperature eps, -1, 1)
+    void sample_actor(const float* obs, const float* noise, uint64_t sd, float temperature, int n, float* out, hipStream_t s, bool own_stream) {
         const int od = cfg.obs_dim, ad = cfg.act_dim, ap = pad16(ad);
-        for (int start = 0; start < n; start += 4096) {
-            const int m = std::min(4096, n - start);
-            Eval& ev = get_eval(pad16(m));
-            const float* o = stage(obs + (size_t)start * od, ev.st_obs, (size_t)m * od, s);
-            const float* z = noise ? stage(noise + (size_t)start * ad, ev.st_noise, (size_t)m * ad, s) : nullptr;
-            drain_staging(s);
-            AssembleArgs aa{o, nullptr, ev.X, seed, sd, m, ev.n_pad, od, 0, nets[NET_BC].in_p()};   // [obs | 0]
-            hipLaunchKernelGGL(fql_assemble_kernel, dim3((ev.n_pad + 3) / 4), dim3(FQL_THREADS), 0, s, aa);
-            run_launches(ev.prog_os, s);
-            float* dst = out + (size_t)start * ad;
-            const bool dev_out = is_device_ptr(dst);
-            float* o_rows = dev_out ? dst : ev.st_out;
-            SacActArgs sa{ev.p_os.out, z, o_rows, o_rows, nullptr, seed, sd, m, ad, ap, ad, ad, 0, start, m, z ? 1 : 2, scfg.tanh_squash, 1,
-                          temperature};
-            hipLaunchKernelGGL(fql_sac_act_kernel, dim3((m + FQL_THREADS - 1) / FQL_THREADS), dim3(FQL_THREADS), 0, s, sa);
-            HIP_CHECK(hipGetLastError());
-            if (!dev_out) {
-                HIP_CHECK(hipMemcpyAsync(dst, ev.st_out, (size_t)m * ad * sizeof(float), hipMemcpyDeviceToHost, s));
-                HIP_CHECK(hipStreamSynchronize(s));
-            } else if (own_stream) {
-                HIP_CHECK(hipStreamSynchronize(s));
+        sample_chunks(obs, noise, n, out, s, own_stream, SampleSpec{temperature}, [&](const SampleChunk& c) {
+            const int m = c.m, start = c.start;
+            const float* z = c.z;
+            AssembleArgs aa{c.o, nullptr, c.ev.X, seed, sd, m, c.ev.n_pad, od, 0, nets[NET_BC].in_p()};   // [obs | 0]
+            hipLaunchKernelGGL(fql_assemble_kernel, dim3((c.ev.n_pad + 3) / 4), dim3(FQL_THREADS), 0, s, aa);
+            run_launches(c.ev.prog_os, s);
+            const float* mean = c.ev.p_os.out;
+            if (kind == AgentKind::REBRAC) {
+                RebracActArgs ra{mean, z, c.out, seed, sd, m, ad, ap, ad, ad, 0, start, z ? 1 : 2, rcfg.tanh_squash, 1,
+                                 rcfg.actor_noise * temperature, rcfg.actor_noise_clip};
+                hipLaunchKernelGGL(fql_rebrac_act_kernel, dim3((m * ad + FQL_THREADS - 1) / FQL_THREADS), dim3(FQL_THREADS), 0, s, ra);
+            } else if (kind == AgentKind::SAC) {
+                SacActArgs sa{mean, z, c.out, c.out, nullptr, seed, sd, m, ad, ap, ad, ad, 0, start, m, z ? 1 : 2, scfg.tanh_squash, 1, temperature};
+                hipLaunchKernelGGL(fql_sac_act_kernel, dim3((m + FQL_THREADS - 1) / FQL_THREADS), dim3(FQL_THREADS), 0, s, sa);
+            } else {
+                IqlSampleArgs sa{mean, qcfg.const_std ? nullptr : P + ls_off, z, c.out, seed, sd, m, ad, ap, start, temperature};
+                hipLaunchKernelGGL(fql_iql_sample_kernel, dim3((m * ad + FQL_THREADS - 1) / FQL_THREADS), dim3(FQL_THREADS), 0, s, sa);
             }
-        }
-    }
-    // IQL sample_actions (agents/iql.py:158-169): clip(mean + exp(clip(log_stds)) temperature eps, -1, 1).
-    // noise: [n, act] raw N(0, 1) or null (Philox keyed by (seed, sd), row numbers of the call: chunking does not change the draw)
-    void iql_sample(const float* obs, const float* noise, uint64_t sd, float temperature, int n, float* out, hipStream_t s, bool own_stream) {
-        if (n <= 0) invalid("n must be positive (got %d)", n);
-        if (!obs || !out) invalid("observations/out must not be NULL");
-        if (!(temperature >= 0.0f)) invalid("temperature must be >= 0");
-        const int od = cfg.obs_dim, ad = cfg.act_dim, ap = pad16(ad);
-        for (int start = 0; start < n; start += 4096) {
-            const int m = std::min(4096, n - start);
-            Eval& ev = get_eval(pad16(m));
-            const float* o = stage(obs + (size_t)start * od, ev.st_obs, (size_t)m * od, s);
-            const float* z = noise ? stage(noise + (size_t)start * ad, ev.st_noise, (size_t)m * ad, s) : nullptr;
-            drain_staging(s);
-            AssembleArgs aa{o, nullptr, ev.X, seed, sd, m, ev.n_pad, od, 0, nets[NET_BC].in_p()};   // [obs | 0]
-            hipLaunchKernelGGL(fql_assemble_kernel, dim3((ev.n_pad + 3) / 4), dim3(FQL_THREADS), 0, s, aa);
-            run_launches(ev.prog_os, s);
-            float* dst = out + (size_t)start * ad;
-            const bool dev_out = is_device_ptr(dst);
-            IqlSampleArgs sa{ev.p_os.out, qcfg.const_std ? nullptr : P + ls_off, z, dev_out ? dst : ev.st_out, seed, sd, m, ad, ap, start, temperature};
-            hipLaunchKernelGGL(fql_iql_sample_kernel, dim3((m * ad + FQL_THREADS - 1) / FQL_THREADS), dim3(FQL_THREADS), 0, s, sa);
-            HIP_CHECK(hipGetLastError());
-            if (!dev_out) {
-                HIP_CHECK(hipMemcpyAsync(dst, ev.st_out, (size_t)m * ad * sizeof(float), hipMemcpyDeviceToHost, s));
-                HIP_CHECK(hipStreamSynchronize(s));
-            } else if (own_stream) {
-                HIP_CHECK(hipStreamSynchronize(s));
-            }
-        }
+        });
     }
     // BC sample_actions (agents/bc.py:86-101): x ~ N(0, I); S times x += policy(obs, x, i / S) / S; clip.  Rows are independent (16-row
     // tiles and per-element kernels, the same at every n), so row j of a call equals the single-observation call on the same noise.
     // noise: [n, act] or null (Philox keyed by (seed, sd) and the row number of the call: chunking does not change the draw)
-    void bc_sample(const float* obs, const float* noise, uint64_t sd, int n, float* out, hipStream_t s, bool own_stream) {
-        if (n <= 0) invalid("n must be positive (got %d)", n);
-        if (!obs || !out) invalid("observations/out must not be NULL");
+    void sample_bc(const float* obs, const float* noise, uint64_t sd, int n, float* out, hipStream_t s, bool own_stream) {
         const int od = cfg.obs_dim, ad = cfg.act_dim, ap = pad16(ad);
-        for (int start = 0; start < n; start += 4096) {
-            const int m = std::min(4096, n - start);
-            Eval& ev = get_eval(pad16(m));
-            const float* o = stage(obs + (size_t)start * od, ev.st_obs, (size_t)m * od, s);
-            const float* z = noise ? stage(noise + (size_t)start * ad, ev.st_noise, (size_t)m * ad, s) : nullptr;
-            drain_staging(s);
-            BcAssembleArgs aa{o, z, ev.X, ev.Xf, seed, sd, m, ev.n_pad, od, ad, nets[NET_BC].in_p(), ap, start};
-            hipLaunchKernelGGL(fql_bc_assemble_kernel, dim3((ev.n_pad + 3) / 4), dim3(FQL_THREADS), 0, s, aa);
+        sample_chunks(obs, noise, n, out, s, own_stream, SampleSpec{}, [&](const SampleChunk& c) {
+            BcAssembleArgs aa{c.o, c.z, c.ev.X, c.ev.Xf, seed, sd, c.m, c.ev.n_pad, od, ad, nets[NET_BC].in_p(), ap, c.start};
+            hipLaunchKernelGGL(fql_bc_assemble_kernel, dim3((c.ev.n_pad + 3) / 4), dim3(FQL_THREADS), 0, s, aa);
+            run_launches(c.ev.prog_flow, s);
+            hipLaunchKernelGGL(fql_extract_kernel, dim3((c.m * ad + 255) / 256), dim3(256), 0, s, (const float*)c.ev.tgt, c.out, c.m, ad, ap);
+        });
+    }
+    // IFQL sample_actions (agents/ifql.py:123-155), per observation: num_samples noises through the Euler flow of actor_flow, clip, score by
+    // min(q1, q2) of the critic, keep the first argmax.  [n, od] is a batched extension of the reference's single observation: row by row
+    // equal to n calls with the same noises.  Chunks of <= 4096 sample rows.
+    void sample_best_of_n(const float* obs, const float* noise, uint64_t sd, int n, float* out, hipStream_t s, bool own_stream) {
+        const int od = cfg.obs_dim, ad = cfg.act_dim, ap = pad16(ad), N = num_samples;
+        sample_chunks(obs, noise, n, out, s, own_stream, SampleSpec{0.f, N}, [&](const SampleChunk& c) {
+            Eval& ev = c.ev;
+            IfqlRepeatArgs ra{c.o, c.z, ev.Xf, seed, sd, c.m, N, ev.n_pad, od, ad, nets[NET_BC].in_p(), c.start * N};
+            hipLaunchKernelGGL(fql_ifql_repeat_kernel, dim3((ev.n_pad + 3) / 4), dim3(FQL_THREADS), 0, s, ra);
             run_launches(ev.prog_flow, s);
-            float* dst = out + (size_t)start * ad;
-            const bool dev_out = is_device_ptr(dst);
-            hipLaunchKernelGGL(fql_extract_kernel, dim3((m * ad + 255) / 256), dim3(256), 0, s, (const float*)ev.tgt, dev_out ? dst : ev.st_out, m, ad, ap);
-            HIP_CHECK(hipGetLastError());
-            if (!dev_out) {
-                HIP_CHECK(hipMemcpyAsync(dst, ev.st_out, (size_t)m * ad * sizeof(float), hipMemcpyDeviceToHost, s));
-                HIP_CHECK(hipStreamSynchronize(s));
-            } else if (own_stream) {
-                HIP_CHECK(hipStreamSynchronize(s));
-            }
+            IfqlQinArgs qa{c.o, ev.tgt, ev.Xq, c.m, N, ev.n_pad, od, ad, ap, nets[NET_C0].in_p()};
+            hipLaunchKernelGGL(fql_ifql_qin_kernel, dim3((ev.n_pad + 3) / 4), dim3(FQL_THREADS), 0, s, qa);
+            run_launches(ev.prog_q, s);
+            IfqlSelectArgs sa{ev.p_q[0].out, ev.p_q[1].out, ev.tgt, c.out, c.m, N, ad, ap};
+            hipLaunchKernelGGL(fql_ifql_select_kernel, dim3((c.m + 3) / 4), dim3(FQL_THREADS), 0, s, sa);
+        });
+    }
+    // sample_actions of the handle's kind (the temperature is ReBRAC's, SAC's and IQL's)
+    void sample(const float* obs, const float* noise, uint64_t sd, float temperature, int n, float* out, hipStream_t s, bool own_stream) {
+        switch (kind) {
+            case AgentKind::FQL: eval_rows(false, obs, noise, sd, n, out, s, own_stream); break;
+            case AgentKind::IFQL: sample_best_of_n(obs, noise, sd, n, out, s, own_stream); break;
+            case AgentKind::BC: sample_bc(obs, noise, sd, n, out, s, own_stream); break;
+            default: sample_actor(obs, noise, sd, temperature, n, out, s, own_stream); break;
         }
     }
-    // ReBRAC batch sources: the FQL ones plus next_actions (explicit [B, act], or the dataset's actions one row on)
+    // ReBRAC host batches: the FQL ones plus next_actions [B, act] (source_from_dataset takes the dataset's actions one row on)
     void rebrac_source_from_batch(const float* obs, const float* act, const float* rew, const float* mask, const float* nobs, const float* nact,
                                   int batch, const fql_noise* nz, int advance, hipStream_t s) {
         if (batch != B) invalid("batch_size %d does not match the engine's workspace (%d); call fql_set_batch_size", batch, B);
@@ -4034,86 +4068,98 @@ struct fql_engine {
         drain_staging(s);
         set_source(d, s);
     }
-    void rebrac_source_from_dataset(const int64_t* idx, int batch, int64_t lo, int64_t hi, const fql_noise* nz, hipStream_t s) {
-        if (batch != B) invalid("batch_size %d does not match the engine's workspace (%d)", batch, B);
-        if (!ds_obs || ds_size <= 0) throw Invalid{"no dataset uploaded (fql_dataset_upload)"};
-        if (lo == 0 && hi == 0) hi = ds_size;
-        if (lo < 0 || hi > ds_size || lo >= hi) invalid("bad sampling range [%lld, %lld) for dataset of %lld rows", (long long)lo, (long long)hi, (long long)ds_size);
-        SrcDesc d{};
-        d.obs = ds_obs; d.act = ds_act; d.rew = ds_rew; d.mask = ds_mask; d.nobs = ds_nobs;
-        d.nact = ds_act; d.nact_rows = ds_size;   // utils/datasets.py:96-100: actions[min(idx + 1, size - 1)], the whole dataset's size
-        if (idx) {
-            if (is_device_ptr(idx)) d.idx = idx;
-            else {
-                hip_touch();
-                HIP_CHECK(hipMemcpyAsync(in_idx, idx, (size_t)B * sizeof(int64_t), hipMemcpyHostToDevice, s));
-                staged_host = true;
-                d.idx = in_idx;
-            }
-        } else {
-            d.use_rng_idx = 1; d.lo = lo; d.span = hi - lo;
-        }
-        fill_noise(d, nz, s);
-        d.advance = 1;
-        drain_staging(s);
-        set_source(d, s);
-    }
-    // IFQL sample_actions (agents/ifql.py:123-155), per observation: num_samples noises through the Euler flow of actor_flow, clip, score by
-    // min(q1, q2) of the critic, keep the first argmax.  [n, od] is a batched extension of the reference's single observation: row by row
-    // equal to n calls with the same noises.  Chunks of <= 4096 sample rows, as eval_rows.
-    void ifql_sample(const float* obs, const float* noise, uint64_t sd, int n, float* out, hipStream_t s, bool own_stream) {
-        if (n <= 0) invalid("n must be positive (got %d)", n);
-        if (!obs || !out) invalid("observations/out must not be NULL");
-        const int od = cfg.obs_dim, ad = cfg.act_dim, ap = pad16(ad), N = num_samples;
-        const int per = std::max(1, 4096 / N);
-        for (int start = 0; start < n; start += per) {
-            const int m = std::min(per, n - start);
-            Eval& ev = get_eval(pad16(m * N));
-            const float* o = stage(obs + (size_t)start * od, ev.st_obs, (size_t)m * od, s);
-            const float* z = noise ? stage(noise + (size_t)start * N * ad, ev.st_noise, (size_t)m * N * ad, s) : nullptr;
-            drain_staging(s);
-            IfqlRepeatArgs ra{o, z, ev.Xf, seed, sd, m, N, ev.n_pad, od, ad, nets[NET_BC].in_p(), start * N};
-            hipLaunchKernelGGL(fql_ifql_repeat_kernel, dim3((ev.n_pad + 3) / 4), dim3(FQL_THREADS), 0, s, ra);
-            run_launches(ev.prog_flow, s);
-            IfqlQinArgs qa{o, ev.tgt, ev.Xq, m, N, ev.n_pad, od, ad, ap, nets[NET_C0].in_p()};
-            hipLaunchKernelGGL(fql_ifql_qin_kernel, dim3((ev.n_pad + 3) / 4), dim3(FQL_THREADS), 0, s, qa);
-            run_launches(ev.prog_q, s);
-            float* dst = out + (size_t)start * ad;
-            const bool dev_out = is_device_ptr(dst);
-            IfqlSelectArgs sa{ev.p_q[0].out, ev.p_q[1].out, ev.tgt, dev_out ? dst : ev.st_out, m, N, ad, ap};
-            hipLaunchKernelGGL(fql_ifql_select_kernel, dim3((m + 3) / 4), dim3(FQL_THREADS), 0, s, sa);
-            HIP_CHECK(hipGetLastError());
-            if (!dev_out) {
-                HIP_CHECK(hipMemcpyAsync(dst, ev.st_out, (size_t)m * ad * sizeof(float), hipMemcpyDeviceToHost, s));
-                HIP_CHECK(hipStreamSynchronize(s));
-            } else if (own_stream) {
-                HIP_CHECK(hipStreamSynchronize(s));
-            }
-        }
-    }
 };
 
 // ================================================================================================
 // C ABI
 // ================================================================================================
-#define FQL_IFQL_REFUSES(h, what)                                                                          \
-    do {                                                                                                \
-        if ((h) && (h)->ifql) { (h)->err = what " is not available on an IFQL handle"; return FQL_E_STATE; } \
-        if ((h) && (h)->rebrac) { (h)->err = what " is not available on a ReBRAC handle"; return FQL_E_STATE; } \
-    } while (0)
-#define FQL_SAC_REFUSES(h, what)                                                                          \
-    do {                                                                                                \
-        if ((h) && (h)->sac) { (h)->err = what " is not available on a SAC handle"; return FQL_E_STATE; } \
-        if ((h) && (h)->iql) { (h)->err = what " is not available on an IQL handle"; return FQL_E_STATE; } \
-    } while (0)
-#define FQL_BC_REFUSES(h, what)                                                                        \
-    do {                                                                                              \
-        if ((h) && (h)->bc) { (h)->err = what " is not available on a BC handle"; return FQL_E_STATE; } \
-    } while (0)
-#define FQL_REBRAC_REFUSES(h, what, why)                                                                                  \
-    do {                                                                                                               \
-        if ((h) && (h)->rebrac) { (h)->err = what " is not available on a ReBRAC handle (" why ")"; return FQL_E_STATE; } \
-    } while (0)
+// Which kind of handle may call which entry point: one row per entry point that is not open to every kind, one column per AgentKind.
+// A cell is OK_ (admitted), NO_ (refused) or the refusal's hint; an ONLY_ row belongs to that kind alone.  A refusal is
+// FQL_E_STATE, "<entry point> is not available on <label> (<hint>)" or "<entry point> needs <label> (<create call>)".
+struct Admission {
+    const char* name;
+    int only;                          // >= 0: that AgentKind alone (the cells are unused)
+    const char* refuse[kNumKinds];     // FQL, IFQL, ReBRAC, SAC, BC, IQL
+};
+#define OK_ nullptr
+#define NO_ ""
+#define FQL_ALONE {OK_, NO_, NO_, NO_, NO_, NO_}
+#define ONLY_(k) (int)AgentKind::k, {}
+#define EP_TABLE(X) \
+    X(update_begin, -1, FQL_ALONE)                                                                                                 \
+    X(update_end, -1, FQL_ALONE)                                                                                                   \
+    X(update, -1, {OK_, OK_, "its batch has no next_actions: fql_rebrac_update", NO_, NO_, NO_})                                   \
+    X(total_loss, -1, {OK_, OK_, "its batch has no next_actions: fql_rebrac_total_loss", NO_, NO_, NO_})                           \
+    X(sample_actions, -1, {OK_, OK_, OK_, OK_, "fql_bc_sample_actions", OK_})                                                      \
+    X(flow_actions, -1, {OK_, OK_, "the actor is deterministic, there is no flow", NO_, NO_, NO_})                                 \
+    X(noise_from_jax_keys, -1, FQL_ALONE)                                                                                          \
+    X(dataset_add_frames, -1, FQL_ALONE)                                                                                           \
+    X(replay_create, -1, {OK_, NO_, NO_, OK_, NO_, NO_})                                                                           \
+    X(replay_add, -1, {OK_, NO_, NO_, OK_, NO_, NO_})                                                                              \
+    X(replay_add_frames, -1, FQL_ALONE)                                                                                            \
+    X(replay_size, -1, {OK_, NO_, NO_, OK_, NO_, NO_})                                                                             \
+    X(update_balanced, -1, FQL_ALONE)                                                                                              \
+    X(update_from_dataset_begin, -1, FQL_ALONE)                                                                                    \
+    X(update_from_dataset_begin_split, -1, FQL_ALONE)                                                                              \
+    X(update_begin_split, -1, FQL_ALONE)                                                                                           \
+    X(update_end_split, -1, FQL_ALONE)                                                                                             \
+    X(grad_buckets, -1, FQL_ALONE)                                                                                                 \
+    X(update_from_dataset, -1, {OK_, OK_, "the step kind is an argument: fql_rebrac_update_from_dataset", NO_, NO_, NO_})          \
+    X(info_wait, -1, {OK_, OK_, OK_, "14 infos: fql_info_wait_n", "4 infos: fql_info_wait_n", "16 or 19 infos: fql_info_wait_n"})  \
+    X(read_info, -1, {OK_, OK_, OK_, "14 infos: fql_read_info_n", "4 infos: fql_read_info_n", "16 or 19 infos: fql_read_info_n"})  \
+    X(profile_update, -1, {OK_, OK_, "FQL batch sources only", NO_, NO_, NO_})                                                     \
+    X(debug_workspace, -1, {OK_, OK_, "FQL workspaces only", NO_, NO_, NO_})                                                       \
+    X(dataset_upload_frames, -1, FQL_ALONE)                                                                                        \
+    X(update_from_frames, -1, FQL_ALONE)                                                                                           \
+    X(rebrac_update, ONLY_(REBRAC))                                                                                                \
+    X(rebrac_update_from_dataset, ONLY_(REBRAC))                                                                                   \
+    X(rebrac_total_loss, ONLY_(REBRAC))                                                                                            \
+    X(rebrac_sample_actions, ONLY_(REBRAC))                                                                                        \
+    X(rebrac_stats, ONLY_(REBRAC))                                                                                                 \
+    X(sac_update, ONLY_(SAC))                                                                                                      \
+    X(sac_update_from_dataset, ONLY_(SAC))                                                                                         \
+    X(sac_update_balanced, ONLY_(SAC))                                                                                             \
+    X(sac_total_loss, ONLY_(SAC))                                                                                                  \
+    X(sac_sample_actions, ONLY_(SAC))                                                                                              \
+    X(sac_stats, ONLY_(SAC))                                                                                                       \
+    X(iql_update, ONLY_(IQL))                                                                                                      \
+    X(iql_update_from_dataset, ONLY_(IQL))                                                                                         \
+    X(iql_total_loss, ONLY_(IQL))                                                                                                  \
+    X(iql_sample_actions, ONLY_(IQL))                                                                                              \
+    X(iql_stats, ONLY_(IQL))                                                                                                       \
+    X(bc_update, ONLY_(BC))                                                                                                        \
+    X(bc_update_from_dataset, ONLY_(BC))                                                                                           \
+    X(bc_policy_loss, ONLY_(BC))                                                                                                   \
+    X(bc_sample_actions, ONLY_(BC))                                                                                                \
+    X(bc_stats, ONLY_(BC))
+#define X(ep, ...) EP_##ep,
+enum EntryPoint { EP_TABLE(X) EP_COUNT };
+#undef X
+#define X(ep, ...) {"fql_" #ep, __VA_ARGS__},
+static const Admission k_admission[EP_COUNT] = {EP_TABLE(X)};
+#undef X
+#undef OK_
+#undef NO_
+#undef FQL_ALONE
+#undef ONLY_
+// false: h->err says why `h` may not call `ep`
+static bool admitted(fql_handle h, EntryPoint ep) {
+    const Admission& a = k_admission[ep];
+    const KindDesc& d = h->desc();
+    if (a.only >= 0) {
+        if ((int)h->kind == a.only) return true;
+        const KindDesc& o = k_kinds[a.only];
+        h->err = std::string(a.name) + " needs " + o.label + " (" + o.create + ")";
+        return false;
+    }
+    const char* hint = a.refuse[(int)h->kind];
+    if (!hint) return true;
+    h->err = std::string(a.name) + " is not available on " + d.label + (*hint ? std::string(" (") + hint + ")" : std::string());
+    return false;
+}
+// the first line of such an entry point; a null handle passes (the entry point's own check answers it)
+#define FQL_ADMIT(h, ep) \
+    do { if ((h) && !admitted((h), (ep))) return FQL_E_STATE; } while (0)
 // FQL_TRY: every entry point that may use HIP on the engine's buffers - updates still on the engine's AQL queues finish first.
 // FQL_TRY_FAST: the update entry points that can go to those queues themselves (run_update decides).
 #define FQL_TRY(h, ...) FQL_TRY_(h, ((h)->group_fence(), (h)->hip_touch()), __VA_ARGS__)
@@ -4133,11 +4179,6 @@ struct fql_engine {
         (h)->err = e.what();                               \
         return FQL_E_HIP;                                  \
     }
-
-static const char* k_info_names[FQL_NUM_INFO] = {
-    "critic/critic_loss", "critic/q_mean", "critic/q_max", "critic/q_min", "actor/actor_loss",
-    "actor/bc_flow_loss", "actor/distill_loss", "actor/q_loss", "actor/q", "actor/mse",
-    "grad/max", "grad/min", "grad/norm"};
 
 // ---- online fine-tuning: ring capacity, uint8 ring insert, the replay ring of balanced sampling ---------------------------------
 namespace {
@@ -4193,9 +4234,12 @@ void fql_default_config(fql_config* c) {
 
 const char* fql_last_error(fql_handle h) { return h ? h->err.c_str() : g_create_error.c_str(); }
 
-static int create_engine(const fql_config* cfg, const fql_ifql_config* icfg, const fql_rebrac_config* rcfg, const fql_sac_config* scfg,
-                         uint64_t seed, fql_handle* out, const fql_bc_config* bcfg = nullptr, const fql_iql_config* qcfg = nullptr);
-int fql_create(const fql_config* cfg, uint64_t seed, fql_handle* out) { return create_engine(cfg, nullptr, nullptr, nullptr, seed, out); }
+struct AgentSpec {
+    AgentKind kind;
+    const void* cfg;   // that kind's config struct (fql_ifql_config, ...); FQL has none
+};
+static int create_engine(const fql_config* cfg, AgentSpec agent, uint64_t seed, fql_handle* out);
+int fql_create(const fql_config* cfg, uint64_t seed, fql_handle* out) { return create_engine(cfg, {AgentKind::FQL, nullptr}, seed, out); }
 
 void fql_ifql_default_config(fql_ifql_config* c) {   // agents/ifql.py:231-250
     std::memset(c, 0, sizeof *c);
@@ -4204,7 +4248,7 @@ void fql_ifql_default_config(fql_ifql_config* c) {   // agents/ifql.py:231-250
 }
 int fql_ifql_create(const fql_config* cfg, const fql_ifql_config* icfg, uint64_t seed, fql_handle* out) {
     if (!icfg) { g_create_error = "icfg must not be NULL"; if (out) *out = nullptr; return FQL_E_INVALID; }
-    return create_engine(cfg, icfg, nullptr, nullptr, seed, out);
+    return create_engine(cfg, {AgentKind::IFQL, icfg}, seed, out);
 }
 void fql_rebrac_default_config(fql_rebrac_config* c) {   // agents/rebrac.py:222-244
     std::memset(c, 0, sizeof *c);
@@ -4217,14 +4261,8 @@ void fql_rebrac_default_config(fql_rebrac_config* c) {   // agents/rebrac.py:222
 }
 int fql_rebrac_create(const fql_config* cfg, const fql_rebrac_config* rcfg, uint64_t seed, fql_handle* out) {
     if (!rcfg) { g_create_error = "rcfg must not be NULL"; if (out) *out = nullptr; return FQL_E_INVALID; }
-    return create_engine(cfg, nullptr, rcfg, nullptr, seed, out);
+    return create_engine(cfg, {AgentKind::REBRAC, rcfg}, seed, out);
 }
-static const char* k_rebrac_info_names[FQL_REBRAC_NUM_INFO] = {
-    "critic/critic_loss", "critic/q_mean", "critic/q_max", "critic/q_min", "actor/total_loss", "actor/actor_loss", "actor/bc_loss",
-    "actor/std", "actor/mse", "grad/max", "grad/min", "grad/norm"};
-static const char* k_ifql_info_names[FQL_IFQL_NUM_INFO] = {
-    "value/value_loss", "value/v_mean", "value/v_max", "value/v_min", "critic/critic_loss", "critic/q_mean", "critic/q_max",
-    "critic/q_min", "actor/actor_loss", "grad/max", "grad/min", "grad/norm"};
 void fql_sac_default_config(fql_sac_config* c) {   // agents/sac.py get_config
     std::memset(c, 0, sizeof *c);
     c->target_entropy = NAN;
@@ -4236,67 +4274,54 @@ void fql_sac_default_config(fql_sac_config* c) {   // agents/sac.py get_config
 }
 int fql_sac_create(const fql_config* cfg, const fql_sac_config* scfg, uint64_t seed, fql_handle* out) {
     if (!scfg) { g_create_error = "scfg must not be NULL"; if (out) *out = nullptr; return FQL_E_INVALID; }
-    return create_engine(cfg, nullptr, nullptr, scfg, seed, out);
+    return create_engine(cfg, {AgentKind::SAC, scfg}, seed, out);
 }
-static const char* k_sac_info_names[FQL_SAC_NUM_INFO] = {
-    "critic/critic_loss", "critic/q_mean", "critic/q_max", "critic/q_min", "actor/total_loss", "actor/actor_loss", "actor/alpha_loss",
-    "actor/alpha", "actor/entropy", "actor/std", "actor/q", "grad/max", "grad/min", "grad/norm"};
-static const char* k_bc_info_names[FQL_BC_NUM_INFO] = {"bc_loss", "grad/max", "grad/min", "grad/norm"};
-static const char* k_iql_info_names[2][FQL_IQL_DDPGBC_NUM_INFO] = {
-    {"value/value_loss", "value/v_mean", "value/v_max", "value/v_min", "critic/critic_loss", "critic/q_mean", "critic/q_max", "critic/q_min",
-     "actor/actor_loss", "actor/adv", "actor/bc_log_prob", "actor/mse", "actor/std", "grad/max", "grad/min", "grad/norm", nullptr, nullptr, nullptr},
-    {"value/value_loss", "value/v_mean", "value/v_max", "value/v_min", "critic/critic_loss", "critic/q_mean", "critic/q_max", "critic/q_min",
-     "actor/actor_loss", "actor/q_loss", "actor/bc_loss", "actor/q_mean", "actor/q_abs_mean", "actor/bc_log_prob", "actor/mse", "actor/std",
-     "grad/max", "grad/min", "grad/norm"}};
-int fql_num_info(fql_handle h) {
-    if (h && h->iql) return h->qcfg.actor_loss == 1 ? FQL_IQL_DDPGBC_NUM_INFO : FQL_IQL_AWR_NUM_INFO;
-    return !h ? FQL_E_INVALID : h->bc ? FQL_BC_NUM_INFO : h->ifql ? FQL_IFQL_NUM_INFO : h->rebrac ? FQL_REBRAC_NUM_INFO : h->sac ? FQL_SAC_NUM_INFO : FQL_NUM_INFO;
-}
-const char* fql_handle_info_name(fql_handle h, int i) {
-    if (!h || i < 0 || i >= fql_num_info(h)) return nullptr;
-    if (h->iql) return k_iql_info_names[h->qcfg.actor_loss == 1 ? 1 : 0][i];
-    return h->bc ? k_bc_info_names[i] : h->ifql ? k_ifql_info_names[i] : h->rebrac ? k_rebrac_info_names[i] : h->sac ? k_sac_info_names[i] : k_info_names[i];
-}
+int fql_num_info(fql_handle h) { return h ? h->num_info() : FQL_E_INVALID; }
+const char* fql_handle_info_name(fql_handle h, int i) { return (!h || i < 0 || i >= h->num_info()) ? nullptr : h->info_names()[i]; }
 
-static int create_engine(const fql_config* cfg, const fql_ifql_config* icfg, const fql_rebrac_config* rcfg, const fql_sac_config* scfg,
-                         uint64_t seed, fql_handle* out, const fql_bc_config* bcfg, const fql_iql_config* qcfg) {
+static int create_engine(const fql_config* cfg, AgentSpec agent, uint64_t seed, fql_handle* out) {
     if (!cfg || !out) { g_create_error = "cfg/out must not be NULL"; return FQL_E_INVALID; }
     *out = nullptr;
-    if (icfg) {   // IFQL: state observations and fp32 only
-        if (cfg->encoder != 0) { g_create_error = "fql_ifql_create: visual encoders are not available for IFQL (encoder must be 0)"; return FQL_E_INVALID; }
-        if (cfg->precision != 0) { g_create_error = "fql_ifql_create: IFQL runs in fp32 only (precision must be 0)"; return FQL_E_INVALID; }
-        if (!(icfg->expectile > 0.0f && icfg->expectile < 1.0f)) { g_create_error = "fql_ifql_create: expectile must be in (0, 1)"; return FQL_E_INVALID; }
-        if (icfg->num_samples < 1 || icfg->num_samples > 4096) { g_create_error = "fql_ifql_create: num_samples must be in [1, 4096]"; return FQL_E_INVALID; }
+    const AgentKind kind = agent.kind;
+    const KindDesc& kd = k_kinds[(int)kind];
+    const auto* icfg = static_cast<const fql_ifql_config*>(agent.cfg);
+    const auto* rcfg = static_cast<const fql_rebrac_config*>(agent.cfg);
+    const auto* scfg = static_cast<const fql_sac_config*>(agent.cfg);
+    const auto* bcfg = static_cast<const fql_bc_config*>(agent.cfg);
+    const auto* qcfg = static_cast<const fql_iql_config*>(agent.cfg);
+    auto refuse = [&](const std::string& why) { g_create_error = std::string(kd.create) + ": " + why; return FQL_E_INVALID; };
+    if (kind != AgentKind::FQL) {   // every other kind: state observations and fp32 only
+        if (cfg->encoder != 0) return refuse(std::string("visual encoders are not available for ") + kd.name + " (encoder must be 0)");
+        if (cfg->precision != 0) return refuse(std::string(kd.name) + " runs in fp32 only (precision must be 0)");
     }
-    if (rcfg) {   // ReBRAC: state observations and fp32 only
-        if (cfg->encoder != 0) { g_create_error = "fql_rebrac_create: visual encoders are not available for ReBRAC (encoder must be 0)"; return FQL_E_INVALID; }
-        if (cfg->precision != 0) { g_create_error = "fql_rebrac_create: ReBRAC runs in fp32 only (precision must be 0)"; return FQL_E_INVALID; }
-        if (!(rcfg->actor_noise >= 0.0f) || !(rcfg->actor_noise_clip >= 0.0f)) { g_create_error = "fql_rebrac_create: actor_noise and actor_noise_clip must be >= 0"; return FQL_E_INVALID; }
-        if (!(rcfg->actor_fc_scale > 0.0f)) { g_create_error = "fql_rebrac_create: actor_fc_scale must be > 0"; return FQL_E_INVALID; }
-        if (!std::isfinite(rcfg->alpha_actor) || !std::isfinite(rcfg->alpha_critic)) { g_create_error = "fql_rebrac_create: alpha_actor and alpha_critic must be finite"; return FQL_E_INVALID; }
-        if (rcfg->tanh_squash != 0 && rcfg->tanh_squash != 1) { g_create_error = "fql_rebrac_create: tanh_squash must be 0 or 1"; return FQL_E_INVALID; }
-    }
-    if (scfg) {   // SAC: state observations and fp32 only
-        if (cfg->encoder != 0) { g_create_error = "fql_sac_create: visual encoders are not available for SAC (encoder must be 0)"; return FQL_E_INVALID; }
-        if (cfg->precision != 0) { g_create_error = "fql_sac_create: SAC runs in fp32 only (precision must be 0)"; return FQL_E_INVALID; }
-        if (scfg->state_dependent_std != 1) { g_create_error = "fql_sac_create: only state_dependent_std = 1 is available (the const_std=False vector form is not)"; return FQL_E_INVALID; }
-        if (scfg->tanh_squash != 0 && scfg->tanh_squash != 1) { g_create_error = "fql_sac_create: tanh_squash must be 0 or 1"; return FQL_E_INVALID; }
-        if (!(scfg->actor_fc_scale > 0.0f)) { g_create_error = "fql_sac_create: actor_fc_scale must be > 0"; return FQL_E_INVALID; }
-        if (!std::isnan(scfg->target_entropy) && !std::isfinite(scfg->target_entropy)) { g_create_error = "fql_sac_create: target_entropy must be finite or NaN (automatic)"; return FQL_E_INVALID; }
-        if (std::isnan(scfg->target_entropy) && !std::isfinite(scfg->target_entropy_multiplier)) { g_create_error = "fql_sac_create: target_entropy_multiplier must be finite"; return FQL_E_INVALID; }
-    }
-    if (bcfg) {   // BC: state observations and fp32 only
-        if (cfg->encoder != 0) { g_create_error = "fql_bc_create: visual encoders are not available for BC (encoder must be 0)"; return FQL_E_INVALID; }
-        if (cfg->precision != 0) { g_create_error = "fql_bc_create: BC runs in fp32 only (precision must be 0)"; return FQL_E_INVALID; }
-        if (bcfg->denoise_steps < 1 || bcfg->denoise_steps > 1024) { g_create_error = "fql_bc_create: denoise_steps must be in [1, 1024]"; return FQL_E_INVALID; }
-    }
-    if (qcfg) {   // IQL: state observations and fp32 only
-        if (cfg->encoder != 0) { g_create_error = "fql_iql_create: visual encoders are not available for IQL (encoder must be 0)"; return FQL_E_INVALID; }
-        if (cfg->precision != 0) { g_create_error = "fql_iql_create: IQL runs in fp32 only (precision must be 0)"; return FQL_E_INVALID; }
-        if (!(qcfg->expectile > 0.0f && qcfg->expectile < 1.0f)) { g_create_error = "fql_iql_create: expectile must be in (0, 1)"; return FQL_E_INVALID; }
-        if (!std::isfinite(qcfg->alpha)) { g_create_error = "fql_iql_create: alpha must be finite"; return FQL_E_INVALID; }
-        if (qcfg->actor_loss != 0 && qcfg->actor_loss != 1) { g_create_error = "fql_iql_create: actor_loss must be 0 (awr) or 1 (ddpgbc)"; return FQL_E_INVALID; }
-        if (qcfg->const_std != 0 && qcfg->const_std != 1) { g_create_error = "fql_iql_create: const_std must be 0 or 1"; return FQL_E_INVALID; }
+    switch (kind) {
+        case AgentKind::FQL: break;
+        case AgentKind::IFQL:
+            if (!(icfg->expectile > 0.0f && icfg->expectile < 1.0f)) return refuse("expectile must be in (0, 1)");
+            if (icfg->num_samples < 1 || icfg->num_samples > 4096) return refuse("num_samples must be in [1, 4096]");
+            break;
+        case AgentKind::REBRAC:
+            if (!(rcfg->actor_noise >= 0.0f) || !(rcfg->actor_noise_clip >= 0.0f)) return refuse("actor_noise and actor_noise_clip must be >= 0");
+            if (!(rcfg->actor_fc_scale > 0.0f)) return refuse("actor_fc_scale must be > 0");
+            if (!std::isfinite(rcfg->alpha_actor) || !std::isfinite(rcfg->alpha_critic)) return refuse("alpha_actor and alpha_critic must be finite");
+            if (rcfg->tanh_squash != 0 && rcfg->tanh_squash != 1) return refuse("tanh_squash must be 0 or 1");
+            break;
+        case AgentKind::SAC:
+            if (scfg->state_dependent_std != 1) return refuse("only state_dependent_std = 1 is available (the const_std=False vector form is not)");
+            if (scfg->tanh_squash != 0 && scfg->tanh_squash != 1) return refuse("tanh_squash must be 0 or 1");
+            if (!(scfg->actor_fc_scale > 0.0f)) return refuse("actor_fc_scale must be > 0");
+            if (!std::isnan(scfg->target_entropy) && !std::isfinite(scfg->target_entropy)) return refuse("target_entropy must be finite or NaN (automatic)");
+            if (std::isnan(scfg->target_entropy) && !std::isfinite(scfg->target_entropy_multiplier)) return refuse("target_entropy_multiplier must be finite");
+            break;
+        case AgentKind::BC:
+            if (bcfg->denoise_steps < 1 || bcfg->denoise_steps > 1024) return refuse("denoise_steps must be in [1, 1024]");
+            break;
+        case AgentKind::IQL:
+            if (!(qcfg->expectile > 0.0f && qcfg->expectile < 1.0f)) return refuse("expectile must be in (0, 1)");
+            if (!std::isfinite(qcfg->alpha)) return refuse("alpha must be finite");
+            if (qcfg->actor_loss != 0 && qcfg->actor_loss != 1) return refuse("actor_loss must be 0 (awr) or 1 (ddpgbc)");
+            if (qcfg->const_std != 0 && qcfg->const_std != 1) return refuse("const_std must be 0 or 1");
+            break;
     }
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
@@ -4308,13 +4333,17 @@ static int create_engine(const fql_config* cfg, const fql_ifql_config* icfg, con
     try {
         h->cfg = *cfg;
         h->seed = seed;
-        if (icfg) { h->ifql = true; h->expectile = icfg->expectile; h->num_samples = icfg->num_samples; }
-        if (rcfg) { h->rebrac = true; h->rcfg = *rcfg; }
-        if (bcfg) { h->bc = true; h->bc_steps = bcfg->denoise_steps; }
-        if (qcfg) { h->iql = true; h->qcfg = *qcfg; }
-        if (scfg) {   // sac.py create: target_entropy = -target_entropy_multiplier * action_dim when None
-            h->sac = true; h->scfg = *scfg;
-            h->target_entropy = std::isnan(scfg->target_entropy) ? -scfg->target_entropy_multiplier * (float)cfg->act_dim : scfg->target_entropy;
+        h->kind = kind;
+        switch (kind) {
+            case AgentKind::FQL: break;
+            case AgentKind::IFQL: h->expectile = icfg->expectile; h->num_samples = icfg->num_samples; break;
+            case AgentKind::REBRAC: h->rcfg = *rcfg; break;
+            case AgentKind::SAC:   // sac.py create: target_entropy = -target_entropy_multiplier * action_dim when None
+                h->scfg = *scfg;
+                h->target_entropy = std::isnan(scfg->target_entropy) ? -scfg->target_entropy_multiplier * (float)cfg->act_dim : scfg->target_entropy;
+                break;
+            case AgentKind::BC: h->bc_steps = bcfg->denoise_steps; break;
+            case AgentKind::IQL: h->qcfg = *qcfg; break;
         }
         if (cfg->encoder != 0) {   // visual agent (agents/fql.py:196-202): the MLPs see the 512-wide encoding instead of obs
             if (cfg->encoder != 1 && cfg->encoder != 2) invalid("encoder %d not available (0 = none, 1 = impala_small, 2 = impala)", cfg->encoder);
@@ -4351,7 +4380,7 @@ static int create_engine(const fql_config* cfg, const fql_ifql_config* icfg, con
         HIP_CHECK(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
         for (int l = 1; l < FQL_LANES; ++l) HIP_CHECK(hipStreamCreateWithFlags(&h->lane_streams[l], hipStreamNonBlocking));
         h->build_nets();
-        if (h->bc) {   // the timestep-embedding table, rows k = 0..S: freq_i = float32(exp_f64(-ln(10000) i / 8)),
+        if (kind == AgentKind::BC) {   // the timestep-embedding table, rows k = 0..S: freq_i = float32(exp_f64(-ln(10000) i / 8)),
                        // arg = float32(float32(t 10000) freq_i), [cos | sin] in fp64 of that fp32 argument, rounded to fp32
             const int S = h->bc_steps;
             std::vector<float> tab((size_t)(S + 1) * BC_EMB);
@@ -4381,7 +4410,7 @@ static int create_engine(const fql_config* cfg, const fql_ifql_config* icfg, con
         h->build_chain_weights();
         h->refresh_chain_weights(h->stream);
         HIP_CHECK(hipMalloc((void**)&h->d_state, sizeof(DevState)));
-        if (h->iql) {
+        if (kind == AgentKind::IQL) {
             HIP_CHECK(hipMalloc((void**)&h->iql_info, 2 * IQL_INFO_STRIDE * sizeof(float)));
             HIP_CHECK(hipMemset(h->iql_info, 0, 2 * IQL_INFO_STRIDE * sizeof(float)));
         }
@@ -4550,12 +4579,23 @@ static void run_update(fql_handle h, Program& pr, hipStream_t s, bool own_stream
     h->hip_touch();
     run_program(h, pr, s);
 }
+// The body of every entry point that is one whole update: source(s) points the step at its batch, `pr` runs through run_update, and
+// the first n_info infos go to `info` (null: none).
+extern "C++" {
+template <typename Source>
+static int update_with(fql_handle h, Program& pr, float* info, int n_info, void* stream, Source&& source) {
+    FQL_TRY_FAST(h, {
+        hipStream_t s = pick(h, stream);
+        source(s);
+        run_update(h, pr, s, stream == nullptr);
+        h->finish_info(info, n_info, s);
+    });
+}
+}
 
 int fql_update_begin(fql_handle h, const float* obs, const float* act, const float* rew, const float* mask,
                      const float* nobs, int batch_size, const fql_noise* noise, void* stream) {
-    FQL_IFQL_REFUSES(h, "fql_update_begin");
-    FQL_SAC_REFUSES(h, "fql_update_begin");
-    FQL_BC_REFUSES(h, "fql_update_begin");
+    FQL_ADMIT(h, EP_update_begin);
     if (!h) return FQL_E_INVALID;
     FQL_TRY(h, {
         hipStream_t s = pick(h, stream);
@@ -4566,9 +4606,7 @@ int fql_update_begin(fql_handle h, const float* obs, const float* act, const flo
     });
 }
 int fql_update_end(fql_handle h, float* info13, void* stream) {
-    FQL_IFQL_REFUSES(h, "fql_update_end");
-    FQL_SAC_REFUSES(h, "fql_update_end");
-    FQL_BC_REFUSES(h, "fql_update_end");
+    FQL_ADMIT(h, EP_update_end);
     if (!h) return FQL_E_INVALID;
     if (!h->began) { h->err = "fql_update_end without fql_update_begin"; return FQL_E_STATE; }
     FQL_TRY(h, {
@@ -4580,15 +4618,10 @@ int fql_update_end(fql_handle h, float* info13, void* stream) {
 }
 int fql_update(fql_handle h, const float* obs, const float* act, const float* rew, const float* mask, const float* nobs,
                int batch_size, const fql_noise* noise, float* info13, void* stream) {
-    FQL_REBRAC_REFUSES(h, "fql_update", "its batch has no next_actions: fql_rebrac_update");
-    FQL_SAC_REFUSES(h, "fql_update");
-    FQL_BC_REFUSES(h, "fql_update");
+    FQL_ADMIT(h, EP_update);
     if (h && !h->began) {
-        FQL_TRY_FAST(h, {
-            hipStream_t s = pick(h, stream);
+        return update_with(h, h->prog_full, info13, FQL_NUM_INFO, stream, [&](hipStream_t s) {
             h->source_from_batch(obs, act, rew, mask, nobs, batch_size, noise, 1, s);
-            run_update(h, h->prog_full, s, stream == nullptr);
-            h->finish_info(info13, FQL_NUM_INFO, s);
         });
     }
     int rc = fql_update_begin(h, obs, act, rew, mask, nobs, batch_size, noise, stream);
@@ -4619,9 +4652,7 @@ int fql_set_rng_stream(fql_handle h, uint64_t stream_id) {
 
 int fql_total_loss(fql_handle h, const float* obs, const float* act, const float* rew, const float* mask, const float* nobs,
                    int batch_size, const fql_noise* noise, float* loss, float* info10, void* stream) {
-    FQL_REBRAC_REFUSES(h, "fql_total_loss", "its batch has no next_actions: fql_rebrac_total_loss");
-    FQL_SAC_REFUSES(h, "fql_total_loss");
-    FQL_BC_REFUSES(h, "fql_total_loss");
+    FQL_ADMIT(h, EP_total_loss);
     if (!h) return FQL_E_INVALID;
     FQL_TRY(h, {
         hipStream_t s = pick(h, stream);
@@ -4630,7 +4661,7 @@ int fql_total_loss(fql_handle h, const float* obs, const float* act, const float
         float tmp[10];
         HIP_CHECK(hipMemcpyAsync(tmp, &h->d_state->info[0], sizeof tmp, hipMemcpyDeviceToHost, s));
         HIP_CHECK(hipStreamSynchronize(s));
-        if (h->ifql) {   // agents/ifql.py:79-98: value + critic + actor; nine infos
+        if (h->kind == AgentKind::IFQL) {   // agents/ifql.py:79-98: value + critic + actor; nine infos
             if (loss) *loss = tmp[0] + tmp[4] + tmp[8];
             if (info10) std::memcpy(info10, tmp, 9 * sizeof(float));
         } else {
@@ -4641,18 +4672,12 @@ int fql_total_loss(fql_handle h, const float* obs, const float* act, const float
 }
 
 int fql_sample_actions(fql_handle h, const float* obs, int n, const float* noise, uint64_t seed, float* out, void* stream) {
-    FQL_BC_REFUSES(h, "fql_sample_actions (fql_bc_sample_actions)");
+    FQL_ADMIT(h, EP_sample_actions);
     if (!h) return FQL_E_INVALID;
-    if (h->rebrac) FQL_TRY(h, h->rebrac_sample(obs, noise, seed, 1.0f, n, out, pick(h, stream), stream == nullptr));
-    if (h->sac) FQL_TRY(h, h->sac_sample(obs, noise, seed, 1.0f, n, out, pick(h, stream), stream == nullptr));
-    if (h->iql) FQL_TRY(h, h->iql_sample(obs, noise, seed, 1.0f, n, out, pick(h, stream), stream == nullptr));
-    if (h->ifql) FQL_TRY(h, h->ifql_sample(obs, noise, seed, n, out, pick(h, stream), stream == nullptr));
-    FQL_TRY(h, h->eval_rows(false, obs, noise, seed, n, out, pick(h, stream), stream == nullptr));
+    FQL_TRY(h, h->sample(obs, noise, seed, 1.0f, n, out, pick(h, stream), stream == nullptr));
 }
 int fql_flow_actions(fql_handle h, const float* obs, const float* noises, int n, float* out, void* stream) {
-    FQL_REBRAC_REFUSES(h, "fql_flow_actions", "the actor is deterministic, there is no flow");
-    FQL_SAC_REFUSES(h, "fql_flow_actions");
-    FQL_BC_REFUSES(h, "fql_flow_actions");
+    FQL_ADMIT(h, EP_flow_actions);
     if (!h) return FQL_E_INVALID;
     FQL_TRY(h, h->eval_rows(true, obs, noises, 0, n, out, pick(h, stream), stream == nullptr));
 }
@@ -4708,9 +4733,7 @@ int fql_dataset_size(fql_handle h, int64_t* size, int64_t* pointer) {
 }
 // ---- online fine-tuning: ring capacity, uint8 ring insert, the replay ring of balanced sampling (helpers above extern "C")
 int fql_noise_from_jax_keys(fql_handle h, const uint32_t* keys10, int partitionable, int batch_size, fql_noise* out, void* stream) {
-    FQL_IFQL_REFUSES(h, "fql_noise_from_jax_keys");
-    FQL_SAC_REFUSES(h, "fql_noise_from_jax_keys");
-    FQL_BC_REFUSES(h, "fql_noise_from_jax_keys");
+    FQL_ADMIT(h, EP_noise_from_jax_keys);
     if (!h || !keys10 || !out) return FQL_E_INVALID;
     FQL_TRY(h, {
         if (batch_size != h->B) invalid("batch_size %d does not match the engine's workspace (%d); call fql_set_batch_size", batch_size, h->B);
@@ -4761,9 +4784,7 @@ int fql_dataset_reserve(fql_handle h, int64_t capacity) {
     });
 }
 int fql_dataset_add_frames(fql_handle h, const uint8_t* frame, const uint8_t* next_frame, const float* ac, float reward, float mask) {
-    FQL_IFQL_REFUSES(h, "fql_dataset_add_frames");
-    FQL_SAC_REFUSES(h, "fql_dataset_add_frames");
-    FQL_BC_REFUSES(h, "fql_dataset_add_frames");
+    FQL_ADMIT(h, EP_dataset_add_frames);
     if (!h) return FQL_E_INVALID;
     FQL_TRY(h, {
         if (!h->visual || !h->ds_frames) throw Invalid{"no frames dataset allocated (fql_dataset_upload_frames)"};
@@ -4775,9 +4796,7 @@ int fql_dataset_add_frames(fql_handle h, const uint8_t* frame, const uint8_t* ne
     });
 }
 int fql_replay_create(fql_handle h, int64_t capacity) {
-    FQL_IFQL_REFUSES(h, "fql_replay_create");
-    if (h && h->iql) { h->err = "fql_replay_create is not available on an IQL handle"; return FQL_E_STATE; }
-    FQL_BC_REFUSES(h, "fql_replay_create");
+    FQL_ADMIT(h, EP_replay_create);
     if (!h) return FQL_E_INVALID;
     FQL_TRY(h, {
         if (capacity < 1) invalid("fql_replay_create: capacity %lld", (long long)capacity);
@@ -4797,9 +4816,7 @@ int fql_replay_create(fql_handle h, int64_t capacity) {
     });
 }
 int fql_replay_add(fql_handle h, const float* ob, const float* ac, float reward, float mask, const float* nob) {
-    FQL_IFQL_REFUSES(h, "fql_replay_add");
-    if (h && h->iql) { h->err = "fql_replay_add is not available on an IQL handle"; return FQL_E_STATE; }
-    FQL_BC_REFUSES(h, "fql_replay_add");
+    FQL_ADMIT(h, EP_replay_add);
     if (!h) return FQL_E_INVALID;
     FQL_TRY(h, {
         if (h->rb_cap <= 0 || h->visual) throw Invalid{"fql_replay_add: no state replay ring (fql_replay_create; frames agents use fql_replay_add_frames)"};
@@ -4810,9 +4827,7 @@ int fql_replay_add(fql_handle h, const float* ob, const float* ac, float reward,
     });
 }
 int fql_replay_add_frames(fql_handle h, const uint8_t* frame, const uint8_t* next_frame, const float* ac, float reward, float mask) {
-    FQL_IFQL_REFUSES(h, "fql_replay_add_frames");
-    FQL_SAC_REFUSES(h, "fql_replay_add_frames");
-    FQL_BC_REFUSES(h, "fql_replay_add_frames");
+    FQL_ADMIT(h, EP_replay_add_frames);
     if (!h) return FQL_E_INVALID;
     FQL_TRY(h, {
         if (h->rb_cap <= 0 || !h->visual) throw Invalid{"fql_replay_add_frames: no frames replay ring (fql_replay_create on a frames agent)"};
@@ -4824,9 +4839,7 @@ int fql_replay_add_frames(fql_handle h, const uint8_t* frame, const uint8_t* nex
     });
 }
 int fql_replay_size(fql_handle h, int64_t* size, int64_t* pointer) {
-    FQL_IFQL_REFUSES(h, "fql_replay_size");
-    if (h && h->iql) { h->err = "fql_replay_size is not available on an IQL handle"; return FQL_E_STATE; }
-    FQL_BC_REFUSES(h, "fql_replay_size");
+    FQL_ADMIT(h, EP_replay_size);
     if (!h) return FQL_E_INVALID;
     if (size) *size = h->rb_size;
     if (pointer) *pointer = h->rb_ptr;
@@ -4834,25 +4847,18 @@ int fql_replay_size(fql_handle h, int64_t* size, int64_t* pointer) {
 }
 int fql_update_balanced(fql_handle h, const int64_t* idx_dataset, const int64_t* idx_replay, const int32_t* crop_froms, int batch_size,
                         const fql_noise* noise, float* info13, void* stream) {
-    FQL_IFQL_REFUSES(h, "fql_update_balanced");
-    FQL_SAC_REFUSES(h, "fql_update_balanced");
-    FQL_BC_REFUSES(h, "fql_update_balanced");
+    FQL_ADMIT(h, EP_update_balanced);
     if (!h) return FQL_E_INVALID;
     if (h->began) { h->err = "fql_update_balanced between fql_update_begin and fql_update_end"; return FQL_E_STATE; }
-    FQL_TRY_FAST(h, {
-        hipStream_t s = pick(h, stream);
+    return update_with(h, h->prog_full, info13, FQL_NUM_INFO, stream, [&](hipStream_t s) {
         if (h->visual) h->hip_touch();
         h->source_balanced(idx_dataset, idx_replay, crop_froms, batch_size, noise, s);
-        run_update(h, h->prog_full, s, stream == nullptr);
-        h->finish_info(info13, FQL_NUM_INFO, s);
     });
 }
 
 int fql_update_from_dataset_begin(fql_handle h, const int64_t* idx, int batch_size, int64_t lo, int64_t hi,
                                   const fql_noise* noise, void* stream) {
-    FQL_IFQL_REFUSES(h, "fql_update_from_dataset_begin");
-    FQL_SAC_REFUSES(h, "fql_update_from_dataset_begin");
-    FQL_BC_REFUSES(h, "fql_update_from_dataset_begin");
+    FQL_ADMIT(h, EP_update_from_dataset_begin);
     if (!h) return FQL_E_INVALID;
     FQL_TRY(h, {
         hipStream_t s = pick(h, stream);
@@ -4864,9 +4870,7 @@ int fql_update_from_dataset_begin(fql_handle h, const int64_t* idx, int batch_si
 }
 int fql_update_from_dataset_begin_split(fql_handle h, const int64_t* idx, int batch_size, int64_t lo, int64_t hi,
                                         const fql_noise* noise, void* stream0, void* stream1) {
-    FQL_IFQL_REFUSES(h, "fql_update_from_dataset_begin_split");
-    FQL_SAC_REFUSES(h, "fql_update_from_dataset_begin_split");
-    FQL_BC_REFUSES(h, "fql_update_from_dataset_begin_split");
+    FQL_ADMIT(h, EP_update_from_dataset_begin_split);
     if (!h) return FQL_E_INVALID;
     if (!h->split_ok || !stream0 || !stream1 || stream0 == stream1) { h->err = "split update unavailable (needs two distinct streams and a two-lane program)"; return FQL_E_STATE; }
     FQL_TRY(h, {
@@ -4877,9 +4881,7 @@ int fql_update_from_dataset_begin_split(fql_handle h, const int64_t* idx, int ba
 }
 int fql_update_begin_split(fql_handle h, const float* obs, const float* act, const float* rew, const float* mask, const float* nobs,
                            int batch_size, const fql_noise* noise, void* stream0, void* stream1) {
-    FQL_IFQL_REFUSES(h, "fql_update_begin_split");
-    FQL_SAC_REFUSES(h, "fql_update_begin_split");
-    FQL_BC_REFUSES(h, "fql_update_begin_split");
+    FQL_ADMIT(h, EP_update_begin_split);
     if (!h) return FQL_E_INVALID;
     if (!h->split_ok || !stream0 || !stream1 || stream0 == stream1) { h->err = "split update unavailable (needs two distinct streams and a two-lane program)"; return FQL_E_STATE; }
     FQL_TRY(h, {
@@ -4889,9 +4891,7 @@ int fql_update_begin_split(fql_handle h, const float* obs, const float* act, con
     });
 }
 int fql_update_end_split(fql_handle h, float* info13, void* stream0, void* stream1) {
-    FQL_IFQL_REFUSES(h, "fql_update_end_split");
-    FQL_SAC_REFUSES(h, "fql_update_end_split");
-    FQL_BC_REFUSES(h, "fql_update_end_split");
+    FQL_ADMIT(h, EP_update_end_split);
     if (!h) return FQL_E_INVALID;
     if (!h->began) { h->err = "fql_update_end_split without fql_update_begin"; return FQL_E_STATE; }
     if (!stream0 || !stream1 || stream0 == stream1) { h->err = "fql_update_end_split needs two distinct streams"; return FQL_E_STATE; }
@@ -4902,9 +4902,7 @@ int fql_update_end_split(fql_handle h, float* info13, void* stream0, void* strea
     });
 }
 int fql_grad_buckets(fql_handle h, size_t offsets[2], size_t lengths[2]) {
-    FQL_IFQL_REFUSES(h, "fql_grad_buckets");
-    FQL_SAC_REFUSES(h, "fql_grad_buckets");
-    FQL_BC_REFUSES(h, "fql_grad_buckets");
+    FQL_ADMIT(h, EP_grad_buckets);
     if (!h || !offsets || !lengths) return FQL_E_INVALID;
     // bucket 0: both critic members + the BC flow actor (all produced on lane 1); bucket 1: the one-step actor (lane 0's tail)
     offsets[0] = 0; lengths[0] = h->nets[NET_OS].off;
@@ -4913,16 +4911,11 @@ int fql_grad_buckets(fql_handle h, size_t offsets[2], size_t lengths[2]) {
 }
 int fql_update_from_dataset(fql_handle h, const int64_t* idx, int batch_size, int64_t lo, int64_t hi, const fql_noise* noise,
                             float* info13, void* stream) {
-    FQL_REBRAC_REFUSES(h, "fql_update_from_dataset", "the step kind is an argument: fql_rebrac_update_from_dataset");
-    FQL_SAC_REFUSES(h, "fql_update_from_dataset");
-    FQL_BC_REFUSES(h, "fql_update_from_dataset");
+    FQL_ADMIT(h, EP_update_from_dataset);
     if (h && h->visual) return fql_update_from_frames(h, idx, nullptr, batch_size, lo, hi, noise, info13, stream);
     if (h && !h->began) {
-        FQL_TRY_FAST(h, {
-            hipStream_t s = pick(h, stream);
+        return update_with(h, h->prog_full, info13, FQL_NUM_INFO, stream, [&](hipStream_t s) {
             h->source_from_dataset(idx, batch_size, lo, hi, noise, s);
-            run_update(h, h->prog_full, s, stream == nullptr);
-            h->finish_info(info13, FQL_NUM_INFO, s);
         });
     }
     int rc = fql_update_from_dataset_begin(h, idx, batch_size, lo, hi, noise, stream);
@@ -4937,16 +4930,14 @@ int fql_info_enqueue(fql_handle h, void* stream, uint64_t* ticket) {
         const uint64_t k = h->info_seq++;
         const int slot = (int)(k % fql_engine::kInfoRing);
         HIP_CHECK(hipMemcpyAsync(h->h_info_ring[slot], h->info_src(),
-                                 (h->iql ? fql_num_info(h) : h->sac ? FQL_SAC_NUM_INFO : FQL_NUM_INFO) * sizeof(float), hipMemcpyDeviceToHost, s));
+                                 std::max(h->num_info(), FQL_NUM_INFO) * sizeof(float), hipMemcpyDeviceToHost, s));
         HIP_CHECK(hipEventRecord(h->info_ev[slot], s));
         *ticket = k;
     });
 }
 static int info_wait(fql_handle h, uint64_t ticket, float* info13_host, int n);
 int fql_info_wait(fql_handle h, uint64_t ticket, float* info13_host) {
-    if (h && h->iql) { h->err = "fql_info_wait is not available on an IQL handle (16 or 19 infos: fql_info_wait_n)"; return FQL_E_STATE; }
-    FQL_SAC_REFUSES(h, "fql_info_wait (14 infos: fql_info_wait_n)");
-    FQL_BC_REFUSES(h, "fql_info_wait (4 infos: fql_info_wait_n)");
+    FQL_ADMIT(h, EP_info_wait);
     return info_wait(h, ticket, info13_host, FQL_NUM_INFO);
 }
 int fql_info_wait_n(fql_handle h, uint64_t ticket, float* out, int n) {
@@ -4975,9 +4966,7 @@ int fql_synchronize(fql_handle h, int* mode) {
 }
 
 int fql_read_info(fql_handle h, float* info13_host) {
-    if (h && h->iql) { h->err = "fql_read_info is not available on an IQL handle (16 or 19 infos: fql_read_info_n)"; return FQL_E_STATE; }
-    FQL_SAC_REFUSES(h, "fql_read_info (14 infos: fql_read_info_n)");
-    FQL_BC_REFUSES(h, "fql_read_info (4 infos: fql_read_info_n)");
+    FQL_ADMIT(h, EP_read_info);
     if (!h || !info13_host) return FQL_E_INVALID;
     FQL_TRY(h, {
         HIP_CHECK(hipDeviceSynchronize());
@@ -5008,35 +4997,27 @@ void* fql_stream(fql_handle h) { return h ? (void*)h->stream : nullptr; }
 
 // ---- ReBRAC (agents/rebrac.py) ---------------------------------------------------------------------------------------------------
 // One update: the full program (full_update != 0) or the critic-only one, through run_update (the AQL form and the graph are bitwise equal).
-#define FQL_REBRAC_ONLY(h, what)                                                                           \
-    do {                                                                                                \
-        if (!(h)) return FQL_E_INVALID;                                                                 \
-        if (!(h)->rebrac) { (h)->err = what " needs a ReBRAC handle (fql_rebrac_create)"; return FQL_E_STATE; } \
-    } while (0)
 int fql_rebrac_update(fql_handle h, const float* obs, const float* act, const float* rew, const float* masks, const float* next_obs,
                       const float* next_actions, int batch_size, const fql_noise* noise, int full_update, float* info13, void* stream) {
-    FQL_REBRAC_ONLY(h, "fql_rebrac_update");
-    FQL_TRY_FAST(h, {
-        hipStream_t s = pick(h, stream);
+    if (!h) return FQL_E_INVALID;
+    FQL_ADMIT(h, EP_rebrac_update);
+    return update_with(h, full_update ? h->prog_full : h->prog_critic, info13, FQL_NUM_INFO, stream, [&](hipStream_t s) {
         h->rebrac_source_from_batch(obs, act, rew, masks, next_obs, next_actions, batch_size, noise, 1, s);
-        run_update(h, full_update ? h->prog_full : h->prog_critic, s, stream == nullptr);
-        h->finish_info(info13, FQL_NUM_INFO, s);
     });
 }
 int fql_rebrac_update_from_dataset(fql_handle h, const int64_t* idx, int batch_size, int64_t lo, int64_t hi, const fql_noise* noise,
                                    int full_update, float* info13, void* stream) {
-    FQL_REBRAC_ONLY(h, "fql_rebrac_update_from_dataset");
-    FQL_TRY_FAST(h, {
-        hipStream_t s = pick(h, stream);
-        h->rebrac_source_from_dataset(idx, batch_size, lo, hi, noise, s);
-        run_update(h, full_update ? h->prog_full : h->prog_critic, s, stream == nullptr);
-        h->finish_info(info13, FQL_NUM_INFO, s);
+    if (!h) return FQL_E_INVALID;
+    FQL_ADMIT(h, EP_rebrac_update_from_dataset);
+    return update_with(h, full_update ? h->prog_full : h->prog_critic, info13, FQL_NUM_INFO, stream, [&](hipStream_t s) {
+        h->source_from_dataset(idx, batch_size, lo, hi, noise, s);
     });
 }
 int fql_rebrac_total_loss(fql_handle h, const float* obs, const float* act, const float* rew, const float* masks, const float* next_obs,
                           const float* next_actions, int batch_size, const fql_noise* noise, int full_update, float* loss, float* info10,
                           void* stream) {
-    FQL_REBRAC_ONLY(h, "fql_rebrac_total_loss");
+    if (!h) return FQL_E_INVALID;
+    FQL_ADMIT(h, EP_rebrac_total_loss);
     FQL_TRY(h, {
         hipStream_t s = pick(h, stream);
         h->rebrac_source_from_batch(obs, act, rew, masks, next_obs, next_actions, batch_size, noise, 0, s);
@@ -5051,56 +5032,48 @@ int fql_rebrac_total_loss(fql_handle h, const float* obs, const float* act, cons
 }
 int fql_rebrac_sample_actions(fql_handle h, const float* obs, int n, const float* noise, uint64_t seed, float temperature, float* out,
                               void* stream) {
-    FQL_REBRAC_ONLY(h, "fql_rebrac_sample_actions");
-    FQL_TRY(h, h->rebrac_sample(obs, noise, seed, temperature, n, out, pick(h, stream), stream == nullptr));
+    if (!h) return FQL_E_INVALID;
+    FQL_ADMIT(h, EP_rebrac_sample_actions);
+    FQL_TRY(h, h->sample(obs, noise, seed, temperature, n, out, pick(h, stream), stream == nullptr));
 }
 int fql_rebrac_stats(fql_handle h, int full_update, int64_t* launches_per_update, int64_t* macs_per_update) {
-    FQL_REBRAC_ONLY(h, "fql_rebrac_stats");
+    if (!h) return FQL_E_INVALID;
+    FQL_ADMIT(h, EP_rebrac_stats);
     if (launches_per_update) *launches_per_update = (int64_t)(full_update ? h->prog_full : h->prog_critic).launches.size();
-    if (macs_per_update) *macs_per_update = h->rebrac_macs(full_update != 0);
+    if (macs_per_update) *macs_per_update = full_update ? h->macs_per_update() : h->rebrac_macs(false);
     return FQL_OK;
 }
 
 // ---- SAC (agents/sac.py; RLPD = SAC online with balanced sampling) ----------------------------------------------------------------
 // One update through run_update (the AQL form and the graph are bitwise equal); 14 infos.
-#define FQL_SAC_ONLY(h, what)                                                                           \
-    do {                                                                                             \
-        if (!(h)) return FQL_E_INVALID;                                                              \
-        if (!(h)->sac) { (h)->err = what " needs a SAC handle (fql_sac_create)"; return FQL_E_STATE; } \
-    } while (0)
 int fql_sac_update(fql_handle h, const float* obs, const float* act, const float* rew, const float* masks, const float* next_obs,
                    int batch_size, const fql_noise* noise, float* info14, void* stream) {
-    FQL_SAC_ONLY(h, "fql_sac_update");
-    FQL_TRY_FAST(h, {
-        hipStream_t s = pick(h, stream);
+    if (!h) return FQL_E_INVALID;
+    FQL_ADMIT(h, EP_sac_update);
+    return update_with(h, h->prog_full, info14, FQL_SAC_NUM_INFO, stream, [&](hipStream_t s) {
         h->source_from_batch(obs, act, rew, masks, next_obs, batch_size, noise, 1, s);
-        run_update(h, h->prog_full, s, stream == nullptr);
-        h->finish_info(info14, FQL_SAC_NUM_INFO, s);
     });
 }
 int fql_sac_update_from_dataset(fql_handle h, const int64_t* idx, int batch_size, int64_t lo, int64_t hi, const fql_noise* noise,
                                 float* info14, void* stream) {
-    FQL_SAC_ONLY(h, "fql_sac_update_from_dataset");
-    FQL_TRY_FAST(h, {
-        hipStream_t s = pick(h, stream);
+    if (!h) return FQL_E_INVALID;
+    FQL_ADMIT(h, EP_sac_update_from_dataset);
+    return update_with(h, h->prog_full, info14, FQL_SAC_NUM_INFO, stream, [&](hipStream_t s) {
         h->source_from_dataset(idx, batch_size, lo, hi, noise, s);
-        run_update(h, h->prog_full, s, stream == nullptr);
-        h->finish_info(info14, FQL_SAC_NUM_INFO, s);
     });
 }
 int fql_sac_update_balanced(fql_handle h, const int64_t* idx_dataset, const int64_t* idx_replay, int batch_size, const fql_noise* noise,
                             float* info14, void* stream) {
-    FQL_SAC_ONLY(h, "fql_sac_update_balanced");
-    FQL_TRY_FAST(h, {
-        hipStream_t s = pick(h, stream);
+    if (!h) return FQL_E_INVALID;
+    FQL_ADMIT(h, EP_sac_update_balanced);
+    return update_with(h, h->prog_full, info14, FQL_SAC_NUM_INFO, stream, [&](hipStream_t s) {
         h->source_balanced(idx_dataset, idx_replay, nullptr, batch_size, noise, s);
-        run_update(h, h->prog_full, s, stream == nullptr);
-        h->finish_info(info14, FQL_SAC_NUM_INFO, s);
     });
 }
 int fql_sac_total_loss(fql_handle h, const float* obs, const float* act, const float* rew, const float* masks, const float* next_obs,
                        int batch_size, const fql_noise* noise, float* loss, float* info11, void* stream) {
-    FQL_SAC_ONLY(h, "fql_sac_total_loss");
+    if (!h) return FQL_E_INVALID;
+    FQL_ADMIT(h, EP_sac_total_loss);
     FQL_TRY(h, {
         hipStream_t s = pick(h, stream);
         h->source_from_batch(obs, act, rew, masks, next_obs, batch_size, noise, 0, s);
@@ -5119,23 +5092,20 @@ int fql_sac_total_loss(fql_handle h, const float* obs, const float* act, const f
 }
 int fql_sac_sample_actions(fql_handle h, const float* obs, int n, const float* noise, uint64_t seed, float temperature, float* out,
                            void* stream) {
-    FQL_SAC_ONLY(h, "fql_sac_sample_actions");
-    FQL_TRY(h, h->sac_sample(obs, noise, seed, temperature, n, out, pick(h, stream), stream == nullptr));
+    if (!h) return FQL_E_INVALID;
+    FQL_ADMIT(h, EP_sac_sample_actions);
+    FQL_TRY(h, h->sample(obs, noise, seed, temperature, n, out, pick(h, stream), stream == nullptr));
 }
 int fql_sac_stats(fql_handle h, int64_t* launches_per_update, int64_t* macs_per_update) {
-    FQL_SAC_ONLY(h, "fql_sac_stats");
+    if (!h) return FQL_E_INVALID;
+    FQL_ADMIT(h, EP_sac_stats);
     if (launches_per_update) *launches_per_update = (int64_t)h->prog_full.launches.size();
-    if (macs_per_update) *macs_per_update = h->sac_macs();
+    if (macs_per_update) *macs_per_update = h->macs_per_update();
     return FQL_OK;
 }
 
 // ---- IQL (agents/iql.py): expectile value, Gaussian actor with the AWR or the DDPG+BC loss -------------------------------------------
 // One update through run_update (the AQL form and the graph are bitwise equal); 16 (awr) or 19 (ddpgbc) infos.
-#define FQL_IQL_ONLY(h, what)                                                                           \
-    do {                                                                                             \
-        if (!(h)) return FQL_E_INVALID;                                                              \
-        if (!(h)->iql) { (h)->err = what " needs an IQL handle (fql_iql_create)"; return FQL_E_STATE; } \
-    } while (0)
 void fql_iql_default_config(fql_iql_config* c) {   // agents/iql.py:242-261
     std::memset(c, 0, sizeof *c);
     c->expectile = 0.9f;
@@ -5145,31 +5115,28 @@ void fql_iql_default_config(fql_iql_config* c) {   // agents/iql.py:242-261
 }
 int fql_iql_create(const fql_config* cfg, const fql_iql_config* qcfg, uint64_t seed, fql_handle* out) {
     if (!qcfg) { g_create_error = "qcfg must not be NULL"; if (out) *out = nullptr; return FQL_E_INVALID; }
-    return create_engine(cfg, nullptr, nullptr, nullptr, seed, out, nullptr, qcfg);
+    return create_engine(cfg, {AgentKind::IQL, qcfg}, seed, out);
 }
 int fql_iql_update(fql_handle h, const float* obs, const float* act, const float* rew, const float* masks, const float* next_obs,
                    int batch_size, const fql_noise* noise, float* info, void* stream) {
-    FQL_IQL_ONLY(h, "fql_iql_update");
-    FQL_TRY_FAST(h, {
-        hipStream_t s = pick(h, stream);
+    if (!h) return FQL_E_INVALID;
+    FQL_ADMIT(h, EP_iql_update);
+    return update_with(h, h->prog_full, info, h->num_info(), stream, [&](hipStream_t s) {
         h->source_from_batch(obs, act, rew, masks, next_obs, batch_size, noise, 1, s);
-        run_update(h, h->prog_full, s, stream == nullptr);
-        h->finish_info(info, fql_num_info(h), s);
     });
 }
 int fql_iql_update_from_dataset(fql_handle h, const int64_t* idx, int batch_size, int64_t lo, int64_t hi, const fql_noise* noise,
                                 float* info, void* stream) {
-    FQL_IQL_ONLY(h, "fql_iql_update_from_dataset");
-    FQL_TRY_FAST(h, {
-        hipStream_t s = pick(h, stream);
+    if (!h) return FQL_E_INVALID;
+    FQL_ADMIT(h, EP_iql_update_from_dataset);
+    return update_with(h, h->prog_full, info, h->num_info(), stream, [&](hipStream_t s) {
         h->source_from_dataset(idx, batch_size, lo, hi, noise, s);
-        run_update(h, h->prog_full, s, stream == nullptr);
-        h->finish_info(info, fql_num_info(h), s);
     });
 }
 int fql_iql_total_loss(fql_handle h, const float* obs, const float* act, const float* rew, const float* masks, const float* next_obs,
                        int batch_size, const fql_noise* noise, float* loss, float* info, void* stream) {
-    FQL_IQL_ONLY(h, "fql_iql_total_loss");
+    if (!h) return FQL_E_INVALID;
+    FQL_ADMIT(h, EP_iql_total_loss);
     FQL_TRY(h, {
         hipStream_t s = pick(h, stream);
         h->source_from_batch(obs, act, rew, masks, next_obs, batch_size, noise, 0, s);
@@ -5184,52 +5151,46 @@ int fql_iql_total_loss(fql_handle h, const float* obs, const float* act, const f
 }
 int fql_iql_sample_actions(fql_handle h, const float* obs, int n, const float* noise, uint64_t seed, float temperature, float* out,
                            void* stream) {
-    FQL_IQL_ONLY(h, "fql_iql_sample_actions");
-    FQL_TRY(h, h->iql_sample(obs, noise, seed, temperature, n, out, pick(h, stream), stream == nullptr));
+    if (!h) return FQL_E_INVALID;
+    FQL_ADMIT(h, EP_iql_sample_actions);
+    FQL_TRY(h, h->sample(obs, noise, seed, temperature, n, out, pick(h, stream), stream == nullptr));
 }
 int fql_iql_stats(fql_handle h, int64_t* launches_per_update, int64_t* macs_per_update) {
-    FQL_IQL_ONLY(h, "fql_iql_stats");
+    if (!h) return FQL_E_INVALID;
+    FQL_ADMIT(h, EP_iql_stats);
     if (launches_per_update) *launches_per_update = (int64_t)h->prog_full.launches.size();
-    if (macs_per_update) *macs_per_update = h->iql_macs();
+    if (macs_per_update) *macs_per_update = h->macs_per_update();
     return FQL_OK;
 }
 
 // ---- BC (agents/bc.py): flow-matching behavioural cloning -------------------------------------------------------------------------
 // One update through run_update (the AQL form and the graph are bitwise equal); 4 infos.
-#define FQL_BC_ONLY(h, what)                                                                          \
-    do {                                                                                            \
-        if (!(h)) return FQL_E_INVALID;                                                             \
-        if (!(h)->bc) { (h)->err = what " needs a BC handle (fql_bc_create)"; return FQL_E_STATE; } \
-    } while (0)
 void fql_bc_default_config(fql_bc_config* c) {   // agents/bc.py:135-148
     std::memset(c, 0, sizeof *c);
     c->denoise_steps = 16;
 }
 int fql_bc_create(const fql_config* cfg, const fql_bc_config* bcfg, uint64_t seed, fql_handle* out) {
     if (!bcfg) { g_create_error = "bcfg must not be NULL"; if (out) *out = nullptr; return FQL_E_INVALID; }
-    return create_engine(cfg, nullptr, nullptr, nullptr, seed, out, bcfg);
+    return create_engine(cfg, {AgentKind::BC, bcfg}, seed, out);
 }
 int fql_bc_update(fql_handle h, const float* obs, const float* act, int batch_size, const fql_noise* noise, float* info4, void* stream) {
-    FQL_BC_ONLY(h, "fql_bc_update");
-    FQL_TRY_FAST(h, {
-        hipStream_t s = pick(h, stream);
+    if (!h) return FQL_E_INVALID;
+    FQL_ADMIT(h, EP_bc_update);
+    return update_with(h, h->prog_full, info4, FQL_BC_NUM_INFO, stream, [&](hipStream_t s) {
         h->bc_source_from_batch(obs, act, batch_size, noise, 1, s);
-        run_update(h, h->prog_full, s, stream == nullptr);
-        h->finish_info(info4, FQL_BC_NUM_INFO, s);
     });
 }
 int fql_bc_update_from_dataset(fql_handle h, const int64_t* idx, int batch_size, int64_t lo, int64_t hi, const fql_noise* noise,
                                float* info4, void* stream) {
-    FQL_BC_ONLY(h, "fql_bc_update_from_dataset");
-    FQL_TRY_FAST(h, {
-        hipStream_t s = pick(h, stream);
+    if (!h) return FQL_E_INVALID;
+    FQL_ADMIT(h, EP_bc_update_from_dataset);
+    return update_with(h, h->prog_full, info4, FQL_BC_NUM_INFO, stream, [&](hipStream_t s) {
         h->source_from_dataset(idx, batch_size, lo, hi, noise, s);
-        run_update(h, h->prog_full, s, stream == nullptr);
-        h->finish_info(info4, FQL_BC_NUM_INFO, s);
     });
 }
 int fql_bc_policy_loss(fql_handle h, const float* obs, const float* act, int batch_size, const fql_noise* noise, float* loss, void* stream) {
-    FQL_BC_ONLY(h, "fql_bc_policy_loss");
+    if (!h) return FQL_E_INVALID;
+    FQL_ADMIT(h, EP_bc_policy_loss);
     FQL_TRY(h, {
         hipStream_t s = pick(h, stream);
         h->bc_source_from_batch(obs, act, batch_size, noise, 0, s);
@@ -5241,13 +5202,15 @@ int fql_bc_policy_loss(fql_handle h, const float* obs, const float* act, int bat
     });
 }
 int fql_bc_sample_actions(fql_handle h, const float* obs, int n, const float* noise, uint64_t seed, float* out, void* stream) {
-    FQL_BC_ONLY(h, "fql_bc_sample_actions");
-    FQL_TRY(h, h->bc_sample(obs, noise, seed, n, out, pick(h, stream), stream == nullptr));
+    if (!h) return FQL_E_INVALID;
+    FQL_ADMIT(h, EP_bc_sample_actions);
+    FQL_TRY(h, h->sample(obs, noise, seed, 1.0f, n, out, pick(h, stream), stream == nullptr));
 }
 int fql_bc_stats(fql_handle h, int64_t* launches_per_update, int64_t* macs_per_update, int64_t* launches_per_sample) {
-    FQL_BC_ONLY(h, "fql_bc_stats");
+    if (!h) return FQL_E_INVALID;
+    FQL_ADMIT(h, EP_bc_stats);
     if (launches_per_update) *launches_per_update = (int64_t)h->prog_full.launches.size();
-    if (macs_per_update) *macs_per_update = h->bc_macs();
+    if (macs_per_update) *macs_per_update = h->macs_per_update();
     if (launches_per_sample) *launches_per_sample = 4 + (int64_t)h->bc_steps * h->nets[NET_BC].nl();   // assemble, step-bias table, C0, S (layer 0 + nh GEMMs), extract
     return FQL_OK;
 }
@@ -5262,9 +5225,7 @@ int fql_bc_stats(fql_handle h, int64_t* launches_per_update, int64_t* macs_per_u
 // one-workgroup kernel that returns at once (median of 32), which the caller subtracts (minus the ~1.4 us such a kernel itself shows
 // in a rocprofv3 trace) to compare with rocprofv3's per-kernel durations.
 extern "C" int fql_profile_update(fql_handle h, int batch_size, int cap, int* type, int* lane, int* grid, float* us, double* macs, float* null_us) {
-    FQL_REBRAC_REFUSES(h, "fql_profile_update", "FQL batch sources only");
-    FQL_SAC_REFUSES(h, "fql_profile_update");
-    FQL_BC_REFUSES(h, "fql_profile_update");
+    FQL_ADMIT(h, EP_profile_update);
     if (!h || !type || !us) return FQL_E_INVALID;
     try {
         require_graph(h->prog_full);
@@ -5300,9 +5261,7 @@ extern "C" int fql_profile_update(fql_handle h, int batch_size, int cap, int* ty
 // 4 X_c1 [B, inp_c], 5 w_rew [B], 6 w_mask [B], 7 in_idx (int64 [B], frames path), 8 in_crop (int32 [B][2], frames path),
 // 9 X_eu [B, inp_b].  *dims receives {rows, row stride in elements}.
 extern "C" int fql_debug_workspace(fql_handle h, int which, void* out, size_t bytes, int* dims) {
-    FQL_REBRAC_REFUSES(h, "fql_debug_workspace", "FQL workspaces only");
-    FQL_SAC_REFUSES(h, "fql_debug_workspace");
-    FQL_BC_REFUSES(h, "fql_debug_workspace");
+    FQL_ADMIT(h, EP_debug_workspace);
     if (!h || !out) return FQL_E_INVALID;
     const int B = h->B, ic = h->nets[NET_OS].in_p(), ib = h->nets[NET_BC].in_p(), ap = pad16(h->cfg.act_dim);
     const void* src = nullptr;
@@ -5433,9 +5392,7 @@ extern "C" int fql_debug_enc(fql_handle h, int enc, int code, void* out, size_t 
 
 int fql_dataset_upload_frames(fql_handle h, int64_t n, const uint8_t* frames, const uint8_t* next_frames, const float* act,
                               const float* rew, const float* mask, const float* terminals, int frame_stack, float p_aug) {
-    FQL_IFQL_REFUSES(h, "fql_dataset_upload_frames");
-    FQL_SAC_REFUSES(h, "fql_dataset_upload_frames");
-    FQL_BC_REFUSES(h, "fql_dataset_upload_frames");
+    FQL_ADMIT(h, EP_dataset_upload_frames);
     if (!h) return FQL_E_INVALID;
     FQL_TRY(h, {
         if (!h->visual) throw Invalid{"fql_dataset_upload_frames needs an agent created with an encoder"};
@@ -5478,15 +5435,11 @@ int fql_dataset_upload_frames(fql_handle h, int64_t n, const uint8_t* frames, co
 }
 int fql_update_from_frames(fql_handle h, const int64_t* idx, const int32_t* crop_froms, int batch_size, int64_t lo, int64_t hi,
                            const fql_noise* noise, float* info13, void* stream) {
-    FQL_IFQL_REFUSES(h, "fql_update_from_frames");
-    FQL_SAC_REFUSES(h, "fql_update_from_frames");
-    FQL_BC_REFUSES(h, "fql_update_from_frames");
+    FQL_ADMIT(h, EP_update_from_frames);
     if (!h) return FQL_E_INVALID;
-    FQL_TRY(h, {
-        hipStream_t s = pick(h, stream);
+    return update_with(h, h->prog_full, info13, FQL_NUM_INFO, stream, [&](hipStream_t s) {
+        h->hip_touch();
         h->source_from_frames(idx, crop_froms, batch_size, lo, hi, noise, s);
-        run_update(h, h->prog_full, s, stream == nullptr);
-        h->finish_info(info13, FQL_NUM_INFO, s);
     });
 }
 
@@ -5703,10 +5656,8 @@ int fql_group_create(const fql_handle* members, int k, fql_group* out) {
     if (!out) { g_create_error = "fql_group_create: out must not be NULL"; return FQL_E_INVALID; }
     *out = nullptr;
     for (int i = 0; members && i < k; ++i)
-        if (members[i] && (members[i]->ifql || members[i]->rebrac || members[i]->sac || members[i]->bc || members[i]->iql)) {
-            g_create_error = "fql_group_create: member " + std::to_string(i) +
-                             (members[i]->ifql ? " is an IFQL handle" : members[i]->rebrac ? " is a ReBRAC handle" : members[i]->sac ? " is a SAC handle" : members[i]->iql ? " is an IQL handle" : " is a BC handle") +
-                             " (groups take FQL agents only)";
+        if (members[i] && members[i]->kind != AgentKind::FQL) {
+            g_create_error = "fql_group_create: member " + std::to_string(i) + " is " + members[i]->desc().label + " (groups take FQL agents only)";
             return FQL_E_STATE;
         }
     auto* g = new fql_group_s();

@@ -53,6 +53,7 @@ def get_config():
 class IFQLAgent(FQLAgent):
     """Implicit flow Q-learning agent backed by the MI355X step engine."""
 
+    _name = 'IFQL'
     _loss_infos = 9
     _jax_sample_noise = False
 
@@ -61,12 +62,7 @@ class IFQLAgent(FQLAgent):
         """agents/ifql.py:157-228.  `config`: dict-like with the keys of get_config()."""
         cfg = get_config()
         cfg.update(dict(config))
-        if cfg.get('encoder') is not None:
-            raise NotImplementedError('IFQL: visual encoders are not available (state observations only)')
-        if cfg.get('precision', 'fp32') not in ('fp32', 0):
-            raise NotImplementedError(f"IFQL runs in fp32 only (precision {cfg['precision']!r})")
-        if cfg.get('rng', 'engine') != 'engine':
-            raise NotImplementedError(f"IFQL draws its noise from the engine's RNG or explicit tensors only (rng {cfg['rng']!r})")
+        cls._refuse_config(cfg)
         lib = _cabi.load()
         c, ob_dims, action_dim = cls._engine_config(lib, cfg, ex_observations, ex_actions)
         ic = _cabi.FqlIfqlConfig()

@@ -13,12 +13,9 @@ from __future__ import annotations
 
 import ctypes as C
 
-import numpy as np
-
 from . import _cabi
-from .agent import FQLAgent, LazyInfo, _Arg, _seed_to_u64
+from .agent import KindAgent, _Arg, _PendingN
 from .config import ConfigDict
-from .sac import _PendingN
 
 _IQL_HEAD_KEYS = (
     'value/value_loss', 'value/v_mean', 'value/v_max', 'value/v_min',
@@ -57,10 +54,14 @@ def get_config():
     )
 
 
-class IQLAgent(FQLAgent):
-    """Implicit Q-learning agent backed by the MI355X step engine."""
+class IQLAgent(KindAgent):
+    """Implicit Q-learning agent backed by the MI355X step engine.  update: agents/iql.py update, 16 (awr) or 19 (ddpgbc) infos;
+    sample_actions: clip(mean + exp(log_stds) temperature N(0, 1), -1, 1)."""
 
-    _jax_sample_noise = False
+    _name = 'IQL'
+    _refused = (('compute_flow_actions', 'compute_flow_actions (the actor is a Gaussian, there is no flow)'),
+                ('update_balanced', 'balanced sampling (IQL trains offline from one dataset)'))
+    _update_fn, _update_dataset_fn, _sample_fn = 'fql_iql_update', 'fql_iql_update_from_dataset', 'fql_iql_sample_actions'
     _pending_cls = _PendingN
 
     @classmethod
@@ -68,12 +69,7 @@ class IQLAgent(FQLAgent):
         """agents/iql.py:171-239.  `config`: dict-like with the keys of get_config()."""
         cfg = get_config()
         cfg.update(dict(config))
-        if cfg.get('encoder') is not None:
-            raise NotImplementedError('IQL: visual encoders are not available (state observations only)')
-        if cfg.get('precision', 'fp32') not in ('fp32', 0):
-            raise NotImplementedError(f"IQL runs in fp32 only (precision {cfg['precision']!r})")
-        if cfg.get('rng', 'engine') != 'engine':
-            raise NotImplementedError(f"IQL draws its noise from the engine's RNG or explicit tensors only (rng {cfg['rng']!r})")
+        cls._refuse_config(cfg)
         if cfg['actor_loss'] not in IQL_INFO_KEYS:
             raise ValueError(f"Unsupported actor loss: {cfg['actor_loss']}")
         lib = _cabi.load()
@@ -104,49 +100,10 @@ class IQLAgent(FQLAgent):
         e = _Arg(noise.get('eps'), (B, self.config['action_dim']))
         return _cabi.FqlNoise(e.ptr, None, None, None, None), [e]
 
-    def _info(self, stream):
-        t = C.c_uint64()
-        self._check(self._lib.fql_info_enqueue(self._h, stream, C.byref(t)))
-        return LazyInfo(self, int(t.value), self._info_keys)
-
-    # -- reference API ----------------------------------------------------------------------
-    def update(self, batch, noise=None, want_info=True):
-        """agents/iql.py update.  Returns (agent, info); info is a LazyInfo with the handle's info keys, or None with want_info=False."""
-        B, args = self._batch_args(batch)
-        self._ensure_batch(B)
-        nz, nargs = self._noise_args(noise, B)
-        stream = self._stream(args + nargs)
-        self._check(self._lib.fql_iql_update(self._h, *[a.ptr for a in args], B, C.byref(nz) if nz else None, None, stream))
-        self._keep = (args, nargs)
-        return self, (self._info(stream) if want_info else None)
-
-    def update_from_dataset(self, batch_size=None, idxs=None, noise=None, shard=(0, 0), want_info=False, stream=None):
-        """train_dataset.sample(B) + update(batch) without leaving the device."""
-        B = int(batch_size or self.config['batch_size'])
-        self._ensure_batch(B)
-        nz, nargs = self._noise_args(noise, B)
-        ip, keep = None, None
-        if idxs is not None:
-            keep, ip = self._host_idx(idxs, B, self.dataset_size()[0], 'idxs')
-        self._check(self._lib.fql_iql_update_from_dataset(self._h, ip, B, int(shard[0]), int(shard[1]), C.byref(nz) if nz else None,
-                                                          None, stream))
-        self._keep = (keep, nargs)
-        return self, (self._info(stream) if want_info else None)
-
-    def read_info(self):
-        """The infos of the last update (blocks until it has run)."""
-        n = len(self._info_keys)
-        buf = (C.c_float * n)()
-        self._check(self._lib.fql_read_info_n(self._h, buf, n))
-        return {k: float(buf[i]) for i, k in enumerate(self._info_keys)}
-
     def total_loss(self, batch, grad_params=None, rng=None, noise=None):
         """agents/iql.py total_loss with grad_params=None (the validation probe, main.py:284): (loss, info) with the value, critic and
         actor infos.  No state changes."""
-        if grad_params is not None:
-            raise NotImplementedError('total_loss with traced grad_params is jax.grad plumbing; use update()')
-        if rng is not None:
-            raise NotImplementedError('IQL draws its noise from the engine RNG or explicit tensors (noise=), not JAX keys')
+        self._probe_guard('total_loss with traced grad_params', grad_params, rng)
         B, args = self._batch_args(batch)
         self._ensure_batch(B)
         nz, nargs = self._noise_args(noise, B)
@@ -158,63 +115,11 @@ class IQLAgent(FQLAgent):
                                                  stream))
         return float(loss.value), {k: float(info[i]) for i, k in enumerate(self._info_keys[:n])}
 
-    def sample_actions(self, observations, seed=None, temperature=1.0, noises=None):
-        """agents/iql.py sample_actions: clip(mean + exp(log_stds) temperature N(0, 1), -1, 1).  [od] -> [act]; [n, od] -> [n, act].
-        `noises`: the raw N(0, 1) with the actions' shape, or None = engine RNG keyed by `seed`."""
-        od, ad = self.config['ob_dims'][0], self.config['action_dim']
-        is_torch = hasattr(observations, 'data_ptr')
-        if int(observations.shape[-1]) != od:
-            raise ValueError(f'observations last dim must be {od}, got {tuple(observations.shape)}')
-        lead = tuple(observations.shape[:-1])
-        n = int(np.prod(lead)) if lead else 1
-        o = _Arg(observations, (n, od))
-        z = _Arg(noises, (n, ad))
-        if is_torch and observations.is_cuda:
-            torch = __import__('torch')
-            out = torch.empty(lead + (ad,), dtype=torch.float32, device=observations.device)
-            optr = out.data_ptr()
-        else:
-            out = np.empty(lead + (ad,), dtype=np.float32)
-            optr = out.ctypes.data
-        if seed is None and noises is None:
-            self._sample_calls += 1
-            sd = (self._seed << 20) ^ self._sample_calls
-        else:
-            sd = _seed_to_u64(seed)
-        self._check(self._lib.fql_iql_sample_actions(self._h, o.ptr, n, z.ptr, sd & 0xFFFFFFFFFFFFFFFF, float(temperature), optr,
-                                                     self._stream([o, z])))
-        return out
-
     def iql_stats(self):
         """(launches, MACs) of one update."""
         la, ma = C.c_int64(), C.c_int64()
         self._check(self._lib.fql_iql_stats(self._h, C.byref(la), C.byref(ma)))
         return int(la.value), int(ma.value)
-
-    # -- FQL-only paths, refused before the library is called ----------------------------------
-    def _refuse(self, what):
-        raise NotImplementedError(f'IQL: {what} is not available (FQL agents only)')
-
-    def compute_flow_actions(self, observations, noises):
-        self._refuse('compute_flow_actions (the actor is a Gaussian, there is no flow)')
-
-    def update_begin(self, *a, **k):
-        self._refuse('the data-parallel update halves')
-
-    def update_begin_split(self, *a, **k):
-        self._refuse('the data-parallel update halves')
-
-    def update_end(self, *a, **k):
-        self._refuse('the data-parallel update halves')
-
-    def update_end_split(self, *a, **k):
-        self._refuse('the data-parallel update halves')
-
-    def update_balanced(self, *a, **k):
-        self._refuse('balanced sampling (IQL trains offline from one dataset)')
-
-    def grad_buckets(self):
-        self._refuse('gradient buckets')
 
 
 __all__ = ['IQLAgent', 'IQL_INFO_KEYS', 'IQL_AWR_INFO_KEYS', 'IQL_DDPGBC_INFO_KEYS', 'IQL_NOISE_KEYS', 'get_config']

@@ -18,10 +18,8 @@ from __future__ import annotations
 
 import ctypes as C
 
-import numpy as np
-
 from . import _cabi
-from .agent import FQLAgent, LazyInfo, _Arg, _seed_to_u64
+from .agent import KindAgent, LazyInfo, _Arg
 from .config import ConfigDict
 
 REBRAC_INFO_KEYS = (
@@ -61,23 +59,22 @@ def get_config():
     )
 
 
-class ReBRACAgent(FQLAgent):
-    """ReBRAC agent backed by the MI355X step engine."""
+class ReBRACAgent(KindAgent):
+    """ReBRAC agent backed by the MI355X step engine.  sample_actions (agents/rebrac.py:136-152):
+    clip(mode + clip(N(0, 1) actor_noise temperature, +-actor_noise_clip), -1, 1)."""
 
+    _name = 'ReBRAC'
+    _refused = (('compute_flow_actions', 'compute_flow_actions (the actor is deterministic)'), ('update_balanced', 'balanced sampling'),
+                ('create_replay_buffer', 'a replay ring beside the dataset'))
+    _update_fn, _update_dataset_fn, _sample_fn = 'fql_rebrac_update', 'fql_rebrac_update_from_dataset', 'fql_rebrac_sample_actions'
     _loss_infos = 9
-    _jax_sample_noise = False
 
     @classmethod
     def create(cls, seed, ex_observations, ex_actions, config):
         """agents/rebrac.py:154-219.  `config`: dict-like with the keys of get_config()."""
         cfg = get_config()
         cfg.update(dict(config))
-        if cfg.get('encoder') is not None:
-            raise NotImplementedError('ReBRAC: visual encoders are not available (state observations only)')
-        if cfg.get('precision', 'fp32') not in ('fp32', 0):
-            raise NotImplementedError(f"ReBRAC runs in fp32 only (precision {cfg['precision']!r})")
-        if cfg.get('rng', 'engine') != 'engine':
-            raise NotImplementedError(f"ReBRAC draws its noise from the engine's RNG or explicit tensors only (rng {cfg['rng']!r})")
+        cls._refuse_config(cfg)
         cfg.setdefault('flow_steps', 10)   # (an fql_config field ReBRAC does not read)
         lib = _cabi.load()
         c, ob_dims, action_dim = cls._engine_config(lib, cfg, ex_observations, ex_actions)
@@ -104,44 +101,28 @@ class ReBRACAgent(FQLAgent):
         eps1 = _Arg(noise.get('eps1'), (B, self.config['action_dim']))
         return _cabi.FqlNoise(eps1.ptr, None, None, None, None), [eps1]
 
-    def _rebrac_batch(self, batch):
+    def _batch_args(self, batch):
         if 'next_actions' not in batch:
             raise KeyError("a ReBRAC batch must carry 'next_actions' (Dataset.return_next_actions = True)")
-        B, args = self._batch_args(batch)
+        B, args = super()._batch_args(batch)
         return B, args + [_Arg(batch['next_actions'], (B, self.config['action_dim']))]
 
-    def _info(self, stream, full_update):
+    def _lazy_info(self, stream):
         t = C.c_uint64()
         self._check(self._lib.fql_info_enqueue(self._h, stream, C.byref(t)))
-        return LazyInfo(self, int(t.value), REBRAC_INFO_KEYS if full_update else REBRAC_CRITIC_INFO_KEYS)
+        return LazyInfo(self, int(t.value), REBRAC_INFO_KEYS if self._last_full else REBRAC_CRITIC_INFO_KEYS)
 
     # -- reference API ----------------------------------------------------------------------
     def update(self, batch, full_update=True, noise=None, want_info=True):
         """agents/rebrac.py:122-134.  Returns (agent, info); info is a LazyInfo with REBRAC_INFO_KEYS (full step) or
         REBRAC_CRITIC_INFO_KEYS (critic-only step), or None with want_info=False."""
-        B, args = self._rebrac_batch(batch)
-        self._ensure_batch(B)
-        nz, nargs = self._noise_args(noise, B)
-        stream = self._stream(args + nargs)
-        self._check(self._lib.fql_rebrac_update(self._h, *[a.ptr for a in args], B, C.byref(nz) if nz else None, int(bool(full_update)),
-                                                None, stream))
-        self._keep = (args, nargs)
         self._last_full = bool(full_update)
-        return self, (self._info(stream, full_update) if want_info else None)
+        return super().update(batch, noise, want_info, _extra=(int(self._last_full),))
 
     def update_from_dataset(self, batch_size=None, idxs=None, noise=None, shard=(0, 0), want_info=False, stream=None, full_update=True):
         """train_dataset.sample(B) (return_next_actions) + update(batch, full_update) without leaving the device."""
-        B = int(batch_size or self.config['batch_size'])
-        self._ensure_batch(B)
-        nz, nargs = self._noise_args(noise, B)
-        ip, keep = None, None
-        if idxs is not None:
-            keep, ip = self._host_idx(idxs, B, self.dataset_size()[0], 'idxs')
-        self._check(self._lib.fql_rebrac_update_from_dataset(self._h, ip, B, int(shard[0]), int(shard[1]), C.byref(nz) if nz else None,
-                                                             int(bool(full_update)), None, stream))
-        self._keep = (keep, nargs)
         self._last_full = bool(full_update)
-        return self, (self._info(stream, full_update) if want_info else None)
+        return super().update_from_dataset(batch_size, idxs, noise, shard, want_info, stream, _extra=(int(self._last_full),))
 
     def read_info(self):
         """The infos of the last update (12 or 7 keys by its kind; blocks until it has run)."""
@@ -153,11 +134,8 @@ class ReBRACAgent(FQLAgent):
     def total_loss(self, batch, grad_params=None, rng=None, noise=None, full_update=True):
         """agents/rebrac.py:86-108 with grad_params=None (the validation probe, main.py:284): (loss, info) with 9 infos on a full step,
         the 4 critic infos otherwise.  No state changes."""
-        if grad_params is not None:
-            raise NotImplementedError('total_loss with traced grad_params is jax.grad plumbing; use update()')
-        if rng is not None:
-            raise NotImplementedError('ReBRAC draws its noise from the engine RNG or explicit tensors (noise=), not JAX keys')
-        B, args = self._rebrac_batch(batch)
+        self._probe_guard('total_loss with traced grad_params', grad_params, rng)
+        B, args = self._batch_args(batch)
         self._ensure_batch(B)
         nz, nargs = self._noise_args(noise, B)
         loss = C.c_float()
@@ -168,66 +146,11 @@ class ReBRACAgent(FQLAgent):
         keys = REBRAC_INFO_KEYS[:9] if full_update else REBRAC_INFO_KEYS[:4]
         return float(loss.value), {k: float(info[i]) for i, k in enumerate(keys)}
 
-    def sample_actions(self, observations, seed=None, temperature=1.0, noises=None):
-        """agents/rebrac.py:136-152: clip(mode + clip(N(0, 1) actor_noise temperature, +-actor_noise_clip), -1, 1).  [od] -> [act];
-        [n, od] -> [n, act].  `noises`: the raw N(0, 1) with the actions' shape, or None = engine RNG keyed by `seed`."""
-        od, ad = self.config['ob_dims'][0], self.config['action_dim']
-        is_torch = hasattr(observations, 'data_ptr')
-        if int(observations.shape[-1]) != od:
-            raise ValueError(f'observations last dim must be {od}, got {tuple(observations.shape)}')
-        lead = tuple(observations.shape[:-1])
-        n = int(np.prod(lead)) if lead else 1
-        o = _Arg(observations, (n, od))
-        z = _Arg(noises, (n, ad))
-        if is_torch and observations.is_cuda:
-            torch = __import__('torch')
-            out = torch.empty(lead + (ad,), dtype=torch.float32, device=observations.device)
-            optr = out.data_ptr()
-        else:
-            out = np.empty(lead + (ad,), dtype=np.float32)
-            optr = out.ctypes.data
-        if seed is None and noises is None:
-            self._sample_calls += 1
-            sd = (self._seed << 20) ^ self._sample_calls
-        else:
-            sd = _seed_to_u64(seed)
-        self._check(self._lib.fql_rebrac_sample_actions(self._h, o.ptr, n, z.ptr, sd & 0xFFFFFFFFFFFFFFFF, float(temperature), optr,
-                                                        self._stream([o, z])))
-        return out
-
     def rebrac_stats(self, full_update=True):
         """(launches, MACs) of one full or critic-only update."""
         la, ma = C.c_int64(), C.c_int64()
         self._check(self._lib.fql_rebrac_stats(self._h, int(bool(full_update)), C.byref(la), C.byref(ma)))
         return int(la.value), int(ma.value)
-
-    # -- FQL-only paths, refused before the library is called ----------------------------------
-    def _refuse(self, what):
-        raise NotImplementedError(f'ReBRAC: {what} is not available (FQL agents only)')
-
-    def compute_flow_actions(self, observations, noises):
-        self._refuse('compute_flow_actions (the actor is deterministic)')
-
-    def update_balanced(self, *a, **k):
-        self._refuse('balanced sampling')
-
-    def create_replay_buffer(self, size):
-        self._refuse('a replay ring beside the dataset')
-
-    def update_begin(self, *a, **k):
-        self._refuse('the data-parallel update halves')
-
-    def update_begin_split(self, *a, **k):
-        self._refuse('the data-parallel update halves')
-
-    def update_end(self, *a, **k):
-        self._refuse('the data-parallel update halves')
-
-    def update_end_split(self, *a, **k):
-        self._refuse('the data-parallel update halves')
-
-    def grad_buckets(self):
-        self._refuse('gradient buckets')
 
 
 __all__ = ['ReBRACAgent', 'REBRAC_INFO_KEYS', 'REBRAC_CRITIC_INFO_KEYS', 'REBRAC_NOISE_KEYS', 'get_config']

@@ -18,10 +18,8 @@ from __future__ import annotations
 import ctypes as C
 import math
 
-import numpy as np
-
 from . import _cabi
-from .agent import FQLAgent, LazyInfo, _Arg, _Pending, _seed_to_u64
+from .agent import KindAgent, _Arg, _PendingN
 from .config import ConfigDict
 
 SAC_INFO_KEYS = (
@@ -61,24 +59,14 @@ def get_config():
     )
 
 
-class _PendingN(_Pending):
-    """_Pending over fql_info_wait_n: all fql_num_info(h) scalars of one update."""
+class SACAgent(KindAgent):
+    """SAC agent (RLPD's learner) backed by the MI355X step engine.  update: agents/sac.py update, 14 infos (SAC_INFO_KEYS);
+    sample_actions: clip(tanh(mean + exp(log_std) temperature N(0, 1)), -1, 1)."""
 
-    def get(self):
-        if self.vals is None:
-            n = len(self.agent._info_keys)
-            buf = (C.c_float * n)()
-            self.agent._check(self.agent._lib.fql_info_wait_n(self.agent._h, self.ticket, buf, n))
-            self.vals = [float(buf[i]) for i in range(n)]
-            self.agent = None
-        return self.vals
-
-
-class SACAgent(FQLAgent):
-    """SAC agent (RLPD's learner) backed by the MI355X step engine."""
-
+    _name = 'SAC'
+    _refused = (('compute_flow_actions', 'compute_flow_actions (the actor is a Gaussian, there is no flow)'),)
+    _update_fn, _update_dataset_fn, _sample_fn = 'fql_sac_update', 'fql_sac_update_from_dataset', 'fql_sac_sample_actions'
     _loss_infos = 11
-    _jax_sample_noise = False
     _pending_cls = _PendingN
 
     @classmethod
@@ -86,12 +74,7 @@ class SACAgent(FQLAgent):
         """agents/sac.py create.  `config`: dict-like with the keys of get_config()."""
         cfg = get_config()
         cfg.update(dict(config))
-        if cfg.get('encoder') is not None:
-            raise NotImplementedError('SAC: visual encoders are not available (state observations only)')
-        if cfg.get('precision', 'fp32') not in ('fp32', 0):
-            raise NotImplementedError(f"SAC runs in fp32 only (precision {cfg['precision']!r})")
-        if cfg.get('rng', 'engine') != 'engine':
-            raise NotImplementedError(f"SAC draws its noise from the engine's RNG or explicit tensors only (rng {cfg['rng']!r})")
+        cls._refuse_config(cfg)
         if not cfg['state_dependent_std']:
             raise NotImplementedError('SAC: only state_dependent_std=True is available')
         cfg.setdefault('flow_steps', 10)   # (an fql_config field SAC does not read)
@@ -122,35 +105,6 @@ class SACAgent(FQLAgent):
         e1, e2 = _Arg(noise.get('eps1'), (B, ad)), _Arg(noise.get('eps2'), (B, ad))
         return _cabi.FqlNoise(e1.ptr, None, None, None, e2.ptr), [e1, e2]
 
-    def _info(self, stream):
-        t = C.c_uint64()
-        self._check(self._lib.fql_info_enqueue(self._h, stream, C.byref(t)))
-        return LazyInfo(self, int(t.value), SAC_INFO_KEYS)
-
-    # -- reference API ----------------------------------------------------------------------
-    def update(self, batch, noise=None, want_info=True):
-        """agents/sac.py update.  Returns (agent, info); info is a LazyInfo with SAC_INFO_KEYS, or None with want_info=False."""
-        B, args = self._batch_args(batch)
-        self._ensure_batch(B)
-        nz, nargs = self._noise_args(noise, B)
-        stream = self._stream(args + nargs)
-        self._check(self._lib.fql_sac_update(self._h, *[a.ptr for a in args], B, C.byref(nz) if nz else None, None, stream))
-        self._keep = (args, nargs)
-        return self, (self._info(stream) if want_info else None)
-
-    def update_from_dataset(self, batch_size=None, idxs=None, noise=None, shard=(0, 0), want_info=False, stream=None):
-        """train_dataset.sample(B) + update(batch) without leaving the device."""
-        B = int(batch_size or self.config['batch_size'])
-        self._ensure_batch(B)
-        nz, nargs = self._noise_args(noise, B)
-        ip, keep = None, None
-        if idxs is not None:
-            keep, ip = self._host_idx(idxs, B, self.dataset_size()[0], 'idxs')
-        self._check(self._lib.fql_sac_update_from_dataset(self._h, ip, B, int(shard[0]), int(shard[1]), C.byref(nz) if nz else None,
-                                                          None, stream))
-        self._keep = (keep, nargs)
-        return self, (self._info(stream) if want_info else None)
-
     def update_balanced(self, batch_size=None, idxs=None, noise=None, want_info=False, stream=None):
         """RLPD's step (main.py:255-259) on the device: concat(train_dataset.sample(B // 2), replay_buffer.sample(B // 2)) -> update.
         `idxs` = (dataset_idxs, replay_idxs), B // 2 each, or None (engine RNG)."""
@@ -165,22 +119,12 @@ class SACAgent(FQLAgent):
             keep = (ka, kb)
         self._check(self._lib.fql_sac_update_balanced(self._h, ia, ib, B, C.byref(nz) if nz else None, None, stream))
         self._keep = (keep, nargs)
-        return self, (self._info(stream) if want_info else None)
-
-    def read_info(self):
-        """The 14 infos of the last update (blocks until it has run)."""
-        n = len(SAC_INFO_KEYS)
-        buf = (C.c_float * n)()
-        self._check(self._lib.fql_read_info_n(self._h, buf, n))
-        return {k: float(buf[i]) for i, k in enumerate(SAC_INFO_KEYS)}
+        return self, (self._lazy_info(stream) if want_info else None)
 
     def total_loss(self, batch, grad_params=None, rng=None, noise=None):
         """agents/sac.py total_loss with grad_params=None (the validation probe, main.py:284): (loss, info) with the 11 critic and
         actor infos.  No state changes."""
-        if grad_params is not None:
-            raise NotImplementedError('total_loss with traced grad_params is jax.grad plumbing; use update()')
-        if rng is not None:
-            raise NotImplementedError('SAC draws its noise from the engine RNG or explicit tensors (noise=), not JAX keys')
+        self._probe_guard('total_loss with traced grad_params', grad_params, rng)
         B, args = self._batch_args(batch)
         self._ensure_batch(B)
         nz, nargs = self._noise_args(noise, B)
@@ -191,60 +135,11 @@ class SACAgent(FQLAgent):
                                                  stream))
         return float(loss.value), {k: float(info[i]) for i, k in enumerate(SAC_INFO_KEYS[:11])}
 
-    def sample_actions(self, observations, seed=None, temperature=1.0, noises=None):
-        """agents/sac.py sample_actions: clip(tanh(mean + exp(log_std) temperature N(0, 1)), -1, 1).  [od] -> [act]; [n, od] -> [n, act].
-        `noises`: the raw N(0, 1) with the actions' shape, or None = engine RNG keyed by `seed`."""
-        od, ad = self.config['ob_dims'][0], self.config['action_dim']
-        is_torch = hasattr(observations, 'data_ptr')
-        if int(observations.shape[-1]) != od:
-            raise ValueError(f'observations last dim must be {od}, got {tuple(observations.shape)}')
-        lead = tuple(observations.shape[:-1])
-        n = int(np.prod(lead)) if lead else 1
-        o = _Arg(observations, (n, od))
-        z = _Arg(noises, (n, ad))
-        if is_torch and observations.is_cuda:
-            torch = __import__('torch')
-            out = torch.empty(lead + (ad,), dtype=torch.float32, device=observations.device)
-            optr = out.data_ptr()
-        else:
-            out = np.empty(lead + (ad,), dtype=np.float32)
-            optr = out.ctypes.data
-        if seed is None and noises is None:
-            self._sample_calls += 1
-            sd = (self._seed << 20) ^ self._sample_calls
-        else:
-            sd = _seed_to_u64(seed)
-        self._check(self._lib.fql_sac_sample_actions(self._h, o.ptr, n, z.ptr, sd & 0xFFFFFFFFFFFFFFFF, float(temperature), optr,
-                                                     self._stream([o, z])))
-        return out
-
     def sac_stats(self):
         """(launches, MACs) of one update."""
         la, ma = C.c_int64(), C.c_int64()
         self._check(self._lib.fql_sac_stats(self._h, C.byref(la), C.byref(ma)))
         return int(la.value), int(ma.value)
-
-    # -- FQL-only paths, refused before the library is called ----------------------------------
-    def _refuse(self, what):
-        raise NotImplementedError(f'SAC: {what} is not available (FQL agents only)')
-
-    def compute_flow_actions(self, observations, noises):
-        self._refuse('compute_flow_actions (the actor is a Gaussian, there is no flow)')
-
-    def update_begin(self, *a, **k):
-        self._refuse('the data-parallel update halves')
-
-    def update_begin_split(self, *a, **k):
-        self._refuse('the data-parallel update halves')
-
-    def update_end(self, *a, **k):
-        self._refuse('the data-parallel update halves')
-
-    def update_end_split(self, *a, **k):
-        self._refuse('the data-parallel update halves')
-
-    def grad_buckets(self):
-        self._refuse('gradient buckets')
 
 
 __all__ = ['SACAgent', 'SAC_INFO_KEYS', 'SAC_NOISE_KEYS', 'get_config']

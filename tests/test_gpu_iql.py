@@ -234,6 +234,26 @@ def test_sample_actions_matches_restatement(const_std):
     np.testing.assert_array_equal(out, a.sample_actions(obs, noises=z, temperature=1.0))
 
 
+@pytest.mark.parametrize('const_std', [True, False])
+def test_sample_actions_across_the_row_chunk(const_std):
+    """n = 4096 + 37 rows: two chunks of the sampling loop, the second one short.  The rows on both sides of the boundary and the last
+    row equal their single-observation calls bitwise, and a seeded draw (keyed by the row number of the call) repeats."""
+    od, ad, B, H = SMALL
+    cfg, _, batch, _, params = _problem(SMALL, 7, const_std=const_std)
+    a = _agent(cfg, batch, params=params)
+    n = 4096 + 37
+    rng = np.random.default_rng(7)
+    obs = rng.standard_normal((n, od)).astype(np.float32)
+    z = rng.standard_normal((n, ad)).astype(np.float32)
+    got = a.sample_actions(obs, noises=z, temperature=1.0)
+    assert got.shape == (n, ad) and np.abs(got).max() <= 1.0
+    np.testing.assert_allclose(got, _ref(params, cfg, SMALL).sample_actions(obs, z, 1.0), atol=2e-5)
+    for row in (4095, 4096, n - 1):
+        np.testing.assert_array_equal(got[row], a.sample_actions(obs[row], noises=z[row], temperature=1.0), err_msg=str(row))
+    drawn = a.sample_actions(obs, seed=11)
+    np.testing.assert_array_equal(drawn, a.sample_actions(obs, seed=11))
+
+
 def test_checkpoint_round_trip_is_bitwise(tmp_path):
     from fql_amd import checkpoint
     cfg, _, batch, noise, _ = _problem(SMALL, 7, actor_loss='ddpgbc', const_std=False)
