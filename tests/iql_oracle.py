@@ -170,10 +170,11 @@ class OracleIQL(O.OracleFQL):
             raise ValueError(f"Unsupported actor loss: {cfg['actor_loss']}")
         return f
 
-    def kink_margins(self, batch, noise):
+    def kink_margins(self, batch, noise, f=None):
         """Distance of every element from each point where the loss is not smooth (or its value branches): q - v = 0 (expectile weight),
-        q1 = q2 of the ddpgbc critic pair, |x| = 1 of the clipped q_actions, alpha adv = log 100 (AWR's cap), log_stds at -5 / 2."""
-        f = self._forward(batch, noise)
+        q1 = q2 of the ddpgbc critic pair, |x| = 1 of the clipped q_actions, alpha adv = log 100 (AWR's cap), log_stds at -5 / 2.  `f`: this
+        state's _forward(batch, noise), where the caller has it already."""
+        f = self._forward(batch, noise) if f is None else f
         m = {'expectile': float(np.abs(f['vdiff']).min())}
         if 'log_stds' in self.params['modules_actor']:
             m['log_stds'] = float(np.minimum(np.abs(f['raw'] - LOG_STD_MIN), np.abs(f['raw'] - LOG_STD_MAX)).min())
@@ -184,10 +185,10 @@ class OracleIQL(O.OracleFQL):
             m['unit_clip'] = float(np.abs(np.abs(f['x']) - 1.0).min())
         return m
 
-    def _losses(self, batch, noise, want_grads: bool):
+    def _losses(self, batch, noise, want_grads: bool, f=None):
         cfg = self.config
         dt = self.dtype.type
-        f = self._forward(batch, noise)
+        f = self._forward(batch, noise) if f is None else f
         B, A, act = f['B'], f['A'], f['act']
         alpha = dt(cfg['alpha'])
         info = {'value/value_loss': f['value_loss'], 'value/v_mean': f['v'].mean(), 'value/v_max': f['v'].max(), 'value/v_min': f['v'].min(),
@@ -254,6 +255,28 @@ class OracleIQL(O.OracleFQL):
 
 def make_noise(batch_size, act_dim, seed):
     return {'eps': np.random.default_rng(seed).standard_normal((batch_size, act_dim)).astype(np.float32)}
+
+
+def clear_of_unit_clip(ref, batch, noise, margin):
+    """A copy of `noise` whose ddpgbc q_actions x = mean + exp(ls) eps keep 2 * margin from the |x| = 1 kink under `ref`'s current
+    parameters.  At B x act in the thousands no seed clears that kink by itself, so each element with ||x| - 1| < 2 * margin gets the
+    eps that puts it at |x| = 1 -/+ 2 * margin on the side it was on, rounded to float32 as the engine receives it (the rounding moves
+    x by about 1e-7 |x - mean|, far inside the second margin).  The mean does not depend on eps, so the move is exact and touches no
+    other element.  Two conditions keep this an ordinary random problem: at most 1 % of the elements move, and between 20 % and 80 %
+    of them end up clipped, so both branches of the clip mask stay live."""
+    mean = ref.actor_mean(batch['observations'])
+    s = np.exp(np.clip(ref.raw_log_stds(), LOG_STD_MIN, LOG_STD_MAX))
+    eps = np.asarray(noise['eps'], np.float32)
+    x = mean + s * eps.astype(np.float64)
+    near = np.abs(np.abs(x) - 1.0) < 2 * margin
+    target = np.sign(x) * (1.0 + np.where(np.abs(x) < 1.0, -2.0, 2.0) * margin)
+    out = np.where(near, ((target - mean) / s).astype(np.float32), eps)
+    x = mean + s * out.astype(np.float64)
+    clipped = float(np.mean(np.abs(x) > 1.0))
+    assert near.mean() <= 0.01, f'{int(near.sum())} of {near.size} elements moved'
+    assert 0.2 <= clipped <= 0.8, f'{clipped:.3f} of the q_actions clipped'
+    assert np.abs(np.abs(x) - 1.0).min() >= margin
+    return dict(noise, eps=out)
 
 
 def randomize(params, seed, scale=0.3, log_stds=(-1.5, 1.0)):

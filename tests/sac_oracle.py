@@ -190,6 +190,19 @@ class OracleSAC(O.OracleFQL):
         grads['modules_alpha'] = {'log_value': np.asarray(alpha_g * (entropy - dt(self.target_entropy())), dtype=self.dtype)}
         return loss, info, grads
 
+    def kink_margins(self, batch, noise):
+        """Distance of every element from each point where the loss is not smooth: the raw log-std at -5 / 2 over all 2B actor rows
+        (next observations under the stored parameters, observations under the differentiated ones), and q1 = q2 of the target pair
+        where q_agg = 'min' takes the smaller (the actor loss takes the pair's mean)."""
+        mn, rn = self.actor_heads(batch['next_observations'], stored=True)
+        raw = np.concatenate([rn, self.actor_heads(batch['observations'])[1]])
+        m = {'log_std_clip': float(np.minimum(np.abs(raw - LOG_STD_MIN), np.abs(raw - LOG_STD_MAX)).min())}
+        if self.config['q_agg'] == 'min':
+            a_n = self.sample(mn, rn, noise['eps1'])[0]
+            tq = self._critic('modules_target_critic', self._c(batch['next_observations']), a_n, stored=True)
+            m['q_tie'] = float(np.abs(tq[0] - tq[1]).min())
+        return m
+
     def total_loss(self, batch, noise):
         loss, info, _ = self._losses(batch, noise, want_grads=False)
         return loss, info

@@ -6,7 +6,7 @@ import pytest
 
 from oracle import fql_oracle as O
 from tests import iql_oracle as IO
-from tests.util import assert_info_close, leaf_dict
+from tests.util import assert_info_close, leaf_dict, sync_restatement
 
 pytestmark = pytest.mark.gpu
 SMALL, BIG = (5, 2, 16, 32), (29, 8, 64, 128)   # obs, act, B, H; BIG: action width 8, rows not a multiple of 32 (tests/test_gpu_shapes.py)
@@ -21,11 +21,18 @@ UPDATE_CASES = [
 ]
 
 
+def _hidden(shape):
+    """(actor hidden, value hidden) of a shape (obs, act, B, H): H is one width for 4 + 4 layers, or the pair of tuples itself."""
+    H = shape[3]
+    return ((H,) * 4, (H,) * 4) if isinstance(H, int) else (tuple(H[0]), tuple(H[1]))
+
+
 def _cfg(shape, **kw):
     import fql_amd
-    od, ad, B, H = shape
+    od, ad, B, _ = shape
+    actor, value = _hidden(shape)
     cfg = fql_amd.iql.get_config()
-    cfg.update(actor_hidden_dims=(H,) * 4, value_hidden_dims=(H,) * 4, batch_size=B)
+    cfg.update(actor_hidden_dims=actor, value_hidden_dims=value, batch_size=B)
     cfg.update(kw)
     return cfg
 
@@ -33,7 +40,7 @@ def _cfg(shape, **kw):
 def _problem(shape=SMALL, seed=0, **kw):
     """(cfg, dataset, batch, noise, params): parameters from the restatement's init, moved away from it (a CPU-only recipe, so the
     kink margins of a seed can be checked without a GPU)."""
-    od, ad, B, H = shape
+    od, ad, B, _ = shape
     cfg = _cfg(shape, **kw)
     ds = O.make_synthetic_dataset(max(4 * B, 64), od, ad, seed=seed)
     idx = np.random.default_rng(seed + 1).integers(0, len(ds['observations']), size=B)
@@ -90,33 +97,43 @@ def test_leaves_match_reference_layout_and_init(const_std):
 
 
 def _check_step(a, ref, batch, noise, cfg, pre):
+    """One update of both sides on (batch, noise) from their current state: the kink margins of the restatement, then infos, every
+    leaf's gradient (read back out of Adam's first moment), nu, the post-step parameters and the Polyak target.  Returns the worst
+    gradient error relative to its leaf's largest gradient, with the leaf's name, and the restatement's infos."""
     keys = IO.INFO_KEYS[cfg['actor_loss']]
-    margins = ref.kink_margins(batch, noise)
+    f = ref._forward(batch, noise)
+    margins = ref.kink_margins(batch, noise, f)
     assert min(margins.values()) >= MARGIN, margins
-    _, _, g_ref = ref._losses(batch, noise, want_grads=True)
+    _, want, g_ref = ref._losses(batch, noise, want_grads=True, f=f)
     mu0 = leaf_dict(a.get_opt_state()['mu'])
     pre_ref = leaf_dict(O.tree_map(np.copy, ref.params))
     _, info = a.update(batch, noise=noise)
     info = info.to_dict()
     assert tuple(info) == keys
-    _, want = ref.update(batch, noise)
+    want.update(ref.grad_stats(g_ref))   # OracleIQL.update, on the forward pass and the gradients computed above
+    ref.apply_gradients(g_ref)
+    want = {k: float(want[k]) for k in keys}
     assert_info_close(info, want, rtol=5e-5, atol=5e-6, keys=keys)
     a.synchronize()
     opt = a.get_opt_state()
     mu, nu, mu_ref, nu_ref = leaf_dict(opt['mu']), leaf_dict(opt['nu']), leaf_dict(ref.mu), leaf_dict(ref.nu)
     new, new_ref = leaf_dict(a.get_params()), leaf_dict(ref.params)
+    worst = (0.0, '')
     for p, g in leaf_dict(g_ref).items():
         if p.startswith('modules_target_'):   # Polyak from the PRE-step critic
             np.testing.assert_allclose(new[p], 0.005 * pre[p.replace('target_', '')] + 0.995 * pre[p], atol=1e-6, err_msg=p)
             continue
         # the bounds of tests/test_gpu_sac.py
         tol = 5e-5 * np.abs(g).max() + 1e-5 * np.abs(mu0[p]).max() + 1e-9
-        np.testing.assert_allclose((mu[p] - np.float32(0.9) * mu0[p]) / 0.1, g, rtol=0, atol=tol, err_msg=f'grad {p}')
+        got = (mu[p] - np.float32(0.9) * mu0[p]) / 0.1
+        worst = max(worst, (float(np.abs(got - g).max() / max(np.abs(g).max(), 1e-30)), p))
+        np.testing.assert_allclose(got, g, rtol=0, atol=tol, err_msg=f'grad {p}')
         np.testing.assert_allclose(nu[p], nu_ref[p], rtol=1e-4, atol=1e-4 * np.abs(nu_ref[p]).max() + 1e-20, err_msg=f'nu {p}')
         d = np.abs((new[p] - pre[p]) - (new_ref[p] - pre_ref[p]))
         stable = (np.abs(g) > 50 * tol) & (np.abs(mu_ref[p]) > 5 * tol)
         assert np.max(d[stable], initial=0) <= 2e-6, (p, np.max(d[stable], initial=0))
         assert d.max() <= 2 * cfg['lr'] + 1e-6, p
+    return worst, want
 
 
 @pytest.mark.parametrize('shape,actor_loss,const_std,actor_ln,seed', UPDATE_CASES)
@@ -129,6 +146,143 @@ def test_update_matches_fp64_restatement(shape, actor_loss, const_std, actor_ln,
     _check_step(a, ref, batch, IO.make_noise(shape[2], shape[1], seed + 77), cfg, leaf_dict(a.get_params()))
     opt = a.get_opt_state()
     assert opt['count'] == 2 and opt['step'] == 3
+
+
+# ---- the shapes that switch kernel paths -----------------------------------------------------------------------------------------------
+#
+# What each case reaches, from the conditions in fql_amd/csrc/fql_engine.hip.  The critic's first layer has in_p = round64(obs + act).
+# Its input gradient (read by fql_iql_actor_grad_kernel at dx[b * in_p + obs + a] under ddpgbc) is the lean 16-column OP_DGRAD0 when
+# K = H is a multiple of 512, M is a multiple of 16, act <= 16 and obs + 16 <= in_p; otherwise the generic first-layer dgrad GEMM.
+# ap = pad16(act) is the width of the log_stds slot, of ls_part [B, ap] and of g_ls [ap].  The row loops of the AWR, DDPG+BC and
+# actor-grad kernels and of iql_reduce_log_stds step by 256 threads; fql_iql_head_kernel takes 256 rows per block.
+#   name: ((obs, act, B, (actor hidden, value hidden)), cfg overrides, steps)
+H512 = ((512,) * 4, (512,) * 4)
+SHAPE_CASES = {
+    # IQL's default configuration: OP_DGRAD0 (in_p 64, 29 + 16 <= 64) with 8 live columns; 64x64 LDS-tiled GEMMs with LayerNorm
+    # partial sums; the value pass at M = 512
+    'default': ((29, 8, 256, H512), {}, 2),
+    # OP_DGRAD0 with all 16 columns live; ap = 16 with no padding column
+    'act16': ((29, 16, 256, H512), {}, 2),
+    # act > 16: the generic dgrad (in_p 128); ap = 32 with 11 padding columns
+    'humanoidmaze': ((69, 21, 256, H512), dict(discount=0.995), 2),
+    # four rows per thread and four head-kernel blocks; the value pass at M = 2048; OP_DGRAD0 with 4 live columns (in_p 64,
+    # 40 + 16 <= 64).  One step: the fp64 restatement costs most here.
+    'b1024': ((40, 4, 1024, H512), {}, 1),
+    # obs + 16 > in_p = 64 with act <= 16: the generic dgrad at H 512 feeding an action block 4 wide; the actor's LayerNorm at H 512
+    'obs50': ((50, 4, 256, H512), dict(actor_layer_norm=True), 1),
+    # ragged widths, actor and value networks of different depth; ap = 32 with 8 padding columns; generic dgrad (K = 80)
+    'ragged_depths': ((45, 24, 48, ((64, 64), (80, 48, 64))), {}, 2),
+    # 256 + 16 rows: threads 0..15 take two rows, the rest one; two head-kernel blocks, the second 16 rows; M no multiple of 64
+    'b272': ((11, 5, 272, ((64,) * 4, (64,) * 4)), {}, 2),
+}
+
+# (case, actor_loss, const_std, seed).  Under ddpgbc with log_stds the |x| = 1 kink is cleared by IO.clear_of_unit_clip at the state
+# of each step.  A later step runs from the engine's own state (sync_restatement: the two trajectories part by up to 2 lr per element
+# where |g| is within fp32 error), which the CPU cannot know, so there the seed must leave room: each seed is the smallest of 0..7
+# for which the fp64 restatement, on its own trajectory, keeps every margin >= MARGIN in the first step and >= 3 MARGIN in the second
+# (tests/test_kink_margins_cpu.py checks that on the CPU; _check_step asserts MARGIN at the state it actually runs from).
+# ragged_depths with ddpgbc and const_std=True is left out: there x = mean has no noise to move, and no seed in 0..7 keeps all
+# 48 x 24 means 1e-3 away from |mean| = 1.
+SHAPE_COMBOS = [
+    ('default', 'awr', False, 1), ('default', 'ddpgbc', False, 1),
+    ('act16', 'awr', False, 1), ('act16', 'ddpgbc', False, 1), ('act16', 'ddpgbc', True, 4),
+    ('humanoidmaze', 'awr', False, 0), ('humanoidmaze', 'ddpgbc', False, 0), ('humanoidmaze', 'ddpgbc', True, 2),
+    ('b1024', 'awr', False, 0), ('b1024', 'ddpgbc', False, 0),
+    ('obs50', 'awr', False, 0), ('obs50', 'ddpgbc', False, 0),
+    ('ragged_depths', 'awr', False, 0), ('ragged_depths', 'ddpgbc', False, 0),
+    ('b272', 'awr', False, 1), ('b272', 'ddpgbc', False, 2),
+]
+# the batch-size switch: one ddpgbc agent with log_stds, these batch sizes in turn (data seed SWITCH_SEED + step)
+SWITCH_SHAPE, SWITCH_BATCHES, SWITCH_SEED = (29, 8, 64, 64), (64, 16, 272, 64), 0
+
+
+def _cleared(ref, batch, noise, cfg):
+    """`noise` moved off the |x| = 1 kink at ref's current parameters, where the loss reads it (ddpgbc with log_stds)."""
+    if cfg['actor_loss'] == 'ddpgbc' and not cfg['const_std']:
+        return IO.clear_of_unit_clip(ref, batch, noise, MARGIN)
+    return noise
+
+
+def shape_problem(case, actor_loss, const_std, seed):
+    """(shape, steps, cfg, batch, params, noises): the problem of one SHAPE_COMBOS entry, built without an engine.  noises[i] is the
+    draw of step i, to be passed through _cleared at the restatement's state before that step."""
+    shape, kw, steps = SHAPE_CASES[case]
+    cfg, _, batch, noise, params = _problem(shape, seed, actor_loss=actor_loss, const_std=const_std, **kw)
+    return shape, steps, cfg, batch, params, [noise, IO.make_noise(shape[2], shape[1], seed + 77)][:steps]
+
+
+def switch_problem(cfg, i, B):
+    """(batch, noise) of step i of the batch-size switch test."""
+    od, ad = SWITCH_SHAPE[:2]
+    ds = O.make_synthetic_dataset(max(4 * B, 64), od, ad, seed=SWITCH_SEED + i)
+    idx = np.random.default_rng(SWITCH_SEED + i + 1).integers(0, len(ds['observations']), size=B)
+    return O.sample_batch(ds, idx), IO.make_noise(B, ad, SWITCH_SEED + i + 2)
+
+
+@pytest.mark.parametrize('case,actor_loss,const_std,seed', SHAPE_COMBOS)
+def test_shape_cases_match_fp64_restatement(case, actor_loss, const_std, seed):
+    """total_loss (no state change), then the update steps of test_update_matches_fp64_restatement, at the shapes above, the second
+    one from the engine's own state and moments.  Nothing is masked out of any comparison."""
+    shape, steps, cfg, batch, params, noises = shape_problem(case, actor_loss, const_std, seed)
+    a = _agent(cfg, batch, params=params)
+    ref = _ref(params, cfg, shape)
+    keys = IO.INFO_KEYS[actor_loss]
+    noise = _cleared(ref, batch, noises[0], cfg)
+    loss, info = a.total_loss(batch, noise=noise)
+    a.synchronize()
+    after = leaf_dict(a.get_params())
+    for k, v in leaf_dict(params).items():
+        np.testing.assert_array_equal(after[k], v, err_msg=k)
+    assert a.get_opt_state()['count'] == 0
+    worst, want = _check_step(a, ref, batch, noise, cfg, leaf_dict(params))
+    # the first step's infos are total_loss's: the restatement computes them once
+    assert tuple(info) == keys[:-3]
+    assert_info_close(info, want, rtol=5e-5, atol=5e-6, keys=keys[:-3])
+    want_loss = want['value/value_loss'] + want['critic/critic_loss'] + want['actor/actor_loss']
+    assert abs(loss - want_loss) <= 1e-5 * max(1.0, abs(want_loss))
+    for nz in noises[1:]:
+        sync_restatement(ref, a)
+        worst = max(worst, _check_step(a, ref, batch, _cleared(ref, batch, nz, cfg), cfg, leaf_dict(a.get_params()))[0])
+    opt = a.get_opt_state()
+    assert opt['count'] == steps and opt['step'] == steps + 1
+    print(f'worst relative gradient error {worst[0]:.3e} ({worst[1]})')
+
+
+def test_batch_size_switches_track_restatement():
+    """B = 64, 16, 272, 64: each switch rebuilds the workspace and the programs; every step is compared after the rebuild, from the
+    engine's own carried state."""
+    cfg, _, _, _, params = _problem(SWITCH_SHAPE, SWITCH_SEED, actor_loss='ddpgbc', const_std=False)
+    batch0, _ = switch_problem(cfg, 0, SWITCH_BATCHES[0])
+    a = _agent(cfg, batch0, params=params)
+    ref = _ref(params, cfg, SWITCH_SHAPE)
+    for i, B in enumerate(SWITCH_BATCHES):
+        batch, noise = switch_problem(cfg, i, B)
+        assert a.get_opt_state()['count'] == i
+        sync_restatement(ref, a)
+        _check_step(a, ref, batch, _cleared(ref, batch, noise, cfg), cfg, leaf_dict(a.get_params()))
+    opt = a.get_opt_state()
+    assert opt['count'] == 4 and opt['step'] == 5
+
+
+@pytest.mark.parametrize('case', ['act16', 'humanoidmaze'])
+def test_sample_actions_at_hidden_512(case):
+    """n = 1, 37 and 4097 (one row past the first 4096-row chunk) with explicit noise at temperature 1 and 0; row n - 1 equals its
+    single-observation call bitwise."""
+    shape, kw, _ = SHAPE_CASES[case]
+    od, ad = shape[:2]
+    cfg, _, batch, _, params = _problem(shape, 6, const_std=False, **kw)
+    a = _agent(cfg, batch, params=params)
+    ref = _ref(params, cfg, shape)
+    rng = np.random.default_rng(6)
+    obs = rng.standard_normal((4097, od)).astype(np.float32)
+    z = rng.standard_normal((4097, ad)).astype(np.float32)
+    want = {t: ref.sample_actions(obs, z, t) for t in (1.0, 0.0)}   # row-wise: the first n rows are the n-row call's
+    for n in (1, 37, 4097):
+        for temp in (1.0, 0.0):
+            got = a.sample_actions(obs[:n], noises=z[:n], temperature=temp)
+            assert got.shape == (n, ad) and np.abs(got).max() <= 1.0
+            np.testing.assert_allclose(got, want[temp][:n], atol=2e-5, err_msg=f'{n} {temp}')
+            np.testing.assert_array_equal(got[n - 1], a.sample_actions(obs[n - 1], noises=z[n - 1], temperature=temp))
 
 
 @pytest.mark.parametrize('actor_loss', ['awr', 'ddpgbc'])

@@ -6,24 +6,26 @@ import pytest
 
 from oracle import fql_oracle as O
 from tests import sac_oracle as SO
-from tests.util import assert_info_close, leaf_dict
+from tests.util import assert_info_close, leaf_dict, sync_restatement
 
 pytestmark = pytest.mark.gpu
 OD, AD = 29, 8
+MARGIN = 1e-3
 
 
-def _cfg(H, B, **kw):
+def _cfg(H, B, actor=None, value=None, **kw):
+    """`actor` / `value`: the hidden tuples where they are not 4 layers of H."""
     import fql_amd
     cfg = fql_amd.sac.get_config()
-    cfg.update(actor_hidden_dims=(H,) * 4, value_hidden_dims=(H,) * 4, batch_size=B)
+    cfg.update(actor_hidden_dims=tuple(actor or (H,) * 4), value_hidden_dims=tuple(value or (H,) * 4), batch_size=B)
     cfg.update(kw)
     return cfg
 
 
-def _problem(H=64, B=64, seed=0, **kw):
-    ds = O.make_synthetic_dataset(max(4 * B, 64), OD, AD, seed=seed)
+def _problem(H=64, B=64, seed=0, od=OD, ad=AD, actor=None, value=None, **kw):
+    ds = O.make_synthetic_dataset(max(4 * B, 64), od, ad, seed=seed)
     idx = np.random.default_rng(seed + 1).integers(0, len(ds['observations']), size=B)
-    return _cfg(H, B, **kw), ds, O.sample_batch(ds, idx), SO.make_noise(B, AD, seed + 2)
+    return _cfg(H, B, actor, value, **kw), ds, O.sample_batch(ds, idx), SO.make_noise(B, ad, seed + 2)
 
 
 def _randomized(params, seed, scale=0.1):
@@ -89,30 +91,38 @@ def test_leaves_match_reference_layout_and_init():
 
 
 def _check_step(a, ref, batch, noise, cfg, pre):
-    _, _, g_ref = ref._losses(batch, noise, want_grads=True)
+    """One update of both sides on (batch, noise) from their current state.  Returns the worst gradient error relative to its leaf's
+    largest gradient, with the leaf's name, and the restatement's infos."""
+    _, want, g_ref = ref._losses(batch, noise, want_grads=True)
     mu0 = leaf_dict(a.get_opt_state()['mu'])
     pre_ref = leaf_dict(O.tree_map(np.copy, ref.params))
     _, info = a.update(batch, noise=noise)
     info = info.to_dict()
     assert tuple(info) == SO.INFO_KEYS
-    _, want = ref.update(batch, noise)
+    want.update(ref.grad_stats(g_ref))   # OracleSAC.update, on the gradients computed above
+    ref.apply_gradients(g_ref)
+    want = {k: float(want[k]) for k in SO.INFO_KEYS}
     assert_info_close(info, want, rtol=5e-5, atol=5e-6, keys=SO.INFO_KEYS)
     a.synchronize()
     opt = a.get_opt_state()
     mu, nu, mu_ref, nu_ref = leaf_dict(opt['mu']), leaf_dict(opt['nu']), leaf_dict(ref.mu), leaf_dict(ref.nu)
     new, new_ref = leaf_dict(a.get_params()), leaf_dict(ref.params)
+    worst = (0.0, '')
     for p, g in leaf_dict(g_ref).items():
         if p.startswith('modules_target_'):   # Polyak from the PRE-step critic
             np.testing.assert_allclose(new[p], 0.005 * pre[p.replace('target_', '')] + 0.995 * pre[p], atol=1e-6, err_msg=p)
             continue
         # (5e-5: the critic's bias gradients at B = 256 sum 256 fp32 rows of LayerNorm backward)
         tol = 5e-5 * np.abs(g).max() + 1e-5 * np.abs(mu0[p]).max() + 1e-9
-        np.testing.assert_allclose((mu[p] - np.float32(0.9) * mu0[p]) / 0.1, g, rtol=0, atol=tol, err_msg=f'grad {p}')
+        got = (mu[p] - np.float32(0.9) * mu0[p]) / 0.1
+        worst = max(worst, (float(np.abs(got - g).max() / max(np.abs(g).max(), 1e-30)), p))
+        np.testing.assert_allclose(got, g, rtol=0, atol=tol, err_msg=f'grad {p}')
         np.testing.assert_allclose(nu[p], nu_ref[p], rtol=1e-4, atol=1e-4 * np.abs(nu_ref[p]).max() + 1e-20, err_msg=f'nu {p}')
         d = np.abs((new[p] - pre[p]) - (new_ref[p] - pre_ref[p]))
         stable = (np.abs(g) > 50 * tol) & (np.abs(mu_ref[p]) > 5 * tol)
         assert np.max(d[stable], initial=0) <= 2e-6, (p, np.max(d[stable], initial=0))
         assert d.max() <= 2 * cfg['lr'] + 1e-6, p
+    return worst, want
 
 
 @pytest.mark.parametrize('H,B,tanh_squash,backup_entropy,q_agg', [(64, 64, True, False, 'min'), (64, 64, False, False, 'min'),
@@ -131,6 +141,91 @@ def test_update_matches_fp64_restatement(H, B, tanh_squash, backup_entropy, q_ag
     _check_step(a, ref, batch, SO.make_noise(B, AD, 77), cfg, leaf_dict(a.get_params()))
     opt = a.get_opt_state()
     assert opt['count'] == 2 and opt['step'] == 3
+
+
+# ---- the shapes that switch kernel paths -----------------------------------------------------------------------------------------------
+#
+# What each case reaches, from the conditions in fql_amd/csrc/fql_engine.hip.  The actor's last layer is [H, 2 ap] with ap =
+# pad16(act): the mean in columns [0, act), the raw log-std in [ap, ap + act); fql_sac_act_kernel reads both and writes the action
+# block of the critic's input at column obs with row stride in_p = round64(obs + act).  The critic's input gradient under the actor
+# loss is the lean 16-column OP_DGRAD0 when H is a multiple of 512, act <= 16 and obs + 16 <= in_p; otherwise the generic dgrad.
+#   name: (obs, act, B, actor hidden, value hidden, cfg overrides, steps, data seed, parameter seed)
+# tanh_squash=True and q_agg='min' unless overridden.  The seeds are the first (data, parameter) pair of a CPU search (parameter seeds
+# from 5, data seeds 1..4 for each) for which the fp64 restatement keeps every raw log-std MARGIN away from -5 and 2 and every target
+# pair MARGIN apart in the first step and, on its own trajectory, 3 MARGIN in the second (tests/test_kink_margins_cpu.py checks that
+# on the CPU).  The second step runs from the engine's own state (sync_restatement), which the CPU cannot know: the room is for that,
+# and the test asserts MARGIN at the state it actually runs from.
+SHAPE_CASES = {
+    # OP_DGRAD0 with all 16 columns live; head layer 32 wide with no padding column
+    'act16': (29, 16, 256, (512,) * 4, (512,) * 4, {}, 2, 4, 5),
+    # generic dgrad (act > 16, in_p 128); head layer 64 wide: raw log-std in columns [32, 53)
+    'humanoidmaze': (69, 21, 256, (512,) * 4, (512,) * 4, {}, 2, 1, 10),
+    # the actor on 2048 rows, the critics at M = 1024; OP_DGRAD0 with 4 live columns (in_p 64, 40 + 16 <= 64).  One step: the fp64
+    # restatement costs most here.
+    'b1024': (40, 4, 1024, (512,) * 4, (512,) * 4, {}, 1, 1, 5),
+    # ragged widths and different depths; head layer 64 wide with 8 padding columns per half; generic dgrad (K = 80)
+    'ragged_depths': (45, 24, 48, (64, 64), (80, 48, 64), dict(backup_entropy=True), 2, 1, 5),
+    # 256 + 16 rows, 544 actor rows: M no multiple of 64; no tanh
+    'b272': (11, 5, 272, (64,) * 4, (64,) * 4, dict(tanh_squash=False), 2, 1, 5),
+}
+
+
+def shape_problem(case):
+    """(od, ad, cfg, batch, params, noises): the problem of one SHAPE_CASES entry, built without an engine (SO.init_params moved by
+    _randomized on both sides).  noises[i] is the draw of step i."""
+    od, ad, B, actor, value, kw, steps, seed, pseed = SHAPE_CASES[case]
+    cfg, _, batch, noise = _problem(0, B, seed, od, ad, actor, value, **kw)
+    params = _randomized(SO.init_params(pseed, od, ad, cfg), pseed)
+    return od, ad, cfg, batch, params, [noise, SO.make_noise(B, ad, 77)][:steps]
+
+
+@pytest.mark.parametrize('case', list(SHAPE_CASES))
+def test_shape_cases_match_fp64_restatement(case):
+    """total_loss (no state change), then the update steps of test_update_matches_fp64_restatement, at the shapes above, the second
+    one from the engine's own state and moments."""
+    od, ad, cfg, batch, params, noises = shape_problem(case)
+    a = _agent(cfg, batch, params=params)
+    ref = SO.OracleSAC(params, dict(cfg), od, ad, np.float64)
+    raw = ref.actor_heads(batch['observations'])[1]
+    assert (raw < SO.LOG_STD_MIN).any() and (raw > SO.LOG_STD_MAX).any()   # the clip bites on both sides
+    loss, info = a.total_loss(batch, noise=noises[0])
+    a.synchronize()
+    after = leaf_dict(a.get_params())
+    for k, v in leaf_dict(params).items():
+        np.testing.assert_array_equal(after[k], v, err_msg=k)
+    assert a.get_opt_state()['count'] == 0
+    worst = (0.0, '')
+    for i, nz in enumerate(noises):
+        if i:
+            sync_restatement(ref, a)
+        margins = ref.kink_margins(batch, nz)
+        assert min(margins.values()) >= MARGIN, margins
+        w, want = _check_step(a, ref, batch, nz, cfg, leaf_dict(a.get_params()))
+        worst = max(worst, w)
+        if i == 0:   # the first step's infos are total_loss's: the restatement computes them once
+            assert tuple(info) == SO.INFO_KEYS[:11]
+            assert_info_close(info, want, rtol=5e-5, atol=5e-6, keys=SO.INFO_KEYS[:11])
+            want_loss = want['critic/critic_loss'] + want['actor/total_loss']
+            assert abs(loss - want_loss) <= 1e-5 * max(1.0, abs(want_loss))
+    opt = a.get_opt_state()
+    assert opt['count'] == len(noises) and opt['step'] == len(noises) + 1
+    print(f'worst relative gradient error {worst[0]:.3e} ({worst[1]})')
+
+
+def test_sample_actions_at_act21_hidden_512():
+    """The 64-wide head layer in the sampling program: n = 1, 37 and 4097 (one row past the first 4096-row chunk), explicit noise."""
+    od, ad, cfg, batch, params, _ = shape_problem('humanoidmaze')
+    a = _agent(cfg, batch, params=params)
+    ref = SO.OracleSAC(params, dict(cfg), od, ad, np.float64)
+    rng = np.random.default_rng(21)
+    obs = rng.standard_normal((4097, od)).astype(np.float32)
+    z = rng.standard_normal((4097, ad)).astype(np.float32)
+    want = ref.sample_actions(obs, z)   # row-wise: the first n rows are the n-row call's
+    for n in (1, 37, 4097):
+        got = a.sample_actions(obs[:n], noises=z[:n])
+        assert got.shape == (n, ad) and np.abs(got).max() <= 1.0
+        np.testing.assert_allclose(got, want[:n], atol=2e-5, err_msg=str(n))
+        np.testing.assert_array_equal(got[n - 1], a.sample_actions(obs[n - 1], noises=z[n - 1]))
 
 
 def test_total_loss_matches_and_changes_no_state():
