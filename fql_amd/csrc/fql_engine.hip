@@ -546,13 +546,19 @@ struct fql_engine {
     fql_group_s* group = nullptr;
     hipEvent_t grp_done = nullptr;
     bool grp_pending = false, grp_touched = true;
+    // grp_legacy: that update ran on the legacy default stream (FQL_STREAM_LEGACY).  No event is recorded there: the HIP runtime keeps the
+    // stream's handle, (hipStream_t)1, in the event, and hipStreamWaitEvent on such an event dereferences it.  Waiting for such an update
+    // is a device synchronise instead.
+    bool grp_legacy = false;
     void group_fence() {   // host wait for the group's last update (every entry point: it may read or write what that update writes)
         grp_touched = true;
-        if (grp_pending) { HIP_CHECK(hipEventSynchronize(grp_done)); grp_pending = false; }
+        if (grp_pending) { HIP_CHECK(grp_legacy ? hipDeviceSynchronize() : hipEventSynchronize(grp_done)); grp_pending = false; }
     }
     void group_order(hipStream_t s) {   // the same as a stream dependency, for entry points that only enqueue on `s`
         grp_touched = true;
-        if (grp_pending) HIP_CHECK(hipStreamWaitEvent(s, grp_done, 0));
+        if (!grp_pending) return;
+        if (!grp_legacy) HIP_CHECK(hipStreamWaitEvent(s, grp_done, 0));
+        else if (s != hipStreamLegacy) { HIP_CHECK(hipDeviceSynchronize()); grp_pending = false; }   // (on the legacy stream itself: in order)
     }
     // lazily read infos (the reference returns device scalars that are only read at log time, main.py:276): a ring of pinned host
     // slots, one asynchronous 52-byte copy + event per ticket
@@ -4535,6 +4541,7 @@ int fql_set_step(fql_handle h, int64_t adam_count, int64_t train_step) {
         DevState st;
         HIP_CHECK(hipMemcpy(&st, h->d_state, sizeof st, hipMemcpyDeviceToHost));
         st.adam_count = adam_count; st.train_step = train_step;
+        st.rng_step = (uint64_t)adam_count;   // every update advances both: a restored agent draws what the saved one would have drawn next
         st.b1pow = std::pow(0.9, (double)adam_count); st.b2pow = std::pow(0.999, (double)adam_count);
         HIP_CHECK(hipMemcpy(h->d_state, &st, sizeof st, hipMemcpyHostToDevice));
     });
@@ -5512,6 +5519,7 @@ struct fql_group_s {
     hipGraphExec_t exec = nullptr;
     std::vector<void*> allocs;
     int64_t* d_idx = nullptr;   // [K][B] staging of host row indices
+    hipStream_t last = nullptr; // the stream of the last update: an update on another stream waits for that update first
 
     void* upload(const void* src, size_t bytes) {
         void* d = nullptr;
@@ -5605,8 +5613,9 @@ struct fql_group_s {
 
     void release() {
         if (lanes[0]) hipStreamSynchronize(lanes[0]);
+        if (last == hipStreamLegacy) hipDeviceSynchronize();
         if (ev_done) hipEventSynchronize(ev_done);
-        for (fql_handle h : m) { h->group = nullptr; h->grp_pending = false; h->grp_done = nullptr; h->grp_touched = true; }
+        for (fql_handle h : m) { h->group = nullptr; h->grp_pending = h->grp_legacy = false; h->grp_done = nullptr; h->grp_touched = true; }
         if (exec) hipGraphExecDestroy(exec);
         if (graph) hipGraphDestroy(graph);
         destroy_lane_events(*this);
@@ -5711,6 +5720,10 @@ int fql_group_update_from_dataset(fql_group g, const int64_t* idx, int batch_siz
         for (int i = 0; i < g->K; ++i)
             if (g->m[i]->began) { g_create_error = "fql_group_update_from_dataset: a member is between fql_update_begin and fql_update_end"; return FQL_E_STATE; }
         const hipStream_t s = stream ? (hipStream_t)stream : g->lanes[0];
+        // behind the group's last update where that ran on another stream (the caller's, then the group's own, or the reverse)
+        if (g->last && g->last != s) HIP_CHECK(g->last == hipStreamLegacy ? hipDeviceSynchronize() : hipStreamWaitEvent(s, g->ev_done, 0));
+        g->last = s;
+        const bool legacy = s == hipStreamLegacy;   // no event there (fql_engine::grp_legacy): waits for this update synchronise the device
         // ordering rule 1: behind everything submitted through a member since the last group update
         for (fql_handle h : g->m) {
             if (!h->grp_touched) continue;
@@ -5731,9 +5744,9 @@ int fql_group_update_from_dataset(fql_group g, const int64_t* idx, int batch_siz
             for (int i = 0; i < g->K; ++i)
                 HIP_CHECK(hipMemcpyAsync(info13xk + (size_t)i * FQL_NUM_INFO, &g->m[i]->d_state->info[0], FQL_NUM_INFO * sizeof(float), hipMemcpyDefault, s));
         }
-        HIP_CHECK(hipEventRecord(g->ev_done, s));
-        for (fql_handle h : g->m) { h->grp_pending = true; h->grp_touched = false; }
-        if (info13xk && !fql_engine::is_device_ptr(info13xk)) HIP_CHECK(hipEventSynchronize(g->ev_done));
+        if (!legacy) HIP_CHECK(hipEventRecord(g->ev_done, s));
+        for (fql_handle h : g->m) { h->grp_pending = true; h->grp_legacy = legacy; h->grp_touched = false; }
+        if (info13xk && !fql_engine::is_device_ptr(info13xk)) HIP_CHECK(legacy ? hipDeviceSynchronize() : hipEventSynchronize(g->ev_done));
     } catch (const Invalid& e) {
         g_create_error = e.msg; return FQL_E_INVALID;
     } catch (const HipError& e) {
@@ -5744,7 +5757,7 @@ int fql_group_update_from_dataset(fql_group g, const int64_t* idx, int batch_siz
 
 int fql_group_synchronize(fql_group g) {
     if (!g) { g_create_error = "fql_group_synchronize: NULL group"; return FQL_E_INVALID; }
-    if (hipEventSynchronize(g->ev_done) != hipSuccess || hipStreamSynchronize(g->lanes[0]) != hipSuccess) {
+    if ((g->last == hipStreamLegacy ? hipDeviceSynchronize() : hipEventSynchronize(g->ev_done)) != hipSuccess || hipStreamSynchronize(g->lanes[0]) != hipSuccess) {
         g_create_error = std::string("fql_group_synchronize: ") + hipGetErrorString(hipGetLastError());
         return FQL_E_HIP;
     }

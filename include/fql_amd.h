@@ -123,7 +123,9 @@ int fql_set_param(fql_handle h, const char* leaf, const float* host_in, size_t n
 /* which: 0 = Adam mu, 1 = Adam nu (optax ScaleByAdamState; utils/flax_utils.py:120-130) */
 int fql_get_opt_state(fql_handle h, int which, const char* leaf, float* host_out, size_t n);
 int fql_set_opt_state(fql_handle h, int which, const char* leaf, const float* host_in, size_t n);
-/* optax count (0 at create) and TrainState.step (1 at create, utils/flax_utils.py:81) */
+/* optax count (0 at create) and TrainState.step (1 at create, utils/flax_utils.py:81).  fql_set_step also positions the device RNG at
+ * the adam_count-th update (the RNG's step counter advances with adam_count), so an agent restored from a checkpoint continues the
+ * saved agent's draws (the reference keeps its rng key in the checkpoint). */
 int fql_get_step(fql_handle h, int64_t* adam_count, int64_t* train_step);
 int fql_set_step(fql_handle h, int64_t adam_count, int64_t train_step);
 
@@ -281,7 +283,8 @@ int fql_group_destroy(fql_group g);
 /* fql_update_from_dataset of every member in one fused update: member i samples its rows from ITS OWN uploaded dataset, idx + i * B
  * ([k][B] int64, device or host) or NULL = each member's device RNG; the noise always comes from each member's device RNG.
  * info13xk: [k][13] (device or host; host = synchronous) or NULL.  `stream` as elsewhere: NULL = the group's own stream.
- * Ordering: (1) the update is ordered after all work submitted earlier through any member: a member's queued engine-queue updates are
+ * Ordering: (0) the update is ordered after the group's previous update, also where that one ran on another stream.
+ * (1) the update is ordered after all work submitted earlier through any member: a member's queued engine-queue updates are
  * drained and the group's stream waits for the member's stream (work the caller enqueued on streams of its own is the caller's to order).
  * (2) every member entry point called afterwards sees this update's results without an explicit synchronise (fql_get_param /
  * fql_set_param included): it waits for the group's update first (fql_info_enqueue: a stream dependency, no host wait). */

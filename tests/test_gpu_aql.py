@@ -8,7 +8,7 @@ import numpy as np
 import pytest
 
 from oracle import fql_oracle as O
-from tests.util import make_problem, randomize_params, leaf_dict
+from tests.util import assert_same_state as _assert_same_state, make_problem, randomize_params
 
 pytestmark = pytest.mark.gpu
 
@@ -23,18 +23,6 @@ def _pair(B=64, H=128, seed=11):
         a.upload_dataset(ds)
         agents.append(a)
     return cfg, ds, batch, agents
-
-
-def _assert_same_state(a, b):
-    pa, pb = leaf_dict(a.get_params()), leaf_dict(b.get_params())
-    for k in pa:
-        np.testing.assert_array_equal(pa[k], pb[k], err_msg=k)
-    oa, ob = a.get_opt_state(), b.get_opt_state()
-    assert oa['count'] == ob['count'] and oa['step'] == ob['step']
-    for part in ('mu', 'nu'):
-        la, lb = leaf_dict(oa[part]), leaf_dict(ob[part])
-        for k in la:
-            np.testing.assert_array_equal(la[k], lb[k], err_msg=f'{part} {k}')
 
 
 def test_aql_update_equals_graph_update_bitwise():

@@ -25,11 +25,15 @@ def _assert_same_state(a, b, what=''):
     assert a.read_info() == b.read_info(), what
 
 
-def _setup(K, B, H, seeds=None, alphas=None):
+def _setup(K, B, hidden, seeds=None, alphas=None, od=29, ad=8, scale=0.1, **kw):
+    """A group of K members and their standalone twins on one problem: `hidden` is the four equal widths' H or the tuple of widths, `kw`
+    are config overrides.  Members and twins differ in seed and alpha only (alphas: the config's alpha times 1, 2, ..) and start from the
+    same randomised parameters."""
     import fql_amd
+    hidden = (hidden,) * 4 if isinstance(hidden, int) else tuple(hidden)
     seeds = list(range(K)) if seeds is None else seeds
-    alphas = [10.0 * (i + 1) for i in range(K)] if alphas is None else alphas
-    cfg, ds, batch, noise = make_problem(29, 8, B, (H,) * 4, seed=7)
+    alphas = [kw.get('alpha', 10.0) * (i + 1) for i in range(K)] if alphas is None else alphas
+    cfg, ds, batch, noise = make_problem(od, ad, B, hidden, seed=7, **kw)
     ex_o, ex_a = batch['observations'][:1], batch['actions'][:1]
     group = fql_amd.FQLAgentGroup.create(seeds, ex_o, ex_a, cfg, alphas=alphas)
     group.upload_dataset(ds)
@@ -38,7 +42,7 @@ def _setup(K, B, H, seeds=None, alphas=None):
         c = dict(cfg)
         c['alpha'] = a
         t = fql_amd.FQLAgent.create(s, ex_o, ex_a, c)
-        p = randomize_params(t.get_params(), 100 + i)
+        p = randomize_params(t.get_params(), 100 + i, scale=scale)
         t.set_params(p)
         group.members[i].set_params(p)
         t.upload_dataset(ds)
@@ -58,6 +62,115 @@ def test_group_equals_standalone_twins_device_rng(K, B, H, n):
     group.synchronize()
     for i, (m, t) in enumerate(zip(group.members, twins)):
         _assert_same_state(m, t, f'member {i}')
+    group.close()
+
+
+# The shapes at which the fused program is built differently (fql_group_s::zip / fuse, fql_amd/csrc/fql_engine.hip).  Each is pinned to the
+# fp64 restatement for a single agent (test_gpu_parity.py, test_gpu_shapes.py, test_gpu_hardening.py; k8 is a shape of the cases above),
+# so the twin is a checked reference.
+PATHS = [
+    # od, ad, B, hidden, cfg overrides, K, n
+    pytest.param(40, 4, 1024, (512,) * 4, dict(alpha=300.0), 2, 3, id='b1024_big_tiles'),   # fql_side_big_kernel's four rebased sub-tables, chain<512> at M 1024
+    pytest.param(29, 15, 64, (256,) * 4, {}, 2, 5, id='act15_chain'),                        # chain<256>, its 16-column block full
+    pytest.param(29, 16, 64, (512,) * 4, {}, 2, 5, id='act16_generic'),                      # generic Euler kernels, fql_dgrad0_multi_kernel at 16 columns
+    pytest.param(69, 21, 64, (512,) * 4, dict(alpha=30.0, discount=0.995), 3, 4, id='humanoidmaze'),   # no chain, generic dgrads, ap = 32
+    pytest.param(45, 24, 48, (80, 48, 64), dict(q_agg='min'), 3, 5, id='ragged_min'),        # ragged widths, 3 layers
+    pytest.param(29, 8, 64, (512,) * 4, dict(actor_layer_norm=True), 2, 5, id='actor_ln'),   # H 512 without chain or OP_WFRAG, unfused Euler finish
+    pytest.param(40, 4, 48, (64, 64), dict(actor_layer_norm=True, flow_steps=3), 2, 5, id='two_layer_fs3'),   # 2 layers, short Euler loop
+    pytest.param(11, 5, 32, (64,) * 4, dict(normalize_q_loss=True), 2, 5, id='norm_q'),      # the loss / finalize tasks' other branch
+    pytest.param(17, 6, 16, (32,) * 4, dict(layer_norm=False), 4, 5, id='no_ln_b16'),        # empty LayerNorm-backward sub-table, minimum batch
+    pytest.param(29, 8, 64, (256,) * 4, {}, 8, 5, id='k8'),                                  # eight members per table, blockIdx.y up to 7
+    pytest.param(29, 8, 32, (1024,) * 3, {}, 2, 3, id='wide1024'),                           # fused tables through the K > 512 kernels
+]
+
+
+@pytest.mark.parametrize('od, ad, B, hidden, kw, K, n', PATHS)
+def test_group_equals_standalone_twins_on_every_path(od, ad, B, hidden, kw, K, n):
+    cfg, ds, batch, noise, group, twins = _setup(K, B, hidden, od=od, ad=ad, scale=0.05 if max(hidden) >= 512 else 0.1, **kw)
+    for _ in range(n):
+        group.update_from_dataset()
+        for t in twins:
+            t.update_from_dataset(B)
+    group.synchronize()
+    for i, (m, t) in enumerate(zip(group.members, twins)):
+        _assert_same_state(m, t, f'member {i}')
+    group.close()
+
+
+def _info_row(agent):
+    from fql_amd import INFO_KEYS
+    info = agent.read_info()
+    return [info[k] for k in INFO_KEYS]
+
+
+def test_group_infos_through_the_c_abi():
+    """fql_group_update_from_dataset's info13xk: a host buffer (synchronous) and a device buffer (read after the group's synchronize) hold
+    every member's 13 infos in the wrapper's key order."""
+    import torch
+    K, B = 3, 64
+    cfg, ds, batch, noise, group, twins = _setup(K, B, 128)
+    lib = group._lib
+    for step in range(4):
+        if step % 2 == 0:
+            host = np.full((K, 13), np.nan, np.float32)
+            group._check(lib.fql_group_update_from_dataset(group._g, None, B, host.ctypes.data, None))
+            got = host
+        else:
+            dev = torch.full((K, 13), float('nan'), dtype=torch.float32, device='cuda')
+            torch.cuda.synchronize()                     # the fill ran on torch's stream, the update runs on the group's own
+            group._check(lib.fql_group_update_from_dataset(group._g, None, B, dev.data_ptr(), None))
+            group.synchronize()
+            got = dev.cpu().numpy()
+        for i, (m, t) in enumerate(zip(group.members, twins)):
+            t.update_from_dataset(B)
+            assert got[i].tolist() == _info_row(m), (step, i)
+            assert got[i].tolist() == _info_row(t), (step, i)
+    for i, (m, t) in enumerate(zip(group.members, twins)):
+        _assert_same_state(m, t, f'member {i}')
+    group.close()
+
+
+def test_group_device_rows_on_the_callers_stream():
+    """Row indices as a CUDA tensor: the update runs on torch's current stream, here its default stream, which reaches the engine as
+    FQL_STREAM_LEGACY.  Alternating with host rows (the group's own stream) with no synchronize in between: each update is ordered behind
+    the one before it on the other stream, and the lazily read infos of either kind are the twins'."""
+    import torch
+    K, B = 2, 64
+    cfg, ds, batch, noise, group, twins = _setup(K, B, 128)
+    assert torch.cuda.current_stream().cuda_stream == 0
+    rng = np.random.default_rng(13)
+    for step in range(6):
+        idxs = rng.integers(0, len(ds['observations']), size=(K, B))
+        lazy = step >= 4      # (the first four updates take no infos: nothing but the group's own ordering is between them)
+        infos = group.update_from_dataset(idxs=torch.from_numpy(idxs).cuda() if step % 2 == 0 else idxs, want_info=lazy)
+        want = [t.update_from_dataset(B, idxs=idxs[i], want_info=lazy)[1] for i, t in enumerate(twins)]
+        for i in range(K if lazy else 0):
+            assert infos[i].to_dict() == want[i].to_dict(), (step, i)
+    group.synchronize()
+    for i, (m, t) in enumerate(zip(group.members, twins)):
+        _assert_same_state(m, t, f'member {i}')
+    group.close()
+
+
+def test_group_member_updates_between_group_updates():
+    """A member's own updates between group updates, on the engine's queues and from a host batch, with no synchronize anywhere: the group
+    update is ordered behind them, and they behind it."""
+    K, B = 3, 64
+    cfg, ds, batch, noise, group, twins = _setup(K, B, 128)
+
+    def sequence(update_all, agents):
+        for _ in range(3):
+            update_all()
+            agents[0].update_from_dataset(B)               # stream left to the engine: its own queues
+            agents[1].update(batch, noise=noise)           # host batch, explicit noise
+            update_all()
+
+    sequence(group.update_from_dataset, group.members)
+    sequence(lambda: [t.update_from_dataset(B) for t in twins], twins)
+    group.synchronize()
+    for i, (m, t) in enumerate(zip(group.members, twins)):
+        _assert_same_state(m, t, f'member {i}')
+    assert group.members[0].get_opt_state()['count'] == 9 and group.members[2].get_opt_state()['count'] == 6
     group.close()
 
 
@@ -133,8 +246,10 @@ def test_group_member_checkpoint_hand_off(tmp_path):
         m.update_from_dataset(B, idxs=idx, noise=nz)
         r.update_from_dataset(B, idxs=idx, noise=nz)
     _assert_same_state(m, r, 'restored')
+    r.update_from_dataset(B)         # the restored twin takes the next update alone
     group.update_from_dataset()      # the member goes back to group updates after standalone ones
     group.synchronize()
+    _assert_same_state(m, r, 'restored, after a group update')
     group.close()
 
 

@@ -7,12 +7,15 @@ The switches these cases sit on either side of (fql_amd/csrc/fql_engine.hip):
   * the critic's input gradient: the lean 16-column OP_DGRAD0 when K % 512 == 0, obs_dim + 16 <= in_p and act_dim <= 16.  At act_dim 21
     the generic first-layer dgrad runs, and the padded action block is 32 wide.
   * sample_actions / compute_flow_actions run in chunks of 4096 rows; a seeded draw keys each chunk by its first row.
+  * a contraction longer than 512 (hidden widths up to 1024, inputs wider than 512): the 16-row GEMM launches switch to
+    fql_gemm16_kernel<true> / fql_gemm16_euler_kernel<true>, whose K > 512 tasks hold sixteen B fragments per wave, and ask for
+    16 (K + 4) + 2304 floats of dynamic LDS (about 75 KB at K 1024, the largest request of any launch).
 """
 import numpy as np
 import pytest
 
 from oracle import fql_oracle as O
-from tests.util import (assert_step_matches, assert_total_loss_matches, assert_trajectory_tracks_oracle, make_problem,
+from tests.util import (assert_same_state, assert_step_matches, assert_total_loss_matches, assert_trajectory_tracks_oracle, make_problem,
                         randomize_params)
 
 pytestmark = pytest.mark.gpu
@@ -24,6 +27,8 @@ CASES = [
     pytest.param(69, 21, 256, (512,) * 4, dict(alpha=30.0, discount=0.995), id='humanoidmaze'),   # generic paths, ap = 32
     pytest.param(39, 30, 64, (256,) * 4, {}, id='relocate'),                         # 2 padding columns in ap = 32
     pytest.param(45, 24, 48, (80, 48, 64), dict(q_agg='min'), id='ragged_wide'),   # ragged widths with a wide action
+    pytest.param(29, 8, 32, (1024,) * 3, {}, id='wide1024'),                        # every hidden contraction at K 1024, no chain
+    pytest.param(600, 4, 16, (64, 64, 64), {}, id='obs600'),                        # K <= 128, <= 512 and > 512 tasks in one launch
 ]
 
 
@@ -69,3 +74,31 @@ def test_sample_and_flow_actions_across_the_row_chunk(od, ad, B, hidden, kw):
 
 def test_humanoidmaze_shape_trajectory_tracks_oracle():
     assert_trajectory_tracks_oracle(69, 21, 256, (512,) * 4, seed=23, alpha=30.0, discount=0.995)
+
+
+def test_wide1024_aql_update_equals_graph_update_bitwise():
+    """The K > 512 launches and their > 64 KB LDS request in both dispatch forms: the engine's own queues against the captured graph on a
+    caller's stream, three updates from the same rows and noise."""
+    import torch
+    import fql_amd
+    od, ad, B, hidden = 29, 8, 32, (1024,) * 3
+    cfg, ds, batch, noise = make_problem(od, ad, B, hidden, seed=3)
+    agents = []
+    for _ in range(2):
+        a = fql_amd.FQLAgent.create(0, batch['observations'][:1], batch['actions'][:1], cfg)
+        a.set_params(randomize_params(a.get_params(), seed=5, scale=0.05))
+        a.upload_dataset(ds)
+        agents.append(a)
+    a, b = agents
+    st = torch.cuda.Stream()
+    rng = np.random.default_rng(5)
+    for step in range(3):
+        idxs = rng.integers(0, len(ds['observations']), size=B)
+        nz = O.make_noise(B, ad, 40 + step)
+        a.update_from_dataset(B, idxs=idxs, noise=nz)                          # stream left to the engine -> its own queues
+        b.update_from_dataset(B, idxs=idxs, noise=nz, stream=st.cuda_stream)    # a caller's stream -> the captured graph
+        assert a.synchronize() == 'aql'
+        assert b.synchronize() == 'graph'
+        st.synchronize()
+        assert a.read_info() == b.read_info()
+    assert_same_state(a, b)

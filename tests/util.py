@@ -36,6 +36,19 @@ def leaf_dict(tree):
     return dict(O.tree_leaves_with_path(tree))
 
 
+def assert_same_state(a, b):
+    """Two agents bitwise in the same state: every parameter leaf, the optimizer counters and both Adam moments."""
+    pa, pb = leaf_dict(a.get_params()), leaf_dict(b.get_params())
+    for k in pa:
+        np.testing.assert_array_equal(pa[k], pb[k], err_msg=k)
+    oa, ob = a.get_opt_state(), b.get_opt_state()
+    assert oa['count'] == ob['count'] and oa['step'] == ob['step']
+    for part in ('mu', 'nu'):
+        la, lb = leaf_dict(oa[part]), leaf_dict(ob[part])
+        for k in la:
+            np.testing.assert_array_equal(la[k], lb[k], err_msg=f'{part} {k}')
+
+
 def assert_info_close(got, want, rtol=2e-5, atol=2e-6, keys=None):
     for k in (keys or O.INFO_KEYS):
         g, w = float(got[k]), float(want[k])
