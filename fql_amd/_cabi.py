@@ -21,6 +21,7 @@ FQL_SAC_NUM_INFO = 14
 FQL_BC_NUM_INFO = 4
 FQL_IQL_AWR_NUM_INFO = 16
 FQL_IQL_DDPGBC_NUM_INFO = 19
+FQL_IQLD_NUM_INFO = 21
 FQL_OK, FQL_E_INVALID, FQL_E_NODEVICE, FQL_E_HIP, FQL_E_STATE, FQL_E_NOTFOUND = 0, -1, -2, -3, -4, -5
 
 
@@ -55,6 +56,12 @@ class FqlSacConfig(C.Structure):
 class FqlIqlConfig(C.Structure):
     _fields_ = [('expectile', C.c_float), ('alpha', C.c_float), ('actor_loss', C.c_int32), ('const_std', C.c_int32),
                 ('reserved', C.c_int32 * 8)]
+
+
+class FqlIqldConfig(C.Structure):
+    _fields_ = [('actor_lr', C.c_float), ('value_lr', C.c_float), ('critic_lr', C.c_float), ('expectile', C.c_float),
+                ('awr_temperature', C.c_float), ('softmax_beta', C.c_float), ('optimal_var', C.c_int32), ('target_extraction', C.c_int32),
+                ('denoise_steps', C.c_int32), ('opt_decay_schedule', C.c_int32), ('reserved', C.c_int32 * 6)]
 
 
 class FqlBcConfig(C.Structure):
@@ -155,6 +162,16 @@ SYMBOLS = {
     'fql_iql_total_loss': (_I, [_VP] + _BATCH + [C.POINTER(FqlNoise), C.POINTER(_F), C.POINTER(_F), _VP]),
     'fql_iql_sample_actions': (_I, [_VP, _VP, _I, _VP, _U64, _F, _VP, _VP]),
     'fql_iql_stats': (_I, [_VP, C.POINTER(_I64), C.POINTER(_I64)]),
+    'fql_iqld_default_config': (None, [C.POINTER(FqlIqldConfig)]),
+    'fql_iqld_create': (_I, [C.POINTER(FqlConfig), C.POINTER(FqlIqldConfig), _U64, C.POINTER(_VP)]),
+    'fql_iqld_update': (_I, [_VP] + _BATCH + [C.POINTER(FqlNoise), _I, _I, _VP, _VP]),
+    'fql_iqld_update_from_dataset': (_I, [_VP, _VP, _I, _I64, _I64, C.POINTER(FqlNoise), _I, _I, _VP, _VP]),
+    'fql_iqld_total_loss': (_I, [_VP] + _BATCH + [C.POINTER(FqlNoise), C.POINTER(_F), C.POINTER(_F), _VP]),
+    'fql_iqld_sample_actions': (_I, [_VP, _VP, _I, _VP, _U64, _F, _VP, _VP]),
+    'fql_iqld_read_rows': (_I, [_VP, _I, _VP, _I]),
+    'fql_iqld_get_steps': (_I, [_VP, C.POINTER(_I64)]),
+    'fql_iqld_set_steps': (_I, [_VP, C.POINTER(_I64)]),
+    'fql_iqld_stats': (_I, [_VP, _I, _I, C.POINTER(_I64), C.POINTER(_I64), C.POINTER(_I64)]),
     'fql_read_info_n': (_I, [_VP, _VP, _I]),
     'fql_info_wait_n': (_I, [_VP, _U64, _VP, _I]),
 }

@@ -12,6 +12,11 @@ FQLAgent (agents/fql.py:18-20, utils/flax_utils.py:53-88) that state dict is
 (optax.adam = chain(scale_by_adam, scale): a 2-tuple of states, tuples serialise with string indices).
 BCAgent (agents/bc.py) holds a bare TrainState named ``policy``: ``{'rng', 'policy': {'step', 'params': {'Dense_0': ..,
 'MLP_0': ..}, 'opt_state': ..}}``; the agent class names its TrainState key (``_train_state_key``).
+IQLDiffusionAgent (agents/iql_diffusion.py:87-91) holds FOUR bare TrainStates as fields: ``{'rng', 'critic', 'target_critic', 'value',
+'actor'}``, each ``{'step', 'params', 'opt_state'}`` with its own Adam count; the target critic was created without an optimizer
+(``opt_state`` None, ``step`` 1).  Such an agent lists its fields in ``_train_states``.  The engine's noise is a function of the seed and of
+the number of updates so far, which the per-net counts do not determine (a step kind may skip either net): ``rng`` carries four words
+there, the seed's two and the update counter's two.
 This module writes and reads exactly that nesting with numpy leaves.  SURVEY.md 8f N2.
 
 **Parity unpinned**: no checkpoint written by the JAX reference exists in this environment (jax/flax are absent
@@ -116,6 +121,16 @@ def to_state_dict(agent, visual_layout: str = 'nested') -> dict:
     modules_actor_bc_flow_encoder (no nested copy) - the layout flax is likely to produce, since ModuleDict adopts the shared encoder
     instance first (agents/fql.py:230-232); use it to export to the JAX reference (unverified: no reference checkpoint exists here)."""
     opt = agent.get_opt_state()
+    fields = getattr(agent, '_train_states', None)
+    if fields:   # bare TrainStates as fields of the agent (agents/iql_diffusion.py)
+        params = agent.get_params()
+        n = opt['updates']
+        out = {'rng': np.asarray([(agent._seed >> 32) & 0xFFFFFFFF, agent._seed & 0xFFFFFFFF, (n >> 32) & 0xFFFFFFFF, n & 0xFFFFFFFF],
+                                 dtype=np.uint32)}
+        for f, trained, count in fields_of(agent, opt):
+            out[f] = {'step': np.int64(count + 1 if trained else 1), 'params': params[f],
+                      'opt_state': ({'0': {'count': np.int32(count), 'mu': opt['mu'][f], 'nu': opt['nu'][f]}, '1': {}} if trained else None)}
+        return out
     rng = np.asarray(getattr(agent, 'rng', [(agent._seed >> 32) & 0xFFFFFFFF, agent._seed & 0xFFFFFFFF]), dtype=np.uint32)
     trees = [agent.get_params(), opt['mu'], opt['nu']]
     if visual_layout in ('toplevel', 'toplevel-only'):
@@ -134,6 +149,12 @@ def to_state_dict(agent, visual_layout: str = 'nested') -> dict:
             'opt_state': {'0': {'count': np.int32(opt['count']), 'mu': trees[1], 'nu': trees[2]}, '1': {}},
         },
     }
+
+
+def fields_of(agent, opt):
+    """(field, trained, Adam count) of an agent whose TrainStates are bare fields: the actor counts by itself, the critic and the value net
+    step together, the target critic has no optimizer."""
+    return [(f, f != 'target_critic', opt['actor_count'] if f == 'actor' else opt['count']) for f in agent._train_states]
 
 
 def _flatten(tree, prefix=''):
@@ -174,6 +195,9 @@ def from_state_dict(agent, state: dict, strict: bool = True) -> dict:
     Returns a report: {'visual_layout': 'state'|'nested'|'toplevel'|'both-shared'|'both-distinct', 'dropped': [...],
     'missing': [...], 'unexpected': [...]}.  With strict=True missing / unexpected leaves raise KeyError naming them."""
     report: Dict[str, Any] = {'dropped': [], 'missing': [], 'unexpected': []}
+    fields = getattr(agent, '_train_states', None)
+    if fields:
+        return _from_field_states(agent, state, fields, strict, report)
     net = state[getattr(agent, '_train_state_key', 'network')]
     want = {p for p, _ in agent.leaves()}
 
@@ -207,6 +231,35 @@ def from_state_dict(agent, state: dict, strict: bool = True) -> dict:
         if r.size >= 2:
             agent.rng = r[:2].astype(np.uint32)
             agent._seed = int((int(r[0]) << 32) | int(r[1]))
+    return report
+
+
+def _from_field_states(agent, state, fields, strict, report):
+    """from_state_dict for an agent whose TrainStates are bare fields (IQLDiffusionAgent)."""
+    want = {p for p, _ in agent.leaves()}
+    params = {f: _np_tree(state[f]['params']) for f in fields}
+    have = {p for p, _ in _flatten(params)}
+    report['missing'], report['unexpected'] = sorted(want - have), sorted(have - want)
+    report['visual_layout'] = 'state'
+    if strict and (report['missing'] or report['unexpected']):
+        raise KeyError(f"checkpoint params: missing leaves {report['missing'][:8]}, unexpected leaves {report['unexpected'][:8]}")
+    agent.set_params(params)
+    zeros = lambda t: {k: zeros(v) if isinstance(v, dict) else np.zeros_like(v) for k, v in t.items()}   # noqa: E731
+    mu, nu, counts = {}, {}, {}
+    for f in fields:
+        adam = (state[f].get('opt_state') or {}).get('0')
+        mu[f] = _np_tree(adam['mu']) if adam else zeros(params[f])
+        nu[f] = _np_tree(adam['nu']) if adam else zeros(params[f])
+        counts[f] = int(np.asarray(adam['count'])) if adam else 0
+    if counts.get('critic', 0) != counts.get('value', 0):
+        raise ValueError(f"checkpoint: the critic's Adam count ({counts.get('critic')}) and the value net's ({counts.get('value')}) differ; "
+                         'the engine steps them together')
+    r = np.asarray(state['rng']).astype(np.uint64).reshape(-1) if state.get('rng') is not None else np.zeros(0, np.uint64)
+    updates = int((int(r[2]) << 32) | int(r[3])) if r.size >= 4 else max(counts.values())
+    agent.set_opt_state({'mu': mu, 'nu': nu, 'count': counts.get('critic', 0), 'actor_count': counts.get('actor', 0), 'updates': updates})
+    if r.size >= 2:
+        agent.rng = r[:2].astype(np.uint32)
+        agent._seed = int((int(r[0]) << 32) | int(r[1]))
     return report
 
 

@@ -19,6 +19,7 @@
 #include "fql_sac.h"
 #include "fql_bc.h"
 #include "fql_iql.h"
+#include "fql_iqld.h"
 #include <hip/hip_ext.h>
 #include "fql_aql.h"
 
@@ -139,7 +140,10 @@ enum OpType { OP_GEMM, OP_GEMM64, OP_WGRAD, OP_LNBWD, OP_PREP, OP_POSTOS, OP_EUL
               // BC (agents/bc.py) only: after SAC's
               OP_BC_PREP, OP_BC_FIN, OP_BC_STEPBIAS, OP_BC_LAYER0,
               // IQL (agents/iql.py) only: after BC's
-              OP_IQL_PREP, OP_IQL_HEAD, OP_IQL_LOSS_AWR, OP_IQL_LOSS_DDPGBC, OP_IQL_AGRAD, OP_IQL_FIN, OP_NUM_TYPES };
+              OP_IQL_PREP, OP_IQL_HEAD, OP_IQL_LOSS_AWR, OP_IQL_LOSS_DDPGBC, OP_IQL_AGRAD, OP_IQL_FIN,
+              // IQL-diffusion (agents/iql_diffusion.py) only: after IQL's
+              OP_IQLD_PREP, OP_IQLD_LOSS_C, OP_IQLD_WEIGHT, OP_IQLD_LOSS_A, OP_IQLD_EGRAD, OP_IQLD_FIN, OP_IQLD_STEPBIAS, OP_IQLD_LAYER0,
+              OP_IQLD_CFG, OP_NUM_TYPES };
 
 struct Op {
     OpType type;
@@ -181,6 +185,15 @@ struct Op {
     IqlAwrArgs qawr;
     IqlDdpgArgs qddpg;
     IqlActorGradArgs qag;
+    IqldPrepArgs dprep;
+    IqldCriticArgs dc;
+    IqldWeightArgs dw;
+    IqldActorLossArgs dla;
+    IqldEmbedGradArgs deg;
+    IqldFinalizeArgs dfin;
+    IqldStepBiasArgs dsb;
+    IqldLayer0Args dl0;
+    IqldCfgStepArgs dstep;
     ChainArgs chain;
     const ConvWprepTask* wprep_tasks = nullptr;
     int wprep_n = 0;
@@ -188,6 +201,8 @@ struct Op {
     int adam_c0 = 0, adam_n = -1;  // chunk range of an Adam op (-1: all chunks)
     int adam_c1 = 0, adam_n1 = 0;  // second chunk range of the same launch (two modules merged), adam_n1 = 0: none
     int adam_polyak = -1;          // Polyak range of an Adam op in floats from offset 0 (-1: critic_size; 0: no Polyak step)
+    float adam_lr = 0.f;           // > 0: this launch's learning rate (IQL-diffusion: one per TrainState), else fql_config.lr
+    DevState* adam_st = nullptr;   // the counters this launch's bias correction reads (IQL-diffusion's actor), null: the handle's
     int fin_mode = 0;
     int level = 0;
     int lane = 0;            // 0 = critical lane (Euler chain, one-step backward), 1 = side lane
@@ -326,8 +341,8 @@ struct EncBuf {
 // ------------------------------------------------------------------------------------------------
 // agent kinds: what a handle is, and what the engine says about it
 // ------------------------------------------------------------------------------------------------
-enum class AgentKind { FQL, IFQL, REBRAC, SAC, BC, IQL };
-constexpr int kNumKinds = 6;
+enum class AgentKind { FQL, IFQL, REBRAC, SAC, BC, IQL, IQLD };
+constexpr int kNumKinds = 7;
 
 const char* const k_info_names[FQL_NUM_INFO] = {
     "critic/critic_loss", "critic/q_mean", "critic/q_max", "critic/q_min", "actor/actor_loss",
@@ -349,6 +364,10 @@ const char* const k_iql_info_names[2][FQL_IQL_DDPGBC_NUM_INFO] = {
     {"value/value_loss", "value/v_mean", "value/v_max", "value/v_min", "critic/critic_loss", "critic/q_mean", "critic/q_max", "critic/q_min",
      "actor/actor_loss", "actor/q_loss", "actor/bc_loss", "actor/q_mean", "actor/q_abs_mean", "actor/bc_log_prob", "actor/mse", "actor/std",
      "grad/max", "grad/min", "grad/norm"}};
+const char* const k_iqld_info_names[FQL_IQLD_NUM_INFO] = {
+    "critic_loss", "q", "value_loss", "v", "v_min", "v_max", "actor_q", "actor_loss", "actor_positive_ratio", "actor_loss_positive",
+    "actor_loss_uncond", "o_mean", "o_std", "o_min", "o_max", "effective_batch_size", "loss_weights_top_10_mass", "loss_weights_max",
+    "grad/max", "grad/min", "grad/norm"};
 
 enum { NZ_EPS1 = 1, NZ_X0 = 2, NZ_T = 4, NZ_Z = 8, NZ_EPS2 = 16 };   // the fields of fql_noise
 // One row per kind, indexed by AgentKind.  A new agent adds a row here and a column to k_admission (C ABI, below).
@@ -373,6 +392,8 @@ const KindDesc k_kinds[kNumKinds] = {
      "BC reads only x0 and t of fql_noise (eps1, z and eps2 must be NULL)"},
     {"IQL", "an IQL handle", "fql_iql_create", nullptr, 0, NZ_EPS1,
      "IQL reads only eps1 of fql_noise (x0, t, z and eps2 must be NULL)"},
+    {"IQL-diffusion", "an IQL-diffusion handle", "fql_iqld_create", k_iqld_info_names, FQL_IQLD_NUM_INFO, NZ_X0 | NZ_T,
+     "IQL-diffusion reads only x0 and t of fql_noise (eps1, z and eps2 must be NULL)"},
 };
 
 }  // namespace
@@ -382,7 +403,7 @@ struct fql_engine {
     fql_config cfg{};
     AgentKind kind = AgentKind::FQL;
     const KindDesc& desc() const { return k_kinds[(int)kind]; }
-    bool has_value_net() const { return kind == AgentKind::IFQL || kind == AgentKind::IQL; }      // NET_OS holds V(obs)
+    bool has_value_net() const { return kind == AgentKind::IFQL || kind == AgentKind::IQL || kind == AgentKind::IQLD; }      // NET_OS holds V(obs)
     bool actor_on_obs() const { return kind == AgentKind::REBRAC || kind == AgentKind::SAC || kind == AgentKind::IQL; }   // NET_BC is actor(obs), no flow
     int num_info() const {
         if (kind == AgentKind::IQL) return qcfg.actor_loss == 1 ? FQL_IQL_DDPGBC_NUM_INFO : FQL_IQL_AWR_NUM_INFO;
@@ -424,6 +445,19 @@ struct fql_engine {
     size_t ls_off = 0;
     float *se_buf = nullptr, *ls_part = nullptr;   // [B]: squared error per row; [B, ap]: per-row terms of the log_stds gradient
     float* iql_info = nullptr;
+    // IQL-diffusion agent (agents/iql_diffusion.py, binary optimality family; fql_iqld_create): critic pair, target pair and value net as
+    // IQL's; NET_BC is the DiffusionPolicy on [obs | x_t | emb(t) | Embed[is_positive]] (BC's policy with 32 more input columns) and
+    // Embed_0/embedding ([2, 32]) follows the value net at emb_off.  p_bc runs over 2B rows (positive half, unconditional half).  Four
+    // programs on one handle: prog_full (both), prog_critic (critic and value only), prog_actor (actor only), prog_none (neither: the RNG
+    // step alone).  The critic and the value TrainState count in d_state, the actor's in d_state_a.  The 21 infos live in iql_info ([0, 32)
+    // of the last update, [32, 64) of the last loss probe), the three per-row arrays in rows_buf ([2][3][B], the same halves).
+    fql_iqld_config dcfg{};
+    size_t emb_off = 0;
+    DevState* d_state_a = nullptr;
+    float *w_lw = nullptr, *rows_buf = nullptr;   // [B] loss weights; [2][3][B]
+    Program prog_actor, prog_none;
+    float sample_cfg = 1.0f;                      // cfg of the sampling call in flight (read when its step launches are issued)
+    bool own_info() const { return kind == AgentKind::IQL || kind == AgentKind::IQLD; }
     uint64_t seed = 0;
     int device = 0;
     hipStream_t stream = nullptr;
@@ -605,6 +639,7 @@ struct fql_engine {
             case AgentKind::SAC: nets[NET_BC] = actor(od, 2 * pad16(ad)); break;                             // actor_net + [mean_net | log_std_net]
             case AgentKind::BC: nets[NET_BC] = actor(od + ad + BC_EMB, ad); break;                           // policy(obs, x_t, emb(t)) (agents/bc.py:26-44)
             case AgentKind::IQL: nets[NET_BC] = actor(od, ad); nets[NET_OS] = value(od); break;
+            case AgentKind::IQLD: nets[NET_BC] = actor(od + ad + BC_EMB + IQLD_EMBED, ad); nets[NET_OS] = value(od); break;   // iql_diffusion.py:54-67
         }
         nets[NET_C1] = nets[NET_T0] = nets[NET_T1] = nets[NET_C0];
         size_t off = 0;
@@ -657,6 +692,7 @@ struct fql_engine {
                 place_enc(ENC_OS);
                 if (kind == AgentKind::SAC) { alpha_off = off; off += 4; }   // modules_alpha/log_value: one float, padded to an Adam quad
                 if (kind == AgentKind::IQL && !qcfg.const_std) { ls_off = off; off += pad16(ad); }   // modules_actor/log_stds: [act], padded to ap
+                if (kind == AgentKind::IQLD) { emb_off = off; off += 2 * IQLD_EMBED; }               // actor/Embed_0/embedding: [2, 32]
                 n_train = off;
             }
             if (ni == NET_T1) place_enc(ENC_T);
@@ -769,21 +805,28 @@ struct fql_engine {
                                  {"modules_critic", "value_net", NET_C0, NET_C1, true, ENC_C},
                                  {"modules_target_critic", "value_net", NET_T0, NET_T1, false, ENC_T},
                                  {"modules_value", "value_net", NET_OS, -1, true, ENC_OS}};
+        // IQL-diffusion (agents/iql_diffusion.py:87-91): four bare TrainStates, no ModuleDict; the actor's leaves are BC's plus the embedding
+        const Mod iqld_mods[3] = {{"critic", "value_net", NET_C0, NET_C1, true, ENC_C},
+                                  {"target_critic", "value_net", NET_T0, NET_T1, false, ENC_T},
+                                  {"value", "value_net", NET_OS, -1, true, ENC_OS}};
         const Mod* mods = nullptr;   // BC: no modules, the leaves of one bare net
+        int nmods = 4;
+        const char* bare = nullptr;  // prefix of the bare policy net's leaves (BC: none, IQL-diffusion: its `actor` field)
         switch (kind) {
             case AgentKind::FQL: mods = fql_mods; break;
             case AgentKind::IFQL: mods = ifql_mods; break;
             case AgentKind::REBRAC: mods = rebrac_mods; break;
             case AgentKind::SAC: mods = sac_mods; break;
-            case AgentKind::BC: break;
+            case AgentKind::BC: bare = ""; nmods = 0; break;
             case AgentKind::IQL: mods = iql_mods; break;
+            case AgentKind::IQLD: bare = "actor/"; mods = iqld_mods; nmods = 3; break;
         }
         int tid = 0;
-        if (!mods) {   // agents/bc.py:26-44: a bare TrainState: Dense_0 (the head), then MLP_0/Dense_i and MLP_0/LayerNorm_i (jax dict order)
+        if (bare) {   // agents/bc.py:26-44: a bare TrainState: Dense_0 (the head), then MLP_0/Dense_i and MLP_0/LayerNorm_i (jax dict order)
             const Net& n0 = nets[NET_BC];
             auto add = [&](const std::string& name, bool matrix, int rows, int cols, size_t o0, int rp, int cp) {
                 Leaf lf;
-                lf.name = name;
+                lf.name = bare + name;
                 int d = 0;
                 if (matrix) lf.shape[d++] = rows;
                 lf.shape[d++] = cols;
@@ -797,6 +840,7 @@ struct fql_engine {
             const Layer& hd = n0.layers.back();
             add("Dense_0/bias", false, 1, hd.out, hd.b, 1, hd.out_p);
             add("Dense_0/kernel", true, hd.in, hd.out, hd.w, hd.in_p, hd.out_p);
+            if (kind == AgentKind::IQLD) add("Embed_0/embedding", true, 2, IQLD_EMBED, emb_off, 2, IQLD_EMBED);   // nn.Embed(2, 32): sorts behind Dense_0
             for (int i = 0; i + 1 < n0.nl(); ++i) {
                 const Layer& a = n0.layers[i];
                 add("MLP_0/Dense_" + std::to_string(i) + "/bias", false, 1, a.out, a.b, 1, a.out_p);
@@ -809,7 +853,7 @@ struct fql_engine {
                 add("MLP_0/LayerNorm_" + std::to_string(i) + "/scale", false, 1, a.out, a.g, 1, a.out_p);
             }
         }
-        for (int mi = 0; mi < (mods ? 4 : 0); ++mi) {
+        for (int mi = 0; mi < (mods ? nmods : 0); ++mi) {
             const Mod& m = mods[mi];
             if (m.n0 < 0) {   // modules_alpha/log_value: shape ()
                 Leaf lf;
@@ -927,7 +971,8 @@ struct fql_engine {
                 {"modules_actor/", "modules_critic/", "modules_critic/"},   // (ReBRAC, two trained modules: the critic's range twice)
                 {"modules_actor/", "modules_alpha/", "modules_critic/"},
                 {nullptr, nullptr, nullptr},                                // (BC, one module: every chunk)
-                {"modules_actor/", "modules_value/", "modules_critic/"}};
+                {"modules_actor/", "modules_value/", "modules_critic/"},
+                {"actor/", "value/", "critic/"}};
             const char* const* mods = trained[(int)kind];
             for (int m = 0; m < 3; ++m) {
                 if (!mods[m]) { mod_chunk0[m] = 0; mod_chunkn[m] = n_chunks; continue; }
@@ -978,7 +1023,7 @@ struct fql_engine {
                 const double scale = !actor_head ? 1.0 : kind == AgentKind::REBRAC ? (double)rcfg.actor_fc_scale
                                      : kind == AgentKind::IQL ? 1e-2   // Actor.final_fc_init_scale (utils/networks.py:106)
                                                               : 1.0;
-                if (kind == AgentKind::BC && actor_head) {
+                if ((kind == AgentKind::BC || kind == AgentKind::IQLD) && actor_head) {
                     // BC's Dense_0 is a bare nn.Dense (agents/bc.py:43): flax's default lecun_normal = variance_scaling(1, fan_in,
                     // truncated_normal): N(0, 1) truncated to [-2, 2], scaled by sqrt(1 / fan_in) / 0.87962566103423978
                     const double sd = std::sqrt(1.0 / (double)L.in) / 0.87962566103423978;
@@ -1022,6 +1067,13 @@ struct fql_engine {
                 std::uniform_real_distribution<double> U(-lim, lim);
                 for (size_t i = 0; i < (size_t)D.in * D.out; ++i) h[D.w + i] = (float)U(gen);
             }
+        if (kind == AgentKind::IQLD) {
+            // nn.Embed's default init: variance_scaling(1.0, 'fan_in', 'normal', out_axis=0) on [2, 32].  With in_axis = -2 and out_axis = 0
+            // both name axis 0: in_size = out_size = 2, receptive field = 64 / (2 * 2) = 16, fan_in = 2 * 16 = 32 (the feature count);
+            // 'normal' is the untruncated N(0, 1 / fan_in)
+            std::normal_distribution<double> Nd(0.0, std::sqrt(1.0 / (double)IQLD_EMBED));
+            for (int i = 0; i < 2 * IQLD_EMBED; ++i) h[emb_off + i] = (float)Nd(gen);
+        }
         std::memcpy(h.data() + n_train, h.data(), critic_size * sizeof(float));
         HIP_CHECK(hipMemcpy(P, h.data(), n_total * sizeof(float), hipMemcpyHostToDevice));
     }
@@ -2216,7 +2268,8 @@ struct fql_engine {
                 FQL_LAUNCH(fql_head_dgrad_kernel, dim3((L.op.gemm.M / 16) * (L.op.gemm.N / 64)), dim3(FQL_THREADS), 0, s, L.op.gemm);
                 break;
             case OP_ADAM: {
-                AdamArgs a{P, G, Mu, Nu, P + n_train, d_chunks, d_state, d_partials, L.op.adam_c0, L.op.adam_polyak >= 0 ? L.op.adam_polyak : (int)critic_size, cfg.lr, cfg.tau, tl,
+                AdamArgs a{P, G, Mu, Nu, P + n_train, d_chunks, L.op.adam_st ? L.op.adam_st : d_state, d_partials, L.op.adam_c0,
+                           L.op.adam_polyak >= 0 ? L.op.adam_polyak : (int)critic_size, L.op.adam_lr > 0.f ? L.op.adam_lr : cfg.lr, cfg.tau, tl,
                            L.op.adam_n1 > 0 ? L.op.adam_n : -1, L.op.adam_c1};
                 FQL_LAUNCH(fql_adam_kernel, dim3(L.op.adam_n < 0 ? n_chunks : L.op.adam_n + L.op.adam_n1), dim3(FQL_THREADS), 0, s, a);
                 break;
@@ -2310,6 +2363,36 @@ struct fql_engine {
                                    IqlFinalizeArgs{FinalizeArgs{d_state, d_chunks, d_partials, d_leaf_range, n_chunks, n_train_leaves, L.op.fin_mode & 1, tl},
                                                    iql_info + ((L.op.fin_mode & 1) ? 0 : IQL_INFO_STRIDE), qcfg.actor_loss == 1 ? IQL_N_DDPGBC : IQL_N_AWR});
                 break;
+            case OP_IQLD_PREP:
+                FQL_LAUNCH(fql_iqld_prep_kernel, dim3((L.op.dprep.B + 3) / 4), dim3(FQL_THREADS), 0, s, L.op.dprep);
+                break;
+            case OP_IQLD_LOSS_C:
+                FQL_LAUNCH(fql_iqld_loss_critic_kernel, dim3(1), dim3(FQL_THREADS), 0, s, L.op.dc);
+                break;
+            case OP_IQLD_WEIGHT:
+                FQL_LAUNCH(fql_iqld_weight_kernel, dim3(1), dim3(FQL_THREADS), 0, s, L.op.dw);
+                break;
+            case OP_IQLD_LOSS_A:
+                FQL_LAUNCH(fql_iqld_loss_actor_kernel, dim3(1), dim3(FQL_THREADS), 0, s, L.op.dla);
+                break;
+            case OP_IQLD_EGRAD:
+                FQL_LAUNCH(fql_iqld_embed_grad_kernel, dim3(2), dim3(FQL_THREADS), 0, s, L.op.deg);
+                break;
+            case OP_IQLD_FIN:
+                FQL_LAUNCH(fql_iqld_finalize_kernel, dim3(1), dim3(FQL_THREADS), 0, s, L.op.dfin);
+                break;
+            case OP_IQLD_STEPBIAS:
+                FQL_LAUNCH(fql_iqld_stepbias_kernel, dim3((L.op.dsb.S * 2 * L.op.dsb.H + FQL_THREADS - 1) / FQL_THREADS), dim3(FQL_THREADS), 0, s, L.op.dsb);
+                break;
+            case OP_IQLD_LAYER0:
+                FQL_LAUNCH(fql_iqld_layer0_kernel, dim3((2 * L.op.dl0.n_pad * L.op.dl0.H + FQL_THREADS - 1) / FQL_THREADS), dim3(FQL_THREADS), 0, s, L.op.dl0);
+                break;
+            case OP_IQLD_CFG: {
+                IqldCfgStepArgs a = L.op.dstep;
+                a.cfg = sample_cfg;   // a run-time float: the cached sampling program holds every other argument
+                FQL_LAUNCH(fql_iqld_cfg_step_kernel, dim3((a.n_pad * a.ad + FQL_THREADS - 1) / FQL_THREADS), dim3(FQL_THREADS), 0, s, a);
+                break;
+            }
             case OP_WGRAD: case OP_LNBWD: case OP_POSTOS: case OP_LOSS_CRITIC: case OP_LOSS_Q: case OP_LOSS_BC:   // (inside OP_GEMM64 launches)
             case OP_PEC: case OP_XCHAIN: case OP_NUM_TYPES:
                 throw HipError{"internal: op type " + std::to_string((int)L.type) + " has no launch of its own"};
@@ -3460,6 +3543,181 @@ struct fql_engine {
         return m * (int64_t)B;
     }
 
+
+    // ---------------------------------------------------------------------------------------
+    // the IQL-diffusion update as a program (agents/iql_diffusion.py:94-247), one per step kind: (update_critic, update_actor) in
+    // {(1, 1), (1, 0), (0, 1), (0, 0)} and the loss probe (with_grads = false: both losses, no backward, the probe halves of the buffers).
+    //   lane 0: batch assembly; one Adam launch per TrainState that steps (critic + Polyak, value, actor: three learning rates, the
+    //           actor's own counters) and the finalize, behind both side lanes
+    //   lane 1: value on [obs ; next_obs] (2B rows) -> target pair -> value loss -> value backward (obs half)
+    //   lane 2: critic pair forward -> critic loss (waits for value(next_obs) on lane 1) -> critic backward; then the actor: loss weights
+    //           from the pair's forward pass that already ran (target_extraction: lane 1's target pair, else this lane's critic pair) and
+    //           the obs half of the value pass -> the policy over 2B rows -> weighted loss -> backward -> embedding gradient
+    // A step kind that does not update a net still runs the forward passes the other one reads, forward-only.  Edges between the forked
+    // lanes run 1 -> 2 only (see schedule()).
+    // ---------------------------------------------------------------------------------------
+    void iqld_leaf_ranges(int& a_lo, int& a_hi, int& v_lo, int& v_hi) const {
+        a_lo = v_lo = 1 << 30; a_hi = v_hi = 0;
+        for (const Leaf& lf : leaves) {
+            if (!lf.trainable) continue;
+            if (lf.name.rfind("actor/", 0) == 0) { a_lo = std::min(a_lo, lf.train_id); a_hi = std::max(a_hi, lf.train_id + 1); }
+            if (lf.name.rfind("value/", 0) == 0) { v_lo = std::min(v_lo, lf.train_id); v_hi = std::max(v_hi, lf.train_id + 1); }
+        }
+    }
+    void build_iqld_program(Program& pr, bool upd_critic, bool upd_actor, bool with_grads) {
+        const int od = cfg.obs_dim, ad = cfg.act_dim, ap = pad16(ad);
+        const bool probe = !with_grads;
+        const bool do_c = upd_critic || probe, do_a = upd_actor || probe;
+        const bool gc = upd_critic && with_grads, ga = upd_actor && with_grads;
+        const bool te = dcfg.target_extraction != 0;
+        DevState* st = d_state;
+        float* out = iql_info + (probe ? IQLD_INFO_STRIDE : 0);
+        float* rows = rows_buf + (probe ? (size_t)3 * B : 0);
+        const void *I_V = &st->info[IFQL_I_VALUE], *I_C = out + IQLD_I_CRITIC, *I_W = out + IQLD_I_ACTOR, *I_A = out + IQLD_I_ACTOR + 1;
+        const Net& na = nets[NET_BC];
+        wide_tiles = true;
+        allow64 = true;
+        emit_lane = 0;
+        if (do_c || do_a) {
+            Op op{};
+            op.type = OP_IQLD_PREP;
+            op.dprep = IqldPrepArgs{d_src, st, seed, d_emb, P + emb_off, B, od, ad, nets[NET_OS].in_p(), nets[NET_C0].in_p(), na.in_p(), ap,
+                                    bc_steps, X_v, X_c1, X_bc, vel, w_rew, w_mask};
+            op.reads = {P + emb_off};
+            op.writes = {X_v, X_c1, X_bc, vel, w_rew, w_mask};
+            push(pr, op);
+            emit_lane = 1;
+            emit_forward(pr, p_v, gc);                                              // value(obs) :109,131; value(next_obs) :96
+            if (do_c || te) for (int e = 0; e < 2; ++e) emit_forward(pr, p_ct[e], false);   // target_critic(obs, actions) :107,133
+        }
+        if (do_c) {
+            Op op{};
+            op.type = OP_IFQL_LOSS_V;
+            op.iv = IfqlValueArgs{p_v.out, p_ct[0].out, p_ct[1].out, gc ? p_v.dz.back() : nullptr, st, B, dcfg.expectile};
+            op.reads = {p_v.out, p_ct[0].out, p_ct[1].out};
+            op.writes = {I_V};
+            if (gc) op.writes.push_back(p_v.dz.back());
+            push(pr, op);
+            if (gc) emit_backward(pr, p_v, 0, B, true, false);
+        }
+        emit_lane = 2;
+        if (do_c || (do_a && !te)) for (int e = 0; e < 2; ++e) emit_forward(pr, p_c1[e], gc);   // critic(obs, actions) :98,135
+        if (do_c) {
+            Op op{};
+            op.type = OP_IQLD_LOSS_C;
+            op.dc = IqldCriticArgs{p_v.out + (size_t)B * nets[NET_OS].layers.back().out_p, p_c1[0].out, p_c1[1].out, w_rew, w_mask,
+                                   gc ? p_c1[0].dz.back() : nullptr, gc ? p_c1[1].dz.back() : nullptr, out, B, cfg.discount};
+            op.reads = {p_v.out, p_c1[0].out, p_c1[1].out, w_rew, w_mask};
+            op.writes = {I_C};
+            if (gc) { op.writes.push_back(p_c1[0].dz.back()); op.writes.push_back(p_c1[1].dz.back()); }
+            push(pr, op);
+            if (gc) for (int e = 0; e < 2; ++e) emit_backward(pr, p_c1[e], 0, B, true, false);
+        }
+        if (do_a) {
+            const PassBuf* pq = te ? p_ct : p_c1;
+            {
+                Op op{};
+                op.type = OP_IQLD_WEIGHT;
+                op.dw = IqldWeightArgs{pq[0].out, pq[1].out, p_v.out, w_lw, rows, out, B, dcfg.optimal_var, (int)(0.1 * (double)B),
+                                       dcfg.optimal_var == IQLD_BINARY_SOFTMAX ? dcfg.softmax_beta : dcfg.awr_temperature};
+                op.reads = {pq[0].out, pq[1].out, p_v.out};
+                op.writes = {w_lw, rows + (size_t)B, I_W};
+                push(pr, op);
+            }
+            emit_forward(pr, p_bc, ga);                                             // actor(obs, 1, x_t, t) :181 and actor(obs, 0, x_t, t) :186
+            {
+                Op op{};
+                op.type = OP_IQLD_LOSS_A;
+                op.dla = IqldActorLossArgs{p_bc.out, vel, w_lw, ga ? p_bc.dz.back() : nullptr, rows, out, B, ad, ap};
+                op.reads = {p_bc.out, vel, w_lw, I_W};   // (I_W: the two kernels write disjoint slots of one info block, in this order)
+                op.writes = {rows, I_A};
+                if (ga) op.writes.push_back(p_bc.dz.back());
+                push(pr, op);
+            }
+            if (ga) {
+                emit_backward(pr, p_bc, 0, 2 * B, true, false);
+                const Layer& l0 = na.layers[0];
+                Op op{};
+                op.type = OP_IQLD_EGRAD;
+                op.deg = IqldEmbedGradArgs{p_bc.dz[0], P + l0.w + (size_t)(od + ad + BC_EMB) * l0.out_p, G + emb_off, B, l0.out_p};
+                op.reads = {p_bc.dz[0], P + l0.w};
+                op.writes = {G + emb_off};
+                push(pr, op);
+            }
+        }
+        if (gc) {
+            adam_for(pr, 2, {NET_C0, NET_C1}, 0);          // critic_lr; Polyak from the pre-step critic (:230)
+            pr.ops.back().adam_lr = dcfg.critic_lr;
+            adam_for(pr, 1, {NET_OS}, 0);                  // value_lr
+            pr.ops.back().adam_lr = dcfg.value_lr;
+        }
+        if (ga) {
+            adam_for(pr, 0, {NET_BC}, 0);                  // actor_lr, the actor TrainState's own count
+            Op& a = pr.ops.back();
+            a.adam_lr = dcfg.actor_lr;
+            a.adam_st = d_state_a;
+            a.reads[0] = d_state_a;
+            a.reads.push_back(G + emb_off);
+            a.writes.push_back(P + emb_off);
+        }
+        int a_lo, a_hi, v_lo, v_hi;
+        iqld_leaf_ranges(a_lo, a_hi, v_lo, v_hi);
+        Op f{};
+        f.type = OP_IQLD_FIN;
+        f.dfin = IqldFinalizeArgs{st, d_state_a, d_partials, d_leaf_range, out, ga ? a_lo : (gc ? v_lo : 0), ga ? a_hi : (gc ? v_hi : 0),
+                                  do_c ? 1 : 0, do_a ? 1 : 0, gc ? 1 : 0, ga ? 1 : 0, with_grads ? 1 : 0};
+        f.reads = {I_V, I_C, I_W, I_A};
+        if (with_grads) for (int m = 0; m < 3; ++m) f.reads.push_back(d_partials + mod_chunk0[m] * 4);
+        f.writes = {out, st, d_state_a};
+        emit_lane = 0;
+        push(pr, f);
+    }
+
+    void build_iqld_workspace() {
+        const int ap = pad16(cfg.act_dim);
+        auto& W = ws_allocs;
+        X_v = dalloc(W, (size_t)2 * B * nets[NET_OS].in_p());
+        X_c1 = dalloc(W, (size_t)B * nets[NET_C0].in_p());
+        X_bc = dalloc(W, (size_t)2 * B * nets[NET_BC].in_p());
+        vel = dalloc(W, (size_t)B * ap);
+        w_rew = dalloc(W, B); w_mask = dalloc(W, B); w_lw = dalloc(W, B);
+        rows_buf = dalloc(W, (size_t)6 * B);
+        X_os = X_eu = X_c2 = X_ct = X_e0 = C0 = Vpart = w_act = tgt = nullptr;
+        fused_euler = euler_finish_fused = false;
+        p_v = make_pass(W, NET_OS, 2 * B, X_v, true, false);
+        p_bc = make_pass(W, NET_BC, 2 * B, X_bc, true, false);
+        for (int e = 0; e < 2; ++e) {
+            p_c1[e] = make_pass(W, NET_C0 + e, B, X_c1, true, false);
+            p_ct[e] = make_pass(W, NET_T0 + e, B, X_c1, false, false);
+        }
+        build_iqld_program(prog_full, true, true, true);
+        build_iqld_program(prog_critic, true, false, true);
+        build_iqld_program(prog_actor, false, true, true);
+        build_iqld_program(prog_none, false, false, true);
+        build_iqld_program(prog_loss, false, false, false);
+        for (Program* pr : {&prog_full, &prog_critic, &prog_actor, &prog_none, &prog_loss}) schedule(*pr, W);
+        for (Program* pr : {&prog_full, &prog_critic, &prog_actor, &prog_none, &prog_loss}) capture(*pr);
+        split_ok = false;
+        src_valid = false;
+    }
+    Program& iqld_program(bool upd_critic, bool upd_actor) {
+        return upd_critic ? (upd_actor ? prog_full : prog_critic) : (upd_actor ? prog_actor : prog_none);
+    }
+    // multiply-accumulates of one IQL-diffusion update per batch row, algorithmic (full GEMM shapes at the logical widths)
+    int64_t iqld_macs(bool upd_critic, bool upd_actor) const {
+        auto macs = [&](const Net& n) { int64_t m = 0; for (const Layer& L : n.layers) m += (int64_t)L.in * L.out; return m; };
+        auto first = [&](const Net& n) { return (int64_t)n.layers[0].in * n.layers[0].out; };
+        const int64_t va = macs(nets[NET_OS]), ac = macs(nets[NET_BC]), cr = macs(nets[NET_C0]);
+        const bool te = dcfg.target_extraction != 0;
+        int64_t m = 0;
+        if (upd_critic || upd_actor) m += 2 * va;                                  // value on 2B rows
+        if (upd_critic || (upd_actor && te)) m += 2 * cr;                          // target pair
+        if (upd_critic || (upd_actor && !te)) m += 2 * cr;                         // critic pair
+        if (upd_critic) m += (2 * va - first(nets[NET_OS])) + 2 * (2 * cr - first(nets[NET_C0]));
+        if (upd_actor) m += 2 * ac + 2 * (2 * ac - first(nets[NET_BC]));           // the policy on 2B rows, forward + backward
+        return m * (int64_t)B;
+    }
+
     // multiply-accumulates of one ReBRAC update per batch row, algorithmic (full GEMM shapes)
     int64_t rebrac_macs(bool full_update) const {
         auto macs = [&](const Net& n) { int64_t m = 0; for (const Layer& L : n.layers) m += (int64_t)L.in * L.out; return m; };
@@ -3480,6 +3738,7 @@ struct fql_engine {
             case AgentKind::SAC: return sac_macs();
             case AgentKind::BC: return bc_macs();
             case AgentKind::IQL: return iql_macs();
+            case AgentKind::IQLD: return iqld_macs(true, true);
             default: break;
         }
         const int64_t os = macs(nets[NET_OS]), bc = macs(nets[NET_BC]), cr = macs(nets[NET_C0]);
@@ -3519,6 +3778,8 @@ struct fql_engine {
         free_program(prog_split);
         free_program(prog_full);
         free_program(prog_critic);
+        free_program(prog_actor);
+        free_program(prog_none);
         free_split();
         for (void* p : ws_allocs) hipFree(p);
         ws_allocs.clear();
@@ -3542,6 +3803,7 @@ struct fql_engine {
             case AgentKind::SAC: build_sac_workspace(); return;
             case AgentKind::BC: build_bc_workspace(); return;
             case AgentKind::IQL: build_iql_workspace(); return;
+            case AgentKind::IQLD: build_iqld_workspace(); return;
         }
         const int inp_c = nets[NET_OS].in_p(), inp_b = nets[NET_BC].in_p();
         X_os = dalloc(W, (size_t)3 * B * inp_c); X_bc = dalloc(W, (size_t)B * inp_b); X_eu = dalloc(W, (size_t)B * inp_b);
@@ -3695,11 +3957,11 @@ struct fql_engine {
         if (!nz) return;
         const int given = (nz->eps1 ? NZ_EPS1 : 0) | (nz->x0 ? NZ_X0 : 0) | (nz->t ? NZ_T : 0) | (nz->z ? NZ_Z : 0) | (nz->eps2 ? NZ_EPS2 : 0);
         if (given & ~desc().noise_reads) invalid("%s", desc().noise_refusal);
-        if (kind == AgentKind::BC && nz->t && !is_device_ptr(nz->t))   // t = k / S on the grid (device pointers are the caller's to keep on it: read as round(t S))
+        if ((kind == AgentKind::BC || kind == AgentKind::IQLD) && nz->t && !is_device_ptr(nz->t))   // t = k / S on the grid (device pointers are the caller's to keep on it: read as round(t S))
             for (int b = 0; b < B; ++b) {
                 const float ts = nz->t[b] * (float)bc_steps;
                 if (!(ts >= -1e-3f && ts <= (float)bc_steps + 1e-3f) || std::fabs(ts - std::nearbyint(ts)) > 1e-3f)
-                    invalid("BC: t[%d] = %g is not on the grid {0, 1/%d, ..., 1}", b, (double)nz->t[b], bc_steps);
+                    invalid("%s: t[%d] = %g is not on the grid {0, 1/%d, ..., 1}", desc().name, b, (double)nz->t[b], bc_steps);
             }
         d.eps1 = stage(nz->eps1, in_noise[0], (size_t)B * ad, s);
         d.x0 = stage(nz->x0, in_noise[1], (size_t)B * ad, s);
@@ -3809,7 +4071,7 @@ struct fql_engine {
         set_source(d, s);
     }
     // where the infos of the last update are: DevState::info, or an IQL handle's own buffer
-    const float* info_src() const { return kind == AgentKind::IQL ? iql_info : &d_state->info[0]; }
+    const float* info_src() const { return own_info() ? iql_info : &d_state->info[0]; }
     void finish_info(float* info, int n, hipStream_t s) {
         if (!info) return;
         hip_touch();
@@ -3884,6 +4146,65 @@ struct fql_engine {
             evals[n_pad] = std::move(ev);
             return ref;
         }
+        if (kind == AgentKind::IQLD) {   // sample_actions with classifier-free guidance (prog_flow): BC's hoisted form over two halves.  n_pad counts
+                    // both: rows [0, half) are the positive pass, [half, n_pad) the unconditional one, half = n_pad / 2 a multiple of 16.  The
+                    // step-bias table [S, 2, H] and the shared C0 = obs W0 + b0 at the head of the program, then per Euler step layer 0 of both
+                    // halves (one launch), layers 1.. of the 16-row Dense kernel over n_pad rows, and the CFG combine + Euler add (one launch
+                    // behind the head GEMM; the last one writes the clipped actions)
+            const int S = bc_steps, ap = pad16(ad), half = n_pad / 2;
+            const Net& n = nets[NET_BC];
+            const Layer& l0 = n.layers[0];
+            const int H = l0.out_p;
+            ev->X = dalloc(W, (size_t)half * n.in_p());      // [obs | 0]
+            ev->Xf = dalloc(W, (size_t)half * ap);           // the flow's state x
+            ev->Xq = dalloc(W, (size_t)S * 2 * H);           // step-bias table c[i][half]
+            float* C0e = dalloc(W, (size_t)half * H);
+            ev->tgt = dalloc(W, (size_t)half * ap);
+            ev->st_obs = dalloc(W, (size_t)half * od);
+            ev->st_noise = dalloc(W, (size_t)half * ad);
+            ev->st_out = dalloc(W, (size_t)half * ad);
+            ev->p_eu = make_pass(W, NET_BC, n_pad, ev->X, false, false);
+            emit_lane = 0;
+            Program& pr = ev->prog_flow;
+            {
+                Op op{};
+                op.type = OP_IQLD_STEPBIAS;
+                op.dsb = IqldStepBiasArgs{d_emb, P + emb_off, P + l0.w + (size_t)(od + ad) * H, ev->Xq, S, H};
+                op.reads = {d_emb, P + emb_off, P + l0.w};
+                op.writes = {ev->Xq};
+                push(pr, op);
+            }
+            {
+                Op op{};
+                op.type = OP_GEMM;
+                GemmTask& t = op.gemm;
+                t.A = ev->X; t.lda = l0.in_p; t.B = P + l0.w; t.ldb = H; t.bias = P + l0.b; t.C = C0e; t.ldc = H;
+                t.M = half; t.N = H; t.K = l0.in_p; t.flags = GF_BIAS;
+                op.reads = {ev->X, t.B};
+                op.writes = {C0e};
+                push(pr, op);
+            }
+            for (int i = 0; i < S; ++i) {
+                Op op{};
+                op.type = OP_IQLD_LAYER0;
+                op.dl0 = IqldLayer0Args{C0e, ev->Xf, P + l0.w + (size_t)od * H, ev->Xq + (size_t)i * 2 * H, ev->p_eu.g[0], half, H, ad, ap};
+                op.reads = {C0e, ev->Xf, ev->Xq, P + l0.w};
+                op.writes = {ev->p_eu.g[0]};
+                push(pr, op);
+                emit_forward(pr, ev->p_eu, false, 0, nullptr, nullptr, 0.f, 0.f, 1);
+                Op st{};
+                st.type = OP_IQLD_CFG;
+                st.dstep = IqldCfgStepArgs{ev->p_eu.out, ev->Xf, i == S - 1 ? ev->tgt : nullptr, half, ad, ap, 1.0f, 1.0f / (float)S};
+                st.reads = {ev->p_eu.out};
+                st.writes = {ev->Xf};
+                if (i == S - 1) st.writes.push_back(ev->tgt);
+                push(pr, st);
+            }
+            schedule(pr, W);
+            Eval& ref = *ev;
+            evals[n_pad] = std::move(ev);
+            return ref;
+        }
         if (actor_on_obs()) {   // sample_actions: the actor's forward over the rows (prog_os on p_os; NET_OS is empty here)
             ev->X = dalloc(W, (size_t)n_pad * nets[NET_BC].in_p());
             ev->st_obs = dalloc(W, (size_t)n_pad * od);
@@ -3940,7 +4261,7 @@ struct fql_engine {
     // The row-chunk loop of every sampling path.  A chunk is <= 4096 rows (256 image rows) of rows_per_obs rows per observation: its
     // observations and noise are staged, `body` enqueues what differs between the paths - the assemble launch, the program(s) and the
     // finishing launch that writes the chunk's [m, act] actions to c.out - and the actions are copied out or, on the engine's own stream, waited for.
-    struct SampleSpec { float temperature = 0.f; int rows_per_obs = 1; bool need_noise = false; int enc = ENC_OS; };   // enc: the encoder of a visual agent's rows
+    struct SampleSpec { float temperature = 0.f; int rows_per_obs = 1; bool need_noise = false; int enc = ENC_OS; int noise_rows = -1; };   // enc: the encoder of a visual agent's rows; noise_rows: noise rows per observation (-1: rows_per_obs)
     struct SampleChunk { Eval& ev; const float *o, *z; float* out; int start, m; };   // observations [start, start + m) of the call
     template <typename Body>
     void sample_chunks(const float* obs, const float* noise, int n, float* out, hipStream_t s, bool own_stream, const SampleSpec& sp, Body&& body) {
@@ -3948,11 +4269,12 @@ struct fql_engine {
         if (!obs || !out) invalid("observations/out must not be NULL");
         if (sp.need_noise && !noise) invalid("noises must not be NULL");
         if (!(sp.temperature >= 0.0f)) invalid("temperature must be >= 0");
-        const int od = cfg.obs_dim, ad = cfg.act_dim, N = sp.rows_per_obs;
+        const int od = cfg.obs_dim, ad = cfg.act_dim, N = sp.rows_per_obs, NZ = sp.noise_rows >= 0 ? sp.noise_rows : N;
         const int per = std::max(1, (visual ? 256 : 4096) / N);
         for (int start = 0; start < n; start += per) {
             const int m = std::min(per, n - start);
-            Eval& ev = get_eval(visual ? (m + 63) & ~63 : pad16(m * N));
+            // (IQL-diffusion: two halves of pad16(m) rows each, so that either half starts on a 16-row tile)
+            Eval& ev = get_eval(visual ? (m + 63) & ~63 : kind == AgentKind::IQLD ? 2 * pad16(m) : pad16(m * N));
             const float* o;
             if (visual) {   // `obs` is uint8 [n, H, W, C]: encode with the module's encoder, then proceed on the encodings
                 const size_t ib = (size_t)cfg.img_h * cfg.img_w * cfg.img_c;
@@ -3964,7 +4286,7 @@ struct fql_engine {
             } else {
                 o = stage(obs + (size_t)start * od, ev.st_obs, (size_t)m * od, s);
             }
-            const float* z = noise ? stage(noise + (size_t)start * N * ad, ev.st_noise, (size_t)m * N * ad, s) : nullptr;
+            const float* z = noise ? stage(noise + (size_t)start * NZ * ad, ev.st_noise, (size_t)m * NZ * ad, s) : nullptr;
             drain_staging(s);
             float* dst = out + (size_t)start * ad;
             const bool dev_out = is_device_ptr(dst);
@@ -4030,6 +4352,23 @@ struct fql_engine {
             hipLaunchKernelGGL(fql_extract_kernel, dim3((c.m * ad + 255) / 256), dim3(256), 0, s, (const float*)c.ev.tgt, c.out, c.m, ad, ap);
         });
     }
+    // IQL-diffusion sample_actions (agents/iql_diffusion.py:249-270): x ~ N(0, I); S times v = v_unc + cfg (v_pos - v_unc), x += v / S; clip.
+    // 2n rows per call, [pos ; unc], chunks of 2048 observations.  Rows are independent (16-row tiles and per-element kernels, the same at
+    // every n), so row j of a call equals the single-observation call on the same noise.
+    void sample_iqld(const float* obs, const float* noise, uint64_t sd, float cfg_scale, int n, float* out, hipStream_t s, bool own_stream) {
+        const int od = cfg.obs_dim, ad = cfg.act_dim, ap = pad16(ad);
+        if (!std::isfinite(cfg_scale)) invalid("cfg must be finite");
+        sample_cfg = cfg_scale;
+        SampleSpec sp{};
+        sp.rows_per_obs = 2; sp.noise_rows = 1;
+        sample_chunks(obs, noise, n, out, s, own_stream, sp, [&](const SampleChunk& c) {
+            const int half = c.ev.n_pad / 2;
+            BcAssembleArgs aa{c.o, c.z, c.ev.X, c.ev.Xf, seed, sd, c.m, half, od, ad, nets[NET_BC].in_p(), ap, c.start};
+            hipLaunchKernelGGL(fql_bc_assemble_kernel, dim3((half + 3) / 4), dim3(FQL_THREADS), 0, s, aa);
+            run_launches(c.ev.prog_flow, s);
+            hipLaunchKernelGGL(fql_extract_kernel, dim3((c.m * ad + 255) / 256), dim3(256), 0, s, (const float*)c.ev.tgt, c.out, c.m, ad, ap);
+        });
+    }
     // IFQL sample_actions (agents/ifql.py:123-155), per observation: num_samples noises through the Euler flow of actor_flow, clip, score by
     // min(q1, q2) of the critic, keep the first argmax.  [n, od] is a batched extension of the reference's single observation: row by row
     // equal to n calls with the same noises.  Chunks of <= 4096 sample rows.
@@ -4085,38 +4424,40 @@ struct fql_engine {
 struct Admission {
     const char* name;
     int only;                          // >= 0: that AgentKind alone (the cells are unused)
-    const char* refuse[kNumKinds];     // FQL, IFQL, ReBRAC, SAC, BC, IQL
+    const char* refuse[kNumKinds];     // FQL, IFQL, ReBRAC, SAC, BC, IQL, IQL-diffusion
 };
 #define OK_ nullptr
 #define NO_ ""
-#define FQL_ALONE {OK_, NO_, NO_, NO_, NO_, NO_}
+#define FQL_ALONE {OK_, NO_, NO_, NO_, NO_, NO_, NO_}
 #define ONLY_(k) (int)AgentKind::k, {}
 #define EP_TABLE(X) \
     X(update_begin, -1, FQL_ALONE)                                                                                                 \
     X(update_end, -1, FQL_ALONE)                                                                                                   \
-    X(update, -1, {OK_, OK_, "its batch has no next_actions: fql_rebrac_update", NO_, NO_, NO_})                                   \
-    X(total_loss, -1, {OK_, OK_, "its batch has no next_actions: fql_rebrac_total_loss", NO_, NO_, NO_})                           \
-    X(sample_actions, -1, {OK_, OK_, OK_, OK_, "fql_bc_sample_actions", OK_})                                                      \
-    X(flow_actions, -1, {OK_, OK_, "the actor is deterministic, there is no flow", NO_, NO_, NO_})                                 \
+    X(update, -1, {OK_, OK_, "its batch has no next_actions: fql_rebrac_update", NO_, NO_, NO_, "the step kind is an argument: fql_iqld_update"})                                   \
+    X(total_loss, -1, {OK_, OK_, "its batch has no next_actions: fql_rebrac_total_loss", NO_, NO_, NO_, "fql_iqld_total_loss"})                           \
+    X(sample_actions, -1, {OK_, OK_, OK_, OK_, "fql_bc_sample_actions", OK_, "fql_iqld_sample_actions"})                                                      \
+    X(flow_actions, -1, {OK_, OK_, "the actor is deterministic, there is no flow", NO_, NO_, NO_, NO_})                                 \
     X(noise_from_jax_keys, -1, FQL_ALONE)                                                                                          \
     X(dataset_add_frames, -1, FQL_ALONE)                                                                                           \
-    X(replay_create, -1, {OK_, NO_, NO_, OK_, NO_, NO_})                                                                           \
-    X(replay_add, -1, {OK_, NO_, NO_, OK_, NO_, NO_})                                                                              \
+    X(replay_create, -1, {OK_, NO_, NO_, OK_, NO_, NO_, NO_})                                                                           \
+    X(replay_add, -1, {OK_, NO_, NO_, OK_, NO_, NO_, NO_})                                                                              \
     X(replay_add_frames, -1, FQL_ALONE)                                                                                            \
-    X(replay_size, -1, {OK_, NO_, NO_, OK_, NO_, NO_})                                                                             \
+    X(replay_size, -1, {OK_, NO_, NO_, OK_, NO_, NO_, NO_})                                                                             \
     X(update_balanced, -1, FQL_ALONE)                                                                                              \
     X(update_from_dataset_begin, -1, FQL_ALONE)                                                                                    \
     X(update_from_dataset_begin_split, -1, FQL_ALONE)                                                                              \
     X(update_begin_split, -1, FQL_ALONE)                                                                                           \
     X(update_end_split, -1, FQL_ALONE)                                                                                             \
     X(grad_buckets, -1, FQL_ALONE)                                                                                                 \
-    X(update_from_dataset, -1, {OK_, OK_, "the step kind is an argument: fql_rebrac_update_from_dataset", NO_, NO_, NO_})          \
-    X(info_wait, -1, {OK_, OK_, OK_, "14 infos: fql_info_wait_n", "4 infos: fql_info_wait_n", "16 or 19 infos: fql_info_wait_n"})  \
-    X(read_info, -1, {OK_, OK_, OK_, "14 infos: fql_read_info_n", "4 infos: fql_read_info_n", "16 or 19 infos: fql_read_info_n"})  \
-    X(profile_update, -1, {OK_, OK_, "FQL batch sources only", NO_, NO_, NO_})                                                     \
-    X(debug_workspace, -1, {OK_, OK_, "FQL workspaces only", NO_, NO_, NO_})                                                       \
+    X(update_from_dataset, -1, {OK_, OK_, "the step kind is an argument: fql_rebrac_update_from_dataset", NO_, NO_, NO_, "the step kind is an argument: fql_iqld_update_from_dataset"})          \
+    X(info_wait, -1, {OK_, OK_, OK_, "14 infos: fql_info_wait_n", "4 infos: fql_info_wait_n", "16 or 19 infos: fql_info_wait_n", "21 infos: fql_info_wait_n"})  \
+    X(read_info, -1, {OK_, OK_, OK_, "14 infos: fql_read_info_n", "4 infos: fql_read_info_n", "16 or 19 infos: fql_read_info_n", "21 infos: fql_read_info_n"})  \
+    X(profile_update, -1, {OK_, OK_, "FQL batch sources only", NO_, NO_, NO_, NO_})                                                     \
+    X(debug_workspace, -1, {OK_, OK_, "FQL workspaces only", NO_, NO_, NO_, NO_})                                                       \
     X(dataset_upload_frames, -1, FQL_ALONE)                                                                                        \
     X(update_from_frames, -1, FQL_ALONE)                                                                                           \
+    X(set_step, -1, {OK_, OK_, OK_, OK_, OK_, OK_, "one count per TrainState: fql_iqld_set_steps"})                                \
+    X(set_grad_scale, -1, {OK_, OK_, OK_, OK_, OK_, OK_, "no data-parallel halves on this kind"})                                  \
     X(rebrac_update, ONLY_(REBRAC))                                                                                                \
     X(rebrac_update_from_dataset, ONLY_(REBRAC))                                                                                   \
     X(rebrac_total_loss, ONLY_(REBRAC))                                                                                            \
@@ -4137,7 +4478,15 @@ struct Admission {
     X(bc_update_from_dataset, ONLY_(BC))                                                                                           \
     X(bc_policy_loss, ONLY_(BC))                                                                                                   \
     X(bc_sample_actions, ONLY_(BC))                                                                                                \
-    X(bc_stats, ONLY_(BC))
+    X(bc_stats, ONLY_(BC))                                                                                                         \
+    X(iqld_update, ONLY_(IQLD))                                                                                                    \
+    X(iqld_update_from_dataset, ONLY_(IQLD))                                                                                       \
+    X(iqld_total_loss, ONLY_(IQLD))                                                                                                \
+    X(iqld_sample_actions, ONLY_(IQLD))                                                                                            \
+    X(iqld_read_rows, ONLY_(IQLD))                                                                                                 \
+    X(iqld_get_steps, ONLY_(IQLD))                                                                                                 \
+    X(iqld_set_steps, ONLY_(IQLD))                                                                                                 \
+    X(iqld_stats, ONLY_(IQLD))
 #define X(ep, ...) EP_##ep,
 enum EntryPoint { EP_TABLE(X) EP_COUNT };
 #undef X
@@ -4295,6 +4644,7 @@ static int create_engine(const fql_config* cfg, AgentSpec agent, uint64_t seed, 
     const auto* scfg = static_cast<const fql_sac_config*>(agent.cfg);
     const auto* bcfg = static_cast<const fql_bc_config*>(agent.cfg);
     const auto* qcfg = static_cast<const fql_iql_config*>(agent.cfg);
+    const auto* dcfg = static_cast<const fql_iqld_config*>(agent.cfg);
     auto refuse = [&](const std::string& why) { g_create_error = std::string(kd.create) + ": " + why; return FQL_E_INVALID; };
     if (kind != AgentKind::FQL) {   // every other kind: state observations and fp32 only
         if (cfg->encoder != 0) return refuse(std::string("visual encoders are not available for ") + kd.name + " (encoder must be 0)");
@@ -4328,6 +4678,18 @@ static int create_engine(const fql_config* cfg, AgentSpec agent, uint64_t seed, 
             if (qcfg->actor_loss != 0 && qcfg->actor_loss != 1) return refuse("actor_loss must be 0 (awr) or 1 (ddpgbc)");
             if (qcfg->const_std != 0 && qcfg->const_std != 1) return refuse("const_std must be 0 or 1");
             break;
+        case AgentKind::IQLD:
+            if (dcfg->optimal_var == 3 || dcfg->optimal_var == 4)
+                return refuse("optimal_var 'softmax' / 'sampled_adv_softmax' (the continuous policy with an external bc_agent) is not available: "
+                              "the binary family only (0 binary, 1 binary_awr_loss, 2 binary_softmax_loss)");
+            if (dcfg->optimal_var < 0 || dcfg->optimal_var > 4) return refuse("optimal_var must be 0 (binary), 1 (binary_awr_loss) or 2 (binary_softmax_loss)");
+            if (dcfg->opt_decay_schedule != 0) return refuse("opt_decay_schedule 'cosine' is not available (a constant actor_lr only)");
+            if (!(dcfg->expectile > 0.0f && dcfg->expectile < 1.0f)) return refuse("expectile must be in (0, 1)");
+            if (!(dcfg->actor_lr > 0.0f) || !(dcfg->value_lr > 0.0f) || !(dcfg->critic_lr > 0.0f)) return refuse("actor_lr, value_lr and critic_lr must be > 0");
+            if (!std::isfinite(dcfg->awr_temperature) || !std::isfinite(dcfg->softmax_beta)) return refuse("awr_temperature and softmax_beta must be finite");
+            if (dcfg->target_extraction != 0 && dcfg->target_extraction != 1) return refuse("target_extraction must be 0 or 1");
+            if (dcfg->denoise_steps < 1 || dcfg->denoise_steps > 1024) return refuse("denoise_steps must be in [1, 1024]");
+            break;
     }
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
@@ -4350,6 +4712,7 @@ static int create_engine(const fql_config* cfg, AgentSpec agent, uint64_t seed, 
                 break;
             case AgentKind::BC: h->bc_steps = bcfg->denoise_steps; break;
             case AgentKind::IQL: h->qcfg = *qcfg; break;
+            case AgentKind::IQLD: h->dcfg = *dcfg; h->bc_steps = dcfg->denoise_steps; break;
         }
         if (cfg->encoder != 0) {   // visual agent (agents/fql.py:196-202): the MLPs see the 512-wide encoding instead of obs
             if (cfg->encoder != 1 && cfg->encoder != 2) invalid("encoder %d not available (0 = none, 1 = impala_small, 2 = impala)", cfg->encoder);
@@ -4386,7 +4749,7 @@ static int create_engine(const fql_config* cfg, AgentSpec agent, uint64_t seed, 
         HIP_CHECK(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
         for (int l = 1; l < FQL_LANES; ++l) HIP_CHECK(hipStreamCreateWithFlags(&h->lane_streams[l], hipStreamNonBlocking));
         h->build_nets();
-        if (kind == AgentKind::BC) {   // the timestep-embedding table, rows k = 0..S: freq_i = float32(exp_f64(-ln(10000) i / 8)),
+        if (kind == AgentKind::BC || kind == AgentKind::IQLD) {   // the timestep-embedding table, rows k = 0..S: freq_i = float32(exp_f64(-ln(10000) i / 8)),
                        // arg = float32(float32(t 10000) freq_i), [cos | sin] in fp64 of that fp32 argument, rounded to fp32
             const int S = h->bc_steps;
             std::vector<float> tab((size_t)(S + 1) * BC_EMB);
@@ -4416,7 +4779,7 @@ static int create_engine(const fql_config* cfg, AgentSpec agent, uint64_t seed, 
         h->build_chain_weights();
         h->refresh_chain_weights(h->stream);
         HIP_CHECK(hipMalloc((void**)&h->d_state, sizeof(DevState)));
-        if (kind == AgentKind::IQL) {
+        if (h->own_info()) {
             HIP_CHECK(hipMalloc((void**)&h->iql_info, 2 * IQL_INFO_STRIDE * sizeof(float)));
             HIP_CHECK(hipMemset(h->iql_info, 0, 2 * IQL_INFO_STRIDE * sizeof(float)));
         }
@@ -4430,6 +4793,10 @@ static int create_engine(const fql_config* cfg, AgentSpec agent, uint64_t seed, 
         int bi; std::memcpy(&bi, &ninf, 4); st.gmax = bi >= 0 ? bi : bi ^ 0x7FFFFFFF;
         std::memcpy(&bi, &pinf, 4); st.gmin = bi >= 0 ? bi : bi ^ 0x7FFFFFFF;
         HIP_CHECK(hipMemcpy(h->d_state, &st, sizeof st, hipMemcpyHostToDevice));
+        if (kind == AgentKind::IQLD) {   // the actor TrainState's counters (the same initial values)
+            HIP_CHECK(hipMalloc((void**)&h->d_state_a, sizeof(DevState)));
+            HIP_CHECK(hipMemcpy(h->d_state_a, &st, sizeof st, hipMemcpyHostToDevice));
+        }
         h->build_workspace(cfg->batch_size);
     } catch (const Invalid& e) {
         g_create_error = e.msg; fql_destroy(h); return FQL_E_INVALID;
@@ -4451,7 +4818,7 @@ int fql_destroy(fql_handle h) {
     for (auto& kv : h->evals) {
         for (void* p : kv.second->allocs) hipFree(p);
     }
-    hipFree(h->P); hipFree(h->G); hipFree(h->Mu); hipFree(h->Nu); hipFree(h->d_chunks); hipFree(h->d_partials); hipFree(h->d_leaf_range); hipFree(h->d_state); hipFree(h->d_src); hipFree(h->d_emb); hipFree(h->iql_info);
+    hipFree(h->P); hipFree(h->G); hipFree(h->Mu); hipFree(h->Nu); hipFree(h->d_chunks); hipFree(h->d_partials); hipFree(h->d_leaf_range); hipFree(h->d_state); hipFree(h->d_src); hipFree(h->d_emb); hipFree(h->iql_info); hipFree(h->d_state_a);
     if (h->h_src_ring) hipHostFree(h->h_src_ring);
     if (h->h_info_ring) hipHostFree(h->h_info_ring);
     for (auto& e : h->info_ev) if (e) hipEventDestroy(e);
@@ -4535,6 +4902,7 @@ int fql_get_step(fql_handle h, int64_t* adam_count, int64_t* train_step) {
 }
 int fql_set_step(fql_handle h, int64_t adam_count, int64_t train_step) {
     if (!h) return FQL_E_INVALID;
+    FQL_ADMIT(h, EP_set_step);   // (an IQL-diffusion handle keeps a second counter block, which this call does not write)
     FQL_TRY(h, {
         if (adam_count < 0) invalid("adam_count must be >= 0");
         HIP_CHECK(hipDeviceSynchronize());
@@ -4643,6 +5011,7 @@ int fql_grad_buffer(fql_handle h, void** device_ptr, size_t* num_floats) {
 }
 int fql_set_grad_scale(fql_handle h, float scale) {
     if (!h) return FQL_E_INVALID;
+    FQL_ADMIT(h, EP_set_grad_scale);   // (the actor's Adam launch of an IQL-diffusion handle reads the scale of its own counter block)
     FQL_TRY(h, {
         HIP_CHECK(hipDeviceSynchronize());
         HIP_CHECK(hipMemcpy(&h->d_state->grad_scale, &scale, sizeof scale, hipMemcpyHostToDevice));
@@ -5219,6 +5588,116 @@ int fql_bc_stats(fql_handle h, int64_t* launches_per_update, int64_t* macs_per_u
     if (launches_per_update) *launches_per_update = (int64_t)h->prog_full.launches.size();
     if (macs_per_update) *macs_per_update = h->macs_per_update();
     if (launches_per_sample) *launches_per_sample = 4 + (int64_t)h->bc_steps * h->nets[NET_BC].nl();   // assemble, step-bias table, C0, S (layer 0 + nh GEMMs), extract
+    return FQL_OK;
+}
+
+// ---- IQL-diffusion (agents/iql_diffusion.py): IQL critics, weighted flow actor, classifier-free guidance -----------------------------
+// One update through run_update (the AQL form and the graph are bitwise equal), one program per step kind; 21 infos.
+static_assert(IQLD_NUM_INFO == FQL_IQLD_NUM_INFO && IQLD_INFO_STRIDE == IQL_INFO_STRIDE, "IQL-diffusion info layout");
+void fql_iqld_default_config(fql_iqld_config* c) {   // agents/iql_diffusion.py:362-396
+    std::memset(c, 0, sizeof *c);
+    c->actor_lr = c->value_lr = c->critic_lr = 3e-4f;
+    c->expectile = 0.9f;
+    c->awr_temperature = 0.1f;
+    c->softmax_beta = 3.0f;
+    c->optimal_var = IQLD_BINARY_AWR;
+    c->target_extraction = 1;
+    c->denoise_steps = 16;
+    c->opt_decay_schedule = 0;
+}
+int fql_iqld_create(const fql_config* cfg, const fql_iqld_config* dcfg, uint64_t seed, fql_handle* out) {
+    if (!dcfg) { g_create_error = "dcfg must not be NULL"; if (out) *out = nullptr; return FQL_E_INVALID; }
+    return create_engine(cfg, {AgentKind::IQLD, dcfg}, seed, out);
+}
+int fql_iqld_update(fql_handle h, const float* obs, const float* act, const float* rew, const float* masks, const float* next_obs,
+                    int batch_size, const fql_noise* noise, int update_critic, int update_actor, float* info, void* stream) {
+    if (!h) return FQL_E_INVALID;
+    FQL_ADMIT(h, EP_iqld_update);
+    return update_with(h, h->iqld_program(update_critic != 0, update_actor != 0), info, FQL_IQLD_NUM_INFO, stream, [&](hipStream_t s) {
+        h->source_from_batch(obs, act, rew, masks, next_obs, batch_size, noise, 1, s);
+    });
+}
+int fql_iqld_update_from_dataset(fql_handle h, const int64_t* idx, int batch_size, int64_t lo, int64_t hi, const fql_noise* noise,
+                                 int update_critic, int update_actor, float* info, void* stream) {
+    if (!h) return FQL_E_INVALID;
+    FQL_ADMIT(h, EP_iqld_update_from_dataset);
+    return update_with(h, h->iqld_program(update_critic != 0, update_actor != 0), info, FQL_IQLD_NUM_INFO, stream, [&](hipStream_t s) {
+        h->source_from_dataset(idx, batch_size, lo, hi, noise, s);
+    });
+}
+int fql_iqld_total_loss(fql_handle h, const float* obs, const float* act, const float* rew, const float* masks, const float* next_obs,
+                        int batch_size, const fql_noise* noise, float* loss, float* info, void* stream) {
+    if (!h) return FQL_E_INVALID;
+    FQL_ADMIT(h, EP_iqld_total_loss);
+    FQL_TRY(h, {
+        hipStream_t s = pick(h, stream);
+        h->source_from_batch(obs, act, rew, masks, next_obs, batch_size, noise, 0, s);
+        run_program(h, h->prog_loss, s);   // writes the probe halves of the info and row buffers: the last update's stay
+        float tmp[IQLD_INFO_STRIDE];
+        HIP_CHECK(hipMemcpyAsync(tmp, h->iql_info + IQLD_INFO_STRIDE, sizeof tmp, hipMemcpyDeviceToHost, s));
+        HIP_CHECK(hipStreamSynchronize(s));
+        // iql_diffusion.py:272-285: critic_loss + value_loss + actor_loss; every info but the grad statistics
+        if (loss) *loss = tmp[IQLD_I_CRITIC] + tmp[IQLD_I_VALUE] + tmp[IQLD_I_ACTOR + 1];
+        if (info) std::memcpy(info, tmp, (size_t)IQLD_I_GRAD * sizeof(float));
+    });
+}
+int fql_iqld_sample_actions(fql_handle h, const float* obs, int n, const float* noise, uint64_t seed, float cfg, float* out, void* stream) {
+    if (!h) return FQL_E_INVALID;
+    FQL_ADMIT(h, EP_iqld_sample_actions);
+    FQL_TRY(h, h->sample_iqld(obs, noise, seed, cfg, n, out, pick(h, stream), stream == nullptr));
+}
+int fql_iqld_read_rows(fql_handle h, int which, float* out, int n) {
+    if (!h) return FQL_E_INVALID;
+    FQL_ADMIT(h, EP_iqld_read_rows);
+    FQL_TRY(h, {
+        if (which < 0 || which > 5) invalid("which must be in [0, 5] (got %d)", which);
+        if (!out) invalid("out must not be NULL");
+        if (n != h->B) invalid("n = %d does not match the batch size %d", n, h->B);
+        HIP_CHECK(hipStreamSynchronize(h->stream));
+        HIP_CHECK(hipDeviceSynchronize());
+        HIP_CHECK(hipMemcpy(out, h->rows_buf + (size_t)which * h->B, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
+    });
+}
+int fql_iqld_get_steps(fql_handle h, int64_t steps[3]) {
+    if (!h) return FQL_E_INVALID;
+    FQL_ADMIT(h, EP_iqld_get_steps);
+    FQL_TRY(h, {
+        if (!steps) invalid("steps must not be NULL");
+        HIP_CHECK(hipStreamSynchronize(h->stream));
+        HIP_CHECK(hipDeviceSynchronize());
+        DevState st, sa;
+        HIP_CHECK(hipMemcpy(&st, h->d_state, sizeof st, hipMemcpyDeviceToHost));
+        HIP_CHECK(hipMemcpy(&sa, h->d_state_a, sizeof sa, hipMemcpyDeviceToHost));
+        steps[0] = (int64_t)st.rng_step; steps[1] = st.adam_count; steps[2] = sa.adam_count;
+    });
+}
+int fql_iqld_set_steps(fql_handle h, const int64_t steps[3]) {
+    if (!h) return FQL_E_INVALID;
+    FQL_ADMIT(h, EP_iqld_set_steps);
+    FQL_TRY(h, {
+        if (!steps) invalid("steps must not be NULL");
+        if (steps[0] < 0 || steps[1] < 0 || steps[2] < 0) invalid("the counters must be >= 0");
+        HIP_CHECK(hipDeviceSynchronize());
+        DevState st, sa;
+        HIP_CHECK(hipMemcpy(&st, h->d_state, sizeof st, hipMemcpyDeviceToHost));
+        HIP_CHECK(hipMemcpy(&sa, h->d_state_a, sizeof sa, hipMemcpyDeviceToHost));
+        st.rng_step = (uint64_t)steps[0];
+        st.adam_count = steps[1]; st.train_step = steps[1] + 1;
+        st.b1pow = std::pow(0.9, (double)steps[1]); st.b2pow = std::pow(0.999, (double)steps[1]);
+        sa.adam_count = steps[2]; sa.train_step = steps[2] + 1;
+        sa.b1pow = std::pow(0.9, (double)steps[2]); sa.b2pow = std::pow(0.999, (double)steps[2]);
+        HIP_CHECK(hipMemcpy(h->d_state, &st, sizeof st, hipMemcpyHostToDevice));
+        HIP_CHECK(hipMemcpy(h->d_state_a, &sa, sizeof sa, hipMemcpyHostToDevice));
+    });
+}
+int fql_iqld_stats(fql_handle h, int update_critic, int update_actor, int64_t* launches_per_update, int64_t* macs_per_update,
+                   int64_t* launches_per_sample) {
+    if (!h) return FQL_E_INVALID;
+    FQL_ADMIT(h, EP_iqld_stats);
+    if (launches_per_update) *launches_per_update = (int64_t)h->iqld_program(update_critic != 0, update_actor != 0).launches.size();
+    if (macs_per_update) *macs_per_update = h->iqld_macs(update_critic != 0, update_actor != 0);
+    // assemble, step-bias table, C0, S (layer 0 + nh GEMMs + the CFG step), extract
+    if (launches_per_sample) *launches_per_sample = 4 + (int64_t)h->bc_steps * (h->nets[NET_BC].nl() + 1);
     return FQL_OK;
 }
 

@@ -541,6 +541,83 @@ int fql_iql_sample_actions(fql_handle h, const float* observations, int n, const
 /* launches and algorithmic MACs of one update */
 int fql_iql_stats(fql_handle h, int64_t* launches_per_update, int64_t* macs_per_update);
 
+/* ---- IQL-diffusion (agents/iql_diffusion.py): IQL critics with an optimality-conditioned flow actor and classifier-free guidance, the
+ * agent the CFGRL training script defaults to.  The BINARY optimality family only: optimal_var in {binary, binary_awr_loss,
+ * binary_softmax_loss}, whose actor is DiffusionPolicy with nn.Embed(2, 32).  State observations, fp32, GELU, a constant learning rate.
+ * Four bare TrainStates (no ModuleDict), leaves in jax dict order:
+ *   "actor/Dense_0/{bias,kernel}" (the head, flax's lecun_normal), "actor/Embed_0/embedding" ([2, 32], N(0, 1 / 32): flax's
+ *   variance_scaling(1, fan_in, normal, out_axis=0), whose fan_in on [2, 32] is 32), "actor/MLP_0/Dense_i/{bias,kernel}" (first layer
+ *   obs + act + 16 + 32 -> hidden) and "actor/MLP_0/LayerNorm_i/{bias,scale}" with actor_layer_norm;
+ *   "critic/value_net/..." and "target_critic/value_net/..." (stacked [2, ...]), "value/value_net/..." (one member, unstacked).
+ * fql_config mapping: actor_hidden = actor_hidden_dims, value_hidden = hidden_dims, layer_norm = actor_layer_norm = use_layer_norm;
+ * lr, alpha, q_agg, flow_steps and normalize_q_loss are ignored (the three learning rates travel in fql_iqld_config).
+ * Update (agents/iql_diffusion.py:215-247), the reference's static flags as arguments: update_critic steps the critic (Adam critic_lr,
+ * Polyak of the target from the PRE-step critic) and the value net (Adam value_lr); update_actor steps the actor (Adam actor_lr).  Each
+ * TrainState keeps its own Adam count: a step kind leaves the other nets' parameters, moments and counts untouched; (0, 0) changes no
+ * parameter and still advances the RNG step.  Losses: value = expectile regression onto min of the target pair at (obs, act); critic =
+ * mean over BOTH members and the batch of (q_e - r - discount mask v(next_obs))^2 (half of agents/iql.py's); actor = mean_b(w_b
+ * mean_a((vel - v_pos)^2) + 0.1 mean_a((vel - v_unc)^2)) with the weights w from adv = min(q1, q2)(obs, act) - v(obs) on stored
+ * parameters (the target pair with target_extraction, else the critic): binary adv > 0; binary_awr_loss min(where(adv > 0,
+ * clip(exp(adv awr_temperature), 0, 1e8), 0), 100); binary_softmax_loss e / (sum e + 1e-8), e = where(adv > 0, clip(exp(adv
+ * softmax_beta), 0, 1e8), 0).
+ * Infos: 21 floats (FQL_IQLD_NUM_INFO, fql_handle_info_name): 0 critic_loss 1 q (member 0's mean) 2 value_loss 3 v 4 v_min 5 v_max
+ *   6 actor_q 7 actor_loss 8 actor_positive_ratio 9 actor_loss_positive 10 actor_loss_uncond 11 o_mean 12 o_std 13 o_min 14 o_max
+ *   15 effective_batch_size 16 loss_weights_top_10_mass 17 loss_weights_max 18 grad/max 19 grad/min 20 grad/norm.  The reference merges
+ *   {**critic_info, **value_info, **actor_info}: grad/... are the ACTOR's gradient statistics when update_actor, otherwise the value
+ *   net's, never the critic's.  The slots of a net that did not step are 0.  fql_read_info and fql_info_wait return FQL_E_STATE.
+ * fql_noise: only x0 [B, act] (raw N(0, 1)) and t [B] on the grid {0, 1/S, ..., 1} are read, as on a BC handle.
+ * An IQL-diffusion handle is an ordinary fql_handle for destroy, set_batch_size, leaf / param / opt-state access, dataset upload / add /
+ * reserve / size, info enqueue / fql_info_wait_n / fql_read_info_n, fql_synchronize, fql_stats (the full step) and fql_stream;
+ * fql_get_step reads the critic's count and step (fql_iqld_get_steps reads all three counters).  Refused: at create, FQL_E_INVALID
+ * naming the field: optimal_var softmax / sampled_adv_softmax (the continuous policy with an external bc_agent), opt_decay_schedule
+ * cosine, encoder != 0, precision != 0.  On an IQL-diffusion handle fql_update*, fql_update_begin* / _end*, fql_total_loss,
+ * fql_sample_actions, fql_flow_actions, fql_grad_buckets, frame uploads / updates, fql_replay_*, fql_update_balanced,
+ * fql_noise_from_jax_keys, fql_read_info, fql_info_wait, fql_set_step (fql_iqld_set_steps writes both counter blocks), fql_set_grad_scale
+ * and every other kind's calls return FQL_E_STATE, and fql_group_create with such a
+ * member returns FQL_E_STATE.  The fql_iqld_* calls on another handle return FQL_E_STATE. */
+#define FQL_IQLD_NUM_INFO 21
+typedef struct fql_iqld_config {
+    float actor_lr, value_lr, critic_lr;  /* 3e-4 each                                                          */
+    float expectile;                      /* 0.9                                                                */
+    float awr_temperature;                /* 0.1                                                                */
+    float softmax_beta;                   /* 3.0                                                                */
+    int32_t optimal_var;                  /* 0 binary, 1 binary_awr_loss (default), 2 binary_softmax_loss; 3 softmax and
+                                             4 sampled_adv_softmax are refused                                  */
+    int32_t target_extraction;            /* adv from the target critic (1) or the critic (0)                   */
+    int32_t denoise_steps;                /* S: grid of t and Euler steps of sample_actions (16)                */
+    int32_t opt_decay_schedule;           /* 0 none; 1 cosine is refused                                        */
+    int32_t reserved[6];
+} fql_iqld_config;
+void fql_iqld_default_config(fql_iqld_config* c);
+int fql_iqld_create(const fql_config* cfg, const fql_iqld_config* dcfg, uint64_t seed, fql_handle* out);
+/* IQLDiffusionAgent.update(batch, update_critic, update_actor).  `info`: 21 floats, or NULL. */
+int fql_iqld_update(fql_handle h, const float* observations, const float* actions, const float* rewards, const float* masks,
+                    const float* next_observations, int batch_size, const fql_noise* noise, int update_critic, int update_actor,
+                    float* info, void* stream);
+/* train_dataset.sample(B) + update(batch, ...) on the device; idx / lo / hi as fql_update_from_dataset's. */
+int fql_iqld_update_from_dataset(fql_handle h, const int64_t* idx, int batch_size, int64_t lo, int64_t hi, const fql_noise* noise,
+                                 int update_critic, int update_actor, float* info, void* stream);
+/* IQLDiffusionAgent.total_loss(batch): pure forward, no state change (parameters, moments, counters, and what fql_read_info_n and
+ * fql_iqld_read_rows(0..2) read are as the last update left them).  loss = critic_loss + value_loss + actor_loss; `info`
+ * receives the 18 infos before the grad statistics.  Synchronous. */
+int fql_iqld_total_loss(fql_handle h, const float* observations, const float* actions, const float* rewards, const float* masks,
+                        const float* next_observations, int batch_size, const fql_noise* noise, float* loss, float* info, void* stream);
+/* IQLDiffusionAgent.sample_actions(observations, seed, temperature, cfg, o): x ~ N(0, I); S times v = v_unc + cfg (v_pos - v_unc),
+ * x += v / S; clip to [-1, 1].  temperature and o are not read in this family.  noise [n, act] or NULL (engine RNG keyed by `seed`);
+ * rows of one call equal single calls with the same noise rows. */
+int fql_iqld_sample_actions(fql_handle h, const float* observations, int n, const float* noise, uint64_t seed, float cfg, float* out,
+                            void* stream);
+/* The per-row infos of the last actor step: which = 0 actor_losses, 1 o (all ones), 2 loss_weights; 3, 4, 5: the same of the last
+ * fql_iqld_total_loss.  n = the batch size; `out` host.  Synchronous. */
+int fql_iqld_read_rows(fql_handle h, int which, float* out, int n);
+/* [0] updates so far (the RNG step), [1] the critic's and value net's Adam count, [2] the actor's; TrainState.step is count + 1.
+ * fql_iqld_set_steps restores them (a checkpoint): the next update draws what the saved agent would have drawn. */
+int fql_iqld_get_steps(fql_handle h, int64_t steps[3]);
+int fql_iqld_set_steps(fql_handle h, const int64_t steps[3]);
+/* launches and algorithmic MACs of one update of that step kind; launches of one sampling call of <= 2048 observations */
+int fql_iqld_stats(fql_handle h, int update_critic, int update_actor, int64_t* launches_per_update, int64_t* macs_per_update,
+                   int64_t* launches_per_sample);
+
 #ifdef __cplusplus
 }
 #endif
