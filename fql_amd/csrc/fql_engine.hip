@@ -223,6 +223,10 @@ struct Launch {
     void *table_w = nullptr, *table_l = nullptr, *table_m = nullptr;
     int n_w = 0, n_l = 0, tile_w = 0, tile_l = 0, tile_m = 0;
     std::vector<GemmTask> dg_tasks;   // OP_DGRAD0: the (<= 4) tasks of this launch, handed over as the kernel argument
+    // host copies of the device task tables above, as schedule() uploaded them (read by fql_debug_plan only)
+    std::vector<GemmTask> h_gemm;
+    std::vector<WgradTask> h_wgrad;
+    std::vector<LnBwdTask> h_ln;
     std::vector<int> waits;      // launches of the OTHER lane that must have completed
     bool record_after = false;   // some launch of the other lane waits on this one
     hipEvent_t ev = nullptr;
@@ -1908,6 +1912,7 @@ struct fql_engine {
                     L.table_w = up(tw.data(), tw.size() * sizeof(WgradTask));
                     L.table_l = up(tl.data(), tl.size() * sizeof(LnBwdTask));
                     L.table_m = up(tmisc.data(), tmisc.size() * sizeof(MiscTask));
+                    L.h_gemm = tg; L.h_wgrad = tw; L.h_ln = tl;
                     pr.launches.push_back(L);
                     continue;
                 }
@@ -2044,6 +2049,7 @@ struct fql_engine {
                 L.table = dalloc(owner, tb.size() * sizeof(GemmTask) / sizeof(float) + 4);
                 HIP_CHECK(hipMemcpy(L.table, tb.data(), tb.size() * sizeof(GemmTask), hipMemcpyHostToDevice));
                 L.grid = tile;
+                L.h_gemm = tb;
                 pr.launches.push_back(L);
             }
           }
@@ -2124,6 +2130,21 @@ struct fql_engine {
                 if (edge[a][b] && edge[b][a])
                     invalid("lane placement makes lanes %d and %d wait on each other in both directions: not capturable on this HIP runtime "
                             "(hipStreamEndCapture recursion); move one of the passes", a, b);
+    }
+
+    // XCD-aware tile order of a chain launch over M rows of an H-wide layer (16-row tiles x 32-column tiles): the number of row groups gm
+    // (gm x gn = 8 blocks of the tile grid) with the fewest panel fetches, 0 = row-major when no grouping divides the grid
+    static int chain_xg(int M, int H) {
+        const int ntm = M / 16, ntn = H / 32;
+        int xg = 0;
+        double best = 1e30;
+        for (int gm : {1, 2, 4, 8}) {
+            const int gn = 8 / gm;
+            if (ntm % gm || ntn % gn) continue;
+            const double cost = (double)gn * M + (double)gm * H;
+            if (cost < best) { best = cost; xg = gm; }
+        }
+        return xg;
     }
 
     // one launch of a program on stream s (tl: timeline id of the diagnostics build, -1 = none); reads engine state only
@@ -2229,17 +2250,7 @@ struct fql_engine {
             }
             case OP_CHAIN: {
                 ChainArgs ca = L.op.chain; ca.tl = tl;
-                {   // XCD-aware tile order of the chain launches (16-row tiles x 32-column tiles)
-                    const int ntm = ca.M / 16, ntn = cfg.actor_hidden[0] / 32;
-                    ca.xg = 0;
-                    double best = 1e30;
-                    for (int gm : {1, 2, 4, 8}) {
-                        const int gn = 8 / gm;
-                        if (ntm % gm || ntn % gn) continue;
-                        const double cost = (double)gn * ca.M + (double)gm * cfg.actor_hidden[0];
-                        if (cost < best) { best = cost; ca.xg = gm; }
-                    }
-                }
+                ca.xg = chain_xg(ca.M, cfg.actor_hidden[0]);
                 if (cfg.precision == 2 && ca.variant != 3) {   // (variant D keeps fp32 operands: its dZ / W arrive as fp32 and splitting both in the kernel costs what the MFMAs save)
 #define FQL_CHAIN_SPLIT(HH, VV) FQL_LAUNCH((fql_chain_split_kernel<HH, VV>), dim3((L.op.chain.M / 16) * (HH / 32)), dim3(FQL_CHAIN_THREADS), FQL_CHAIN_LDS_BYTES(HH), s, ca)
                     if (cfg.actor_hidden[0] == 512) { if (ca.variant == 0) FQL_CHAIN_SPLIT(512, 0); else if (ca.variant == 1) FQL_CHAIN_SPLIT(512, 1); else FQL_CHAIN_SPLIT(512, 2); }
@@ -5874,6 +5885,80 @@ extern "C" int fql_debug_enc(fql_handle h, int enc, int code, void* out, size_t 
     if (it == b->bytes.end() || bytes > it->second) return FQL_E_INVALID;
     hipDeviceSynchronize();
     return hipMemcpy(out, src, bytes, hipMemcpyDeviceToHost) == hipSuccess ? FQL_OK : FQL_E_HIP;
+}
+
+// Diagnostic only (not in include/fql_amd.h): what the update program (prog_full) of a state agent will launch, as int32 words.  Nothing is
+// launched and no state changes: the launches come from record_dispatches (issue() recording what it would hand to the runtime), the tasks
+// from the host copies of the tables schedule() uploaded.  Layout:
+//   [words in the plan (this one included), launches], then per launch
+//   [index, lane, op type, grid (workgroups), kernel entry, GEMM tasks g, weight-gradient tasks w, LayerNorm-backward tasks l, chain records c (0 / 1)]
+//   g x [M, N, K, rows per tile, column tiles per wave (wk), xg]     w x [M, Kin, N, split body (0 / 1)]     l x [M]
+//   c x [M, H, variant, xg, split (0 / 1)]
+// kernel entry: 0 = the launch's only kernel, named by its op type; 1 / 2 fql_gemm16_kernel<false / true>; 3 / 4 fql_gemm16_euler_kernel<false / true>;
+// 5 fql_side_kernel; 6 fql_side_split_kernel; 7 fql_side_big_kernel; 8 fql_chain_kernel<H, variant>; 9 fql_chain_split_kernel<H, variant> - found by
+// the address of the recorded kernel, so H, variant and `split` of a chain record are those of the instantiation dispatched, and M and xg are read from
+// the ChainArgs recorded with it.  Rows per tile: 16 in an OP_GEMM launch, 32 tmt in an OP_GEMM64 launch.
+// The first `bytes` bytes of the plan are copied out (4 bytes give its size): a request larger than the plan is FQL_E_INVALID.  Refused with
+// FQL_E_STATE: a visual handle (its update is led by HIP launches that are not in prog_full), and a handle that holds no update program (the last
+// fql_set_batch_size failed halfway).  Every agent kind builds a prog_full, so no kind is refused.
+namespace {
+enum { PLAN_K_OTHER = 0, PLAN_K_GEMM16, PLAN_K_GEMM16_KBIG, PLAN_K_GEMM16_EULER, PLAN_K_GEMM16_EULER_KBIG, PLAN_K_SIDE, PLAN_K_SIDE_SPLIT, PLAN_K_SIDE_BIG,
+       PLAN_K_CHAIN, PLAN_K_CHAIN_SPLIT };
+struct PlanKernel { const void* fn; int entry, H, V; };
+template <typename... Pm> const void* plan_fn(void (*k)(Pm...)) { return (const void*)k; }   // the address issue() records (aql_record)
+const std::vector<PlanKernel>& plan_kernels() {
+#define FQL_PLAN_CHAIN(HH) \
+    {plan_fn(fql_chain_kernel<HH, 0>), PLAN_K_CHAIN, HH, 0}, {plan_fn(fql_chain_kernel<HH, 1>), PLAN_K_CHAIN, HH, 1},                    \
+    {plan_fn(fql_chain_kernel<HH, 2>), PLAN_K_CHAIN, HH, 2}, {plan_fn(fql_chain_kernel<HH, 3>), PLAN_K_CHAIN, HH, 3},                    \
+    {plan_fn(fql_chain_split_kernel<HH, 0>), PLAN_K_CHAIN_SPLIT, HH, 0}, {plan_fn(fql_chain_split_kernel<HH, 1>), PLAN_K_CHAIN_SPLIT, HH, 1}, \
+    {plan_fn(fql_chain_split_kernel<HH, 2>), PLAN_K_CHAIN_SPLIT, HH, 2}
+    static const std::vector<PlanKernel> t = {
+        {plan_fn(fql_gemm16_kernel<false>), PLAN_K_GEMM16, 0, 0}, {plan_fn(fql_gemm16_kernel<true>), PLAN_K_GEMM16_KBIG, 0, 0},
+        {plan_fn(fql_gemm16_euler_kernel<false>), PLAN_K_GEMM16_EULER, 0, 0}, {plan_fn(fql_gemm16_euler_kernel<true>), PLAN_K_GEMM16_EULER_KBIG, 0, 0},
+        {plan_fn(fql_side_kernel), PLAN_K_SIDE, 0, 0}, {plan_fn(fql_side_split_kernel), PLAN_K_SIDE_SPLIT, 0, 0},
+        {plan_fn(fql_side_big_kernel), PLAN_K_SIDE_BIG, 0, 0}, FQL_PLAN_CHAIN(256), FQL_PLAN_CHAIN(512)};
+#undef FQL_PLAN_CHAIN
+    return t;
+}
+}  // namespace
+extern "C" int fql_debug_plan(fql_handle h, void* out, size_t bytes) {
+    if (!h || (bytes && !out) || bytes % sizeof(int32_t)) return FQL_E_INVALID;
+    if (h->visual || !h->prog_full.exec || h->prog_full.launches.empty()) return FQL_E_STATE;
+    try {
+        const Program& pr = h->prog_full;
+        const std::vector<AqlDispatch> rec = h->record_dispatches(pr);
+        std::vector<int32_t> plan{0, (int32_t)pr.launches.size()};
+        for (size_t i = 0; i < pr.launches.size(); ++i) {
+            const Launch& L = pr.launches[i];
+            const AqlDispatch& d = rec[i];
+            PlanKernel k{d.fn, PLAN_K_OTHER, 0, 0};
+            for (const PlanKernel& c : plan_kernels()) if (c.fn == d.fn) k = c;
+            const bool table = L.type == OP_GEMM || L.type == OP_GEMM64;   // (other launches keep no task table)
+            const bool chain = L.type == OP_CHAIN;
+            if (chain != (k.entry == PLAN_K_CHAIN || k.entry == PLAN_K_CHAIN_SPLIT)) throw HipError{"internal: a chain launch records an unknown kernel"};
+            if (table == (k.entry == PLAN_K_OTHER || chain)) throw HipError{"internal: a GEMM launch records an unknown kernel"};
+            plan.insert(plan.end(), {(int32_t)i, L.lane, (int32_t)L.type, (int32_t)(d.grid[0] * d.grid[1] * d.grid[2]), k.entry,
+                                     table ? (int32_t)L.h_gemm.size() : 0, table ? (int32_t)L.h_wgrad.size() : 0, table ? (int32_t)L.h_ln.size() : 0,
+                                     chain ? 1 : 0});
+            if (table) {
+                for (const GemmTask& t : L.h_gemm) plan.insert(plan.end(), {t.M, t.N, t.K, (L.type == OP_GEMM ? 16 : 32) * t.tmt, t.wk, t.xg});
+                for (const WgradTask& t : L.h_wgrad) plan.insert(plan.end(), {t.M, t.Kin, t.N, k.entry == PLAN_K_SIDE_SPLIT ? 1 : 0});
+                for (const LnBwdTask& t : L.h_ln) plan.push_back(t.M);
+            }
+            if (chain) {
+                ChainArgs ca;
+                if (d.args.size() < sizeof(ChainArgs)) throw HipError{"internal: a chain launch records no ChainArgs"};
+                std::memcpy(&ca, d.args.data(), sizeof(ChainArgs));
+                plan.insert(plan.end(), {ca.M, k.H, k.V, ca.xg, k.entry == PLAN_K_CHAIN_SPLIT ? 1 : 0});
+            }
+        }
+        plan[0] = (int32_t)plan.size();
+        if (bytes > plan.size() * sizeof(int32_t)) return FQL_E_INVALID;
+        if (bytes) std::memcpy(out, plan.data(), bytes);
+        return FQL_OK;
+    } catch (...) {
+        return FQL_E_HIP;
+    }
 }
 
 int fql_dataset_upload_frames(fql_handle h, int64_t n, const uint8_t* frames, const uint8_t* next_frames, const float* act,

@@ -6,7 +6,7 @@ import numpy as np
 import pytest
 
 from oracle import fql_oracle as O
-from tests.util import make_problem, randomize_params, leaf_dict
+from tests.util import K_SIDE_BIG, make_problem, randomize_params, leaf_dict, read_plan
 
 pytestmark = pytest.mark.gpu
 
@@ -85,8 +85,13 @@ PATHS = [
 
 
 @pytest.mark.parametrize('od, ad, B, hidden, kw, K, n', PATHS)
-def test_group_equals_standalone_twins_on_every_path(od, ad, B, hidden, kw, K, n):
+def test_group_equals_standalone_twins_on_every_path(od, ad, B, hidden, kw, K, n, request):
     cfg, ds, batch, noise, group, twins = _setup(K, B, hidden, od=od, ad=ad, scale=0.05 if max(hidden) >= 512 else 0.1, **kw)
+    if request.node.callspec.id == 'b1024_big_tiles':
+        # a fused table launch is member 0's launch over the members' concatenated tables (fql_group_s::zip), dispatched by the member's
+        # own issue(): the kernel in the member's plan is the kernel the group runs
+        for m in group.members:
+            assert any(L['kernel'] == K_SIDE_BIG and any(t['rows'] == 64 and t['M'] == B for t in L['gemm']) for L in read_plan(m))
     for _ in range(n):
         group.update_from_dataset()
         for t in twins:

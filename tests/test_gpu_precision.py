@@ -14,7 +14,7 @@ import numpy as np
 import pytest
 
 from oracle import fql_oracle as O
-from tests.util import leaf_dict, make_problem, randomize_params
+from tests.util import bf16x3_update_errors, leaf_dict, make_problem, randomize_params
 
 pytestmark = pytest.mark.gpu
 
@@ -30,16 +30,7 @@ def _one_update(od, ad, B, hidden, alpha, precision, **kw):
     params = randomize_params(agent.get_params(), seed=9, scale=0.05)
     agent.set_params(params)
     ref = O.OracleFQL(params, dict(cfg), od, ad, np.float64)
-    _, _, g_ref = ref.grads(batch, noise)
-    _, info = agent.update(batch, noise=noise)
-    _, info_r = ref.update(batch, noise)
-    mu = leaf_dict(agent.get_opt_state()['mu'])
-    worst = (0.0, None)
-    for p, g in leaf_dict(g_ref).items():
-        sc = np.abs(g).max()
-        worst = max(worst, (float(np.abs(mu[p] / 0.1 - g).max() / max(sc, 1e-30)), p))
-    deltas = {k: abs(float(info[k]) - float(info_r[k])) / max(1.0, abs(float(info_r[k]))) for k in O.INFO_KEYS}
-    return worst, deltas
+    return bf16x3_update_errors(agent, ref, batch, noise)
 
 
 CASES = [

@@ -15,8 +15,8 @@ import numpy as np
 import pytest
 
 from oracle import fql_oracle as O
-from tests.util import (assert_same_state, assert_step_matches, assert_total_loss_matches, assert_trajectory_tracks_oracle, make_problem,
-                        randomize_params)
+from tests.util import (K_GEMM16_KBIG, OP_CHAIN, assert_same_state, assert_step_matches, assert_total_loss_matches,
+                        assert_trajectory_tracks_oracle, make_problem, randomize_params, read_plan)
 
 pytestmark = pytest.mark.gpu
 
@@ -32,6 +32,16 @@ CASES = [
 ]
 
 
+# the path a case's id names, asserted from the engine's plan (fql_debug_plan) before any number is compared
+PATH = {
+    'act15_chain': lambda plan: any(L['type'] == OP_CHAIN for L in plan),
+    'act16_generic': lambda plan: not any(L['type'] == OP_CHAIN for L in plan),
+    'humanoidmaze': lambda plan: not any(L['type'] == OP_CHAIN for L in plan),
+    'wide1024': lambda plan: any(L['kernel'] == K_GEMM16_KBIG for L in plan),
+    'obs600': lambda plan: any(L['kernel'] == K_GEMM16_KBIG for L in plan),
+}
+
+
 def _setup(od, ad, B, hidden, kw, seed=3):
     import fql_amd
     cfg, ds, batch, noise = make_problem(od, ad, B, hidden, seed=seed, **kw)
@@ -42,8 +52,10 @@ def _setup(od, ad, B, hidden, kw, seed=3):
 
 
 @pytest.mark.parametrize('od,ad,B,hidden,kw', CASES)
-def test_total_loss_and_update_match_oracle(od, ad, B, hidden, kw):
+def test_total_loss_and_update_match_oracle(od, ad, B, hidden, kw, request):
     cfg, batch, noise, agent, params = _setup(od, ad, B, hidden, kw)
+    on_path = PATH.get(request.node.callspec.id)
+    assert on_path is None or on_path(read_plan(agent)), request.node.callspec.id
     ref = O.OracleFQL(params, dict(cfg), od, ad, np.float64)
     assert_total_loss_matches(agent, ref, params, batch, noise)
     worst = assert_step_matches(agent, ref, cfg, batch, noise)

@@ -98,6 +98,70 @@ def assert_step_matches(agent, ref, cfg, batch, noise, step=None):
     return worst
 
 
+def bf16x3_update_errors(agent, ref, batch, noise):
+    """One update on both sides in the form test_gpu_precision.py bounds at 1e-4: (worst |g_gpu - g_ref| / max|g_ref| over the leaves and
+    its leaf, {info: |delta| / max(1, |ref|)})."""
+    _, _, g_ref = ref.grads(batch, noise)
+    _, info = agent.update(batch, noise=noise)
+    _, info_r = ref.update(batch, noise)
+    mu = leaf_dict(agent.get_opt_state()['mu'])
+    worst = (0.0, None)
+    for p, g in leaf_dict(g_ref).items():
+        sc = np.abs(g).max()
+        worst = max(worst, (float(np.abs(mu[p] / 0.1 - g).max() / max(sc, 1e-30)), p))
+    deltas = {k: abs(float(info[k]) - float(info_r[k])) / max(1.0, abs(float(info_r[k]))) for k in O.INFO_KEYS}
+    return worst, deltas
+
+
+BF16X3_BOUND = 1e-4          # both bounds of the bf16x3 mode: every info (BASELINE.json's "losses within 1e-4") and every leaf's gradient
+
+# fql_debug_plan's kernel entries and the op types its records name (fql_amd/csrc/fql_engine.hip: the PLAN_K_* codes, enum OpType)
+K_OTHER, K_GEMM16, K_GEMM16_KBIG, K_GEMM16_EULER, K_GEMM16_EULER_KBIG, K_SIDE, K_SIDE_SPLIT, K_SIDE_BIG, K_CHAIN, K_CHAIN_SPLIT = range(10)
+OP_GEMM, OP_GEMM64, OP_CHAIN = 0, 1, 20
+
+
+def plan_lib():
+    import ctypes as C
+    from fql_amd import _cabi
+    lib = _cabi.load()
+    lib.fql_debug_plan.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+    lib.fql_debug_plan.restype = C.c_int
+    return lib
+
+
+def read_plan(agent):
+    """The update program of a state agent as the engine would launch it (the diagnostic export fql_debug_plan): a list of launches
+    {index, lane, type, grid, kernel, gemm: [{M, N, K, rows, wk, xg}], wgrad: [{M, Kin, N, split}], ln: [M], chain: {M, H, variant, xg,
+    split} or None}."""
+    lib = plan_lib()
+    head = np.zeros(1, np.int32)
+    rc = lib.fql_debug_plan(agent._h, head.ctypes.data, 4)
+    assert rc == 0, rc
+    w = np.zeros(int(head[0]), np.int32)
+    rc = lib.fql_debug_plan(agent._h, w.ctypes.data, w.nbytes)
+    assert rc == 0, rc
+    w = [int(v) for v in w]
+    at, out = 2, []
+    for _ in range(w[1]):
+        index, lane, ty, grid, kernel, ng, nw, nl, nc = w[at:at + 9]
+        at += 9
+        L = dict(index=index, lane=lane, type=ty, grid=grid, kernel=kernel, gemm=[], wgrad=[], ln=[], chain=None)
+        for _ in range(ng):
+            L['gemm'].append(dict(zip(('M', 'N', 'K', 'rows', 'wk', 'xg'), w[at:at + 6])))
+            at += 6
+        for _ in range(nw):
+            L['wgrad'].append(dict(zip(('M', 'Kin', 'N', 'split'), w[at:at + 4])))
+            at += 4
+        L['ln'] = w[at:at + nl]
+        at += nl
+        if nc:
+            L['chain'] = dict(zip(('M', 'H', 'variant', 'xg', 'split'), w[at:at + 5]))
+            at += 5
+        out.append(L)
+    assert at == len(w) and [L['index'] for L in out] == list(range(len(out)))
+    return out
+
+
 def assert_trajectory_tracks_oracle(od, ad, B, hidden, seed, steps=20, **cfgkw):
     """`steps` updates from the engine's own init on fresh rows and noise, against the fp32 oracle on the same sequence: the infos of
     every step within 2e-3 relative.  The optimizer counters advance once per update."""
