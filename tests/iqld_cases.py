@@ -16,8 +16,12 @@ MARGIN = 1e-3
 OD, AD = 29, 8
 
 
-def case(od=OD, ad=AD, H=64, nh=4, B=64, S=16, ov='binary_awr_loss', te=1, ln=1, seed=0, actor_hidden=None, cap_q=0.85):
-    return dict(od=od, ad=ad, H=H, nh=nh, B=B, S=S, ov=ov, te=te, ln=ln, seed=seed, actor_hidden=actor_hidden, cap_q=cap_q)
+def case(od=OD, ad=AD, H=64, nh=4, B=64, S=16, ov='binary_awr_loss', te=1, ln=1, seed=0, actor_hidden=None, cap_q=0.85, hidden=None):
+    """hidden: the critic's and the value net's widths (default (H,) * nh); actor_hidden: the actor's (default: the same)."""
+    c = dict(od=od, ad=ad, H=H, nh=nh, B=B, S=S, ov=ov, te=te, ln=ln, seed=seed, actor_hidden=actor_hidden, cap_q=cap_q)
+    if hidden is not None:   # (a case without it is the dict it always was: tests/golden/iqld records its case)
+        c['hidden'] = tuple(hidden)
+    return c
 
 
 # one update against the fp64 oracle: H 64 / B 64 for the three variants x both target_extraction values; the default shape; B 16 (the
@@ -39,12 +43,34 @@ SHAPES = {
 }
 STEP_KINDS = case(seed=50)
 SWITCH = [case(B=64, seed=60), case(B=16, seed=61), case(B=256, seed=62)]   # one agent, the batch and noise of each size
+# the shapes and batches at which the update's kernels change (tests/test_gpu_iqld.py::test_paths_match_fp64_restatement asserts each
+# path from the engine's plan): the 2B-row passes at M 2048 (b1024), 544 (b272) and 4128 (b2064-*), the weight kernel past its 2048-row
+# LDS stage (b2064-awr; b2064-binary with every positive weight tied), padded action width 32 and an actor in_p of 192 under hidden 512
+# (humanoidmaze), act == padded width 16 (act16), hidden 1024 (wide1024) and widths that differ layer to layer in both families (ragged)
+PATHS = {
+    'humanoidmaze': case(od=69, ad=21, H=512, B=256, seed=200),
+    'act16': case(ad=16, H=512, B=256, seed=220, ov='binary_softmax_loss'),
+    'b1024': case(od=40, ad=4, H=512, B=1024, seed=242, ov='binary'),
+    'b272': case(H=512, B=272, seed=261),
+    'b2064-awr': case(B=2064, seed=280),
+    'b2064-binary': case(B=2064, seed=300, ov='binary'),
+    'wide1024': case(H=1024, nh=2, B=48, seed=320),
+    'ragged': case(B=32, seed=340, ov='binary_softmax_loss', hidden=(48, 80, 64), actor_hidden=(128, 64, 96)),
+}
+# after the full update of these two: a critic-only and then an actor-only step on the batch and noise of these data seeds (the other
+# two update programs at those sizes)
+PATH_STEPS = {'humanoidmaze': (600, 620), 'b1024': (680, 700)}
+# one agent through these batch sizes, full updates: hidden 512 across M 512 -> 2048 -> 544 -> 512 of the 2B-row passes, and hidden 64 across
+# the weight kernel's 2048-row stage and back.  The first entry's seed builds the parameters, every entry's seed its own batch and noise.
+WALK512 = [case(H=512, B=256, seed=300), case(H=512, B=1024, seed=700), case(H=512, B=272, seed=730), case(H=512, B=256, seed=761)]
+WALK64 = [case(B=64, seed=340), case(B=2064, seed=805), case(B=64, seed=830)]
 TRAJECTORY = case(seed=470, cap_q=0.1)   # a high temperature: the value net learns and the advantages sink, rows still reach the cap at every step
 
 
 def config(c):
     cfg = DO.get_config()
-    cfg.update(actor_hidden_dims=tuple(c['actor_hidden'] or (c['H'],) * c['nh']), hidden_dims=(c['H'],) * c['nh'], batch_size=c['B'],
+    hidden = tuple(c.get('hidden') or (c['H'],) * c['nh'])
+    cfg.update(actor_hidden_dims=tuple(c['actor_hidden'] or hidden), hidden_dims=hidden, batch_size=c['B'],
                denoise_steps=c['S'], optimal_var=c['ov'], target_extraction=c['te'], use_layer_norm=c['ln'])
     return cfg
 
@@ -87,6 +113,8 @@ def all_cases():
     out['step-kinds'] = STEP_KINDS
     out['trajectory'] = TRAJECTORY
     out.update({f'switch-{c["B"]}': c for c in SWITCH})
+    out.update(PATHS)
+    out['walk512'], out['walk64'] = WALK512[0], WALK64[0]
     return out
 
 
@@ -98,17 +126,23 @@ def trajectory_kind(i):
 
 
 SAMPLER_HEAD_SCALE = 2.0
+# the sampler at the humanoidmaze shape (act 21: padded action width 32; hidden 512).  fp32 numpy at a head scale of 2 is 1.2e-5 from
+# fp64 at cfg 3 on these inputs, at 1 it is 4.6e-6; at 0.5 it is 2.5e-6, a factor of 2 inside the 5e-6 that
+# tests/test_iqld_cpu.py::test_fp32_rounding_of_the_cfg_sampler_at_hidden_512 asserts, and 38 % of the coordinates still end on the clip
+SAMPLER512 = case(od=69, ad=21, H=512, seed=81)
+SAMPLER512_HEAD_SCALE = 0.5
+SAMPLER512_N = (1, 37, 2049)
 
 
-def sampler_problem(scale=SAMPLER_HEAD_SCALE):
+def sampler_problem(scale=SAMPLER_HEAD_SCALE, c=None):
     """(cfg, params, None) of the sampler tests: randomized parameters with the head kernel scaled so that the clip is reached."""
-    c = case(seed=80)
+    c = c or case(seed=80)
     cfg = config(c)
     params = DO.randomize(DO.init_params(c['seed'], c['od'], c['ad'], cfg), c['seed'] + 1)
     params['actor']['Dense_0']['kernel'] = (params['actor']['Dense_0']['kernel'] * np.float32(scale)).astype(np.float32)
     return cfg, params, None
 
 
-def sampler_inputs(n):
+def sampler_inputs(n, od=OD, ad=AD):
     rng = np.random.default_rng(n)
-    return rng.standard_normal((n, OD)).astype(np.float32), rng.standard_normal((n, AD)).astype(np.float32)
+    return rng.standard_normal((n, od)).astype(np.float32), rng.standard_normal((n, ad)).astype(np.float32)

@@ -1,6 +1,18 @@
 """GPU: the BC agent (agents/bc.py) on the engine against the fp64 restatement in tests/bc_oracle.py.  Tolerances are the ones
 tests/test_gpu_ifql.py holds its agent to: infos rtol 5e-5 / atol 5e-6, per-leaf gradients (Adam mu / 0.1) within 2e-5 max|g| + 1e-9,
-sampled actions atol 2e-5."""
+sampled actions atol 2e-5.
+
+test_paths_match_fp64_restatement runs the first-update comparison at hidden 512 x 4 (wide1024: 1024 x 2) after asserting from the
+engine's plan (fql_debug_plan; [M, N, K] of a GEMM task, rows per tile) the launches the case is named for:
+  humanoidmaze (obs 69, act 21, B 256, with and without LayerNorm): layer 0 [256, 512, 128], head [256, 32, 512] and its dgrad
+      [256, 512, 32] on the 16-row kernel (padded action width 32), weight gradients (M, Kin, N) = (256, 128, 512) and (256, 512, 32)
+  act16 (obs 29, act 16, B 256): head [256, 16, 512], dgrad [256, 512, 16], no task 32 wide
+  b1024 (obs 40, act 4): every 512 x 512 task on fql_side_big_kernel's 64-row tiles at M 1024
+  b272 (obs 29, act 8): every task at M 272 on fql_gemm16_kernel<false> (16 rows)
+  wide1024 (B 48): every K 1024 task on fql_gemm16_kernel<true>: [48, 1024, 1024] and the head [48, 16, 1024]
+No plan holds an OP_DGRAD0 launch or a dgrad with N = in_p: BC takes no input gradient of layer 0, at any action width.  Measured on an
+MI355X, worst |g_gpu - g_ref| / max|g_ref| over the leaves (figures, not bounds): humanoidmaze 1.1e-06, act16 1.1e-06, b1024 9.1e-07,
+b272 7.4e-07, wide1024 4.7e-07, humanoidmaze without LayerNorm 4.5e-07; the sampler at obs 69 / act 21 / hidden 512: 3.0e-06 at n 4097."""
 import ctypes as C
 
 import numpy as np
@@ -8,10 +20,12 @@ import pytest
 
 from oracle import fql_oracle as O
 from tests import bc_oracle as BO
-from tests.util import assert_info_close, leaf_dict, sync_restatement
+from tests.util import (K_GEMM16, K_GEMM16_KBIG, K_SIDE, K_SIDE_BIG, OP_GEMM, OP_GEMM64, assert_info_close, leaf_dict, read_plan,
+                        sync_restatement)
 
 pytestmark = pytest.mark.gpu
 OD, AD = 29, 8
+OP_DGRAD0 = 24   # enum OpType (fql_amd/csrc/fql_engine.hip): the lean 16-column first-layer input gradient
 
 
 def _cfg(H=64, B=64, nh=4, **kw):
@@ -288,6 +302,145 @@ def test_sample_actions_match_oracle_and_single_calls(n):
     assert a.sample_actions(obs[:1], noises=sn[:1]).shape == (AD,)   # [1, od] -> [act]: the reference's squeeze
     if n == 5:   # engine RNG: a seed fixes the draw, chunking does not change it
         np.testing.assert_array_equal(a.sample_actions(obs, seed=7), a.sample_actions(obs, seed=7))
+
+
+# ---- hidden 512 at the shapes and batches that switch kernels: what the update program's plan holds --------------------------------
+def _gemm(plan, kernels=None):
+    return [dict(t, kernel=L['kernel'], type=L['type']) for L in plan if kernels is None or L['kernel'] in kernels for t in L['gemm']]
+
+
+def _wgrad(plan):
+    return {(t['M'], t['Kin'], t['N']) for L in plan for t in L['wgrad']}
+
+
+def _has(tasks, M, N, K, **kw):
+    return [t for t in tasks if (t['M'], t['N'], t['K']) == (M, N, K) and all(t[k] == v for k, v in kw.items())]
+
+
+def _p_humanoidmaze(plan, B):
+    g = _gemm(plan)
+    assert not [L for L in plan if L['type'] == OP_DGRAD0]       # BC takes no first-layer input gradient, at any action width
+    assert _has(g, B, 512, 128)                                  # layer 0 at in_p 128 (69 + 21 + 16 = 106)
+    assert _has(g, B, 32, 512, rows=16, kernel=K_GEMM16)         # the head at the padded action width 32
+    assert _has(g, B, 512, 32)                                   # ... and its dgrad: K = 32
+    assert not [t for t in g if t['N'] == 128]                   # no first-layer dgrad
+    assert {(B, 128, 512), (B, 512, 32)} <= _wgrad(plan)
+
+
+def _p_act16(plan, B):
+    g = _gemm(plan)
+    assert not [L for L in plan if L['type'] == OP_DGRAD0]
+    assert _has(g, B, 16, 512, rows=16, kernel=K_GEMM16) and _has(g, B, 512, 16)   # act == padded width 16: no padding column
+    assert not [t for t in g if t['N'] == 32 or t['K'] == 32] and (B, 512, 16) in _wgrad(plan)
+
+
+def _p_b1024(plan, B):
+    hid = [t for t in _gemm(plan) if (t['N'], t['K']) == (512, 512)]
+    assert hid and all(t['M'] == B and t['rows'] == 64 and t['kernel'] == K_SIDE_BIG for t in hid)   # fql_side_big_kernel's 64-row tiles
+    assert (B, 512, 512) in _wgrad(plan) and B in {m for L in plan for m in L['ln']}
+
+
+def _p_b272(plan, B):
+    g = _gemm(plan)
+    assert g and all(t['M'] == B and t['rows'] == 16 and t['kernel'] == K_GEMM16 and t['type'] == OP_GEMM for t in g)   # M % 64 != 0
+    assert _has(g, B, 512, 512) and (B, 512, 512) in _wgrad(plan) and B in {m for L in plan for m in L['ln']}
+
+
+def _p_wide1024(plan, B):
+    kbig = [t for t in _gemm(plan) if t['K'] > 512]
+    assert kbig and all(t['kernel'] == K_GEMM16_KBIG and t['rows'] == 16 for t in kbig)
+    assert _has(kbig, B, 1024, 1024) and _has(kbig, B, 16, 1024) and (B, 1024, 1024) in _wgrad(plan)
+
+
+H512_CASES = {   # id -> (od, ad, hidden, B, S, use_layer_norm, plan assertion)
+    'humanoidmaze': (69, 21, (512,) * 4, 256, 16, 1, _p_humanoidmaze),
+    'act16': (29, 16, (512,) * 4, 256, 16, 1, _p_act16),
+    'b1024': (40, 4, (512,) * 4, 1024, 16, 1, _p_b1024),
+    'b272': (29, 8, (512,) * 4, 272, 16, 1, _p_b272),
+    'wide1024': (29, 8, (1024,) * 2, 48, 16, 1, _p_wide1024),
+    'humanoidmaze-no-ln': (69, 21, (512,) * 4, 256, 16, 0, _p_humanoidmaze),
+}
+
+
+@pytest.mark.parametrize('cid', list(H512_CASES))
+def test_paths_match_fp64_restatement(cid):
+    """Each case first asserts, from the engine's own plan (fql_debug_plan), the path its id names, then runs _check_first_update at its
+    bounds.  fql_bc_prep_kernel is one entry in the plan; it writes vel at the padded action stride (32 at humanoidmaze)."""
+    od, ad, hidden, B, S, ln, check = H512_CASES[cid]
+    cfg = _cfg(B=B, hidden_dims=hidden, denoise_steps=S, use_layer_norm=ln)
+    batch, noise = _data(od, ad, B, S, seed=40 + od + ad)
+    a = _agent(cfg, od, ad)
+    plan = read_plan(a)
+    print(cid, 'gemm (kernel, type, M, N, K, rows):', sorted({(t['kernel'], t['type'], t['M'], t['N'], t['K'], t['rows']) for t in _gemm(plan)}))
+    print(cid, 'wgrad (M, Kin, N):', sorted(_wgrad(plan)), 'ln M:', sorted({m for L in plan for m in L['ln']}),
+          'other launch types:', sorted({L['type'] for L in plan if L['type'] not in (OP_GEMM, OP_GEMM64)}))
+    check(plan, B)
+    _check_first_update(a, cfg, od, ad, batch, noise)
+    check(read_plan(a), B)   # reading the plan changed no launch
+
+
+def test_batch_size_walk_at_hidden_512():
+    """B = 256, 1024, 272, 256 on one hidden-512 handle: 32-row tiles, fql_side_big_kernel's 64-row tiles, the 16-row kernel, and back.
+    The rebuilt plan holds the new row count only; every step is compared from the engine's own pre-step state."""
+    cfg = _cfg(512, 256)
+    a = _agent(cfg)
+    params = _randomized(a.get_params(), 16)
+    a.set_params(params)
+    ref = BO.OracleBC(params, dict(cfg), OD, AD, np.float64)
+    tiles = {256: (32, K_SIDE), 1024: (64, K_SIDE_BIG), 272: (16, K_GEMM16)}
+    for i, B in enumerate((256, 1024, 272, 256)):
+        batch, noise = _data(OD, AD, B, 16, seed=50 + i)
+        assert a.get_opt_state()['count'] == i
+        _check_step(a, ref, cfg, batch, noise)
+        plan = read_plan(a)
+        assert {t['M'] for t in _gemm(plan)} == {B} == {M for M, _, _ in _wgrad(plan)}
+        hid = _has(_gemm(plan), B, 512, 512)
+        assert hid and {(t['rows'], t['kernel']) for t in hid} == {tiles[B]}
+    assert a.get_opt_state()['count'] == 4
+
+
+SAMPLER512 = dict(od=69, ad=21, hidden=(512,) * 4, scale=2.0, ns=(1, 37, 4097))
+
+
+def sampler512_problem(scale=SAMPLER512['scale']):
+    """(cfg, params) of the sampler at the humanoidmaze shape (act 21: fql_bc_layer0_kernel strides the action rows by the padded width
+    32, and the head's GF_EULER | GF_EULER_BARE epilogue adds into rows of that stride), hidden 512, the head scaled by 2 as above.
+    tests/test_bc_cpu.py::test_fp32_rounding_of_the_sampler_at_hidden_512 holds fp32 numpy to 5e-6 of fp64 on these inputs."""
+    cfg = _cfg(hidden_dims=SAMPLER512['hidden'], batch_size=256)
+    params = _randomized(BO.init_params(8, SAMPLER512['od'], SAMPLER512['ad'], cfg), 8)
+    params['Dense_0']['kernel'] *= np.float32(scale)
+    return cfg, params
+
+
+def sampler512_inputs(n):
+    rng = np.random.default_rng(n)
+    return rng.standard_normal((n, SAMPLER512['od'])).astype(np.float32), rng.standard_normal((n, SAMPLER512['ad'])).astype(np.float32)
+
+
+@pytest.fixture(scope='module')
+def sampler512():
+    cfg, params = sampler512_problem()
+    od, ad = SAMPLER512['od'], SAMPLER512['ad']
+    return _agent(cfg, od, ad, params=params), BO.OracleBC(params, dict(cfg), od, ad, np.float64)
+
+
+@pytest.mark.parametrize('n', SAMPLER512['ns'])
+def test_sample_actions_at_hidden_512_and_padded_action_width_32(sampler512, n):
+    """n = 1, 37 and 4097 (one row past the 4096-row chunk) against the restatement at 2e-5; the clip is reached; rows 0, n // 2 and n - 1
+    are bitwise the single-observation calls."""
+    a, ref = sampler512
+    ad = SAMPLER512['ad']
+    obs, sn = sampler512_inputs(n)
+    got = a.sample_actions(obs, noises=sn)
+    want = ref.sample_actions(obs, sn)
+    assert got.shape == ((ad,) if n == 1 else (n, ad)) == want.shape
+    print('n', n, 'max err', float(np.abs(got - want).max()), 'saturated', int((np.abs(want) == 1).sum()))
+    np.testing.assert_allclose(got, want, rtol=0, atol=2e-5)
+    assert (np.abs(want) == 1).any() and (np.abs(got) == 1).any() and (np.abs(got) <= 1).all()
+    for j in sorted({0, n // 2, n - 1}):
+        one = a.sample_actions(obs[j], noises=sn[j])
+        assert one.shape == (ad,)
+        np.testing.assert_array_equal(one, got.reshape(n, ad)[j])
 
 
 def test_checkpoint_round_trip_is_bitwise(tmp_path):

@@ -4,7 +4,24 @@ hold their agents to: infos rtol 5e-5 / atol 5e-6, per-leaf gradients (from Adam
 2e-5, a 100-update trajectory within 2e-3 relative (infos) and 5e-3 (parameters).
 
 The loss weights are discontinuous at adv = 0 and kinked at adv awr_temperature = ln 100: every compared step first asserts, on the
-fp64 values, that every row keeps 1e-3 from both (iqld_cases.check_margins); no row is masked out of a comparison."""
+fp64 values, that every row keeps 1e-3 from both (iqld_cases.check_margins); no row is masked out of a comparison.
+
+iqld_cases.PATHS run one update each at the shapes and batches where the kernels change, after asserting from the engine's plan
+(fql_debug_plan, tests/util.py read_plan; [M, N, K] of a GEMM task, rows per tile) the launches the case is named for:
+  humanoidmaze  obs 69, act 21, 512 x 4, B 256: actor layer 0 [512, 512, 192] (in_p 192), head [512, 32, 512] and its dgrad [512, 512, 32]
+                on the 16-row kernel (padded action width 32), weight gradients (M, Kin, N) = (512, 192, 512) and (512, 512, 32)
+  act16         obs 29, act 16, 512 x 4, B 256: head [512, 16, 512], dgrad [512, 512, 16], no task 32 wide (no padding column)
+  b1024         obs 40, act 4, 512 x 4, B 1024: every 512 x 512 task on fql_side_big_kernel's 64-row tiles, at M 2048 and M 1024
+  b272          512 x 4, B 272: M 544 and 272 only, every task on fql_gemm16_kernel<false> (16 rows, K <= 512)
+  b2064-*       64 x 4, B 2064: M 4128 and 2064 only, every task on fql_gemm16_kernel<false>
+  wide1024      1024 x 2, B 48: every K 1024 task on fql_gemm16_kernel<true>, [M, 1024, 1024] and the heads [M, 16, 1024] at M 48 and 96
+  ragged        critic / value (48, 80, 64), actor (128, 64, 96), B 32: [M, 80, 48], [M, 64, 80], [M, 16, 64] at M 32 and 64; [64, 64, 128],
+                [64, 96, 64], [64, 16, 96]
+No plan holds an OP_DGRAD0 launch or a first-layer dgrad (N = in_p): this agent takes no input gradient of a layer 0, so the act_dim <= 16
+admission of OP_DGRAD0 is out of its reach at act 16 and at act 21 alike, and the cases assert that absence.  Every case landed where
+reading the selection code had placed it.  Measured on an MI355X, worst |g_gpu - g_ref| / max|g_ref| over the leaves of the first update
+(figures, not bounds): humanoidmaze 3.6e-06, act16 1.0e-06, b1024 1.1e-06, b272 2.1e-06, b2064-awr 1.8e-06, b2064-binary 5.1e-07,
+wide1024 3.9e-06, ragged 2.3e-06; the sampler at obs 69 / act 21 / hidden 512: 6.1e-07 (cfg 0) and 1.3e-06 (cfg 3) at n 2049."""
 import ctypes as C
 
 import numpy as np
@@ -13,13 +30,14 @@ import pytest
 from oracle import fql_oracle as O
 from tests import iqld_cases as K
 from tests import iqld_oracle as DO
-from tests.util import leaf_dict
+from tests.util import K_GEMM16, K_GEMM16_KBIG, K_SIDE, K_SIDE_BIG, OP_GEMM, OP_GEMM64, leaf_dict, read_plan
 from fql_amd.iql_diffusion import info_keys, IQLD_INFO_KEYS, IQLD_ROW_KEYS
 
 pytestmark = pytest.mark.gpu
 OD, AD = K.OD, K.AD
 NETS = ('actor', 'critic', 'value')
 KINDS = [(True, True), (True, False), (False, True)]
+OP_DGRAD0 = 24   # enum OpType (fql_amd/csrc/fql_engine.hip): the lean 16-column first-layer input gradient
 
 
 def _agent(cfg, od=OD, ad=AD, seed=3, params=None):
@@ -167,6 +185,162 @@ def test_batch_size_switches_track_restatement():
         batch, noise = K.data(c)
         assert a.get_opt_state()['updates'] == i
         _check_step(a, ref, cfg, batch, noise)
+
+
+# ---- the shapes and batches that switch kernels (iqld_cases.PATHS): what the update program's plan holds ----------------------------
+def _gemm(plan, kernels=None):
+    return [dict(t, kernel=L['kernel'], type=L['type']) for L in plan if kernels is None or L['kernel'] in kernels for t in L['gemm']]
+
+
+def _wgrad(plan):
+    return [t for L in plan for t in L['wgrad']]
+
+
+def _has(tasks, M, N, K, **kw):
+    return [t for t in tasks if (t['M'], t['N'], t['K']) == (M, N, K) and all(t[k] == v for k, v in kw.items())]
+
+
+def _print_plan(name, plan):
+    seen = sorted({(t['kernel'], t['type'], t['M'], t['N'], t['K'], t['rows']) for t in _gemm(plan)})
+    print(name, 'gemm (kernel, type, M, N, K, rows):', seen)
+    print(name, 'wgrad (M, Kin, N):', sorted({(t['M'], t['Kin'], t['N']) for t in _wgrad(plan)}), 'ln M:', sorted({m for L in plan for m in L['ln']}),
+          'other launch types:', sorted({L['type'] for L in plan if L['type'] not in (OP_GEMM, OP_GEMM64)}))
+
+
+def _assert_no_dgrad0(plan):
+    """This agent takes no first-layer input gradient: the embedding gradient is formed from dZ0 (fql_iqld_embed_grad_kernel) and the
+    critic's dQ/da is not read, so neither OP_DGRAD0 nor a generic first-layer dgrad (N = in_p) is in the plan at any action width."""
+    assert not [L for L in plan if L['type'] == OP_DGRAD0]
+
+
+def _assert_rows16_only(plan, kernel=K_GEMM16):
+    g = _gemm(plan)
+    assert g and all(t['rows'] == 16 and t['kernel'] == kernel and t['type'] == OP_GEMM for t in g), sorted({(t['kernel'], t['rows']) for t in g})
+
+
+def _p_humanoidmaze(plan, c):
+    B = c['B']
+    _assert_no_dgrad0(plan)
+    g = _gemm(plan)
+    assert _has(g, 2 * B, 512, 192)                              # the actor's layer 0 at in_p 192 (69 + 21 + 16 + 32 = 138)
+    assert _has(g, 2 * B, 32, 512, rows=16, kernel=K_GEMM16)     # its head at the padded action width 32
+    assert _has(g, 2 * B, 512, 32)                               # the head's dgrad: K = 32
+    assert not [t for t in g if t['N'] == 192 or (t['N'] == 128 and t['K'] == 512)]   # no first-layer dgrad of any net
+    w = {(t['M'], t['Kin'], t['N']) for t in _wgrad(plan)}
+    assert (2 * B, 192, 512) in w and (2 * B, 512, 32) in w, sorted(w)
+
+
+def _p_act16(plan, c):
+    B = c['B']
+    _assert_no_dgrad0(plan)
+    g = _gemm(plan)
+    assert _has(g, 2 * B, 16, 512, rows=16, kernel=K_GEMM16)     # the head at act == padded width 16: no padding column
+    assert _has(g, 2 * B, 512, 16) and not [t for t in g if t['N'] == 32 or t['K'] == 32]
+    assert _has(g, 2 * B, 512, 128)                              # layer 0 at in_p 128 (29 + 16 + 48 = 93)
+    assert (2 * B, 512, 16) in {(t['M'], t['Kin'], t['N']) for t in _wgrad(plan)}
+
+
+def _p_b1024(plan, c):
+    B = c['B']
+    big = _gemm(plan, (K_SIDE_BIG,))
+    assert _has(big, 2 * B, 512, 512, rows=64) and _has(big, B, 512, 512, rows=64)   # fql_side_big_kernel's 64-row tiles at M 2048 and 1024
+    hid = [t for t in _gemm(plan) if (t['N'], t['K']) == (512, 512)]
+    assert hid and all(t['rows'] == 64 and t['kernel'] == K_SIDE_BIG for t in hid)
+    assert {t['M'] for t in _wgrad(plan)} == {B, 2 * B} and 2 * B in {m for L in plan for m in L['ln']}
+
+
+def _p_b272(plan, c):
+    B = c['B']
+    _assert_rows16_only(plan)                                    # M 544 and 272: no multiple of 64, every GEMM on the 16-row kernel at K <= 512
+    g = _gemm(plan)
+    assert _has(g, 2 * B, 512, 512) and _has(g, B, 512, 512) and {t['M'] for t in g} == {B, 2 * B}
+    assert {t['M'] for t in _wgrad(plan)} == {B, 2 * B} and 2 * B in {m for L in plan for m in L['ln']}
+    assert (2 * B) // 16 == 34 and B % 256 == 16
+
+
+def _p_b2064(plan, c):
+    B = c['B']
+    _assert_rows16_only(plan)                                    # M 4128 and 2064 (no multiple of 64): the 16-row fallback above 1024 rows
+    g = _gemm(plan)
+    assert _has(g, 2 * B, 64, 64) and _has(g, B, 64, 64) and {t['M'] for t in g} == {B, 2 * B}
+    assert {t['M'] for t in _wgrad(plan)} == {B, 2 * B}
+    assert B > 2048 and B % 256 == 16
+
+
+def _p_wide1024(plan, c):
+    B = c['B']
+    g = _gemm(plan)
+    kbig = [t for t in g if t['K'] > 512]
+    assert kbig and all(t['kernel'] == K_GEMM16_KBIG and t['rows'] == 16 for t in kbig)
+    for M in (B, 2 * B):                                         # critic (B rows), value and actor (2B rows): hidden layer and head
+        assert _has(kbig, M, 1024, 1024)
+    assert _has(kbig, 2 * B, 16, 1024) and _has(kbig, B, 16, 1024)
+    assert {(2 * B, 1024, 1024), (B, 1024, 1024)} <= {(t['M'], t['Kin'], t['N']) for t in _wgrad(plan)}
+
+
+def _p_ragged(plan, c):
+    B = c['B']
+    g = _gemm(plan)
+    for M in (B, 2 * B):                                         # critic on B rows, value on 2B: 48 -> 80 -> 64
+        assert _has(g, M, 80, 48) and _has(g, M, 64, 80) and _has(g, M, 16, 64)
+    assert _has(g, 2 * B, 64, 128) and _has(g, 2 * B, 96, 64) and _has(g, 2 * B, 16, 96)   # the actor: 128 -> 64 -> 96 -> act
+    assert {(2 * B, 64, 96), (2 * B, 128, 64), (B, 48, 80), (B, 80, 64)} <= {(t['M'], t['Kin'], t['N']) for t in _wgrad(plan)}
+
+
+PATH_PLAN = {'humanoidmaze': _p_humanoidmaze, 'act16': _p_act16, 'b1024': _p_b1024, 'b272': _p_b272, 'b2064-awr': _p_b2064,
+             'b2064-binary': _p_b2064, 'wide1024': _p_wide1024, 'ragged': _p_ragged}
+PATH_TOPK = {'humanoidmaze': 25, 'act16': 25, 'b1024': 102, 'b272': 27, 'b2064-awr': 206, 'b2064-binary': 206, 'wide1024': 4, 'ragged': 3}
+
+
+@pytest.mark.parametrize('name', list(K.PATHS))
+def test_paths_match_fp64_restatement(name):
+    """Each case first asserts, from the engine's own plan (fql_debug_plan), the path its id names, then runs one full update through
+    _check_step at its bounds.  The agent's own kernels are one entry in the plan (K_OTHER); their branches follow from B and the code:
+    fql_iqld_weight_kernel reads the weights from global memory when B > 2048 (b2064-*), its loops and those of the two loss kernels
+    run B / 256 rows per thread with a strided tail of 16 rows at B 272 and 2064 and four rows per thread at B 1024, and
+    fql_iqld_embed_grad_kernel fills cs[H] in H / 256 strides (four at wide1024).  humanoidmaze and b1024 go on with a critic-only and an
+    actor-only step on fresh rows: the other two programs at those sizes."""
+    c = K.PATHS[name]
+    cfg, params, batch, noise, ref, a = _built(c)
+    plan = read_plan(a)
+    _print_plan(name, plan)
+    PATH_PLAN[name](plan, c)
+    info = _check_step(a, ref, cfg, batch, noise)
+    w = np.asarray(info['loss_weights'])
+    assert w.shape == (c['B'],) and (w > 0).any() and (w == 0).any()
+    assert int(0.1 * c['B']) == PATH_TOPK[name]
+    if c['ov'] == 'binary_awr_loss':
+        assert (w == 100.0).any()
+    if name == 'b2064-binary':   # every positive weight is 1: the mass is 206 / (positive rows) only if exactly 206 tied rows are taken
+        pos = int((w == 1.0).sum())
+        assert pos > 206 and pos == int((w > 0).sum())
+        got = float(info['loss_weights_top_10_mass'])
+        print('top-10 mass', got, 206 / pos)
+        assert abs(got - 206 / pos) <= 5e-6 + 5e-5 * 206 / pos
+    for s, (uc, ua) in zip(K.PATH_STEPS.get(name, ()), ((True, False), (False, True))):
+        b, nz = K.data(c, seed=s)
+        _check_step(a, ref, cfg, b, nz, uc, ua)
+    PATH_PLAN[name](read_plan(a), c)   # reading the plan changed no launch
+
+
+@pytest.mark.parametrize('walk', ['walk512', 'walk64'])
+def test_batch_size_walks_across_kernel_switches(walk):
+    """One hidden-512 handle through B = 256, 1024, 272, 256 (the 2B-row passes on 32-row tiles, fql_side_big_kernel's 64-row tiles, the
+    16-row kernel, and back) and one hidden-64 handle through 64, 2064, 64 (across the weight kernel's 2048-row stage and back): each
+    switch rebuilds the workspace and the four programs; the rebuilt plan holds the new row counts only, and every step is compared from
+    the engine's own pre-step state."""
+    cases = K.WALK512 if walk == 'walk512' else K.WALK64
+    cfg, params, _, _, ref, a = _built(cases[0])
+    for i, c in enumerate(cases):
+        batch, noise = K.data(c)
+        assert a.get_opt_state()['updates'] == i
+        _check_step(a, ref, cfg, batch, noise)
+        plan = read_plan(a)
+        assert {t['M'] for t in _gemm(plan)} == {c['B'], 2 * c['B']} == {t['M'] for t in _wgrad(plan)}
+        if walk == 'walk512':
+            hid = [t for t in _gemm(plan) if (t['M'], t['N'], t['K']) == (2 * c['B'], 512, 512)]
+            assert hid and {(t['rows'], t['kernel']) for t in hid} == {{256: (32, K_SIDE), 1024: (64, K_SIDE_BIG), 272: (16, K_GEMM16)}[c['B']]}
+    assert a.get_steps() == {'updates': len(cases), 'critic': len(cases), 'actor': len(cases)}
 
 
 def test_step_kinds_against_restatement():
@@ -366,6 +540,36 @@ def test_sample_actions_match_oracle_and_single_calls(sampler, n):
     assert a.sample_actions(obs[:1], noises=sn[:1]).shape == (AD,)   # [1, od] -> [act]: the reference's squeeze
     if n == 5:   # engine RNG: a seed fixes the draw
         np.testing.assert_array_equal(a.sample_actions(obs, seed=7, cfg=1.5), a.sample_actions(obs, seed=7, cfg=1.5))
+
+
+@pytest.fixture(scope='module')
+def sampler512():
+    """The sampler at the humanoidmaze shape: obs 69, act 21 (fql_iqld_layer0_kernel and fql_iqld_cfg_step_kernel stride the action rows
+    by the padded width 32), hidden 512.  The head is scaled by K.SAMPLER512_HEAD_SCALE, where
+    tests/test_iqld_cpu.py::test_fp32_rounding_of_the_cfg_sampler_at_hidden_512 shows fp32 numpy within 5e-6 of fp64 on these inputs."""
+    c = K.SAMPLER512
+    cfg, params, _ = K.sampler_problem(K.SAMPLER512_HEAD_SCALE, c)
+    return _agent(cfg, c['od'], c['ad'], params=params), DO.OracleIQLD(params, cfg, c['od'], c['ad'], np.float64)
+
+
+@pytest.mark.parametrize('n', K.SAMPLER512_N)
+def test_sample_actions_at_hidden_512_and_padded_action_width_32(sampler512, n):
+    """n = 1, 37 and 2049 (one row past the 2048-observation chunk), cfg 0 and 3, against the restatement at 2e-5; the clip is reached;
+    rows 0, n // 2 and n - 1 are bitwise the single-observation calls."""
+    a, ref = sampler512
+    od, ad = K.SAMPLER512['od'], K.SAMPLER512['ad']
+    obs, sn = K.sampler_inputs(n, od, ad)
+    for cfg_scale in (0.0, 3.0):
+        got = a.sample_actions(obs, noises=sn, cfg=cfg_scale)
+        want = ref.sample_actions(obs, sn, cfg_scale)
+        assert got.shape == ((ad,) if n == 1 else (n, ad)) == want.shape
+        print('n', n, 'cfg', cfg_scale, 'max err', float(np.abs(got - want).max()), 'saturated', int((np.abs(want) == 1).sum()))
+        np.testing.assert_allclose(got, want, rtol=0, atol=2e-5)
+        assert (np.abs(want) == 1).any() and (np.abs(got) == 1).any() and (np.abs(got) <= 1).all()
+        for j in sorted({0, n // 2, n - 1}):
+            one = a.sample_actions(obs[j], noises=sn[j], cfg=cfg_scale)
+            assert one.shape == (ad,)
+            np.testing.assert_array_equal(one, got.reshape(n, ad)[j])
 
 
 def test_cfg_zero_ignores_the_positive_embedding_row(sampler):
