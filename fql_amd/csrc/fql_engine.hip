@@ -128,6 +128,8 @@ struct Leaf {
 // ------------------------------------------------------------------------------------------------
 // OP_WGRAD, OP_LNBWD, OP_POSTOS and the OP_LOSS_{CRITIC,Q,BC} ops ride in OP_GEMM64 (side-lane) launches, never in launches of their own.
 // OP_PEC and OP_XCHAIN are reserved (retired persistent Euler chains): the values index profile labels (bench.py OP_NAMES) and order launches.
+// An agent's types (OP_IFQL_PREP and later) are labels and sort keys only: their launches are bound where the ops are emitted (Bound, below),
+// so a new agent adds enum labels and emit sites, no payload member of Op and no case of issue().
 enum OpType { OP_GEMM, OP_GEMM64, OP_WGRAD, OP_LNBWD, OP_PREP, OP_POSTOS, OP_EULER_FIN, OP_PEC, OP_LOSS_CRITIC, OP_LOSS_Q, OP_LOSS_BC,
               OP_LOSS_ACTOR, OP_CONV_WPREP, OP_CONV, OP_CONV_U8, OP_POOL, OP_POOL_BWD, OP_CONV_WGRAD, OP_CONV_WRED, OP_ENC_DZ, OP_CHAIN, OP_WFRAG, OP_XCHAIN, OP_HEAD_DGRAD, OP_DGRAD0, OP_ADAM,
               OP_FINALIZE,
@@ -144,6 +146,46 @@ enum OpType { OP_GEMM, OP_GEMM64, OP_WGRAD, OP_LNBWD, OP_PREP, OP_POSTOS, OP_EUL
               // IQL-diffusion (agents/iql_diffusion.py) only: after IQL's
               OP_IQLD_PREP, OP_IQLD_LOSS_C, OP_IQLD_WEIGHT, OP_IQLD_LOSS_A, OP_IQLD_EGRAD, OP_IQLD_FIN, OP_IQLD_STEPBIAS, OP_IQLD_LAYER0,
               OP_IQLD_CFG, OP_NUM_TYPES };
+
+// A launch bound where its op is emitted (every agent op, OP_IFQL_PREP and later): the kernel, a 1-D grid and the packed arguments,
+// always FQL_THREADS threads and no LDS.  issue() launches it as it stands, so such an op has no payload member and no case of its own.
+constexpr int FQL_BOUND_BYTES = 160;
+struct Bound {
+    const void* fn = nullptr;   // the kernel's host address; null: the op carries no bound launch
+    unsigned grid = 0;
+    int len = 0;                // bytes of `args` in use
+    int at[2] = {0, 0};         // byte offset of each argument (at most two)
+    int tl_at = -1;             // byte offset of the int that receives the timeline id at issue time, -1: none
+    alignas(16) unsigned char args[FQL_BOUND_BYTES] = {};
+};
+template <typename... T>
+constexpr size_t packed_bytes() {   // kernarg layout: every argument at its natural alignment
+    size_t off = 0;
+    ((off = ((off + alignof(T) - 1) & ~(alignof(T) - 1)) + sizeof(T)), ...);
+    return off;
+}
+// kernel and arguments meet here, at compile time: each argument is converted to the kernel's parameter type and packed as the kernarg
+// segment lays it out
+template <typename... Pm, typename... A>
+Bound bind(void (*k)(Pm...), int grid, A&&... a) {
+    static_assert(sizeof...(Pm) == sizeof...(A) && sizeof...(Pm) <= 2, "a bound launch takes the kernel's one or two arguments");
+    static_assert(packed_bytes<Pm...>() <= FQL_BOUND_BYTES, "argument struct larger than Bound::args: raise FQL_BOUND_BYTES");
+    Bound b;
+    b.fn = (const void*)k;
+    b.grid = (unsigned)grid;
+    size_t off = 0;
+    int n = 0;
+    auto put = [&](auto v) {
+        using T = decltype(v);
+        off = (off + alignof(T) - 1) & ~(alignof(T) - 1);
+        b.at[n++] = (int)off;
+        std::memcpy(b.args + off, &v, sizeof(T));
+        off += sizeof(T);
+    };
+    (put(static_cast<Pm>(a)), ...);
+    b.len = (int)off;
+    return b;
+}
 
 struct Op {
     OpType type;
@@ -164,36 +206,6 @@ struct Op {
     ConvWgradArgs cw;
     ConvWredArgs cwr;
     EncDzArgs edz;
-    IfqlPrepArgs iprep;
-    IfqlValueArgs iv;
-    IfqlCriticArgs ic;
-    RebracPrepArgs rprep;
-    RebracActArgs ract;
-    RebracCriticArgs rc;
-    RebracActorArgs ra;
-    RebracActorGradArgs rag;
-    SacPrepArgs sprep;
-    SacActArgs sact;
-    SacCriticArgs sc;
-    SacActorArgs sa;
-    SacActorGradArgs sag;
-    BcPrepArgs bprep;
-    BcStepBiasArgs bsb;
-    BcLayer0Args bl0;
-    IqlPrepArgs qprep;
-    IqlHeadArgs qhead;
-    IqlAwrArgs qawr;
-    IqlDdpgArgs qddpg;
-    IqlActorGradArgs qag;
-    IqldPrepArgs dprep;
-    IqldCriticArgs dc;
-    IqldWeightArgs dw;
-    IqldActorLossArgs dla;
-    IqldEmbedGradArgs deg;
-    IqldFinalizeArgs dfin;
-    IqldStepBiasArgs dsb;
-    IqldLayer0Args dl0;
-    IqldCfgStepArgs dstep;
     ChainArgs chain;
     const ConvWprepTask* wprep_tasks = nullptr;
     int wprep_n = 0;
@@ -204,6 +216,7 @@ struct Op {
     float adam_lr = 0.f;           // > 0: this launch's learning rate (IQL-diffusion: one per TrainState), else fql_config.lr
     DevState* adam_st = nullptr;   // the counters this launch's bias correction reads (IQL-diffusion's actor), null: the handle's
     int fin_mode = 0;
+    Bound k;                 // agent ops: the launch, bound where the op is emitted
     int level = 0;
     int lane = 0;            // 0 = critical lane (Euler chain, one-step backward), 1 = side lane
     std::vector<int> deps;   // indices of earlier ops this op must follow (RAW / WAW / WAR)
@@ -2147,7 +2160,8 @@ struct fql_engine {
         return xg;
     }
 
-    // one launch of a program on stream s (tl: timeline id of the diagnostics build, -1 = none); reads engine state only
+    // one launch of a program on stream s (tl: timeline id of the diagnostics build, -1 = none); reads engine state only.  The FQL and
+    // encoder types have a case each; every agent type takes the last one, which launches what the emit site bound (Op::k).
     // Per-launch profiling (fql_profile_update): when set, the next launch carries these two events ON ITS DISPATCH
     // (hipExtLaunchKernelGGL): their elapsed time is the dispatch's own begin-to-end time, the quantity a rocprofv3 kernel trace reports.
     hipEvent_t prof_a = nullptr, prof_b = nullptr;
@@ -2289,124 +2303,23 @@ struct fql_engine {
                 FQL_LAUNCH(fql_finalize_kernel, dim3(1), dim3(FQL_THREADS), 0, s,
                                    FinalizeArgs{d_state, d_chunks, d_partials, d_leaf_range, n_chunks, n_train_leaves, L.op.fin_mode, tl});
                 break;
-            case OP_IFQL_PREP:
-                FQL_LAUNCH(fql_ifql_prep_kernel, dim3((L.op.iprep.B + 3) / 4), dim3(FQL_THREADS), 0, s, L.op.iprep);
-                break;
-            case OP_IFQL_LOSS_V:
-                FQL_LAUNCH(fql_ifql_loss_value_kernel, dim3(1), dim3(FQL_THREADS), 0, s, L.op.iv);
-                break;
-            case OP_IFQL_LOSS_C:
-                FQL_LAUNCH(fql_ifql_loss_critic_kernel, dim3(1), dim3(FQL_THREADS), 0, s, L.op.ic);
-                break;
-            case OP_IFQL_FIN:
-                FQL_LAUNCH(fql_ifql_finalize_kernel, dim3(1), dim3(FQL_THREADS), 0, s,
-                                   FinalizeArgs{d_state, d_chunks, d_partials, d_leaf_range, n_chunks, n_train_leaves, L.op.fin_mode, tl});
-                break;
-            case OP_REBRAC_PREP:
-                FQL_LAUNCH(fql_rebrac_prep_kernel, dim3((L.op.rprep.B + 3) / 4), dim3(FQL_THREADS), 0, s, L.op.rprep);
-                break;
-            case OP_REBRAC_ACT:
-                FQL_LAUNCH(fql_rebrac_act_kernel, dim3((L.op.ract.n * L.op.ract.ad + FQL_THREADS - 1) / FQL_THREADS), dim3(FQL_THREADS), 0, s, L.op.ract);
-                break;
-            case OP_REBRAC_LOSS_C:
-                FQL_LAUNCH(fql_rebrac_loss_critic_kernel, dim3(1), dim3(FQL_THREADS), 0, s, L.op.rc);
-                break;
-            case OP_REBRAC_LOSS_A:
-                FQL_LAUNCH(fql_rebrac_loss_actor_kernel, dim3(1), dim3(FQL_THREADS), 0, s, L.op.ra);
-                break;
-            case OP_REBRAC_AGRAD:
-                FQL_LAUNCH(fql_rebrac_actor_grad_kernel, dim3((L.op.rag.B * L.op.rag.ad + FQL_THREADS - 1) / FQL_THREADS), dim3(FQL_THREADS), 0, s, L.op.rag);
-                break;
-            case OP_REBRAC_FIN:
-                FQL_LAUNCH(fql_rebrac_finalize_kernel, dim3(1), dim3(FQL_THREADS), 0, s,
-                                   FinalizeArgs{d_state, d_chunks, d_partials, d_leaf_range, n_chunks, n_train_leaves, L.op.fin_mode & 1, tl},
-                                   (L.op.fin_mode >> 1) & 1);
-                break;
-            case OP_BC_PREP:
-                FQL_LAUNCH(fql_bc_prep_kernel, dim3((L.op.bprep.B + 3) / 4), dim3(FQL_THREADS), 0, s, L.op.bprep);
-                break;
-            case OP_BC_STEPBIAS:
-                FQL_LAUNCH(fql_bc_stepbias_kernel, dim3((L.op.bsb.S * L.op.bsb.H + FQL_THREADS - 1) / FQL_THREADS), dim3(FQL_THREADS), 0, s, L.op.bsb);
-                break;
-            case OP_BC_LAYER0:
-                FQL_LAUNCH(fql_bc_layer0_kernel, dim3((L.op.bl0.M * L.op.bl0.H + FQL_THREADS - 1) / FQL_THREADS), dim3(FQL_THREADS), 0, s, L.op.bl0);
-                break;
-            case OP_BC_FIN:
-                FQL_LAUNCH(fql_bc_finalize_kernel, dim3(1), dim3(FQL_THREADS), 0, s,
-                                   FinalizeArgs{d_state, d_chunks, d_partials, d_leaf_range, n_chunks, n_train_leaves, L.op.fin_mode & 1, tl});
-                break;
-            case OP_SAC_PREP:
-                FQL_LAUNCH(fql_sac_prep_kernel, dim3((L.op.sprep.B + 3) / 4), dim3(FQL_THREADS), 0, s, L.op.sprep);
-                break;
-            case OP_SAC_ACT:
-                FQL_LAUNCH(fql_sac_act_kernel, dim3((L.op.sact.n + FQL_THREADS - 1) / FQL_THREADS), dim3(FQL_THREADS), 0, s, L.op.sact);
-                break;
-            case OP_SAC_LOSS_C:
-                FQL_LAUNCH(fql_sac_loss_critic_kernel, dim3(1), dim3(FQL_THREADS), 0, s, L.op.sc);
-                break;
-            case OP_SAC_LOSS_A:
-                FQL_LAUNCH(fql_sac_loss_actor_kernel, dim3(1), dim3(FQL_THREADS), 0, s, L.op.sa);
-                break;
-            case OP_SAC_AGRAD:
-                FQL_LAUNCH(fql_sac_actor_grad_kernel, dim3((L.op.sag.B * L.op.sag.ad + FQL_THREADS - 1) / FQL_THREADS), dim3(FQL_THREADS), 0, s, L.op.sag);
-                break;
-            case OP_SAC_FIN:
-                FQL_LAUNCH(fql_sac_finalize_kernel, dim3(1), dim3(FQL_THREADS), 0, s,
-                                   FinalizeArgs{d_state, d_chunks, d_partials, d_leaf_range, n_chunks, n_train_leaves, L.op.fin_mode & 1, tl});
-                break;
-            case OP_IQL_PREP:
-                FQL_LAUNCH(fql_iql_prep_kernel, dim3((L.op.qprep.B + 3) / 4), dim3(FQL_THREADS), 0, s, L.op.qprep);
-                break;
-            case OP_IQL_HEAD:
-                FQL_LAUNCH(fql_iql_head_kernel, dim3((L.op.qhead.B + FQL_THREADS - 1) / FQL_THREADS), dim3(FQL_THREADS), 0, s, L.op.qhead);
-                break;
-            case OP_IQL_LOSS_AWR:
-                FQL_LAUNCH(fql_iql_loss_awr_kernel, dim3(1), dim3(FQL_THREADS), 0, s, L.op.qawr);
-                break;
-            case OP_IQL_LOSS_DDPGBC:
-                FQL_LAUNCH(fql_iql_loss_ddpgbc_kernel, dim3(1), dim3(FQL_THREADS), 0, s, L.op.qddpg);
-                break;
-            case OP_IQL_AGRAD:
-                FQL_LAUNCH(fql_iql_actor_grad_kernel, dim3(1), dim3(FQL_THREADS), 0, s, L.op.qag);
-                break;
-            case OP_IQL_FIN:
-                FQL_LAUNCH(fql_iql_finalize_kernel, dim3(1), dim3(FQL_THREADS), 0, s,
-                                   IqlFinalizeArgs{FinalizeArgs{d_state, d_chunks, d_partials, d_leaf_range, n_chunks, n_train_leaves, L.op.fin_mode & 1, tl},
-                                                   iql_info + ((L.op.fin_mode & 1) ? 0 : IQL_INFO_STRIDE), qcfg.actor_loss == 1 ? IQL_N_DDPGBC : IQL_N_AWR});
-                break;
-            case OP_IQLD_PREP:
-                FQL_LAUNCH(fql_iqld_prep_kernel, dim3((L.op.dprep.B + 3) / 4), dim3(FQL_THREADS), 0, s, L.op.dprep);
-                break;
-            case OP_IQLD_LOSS_C:
-                FQL_LAUNCH(fql_iqld_loss_critic_kernel, dim3(1), dim3(FQL_THREADS), 0, s, L.op.dc);
-                break;
-            case OP_IQLD_WEIGHT:
-                FQL_LAUNCH(fql_iqld_weight_kernel, dim3(1), dim3(FQL_THREADS), 0, s, L.op.dw);
-                break;
-            case OP_IQLD_LOSS_A:
-                FQL_LAUNCH(fql_iqld_loss_actor_kernel, dim3(1), dim3(FQL_THREADS), 0, s, L.op.dla);
-                break;
-            case OP_IQLD_EGRAD:
-                FQL_LAUNCH(fql_iqld_embed_grad_kernel, dim3(2), dim3(FQL_THREADS), 0, s, L.op.deg);
-                break;
-            case OP_IQLD_FIN:
-                FQL_LAUNCH(fql_iqld_finalize_kernel, dim3(1), dim3(FQL_THREADS), 0, s, L.op.dfin);
-                break;
-            case OP_IQLD_STEPBIAS:
-                FQL_LAUNCH(fql_iqld_stepbias_kernel, dim3((L.op.dsb.S * 2 * L.op.dsb.H + FQL_THREADS - 1) / FQL_THREADS), dim3(FQL_THREADS), 0, s, L.op.dsb);
-                break;
-            case OP_IQLD_LAYER0:
-                FQL_LAUNCH(fql_iqld_layer0_kernel, dim3((2 * L.op.dl0.n_pad * L.op.dl0.H + FQL_THREADS - 1) / FQL_THREADS), dim3(FQL_THREADS), 0, s, L.op.dl0);
-                break;
-            case OP_IQLD_CFG: {
-                IqldCfgStepArgs a = L.op.dstep;
-                a.cfg = sample_cfg;   // a run-time float: the cached sampling program holds every other argument
-                FQL_LAUNCH(fql_iqld_cfg_step_kernel, dim3((a.n_pad * a.ad + FQL_THREADS - 1) / FQL_THREADS), dim3(FQL_THREADS), 0, s, a);
-                break;
-            }
             case OP_WGRAD: case OP_LNBWD: case OP_POSTOS: case OP_LOSS_CRITIC: case OP_LOSS_Q: case OP_LOSS_BC:   // (inside OP_GEMM64 launches)
             case OP_PEC: case OP_XCHAIN: case OP_NUM_TYPES:
                 throw HipError{"internal: op type " + std::to_string((int)L.type) + " has no launch of its own"};
+            default: {   // every agent op (OP_IFQL_PREP and later): the launch its emit site bound
+                const Bound& k = L.op.k;
+                if (!k.fn) throw HipError{"internal: op type " + std::to_string((int)L.type) + " carries no bound launch"};
+                alignas(16) unsigned char a[FQL_BOUND_BYTES];
+                std::memcpy(a, k.args, (size_t)k.len);
+                if (k.tl_at >= 0) std::memcpy(a + k.tl_at, &tl, sizeof tl);
+                // a run-time float: the cached sampling program holds every other argument
+                if (L.type == OP_IQLD_CFG) std::memcpy(a + offsetof(IqldCfgStepArgs, cfg), &sample_cfg, sizeof sample_cfg);
+                void* argv[2] = {a + k.at[0], a + k.at[1]};
+                if (aql_rec) aql_rec->push_back(AqlDispatch{k.fn, {k.grid, 1, 1}, {FQL_THREADS, 1, 1}, 0, std::vector<uint8_t>(a, a + k.len)});
+                else if (prof_a) (void)hipExtLaunchKernel(k.fn, dim3(k.grid), dim3(FQL_THREADS), argv, 0, s, prof_a, prof_b, 0);
+                else (void)hipLaunchKernel(k.fn, dim3(k.grid), dim3(FQL_THREADS), argv, 0, s);
+                break;
+            }
         }
     }
 
@@ -2974,6 +2887,12 @@ struct fql_engine {
         push(pr, f);
     }
 
+    // FinalizeArgs of an agent's *_FIN op.  Every field is allocated before the first program is built (build_leaves, create_engine)
+    // and freed by fql_destroy alone, so the emit site binds it like any other argument; tl is written at issue time (Bound::tl_at).
+    FinalizeArgs fin_args(int do_grad_stats) const {
+        return FinalizeArgs{d_state, d_chunks, d_partials, d_leaf_range, n_chunks, n_train_leaves, do_grad_stats, -1};
+    }
+
     // ---------------------------------------------------------------------------------------
     // the IFQL update as a program (agents/ifql.py:79-120).  No Euler chain: every level is throughput work on the side lanes.
     //   lane 0: batch assembly; Adam + Polyak over every chunk and the finalize, behind both side lanes
@@ -2991,8 +2910,9 @@ struct fql_engine {
         {
             Op op{};
             op.type = OP_IFQL_PREP;
-            op.iprep = IfqlPrepArgs{d_src, st, seed, B, od, ad, nets[NET_OS].in_p(), nets[NET_C0].in_p(), nets[NET_BC].in_p(), ap,
-                                    X_v, X_c1, X_bc, vel, w_rew, w_mask};
+            const IfqlPrepArgs iprep{d_src, st, seed, B, od, ad, nets[NET_OS].in_p(), nets[NET_C0].in_p(), nets[NET_BC].in_p(), ap,
+                                     X_v, X_c1, X_bc, vel, w_rew, w_mask};
+            op.k = bind(fql_ifql_prep_kernel, (iprep.B + 3) / 4, iprep);
             op.writes = {X_v, X_c1, X_bc, vel, w_rew, w_mask};
             push(pr, op);
         }
@@ -3002,7 +2922,8 @@ struct fql_engine {
         {
             Op op{};
             op.type = OP_IFQL_LOSS_V;
-            op.iv = IfqlValueArgs{p_v.out, p_ct[0].out, p_ct[1].out, with_grads ? p_v.dz.back() : nullptr, st, B, expectile};
+            const IfqlValueArgs iv{p_v.out, p_ct[0].out, p_ct[1].out, with_grads ? p_v.dz.back() : nullptr, st, B, expectile};
+            op.k = bind(fql_ifql_loss_value_kernel, 1, iv);
             op.reads = {p_v.out, p_ct[0].out, p_ct[1].out};
             op.writes = {I_V};
             if (with_grads) op.writes.push_back(p_v.dz.back());
@@ -3025,8 +2946,9 @@ struct fql_engine {
         {
             Op op{};
             op.type = OP_IFQL_LOSS_C;
-            op.ic = IfqlCriticArgs{p_v.out + (size_t)B * nets[NET_OS].layers.back().out_p, p_c1[0].out, p_c1[1].out, w_rew, w_mask,
-                                   with_grads ? p_c1[0].dz.back() : nullptr, with_grads ? p_c1[1].dz.back() : nullptr, st, B, cfg.discount};
+            const IfqlCriticArgs ic{p_v.out + (size_t)B * nets[NET_OS].layers.back().out_p, p_c1[0].out, p_c1[1].out, w_rew, w_mask,
+                                    with_grads ? p_c1[0].dz.back() : nullptr, with_grads ? p_c1[1].dz.back() : nullptr, st, B, cfg.discount};
+            op.k = bind(fql_ifql_loss_critic_kernel, 1, ic);
             op.reads = {p_v.out, p_c1[0].out, p_c1[1].out, w_rew, w_mask};
             op.writes = {I_C};
             if (with_grads) { op.writes.push_back(p_c1[0].dz.back()); op.writes.push_back(p_c1[1].dz.back()); }
@@ -3037,7 +2959,8 @@ struct fql_engine {
         if (with_grads) adam_for(pr, 2, {NET_C0, NET_C1, NET_BC, NET_OS}, 0, -2);   // every chunk, one launch; Polyak from the pre-step critic
         Op f{};
         f.type = OP_IFQL_FIN;
-        f.fin_mode = with_grads ? 1 : 0;
+        f.k = bind(fql_ifql_finalize_kernel, 1, fin_args(with_grads ? 1 : 0));
+        f.k.tl_at = offsetof(FinalizeArgs, tl);
         f.reads = {I_V, I_C, I_A};
         if (with_grads) for (int m = 0; m < 3; ++m) f.reads.push_back(d_partials + mod_chunk0[m] * 4);
         f.writes = {&st->info[8], st};
@@ -3092,8 +3015,9 @@ struct fql_engine {
         {
             Op op{};
             op.type = OP_REBRAC_PREP;
-            op.rprep = RebracPrepArgs{d_src, st, seed, B, od, ad, inp_a, inp_c, ap, X_c1, X_t, X_q, X_a, X_ta, w_act, w_nact, w_noise,
-                                      w_rew, w_mask, zero_actor ? G + na.off : nullptr, zero_actor ? (int64_t)na.size : 0};
+            const RebracPrepArgs rprep{d_src, st, seed, B, od, ad, inp_a, inp_c, ap, X_c1, X_t, X_q, X_a, X_ta, w_act, w_nact, w_noise,
+                                       w_rew, w_mask, zero_actor ? G + na.off : nullptr, zero_actor ? (int64_t)na.size : 0};
+            op.k = bind(fql_rebrac_prep_kernel, (rprep.B + 3) / 4, rprep);
             op.writes = {X_c1, X_t, X_q, X_a, X_ta, w_act, w_nact, w_noise, w_rew, w_mask};
             if (zero_actor)   // critic-only step: the actor's gradient is zero (rebrac.py:104-106), not the last full step's
                 for (const Layer& L : na.layers) {
@@ -3105,8 +3029,9 @@ struct fql_engine {
         auto act_op = [&](const PassBuf& p, const float* noise, float* X, bool target) {
             Op op{};
             op.type = OP_REBRAC_ACT;
-            op.ract = RebracActArgs{p.out, noise, X, 0, 0, B, ad, ap, ap, inp_c, od, 0, target ? 1 : 0, rcfg.tanh_squash, target ? 1 : 0,
-                                    rcfg.actor_noise, rcfg.actor_noise_clip};
+            const RebracActArgs ract{p.out, noise, X, 0, 0, B, ad, ap, ap, inp_c, od, 0, target ? 1 : 0, rcfg.tanh_squash, target ? 1 : 0,
+                                     rcfg.actor_noise, rcfg.actor_noise_clip};
+            op.k = bind(fql_rebrac_act_kernel, (ract.n * ract.ad + FQL_THREADS - 1) / FQL_THREADS, ract);
             op.reads = {p.out};
             if (noise) op.reads.push_back(noise);
             op.writes = {X};
@@ -3123,8 +3048,9 @@ struct fql_engine {
             {
                 Op op{};
                 op.type = OP_REBRAC_LOSS_A;
-                op.ra = RebracActorArgs{p_q[0].out, p_q[1].out, X_q, w_act, with_grads ? p_q[0].dz.back() : nullptr,
-                                        with_grads ? p_q[1].dz.back() : nullptr, st, B, od, ad, inp_c, ap, rcfg.alpha_actor};
+                const RebracActorArgs ra{p_q[0].out, p_q[1].out, X_q, w_act, with_grads ? p_q[0].dz.back() : nullptr,
+                                         with_grads ? p_q[1].dz.back() : nullptr, st, B, od, ad, inp_c, ap, rcfg.alpha_actor};
+                op.k = bind(fql_rebrac_loss_actor_kernel, 1, ra);
                 op.reads = {p_q[0].out, p_q[1].out, X_q, w_act};
                 op.writes = {I_A};
                 if (with_grads) { op.writes.push_back(p_q[0].dz.back()); op.writes.push_back(p_q[1].dz.back()); }
@@ -3134,8 +3060,9 @@ struct fql_engine {
                 for (int e = 0; e < 2; ++e) emit_backward(pr, p_q[e], 0, B, false, true);   // dQ/da only: the critic's params get no gradient
                 Op op{};
                 op.type = OP_REBRAC_AGRAD;
-                op.rag = RebracActorGradArgs{p_q[0].dx0, p_q[1].dx0, X_q, w_act, p_a.dz.back(), B, od, ad, inp_c, ap,
-                                             rcfg.alpha_actor * 2.0f / (float)B, rcfg.tanh_squash};
+                const RebracActorGradArgs rag{p_q[0].dx0, p_q[1].dx0, X_q, w_act, p_a.dz.back(), B, od, ad, inp_c, ap,
+                                              rcfg.alpha_actor * 2.0f / (float)B, rcfg.tanh_squash};
+                op.k = bind(fql_rebrac_actor_grad_kernel, (rag.B * rag.ad + FQL_THREADS - 1) / FQL_THREADS, rag);
                 op.reads = {p_q[0].dx0, p_q[1].dx0, X_q, w_act};
                 op.writes = {p_a.dz.back()};
                 push(pr, op);
@@ -3147,9 +3074,10 @@ struct fql_engine {
         {
             Op op{};
             op.type = OP_REBRAC_LOSS_C;
-            op.rc = RebracCriticArgs{p_c1[0].out, p_c1[1].out, p_ct[0].out, p_ct[1].out, X_t, w_nact, w_rew, w_mask,
-                                     with_grads ? p_c1[0].dz.back() : nullptr, with_grads ? p_c1[1].dz.back() : nullptr, st, B, od, ad, inp_c, ap,
-                                     cfg.discount, rcfg.alpha_critic};
+            const RebracCriticArgs rc{p_c1[0].out, p_c1[1].out, p_ct[0].out, p_ct[1].out, X_t, w_nact, w_rew, w_mask,
+                                      with_grads ? p_c1[0].dz.back() : nullptr, with_grads ? p_c1[1].dz.back() : nullptr, st, B, od, ad, inp_c, ap,
+                                      cfg.discount, rcfg.alpha_critic};
+            op.k = bind(fql_rebrac_loss_critic_kernel, 1, rc);
             op.reads = {p_c1[0].out, p_c1[1].out, p_ct[0].out, p_ct[1].out, X_t, w_nact, w_rew, w_mask};
             op.writes = {I_C};
             if (with_grads) { op.writes.push_back(p_c1[0].dz.back()); op.writes.push_back(p_c1[1].dz.back()); }
@@ -3165,7 +3093,8 @@ struct fql_engine {
         else a.adam_polyak = 0;
         Op f{};
         f.type = OP_REBRAC_FIN;
-        f.fin_mode = 1 | (full_update ? 2 : 0);
+        f.k = bind(fql_rebrac_finalize_kernel, 1, fin_args(1), full_update ? 1 : 0);
+        f.k.tl_at = offsetof(FinalizeArgs, tl);
         f.reads = {I_C, I_A};
         for (int m = 0; m < 3; ++m) f.reads.push_back(d_partials + mod_chunk0[m] * 4);
         f.writes = {&st->info[8], st};
@@ -3218,7 +3147,8 @@ struct fql_engine {
         {
             Op op{};
             op.type = OP_SAC_PREP;
-            op.sprep = SacPrepArgs{d_src, st, seed, B, od, ad, inp_a, inp_c, ap, X_c1, X_t, X_q, X_a, w_eps, w_rew, w_mask};
+            const SacPrepArgs sprep{d_src, st, seed, B, od, ad, inp_a, inp_c, ap, X_c1, X_t, X_q, X_a, w_eps, w_rew, w_mask};
+            op.k = bind(fql_sac_prep_kernel, (sprep.B + 3) / 4, sprep);
             op.writes = {X_c1, X_t, X_q, X_a, w_eps, w_rew, w_mask};
             push(pr, op);
         }
@@ -3227,7 +3157,8 @@ struct fql_engine {
         {
             Op op{};
             op.type = OP_SAC_ACT;   // a, lp (obs rows) and a', lp' (next rows)  sac.py:27,62
-            op.sact = SacActArgs{p_a.out, w_eps, X_q, X_t, lp_buf, 0, 0, 2 * B, ad, ap, ap, inp_c, od, 0, B, 1, scfg.tanh_squash, 0, 1.0f};
+            const SacActArgs sact{p_a.out, w_eps, X_q, X_t, lp_buf, 0, 0, 2 * B, ad, ap, ap, inp_c, od, 0, B, 1, scfg.tanh_squash, 0, 1.0f};
+            op.k = bind(fql_sac_act_kernel, (sact.n + FQL_THREADS - 1) / FQL_THREADS, sact);
             op.reads = {p_a.out, w_eps};
             op.writes = {X_q, X_t, lp_buf};
             push(pr, op);
@@ -3236,8 +3167,9 @@ struct fql_engine {
         {
             Op op{};
             op.type = OP_SAC_LOSS_A;
-            op.sa = SacActorArgs{p_q[0].out, p_q[1].out, lp_buf, p_a.out, la, with_grads ? G + alpha_off : nullptr,
-                                 with_grads ? p_q[0].dz.back() : nullptr, with_grads ? p_q[1].dz.back() : nullptr, st, B, ad, ap, target_entropy};
+            const SacActorArgs sa{p_q[0].out, p_q[1].out, lp_buf, p_a.out, la, with_grads ? G + alpha_off : nullptr,
+                                  with_grads ? p_q[0].dz.back() : nullptr, with_grads ? p_q[1].dz.back() : nullptr, st, B, ad, ap, target_entropy};
+            op.k = bind(fql_sac_loss_actor_kernel, 1, sa);
             op.reads = {p_q[0].out, p_q[1].out, lp_buf, p_a.out, la};
             op.writes = {I_A, I_Q};
             if (with_grads) { op.writes.push_back(G + alpha_off); op.writes.push_back(p_q[0].dz.back()); op.writes.push_back(p_q[1].dz.back()); }
@@ -3247,7 +3179,8 @@ struct fql_engine {
             for (int e = 0; e < 2; ++e) emit_backward(pr, p_q[e], 0, B, false, true);   // dQ/da only: the critic's params get no gradient
             Op op{};
             op.type = OP_SAC_AGRAD;
-            op.sag = SacActorGradArgs{p_q[0].dx0, p_q[1].dx0, X_q, p_a.out, w_eps, la, p_a.dz.back(), B, od, ad, inp_c, ap, scfg.tanh_squash};
+            const SacActorGradArgs sag{p_q[0].dx0, p_q[1].dx0, X_q, p_a.out, w_eps, la, p_a.dz.back(), B, od, ad, inp_c, ap, scfg.tanh_squash};
+            op.k = bind(fql_sac_actor_grad_kernel, (sag.B * sag.ad + FQL_THREADS - 1) / FQL_THREADS, sag);
             op.reads = {p_q[0].dx0, p_q[1].dx0, X_q, p_a.out, w_eps, la};
             op.writes = {p_a.dz.back()};
             push(pr, op);
@@ -3259,9 +3192,10 @@ struct fql_engine {
         {
             Op op{};
             op.type = OP_SAC_LOSS_C;
-            op.sc = SacCriticArgs{p_c1[0].out, p_c1[1].out, p_ct[0].out, p_ct[1].out, lp_buf + B, w_rew, w_mask, la,
-                                  with_grads ? p_c1[0].dz.back() : nullptr, with_grads ? p_c1[1].dz.back() : nullptr, st, B,
-                                  cfg.q_agg == 1 ? 1 : 0, scfg.backup_entropy ? 1 : 0, cfg.discount};
+            const SacCriticArgs sc{p_c1[0].out, p_c1[1].out, p_ct[0].out, p_ct[1].out, lp_buf + B, w_rew, w_mask, la,
+                                   with_grads ? p_c1[0].dz.back() : nullptr, with_grads ? p_c1[1].dz.back() : nullptr, st, B,
+                                   cfg.q_agg == 1 ? 1 : 0, scfg.backup_entropy ? 1 : 0, cfg.discount};
+            op.k = bind(fql_sac_loss_critic_kernel, 1, sc);
             op.reads = {p_c1[0].out, p_c1[1].out, p_ct[0].out, p_ct[1].out, lp_buf, w_rew, w_mask, la};
             op.writes = {I_C};
             if (with_grads) { op.writes.push_back(p_c1[0].dz.back()); op.writes.push_back(p_c1[1].dz.back()); }
@@ -3276,7 +3210,8 @@ struct fql_engine {
         a.writes.push_back(P + alpha_off);
         Op f{};
         f.type = OP_SAC_FIN;
-        f.fin_mode = 1;
+        f.k = bind(fql_sac_finalize_kernel, 1, fin_args(1));
+        f.k.tl_at = offsetof(FinalizeArgs, tl);
         f.reads = {I_C, I_A, I_Q};
         for (int m = 0; m < 3; ++m) f.reads.push_back(d_partials + mod_chunk0[m] * 4);
         f.writes = {&st->info[10], st};
@@ -3324,7 +3259,8 @@ struct fql_engine {
         {
             Op op{};
             op.type = OP_BC_PREP;
-            op.bprep = BcPrepArgs{d_src, st, seed, d_emb, B, od, ad, nets[NET_BC].in_p(), ap, bc_steps, X_bc, vel};
+            const BcPrepArgs bprep{d_src, st, seed, d_emb, B, od, ad, nets[NET_BC].in_p(), ap, bc_steps, X_bc, vel};
+            op.k = bind(fql_bc_prep_kernel, (bprep.B + 3) / 4, bprep);
             op.writes = {X_bc, vel};
             push(pr, op);
         }
@@ -3343,7 +3279,8 @@ struct fql_engine {
             adam_for(pr, 0, {NET_BC}, 0, -2);   // every chunk in one launch; critic_size = 0: no Polyak range
             Op f{};
             f.type = OP_BC_FIN;
-            f.fin_mode = 1;
+            f.k = bind(fql_bc_finalize_kernel, 1, fin_args(1));
+            f.k.tl_at = offsetof(FinalizeArgs, tl);
             f.reads = {I_L, d_partials};
             f.writes = {&st->info[0], &st->info[10], st};
             push(pr, f);
@@ -3416,7 +3353,8 @@ struct fql_engine {
         {
             Op op{};
             op.type = OP_IQL_PREP;
-            op.qprep = IqlPrepArgs{d_src, st, seed, B, od, ad, inp_v, inp_c, inp_a, ap, X_v, X_c1, X_a, X_q, w_act, eps, w_rew, w_mask};
+            const IqlPrepArgs qprep{d_src, st, seed, B, od, ad, inp_v, inp_c, inp_a, ap, X_v, X_c1, X_a, X_q, w_act, eps, w_rew, w_mask};
+            op.k = bind(fql_iql_prep_kernel, (qprep.B + 3) / 4, qprep);
             op.writes = {X_v, X_c1, X_a, w_act, w_rew, w_mask};
             if (X_q) op.writes.push_back(X_q);
             if (eps) op.writes.push_back(eps);
@@ -3428,7 +3366,8 @@ struct fql_engine {
         {
             Op op{};
             op.type = OP_IFQL_LOSS_V;
-            op.iv = IfqlValueArgs{p_v.out, p_ct[0].out, p_ct[1].out, with_grads ? p_v.dz.back() : nullptr, st, B, qcfg.expectile};
+            const IfqlValueArgs iv{p_v.out, p_ct[0].out, p_ct[1].out, with_grads ? p_v.dz.back() : nullptr, st, B, qcfg.expectile};
+            op.k = bind(fql_ifql_loss_value_kernel, 1, iv);
             op.reads = {p_v.out, p_ct[0].out, p_ct[1].out};
             op.writes = {I_V};
             if (with_grads) op.writes.push_back(p_v.dz.back());
@@ -3439,7 +3378,8 @@ struct fql_engine {
         {
             Op op{};
             op.type = OP_IQL_HEAD;                                      // log_prob(actions) iql.py:70,95; q_actions iql.py:86-89
-            op.qhead = IqlHeadArgs{p_a.out, ls, w_act, eps, lp_buf, se_buf, ddpg ? X_q : nullptr, B, od, ad, ap, inp_c};
+            const IqlHeadArgs qhead{p_a.out, ls, w_act, eps, lp_buf, se_buf, ddpg ? X_q : nullptr, B, od, ad, ap, inp_c};
+            op.k = bind(fql_iql_head_kernel, (qhead.B + FQL_THREADS - 1) / FQL_THREADS, qhead);
             op.reads = {p_a.out, w_act};
             if (ls) op.reads.push_back(ls);
             if (eps) op.reads.push_back(eps);
@@ -3451,8 +3391,9 @@ struct fql_engine {
             for (int e = 0; e < 2; ++e) emit_forward(pr, p_q[e], with_grads);   // critic(obs, q_actions), stored params  iql.py:90
             Op op{};
             op.type = OP_IQL_LOSS_DDPGBC;
-            op.qddpg = IqlDdpgArgs{p_q[0].out, p_q[1].out, lp_buf, se_buf, ls, with_grads ? p_q[0].dz.back() : nullptr,
-                                   with_grads ? p_q[1].dz.back() : nullptr, out, B, ad, qcfg.alpha};
+            const IqlDdpgArgs qddpg{p_q[0].out, p_q[1].out, lp_buf, se_buf, ls, with_grads ? p_q[0].dz.back() : nullptr,
+                                    with_grads ? p_q[1].dz.back() : nullptr, out, B, ad, qcfg.alpha};
+            op.k = bind(fql_iql_loss_ddpgbc_kernel, 1, qddpg);
             op.reads = {p_q[0].out, p_q[1].out, lp_buf, se_buf};
             if (ls) op.reads.push_back(ls);
             op.writes = {I_A};
@@ -3464,8 +3405,9 @@ struct fql_engine {
         {
             Op op{};
             op.type = OP_IFQL_LOSS_C;
-            op.ic = IfqlCriticArgs{p_v.out + (size_t)B * nets[NET_OS].layers.back().out_p, p_c1[0].out, p_c1[1].out, w_rew, w_mask,
-                                   with_grads ? p_c1[0].dz.back() : nullptr, with_grads ? p_c1[1].dz.back() : nullptr, st, B, cfg.discount};
+            const IfqlCriticArgs ic{p_v.out + (size_t)B * nets[NET_OS].layers.back().out_p, p_c1[0].out, p_c1[1].out, w_rew, w_mask,
+                                    with_grads ? p_c1[0].dz.back() : nullptr, with_grads ? p_c1[1].dz.back() : nullptr, st, B, cfg.discount};
+            op.k = bind(fql_ifql_loss_critic_kernel, 1, ic);
             op.reads = {p_v.out, p_c1[0].out, p_c1[1].out, w_rew, w_mask};
             op.writes = {I_C};
             if (with_grads) { op.writes.push_back(p_c1[0].dz.back()); op.writes.push_back(p_c1[1].dz.back()); }
@@ -3476,8 +3418,9 @@ struct fql_engine {
         if (!ddpg) {
             Op op{};
             op.type = OP_IQL_LOSS_AWR;
-            op.qawr = IqlAwrArgs{p_c1[0].out, p_c1[1].out, p_v.out, lp_buf, se_buf, p_a.out, w_act, ls, with_grads ? p_a.dz.back() : nullptr,
-                                 ls_part, g_ls, out, B, ad, ap, qcfg.alpha};
+            const IqlAwrArgs qawr{p_c1[0].out, p_c1[1].out, p_v.out, lp_buf, se_buf, p_a.out, w_act, ls, with_grads ? p_a.dz.back() : nullptr,
+                                  ls_part, g_ls, out, B, ad, ap, qcfg.alpha};
+            op.k = bind(fql_iql_loss_awr_kernel, 1, qawr);
             op.reads = {p_c1[0].out, p_c1[1].out, p_v.out, lp_buf, se_buf, p_a.out, w_act};
             if (ls) op.reads.push_back(ls);
             op.writes = {I_A};
@@ -3488,7 +3431,8 @@ struct fql_engine {
             for (int e = 0; e < 2; ++e) emit_backward(pr, p_q[e], 0, B, false, true);   // dQ/da only: the critic's params get no gradient here
             Op op{};
             op.type = OP_IQL_AGRAD;
-            op.qag = IqlActorGradArgs{p_q[0].dx0, p_q[1].dx0, p_a.out, w_act, eps, ls, p_a.dz.back(), ls_part, g_ls, B, od, ad, ap, inp_c, qcfg.alpha};
+            const IqlActorGradArgs qag{p_q[0].dx0, p_q[1].dx0, p_a.out, w_act, eps, ls, p_a.dz.back(), ls_part, g_ls, B, od, ad, ap, inp_c, qcfg.alpha};
+            op.k = bind(fql_iql_actor_grad_kernel, 1, qag);
             op.reads = {p_q[0].dx0, p_q[1].dx0, p_a.out, w_act};
             if (ls) op.reads.push_back(ls);
             if (eps) op.reads.push_back(eps);
@@ -3507,7 +3451,8 @@ struct fql_engine {
         }
         Op f{};
         f.type = OP_IQL_FIN;
-        f.fin_mode = with_grads ? 1 : 0;
+        f.k = bind(fql_iql_finalize_kernel, 1, IqlFinalizeArgs{fin_args(with_grads ? 1 : 0), out, ddpg ? IQL_N_DDPGBC : IQL_N_AWR});
+        f.k.tl_at = offsetof(IqlFinalizeArgs, fin.tl);
         f.reads = {I_V, I_C, I_A};
         if (with_grads) for (int m = 0; m < 3; ++m) f.reads.push_back(d_partials + mod_chunk0[m] * 4);
         f.writes = {out, st};
@@ -3592,8 +3537,9 @@ struct fql_engine {
         if (do_c || do_a) {
             Op op{};
             op.type = OP_IQLD_PREP;
-            op.dprep = IqldPrepArgs{d_src, st, seed, d_emb, P + emb_off, B, od, ad, nets[NET_OS].in_p(), nets[NET_C0].in_p(), na.in_p(), ap,
-                                    bc_steps, X_v, X_c1, X_bc, vel, w_rew, w_mask};
+            const IqldPrepArgs dprep{d_src, st, seed, d_emb, P + emb_off, B, od, ad, nets[NET_OS].in_p(), nets[NET_C0].in_p(), na.in_p(), ap,
+                                     bc_steps, X_v, X_c1, X_bc, vel, w_rew, w_mask};
+            op.k = bind(fql_iqld_prep_kernel, (dprep.B + 3) / 4, dprep);
             op.reads = {P + emb_off};
             op.writes = {X_v, X_c1, X_bc, vel, w_rew, w_mask};
             push(pr, op);
@@ -3604,7 +3550,8 @@ struct fql_engine {
         if (do_c) {
             Op op{};
             op.type = OP_IFQL_LOSS_V;
-            op.iv = IfqlValueArgs{p_v.out, p_ct[0].out, p_ct[1].out, gc ? p_v.dz.back() : nullptr, st, B, dcfg.expectile};
+            const IfqlValueArgs iv{p_v.out, p_ct[0].out, p_ct[1].out, gc ? p_v.dz.back() : nullptr, st, B, dcfg.expectile};
+            op.k = bind(fql_ifql_loss_value_kernel, 1, iv);
             op.reads = {p_v.out, p_ct[0].out, p_ct[1].out};
             op.writes = {I_V};
             if (gc) op.writes.push_back(p_v.dz.back());
@@ -3616,8 +3563,9 @@ struct fql_engine {
         if (do_c) {
             Op op{};
             op.type = OP_IQLD_LOSS_C;
-            op.dc = IqldCriticArgs{p_v.out + (size_t)B * nets[NET_OS].layers.back().out_p, p_c1[0].out, p_c1[1].out, w_rew, w_mask,
-                                   gc ? p_c1[0].dz.back() : nullptr, gc ? p_c1[1].dz.back() : nullptr, out, B, cfg.discount};
+            const IqldCriticArgs dc{p_v.out + (size_t)B * nets[NET_OS].layers.back().out_p, p_c1[0].out, p_c1[1].out, w_rew, w_mask,
+                                    gc ? p_c1[0].dz.back() : nullptr, gc ? p_c1[1].dz.back() : nullptr, out, B, cfg.discount};
+            op.k = bind(fql_iqld_loss_critic_kernel, 1, dc);
             op.reads = {p_v.out, p_c1[0].out, p_c1[1].out, w_rew, w_mask};
             op.writes = {I_C};
             if (gc) { op.writes.push_back(p_c1[0].dz.back()); op.writes.push_back(p_c1[1].dz.back()); }
@@ -3629,8 +3577,9 @@ struct fql_engine {
             {
                 Op op{};
                 op.type = OP_IQLD_WEIGHT;
-                op.dw = IqldWeightArgs{pq[0].out, pq[1].out, p_v.out, w_lw, rows, out, B, dcfg.optimal_var, (int)(0.1 * (double)B),
-                                       dcfg.optimal_var == IQLD_BINARY_SOFTMAX ? dcfg.softmax_beta : dcfg.awr_temperature};
+                const IqldWeightArgs dw{pq[0].out, pq[1].out, p_v.out, w_lw, rows, out, B, dcfg.optimal_var, (int)(0.1 * (double)B),
+                                        dcfg.optimal_var == IQLD_BINARY_SOFTMAX ? dcfg.softmax_beta : dcfg.awr_temperature};
+                op.k = bind(fql_iqld_weight_kernel, 1, dw);
                 op.reads = {pq[0].out, pq[1].out, p_v.out};
                 op.writes = {w_lw, rows + (size_t)B, I_W};
                 push(pr, op);
@@ -3639,7 +3588,8 @@ struct fql_engine {
             {
                 Op op{};
                 op.type = OP_IQLD_LOSS_A;
-                op.dla = IqldActorLossArgs{p_bc.out, vel, w_lw, ga ? p_bc.dz.back() : nullptr, rows, out, B, ad, ap};
+                const IqldActorLossArgs dla{p_bc.out, vel, w_lw, ga ? p_bc.dz.back() : nullptr, rows, out, B, ad, ap};
+                op.k = bind(fql_iqld_loss_actor_kernel, 1, dla);
                 op.reads = {p_bc.out, vel, w_lw, I_W};   // (I_W: the two kernels write disjoint slots of one info block, in this order)
                 op.writes = {rows, I_A};
                 if (ga) op.writes.push_back(p_bc.dz.back());
@@ -3650,7 +3600,8 @@ struct fql_engine {
                 const Layer& l0 = na.layers[0];
                 Op op{};
                 op.type = OP_IQLD_EGRAD;
-                op.deg = IqldEmbedGradArgs{p_bc.dz[0], P + l0.w + (size_t)(od + ad + BC_EMB) * l0.out_p, G + emb_off, B, l0.out_p};
+                const IqldEmbedGradArgs deg{p_bc.dz[0], P + l0.w + (size_t)(od + ad + BC_EMB) * l0.out_p, G + emb_off, B, l0.out_p};
+                op.k = bind(fql_iqld_embed_grad_kernel, 2, deg);
                 op.reads = {p_bc.dz[0], P + l0.w};
                 op.writes = {G + emb_off};
                 push(pr, op);
@@ -3675,8 +3626,9 @@ struct fql_engine {
         iqld_leaf_ranges(a_lo, a_hi, v_lo, v_hi);
         Op f{};
         f.type = OP_IQLD_FIN;
-        f.dfin = IqldFinalizeArgs{st, d_state_a, d_partials, d_leaf_range, out, ga ? a_lo : (gc ? v_lo : 0), ga ? a_hi : (gc ? v_hi : 0),
-                                  do_c ? 1 : 0, do_a ? 1 : 0, gc ? 1 : 0, ga ? 1 : 0, with_grads ? 1 : 0};
+        const IqldFinalizeArgs dfin{st, d_state_a, d_partials, d_leaf_range, out, ga ? a_lo : (gc ? v_lo : 0), ga ? a_hi : (gc ? v_hi : 0),
+                                    do_c ? 1 : 0, do_a ? 1 : 0, gc ? 1 : 0, ga ? 1 : 0, with_grads ? 1 : 0};
+        f.k = bind(fql_iqld_finalize_kernel, 1, dfin);
         f.reads = {I_V, I_C, I_W, I_A};
         if (with_grads) for (int m = 0; m < 3; ++m) f.reads.push_back(d_partials + mod_chunk0[m] * 4);
         f.writes = {out, st, d_state_a};
@@ -4125,7 +4077,8 @@ struct fql_engine {
             {
                 Op op{};
                 op.type = OP_BC_STEPBIAS;
-                op.bsb = BcStepBiasArgs{d_emb, P + l0.w + (size_t)(od + ad) * H, ev->Xq, S, H};
+                const BcStepBiasArgs bsb{d_emb, P + l0.w + (size_t)(od + ad) * H, ev->Xq, S, H};
+                op.k = bind(fql_bc_stepbias_kernel, (bsb.S * bsb.H + FQL_THREADS - 1) / FQL_THREADS, bsb);
                 op.reads = {d_emb, P + l0.w};
                 op.writes = {ev->Xq};
                 push(pr, op);
@@ -4143,7 +4096,8 @@ struct fql_engine {
             for (int i = 0; i < S; ++i) {
                 Op op{};
                 op.type = OP_BC_LAYER0;
-                op.bl0 = BcLayer0Args{C0e, ev->Xf, P + l0.w + (size_t)od * H, ev->Xq + (size_t)i * H, ev->p_eu.g[0], n_pad, H, ad, ap};
+                const BcLayer0Args bl0{C0e, ev->Xf, P + l0.w + (size_t)od * H, ev->Xq + (size_t)i * H, ev->p_eu.g[0], n_pad, H, ad, ap};
+                op.k = bind(fql_bc_layer0_kernel, (bl0.M * bl0.H + FQL_THREADS - 1) / FQL_THREADS, bl0);
                 op.reads = {C0e, ev->Xf, ev->Xq, P + l0.w};
                 op.writes = {ev->p_eu.g[0]};
                 push(pr, op);
@@ -4180,7 +4134,8 @@ struct fql_engine {
             {
                 Op op{};
                 op.type = OP_IQLD_STEPBIAS;
-                op.dsb = IqldStepBiasArgs{d_emb, P + emb_off, P + l0.w + (size_t)(od + ad) * H, ev->Xq, S, H};
+                const IqldStepBiasArgs dsb{d_emb, P + emb_off, P + l0.w + (size_t)(od + ad) * H, ev->Xq, S, H};
+                op.k = bind(fql_iqld_stepbias_kernel, (dsb.S * 2 * dsb.H + FQL_THREADS - 1) / FQL_THREADS, dsb);
                 op.reads = {d_emb, P + emb_off, P + l0.w};
                 op.writes = {ev->Xq};
                 push(pr, op);
@@ -4198,14 +4153,16 @@ struct fql_engine {
             for (int i = 0; i < S; ++i) {
                 Op op{};
                 op.type = OP_IQLD_LAYER0;
-                op.dl0 = IqldLayer0Args{C0e, ev->Xf, P + l0.w + (size_t)od * H, ev->Xq + (size_t)i * 2 * H, ev->p_eu.g[0], half, H, ad, ap};
+                const IqldLayer0Args dl0{C0e, ev->Xf, P + l0.w + (size_t)od * H, ev->Xq + (size_t)i * 2 * H, ev->p_eu.g[0], half, H, ad, ap};
+                op.k = bind(fql_iqld_layer0_kernel, (2 * dl0.n_pad * dl0.H + FQL_THREADS - 1) / FQL_THREADS, dl0);
                 op.reads = {C0e, ev->Xf, ev->Xq, P + l0.w};
                 op.writes = {ev->p_eu.g[0]};
                 push(pr, op);
                 emit_forward(pr, ev->p_eu, false, 0, nullptr, nullptr, 0.f, 0.f, 1);
                 Op st{};
                 st.type = OP_IQLD_CFG;
-                st.dstep = IqldCfgStepArgs{ev->p_eu.out, ev->Xf, i == S - 1 ? ev->tgt : nullptr, half, ad, ap, 1.0f, 1.0f / (float)S};
+                const IqldCfgStepArgs dstep{ev->p_eu.out, ev->Xf, i == S - 1 ? ev->tgt : nullptr, half, ad, ap, 1.0f, 1.0f / (float)S};
+                st.k = bind(fql_iqld_cfg_step_kernel, (dstep.n_pad * dstep.ad + FQL_THREADS - 1) / FQL_THREADS, dstep);
                 st.reads = {ev->p_eu.out};
                 st.writes = {ev->Xf};
                 if (i == S - 1) st.writes.push_back(ev->tgt);

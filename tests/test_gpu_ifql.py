@@ -189,6 +189,31 @@ def test_aql_and_graph_updates_bitwise_over_20_steps():
     _same_state(a, a2)
 
 
+def test_profile_pass_is_one_update():
+    """fql_profile_update issues the update's launches eagerly, each dispatch carrying its event pair: the launch mode no other test
+    runs for IFQL's kernels.  It reports every launch of the plan, in order, with a device time, and leaves the state one
+    update_from_dataset on the same engine-drawn rows leaves."""
+    from tests.util import read_plan
+    cfg, ds, _, _ = _problem(seed=5)
+    B = cfg['batch_size']
+    a, b = _agent(cfg, ds), _agent(cfg, ds)
+    for x in (a, b):
+        x.upload_dataset(ds)
+    f = a._lib.fql_profile_update
+    f.restype = C.c_int
+    f.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 6
+    cap = 1024
+    typ, lane, grid = (C.c_int * cap)(), (C.c_int * cap)(), (C.c_int * cap)()
+    us, macs, null_us = (C.c_float * cap)(), (C.c_double * cap)(), C.c_float()
+    n = f(a._h, B, cap, typ, lane, grid, us, macs, C.byref(null_us))
+    assert n == a.stats()['launches_per_update']
+    assert list(typ[:n]) == [L['type'] for L in read_plan(a)]
+    assert all(np.isfinite(us[i]) and us[i] > 0 for i in range(n)), list(us[:n])
+    b.update_from_dataset(batch_size=B)
+    a.synchronize(); b.synchronize()
+    _same_state(a, b)
+
+
 def test_sample_actions_best_of_n_and_flow_actions():
     cfg, _, batch, _ = _problem(seed=6)
     params = _randomized(IO.init_params(8, OD, AD, cfg), 8)   # known on the host: the margins below hold for these params and noises
