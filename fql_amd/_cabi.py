@@ -22,6 +22,7 @@ FQL_BC_NUM_INFO = 4
 FQL_IQL_AWR_NUM_INFO = 16
 FQL_IQL_DDPGBC_NUM_INFO = 19
 FQL_IQLD_NUM_INFO = 21
+FQL_CFGRL_NUM_INFO = 4
 FQL_OK, FQL_E_INVALID, FQL_E_NODEVICE, FQL_E_HIP, FQL_E_STATE, FQL_E_NOTFOUND = 0, -1, -2, -3, -4, -5
 
 
@@ -62,6 +63,12 @@ class FqlIqldConfig(C.Structure):
     _fields_ = [('actor_lr', C.c_float), ('value_lr', C.c_float), ('critic_lr', C.c_float), ('expectile', C.c_float),
                 ('awr_temperature', C.c_float), ('softmax_beta', C.c_float), ('optimal_var', C.c_int32), ('target_extraction', C.c_int32),
                 ('denoise_steps', C.c_int32), ('opt_decay_schedule', C.c_int32), ('reserved', C.c_int32 * 6)]
+
+
+class FqlCfgrlConfig(C.Structure):
+    _fields_ = [('goal_dim', C.c_int32), ('flow_steps', C.c_int32), ('cfg', C.c_float), ('actor_geom_sample', C.c_int32),
+                ('p_uncond', C.c_double), ('actor_p_curgoal', C.c_double), ('actor_p_trajgoal', C.c_double),
+                ('actor_p_randomgoal', C.c_double), ('reserved', C.c_int32 * 6)]
 
 
 class FqlBcConfig(C.Structure):
@@ -172,6 +179,15 @@ SYMBOLS = {
     'fql_iqld_get_steps': (_I, [_VP, C.POINTER(_I64)]),
     'fql_iqld_set_steps': (_I, [_VP, C.POINTER(_I64)]),
     'fql_iqld_stats': (_I, [_VP, _I, _I, C.POINTER(_I64), C.POINTER(_I64), C.POINTER(_I64)]),
+    'fql_cfgrl_default_config': (None, [C.POINTER(FqlCfgrlConfig)]),
+    'fql_cfgrl_create': (_I, [C.POINTER(FqlConfig), C.POINTER(FqlCfgrlConfig), _U64, C.POINTER(_VP)]),
+    'fql_cfgrl_update': (_I, [_VP, _VP, _VP, _VP, _I, C.POINTER(FqlNoise), _VP, _VP, _VP]),
+    'fql_cfgrl_dataset_goals': (_I, [_VP, _VP, _VP]),
+    'fql_cfgrl_update_from_dataset': (_I, [_VP, _VP, _I, _I64, _I64, C.POINTER(FqlNoise), _VP, _VP, _VP]),
+    'fql_cfgrl_policy_loss': (_I, [_VP, _VP, _VP, _VP, _I, C.POINTER(FqlNoise), _VP, C.POINTER(_F), _VP]),
+    'fql_cfgrl_sample_actions': (_I, [_VP, _VP, _VP, _I, _VP, _U64, _F, _VP, _VP]),
+    'fql_cfgrl_read_rows': (_I, [_VP, _I, _VP, _VP, _VP, _VP, _VP, _I]),
+    'fql_cfgrl_stats': (_I, [_VP, C.POINTER(_I64), C.POINTER(_I64), C.POINTER(_I64)]),
     'fql_read_info_n': (_I, [_VP, _VP, _I]),
     'fql_info_wait_n': (_I, [_VP, _U64, _VP, _I]),
 }

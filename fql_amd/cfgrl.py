@@ -1,0 +1,241 @@
+"""Host-side mirror of the reference's CFGRLAgent (agents/cfgrl.py) over the C ABI: a goal-conditioned flow-matching policy trained with
+a per-row goal dropout and sampled with classifier-free guidance.
+
+actor_flow is GCActorVectorField: MLP((*actor_hidden_dims, act), GELU, LayerNorm optional) on [obs | goals | x_t | t]; unc_embed is the
+learned [1, goal_dim] row that stands in for the goal of a dropped row (probability 0.1) and for every goal of the unconditional pass of
+sample_actions.  Same call sites as the reference:
+
+    agent = CFGRLAgent.create(seed, example_batch, config)      # reads observations, actions, value_goals
+    agent, info = agent.update(batch)                           # reads observations, actions, actor_goals; info: CFGRL_INFO_KEYS
+    action = agent.sample_actions(observations=ob, goals=goal, seed=key)
+
+GCDataset.sample runs on the device: upload_dataset builds the per-row `final` table from `terminals`, and update_from_dataset draws
+idx, the goal of each row from its own trajectory (utils/datasets.py:224-255, actor_p_curgoal / trajgoal / randomgoal) and the dropout
+mask there.  read_rows() returns the raw 32-bit draws of the last update, so the rule can be restated on the host from the same draws.
+
+State observations, fp32 and GELU only: `encoder`, precision 'bf16x3', rng other than 'engine', frame stacking and actor_geom_sample
+are refused here, before the library is called.  Checkpoints (TrainState key 'network'), get/set_params and synchronize are FQLAgent's
+plumbing on a CFGRL handle.
+"""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+
+from . import _cabi
+from .agent import KindAgent, _Arg, _PendingN
+from .config import ConfigDict
+
+CFGRL_INFO_KEYS = ('actor/actor_loss', 'grad/max', 'grad/min', 'grad/norm')
+CFGRL_NOISE_KEYS = ('x0', 't')
+CFGRL_DRAW_KEYS = ('idx', 'random', 'dist', 'traj', 'cur', 'mask')   # rows of read_rows()['draws']
+P_UNCOND = 0.1   # agents/cfgrl.py:34
+
+
+def get_config():
+    """agents/cfgrl.py:162-191 (same keys and defaults), plus the engine's own 'rng' and 'precision' keys."""
+    return ConfigDict(
+        agent_name='cfgrl',
+        lr=3e-4,
+        batch_size=1024,
+        actor_hidden_dims=(512, 512, 512, 512),
+        actor_layer_norm=False,
+        discount=0.99,
+        flow_steps=16,
+        cfg=3.0,
+        encoder=None,
+        action_dim=None,
+        dataset_class='GCDataset',
+        value_p_curgoal=0.0,
+        value_p_trajgoal=1.0,
+        value_p_randomgoal=0.0,
+        value_geom_sample=False,
+        actor_p_curgoal=0.0,
+        actor_p_trajgoal=1.0,
+        actor_p_randomgoal=0.0,
+        actor_geom_sample=False,
+        gc_negative=True,
+        p_aug=0.0,
+        frame_stack=None,
+        rng='engine',  # not a reference key: device Philox noise or explicit tensors
+        precision='fp32',  # not a reference key: fp32 only
+    )
+
+
+def final_indices(terminals):
+    """utils/datasets.py:151-153,234: per row, the last row of its trajectory, terminal_locs[searchsorted(terminal_locs, i)]."""
+    (terminal_locs,) = np.nonzero(np.asarray(terminals) > 0)
+    n = len(terminals)
+    assert len(terminal_locs) and terminal_locs[-1] == n - 1, 'the last row of the dataset must be terminal'
+    return terminal_locs[np.searchsorted(terminal_locs, np.arange(n))].astype(np.int64)
+
+
+class CFGRLAgent(KindAgent):
+    """CFGRL agent backed by the MI355X step engine.  update: agents/cfgrl.py:58-68, 4 infos (CFGRL_INFO_KEYS)."""
+
+    _name = 'CFGRL'
+    _refused = (('total_loss', 'total_loss (CFGRLAgent has policy_loss)'),
+                ('compute_flow_actions', 'compute_flow_actions (sample_actions(noises=) is the flow)'),
+                ('create_replay_buffer', 'the replay ring'), ('update_balanced', 'balanced sampling'),
+                ('add_transition', 'ring inserts (the goal table describes the uploaded rows)'))
+    _update_dataset_fn = 'fql_cfgrl_update_from_dataset'
+    _loss_infos = 1
+    _pending_cls = _PendingN
+    _train_state_key = 'network'   # agents/cfgrl.py:19: the TrainState's field name (checkpoint layout)
+
+    @classmethod
+    def create(cls, seed, example_batch, config):
+        """agents/cfgrl.py:102-159.  `example_batch`: observations, actions and value_goals (goal_dim is its last axis)."""
+        cfg = get_config()
+        cfg.update(dict(config))
+        cls._refuse_config(cfg)
+        if cfg.get('actor_geom_sample'):
+            raise NotImplementedError('CFGRL: actor_geom_sample=True is not built (uniform trajectory goals only)')
+        if cfg.get('frame_stack') is not None:
+            raise NotImplementedError('CFGRL: frame_stack is not built (state observations only)')
+        if int(cfg['flow_steps']) < 1:
+            raise ValueError('flow_steps must be >= 1')
+        psum = float(cfg['actor_p_curgoal']) + float(cfg['actor_p_trajgoal']) + float(cfg['actor_p_randomgoal'])
+        if not np.isclose(psum, 1.0):   # utils/datasets.py:159-161
+            raise ValueError('actor_p_curgoal + actor_p_trajgoal + actor_p_randomgoal must be 1')
+        for k in ('observations', 'actions', 'value_goals'):
+            if k not in example_batch:
+                raise KeyError(f'example_batch is missing {k!r}')
+        lib = _cabi.load()
+        # fql_config mapping (include/fql_amd.h): actor_hidden_dims -> actor_hidden, actor_layer_norm, lr
+        ec = dict(actor_hidden_dims=tuple(cfg['actor_hidden_dims']), value_hidden_dims=tuple(cfg['actor_hidden_dims']), layer_norm=False,
+                  actor_layer_norm=bool(cfg['actor_layer_norm']), lr=cfg['lr'], discount=cfg['discount'], tau=0.005, flow_steps=1,
+                  batch_size=cfg['batch_size'], precision='fp32', encoder=None)
+        c, ob_dims, action_dim = cls._engine_config(lib, ec, example_batch['observations'], example_batch['actions'])
+        gc = _cabi.FqlCfgrlConfig()
+        lib.fql_cfgrl_default_config(C.byref(gc))
+        gc.goal_dim = int(example_batch['value_goals'].shape[-1])
+        gc.flow_steps, gc.cfg, gc.p_uncond = int(cfg['flow_steps']), float(cfg['cfg']), P_UNCOND
+        gc.actor_p_curgoal, gc.actor_p_trajgoal = float(cfg['actor_p_curgoal']), float(cfg['actor_p_trajgoal'])
+        gc.actor_p_randomgoal, gc.actor_geom_sample = float(cfg['actor_p_randomgoal']), 0
+        h = C.c_void_p()
+        _cabi.check(lib, None, lib.fql_cfgrl_create(C.byref(c), C.byref(gc), int(seed) & 0xFFFFFFFFFFFFFFFF, C.byref(h)))
+        cfg['ob_dims'] = ob_dims
+        cfg['action_dim'] = action_dim
+        cfg['goal_dim'] = int(gc.goal_dim)
+        return cls(h, cfg, int(seed))
+
+    def _batch_args(self, batch):   # CFGRL reads observations, actions and actor_goals of the goal-conditioned batch
+        for k in ('observations', 'actions', 'actor_goals'):
+            if k not in batch:
+                raise KeyError(f'batch is missing {k!r}')
+        B = int(batch['actions'].shape[0]) if hasattr(batch['actions'], 'shape') else int(np.shape(batch['actions'])[0])
+        od, ad, G = self.config['ob_dims'][0], self.config['action_dim'], self.config['goal_dim']
+        return B, [_Arg(batch['observations'], (B, od)), _Arg(batch['actions'], (B, ad)), _Arg(batch['actor_goals'], (B, G))]
+
+    def _noise_args(self, noise, B):
+        """Explicit x0 [B, act] and t [B] or [B, 1] (agents/cfgrl.py:27-29); other keys are refused."""
+        if noise is None:
+            return None, []
+        extra = set(noise) - set(CFGRL_NOISE_KEYS)
+        if extra:
+            raise ValueError(f'CFGRL reads only {CFGRL_NOISE_KEYS} of the noise dict, got {sorted(extra)}')
+        x0, ta = _Arg(noise.get('x0'), (B, self.config['action_dim'])), _Arg(noise.get('t'), (B,))
+        return _cabi.FqlNoise(None, x0.ptr, ta.ptr, None, None), [x0, ta]
+
+    @staticmethod
+    def _mask_arg(do_cfg, B):
+        """[B] booleans as bytes (agents/cfgrl.py:34), or None = the engine's draw."""
+        if do_cfg is None:
+            return _Arg(None)
+        if hasattr(do_cfg, 'data_ptr'):
+            do_cfg = do_cfg != 0
+        else:
+            do_cfg = np.asarray(do_cfg) != 0
+        return _Arg(do_cfg, (B,), u8=True)
+
+    def update(self, batch, noise=None, do_cfg=None, want_info=True):
+        """agents/cfgrl.py:58-68.  `noise`: explicit x0 / t; `do_cfg`: the explicit [B] dropout mask.  Returns (agent, info)."""
+        B, args = self._batch_args(batch)
+        self._ensure_batch(B)
+        nz, nargs = self._noise_args(noise, B)
+        m = self._mask_arg(do_cfg, B)
+        stream = self._stream(args + nargs + [m])
+        self._check(self._lib.fql_cfgrl_update(self._h, *[a.ptr for a in args], B, C.byref(nz) if nz else None, m.ptr, None, stream))
+        self._keep = (args, nargs, m)
+        return self, (self._lazy_info(stream) if want_info else None)
+
+    def policy_loss(self, batch, grad_params=None, rng=None, noise=None, do_cfg=None):
+        """agents/cfgrl.py:22-42 with the stored parameters: (loss, {'actor_loss': loss}).  No state changes."""
+        self._probe_guard('actor_loss with traced grad_params', grad_params, rng)
+        B, args = self._batch_args(batch)
+        self._ensure_batch(B)
+        nz, nargs = self._noise_args(noise, B)
+        m = self._mask_arg(do_cfg, B)
+        loss = C.c_float()
+        self._check(self._lib.fql_cfgrl_policy_loss(self._h, *[a.ptr for a in args], B, C.byref(nz) if nz else None, m.ptr, C.byref(loss),
+                                                    self._stream(args + nargs + [m])))
+        return float(loss.value), {'actor_loss': float(loss.value)}
+
+    def upload_dataset(self, dataset, capacity=None):
+        """GCDataset(Dataset.create(...)) -> HBM: the transitions, the per-row `final` table built from `terminals` (the last row must be
+        terminal, utils/datasets.py:153) and `oracle_reps` as the goal representations when the dataset has that key."""
+        final = final_indices(dataset['terminals'])
+        n = int(len(dataset['observations']))
+        od, ad = self.config['ob_dims'][0], self.config['action_dim']
+        zeros = np.zeros(n, np.float32)   # CFGRL reads neither rewards, masks nor next_observations (compact datasets have none)
+        args = [_Arg(dataset['observations'], (n, od)), _Arg(dataset['actions'], (n, ad)), _Arg(zeros), _Arg(zeros),
+                _Arg(dataset['observations'], (n, od))]
+        self._check(self._lib.fql_dataset_upload(self._h, n, int(capacity) if capacity is not None else max(n, 1), *[a.ptr for a in args]))
+        reps = _Arg(dataset['oracle_reps'], (n, self.config['goal_dim'])) if 'oracle_reps' in dataset else _Arg(None)
+        self._check(self._lib.fql_cfgrl_dataset_goals(self._h, final.ctypes.data, reps.ptr))
+
+    def update_from_dataset(self, batch_size=None, idxs=None, noise=None, shard=(0, 0), want_info=False, stream=None, do_cfg=None):
+        """GCDataset.sample(B) + update(batch) without leaving the device."""
+        B = int(batch_size or self.config['batch_size'])
+        m = self._mask_arg(do_cfg, B)
+        out = super().update_from_dataset(batch_size, idxs, noise, shard, want_info, stream, _extra=(m.ptr,))
+        self._keep = (self._keep, m)
+        return out
+
+    def read_rows(self, probe=False):
+        """The rows of the last update (probe=True: of the last policy_loss): idx, goal_idx (-1 where the goals came with the batch),
+        do_cfg, the raw 32-bit draws by name (CFGRL_DRAW_KEYS) and the goal columns of the assembled input rows."""
+        B, G = int(self.config['batch_size']), self.config['goal_dim']
+        idx, gi = np.empty(B, np.int64), np.empty(B, np.int64)
+        m, dr, goals = np.empty(B, np.uint8), np.empty((len(CFGRL_DRAW_KEYS), B), np.uint32), np.empty((B, G), np.float32)
+        self._check(self._lib.fql_cfgrl_read_rows(self._h, int(bool(probe)), idx.ctypes.data, gi.ctypes.data, m.ctypes.data, dr.ctypes.data,
+                                                  goals.ctypes.data, B))
+        return {'idx': idx, 'goal_idx': gi, 'do_cfg': m.astype(bool), 'draws': dict(zip(CFGRL_DRAW_KEYS, dr)), 'goals': goals}
+
+    def sample_actions(self, observations, goals=None, seed=None, temperature=1.0, cfg=None, noises=None):
+        """agents/cfgrl.py:70-100: x ~ N(0, I); flow_steps times v = v_unc + cfg (v_cond - v_unc), x += v / flow_steps; clip.  [od] with
+        [G] -> [act]; [n, od] with [n, G], or with one [G] for every row, -> [n, act], row by row the single-observation result.
+        `cfg=None`: the config's value.  `noises`: x with the shape [n, act] (or [act]), or None = engine RNG keyed by `seed`.
+        `temperature` is accepted and ignored, as in the reference."""
+        if goals is None:
+            raise ValueError('CFGRL: sample_actions needs goals (the conditional pass reads them, agents/cfgrl.py:93)')
+        od, ad, G = self.config['ob_dims'][0], self.config['action_dim'], self.config['goal_dim']
+        if not hasattr(observations, 'shape'):
+            observations = np.asarray(observations, dtype=np.float32)
+        if not hasattr(goals, 'shape'):
+            goals = np.asarray(goals, dtype=np.float32)
+        if int(observations.shape[-1]) != od or len(observations.shape) > 2:
+            raise ValueError(f'observations must be [{od}] or [n, {od}], got {tuple(observations.shape)}')
+        n = int(observations.shape[0]) if len(observations.shape) == 2 else 1
+        if int(goals.shape[-1]) != G or tuple(goals.shape[:-1]) not in ((), (1,), (n,)):
+            raise ValueError(f'goals must be [{G}] or [{n}, {G}], got {tuple(goals.shape)}')
+        if int(np.prod(goals.shape)) == G and n > 1:   # one goal for every row
+            goals = goals.reshape(1, G).expand(n, G) if hasattr(goals, 'data_ptr') else np.broadcast_to(np.reshape(goals, (1, G)), (n, G))
+        shape = (ad,) if n == 1 else (n, ad)
+        o, g, z = _Arg(observations, (n, od)), _Arg(goals, (n, G)), _Arg(noises, (n, ad))
+        out, optr = self._actions_out(observations, shape)
+        scale = float(self.config['cfg'] if cfg is None else cfg)
+        self._check(self._lib.fql_cfgrl_sample_actions(self._h, o.ptr, g.ptr, n, z.ptr, self._sample_seed(seed, noises), scale, optr,
+                                                       self._stream([o, g, z])))
+        return out
+
+    def cfgrl_stats(self):
+        """(launches of one update, MACs of one update, launches of one sampling call of <= 2048 observations)."""
+        la, ma, ls = C.c_int64(), C.c_int64(), C.c_int64()
+        self._check(self._lib.fql_cfgrl_stats(self._h, C.byref(la), C.byref(ma), C.byref(ls)))
+        return int(la.value), int(ma.value), int(ls.value)
+
+
+__all__ = ['CFGRLAgent', 'CFGRL_INFO_KEYS', 'CFGRL_NOISE_KEYS', 'CFGRL_DRAW_KEYS', 'get_config', 'final_indices']

@@ -20,6 +20,7 @@
 #include "fql_bc.h"
 #include "fql_iql.h"
 #include "fql_iqld.h"
+#include "fql_cfgrl.h"
 #include <hip/hip_ext.h>
 #include "fql_aql.h"
 
@@ -145,7 +146,9 @@ enum OpType { OP_GEMM, OP_GEMM64, OP_WGRAD, OP_LNBWD, OP_PREP, OP_POSTOS, OP_EUL
               OP_IQL_PREP, OP_IQL_HEAD, OP_IQL_LOSS_AWR, OP_IQL_LOSS_DDPGBC, OP_IQL_AGRAD, OP_IQL_FIN,
               // IQL-diffusion (agents/iql_diffusion.py) only: after IQL's
               OP_IQLD_PREP, OP_IQLD_LOSS_C, OP_IQLD_WEIGHT, OP_IQLD_LOSS_A, OP_IQLD_EGRAD, OP_IQLD_FIN, OP_IQLD_STEPBIAS, OP_IQLD_LAYER0,
-              OP_IQLD_CFG, OP_NUM_TYPES };
+              OP_IQLD_CFG,
+              // CFGRL (agents/cfgrl.py) only: after IQL-diffusion's
+              OP_CFGRL_PREP, OP_CFGRL_EGRAD, OP_CFGRL_FIN, OP_CFGRL_LAYER0, OP_NUM_TYPES };
 
 // A launch bound where its op is emitted (every agent op, OP_IFQL_PREP and later): the kernel, a 1-D grid and the packed arguments,
 // always FQL_THREADS threads and no LDS.  issue() launches it as it stands, so such an op has no payload member and no case of its own.
@@ -358,8 +361,8 @@ struct EncBuf {
 // ------------------------------------------------------------------------------------------------
 // agent kinds: what a handle is, and what the engine says about it
 // ------------------------------------------------------------------------------------------------
-enum class AgentKind { FQL, IFQL, REBRAC, SAC, BC, IQL, IQLD };
-constexpr int kNumKinds = 7;
+enum class AgentKind { FQL, IFQL, REBRAC, SAC, BC, IQL, IQLD, CFGRL };
+constexpr int kNumKinds = 8;
 
 const char* const k_info_names[FQL_NUM_INFO] = {
     "critic/critic_loss", "critic/q_mean", "critic/q_max", "critic/q_min", "actor/actor_loss",
@@ -385,6 +388,7 @@ const char* const k_iqld_info_names[FQL_IQLD_NUM_INFO] = {
     "critic_loss", "q", "value_loss", "v", "v_min", "v_max", "actor_q", "actor_loss", "actor_positive_ratio", "actor_loss_positive",
     "actor_loss_uncond", "o_mean", "o_std", "o_min", "o_max", "effective_batch_size", "loss_weights_top_10_mass", "loss_weights_max",
     "grad/max", "grad/min", "grad/norm"};
+const char* const k_cfgrl_info_names[FQL_CFGRL_NUM_INFO] = {"actor/actor_loss", "grad/max", "grad/min", "grad/norm"};
 
 enum { NZ_EPS1 = 1, NZ_X0 = 2, NZ_T = 4, NZ_Z = 8, NZ_EPS2 = 16 };   // the fields of fql_noise
 // One row per kind, indexed by AgentKind.  A new agent adds a row here and a column to k_admission (C ABI, below).
@@ -411,6 +415,8 @@ const KindDesc k_kinds[kNumKinds] = {
      "IQL reads only eps1 of fql_noise (x0, t, z and eps2 must be NULL)"},
     {"IQL-diffusion", "an IQL-diffusion handle", "fql_iqld_create", k_iqld_info_names, FQL_IQLD_NUM_INFO, NZ_X0 | NZ_T,
      "IQL-diffusion reads only x0 and t of fql_noise (eps1, z and eps2 must be NULL)"},
+    {"CFGRL", "a CFGRL handle", "fql_cfgrl_create", k_cfgrl_info_names, FQL_CFGRL_NUM_INFO, NZ_X0 | NZ_T,
+     "CFGRL reads only x0 and t of fql_noise (eps1, z and eps2 must be NULL)"},
 };
 
 }  // namespace
@@ -474,6 +480,24 @@ struct fql_engine {
     float *w_lw = nullptr, *rows_buf = nullptr;   // [B] loss weights; [2][3][B]
     Program prog_actor, prog_none;
     float sample_cfg = 1.0f;                      // cfg of the sampling call in flight (read when its step launches are issued)
+    // CFGRL agent (agents/cfgrl.py; fql_cfgrl_create): the arena holds actor_flow in the NET_BC slot (input [obs | goal | x_t | t]) and
+    // modules_unc_embed/Embed_0/embedding ([1, G], padded to 16 floats) behind it at emb_off; every other net is empty, so critic_size = 0
+    // and Adam has no Polyak range, as on a BC handle.  One lane: prep, forward, loss, backward, embedding gradient, Adam, finalize.
+    // Where a step's goals and mask come from travels in d_gsrc (CfgrlSrc), rewritten only when it changes, as d_src is.  The goal draw of
+    // update_from_dataset reads ds_final / ds_reps (fql_cfgrl_dataset_goals).  The per-row read-back (cf_rows, cf_draws, cf_mask) has two
+    // halves: the last update's, then the last loss probe's.
+    fql_cfgrl_config gcfg{};
+    CfgrlSrc* d_gsrc = nullptr;
+    CfgrlSrc* h_gsrc_ring = nullptr;
+    CfgrlSrc h_gsrc_shadow{};
+    bool gsrc_valid = false;
+    int gsrc_ring_pos = 0;
+    int64_t* ds_final = nullptr;
+    float* ds_reps = nullptr;
+    float* in_goal = nullptr;                     // [B, G] staging of host goals
+    unsigned char *in_cfg = nullptr, *cf_mask = nullptr;   // [B] staging of a host mask; [2][B] do_cfg
+    int64_t* cf_rows = nullptr;                   // [2][2][B]
+    uint32_t* cf_draws = nullptr;                 // [2][CFGRL_NUM_DRAWS][B]
     bool own_info() const { return kind == AgentKind::IQL || kind == AgentKind::IQLD; }
     uint64_t seed = 0;
     int device = 0;
@@ -581,6 +605,7 @@ struct fql_engine {
         PassBuf p_os, p_eu;
         Program prog_os, prog_flow;
         float *st_obs = nullptr, *st_noise = nullptr, *st_out = nullptr;
+        float* st_goal = nullptr;   // CFGRL: staging of host goals [half, G]
         // visual agents: the rows are images; they pass through the module's encoder first (agents/fql.py:162-163, networks.py:221)
         unsigned char* st_img = nullptr;
         EncBuf eb_os, eb_bc;
@@ -648,7 +673,7 @@ struct fql_engine {
         auto actor = [&](int in, int out) { return make(in, cfg.actor_hidden, cfg.num_actor_hidden, out, cfg.actor_layer_norm != 0); };
         auto value = [&](int in) { return make(in, cfg.value_hidden, cfg.num_value_hidden, 1, cfg.layer_norm != 0); };
         for (Net& n : nets) n = Net{};
-        if (kind != AgentKind::BC) nets[NET_C0] = value(od + ad);
+        if (kind != AgentKind::BC && kind != AgentKind::CFGRL) nets[NET_C0] = value(od + ad);
         switch (kind) {
             case AgentKind::FQL: nets[NET_BC] = actor(od + ad + 1, ad); nets[NET_OS] = actor(od + ad, ad); break;
             case AgentKind::IFQL: nets[NET_BC] = actor(od + ad + 1, ad); nets[NET_OS] = value(od); break;   // value (agents/ifql.py:188-193)
@@ -657,6 +682,7 @@ struct fql_engine {
             case AgentKind::BC: nets[NET_BC] = actor(od + ad + BC_EMB, ad); break;                           // policy(obs, x_t, emb(t)) (agents/bc.py:26-44)
             case AgentKind::IQL: nets[NET_BC] = actor(od, ad); nets[NET_OS] = value(od); break;
             case AgentKind::IQLD: nets[NET_BC] = actor(od + ad + BC_EMB + IQLD_EMBED, ad); nets[NET_OS] = value(od); break;   // iql_diffusion.py:54-67
+            case AgentKind::CFGRL: nets[NET_BC] = actor(od + gcfg.goal_dim + ad + 1, ad); break;               // actor_flow(obs, goals, x_t, t) (utils/networks.py:237-284)
         }
         nets[NET_C1] = nets[NET_T0] = nets[NET_T1] = nets[NET_C0];
         size_t off = 0;
@@ -710,6 +736,7 @@ struct fql_engine {
                 if (kind == AgentKind::SAC) { alpha_off = off; off += 4; }   // modules_alpha/log_value: one float, padded to an Adam quad
                 if (kind == AgentKind::IQL && !qcfg.const_std) { ls_off = off; off += pad16(ad); }   // modules_actor/log_stds: [act], padded to ap
                 if (kind == AgentKind::IQLD) { emb_off = off; off += 2 * IQLD_EMBED; }               // actor/Embed_0/embedding: [2, 32]
+                if (kind == AgentKind::CFGRL) { emb_off = off; off += pad16(gcfg.goal_dim); }        // modules_unc_embed/Embed_0/embedding: [1, G], padded
                 n_train = off;
             }
             if (ni == NET_T1) place_enc(ENC_T);
@@ -826,6 +853,8 @@ struct fql_engine {
         const Mod iqld_mods[3] = {{"critic", "value_net", NET_C0, NET_C1, true, ENC_C},
                                   {"target_critic", "value_net", NET_T0, NET_T1, false, ENC_T},
                                   {"value", "value_net", NET_OS, -1, true, ENC_OS}};
+        // CFGRL (agents/cfgrl.py:143-156): one ModuleDict, actor_flow and the [1, G] embedding behind it
+        const Mod cfgrl_mods[1] = {{"modules_actor_flow", "mlp", NET_BC, -1, true, ENC_BC}};
         const Mod* mods = nullptr;   // BC: no modules, the leaves of one bare net
         int nmods = 4;
         const char* bare = nullptr;  // prefix of the bare policy net's leaves (BC: none, IQL-diffusion: its `actor` field)
@@ -837,6 +866,7 @@ struct fql_engine {
             case AgentKind::BC: bare = ""; nmods = 0; break;
             case AgentKind::IQL: mods = iql_mods; break;
             case AgentKind::IQLD: bare = "actor/"; mods = iqld_mods; nmods = 3; break;
+            case AgentKind::CFGRL: mods = cfgrl_mods; nmods = 1; break;
         }
         int tid = 0;
         if (bare) {   // agents/bc.py:26-44: a bare TrainState: Dense_0 (the head), then MLP_0/Dense_i and MLP_0/LayerNorm_i (jax dict order)
@@ -959,6 +989,16 @@ struct fql_engine {
                 add(hb + "kernel", true, a.in, a.out, a.w, 0, a.in_p, a.out_p);
             }
         }
+        if (kind == AgentKind::CFGRL) {   // nn.Embed(1, goal_dim): "modules_unc_embed" sorts behind "modules_actor_flow"
+            Leaf lf;
+            lf.name = "modules_unc_embed/Embed_0/embedding";
+            lf.ndim = 2;
+            lf.shape[0] = 1; lf.shape[1] = gcfg.goal_dim; lf.shape[2] = lf.shape[3] = 1;
+            lf.segs.push_back(Segment{emb_off, 1, gcfg.goal_dim, 1, pad16(gcfg.goal_dim)});
+            lf.trainable = true;
+            lf.train_id = tid++;
+            leaves.push_back(lf);
+        }
         n_train_leaves = tid;
         if (n_train_leaves > 256) invalid("too many trainable leaves (%d)", n_train_leaves);
         // Adam chunks: contiguous pieces of one leaf, <= 4096 elements
@@ -989,7 +1029,8 @@ struct fql_engine {
                 {"modules_actor/", "modules_alpha/", "modules_critic/"},
                 {nullptr, nullptr, nullptr},                                // (BC, one module: every chunk)
                 {"modules_actor/", "modules_value/", "modules_critic/"},
-                {"actor/", "value/", "critic/"}};
+                {"actor/", "value/", "critic/"},
+                {nullptr, nullptr, nullptr}};                               // (CFGRL, one TrainState: every chunk)
             const char* const* mods = trained[(int)kind];
             for (int m = 0; m < 3; ++m) {
                 if (!mods[m]) { mod_chunk0[m] = 0; mod_chunkn[m] = n_chunks; continue; }
@@ -1090,6 +1131,12 @@ struct fql_engine {
             // 'normal' is the untruncated N(0, 1 / fan_in)
             std::normal_distribution<double> Nd(0.0, std::sqrt(1.0 / (double)IQLD_EMBED));
             for (int i = 0; i < 2 * IQLD_EMBED; ++i) h[emb_off + i] = (float)Nd(gen);
+        }
+        if (kind == AgentKind::CFGRL) {
+            // nn.Embed(1, G): variance_scaling(1.0, 'fan_in', 'normal', out_axis=0) on [1, G].  By the derivation above in_size = out_size = 1,
+            // receptive field = G, fan_in = G: the untruncated N(0, 1 / G)
+            std::normal_distribution<double> Nd(0.0, std::sqrt(1.0 / (double)gcfg.goal_dim));
+            for (int i = 0; i < gcfg.goal_dim; ++i) h[emb_off + i] = (float)Nd(gen);
         }
         std::memcpy(h.data() + n_train, h.data(), critic_size * sizeof(float));
         HIP_CHECK(hipMemcpy(P, h.data(), n_total * sizeof(float), hipMemcpyHostToDevice));
@@ -3302,6 +3349,91 @@ struct fql_engine {
         split_ok = false;
         src_valid = false;
     }
+    // ---------------------------------------------------------------------------------------
+    // the CFGRL update as a program (agents/cfgrl.py:22-68): BC's single lane with a goal block in the input rows.  Batch assembly (index,
+    // goal and mask draw, gather, the goal columns of a dropped row from the CURRENT unc_embed leaf) -> actor_flow forward -> flow-matching
+    // loss -> backward (no input-gradient pass) -> the embedding gradient from dZ0 of the dropped rows -> Adam over every chunk -> finalize.
+    // with_grads = false: the loss probe (it writes info slot 5 and the probe half of the row read-back only).
+    // ---------------------------------------------------------------------------------------
+    void build_cfgrl_program(Program& pr, bool with_grads) {
+        const int od = cfg.obs_dim, ad = cfg.act_dim, ap = pad16(ad), Gd = gcfg.goal_dim;
+        DevState* st = d_state;
+        const void* I_L = &st->info[CFGRL_I_LOSS];
+        const int half = with_grads ? 0 : 1;
+        unsigned char* mask = cf_mask + (size_t)half * B;
+        int64_t* rows = cf_rows + (size_t)half * 2 * B;
+        uint32_t* draws = cf_draws + (size_t)half * CFGRL_NUM_DRAWS * B;
+        const Layer& l0 = nets[NET_BC].layers[0];
+        wide_tiles = true;
+        allow64 = true;
+        lane0_64 = true;
+        emit_lane = 0;
+        {
+            Op op{};
+            op.type = OP_CFGRL_PREP;
+            const CfgrlPrepArgs gp{d_src, d_gsrc, st, seed, P + emb_off, B, od, Gd, ad, nets[NET_BC].in_p(), ap, X_bc, vel, rows, draws, mask};
+            op.k = bind(fql_cfgrl_prep_kernel, (gp.B + 3) / 4, gp);
+            op.reads = {P + emb_off};
+            op.writes = {X_bc, vel, mask, rows, draws};
+            push(pr, op);
+        }
+        emit_forward(pr, p_bc, with_grads);   // actor_flow(obs, x_t, t, goals)  cfgrl.py:37
+        {
+            Op op{};
+            op.type = OP_LOSS_BC;              // mean((pred - vel)^2) over B act elements  cfgrl.py:38
+            op.lb = LossBcArgs{p_bc.out, vel, with_grads ? p_bc.dz.back() : nullptr, st, B, ad, ap, with_grads ? 1 : 0};
+            op.reads = {p_bc.out, vel};
+            op.writes = {I_L};
+            if (with_grads) op.writes.push_back(p_bc.dz.back());
+            push(pr, op);
+        }
+        if (with_grads) {
+            emit_backward(pr, p_bc, 0, B, true, false);
+            {
+                Op op{};
+                op.type = OP_CFGRL_EGRAD;
+                const CfgrlEmbedGradArgs eg{p_bc.dz[0], P + l0.w + (size_t)od * l0.out_p, mask, G + emb_off, B, l0.out_p, Gd};
+                op.k = bind(fql_cfgrl_embed_grad_kernel, 1, eg);
+                op.reads = {p_bc.dz[0], P + l0.w, mask};
+                op.writes = {G + emb_off};
+                push(pr, op);
+            }
+            adam_for(pr, 0, {NET_BC}, 0, -2);   // every chunk in one launch; critic_size = 0: no Polyak range
+            Op& a = pr.ops.back();
+            a.reads.push_back(G + emb_off);
+            a.writes.push_back(P + emb_off);
+            Op f{};
+            f.type = OP_CFGRL_FIN;
+            f.k = bind(fql_cfgrl_finalize_kernel, 1, fin_args(1));
+            f.k.tl_at = offsetof(FinalizeArgs, tl);
+            f.reads = {I_L, d_partials};
+            f.writes = {&st->info[0], &st->info[10], st};
+            push(pr, f);
+        }
+        lane0_64 = false;
+    }
+    void build_cfgrl_workspace() {
+        const int ap = pad16(cfg.act_dim), Gd = gcfg.goal_dim;
+        auto& W = ws_allocs;
+        X_bc = dalloc(W, (size_t)B * nets[NET_BC].in_p());
+        vel = dalloc(W, (size_t)B * ap);
+        in_goal = dalloc(W, (size_t)B * Gd);
+        in_cfg = (unsigned char*)dalloc(W, (size_t)(B + 3) / 4);
+        cf_mask = (unsigned char*)dalloc(W, (size_t)(2 * B + 3) / 4);
+        cf_rows = (int64_t*)dalloc(W, (size_t)2 * 2 * B * 2);
+        cf_draws = (uint32_t*)dalloc(W, (size_t)2 * CFGRL_NUM_DRAWS * B);
+        X_os = X_eu = X_c1 = X_c2 = X_ct = X_e0 = C0 = Vpart = w_act = tgt = w_rew = w_mask = nullptr;
+        fused_euler = euler_finish_fused = false;
+        p_bc = make_pass(W, NET_BC, B, X_bc, true, false);
+        build_cfgrl_program(prog_full, true);
+        build_cfgrl_program(prog_loss, false);
+        for (Program* pr : {&prog_full, &prog_loss}) schedule(*pr, W);
+        for (Program* pr : {&prog_full, &prog_loss}) capture(*pr);
+        split_ok = false;
+        src_valid = false;
+        gsrc_valid = false;
+    }
+
     // multiply-accumulates of one BC update per batch row, algorithmic: forward + backward without the input gradient
     int64_t bc_macs() const {
         int64_t m = 0;
@@ -3699,7 +3831,7 @@ struct fql_engine {
         switch (kind) {
             case AgentKind::REBRAC: return rebrac_macs(true);
             case AgentKind::SAC: return sac_macs();
-            case AgentKind::BC: return bc_macs();
+            case AgentKind::BC: case AgentKind::CFGRL: return bc_macs();
             case AgentKind::IQL: return iql_macs();
             case AgentKind::IQLD: return iqld_macs(true, true);
             default: break;
@@ -3767,6 +3899,7 @@ struct fql_engine {
             case AgentKind::BC: build_bc_workspace(); return;
             case AgentKind::IQL: build_iql_workspace(); return;
             case AgentKind::IQLD: build_iqld_workspace(); return;
+            case AgentKind::CFGRL: build_cfgrl_workspace(); return;
         }
         const int inp_c = nets[NET_OS].in_p(), inp_b = nets[NET_BC].in_p();
         X_os = dalloc(W, (size_t)3 * B * inp_c); X_bc = dalloc(W, (size_t)B * inp_b); X_eu = dalloc(W, (size_t)B * inp_b);
@@ -3914,6 +4047,69 @@ struct fql_engine {
         d.advance = advance;
         drain_staging(s);
         set_source(d, s);
+    }
+    void drop_goal_table() {   // the dataset's rows changed: the per-row `final` table and the representations no longer describe them
+        if (!ds_final && !ds_reps) return;
+        hipFree(ds_final); hipFree(ds_reps);
+        ds_final = nullptr; ds_reps = nullptr;
+        gsrc_valid = false;
+    }
+    // CFGRL: where the goals and the mask of the next step come from (CfgrlSrc), rewritten when it changes as set_source does
+    void set_goal_source(const CfgrlSrc& g, hipStream_t s) {
+        if (gsrc_valid && std::memcmp(&g, &h_gsrc_shadow, sizeof g) == 0) return;
+        CfgrlSrc* slot = &h_gsrc_ring[gsrc_ring_pos];
+        gsrc_ring_pos = (gsrc_ring_pos + 1) % 64;
+        std::memcpy(slot, &g, sizeof g);
+        hip_touch();
+        HIP_CHECK(hipMemcpyAsync(d_gsrc, slot, sizeof g, hipMemcpyHostToDevice, s));
+        std::memcpy(&h_gsrc_shadow, &g, sizeof g);
+        gsrc_valid = true;
+    }
+    CfgrlSrc goal_source(const float* goals, const unsigned char* do_cfg, hipStream_t s) {
+        CfgrlSrc g;
+        std::memset(&g, 0, sizeof g);   // (padding bytes too: set_goal_source compares the bytes)
+        g.goals = stage(goals, in_goal, (size_t)B * gcfg.goal_dim, s);
+        if (do_cfg) {
+            if (is_device_ptr(do_cfg)) g.do_cfg = do_cfg;
+            else {
+                hip_touch();
+                HIP_CHECK(hipMemcpyAsync(in_cfg, do_cfg, (size_t)B, hipMemcpyHostToDevice, s));
+                staged_host = true;
+                g.do_cfg = in_cfg;
+            }
+        }
+        g.final_idx = ds_final;
+        g.reps = ds_reps ? ds_reps : ds_obs;
+        g.n = ds_size;
+        g.all_cur = gcfg.actor_p_curgoal == 1.0 ? 1 : 0;
+        g.thr_traj = g.all_cur ? 0.0 : gcfg.actor_p_trajgoal / (1.0 - gcfg.actor_p_curgoal);   // utils/datasets.py:249
+        g.p_cur = gcfg.actor_p_curgoal;
+        g.thr_mask = (uint64_t)(gcfg.p_uncond * 4294967296.0);
+        return g;
+    }
+    // CFGRL batches carry observations, actions and actor_goals (agents/cfgrl.py:24-37); do_cfg: [B] bytes or null (engine RNG)
+    void cfgrl_source_from_batch(const float* obs, const float* act, const float* goals, const unsigned char* do_cfg, int batch,
+                                 const fql_noise* nz, int advance, hipStream_t s) {
+        if (batch != B) invalid("batch_size %d does not match the engine's workspace (%d); call fql_set_batch_size", batch, B);
+        if (!obs || !act || !goals) invalid("batch pointers must not be NULL (CFGRL batches carry actor_goals)");
+        SrcDesc d{};
+        d.obs = stage(obs, in_obs, (size_t)B * cfg.obs_dim, s);
+        d.act = stage(act, in_act, (size_t)B * cfg.act_dim, s);
+        fill_noise(d, nz, s);
+        d.advance = advance;
+        const CfgrlSrc g = goal_source(goals, do_cfg, s);
+        drain_staging(s);
+        set_source(d, s);
+        set_goal_source(g, s);
+    }
+    // GCDataset.sample on the device: the index draw of every update_from_dataset, then the goal of each row from its own trajectory
+    void cfgrl_source_from_dataset(const int64_t* idx, int batch, int64_t lo, int64_t hi, const fql_noise* nz, const unsigned char* do_cfg,
+                                   hipStream_t s) {
+        if (!ds_final) throw Invalid{"fql_cfgrl_update_from_dataset: no goal table (fql_cfgrl_dataset_goals after fql_dataset_upload)"};
+        source_from_dataset(idx, batch, lo, hi, nz, s);
+        const CfgrlSrc g = goal_source(nullptr, do_cfg, s);
+        drain_staging(s);
+        set_goal_source(g, s);
     }
     void fill_noise(SrcDesc& d, const fql_noise* nz, hipStream_t s) {
         const int ad = cfg.act_dim;
@@ -4173,6 +4369,59 @@ struct fql_engine {
             evals[n_pad] = std::move(ev);
             return ref;
         }
+        if (kind == AgentKind::CFGRL) {   // sample_actions with classifier-free guidance (prog_flow): IQL-diffusion's two halves, rows [0, half) the
+                    // conditional pass and [half, n_pad) the unconditional one.  C0 = [obs | goal or unc_embed] W0 + b0 of both halves at the head of
+                    // the program, then per Euler step layer 0 of both halves (one launch; t is one row of W0), layers 1.. of the 16-row Dense
+                    // kernel over n_pad rows, and fql_iqld_cfg_step_kernel (CFG combine + Euler add; the last one writes the clipped actions)
+            const int S = gcfg.flow_steps, ap = pad16(ad), half = n_pad / 2, Gd = gcfg.goal_dim;
+            const Net& n = nets[NET_BC];
+            const Layer& l0 = n.layers[0];
+            const int H = l0.out_p;
+            ev->X = dalloc(W, (size_t)n_pad * n.in_p());     // [obs | goal | 0] ; [obs | unc_embed | 0]
+            ev->Xf = dalloc(W, (size_t)half * ap);           // the flow's state x
+            float* C0e = dalloc(W, (size_t)n_pad * H);
+            ev->tgt = dalloc(W, (size_t)half * ap);
+            ev->st_obs = dalloc(W, (size_t)half * od);
+            ev->st_goal = dalloc(W, (size_t)half * Gd);
+            ev->st_noise = dalloc(W, (size_t)half * ad);
+            ev->st_out = dalloc(W, (size_t)half * ad);
+            ev->p_eu = make_pass(W, NET_BC, n_pad, ev->X, false, false);
+            emit_lane = 0;
+            Program& pr = ev->prog_flow;
+            {
+                Op op{};
+                op.type = OP_GEMM;
+                GemmTask& t = op.gemm;
+                t.A = ev->X; t.lda = l0.in_p; t.B = P + l0.w; t.ldb = H; t.bias = P + l0.b; t.C = C0e; t.ldc = H;
+                t.M = n_pad; t.N = H; t.K = l0.in_p; t.flags = GF_BIAS;
+                op.reads = {ev->X, t.B};
+                op.writes = {C0e};
+                push(pr, op);
+            }
+            for (int i = 0; i < S; ++i) {
+                Op op{};
+                op.type = OP_CFGRL_LAYER0;
+                const CfgrlLayer0Args gl0{C0e, ev->Xf, P + l0.w + (size_t)(od + Gd) * H, ev->p_eu.g[0], half, H, ad, ap,
+                                          (float)((double)i / (double)S)};   // cfgrl.py:90: a Python float, cast to fp32
+                op.k = bind(fql_cfgrl_layer0_kernel, (2 * gl0.n_pad * gl0.H + FQL_THREADS - 1) / FQL_THREADS, gl0);
+                op.reads = {C0e, ev->Xf, P + l0.w};
+                op.writes = {ev->p_eu.g[0]};
+                push(pr, op);
+                emit_forward(pr, ev->p_eu, false, 0, nullptr, nullptr, 0.f, 0.f, 1);
+                Op st{};
+                st.type = OP_IQLD_CFG;   // (issue() writes the call's cfg into this launch)
+                const IqldCfgStepArgs dstep{ev->p_eu.out, ev->Xf, i == S - 1 ? ev->tgt : nullptr, half, ad, ap, 1.0f, 1.0f / (float)S};
+                st.k = bind(fql_iqld_cfg_step_kernel, (dstep.n_pad * dstep.ad + FQL_THREADS - 1) / FQL_THREADS, dstep);
+                st.reads = {ev->p_eu.out};
+                st.writes = {ev->Xf};
+                if (i == S - 1) st.writes.push_back(ev->tgt);
+                push(pr, st);
+            }
+            schedule(pr, W);
+            Eval& ref = *ev;
+            evals[n_pad] = std::move(ev);
+            return ref;
+        }
         if (actor_on_obs()) {   // sample_actions: the actor's forward over the rows (prog_os on p_os; NET_OS is empty here)
             ev->X = dalloc(W, (size_t)n_pad * nets[NET_BC].in_p());
             ev->st_obs = dalloc(W, (size_t)n_pad * od);
@@ -4242,7 +4491,7 @@ struct fql_engine {
         for (int start = 0; start < n; start += per) {
             const int m = std::min(per, n - start);
             // (IQL-diffusion: two halves of pad16(m) rows each, so that either half starts on a 16-row tile)
-            Eval& ev = get_eval(visual ? (m + 63) & ~63 : kind == AgentKind::IQLD ? 2 * pad16(m) : pad16(m * N));
+            Eval& ev = get_eval(visual ? (m + 63) & ~63 : (kind == AgentKind::IQLD || kind == AgentKind::CFGRL) ? 2 * pad16(m) : pad16(m * N));
             const float* o;
             if (visual) {   // `obs` is uint8 [n, H, W, C]: encode with the module's encoder, then proceed on the encodings
                 const size_t ib = (size_t)cfg.img_h * cfg.img_w * cfg.img_c;
@@ -4337,6 +4586,27 @@ struct fql_engine {
             hipLaunchKernelGGL(fql_extract_kernel, dim3((c.m * ad + 255) / 256), dim3(256), 0, s, (const float*)c.ev.tgt, c.out, c.m, ad, ap);
         });
     }
+    // CFGRL sample_actions (agents/cfgrl.py:70-100): x ~ N(0, I); flow_steps times v = v_unc + cfg (v_cond - v_unc), x += v / flow_steps; clip.
+    // 2n rows per call, [cond ; unc], chunks of 2048 observations; goals: [n, G].  Rows are independent (16-row tiles and per-element
+    // kernels, the same at every n), so row j of a call equals the single-observation call.
+    void sample_cfgrl(const float* obs, const float* goals, const float* noise, uint64_t sd, float cfg_scale, int n, float* out,
+                      hipStream_t s, bool own_stream) {
+        const int od = cfg.obs_dim, ad = cfg.act_dim, ap = pad16(ad), Gd = gcfg.goal_dim;
+        if (!goals) invalid("goals must not be NULL (the conditional pass reads them: agents/cfgrl.py:93)");
+        if (!std::isfinite(cfg_scale)) invalid("cfg must be finite");
+        sample_cfg = cfg_scale;
+        SampleSpec sp{};
+        sp.rows_per_obs = 2; sp.noise_rows = 1;
+        sample_chunks(obs, noise, n, out, s, own_stream, sp, [&](const SampleChunk& c) {
+            const int half = c.ev.n_pad / 2;
+            const float* g = stage(goals + (size_t)c.start * Gd, c.ev.st_goal, (size_t)c.m * Gd, s);
+            drain_staging(s);
+            CfgrlAssembleArgs aa{c.o, g, P + emb_off, c.z, c.ev.X, c.ev.Xf, seed, sd, c.m, half, od, Gd, ad, nets[NET_BC].in_p(), ap, c.start};
+            hipLaunchKernelGGL(fql_cfgrl_assemble_kernel, dim3((half + 3) / 4), dim3(FQL_THREADS), 0, s, aa);
+            run_launches(c.ev.prog_flow, s);
+            hipLaunchKernelGGL(fql_extract_kernel, dim3((c.m * ad + 255) / 256), dim3(256), 0, s, (const float*)c.ev.tgt, c.out, c.m, ad, ap);
+        });
+    }
     // IFQL sample_actions (agents/ifql.py:123-155), per observation: num_samples noises through the Euler flow of actor_flow, clip, score by
     // min(q1, q2) of the critic, keep the first argmax.  [n, od] is a batched extension of the reference's single observation: row by row
     // equal to n calls with the same noises.  Chunks of <= 4096 sample rows.
@@ -4392,40 +4662,40 @@ struct fql_engine {
 struct Admission {
     const char* name;
     int only;                          // >= 0: that AgentKind alone (the cells are unused)
-    const char* refuse[kNumKinds];     // FQL, IFQL, ReBRAC, SAC, BC, IQL, IQL-diffusion
+    const char* refuse[kNumKinds];     // FQL, IFQL, ReBRAC, SAC, BC, IQL, IQL-diffusion, CFGRL
 };
 #define OK_ nullptr
 #define NO_ ""
-#define FQL_ALONE {OK_, NO_, NO_, NO_, NO_, NO_, NO_}
+#define FQL_ALONE {OK_, NO_, NO_, NO_, NO_, NO_, NO_, NO_}
 #define ONLY_(k) (int)AgentKind::k, {}
 #define EP_TABLE(X) \
     X(update_begin, -1, FQL_ALONE)                                                                                                 \
     X(update_end, -1, FQL_ALONE)                                                                                                   \
-    X(update, -1, {OK_, OK_, "its batch has no next_actions: fql_rebrac_update", NO_, NO_, NO_, "the step kind is an argument: fql_iqld_update"})                                   \
-    X(total_loss, -1, {OK_, OK_, "its batch has no next_actions: fql_rebrac_total_loss", NO_, NO_, NO_, "fql_iqld_total_loss"})                           \
-    X(sample_actions, -1, {OK_, OK_, OK_, OK_, "fql_bc_sample_actions", OK_, "fql_iqld_sample_actions"})                                                      \
-    X(flow_actions, -1, {OK_, OK_, "the actor is deterministic, there is no flow", NO_, NO_, NO_, NO_})                                 \
+    X(update, -1, {OK_, OK_, "its batch has no next_actions: fql_rebrac_update", NO_, NO_, NO_, "the step kind is an argument: fql_iqld_update", "its batch carries actor_goals: fql_cfgrl_update"})                                   \
+    X(total_loss, -1, {OK_, OK_, "its batch has no next_actions: fql_rebrac_total_loss", NO_, NO_, NO_, "fql_iqld_total_loss", "fql_cfgrl_policy_loss"})                           \
+    X(sample_actions, -1, {OK_, OK_, OK_, OK_, "fql_bc_sample_actions", OK_, "fql_iqld_sample_actions", "it takes goals: fql_cfgrl_sample_actions"})                                                      \
+    X(flow_actions, -1, {OK_, OK_, "the actor is deterministic, there is no flow", NO_, NO_, NO_, NO_, NO_})                                 \
     X(noise_from_jax_keys, -1, FQL_ALONE)                                                                                          \
     X(dataset_add_frames, -1, FQL_ALONE)                                                                                           \
-    X(replay_create, -1, {OK_, NO_, NO_, OK_, NO_, NO_, NO_})                                                                           \
-    X(replay_add, -1, {OK_, NO_, NO_, OK_, NO_, NO_, NO_})                                                                              \
+    X(replay_create, -1, {OK_, NO_, NO_, OK_, NO_, NO_, NO_, NO_})                                                                           \
+    X(replay_add, -1, {OK_, NO_, NO_, OK_, NO_, NO_, NO_, NO_})                                                                              \
     X(replay_add_frames, -1, FQL_ALONE)                                                                                            \
-    X(replay_size, -1, {OK_, NO_, NO_, OK_, NO_, NO_, NO_})                                                                             \
+    X(replay_size, -1, {OK_, NO_, NO_, OK_, NO_, NO_, NO_, NO_})                                                                             \
     X(update_balanced, -1, FQL_ALONE)                                                                                              \
     X(update_from_dataset_begin, -1, FQL_ALONE)                                                                                    \
     X(update_from_dataset_begin_split, -1, FQL_ALONE)                                                                              \
     X(update_begin_split, -1, FQL_ALONE)                                                                                           \
     X(update_end_split, -1, FQL_ALONE)                                                                                             \
     X(grad_buckets, -1, FQL_ALONE)                                                                                                 \
-    X(update_from_dataset, -1, {OK_, OK_, "the step kind is an argument: fql_rebrac_update_from_dataset", NO_, NO_, NO_, "the step kind is an argument: fql_iqld_update_from_dataset"})          \
-    X(info_wait, -1, {OK_, OK_, OK_, "14 infos: fql_info_wait_n", "4 infos: fql_info_wait_n", "16 or 19 infos: fql_info_wait_n", "21 infos: fql_info_wait_n"})  \
-    X(read_info, -1, {OK_, OK_, OK_, "14 infos: fql_read_info_n", "4 infos: fql_read_info_n", "16 or 19 infos: fql_read_info_n", "21 infos: fql_read_info_n"})  \
-    X(profile_update, -1, {OK_, OK_, "FQL batch sources only", NO_, NO_, NO_, NO_})                                                     \
-    X(debug_workspace, -1, {OK_, OK_, "FQL workspaces only", NO_, NO_, NO_, NO_})                                                       \
+    X(update_from_dataset, -1, {OK_, OK_, "the step kind is an argument: fql_rebrac_update_from_dataset", NO_, NO_, NO_, "the step kind is an argument: fql_iqld_update_from_dataset", "the goal draw: fql_cfgrl_update_from_dataset"})          \
+    X(info_wait, -1, {OK_, OK_, OK_, "14 infos: fql_info_wait_n", "4 infos: fql_info_wait_n", "16 or 19 infos: fql_info_wait_n", "21 infos: fql_info_wait_n", "4 infos: fql_info_wait_n"})  \
+    X(read_info, -1, {OK_, OK_, OK_, "14 infos: fql_read_info_n", "4 infos: fql_read_info_n", "16 or 19 infos: fql_read_info_n", "21 infos: fql_read_info_n", "4 infos: fql_read_info_n"})  \
+    X(profile_update, -1, {OK_, OK_, "FQL batch sources only", NO_, NO_, NO_, NO_, NO_})                                                     \
+    X(debug_workspace, -1, {OK_, OK_, "FQL workspaces only", NO_, NO_, NO_, NO_, NO_})                                                       \
     X(dataset_upload_frames, -1, FQL_ALONE)                                                                                        \
     X(update_from_frames, -1, FQL_ALONE)                                                                                           \
-    X(set_step, -1, {OK_, OK_, OK_, OK_, OK_, OK_, "one count per TrainState: fql_iqld_set_steps"})                                \
-    X(set_grad_scale, -1, {OK_, OK_, OK_, OK_, OK_, OK_, "no data-parallel halves on this kind"})                                  \
+    X(set_step, -1, {OK_, OK_, OK_, OK_, OK_, OK_, "one count per TrainState: fql_iqld_set_steps", OK_})                                \
+    X(set_grad_scale, -1, {OK_, OK_, OK_, OK_, OK_, OK_, "no data-parallel halves on this kind", OK_})                                  \
     X(rebrac_update, ONLY_(REBRAC))                                                                                                \
     X(rebrac_update_from_dataset, ONLY_(REBRAC))                                                                                   \
     X(rebrac_total_loss, ONLY_(REBRAC))                                                                                            \
@@ -4454,7 +4724,14 @@ struct Admission {
     X(iqld_read_rows, ONLY_(IQLD))                                                                                                 \
     X(iqld_get_steps, ONLY_(IQLD))                                                                                                 \
     X(iqld_set_steps, ONLY_(IQLD))                                                                                                 \
-    X(iqld_stats, ONLY_(IQLD))
+    X(iqld_stats, ONLY_(IQLD))                                                                                                     \
+    X(cfgrl_update, ONLY_(CFGRL))                                                                                                  \
+    X(cfgrl_update_from_dataset, ONLY_(CFGRL))                                                                                     \
+    X(cfgrl_policy_loss, ONLY_(CFGRL))                                                                                             \
+    X(cfgrl_dataset_goals, ONLY_(CFGRL))                                                                                           \
+    X(cfgrl_sample_actions, ONLY_(CFGRL))                                                                                          \
+    X(cfgrl_read_rows, ONLY_(CFGRL))                                                                                               \
+    X(cfgrl_stats, ONLY_(CFGRL))
 #define X(ep, ...) EP_##ep,
 enum EntryPoint { EP_TABLE(X) EP_COUNT };
 #undef X
@@ -4613,6 +4890,7 @@ static int create_engine(const fql_config* cfg, AgentSpec agent, uint64_t seed, 
     const auto* bcfg = static_cast<const fql_bc_config*>(agent.cfg);
     const auto* qcfg = static_cast<const fql_iql_config*>(agent.cfg);
     const auto* dcfg = static_cast<const fql_iqld_config*>(agent.cfg);
+    const auto* gcfg = static_cast<const fql_cfgrl_config*>(agent.cfg);
     auto refuse = [&](const std::string& why) { g_create_error = std::string(kd.create) + ": " + why; return FQL_E_INVALID; };
     if (kind != AgentKind::FQL) {   // every other kind: state observations and fp32 only
         if (cfg->encoder != 0) return refuse(std::string("visual encoders are not available for ") + kd.name + " (encoder must be 0)");
@@ -4658,6 +4936,19 @@ static int create_engine(const fql_config* cfg, AgentSpec agent, uint64_t seed, 
             if (dcfg->target_extraction != 0 && dcfg->target_extraction != 1) return refuse("target_extraction must be 0 or 1");
             if (dcfg->denoise_steps < 1 || dcfg->denoise_steps > 1024) return refuse("denoise_steps must be in [1, 1024]");
             break;
+        case AgentKind::CFGRL: {
+            if (gcfg->actor_geom_sample != 0)
+                return refuse("actor_geom_sample = True is not available: the geometric offset is a ceil of a ratio of logarithms, which the device's "
+                              "log and numpy's may round to different integers (uniform trajectory goals only)");
+            if (gcfg->goal_dim < 1 || gcfg->goal_dim > 1024) return refuse("goal_dim must be in [1, 1024] (layer 0 is obs + goal_dim + act + 1 wide)");
+            if (gcfg->flow_steps < 1 || gcfg->flow_steps > 1024) return refuse("flow_steps must be in [1, 1024]");
+            if (!std::isfinite(gcfg->cfg)) return refuse("cfg must be finite");
+            if (!(gcfg->p_uncond >= 0.0 && gcfg->p_uncond <= 1.0)) return refuse("p_uncond must be in [0, 1]");
+            const double pc = gcfg->actor_p_curgoal, pt = gcfg->actor_p_trajgoal, pr = gcfg->actor_p_randomgoal;
+            if (!(pc >= 0.0 && pt >= 0.0 && pr >= 0.0) || std::fabs(pc + pt + pr - 1.0) > 1e-8)   // utils/datasets.py:159-161
+                return refuse("actor_p_curgoal + actor_p_trajgoal + actor_p_randomgoal must be 1, each >= 0");
+            break;
+        }
     }
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
@@ -4681,6 +4972,7 @@ static int create_engine(const fql_config* cfg, AgentSpec agent, uint64_t seed, 
             case AgentKind::BC: h->bc_steps = bcfg->denoise_steps; break;
             case AgentKind::IQL: h->qcfg = *qcfg; break;
             case AgentKind::IQLD: h->dcfg = *dcfg; h->bc_steps = dcfg->denoise_steps; break;
+            case AgentKind::CFGRL: h->gcfg = *gcfg; break;
         }
         if (cfg->encoder != 0) {   // visual agent (agents/fql.py:196-202): the MLPs see the 512-wide encoding instead of obs
             if (cfg->encoder != 1 && cfg->encoder != 2) invalid("encoder %d not available (0 = none, 1 = impala_small, 2 = impala)", cfg->encoder);
@@ -4765,6 +5057,11 @@ static int create_engine(const fql_config* cfg, AgentSpec agent, uint64_t seed, 
             HIP_CHECK(hipMalloc((void**)&h->d_state_a, sizeof(DevState)));
             HIP_CHECK(hipMemcpy(h->d_state_a, &st, sizeof st, hipMemcpyHostToDevice));
         }
+        if (kind == AgentKind::CFGRL) {
+            HIP_CHECK(hipMalloc((void**)&h->d_gsrc, sizeof(CfgrlSrc)));
+            HIP_CHECK(hipMemset(h->d_gsrc, 0, sizeof(CfgrlSrc)));
+            HIP_CHECK(hipHostMalloc((void**)&h->h_gsrc_ring, 64 * sizeof(CfgrlSrc), hipHostMallocDefault));
+        }
         h->build_workspace(cfg->batch_size);
     } catch (const Invalid& e) {
         g_create_error = e.msg; fql_destroy(h); return FQL_E_INVALID;
@@ -4788,6 +5085,8 @@ int fql_destroy(fql_handle h) {
     }
     hipFree(h->P); hipFree(h->G); hipFree(h->Mu); hipFree(h->Nu); hipFree(h->d_chunks); hipFree(h->d_partials); hipFree(h->d_leaf_range); hipFree(h->d_state); hipFree(h->d_src); hipFree(h->d_emb); hipFree(h->iql_info); hipFree(h->d_state_a);
     if (h->h_src_ring) hipHostFree(h->h_src_ring);
+    hipFree(h->d_gsrc); hipFree(h->ds_final); hipFree(h->ds_reps);
+    if (h->h_gsrc_ring) hipHostFree(h->h_gsrc_ring);
     if (h->h_info_ring) hipHostFree(h->h_info_ring);
     for (auto& e : h->info_ev) if (e) hipEventDestroy(e);
     hipFree(h->ds_obs); hipFree(h->ds_act); hipFree(h->ds_rew); hipFree(h->ds_mask); hipFree(h->ds_nobs); hipFree(h->ds_row);
@@ -5045,6 +5344,7 @@ int fql_dataset_upload(fql_handle h, int64_t n, int64_t capacity, const float* o
         if (!h->ds_row) HIP_CHECK(hipMalloc((void**)&h->ds_row, (size_t)(2 * od + ad + 2) * sizeof(float)));
         h->ds_size = n; h->ds_cap = capacity; h->ds_ptr = n % capacity;
         h->src_valid = false;
+        h->drop_goal_table();   // (a CFGRL handle's table describes the rows it was built for)
     });
 }
 int fql_dataset_add(fql_handle h, const float* ob, const float* ac, float reward, float mask, const float* nob) {
@@ -5064,6 +5364,7 @@ int fql_dataset_add(fql_handle h, const float* ob, const float* ac, float reward
                            h->ds_act, h->ds_rew, h->ds_mask, h->ds_nobs, h->ds_row, h->ds_ptr, od, ad);
         HIP_CHECK(hipGetLastError());
         HIP_CHECK(hipStreamSynchronize(h->stream));
+        h->drop_goal_table();
         // utils/datasets.py:489-491
         h->ds_ptr = (h->ds_ptr + 1) % h->ds_cap;
         h->ds_size = std::max(h->ds_ptr, h->ds_size);
@@ -5666,6 +5967,113 @@ int fql_iqld_stats(fql_handle h, int update_critic, int update_actor, int64_t* l
     if (macs_per_update) *macs_per_update = h->iqld_macs(update_critic != 0, update_actor != 0);
     // assemble, step-bias table, C0, S (layer 0 + nh GEMMs + the CFG step), extract
     if (launches_per_sample) *launches_per_sample = 4 + (int64_t)h->bc_steps * (h->nets[NET_BC].nl() + 1);
+    return FQL_OK;
+}
+
+// ---- CFGRL (agents/cfgrl.py): goal-conditioned flow policy, classifier-free guidance -------------------------------------------------
+// One update through run_update (the AQL form and the graph are bitwise equal); 4 infos.
+static_assert(FQL_CFGRL_NUM_INFO == 4, "CFGRL info layout");
+void fql_cfgrl_default_config(fql_cfgrl_config* c) {   // agents/cfgrl.py:162-191
+    std::memset(c, 0, sizeof *c);
+    c->goal_dim = 0;
+    c->flow_steps = 16;
+    c->cfg = 3.0f;
+    c->p_uncond = 0.1;
+    c->actor_p_curgoal = 0.0; c->actor_p_trajgoal = 1.0; c->actor_p_randomgoal = 0.0;
+    c->actor_geom_sample = 0;
+}
+int fql_cfgrl_create(const fql_config* cfg, const fql_cfgrl_config* gcfg, uint64_t seed, fql_handle* out) {
+    if (!gcfg) { g_create_error = "gcfg must not be NULL"; if (out) *out = nullptr; return FQL_E_INVALID; }
+    return create_engine(cfg, {AgentKind::CFGRL, gcfg}, seed, out);
+}
+int fql_cfgrl_update(fql_handle h, const float* obs, const float* act, const float* goals, int batch_size, const fql_noise* noise,
+                     const uint8_t* do_cfg, float* info4, void* stream) {
+    if (!h) return FQL_E_INVALID;
+    FQL_ADMIT(h, EP_cfgrl_update);
+    return update_with(h, h->prog_full, info4, FQL_CFGRL_NUM_INFO, stream, [&](hipStream_t s) {
+        h->cfgrl_source_from_batch(obs, act, goals, do_cfg, batch_size, noise, 1, s);
+    });
+}
+int fql_cfgrl_update_from_dataset(fql_handle h, const int64_t* idx, int batch_size, int64_t lo, int64_t hi, const fql_noise* noise,
+                                  const uint8_t* do_cfg, float* info4, void* stream) {
+    if (!h) return FQL_E_INVALID;
+    FQL_ADMIT(h, EP_cfgrl_update_from_dataset);
+    return update_with(h, h->prog_full, info4, FQL_CFGRL_NUM_INFO, stream, [&](hipStream_t s) {
+        h->cfgrl_source_from_dataset(idx, batch_size, lo, hi, noise, do_cfg, s);
+    });
+}
+int fql_cfgrl_policy_loss(fql_handle h, const float* obs, const float* act, const float* goals, int batch_size, const fql_noise* noise,
+                          const uint8_t* do_cfg, float* loss, void* stream) {
+    if (!h) return FQL_E_INVALID;
+    FQL_ADMIT(h, EP_cfgrl_policy_loss);
+    FQL_TRY(h, {
+        hipStream_t s = pick(h, stream);
+        h->cfgrl_source_from_batch(obs, act, goals, do_cfg, batch_size, noise, 0, s);
+        run_program(h, h->prog_loss, s);   // writes info slot 5 and the probe half of the row read-back: what fql_read_info_n reads stays the last update's
+        float v = 0.f;
+        HIP_CHECK(hipMemcpyAsync(&v, &h->d_state->info[CFGRL_I_LOSS], sizeof v, hipMemcpyDeviceToHost, s));
+        HIP_CHECK(hipStreamSynchronize(s));
+        if (loss) *loss = v;
+    });
+}
+int fql_cfgrl_dataset_goals(fql_handle h, const int64_t* final_idx, const float* reps) {
+    if (!h) return FQL_E_INVALID;
+    FQL_ADMIT(h, EP_cfgrl_dataset_goals);
+    FQL_TRY(h, {
+        const int64_t n = h->ds_size;
+        const int Gd = h->gcfg.goal_dim;
+        if (!h->ds_obs || n <= 0) throw Invalid{"fql_cfgrl_dataset_goals: no dataset uploaded (fql_dataset_upload)"};
+        if (n >= ((int64_t)1 << 32)) invalid("fql_cfgrl_dataset_goals: %lld rows: the goal draw indexes fewer than 2^32", (long long)n);
+        if (!final_idx) invalid("final_idx must not be NULL");
+        if (!reps && Gd != h->cfg.obs_dim) invalid("goal_dim %d differs from obs_dim %d: pass the [N, %d] representations", Gd, h->cfg.obs_dim, Gd);
+        if (!fql_engine::is_device_ptr(final_idx))   // the device reads row final_idx[i] of the representations: every entry must name a row at or behind i
+            for (int64_t i = 0; i < n; ++i)
+                if (final_idx[i] < i || final_idx[i] >= n) invalid("final_idx[%lld] = %lld is not in [%lld, %lld)", (long long)i, (long long)final_idx[i], (long long)i, (long long)n);
+        HIP_CHECK(hipDeviceSynchronize());
+        h->drop_goal_table();
+        HIP_CHECK(hipMalloc((void**)&h->ds_final, (size_t)n * sizeof(int64_t)));
+        HIP_CHECK(hipMemcpy(h->ds_final, final_idx, (size_t)n * sizeof(int64_t), hipMemcpyDefault));
+        if (reps) {
+            HIP_CHECK(hipMalloc((void**)&h->ds_reps, (size_t)n * Gd * sizeof(float)));
+            HIP_CHECK(hipMemcpy(h->ds_reps, reps, (size_t)n * Gd * sizeof(float), hipMemcpyDefault));
+        }
+        h->gsrc_valid = false;
+    });
+}
+int fql_cfgrl_sample_actions(fql_handle h, const float* obs, const float* goals, int n, const float* noise, uint64_t seed, float cfg,
+                             float* out, void* stream) {
+    if (!h) return FQL_E_INVALID;
+    FQL_ADMIT(h, EP_cfgrl_sample_actions);
+    FQL_TRY(h, h->sample_cfgrl(obs, goals, noise, seed, cfg, n, out, pick(h, stream), stream == nullptr));
+}
+int fql_cfgrl_read_rows(fql_handle h, int probe, int64_t* idx, int64_t* goal_idx, uint8_t* do_cfg, uint32_t* draws, float* goals, int n) {
+    if (!h) return FQL_E_INVALID;
+    FQL_ADMIT(h, EP_cfgrl_read_rows);
+    FQL_TRY(h, {
+        if (probe != 0 && probe != 1) invalid("probe must be 0 (the last update) or 1 (the last policy_loss)");
+        if (n != h->B) invalid("n = %d does not match the batch size %d", n, h->B);
+        HIP_CHECK(hipStreamSynchronize(h->stream));
+        HIP_CHECK(hipDeviceSynchronize());
+        const size_t B = (size_t)h->B;
+        const int64_t* rows = h->cf_rows + (size_t)probe * 2 * B;
+        if (idx) HIP_CHECK(hipMemcpy(idx, rows, B * sizeof(int64_t), hipMemcpyDeviceToHost));
+        if (goal_idx) HIP_CHECK(hipMemcpy(goal_idx, rows + B, B * sizeof(int64_t), hipMemcpyDeviceToHost));
+        if (do_cfg) HIP_CHECK(hipMemcpy(do_cfg, h->cf_mask + (size_t)probe * B, B, hipMemcpyDeviceToHost));
+        if (draws) HIP_CHECK(hipMemcpy(draws, h->cf_draws + (size_t)probe * CFGRL_NUM_DRAWS * B, CFGRL_NUM_DRAWS * B * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        if (goals) {   // the goal columns of the assembled input rows (the probe shares X with the update: the rows of whichever ran last)
+            const int Gd = h->gcfg.goal_dim, inp = h->nets[NET_BC].in_p();
+            HIP_CHECK(hipMemcpy2D(goals, (size_t)Gd * sizeof(float), h->X_bc + h->cfg.obs_dim, (size_t)inp * sizeof(float), (size_t)Gd * sizeof(float), B,
+                                  hipMemcpyDeviceToHost));
+        }
+    });
+}
+int fql_cfgrl_stats(fql_handle h, int64_t* launches_per_update, int64_t* macs_per_update, int64_t* launches_per_sample) {
+    if (!h) return FQL_E_INVALID;
+    FQL_ADMIT(h, EP_cfgrl_stats);
+    if (launches_per_update) *launches_per_update = (int64_t)h->prog_full.launches.size();
+    if (macs_per_update) *macs_per_update = h->macs_per_update();
+    // assemble, C0, S (layer 0 + nh GEMMs + the CFG step), extract
+    if (launches_per_sample) *launches_per_sample = 3 + (int64_t)h->gcfg.flow_steps * (h->nets[NET_BC].nl() + 1);
     return FQL_OK;
 }
 

@@ -618,6 +618,72 @@ int fql_iqld_set_steps(fql_handle h, const int64_t steps[3]);
 int fql_iqld_stats(fql_handle h, int update_critic, int update_actor, int64_t* launches_per_update, int64_t* macs_per_update,
                    int64_t* launches_per_sample);
 
+/* ---- CFGRL (agents/cfgrl.py): classifier-free-guidance RL, a goal-conditioned flow policy.  State observations, fp32, GELU.
+ * One ModuleDict TrainState (`network`), leaves in jax dict order:
+ *   "modules_actor_flow/mlp/Dense_i/{bias,kernel}" (GCActorVectorField: MLP((*actor_hidden, act)) on [obs | goals | x_t | t], first layer
+ *   obs + goal_dim + act + 1 -> hidden, every kernel Glorot uniform) and "modules_actor_flow/mlp/LayerNorm_i/{bias,scale}" with
+ *   actor_layer_norm; "modules_unc_embed/Embed_0/embedding" ([1, goal_dim], N(0, 1 / goal_dim): flax's variance_scaling(1, fan_in,
+ *   normal, out_axis=0), whose fan_in on [1, G] is G).
+ * fql_config mapping: actor_hidden = actor_hidden_dims, actor_layer_norm, lr; value_hidden, layer_norm, discount, tau, alpha, q_agg,
+ * flow_steps and normalize_q_loss are ignored (flow_steps travels in fql_cfgrl_config).
+ * Update (agents/cfgrl.py:22-68): x_0 ~ N(0, I), t ~ U[0, 1), x_t = (1 - t) x_0 + t a, vel = a - x_0; do_cfg ~ Bernoulli(p_uncond) per
+ * row; goals = where(do_cfg, unc_embed, actor_goals); loss = mean((actor_flow(obs, x_t, t, goals) - vel)^2) over B act elements.  The
+ * gradient reaches unc_embed through the dropped rows only.  Adam over the whole tree, no target network.
+ * Infos: 4 floats (FQL_CFGRL_NUM_INFO, fql_handle_info_name): 0 actor/actor_loss 1 grad/max 2 grad/min 3 grad/norm; fql_read_info and
+ * fql_info_wait return FQL_E_STATE.
+ * fql_noise: only x0 [B, act] (raw N(0, 1)) and t [B] in [0, 1) are read; any other non-NULL pointer is FQL_E_INVALID.  do_cfg: [B]
+ * bytes (non-zero = the row's goal is dropped), host or device, or NULL = u32 < floor(p_uncond 2^32) of a Philox tensor of its own.
+ * Goals on the device (utils/datasets.py:224-255, GCDataset.sample_goals with the actor's probabilities): fql_cfgrl_dataset_goals stores
+ * the per-row `final` table beside the uploaded dataset; fql_cfgrl_update_from_dataset then draws, per row, idx, a random goal, d, u and
+ * u' (32 bits each, u32 / 2^32 as a double) and takes round(min(idx + 1, final) d + final (1 - d)) in fp64 (each operation rounded on
+ * its own, half to even), where(u < p_traj / (1 - p_cur), ., random), where(u' < p_cur, idx, .); p_cur == 1: goal = idx.
+ * A CFGRL handle is an ordinary fql_handle for destroy, set_batch_size, leaf / param / opt-state / step access, dataset upload / reserve /
+ * size, info enqueue / fql_info_wait_n / fql_read_info_n, fql_synchronize, fql_stats and fql_stream; fql_dataset_upload and
+ * fql_dataset_add drop the goal table.  Refused: at create, FQL_E_INVALID naming the field: actor_geom_sample != 0, encoder != 0,
+ * precision != 0, goal_dim outside [1, 1024], probabilities that do not sum to 1.  On a CFGRL handle fql_update*, fql_update_begin* /
+ * _end*, fql_total_loss, fql_sample_actions, fql_flow_actions, fql_grad_buckets, frame uploads / updates, fql_replay_*,
+ * fql_update_balanced, fql_noise_from_jax_keys, fql_read_info, fql_info_wait and every other kind's calls return FQL_E_STATE, and
+ * fql_group_create with such a member returns FQL_E_STATE.  The fql_cfgrl_* calls on another handle return FQL_E_STATE. */
+#define FQL_CFGRL_NUM_INFO 4
+typedef struct fql_cfgrl_config {
+    int32_t goal_dim;                 /* G: last axis of example_batch['value_goals']; need not equal obs_dim   */
+    int32_t flow_steps;               /* Euler steps of sample_actions (16)                                     */
+    float cfg;                        /* the guidance scale the host mirror passes by default (3.0)             */
+    int32_t actor_geom_sample;        /* 0; 1 is refused                                                        */
+    double p_uncond;                  /* probability that a row's goal is replaced by unc_embed (0.1)           */
+    double actor_p_curgoal;           /* 0.0                                                                    */
+    double actor_p_trajgoal;          /* 1.0                                                                    */
+    double actor_p_randomgoal;        /* 0.0                                                                    */
+    int32_t reserved[6];
+} fql_cfgrl_config;
+void fql_cfgrl_default_config(fql_cfgrl_config* c);
+int fql_cfgrl_create(const fql_config* cfg, const fql_cfgrl_config* gcfg, uint64_t seed, fql_handle* out);
+/* CFGRLAgent.update(batch): observations [B, obs], actions [B, act], actor_goals [B, goal_dim].  `info4`: 4 floats, or NULL. */
+int fql_cfgrl_update(fql_handle h, const float* observations, const float* actions, const float* actor_goals, int batch_size,
+                     const fql_noise* noise, const uint8_t* do_cfg, float* info4, void* stream);
+/* The per-row `final` table (int64 [N]: the last row of row i's trajectory, terminal_locs[searchsorted(terminal_locs, i)]) and the goal
+ * representations (float [N, goal_dim], or NULL: the observations, which needs goal_dim == obs_dim) of the uploaded dataset. */
+int fql_cfgrl_dataset_goals(fql_handle h, const int64_t* final_idx, const float* reps);
+/* GCDataset.sample(B) + update(batch) on the device; idx / lo / hi as fql_update_from_dataset's.  FQL_E_INVALID without the goal table. */
+int fql_cfgrl_update_from_dataset(fql_handle h, const int64_t* idx, int batch_size, int64_t lo, int64_t hi, const fql_noise* noise,
+                                  const uint8_t* do_cfg, float* info4, void* stream);
+/* actor_loss with the stored parameters: pure forward, no state change (parameters, moments, counters, and what fql_read_info_n and
+ * fql_cfgrl_read_rows(probe = 0) read are as the last update left them).  Synchronous. */
+int fql_cfgrl_policy_loss(fql_handle h, const float* observations, const float* actions, const float* actor_goals, int batch_size,
+                          const fql_noise* noise, const uint8_t* do_cfg, float* loss, void* stream);
+/* CFGRLAgent.sample_actions(observations, goals, seed): x ~ N(0, I); flow_steps times v = v_unc + cfg (v_cond - v_unc) at t = i /
+ * flow_steps, x += v / flow_steps; clip to [-1, 1].  goals [n, goal_dim]: NULL is FQL_E_INVALID.  noise [n, act] or NULL (engine RNG
+ * keyed by `seed` and the row number); rows of one call equal single calls with the same noise rows. */
+int fql_cfgrl_sample_actions(fql_handle h, const float* observations, const float* goals, int n, const float* noise, uint64_t seed,
+                             float cfg, float* out, void* stream);
+/* The rows of the last update (probe = 0) or the last fql_cfgrl_policy_loss (probe = 1); every pointer host, NULL = not wanted:
+ * idx [n], goal_idx [n] (-1: the goals came with the batch), do_cfg [n], draws [6][n] (the raw 32-bit draws: idx, random goal, d, u, u',
+ * mask; 0 where none was made), goals [n, goal_dim] (the goal columns of the input rows as assembled, whichever call ran last).
+ * n = the batch size.  Synchronous. */
+int fql_cfgrl_read_rows(fql_handle h, int probe, int64_t* idx, int64_t* goal_idx, uint8_t* do_cfg, uint32_t* draws, float* goals, int n);
+/* launches and algorithmic MACs of one update; launches of one sampling call of <= 2048 observations */
+int fql_cfgrl_stats(fql_handle h, int64_t* launches_per_update, int64_t* macs_per_update, int64_t* launches_per_sample);
+
 #ifdef __cplusplus
 }
 #endif
