@@ -68,7 +68,10 @@ def assert_total_loss_matches(agent, ref, params, batch, noise):
 
 def assert_step_matches(agent, ref, cfg, batch, noise, step=None):
     """One update on both sides: 13 infos, every leaf's gradient (Adam mu / 0.1 after the first step from zero moments), nu, post-step
-    parameters.  `step(agent, batch, noise)` runs the GPU side (default: agent.update) and returns the infos or None (then read_info)."""
+    parameters.  `step(agent, batch, noise)` runs the GPU side (default: agent.update) and returns the infos or None (then read_info).
+    The parameter check here is a first-step check only: from zero moments Adam's step is lr g / (|g| + 1e-8), +-lr whatever the gradient is,
+    so it says little about the Adam arithmetic; tests/test_gpu_optimizer.py holds Adam, Polyak and the gradient statistics to the fp64
+    restatement from non-zero moments and at large counts."""
     _, _, g_ref = ref.grads(batch, noise)
     info_u = step(agent, batch, noise) if step is not None else agent.update(batch, noise=noise)[1]
     if info_u is None:
