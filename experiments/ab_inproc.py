@@ -50,4 +50,5 @@ for r in range(rounds):
         res[i].append((time.perf_counter() - t0) / n * 1e6)
 for i, e in enumerate(envs):
     print(f'{"AB"[i]} {e}: median {statistics.median(res[i]):.1f} us/update  (min {min(res[i]):.1f}, max {max(res[i]):.1f})  = {1e6 / statistics.median(res[i]):.0f} updates/s')
+    print(f'  {"AB"[i]} windows (us/update): ' + ' '.join(f'{v:.1f}' for v in res[i]))
 print(f'B / A time: {statistics.median(res[1]) / statistics.median(res[0]):.4f}')

@@ -243,11 +243,38 @@ struct Launch {
     std::vector<GemmTask> h_gemm;
     std::vector<WgradTask> h_wgrad;
     std::vector<LnBwdTask> h_ln;
+    std::vector<MiscTask> h_misc;
+    // OP_GEMM64: the same tasks as the kernel argument (fql_kernels.h, find_front), set where the launch is built when they fit the
+    // capacities and FQL_KERNARG_TASKS does not forbid it; issue() then launches the *_ka_kernel twin and the tables stay unused
+    std::shared_ptr<const SideArgs> ka_side;
     std::vector<int> waits;      // launches of the OTHER lane that must have completed
     bool record_after = false;   // some launch of the other lane waits on this one
     hipEvent_t ev = nullptr;
 };
 
+// FQL_KERNARG_TASKS=0: every launch reads its tasks from its table in HBM (A/B, and the bitwise test of the argument form).  Read when an
+// engine is created.
+inline bool ka_tasks_env() {
+    const char* e = getenv("FQL_KERNARG_TASKS");
+    return !e || atoi(e) != 0;
+}
+// a side-lane launch's four host tables as SideArgs; null when a family exceeds its capacity
+inline std::shared_ptr<const SideArgs> ka_side_args(const Launch& L) {
+    const size_t ng = L.h_gemm.size(), nw = L.h_wgrad.size(), nl = L.h_ln.size(), nm = L.h_misc.size();
+    if (ng > FQL_KA_GEMM || nw > FQL_KA_WGRAD || nl > FQL_KA_LN || nm > FQL_KA_MISC) return nullptr;
+    auto a = std::make_shared<SideArgs>();
+    std::memset(a.get(), 0, sizeof(SideArgs));
+    SideFront& f = a->f;
+    f.tile_w = L.tile_w; f.tile_l = L.tile_l; f.tile_m = L.tile_m; f.tl = -1;
+    for (int& v : f.g0) v = FQL_KA_FRONT_PAD;
+    for (int& v : f.w0) v = FQL_KA_FRONT_PAD;
+    for (int& v : f.l0) v = FQL_KA_FRONT_PAD;
+    for (size_t i = 0; i < ng; ++i) { a->g[i] = L.h_gemm[i]; if (i) f.g0[i - 1] = L.h_gemm[i].tile0; }
+    for (size_t i = 0; i < nw; ++i) { a->w[i] = L.h_wgrad[i]; if (i) f.w0[i - 1] = L.h_wgrad[i].tile0; }
+    for (size_t i = 0; i < nl; ++i) { a->l[i] = L.h_ln[i]; if (i) f.l0[i - 1] = L.h_ln[i].tile0; }
+    for (size_t i = 0; i < nm; ++i) a->m[i] = L.h_misc[i];
+    return a;
+}
 struct Program {
     std::vector<Op> ops;
     std::vector<Launch> launches;
@@ -551,6 +578,7 @@ struct fql_engine {
     float *wf_w0 = nullptr, *wf_w4 = nullptr;
     WfragTask* d_wfrag = nullptr;
     int wfrag_n = 0, wfrag_grid = 0;
+    const bool ka_tasks = ka_tasks_env();   // FQL_KERNARG_TASKS, as it stood when this engine was created
     std::vector<void*> chain_allocs;
     bool split_build = false;   // building the data-parallel program: lane 1 must not depend on lane 0's backward
     bool wide_tiles = false;    // three-lane programs: 32 x 64 side tiles everywhere (the other lanes fill the CUs a launch leaves idle; +1 %)
@@ -1972,7 +2000,8 @@ struct fql_engine {
                     L.table_w = up(tw.data(), tw.size() * sizeof(WgradTask));
                     L.table_l = up(tl.data(), tl.size() * sizeof(LnBwdTask));
                     L.table_m = up(tmisc.data(), tmisc.size() * sizeof(MiscTask));
-                    L.h_gemm = tg; L.h_wgrad = tw; L.h_ln = tl;
+                    L.h_gemm = tg; L.h_wgrad = tw; L.h_ln = tl; L.h_misc = tmisc;
+                    if (ka_tasks) L.ka_side = ka_side_args(L);
                     pr.launches.push_back(L);
                     continue;
                 }
@@ -2245,7 +2274,13 @@ struct fql_engine {
                 else FQL_LAUNCH((fql_gemm16_kernel<false>), dim3(L.grid), dim3(FQL_THREADS), L.lds, s, (const GemmTask*)L.table, L.ntasks, tl);
                 break;
             case OP_GEMM64:   // the level's side-lane launch (schedule())
-                if (L.tmt2)
+                if (L.ka_side) {
+                    SideArgs a = *L.ka_side; a.f.tl = tl;
+                    if (L.tmt2) FQL_LAUNCH(fql_side_big_ka_kernel, dim3(L.grid), dim3(FQL_THREADS), L.lds, s, a);
+                    else if (cfg.precision == 2) FQL_LAUNCH(fql_side_split_ka_kernel, dim3(L.grid), dim3(FQL_THREADS), L.lds, s, a);
+                    else FQL_LAUNCH(fql_side_ka_kernel, dim3(L.grid), dim3(FQL_THREADS), L.lds, s, a);
+                }
+                else if (L.tmt2)
                     FQL_LAUNCH(fql_side_big_kernel, dim3(L.grid), dim3(FQL_THREADS), L.lds, s, (const GemmTask*)L.table, L.ntasks,
                                        (const WgradTask*)L.table_w, L.n_w, (const LnBwdTask*)L.table_l, L.n_l, L.tile_w, L.tile_l,
                                        (const MiscTask*)L.table_m, L.tile_m, tl);
@@ -6281,7 +6316,10 @@ const std::vector<PlanKernel>& plan_kernels() {
         {plan_fn(fql_gemm16_kernel<false>), PLAN_K_GEMM16, 0, 0}, {plan_fn(fql_gemm16_kernel<true>), PLAN_K_GEMM16_KBIG, 0, 0},
         {plan_fn(fql_gemm16_euler_kernel<false>), PLAN_K_GEMM16_EULER, 0, 0}, {plan_fn(fql_gemm16_euler_kernel<true>), PLAN_K_GEMM16_EULER_KBIG, 0, 0},
         {plan_fn(fql_side_kernel), PLAN_K_SIDE, 0, 0}, {plan_fn(fql_side_split_kernel), PLAN_K_SIDE_SPLIT, 0, 0},
-        {plan_fn(fql_side_big_kernel), PLAN_K_SIDE_BIG, 0, 0}, FQL_PLAN_CHAIN(256), FQL_PLAN_CHAIN(512)};
+        {plan_fn(fql_side_big_kernel), PLAN_K_SIDE_BIG, 0, 0}, FQL_PLAN_CHAIN(256), FQL_PLAN_CHAIN(512),
+        // the same launches with their tasks in the kernel arguments: the entry names the tile bodies, fql_debug_task_forms the form
+        {plan_fn(fql_side_ka_kernel), PLAN_K_SIDE, 0, 0}, {plan_fn(fql_side_split_ka_kernel), PLAN_K_SIDE_SPLIT, 0, 0},
+        {plan_fn(fql_side_big_ka_kernel), PLAN_K_SIDE_BIG, 0, 0}};
 #undef FQL_PLAN_CHAIN
     return t;
 }
@@ -6459,8 +6497,8 @@ struct fql_group_s {
     }
     // the members' task tables one after the other, each member's tile0 shifted by `shift[member]` (MiscTask: no tile0, no shift)
     template <typename T>
-    void* fuse(const std::vector<const void*>& tables, const std::vector<int>& counts, const std::vector<int>& shift, bool rebase = true) {
-        std::vector<T> all;
+    void* fuse(const std::vector<const void*>& tables, const std::vector<int>& counts, const std::vector<int>& shift, std::vector<T>& all, bool rebase = true) {
+        all.clear();
         for (size_t i = 0; i < tables.size(); ++i) {
             std::vector<T> h((size_t)counts[i]);
             if (counts[i]) HIP_CHECK(hipMemcpy(h.data(), tables[i], (size_t)counts[i] * sizeof(T), hipMemcpyDeviceToHost));
@@ -6481,6 +6519,8 @@ struct fql_group_s {
             G.table = true;
             Launch F = L0;
             F.ev = nullptr; F.waits.clear();
+            F.ka_side = nullptr;   // (member 0's: the fused launch takes the form ITS task counts allow)
+            std::vector<WfragTask> h_wf;
             std::vector<const void*> tg, tw, tl, tm;
             std::vector<int> ng, nw, nl, nm, sg, sw, sl, sm;
             int cg = 0, cw = 0, cl = 0, cm = 0, ntot = 0;
@@ -6498,17 +6538,18 @@ struct fql_group_s {
                 }
             }
             if (L0.type == OP_WFRAG) {
-                F.table = fuse<WfragTask>(tg, ng, sg); F.ntasks = ntot; F.grid = cg;
+                F.table = fuse<WfragTask>(tg, ng, sg, h_wf); F.ntasks = ntot; F.grid = cg;
             } else if (L0.type == OP_GEMM64) {
-                F.table = fuse<GemmTask>(tg, ng, sg);
-                F.table_w = fuse<WgradTask>(tw, nw, sw);
-                F.table_l = fuse<LnBwdTask>(tl, nl, sl);
-                F.table_m = fuse<MiscTask>(tm, nm, sm, false);
+                F.table = fuse<GemmTask>(tg, ng, sg, F.h_gemm);
+                F.table_w = fuse<WgradTask>(tw, nw, sw, F.h_wgrad);
+                F.table_l = fuse<LnBwdTask>(tl, nl, sl, F.h_ln);
+                F.table_m = fuse<MiscTask>(tm, nm, sm, F.h_misc, false);
                 F.ntasks = F.n_w = F.n_l = 0;
                 for (int k = 0; k < K; ++k) { F.ntasks += ng[k]; F.n_w += nw[k]; F.n_l += nl[k]; }
                 F.tile_w = cg; F.tile_l = cg + cw; F.tile_m = cg + cw + cl; F.grid = F.tile_m + cm;
+                if (m[0]->ka_tasks) F.ka_side = ka_side_args(F);
             } else {
-                F.table = fuse<GemmTask>(tg, ng, sg);
+                F.table = fuse<GemmTask>(tg, ng, sg, F.h_gemm);
                 F.ntasks = ntot; F.grid = cg;
             }
             G.L = F;
@@ -6632,6 +6673,25 @@ int fql_group_create(const fql_handle* members, int k, fql_group* out) {
     }
     for (fql_handle h : g->m) { h->group = g; h->grp_done = g->ev_done; h->grp_pending = false; h->grp_touched = true; }
     *out = g;
+    return FQL_OK;
+}
+
+// Diagnostic only (not in include/fql_amd.h, beside fql_debug_plan): where each launch of an update program takes its tasks from, as int32 words
+//   [words (this one included), capacities of the argument form of a side-lane launch: GEMM-tile, weight-gradient, LayerNorm-backward, loss / metric
+//    tasks, launches], then per launch one word:
+//   0 = the launch has no task table, 1 = its tasks are a table in HBM, 2 = they are the kernel argument (FQL_KERNARG_TASKS, fql_kernels.h find_front)
+// of the group `g`'s fused program when g is given, else of the handle's prog_full (same refusals as fql_debug_plan).  Prefix reads as there.
+int fql_debug_task_forms(fql_handle h, fql_group g, void* out, size_t bytes) {
+    if ((!h && !g) || (bytes && !out) || bytes % sizeof(int32_t)) return FQL_E_INVALID;
+    if (!g && (h->visual || !h->prog_full.exec || h->prog_full.launches.empty())) return FQL_E_STATE;
+    auto form = [](const Launch& L) { return !is_table_launch(L.type) ? 0 : L.ka_side ? 2 : 1; };
+    std::vector<int32_t> w{0, FQL_KA_GEMM, FQL_KA_WGRAD, FQL_KA_LN, FQL_KA_MISC, 0};
+    if (g) for (const GLaunch& G : g->launches) w.push_back(G.table ? form(G.L) : 0);
+    else for (const Launch& L : h->prog_full.launches) w.push_back(form(L));
+    w[5] = (int32_t)w.size() - 6;
+    w[0] = (int32_t)w.size();
+    if (bytes > w.size() * sizeof(int32_t)) return FQL_E_INVALID;
+    if (bytes) std::memcpy(out, w.data(), bytes);
     return FQL_OK;
 }
 

@@ -338,6 +338,88 @@ __device__ __forceinline__ int find_task(const T* tasks, int ntasks, int b) {
 }
 
 // ------------------------------------------------------------------------------------------------
+// Tasks by value in the kernel arguments (the *_ka_kernel entry points).  A table in HBM costs a workgroup a chain of dependent scalar
+// misses before its first data load: the table pointer from the kernarg, one probe per find_task trip (every task another cache line),
+// then the record's fields as the code reaches them.  Here the launch's argument IS the table: the first-tile index of every task sits
+// at the front and is searched in registers, the record follows in the same kernarg block at a wave-uniform offset and is copied into
+// registers once - two dependent scalar round trips, both off the kernarg pointer.  The capacities are what fits the 4 KB a launch
+// accepts (the hidden block of 72 bytes included); a launch with more tasks keeps its table (schedule()).
+// ------------------------------------------------------------------------------------------------
+#define FQL_KA_LIMIT (4096 - 72)
+#define FQL_KA_FRONT_PAD 0x7fffffff   // first-tile word of an unused slot: no workgroup index reaches it
+// N dwords from the kernarg segment in ONE batch of scalar loads and one wait.  Left to the compiler, the loads of a record are issued
+// where each field is first used (a field only one tile body reads is loaded inside that body): a round trip per use site.  The words
+// come back as a struct so that the caller's memcpy into the record type dissolves into registers.
+typedef int ka_i32x16 __attribute__((ext_vector_type(16)));
+typedef int ka_i32x8 __attribute__((ext_vector_type(8)));
+typedef int ka_i32x4 __attribute__((ext_vector_type(4)));
+#if defined(__HIP_DEVICE_COMPILE__)
+#define FQL_CONST_AS __attribute__((address_space(4)))   // the constant address space: scalar loads
+#else
+#define FQL_CONST_AS
+#endif
+template <typename T>
+__device__ __forceinline__ T ka_load(const FQL_CONST_AS void* p) {
+    constexpr int N = sizeof(T) / 4;
+    static_assert(sizeof(T) % 4 == 0 && (N == 16 || N == 24 || N == 28 || N == 32 || N == 56), "ka_load: no load sequence for this record size");
+    int w[N];
+#if defined(__HIP_DEVICE_COMPILE__)
+    ka_i32x16 a, b, c;
+    ka_i32x8 d;
+    ka_i32x4 q;
+    if constexpr (N == 16) asm volatile("s_load_dwordx16 %0, %1, 0x0\n\ts_waitcnt lgkmcnt(0)" : "=&s"(a) : "s"(p));
+    if constexpr (N == 24) asm volatile("s_load_dwordx16 %0, %2, 0x0\n\ts_load_dwordx8 %1, %2, 0x40\n\ts_waitcnt lgkmcnt(0)" : "=&s"(a), "=&s"(d) : "s"(p));
+    if constexpr (N == 28)
+        asm volatile("s_load_dwordx16 %0, %3, 0x0\n\ts_load_dwordx8 %1, %3, 0x40\n\ts_load_dwordx4 %2, %3, 0x60\n\ts_waitcnt lgkmcnt(0)"
+                     : "=&s"(a), "=&s"(d), "=&s"(q) : "s"(p));
+    if constexpr (N == 32) asm volatile("s_load_dwordx16 %0, %2, 0x0\n\ts_load_dwordx16 %1, %2, 0x40\n\ts_waitcnt lgkmcnt(0)" : "=&s"(a), "=&s"(b) : "s"(p));
+    if constexpr (N == 56)
+        asm volatile("s_load_dwordx16 %0, %4, 0x0\n\ts_load_dwordx16 %1, %4, 0x40\n\ts_load_dwordx16 %2, %4, 0x80\n\ts_load_dwordx8 %3, %4, 0xc0\n\t"
+                     "s_waitcnt lgkmcnt(0)" : "=&s"(a), "=&s"(b), "=&s"(c), "=&s"(d) : "s"(p));
+#pragma unroll
+    for (int i = 0; i < 16; ++i) w[i] = a[i];
+    if constexpr (N == 24 || N == 28) {
+#pragma unroll
+        for (int i = 0; i < 8; ++i) w[16 + i] = d[i];
+    }
+    if constexpr (N == 28) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) w[24 + i] = q[i];
+    }
+    if constexpr (N == 32 || N == 56) {
+#pragma unroll
+        for (int i = 0; i < 16; ++i) w[16 + i] = b[i];
+    }
+    if constexpr (N == 56) {
+#pragma unroll
+        for (int i = 0; i < 16; ++i) w[32 + i] = c[i];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) w[48 + i] = d[i];
+    }
+#else
+    (void)p;
+    for (int i = 0; i < N; ++i) w[i] = 0;
+#endif
+    T t;
+    __builtin_memcpy(&t, w, sizeof(T));
+    return t;
+}
+__device__ __forceinline__ const FQL_CONST_AS char* ka_base() {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return (const FQL_CONST_AS char*)__builtin_amdgcn_kernarg_segment_ptr();
+#else
+    return nullptr;
+#endif
+}
+// the task of workgroup b from the first-tile words of tasks 1 .. N (they ascend; unused slots hold FQL_KA_FRONT_PAD): the last one b has reached
+template <int N>
+__device__ __forceinline__ int find_front(const int (&t0)[N], int b) {
+    int t = 0;
+#pragma unroll
+    for (int i = 0; i < N; ++i) t = (b >= t0[i]) ? i + 1 : t;
+    return t;
+}
+// ------------------------------------------------------------------------------------------------
 // K1-K6: Dense (+bias) (+GELU) with optional LayerNorm prologue on the A tile; also dgrad (C = A W^T)
 //   utils/networks.py:53-58 (Dense -> GELU -> LN), agents/fql.py:166-170 (Euler epilogue)
 //
@@ -1879,12 +1961,7 @@ struct PrepArgs {
 // agents/fql.py:52-56 (x_t, vel), :144-150 (noise), utils/datasets.py:64-100 (index draw + gather),
 // utils/networks.py:191,229-231 (concatenate) -- one pass builds every network input of the step.
 // Multi-instance entry points read their member's argument struct through the constant address space: scalar loads into SGPRs, as from
-// the kernel-argument segment of the single-instance kernel (same registers, no VGPR copies of the fields)
-#if defined(__HIP_DEVICE_COMPILE__)
-#define FQL_CONST_AS __attribute__((address_space(4)))
-#else
-#define FQL_CONST_AS
-#endif
+// the kernel-argument segment of the single-instance kernel (same registers, no VGPR copies of the fields): FQL_CONST_AS, above
 __device__ __forceinline__ void fql_prep_body(const PrepArgs& P) {
     tl_enter(P.tl);
     const SrcDesc& S = *P.src;
@@ -2410,4 +2487,74 @@ __global__ __launch_bounds__(FQL_THREADS, 2) void fql_side_big_kernel(
     tl_enter(tl);
     side_body<true>(gt, ngt, wt, nwt, lt, nlt, tile_w, tile_l, mt, tile_m);
     tl_exit(tl);
+}
+
+// The same three launches with the level's tasks in the kernel arguments.  The front holds the family bounds and, per family, the first
+// workgroup of its tasks 1 .. (counted inside the family, as WgradTask::tile0 and LnBwdTask::tile0 are): 32 dwords, one batch of loads,
+// after which every family finds its task in registers and reaches its record in the second round trip.
+#define FQL_KA_GEMM 8
+#define FQL_KA_WGRAD 16
+#define FQL_KA_LN 6
+#define FQL_KA_MISC 4
+struct SideFront {
+    int tile_w, tile_l, tile_m, tl;   // family bounds in workgroups (as the table launch takes them), timeline id
+    int g0[FQL_KA_GEMM - 1];          // first workgroup of GEMM-tile tasks 1 .. (FQL_KA_FRONT_PAD: unused slot)
+    int w0[FQL_KA_WGRAD - 1];         // ... of weight-gradient tasks 1 ..
+    int l0[FQL_KA_LN - 1];            // ... of LayerNorm-backward tasks 1 ..
+    int pad;
+};
+struct SideArgs {
+    SideFront f;
+    GemmTask g[FQL_KA_GEMM];
+    WgradTask w[FQL_KA_WGRAD];
+    LnBwdTask l[FQL_KA_LN];
+    MiscTask m[FQL_KA_MISC];
+};
+static_assert(sizeof(SideFront) == 128, "the front is two 16-dword loads");
+static_assert(sizeof(SideArgs) <= FQL_KA_LIMIT, "SideArgs and the hidden block must fit the 4 KB of a launch's arguments");
+template <bool BIG, bool SPLIT = false>
+__device__ __forceinline__ void side_ka_body(const SideFront& F) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    const int b = blockIdx.x;
+    if (b < F.tile_w) {
+        const GemmTask T = ka_load<GemmTask>(ka_base() + offsetof(SideArgs, g) + (size_t)find_front(F.g0, b) * sizeof(GemmTask));
+        gemm_tile_dispatch<BIG, SPLIT>(T, lds);
+    } else if (b < F.tile_l) {
+        const int bid = b - F.tile_w;
+        const WgradTask T = ka_load<WgradTask>(ka_base() + offsetof(SideArgs, w) + (size_t)find_front(F.w0, bid) * sizeof(WgradTask));
+        if (SPLIT) wgrad_split_body(T, bid, lds);
+        else wgrad_body(T, bid, lds);
+    } else if (b < F.tile_m) {
+        const int bid = b - F.tile_l;
+        const LnBwdTask T = ka_load<LnBwdTask>(ka_base() + offsetof(SideArgs, l) + (size_t)find_front(F.l0, bid) * sizeof(LnBwdTask));
+        float (*red)[16][16] = reinterpret_cast<float (*)[16][16]>(lds);
+        if (T.dq) lnbwd_body<true>(T, bid, red);
+        else lnbwd_body<false>(T, bid, red);
+    } else {
+        const MiscTask T = ka_load<MiscTask>(ka_base() + offsetof(SideArgs, m) + (size_t)(b - F.tile_m) * sizeof(MiscTask));
+        switch (T.kind) {
+            case MISC_POSTOS: fql_post_onestep_body(T.po, lds); break;
+            case MISC_LOSS_CRITIC: fql_loss_critic_body(T.lc, lds); break;
+            case MISC_LOSS_Q: fql_loss_q_body(T.lq, lds); break;
+            default: fql_loss_bc_body(T.lb, lds); break;
+        }
+    }
+}
+__global__ __launch_bounds__(FQL_THREADS, FQL_SIDE_WAVES) void fql_side_ka_kernel(const SideArgs) {
+    const SideFront F = ka_load<SideFront>(ka_base());
+    tl_enter(F.tl);
+    side_ka_body<false>(F);
+    tl_exit(F.tl);
+}
+__global__ __launch_bounds__(FQL_THREADS, FQL_SIDE_WAVES) void fql_side_split_ka_kernel(const SideArgs) {
+    const SideFront F = ka_load<SideFront>(ka_base());
+    tl_enter(F.tl);
+    side_ka_body<false, true>(F);
+    tl_exit(F.tl);
+}
+__global__ __launch_bounds__(FQL_THREADS, 2) void fql_side_big_ka_kernel(const SideArgs) {
+    const SideFront F = ka_load<SideFront>(ka_base());
+    tl_enter(F.tl);
+    side_ka_body<true>(F);
+    tl_exit(F.tl);
 }
