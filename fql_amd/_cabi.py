@@ -188,6 +188,9 @@ SYMBOLS = {
     'fql_cfgrl_sample_actions': (_I, [_VP, _VP, _VP, _I, _VP, _U64, _F, _VP, _VP]),
     'fql_cfgrl_read_rows': (_I, [_VP, _I, _VP, _VP, _VP, _VP, _VP, _I]),
     'fql_cfgrl_stats': (_I, [_VP, C.POINTER(_I64), C.POINTER(_I64), C.POINTER(_I64)]),
+    'fql_iqld_sample_actions_cfgs': (_I, [_VP, _VP, _I, _VP, _U64, _VP, _VP, _VP]),
+    'fql_cfgrl_sample_actions_cfgs': (_I, [_VP, _VP, _VP, _I, _VP, _U64, _VP, _VP, _VP]),
+    'fql_sample_cfgs_stats': (_I, [_VP, C.POINTER(_I64)]),
     'fql_read_info_n': (_I, [_VP, _VP, _I]),
     'fql_info_wait_n': (_I, [_VP, _U64, _VP, _I]),
 }

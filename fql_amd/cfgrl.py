@@ -26,6 +26,7 @@ import numpy as np
 from . import _cabi
 from .agent import KindAgent, _Arg, _PendingN
 from .config import ConfigDict
+from .iql_diffusion import as_array, check_cfgs, sweep_inputs
 
 CFGRL_INFO_KEYS = ('actor/actor_loss', 'grad/max', 'grad/min', 'grad/norm')
 CFGRL_NOISE_KEYS = ('x0', 't')
@@ -230,6 +231,48 @@ class CFGRLAgent(KindAgent):
         self._check(self._lib.fql_cfgrl_sample_actions(self._h, o.ptr, g.ptr, n, z.ptr, self._sample_seed(seed, noises), scale, optr,
                                                        self._stream([o, g, z])))
         return out
+
+    # -- guidance sweeps: one weight per row --------------------------------------------------------
+    def sample_actions_rows(self, observations, goals, cfgs, seed=None, noises=None):
+        """sample_actions with one guidance weight per row, in ONE call: observations [N, od], goals [N, G] or one [G], cfgs [N] ->
+        [N, act] (no squeeze).  Row j is, bit for bit, sample_actions(observations[j], goals[j], cfg=cfgs[j], noises=noises[j]); with
+        engine noise row j draws what row j of sample_actions(.., seed=seed) draws.  3 + S nl + 1 launches whatever N <= 2048 is."""
+        if goals is None:
+            raise ValueError('CFGRL: sample_actions_rows needs goals (the conditional pass reads them, agents/cfgrl.py:93)')
+        od, ad, G = self.config['ob_dims'][0], self.config['action_dim'], self.config['goal_dim']
+        observations, goals = as_array(observations), as_array(goals)
+        if len(observations.shape) != 2 or int(observations.shape[1]) != od or int(observations.shape[0]) < 1:
+            raise ValueError(f'observations must be [N, {od}] with N >= 1, got {tuple(observations.shape)}')
+        n = int(observations.shape[0])
+        if tuple(int(d) for d in goals.shape) not in ((G,), (1, G), (n, G)):
+            raise ValueError(f'goals must be [{G}] or [{n}, {G}], got {tuple(goals.shape)}')
+        if int(np.prod(goals.shape)) == G and n > 1:   # one goal for every row
+            goals = goals.reshape(1, G).expand(n, G) if hasattr(goals, 'data_ptr') else np.broadcast_to(np.reshape(goals, (1, G)), (n, G))
+        cfgs = check_cfgs(cfgs, n, 'row')
+        if noises is not None and tuple(as_array(noises).shape) != (n, ad):
+            raise ValueError(f'noises must be [{n}, {ad}], got {tuple(as_array(noises).shape)}')
+        o, g, w, z = _Arg(observations, (n, od)), _Arg(goals, (n, G)), _Arg(cfgs, (n,)), _Arg(noises, (n, ad))
+        out, optr = self._actions_out(observations, (n, ad))
+        self._check(self._lib.fql_cfgrl_sample_actions_cfgs(self._h, o.ptr, g.ptr, n, z.ptr, self._sample_seed(seed, noises), w.ptr, optr,
+                                                            self._stream([o, g, z, w])))
+        return out
+
+    def sample_actions_sweep(self, observations, goals, cfgs, seed=None, noises=None):
+        """Every weight of an evaluation sweep in one call: cfgs [K] -> [K, n, act], slice k = sample_actions(.., cfg=cfgs[k]).
+        observations: [n, od] (every weight sees the same rows) or [K, n, od] (one vector env per weight); goals: [G], [n, G] or
+        [K, n, G] by the same rule; noises: None (engine RNG: row k n + j of the flat call), [n, act] (shared by every weight: common
+        random numbers) or [K, n, act]."""
+        if goals is None:
+            raise ValueError('CFGRL: sample_actions_sweep needs goals (the conditional pass reads them, agents/cfgrl.py:93)')
+        od, ad, G = self.config['ob_dims'][0], self.config['action_dim'], self.config['goal_dim']
+        K, n, (ob, g, z), w = sweep_inputs(cfgs, [('observations', observations, od), ('goals', goals, G, True), ('noises', noises, ad)])
+        return self.sample_actions_rows(ob, g, w, seed=seed, noises=z).reshape(K, n, ad)
+
+    def sample_cfgs_stats(self):
+        """Launches of one sample_actions_rows / sample_actions_sweep call of <= 2048 rows."""
+        ls = C.c_int64()
+        self._check(self._lib.fql_sample_cfgs_stats(self._h, C.byref(ls)))
+        return int(ls.value)
 
     def cfgrl_stats(self):
         """(launches of one update, MACs of one update, launches of one sampling call of <= 2048 observations)."""

@@ -3,6 +3,7 @@
 // by the learned unc_embed row, the gradient of that row, the 4-info finalize, and the sampler's input rows and layer 0.  The GEMM bodies,
 // weight gradients, LayerNorm backward, the flow-matching loss (fql_loss_bc_body: its 2 / (B act) scaling is this loss's), Adam and the
 // grad statistics are FQL's; the sampler's CFG combine, Euler add and final clip are IQL-diffusion's fql_iqld_cfg_step_kernel, unchanged.
+// The sweep program (one guidance weight per row) adds fql_cfgrl_cfg_layer0_kernel and ends on IQL-diffusion's rows step kernel.
 //
 // actor_flow is GCActorVectorField: MLP((*hidden, act), GELU, LayerNorm optional) on [obs | goal | x_t | t], t one column.
 #pragma once
@@ -262,4 +263,31 @@ __global__ __launch_bounds__(FQL_THREADS) void fql_cfgrl_layer0_kernel(CfgrlLaye
     for (int a = 0; a < P.ad; ++a) s = fmaf(x[a], P.W0a[(size_t)a * P.H + h], s);
     s = fmaf(P.t, P.W0a[(size_t)P.ad * P.H + h], s);
     P.G0[e] = gelu_f(s);
+}
+
+struct CfgrlCfgLayer0Args {
+    const float *C0, *V, *Xin, *cfg, *W0a;   // C0 [2 n_pad, H]; V [2 n_pad, ap]: the previous step's head output; Xin [n_pad, ap]; cfg [n_pad];
+                                             // W0a = row od + G of W0 [in_p, H]: ad action rows, then the t row
+    float *Xout, *G0;                        // Xout [n_pad, ap]: the other ping-pong buffer; G0 [2 n_pad, H]
+    int n_pad, H, ad, ap;
+    float t, dt;                             // i / flow_steps; 1 / flow_steps
+};
+// Euler step i >= 1 of a sweep program (sample_actions_cfgs) in one launch: fql_iqld_cfg_layer0_kernel around fql_cfgrl_layer0_kernel's
+// layer 0 (C0 spans both halves; the act terms in rising order, then the t term)
+__global__ __launch_bounds__(FQL_THREADS) void fql_cfgrl_cfg_layer0_kernel(CfgrlCfgLayer0Args P) {
+    const int e = blockIdx.x * FQL_THREADS + threadIdx.x;
+    if (e >= 2 * P.n_pad * P.H) return;
+    const int r = e / P.H, h = e - r * P.H;
+    const int half = r >= P.n_pad ? 1 : 0, src = r - half * P.n_pad;
+    float s = P.C0[e];
+    const float* x = P.Xin + (size_t)src * P.ap;
+    const float* vp = P.V + (size_t)src * P.ap;
+    const float* vu = P.V + (size_t)(P.n_pad + src) * P.ap;
+    const float c = P.cfg[src];
+    for (int a = 0; a < P.ad; ++a) s = fmaf(iqld_cfg_euler(x[a], vp[a], vu[a], c, P.dt), P.W0a[(size_t)a * P.H + h], s);
+    s = fmaf(P.t, P.W0a[(size_t)P.ad * P.H + h], s);
+    P.G0[e] = gelu_f(s);
+    if (half == 0)
+        for (int a = h; a < P.ap; a += P.H)
+            P.Xout[(size_t)src * P.ap + a] = a < P.ad ? iqld_cfg_euler(x[a], vp[a], vu[a], c, P.dt) : 0.f;
 }

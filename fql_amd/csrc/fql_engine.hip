@@ -148,7 +148,9 @@ enum OpType { OP_GEMM, OP_GEMM64, OP_WGRAD, OP_LNBWD, OP_PREP, OP_POSTOS, OP_EUL
               OP_IQLD_PREP, OP_IQLD_LOSS_C, OP_IQLD_WEIGHT, OP_IQLD_LOSS_A, OP_IQLD_EGRAD, OP_IQLD_FIN, OP_IQLD_STEPBIAS, OP_IQLD_LAYER0,
               OP_IQLD_CFG,
               // CFGRL (agents/cfgrl.py) only: after IQL-diffusion's
-              OP_CFGRL_PREP, OP_CFGRL_EGRAD, OP_CFGRL_FIN, OP_CFGRL_LAYER0, OP_NUM_TYPES };
+              OP_CFGRL_PREP, OP_CFGRL_EGRAD, OP_CFGRL_FIN, OP_CFGRL_LAYER0,
+              // the sweep programs of both CFG samplers (one guidance weight per row): after CFGRL's
+              OP_CFG_ROWS_LAYER0, OP_CFG_ROWS_STEP, OP_NUM_TYPES };
 
 // A launch bound where its op is emitted (every agent op, OP_IFQL_PREP and later): the kernel, a 1-D grid and the packed arguments,
 // always FQL_THREADS threads and no LDS.  issue() launches it as it stands, so such an op has no payload member and no case of its own.
@@ -634,6 +636,7 @@ struct fql_engine {
         Program prog_os, prog_flow;
         float *st_obs = nullptr, *st_noise = nullptr, *st_out = nullptr;
         float* st_goal = nullptr;   // CFGRL: staging of host goals [half, G]
+        float *Xf2 = nullptr, *cfgs = nullptr;   // sweep programs: the second ping-pong buffer of x [half, ap]; the per-row weights [half]
         // visual agents: the rows are images; they pass through the module's encoder first (agents/fql.py:162-163, networks.py:221)
         unsigned char* st_img = nullptr;
         EncBuf eb_os, eb_bc;
@@ -644,6 +647,8 @@ struct fql_engine {
         Program prog_q;
     };
     std::map<int, std::unique_ptr<Eval>> evals;
+    // the sweep programs of the CFG samplers (get_sweep): workspaces of their own, so that no sample_actions workspace or program changes
+    std::map<int, std::unique_ptr<Eval>> sweeps;
 
     // agent groups (fql_group_*): the group this engine is a member of, the event behind that group's last update and whether an entry
     // point of this engine has run since (then the next group update orders itself behind this engine's stream)
@@ -4510,10 +4515,106 @@ struct fql_engine {
         evals[n_pad] = std::move(ev);
         return ref;
     }
+    // The sweep program of a CFG sampler (IQL-diffusion, CFGRL): sample_actions' program with one guidance weight
+    // per row and S - 1 launches fewer.  The head is the same (IQL-diffusion's step-bias table, the C0 GEMM) and step 0 runs the existing
+    // layer-0 kernel on X[0], where the assemble kernel wrote x.  Step i >= 1 is ONE launch in front of its GEMMs: the CFG combine and
+    // Euler add of step i - 1 with the row's weight, then layer 0 on the new x, which it also writes to X[i & 1] while every thread reads
+    // X[(i - 1) & 1].  Behind the last head GEMM the rows step kernel reads X[(S - 1) & 1] and writes the clipped actions.  The weights
+    // [half] live in the workspace and are bound here; the call copies them in (sample_cfgs), so issue() patches nothing.
+    Eval& get_sweep(int n_pad) {
+        auto it = sweeps.find(n_pad);
+        if (it != sweeps.end()) return *it->second;
+        const bool iqld = kind == AgentKind::IQLD;
+        auto ev = std::make_unique<Eval>();
+        ev->n_pad = n_pad;
+        auto& W = ev->allocs;
+        const int od = cfg.obs_dim, ad = cfg.act_dim, ap = pad16(ad), half = n_pad / 2;
+        const int S = iqld ? bc_steps : gcfg.flow_steps, Gd = iqld ? 0 : gcfg.goal_dim;
+        const Net& n = nets[NET_BC];
+        const Layer& l0 = n.layers[0];
+        const int H = l0.out_p;
+        const int rows0 = iqld ? half : n_pad;               // IQL-diffusion's halves share [obs | 0] and C0; CFGRL's differ in the goal columns
+        const float dt = 1.0f / (float)S;
+        ev->X = dalloc(W, (size_t)rows0 * n.in_p());
+        ev->Xf = dalloc(W, (size_t)half * ap);               // X[0]
+        ev->Xf2 = dalloc(W, (size_t)half * ap);              // X[1]
+        if (iqld) ev->Xq = dalloc(W, (size_t)S * 2 * H);     // step-bias table c[i][half]
+        float* C0e = dalloc(W, (size_t)rows0 * H);
+        ev->tgt = dalloc(W, (size_t)half * ap);
+        ev->cfgs = dalloc(W, (size_t)half);
+        ev->st_obs = dalloc(W, (size_t)half * od);
+        if (!iqld) ev->st_goal = dalloc(W, (size_t)half * Gd);
+        ev->st_noise = dalloc(W, (size_t)half * ad);
+        ev->st_out = dalloc(W, (size_t)half * ad);
+        ev->p_eu = make_pass(W, NET_BC, n_pad, ev->X, false, false);
+        float* const Xpp[2] = {ev->Xf, ev->Xf2};
+        const float* W0a = P + l0.w + (size_t)(od + Gd) * H;   // the action rows of W0 (CFGRL: the t row behind them)
+        const int grid0 = (2 * half * H + FQL_THREADS - 1) / FQL_THREADS;
+        emit_lane = 0;
+        Program& pr = ev->prog_flow;
+        if (iqld) {
+            Op op{};
+            op.type = OP_IQLD_STEPBIAS;
+            const IqldStepBiasArgs dsb{d_emb, P + emb_off, P + l0.w + (size_t)(od + ad) * H, ev->Xq, S, H};
+            op.k = bind(fql_iqld_stepbias_kernel, (dsb.S * 2 * dsb.H + FQL_THREADS - 1) / FQL_THREADS, dsb);
+            op.reads = {d_emb, P + emb_off, P + l0.w};
+            op.writes = {ev->Xq};
+            push(pr, op);
+        }
+        {
+            Op op{};
+            op.type = OP_GEMM;
+            GemmTask& t = op.gemm;
+            t.A = ev->X; t.lda = l0.in_p; t.B = P + l0.w; t.ldb = H; t.bias = P + l0.b; t.C = C0e; t.ldc = H;
+            t.M = rows0; t.N = H; t.K = l0.in_p; t.flags = GF_BIAS;
+            op.reads = {ev->X, t.B};
+            op.writes = {C0e};
+            push(pr, op);
+        }
+        for (int i = 0; i < S; ++i) {
+            const float ti = (float)((double)i / (double)S);   // cfgrl.py:90: a Python float, cast to fp32
+            const float* cb = iqld ? ev->Xq + (size_t)i * 2 * H : nullptr;
+            Op op{};
+            if (i == 0) {
+                op.type = iqld ? OP_IQLD_LAYER0 : OP_CFGRL_LAYER0;
+                if (iqld) op.k = bind(fql_iqld_layer0_kernel, grid0, IqldLayer0Args{C0e, Xpp[0], W0a, cb, ev->p_eu.g[0], half, H, ad, ap});
+                else op.k = bind(fql_cfgrl_layer0_kernel, grid0, CfgrlLayer0Args{C0e, Xpp[0], W0a, ev->p_eu.g[0], half, H, ad, ap, ti});
+                op.reads = {C0e, Xpp[0], P + l0.w};
+                op.writes = {ev->p_eu.g[0]};
+            } else {
+                float *xin = Xpp[(i - 1) & 1], *xout = Xpp[i & 1];
+                op.type = OP_CFG_ROWS_LAYER0;
+                if (iqld)
+                    op.k = bind(fql_iqld_cfg_layer0_kernel, grid0,
+                                IqldCfgLayer0Args{C0e, ev->p_eu.out, xin, ev->cfgs, W0a, cb, xout, ev->p_eu.g[0], half, H, ad, ap, dt});
+                else
+                    op.k = bind(fql_cfgrl_cfg_layer0_kernel, grid0,
+                                CfgrlCfgLayer0Args{C0e, ev->p_eu.out, xin, ev->cfgs, W0a, xout, ev->p_eu.g[0], half, H, ad, ap, ti, dt});
+                op.reads = {C0e, ev->p_eu.out, xin, ev->cfgs, P + l0.w};
+                op.writes = {ev->p_eu.g[0], xout};
+            }
+            if (iqld) op.reads.push_back(ev->Xq);
+            push(pr, op);
+            emit_forward(pr, ev->p_eu, false, 0, nullptr, nullptr, 0.f, 0.f, 1);
+        }
+        {
+            Op st{};
+            st.type = OP_CFG_ROWS_STEP;
+            const IqldCfgRowsStepArgs dstep{ev->p_eu.out, Xpp[(S - 1) & 1], ev->cfgs, ev->tgt, half, ad, ap, dt};
+            st.k = bind(fql_iqld_cfg_rows_step_kernel, (dstep.n_pad * dstep.ad + FQL_THREADS - 1) / FQL_THREADS, dstep);
+            st.reads = {ev->p_eu.out, dstep.X, ev->cfgs};
+            st.writes = {ev->tgt};
+            push(pr, st);
+        }
+        schedule(pr, W);
+        Eval& ref = *ev;
+        sweeps[n_pad] = std::move(ev);
+        return ref;
+    }
     // The row-chunk loop of every sampling path.  A chunk is <= 4096 rows (256 image rows) of rows_per_obs rows per observation: its
     // observations and noise are staged, `body` enqueues what differs between the paths - the assemble launch, the program(s) and the
     // finishing launch that writes the chunk's [m, act] actions to c.out - and the actions are copied out or, on the engine's own stream, waited for.
-    struct SampleSpec { float temperature = 0.f; int rows_per_obs = 1; bool need_noise = false; int enc = ENC_OS; int noise_rows = -1; };   // enc: the encoder of a visual agent's rows; noise_rows: noise rows per observation (-1: rows_per_obs)
+    struct SampleSpec { float temperature = 0.f; int rows_per_obs = 1; bool need_noise = false; int enc = ENC_OS; int noise_rows = -1; bool sweep = false; };   // enc: the encoder of a visual agent's rows; noise_rows: noise rows per observation (-1: rows_per_obs); sweep: the chunk's workspace is get_sweep's
     struct SampleChunk { Eval& ev; const float *o, *z; float* out; int start, m; };   // observations [start, start + m) of the call
     template <typename Body>
     void sample_chunks(const float* obs, const float* noise, int n, float* out, hipStream_t s, bool own_stream, const SampleSpec& sp, Body&& body) {
@@ -4526,7 +4627,8 @@ struct fql_engine {
         for (int start = 0; start < n; start += per) {
             const int m = std::min(per, n - start);
             // (IQL-diffusion: two halves of pad16(m) rows each, so that either half starts on a 16-row tile)
-            Eval& ev = get_eval(visual ? (m + 63) & ~63 : (kind == AgentKind::IQLD || kind == AgentKind::CFGRL) ? 2 * pad16(m) : pad16(m * N));
+            Eval& ev = sp.sweep ? get_sweep(2 * pad16(m))
+                                : get_eval(visual ? (m + 63) & ~63 : (kind == AgentKind::IQLD || kind == AgentKind::CFGRL) ? 2 * pad16(m) : pad16(m * N));
             const float* o;
             if (visual) {   // `obs` is uint8 [n, H, W, C]: encode with the module's encoder, then proceed on the encodings
                 const size_t ib = (size_t)cfg.img_h * cfg.img_w * cfg.img_c;
@@ -4642,6 +4744,43 @@ struct fql_engine {
             hipLaunchKernelGGL(fql_extract_kernel, dim3((c.m * ad + 255) / 256), dim3(256), 0, s, (const float*)c.ev.tgt, c.out, c.m, ad, ap);
         });
     }
+    // sample_actions of both CFG kinds with one guidance weight per row (fql_iqld_sample_actions_cfgs, fql_cfgrl_sample_actions_cfgs): the
+    // sweep program of get_sweep on the same assemble and extract launches.  Row j equals sample_actions on row j with cfg = cfgs[j], bit
+    // for bit.  cfgs: [n], host (checked here: finite) or device (not read on the host); each chunk's weights are copied into the
+    // workspace buffer the program was bound to, with 0 behind them.  goals: CFGRL's [n, G], null on IQL-diffusion.
+    void sample_cfgs(const float* obs, const float* goals, const float* noise, uint64_t sd, const float* cfgs, int n, float* out,
+                     hipStream_t s, bool own_stream) {
+        const bool iqld = kind == AgentKind::IQLD;
+        const int od = cfg.obs_dim, ad = cfg.act_dim, ap = pad16(ad), Gd = iqld ? 0 : gcfg.goal_dim;
+        if (n <= 0) invalid("n must be positive (got %d)", n);
+        if (!cfgs) invalid("cfgs must not be NULL (one guidance weight per row)");
+        if (!iqld && !goals) invalid("goals must not be NULL (the conditional pass reads them: agents/cfgrl.py:93)");
+        const bool host_cfgs = !is_device_ptr(cfgs);
+        if (host_cfgs)
+            for (int i = 0; i < n; ++i)
+                if (!std::isfinite(cfgs[i])) invalid("cfgs[%d] = %g: every guidance weight must be finite", i, (double)cfgs[i]);
+        SampleSpec sp{};
+        sp.rows_per_obs = 2; sp.noise_rows = 1; sp.sweep = true;
+        sample_chunks(obs, noise, n, out, s, own_stream, sp, [&](const SampleChunk& c) {
+            const int half = c.ev.n_pad / 2;
+            HIP_CHECK(hipMemcpyAsync(c.ev.cfgs, cfgs + c.start, (size_t)c.m * sizeof(float), hipMemcpyDefault, s));
+            if (host_cfgs) staged_host = true;
+            if (half > c.m) HIP_CHECK(hipMemsetAsync(c.ev.cfgs + c.m, 0, (size_t)(half - c.m) * sizeof(float), s));
+            const float* g = iqld ? nullptr : stage(goals + (size_t)c.start * Gd, c.ev.st_goal, (size_t)c.m * Gd, s);
+            drain_staging(s);
+            if (iqld) {
+                BcAssembleArgs aa{c.o, c.z, c.ev.X, c.ev.Xf, seed, sd, c.m, half, od, ad, nets[NET_BC].in_p(), ap, c.start};
+                hipLaunchKernelGGL(fql_bc_assemble_kernel, dim3((half + 3) / 4), dim3(FQL_THREADS), 0, s, aa);
+            } else {
+                CfgrlAssembleArgs aa{c.o, g, P + emb_off, c.z, c.ev.X, c.ev.Xf, seed, sd, c.m, half, od, Gd, ad, nets[NET_BC].in_p(), ap, c.start};
+                hipLaunchKernelGGL(fql_cfgrl_assemble_kernel, dim3((half + 3) / 4), dim3(FQL_THREADS), 0, s, aa);
+            }
+            run_launches(c.ev.prog_flow, s);
+            hipLaunchKernelGGL(fql_extract_kernel, dim3((c.m * ad + 255) / 256), dim3(256), 0, s, (const float*)c.ev.tgt, c.out, c.m, ad, ap);
+        });
+    }
+    // launches of one such call of <= 2048 rows, counted from the built program: assemble, the program's launches, extract
+    int64_t sample_cfgs_launches() { return 2 + (int64_t)get_sweep(2 * 16).prog_flow.launches.size(); }
     // IFQL sample_actions (agents/ifql.py:123-155), per observation: num_samples noises through the Euler flow of actor_flow, clip, score by
     // min(q1, q2) of the critic, keep the first argmax.  [n, od] is a batched extension of the reference's single observation: row by row
     // equal to n calls with the same noises.  Chunks of <= 4096 sample rows.
@@ -4760,13 +4899,16 @@ struct Admission {
     X(iqld_get_steps, ONLY_(IQLD))                                                                                                 \
     X(iqld_set_steps, ONLY_(IQLD))                                                                                                 \
     X(iqld_stats, ONLY_(IQLD))                                                                                                     \
+    X(iqld_sample_actions_cfgs, ONLY_(IQLD))                                                                                       \
     X(cfgrl_update, ONLY_(CFGRL))                                                                                                  \
     X(cfgrl_update_from_dataset, ONLY_(CFGRL))                                                                                     \
     X(cfgrl_policy_loss, ONLY_(CFGRL))                                                                                             \
     X(cfgrl_dataset_goals, ONLY_(CFGRL))                                                                                           \
     X(cfgrl_sample_actions, ONLY_(CFGRL))                                                                                          \
     X(cfgrl_read_rows, ONLY_(CFGRL))                                                                                               \
-    X(cfgrl_stats, ONLY_(CFGRL))
+    X(cfgrl_stats, ONLY_(CFGRL))                                                                                                   \
+    X(cfgrl_sample_actions_cfgs, ONLY_(CFGRL))                                                                                     \
+    X(sample_cfgs_stats, -1, {NO_, NO_, NO_, NO_, NO_, NO_, OK_, OK_})
 #define X(ep, ...) EP_##ep,
 enum EntryPoint { EP_TABLE(X) EP_COUNT };
 #undef X
@@ -5115,9 +5257,9 @@ int fql_destroy(fql_handle h) {
     hipDeviceSynchronize();
     h->free_workspace();
     h->aql.shutdown();
-    for (auto& kv : h->evals) {
-        for (void* p : kv.second->allocs) hipFree(p);
-    }
+    for (auto* m : {&h->evals, &h->sweeps})
+        for (auto& kv : *m)
+            for (void* p : kv.second->allocs) hipFree(p);
     hipFree(h->P); hipFree(h->G); hipFree(h->Mu); hipFree(h->Nu); hipFree(h->d_chunks); hipFree(h->d_partials); hipFree(h->d_leaf_range); hipFree(h->d_state); hipFree(h->d_src); hipFree(h->d_emb); hipFree(h->iql_info); hipFree(h->d_state_a);
     if (h->h_src_ring) hipHostFree(h->h_src_ring);
     hipFree(h->d_gsrc); hipFree(h->ds_final); hipFree(h->ds_reps);
@@ -6110,6 +6252,28 @@ int fql_cfgrl_stats(fql_handle h, int64_t* launches_per_update, int64_t* macs_pe
     // assemble, C0, S (layer 0 + nh GEMMs + the CFG step), extract
     if (launches_per_sample) *launches_per_sample = 3 + (int64_t)h->gcfg.flow_steps * (h->nets[NET_BC].nl() + 1);
     return FQL_OK;
+}
+
+// ---- guidance sweeps: the two CFG samplers with one weight per row ------------------------------------------
+int fql_iqld_sample_actions_cfgs(fql_handle h, const float* obs, int n, const float* noise, uint64_t seed, const float* cfgs, float* out,
+                                 void* stream) {
+    if (!h) return FQL_E_INVALID;
+    FQL_ADMIT(h, EP_iqld_sample_actions_cfgs);
+    FQL_TRY(h, h->sample_cfgs(obs, nullptr, noise, seed, cfgs, n, out, pick(h, stream), stream == nullptr));
+}
+int fql_cfgrl_sample_actions_cfgs(fql_handle h, const float* obs, const float* goals, int n, const float* noise, uint64_t seed,
+                                  const float* cfgs, float* out, void* stream) {
+    if (!h) return FQL_E_INVALID;
+    FQL_ADMIT(h, EP_cfgrl_sample_actions_cfgs);
+    FQL_TRY(h, h->sample_cfgs(obs, goals, noise, seed, cfgs, n, out, pick(h, stream), stream == nullptr));
+}
+int fql_sample_cfgs_stats(fql_handle h, int64_t* launches_per_call) {
+    if (!h) return FQL_E_INVALID;
+    FQL_ADMIT(h, EP_sample_cfgs_stats);
+    FQL_TRY(h, {
+        const int64_t n = h->sample_cfgs_launches();
+        if (launches_per_call) *launches_per_call = n;
+    });
 }
 
 }  // extern "C"

@@ -3,7 +3,8 @@
 // the loss weights and their statistics, the weighted two-half flow-matching loss, the embedding gradient, the per-TrainState finalize
 // and the sampler's step-bias table, layer 0 and classifier-free-guidance step.  The value loss is IFQL's (fql_ifql_loss_value_kernel);
 // the GEMM bodies, weight gradients, LayerNorm backward, Adam + Polyak and the sampler's row assembly (fql_bc_assemble_kernel) are
-// FQL's and BC's.  Every reduction runs in one workgroup in a fixed order (no float atomics).
+// FQL's and BC's.  Every reduction runs in one workgroup in a fixed order (no float atomics).  At the end of the file: the two kernels
+// of the sweep programs (one guidance weight per row), the guidance step folded into the next step's layer 0 and the last step alone.
 //
 // The actor (DiffusionPolicy) is MLP(hidden, GELU, LayerNorm) + Dense(act) on [obs | x_t | emb(t) | Embed[is_positive]]: BC's policy
 // with 32 more input columns.  The positive and the unconditional pass of a batch share obs, x_t, t and vel, so they run as ONE pass
@@ -381,4 +382,60 @@ __global__ __launch_bounds__(FQL_THREADS) void fql_iqld_cfg_step_kernel(IqldCfgS
     const float x = P.A[o] + v * P.dt;
     P.A[o] = x;
     if (P.tgt) P.tgt[o] = clip1(x);
+}
+
+// ---- guidance sweeps (sample_actions_cfgs): one weight per row ---------------------------------------------------------------------
+// The CFG combine and Euler add as fql_iqld_cfg_step_kernel's code object rounds them (v_sub, v_fmac, v_fmac): t = vp - vu; v = c t + vu;
+// x + v dt.  Spelled with fmaf so that the rounding is the source's, not an optimiser's choice per kernel body: a subtraction feeding
+// an fma cannot contract, and nothing else here is a bare multiply-add.
+__device__ __forceinline__ float iqld_cfg_euler(float x, float vp, float vu, float c, float dt) {
+    const float t = vp - vu;
+    const float v = fmaf(c, t, vu);
+    return fmaf(v, dt, x);
+}
+
+struct IqldCfgRowsStepArgs {
+    const float* V;            // [2 n_pad, ap]: the head's output, positive half then unconditional half
+    const float* X;            // [n_pad, ap]: x before the step (the ping-pong buffer that holds it)
+    const float* cfg;          // [n_pad]: the weight of each source row (0 for rows >= n)
+    float* tgt;                // [n_pad, ap]: clip(x + v dt)
+    int n_pad, ad, ap;
+    float dt;
+};
+// the last Euler step of a sweep program: fql_iqld_cfg_step_kernel with the row's own weight; x itself is not written back
+__global__ __launch_bounds__(FQL_THREADS) void fql_iqld_cfg_rows_step_kernel(IqldCfgRowsStepArgs P) {
+    const int e = blockIdx.x * FQL_THREADS + threadIdx.x;
+    if (e >= P.n_pad * P.ad) return;
+    const int r = e / P.ad, a = e - r * P.ad;
+    const size_t o = (size_t)r * P.ap + a;
+    P.tgt[o] = clip1(iqld_cfg_euler(P.X[o], P.V[o], P.V[(size_t)P.n_pad * P.ap + o], P.cfg[r], P.dt));
+}
+
+struct IqldCfgLayer0Args {
+    const float *C0, *V, *Xin, *cfg, *W0a, *cb;   // C0 [n_pad, H]; V [2 n_pad, ap]: the previous step's head output; Xin [n_pad, ap]; cfg [n_pad];
+                                                  // W0a = row od of W0 (ad rows); cb = rows (i, 0) and (i, 1) of the step-bias table [2, H]
+    float *Xout, *G0;                             // Xout [n_pad, ap]: x after the previous step's Euler add (the other ping-pong buffer); G0 [2 n_pad, H]
+    int n_pad, H, ad, ap;
+    float dt;
+};
+// Euler step i >= 1 of a sweep program in one launch: the CFG combine and Euler add of step i - 1 (fql_iqld_cfg_step_kernel's
+// arithmetic, the row's own weight), then layer 0 of step i on the new x (fql_iqld_layer0_kernel's: C0 + cb, the act terms in rising
+// order, GELU).  One thread per (row, column) as there; every thread forms the ad values x_new[src][.] it multiplies (a wave reads one
+// row: the loads are broadcasts).  Xin is read and Xout written, so no thread reads what another writes; the positive half's threads
+// h, h + H, .. < ap store x_new (0 in the padding columns) for the next launch.
+__global__ __launch_bounds__(FQL_THREADS) void fql_iqld_cfg_layer0_kernel(IqldCfgLayer0Args P) {
+    const int e = blockIdx.x * FQL_THREADS + threadIdx.x;
+    if (e >= 2 * P.n_pad * P.H) return;
+    const int r = e / P.H, h = e - r * P.H;
+    const int half = r >= P.n_pad ? 1 : 0, src = r - half * P.n_pad;
+    float s = P.C0[(size_t)src * P.H + h] + P.cb[half * P.H + h];
+    const float* x = P.Xin + (size_t)src * P.ap;
+    const float* vp = P.V + (size_t)src * P.ap;
+    const float* vu = P.V + (size_t)(P.n_pad + src) * P.ap;
+    const float c = P.cfg[src];
+    for (int a = 0; a < P.ad; ++a) s = fmaf(iqld_cfg_euler(x[a], vp[a], vu[a], c, P.dt), P.W0a[(size_t)a * P.H + h], s);
+    P.G0[e] = gelu_f(s);
+    if (half == 0)
+        for (int a = h; a < P.ap; a += P.H)
+            P.Xout[(size_t)src * P.ap + a] = a < P.ad ? iqld_cfg_euler(x[a], vp[a], vu[a], c, P.dt) : 0.f;
 }

@@ -90,6 +90,54 @@ def get_config():
     )
 
 
+def as_array(x):
+    """`x` itself when it has a shape (numpy array, torch tensor), else a float32 numpy array of it."""
+    return x if hasattr(x, 'shape') else np.asarray(x, dtype=np.float32)
+
+
+def check_cfgs(cfgs, n, per):
+    """[n] finite guidance weights (numpy or torch), or ValueError: the checks of both CFG samplers' per-row calls."""
+    cfgs = as_array(cfgs)
+    if len(cfgs.shape) != 1 or int(cfgs.shape[0]) != n:
+        raise ValueError(f'cfgs must hold one guidance weight per {per}: [{n}], got {tuple(cfgs.shape)}')
+    finite = cfgs.isfinite().all() if hasattr(cfgs, 'data_ptr') else np.isfinite(np.asarray(cfgs, dtype=np.float64)).all()
+    if not bool(finite):
+        raise ValueError('cfgs: every guidance weight must be finite')
+    return cfgs
+
+
+def sweep_inputs(cfgs, items):
+    """The flatten and repeat of sample_actions_sweep.  cfgs: [G], G >= 1.  items: (name, array, width[, one_ok]) tuples, the first
+    the observations: each array is [n, width] (shared by every weight), [G, n, width], None, or with one_ok one [width] row for
+    every row.  Returns G, n, the arrays as [G n, width] with row g n + j = (weight g, row j), and the weights repeated to [G n]."""
+    cfgs = as_array(cfgs)
+    if len(cfgs.shape) != 1 or int(cfgs.shape[0]) < 1:
+        raise ValueError(f'cfgs must be [G] with G >= 1 (an empty sweep has no rows), got {tuple(cfgs.shape)}')
+    G = int(cfgs.shape[0])
+    check_cfgs(cfgs, G, 'sweep entry')
+    ob, od = as_array(items[0][1]), items[0][2]
+    sh = tuple(int(d) for d in ob.shape)
+    if len(sh) not in (2, 3) or sh[-1] != od or sh[-2] < 1 or (len(sh) == 3 and sh[0] != G):
+        raise ValueError(f'observations must be [n, {od}] or [{G}, n, {od}] with n >= 1, got {sh}')
+    n = sh[-2]
+    flat = []
+    for name, x, w, *one_ok in items:
+        if x is None:
+            flat.append(None)
+            continue
+        x = as_array(x)
+        sh = tuple(int(d) for d in x.shape)
+        if one_ok and one_ok[0] and sh in ((w,), (1, w)):
+            x, sh = x.reshape(1, w).expand(n, w) if hasattr(x, 'data_ptr') else np.broadcast_to(np.reshape(x, (1, w)), (n, w)), (n, w)
+        if sh == (n, w):
+            x = x.unsqueeze(0).expand(G, n, w) if hasattr(x, 'data_ptr') else np.broadcast_to(x[None], (G, n, w))
+        elif sh != (G, n, w):
+            raise ValueError(f'{name} must be [{n}, {w}] or [{G}, {n}, {w}], got {sh}')
+        flat.append(x.reshape(G * n, w))
+    rep = cfgs.repeat_interleave(n) if hasattr(cfgs, 'data_ptr') else np.repeat(np.asarray(cfgs, dtype=np.float32), n)
+    return G, n, flat, rep
+
+
 class _Rows:
     """One per-row info array of an update, read from the engine on first use (fql_iqld_read_rows) and cached.  The engine keeps the
     rows of the LAST actor step only: a first read after a later actor step raises instead of returning that later step's rows."""
@@ -265,6 +313,39 @@ class IQLDiffusionAgent(KindAgent):
         self._check(self._lib.fql_iqld_sample_actions(self._h, ob.ptr, n, z.ptr, self._sample_seed(seed, noises), float(cfg), optr,
                                                       self._stream([ob, z])))
         return out
+
+    # -- guidance sweeps: one weight per row --------------------------------------------------------
+    def sample_actions_rows(self, observations, cfgs, seed=None, noises=None):
+        """sample_actions with one guidance weight per row, in ONE call: observations [N, od], cfgs [N] -> [N, act] (no squeeze).  Row
+        j is, bit for bit, sample_actions(observations[j], cfg=cfgs[j], noises=noises[j]); with engine noise (`noises=None`) row j draws
+        what row j of sample_actions(observations, seed=seed) draws.  A call costs 4 + S nl + 1 launches whatever N <= 2048 is."""
+        od, ad = self.config['ob_dims'][0], self.config['action_dim']
+        observations = as_array(observations)
+        if len(observations.shape) != 2 or int(observations.shape[1]) != od or int(observations.shape[0]) < 1:
+            raise ValueError(f'observations must be [N, {od}] with N >= 1, got {tuple(observations.shape)}')
+        n = int(observations.shape[0])
+        cfgs = check_cfgs(cfgs, n, 'row')
+        if noises is not None and tuple(as_array(noises).shape) != (n, ad):
+            raise ValueError(f'noises must be [{n}, {ad}], got {tuple(as_array(noises).shape)}')
+        ob, w, z = _Arg(observations, (n, od)), _Arg(cfgs, (n,)), _Arg(noises, (n, ad))
+        out, optr = self._actions_out(observations, (n, ad))
+        self._check(self._lib.fql_iqld_sample_actions_cfgs(self._h, ob.ptr, n, z.ptr, self._sample_seed(seed, noises), w.ptr, optr,
+                                                           self._stream([ob, z, w])))
+        return out
+
+    def sample_actions_sweep(self, observations, cfgs, seed=None, noises=None):
+        """Every weight of an evaluation sweep in one call: cfgs [G] -> [G, n, act], slice g = sample_actions(.., cfg=cfgs[g]).
+        observations: [n, od] (every weight sees the same rows) or [G, n, od] (one vector env per weight).  noises: None (engine RNG:
+        row g n + j of the flat call), [n, act] (shared by every weight: common random numbers) or [G, n, act]."""
+        od, ad = self.config['ob_dims'][0], self.config['action_dim']
+        G, n, (ob, z), w = sweep_inputs(cfgs, [('observations', observations, od), ('noises', noises, ad)])
+        return self.sample_actions_rows(ob, w, seed=seed, noises=z).reshape(G, n, ad)
+
+    def sample_cfgs_stats(self):
+        """Launches of one sample_actions_rows / sample_actions_sweep call of <= 2048 rows."""
+        ls = C.c_int64()
+        self._check(self._lib.fql_sample_cfgs_stats(self._h, C.byref(ls)))
+        return int(ls.value)
 
     # -- per-TrainState optimizer state ------------------------------------------------------------
     def get_steps(self):

@@ -684,6 +684,22 @@ int fql_cfgrl_read_rows(fql_handle h, int probe, int64_t* idx, int64_t* goal_idx
 /* launches and algorithmic MACs of one update; launches of one sampling call of <= 2048 observations */
 int fql_cfgrl_stats(fql_handle h, int64_t* launches_per_update, int64_t* macs_per_update, int64_t* launches_per_sample);
 
+/* ---- Guidance sweeps: the two classifier-free-guidance samplers with ONE WEIGHT PER ROW, so that one call serves every weight of an
+ * evaluation sweep (main.py:298-330 evaluates cfg in [1, 1.5, 3, 5], one rollout each) or several vector envs stepped in lockstep.
+ * cfgs: [n] floats, host or device.  Row j of the result is, bit for bit, row j of fql_iqld_sample_actions / fql_cfgrl_sample_actions
+ * called with cfg = cfgs[j] on the same observation (goal), noise row and, with engine noise, the same seed and row number.  The call
+ * runs a program of its own (S - 1 launches fewer: the guidance step of Euler step i - 1 runs inside the first launch of step i); the
+ * scalar calls above, their launches and their results are untouched.
+ * FQL_E_INVALID: cfgs == NULL, n <= 0, a non-finite weight in a host array (fql_last_error names the row; a device array is not read on
+ * the host), goals == NULL on CFGRL.  FQL_E_STATE: a handle of another kind. */
+int fql_iqld_sample_actions_cfgs(fql_handle h, const float* observations, int n, const float* noise, uint64_t seed,
+                                 const float* cfgs /* [n] */, float* out, void* stream);
+int fql_cfgrl_sample_actions_cfgs(fql_handle h, const float* observations, const float* goals, int n, const float* noise,
+                                  uint64_t seed, const float* cfgs /* [n] */, float* out, void* stream);
+/* launches of one such call of <= 2048 rows, counted from the built program: 4 + S nl + 1 (IQL-diffusion), 3 + S nl + 1 (CFGRL), where
+ * fql_iqld_stats / fql_cfgrl_stats report 4 + S (nl + 1) / 3 + S (nl + 1) for the scalar call.  IQL-diffusion and CFGRL handles only. */
+int fql_sample_cfgs_stats(fql_handle h, int64_t* launches_per_call);
+
 #ifdef __cplusplus
 }
 #endif
