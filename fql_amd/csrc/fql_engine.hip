@@ -220,6 +220,7 @@ struct Op {
     int adam_polyak = -1;          // Polyak range of an Adam op in floats from offset 0 (-1: critic_size; 0: no Polyak step)
     float adam_lr = 0.f;           // > 0: this launch's learning rate (IQL-diffusion: one per TrainState), else fql_config.lr
     DevState* adam_st = nullptr;   // the counters this launch's bias correction reads (IQL-diffusion's actor), null: the handle's
+    bool adam_fin = false;         // an Adam op of an update without a finalize launch: its workgroups take tickets, the last runs that code (fin_mode)
     int fin_mode = 0;
     Bound k;                 // agent ops: the launch, bound where the op is emitted
     int level = 0;
@@ -258,6 +259,12 @@ struct Launch {
 // engine is created.
 inline bool ka_tasks_env() {
     const char* e = getenv("FQL_KERNARG_TASKS");
+    return !e || atoi(e) != 0;
+}
+// FQL_FUSED_TAIL=0: the FQL update keeps its finalize launch; by default the last-arriving workgroup of its two Adam launches runs that code
+// (DESIGN.md section 4).  For the A/B and the bitwise twin of the tests.  Read when an engine is created.
+inline bool fused_tail_env() {
+    const char* e = getenv("FQL_FUSED_TAIL");
     return !e || atoi(e) != 0;
 }
 // a side-lane launch's four host tables as SideArgs; null when a family exceeds its capacity
@@ -581,6 +588,8 @@ struct fql_engine {
     WfragTask* d_wfrag = nullptr;
     int wfrag_n = 0, wfrag_grid = 0;
     const bool ka_tasks = ka_tasks_env();   // FQL_KERNARG_TASKS, as it stood when this engine was created
+    const bool fused_tail = fused_tail_env();   // FQL_FUSED_TAIL, as it stood when this engine was created
+    unsigned* d_ticket = nullptr;    // arrival counter of an update's Adam workgroups (fql_adam_body): 0 between updates
     std::vector<void*> chain_allocs;
     bool split_build = false;   // building the data-parallel program: lane 1 must not depend on lane 0's backward
     bool wide_tiles = false;    // three-lane programs: 32 x 64 side tiles everywhere (the other lanes fill the CUs a launch leaves idle; +1 %)
@@ -1078,6 +1087,9 @@ struct fql_engine {
         HIP_CHECK(hipMemcpy(d_leaf_range, range.data(), range.size() * sizeof(int), hipMemcpyHostToDevice));
         HIP_CHECK(hipMalloc((void**)&d_partials, (size_t)n_chunks * 4 * sizeof(float)));
         HIP_CHECK(hipMemset(d_partials, 0, (size_t)n_chunks * 4 * sizeof(float)));
+        // zeroed here and never again: the workgroup that finds the launch complete puts the counter back to 0 (fql_adam_body)
+        HIP_CHECK(hipMalloc((void**)&d_ticket, 16));
+        HIP_CHECK(hipMemset(d_ticket, 0, 16));
     }
 
     const Leaf* find_leaf(const char* name) const {
@@ -2383,6 +2395,11 @@ struct fql_engine {
                 AdamArgs a{P, G, Mu, Nu, P + n_train, d_chunks, L.op.adam_st ? L.op.adam_st : d_state, d_partials, L.op.adam_c0,
                            L.op.adam_polyak >= 0 ? L.op.adam_polyak : (int)critic_size, L.op.adam_lr > 0.f ? L.op.adam_lr : cfg.lr, cfg.tau, tl,
                            L.op.adam_n1 > 0 ? L.op.adam_n : -1, L.op.adam_c1};
+                if (L.op.adam_fin) {
+                    a.ticket = d_ticket;
+                    a.ticket_n = n_chunks;
+                    a.fin = FinalizeArgs{d_state, d_chunks, d_partials, d_leaf_range, n_chunks, n_train_leaves, L.op.fin_mode, -1};
+                }
                 FQL_LAUNCH(fql_adam_kernel, dim3(L.op.adam_n < 0 ? n_chunks : L.op.adam_n + L.op.adam_n1), dim3(FQL_THREADS), 0, s, a);
                 break;
             }
@@ -2964,6 +2981,16 @@ struct fql_engine {
         adam_for(pr, 2, {NET_C0, NET_C1, NET_BC}, fill_lane_full, 0);
         emit_wfrag(pr);   // lane 1, behind the BC flow's Adam: the next update's chain reads the copies
         adam_for(pr, 1, {NET_OS}, 0);
+        // (the modules' chunk ranges tile [0, n_chunks): were a leaf outside the three trained modules, the ticket would never complete)
+        if (fused_tail && mod_chunkn[0] + mod_chunkn[1] + mod_chunkn[2] == n_chunks) {
+            // No finalize launch: the two Adam launches above cover every chunk once, each of their workgroups takes a ticket, and the
+            // workgroup that takes the last one runs the finalize code (fql_adam_body).  That workgroup may sit in either launch, so the
+            // ops keep their own read and write sets and no edge joins the lanes: the ticket, not the schedule, puts the counters'
+            // update behind their last reader.  Nothing behind the two launches reads the counters or the infos (the weight-copy
+            // refresh does not), and the update ends behind every lane.
+            for (Op& o : pr.ops) if (o.type == OP_ADAM) { o.adam_fin = true; o.fin_mode = 1; }
+            return;
+        }
         Op f{};
         f.type = OP_FINALIZE;
         f.fin_mode = 1;
@@ -5260,7 +5287,7 @@ int fql_destroy(fql_handle h) {
     for (auto* m : {&h->evals, &h->sweeps})
         for (auto& kv : *m)
             for (void* p : kv.second->allocs) hipFree(p);
-    hipFree(h->P); hipFree(h->G); hipFree(h->Mu); hipFree(h->Nu); hipFree(h->d_chunks); hipFree(h->d_partials); hipFree(h->d_leaf_range); hipFree(h->d_state); hipFree(h->d_src); hipFree(h->d_emb); hipFree(h->iql_info); hipFree(h->d_state_a);
+    hipFree(h->P); hipFree(h->G); hipFree(h->Mu); hipFree(h->Nu); hipFree(h->d_chunks); hipFree(h->d_partials); hipFree(h->d_ticket); hipFree(h->d_leaf_range); hipFree(h->d_state); hipFree(h->d_src); hipFree(h->d_emb); hipFree(h->iql_info); hipFree(h->d_state_a);
     if (h->h_src_ring) hipHostFree(h->h_src_ring);
     hipFree(h->d_gsrc); hipFree(h->ds_final); hipFree(h->ds_reps);
     if (h->h_gsrc_ring) hipHostFree(h->h_gsrc_ring);

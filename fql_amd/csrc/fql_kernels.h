@@ -2222,6 +2222,14 @@ struct MiscTask {
 //   reads the PRE-step critic: p_old is still in a register when the target is written).
 // ------------------------------------------------------------------------------------------------
 struct AdamChunk { int off, len, leaf; };
+struct FinalizeArgs {
+    DevState* st;
+    const AdamChunk* chunks;
+    const float* partials;   // [n_chunks][4]
+    const int* leaf_range;   // [nleaves + 1] chunk index ranges (chunks of a leaf are contiguous)
+    int n_chunks, nleaves, do_grad_stats;
+    int tl;
+};
 struct AdamArgs {
     float *P, *G, *Mu, *Nu, *T;  // T = target arena (same layout as the critic block at offset 0)
     const AdamChunk* chunks;
@@ -2232,6 +2240,13 @@ struct AdamArgs {
     float lr, tau;
     int tl;
     int n0, chunk1;        // two modules in one launch: workgroups [0, n0) take chunks chunk0 + b, the rest chunk1 + (b - n0); n0 < 0: one range
+    // The update's fused tail (FQL programs, FQL_FUSED_TAIL): ticket != null makes this one of the update's Adam launches, which run on two
+    // lanes with no edge between them and together cover every chunk once.  Each of their workgroups publishes its partial write-through and
+    // takes a ticket from the handle's one counter; the workgroup whose ticket is ticket_n - 1, in whichever launch it runs, has every chunk's
+    // partial published in front of it: it runs the finalize code (fin) and puts the counter back to 0.  Nobody waits for anybody.
+    unsigned* ticket;
+    int ticket_n;          // arrivals that complete the update: the Adam workgroups of all its launches (= the chunks)
+    FinalizeArgs fin;
 };
 __device__ __forceinline__ int f2ord(float f) {
     const int i = __float_as_int(f);
@@ -2239,8 +2254,73 @@ __device__ __forceinline__ int f2ord(float f) {
 }
 __device__ __forceinline__ float ord2f(int i) { return __int_as_float(i >= 0 ? i : i ^ 0x7FFFFFFF); }
 
+// one float of the Adam partials as the finalize code reads it.  SC1: past this CU's L1 (an agent-scope load), the form every load takes in
+// a workgroup that reads partials other workgroups, of its own launch or of one running beside it, have just published (fql_adam_body)
+template <bool SC1>
+__device__ __forceinline__ float ld_partial(const float* p) {
+    if constexpr (SC1) return __hip_atomic_load((FQL_GAS float*)p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    else return *p;
+}
+// grad/max, grad/min, grad/norm = sum over leaves of ||g_leaf||_2 (utils/flax_utils.py:139-157); target-critic leaves
+// contribute zeros, which bound grad/max >= 0 >= grad/min (F5).  Also advances optax count / TrainState.step / RNG step.
+// One workgroup; sh[4] and leafn[256] are its LDS.
+template <bool SC1>
+__device__ __forceinline__ void fql_finalize_core(const FinalizeArgs& A, float* sh, float* leafn) {
+    DevState* st = A.st;
+    if (!A.do_grad_stats) return;
+    // (the loads of a pass are issued several at a time and folded in the order of the chunks: a load past L1 is a trip to L2 or further,
+    // and a thread's 16 of them one behind the other were most of what this code cost inside the Adam launch)
+    float mx = -INFINITY, mn = INFINITY;
+    for (int c0 = threadIdx.x; c0 < A.n_chunks; c0 += 4 * FQL_THREADS) {
+        float vx[4], vn[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int cidx = c0 + j * FQL_THREADS;
+            vx[j] = cidx < A.n_chunks ? ld_partial<SC1>(A.partials + 4 * cidx + 1) : -INFINITY;
+            vn[j] = cidx < A.n_chunks ? ld_partial<SC1>(A.partials + 4 * cidx + 2) : INFINITY;
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) { mx = fmaxf(mx, vx[j]); mn = fminf(mn, vn[j]); }
+    }
+    // 4 threads per leaf, each a contiguous quarter of the leaf's chunks, combined in fixed order
+    for (int base = 0; base < A.nleaves; base += 64) {
+        const int l = base + (threadIdx.x >> 2), sub = threadIdx.x & 3;
+        float s = 0.f;
+        if (l < A.nleaves) {
+            const int b = A.leaf_range[l], e = A.leaf_range[l + 1];
+            const int per = (e - b + 3) >> 2;
+            const int lo = b + sub * per, hi = min(e, lo + per);
+            for (int c0 = lo; c0 < hi; c0 += 8) {
+                float v[8];
+#pragma unroll
+                for (int j = 0; j < 8; ++j) v[j] = c0 + j < hi ? ld_partial<SC1>(A.partials + 4 * (c0 + j)) : 0.f;
+#pragma unroll
+                for (int j = 0; j < 8; ++j) if (c0 + j < hi) s += v[j];
+            }
+        }
+        s += __shfl_xor(s, 1);
+        s += __shfl_xor(s, 2);
+        if (l < A.nleaves && sub == 0) leafn[l] = sqrtf(s);
+    }
+    const float tmx = block_max(mx, sh), tmn = -block_max(-mn, sh);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        float nrm = 0.f;
+        for (int i = 0; i < A.nleaves; ++i) nrm += leafn[i];
+        st->info[10] = fmaxf(tmx, 0.0f);
+        st->info[11] = fminf(tmn, 0.0f);
+        st->info[12] = nrm;
+        st->rng_step += 1;
+        st->adam_count += 1;
+        st->train_step += 1;
+        st->b1pow *= 0.9;
+        st->b2pow *= 0.999;
+    }
+}
+
 __device__ __forceinline__ void fql_adam_body(const AdamArgs& A) {
     __shared__ float sh[4];
+    __shared__ float leafn[256];   // the finalize code's, in the workgroup that runs it
     tl_enter(A.tl);
     const int cidx = (A.n0 < 0 || (int)blockIdx.x < A.n0) ? (int)blockIdx.x + A.chunk0 : (int)blockIdx.x - A.n0 + A.chunk1;
     const AdamChunk ch = A.chunks[cidx];  // <= 4096 elements, offset and length multiples of 4
@@ -2282,9 +2362,29 @@ __device__ __forceinline__ void fql_adam_body(const AdamArgs& A) {
     // per-chunk partials, folded in fixed order by the finalize kernel: no atomics, bitwise reproducible stats
     const float tss = block_sum(ss, sh);
     const float tmx = block_max(mx, sh), tmn = -block_max(-mn, sh);
+    float* pp = A.partials + 4 * (size_t)cidx;
+    if (!A.ticket) {
+        if (threadIdx.x == 0) { pp[0] = tss; pp[1] = tmx; pp[2] = tmn; }
+        tl_exit(A.tl);
+        return;
+    }
+    // The hand-off to the last arriver (cdna_hip_programming.md Guideline 16, R1 with a counter): the partial leaves as ONE write-through
+    // 16-byte store, the storing lane waits for it, then takes its ticket.  No fence: this workgroup has just dirtied tens of KB, and an
+    // agent-scope release would write all of it back before the ticket.  st->b1pow, b2pow and grad_scale were read above, in front of the
+    // add, in every Adam launch of the update, so the counters the last arriver advances are read by nobody else any more.
     if (threadIdx.x == 0) {
-        float* pp = A.partials + 4 * (size_t)cidx;
-        pp[0] = tss; pp[1] = tmx; pp[2] = tmn;
+        const u32x4 v = {__float_as_uint(tss), __float_as_uint(tmx), __float_as_uint(tmn), 0u};
+        __builtin_amdgcn_raw_buffer_store_b128(v, __builtin_amdgcn_make_buffer_rsrc(pp, 0, 16, 0x00020000), 0, 0, 16);   // aux 16 = sc1
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        const unsigned t = __hip_atomic_fetch_add((FQL_GAS unsigned*)A.ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        sh[0] = t == (unsigned)(A.ticket_n - 1) ? 1.0f : 0.0f;
+    }
+    __syncthreads();
+    const bool last = sh[0] != 0.0f;   // (the finalize code's first write of sh is behind a barrier of its own)
+    if (last) {
+        // every partial is read past this CU's L1: each was published as above, by this launch or by the update's other Adam launch
+        fql_finalize_core<true>(A.fin, sh, leafn);
+        if (threadIdx.x == 0) __hip_atomic_store((FQL_GAS unsigned*)A.ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
     tl_exit(A.tl);
 }
@@ -2292,55 +2392,12 @@ __global__ __launch_bounds__(FQL_THREADS) void fql_adam_kernel(AdamArgs A) { fql
 // multi-instance entry point (agent groups): blockIdx.y picks the member, its argument struct comes from a device array
 __global__ __launch_bounds__(FQL_THREADS) void fql_adam_multi_kernel(const AdamArgs* __restrict__ args) { const AdamArgs A = ((const FQL_CONST_AS AdamArgs*)args)[blockIdx.y]; fql_adam_body(A); }
 
-struct FinalizeArgs {
-    DevState* st;
-    const AdamChunk* chunks;
-    const float* partials;   // [n_chunks][4]
-    const int* leaf_range;   // [nleaves + 1] chunk index ranges (chunks of a leaf are contiguous)
-    int n_chunks, nleaves, do_grad_stats;
-    int tl;
-};
-// grad/max, grad/min, grad/norm = sum over leaves of ||g_leaf||_2 (utils/flax_utils.py:139-157); target-critic leaves
-// contribute zeros, which bound grad/max >= 0 >= grad/min (F5).  Also advances optax count / TrainState.step / RNG step.
+// the finalize launch (every kind but FQL with its fused tail): the code above as one workgroup of its own, behind every Adam launch
 __device__ __forceinline__ void fql_finalize_body(const FinalizeArgs& A) {
     __shared__ float sh[4];
     __shared__ float leafn[256];
-    DevState* st = A.st;
     tl_enter(A.tl);
-    if (!A.do_grad_stats) return;
-    float mx = -INFINITY, mn = INFINITY;
-    for (int cidx = threadIdx.x; cidx < A.n_chunks; cidx += FQL_THREADS) {
-        mx = fmaxf(mx, A.partials[4 * cidx + 1]);
-        mn = fminf(mn, A.partials[4 * cidx + 2]);
-    }
-    // 4 threads per leaf, each a contiguous quarter of the leaf's chunks, combined in fixed order
-    for (int base = 0; base < A.nleaves; base += 64) {
-        const int l = base + (threadIdx.x >> 2), sub = threadIdx.x & 3;
-        float s = 0.f;
-        if (l < A.nleaves) {
-            const int b = A.leaf_range[l], e = A.leaf_range[l + 1];
-            const int per = (e - b + 3) >> 2;
-            const int lo = b + sub * per, hi = min(e, lo + per);
-            for (int cidx = lo; cidx < hi; ++cidx) s += A.partials[4 * cidx];
-        }
-        s += __shfl_xor(s, 1);
-        s += __shfl_xor(s, 2);
-        if (l < A.nleaves && sub == 0) leafn[l] = sqrtf(s);
-    }
-    const float tmx = block_max(mx, sh), tmn = -block_max(-mn, sh);
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        float nrm = 0.f;
-        for (int i = 0; i < A.nleaves; ++i) nrm += leafn[i];
-        st->info[10] = fmaxf(tmx, 0.0f);
-        st->info[11] = fminf(tmn, 0.0f);
-        st->info[12] = nrm;
-        st->rng_step += 1;
-        st->adam_count += 1;
-        st->train_step += 1;
-        st->b1pow *= 0.9;
-        st->b2pow *= 0.999;
-    }
+    fql_finalize_core<false>(A, sh, leafn);
 }
 __global__ __launch_bounds__(FQL_THREADS) void fql_finalize_kernel(FinalizeArgs A) { fql_finalize_body(A); }
 // multi-instance entry point (agent groups): blockIdx.y picks the member, its argument struct comes from a device array
