@@ -130,7 +130,7 @@ struct Leaf {
 // OP_WGRAD, OP_LNBWD, OP_POSTOS and the OP_LOSS_{CRITIC,Q,BC} ops ride in OP_GEMM64 (side-lane) launches, never in launches of their own.
 // OP_PEC and OP_XCHAIN are reserved (retired persistent Euler chains): the values index profile labels (bench.py OP_NAMES) and order launches.
 // An agent's types (OP_IFQL_PREP and later) are labels and sort keys only: their launches are bound where the ops are emitted (Bound, below),
-// so a new agent adds enum labels and emit sites, no payload member of Op and no case of issue().
+// so a new agent adds enum labels and emit sites (fql_engine::emit()), no payload member of Op and no case of issue().
 enum OpType { OP_GEMM, OP_GEMM64, OP_WGRAD, OP_LNBWD, OP_PREP, OP_POSTOS, OP_EULER_FIN, OP_PEC, OP_LOSS_CRITIC, OP_LOSS_Q, OP_LOSS_BC,
               OP_LOSS_ACTOR, OP_CONV_WPREP, OP_CONV, OP_CONV_U8, OP_POOL, OP_POOL_BWD, OP_CONV_WGRAD, OP_CONV_WRED, OP_ENC_DZ, OP_CHAIN, OP_WFRAG, OP_XCHAIN, OP_HEAD_DGRAD, OP_DGRAD0, OP_ADAM,
               OP_FINALIZE,
@@ -655,9 +655,8 @@ struct fql_engine {
         PassBuf p_q[2];
         Program prog_q;
     };
-    std::map<int, std::unique_ptr<Eval>> evals;
-    // the sweep programs of the CFG samplers (get_sweep): workspaces of their own, so that no sample_actions workspace or program changes
-    std::map<int, std::unique_ptr<Eval>> sweeps;
+    // (the bool: the sweep programs of the CFG samplers, workspaces of their own: get_eval)
+    std::map<std::pair<int, bool>, std::unique_ptr<Eval>> evals;
 
     // agent groups (fql_group_*): the group this engine is a member of, the event behind that group's last update and whether an entry
     // point of this engine has run since (then the next group update orders itself behind this engine's stream)
@@ -1498,6 +1497,17 @@ struct fql_engine {
     void push(Program& pr, Op& op) {
         op.lane = emit_lane;
         pr.ops.push_back(op);
+    }
+    // an agent op appended on emit_lane: the bound launch and the buffers it reads and writes.  The reference is for the sites that
+    // append conditional reads or writes (it holds until the next op is pushed).
+    Op& emit(Program& pr, OpType type, const Bound& k, std::vector<const void*> reads, std::vector<const void*> writes) {
+        Op op{};
+        op.type = type;
+        op.k = k;
+        op.reads = std::move(reads);
+        op.writes = std::move(writes);
+        push(pr, op);
+        return pr.ops.back();
     }
 
     // forward of one pass appended to a program.  final_flags: epilogue of the last layer.
@@ -3006,6 +3016,35 @@ struct fql_engine {
     FinalizeArgs fin_args(int do_grad_stats) const {
         return FinalizeArgs{d_state, d_chunks, d_partials, d_leaf_range, n_chunks, n_train_leaves, do_grad_stats, -1};
     }
+    // An agent's finalize op, on lane 0.  tl_at: where the bound arguments hold FinalizeArgs::tl (-1: the kernel takes none);
+    // grad_partials: it also reads the three modules' gradient partials the Adam launch left.
+    void emit_fin(Program& pr, OpType type, Bound k, int tl_at, std::vector<const void*> reads, bool grad_partials, std::vector<const void*> writes) {
+        k.tl_at = tl_at;
+        if (grad_partials) for (int m = 0; m < 3; ++m) reads.push_back(d_partials + mod_chunk0[m] * 4);
+        emit_lane = 0;
+        emit(pr, type, k, std::move(reads), std::move(writes));
+    }
+    // the flow-matching loss mean((pred - vel)^2) over B act elements of pass `p` into `info_slot` (IFQL, BC, CFGRL): a payload op, it
+    // rides in the side launch of its level
+    void emit_loss_bc(Program& pr, const PassBuf& p, const void* info_slot, bool with_grads) {
+        const int ad = cfg.act_dim;
+        Op op{};
+        op.type = OP_LOSS_BC;
+        op.lb = LossBcArgs{p.out, vel, with_grads ? p.dz.back() : nullptr, d_state, B, ad, pad16(ad), with_grads ? 1 : 0};
+        op.reads = {p.out, vel};
+        op.writes = {info_slot};
+        if (with_grads) op.writes.push_back(p.dz.back());
+        push(pr, op);
+    }
+    // the tail of every agent's build_*_workspace(): launches and graphs of the programs just built (schedule() reads the ops alone, so
+    // no schedule depends on another program's capture); the sources are described again on the next update
+    void finish_programs(std::initializer_list<Program*> progs) {
+        for (Program* pr : progs) schedule(*pr, ws_allocs);
+        for (Program* pr : progs) capture(*pr);
+        split_ok = false;
+        src_valid = false;
+        gsrc_valid = false;
+    }
 
     // ---------------------------------------------------------------------------------------
     // the IFQL update as a program (agents/ifql.py:79-120).  No Euler chain: every level is throughput work on the side lanes.
@@ -3022,64 +3061,35 @@ struct fql_engine {
         allow64 = true;
         emit_lane = 0;
         {
-            Op op{};
-            op.type = OP_IFQL_PREP;
             const IfqlPrepArgs iprep{d_src, st, seed, B, od, ad, nets[NET_OS].in_p(), nets[NET_C0].in_p(), nets[NET_BC].in_p(), ap,
                                      X_v, X_c1, X_bc, vel, w_rew, w_mask};
-            op.k = bind(fql_ifql_prep_kernel, (iprep.B + 3) / 4, iprep);
-            op.writes = {X_v, X_c1, X_bc, vel, w_rew, w_mask};
-            push(pr, op);
+            emit(pr, OP_IFQL_PREP, bind(fql_ifql_prep_kernel, (iprep.B + 3) / 4, iprep), {}, {X_v, X_c1, X_bc, vel, w_rew, w_mask});
         }
         emit_lane = 1;
         emit_forward(pr, p_v, with_grads);                        // value(obs) ifql.py:34, value(next_obs) ifql.py:47
         for (int e = 0; e < 2; ++e) emit_forward(pr, p_ct[e], false);   // target_critic(obs, actions) ifql.py:33
         {
-            Op op{};
-            op.type = OP_IFQL_LOSS_V;
             const IfqlValueArgs iv{p_v.out, p_ct[0].out, p_ct[1].out, with_grads ? p_v.dz.back() : nullptr, st, B, expectile};
-            op.k = bind(fql_ifql_loss_value_kernel, 1, iv);
-            op.reads = {p_v.out, p_ct[0].out, p_ct[1].out};
-            op.writes = {I_V};
+            Op& op = emit(pr, OP_IFQL_LOSS_V, bind(fql_ifql_loss_value_kernel, 1, iv), {p_v.out, p_ct[0].out, p_ct[1].out}, {I_V});
             if (with_grads) op.writes.push_back(p_v.dz.back());
-            push(pr, op);
         }
         if (with_grads) emit_backward(pr, p_v, 0, B, true, false);
         emit_forward(pr, p_bc, with_grads);                       // actor_flow(obs, x_t, t) ifql.py:71
-        {
-            Op op{};
-            op.type = OP_LOSS_BC;
-            op.lb = LossBcArgs{p_bc.out, vel, with_grads ? p_bc.dz.back() : nullptr, st, B, ad, ap, with_grads ? 1 : 0};
-            op.reads = {p_bc.out, vel};
-            op.writes = {I_A};
-            if (with_grads) op.writes.push_back(p_bc.dz.back());
-            push(pr, op);
-        }
+        emit_loss_bc(pr, p_bc, I_A, with_grads);
         if (with_grads) emit_backward(pr, p_bc, 0, B, true, false);
         emit_lane = 2;
         for (int e = 0; e < 2; ++e) emit_forward(pr, p_c1[e], with_grads);   // critic(obs, actions) ifql.py:50
         {
-            Op op{};
-            op.type = OP_IFQL_LOSS_C;
             const IfqlCriticArgs ic{p_v.out + (size_t)B * nets[NET_OS].layers.back().out_p, p_c1[0].out, p_c1[1].out, w_rew, w_mask,
                                     with_grads ? p_c1[0].dz.back() : nullptr, with_grads ? p_c1[1].dz.back() : nullptr, st, B, cfg.discount};
-            op.k = bind(fql_ifql_loss_critic_kernel, 1, ic);
-            op.reads = {p_v.out, p_c1[0].out, p_c1[1].out, w_rew, w_mask};
-            op.writes = {I_C};
+            Op& op = emit(pr, OP_IFQL_LOSS_C, bind(fql_ifql_loss_critic_kernel, 1, ic), {p_v.out, p_c1[0].out, p_c1[1].out, w_rew, w_mask}, {I_C});
             if (with_grads) { op.writes.push_back(p_c1[0].dz.back()); op.writes.push_back(p_c1[1].dz.back()); }
-            push(pr, op);
         }
         if (with_grads)
             for (int e = 0; e < 2; ++e) emit_backward(pr, p_c1[e], 0, B, true, false);
         if (with_grads) adam_for(pr, 2, {NET_C0, NET_C1, NET_BC, NET_OS}, 0, -2);   // every chunk, one launch; Polyak from the pre-step critic
-        Op f{};
-        f.type = OP_IFQL_FIN;
-        f.k = bind(fql_ifql_finalize_kernel, 1, fin_args(with_grads ? 1 : 0));
-        f.k.tl_at = offsetof(FinalizeArgs, tl);
-        f.reads = {I_V, I_C, I_A};
-        if (with_grads) for (int m = 0; m < 3; ++m) f.reads.push_back(d_partials + mod_chunk0[m] * 4);
-        f.writes = {&st->info[8], st};
-        emit_lane = 0;
-        push(pr, f);
+        emit_fin(pr, OP_IFQL_FIN, bind(fql_ifql_finalize_kernel, 1, fin_args(with_grads ? 1 : 0)), offsetof(FinalizeArgs, tl), {I_V, I_C, I_A},
+                 with_grads, {&st->info[8], st});
     }
 
     void build_ifql_workspace() {
@@ -3100,12 +3110,7 @@ struct fql_engine {
         }
         build_ifql_program(prog_full, true);
         build_ifql_program(prog_loss, false);
-        schedule(prog_full, W);
-        schedule(prog_loss, W);
-        capture(prog_full);
-        capture(prog_loss);
-        split_ok = false;
-        src_valid = false;
+        finish_programs({&prog_full, &prog_loss});
     }
 
     // ---------------------------------------------------------------------------------------
@@ -3127,29 +3132,21 @@ struct fql_engine {
         allow64 = true;
         emit_lane = 0;
         {
-            Op op{};
-            op.type = OP_REBRAC_PREP;
             const RebracPrepArgs rprep{d_src, st, seed, B, od, ad, inp_a, inp_c, ap, X_c1, X_t, X_q, X_a, X_ta, w_act, w_nact, w_noise,
                                        w_rew, w_mask, zero_actor ? G + na.off : nullptr, zero_actor ? (int64_t)na.size : 0};
-            op.k = bind(fql_rebrac_prep_kernel, (rprep.B + 3) / 4, rprep);
-            op.writes = {X_c1, X_t, X_q, X_a, X_ta, w_act, w_nact, w_noise, w_rew, w_mask};
+            Op& op = emit(pr, OP_REBRAC_PREP, bind(fql_rebrac_prep_kernel, (rprep.B + 3) / 4, rprep), {},
+                          {X_c1, X_t, X_q, X_a, X_ta, w_act, w_nact, w_noise, w_rew, w_mask});
             if (zero_actor)   // critic-only step: the actor's gradient is zero (rebrac.py:104-106), not the last full step's
                 for (const Layer& L : na.layers) {
                     op.writes.push_back(G + L.w); op.writes.push_back(G + L.b);
                     if (L.ln) { op.writes.push_back(G + L.g); op.writes.push_back(G + L.be); }
                 }
-            push(pr, op);
         }
         auto act_op = [&](const PassBuf& p, const float* noise, float* X, bool target) {
-            Op op{};
-            op.type = OP_REBRAC_ACT;
             const RebracActArgs ract{p.out, noise, X, 0, 0, B, ad, ap, ap, inp_c, od, 0, target ? 1 : 0, rcfg.tanh_squash, target ? 1 : 0,
                                      rcfg.actor_noise, rcfg.actor_noise_clip};
-            op.k = bind(fql_rebrac_act_kernel, (ract.n * ract.ad + FQL_THREADS - 1) / FQL_THREADS, ract);
-            op.reads = {p.out};
+            Op& op = emit(pr, OP_REBRAC_ACT, bind(fql_rebrac_act_kernel, (ract.n * ract.ad + FQL_THREADS - 1) / FQL_THREADS, ract), {p.out}, {X});
             if (noise) op.reads.push_back(noise);
-            op.writes = {X};
-            push(pr, op);
         };
         emit_lane = 1;
         emit_forward(pr, p_ta, false);                                  // target_actor(next_obs)  rebrac.py:28
@@ -3160,42 +3157,29 @@ struct fql_engine {
             act_op(p_a, nullptr, X_q, false);                           // a = mode  rebrac.py:58
             for (int e = 0; e < 2; ++e) emit_forward(pr, p_q[e], with_grads);   // critic(obs, a), stored params  rebrac.py:61
             {
-                Op op{};
-                op.type = OP_REBRAC_LOSS_A;
                 const RebracActorArgs ra{p_q[0].out, p_q[1].out, X_q, w_act, with_grads ? p_q[0].dz.back() : nullptr,
                                          with_grads ? p_q[1].dz.back() : nullptr, st, B, od, ad, inp_c, ap, rcfg.alpha_actor};
-                op.k = bind(fql_rebrac_loss_actor_kernel, 1, ra);
-                op.reads = {p_q[0].out, p_q[1].out, X_q, w_act};
-                op.writes = {I_A};
+                Op& op = emit(pr, OP_REBRAC_LOSS_A, bind(fql_rebrac_loss_actor_kernel, 1, ra), {p_q[0].out, p_q[1].out, X_q, w_act}, {I_A});
                 if (with_grads) { op.writes.push_back(p_q[0].dz.back()); op.writes.push_back(p_q[1].dz.back()); }
-                push(pr, op);
             }
             if (with_grads) {
                 for (int e = 0; e < 2; ++e) emit_backward(pr, p_q[e], 0, B, false, true);   // dQ/da only: the critic's params get no gradient
-                Op op{};
-                op.type = OP_REBRAC_AGRAD;
                 const RebracActorGradArgs rag{p_q[0].dx0, p_q[1].dx0, X_q, w_act, p_a.dz.back(), B, od, ad, inp_c, ap,
                                               rcfg.alpha_actor * 2.0f / (float)B, rcfg.tanh_squash};
-                op.k = bind(fql_rebrac_actor_grad_kernel, (rag.B * rag.ad + FQL_THREADS - 1) / FQL_THREADS, rag);
-                op.reads = {p_q[0].dx0, p_q[1].dx0, X_q, w_act};
-                op.writes = {p_a.dz.back()};
-                push(pr, op);
+                emit(pr, OP_REBRAC_AGRAD, bind(fql_rebrac_actor_grad_kernel, (rag.B * rag.ad + FQL_THREADS - 1) / FQL_THREADS, rag),
+                     {p_q[0].dx0, p_q[1].dx0, X_q, w_act}, {p_a.dz.back()});
                 emit_backward(pr, p_a, 0, B, true, false);
             }
         }
         emit_lane = 2;
         for (int e = 0; e < 2; ++e) emit_forward(pr, p_c1[e], with_grads);   // critic(obs, actions)  rebrac.py:44
         {
-            Op op{};
-            op.type = OP_REBRAC_LOSS_C;
             const RebracCriticArgs rc{p_c1[0].out, p_c1[1].out, p_ct[0].out, p_ct[1].out, X_t, w_nact, w_rew, w_mask,
                                       with_grads ? p_c1[0].dz.back() : nullptr, with_grads ? p_c1[1].dz.back() : nullptr, st, B, od, ad, inp_c, ap,
                                       cfg.discount, rcfg.alpha_critic};
-            op.k = bind(fql_rebrac_loss_critic_kernel, 1, rc);
-            op.reads = {p_c1[0].out, p_c1[1].out, p_ct[0].out, p_ct[1].out, X_t, w_nact, w_rew, w_mask};
-            op.writes = {I_C};
+            Op& op = emit(pr, OP_REBRAC_LOSS_C, bind(fql_rebrac_loss_critic_kernel, 1, rc),
+                          {p_c1[0].out, p_c1[1].out, p_ct[0].out, p_ct[1].out, X_t, w_nact, w_rew, w_mask}, {I_C});
             if (with_grads) { op.writes.push_back(p_c1[0].dz.back()); op.writes.push_back(p_c1[1].dz.back()); }
-            push(pr, op);
         }
         if (!with_grads) return;
         for (int e = 0; e < 2; ++e) emit_backward(pr, p_c1[e], 0, B, true, false);
@@ -3205,15 +3189,8 @@ struct fql_engine {
         Op& a = pr.ops.back();
         if (full_update) for (const Layer& L : na.layers) a.writes.push_back(P + n_train + L.w);   // the target actor
         else a.adam_polyak = 0;
-        Op f{};
-        f.type = OP_REBRAC_FIN;
-        f.k = bind(fql_rebrac_finalize_kernel, 1, fin_args(1), full_update ? 1 : 0);
-        f.k.tl_at = offsetof(FinalizeArgs, tl);
-        f.reads = {I_C, I_A};
-        for (int m = 0; m < 3; ++m) f.reads.push_back(d_partials + mod_chunk0[m] * 4);
-        f.writes = {&st->info[8], st};
-        emit_lane = 0;
-        push(pr, f);
+        emit_fin(pr, OP_REBRAC_FIN, bind(fql_rebrac_finalize_kernel, 1, fin_args(1), full_update ? 1 : 0), offsetof(FinalizeArgs, tl), {I_C, I_A},
+                 true, {&st->info[8], st});
     }
 
     void build_rebrac_workspace() {
@@ -3236,10 +3213,7 @@ struct fql_engine {
         build_rebrac_program(prog_full, true, true);
         build_rebrac_program(prog_critic, false, true);
         build_rebrac_program(prog_loss, true, false);
-        for (Program* pr : {&prog_full, &prog_critic, &prog_loss}) schedule(*pr, W);
-        for (Program* pr : {&prog_full, &prog_critic, &prog_loss}) capture(*pr);
-        split_ok = false;
-        src_valid = false;
+        finish_programs({&prog_full, &prog_critic, &prog_loss});
     }
     // ---------------------------------------------------------------------------------------
     // the SAC update as a program (agents/sac.py:23-122).  No Euler chain: throughput work on the side lanes.
@@ -3259,61 +3233,39 @@ struct fql_engine {
         allow64 = true;
         emit_lane = 0;
         {
-            Op op{};
-            op.type = OP_SAC_PREP;
             const SacPrepArgs sprep{d_src, st, seed, B, od, ad, inp_a, inp_c, ap, X_c1, X_t, X_q, X_a, w_eps, w_rew, w_mask};
-            op.k = bind(fql_sac_prep_kernel, (sprep.B + 3) / 4, sprep);
-            op.writes = {X_c1, X_t, X_q, X_a, w_eps, w_rew, w_mask};
-            push(pr, op);
+            emit(pr, OP_SAC_PREP, bind(fql_sac_prep_kernel, (sprep.B + 3) / 4, sprep), {}, {X_c1, X_t, X_q, X_a, w_eps, w_rew, w_mask});
         }
         emit_lane = 1;
         emit_forward(pr, p_a, with_grads);   // actor(obs), actor(next_obs)  sac.py:26,61
-        {
-            Op op{};
-            op.type = OP_SAC_ACT;   // a, lp (obs rows) and a', lp' (next rows)  sac.py:27,62
+        {   // a, lp (obs rows) and a', lp' (next rows)  sac.py:27,62
             const SacActArgs sact{p_a.out, w_eps, X_q, X_t, lp_buf, 0, 0, 2 * B, ad, ap, ap, inp_c, od, 0, B, 1, scfg.tanh_squash, 0, 1.0f};
-            op.k = bind(fql_sac_act_kernel, (sact.n + FQL_THREADS - 1) / FQL_THREADS, sact);
-            op.reads = {p_a.out, w_eps};
-            op.writes = {X_q, X_t, lp_buf};
-            push(pr, op);
+            emit(pr, OP_SAC_ACT, bind(fql_sac_act_kernel, (sact.n + FQL_THREADS - 1) / FQL_THREADS, sact), {p_a.out, w_eps}, {X_q, X_t, lp_buf});
         }
         for (int e = 0; e < 2; ++e) emit_forward(pr, p_q[e], with_grads);   // critic(obs, a), stored params  sac.py:65
         {
-            Op op{};
-            op.type = OP_SAC_LOSS_A;
             const SacActorArgs sa{p_q[0].out, p_q[1].out, lp_buf, p_a.out, la, with_grads ? G + alpha_off : nullptr,
                                   with_grads ? p_q[0].dz.back() : nullptr, with_grads ? p_q[1].dz.back() : nullptr, st, B, ad, ap, target_entropy};
-            op.k = bind(fql_sac_loss_actor_kernel, 1, sa);
-            op.reads = {p_q[0].out, p_q[1].out, lp_buf, p_a.out, la};
-            op.writes = {I_A, I_Q};
+            Op& op = emit(pr, OP_SAC_LOSS_A, bind(fql_sac_loss_actor_kernel, 1, sa), {p_q[0].out, p_q[1].out, lp_buf, p_a.out, la}, {I_A, I_Q});
             if (with_grads) { op.writes.push_back(G + alpha_off); op.writes.push_back(p_q[0].dz.back()); op.writes.push_back(p_q[1].dz.back()); }
-            push(pr, op);
         }
         if (with_grads) {
             for (int e = 0; e < 2; ++e) emit_backward(pr, p_q[e], 0, B, false, true);   // dQ/da only: the critic's params get no gradient
-            Op op{};
-            op.type = OP_SAC_AGRAD;
             const SacActorGradArgs sag{p_q[0].dx0, p_q[1].dx0, X_q, p_a.out, w_eps, la, p_a.dz.back(), B, od, ad, inp_c, ap, scfg.tanh_squash};
-            op.k = bind(fql_sac_actor_grad_kernel, (sag.B * sag.ad + FQL_THREADS - 1) / FQL_THREADS, sag);
-            op.reads = {p_q[0].dx0, p_q[1].dx0, X_q, p_a.out, w_eps, la};
-            op.writes = {p_a.dz.back()};
-            push(pr, op);
+            emit(pr, OP_SAC_AGRAD, bind(fql_sac_actor_grad_kernel, (sag.B * sag.ad + FQL_THREADS - 1) / FQL_THREADS, sag),
+                 {p_q[0].dx0, p_q[1].dx0, X_q, p_a.out, w_eps, la}, {p_a.dz.back()});
             emit_backward(pr, p_a, 0, B, true, false);
         }
         emit_lane = 2;
         for (int e = 0; e < 2; ++e) emit_forward(pr, p_c1[e], with_grads);   // critic(obs, actions)  sac.py:46
         for (int e = 0; e < 2; ++e) emit_forward(pr, p_ct[e], false);         // target_critic(next_obs, a')  sac.py:30
         {
-            Op op{};
-            op.type = OP_SAC_LOSS_C;
             const SacCriticArgs sc{p_c1[0].out, p_c1[1].out, p_ct[0].out, p_ct[1].out, lp_buf + B, w_rew, w_mask, la,
                                    with_grads ? p_c1[0].dz.back() : nullptr, with_grads ? p_c1[1].dz.back() : nullptr, st, B,
                                    cfg.q_agg == 1 ? 1 : 0, scfg.backup_entropy ? 1 : 0, cfg.discount};
-            op.k = bind(fql_sac_loss_critic_kernel, 1, sc);
-            op.reads = {p_c1[0].out, p_c1[1].out, p_ct[0].out, p_ct[1].out, lp_buf, w_rew, w_mask, la};
-            op.writes = {I_C};
+            Op& op = emit(pr, OP_SAC_LOSS_C, bind(fql_sac_loss_critic_kernel, 1, sc),
+                          {p_c1[0].out, p_c1[1].out, p_ct[0].out, p_ct[1].out, lp_buf, w_rew, w_mask, la}, {I_C});
             if (with_grads) { op.writes.push_back(p_c1[0].dz.back()); op.writes.push_back(p_c1[1].dz.back()); }
-            push(pr, op);
         }
         if (!with_grads) return;
         for (int e = 0; e < 2; ++e) emit_backward(pr, p_c1[e], 0, B, true, false);
@@ -3322,15 +3274,7 @@ struct fql_engine {
         Op& a = pr.ops.back();
         a.reads.push_back(G + alpha_off);
         a.writes.push_back(P + alpha_off);
-        Op f{};
-        f.type = OP_SAC_FIN;
-        f.k = bind(fql_sac_finalize_kernel, 1, fin_args(1));
-        f.k.tl_at = offsetof(FinalizeArgs, tl);
-        f.reads = {I_C, I_A, I_Q};
-        for (int m = 0; m < 3; ++m) f.reads.push_back(d_partials + mod_chunk0[m] * 4);
-        f.writes = {&st->info[10], st};
-        emit_lane = 0;
-        push(pr, f);
+        emit_fin(pr, OP_SAC_FIN, bind(fql_sac_finalize_kernel, 1, fin_args(1)), offsetof(FinalizeArgs, tl), {I_C, I_A, I_Q}, true, {&st->info[10], st});
     }
 
     void build_sac_workspace() {
@@ -3351,10 +3295,7 @@ struct fql_engine {
         }
         build_sac_program(prog_full, true);
         build_sac_program(prog_loss, false);
-        for (Program* pr : {&prog_full, &prog_loss}) schedule(*pr, W);
-        for (Program* pr : {&prog_full, &prog_loss}) capture(*pr);
-        split_ok = false;
-        src_valid = false;
+        finish_programs({&prog_full, &prog_loss});
     }
     // ---------------------------------------------------------------------------------------
     // the BC update as a program (agents/bc.py:48-84): ONE lane, no cross-lane edge.  Batch assembly -> policy forward (64-column LDS
@@ -3371,33 +3312,16 @@ struct fql_engine {
         lane0_64 = true;
         emit_lane = 0;
         {
-            Op op{};
-            op.type = OP_BC_PREP;
             const BcPrepArgs bprep{d_src, st, seed, d_emb, B, od, ad, nets[NET_BC].in_p(), ap, bc_steps, X_bc, vel};
-            op.k = bind(fql_bc_prep_kernel, (bprep.B + 3) / 4, bprep);
-            op.writes = {X_bc, vel};
-            push(pr, op);
+            emit(pr, OP_BC_PREP, bind(fql_bc_prep_kernel, (bprep.B + 3) / 4, bprep), {}, {X_bc, vel});
         }
-        emit_forward(pr, p_bc, with_grads);   // policy(obs, x_t, t)  bc.py:67
-        {
-            Op op{};
-            op.type = OP_LOSS_BC;              // mean((vel - pred)^2) over B act elements  bc.py:69
-            op.lb = LossBcArgs{p_bc.out, vel, with_grads ? p_bc.dz.back() : nullptr, st, B, ad, ap, with_grads ? 1 : 0};
-            op.reads = {p_bc.out, vel};
-            op.writes = {I_L};
-            if (with_grads) op.writes.push_back(p_bc.dz.back());
-            push(pr, op);
-        }
+        emit_forward(pr, p_bc, with_grads);        // policy(obs, x_t, t)  bc.py:67
+        emit_loss_bc(pr, p_bc, I_L, with_grads);   // mean((vel - pred)^2) over B act elements  bc.py:69
         if (with_grads) {
             emit_backward(pr, p_bc, 0, B, true, false);
             adam_for(pr, 0, {NET_BC}, 0, -2);   // every chunk in one launch; critic_size = 0: no Polyak range
-            Op f{};
-            f.type = OP_BC_FIN;
-            f.k = bind(fql_bc_finalize_kernel, 1, fin_args(1));
-            f.k.tl_at = offsetof(FinalizeArgs, tl);
-            f.reads = {I_L, d_partials};
-            f.writes = {&st->info[0], &st->info[10], st};
-            push(pr, f);
+            emit_fin(pr, OP_BC_FIN, bind(fql_bc_finalize_kernel, 1, fin_args(1)), offsetof(FinalizeArgs, tl), {I_L, d_partials}, false,
+                     {&st->info[0], &st->info[10], st});
         }
         lane0_64 = false;
     }
@@ -3411,10 +3335,7 @@ struct fql_engine {
         p_bc = make_pass(W, NET_BC, B, X_bc, true, false);
         build_bc_program(prog_full, true);
         build_bc_program(prog_loss, false);
-        for (Program* pr : {&prog_full, &prog_loss}) schedule(*pr, W);
-        for (Program* pr : {&prog_full, &prog_loss}) capture(*pr);
-        split_ok = false;
-        src_valid = false;
+        finish_programs({&prog_full, &prog_loss});
     }
     // ---------------------------------------------------------------------------------------
     // the CFGRL update as a program (agents/cfgrl.py:22-68): BC's single lane with a goal block in the input rows.  Batch assembly (index,
@@ -3436,46 +3357,21 @@ struct fql_engine {
         lane0_64 = true;
         emit_lane = 0;
         {
-            Op op{};
-            op.type = OP_CFGRL_PREP;
             const CfgrlPrepArgs gp{d_src, d_gsrc, st, seed, P + emb_off, B, od, Gd, ad, nets[NET_BC].in_p(), ap, X_bc, vel, rows, draws, mask};
-            op.k = bind(fql_cfgrl_prep_kernel, (gp.B + 3) / 4, gp);
-            op.reads = {P + emb_off};
-            op.writes = {X_bc, vel, mask, rows, draws};
-            push(pr, op);
+            emit(pr, OP_CFGRL_PREP, bind(fql_cfgrl_prep_kernel, (gp.B + 3) / 4, gp), {P + emb_off}, {X_bc, vel, mask, rows, draws});
         }
-        emit_forward(pr, p_bc, with_grads);   // actor_flow(obs, x_t, t, goals)  cfgrl.py:37
-        {
-            Op op{};
-            op.type = OP_LOSS_BC;              // mean((pred - vel)^2) over B act elements  cfgrl.py:38
-            op.lb = LossBcArgs{p_bc.out, vel, with_grads ? p_bc.dz.back() : nullptr, st, B, ad, ap, with_grads ? 1 : 0};
-            op.reads = {p_bc.out, vel};
-            op.writes = {I_L};
-            if (with_grads) op.writes.push_back(p_bc.dz.back());
-            push(pr, op);
-        }
+        emit_forward(pr, p_bc, with_grads);        // actor_flow(obs, x_t, t, goals)  cfgrl.py:37
+        emit_loss_bc(pr, p_bc, I_L, with_grads);   // mean((pred - vel)^2) over B act elements  cfgrl.py:38
         if (with_grads) {
             emit_backward(pr, p_bc, 0, B, true, false);
-            {
-                Op op{};
-                op.type = OP_CFGRL_EGRAD;
-                const CfgrlEmbedGradArgs eg{p_bc.dz[0], P + l0.w + (size_t)od * l0.out_p, mask, G + emb_off, B, l0.out_p, Gd};
-                op.k = bind(fql_cfgrl_embed_grad_kernel, 1, eg);
-                op.reads = {p_bc.dz[0], P + l0.w, mask};
-                op.writes = {G + emb_off};
-                push(pr, op);
-            }
+            const CfgrlEmbedGradArgs eg{p_bc.dz[0], P + l0.w + (size_t)od * l0.out_p, mask, G + emb_off, B, l0.out_p, Gd};
+            emit(pr, OP_CFGRL_EGRAD, bind(fql_cfgrl_embed_grad_kernel, 1, eg), {p_bc.dz[0], P + l0.w, mask}, {G + emb_off});
             adam_for(pr, 0, {NET_BC}, 0, -2);   // every chunk in one launch; critic_size = 0: no Polyak range
             Op& a = pr.ops.back();
             a.reads.push_back(G + emb_off);
             a.writes.push_back(P + emb_off);
-            Op f{};
-            f.type = OP_CFGRL_FIN;
-            f.k = bind(fql_cfgrl_finalize_kernel, 1, fin_args(1));
-            f.k.tl_at = offsetof(FinalizeArgs, tl);
-            f.reads = {I_L, d_partials};
-            f.writes = {&st->info[0], &st->info[10], st};
-            push(pr, f);
+            emit_fin(pr, OP_CFGRL_FIN, bind(fql_cfgrl_finalize_kernel, 1, fin_args(1)), offsetof(FinalizeArgs, tl), {I_L, d_partials}, false,
+                     {&st->info[0], &st->info[10], st});
         }
         lane0_64 = false;
     }
@@ -3494,11 +3390,7 @@ struct fql_engine {
         p_bc = make_pass(W, NET_BC, B, X_bc, true, false);
         build_cfgrl_program(prog_full, true);
         build_cfgrl_program(prog_loss, false);
-        for (Program* pr : {&prog_full, &prog_loss}) schedule(*pr, W);
-        for (Program* pr : {&prog_full, &prog_loss}) capture(*pr);
-        split_ok = false;
-        src_valid = false;
-        gsrc_valid = false;
+        finish_programs({&prog_full, &prog_loss});
     }
 
     // multiply-accumulates of one BC update per batch row, algorithmic: forward + backward without the input gradient
@@ -3550,94 +3442,62 @@ struct fql_engine {
         allow64 = true;
         emit_lane = 0;
         {
-            Op op{};
-            op.type = OP_IQL_PREP;
             const IqlPrepArgs qprep{d_src, st, seed, B, od, ad, inp_v, inp_c, inp_a, ap, X_v, X_c1, X_a, X_q, w_act, eps, w_rew, w_mask};
-            op.k = bind(fql_iql_prep_kernel, (qprep.B + 3) / 4, qprep);
-            op.writes = {X_v, X_c1, X_a, w_act, w_rew, w_mask};
+            Op& op = emit(pr, OP_IQL_PREP, bind(fql_iql_prep_kernel, (qprep.B + 3) / 4, qprep), {}, {X_v, X_c1, X_a, w_act, w_rew, w_mask});
             if (X_q) op.writes.push_back(X_q);
             if (eps) op.writes.push_back(eps);
-            push(pr, op);
         }
         emit_lane = 1;
         emit_forward(pr, p_v, with_grads);                              // value(obs) iql.py:32, value(next_obs) iql.py:44
         for (int e = 0; e < 2; ++e) emit_forward(pr, p_ct[e], false);   // target_critic(obs, actions) iql.py:30
         {
-            Op op{};
-            op.type = OP_IFQL_LOSS_V;
             const IfqlValueArgs iv{p_v.out, p_ct[0].out, p_ct[1].out, with_grads ? p_v.dz.back() : nullptr, st, B, qcfg.expectile};
-            op.k = bind(fql_ifql_loss_value_kernel, 1, iv);
-            op.reads = {p_v.out, p_ct[0].out, p_ct[1].out};
-            op.writes = {I_V};
+            Op& op = emit(pr, OP_IFQL_LOSS_V, bind(fql_ifql_loss_value_kernel, 1, iv), {p_v.out, p_ct[0].out, p_ct[1].out}, {I_V});
             if (with_grads) op.writes.push_back(p_v.dz.back());
-            push(pr, op);
         }
         if (with_grads) emit_backward(pr, p_v, 0, B, true, false);
         emit_forward(pr, p_a, with_grads);                              // actor(obs) iql.py:69,85
-        {
-            Op op{};
-            op.type = OP_IQL_HEAD;                                      // log_prob(actions) iql.py:70,95; q_actions iql.py:86-89
+        {   // log_prob(actions) iql.py:70,95; q_actions iql.py:86-89
             const IqlHeadArgs qhead{p_a.out, ls, w_act, eps, lp_buf, se_buf, ddpg ? X_q : nullptr, B, od, ad, ap, inp_c};
-            op.k = bind(fql_iql_head_kernel, (qhead.B + FQL_THREADS - 1) / FQL_THREADS, qhead);
-            op.reads = {p_a.out, w_act};
+            Op& op = emit(pr, OP_IQL_HEAD, bind(fql_iql_head_kernel, (qhead.B + FQL_THREADS - 1) / FQL_THREADS, qhead), {p_a.out, w_act},
+                          {lp_buf, se_buf});
             if (ls) op.reads.push_back(ls);
             if (eps) op.reads.push_back(eps);
-            op.writes = {lp_buf, se_buf};
             if (ddpg) op.writes.push_back(X_q);
-            push(pr, op);
         }
         if (ddpg) {
             for (int e = 0; e < 2; ++e) emit_forward(pr, p_q[e], with_grads);   // critic(obs, q_actions), stored params  iql.py:90
-            Op op{};
-            op.type = OP_IQL_LOSS_DDPGBC;
             const IqlDdpgArgs qddpg{p_q[0].out, p_q[1].out, lp_buf, se_buf, ls, with_grads ? p_q[0].dz.back() : nullptr,
                                     with_grads ? p_q[1].dz.back() : nullptr, out, B, ad, qcfg.alpha};
-            op.k = bind(fql_iql_loss_ddpgbc_kernel, 1, qddpg);
-            op.reads = {p_q[0].out, p_q[1].out, lp_buf, se_buf};
+            Op& op = emit(pr, OP_IQL_LOSS_DDPGBC, bind(fql_iql_loss_ddpgbc_kernel, 1, qddpg), {p_q[0].out, p_q[1].out, lp_buf, se_buf}, {I_A});
             if (ls) op.reads.push_back(ls);
-            op.writes = {I_A};
             if (with_grads) { op.writes.push_back(p_q[0].dz.back()); op.writes.push_back(p_q[1].dz.back()); }
-            push(pr, op);
         }
         emit_lane = 2;
         for (int e = 0; e < 2; ++e) emit_forward(pr, p_c1[e], with_grads);   // critic(obs, actions) iql.py:47 (and :62: the same numbers)
         {
-            Op op{};
-            op.type = OP_IFQL_LOSS_C;
             const IfqlCriticArgs ic{p_v.out + (size_t)B * nets[NET_OS].layers.back().out_p, p_c1[0].out, p_c1[1].out, w_rew, w_mask,
                                     with_grads ? p_c1[0].dz.back() : nullptr, with_grads ? p_c1[1].dz.back() : nullptr, st, B, cfg.discount};
-            op.k = bind(fql_ifql_loss_critic_kernel, 1, ic);
-            op.reads = {p_v.out, p_c1[0].out, p_c1[1].out, w_rew, w_mask};
-            op.writes = {I_C};
+            Op& op = emit(pr, OP_IFQL_LOSS_C, bind(fql_ifql_loss_critic_kernel, 1, ic), {p_v.out, p_c1[0].out, p_c1[1].out, w_rew, w_mask}, {I_C});
             if (with_grads) { op.writes.push_back(p_c1[0].dz.back()); op.writes.push_back(p_c1[1].dz.back()); }
-            push(pr, op);
         }
         if (with_grads)
             for (int e = 0; e < 2; ++e) emit_backward(pr, p_c1[e], 0, B, true, false);
         if (!ddpg) {
-            Op op{};
-            op.type = OP_IQL_LOSS_AWR;
             const IqlAwrArgs qawr{p_c1[0].out, p_c1[1].out, p_v.out, lp_buf, se_buf, p_a.out, w_act, ls, with_grads ? p_a.dz.back() : nullptr,
                                   ls_part, g_ls, out, B, ad, ap, qcfg.alpha};
-            op.k = bind(fql_iql_loss_awr_kernel, 1, qawr);
-            op.reads = {p_c1[0].out, p_c1[1].out, p_v.out, lp_buf, se_buf, p_a.out, w_act};
+            Op& op = emit(pr, OP_IQL_LOSS_AWR, bind(fql_iql_loss_awr_kernel, 1, qawr),
+                          {p_c1[0].out, p_c1[1].out, p_v.out, lp_buf, se_buf, p_a.out, w_act}, {I_A});
             if (ls) op.reads.push_back(ls);
-            op.writes = {I_A};
             if (with_grads) op.writes.push_back(p_a.dz.back());
             if (g_ls) { op.writes.push_back(ls_part); op.writes.push_back(g_ls); }
-            push(pr, op);
         } else if (with_grads) {
             for (int e = 0; e < 2; ++e) emit_backward(pr, p_q[e], 0, B, false, true);   // dQ/da only: the critic's params get no gradient here
-            Op op{};
-            op.type = OP_IQL_AGRAD;
             const IqlActorGradArgs qag{p_q[0].dx0, p_q[1].dx0, p_a.out, w_act, eps, ls, p_a.dz.back(), ls_part, g_ls, B, od, ad, ap, inp_c, qcfg.alpha};
-            op.k = bind(fql_iql_actor_grad_kernel, 1, qag);
-            op.reads = {p_q[0].dx0, p_q[1].dx0, p_a.out, w_act};
+            Op& op = emit(pr, OP_IQL_AGRAD, bind(fql_iql_actor_grad_kernel, 1, qag), {p_q[0].dx0, p_q[1].dx0, p_a.out, w_act}, {p_a.dz.back()});
             if (ls) op.reads.push_back(ls);
             if (eps) op.reads.push_back(eps);
-            op.writes = {p_a.dz.back()};
             if (g_ls) { op.writes.push_back(ls_part); op.writes.push_back(g_ls); }
-            push(pr, op);
         }
         if (with_grads) {
             emit_backward(pr, p_a, 0, B, true, false);
@@ -3648,15 +3508,8 @@ struct fql_engine {
                 a.writes.push_back(P + ls_off);
             }
         }
-        Op f{};
-        f.type = OP_IQL_FIN;
-        f.k = bind(fql_iql_finalize_kernel, 1, IqlFinalizeArgs{fin_args(with_grads ? 1 : 0), out, ddpg ? IQL_N_DDPGBC : IQL_N_AWR});
-        f.k.tl_at = offsetof(IqlFinalizeArgs, fin.tl);
-        f.reads = {I_V, I_C, I_A};
-        if (with_grads) for (int m = 0; m < 3; ++m) f.reads.push_back(d_partials + mod_chunk0[m] * 4);
-        f.writes = {out, st};
-        emit_lane = 0;
-        push(pr, f);
+        emit_fin(pr, OP_IQL_FIN, bind(fql_iql_finalize_kernel, 1, IqlFinalizeArgs{fin_args(with_grads ? 1 : 0), out, ddpg ? IQL_N_DDPGBC : IQL_N_AWR}),
+                 offsetof(IqlFinalizeArgs, fin.tl), {I_V, I_C, I_A}, with_grads, {out, st});
     }
 
     void build_iql_workspace() {
@@ -3682,10 +3535,7 @@ struct fql_engine {
         }
         build_iql_program(prog_full, true);
         build_iql_program(prog_loss, false);
-        for (Program* pr : {&prog_full, &prog_loss}) schedule(*pr, W);
-        for (Program* pr : {&prog_full, &prog_loss}) capture(*pr);
-        split_ok = false;
-        src_valid = false;
+        finish_programs({&prog_full, &prog_loss});
     }
     // multiply-accumulates of one IQL update per batch row, algorithmic (full GEMM shapes at the logical widths)
     int64_t iql_macs() const {
@@ -3734,76 +3584,45 @@ struct fql_engine {
         allow64 = true;
         emit_lane = 0;
         if (do_c || do_a) {
-            Op op{};
-            op.type = OP_IQLD_PREP;
             const IqldPrepArgs dprep{d_src, st, seed, d_emb, P + emb_off, B, od, ad, nets[NET_OS].in_p(), nets[NET_C0].in_p(), na.in_p(), ap,
                                      bc_steps, X_v, X_c1, X_bc, vel, w_rew, w_mask};
-            op.k = bind(fql_iqld_prep_kernel, (dprep.B + 3) / 4, dprep);
-            op.reads = {P + emb_off};
-            op.writes = {X_v, X_c1, X_bc, vel, w_rew, w_mask};
-            push(pr, op);
+            emit(pr, OP_IQLD_PREP, bind(fql_iqld_prep_kernel, (dprep.B + 3) / 4, dprep), {P + emb_off}, {X_v, X_c1, X_bc, vel, w_rew, w_mask});
             emit_lane = 1;
             emit_forward(pr, p_v, gc);                                              // value(obs) :109,131; value(next_obs) :96
             if (do_c || te) for (int e = 0; e < 2; ++e) emit_forward(pr, p_ct[e], false);   // target_critic(obs, actions) :107,133
         }
         if (do_c) {
-            Op op{};
-            op.type = OP_IFQL_LOSS_V;
             const IfqlValueArgs iv{p_v.out, p_ct[0].out, p_ct[1].out, gc ? p_v.dz.back() : nullptr, st, B, dcfg.expectile};
-            op.k = bind(fql_ifql_loss_value_kernel, 1, iv);
-            op.reads = {p_v.out, p_ct[0].out, p_ct[1].out};
-            op.writes = {I_V};
+            Op& op = emit(pr, OP_IFQL_LOSS_V, bind(fql_ifql_loss_value_kernel, 1, iv), {p_v.out, p_ct[0].out, p_ct[1].out}, {I_V});
             if (gc) op.writes.push_back(p_v.dz.back());
-            push(pr, op);
             if (gc) emit_backward(pr, p_v, 0, B, true, false);
         }
         emit_lane = 2;
         if (do_c || (do_a && !te)) for (int e = 0; e < 2; ++e) emit_forward(pr, p_c1[e], gc);   // critic(obs, actions) :98,135
         if (do_c) {
-            Op op{};
-            op.type = OP_IQLD_LOSS_C;
             const IqldCriticArgs dc{p_v.out + (size_t)B * nets[NET_OS].layers.back().out_p, p_c1[0].out, p_c1[1].out, w_rew, w_mask,
                                     gc ? p_c1[0].dz.back() : nullptr, gc ? p_c1[1].dz.back() : nullptr, out, B, cfg.discount};
-            op.k = bind(fql_iqld_loss_critic_kernel, 1, dc);
-            op.reads = {p_v.out, p_c1[0].out, p_c1[1].out, w_rew, w_mask};
-            op.writes = {I_C};
+            Op& op = emit(pr, OP_IQLD_LOSS_C, bind(fql_iqld_loss_critic_kernel, 1, dc), {p_v.out, p_c1[0].out, p_c1[1].out, w_rew, w_mask}, {I_C});
             if (gc) { op.writes.push_back(p_c1[0].dz.back()); op.writes.push_back(p_c1[1].dz.back()); }
-            push(pr, op);
             if (gc) for (int e = 0; e < 2; ++e) emit_backward(pr, p_c1[e], 0, B, true, false);
         }
         if (do_a) {
             const PassBuf* pq = te ? p_ct : p_c1;
-            {
-                Op op{};
-                op.type = OP_IQLD_WEIGHT;
-                const IqldWeightArgs dw{pq[0].out, pq[1].out, p_v.out, w_lw, rows, out, B, dcfg.optimal_var, (int)(0.1 * (double)B),
-                                        dcfg.optimal_var == IQLD_BINARY_SOFTMAX ? dcfg.softmax_beta : dcfg.awr_temperature};
-                op.k = bind(fql_iqld_weight_kernel, 1, dw);
-                op.reads = {pq[0].out, pq[1].out, p_v.out};
-                op.writes = {w_lw, rows + (size_t)B, I_W};
-                push(pr, op);
-            }
+            const IqldWeightArgs dw{pq[0].out, pq[1].out, p_v.out, w_lw, rows, out, B, dcfg.optimal_var, (int)(0.1 * (double)B),
+                                    dcfg.optimal_var == IQLD_BINARY_SOFTMAX ? dcfg.softmax_beta : dcfg.awr_temperature};
+            emit(pr, OP_IQLD_WEIGHT, bind(fql_iqld_weight_kernel, 1, dw), {pq[0].out, pq[1].out, p_v.out}, {w_lw, rows + (size_t)B, I_W});
             emit_forward(pr, p_bc, ga);                                             // actor(obs, 1, x_t, t) :181 and actor(obs, 0, x_t, t) :186
             {
-                Op op{};
-                op.type = OP_IQLD_LOSS_A;
                 const IqldActorLossArgs dla{p_bc.out, vel, w_lw, ga ? p_bc.dz.back() : nullptr, rows, out, B, ad, ap};
-                op.k = bind(fql_iqld_loss_actor_kernel, 1, dla);
-                op.reads = {p_bc.out, vel, w_lw, I_W};   // (I_W: the two kernels write disjoint slots of one info block, in this order)
-                op.writes = {rows, I_A};
+                // (I_W: the two kernels write disjoint slots of one info block, in this order)
+                Op& op = emit(pr, OP_IQLD_LOSS_A, bind(fql_iqld_loss_actor_kernel, 1, dla), {p_bc.out, vel, w_lw, I_W}, {rows, I_A});
                 if (ga) op.writes.push_back(p_bc.dz.back());
-                push(pr, op);
             }
             if (ga) {
                 emit_backward(pr, p_bc, 0, 2 * B, true, false);
                 const Layer& l0 = na.layers[0];
-                Op op{};
-                op.type = OP_IQLD_EGRAD;
                 const IqldEmbedGradArgs deg{p_bc.dz[0], P + l0.w + (size_t)(od + ad + BC_EMB) * l0.out_p, G + emb_off, B, l0.out_p};
-                op.k = bind(fql_iqld_embed_grad_kernel, 2, deg);
-                op.reads = {p_bc.dz[0], P + l0.w};
-                op.writes = {G + emb_off};
-                push(pr, op);
+                emit(pr, OP_IQLD_EGRAD, bind(fql_iqld_embed_grad_kernel, 2, deg), {p_bc.dz[0], P + l0.w}, {G + emb_off});
             }
         }
         if (gc) {
@@ -3823,16 +3642,9 @@ struct fql_engine {
         }
         int a_lo, a_hi, v_lo, v_hi;
         iqld_leaf_ranges(a_lo, a_hi, v_lo, v_hi);
-        Op f{};
-        f.type = OP_IQLD_FIN;
         const IqldFinalizeArgs dfin{st, d_state_a, d_partials, d_leaf_range, out, ga ? a_lo : (gc ? v_lo : 0), ga ? a_hi : (gc ? v_hi : 0),
                                     do_c ? 1 : 0, do_a ? 1 : 0, gc ? 1 : 0, ga ? 1 : 0, with_grads ? 1 : 0};
-        f.k = bind(fql_iqld_finalize_kernel, 1, dfin);
-        f.reads = {I_V, I_C, I_W, I_A};
-        if (with_grads) for (int m = 0; m < 3; ++m) f.reads.push_back(d_partials + mod_chunk0[m] * 4);
-        f.writes = {out, st, d_state_a};
-        emit_lane = 0;
-        push(pr, f);
+        emit_fin(pr, OP_IQLD_FIN, bind(fql_iqld_finalize_kernel, 1, dfin), -1, {I_V, I_C, I_W, I_A}, with_grads, {out, st, d_state_a});
     }
 
     void build_iqld_workspace() {
@@ -3857,10 +3669,7 @@ struct fql_engine {
         build_iqld_program(prog_actor, false, true, true);
         build_iqld_program(prog_none, false, false, true);
         build_iqld_program(prog_loss, false, false, false);
-        for (Program* pr : {&prog_full, &prog_critic, &prog_actor, &prog_none, &prog_loss}) schedule(*pr, W);
-        for (Program* pr : {&prog_full, &prog_critic, &prog_actor, &prog_none, &prog_loss}) capture(*pr);
-        split_ok = false;
-        src_valid = false;
+        finish_programs({&prog_full, &prog_critic, &prog_actor, &prog_none, &prog_loss});
     }
     Program& iqld_program(bool upd_critic, bool upd_actor) {
         return upd_critic ? (upd_actor ? prog_full : prog_critic) : (upd_actor ? prog_actor : prog_none);
@@ -4312,336 +4121,195 @@ struct fql_engine {
     // ---------------------------------------------------------------------------------------
     // eval paths
     // ---------------------------------------------------------------------------------------
-    Eval& get_eval(int n_pad) {
-        auto it = evals.find(n_pad);
-        if (it != evals.end()) return *it->second;
-        auto ev = std::make_unique<Eval>();
-        ev->n_pad = n_pad;
-        auto& W = ev->allocs;
-        const int od = cfg.obs_dim, ad = cfg.act_dim;
-        if (kind == AgentKind::BC) {   // sample_actions (prog_flow): the step-bias table and the loop-invariant C0 = obs W0 + b0 at the head of the program, then per
-                    // Euler step layer 0 as a rank-act update of C0 plus the step's row, and layers 1.. of the 16-row Dense kernel, whose head
-                    // epilogue adds v / S to the actions in place and on the last step writes the clipped actions (GF_EULER | GF_EULER_BARE)
-            const int S = bc_steps, ap = pad16(ad);
-            const Net& n = nets[NET_BC];
-            const Layer& l0 = n.layers[0];
-            const int H = l0.out_p;
-            ev->X = dalloc(W, (size_t)n_pad * n.in_p());     // [obs | 0]
-            ev->Xf = dalloc(W, (size_t)n_pad * ap);          // the flow's state x
-            ev->Xq = dalloc(W, (size_t)S * H);               // step-bias table c_i
-            float* C0e = dalloc(W, (size_t)n_pad * H);
-            ev->tgt = dalloc(W, (size_t)n_pad * ap);
-            ev->st_obs = dalloc(W, (size_t)n_pad * od);
-            ev->st_noise = dalloc(W, (size_t)n_pad * ad);
-            ev->st_out = dalloc(W, (size_t)n_pad * ad);
-            ev->p_eu = make_pass(W, NET_BC, n_pad, ev->X, false, false);
-            emit_lane = 0;
-            Program& pr = ev->prog_flow;
-            {
-                Op op{};
-                op.type = OP_BC_STEPBIAS;
-                const BcStepBiasArgs bsb{d_emb, P + l0.w + (size_t)(od + ad) * H, ev->Xq, S, H};
-                op.k = bind(fql_bc_stepbias_kernel, (bsb.S * bsb.H + FQL_THREADS - 1) / FQL_THREADS, bsb);
-                op.reads = {d_emb, P + l0.w};
-                op.writes = {ev->Xq};
-                push(pr, op);
-            }
-            {
-                Op op{};
-                op.type = OP_GEMM;
-                GemmTask& t = op.gemm;
-                t.A = ev->X; t.lda = l0.in_p; t.B = P + l0.w; t.ldb = H; t.bias = P + l0.b; t.C = C0e; t.ldc = H;
-                t.M = n_pad; t.N = H; t.K = l0.in_p; t.flags = GF_BIAS;
-                op.reads = {ev->X, t.B};
-                op.writes = {C0e};
-                push(pr, op);
-            }
-            for (int i = 0; i < S; ++i) {
-                Op op{};
-                op.type = OP_BC_LAYER0;
-                const BcLayer0Args bl0{C0e, ev->Xf, P + l0.w + (size_t)od * H, ev->Xq + (size_t)i * H, ev->p_eu.g[0], n_pad, H, ad, ap};
-                op.k = bind(fql_bc_layer0_kernel, (bl0.M * bl0.H + FQL_THREADS - 1) / FQL_THREADS, bl0);
-                op.reads = {C0e, ev->Xf, ev->Xq, P + l0.w};
-                op.writes = {ev->p_eu.g[0]};
-                push(pr, op);
-                emit_forward(pr, ev->p_eu, false, GF_EULER | (i == S - 1 ? GF_EULER_LAST : 0), ev->Xf, ev->tgt, 1.0f / (float)S, 0.f, 1);
-                GemmTask& hd = pr.ops.back().gemm;   // the actions alone: ld ap, no observation block in front, no time block behind
-                hd.flags |= GF_EULER_BARE;
-                hd.i0 = ap; hd.i1 = 0;
-            }
-            schedule(pr, W);
-            Eval& ref = *ev;
-            evals[n_pad] = std::move(ev);
-            return ref;
-        }
-        if (kind == AgentKind::IQLD) {   // sample_actions with classifier-free guidance (prog_flow): BC's hoisted form over two halves.  n_pad counts
-                    // both: rows [0, half) are the positive pass, [half, n_pad) the unconditional one, half = n_pad / 2 a multiple of 16.  The
-                    // step-bias table [S, 2, H] and the shared C0 = obs W0 + b0 at the head of the program, then per Euler step layer 0 of both
-                    // halves (one launch), layers 1.. of the 16-row Dense kernel over n_pad rows, and the CFG combine + Euler add (one launch
-                    // behind the head GEMM; the last one writes the clipped actions)
-            const int S = bc_steps, ap = pad16(ad), half = n_pad / 2;
-            const Net& n = nets[NET_BC];
-            const Layer& l0 = n.layers[0];
-            const int H = l0.out_p;
-            ev->X = dalloc(W, (size_t)half * n.in_p());      // [obs | 0]
-            ev->Xf = dalloc(W, (size_t)half * ap);           // the flow's state x
-            ev->Xq = dalloc(W, (size_t)S * 2 * H);           // step-bias table c[i][half]
-            float* C0e = dalloc(W, (size_t)half * H);
-            ev->tgt = dalloc(W, (size_t)half * ap);
-            ev->st_obs = dalloc(W, (size_t)half * od);
-            ev->st_noise = dalloc(W, (size_t)half * ad);
-            ev->st_out = dalloc(W, (size_t)half * ad);
-            ev->p_eu = make_pass(W, NET_BC, n_pad, ev->X, false, false);
-            emit_lane = 0;
-            Program& pr = ev->prog_flow;
-            {
-                Op op{};
-                op.type = OP_IQLD_STEPBIAS;
-                const IqldStepBiasArgs dsb{d_emb, P + emb_off, P + l0.w + (size_t)(od + ad) * H, ev->Xq, S, H};
-                op.k = bind(fql_iqld_stepbias_kernel, (dsb.S * 2 * dsb.H + FQL_THREADS - 1) / FQL_THREADS, dsb);
-                op.reads = {d_emb, P + emb_off, P + l0.w};
-                op.writes = {ev->Xq};
-                push(pr, op);
-            }
-            {
-                Op op{};
-                op.type = OP_GEMM;
-                GemmTask& t = op.gemm;
-                t.A = ev->X; t.lda = l0.in_p; t.B = P + l0.w; t.ldb = H; t.bias = P + l0.b; t.C = C0e; t.ldc = H;
-                t.M = half; t.N = H; t.K = l0.in_p; t.flags = GF_BIAS;
-                op.reads = {ev->X, t.B};
-                op.writes = {C0e};
-                push(pr, op);
-            }
-            for (int i = 0; i < S; ++i) {
-                Op op{};
-                op.type = OP_IQLD_LAYER0;
-                const IqldLayer0Args dl0{C0e, ev->Xf, P + l0.w + (size_t)od * H, ev->Xq + (size_t)i * 2 * H, ev->p_eu.g[0], half, H, ad, ap};
-                op.k = bind(fql_iqld_layer0_kernel, (2 * dl0.n_pad * dl0.H + FQL_THREADS - 1) / FQL_THREADS, dl0);
-                op.reads = {C0e, ev->Xf, ev->Xq, P + l0.w};
-                op.writes = {ev->p_eu.g[0]};
-                push(pr, op);
-                emit_forward(pr, ev->p_eu, false, 0, nullptr, nullptr, 0.f, 0.f, 1);
-                Op st{};
-                st.type = OP_IQLD_CFG;
-                const IqldCfgStepArgs dstep{ev->p_eu.out, ev->Xf, i == S - 1 ? ev->tgt : nullptr, half, ad, ap, 1.0f, 1.0f / (float)S};
-                st.k = bind(fql_iqld_cfg_step_kernel, (dstep.n_pad * dstep.ad + FQL_THREADS - 1) / FQL_THREADS, dstep);
-                st.reads = {ev->p_eu.out};
-                st.writes = {ev->Xf};
-                if (i == S - 1) st.writes.push_back(ev->tgt);
-                push(pr, st);
-            }
-            schedule(pr, W);
-            Eval& ref = *ev;
-            evals[n_pad] = std::move(ev);
-            return ref;
-        }
-        if (kind == AgentKind::CFGRL) {   // sample_actions with classifier-free guidance (prog_flow): IQL-diffusion's two halves, rows [0, half) the
-                    // conditional pass and [half, n_pad) the unconditional one.  C0 = [obs | goal or unc_embed] W0 + b0 of both halves at the head of
-                    // the program, then per Euler step layer 0 of both halves (one launch; t is one row of W0), layers 1.. of the 16-row Dense
-                    // kernel over n_pad rows, and fql_iqld_cfg_step_kernel (CFG combine + Euler add; the last one writes the clipped actions)
-            const int S = gcfg.flow_steps, ap = pad16(ad), half = n_pad / 2, Gd = gcfg.goal_dim;
-            const Net& n = nets[NET_BC];
-            const Layer& l0 = n.layers[0];
-            const int H = l0.out_p;
-            ev->X = dalloc(W, (size_t)n_pad * n.in_p());     // [obs | goal | 0] ; [obs | unc_embed | 0]
-            ev->Xf = dalloc(W, (size_t)half * ap);           // the flow's state x
-            float* C0e = dalloc(W, (size_t)n_pad * H);
-            ev->tgt = dalloc(W, (size_t)half * ap);
-            ev->st_obs = dalloc(W, (size_t)half * od);
-            ev->st_goal = dalloc(W, (size_t)half * Gd);
-            ev->st_noise = dalloc(W, (size_t)half * ad);
-            ev->st_out = dalloc(W, (size_t)half * ad);
-            ev->p_eu = make_pass(W, NET_BC, n_pad, ev->X, false, false);
-            emit_lane = 0;
-            Program& pr = ev->prog_flow;
-            {
-                Op op{};
-                op.type = OP_GEMM;
-                GemmTask& t = op.gemm;
-                t.A = ev->X; t.lda = l0.in_p; t.B = P + l0.w; t.ldb = H; t.bias = P + l0.b; t.C = C0e; t.ldc = H;
-                t.M = n_pad; t.N = H; t.K = l0.in_p; t.flags = GF_BIAS;
-                op.reads = {ev->X, t.B};
-                op.writes = {C0e};
-                push(pr, op);
-            }
-            for (int i = 0; i < S; ++i) {
-                Op op{};
-                op.type = OP_CFGRL_LAYER0;
-                const CfgrlLayer0Args gl0{C0e, ev->Xf, P + l0.w + (size_t)(od + Gd) * H, ev->p_eu.g[0], half, H, ad, ap,
-                                          (float)((double)i / (double)S)};   // cfgrl.py:90: a Python float, cast to fp32
-                op.k = bind(fql_cfgrl_layer0_kernel, (2 * gl0.n_pad * gl0.H + FQL_THREADS - 1) / FQL_THREADS, gl0);
-                op.reads = {C0e, ev->Xf, P + l0.w};
-                op.writes = {ev->p_eu.g[0]};
-                push(pr, op);
-                emit_forward(pr, ev->p_eu, false, 0, nullptr, nullptr, 0.f, 0.f, 1);
-                Op st{};
-                st.type = OP_IQLD_CFG;   // (issue() writes the call's cfg into this launch)
-                const IqldCfgStepArgs dstep{ev->p_eu.out, ev->Xf, i == S - 1 ? ev->tgt : nullptr, half, ad, ap, 1.0f, 1.0f / (float)S};
-                st.k = bind(fql_iqld_cfg_step_kernel, (dstep.n_pad * dstep.ad + FQL_THREADS - 1) / FQL_THREADS, dstep);
-                st.reads = {ev->p_eu.out};
-                st.writes = {ev->Xf};
-                if (i == S - 1) st.writes.push_back(ev->tgt);
-                push(pr, st);
-            }
-            schedule(pr, W);
-            Eval& ref = *ev;
-            evals[n_pad] = std::move(ev);
-            return ref;
-        }
-        if (actor_on_obs()) {   // sample_actions: the actor's forward over the rows (prog_os on p_os; NET_OS is empty here)
-            ev->X = dalloc(W, (size_t)n_pad * nets[NET_BC].in_p());
-            ev->st_obs = dalloc(W, (size_t)n_pad * od);
-            ev->st_noise = dalloc(W, (size_t)n_pad * ad);
-            ev->st_out = dalloc(W, (size_t)n_pad * ad);
-            ev->p_os = make_pass(W, NET_BC, n_pad, ev->X, false, false);
-            emit_lane = 0;
-            emit_forward(ev->prog_os, ev->p_os, false);
-            schedule(ev->prog_os, W);
-            Eval& ref = *ev;
-            evals[n_pad] = std::move(ev);
-            return ref;
-        }
-        ev->X = dalloc(W, (size_t)n_pad * nets[NET_OS].in_p());
-        ev->Xf = dalloc(W, (size_t)n_pad * nets[NET_BC].in_p());
-        ev->tgt = dalloc(W, (size_t)n_pad * pad16(ad));
-        ev->st_obs = dalloc(W, (size_t)n_pad * od);
-        ev->st_noise = dalloc(W, (size_t)n_pad * ad);
-        ev->st_out = dalloc(W, (size_t)n_pad * ad);
-        ev->p_os = make_pass(W, NET_OS, n_pad, ev->X, false, false);
-        ev->p_eu = make_pass(W, NET_BC, n_pad, ev->Xf, false, false);
-        emit_lane = 0;
-        emit_forward(ev->prog_os, ev->p_os, false, GF_CLIP_OUT);
-        const int fs = cfg.flow_steps;
-        for (int s = 0; s < fs; ++s)
-            emit_forward(ev->prog_flow, ev->p_eu, false, GF_EULER | (s == fs - 1 ? GF_EULER_LAST : 0), ev->Xf, ev->tgt,
-                         1.0f / (float)fs, (float)(s + 1) / (float)fs);
-        schedule(ev->prog_os, W);
-        schedule(ev->prog_flow, W);
-        if (kind == AgentKind::IFQL) {   // best-of-N scoring: the critic pair on every sample row
-            ev->Xq = dalloc(W, (size_t)n_pad * nets[NET_C0].in_p());
-            for (int e = 0; e < 2; ++e) {
-                ev->p_q[e] = make_pass(W, NET_C0 + e, n_pad, ev->Xq, false, false);
-                emit_forward(ev->prog_q, ev->p_q[e], false);
-            }
-            schedule(ev->prog_q, W);
-        }
-        if (visual) {
-            const size_t ib = (size_t)cfg.img_h * cfg.img_w * cfg.img_c;
-            ev->st_img = (unsigned char*)dalloc(W, ((size_t)n_pad * ib + 3) / 4 + 4);
-            ev->eb_os = make_enc_buf(W, ENC_OS, n_pad, ev->st_img, false);
-            ev->eb_bc = make_enc_buf(W, ENC_BC, n_pad, ev->st_img, false);
-            emit_lane = 1;   // throughput kernels (the encoder's Dense has K = flat > 1024)
-            emit_encoder_forward(ev->prog_enc_os, ev->eb_os);
-            emit_encoder_forward(ev->prog_enc_bc, ev->eb_bc);
-            emit_lane = 0;
-            schedule(ev->prog_enc_os, W);
-            schedule(ev->prog_enc_bc, W);
-        }
-        Eval& ref = *ev;
-        evals[n_pad] = std::move(ev);
-        return ref;
+    // What differs between the hoisted flow samplers (DESIGN.md sections 16 and 18-20): BC's, and the two CFG kinds' with a scalar cfg
+    // or, as a sweep, with one guidance weight per row.
+    struct FlowShape {
+        int halves;      // 1: BC, one block of n_pad rows.  2: the CFG kinds, rows [0, half) the positive / conditional pass, [half, n_pad) the unconditional one
+        bool shared_x;   // the halves share X = [obs | 0] and C0 (IQL-diffusion); CFGRL's differ in the goal columns
+        int tables;      // step-bias rows per step: 1 BC [S, H], 2 IQL-diffusion [S, 2, H], 0 CFGRL (t is an argument of its layer-0 kernels)
+        int S;           // Euler steps
+        int goal_dim;    // CFGRL: the goal block in front of the action rows of W0, and goals to stage; else 0
+        bool sweep;      // the weights come per row from the workspace (cfgs), and the combine of step i - 1 rides in front of layer 0 of step i
+    };
+    bool flow_sampler() const { return kind == AgentKind::BC || kind == AgentKind::IQLD || kind == AgentKind::CFGRL; }
+    FlowShape flow_shape(bool sweep) const {
+        if (kind == AgentKind::BC) return {1, true, 1, bc_steps, 0, false};
+        if (kind == AgentKind::IQLD) return {2, true, 2, bc_steps, 0, sweep};
+        return {2, false, 0, gcfg.flow_steps, gcfg.goal_dim, sweep};   // CFGRL
     }
-    // The sweep program of a CFG sampler (IQL-diffusion, CFGRL): sample_actions' program with one guidance weight
-    // per row and S - 1 launches fewer.  The head is the same (IQL-diffusion's step-bias table, the C0 GEMM) and step 0 runs the existing
-    // layer-0 kernel on X[0], where the assemble kernel wrote x.  Step i >= 1 is ONE launch in front of its GEMMs: the CFG combine and
-    // Euler add of step i - 1 with the row's weight, then layer 0 on the new x, which it also writes to X[i & 1] while every thread reads
-    // X[(i - 1) & 1].  Behind the last head GEMM the rows step kernel reads X[(S - 1) & 1] and writes the clipped actions.  The weights
-    // [half] live in the workspace and are bound here; the call copies them in (sample_cfgs), so issue() patches nothing.
-    Eval& get_sweep(int n_pad) {
-        auto it = sweeps.find(n_pad);
-        if (it != sweeps.end()) return *it->second;
-        const bool iqld = kind == AgentKind::IQLD;
-        auto ev = std::make_unique<Eval>();
-        ev->n_pad = n_pad;
-        auto& W = ev->allocs;
-        const int od = cfg.obs_dim, ad = cfg.act_dim, ap = pad16(ad), half = n_pad / 2;
-        const int S = iqld ? bc_steps : gcfg.flow_steps, Gd = iqld ? 0 : gcfg.goal_dim;
+    // the loop-invariant layer-0 term of a hoisted flow sampler: C0 = X W0 + b0 over `rows` rows
+    void emit_c0(Program& pr, const float* X, int rows, float* C0e) {
+        const Layer& l0 = nets[NET_BC].layers[0];
+        Op op{};
+        op.type = OP_GEMM;
+        GemmTask& t = op.gemm;
+        t.A = X; t.lda = l0.in_p; t.B = P + l0.w; t.ldb = l0.out_p; t.bias = P + l0.b; t.C = C0e; t.ldc = l0.out_p;
+        t.M = rows; t.N = l0.out_p; t.K = l0.in_p; t.flags = GF_BIAS;
+        op.reads = {X, t.B};
+        op.writes = {C0e};
+        push(pr, op);
+    }
+    // sample_actions of the flow policies (prog_flow), hoisted: the step-bias table (BC, IQL-diffusion) and the loop-invariant C0 at the
+    // head of the program, then per Euler step layer 0 as a rank-act update of C0 plus the step's row (one launch, both halves), layers
+    // 1.. of the 16-row Dense kernel over n_pad rows, and the guidance step:
+    //   BC: none, the head GEMM's epilogue adds v / S to the actions in place and on the last step writes the clipped actions
+    //   scalar cfg: fql_iqld_cfg_step_kernel behind every head GEMM (CFG combine + Euler add; issue() writes the call's cfg into the
+    //     launch; the last one writes the clipped actions)
+    //   sweep: S - 1 launches fewer.  Step 0 runs the plain layer-0 kernel on X[0], where the assemble kernel
+    //     wrote x.  Step i >= 1 is ONE launch in front of its GEMMs: the combine and Euler add of step i - 1 with the row's weight, then
+    //     layer 0 on the new x, which it also writes to X[i & 1] while every thread reads X[(i - 1) & 1].  Behind the last head GEMM the
+    //     rows step kernel reads X[(S - 1) & 1] and writes the clipped actions.  The weights [half] are bound here; the call copies them
+    //     in (sample_flow), so issue() patches nothing.
+    // n_pad counts both halves of a CFG kind, half = n_pad / 2 a multiple of 16.
+    void build_flow_sampler(Eval& ev, const FlowShape& sh) {
+        auto& W = ev.allocs;
+        const int od = cfg.obs_dim, ad = cfg.act_dim, ap = pad16(ad), S = sh.S, Gd = sh.goal_dim;
+        const int n_pad = ev.n_pad, half = n_pad / sh.halves, rows0 = sh.shared_x ? half : n_pad;
         const Net& n = nets[NET_BC];
         const Layer& l0 = n.layers[0];
         const int H = l0.out_p;
-        const int rows0 = iqld ? half : n_pad;               // IQL-diffusion's halves share [obs | 0] and C0; CFGRL's differ in the goal columns
         const float dt = 1.0f / (float)S;
-        ev->X = dalloc(W, (size_t)rows0 * n.in_p());
-        ev->Xf = dalloc(W, (size_t)half * ap);               // X[0]
-        ev->Xf2 = dalloc(W, (size_t)half * ap);              // X[1]
-        if (iqld) ev->Xq = dalloc(W, (size_t)S * 2 * H);     // step-bias table c[i][half]
+        ev.X = dalloc(W, (size_t)rows0 * n.in_p());                      // [obs | 0]; CFGRL: [obs | goal | 0] ; [obs | unc_embed | 0]
+        ev.Xf = dalloc(W, (size_t)half * ap);                            // the flow's state x (sweep: X[0])
+        if (sh.sweep) ev.Xf2 = dalloc(W, (size_t)half * ap);             // X[1]
+        if (sh.tables) ev.Xq = dalloc(W, (size_t)S * sh.tables * H);     // step-bias table c[i] / c[i][half]
         float* C0e = dalloc(W, (size_t)rows0 * H);
-        ev->tgt = dalloc(W, (size_t)half * ap);
-        ev->cfgs = dalloc(W, (size_t)half);
-        ev->st_obs = dalloc(W, (size_t)half * od);
-        if (!iqld) ev->st_goal = dalloc(W, (size_t)half * Gd);
-        ev->st_noise = dalloc(W, (size_t)half * ad);
-        ev->st_out = dalloc(W, (size_t)half * ad);
-        ev->p_eu = make_pass(W, NET_BC, n_pad, ev->X, false, false);
-        float* const Xpp[2] = {ev->Xf, ev->Xf2};
+        ev.tgt = dalloc(W, (size_t)half * ap);
+        if (sh.sweep) ev.cfgs = dalloc(W, (size_t)half);
+        ev.st_obs = dalloc(W, (size_t)half * od);
+        if (Gd) ev.st_goal = dalloc(W, (size_t)half * Gd);
+        ev.st_noise = dalloc(W, (size_t)half * ad);
+        ev.st_out = dalloc(W, (size_t)half * ad);
+        ev.p_eu = make_pass(W, NET_BC, n_pad, ev.X, false, false);
+        float* const Xpp[2] = {ev.Xf, ev.Xf2};
+        float* const g0 = ev.p_eu.g[0];
         const float* W0a = P + l0.w + (size_t)(od + Gd) * H;   // the action rows of W0 (CFGRL: the t row behind them)
-        const int grid0 = (2 * half * H + FQL_THREADS - 1) / FQL_THREADS;
+        const float* W0e = P + l0.w + (size_t)(od + ad) * H;   // BC, IQL-diffusion: the time-embedding rows behind them
+        const int grid0 = (sh.halves * half * H + FQL_THREADS - 1) / FQL_THREADS;
         emit_lane = 0;
-        Program& pr = ev->prog_flow;
-        if (iqld) {
-            Op op{};
-            op.type = OP_IQLD_STEPBIAS;
-            const IqldStepBiasArgs dsb{d_emb, P + emb_off, P + l0.w + (size_t)(od + ad) * H, ev->Xq, S, H};
-            op.k = bind(fql_iqld_stepbias_kernel, (dsb.S * 2 * dsb.H + FQL_THREADS - 1) / FQL_THREADS, dsb);
-            op.reads = {d_emb, P + emb_off, P + l0.w};
-            op.writes = {ev->Xq};
-            push(pr, op);
+        Program& pr = ev.prog_flow;
+        if (sh.tables == 1) {
+            const BcStepBiasArgs bsb{d_emb, W0e, ev.Xq, S, H};
+            emit(pr, OP_BC_STEPBIAS, bind(fql_bc_stepbias_kernel, (bsb.S * bsb.H + FQL_THREADS - 1) / FQL_THREADS, bsb), {d_emb, P + l0.w}, {ev.Xq});
+        } else if (sh.tables == 2) {
+            const IqldStepBiasArgs dsb{d_emb, P + emb_off, W0e, ev.Xq, S, H};
+            emit(pr, OP_IQLD_STEPBIAS, bind(fql_iqld_stepbias_kernel, (dsb.S * 2 * dsb.H + FQL_THREADS - 1) / FQL_THREADS, dsb),
+                 {d_emb, P + emb_off, P + l0.w}, {ev.Xq});
         }
-        {
-            Op op{};
-            op.type = OP_GEMM;
-            GemmTask& t = op.gemm;
-            t.A = ev->X; t.lda = l0.in_p; t.B = P + l0.w; t.ldb = H; t.bias = P + l0.b; t.C = C0e; t.ldc = H;
-            t.M = rows0; t.N = H; t.K = l0.in_p; t.flags = GF_BIAS;
-            op.reads = {ev->X, t.B};
-            op.writes = {C0e};
-            push(pr, op);
-        }
+        emit_c0(pr, ev.X, rows0, C0e);
         for (int i = 0; i < S; ++i) {
+            const bool last = i == S - 1;
             const float ti = (float)((double)i / (double)S);   // cfgrl.py:90: a Python float, cast to fp32
-            const float* cb = iqld ? ev->Xq + (size_t)i * 2 * H : nullptr;
-            Op op{};
-            if (i == 0) {
-                op.type = iqld ? OP_IQLD_LAYER0 : OP_CFGRL_LAYER0;
-                if (iqld) op.k = bind(fql_iqld_layer0_kernel, grid0, IqldLayer0Args{C0e, Xpp[0], W0a, cb, ev->p_eu.g[0], half, H, ad, ap});
-                else op.k = bind(fql_cfgrl_layer0_kernel, grid0, CfgrlLayer0Args{C0e, Xpp[0], W0a, ev->p_eu.g[0], half, H, ad, ap, ti});
-                op.reads = {C0e, Xpp[0], P + l0.w};
-                op.writes = {ev->p_eu.g[0]};
+            const float* cb = sh.tables ? ev.Xq + (size_t)i * sh.tables * H : nullptr;
+            Op* op;
+            if (!sh.sweep || i == 0) {   // layer 0 on x = Xf
+                const OpType ty = sh.tables == 1 ? OP_BC_LAYER0 : sh.tables == 2 ? OP_IQLD_LAYER0 : OP_CFGRL_LAYER0;
+                const Bound k = sh.tables == 1   ? bind(fql_bc_layer0_kernel, grid0, BcLayer0Args{C0e, ev.Xf, W0a, cb, g0, half, H, ad, ap})
+                                : sh.tables == 2 ? bind(fql_iqld_layer0_kernel, grid0, IqldLayer0Args{C0e, ev.Xf, W0a, cb, g0, half, H, ad, ap})
+                                                 : bind(fql_cfgrl_layer0_kernel, grid0, CfgrlLayer0Args{C0e, ev.Xf, W0a, g0, half, H, ad, ap, ti});
+                op = &emit(pr, ty, k, {C0e, ev.Xf, P + l0.w}, {g0});
             } else {
                 float *xin = Xpp[(i - 1) & 1], *xout = Xpp[i & 1];
-                op.type = OP_CFG_ROWS_LAYER0;
-                if (iqld)
-                    op.k = bind(fql_iqld_cfg_layer0_kernel, grid0,
-                                IqldCfgLayer0Args{C0e, ev->p_eu.out, xin, ev->cfgs, W0a, cb, xout, ev->p_eu.g[0], half, H, ad, ap, dt});
-                else
-                    op.k = bind(fql_cfgrl_cfg_layer0_kernel, grid0,
-                                CfgrlCfgLayer0Args{C0e, ev->p_eu.out, xin, ev->cfgs, W0a, xout, ev->p_eu.g[0], half, H, ad, ap, ti, dt});
-                op.reads = {C0e, ev->p_eu.out, xin, ev->cfgs, P + l0.w};
-                op.writes = {ev->p_eu.g[0], xout};
+                const Bound k = sh.tables ? bind(fql_iqld_cfg_layer0_kernel, grid0,
+                                                 IqldCfgLayer0Args{C0e, ev.p_eu.out, xin, ev.cfgs, W0a, cb, xout, g0, half, H, ad, ap, dt})
+                                          : bind(fql_cfgrl_cfg_layer0_kernel, grid0,
+                                                 CfgrlCfgLayer0Args{C0e, ev.p_eu.out, xin, ev.cfgs, W0a, xout, g0, half, H, ad, ap, ti, dt});
+                op = &emit(pr, OP_CFG_ROWS_LAYER0, k, {C0e, ev.p_eu.out, xin, ev.cfgs, P + l0.w}, {g0, xout});
             }
-            if (iqld) op.reads.push_back(ev->Xq);
-            push(pr, op);
-            emit_forward(pr, ev->p_eu, false, 0, nullptr, nullptr, 0.f, 0.f, 1);
-        }
-        {
-            Op st{};
-            st.type = OP_CFG_ROWS_STEP;
-            const IqldCfgRowsStepArgs dstep{ev->p_eu.out, Xpp[(S - 1) & 1], ev->cfgs, ev->tgt, half, ad, ap, dt};
-            st.k = bind(fql_iqld_cfg_rows_step_kernel, (dstep.n_pad * dstep.ad + FQL_THREADS - 1) / FQL_THREADS, dstep);
-            st.reads = {ev->p_eu.out, dstep.X, ev->cfgs};
-            st.writes = {ev->tgt};
-            push(pr, st);
+            if (sh.tables) op->reads.push_back(ev.Xq);
+            if (sh.halves == 1) {
+                emit_forward(pr, ev.p_eu, false, GF_EULER | (last ? GF_EULER_LAST : 0), ev.Xf, ev.tgt, dt, 0.f, 1);
+                GemmTask& hd = pr.ops.back().gemm;   // the actions alone: ld ap, no observation block in front, no time block behind
+                hd.flags |= GF_EULER_BARE;
+                hd.i0 = ap; hd.i1 = 0;
+                continue;
+            }
+            emit_forward(pr, ev.p_eu, false, 0, nullptr, nullptr, 0.f, 0.f, 1);
+            if (!sh.sweep) {
+                const IqldCfgStepArgs dstep{ev.p_eu.out, ev.Xf, last ? ev.tgt : nullptr, half, ad, ap, 1.0f, dt};
+                Op& st = emit(pr, OP_IQLD_CFG, bind(fql_iqld_cfg_step_kernel, (dstep.n_pad * dstep.ad + FQL_THREADS - 1) / FQL_THREADS, dstep),
+                              {ev.p_eu.out}, {ev.Xf});
+                if (last) st.writes.push_back(ev.tgt);
+            } else if (last) {
+                const IqldCfgRowsStepArgs dstep{ev.p_eu.out, Xpp[i & 1], ev.cfgs, ev.tgt, half, ad, ap, dt};
+                emit(pr, OP_CFG_ROWS_STEP, bind(fql_iqld_cfg_rows_step_kernel, (dstep.n_pad * dstep.ad + FQL_THREADS - 1) / FQL_THREADS, dstep),
+                     {ev.p_eu.out, dstep.X, ev.cfgs}, {ev.tgt});
+            }
         }
         schedule(pr, W);
-        Eval& ref = *ev;
-        sweeps[n_pad] = std::move(ev);
-        return ref;
+    }
+    // ReBRAC, SAC, IQL sample_actions: the actor's forward over the rows (prog_os on p_os; NET_OS is empty here)
+    void build_actor_eval(Eval& ev) {
+        auto& W = ev.allocs;
+        const int od = cfg.obs_dim, ad = cfg.act_dim, n_pad = ev.n_pad;
+        ev.X = dalloc(W, (size_t)n_pad * nets[NET_BC].in_p());
+        ev.st_obs = dalloc(W, (size_t)n_pad * od);
+        ev.st_noise = dalloc(W, (size_t)n_pad * ad);
+        ev.st_out = dalloc(W, (size_t)n_pad * ad);
+        ev.p_os = make_pass(W, NET_BC, n_pad, ev.X, false, false);
+        emit_lane = 0;
+        emit_forward(ev.prog_os, ev.p_os, false);
+        schedule(ev.prog_os, W);
+    }
+    // FQL, IFQL: the one-step actor (prog_os) and the Euler flow of the BC actor (prog_flow); IFQL's critic pair for best-of-N scoring;
+    // a visual agent's two encoders
+    void build_fql_eval(Eval& ev) {
+        auto& W = ev.allocs;
+        const int od = cfg.obs_dim, ad = cfg.act_dim, n_pad = ev.n_pad;
+        ev.X = dalloc(W, (size_t)n_pad * nets[NET_OS].in_p());
+        ev.Xf = dalloc(W, (size_t)n_pad * nets[NET_BC].in_p());
+        ev.tgt = dalloc(W, (size_t)n_pad * pad16(ad));
+        ev.st_obs = dalloc(W, (size_t)n_pad * od);
+        ev.st_noise = dalloc(W, (size_t)n_pad * ad);
+        ev.st_out = dalloc(W, (size_t)n_pad * ad);
+        ev.p_os = make_pass(W, NET_OS, n_pad, ev.X, false, false);
+        ev.p_eu = make_pass(W, NET_BC, n_pad, ev.Xf, false, false);
+        emit_lane = 0;
+        emit_forward(ev.prog_os, ev.p_os, false, GF_CLIP_OUT);
+        const int fs = cfg.flow_steps;
+        for (int s = 0; s < fs; ++s)
+            emit_forward(ev.prog_flow, ev.p_eu, false, GF_EULER | (s == fs - 1 ? GF_EULER_LAST : 0), ev.Xf, ev.tgt,
+                         1.0f / (float)fs, (float)(s + 1) / (float)fs);
+        schedule(ev.prog_os, W);
+        schedule(ev.prog_flow, W);
+        if (kind == AgentKind::IFQL) {   // best-of-N scoring: the critic pair on every sample row
+            ev.Xq = dalloc(W, (size_t)n_pad * nets[NET_C0].in_p());
+            for (int e = 0; e < 2; ++e) {
+                ev.p_q[e] = make_pass(W, NET_C0 + e, n_pad, ev.Xq, false, false);
+                emit_forward(ev.prog_q, ev.p_q[e], false);
+            }
+            schedule(ev.prog_q, W);
+        }
+        if (visual) {
+            const size_t ib = (size_t)cfg.img_h * cfg.img_w * cfg.img_c;
+            ev.st_img = (unsigned char*)dalloc(W, ((size_t)n_pad * ib + 3) / 4 + 4);
+            ev.eb_os = make_enc_buf(W, ENC_OS, n_pad, ev.st_img, false);
+            ev.eb_bc = make_enc_buf(W, ENC_BC, n_pad, ev.st_img, false);
+            emit_lane = 1;   // throughput kernels (the encoder's Dense has K = flat > 1024)
+            emit_encoder_forward(ev.prog_enc_os, ev.eb_os);
+            emit_encoder_forward(ev.prog_enc_bc, ev.eb_bc);
+            emit_lane = 0;
+            schedule(ev.prog_enc_os, W);
+            schedule(ev.prog_enc_bc, W);
+        }
+    }
+    // The workspace of a sampling call over n_pad padded rows.  sweep: the CFG kinds' program with one guidance weight per row, a workspace
+    // of its own under its own key, so that no sample_actions workspace or program changes and neither call is ever handed the other's.
+    Eval& get_eval(int n_pad, bool sweep = false) {
+        const std::pair<int, bool> key{n_pad, sweep};
+        auto it = evals.find(key);
+        if (it != evals.end()) return *it->second;
+        auto ev = std::make_unique<Eval>();
+        ev->n_pad = n_pad;
+        if (flow_sampler()) build_flow_sampler(*ev, flow_shape(sweep));
+        else if (actor_on_obs()) build_actor_eval(*ev);
+        else build_fql_eval(*ev);
+        return *(evals[key] = std::move(ev));
     }
     // The row-chunk loop of every sampling path.  A chunk is <= 4096 rows (256 image rows) of rows_per_obs rows per observation: its
     // observations and noise are staged, `body` enqueues what differs between the paths - the assemble launch, the program(s) and the
     // finishing launch that writes the chunk's [m, act] actions to c.out - and the actions are copied out or, on the engine's own stream, waited for.
-    struct SampleSpec { float temperature = 0.f; int rows_per_obs = 1; bool need_noise = false; int enc = ENC_OS; int noise_rows = -1; bool sweep = false; };   // enc: the encoder of a visual agent's rows; noise_rows: noise rows per observation (-1: rows_per_obs); sweep: the chunk's workspace is get_sweep's
+    struct SampleSpec { float temperature = 0.f; int rows_per_obs = 1; bool need_noise = false; int enc = ENC_OS; int noise_rows = -1; bool sweep = false; };   // enc: the encoder of a visual agent's rows; noise_rows: noise rows per observation (-1: rows_per_obs); sweep: the chunk's workspace is the sweep program's (get_eval)
     struct SampleChunk { Eval& ev; const float *o, *z; float* out; int start, m; };   // observations [start, start + m) of the call
     template <typename Body>
     void sample_chunks(const float* obs, const float* noise, int n, float* out, hipStream_t s, bool own_stream, const SampleSpec& sp, Body&& body) {
@@ -4653,9 +4321,8 @@ struct fql_engine {
         const int per = std::max(1, (visual ? 256 : 4096) / N);
         for (int start = 0; start < n; start += per) {
             const int m = std::min(per, n - start);
-            // (IQL-diffusion: two halves of pad16(m) rows each, so that either half starts on a 16-row tile)
-            Eval& ev = sp.sweep ? get_sweep(2 * pad16(m))
-                                : get_eval(visual ? (m + 63) & ~63 : (kind == AgentKind::IQLD || kind == AgentKind::CFGRL) ? 2 * pad16(m) : pad16(m * N));
+            // (the CFG kinds: N = 2 halves of pad16(m) rows each, so that either half starts on a 16-row tile)
+            Eval& ev = get_eval(visual ? (m + 63) & ~63 : flow_sampler() ? N * pad16(m) : pad16(m * N), sp.sweep);
             const float* o;
             if (visual) {   // `obs` is uint8 [n, H, W, C]: encode with the module's encoder, then proceed on the encodings
                 const size_t ib = (size_t)cfg.img_h * cfg.img_w * cfg.img_c;
@@ -4721,93 +4388,60 @@ struct fql_engine {
             }
         });
     }
-    // BC sample_actions (agents/bc.py:86-101): x ~ N(0, I); S times x += policy(obs, x, i / S) / S; clip.  Rows are independent (16-row
-    // tiles and per-element kernels, the same at every n), so row j of a call equals the single-observation call on the same noise.
-    // noise: [n, act] or null (Philox keyed by (seed, sd) and the row number of the call: chunking does not change the draw)
-    void sample_bc(const float* obs, const float* noise, uint64_t sd, int n, float* out, hipStream_t s, bool own_stream) {
-        const int od = cfg.obs_dim, ad = cfg.act_dim, ap = pad16(ad);
-        sample_chunks(obs, noise, n, out, s, own_stream, SampleSpec{}, [&](const SampleChunk& c) {
-            BcAssembleArgs aa{c.o, c.z, c.ev.X, c.ev.Xf, seed, sd, c.m, c.ev.n_pad, od, ad, nets[NET_BC].in_p(), ap, c.start};
-            hipLaunchKernelGGL(fql_bc_assemble_kernel, dim3((c.ev.n_pad + 3) / 4), dim3(FQL_THREADS), 0, s, aa);
-            run_launches(c.ev.prog_flow, s);
-            hipLaunchKernelGGL(fql_extract_kernel, dim3((c.m * ad + 255) / 256), dim3(256), 0, s, (const float*)c.ev.tgt, c.out, c.m, ad, ap);
-        });
-    }
-    // IQL-diffusion sample_actions (agents/iql_diffusion.py:249-270): x ~ N(0, I); S times v = v_unc + cfg (v_pos - v_unc), x += v / S; clip.
-    // 2n rows per call, [pos ; unc], chunks of 2048 observations.  Rows are independent (16-row tiles and per-element kernels, the same at
-    // every n), so row j of a call equals the single-observation call on the same noise.
-    void sample_iqld(const float* obs, const float* noise, uint64_t sd, float cfg_scale, int n, float* out, hipStream_t s, bool own_stream) {
-        const int od = cfg.obs_dim, ad = cfg.act_dim, ap = pad16(ad);
-        if (!std::isfinite(cfg_scale)) invalid("cfg must be finite");
-        sample_cfg = cfg_scale;
-        SampleSpec sp{};
-        sp.rows_per_obs = 2; sp.noise_rows = 1;
-        sample_chunks(obs, noise, n, out, s, own_stream, sp, [&](const SampleChunk& c) {
-            const int half = c.ev.n_pad / 2;
-            BcAssembleArgs aa{c.o, c.z, c.ev.X, c.ev.Xf, seed, sd, c.m, half, od, ad, nets[NET_BC].in_p(), ap, c.start};
-            hipLaunchKernelGGL(fql_bc_assemble_kernel, dim3((half + 3) / 4), dim3(FQL_THREADS), 0, s, aa);
-            run_launches(c.ev.prog_flow, s);
-            hipLaunchKernelGGL(fql_extract_kernel, dim3((c.m * ad + 255) / 256), dim3(256), 0, s, (const float*)c.ev.tgt, c.out, c.m, ad, ap);
-        });
-    }
-    // CFGRL sample_actions (agents/cfgrl.py:70-100): x ~ N(0, I); flow_steps times v = v_unc + cfg (v_cond - v_unc), x += v / flow_steps; clip.
-    // 2n rows per call, [cond ; unc], chunks of 2048 observations; goals: [n, G].  Rows are independent (16-row tiles and per-element
-    // kernels, the same at every n), so row j of a call equals the single-observation call.
-    void sample_cfgrl(const float* obs, const float* goals, const float* noise, uint64_t sd, float cfg_scale, int n, float* out,
-                      hipStream_t s, bool own_stream) {
-        const int od = cfg.obs_dim, ad = cfg.act_dim, ap = pad16(ad), Gd = gcfg.goal_dim;
-        if (!goals) invalid("goals must not be NULL (the conditional pass reads them: agents/cfgrl.py:93)");
-        if (!std::isfinite(cfg_scale)) invalid("cfg must be finite");
-        sample_cfg = cfg_scale;
-        SampleSpec sp{};
-        sp.rows_per_obs = 2; sp.noise_rows = 1;
-        sample_chunks(obs, noise, n, out, s, own_stream, sp, [&](const SampleChunk& c) {
-            const int half = c.ev.n_pad / 2;
-            const float* g = stage(goals + (size_t)c.start * Gd, c.ev.st_goal, (size_t)c.m * Gd, s);
-            drain_staging(s);
-            CfgrlAssembleArgs aa{c.o, g, P + emb_off, c.z, c.ev.X, c.ev.Xf, seed, sd, c.m, half, od, Gd, ad, nets[NET_BC].in_p(), ap, c.start};
-            hipLaunchKernelGGL(fql_cfgrl_assemble_kernel, dim3((half + 3) / 4), dim3(FQL_THREADS), 0, s, aa);
-            run_launches(c.ev.prog_flow, s);
-            hipLaunchKernelGGL(fql_extract_kernel, dim3((c.m * ad + 255) / 256), dim3(256), 0, s, (const float*)c.ev.tgt, c.out, c.m, ad, ap);
-        });
-    }
-    // sample_actions of both CFG kinds with one guidance weight per row (fql_iqld_sample_actions_cfgs, fql_cfgrl_sample_actions_cfgs): the
-    // sweep program of get_sweep on the same assemble and extract launches.  Row j equals sample_actions on row j with cfg = cfgs[j], bit
-    // for bit.  cfgs: [n], host (checked here: finite) or device (not read on the host); each chunk's weights are copied into the
-    // workspace buffer the program was bound to, with 0 behind them.  goals: CFGRL's [n, G], null on IQL-diffusion.
-    void sample_cfgs(const float* obs, const float* goals, const float* noise, uint64_t sd, const float* cfgs, int n, float* out,
-                     hipStream_t s, bool own_stream) {
-        const bool iqld = kind == AgentKind::IQLD;
-        const int od = cfg.obs_dim, ad = cfg.act_dim, ap = pad16(ad), Gd = iqld ? 0 : gcfg.goal_dim;
-        if (n <= 0) invalid("n must be positive (got %d)", n);
-        if (!cfgs) invalid("cfgs must not be NULL (one guidance weight per row)");
-        if (!iqld && !goals) invalid("goals must not be NULL (the conditional pass reads them: agents/cfgrl.py:93)");
-        const bool host_cfgs = !is_device_ptr(cfgs);
+    // sample_actions of the flow policies (build_flow_sampler's program between the kind's assemble launch and the extract launch):
+    //   BC (agents/bc.py:86-101): x ~ N(0, I); S times x += policy(obs, x, i / S) / S; clip
+    //   IQL-diffusion (agents/iql_diffusion.py:249-270): ... S times v = v_unc + cfg (v_pos - v_unc), x += v / S; clip
+    //   CFGRL (agents/cfgrl.py:70-100): ... flow_steps times v = v_unc + cfg (v_cond - v_unc), x += v / flow_steps; clip.  goals: [n, G]
+    // The CFG kinds run 2n rows per call, [pos ; unc], in chunks of 2048 observations.  Rows are independent (16-row tiles and per-element
+    // kernels, the same at every n), so row j of a call equals the single-observation call on the same noise.  noise: [n, act] or null
+    // (Philox keyed by (seed, sd) and the row number of the call: chunking does not change the draw).
+    // sweep (fql_iqld_sample_actions_cfgs, fql_cfgrl_sample_actions_cfgs): one guidance weight per row, the sweep program on the same
+    // assemble and extract launches.  Row j equals the scalar call on row j with cfg = cfgs[j], bit for bit.  cfgs: [n], host (checked
+    // here: finite) or device (not read on the host); each chunk's weights are copied into the workspace buffer the program was bound to,
+    // with 0 behind them.
+    struct FlowCall { const float* goals = nullptr; float cfg = 1.0f; const float* cfgs = nullptr; bool sweep = false; };
+    void sample_flow(const float* obs, const float* noise, uint64_t sd, int n, float* out, hipStream_t s, bool own_stream, const FlowCall& fc) {
+        const FlowShape sh = flow_shape(fc.sweep);
+        const int od = cfg.obs_dim, ad = cfg.act_dim, ap = pad16(ad), Gd = sh.goal_dim, inp = nets[NET_BC].in_p();
+        if (fc.sweep) {
+            if (n <= 0) invalid("n must be positive (got %d)", n);
+            if (!fc.cfgs) invalid("cfgs must not be NULL (one guidance weight per row)");
+        }
+        if (Gd && !fc.goals) invalid("goals must not be NULL (the conditional pass reads them: agents/cfgrl.py:93)");
+        const bool host_cfgs = fc.sweep && !is_device_ptr(fc.cfgs);
         if (host_cfgs)
             for (int i = 0; i < n; ++i)
-                if (!std::isfinite(cfgs[i])) invalid("cfgs[%d] = %g: every guidance weight must be finite", i, (double)cfgs[i]);
+                if (!std::isfinite(fc.cfgs[i])) invalid("cfgs[%d] = %g: every guidance weight must be finite", i, (double)fc.cfgs[i]);
+        if (sh.halves == 2 && !fc.sweep) {
+            if (!std::isfinite(fc.cfg)) invalid("cfg must be finite");
+            sample_cfg = fc.cfg;
+        }
         SampleSpec sp{};
-        sp.rows_per_obs = 2; sp.noise_rows = 1; sp.sweep = true;
+        sp.rows_per_obs = sh.halves; sp.noise_rows = 1; sp.sweep = fc.sweep;
         sample_chunks(obs, noise, n, out, s, own_stream, sp, [&](const SampleChunk& c) {
-            const int half = c.ev.n_pad / 2;
-            HIP_CHECK(hipMemcpyAsync(c.ev.cfgs, cfgs + c.start, (size_t)c.m * sizeof(float), hipMemcpyDefault, s));
-            if (host_cfgs) staged_host = true;
-            if (half > c.m) HIP_CHECK(hipMemsetAsync(c.ev.cfgs + c.m, 0, (size_t)(half - c.m) * sizeof(float), s));
-            const float* g = iqld ? nullptr : stage(goals + (size_t)c.start * Gd, c.ev.st_goal, (size_t)c.m * Gd, s);
-            drain_staging(s);
-            if (iqld) {
-                BcAssembleArgs aa{c.o, c.z, c.ev.X, c.ev.Xf, seed, sd, c.m, half, od, ad, nets[NET_BC].in_p(), ap, c.start};
-                hipLaunchKernelGGL(fql_bc_assemble_kernel, dim3((half + 3) / 4), dim3(FQL_THREADS), 0, s, aa);
-            } else {
-                CfgrlAssembleArgs aa{c.o, g, P + emb_off, c.z, c.ev.X, c.ev.Xf, seed, sd, c.m, half, od, Gd, ad, nets[NET_BC].in_p(), ap, c.start};
-                hipLaunchKernelGGL(fql_cfgrl_assemble_kernel, dim3((half + 3) / 4), dim3(FQL_THREADS), 0, s, aa);
+            Eval& ev = c.ev;
+            const int half = ev.n_pad / sh.halves;
+            if (fc.sweep) {
+                HIP_CHECK(hipMemcpyAsync(ev.cfgs, fc.cfgs + c.start, (size_t)c.m * sizeof(float), hipMemcpyDefault, s));
+                if (host_cfgs) staged_host = true;
+                if (half > c.m) HIP_CHECK(hipMemsetAsync(ev.cfgs + c.m, 0, (size_t)(half - c.m) * sizeof(float), s));
             }
-            run_launches(c.ev.prog_flow, s);
-            hipLaunchKernelGGL(fql_extract_kernel, dim3((c.m * ad + 255) / 256), dim3(256), 0, s, (const float*)c.ev.tgt, c.out, c.m, ad, ap);
+            const float* g = Gd ? stage(fc.goals + (size_t)c.start * Gd, ev.st_goal, (size_t)c.m * Gd, s) : nullptr;
+            drain_staging(s);
+            if (Gd) {
+                CfgrlAssembleArgs aa{c.o, g, P + emb_off, c.z, ev.X, ev.Xf, seed, sd, c.m, half, od, Gd, ad, inp, ap, c.start};
+                hipLaunchKernelGGL(fql_cfgrl_assemble_kernel, dim3((half + 3) / 4), dim3(FQL_THREADS), 0, s, aa);
+            } else {   // BC over its n_pad rows, IQL-diffusion over the half the two passes share
+                BcAssembleArgs aa{c.o, c.z, ev.X, ev.Xf, seed, sd, c.m, half, od, ad, inp, ap, c.start};
+                hipLaunchKernelGGL(fql_bc_assemble_kernel, dim3((half + 3) / 4), dim3(FQL_THREADS), 0, s, aa);
+            }
+            run_launches(ev.prog_flow, s);
+            hipLaunchKernelGGL(fql_extract_kernel, dim3((c.m * ad + 255) / 256), dim3(256), 0, s, (const float*)ev.tgt, c.out, c.m, ad, ap);
         });
     }
-    // launches of one such call of <= 2048 rows, counted from the built program: assemble, the program's launches, extract
-    int64_t sample_cfgs_launches() { return 2 + (int64_t)get_sweep(2 * 16).prog_flow.launches.size(); }
+    // launches of one flow-sampling call on a single chunk, counted from the built program: assemble, the program's launches, extract.
+    // The smallest workspace of the kind (the count does not depend on the rows): 16 rows, or two halves of 16.
+    int64_t sample_flow_launches(bool sweep) { return 2 + (int64_t)get_eval(flow_shape(sweep).halves * 16, sweep).prog_flow.launches.size(); }
     // IFQL sample_actions (agents/ifql.py:123-155), per observation: num_samples noises through the Euler flow of actor_flow, clip, score by
     // min(q1, q2) of the critic, keep the first argmax.  [n, od] is a batched extension of the reference's single observation: row by row
     // equal to n calls with the same noises.  Chunks of <= 4096 sample rows.
@@ -4830,7 +4464,7 @@ struct fql_engine {
         switch (kind) {
             case AgentKind::FQL: eval_rows(false, obs, noise, sd, n, out, s, own_stream); break;
             case AgentKind::IFQL: sample_best_of_n(obs, noise, sd, n, out, s, own_stream); break;
-            case AgentKind::BC: sample_bc(obs, noise, sd, n, out, s, own_stream); break;
+            case AgentKind::BC: sample_flow(obs, noise, sd, n, out, s, own_stream, FlowCall{}); break;
             default: sample_actor(obs, noise, sd, temperature, n, out, s, own_stream); break;
         }
     }
@@ -5284,9 +4918,8 @@ int fql_destroy(fql_handle h) {
     hipDeviceSynchronize();
     h->free_workspace();
     h->aql.shutdown();
-    for (auto* m : {&h->evals, &h->sweeps})
-        for (auto& kv : *m)
-            for (void* p : kv.second->allocs) hipFree(p);
+    for (auto& kv : h->evals)
+        for (void* p : kv.second->allocs) hipFree(p);
     hipFree(h->P); hipFree(h->G); hipFree(h->Mu); hipFree(h->Nu); hipFree(h->d_chunks); hipFree(h->d_partials); hipFree(h->d_ticket); hipFree(h->d_leaf_range); hipFree(h->d_state); hipFree(h->d_src); hipFree(h->d_emb); hipFree(h->iql_info); hipFree(h->d_state_a);
     if (h->h_src_ring) hipHostFree(h->h_src_ring);
     hipFree(h->d_gsrc); hipFree(h->ds_final); hipFree(h->ds_reps);
@@ -6058,10 +5691,11 @@ int fql_bc_sample_actions(fql_handle h, const float* obs, int n, const float* no
 int fql_bc_stats(fql_handle h, int64_t* launches_per_update, int64_t* macs_per_update, int64_t* launches_per_sample) {
     if (!h) return FQL_E_INVALID;
     FQL_ADMIT(h, EP_bc_stats);
-    if (launches_per_update) *launches_per_update = (int64_t)h->prog_full.launches.size();
-    if (macs_per_update) *macs_per_update = h->macs_per_update();
-    if (launches_per_sample) *launches_per_sample = 4 + (int64_t)h->bc_steps * h->nets[NET_BC].nl();   // assemble, step-bias table, C0, S (layer 0 + nh GEMMs), extract
-    return FQL_OK;
+    FQL_TRY(h, {
+        if (launches_per_update) *launches_per_update = (int64_t)h->prog_full.launches.size();
+        if (macs_per_update) *macs_per_update = h->macs_per_update();
+        if (launches_per_sample) *launches_per_sample = h->sample_flow_launches(false);   // assemble, step-bias table, C0, S (layer 0 + nh GEMMs), extract
+    });
 }
 
 // ---- IQL-diffusion (agents/iql_diffusion.py): IQL critics, weighted flow actor, classifier-free guidance -----------------------------
@@ -6117,7 +5751,7 @@ int fql_iqld_total_loss(fql_handle h, const float* obs, const float* act, const 
 int fql_iqld_sample_actions(fql_handle h, const float* obs, int n, const float* noise, uint64_t seed, float cfg, float* out, void* stream) {
     if (!h) return FQL_E_INVALID;
     FQL_ADMIT(h, EP_iqld_sample_actions);
-    FQL_TRY(h, h->sample_iqld(obs, noise, seed, cfg, n, out, pick(h, stream), stream == nullptr));
+    FQL_TRY(h, h->sample_flow(obs, noise, seed, n, out, pick(h, stream), stream == nullptr, {nullptr, cfg}));
 }
 int fql_iqld_read_rows(fql_handle h, int which, float* out, int n) {
     if (!h) return FQL_E_INVALID;
@@ -6167,11 +5801,12 @@ int fql_iqld_stats(fql_handle h, int update_critic, int update_actor, int64_t* l
                    int64_t* launches_per_sample) {
     if (!h) return FQL_E_INVALID;
     FQL_ADMIT(h, EP_iqld_stats);
-    if (launches_per_update) *launches_per_update = (int64_t)h->iqld_program(update_critic != 0, update_actor != 0).launches.size();
-    if (macs_per_update) *macs_per_update = h->iqld_macs(update_critic != 0, update_actor != 0);
-    // assemble, step-bias table, C0, S (layer 0 + nh GEMMs + the CFG step), extract
-    if (launches_per_sample) *launches_per_sample = 4 + (int64_t)h->bc_steps * (h->nets[NET_BC].nl() + 1);
-    return FQL_OK;
+    FQL_TRY(h, {
+        if (launches_per_update) *launches_per_update = (int64_t)h->iqld_program(update_critic != 0, update_actor != 0).launches.size();
+        if (macs_per_update) *macs_per_update = h->iqld_macs(update_critic != 0, update_actor != 0);
+        // assemble, step-bias table, C0, S (layer 0 + nh GEMMs + the CFG step), extract
+        if (launches_per_sample) *launches_per_sample = h->sample_flow_launches(false);
+    });
 }
 
 // ---- CFGRL (agents/cfgrl.py): goal-conditioned flow policy, classifier-free guidance -------------------------------------------------
@@ -6248,7 +5883,7 @@ int fql_cfgrl_sample_actions(fql_handle h, const float* obs, const float* goals,
                              float* out, void* stream) {
     if (!h) return FQL_E_INVALID;
     FQL_ADMIT(h, EP_cfgrl_sample_actions);
-    FQL_TRY(h, h->sample_cfgrl(obs, goals, noise, seed, cfg, n, out, pick(h, stream), stream == nullptr));
+    FQL_TRY(h, h->sample_flow(obs, noise, seed, n, out, pick(h, stream), stream == nullptr, {goals, cfg}));
 }
 int fql_cfgrl_read_rows(fql_handle h, int probe, int64_t* idx, int64_t* goal_idx, uint8_t* do_cfg, uint32_t* draws, float* goals, int n) {
     if (!h) return FQL_E_INVALID;
@@ -6274,11 +5909,12 @@ int fql_cfgrl_read_rows(fql_handle h, int probe, int64_t* idx, int64_t* goal_idx
 int fql_cfgrl_stats(fql_handle h, int64_t* launches_per_update, int64_t* macs_per_update, int64_t* launches_per_sample) {
     if (!h) return FQL_E_INVALID;
     FQL_ADMIT(h, EP_cfgrl_stats);
-    if (launches_per_update) *launches_per_update = (int64_t)h->prog_full.launches.size();
-    if (macs_per_update) *macs_per_update = h->macs_per_update();
-    // assemble, C0, S (layer 0 + nh GEMMs + the CFG step), extract
-    if (launches_per_sample) *launches_per_sample = 3 + (int64_t)h->gcfg.flow_steps * (h->nets[NET_BC].nl() + 1);
-    return FQL_OK;
+    FQL_TRY(h, {
+        if (launches_per_update) *launches_per_update = (int64_t)h->prog_full.launches.size();
+        if (macs_per_update) *macs_per_update = h->macs_per_update();
+        // assemble, C0, S (layer 0 + nh GEMMs + the CFG step), extract
+        if (launches_per_sample) *launches_per_sample = h->sample_flow_launches(false);
+    });
 }
 
 // ---- guidance sweeps: the two CFG samplers with one weight per row ------------------------------------------
@@ -6286,19 +5922,19 @@ int fql_iqld_sample_actions_cfgs(fql_handle h, const float* obs, int n, const fl
                                  void* stream) {
     if (!h) return FQL_E_INVALID;
     FQL_ADMIT(h, EP_iqld_sample_actions_cfgs);
-    FQL_TRY(h, h->sample_cfgs(obs, nullptr, noise, seed, cfgs, n, out, pick(h, stream), stream == nullptr));
+    FQL_TRY(h, h->sample_flow(obs, noise, seed, n, out, pick(h, stream), stream == nullptr, {nullptr, 1.0f, cfgs, true}));
 }
 int fql_cfgrl_sample_actions_cfgs(fql_handle h, const float* obs, const float* goals, int n, const float* noise, uint64_t seed,
                                   const float* cfgs, float* out, void* stream) {
     if (!h) return FQL_E_INVALID;
     FQL_ADMIT(h, EP_cfgrl_sample_actions_cfgs);
-    FQL_TRY(h, h->sample_cfgs(obs, goals, noise, seed, cfgs, n, out, pick(h, stream), stream == nullptr));
+    FQL_TRY(h, h->sample_flow(obs, noise, seed, n, out, pick(h, stream), stream == nullptr, {goals, 1.0f, cfgs, true}));
 }
 int fql_sample_cfgs_stats(fql_handle h, int64_t* launches_per_call) {
     if (!h) return FQL_E_INVALID;
     FQL_ADMIT(h, EP_sample_cfgs_stats);
     FQL_TRY(h, {
-        const int64_t n = h->sample_cfgs_launches();
+        const int64_t n = h->sample_flow_launches(true);
         if (launches_per_call) *launches_per_call = n;
     });
 }

@@ -304,6 +304,30 @@ def test_sample_actions_match_oracle_and_single_calls(n):
         np.testing.assert_array_equal(a.sample_actions(obs, seed=7), a.sample_actions(obs, seed=7))
 
 
+@pytest.mark.parametrize('S', [1, 3])
+def test_sampler_program_at_two_hidden_layers_and_act_1(S):
+    """The sampler's program away from S = 16, nl = 5: hidden 64 x 2 (nl = 3), obs 5, act 1 (the narrowest padded width).  bc_stats counts
+    the launches of the built program: assemble, step-bias table, C0, S (layer 0 + 2 GEMMs), extract.  At S = 1 the first Euler step is
+    also the last one (the head's epilogue adds v / S and writes the clipped actions in one launch)."""
+    od, ad = 5, 1
+    cfg = _cfg(64, 32, 2, denoise_steps=S)
+    params = _randomized(BO.init_params(8, od, ad, cfg), 8)
+    a = _agent(cfg, od, ad, params=params)
+    assert a.bc_stats()[2] == 4 + S * 3
+    ref = BO.OracleBC(params, dict(cfg), od, ad, np.float64)
+    rng = np.random.default_rng(S)
+    obs = rng.standard_normal((17, od)).astype(np.float32)
+    sn = rng.standard_normal((17, ad)).astype(np.float32)
+    for n in (5, 17):
+        got = a.sample_actions(obs[:n], noises=sn[:n])
+        want = ref.sample_actions(obs[:n], sn[:n])
+        assert got.shape == (n, ad) == want.shape
+        print('S', S, 'n', n, 'max err', float(np.abs(got - want).max()))
+        np.testing.assert_allclose(got, want, rtol=0, atol=2e-5)
+    for j in range(17):   # row j of the n = 17 call is the single-row call on row j
+        np.testing.assert_array_equal(a.sample_actions(obs[j], noises=sn[j]), got[j])
+
+
 # ---- hidden 512 at the shapes and batches that switch kernels: what the update program's plan holds --------------------------------
 def _gemm(plan, kernels=None):
     return [dict(t, kernel=L['kernel'], type=L['type']) for L in plan if kernels is None or L['kernel'] in kernels for t in L['gemm']]
