@@ -38,6 +38,18 @@
 
 #define FQL_LANES 4
 
+// The code object holds the template kernels in the order they are instantiated, which would otherwise be the order in which the host code
+// below happens to name them.  It is fixed here: with the same ISA in every kernel, another placement alone moved the update rate by 0.4 %
+// (MEASUREMENTS.md, "Every launch bound when built").
+template __global__ void fql_gemm16_euler_kernel<true>(const GemmTask*, int, int);
+template __global__ void fql_gemm16_euler_kernel<false>(const GemmTask*, int, int);
+template __global__ void fql_gemm16_kernel<true>(const GemmTask*, int, int);
+template __global__ void fql_gemm16_kernel<false>(const GemmTask*, int, int);
+template __global__ void fql_chain_split_kernel<512, 0>(ChainArgs); template __global__ void fql_chain_split_kernel<512, 1>(ChainArgs); template __global__ void fql_chain_split_kernel<512, 2>(ChainArgs);
+template __global__ void fql_chain_split_kernel<256, 0>(ChainArgs); template __global__ void fql_chain_split_kernel<256, 1>(ChainArgs); template __global__ void fql_chain_split_kernel<256, 2>(ChainArgs);
+template __global__ void fql_chain_kernel<512, 0>(ChainArgs); template __global__ void fql_chain_kernel<512, 1>(ChainArgs); template __global__ void fql_chain_kernel<512, 2>(ChainArgs); template __global__ void fql_chain_kernel<512, 3>(ChainArgs);
+template __global__ void fql_chain_kernel<256, 0>(ChainArgs); template __global__ void fql_chain_kernel<256, 1>(ChainArgs); template __global__ void fql_chain_kernel<256, 2>(ChainArgs); template __global__ void fql_chain_kernel<256, 3>(ChainArgs);
+
 namespace {
 
 thread_local std::string g_create_error;
@@ -129,8 +141,12 @@ struct Leaf {
 // ------------------------------------------------------------------------------------------------
 // OP_WGRAD, OP_LNBWD, OP_POSTOS and the OP_LOSS_{CRITIC,Q,BC} ops ride in OP_GEMM64 (side-lane) launches, never in launches of their own.
 // OP_PEC and OP_XCHAIN are reserved (retired persistent Euler chains): the values index profile labels (bench.py OP_NAMES) and order launches.
-// An agent's types (OP_IFQL_PREP and later) are labels and sort keys only: their launches are bound where the ops are emitted (Bound, below),
-// so a new agent adds enum labels and emit sites (fql_engine::emit()), no payload member of Op and no case of issue().
+// A type is a label (fql_debug_plan, FQL_TRACE, FQL_DUMP, the profile pass, bench.py OP_NAMES) and the sort key inside a (level, lane) of
+// schedule(); it does not say how a launch is issued.  Every launch is a Bound (below): the ops that are launches of their own (OP_PREP,
+// OP_EULER_FIN, OP_LOSS_ACTOR, OP_POOL, OP_POOL_BWD, OP_ENC_DZ, OP_CHAIN, OP_WFRAG, OP_HEAD_DGRAD, OP_ADAM, OP_FINALIZE, an unmerged
+// OP_CONV_WPREP and every agent type, OP_IFQL_PREP and later) are bound where they are emitted (fql_engine::emit()); the types whose ops
+// schedule() merges per level (OP_GEMM, OP_GEMM64 with its riders, the convolution families, OP_DGRAD0, merged OP_CONV_WPREP) carry a payload
+// in Op and are bound where schedule() forms the launch.  A new kernel adds an enum label and an emit site: no member of Op, nothing in issue().
 enum OpType { OP_GEMM, OP_GEMM64, OP_WGRAD, OP_LNBWD, OP_PREP, OP_POSTOS, OP_EULER_FIN, OP_PEC, OP_LOSS_CRITIC, OP_LOSS_Q, OP_LOSS_BC,
               OP_LOSS_ACTOR, OP_CONV_WPREP, OP_CONV, OP_CONV_U8, OP_POOL, OP_POOL_BWD, OP_CONV_WGRAD, OP_CONV_WRED, OP_ENC_DZ, OP_CHAIN, OP_WFRAG, OP_XCHAIN, OP_HEAD_DGRAD, OP_DGRAD0, OP_ADAM,
               OP_FINALIZE,
@@ -152,16 +168,27 @@ enum OpType { OP_GEMM, OP_GEMM64, OP_WGRAD, OP_LNBWD, OP_PREP, OP_POSTOS, OP_EUL
               // the sweep programs of both CFG samplers (one guidance weight per row): after CFGRL's
               OP_CFG_ROWS_LAYER0, OP_CFG_ROWS_STEP, OP_NUM_TYPES };
 
-// A launch bound where its op is emitted (every agent op, OP_IFQL_PREP and later): the kernel, a 1-D grid and the packed arguments,
-// always FQL_THREADS threads and no LDS.  issue() launches it as it stands, so such an op has no payload member and no case of its own.
-constexpr int FQL_BOUND_BYTES = 160;
+// One dispatch, complete: the kernel, its grid, block and dynamic LDS bytes, and the arguments packed as the kernarg segment lays them out.
+// Every launch of every program is one of these, bound where the launch is formed - at the emit site of a single-op launch (fql_engine::emit()),
+// in schedule() for the launches that merge the ops of a level - and issue() launches it as it stands.
+constexpr int FQL_BOUND_ARGS = 11;      // (the table form of the side kernels)
+constexpr int FQL_BOUND_BYTES = 4096;   // a launch's arguments never exceed the kernarg segment (FQL_KA_LIMIT and the hidden block)
 struct Bound {
     const void* fn = nullptr;   // the kernel's host address; null: the op carries no bound launch
-    unsigned grid = 0;
-    int len = 0;                // bytes of `args` in use
-    int at[2] = {0, 0};         // byte offset of each argument (at most two)
+    unsigned grid[3] = {1, 1, 1}, block[3] = {FQL_THREADS, 1, 1};
+    unsigned lds = 0;           // dynamic LDS bytes
+    int nargs = 0;
+    int at[FQL_BOUND_ARGS] = {};   // byte offset of each argument
     int tl_at = -1;             // byte offset of the int that receives the timeline id at issue time, -1: none
-    alignas(16) unsigned char args[FQL_BOUND_BYTES] = {};
+    std::vector<uint8_t> args;
+    unsigned workgroups() const { return grid[0] * grid[1] * grid[2]; }
+};
+// grid, block and LDS bytes of a bound launch; a plain workgroup count means FQL_THREADS threads and no LDS
+struct Geo {
+    dim3 grid, block;
+    size_t lds;
+    Geo(int g) : grid((unsigned)g), block(FQL_THREADS), lds(0) {}
+    Geo(dim3 g, dim3 b, size_t l) : grid(g), block(b), lds(l) {}
 };
 template <typename... T>
 constexpr size_t packed_bytes() {   // kernarg layout: every argument at its natural alignment
@@ -172,84 +199,82 @@ constexpr size_t packed_bytes() {   // kernarg layout: every argument at its nat
 // kernel and arguments meet here, at compile time: each argument is converted to the kernel's parameter type and packed as the kernarg
 // segment lays it out
 template <typename... Pm, typename... A>
-Bound bind(void (*k)(Pm...), int grid, A&&... a) {
-    static_assert(sizeof...(Pm) == sizeof...(A) && sizeof...(Pm) <= 2, "a bound launch takes the kernel's one or two arguments");
-    static_assert(packed_bytes<Pm...>() <= FQL_BOUND_BYTES, "argument struct larger than Bound::args: raise FQL_BOUND_BYTES");
+Bound bind(void (*k)(Pm...), Geo g, A&&... a) {
+    static_assert(sizeof...(Pm) == sizeof...(A) && sizeof...(Pm) <= FQL_BOUND_ARGS, "a bound launch takes exactly the kernel's arguments");
+    static_assert(packed_bytes<Pm...>() <= FQL_BOUND_BYTES, "arguments larger than a kernarg segment");
     Bound b;
     b.fn = (const void*)k;
-    b.grid = (unsigned)grid;
+    b.grid[0] = g.grid.x; b.grid[1] = g.grid.y; b.grid[2] = g.grid.z;
+    b.block[0] = g.block.x; b.block[1] = g.block.y; b.block[2] = g.block.z;
+    b.lds = (unsigned)g.lds;
+    b.args.resize(packed_bytes<Pm...>());
     size_t off = 0;
-    int n = 0;
     auto put = [&](auto v) {
         using T = decltype(v);
         off = (off + alignof(T) - 1) & ~(alignof(T) - 1);
-        b.at[n++] = (int)off;
-        std::memcpy(b.args + off, &v, sizeof(T));
+        b.at[b.nargs++] = (int)off;
+        std::memcpy(b.args.data() + off, &v, sizeof(T));
         off += sizeof(T);
     };
     (put(static_cast<Pm>(a)), ...);
-    b.len = (int)off;
     return b;
 }
+// the same launch with the timeline id written, at issue time, `off` bytes into its first argument / into its last argument (an int)
+inline Bound tl_in(Bound k, size_t off) { k.tl_at = k.at[0] + (int)off; return k; }
+inline Bound tl_last(Bound k) { k.tl_at = k.at[k.nargs - 1]; return k; }
+// The one launch body: bound launch k with the argument bytes `args` (k.args, or a copy with the issue-time words written) on stream s.
+// pa / pb set: the dispatch carries the two events (fql_profile_update).
+inline void launch_bound(const Bound& k, const void* args, hipStream_t s, hipEvent_t pa = nullptr, hipEvent_t pb = nullptr) {
+    void* argv[FQL_BOUND_ARGS];
+    for (int i = 0; i < k.nargs; ++i) argv[i] = (unsigned char*)args + k.at[i];
+    const dim3 g(k.grid[0], k.grid[1], k.grid[2]), b(k.block[0], k.block[1], k.block[2]);
+    if (pa) (void)hipExtLaunchKernel(k.fn, g, b, argv, k.lds, s, pa, pb, 0);
+    else (void)hipLaunchKernel(k.fn, g, b, argv, k.lds, s);
+}
 
+// An op is a launch of its own (k is bound, no payload) or a task that schedule() merges with the others of its level, lane and family into
+// one launch (a payload below, k unbound).
 struct Op {
     OpType type;
     std::vector<const void*> reads, writes;
     GemmTask gemm;
     WgradTask wgrad;
     LnBwdTask ln;
-    PrepArgs prep;
     PostOsArgs postos;
     LossCriticArgs lc;
     LossQArgs lq;
     LossBcArgs lb;
-    LossActorArgs la;
-    EulerFinishArgs ef;
     ConvArgs conv;
-    PoolArgs pool;
-    PoolBwdArgs poolb;
     ConvWgradArgs cw;
     ConvWredArgs cwr;
-    EncDzArgs edz;
-    ChainArgs chain;
     const ConvWprepTask* wprep_tasks = nullptr;
     int wprep_n = 0;
     int cw_grid = 0;
-    int adam_c0 = 0, adam_n = -1;  // chunk range of an Adam op (-1: all chunks)
-    int adam_c1 = 0, adam_n1 = 0;  // second chunk range of the same launch (two modules merged), adam_n1 = 0: none
-    int adam_polyak = -1;          // Polyak range of an Adam op in floats from offset 0 (-1: critic_size; 0: no Polyak step)
-    float adam_lr = 0.f;           // > 0: this launch's learning rate (IQL-diffusion: one per TrainState), else fql_config.lr
-    DevState* adam_st = nullptr;   // the counters this launch's bias correction reads (IQL-diffusion's actor), null: the handle's
-    bool adam_fin = false;         // an Adam op of an update without a finalize launch: its workgroups take tickets, the last runs that code (fin_mode)
-    int fin_mode = 0;
-    Bound k;                 // agent ops: the launch, bound where the op is emitted
+    Bound k;                 // single-op launches: the launch, bound where the op is emitted
+    double macs = 0.0;       // ... and its algorithmic multiply-accumulates where its payload does not say them (chain launches)
     int level = 0;
     int lane = 0;            // 0 = critical lane (Euler chain, one-step backward), 1 = side lane
     std::vector<int> deps;   // indices of earlier ops this op must follow (RAW / WAW / WAR)
 };
 
+// What issue() needs of a launch is its Bound; the rest is what the diagnostics report, what orders the lanes, and what an agent group needs
+// to fuse the members' table-driven launches.
 struct Launch {
     OpType type;
-    int grid = 0, ntasks = 0;
-    size_t lds = 0;
-    void* table = nullptr;  // device task table (GEMM / GEMM64 / convolution families)
-    Op op;                  // arg-struct kernels
-    bool pool_fused = false; // OP_CONV_U8: the stack's max-pool runs inside the convolution kernel (fql_conv3x3_pool_kernel)
     int lane = 0;
-    bool tmt2 = false, kbig = false, euler = false;   // tmt2: OP_GEMM64 launch with 64 x 64 tile tasks (fql_side_big_kernel)
+    int grid = 0, ntasks = 0;    // table-driven launches: workgroups and tasks (0 in a single-op launch; fql_profile_update, FQL_TRACE, FQL_DUMP)
+    Bound k;
     double macs = 0.0;           // algorithmic multiply-accumulates of the GEMM-shaped tasks of this launch (roofline accounting)
+    void* table = nullptr;       // device task table (GEMM / GEMM64 / convolution families)
     // OP_GEMM64 (side-lane) launches: gemm64 tiles, then weight-gradient, LayerNorm-backward and loss / metric tasks of the level
     void *table_w = nullptr, *table_l = nullptr, *table_m = nullptr;
     int n_w = 0, n_l = 0, tile_w = 0, tile_l = 0, tile_m = 0;
-    std::vector<GemmTask> dg_tasks;   // OP_DGRAD0: the (<= 4) tasks of this launch, handed over as the kernel argument
-    // host copies of the device task tables above, as schedule() uploaded them (read by fql_debug_plan only)
+    // host copies of the device task tables above, as schedule() uploaded them (fql_debug_plan, fql_group_s::zip)
     std::vector<GemmTask> h_gemm;
     std::vector<WgradTask> h_wgrad;
     std::vector<LnBwdTask> h_ln;
     std::vector<MiscTask> h_misc;
-    // OP_GEMM64: the same tasks as the kernel argument (fql_kernels.h, find_front), set where the launch is built when they fit the
-    // capacities and FQL_KERNARG_TASKS does not forbid it; issue() then launches the *_ka_kernel twin and the tables stay unused
-    std::shared_ptr<const SideArgs> ka_side;
+    bool ka = false;             // OP_GEMM64: the tasks travel as the kernel argument and the tables stay unused (bind_side)
     std::vector<int> waits;      // launches of the OTHER lane that must have completed
     bool record_after = false;   // some launch of the other lane waits on this one
     hipEvent_t ev = nullptr;
@@ -268,10 +293,10 @@ inline bool fused_tail_env() {
     return !e || atoi(e) != 0;
 }
 // a side-lane launch's four host tables as SideArgs; null when a family exceeds its capacity
-inline std::shared_ptr<const SideArgs> ka_side_args(const Launch& L) {
+inline std::unique_ptr<SideArgs> ka_side_args(const Launch& L) {
     const size_t ng = L.h_gemm.size(), nw = L.h_wgrad.size(), nl = L.h_ln.size(), nm = L.h_misc.size();
     if (ng > FQL_KA_GEMM || nw > FQL_KA_WGRAD || nl > FQL_KA_LN || nm > FQL_KA_MISC) return nullptr;
-    auto a = std::make_shared<SideArgs>();
+    auto a = std::make_unique<SideArgs>();
     std::memset(a.get(), 0, sizeof(SideArgs));
     SideFront& f = a->f;
     f.tile_w = L.tile_w; f.tile_l = L.tile_l; f.tile_m = L.tile_m; f.tl = -1;
@@ -284,6 +309,13 @@ inline std::shared_ptr<const SideArgs> ka_side_args(const Launch& L) {
     for (size_t i = 0; i < nm; ++i) a->m[i] = L.h_misc[i];
     return a;
 }
+// What an Adam launch does besides its chunks, decided by the program that emits it (fql_engine::adam_for)
+struct AdamOpt {
+    float lr = 0.f;           // > 0: this launch's learning rate (IQL-diffusion: one per TrainState), else fql_config.lr
+    DevState* st = nullptr;   // the counters this launch's bias correction reads (IQL-diffusion's actor), null: the handle's
+    int polyak = -1;          // Polyak range in floats from offset 0 (-1: critic_size; 0: no Polyak step)
+    bool fin = false;         // an update without a finalize launch: the workgroups take tickets, the last one runs that code
+};
 struct Program {
     std::vector<Op> ops;
     std::vector<Launch> launches;
@@ -586,6 +618,7 @@ struct fql_engine {
     std::vector<float*> wf_bc;       // per layer 1..nh-1: [H/4][H][4]
     float *wf_w0 = nullptr, *wf_w4 = nullptr;
     WfragTask* d_wfrag = nullptr;
+    std::vector<WfragTask> h_wfrag;   // host copy of d_wfrag (fql_group_s::zip)
     int wfrag_n = 0, wfrag_grid = 0;
     const bool ka_tasks = ka_tasks_env();   // FQL_KERNARG_TASKS, as it stood when this engine was created
     const bool fused_tail = fused_tail_env();   // FQL_FUSED_TAIL, as it stood when this engine was created
@@ -611,7 +644,6 @@ struct fql_engine {
     bool began = false;
     // the single-GPU update as AQL packets on the engine's own HSA queues (fql_aql.h); everything else stays on HIP streams
     AqlRuntime aql;
-    std::vector<AqlDispatch>* aql_rec = nullptr;   // issue() records instead of launching while this is set
     bool last_update_aql = false;
     bool hip_dirty = true;                         // HIP work may be pending on the engine's stream: drain it before the next AQL submit
     void aql_drain() {                             // every AQL update submitted so far has finished (host wait)
@@ -854,6 +886,7 @@ struct fql_engine {
         wfrag_n = (int)tasks.size(); wfrag_grid = tile;
         d_wfrag = (WfragTask*)dalloc(chain_allocs, tasks.size() * sizeof(WfragTask) / sizeof(float) + 4);
         HIP_CHECK(hipMemcpy(d_wfrag, tasks.data(), tasks.size() * sizeof(WfragTask), hipMemcpyHostToDevice));
+        h_wfrag = tasks;
     }
     // after any out-of-graph parameter write (init, fql_set_param): bring the copies up to date
     void refresh_chain_weights(hipStream_t s) {
@@ -1301,8 +1334,9 @@ struct fql_engine {
         {   // this pass's weights in LDS layout (forward and data-gradient forms), one small launch per encoder pass
             Op op{};
             op.type = OP_CONV_WPREP;
-            op.wprep_tasks = enc_wprep[b.enc];
+            op.wprep_tasks = enc_wprep[b.enc];   // (the payload: the passes of one level merge into one launch; alone, this one)
             op.wprep_n = enc_nconv[b.enc];
+            op.k = bind_wprep(op.wprep_tasks, op.wprep_n);
             for (const EncStack& st : en.stacks)
                 for (const ConvL& c : st.conv) {
                     op.reads.push_back(P + c.w);
@@ -1326,12 +1360,9 @@ struct fql_engine {
                 co.writes = {bs.pool, bs.arg};
             } else
             {
-                Op op{};
-                op.type = OP_POOL;
-                op.pool = PoolArgs{bs.c0, bs.pool, bs.arg, n, st.H, st.W, C};
-                op.reads = {bs.c0};
-                op.writes = {bs.pool, bs.arg};
-                push(pr, op);
+                const PoolArgs a{bs.c0, bs.pool, bs.arg, n, st.H, st.W, C};
+                const size_t tot = (size_t)a.N * (a.H / 2) * (a.W / 2) * (a.C / 4);
+                emit(pr, OP_POOL, bind(fql_maxpool_kernel, (tot + FQL_THREADS - 1) / FQL_THREADS, a), {bs.c0}, {bs.pool, bs.arg});
             }
             const float* y = bs.pool;
             for (size_t blk = 0; blk < bs.c1.size(); ++blk) {
@@ -1387,16 +1418,12 @@ struct fql_engine {
         const EncNet& en = encs[b.enc];
         const Layer& D = en.dense;
         {
-            Op op{};
-            op.type = OP_ENC_DZ;
-            op.edz = EncDzArgs{dxa, dxb, b.z + (size_t)img0 * enc_dim, b.dz, n, enc_dim, ld};
-            op.reads = {dxa, b.z};
+            const EncDzArgs a{dxa, dxb, b.z + (size_t)img0 * enc_dim, b.dz, n, enc_dim, ld};
+            Op& op = emit(pr, OP_ENC_DZ, bind(fql_enc_dz_kernel, (a.M * a.n + FQL_THREADS - 1) / FQL_THREADS, a), {dxa, b.z}, {b.dz});
             if (dxb) op.reads.push_back(dxb);
             // level alignment: the three encoder backward passes start together so that their per-level convolutions,
             // weight gradients and partial folds share launches (the lane is serial either way)
             if (align_with) op.reads.push_back(align_with);
-            op.writes = {b.dz};
-            push(pr, op);
         }
         {
             Op op{};
@@ -1452,12 +1479,9 @@ struct fql_engine {
             }
             float* d_c0 = take();
             {
-                Op op{};
-                op.type = OP_POOL_BWD;
-                op.poolb = PoolBwdArgs{dy, bs.arg + (size_t)img0 * q_img, d_c0, n, st.H, st.W, C};
-                op.reads = {dy, bs.arg};
-                op.writes = {d_c0};
-                push(pr, op);
+                const PoolBwdArgs a{dy, bs.arg + (size_t)img0 * q_img, d_c0, n, st.H, st.W, C};
+                const size_t tot = (size_t)a.N * a.H * a.W * (a.C / 4);
+                emit(pr, OP_POOL_BWD, bind(fql_maxpool_bwd_kernel, (tot + FQL_THREADS - 1) / FQL_THREADS, a), {dy, bs.arg}, {d_c0});
             }
             if (s == 0) {
                 const size_t ib = (size_t)st.H * st.W * st.conv[0].cin;
@@ -1498,7 +1522,7 @@ struct fql_engine {
         op.lane = emit_lane;
         pr.ops.push_back(op);
     }
-    // an agent op appended on emit_lane: the bound launch and the buffers it reads and writes.  The reference is for the sites that
+    // a single-op launch appended on emit_lane: the bound launch and the buffers it reads and writes.  The reference is for the sites that
     // append conditional reads or writes (it holds until the next op is pushed).
     Op& emit(Program& pr, OpType type, const Bound& k, std::vector<const void*> reads, std::vector<const void*> writes) {
         Op op{};
@@ -1635,14 +1659,56 @@ struct fql_engine {
                 push(pr, op);
             }
         }
-        Op op{};
-        op.type = OP_EULER_FIN;
+        emit_euler_finish(pr);
+    }
+
+    // the last Euler step of both fused chains: target = clip(a + (folded head partials + bias) / flow_steps)
+    void emit_euler_finish(Program& pr) {
+        const Net& n = nets[NET_BC];
+        const int nh = n.nl() - 1, fs = cfg.flow_steps, od = cfg.obs_dim, ad = cfg.act_dim, ap = pad16(ad);
         const bool from_x = fs == 1;
-        op.ef = EulerFinishArgs{from_x ? X_eu + od : Abuf[(fs - 1) & 1], Vpart, P + n.layers[nh].b, tgt, B, ad, ap, vp_tiles,
-                                from_x ? inp_b : ap, 1.0f / (float)fs};
-        op.reads = {from_x ? (const void*)X_eu : (const void*)Abuf[(fs - 1) & 1], Vpart, P + n.layers[nh].w};   // (head bias: WAR against Adam)
-        op.writes = {tgt};
-        push(pr, op);
+        const EulerFinishArgs ef{from_x ? X_eu + od : Abuf[(fs - 1) & 1], Vpart, P + n.layers[nh].b, tgt, B, ad, ap, vp_tiles,
+                                 from_x ? n.in_p() : ap, 1.0f / (float)fs};
+        emit(pr, OP_EULER_FIN, bind(fql_euler_finish_kernel, (ef.M * ef.ad + FQL_THREADS - 1) / FQL_THREADS, ef),
+             {from_x ? (const void*)X_eu : (const void*)Abuf[(fs - 1) & 1], Vpart, P + n.layers[nh].w},   // (head bias: WAR against Adam)
+             {tgt});
+    }
+
+    // XCD-aware tile order of a chain launch over M rows of an H-wide layer (16-row tiles x 32-column tiles): the number of row groups gm
+    // (gm x gn = 8 blocks of the tile grid) with the fewest panel fetches, 0 = row-major when no grouping divides the grid
+    static int chain_xg(int M, int H) {
+        const int ntm = M / 16, ntn = H / 32;
+        int xg = 0;
+        double best = 1e30;
+        for (int gm : {1, 2, 4, 8}) {
+            const int gn = 8 / gm;
+            if (ntm % gm || ntn % gn) continue;
+            const double cost = (double)gn * M + (double)gm * H;
+            if (cost < best) { best = cost; xg = gm; }
+        }
+        return xg;
+    }
+    // One launch of the chain kernel (fql_chain.h) over `a` (variant 0 .. 2: a link of the Euler chain; 3: a hidden layer's data gradient):
+    // the instantiation for this hidden width and variant, split-bf16 operands at precision = 2 except in variant 3 (its dZ / W arrive as
+    // fp32 and splitting both in the kernel costs what the MFMAs save).  The caller sets the op's reads and writes.
+    Op chain_op(ChainArgs a) {
+        const int H = cfg.actor_hidden[0];
+        a.tl = -1;
+        a.xg = chain_xg(a.M, H);
+        const bool split = cfg.precision == 2 && a.variant != 3;
+        const Geo g512(dim3((a.M / 16) * (512 / 32)), dim3(FQL_CHAIN_THREADS), FQL_CHAIN_LDS_BYTES(512));
+        const Geo g256(dim3((a.M / 16) * (256 / 32)), dim3(FQL_CHAIN_THREADS), FQL_CHAIN_LDS_BYTES(256));
+        Op op{};
+        op.type = OP_CHAIN;
+#define FQL_CHAIN_PICK(KERNEL, VV) (H == 512 ? bind(KERNEL<512, VV>, g512, a) : bind(KERNEL<256, VV>, g256, a))
+        if (split) op.k = a.variant == 0 ? FQL_CHAIN_PICK(fql_chain_split_kernel, 0) : a.variant == 1 ? FQL_CHAIN_PICK(fql_chain_split_kernel, 1)
+                                                                                                       : FQL_CHAIN_PICK(fql_chain_split_kernel, 2);
+        else op.k = a.variant == 0 ? FQL_CHAIN_PICK(fql_chain_kernel, 0) : a.variant == 1 ? FQL_CHAIN_PICK(fql_chain_kernel, 1)
+                  : a.variant == 2 ? FQL_CHAIN_PICK(fql_chain_kernel, 2) : FQL_CHAIN_PICK(fql_chain_kernel, 3);
+#undef FQL_CHAIN_PICK
+        op.k = tl_in(op.k, offsetof(ChainArgs, tl));
+        op.macs = (double)a.M * H * H + (a.variant == 0 ? (double)a.M * 16.0 * H : 0.0) + (a.variant == 2 ? (double)a.M * H * a.ap : 0.0);
+        return op;
     }
 
     // The same 3-launches-per-step chain on fql_chain_kernel (512-thread workgroups, fragment-major weights, kernarg tasks)
@@ -1665,52 +1731,46 @@ struct fql_engine {
         for (int s = 0; s < fs; ++s) {
             for (int l = 1; l < nh; ++l) {
                 const Layer& ly = n.layers[l];
-                Op op{};
-                op.type = OP_CHAIN;
-                ChainArgs& a = op.chain;
+                ChainArgs a{};
+                std::vector<const void*> reads, writes;
                 a.Wf = wf_bc[l - 1]; a.bias = P + ly.b;
                 a.M = B; a.ad = ad; a.ap = ap;
                 a.inv_steps = 1.0f / (float)fs; a.t_s = (float)s / (float)fs;
                 a.variant = 1;
-                op.reads = {a.Wf, P + ly.w};
+                reads = {a.Wf, P + ly.w};
                 if (l == 1) {
                     a.variant = 0;
                     a.A = C0; a.W0f = wf_w0;
                     if (s <= 1) { a.ea_in = X_eu + od; a.ea_ld = inp_b; } else { a.ea_in = Abuf[(s - 1) & 1]; a.ea_ld = ap; }
-                    op.reads.push_back(C0);
-                    op.reads.push_back(wf_w0);
-                    op.reads.push_back((s <= 1) ? (const void*)X_eu : (const void*)Abuf[(s - 1) & 1]);
+                    reads.push_back(C0);
+                    reads.push_back(wf_w0);
+                    reads.push_back((s <= 1) ? (const void*)X_eu : (const void*)Abuf[(s - 1) & 1]);
                     if (s >= 1) {
                         a.evp_in = Vpart; a.eb = P + n.layers[nh].b; a.ea_out = Abuf[s & 1];
-                        op.reads.push_back(Vpart);
-                        op.reads.push_back(P + n.layers[nh].w);
-                        op.writes.push_back(Abuf[s & 1]);
+                        reads.push_back(Vpart);
+                        reads.push_back(P + n.layers[nh].w);
+                        writes.push_back(Abuf[s & 1]);
                     }
                 } else {
                     a.A = p_eu.g[l - 1];
-                    op.reads.push_back(a.A);
+                    reads.push_back(a.A);
                 }
                 if (l == nh - 1) {   // nh >= 3: never the same launch as variant A
                     a.variant = 2;
                     a.W4f = wf_w4; a.evp_out = Vpart;
-                    op.reads.push_back(wf_w4);
-                    op.writes.push_back(Vpart);
+                    reads.push_back(wf_w4);
+                    writes.push_back(Vpart);
                 } else {
                     a.C = p_eu.g[l];
-                    op.writes.push_back(a.C);
+                    writes.push_back(a.C);
                 }
+                Op op = chain_op(a);
+                op.reads = reads; op.writes = writes;
                 push(pr, op);
             }
         }
         if (euler_finish_fused) return;
-        Op op{};
-        op.type = OP_EULER_FIN;
-        const bool from_x = fs == 1;
-        op.ef = EulerFinishArgs{from_x ? X_eu + od : Abuf[(fs - 1) & 1], Vpart, P + n.layers[nh].b, tgt, B, ad, ap, vp_tiles,
-                                from_x ? inp_b : ap, 1.0f / (float)fs};
-        op.reads = {from_x ? (const void*)X_eu : (const void*)Abuf[(fs - 1) & 1], Vpart, P + n.layers[nh].w};   // (head bias: WAR against Adam)
-        op.writes = {tgt};
-        push(pr, op);
+        emit_euler_finish(pr);
     }
     // refresh of the fragment-major copies inside a program, behind the Adam launch that rewrites the BC flow's kernels
     void emit_wfrag(Program& pr) {
@@ -1718,6 +1778,7 @@ struct fql_engine {
         const Net& n = nets[NET_BC];
         Op op{};
         op.type = OP_WFRAG;
+        op.k = tl_last(bind(fql_wfrag_kernel, wfrag_grid, d_wfrag, wfrag_n, -1));
         for (const Layer& L : n.layers) op.reads.push_back(P + L.w);
         for (float* w : wf_bc) op.writes.push_back(w);
         op.writes.push_back(wf_w0);
@@ -1835,12 +1896,11 @@ struct fql_engine {
                 // kernel's variant D does it in about half the time of the generic 16-row kernel
                 if (op.type == OP_GEMM && use_chain && t.N == t.K && t.N == cfg.actor_hidden[0] && t.M % 16 == 0 &&
                     t.lda == t.K && t.ldb == t.K && t.ldc == t.N && prev.out_p == t.N) {
-                    Op co{};
-                    co.type = OP_CHAIN;
-                    ChainArgs& a = co.chain;
+                    ChainArgs a{};
                     a.A = t.A; a.Wf = t.B; a.C = t.C; a.Zprev = t.Zprev; a.bias = nullptr;
                     a.M = t.M; a.ad = cfg.act_dim; a.ap = pad16(cfg.act_dim);
                     a.variant = 3;
+                    Op co = chain_op(a);
                     co.reads = op.reads; co.writes = op.writes;
                     push(pr, co);
                 } else
@@ -1856,6 +1916,58 @@ struct fql_engine {
     // ---------------------------------------------------------------------------------------
     // scheduling + launch tables + graph capture
     // ---------------------------------------------------------------------------------------
+    // The launches that merge the ops of a level are bound where they are formed, by one helper per family, from what the Launch holds by
+    // then: its tables, counts, grid and host task copies.  (An agent group binds its fused launches with the first two.)
+    // OP_GEMM: the 16-row kernel; its K > 512 and Euler-prologue instantiations where a task of the launch needs them
+    void bind_gemm16(Launch& L) const {
+        bool kbig = false, euler = false;
+        size_t lds = 0;
+        for (const GemmTask& t : L.h_gemm) {
+            kbig |= t.K > 512;
+            euler |= (t.flags & (GF_A_EULER0 | GF_HEAD_PART | GF_A_LOSSACT)) != 0;
+            lds = std::max(lds, ((size_t)16 * (t.K + 4) + 1024 + 1280) * sizeof(float));
+        }
+        const Geo g(dim3(L.grid), dim3(FQL_THREADS), lds);
+        auto table = [&](auto kernel) { return tl_last(bind(kernel, g, (const GemmTask*)L.table, L.ntasks, -1)); };
+        L.k = euler ? (kbig ? table(fql_gemm16_euler_kernel<true>) : table(fql_gemm16_euler_kernel<false>))
+                    : (kbig ? table(fql_gemm16_kernel<true>) : table(fql_gemm16_kernel<false>));
+    }
+    // OP_GEMM64, the level's side-lane launch: 64 x 64 tile tasks take fql_side_big_kernel, precision = 2 the split bodies; the tasks travel
+    // as the kernel argument when they fit its capacities and FQL_KERNARG_TASKS does not forbid it, else the kernel reads the four tables
+    void bind_side(Launch& L, size_t lds) const {
+        bool big = false;
+        for (const GemmTask& t : L.h_gemm) big |= t.tmt == 2;
+        const bool split = cfg.precision == 2;
+        const Geo g(dim3(L.grid), dim3(FQL_THREADS), lds);
+        const std::unique_ptr<SideArgs> a = ka_tasks ? ka_side_args(L) : nullptr;
+        L.ka = a != nullptr;
+        auto ka = [&](auto kernel) { return tl_in(bind(kernel, g, *a), offsetof(SideArgs, f) + offsetof(SideFront, tl)); };
+        auto table = [&](auto kernel) {
+            return tl_last(bind(kernel, g, (const GemmTask*)L.table, L.ntasks, (const WgradTask*)L.table_w, L.n_w, (const LnBwdTask*)L.table_l, L.n_l,
+                                L.tile_w, L.tile_l, (const MiscTask*)L.table_m, L.tile_m, -1));
+        };
+        if (a) L.k = big ? ka(fql_side_big_ka_kernel) : split ? ka(fql_side_split_ka_kernel) : ka(fql_side_ka_kernel);
+        else L.k = big ? table(fql_side_big_kernel) : split ? table(fql_side_split_kernel) : table(fql_side_kernel);
+    }
+    // OP_CONV, OP_CONV_U8, OP_CONV_WGRAD, OP_CONV_WRED: the arg structs of the level in L.table.  pool_fused: the stack's max-pool runs inside
+    // the convolution kernel
+    void bind_conv(Launch& L, bool pool_fused, size_t lds) const {
+        const bool split = cfg.precision == 2;
+        const Geo g(dim3(L.grid), dim3(FQL_THREADS), lds);
+        auto conv = [&](auto kernel) { return bind(kernel, g, (const ConvArgs*)L.table, L.ntasks); };
+        if (L.type == OP_CONV_WRED) L.k = bind(fql_conv_wgrad_reduce_kernel, L.grid, (const ConvWredArgs*)L.table, L.ntasks);
+        else if (L.type == OP_CONV_WGRAD)
+            L.k = split ? bind(fql_conv_wgrad_split_kernel, g, (const ConvWgradArgs*)L.table, L.ntasks)
+                        : bind(fql_conv_wgrad_kernel, g, (const ConvWgradArgs*)L.table, L.ntasks);
+        else if (pool_fused) L.k = split ? conv(fql_conv3x3_pool_split_kernel) : conv(fql_conv3x3_pool_kernel);
+        else if (L.type == OP_CONV) L.k = split ? conv(fql_conv3x3_split_kernel) : conv(fql_conv3x3_kernel);
+        else L.k = split ? conv(fql_conv3x3_u8_split_kernel) : conv(fql_conv3x3_u8_kernel);
+    }
+    // OP_CONV_WPREP: n tasks (one encoder pass's, or those of the passes of a level), four workgroups each
+    static Bound bind_wprep(const ConvWprepTask* tasks, int n) {
+        return bind(fql_conv_wprep_kernel, Geo(dim3(4, n), dim3(FQL_THREADS), 0), tasks);
+    }
+
     void schedule(Program& pr, std::vector<void*>& owner) {
         // list scheduling: level = 1 + max level of every op this one conflicts with (RAW, WAW, WAR)
         std::map<const void*, int> last_writer;               // buffer -> op index of last writer
@@ -1905,6 +2017,11 @@ struct fql_engine {
         pr.launches.clear();
         for (bool& b : pr.lane_used) b = false;
         std::vector<int> launch_of(pr.ops.size(), -1);
+        auto up = [&](const void* src, size_t bytes) -> void* {   // a task table in device memory
+            void* d = dalloc(owner, bytes / sizeof(float) + 4);
+            if (bytes) HIP_CHECK(hipMemcpy(d, src, bytes, hipMemcpyHostToDevice));
+            return d;
+        };
         for (int lv = 0; lv <= maxlv; ++lv) {
           for (int lane = 0; lane < FQL_LANES; ++lane) {
             for (int ty = 0; ty < OP_NUM_TYPES; ++ty) {
@@ -1961,7 +2078,6 @@ struct fql_engine {
                         GemmTask t = o->gemm;
                         const int ri_t = cfg.precision != 2 && t.M >= 1024 && t.M % 64 == 0 ? 2 : 1;   // split bodies are 32-row tiles
                         ri = std::max(ri, ri_t);
-                        if (ri_t == 2) L.tmt2 = true;
                         t.tmt = ri_t;
                         t.wk = ri_t == 2 ? 2 : nj;          // MFMA column tiles per wave: tile = 32 x (32 wk)
                         t.ntn = t.N / (32 * t.wk); t.tile0 = tile;
@@ -2013,22 +2129,17 @@ struct fql_engine {
                     L.grid = L.tile_m + (int)tmisc.size();
                     L.ntasks = (int)tg.size(); L.n_w = (int)tw.size(); L.n_l = (int)tl.size();
                     const size_t wlds = cfg.precision == 2 ? (size_t)(4 * 4 * 64 * 4 + 4 * 64) : (size_t)FQL_WGRAD_LDS_FLOATS;   // 16- / 32-input tiles
-                    L.lds = sizeof(float) * (tg.empty() ? wlds
+                    size_t lds = sizeof(float) * (tg.empty() ? wlds
                                              : ri == 2 ? (size_t)(2 * (32 * ri + 64) * 68 + 256)
                                              : cfg.precision == 2 ? (size_t)FQL_TILE_SPLIT_LDS_FLOATS(nj)
                                              : nj == 1 ? (size_t)(2 * 32 * 68 + 2 * 64 * 36 + 128) : (size_t)(2 * 32 * 68 + 2 * 64 * 68 + 128));
-                    L.lds = std::max(L.lds, sizeof(float) * (selw.empty() ? (size_t)0 : wlds));
-                    auto up = [&](const void* src, size_t bytes) -> void* {
-                        void* d = dalloc(owner, bytes / sizeof(float) + 4);
-                        if (bytes) HIP_CHECK(hipMemcpy(d, src, bytes, hipMemcpyHostToDevice));
-                        return d;
-                    };
+                    lds = std::max(lds, sizeof(float) * (selw.empty() ? (size_t)0 : wlds));
                     L.table = up(tg.data(), tg.size() * sizeof(GemmTask));
                     L.table_w = up(tw.data(), tw.size() * sizeof(WgradTask));
                     L.table_l = up(tl.data(), tl.size() * sizeof(LnBwdTask));
                     L.table_m = up(tmisc.data(), tmisc.size() * sizeof(MiscTask));
                     L.h_gemm = tg; L.h_wgrad = tw; L.h_ln = tl; L.h_misc = tmisc;
-                    if (ka_tasks) L.ka_side = ka_side_args(L);
+                    bind_side(L, lds);
                     pr.launches.push_back(L);
                     continue;
                 }
@@ -2043,11 +2154,8 @@ struct fql_engine {
                     for (const Op* o : sel) launch_of[o - pr.ops.data()] = (int)pr.launches.size();
                     L.ntasks = (int)sel.size();
                     int tile = 0;
-                    auto up = [&](const void* src, size_t bytes) {
-                        void* d = dalloc(owner, bytes / sizeof(float) + 4);
-                        HIP_CHECK(hipMemcpy(d, src, bytes, hipMemcpyHostToDevice));
-                        return d;
-                    };
+                    size_t lds = 0;
+                    bool pool_fused = false;
                     if (ty == OP_CONV || ty == OP_CONV_U8) {
                         std::vector<ConvArgs> tb;
                         long long nb_all = 0;
@@ -2064,12 +2172,12 @@ struct fql_engine {
                             a.nwg = ty == OP_CONV_U8 ? std::min(nb, std::max(1, (int)(((long long)u8_per_cu * num_cus * nb) / nb_all))) : nb;
                             if (a.parg) {   // convolution + max-pool in one kernel: a workgroup per (image, pooled row pair)
                                 a.nwg = a.N * ((a.H + 3) / 4);
-                                L.pool_fused = true;
-                                L.lds = std::max(L.lds, (size_t)FQL_CONV_POOL_LDS_FLOATS(a.W, a.Ci, a.Co) * sizeof(float));
-                            } else if (L.pool_fused) invalid("internal: a launch mixes fused and plain convolutions");
+                                pool_fused = true;
+                                lds = std::max(lds, (size_t)FQL_CONV_POOL_LDS_FLOATS(a.W, a.Ci, a.Co) * sizeof(float));
+                            } else if (pool_fused) invalid("internal: a launch mixes fused and plain convolutions");
                             tile += a.nwg;
-                            L.lds = std::max(L.lds, ((size_t)(a.R + 2) * (a.W + 2) * (a.Ci + 4) + (size_t)a.Co * (9 * a.Ci + 4)) * sizeof(float));
-                            if (ty == OP_CONV && cfg.precision == 2) L.lds = std::max(L.lds, (size_t)FQL_CONV_SPLIT_LDS_WORDS(a.R, a.W, a.Ci, a.Co) * sizeof(float));
+                            lds = std::max(lds, ((size_t)(a.R + 2) * (a.W + 2) * (a.Ci + 4) + (size_t)a.Co * (9 * a.Ci + 4)) * sizeof(float));
+                            if (ty == OP_CONV && cfg.precision == 2) lds = std::max(lds, (size_t)FQL_CONV_SPLIT_LDS_WORDS(a.R, a.W, a.Ci, a.Co) * sizeof(float));
                             tb.push_back(a);
                         }
                         L.table = up(tb.data(), tb.size() * sizeof(ConvArgs));
@@ -2079,7 +2187,7 @@ struct fql_engine {
                             ConvWgradArgs a = o->cw;
                             a.tile0 = tile; a.nwg = o->cw_grid;
                             tile += a.nwg;
-                            L.lds = std::max(L.lds, ((size_t)(a.R + 2) * (a.W + 2) * (a.Ci + 4) + (size_t)a.R * a.W * (a.Co + 4)) * sizeof(float));
+                            lds = std::max(lds, ((size_t)(a.R + 2) * (a.W + 2) * (a.Ci + 4) + (size_t)a.R * a.W * (a.Co + 4)) * sizeof(float));
                             tb.push_back(a);
                         }
                         L.table = up(tb.data(), tb.size() * sizeof(ConvWgradArgs));
@@ -2094,6 +2202,7 @@ struct fql_engine {
                         L.table = up(tb.data(), tb.size() * sizeof(ConvWredArgs));
                     }
                     L.grid = tile;
+                    bind_conv(L, pool_fused, lds);
                     pr.launches.push_back(L);
                     continue;
                 }
@@ -2101,13 +2210,15 @@ struct fql_engine {
                     for (size_t i0 = 0; i0 < sel.size(); i0 += 4) {
                         Launch L;
                         L.type = OP_DGRAD0;
-                        L.op = *sel[i0];
                         L.lane = lane;
+                        Dgrad0Args a{};
+                        a.col0 = sel[i0]->gemm.i1;
                         for (size_t i = i0; i < std::min(sel.size(), i0 + 4); ++i) {
                             if (sel[i]->gemm.M != sel[i0]->gemm.M || sel[i]->gemm.i1 != sel[i0]->gemm.i1) invalid("internal: dQ/da tasks of one level differ in shape");
-                            L.dg_tasks.push_back(sel[i]->gemm);
+                            a.t[a.ntasks++] = sel[i]->gemm;
                             launch_of[sel[i] - pr.ops.data()] = (int)pr.launches.size();
                         }
+                        L.k = bind(fql_dgrad0_kernel, a.ntasks * (sel[i0]->gemm.M / 16), a);
                         pr.launches.push_back(L);
                     }
                     continue;
@@ -2124,9 +2235,7 @@ struct fql_engine {
                     }
                     Launch L;
                     L.type = OP_CONV_WPREP;
-                    L.op = *sel[0];
-                    L.op.wprep_tasks = all;
-                    L.op.wprep_n = tot;
+                    L.k = bind_wprep(all, tot);
                     L.lane = lane;
                     pr.launches.push_back(L);
                     continue;
@@ -2135,7 +2244,7 @@ struct fql_engine {
                     for (const Op* o : sel) {
                         Launch L;
                         L.type = (OpType)ty;
-                        L.op = *o;
+                        L.k = o->k;
                         L.lane = lane;
                         launch_of[o - pr.ops.data()] = (int)pr.launches.size();
                         pr.launches.push_back(L);
@@ -2157,15 +2266,12 @@ struct fql_engine {
                     t.ntn = (t.N / 16 + (4 / t.wk) - 1) / (4 / t.wk);
                     t.tile0 = tile;
                     tile += (t.M / 16) * t.ntn;
-                    if (t.K > 512) L.kbig = true;
-                    if (t.flags & (GF_A_EULER0 | GF_HEAD_PART | GF_A_LOSSACT)) L.euler = true;
-                    L.lds = std::max(L.lds, ((size_t)16 * (t.K + 4) + 1024 + 1280) * sizeof(float));
                     tb.push_back(t);
                 }
-                L.table = dalloc(owner, tb.size() * sizeof(GemmTask) / sizeof(float) + 4);
-                HIP_CHECK(hipMemcpy(L.table, tb.data(), tb.size() * sizeof(GemmTask), hipMemcpyHostToDevice));
+                L.table = up(tb.data(), tb.size() * sizeof(GemmTask));
                 L.grid = tile;
                 L.h_gemm = tb;
+                bind_gemm16(L);
                 pr.launches.push_back(L);
             }
           }
@@ -2202,10 +2308,7 @@ struct fql_engine {
             if (o.type == OP_GEMM || o.type == OP_GEMM64 || o.type == OP_HEAD_DGRAD) m = (double)o.gemm.M * o.gemm.N * o.gemm.K;
             else if (o.type == OP_DGRAD0) m = (double)o.gemm.M * 16.0 * o.gemm.K;
             else if (o.type == OP_WGRAD) m = (double)o.wgrad.M * o.wgrad.Kin * o.wgrad.N;
-            else if (o.type == OP_CHAIN) {
-                const double H = cfg.actor_hidden[0];
-                m = (double)o.chain.M * H * H + (o.chain.variant == 0 ? (double)o.chain.M * 16.0 * H : 0.0) + (o.chain.variant == 2 ? (double)o.chain.M * H * o.chain.ap : 0.0);
-            }
+            else if (o.type == OP_CHAIN) m = o.macs;
             else if (o.type == OP_CONV || o.type == OP_CONV_U8) m = (double)o.conv.N * o.conv.H * o.conv.W * 9.0 * (o.conv.transposed ? o.conv.Ci : o.conv.Ci_real) * o.conv.Co;
             else if (o.type == OP_CONV_WGRAD) m = (double)o.cw.N * o.cw.H * o.cw.W * 9.0 * o.cw.Ci_real * o.cw.Co;
             pr.launches[li].macs += m;
@@ -2248,200 +2351,27 @@ struct fql_engine {
                             "(hipStreamEndCapture recursion); move one of the passes", a, b);
     }
 
-    // XCD-aware tile order of a chain launch over M rows of an H-wide layer (16-row tiles x 32-column tiles): the number of row groups gm
-    // (gm x gn = 8 blocks of the tile grid) with the fewest panel fetches, 0 = row-major when no grouping divides the grid
-    static int chain_xg(int M, int H) {
-        const int ntm = M / 16, ntn = H / 32;
-        int xg = 0;
-        double best = 1e30;
-        for (int gm : {1, 2, 4, 8}) {
-            const int gn = 8 / gm;
-            if (ntm % gm || ntn % gn) continue;
-            const double cost = (double)gn * M + (double)gm * H;
-            if (cost < best) { best = cost; xg = gm; }
-        }
-        return xg;
-    }
-
-    // one launch of a program on stream s (tl: timeline id of the diagnostics build, -1 = none); reads engine state only.  The FQL and
-    // encoder types have a case each; every agent type takes the last one, which launches what the emit site bound (Op::k).
+    // One launch of a program on stream s: what was bound where the launch was formed (Launch::k), as it stands but for the timeline id
+    // (tl, diagnostics build only, -1 = none) and the one run-time argument of the programs, the sampling call's cfg.
     // Per-launch profiling (fql_profile_update): when set, the next launch carries these two events ON ITS DISPATCH
-    // (hipExtLaunchKernelGGL): their elapsed time is the dispatch's own begin-to-end time, the quantity a rocprofv3 kernel trace reports.
+    // (hipExtLaunchKernel): their elapsed time is the dispatch's own begin-to-end time, the quantity a rocprofv3 kernel trace reports.
     hipEvent_t prof_a = nullptr, prof_b = nullptr;
-    template <typename... Pm, typename... A>
-    void aql_record(void (*k)(Pm...), dim3 g, dim3 b, size_t l, A&&... a) {
-        AqlDispatch d;
-        d.fn = (const void*)k;
-        d.grid[0] = g.x; d.grid[1] = g.y; d.grid[2] = g.z;
-        d.block[0] = b.x; d.block[1] = b.y; d.block[2] = b.z;
-        d.lds = (uint32_t)l;
-        size_t off = 0;
-        auto put = [&](auto v) {   // kernarg layout: every argument at its natural alignment
-            using T = decltype(v);
-            off = (off + alignof(T) - 1) & ~(alignof(T) - 1);
-            d.args.resize(off + sizeof(T));
-            std::memcpy(d.args.data() + off, &v, sizeof(T));
-            off += sizeof(T);
-        };
-        (put(static_cast<Pm>(a)), ...);
-        aql_rec->push_back(std::move(d));
+    // the arguments of launch L as issued: a (FQL_BOUND_BYTES) receives L.k.args with tl and sample_cfg written
+    void issue_args(const Launch& L, int tl, unsigned char* a) const {
+        const Bound& k = L.k;
+        if (!k.fn) throw HipError{"internal: op type " + std::to_string((int)L.type) + " carries no bound launch"};
+        std::memcpy(a, k.args.data(), k.args.size());
+        if (k.tl_at >= 0) std::memcpy(a + k.tl_at, &tl, sizeof tl);
+        // a run-time float: the cached sampling program holds every other argument
+        if (L.type == OP_IQLD_CFG) std::memcpy(a + offsetof(IqldCfgStepArgs, cfg), &sample_cfg, sizeof sample_cfg);
     }
-#define FQL_LAUNCH(k, g, b, l, st, ...)                                                          \
-    do {                                                                                          \
-        if (aql_rec) aql_record(k, g, b, (size_t)(l), __VA_ARGS__);                               \
-        else if (prof_a) hipExtLaunchKernelGGL(k, g, b, (std::uint32_t)(l), st, prof_a, prof_b, 0u, __VA_ARGS__); \
-        else hipLaunchKernelGGL(k, g, b, l, st, __VA_ARGS__);                                     \
-    } while (0)
     void issue(const Launch& L, hipStream_t s, int tl) {
-        switch (L.type) {
-            case OP_GEMM:
-                if (L.euler && L.kbig) FQL_LAUNCH((fql_gemm16_euler_kernel<true>), dim3(L.grid), dim3(FQL_THREADS), L.lds, s, (const GemmTask*)L.table, L.ntasks, tl);
-                else if (L.euler) FQL_LAUNCH((fql_gemm16_euler_kernel<false>), dim3(L.grid), dim3(FQL_THREADS), L.lds, s, (const GemmTask*)L.table, L.ntasks, tl);
-                else if (L.kbig) FQL_LAUNCH((fql_gemm16_kernel<true>), dim3(L.grid), dim3(FQL_THREADS), L.lds, s, (const GemmTask*)L.table, L.ntasks, tl);
-                else FQL_LAUNCH((fql_gemm16_kernel<false>), dim3(L.grid), dim3(FQL_THREADS), L.lds, s, (const GemmTask*)L.table, L.ntasks, tl);
-                break;
-            case OP_GEMM64:   // the level's side-lane launch (schedule())
-                if (L.ka_side) {
-                    SideArgs a = *L.ka_side; a.f.tl = tl;
-                    if (L.tmt2) FQL_LAUNCH(fql_side_big_ka_kernel, dim3(L.grid), dim3(FQL_THREADS), L.lds, s, a);
-                    else if (cfg.precision == 2) FQL_LAUNCH(fql_side_split_ka_kernel, dim3(L.grid), dim3(FQL_THREADS), L.lds, s, a);
-                    else FQL_LAUNCH(fql_side_ka_kernel, dim3(L.grid), dim3(FQL_THREADS), L.lds, s, a);
-                }
-                else if (L.tmt2)
-                    FQL_LAUNCH(fql_side_big_kernel, dim3(L.grid), dim3(FQL_THREADS), L.lds, s, (const GemmTask*)L.table, L.ntasks,
-                                       (const WgradTask*)L.table_w, L.n_w, (const LnBwdTask*)L.table_l, L.n_l, L.tile_w, L.tile_l,
-                                       (const MiscTask*)L.table_m, L.tile_m, tl);
-                else if (cfg.precision == 2)
-                    FQL_LAUNCH(fql_side_split_kernel, dim3(L.grid), dim3(FQL_THREADS), L.lds, s, (const GemmTask*)L.table, L.ntasks,
-                                       (const WgradTask*)L.table_w, L.n_w, (const LnBwdTask*)L.table_l, L.n_l, L.tile_w, L.tile_l,
-                                       (const MiscTask*)L.table_m, L.tile_m, tl);
-                else
-                    FQL_LAUNCH(fql_side_kernel, dim3(L.grid), dim3(FQL_THREADS), L.lds, s, (const GemmTask*)L.table, L.ntasks,
-                                       (const WgradTask*)L.table_w, L.n_w, (const LnBwdTask*)L.table_l, L.n_l, L.tile_w, L.tile_l,
-                                       (const MiscTask*)L.table_m, L.tile_m, tl);
-                break;
-            case OP_PREP:
-                { PrepArgs pa = L.op.prep; pa.tl = tl; FQL_LAUNCH(fql_prep_kernel, dim3((pa.B + 3) / 4), dim3(FQL_THREADS), 0, s, pa); }
-                break;
-            case OP_EULER_FIN:
-                FQL_LAUNCH(fql_euler_finish_kernel, dim3((L.op.ef.M * L.op.ef.ad + FQL_THREADS - 1) / FQL_THREADS), dim3(FQL_THREADS), 0, s, L.op.ef);
-                break;
-            case OP_LOSS_ACTOR:
-                FQL_LAUNCH(fql_loss_actor_kernel, dim3(1), dim3(FQL_THREADS), 0, s, L.op.la);
-                break;
-            case OP_CONV_WPREP:
-                FQL_LAUNCH(fql_conv_wprep_kernel, dim3(4, L.op.wprep_n), dim3(FQL_THREADS), 0, s, L.op.wprep_tasks);
-                break;
-            case OP_CONV:
-                if (L.pool_fused && cfg.precision == 2) FQL_LAUNCH(fql_conv3x3_pool_split_kernel, dim3(L.grid), dim3(FQL_THREADS), L.lds, s, (const ConvArgs*)L.table, L.ntasks);
-                else if (L.pool_fused) FQL_LAUNCH(fql_conv3x3_pool_kernel, dim3(L.grid), dim3(FQL_THREADS), L.lds, s, (const ConvArgs*)L.table, L.ntasks);
-                else if (cfg.precision == 2) FQL_LAUNCH(fql_conv3x3_split_kernel, dim3(L.grid), dim3(FQL_THREADS), L.lds, s, (const ConvArgs*)L.table, L.ntasks);
-                else
-                FQL_LAUNCH(fql_conv3x3_kernel, dim3(L.grid), dim3(FQL_THREADS), L.lds, s, (const ConvArgs*)L.table, L.ntasks);
-                break;
-            case OP_CONV_U8:
-                if (L.pool_fused && cfg.precision == 2) FQL_LAUNCH(fql_conv3x3_pool_split_kernel, dim3(L.grid), dim3(FQL_THREADS), L.lds, s, (const ConvArgs*)L.table, L.ntasks);
-                else if (L.pool_fused) FQL_LAUNCH(fql_conv3x3_pool_kernel, dim3(L.grid), dim3(FQL_THREADS), L.lds, s, (const ConvArgs*)L.table, L.ntasks);
-                else if (cfg.precision == 2) FQL_LAUNCH(fql_conv3x3_u8_split_kernel, dim3(L.grid), dim3(FQL_THREADS), L.lds, s, (const ConvArgs*)L.table, L.ntasks);
-                else
-                FQL_LAUNCH(fql_conv3x3_u8_kernel, dim3(L.grid), dim3(FQL_THREADS), L.lds, s, (const ConvArgs*)L.table, L.ntasks);
-                break;
-            case OP_POOL: {
-                const PoolArgs& a = L.op.pool;
-                const size_t tot = (size_t)a.N * (a.H / 2) * (a.W / 2) * (a.C / 4);
-                FQL_LAUNCH(fql_maxpool_kernel, dim3((unsigned)((tot + FQL_THREADS - 1) / FQL_THREADS)), dim3(FQL_THREADS), 0, s, a);
-                break;
-            }
-            case OP_POOL_BWD: {
-                const PoolBwdArgs& a = L.op.poolb;
-                const size_t tot = (size_t)a.N * a.H * a.W * (a.C / 4);
-                FQL_LAUNCH(fql_maxpool_bwd_kernel, dim3((unsigned)((tot + FQL_THREADS - 1) / FQL_THREADS)), dim3(FQL_THREADS), 0, s, a);
-                break;
-            }
-            case OP_CONV_WGRAD:
-                if (cfg.precision == 2) FQL_LAUNCH(fql_conv_wgrad_split_kernel, dim3(L.grid), dim3(FQL_THREADS), L.lds, s, (const ConvWgradArgs*)L.table, L.ntasks);
-                else
-                FQL_LAUNCH(fql_conv_wgrad_kernel, dim3(L.grid), dim3(FQL_THREADS), L.lds, s, (const ConvWgradArgs*)L.table, L.ntasks);
-                break;
-            case OP_CONV_WRED:
-                FQL_LAUNCH(fql_conv_wgrad_reduce_kernel, dim3(L.grid), dim3(FQL_THREADS), 0, s, (const ConvWredArgs*)L.table, L.ntasks);
-                break;
-            case OP_ENC_DZ: {
-                const EncDzArgs& a = L.op.edz;
-                FQL_LAUNCH(fql_enc_dz_kernel, dim3((a.M * a.n + FQL_THREADS - 1) / FQL_THREADS), dim3(FQL_THREADS), 0, s, a);
-                break;
-            }
-            case OP_CHAIN: {
-                ChainArgs ca = L.op.chain; ca.tl = tl;
-                ca.xg = chain_xg(ca.M, cfg.actor_hidden[0]);
-                if (cfg.precision == 2 && ca.variant != 3) {   // (variant D keeps fp32 operands: its dZ / W arrive as fp32 and splitting both in the kernel costs what the MFMAs save)
-#define FQL_CHAIN_SPLIT(HH, VV) FQL_LAUNCH((fql_chain_split_kernel<HH, VV>), dim3((L.op.chain.M / 16) * (HH / 32)), dim3(FQL_CHAIN_THREADS), FQL_CHAIN_LDS_BYTES(HH), s, ca)
-                    if (cfg.actor_hidden[0] == 512) { if (ca.variant == 0) FQL_CHAIN_SPLIT(512, 0); else if (ca.variant == 1) FQL_CHAIN_SPLIT(512, 1); else FQL_CHAIN_SPLIT(512, 2); }
-                    else { if (ca.variant == 0) FQL_CHAIN_SPLIT(256, 0); else if (ca.variant == 1) FQL_CHAIN_SPLIT(256, 1); else FQL_CHAIN_SPLIT(256, 2); }
-#undef FQL_CHAIN_SPLIT
-                }
-                else {
-#define FQL_CHAIN_F32(HH, VV) FQL_LAUNCH((fql_chain_kernel<HH, VV>), dim3((L.op.chain.M / 16) * (HH / 32)), dim3(FQL_CHAIN_THREADS), FQL_CHAIN_LDS_BYTES(HH), s, ca)
-                    if (cfg.actor_hidden[0] == 512) { if (ca.variant == 0) FQL_CHAIN_F32(512, 0); else if (ca.variant == 1) FQL_CHAIN_F32(512, 1); else if (ca.variant == 2) FQL_CHAIN_F32(512, 2); else FQL_CHAIN_F32(512, 3); }
-                    else { if (ca.variant == 0) FQL_CHAIN_F32(256, 0); else if (ca.variant == 1) FQL_CHAIN_F32(256, 1); else if (ca.variant == 2) FQL_CHAIN_F32(256, 2); else FQL_CHAIN_F32(256, 3); }
-#undef FQL_CHAIN_F32
-                }
-                break;
-            }
-            case OP_WFRAG:
-                FQL_LAUNCH(fql_wfrag_kernel, dim3(wfrag_grid), dim3(FQL_THREADS), 0, s, (const WfragTask*)d_wfrag, wfrag_n, tl);
-                break;
-            case OP_DGRAD0: {
-                Dgrad0Args a{};
-                a.ntasks = (int)L.dg_tasks.size(); a.col0 = L.op.gemm.i1;
-                for (int i = 0; i < a.ntasks; ++i) a.t[i] = L.dg_tasks[i];
-                FQL_LAUNCH(fql_dgrad0_kernel, dim3(a.ntasks * (L.op.gemm.M / 16)), dim3(FQL_THREADS), 0, s, a);
-                break;
-            }
-            case OP_HEAD_DGRAD:
-                FQL_LAUNCH(fql_head_dgrad_kernel, dim3((L.op.gemm.M / 16) * (L.op.gemm.N / 64)), dim3(FQL_THREADS), 0, s, L.op.gemm);
-                break;
-            case OP_ADAM: {
-                AdamArgs a{P, G, Mu, Nu, P + n_train, d_chunks, L.op.adam_st ? L.op.adam_st : d_state, d_partials, L.op.adam_c0,
-                           L.op.adam_polyak >= 0 ? L.op.adam_polyak : (int)critic_size, L.op.adam_lr > 0.f ? L.op.adam_lr : cfg.lr, cfg.tau, tl,
-                           L.op.adam_n1 > 0 ? L.op.adam_n : -1, L.op.adam_c1};
-                if (L.op.adam_fin) {
-                    a.ticket = d_ticket;
-                    a.ticket_n = n_chunks;
-                    a.fin = FinalizeArgs{d_state, d_chunks, d_partials, d_leaf_range, n_chunks, n_train_leaves, L.op.fin_mode, -1};
-                }
-                FQL_LAUNCH(fql_adam_kernel, dim3(L.op.adam_n < 0 ? n_chunks : L.op.adam_n + L.op.adam_n1), dim3(FQL_THREADS), 0, s, a);
-                break;
-            }
-            case OP_FINALIZE:
-                FQL_LAUNCH(fql_finalize_kernel, dim3(1), dim3(FQL_THREADS), 0, s,
-                                   FinalizeArgs{d_state, d_chunks, d_partials, d_leaf_range, n_chunks, n_train_leaves, L.op.fin_mode, tl});
-                break;
-            case OP_WGRAD: case OP_LNBWD: case OP_POSTOS: case OP_LOSS_CRITIC: case OP_LOSS_Q: case OP_LOSS_BC:   // (inside OP_GEMM64 launches)
-            case OP_PEC: case OP_XCHAIN: case OP_NUM_TYPES:
-                throw HipError{"internal: op type " + std::to_string((int)L.type) + " has no launch of its own"};
-            default: {   // every agent op (OP_IFQL_PREP and later): the launch its emit site bound
-                const Bound& k = L.op.k;
-                if (!k.fn) throw HipError{"internal: op type " + std::to_string((int)L.type) + " carries no bound launch"};
-                alignas(16) unsigned char a[FQL_BOUND_BYTES];
-                std::memcpy(a, k.args, (size_t)k.len);
-                if (k.tl_at >= 0) std::memcpy(a + k.tl_at, &tl, sizeof tl);
-                // a run-time float: the cached sampling program holds every other argument
-                if (L.type == OP_IQLD_CFG) std::memcpy(a + offsetof(IqldCfgStepArgs, cfg), &sample_cfg, sizeof sample_cfg);
-                void* argv[2] = {a + k.at[0], a + k.at[1]};
-                if (aql_rec) aql_rec->push_back(AqlDispatch{k.fn, {k.grid, 1, 1}, {FQL_THREADS, 1, 1}, 0, std::vector<uint8_t>(a, a + k.len)});
-                else if (prof_a) (void)hipExtLaunchKernel(k.fn, dim3(k.grid), dim3(FQL_THREADS), argv, 0, s, prof_a, prof_b, 0);
-                else (void)hipLaunchKernel(k.fn, dim3(k.grid), dim3(FQL_THREADS), argv, 0, s);
-                break;
-            }
-        }
+        alignas(16) unsigned char a[FQL_BOUND_BYTES];
+        issue_args(L, tl, a);
+        launch_bound(L.k, a, s, prof_a, prof_b);
     }
-
-#undef FQL_LAUNCH
-    // issue() of a launch of `pr` (timeline ids, diagnostics build only: the launches of prog_full)
-    void issue_of(const Program& pr, const Launch& L, hipStream_t s) {
-        issue(L, s, &pr == &prog_full ? (int)(&L - pr.launches.data()) : -1);
-    }
+    // the timeline id of a launch of `pr` (diagnostics build only: the launches of prog_full)
+    int tl_of(const Program& pr, const Launch& L) const { return &pr == &prog_full ? (int)(&L - pr.launches.data()) : -1; }
     // a program's launches through issue_lanes (ls == nullptr: every launch on s0), logged under FQL_TRACE
     void run_launches(Program& pr, hipStream_t s0, const hipStream_t* ls = nullptr, bool fork = true) {
         static const bool trace_l = getenv("FQL_TRACE") != nullptr;
@@ -2451,19 +2381,19 @@ struct fql_engine {
                 for (int w : L.waits) fprintf(stderr, " %d(lane %d)", w, pr.launches[w].lane);
                 fprintf(stderr, "\n");
             }
-            issue_of(pr, L, s);
+            issue(L, s, tl_of(pr, L));
         });
     }
-    // what issue() dispatches for each launch of `pr`, in order, recorded instead of launched
-    std::vector<AqlDispatch> record_dispatches(const Program& pr) {
-        std::vector<AqlDispatch> rec;
-        aql_rec = &rec;
-        try {
-            for (const Launch& L : pr.launches) issue_of(pr, L, nullptr);
-        } catch (...) { aql_rec = nullptr; throw; }
-        aql_rec = nullptr;
-        if (rec.size() != pr.launches.size()) throw HipError{"internal: a launch did not record exactly one dispatch"};
-        return rec;
+    // what issue() hands to the runtime for each launch of `pr`, in order, as the AQL path takes it (fql_aql.h): a plain copy of Launch::k
+    std::vector<AqlDispatch> dispatches(const Program& pr) const {
+        std::vector<AqlDispatch> out;
+        alignas(16) unsigned char a[FQL_BOUND_BYTES];
+        for (const Launch& L : pr.launches) {
+            issue_args(L, tl_of(pr, L), a);
+            const Bound& k = L.k;
+            out.push_back(AqlDispatch{k.fn, {k.grid[0], k.grid[1], k.grid[2]}, {k.block[0], k.block[1], k.block[2]}, k.lds, std::vector<uint8_t>(a, a + k.args.size())});
+        }
+        return out;
     }
 
     // The program as AQL packet templates for the engine's own HSA queues (fql_aql.h): one queue per lane, the barrier bit inside a lane,
@@ -2479,7 +2409,7 @@ struct fql_engine {
         try {
             if (!aql.up && aql.why.empty()) aql.init(device, (const void*)&fql_create);
             if (!aql.up) throw AqlError{aql.why};
-            const std::vector<AqlDispatch> rec = record_dispatches(pr);
+            const std::vector<AqlDispatch> rec = dispatches(pr);
             const size_t n = pr.launches.size();
 
             std::vector<const AqlKernelInfo*> ki(n);
@@ -2655,22 +2585,23 @@ struct fql_engine {
         {   // batch gather + noise + every network input
             Op op{};
             op.type = OP_PREP;
-            op.prep = PrepArgs{d_src, st, seed, B, od, ad, inp_c, inp_b, ap, X_os, X_bc, X_eu, X_c1, X_c2, X_ct, vel, w_rew, w_mask, w_act,
-                               fused_euler ? X_e0 : nullptr, nullptr, nullptr, nullptr, nullptr};
-            op.prep.tl = -1; op.prep.part = 0;
+            PrepArgs pa{d_src, st, seed, B, od, ad, inp_c, inp_b, ap, X_os, X_bc, X_eu, X_c1, X_c2, X_ct, vel, w_rew, w_mask, w_act,
+                        fused_euler ? X_e0 : nullptr, nullptr, nullptr, nullptr, nullptr};
+            pa.tl = -1; pa.part = 0;
+            auto bound = [&](int part) { pa.part = part; return tl_in(bind(fql_prep_kernel, (pa.B + 3) / 4, pa), offsetof(PrepArgs, tl)); };
             // One batch-assembly launch per lane (state agents): the side lane then has no dependency on the critical lane at the
             // start of the update.  (On this runtime a graph branch whose first node waits for a node of the other branch starts
             // only ~16 launches of that branch later: profiles/r02_timeline_concurrent.txt.)
             if (visual) {
-                op.prep.E_c = eb_c.E; op.prep.E_t = eb_t.E; op.prep.E_bc = eb_bc.E; op.prep.E_os = eb_os.E;
+                pa.E_c = eb_c.E; pa.E_t = eb_t.E; pa.E_bc = eb_bc.E; pa.E_os = eb_os.E;
                 op.reads = {eb_c.E, eb_t.E, eb_bc.E, eb_os.E};
             }
             if (!visual && !split_build) {
                 Op a = op, b = op;
-                a.prep.part = 1;
+                a.k = bound(1);
                 a.writes = {X_eu};
                 if (fused_euler) a.writes.push_back(X_e0);
-                b.prep.part = 2;
+                b.k = bound(2);
                 b.writes = {X_os, X_bc, X_c1, X_c2, X_ct, vel, w_rew, w_mask, w_act};
                 emit_lane = 0; push(pr, a);
                 emit_lane = 1; push(pr, b);
@@ -2678,6 +2609,7 @@ struct fql_engine {
             } else {
                 op.writes = {X_os, X_bc, X_eu, X_c1, X_c2, X_ct, vel, w_rew, w_mask, w_act};
                 if (fused_euler) op.writes.push_back(X_e0);
+                op.k = bound(0);
                 push(pr, op);
             }
         }
@@ -2807,9 +2739,9 @@ struct fql_engine {
             Op op{};
             op.type = OP_LOSS_ACTOR;
             const bool kgrad = with_grads && !fuse_la;
-            op.la = LossActorArgs{p_os.out + (size_t)B * ap, tgt, kgrad ? p_c2[0].dx0 : nullptr,
-                                  kgrad ? p_c2[1].dx0 : nullptr, kgrad ? p_os_bwd.dz.back() : nullptr, st, B, od, ad,
-                                  inp_c, ap, kgrad ? 1 : 0, cfg.alpha};
+            op.k = bind(fql_loss_actor_kernel, 1, LossActorArgs{p_os.out + (size_t)B * ap, tgt, kgrad ? p_c2[0].dx0 : nullptr,
+                                                                kgrad ? p_c2[1].dx0 : nullptr, kgrad ? p_os_bwd.dz.back() : nullptr, st, B, od, ad,
+                                                                inp_c, ap, kgrad ? 1 : 0, cfg.alpha});
             op.reads = {p_os.out, tgt, I_BC, I_Q};
             op.writes = {I_ACT};
             if (kgrad) {
@@ -2867,6 +2799,7 @@ struct fql_engine {
                     for (const void* r : {(const void*)Abuf[(fs - 1) & 1], (const void*)Vpart, (const void*)(P + nb.layers[nb.nl() - 1].w)}) d.reads.push_back(r);   // (head bias: WAR against Adam)
                     d.writes.push_back(tgt);
                 }
+                if (d.type == OP_HEAD_DGRAD) d.k = bind(fql_head_dgrad_kernel, (t.M / 16) * (t.N / 64), t);   // (the task is complete only here)
             }
             if (euler_finish_fused) {   // the metric kernel reads the target the head dgrad has just written
                 const int keep = emit_lane;
@@ -2891,30 +2824,33 @@ struct fql_engine {
                 emit_encoder_backward(pr, eb_bc, 0, B, p_bc.dx0, nullptr, nets[NET_BC].in_p(), p_os_bwd.dx0);
             }
         }
-        if (!with_grads) {
-            Op op{};
-            op.type = OP_FINALIZE;
-            op.fin_mode = 0;
-            op.reads = {I_CR, I_BC, I_Q, I_MSE, I_ACT};
-            op.writes = {INFO};
-            push(pr, op);
-        }
+        if (!with_grads) emit(pr, OP_FINALIZE, finalize_launch(0), {I_CR, I_BC, I_Q, I_MSE, I_ACT}, {INFO});
     }
 
     // Adam (+ Polyak for the critic) of one module (0 BC flow, 1 one-step actor, 2 critic) as its own launch on `lane`
-    // m2 >= 0: a second module (its nets in net_ids as well) rides in the same launch
-    void adam_for(Program& pr, int m, std::initializer_list<int> net_ids, int lane, int m2 = -1) {
-        DevState* st = d_state;
+    // m2 >= 0: a second module (its nets in net_ids as well) rides in the same launch; m2 == -2: every chunk.
+    // Everything the arguments read (the arenas, chunk tables, counters, ticket) is allocated before the first program is built and freed
+    // by fql_destroy alone.  The reference is for the sites that append reads or writes (it holds until the next op is pushed).
+    Op& adam_for(Program& pr, int m, std::initializer_list<int> net_ids, int lane, int m2 = -1, AdamOpt o = AdamOpt{}) {
+        DevState* st = o.st ? o.st : d_state;
             Op a{};
             a.type = OP_ADAM;
-            a.adam_c0 = mod_chunk0[m]; a.adam_n = mod_chunkn[m];
+            int c0 = mod_chunk0[m], n0 = mod_chunkn[m], c1 = 0, n1 = 0;   // chunk ranges (n0 = -1: all chunks; n1 = 0: no second range)
             a.reads = {st};
             a.writes = {d_partials + mod_chunk0[m] * 4};
-            if (m2 >= 0) { a.adam_c1 = mod_chunk0[m2]; a.adam_n1 = mod_chunkn[m2]; a.writes.push_back(d_partials + mod_chunk0[m2] * 4); }
+            if (m2 >= 0) { c1 = mod_chunk0[m2]; n1 = mod_chunkn[m2]; a.writes.push_back(d_partials + mod_chunk0[m2] * 4); }
             if (m2 == -2) {   // all chunks (the modules' ranges tile [0, n_chunks))
-                a.adam_c0 = 0; a.adam_n = -1;
+                c0 = 0; n0 = -1;
                 for (int mm = 0; mm < 3; ++mm) a.writes.push_back(d_partials + mod_chunk0[mm] * 4);
             }
+            AdamArgs aa{P, G, Mu, Nu, P + n_train, d_chunks, st, d_partials, c0, o.polyak >= 0 ? o.polyak : (int)critic_size,
+                        o.lr > 0.f ? o.lr : cfg.lr, cfg.tau, -1, n1 > 0 ? n0 : -1, c1};
+            if (o.fin) {
+                aa.ticket = d_ticket;
+                aa.ticket_n = n_chunks;
+                aa.fin = fin_args(1);   // (its tl stays -1: the launch's own id is AdamArgs::tl)
+            }
+            a.k = tl_in(bind(fql_adam_kernel, n0 < 0 ? n_chunks : n0 + n1, aa), offsetof(AdamArgs, tl));
             // the critic's Adam, the first launch of lane 2's tail, also waits for the Euler target the actor-loss kernel behind it reads -
             // one launch with two cross-lane edges instead of two launches with one each (every such edge costs the waiting lane ~10 us)
             if (m == 2 && tgt) a.reads.push_back(tgt);
@@ -2941,7 +2877,12 @@ struct fql_engine {
                 }
             emit_lane = lane;
             push(pr, a);
+            return pr.ops.back();
         }
+    // the FQL programs' finalize launch (do_grad_stats: behind an optimizer pass)
+    Bound finalize_launch(int do_grad_stats) const {
+        return tl_in(bind(fql_finalize_kernel, 1, fin_args(do_grad_stats)), offsetof(FinalizeArgs, tl));
+    }
 
     // The optimizer half of the begin / end pair (data-parallel step: gradients are all-reduced between the halves): per-module Adam
     // as in the fused program - critic and BC flow (gradient bucket 0) + the chain's weight-copy refresh on lane 1, the one-step
@@ -2960,14 +2901,8 @@ struct fql_engine {
             adam_for(pr, 2, {NET_C0, NET_C1, NET_BC, NET_OS}, 0, -2);
             if (use_chain) { emit_lane = 0; emit_wfrag(pr); }
         }
-        Op f{};
-        f.type = OP_FINALIZE;
-        f.fin_mode = 1;
-        f.reads = {d_partials + mod_chunk0[0] * 4, d_partials + mod_chunk0[1] * 4, d_partials + mod_chunk0[2] * 4, &st->info[0],
-                   &st->info[4], &st->info[5], &st->info[7], &st->info[9]};
-        f.writes = {&st->info[10], st};
-        emit_lane = 0;
-        push(pr, f);
+        emit_fin(pr, OP_FINALIZE, finalize_launch(1), offsetof(FinalizeArgs, tl), {&st->info[0], &st->info[4], &st->info[5], &st->info[7], &st->info[9]}, true,
+                 {&st->info[10], st});
     }
     // the optimizer program as plain launches on two caller streams (no capture: five launches)
     void run_opt_split(hipStream_t s0, hipStream_t s1) {
@@ -2988,35 +2923,28 @@ struct fql_engine {
         DevState* st = d_state;
         // the critic's and the BC flow's Adam as ONE launch (rather than two): both sit at the end of the same lane behind the same
         // dependencies, and every graph node costs the host 3-4 us
-        adam_for(pr, 2, {NET_C0, NET_C1, NET_BC}, fill_lane_full, 0);
-        emit_wfrag(pr);   // lane 1, behind the BC flow's Adam: the next update's chain reads the copies
-        adam_for(pr, 1, {NET_OS}, 0);
+        // No finalize launch by default: the two Adam launches below cover every chunk once, each of their workgroups takes a ticket, and the
+        // workgroup that takes the last one runs the finalize code (fql_adam_body).  That workgroup may sit in either launch, so the
+        // ops keep their own read and write sets and no edge joins the lanes: the ticket, not the schedule, puts the counters'
+        // update behind their last reader.  Nothing behind the two launches reads the counters or the infos (the weight-copy
+        // refresh does not), and the update ends behind every lane.
         // (the modules' chunk ranges tile [0, n_chunks): were a leaf outside the three trained modules, the ticket would never complete)
-        if (fused_tail && mod_chunkn[0] + mod_chunkn[1] + mod_chunkn[2] == n_chunks) {
-            // No finalize launch: the two Adam launches above cover every chunk once, each of their workgroups takes a ticket, and the
-            // workgroup that takes the last one runs the finalize code (fql_adam_body).  That workgroup may sit in either launch, so the
-            // ops keep their own read and write sets and no edge joins the lanes: the ticket, not the schedule, puts the counters'
-            // update behind their last reader.  Nothing behind the two launches reads the counters or the infos (the weight-copy
-            // refresh does not), and the update ends behind every lane.
-            for (Op& o : pr.ops) if (o.type == OP_ADAM) { o.adam_fin = true; o.fin_mode = 1; }
-            return;
-        }
-        Op f{};
-        f.type = OP_FINALIZE;
-        f.fin_mode = 1;
-        f.reads = {d_partials + mod_chunk0[0] * 4, d_partials + mod_chunk0[1] * 4, d_partials + mod_chunk0[2] * 4, &st->info[0],
-                   &st->info[4], &st->info[5], &st->info[7], &st->info[9]};
-        f.writes = {&st->info[10], st};
-        emit_lane = 0;
-        push(pr, f);
+        AdamOpt tail;
+        tail.fin = fused_tail && mod_chunkn[0] + mod_chunkn[1] + mod_chunkn[2] == n_chunks;
+        adam_for(pr, 2, {NET_C0, NET_C1, NET_BC}, fill_lane_full, 0, tail);
+        emit_wfrag(pr);   // lane 1, behind the BC flow's Adam: the next update's chain reads the copies
+        adam_for(pr, 1, {NET_OS}, 0, -1, tail);
+        if (tail.fin) return;
+        emit_fin(pr, OP_FINALIZE, finalize_launch(1), offsetof(FinalizeArgs, tl), {&st->info[0], &st->info[4], &st->info[5], &st->info[7], &st->info[9]}, true,
+                 {&st->info[10], st});
     }
 
-    // FinalizeArgs of an agent's *_FIN op.  Every field is allocated before the first program is built (build_leaves, create_engine)
+    // FinalizeArgs of a finalize launch, or of the finalize code inside an Adam launch.  Every field is allocated before the first program is built (build_leaves, create_engine)
     // and freed by fql_destroy alone, so the emit site binds it like any other argument; tl is written at issue time (Bound::tl_at).
     FinalizeArgs fin_args(int do_grad_stats) const {
         return FinalizeArgs{d_state, d_chunks, d_partials, d_leaf_range, n_chunks, n_train_leaves, do_grad_stats, -1};
     }
-    // An agent's finalize op, on lane 0.  tl_at: where the bound arguments hold FinalizeArgs::tl (-1: the kernel takes none);
+    // A finalize op (OP_FINALIZE or an agent's *_FIN), on lane 0.  tl_at: where the bound arguments hold FinalizeArgs::tl (-1: the kernel takes none);
     // grad_partials: it also reads the three modules' gradient partials the Adam launch left.
     void emit_fin(Program& pr, OpType type, Bound k, int tl_at, std::vector<const void*> reads, bool grad_partials, std::vector<const void*> writes) {
         k.tl_at = tl_at;
@@ -3185,10 +3113,10 @@ struct fql_engine {
         for (int e = 0; e < 2; ++e) emit_backward(pr, p_c1[e], 0, B, true, false);
         // every chunk in one launch (the actor's too: on a critic-only step Adam still moves it with a zero gradient); Polyak from the
         // pre-step critic and actor on full steps only (rebrac.py:112-120,131-133)
-        adam_for(pr, 0, {NET_C0, NET_C1, NET_BC}, 0, -2);
-        Op& a = pr.ops.back();
+        AdamOpt ao;
+        if (!full_update) ao.polyak = 0;
+        Op& a = adam_for(pr, 0, {NET_C0, NET_C1, NET_BC}, 0, -2, ao);
         if (full_update) for (const Layer& L : na.layers) a.writes.push_back(P + n_train + L.w);   // the target actor
-        else a.adam_polyak = 0;
         emit_fin(pr, OP_REBRAC_FIN, bind(fql_rebrac_finalize_kernel, 1, fin_args(1), full_update ? 1 : 0), offsetof(FinalizeArgs, tl), {I_C, I_A},
                  true, {&st->info[8], st});
     }
@@ -3626,17 +3554,17 @@ struct fql_engine {
             }
         }
         if (gc) {
-            adam_for(pr, 2, {NET_C0, NET_C1}, 0);          // critic_lr; Polyak from the pre-step critic (:230)
-            pr.ops.back().adam_lr = dcfg.critic_lr;
-            adam_for(pr, 1, {NET_OS}, 0);                  // value_lr
-            pr.ops.back().adam_lr = dcfg.value_lr;
+            AdamOpt ao;
+            ao.lr = dcfg.critic_lr;
+            adam_for(pr, 2, {NET_C0, NET_C1}, 0, -1, ao);  // critic_lr; Polyak from the pre-step critic (:230)
+            ao.lr = dcfg.value_lr;
+            adam_for(pr, 1, {NET_OS}, 0, -1, ao);          // value_lr
         }
         if (ga) {
-            adam_for(pr, 0, {NET_BC}, 0);                  // actor_lr, the actor TrainState's own count
-            Op& a = pr.ops.back();
-            a.adam_lr = dcfg.actor_lr;
-            a.adam_st = d_state_a;
-            a.reads[0] = d_state_a;
+            AdamOpt ao;
+            ao.lr = dcfg.actor_lr;
+            ao.st = d_state_a;                             // the actor TrainState's own count
+            Op& a = adam_for(pr, 0, {NET_BC}, 0, -1, ao);
             a.reads.push_back(G + emb_off);
             a.writes.push_back(P + emb_off);
         }
@@ -6115,7 +6043,7 @@ extern "C" int fql_debug_enc(fql_handle h, int enc, int code, void* out, size_t 
 }
 
 // Diagnostic only (not in include/fql_amd.h): what the update program (prog_full) of a state agent will launch, as int32 words.  Nothing is
-// launched and no state changes: the launches come from record_dispatches (issue() recording what it would hand to the runtime), the tasks
+// launched and no state changes: the launches are what schedule() and the emit sites bound (Launch::k, what issue() hands to the runtime), the tasks
 // from the host copies of the tables schedule() uploaded.  Layout:
 //   [words in the plan (this one included), launches], then per launch
 //   [index, lane, op type, grid (workgroups), kernel entry, GEMM tasks g, weight-gradient tasks w, LayerNorm-backward tasks l, chain records c (0 / 1)]
@@ -6132,7 +6060,7 @@ namespace {
 enum { PLAN_K_OTHER = 0, PLAN_K_GEMM16, PLAN_K_GEMM16_KBIG, PLAN_K_GEMM16_EULER, PLAN_K_GEMM16_EULER_KBIG, PLAN_K_SIDE, PLAN_K_SIDE_SPLIT, PLAN_K_SIDE_BIG,
        PLAN_K_CHAIN, PLAN_K_CHAIN_SPLIT };
 struct PlanKernel { const void* fn; int entry, H, V; };
-template <typename... Pm> const void* plan_fn(void (*k)(Pm...)) { return (const void*)k; }   // the address issue() records (aql_record)
+template <typename... Pm> const void* plan_fn(void (*k)(Pm...)) { return (const void*)k; }   // the address a launch binds (Bound::fn)
 const std::vector<PlanKernel>& plan_kernels() {
 #define FQL_PLAN_CHAIN(HH) \
     {plan_fn(fql_chain_kernel<HH, 0>), PLAN_K_CHAIN, HH, 0}, {plan_fn(fql_chain_kernel<HH, 1>), PLAN_K_CHAIN, HH, 1},                    \
@@ -6156,18 +6084,17 @@ extern "C" int fql_debug_plan(fql_handle h, void* out, size_t bytes) {
     if (h->visual || !h->prog_full.exec || h->prog_full.launches.empty()) return FQL_E_STATE;
     try {
         const Program& pr = h->prog_full;
-        const std::vector<AqlDispatch> rec = h->record_dispatches(pr);
         std::vector<int32_t> plan{0, (int32_t)pr.launches.size()};
         for (size_t i = 0; i < pr.launches.size(); ++i) {
             const Launch& L = pr.launches[i];
-            const AqlDispatch& d = rec[i];
+            const Bound& d = L.k;
             PlanKernel k{d.fn, PLAN_K_OTHER, 0, 0};
             for (const PlanKernel& c : plan_kernels()) if (c.fn == d.fn) k = c;
             const bool table = L.type == OP_GEMM || L.type == OP_GEMM64;   // (other launches keep no task table)
             const bool chain = L.type == OP_CHAIN;
-            if (chain != (k.entry == PLAN_K_CHAIN || k.entry == PLAN_K_CHAIN_SPLIT)) throw HipError{"internal: a chain launch records an unknown kernel"};
-            if (table == (k.entry == PLAN_K_OTHER || chain)) throw HipError{"internal: a GEMM launch records an unknown kernel"};
-            plan.insert(plan.end(), {(int32_t)i, L.lane, (int32_t)L.type, (int32_t)(d.grid[0] * d.grid[1] * d.grid[2]), k.entry,
+            if (chain != (k.entry == PLAN_K_CHAIN || k.entry == PLAN_K_CHAIN_SPLIT)) throw HipError{"internal: a chain launch binds an unknown kernel"};
+            if (table == (k.entry == PLAN_K_OTHER || chain)) throw HipError{"internal: a GEMM launch binds an unknown kernel"};
+            plan.insert(plan.end(), {(int32_t)i, L.lane, (int32_t)L.type, (int32_t)d.workgroups(), k.entry,
                                      table ? (int32_t)L.h_gemm.size() : 0, table ? (int32_t)L.h_wgrad.size() : 0, table ? (int32_t)L.h_ln.size() : 0,
                                      chain ? 1 : 0});
             if (table) {
@@ -6177,7 +6104,7 @@ extern "C" int fql_debug_plan(fql_handle h, void* out, size_t bytes) {
             }
             if (chain) {
                 ChainArgs ca;
-                if (d.args.size() < sizeof(ChainArgs)) throw HipError{"internal: a chain launch records no ChainArgs"};
+                if (d.args.size() < sizeof(ChainArgs)) throw HipError{"internal: a chain launch binds no ChainArgs"};
                 std::memcpy(&ca, d.args.data(), sizeof(ChainArgs));
                 plan.insert(plan.end(), {ca.M, k.H, k.V, ca.xg, k.entry == PLAN_K_CHAIN_SPLIT ? 1 : 0});
             }
@@ -6253,9 +6180,9 @@ int fql_update_from_frames(fql_handle h, const int64_t* idx, const int32_t* crop
 // ================================================================================================
 namespace {
 
-typedef void (*MultiLaunch)(dim3 g, dim3 b, size_t lds, hipStream_t s, const void* args);
+typedef Bound (*MultiBind)(Geo g, const void* args);   // the multi-instance kernel bound over a device array of argument structs
 struct MultiEntry {
-    MultiLaunch launch;
+    MultiBind bind;
     size_t arg_bytes;
 };
 // single-instance kernel -> its multi-instance entry point
@@ -6263,7 +6190,7 @@ const std::map<const void*, MultiEntry>& multi_entries() {
     static const std::map<const void*, MultiEntry> m = [] {
         std::map<const void*, MultiEntry> e;
 #define FQL_MULTI(single, multi, A) \
-    e[(const void*)(single)] = MultiEntry{[](dim3 g, dim3 b, size_t l, hipStream_t s, const void* a) { hipLaunchKernelGGL(multi, g, b, l, s, (const A*)a); }, sizeof(A)}
+    e[(const void*)(single)] = MultiEntry{[](Geo g, const void* a) { return bind(multi, g, (const A*)a); }, sizeof(A)}
         FQL_MULTI(fql_prep_kernel, fql_prep_multi_kernel, PrepArgs);
         FQL_MULTI(fql_loss_actor_kernel, fql_loss_actor_multi_kernel, LossActorArgs);
         FQL_MULTI(fql_euler_finish_kernel, fql_euler_finish_multi_kernel, EulerFinishArgs);
@@ -6292,12 +6219,10 @@ struct GLaunch {
     std::vector<int> waits;
     bool record_after = false;
     hipEvent_t ev = nullptr;
-    bool table = false;
-    Launch L;                   // table-driven: the fused launch (tables, counts, grid), issued like a member's own
-    MultiLaunch multi = nullptr;   // argument-struct: the multi-instance kernel, its grid (y = member), LDS and [K] argument structs
-    dim3 grid, block;
-    size_t lds = 0;
-    void* args = nullptr;
+    int form = 0;   // fql_debug_task_forms' word
+    // table-driven: the launch over the members' concatenated tables, bound like a member's own; argument-struct: the kernel's
+    // multi-instance entry point, grid y = member, over the [K] argument structs in device memory
+    Bound k;
 };
 
 }  // namespace
@@ -6322,90 +6247,83 @@ struct fql_group_s {
         if (bytes) HIP_CHECK(hipMemcpy(d, src, bytes, hipMemcpyHostToDevice));
         return d;
     }
-    // the members' task tables one after the other, each member's tile0 shifted by `shift[member]` (MiscTask: no tile0, no shift)
+    // the members' task tables (their host copies) one after the other into `all` and onto the device, each member's tile0 shifted by
+    // `shift[member]` (MiscTask: no tile0, no shift)
     template <typename T>
-    void* fuse(const std::vector<const void*>& tables, const std::vector<int>& counts, const std::vector<int>& shift, std::vector<T>& all, bool rebase = true) {
+    void* fuse(const std::vector<const std::vector<T>*>& tables, const std::vector<int>& shift, std::vector<T>& all) {
         all.clear();
-        for (size_t i = 0; i < tables.size(); ++i) {
-            std::vector<T> h((size_t)counts[i]);
-            if (counts[i]) HIP_CHECK(hipMemcpy(h.data(), tables[i], (size_t)counts[i] * sizeof(T), hipMemcpyDeviceToHost));
-            if (rebase) for (T& t : h) rebase_tile0(t, shift[i]);
-            all.insert(all.end(), h.begin(), h.end());
-        }
+        for (size_t i = 0; i < tables.size(); ++i)
+            for (T t : *tables[i]) { rebase_tile0(t, shift[i]); all.push_back(t); }
         return upload(all.data(), all.size() * sizeof(T));
     }
     template <typename T> static void rebase_tile0(T& t, int d) { t.tile0 += d; }
     static void rebase_tile0(MiscTask&, int) {}   // (indexed by workgroup - tile_m: concatenation is the rebase)
 
-    // one fused launch from launch `li` of every member's prog_full; `rec[k]` = what member k's issue() would dispatch
-    GLaunch zip(int li, const std::vector<AqlDispatch>& rec) {
+    // one fused launch from launch `li` of every member's prog_full
+    GLaunch zip(int li) {
         const Launch& L0 = m[0]->prog_full.launches[li];
         GLaunch G;
         G.lane = L0.lane; G.waits = L0.waits; G.record_after = L0.record_after;
         if (is_table_launch(L0.type)) {
-            G.table = true;
-            Launch F = L0;
-            F.ev = nullptr; F.waits.clear();
-            F.ka_side = nullptr;   // (member 0's: the fused launch takes the form ITS task counts allow)
-            std::vector<WfragTask> h_wf;
-            std::vector<const void*> tg, tw, tl, tm;
-            std::vector<int> ng, nw, nl, nm, sg, sw, sl, sm;
-            int cg = 0, cw = 0, cl = 0, cm = 0, ntot = 0;
+            Launch F;   // bound by the family's helper of schedule(): the fused launch takes the form ITS task counts allow
+            F.type = L0.type;
+            std::vector<const std::vector<GemmTask>*> tg;
+            std::vector<const std::vector<WgradTask>*> tw;
+            std::vector<const std::vector<LnBwdTask>*> tl;
+            std::vector<const std::vector<MiscTask>*> tm;
+            std::vector<const std::vector<WfragTask>*> tf;
+            std::vector<int> sg, sw, sl, sm;
+            int cg = 0, cw = 0, cl = 0, cm = 0;
             for (int k = 0; k < K; ++k) {
                 const Launch& L = m[k]->prog_full.launches[li];
-                if (L0.type == OP_WFRAG) {
-                    tg.push_back(m[k]->d_wfrag); ng.push_back(m[k]->wfrag_n); sg.push_back(cg); cg += m[k]->wfrag_grid; ntot += m[k]->wfrag_n;
-                } else if (L0.type == OP_GEMM64) {
-                    tg.push_back(L.table); ng.push_back(L.ntasks); sg.push_back(cg); cg += L.tile_w;
-                    tw.push_back(L.table_w); nw.push_back(L.n_w); sw.push_back(cw); cw += L.tile_l - L.tile_w;
-                    tl.push_back(L.table_l); nl.push_back(L.n_l); sl.push_back(cl); cl += L.tile_m - L.tile_l;
-                    tm.push_back(L.table_m); nm.push_back(L.grid - L.tile_m); sm.push_back(0); cm += L.grid - L.tile_m;
-                } else {
-                    tg.push_back(L.table); ng.push_back(L.ntasks); sg.push_back(cg); cg += L.grid; ntot += L.ntasks;
-                }
+                sg.push_back(cg); sw.push_back(cw); sl.push_back(cl); sm.push_back(0);
+                if (L0.type == OP_WFRAG) { tf.push_back(&m[k]->h_wfrag); cg += m[k]->wfrag_grid; }
+                else if (L0.type == OP_GEMM64) {
+                    tg.push_back(&L.h_gemm); cg += L.tile_w;
+                    tw.push_back(&L.h_wgrad); cw += L.tile_l - L.tile_w;
+                    tl.push_back(&L.h_ln); cl += L.tile_m - L.tile_l;
+                    tm.push_back(&L.h_misc); cm += L.grid - L.tile_m;
+                } else { tg.push_back(&L.h_gemm); cg += L.grid; }
             }
             if (L0.type == OP_WFRAG) {
-                F.table = fuse<WfragTask>(tg, ng, sg, h_wf); F.ntasks = ntot; F.grid = cg;
+                std::vector<WfragTask> h_wf;
+                F.table = fuse(tf, sg, h_wf); F.ntasks = (int)h_wf.size(); F.grid = cg;
+                F.k = bind(fql_wfrag_kernel, F.grid, (const WfragTask*)F.table, F.ntasks, -1);
             } else if (L0.type == OP_GEMM64) {
-                F.table = fuse<GemmTask>(tg, ng, sg, F.h_gemm);
-                F.table_w = fuse<WgradTask>(tw, nw, sw, F.h_wgrad);
-                F.table_l = fuse<LnBwdTask>(tl, nl, sl, F.h_ln);
-                F.table_m = fuse<MiscTask>(tm, nm, sm, F.h_misc, false);
-                F.ntasks = F.n_w = F.n_l = 0;
-                for (int k = 0; k < K; ++k) { F.ntasks += ng[k]; F.n_w += nw[k]; F.n_l += nl[k]; }
+                F.table = fuse(tg, sg, F.h_gemm);
+                F.table_w = fuse(tw, sw, F.h_wgrad);
+                F.table_l = fuse(tl, sl, F.h_ln);
+                F.table_m = fuse(tm, sm, F.h_misc);
+                F.ntasks = (int)F.h_gemm.size(); F.n_w = (int)F.h_wgrad.size(); F.n_l = (int)F.h_ln.size();
                 F.tile_w = cg; F.tile_l = cg + cw; F.tile_m = cg + cw + cl; F.grid = F.tile_m + cm;
-                if (m[0]->ka_tasks) F.ka_side = ka_side_args(F);
+                m[0]->bind_side(F, L0.k.lds);
             } else {
-                F.table = fuse<GemmTask>(tg, ng, sg, F.h_gemm);
-                F.ntasks = ntot; F.grid = cg;
+                F.table = fuse(tg, sg, F.h_gemm);
+                F.ntasks = (int)F.h_gemm.size(); F.grid = cg;
+                m[0]->bind_gemm16(F);
             }
-            G.L = F;
+            G.k = F.k;
+            G.form = F.ka ? 2 : 1;
             return G;
         }
-        auto it = multi_entries().find(rec[0].fn);
+        const Bound& k0 = L0.k;
+        auto it = multi_entries().find(k0.fn);
         if (it == multi_entries().end()) invalid("agent groups: launch %d (op type %d) has no multi-instance kernel", li, (int)L0.type);
         std::vector<uint8_t> args;
-        for (int k = 0; k < K; ++k) {
-            if (rec[k].args.size() != it->second.arg_bytes) invalid("internal: launch %d records %zu argument bytes, its struct has %zu", li, rec[k].args.size(), it->second.arg_bytes);
-            args.insert(args.end(), rec[k].args.begin(), rec[k].args.end());
+        for (int k = 0; k < K; ++k) {   // the structs are exactly what the member's own issue() passes
+            const Launch& L = m[k]->prog_full.launches[li];
+            if (L.k.args.size() != it->second.arg_bytes) invalid("internal: launch %d binds %zu argument bytes, its struct has %zu", li, L.k.args.size(), it->second.arg_bytes);
+            alignas(16) unsigned char a[FQL_BOUND_BYTES];
+            m[k]->issue_args(L, m[k]->tl_of(m[k]->prog_full, L), a);
+            args.insert(args.end(), a, a + L.k.args.size());
         }
-        G.multi = it->second.launch;
-        G.grid = dim3(rec[0].grid[0], K);
-        G.block = dim3(rec[0].block[0], rec[0].block[1], rec[0].block[2]);
-        G.lds = rec[0].lds;
-        G.args = upload(args.data(), args.size());
+        G.k = it->second.bind(Geo(dim3(k0.grid[0], K), dim3(k0.block[0], k0.block[1], k0.block[2]), k0.lds), upload(args.data(), args.size()));
         return G;
-    }
-
-    void issue(GLaunch& G, hipStream_t s) {
-        if (!G.table) { G.multi(G.grid, G.block, G.lds, s, G.args); return; }
-        if (G.L.type == OP_WFRAG) hipLaunchKernelGGL(fql_wfrag_kernel, dim3(G.L.grid), dim3(FQL_THREADS), 0, s, (const WfragTask*)G.L.table, G.L.ntasks, -1);
-        else m[0]->issue(G.L, s, -1);   // (reads the launch and the members' shared config only)
     }
 
     // the fused program as ONE graph with the lanes, forks, joins and cross-lane events of a member's own
     void capture() {
-        capture_graph(lanes[0], [&] { issue_lanes(*this, lanes[0], lanes, true, [&](GLaunch& G, hipStream_t s) { issue(G, s); }); }, graph, exec);
+        capture_graph(lanes[0], [&] { issue_lanes(*this, lanes[0], lanes, true, [&](GLaunch& G, hipStream_t s) { launch_bound(G.k, G.k.args.data(), s); }); }, graph, exec);
     }
 
     void release() {
@@ -6446,8 +6364,7 @@ void group_check(const fql_handle* members, int k) {
         if (p.launches.size() != p0.launches.size()) invalid("fql_group_create: member %d's update has %zu launches, member 0's %zu", i, p.launches.size(), p0.launches.size());
         for (size_t li = 0; li < p.launches.size(); ++li) {
             const Launch &L = p.launches[li], &L0 = p0.launches[li];
-            if (L.type != L0.type || L.lane != L0.lane || L.grid != L0.grid || L.waits != L0.waits || L.tmt2 != L0.tmt2 ||
-                L.kbig != L0.kbig || L.euler != L0.euler || L.record_after != L0.record_after || L.lds != L0.lds)
+            if (L.type != L0.type || L.lane != L0.lane || L.grid != L0.grid || L.waits != L0.waits || L.record_after != L0.record_after)
                 invalid("fql_group_create: launch %zu of member %d differs from member 0's (type %d/%d, lane %d/%d, grid %d/%d)", li, i, (int)L.type,
                         (int)L0.type, L.lane, L0.lane, L.grid, L0.grid);
             if (L.type == OP_WFRAG && h->wfrag_grid != members[0]->wfrag_grid) invalid("fql_group_create: member %d's weight-copy launch differs", i);
@@ -6473,20 +6390,17 @@ int fql_group_create(const fql_handle* members, int k, fql_group* out) {
         g->K = k;
         g->B = members[0]->B;
         for (fql_handle h : g->m) { h->aql_drain(); HIP_CHECK(hipStreamSynchronize(h->stream)); }
-        std::vector<std::vector<AqlDispatch>> rec;
-        for (fql_handle h : g->m) rec.push_back(h->record_dispatches(h->prog_full));
         const size_t n = g->m[0]->prog_full.launches.size();
         for (size_t li = 0; li < n; ++li)
             for (int i = 1; i < k; ++i) {
-                const AqlDispatch &a = rec[i][li], &b = rec[0][li];
+                const Bound &a = g->m[i]->prog_full.launches[li].k, &b = g->m[0]->prog_full.launches[li].k;
                 if (a.fn != b.fn || std::memcmp(a.grid, b.grid, sizeof a.grid) || std::memcmp(a.block, b.block, sizeof a.block) || a.lds != b.lds)
                     invalid("fql_group_create: launch %zu of member %d runs another kernel or shape than member 0's", li, i);
             }
         for (size_t li = 0; li < n; ++li) {
-            if (rec[0][li].grid[1] != 1 || rec[0][li].grid[2] != 1) invalid("fql_group_create: launch %zu has a 2-D grid: not groupable", li);
-            std::vector<AqlDispatch> col;
-            for (int i = 0; i < k; ++i) col.push_back(rec[i][li]);
-            g->launches.push_back(g->zip((int)li, col));
+            const Bound& k0 = g->m[0]->prog_full.launches[li].k;
+            if (k0.grid[1] != 1 || k0.grid[2] != 1) invalid("fql_group_create: launch %zu has a 2-D grid: not groupable", li);
+            g->launches.push_back(g->zip((int)li));
             g->lane_used[g->launches.back().lane] = true;
         }
         for (int l = 0; l < FQL_LANES; ++l) HIP_CHECK(hipStreamCreateWithFlags(&g->lanes[l], hipStreamNonBlocking));
@@ -6511,9 +6425,9 @@ int fql_group_create(const fql_handle* members, int k, fql_group* out) {
 int fql_debug_task_forms(fql_handle h, fql_group g, void* out, size_t bytes) {
     if ((!h && !g) || (bytes && !out) || bytes % sizeof(int32_t)) return FQL_E_INVALID;
     if (!g && (h->visual || !h->prog_full.exec || h->prog_full.launches.empty())) return FQL_E_STATE;
-    auto form = [](const Launch& L) { return !is_table_launch(L.type) ? 0 : L.ka_side ? 2 : 1; };
+    auto form = [](const Launch& L) { return !is_table_launch(L.type) ? 0 : L.ka ? 2 : 1; };
     std::vector<int32_t> w{0, FQL_KA_GEMM, FQL_KA_WGRAD, FQL_KA_LN, FQL_KA_MISC, 0};
-    if (g) for (const GLaunch& G : g->launches) w.push_back(G.table ? form(G.L) : 0);
+    if (g) for (const GLaunch& G : g->launches) w.push_back(G.form);
     else for (const Launch& L : h->prog_full.launches) w.push_back(form(L));
     w[5] = (int32_t)w.size() - 6;
     w[0] = (int32_t)w.size();

@@ -164,3 +164,68 @@ def test_config3_shape_b1024_matches_oracle():
         _, ig = agent.update(batch, noise=nz)
         _, ir = ref.update(batch, nz)
         assert_info_close(ig, ir, rtol=1e-4, atol=1e-5)
+
+
+def _state_case(hidden, value_hidden, **kw):
+    od, ad, B = 11, 3, 32
+    cfg, ds, batch, _ = make_problem(od, ad, B, hidden, seed=41, **kw)
+    cfg.update(value_hidden_dims=tuple(value_hidden))
+    return cfg, ds, batch['observations'][:1], batch['actions'][:1], {}
+
+
+def _frames_case():
+    from tests.test_gpu_visual import make_visual
+    cfg, batch, _ = make_visual()   # 32 x 32 x 3 images, batch 32: the smallest shape of the visual tests
+    n = 64
+    rng = np.random.default_rng(42)
+    term = np.zeros(n, np.float32); term[[20, n - 1]] = 1
+    ds = dict(observations=rng.integers(0, 256, size=(n, 32, 32, 3), dtype=np.uint8),
+              next_observations=rng.integers(0, 256, size=(n, 32, 32, 3), dtype=np.uint8), terminals=term, masks=1 - term,
+              actions=rng.uniform(-1, 1, size=(n, 4)).astype(np.float32), rewards=-np.ones(n, np.float32))
+    return cfg, ds, batch['observations'][:1], batch['actions'][:1], dict(frame_stack=1, p_aug=0.5)
+
+
+PROFILE_CASES = {
+    'state_h64': lambda: _state_case((64, 64), (64, 64)),
+    # three equal hidden layers of 256 in the actors: the smallest net the Euler chain kernels take
+    'chain_h256': lambda: _state_case((256, 256, 256), (64, 64)),
+    'chain_h256_bf16x3': lambda: _state_case((256, 256, 256), (64, 64), precision='bf16x3'),
+    'frames': _frames_case,
+}
+
+
+@pytest.mark.parametrize('case', list(PROFILE_CASES))
+def test_profile_pass_is_one_update(case):
+    """fql_profile_update issues the update's launches eagerly, each dispatch carrying its event pair: the launch mode no other test runs
+    for the FQL kernels (16-row and side-lane launches, the chain kernels in fp32 and in their split form, the encoder kernels).  It
+    reports every launch of the plan, in order, with a device time, and leaves the state one update_from_dataset on the same
+    engine-drawn rows leaves (fql_debug_plan refuses visual handles: no plan to compare there)."""
+    import ctypes as C
+    import fql_amd
+    from tests.util import OP_CHAIN, assert_same_state, read_plan
+    cfg, ds, ob, ac, upload_kw = PROFILE_CASES[case]()
+    B = cfg['batch_size']
+    assert B == 32
+    a, b = (fql_amd.FQLAgent.create(3, ob, ac, cfg) for _ in range(2))
+    for x in (a, b):
+        x.upload_dataset(ds, **upload_kw)
+    f = a._lib.fql_profile_update
+    f.restype = C.c_int
+    f.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 6
+    cap = 1024
+    typ, lane, grid = (C.c_int * cap)(), (C.c_int * cap)(), (C.c_int * cap)()
+    us, macs, null_us = (C.c_float * cap)(), (C.c_double * cap)(), C.c_float()
+    n = f(a._h, B, cap, typ, lane, grid, us, macs, C.byref(null_us))
+    assert n == a.stats()['launches_per_update']
+    if case != 'frames':
+        plan = read_plan(a)
+        assert list(typ[:n]) == [L['type'] for L in plan]
+        chains = [L['chain'] for L in plan if L['type'] == OP_CHAIN]
+        assert bool(chains) == case.startswith('chain'), chains
+        if chains:   # variant 3 (a hidden layer's data gradient) keeps fp32 operands in both precisions
+            assert {c['split'] for c in chains if c['variant'] != 3} == {int(case.endswith('bf16x3'))}
+    assert all(np.isfinite(us[i]) and us[i] > 0 for i in range(n)), list(us[:n])
+    b.update_from_dataset(batch_size=B)
+    a.synchronize(); b.synchronize()
+    assert_same_state(a, b)
+    a.close(); b.close()
