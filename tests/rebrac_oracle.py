@@ -142,6 +142,15 @@ class OracleReBRAC(O.OracleFQL):
             grads['modules_actor'] = split(g, self._nh())
         return loss, info, grads
 
+    def kink_margins(self, batch, noise=None):
+        """Distance of every row from the one point where a full step's loss is not smooth in what it differentiates: q1 = q2 of the
+        stored critic pair at (obs, actor action), where the actor loss takes the smaller (tests/sac_oracle.py's q_tie: the smallest
+        |q1 - q2| over the rows, unnormalised).  The target side (noise clip, action clip, min of the target pair) carries no gradient
+        and is continuous, so it needs no margin, and `noise` is not read: the actor's action is its mode."""
+        a = self._mode(self.actor_mean('modules_actor', batch['observations']))
+        qs = self._critic('modules_critic', self._c(batch['observations']), a, stored=True)
+        return {'q_tie': float(np.abs(qs[0] - qs[1]).min())}
+
     def total_loss(self, batch, noise, full_update=True):
         loss, info, _ = self._losses(batch, noise, want_grads=False, full_update=full_update)
         info.pop('_lam', None)

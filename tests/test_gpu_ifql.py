@@ -6,6 +6,7 @@ import pytest
 
 from oracle import fql_oracle as O
 from tests import ifql_oracle as IO
+from tests.ifql_cases import best_of_n as _best_of_n
 from tests.util import assert_info_close, leaf_dict, make_problem, randomize_params, sync_restatement
 
 pytestmark = pytest.mark.gpu
@@ -369,17 +370,6 @@ def test_total_loss_and_update_across_shapes_and_configs(od, ad, B, actor, value
     _check_total_loss(a, ref, params, batch, noise)
     worst = _check_first_update(a, ref, cfg, params, batch, noise)
     print(f'worst relative gradient error {worst[0]:.3e} ({worst[1]})')
-
-
-def _best_of_n(ref, obs, noises):
-    """OracleIFQL.sample_actions for every row of obs [n, od] at once: the flow of each of the N noises, min(q1, q2), the first argmax.
-    Returns the chosen actions [n, act], every candidate [n, N, act] and their scores [n, N]."""
-    n, N, ad = noises.shape
-    rep = np.repeat(obs, N, axis=0)
-    acts = ref.compute_flow_actions(rep, noises.reshape(n * N, ad))
-    q = ref._critic('modules_critic', rep, acts, stored=True).min(axis=0).reshape(n, N)
-    acts = acts.reshape(n, N, ad)
-    return acts[np.arange(n), np.argmax(q, axis=1)], acts, q
 
 
 @pytest.mark.parametrize('N,n', [(1, 4097), (7, 590), (65, 64), (100, 42)])

@@ -373,7 +373,9 @@ SHAPE_CASES = [
     pytest.param(17, 6, 64, (64,) * 4, (64,) * 4, dict(actor_layer_norm=True, layer_norm=False), id='actor_ln_no_critic_ln'),
     pytest.param(69, 21, 256, (512,) * 4, (512,) * 4, dict(alpha_actor=0.01, alpha_critic=0.01, discount=0.995), id='humanoidmaze'),
     pytest.param(29, 16, 256, (512,) * 4, (512,) * 4, {}, id='act16'),               # OP_DGRAD0 with a full 16-column action block
-    # the reference's default alphas; obs + 16 > in_p = 48: the generic first-layer dgrad at H 512
+    # the reference's default alphas; the hidden layers on fql_side_big_kernel's 64-row tiles.  in_p = round64(40 + 4) = 64 and 40 + 16 <= 64:
+    # OP_DGRAD0 with 4 live columns, as in IQL's table (tests/test_gpu_rebrac_paths.py asserts it from the plan; the generic first-layer dgrad
+    # at H 512 with act <= 16 is that file's obs50)
     pytest.param(40, 4, 1024, (512,) * 4, (512,) * 4, dict(alpha_actor=0.0, alpha_critic=0.0), id='b1024'),
 ]
 

@@ -1,4 +1,5 @@
-"""CPU: the inputs of the IQL and SAC shape cases (tests/test_gpu_iql.py, tests/test_gpu_sac.py) are clear of the losses' kinks.
+"""CPU: the inputs of the IQL and SAC shape cases (tests/test_gpu_iql.py, tests/test_gpu_sac.py) and of the ReBRAC path cases
+(tests/rebrac_cases.py) are clear of the losses' kinks, and IFQL's hidden-512 sampler problems (tests/ifql_cases.py) are inside their cap.
 
 The GPU tests compare every element of every gradient with the fp64 restatement and mask nothing out, which is sound only where the
 restatement itself is a margin away from each point where a loss is not smooth: an element that sits on a kink may fall on the other
@@ -11,7 +12,11 @@ restatement's trajectory by up to 2 lr per element; there the restatement's own 
 import numpy as np
 import pytest
 
+from tests import ifql_cases as FC
+from tests import ifql_oracle as FO
 from tests import iql_oracle as IO
+from tests import rebrac_cases as RC
+from tests import rebrac_oracle as RO
 from tests import sac_oracle as SO
 from tests import test_gpu_iql as TI
 from tests import test_gpu_sac as TS
@@ -91,3 +96,86 @@ def test_sac_shape_cases_cover_the_configurations_asked_for():
     kws = [c[5] for c in TS.SHAPE_CASES.values()]
     assert sum(kw.get('backup_entropy', False) for kw in kws) == 1 and sum(not kw.get('tanh_squash', True) for kw in kws) == 1
     assert set(TS.SHAPE_CASES) == {'act16', 'humanoidmaze', 'b1024', 'ragged_depths', 'b272'}
+
+
+# ---- ReBRAC: q1 = q2 at (obs, actor action) --------------------------------------------------------------------------------------------
+def _rebrac_seed_holds(od, ad, cfg, params, steps):
+    """The admission rule of tests/rebrac_cases.py on the restatement's own trajectory through `steps` ((batch, noise, full_update)
+    each): q_tie >= MARGIN in the first step, >= 3 MARGIN in every later full step.  Returns (holds, [q_tie of each full step])."""
+    ref = RO.OracleReBRAC(params, dict(cfg), od, ad, np.float64)
+    ties = []
+    for i, (batch, noise, full) in enumerate(steps):
+        if full:
+            m = ref.kink_margins(batch, noise)
+            assert set(m) == {'q_tie'}
+            ties.append(m['q_tie'])
+            if m['q_tie'] < (3 if i else 1) * RC.MARGIN:
+                return False, ties
+        if i + 1 < len(steps):
+            ref.update(batch, noise, full_update=full)
+    return True, ties
+
+
+@pytest.mark.parametrize('case', list(RC.PATHS))
+def test_rebrac_path_cases_keep_their_margin_at_the_smallest_seed(case):
+    """The recorded data seed keeps the margin through the case's full, critic-only and full step, and no smaller seed does."""
+    od, ad = RC.PATHS[case][:2]
+    recorded = RC.PATHS[case][6]
+    assert 0 <= recorded <= 7 and RC.STEP_KINDS == (True, False, True)
+    for seed in range(recorded + 1):
+        cfg, batch, params, noises = RC.problem(case, seed)
+        assert len(noises) == len(RC.STEP_KINDS)
+        holds, ties = _rebrac_seed_holds(od, ad, cfg, params, [(batch, nz, full) for nz, full in zip(noises, RC.STEP_KINDS)])
+        print(case, 'seed', seed, 'q_tie of the full steps', ties)
+        assert holds == (seed == recorded), (case, seed, ties)
+
+
+def test_rebrac_batch_size_walk_keeps_its_margin_at_the_smallest_seed():
+    od, ad, sizes, recorded = RC.WALK
+    for seed in range(recorded + 1):
+        cfg, params, steps = RC.walk_problem(seed)
+        assert [len(b['observations']) for b, _, _ in steps] == list(sizes) and [f for _, _, f in steps] == [True, False] * 2 + [True]
+        holds, ties = _rebrac_seed_holds(od, ad, cfg, params, steps)
+        print('walk seed', seed, 'q_tie of the full steps', ties)
+        assert holds == (seed == recorded), (seed, ties)
+
+
+def test_rebrac_kink_margin_is_the_smallest_q_gap_at_the_actor_action():
+    """kink_margins against the values the loss itself reads: moving the critic pair apart by d moves q_tie by d."""
+    cfg, batch, params, noises = RC.problem('b16')
+    od, ad = RC.PATHS['b16'][:2]
+    ref = RO.OracleReBRAC(params, dict(cfg), od, ad, np.float64)
+    a = ref._mode(ref.actor_mean('modules_actor', batch['observations']))
+    qs = ref._critic('modules_critic', ref._c(batch['observations']), a, stored=True)
+    assert ref.kink_margins(batch, noises[0]) == {'q_tie': float(np.abs(qs[0] - qs[1]).min())}
+    assert RC.MARGIN == TS.MARGIN == TI.MARGIN
+
+
+# ---- IFQL: no margins (C1 losses, see tests/ifql_cases.py); the sampler problems are inside the clear-winner cap ---------------------------
+@pytest.mark.parametrize('N,n', list(FC.SAMPLER_CASES))
+def test_ifql_sampler_problems_at_hidden_512_have_clear_winners(N, n):
+    """At least half the rows of each best-of-N problem have a top-two gap above 1e-2 in fp64, so the GPU test's strict branch (pick the
+    restatement's action to 2e-5) covers them."""
+    cfg, params, obs, noises = FC.sampler_problem(N, n)
+    od, ad = FC.SAMPLER_SHAPE[:2]
+    assert obs.shape == (n, od) and noises.shape == (n, N, ad) and cfg['num_samples'] == N and cfg['value_hidden_dims'] == (512,) * 4
+    ref = FO.OracleIFQL(params, dict(cfg), od, ad, np.float64)
+    _, _, q = FC.best_of_n(ref, obs, noises)
+    clear = FC.clear_winners(q)
+    print(f'N {N} n {n}: clear-winner share {clear.mean():.3f}, score spread {q.std():.3f}')
+    assert FC.SAMPLER_GAP == 1e-2 and clear.mean() >= 0.5, clear.mean()
+
+
+def test_ifql_and_rebrac_case_tables_hold_the_cases_asked_for():
+    assert list(FC.PATHS) == ['b512_mixed', 'b272', 'b544_h64', 'b1040_h64', 'b2048_h64', 'wide1024', 'obs600', 'no_ln_h512', 'act16', 'b16']
+    assert list(RC.PATHS) == ['b272', 'obs50', 'b1040_h64', 'b2048_h64', 'wide1024', 'obs600', 'no_ln_h512_no_tanh', 'b16']
+    assert list(FC.SAMPLER_CASES) == [(1, 37), (7, 590), (65, 64)] and FC.SAMPLER_SHAPE[:2] == (69, 21)
+    big = 1024 * 512 ** 2   # no new case costs more than the existing b1024 cases: B x H^2
+    for table in (FC.PATHS, RC.PATHS):
+        for name, (od, ad, B, actor, value, kw, seed) in table.items():
+            assert B * max(actor + value) ** 2 <= big, name
+    for case in FC.PATHS:
+        cfg, batch, params, noises = FC.problem(case)
+        od, ad, B = FC.PATHS[case][:3]
+        assert batch['observations'].shape == (B, od) and noises[0]['x0'].shape == (B, ad) and len(noises) == 2
+        assert not np.array_equal(noises[0]['x0'], noises[1]['x0'])

@@ -121,6 +121,7 @@ BF16X3_BOUND = 1e-4          # both bounds of the bf16x3 mode: every info (BASEL
 # fql_debug_plan's kernel entries and the op types its records name (fql_amd/csrc/fql_engine.hip: the PLAN_K_* codes, enum OpType)
 K_OTHER, K_GEMM16, K_GEMM16_KBIG, K_GEMM16_EULER, K_GEMM16_EULER_KBIG, K_SIDE, K_SIDE_SPLIT, K_SIDE_BIG, K_CHAIN, K_CHAIN_SPLIT = range(10)
 OP_GEMM, OP_GEMM64, OP_CHAIN = 0, 1, 20
+OP_DGRAD0 = 24   # the lean 16-column first-layer input gradient: a launch of its own, 16 rows per workgroup and task, no task records
 
 
 def plan_lib():
@@ -163,6 +164,32 @@ def read_plan(agent):
         out.append(L)
     assert at == len(w) and [L['index'] for L in out] == list(range(len(out)))
     return out
+
+
+def plan_gemm(plan, kernels=None):
+    """Every GEMM task of a plan (of the launches bound to `kernels`, if given) with its launch's kernel entry, type and index."""
+    return [dict(t, kernel=L['kernel'], type=L['type'], launch=L['index']) for L in plan if kernels is None or L['kernel'] in kernels
+            for t in L['gemm']]
+
+
+def plan_wgrad(plan):
+    return [t for L in plan for t in L['wgrad']]
+
+
+def plan_ln(plan):
+    return [m for L in plan for m in L['ln']]
+
+
+def plan_has(tasks, M, N, K, **kw):
+    return [t for t in tasks if (t['M'], t['N'], t['K']) == (M, N, K) and all(t[k] == v for k, v in kw.items())]
+
+
+def print_plan(name, plan):
+    """One line per family: what a path test prints before it asserts its property."""
+    g = plan_gemm(plan)
+    print(name, 'gemm (kernel, type, M, N, K, rows):', sorted({(t['kernel'], t['type'], t['M'], t['N'], t['K'], t['rows']) for t in g}))
+    print(name, 'wgrad (M, Kin, N):', sorted({(t['M'], t['Kin'], t['N']) for t in plan_wgrad(plan)}), 'ln M:', sorted(set(plan_ln(plan))),
+          'other launches (type, grid):', sorted({(L['type'], L['grid']) for L in plan if L['type'] not in (OP_GEMM, OP_GEMM64)}))
 
 
 def assert_trajectory_tracks_oracle(od, ad, B, hidden, seed, steps=20, **cfgkw):
