@@ -1,0 +1,261 @@
+"""Two builds of the library build and compute the same thing, bit for bit: the equality pass of a host-side refactor.
+
+usage: python experiments/compare_builds.py <library a> <library b> [out dir, default build/compare_builds]
+
+For each library in turn, and one at a time, a fresh child process per job below loads it through FQL_AMD_LIB with FQL_DUMP=1 under its
+own `timeout -k 10`, and writes what it read to <out dir>/<a|b>/<job>/: arrays.npz (the fql_debug_plan and fql_debug_task_forms words,
+the *_stats counts, the sampler outputs, and after 8 update_from_dataset calls from one seed every parameter leaf, both Adam moments and
+the counters) and dump.txt (its stderr: the FQL_DUMP lines of every program the handles build, sampler programs included).  The first
+non-zero exit or time-out stops the script.  This process never opens the GPU: it compares the two directories, prints the first
+difference and the number of arrays and lines compared, and exits 1 on a difference.
+
+Jobs: `kinds`: FQL, IFQL, ReBRAC, SAC, IQL ddpgbc and awr, BC, IQL-diffusion, CFGRL at hidden 64 x 2, batch 32 (ReBRAC alternates
+critic-only and full steps, IQL-diffusion runs its four step kinds; one sample_actions of 5 rows each, cfg 3 and one per-row sweep call for
+the two CFG kinds).  `h512_<precision>`: FQL at hidden 512 x 4, batch 256, then one update_begin_split / update_end_split pair.
+`edges_<precision>`: the FQL shapes of tests/test_gpu_batch_edges.py CASES.  `frames`: a 32 x 32 x 3 frames handle in both precisions (no
+plan: the read-out refuses visual handles).  `group`: the two members of a K = 2 group at hidden 256 x 4, batch 64."""
+import ctypes as C
+import os
+import subprocess
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+OD, AD, UPDATES = 29, 8, 8
+PRECISIONS = ('fp32', 'bf16x3')
+# job -> its time limit in seconds (each takes 1 - 3 s on an MI355X; a cold start of the runtime can add several)
+JOBS = {'kinds': 30, 'h512_fp32': 30, 'h512_bf16x3': 30, 'edges_fp32': 30, 'edges_bf16x3': 30, 'frames': 20, 'group': 20}
+
+
+# ---- child: one job on one library ---------------------------------------------------------------------------------------------------
+def flat(tree, prefix):
+    for k, v in sorted(tree.items()):
+        if isinstance(v, dict):
+            yield from flat(v, f'{prefix}/{k}')
+        else:
+            yield f'{prefix}/{k}', np.asarray(v)
+
+
+def words(fn, *handles):
+    """The int32 words of a diagnostic read-out (size in word 0), or its refusal code."""
+    head = np.zeros(1, np.int32)
+    rc = fn(*handles, head.ctypes.data, 4)
+    if rc != 0:
+        return np.array([rc], np.int32)
+    w = np.zeros(int(head[0]), np.int32)
+    assert fn(*handles, w.ctypes.data, w.nbytes) == 0
+    return w
+
+
+def plan_and_forms(out, tag, agent=None, group=None):
+    from fql_amd import _cabi
+    lib = _cabi.load()
+    lib.fql_debug_plan.argtypes, lib.fql_debug_plan.restype = [C.c_void_p, C.c_void_p, C.c_size_t], C.c_int
+    lib.fql_debug_task_forms.argtypes, lib.fql_debug_task_forms.restype = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t], C.c_int
+    if agent is not None:
+        out[f'{tag}/plan'] = words(lib.fql_debug_plan, agent._h)
+    out[f'{tag}/forms'] = words(lib.fql_debug_task_forms, agent._h if agent is not None else None, group._g if group is not None else None)
+
+
+def state(out, tag, agent):
+    agent.synchronize()
+    out.update(flat(agent.get_params(), f'{tag}/params'))
+    st = agent.get_opt_state()
+    out.update(flat(st.pop('mu'), f'{tag}/mu'))
+    out.update(flat(st.pop('nu'), f'{tag}/nu'))
+    out[f'{tag}/counters'] = np.array([st[k] for k in sorted(st)], np.int64)
+
+
+def dataset(n, seed=0):
+    from fql_amd.synthetic import make_synthetic_dataset
+    ds = make_synthetic_dataset(n, OD, AD, seed=seed)
+    ds['terminals'][-1] = 1.0
+    return ds
+
+
+def fql_handle(out, tag, B, hidden, precision):
+    """One FQL handle: plan, forms, stats, both samplers, UPDATES updates, state.  Returns it for what a job adds."""
+    import fql_amd
+    cfg = fql_amd.get_config()
+    cfg.update(actor_hidden_dims=tuple(hidden), value_hidden_dims=tuple(hidden), alpha=10.0, batch_size=B, precision=precision)
+    ds = dataset(max(4 * B, 64), seed=3)
+    a = fql_amd.FQLAgent.create(0, ds['observations'][:1], ds['actions'][:1], cfg)
+    plan_and_forms(out, tag, agent=a)
+    out[f'{tag}/stats'] = np.array([v for _, v in sorted(a.stats().items())], np.int64)
+    a.upload_dataset(ds)
+    z = np.random.default_rng(1).standard_normal((5, AD)).astype(np.float32)
+    out[f'{tag}/sample'] = a.sample_actions(ds['observations'][:5], noises=z)
+    out[f'{tag}/flow'] = a.compute_flow_actions(ds['observations'][:5], z)
+    for _ in range(UPDATES):
+        a.update_from_dataset(B)
+    state(out, tag, a)
+    return a
+
+
+def job_kinds(out):
+    import fql_amd
+    import fql_amd.cfgrl
+    ds = dataset(256)
+    obs, z = ds['observations'][:5], np.random.default_rng(1).standard_normal((5, AD)).astype(np.float32)
+    w = np.array([1.0, 1.5, 3.0, 5.0, 3.0], np.float32)
+    hid = dict(actor_hidden_dims=(64, 64), value_hidden_dims=(64, 64), hidden_dims=(64, 64), batch_size=32)
+    fql_handle(out, 'fql', 32, (64, 64), 'fp32').close()
+    ex = (ds['observations'][:1], ds['actions'][:1])
+    kinds = [('ifql', fql_amd.IFQLAgent, fql_amd.ifql.get_config(), lambda a: a.stats().values()),
+             ('rebrac', fql_amd.ReBRACAgent, fql_amd.rebrac.get_config(), lambda a: a.rebrac_stats(True) + a.rebrac_stats(False)),
+             ('sac', fql_amd.SACAgent, fql_amd.sac.get_config(), lambda a: a.sac_stats()),
+             ('iql_ddpgbc', fql_amd.IQLAgent, dict(fql_amd.iql.get_config(), actor_loss='ddpgbc'), lambda a: a.iql_stats()),
+             ('iql_awr', fql_amd.IQLAgent, dict(fql_amd.iql.get_config(), actor_loss='awr'), lambda a: a.iql_stats()),
+             ('bc', fql_amd.BCAgent, fql_amd.bc.get_config(), lambda a: a.bc_stats()),
+             ('iqld', fql_amd.IQLDiffusionAgent, fql_amd.iql_diffusion.get_config(),
+              lambda a: sum((a.iqld_stats(c, p) for c in (1, 0) for p in (1, 0)), ()) + (a.sample_cfgs_stats(),))]
+    for tag, cls, cfg, stats in kinds:
+        cfg = dict(cfg, **hid)
+        a = cls.create(0, *ex, cfg)
+        plan_and_forms(out, tag, agent=a)
+        out[f'{tag}/stats'] = np.array([int(v) for v in stats(a)], np.int64)
+        a.upload_dataset(ds)
+        if tag == 'iqld':
+            out[f'{tag}/sample'] = a.sample_actions(obs, noises=z, cfg=3.0)
+            out[f'{tag}/rows'] = a.sample_actions_rows(obs, w, noises=z)
+        else:
+            out[f'{tag}/sample'] = a.sample_actions(obs, seed=7)
+        for i in range(UPDATES):
+            if tag == 'rebrac':
+                a.update_from_dataset(32, full_update=bool(i % 2))
+            elif tag == 'iqld':
+                a.update_from_dataset(32, update_critic=i % 4 < 2, update_actor=i % 2 == 0)
+            else:
+                a.update_from_dataset(32)
+        state(out, tag, a)
+        a.close()
+    goals = ds['next_observations'][:5]
+    g = fql_amd.CFGRLAgent.create(0, {'observations': ex[0], 'actions': ex[1], 'value_goals': goals[:1]}, dict(fql_amd.cfgrl.get_config(), **hid))
+    plan_and_forms(out, 'cfgrl', agent=g)
+    out['cfgrl/stats'] = np.array(g.cfgrl_stats() + (g.sample_cfgs_stats(),), np.int64)
+    g.upload_dataset(ds)
+    out['cfgrl/sample'] = g.sample_actions(obs, goals, noises=z, cfg=3.0)
+    out['cfgrl/rows'] = g.sample_actions_rows(obs, goals, w, noises=z)
+    for _ in range(UPDATES):
+        g.update_from_dataset(32)
+    state(out, 'cfgrl', g)
+    g.close()
+
+
+def job_h512(out, precision):
+    import torch
+    a = fql_handle(out, 'h512', 256, (512,) * 4, precision)
+    s0, s1 = torch.cuda.Stream(), torch.cuda.Stream()
+    a.update_begin_split(s0.cuda_stream, s1.cuda_stream, batch_size=256)
+    a.update_end_split(s0.cuda_stream, s1.cuda_stream)
+    torch.cuda.synchronize()
+    state(out, 'h512/split', a)
+    a.close()
+
+
+def job_edges(out, precision):
+    from tests.test_gpu_batch_edges import CASES
+    for cid, (B, hidden) in CASES.items():
+        fql_handle(out, cid, B, hidden, precision).close()
+
+
+def job_frames(out):
+    import fql_amd
+    from fql_amd.synthetic import make_synthetic_frames
+    ds = make_synthetic_frames(150, 4, h=32, w=32, c=3, seed=0, episode_len=25)
+    for precision in PRECISIONS:
+        cfg = fql_amd.get_config()
+        cfg.update(encoder='impala_small', actor_hidden_dims=(64, 64), value_hidden_dims=(64, 64), alpha=3.0, batch_size=32, precision=precision)
+        a = fql_amd.FQLAgent.create(0, np.zeros((1, 32, 32, 9), np.uint8), ds['actions'][:1], cfg)
+        a.upload_dataset(ds, frame_stack=3, p_aug=0.5)
+        rng = np.random.default_rng(2)
+        out[f'{precision}/sample'] = a.sample_actions(rng.integers(0, 256, size=(5, 32, 32, 9), dtype=np.uint8),
+                                                      noises=rng.standard_normal((5, 4)).astype(np.float32))
+        for _ in range(UPDATES):
+            a.update_from_dataset(32)
+        state(out, precision, a)
+        a.close()
+
+
+def job_group(out):
+    import fql_amd
+    cfg = fql_amd.get_config()
+    cfg.update(actor_hidden_dims=(256,) * 4, value_hidden_dims=(256,) * 4, batch_size=64)
+    ds = dataset(256, seed=3)
+    g = fql_amd.FQLAgentGroup.create([0, 1], ds['observations'][:1], ds['actions'][:1], cfg, alphas=[3.0, 30.0])
+    plan_and_forms(out, 'group', group=g)
+    g.upload_dataset(ds)
+    for _ in range(UPDATES):
+        g.update_from_dataset()
+    g.synchronize()
+    for i, m in enumerate(g.members):
+        state(out, f'member{i}', m)
+    g.close()
+
+
+def child(job, where):
+    out = {}
+    name, _, precision = job.partition('_')
+    if precision:
+        {'h512': job_h512, 'edges': job_edges}[name](out, precision)
+    else:
+        {'kinds': job_kinds, 'frames': job_frames, 'group': job_group}[name](out)
+    np.savez(os.path.join(where, 'arrays.npz'), **{k.replace('/', '|'): v for k, v in out.items()})
+
+
+# ---- parent: run the children, compare what they wrote -------------------------------------------------------------------------------
+def run(lib, where):
+    for job, limit in JOBS.items():
+        d = os.path.join(where, job)
+        os.makedirs(d, exist_ok=True)
+        env = dict(os.environ, FQL_AMD_LIB=os.path.abspath(lib), FQL_DUMP='1')
+        t0 = time.perf_counter()
+        with open(os.path.join(d, 'dump.txt'), 'w') as err, open(os.path.join(d, 'stdout.txt'), 'w') as so:
+            rc = subprocess.run(['timeout', '-k', '10', str(limit), sys.executable, os.path.abspath(__file__), '--child', job, d],
+                                env=env, stdout=so, stderr=err, cwd=ROOT).returncode
+        print(f'{lib} {job}: exit {rc} after {time.perf_counter() - t0:.1f} s (limit {limit})', flush=True)
+        if rc != 0:
+            print(f'stopped: see {d}/dump.txt' + (' (time limit)' if rc in (124, 137) else ''))
+            sys.exit(2)
+
+
+def compare(da, db):
+    arrays = lines = 0
+    for job in JOBS:
+        with np.load(os.path.join(da, job, 'arrays.npz')) as a, np.load(os.path.join(db, job, 'arrays.npz')) as b:
+            if sorted(a.files) != sorted(b.files):
+                return f'{job}: array names differ: {sorted(set(a.files) ^ set(b.files))[:5]}', arrays, lines
+            for k in a.files:
+                x, y = a[k], b[k]
+                if x.dtype != y.dtype or x.shape != y.shape or x.tobytes() != y.tobytes():
+                    return f'{job}: {k} differs', arrays, lines
+                arrays += 1
+            n, nwords = len(a.files), sum(a[k].size for k in a.files if k.endswith(('plan', 'forms')))
+        la, lb = (open(os.path.join(d, job, 'dump.txt')).read().splitlines() for d in (da, db))
+        for i, (x, y) in enumerate(zip(la, lb)):
+            if x != y:
+                return f'{job}: dump line {i + 1} differs:\n  a: {x}\n  b: {y}', arrays, lines
+        if len(la) != len(lb):
+            return f'{job}: {len(la)} dump lines against {len(lb)}', arrays, lines
+        lines += len(la)
+        print(f'{job}: {n} arrays ({nwords} plan and form words), {len(la)} dump lines')
+    return None, arrays, lines
+
+
+if __name__ == '__main__':
+    if len(sys.argv) == 4 and sys.argv[1] == '--child':
+        child(sys.argv[2], sys.argv[3])
+        sys.exit(0)
+    if len(sys.argv) not in (3, 4):
+        sys.exit(__doc__)
+    top = sys.argv[3] if len(sys.argv) == 4 else os.path.join(ROOT, 'build', 'compare_builds')
+    for lib, side in ((sys.argv[1], 'a'), (sys.argv[2], 'b')):
+        run(lib, os.path.join(top, side))
+    diff, arrays, lines = compare(os.path.join(top, 'a'), os.path.join(top, 'b'))
+    print(f'compared {arrays} arrays and {lines} dump lines: ' + ('all bitwise equal' if diff is None else 'FIRST DIFFERENCE'))
+    if diff is not None:
+        print(diff)
+        sys.exit(1)

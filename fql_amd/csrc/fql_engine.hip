@@ -34,6 +34,7 @@
 #include <memory>
 #include <random>
 #include <string>
+#include <tuple>
 #include <vector>
 
 #define FQL_LANES 4
@@ -254,12 +255,15 @@ struct Op {
     double macs = 0.0;       // ... and its algorithmic multiply-accumulates where its payload does not say them (chain launches)
     int level = 0;
     int lane = 0;            // 0 = critical lane (Euler chain, one-step backward), 1 = side lane
+    int launch = -1;         // index of the launch schedule() put this op into
     std::vector<int> deps;   // indices of earlier ops this op must follow (RAW / WAW / WAR)
 };
 
 // What issue() needs of a launch is its Bound; the rest is what the diagnostics report, what orders the lanes, and what an agent group needs
 // to fuse the members' table-driven launches.
 struct Launch {
+    Launch() = default;
+    Launch(OpType t, int ln) : type(t), lane(ln) {}
     OpType type;
     int lane = 0;
     int grid = 0, ntasks = 0;    // table-driven launches: workgroups and tasks (0 in a single-op launch; fql_profile_update, FQL_TRACE, FQL_DUMP)
@@ -1794,6 +1798,26 @@ struct fql_engine {
         const Net& n = nets[p.net];
         const int L = n.nl() - 1;
         auto rows = [&](float* base, int ld) { return base + (size_t)row_off * ld; };
+        // backward of the LayerNorm in front of layer l: dZ[l - 1] from the gradient it first reads, which the caller names in the task as dY
+        // (the dgrad's output) or as dq and wq (a scalar head: dY is synthesised)
+        auto ln_bwd = [&](int l, const void* first_read) {
+            const Layer& prev = n.layers[l - 1];
+            Op lo{};
+            lo.type = OP_LNBWD;
+            LnBwdTask& q = lo.ln;
+            q.Z = rows(p.z[l - 1], prev.out_p);
+            q.Gv = rows(p.g[l - 1], prev.out_p);
+            q.stats = p.stats[l - 1] + (size_t)row_off * 2;
+            q.gamma = P + prev.g;
+            q.dZ = p.dz[l - 1];
+            q.dgamma = param_grads ? G + prev.g : nullptr;
+            q.dbeta = param_grads ? G + prev.be : nullptr;
+            q.M = M; q.H = prev.out_p; q.ld = prev.out_p; q.width = prev.out;
+            lo.reads = {first_read, p.z[l - 1], p.g[l - 1], p.stats[l - 1], q.gamma};
+            lo.writes = {q.dZ};
+            if (param_grads) { lo.writes.push_back(q.dgamma); lo.writes.push_back(q.dbeta); }
+            return lo;
+        };
         for (int l = L; l >= 0; --l) {
             const Layer& ly = n.layers[l];
             float* dz = p.dz[l];
@@ -1822,23 +1846,9 @@ struct fql_engine {
             if (l == 0 && !input_grad) break;
             if (l == L && l > 0 && ly.out == 1 && n.layers[l - 1].ln) {
                 // scalar head behind a LayerNorm (critic Q): dY = dq (x) w is rank 1, synthesised inside the LN-backward
-                const Layer& prev = n.layers[l - 1];
-                Op lo{};
-                lo.type = OP_LNBWD;
+                Op lo = ln_bwd(l, dz);
                 LnBwdTask& q = lo.ln;
-                q.dY = nullptr;
                 q.dq = dz; q.ldq = ly.out_p; q.wq = P + ly.w; q.ldw = ly.out_p;
-                q.Z = rows(p.z[l - 1], prev.out_p);
-                q.Gv = rows(p.g[l - 1], prev.out_p);
-                q.stats = p.stats[l - 1] + (size_t)row_off * 2;
-                q.gamma = P + prev.g;
-                q.dZ = p.dz[l - 1];
-                q.dgamma = param_grads ? G + prev.g : nullptr;
-                q.dbeta = param_grads ? G + prev.be : nullptr;
-                q.M = M; q.H = prev.out_p; q.ld = prev.out_p; q.width = prev.out;
-                lo.reads = {dz, p.z[l - 1], p.g[l - 1], p.stats[l - 1], q.gamma};
-                lo.writes = {q.dZ};
-                if (param_grads) { lo.writes.push_back(q.dgamma); lo.writes.push_back(q.dbeta); }
                 push(pr, lo);
                 continue;
             }
@@ -1869,21 +1879,8 @@ struct fql_engine {
                 op.writes = {t.C};
                 if (want64(t.M, t.N, t.K, t.flags)) op.type = OP_GEMM64;
                 push(pr, op);
-                Op lo{};
-                lo.type = OP_LNBWD;
-                LnBwdTask& q = lo.ln;
-                q.dY = p.dy[l - 1];
-                q.Z = rows(p.z[l - 1], prev.out_p);
-                q.Gv = rows(p.g[l - 1], prev.out_p);
-                q.stats = p.stats[l - 1] + (size_t)row_off * 2;
-                q.gamma = P + prev.g;
-                q.dZ = p.dz[l - 1];
-                q.dgamma = param_grads ? G + prev.g : nullptr;
-                q.dbeta = param_grads ? G + prev.be : nullptr;
-                q.M = M; q.H = prev.out_p; q.ld = prev.out_p; q.width = prev.out;
-                lo.reads = {q.dY, p.z[l - 1], p.g[l - 1], p.stats[l - 1], q.gamma};
-                lo.writes = {q.dZ};
-                if (param_grads) { lo.writes.push_back(q.dgamma); lo.writes.push_back(q.dbeta); }
+                Op lo = ln_bwd(l, p.dy[l - 1]);
+                lo.ln.dY = p.dy[l - 1];
                 push(pr, lo);
             } else {
                 t.C = p.dz[l - 1];
@@ -1968,8 +1965,19 @@ struct fql_engine {
         return bind(fql_conv_wprep_kernel, Geo(dim3(4, n), dim3(FQL_THREADS), 0), tasks);
     }
 
+    // schedule(), the steps of which follow in the order it calls them: levels, launches (one former per family), MACs, waits.
     void schedule(Program& pr, std::vector<void*>& owner) {
-        // list scheduling: level = 1 + max level of every op this one conflicts with (RAW, WAW, WAR)
+        assign_levels(pr);
+        form_launches(pr, owner);
+        for (const Op& o : pr.ops)   // algorithmic MACs per launch (real, unpadded layer widths are within 1 % of these)
+            if (o.launch >= 0) pr.launches[o.launch].macs += op_macs(o);
+        cross_lane_waits(pr);
+        if (getenv("FQL_DUMP")) dump_program(pr);
+        check_lane_edges(pr);
+    }
+
+    // list scheduling: level = 1 + max level of every op this one conflicts with (RAW, WAW, WAR)
+    static void assign_levels(Program& pr) {
         std::map<const void*, int> last_writer;               // buffer -> op index of last writer
         std::map<const void*, std::vector<int>> readers;      // buffer -> ops reading it since that write
         for (int oi = 0; oi < (int)pr.ops.size(); ++oi) {
@@ -1994,353 +2002,342 @@ struct fql_engine {
                 readers.erase(w);
             }
         }
-        {
-            // The folds of the encoders' weight-gradient partials (27 tiny tasks, one launch per convolution level = 9 launches of ~16 us in the
-            // middle of the backward pass) are needed by nothing but their module's Adam launch: as late as possible they share one launch per module.
-            std::vector<std::vector<int>> cons(pr.ops.size());
-            for (int oi = 0; oi < (int)pr.ops.size(); ++oi)
-                for (int d : pr.ops[oi].deps) cons[d].push_back(oi);
-            for (int oi = (int)pr.ops.size() - 1; oi >= 0; --oi) {
-                Op& op = pr.ops[oi];
-                if (op.type != OP_CONV_WRED) continue;
-                int lv = 1 << 30;
-                for (int c : cons[oi]) lv = std::min(lv, pr.ops[c].level - 1);
-                if (cons[oi].empty()) {   // (the optimizer is another program: the end of this one)
-                    lv = 0;
-                    for (const Op& o2 : pr.ops) lv = std::max(lv, o2.level);
-                }
-                if (lv > op.level) op.level = lv;
+        // The folds of the encoders' weight-gradient partials (27 tiny tasks, one launch per convolution level = 9 launches of ~16 us in the
+        // middle of the backward pass) are needed by nothing but their module's Adam launch: as late as possible they share one launch per module.
+        std::vector<std::vector<int>> cons(pr.ops.size());
+        for (int oi = 0; oi < (int)pr.ops.size(); ++oi)
+            for (int d : pr.ops[oi].deps) cons[d].push_back(oi);
+        for (int oi = (int)pr.ops.size() - 1; oi >= 0; --oi) {
+            Op& op = pr.ops[oi];
+            if (op.type != OP_CONV_WRED) continue;
+            int lv = 1 << 30;
+            for (int c : cons[oi]) lv = std::min(lv, pr.ops[c].level - 1);
+            if (cons[oi].empty()) {   // (the optimizer is another program: the end of this one)
+                lv = 0;
+                for (const Op& o2 : pr.ops) lv = std::max(lv, o2.level);
             }
+            if (lv > op.level) op.level = lv;
         }
-        int maxlv = 0;
-        for (const Op& op : pr.ops) maxlv = std::max(maxlv, op.level);
+    }
+
+    // The launch family an op type merges into, which is also its place in the launch order of a (level, lane): the side-lane riders of a
+    // level share ONE launch with its gemm64 tiles (fql_side_kernel), at OP_GEMM64's place; every other type is a family of its own.
+    static OpType family(OpType t) {
+        return t == OP_WGRAD || t == OP_LNBWD || t == OP_POSTOS || t == OP_LOSS_CRITIC || t == OP_LOSS_Q || t == OP_LOSS_BC ? OP_GEMM64 : t;
+    }
+    // ... and how many of the n ops of a cell go into one launch: all of a merging family, the dQ/da tasks four at a time (the kernel takes
+    // them as its argument), one of everything else
+    static size_t per_launch(OpType fam, size_t n) {
+        const bool merges = fam == OP_GEMM || fam == OP_GEMM64 || fam == OP_CONV || fam == OP_CONV_U8 || fam == OP_CONV_WGRAD || fam == OP_CONV_WRED || fam == OP_CONV_WPREP;
+        return merges ? n : fam == OP_DGRAD0 ? 4 : 1;
+    }
+    using Cell = std::vector<Op*>;   // ops of one (level, lane, family), in op order
+    // Launch order: level ascending, then lane, then family in enum order, then op order within the family.
+    void form_launches(Program& pr, std::vector<void*>& owner) {
         pr.launches.clear();
         for (bool& b : pr.lane_used) b = false;
-        std::vector<int> launch_of(pr.ops.size(), -1);
-        auto up = [&](const void* src, size_t bytes) -> void* {   // a task table in device memory
-            void* d = dalloc(owner, bytes / sizeof(float) + 4);
-            if (bytes) HIP_CHECK(hipMemcpy(d, src, bytes, hipMemcpyHostToDevice));
-            return d;
-        };
-        for (int lv = 0; lv <= maxlv; ++lv) {
-          for (int lane = 0; lane < FQL_LANES; ++lane) {
-            for (int ty = 0; ty < OP_NUM_TYPES; ++ty) {
-                std::vector<const Op*> sel;
-                for (int oi = 0; oi < (int)pr.ops.size(); ++oi) {
-                    const Op& op = pr.ops[oi];
-                    if (op.level == lv && op.type == ty && op.lane == lane) sel.push_back(&op);
-                }
-                // the side-lane families of a level share ONE launch with its gemm64 tiles (fql_side_kernel)
-                if (ty == OP_WGRAD || ty == OP_LNBWD || ty == OP_POSTOS || ty == OP_LOSS_CRITIC || ty == OP_LOSS_Q || ty == OP_LOSS_BC)
-                    continue;  // folded into the OP_GEMM64 iteration
-                if (ty == OP_GEMM64) {
-                    std::vector<const Op*> selw, sell, selm;
-                    for (const Op& op : pr.ops) {
-                        if (op.level != lv || op.lane != lane) continue;
-                        if (op.type == OP_WGRAD) selw.push_back(&op);
-                        if (op.type == OP_LNBWD) sell.push_back(&op);
-                        if (op.type == OP_POSTOS || op.type == OP_LOSS_CRITIC || op.type == OP_LOSS_Q || op.type == OP_LOSS_BC) selm.push_back(&op);
-                    }
-                    if (sel.empty() && selw.empty() && sell.empty() && selm.empty()) continue;
-                    pr.lane_used[lane] = true;
-                    Launch L;
-                    L.type = OP_GEMM64;
-                    L.lane = lane;
-                    const int li = (int)pr.launches.size();
-                    for (const Op* o : sel) launch_of[o - pr.ops.data()] = li;
-                    for (const Op* o : selw) launch_of[o - pr.ops.data()] = li;
-                    for (const Op* o : sell) launch_of[o - pr.ops.data()] = li;
-                    for (const Op* o : selm) launch_of[o - pr.ops.data()] = li;
-                    // 32 x 64 tiles while a level is a latency chain (B = 256: 1.5 workgroups per CU), 64 x 64 once a task alone
-                    // brings >= 128 of them (M >= 1024: +2 % at B = 1024)
-                    int ri = 1;
-                    int tile = 0;
-                    std::vector<GemmTask> tg;
-                    // tile shape of the 32-row tasks of this launch: 32 x 64 unless 32 x 32 tiles deal out more evenly over the CUs
-                    // (e.g. 384 tiles of 32 x 64 = two tile times on half the CUs; 768 of 32 x 32 = three half-size tiles everywhere)
-                    int nj = 2;
-                    {
-                        int t64 = 0;
-                        double other = 0.0;   // in units of a 32 x 32 x 512 tile
-                        for (const Op* o : sel) {
-                            const GemmTask& t = o->gemm;
-                            const bool big = cfg.precision != 2 && t.M >= 1024 && t.M % 64 == 0;
-                            if (big) other += 4.0 * (t.M / 64) * (t.N / 64) * t.K / 512.0;
-                            else t64 += (t.M / 32) * (t.N / 64);
-                        }
-                        for (const Op* o : selw) other += 0.5 * (o->wgrad.Kin / 16) * ((o->wgrad.N + 63) / 64) * o->wgrad.M / 256.0;
-                        for (const Op* o : sell) other += 0.05 * o->ln.M;
-                        const int ncu = std::max(1, num_cus);
-                        const double m64 = 2.0 * ((t64 + ncu - 1) / ncu) + other / ncu, m32 = 1.0 * ((2 * t64 + ncu - 1) / ncu) + other / ncu;
-                        if (t64 > 0 && m32 < m64 && !wide_tiles) nj = 1;
-                    }
-                    for (const Op* o : sel) {
-                        GemmTask t = o->gemm;
-                        const int ri_t = cfg.precision != 2 && t.M >= 1024 && t.M % 64 == 0 ? 2 : 1;   // split bodies are 32-row tiles
-                        ri = std::max(ri, ri_t);
-                        t.tmt = ri_t;
-                        t.wk = ri_t == 2 ? 2 : nj;          // MFMA column tiles per wave: tile = 32 x (32 wk)
-                        t.ntn = t.N / (32 * t.wk); t.tile0 = tile;
-                        t.xg = 0;
-                        if (ri_t == 1 && tile % 8 == 0) {   // XCD-aware tile order: gm x gn = 8 blocks of the tile grid, fewest panel fetches
-                            const int ntm = t.M / 32;
-                            // gm row groups x gn column groups: an A row panel is fetched by gn XCDs, a B column panel by gm -> fewest panel bytes
-                            // (measured on the whole update: the rule's choice 3075, gm forced to 4: 3001-3061, 8: 2864-3026, 1: 2967-3040, no XCD order: 3025)
-                            double best = 1e30;
-                            for (int gm : {1, 2, 4, 8}) {
-                                const int gn = 8 / gm;
-                                if (ntm % gm || t.ntn % gn) continue;
-                                const double cost = (double)gn * t.M + (double)gm * t.N;
-                                if (cost < best) { best = cost; t.xg = gm; }
-                            }
-                        }
-                        tile += (t.M / (32 * ri_t)) * t.ntn;
-                        tg.push_back(t);
-                    }
-                    L.tile_w = tile;
-                    std::vector<WgradTask> tw;
-                    const int wkt = cfg.precision == 2 ? FQL_WGRAD_KT_SPLIT : FQL_WGRAD_KT;   // weight-gradient tile height of the body this launch runs
-                    int tilew = 0;
-                    for (const Op* o : selw) {
-                        WgradTask t = o->wgrad;
-                        t.ntn = (t.N + 63) / 64; t.tile0 = tilew;
-                        tilew += ((t.Kin + wkt - 1) / wkt) * t.ntn;
-                        tw.push_back(t);
-                    }
-                    L.tile_l = L.tile_w + tilew;
-                    std::vector<LnBwdTask> tl;
-                    int tilel = 0;
-                    for (const Op* o : sell) {
-                        LnBwdTask t = o->ln;
-                        t.ntiles_rows = (t.M + 3) / 4; t.tile0 = tilel;
-                        tilel += t.ntiles_rows + (t.dgamma ? t.H / 16 : 0);
-                        tl.push_back(t);
-                    }
-                    L.tile_m = L.tile_l + tilel;
-                    std::vector<MiscTask> tmisc;
-                    for (const Op* o : selm) {
-                        MiscTask t{};
-                        if (o->type == OP_POSTOS) { t.kind = MISC_POSTOS; t.po = o->postos; }
-                        else if (o->type == OP_LOSS_CRITIC) { t.kind = MISC_LOSS_CRITIC; t.lc = o->lc; }
-                        else if (o->type == OP_LOSS_Q) { t.kind = MISC_LOSS_Q; t.lq = o->lq; }
-                        else { t.kind = MISC_LOSS_BC; t.lb = o->lb; }
-                        tmisc.push_back(t);
-                    }
-                    L.grid = L.tile_m + (int)tmisc.size();
-                    L.ntasks = (int)tg.size(); L.n_w = (int)tw.size(); L.n_l = (int)tl.size();
-                    const size_t wlds = cfg.precision == 2 ? (size_t)(4 * 4 * 64 * 4 + 4 * 64) : (size_t)FQL_WGRAD_LDS_FLOATS;   // 16- / 32-input tiles
-                    size_t lds = sizeof(float) * (tg.empty() ? wlds
-                                             : ri == 2 ? (size_t)(2 * (32 * ri + 64) * 68 + 256)
-                                             : cfg.precision == 2 ? (size_t)FQL_TILE_SPLIT_LDS_FLOATS(nj)
-                                             : nj == 1 ? (size_t)(2 * 32 * 68 + 2 * 64 * 36 + 128) : (size_t)(2 * 32 * 68 + 2 * 64 * 68 + 128));
-                    lds = std::max(lds, sizeof(float) * (selw.empty() ? (size_t)0 : wlds));
-                    L.table = up(tg.data(), tg.size() * sizeof(GemmTask));
-                    L.table_w = up(tw.data(), tw.size() * sizeof(WgradTask));
-                    L.table_l = up(tl.data(), tl.size() * sizeof(LnBwdTask));
-                    L.table_m = up(tmisc.data(), tmisc.size() * sizeof(MiscTask));
-                    L.h_gemm = tg; L.h_wgrad = tw; L.h_ln = tl; L.h_misc = tmisc;
-                    bind_side(L, lds);
-                    pr.launches.push_back(L);
-                    continue;
-                }
-                if (sel.empty()) continue;
-                pr.lane_used[lane] = true;
-                if (ty == OP_CONV || ty == OP_CONV_U8 || ty == OP_CONV_WGRAD || ty == OP_CONV_WRED) {
-                    // every convolution-family op of this level and lane shares ONE launch (e.g. the same layer of the four
-                    // encoder passes): arg structs in an HBM table, workgroup ranges by tile0
-                    Launch L;
-                    L.type = (OpType)ty;
-                    L.lane = lane;
-                    for (const Op* o : sel) launch_of[o - pr.ops.data()] = (int)pr.launches.size();
-                    L.ntasks = (int)sel.size();
-                    int tile = 0;
-                    size_t lds = 0;
-                    bool pool_fused = false;
-                    if (ty == OP_CONV || ty == OP_CONV_U8) {
-                        std::vector<ConvArgs> tb;
-                        long long nb_all = 0;
-                        for (const Op* o : sel) nb_all += (long long)o->conv.N * (o->conv.H / o->conv.R);
-                        // persistent uint8 kernel: its 162 registers (launch bound 3 waves per SIMD) allow three workgroups per CU; exactly that many are launched (a fourth
-                        // round of workgroups would run alone) and dealt to the tasks in proportion to their row blocks (the one-step pass
-                        // holds [obs ; next_obs], twice the images of the others), rounded DOWN so the total never exceeds the resident set
-                        constexpr int u8_per_cu = 3;
-                        for (const Op* o : sel) {
-                            ConvArgs a = o->conv;
-                            const int nb = a.N * (a.H / a.R);
-                            a.tile0 = tile;
-                            // float layers: a workgroup per row block (persistent float layers were measured at +-1 %)
-                            a.nwg = ty == OP_CONV_U8 ? std::min(nb, std::max(1, (int)(((long long)u8_per_cu * num_cus * nb) / nb_all))) : nb;
-                            if (a.parg) {   // convolution + max-pool in one kernel: a workgroup per (image, pooled row pair)
-                                a.nwg = a.N * ((a.H + 3) / 4);
-                                pool_fused = true;
-                                lds = std::max(lds, (size_t)FQL_CONV_POOL_LDS_FLOATS(a.W, a.Ci, a.Co) * sizeof(float));
-                            } else if (pool_fused) invalid("internal: a launch mixes fused and plain convolutions");
-                            tile += a.nwg;
-                            lds = std::max(lds, ((size_t)(a.R + 2) * (a.W + 2) * (a.Ci + 4) + (size_t)a.Co * (9 * a.Ci + 4)) * sizeof(float));
-                            if (ty == OP_CONV && cfg.precision == 2) lds = std::max(lds, (size_t)FQL_CONV_SPLIT_LDS_WORDS(a.R, a.W, a.Ci, a.Co) * sizeof(float));
-                            tb.push_back(a);
-                        }
-                        L.table = up(tb.data(), tb.size() * sizeof(ConvArgs));
-                    } else if (ty == OP_CONV_WGRAD) {
-                        std::vector<ConvWgradArgs> tb;
-                        for (const Op* o : sel) {
-                            ConvWgradArgs a = o->cw;
-                            a.tile0 = tile; a.nwg = o->cw_grid;
-                            tile += a.nwg;
-                            lds = std::max(lds, ((size_t)(a.R + 2) * (a.W + 2) * (a.Ci + 4) + (size_t)a.R * a.W * (a.Co + 4)) * sizeof(float));
-                            tb.push_back(a);
-                        }
-                        L.table = up(tb.data(), tb.size() * sizeof(ConvWgradArgs));
-                    } else {
-                        std::vector<ConvWredArgs> tb;
-                        for (const Op* o : sel) {
-                            ConvWredArgs a = o->cwr;
-                            a.tile0 = tile;
-                            tile += ((9 * a.Ci + 1) * a.Co + 63) / 64;
-                            tb.push_back(a);
-                        }
-                        L.table = up(tb.data(), tb.size() * sizeof(ConvWredArgs));
-                    }
-                    L.grid = tile;
-                    bind_conv(L, pool_fused, lds);
-                    pr.launches.push_back(L);
-                    continue;
-                }
-                if (ty == OP_DGRAD0 && !sel.empty()) {   // the members' tasks of a level in launches of up to four (the kernel takes them as its argument)
-                    for (size_t i0 = 0; i0 < sel.size(); i0 += 4) {
-                        Launch L;
-                        L.type = OP_DGRAD0;
-                        L.lane = lane;
-                        Dgrad0Args a{};
-                        a.col0 = sel[i0]->gemm.i1;
-                        for (size_t i = i0; i < std::min(sel.size(), i0 + 4); ++i) {
-                            if (sel[i]->gemm.M != sel[i0]->gemm.M || sel[i]->gemm.i1 != sel[i0]->gemm.i1) invalid("internal: dQ/da tasks of one level differ in shape");
-                            a.t[a.ntasks++] = sel[i]->gemm;
-                            launch_of[sel[i] - pr.ops.data()] = (int)pr.launches.size();
-                        }
-                        L.k = bind(fql_dgrad0_kernel, a.ntasks * (sel[i0]->gemm.M / 16), a);
-                        pr.launches.push_back(L);
-                    }
-                    continue;
-                }
-                if (ty == OP_CONV_WPREP && sel.size() > 1) {   // the encoder passes of one level refresh their LDS-layout weight copies in ONE launch
-                    int tot = 0;
-                    for (const Op* o : sel) tot += o->wprep_n;
-                    ConvWprepTask* all = (ConvWprepTask*)dalloc(owner, (size_t)tot * sizeof(ConvWprepTask) / sizeof(float) + 4);
-                    int at = 0;
-                    for (const Op* o : sel) {
-                        HIP_CHECK(hipMemcpy(all + at, o->wprep_tasks, (size_t)o->wprep_n * sizeof(ConvWprepTask), hipMemcpyDeviceToDevice));
-                        at += o->wprep_n;
-                        launch_of[o - pr.ops.data()] = (int)pr.launches.size();
-                    }
-                    Launch L;
-                    L.type = OP_CONV_WPREP;
-                    L.k = bind_wprep(all, tot);
-                    L.lane = lane;
-                    pr.launches.push_back(L);
-                    continue;
-                }
-                if (ty != OP_GEMM) {
-                    for (const Op* o : sel) {
-                        Launch L;
-                        L.type = (OpType)ty;
-                        L.k = o->k;
-                        L.lane = lane;
-                        launch_of[o - pr.ops.data()] = (int)pr.launches.size();
-                        pr.launches.push_back(L);
-                    }
-                    continue;
-                }
-                Launch L;
-                L.type = OP_GEMM;
-                L.lane = lane;
-                for (const Op* o : sel) launch_of[o - pr.ops.data()] = (int)pr.launches.size();
-                L.ntasks = (int)sel.size();
-                int tile = 0;
-                std::vector<GemmTask> tb;
-                for (const Op* o : sel) {
-                    GemmTask t = o->gemm;
-                    t.wk = (t.N <= 16) ? 4 : 2;
-                    // (two 16-row tiles per workgroup sharing each B fragment were tried on the throughput lane: not kept)
-                    t.tmt = 1;
-                    t.ntn = (t.N / 16 + (4 / t.wk) - 1) / (4 / t.wk);
-                    t.tile0 = tile;
-                    tile += (t.M / 16) * t.ntn;
-                    tb.push_back(t);
-                }
-                L.table = up(tb.data(), tb.size() * sizeof(GemmTask));
-                L.grid = tile;
-                L.h_gemm = tb;
-                bind_gemm16(L);
-                pr.launches.push_back(L);
-            }
-          }
+        std::map<std::tuple<int, int, int>, Cell> cells;
+        for (Op& op : pr.ops) {
+            op.launch = -1;
+            if (op.lane >= 0 && op.lane < FQL_LANES) cells[{op.level, op.lane, (int)family(op.type)}].push_back(&op);
         }
-        // cross-lane edges (computed below) are printed by the dump too: move the dump after them
-        auto dump_program = [&]() {
-            int cnt[FQL_LANES] = {};
-            for (const Launch& L : pr.launches) {
-                cnt[L.lane]++;
-                int lv = -1;
-                for (int oi = 0; oi < (int)pr.ops.size(); ++oi) if (launch_of[oi] == (int)(&L - pr.launches.data())) lv = pr.ops[oi].level;
-                fprintf(stderr, "[fql] #%2d level %3d lane %d type %2d ntasks %2d grid %5d waits[", (int)(&L - pr.launches.data()), lv, L.lane, (int)L.type, L.ntasks, L.grid);
-                for (int w : L.waits) fprintf(stderr, "%d ", w);
-                fprintf(stderr, "] :");
-                for (int oi = 0; oi < (int)pr.ops.size(); ++oi) {
-                    if (launch_of[oi] != (int)(&L - pr.launches.data())) continue;
-                    const Op& o = pr.ops[oi];
-                    if (o.type == OP_GEMM || o.type == OP_GEMM64) fprintf(stderr, " g%s(%dx%dx%d%s)", o.type == OP_GEMM64 ? "64" : "16", o.gemm.M, o.gemm.N, o.gemm.K, (o.gemm.flags & GF_TRANS_B) ? "T" : "");
-                    else if (o.type == OP_WGRAD) fprintf(stderr, " w(%dx%dx%d)", o.wgrad.M, o.wgrad.Kin, o.wgrad.N);
-                    else if (o.type == OP_LNBWD) fprintf(stderr, " ln(%d)", o.ln.M);
-                    else fprintf(stderr, " t%d", (int)o.type);
-                }
-                fprintf(stderr, "\n");
+        for (const auto& [key, ops] : cells) {
+            const OpType fam = (OpType)std::get<2>(key);
+            const size_t n = per_launch(fam, ops.size());
+            for (size_t i = 0; i < ops.size(); i += n) {
+                const Cell part(ops.begin() + i, ops.begin() + std::min(ops.size(), i + n));
+                for (Op* o : part) o->launch = (int)pr.launches.size();
+                pr.lane_used[part[0]->lane] = true;
+                pr.launches.push_back(form(fam, part, owner));
             }
-            fprintf(stderr, "[fql] launches per lane:");
-            for (int l = 0; l < FQL_LANES; ++l) fprintf(stderr, " %d", cnt[l]);
-            fprintf(stderr, "\n");
-        };
-        for (int oi = 0; oi < (int)pr.ops.size(); ++oi) {   // algorithmic MACs per launch (real, unpadded layer widths are within 1 % of these)
-            const Op& o = pr.ops[oi];
-            const int li = launch_of[oi];
-            if (li < 0) continue;
-            double m = 0.0;
-            if (o.type == OP_GEMM || o.type == OP_GEMM64 || o.type == OP_HEAD_DGRAD) m = (double)o.gemm.M * o.gemm.N * o.gemm.K;
-            else if (o.type == OP_DGRAD0) m = (double)o.gemm.M * 16.0 * o.gemm.K;
-            else if (o.type == OP_WGRAD) m = (double)o.wgrad.M * o.wgrad.Kin * o.wgrad.N;
-            else if (o.type == OP_CHAIN) m = o.macs;
-            else if (o.type == OP_CONV || o.type == OP_CONV_U8) m = (double)o.conv.N * o.conv.H * o.conv.W * 9.0 * (o.conv.transposed ? o.conv.Ci : o.conv.Ci_real) * o.conv.Co;
-            else if (o.type == OP_CONV_WGRAD) m = (double)o.cw.N * o.cw.H * o.cw.W * 9.0 * o.cw.Ci_real * o.cw.Co;
-            pr.launches[li].macs += m;
         }
-        // cross-lane edges: a launch waits for the latest launch of the other lane it depends on (lane streams
-        // are in-order, so that covers the earlier ones); skip waits already implied by an earlier wait.
+    }
+    // one former per family: the ops of a launch in, the launch out - task fields, table upload and bind_* call inside
+    Launch form(OpType fam, const Cell& ops, std::vector<void*>& owner) {
+        switch (fam) {
+        case OP_GEMM: return form_gemm16(ops, owner);
+        case OP_GEMM64: return form_side(ops, owner);
+        case OP_CONV: case OP_CONV_U8: case OP_CONV_WGRAD: case OP_CONV_WRED: return form_conv(ops, owner);
+        case OP_DGRAD0: return form_dgrad0(ops);
+        case OP_CONV_WPREP: if (ops.size() > 1) return form_wprep(ops, owner); [[fallthrough]];   // a lone one keeps its own bound launch
+        default: return form_single(*ops[0]);
+        }
+    }
+    void* upload(std::vector<void*>& owner, const void* src, size_t bytes) {   // a task table in device memory
+        void* d = dalloc(owner, bytes / sizeof(float) + 4);
+        if (bytes) HIP_CHECK(hipMemcpy(d, src, bytes, hipMemcpyHostToDevice));
+        return d;
+    }
+    static Launch form_single(const Op& o) {   // a launch of its own, bound where the op was emitted
+        Launch L(o.type, o.lane);
+        L.k = o.k;
+        return L;
+    }
+
+    // The tile policies of the side launch.
+    // 32 x 64 tiles while a level is a latency chain (B = 256: 1.5 workgroups per CU), 64 x 64 once a task alone
+    // brings >= 128 of them (M >= 1024: +2 % at B = 1024); returns the tile's rows / 32 (split bodies are 32-row tiles)
+    int side_ri(const GemmTask& t) const { return cfg.precision != 2 && t.M >= 1024 && t.M % 64 == 0 ? 2 : 1; }
+    // tile shape of the 32-row tasks of a launch: 32 x 64 unless 32 x 32 tiles deal out more evenly over the CUs
+    // (e.g. 384 tiles of 32 x 64 = two tile times on half the CUs; 768 of 32 x 32 = three half-size tiles everywhere); returns the tile's columns / 32
+    int side_nj(const Cell& g, const Cell& w, const Cell& l) const {
+        int t64 = 0;
+        double other = 0.0;   // in units of a 32 x 32 x 512 tile
+        for (const Op* o : g) {
+            const GemmTask& t = o->gemm;
+            if (side_ri(t) == 2) other += 4.0 * (t.M / 64) * (t.N / 64) * t.K / 512.0;
+            else t64 += (t.M / 32) * (t.N / 64);
+        }
+        for (const Op* o : w) other += 0.5 * (o->wgrad.Kin / 16) * ((o->wgrad.N + 63) / 64) * o->wgrad.M / 256.0;
+        for (const Op* o : l) other += 0.05 * o->ln.M;
+        const int ncu = std::max(1, num_cus);
+        const double m64 = 2.0 * ((t64 + ncu - 1) / ncu) + other / ncu, m32 = 1.0 * ((2 * t64 + ncu - 1) / ncu) + other / ncu;
+        return t64 > 0 && m32 < m64 && !wide_tiles ? 1 : 2;
+    }
+    // XCD-aware tile order of a 32-row task (ntn set): gm x gn = 8 blocks of the tile grid, fewest panel fetches; returns gm, 0 = none fits
+    static int side_xg(const GemmTask& t) {
+        const int ntm = t.M / 32;
+        // gm row groups x gn column groups: an A row panel is fetched by gn XCDs, a B column panel by gm -> fewest panel bytes
+        // (measured on the whole update: the rule's choice 3075, gm forced to 4: 3001-3061, 8: 2864-3026, 1: 2967-3040, no XCD order: 3025)
+        int xg = 0;
+        double best = 1e30;
+        for (int gm : {1, 2, 4, 8}) {
+            const int gn = 8 / gm;
+            if (ntm % gm || t.ntn % gn) continue;
+            const double cost = (double)gn * t.M + (double)gm * t.N;
+            if (cost < best) { best = cost; xg = gm; }
+        }
+        return xg;
+    }
+    // OP_GEMM64 and its riders: the gemm64 tiles of the cell, then its weight-gradient, LayerNorm-backward and loss / metric tasks
+    Launch form_side(const Cell& ops, std::vector<void*>& owner) {
+        Cell sel, selw, sell, selm;
+        for (Op* o : ops) (o->type == OP_GEMM64 ? sel : o->type == OP_WGRAD ? selw : o->type == OP_LNBWD ? sell : selm).push_back(o);
+        Launch L(OP_GEMM64, ops[0]->lane);
+        const int nj = side_nj(sel, selw, sell);
+        int ri = 1;
+        int tile = 0;
+        for (const Op* o : sel) {
+            GemmTask t = o->gemm;
+            t.tmt = side_ri(t);
+            ri = std::max(ri, t.tmt);
+            t.wk = t.tmt == 2 ? 2 : nj;          // MFMA column tiles per wave: tile = 32 x (32 wk)
+            t.ntn = t.N / (32 * t.wk); t.tile0 = tile;
+            t.xg = t.tmt == 1 && tile % 8 == 0 ? side_xg(t) : 0;
+            tile += (t.M / (32 * t.tmt)) * t.ntn;
+            L.h_gemm.push_back(t);
+        }
+        L.tile_w = tile;
+        const int wkt = cfg.precision == 2 ? FQL_WGRAD_KT_SPLIT : FQL_WGRAD_KT;   // weight-gradient tile height of the body this launch runs
+        int tilew = 0;
+        for (const Op* o : selw) {
+            WgradTask t = o->wgrad;
+            t.ntn = (t.N + 63) / 64; t.tile0 = tilew;
+            tilew += ((t.Kin + wkt - 1) / wkt) * t.ntn;
+            L.h_wgrad.push_back(t);
+        }
+        L.tile_l = L.tile_w + tilew;
+        int tilel = 0;
+        for (const Op* o : sell) {
+            LnBwdTask t = o->ln;
+            t.ntiles_rows = (t.M + 3) / 4; t.tile0 = tilel;
+            tilel += t.ntiles_rows + (t.dgamma ? t.H / 16 : 0);
+            L.h_ln.push_back(t);
+        }
+        L.tile_m = L.tile_l + tilel;
+        for (const Op* o : selm) {
+            MiscTask t{};
+            if (o->type == OP_POSTOS) { t.kind = MISC_POSTOS; t.po = o->postos; }
+            else if (o->type == OP_LOSS_CRITIC) { t.kind = MISC_LOSS_CRITIC; t.lc = o->lc; }
+            else if (o->type == OP_LOSS_Q) { t.kind = MISC_LOSS_Q; t.lq = o->lq; }
+            else { t.kind = MISC_LOSS_BC; t.lb = o->lb; }
+            L.h_misc.push_back(t);
+        }
+        L.grid = L.tile_m + (int)L.h_misc.size();
+        L.ntasks = (int)L.h_gemm.size(); L.n_w = (int)L.h_wgrad.size(); L.n_l = (int)L.h_ln.size();
+        const size_t wlds = cfg.precision == 2 ? (size_t)(4 * 4 * 64 * 4 + 4 * 64) : (size_t)FQL_WGRAD_LDS_FLOATS;   // 16- / 32-input tiles
+        size_t lds = sizeof(float) * (sel.empty() ? wlds
+                                 : ri == 2 ? (size_t)(2 * (32 * ri + 64) * 68 + 256)
+                                 : cfg.precision == 2 ? (size_t)FQL_TILE_SPLIT_LDS_FLOATS(nj)
+                                 : nj == 1 ? (size_t)(2 * 32 * 68 + 2 * 64 * 36 + 128) : (size_t)(2 * 32 * 68 + 2 * 64 * 68 + 128));
+        lds = std::max(lds, sizeof(float) * (selw.empty() ? (size_t)0 : wlds));
+        L.table = upload(owner, L.h_gemm.data(), L.h_gemm.size() * sizeof(GemmTask));
+        L.table_w = upload(owner, L.h_wgrad.data(), L.h_wgrad.size() * sizeof(WgradTask));
+        L.table_l = upload(owner, L.h_ln.data(), L.h_ln.size() * sizeof(LnBwdTask));
+        L.table_m = upload(owner, L.h_misc.data(), L.h_misc.size() * sizeof(MiscTask));
+        bind_side(L, lds);
+        return L;
+    }
+    // OP_CONV, OP_CONV_U8, OP_CONV_WGRAD, OP_CONV_WRED: every convolution-family op of a cell shares ONE launch (e.g. the same layer of the
+    // four encoder passes): arg structs in an HBM table, workgroup ranges by tile0
+    Launch form_conv(const Cell& sel, std::vector<void*>& owner) {
+        Launch L(sel[0]->type, sel[0]->lane);
+        L.ntasks = (int)sel.size();
+        int tile = 0;
+        size_t lds = 0;
+        bool pool_fused = false;
+        if (L.type == OP_CONV || L.type == OP_CONV_U8) {
+            std::vector<ConvArgs> tb;
+            long long nb_all = 0;
+            for (const Op* o : sel) nb_all += (long long)o->conv.N * (o->conv.H / o->conv.R);
+            // persistent uint8 kernel: its 162 registers (launch bound 3 waves per SIMD) allow three workgroups per CU; exactly that many are launched (a fourth
+            // round of workgroups would run alone) and dealt to the tasks in proportion to their row blocks (the one-step pass
+            // holds [obs ; next_obs], twice the images of the others), rounded DOWN so the total never exceeds the resident set
+            constexpr int u8_per_cu = 3;
+            for (const Op* o : sel) {
+                ConvArgs a = o->conv;
+                const int nb = a.N * (a.H / a.R);
+                a.tile0 = tile;
+                // float layers: a workgroup per row block (persistent float layers were measured at +-1 %)
+                a.nwg = L.type == OP_CONV_U8 ? std::min(nb, std::max(1, (int)(((long long)u8_per_cu * num_cus * nb) / nb_all))) : nb;
+                if (a.parg) {   // convolution + max-pool in one kernel: a workgroup per (image, pooled row pair)
+                    a.nwg = a.N * ((a.H + 3) / 4);
+                    pool_fused = true;
+                    lds = std::max(lds, (size_t)FQL_CONV_POOL_LDS_FLOATS(a.W, a.Ci, a.Co) * sizeof(float));
+                } else if (pool_fused) invalid("internal: a launch mixes fused and plain convolutions");
+                tile += a.nwg;
+                lds = std::max(lds, ((size_t)(a.R + 2) * (a.W + 2) * (a.Ci + 4) + (size_t)a.Co * (9 * a.Ci + 4)) * sizeof(float));
+                if (L.type == OP_CONV && cfg.precision == 2) lds = std::max(lds, (size_t)FQL_CONV_SPLIT_LDS_WORDS(a.R, a.W, a.Ci, a.Co) * sizeof(float));
+                tb.push_back(a);
+            }
+            L.table = upload(owner, tb.data(), tb.size() * sizeof(ConvArgs));
+        } else if (L.type == OP_CONV_WGRAD) {
+            std::vector<ConvWgradArgs> tb;
+            for (const Op* o : sel) {
+                ConvWgradArgs a = o->cw;
+                a.tile0 = tile; a.nwg = o->cw_grid;
+                tile += a.nwg;
+                lds = std::max(lds, ((size_t)(a.R + 2) * (a.W + 2) * (a.Ci + 4) + (size_t)a.R * a.W * (a.Co + 4)) * sizeof(float));
+                tb.push_back(a);
+            }
+            L.table = upload(owner, tb.data(), tb.size() * sizeof(ConvWgradArgs));
+        } else {
+            std::vector<ConvWredArgs> tb;
+            for (const Op* o : sel) {
+                ConvWredArgs a = o->cwr;
+                a.tile0 = tile;
+                tile += ((9 * a.Ci + 1) * a.Co + 63) / 64;
+                tb.push_back(a);
+            }
+            L.table = upload(owner, tb.data(), tb.size() * sizeof(ConvWredArgs));
+        }
+        L.grid = tile;
+        bind_conv(L, pool_fused, lds);
+        return L;
+    }
+    // OP_DGRAD0: up to four members' dQ/da tasks of a level, as the kernel's argument
+    Launch form_dgrad0(const Cell& sel) {
+        Launch L(OP_DGRAD0, sel[0]->lane);
+        Dgrad0Args a{};
+        a.col0 = sel[0]->gemm.i1;
+        for (const Op* o : sel) {
+            if (o->gemm.M != sel[0]->gemm.M || o->gemm.i1 != sel[0]->gemm.i1) invalid("internal: dQ/da tasks of one level differ in shape");
+            a.t[a.ntasks++] = o->gemm;
+        }
+        L.k = bind(fql_dgrad0_kernel, a.ntasks * (sel[0]->gemm.M / 16), a);
+        return L;
+    }
+    // OP_CONV_WPREP, more than one in a cell: the encoder passes of one level refresh their LDS-layout weight copies in ONE launch
+    Launch form_wprep(const Cell& sel, std::vector<void*>& owner) {
+        int tot = 0;
+        for (const Op* o : sel) tot += o->wprep_n;
+        ConvWprepTask* all = (ConvWprepTask*)dalloc(owner, (size_t)tot * sizeof(ConvWprepTask) / sizeof(float) + 4);
+        int at = 0;
+        for (const Op* o : sel) {
+            HIP_CHECK(hipMemcpy(all + at, o->wprep_tasks, (size_t)o->wprep_n * sizeof(ConvWprepTask), hipMemcpyDeviceToDevice));
+            at += o->wprep_n;
+        }
+        Launch L(OP_CONV_WPREP, sel[0]->lane);
+        L.k = bind_wprep(all, tot);
+        return L;
+    }
+    // OP_GEMM: the 16-row tasks of a cell, from a table
+    Launch form_gemm16(const Cell& sel, std::vector<void*>& owner) {
+        Launch L(OP_GEMM, sel[0]->lane);
+        L.ntasks = (int)sel.size();
+        int tile = 0;
+        for (const Op* o : sel) {
+            GemmTask t = o->gemm;
+            t.wk = (t.N <= 16) ? 4 : 2;
+            // (two 16-row tiles per workgroup sharing each B fragment were tried on the throughput lane: not kept)
+            t.tmt = 1;
+            t.ntn = (t.N / 16 + (4 / t.wk) - 1) / (4 / t.wk);
+            t.tile0 = tile;
+            tile += (t.M / 16) * t.ntn;
+            L.h_gemm.push_back(t);
+        }
+        L.table = upload(owner, L.h_gemm.data(), L.h_gemm.size() * sizeof(GemmTask));
+        L.grid = tile;
+        bind_gemm16(L);
+        return L;
+    }
+
+    // algorithmic multiply-accumulates of one op
+    static double op_macs(const Op& o) {
+        if (o.type == OP_GEMM || o.type == OP_GEMM64 || o.type == OP_HEAD_DGRAD) return (double)o.gemm.M * o.gemm.N * o.gemm.K;
+        if (o.type == OP_DGRAD0) return (double)o.gemm.M * 16.0 * o.gemm.K;
+        if (o.type == OP_WGRAD) return (double)o.wgrad.M * o.wgrad.Kin * o.wgrad.N;
+        if (o.type == OP_CHAIN) return o.macs;
+        if (o.type == OP_CONV || o.type == OP_CONV_U8) return (double)o.conv.N * o.conv.H * o.conv.W * 9.0 * (o.conv.transposed ? o.conv.Ci : o.conv.Ci_real) * o.conv.Co;
+        if (o.type == OP_CONV_WGRAD) return (double)o.cw.N * o.cw.H * o.cw.W * 9.0 * o.cw.Ci_real * o.cw.Co;
+        return 0.0;
+    }
+    // cross-lane edges: a launch waits for the latest launch of the other lane it depends on (lane streams
+    // are in-order, so that covers the earlier ones); skip waits already implied by an earlier wait.
+    static void cross_lane_waits(Program& pr) {
+        std::vector<int> need(pr.launches.size() * FQL_LANES, -1);   // [launch][other lane]: the latest launch there it depends on
+        for (const Op& o : pr.ops) {
+            if (o.launch < 0) continue;
+            for (int d : o.deps) {
+                const int dl = pr.ops[d].launch;
+                const int ol = pr.launches[dl].lane;
+                int& nd = need[o.launch * FQL_LANES + ol];
+                if (ol != o.lane) nd = std::max(nd, dl);
+            }
+        }
         int waited_upto[FQL_LANES][FQL_LANES];  // [waiting lane][other lane]: highest launch index already waited for
         for (auto& r : waited_upto) for (int& v : r) v = -1;
         for (int li = 0; li < (int)pr.launches.size(); ++li) {
             Launch& L = pr.launches[li];
-            int need[FQL_LANES];
-            for (int& v : need) v = -1;
-            for (int oi = 0; oi < (int)pr.ops.size(); ++oi) {
-                if (launch_of[oi] != li) continue;
-                for (int d : pr.ops[oi].deps) {
-                    const int dl = launch_of[d];
-                    const int ol = pr.launches[dl].lane;
-                    if (ol != L.lane) need[ol] = std::max(need[ol], dl);
-                }
+            for (int ol = 0; ol < FQL_LANES; ++ol) {
+                const int nd = need[li * FQL_LANES + ol];
+                if (nd <= waited_upto[L.lane][ol]) continue;
+                L.waits.push_back(nd);
+                pr.launches[nd].record_after = true;
+                waited_upto[L.lane][ol] = nd;
             }
-            for (int ol = 0; ol < FQL_LANES; ++ol)
-                if (need[ol] > waited_upto[L.lane][ol]) {
-                    L.waits.push_back(need[ol]);
-                    pr.launches[need[ol]].record_after = true;
-                    waited_upto[L.lane][ol] = need[ol];
-                }
         }
-        if (getenv("FQL_DUMP")) dump_program();
-        // Two FORKED lanes (>= 1; lane 0 is the capture's origin stream) must not wait on each other in both directions: the HIP
-        // runtime bundled with torch 2.10 (ROCm 7.0) walks the resulting cycle of parallel capture streams forever in
-        // hip::Stream::EndCapture (a segmentation fault by stack exhaustion; diagnosed with rocgdb, profiles/r02_capture_crash.txt).
-        // The default programs keep such edges one-directional by construction; placement overrides that do not are refused.
+    }
+    void dump_program(const Program& pr) const {   // FQL_DUMP: the launches with their level, waits and ops
+        std::vector<int> level(pr.launches.size(), -1);
+        std::vector<std::string> what(pr.launches.size());
+        char b[96];
+        for (const Op& o : pr.ops) {
+            if (o.launch < 0) continue;
+            level[o.launch] = o.level;
+            if (o.type == OP_GEMM || o.type == OP_GEMM64) snprintf(b, sizeof b, " g%s(%dx%dx%d%s)", o.type == OP_GEMM64 ? "64" : "16", o.gemm.M, o.gemm.N, o.gemm.K, (o.gemm.flags & GF_TRANS_B) ? "T" : "");
+            else if (o.type == OP_WGRAD) snprintf(b, sizeof b, " w(%dx%dx%d)", o.wgrad.M, o.wgrad.Kin, o.wgrad.N);
+            else if (o.type == OP_LNBWD) snprintf(b, sizeof b, " ln(%d)", o.ln.M);
+            else snprintf(b, sizeof b, " t%d", (int)o.type);
+            what[o.launch] += b;
+        }
+        int cnt[FQL_LANES] = {};
+        for (int li = 0; li < (int)pr.launches.size(); ++li) {
+            const Launch& L = pr.launches[li];
+            cnt[L.lane]++;
+            fprintf(stderr, "[fql] #%2d level %3d lane %d type %2d ntasks %2d grid %5d waits[", li, level[li], L.lane, (int)L.type, L.ntasks, L.grid);
+            for (int w : L.waits) fprintf(stderr, "%d ", w);
+            fprintf(stderr, "] :%s\n", what[li].c_str());
+        }
+        fprintf(stderr, "[fql] launches per lane:");
+        for (int l = 0; l < FQL_LANES; ++l) fprintf(stderr, " %d", cnt[l]);
+        fprintf(stderr, "\n");
+    }
+    // Two FORKED lanes (>= 1; lane 0 is the capture's origin stream) must not wait on each other in both directions: the HIP
+    // runtime bundled with torch 2.10 (ROCm 7.0) walks the resulting cycle of parallel capture streams forever in
+    // hip::Stream::EndCapture (a segmentation fault by stack exhaustion; diagnosed with rocgdb, profiles/r02_capture_crash.txt).
+    // The default programs keep such edges one-directional by construction; placement overrides that do not are refused.
+    static void check_lane_edges(const Program& pr) {
         bool edge[FQL_LANES][FQL_LANES] = {};
         for (const Launch& L : pr.launches)
             for (int w : L.waits) edge[pr.launches[w].lane][L.lane] = true;
