@@ -113,6 +113,7 @@ SYMBOLS = {
     'fql_total_loss': (_I, [_VP] + _BATCH + [C.POINTER(FqlNoise), C.POINTER(_F), C.POINTER(_F), _VP]),
     'fql_sample_actions': (_I, [_VP, _VP, _I, _VP, _U64, _VP, _VP]),
     'fql_flow_actions': (_I, [_VP, _VP, _VP, _I, _VP, _VP]),
+    'fql_module_forward': (_I, [_VP, C.c_char_p, _VP, _VP, _VP, _I, _VP, _VP]),
     'fql_dataset_upload': (_I, [_VP, _I64, _I64, _VP, _VP, _VP, _VP, _VP]),
     'fql_dataset_add': (_I, [_VP, _VP, _VP, _F, _F, _VP]),
     'fql_dataset_size': (_I, [_VP, C.POINTER(_I64), C.POINTER(_I64)]),

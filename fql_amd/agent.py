@@ -7,6 +7,7 @@ Same method names, keyword names and return shapes as the reference so its call 
     actions = agent.sample_actions(observations=ob, temperature=1, seed=key)  # main.py:225
     loss, info = agent.total_loss(val_batch, grad_params=None)                # main.py:284
     actions = agent.compute_flow_actions(observations, noises)                # agents/fql.py:155
+    qs = agent.network.select('critic')(observations, actions=actions)        # agents/fql.py:36,70 (stored parameters)
 
 The reference is functional (update returns a NEW agent, callers rebind); here the engine owns the
 state in HBM, update mutates it and returns ``self`` -- compatible with every reference call site.
@@ -168,12 +169,37 @@ class LazyInfo(dict):
         return (dict, (self.to_dict(),))
 
 
+class _Network:
+    """`agent.network` as far as reference call sites use it for forward queries: select(name) (utils/flax_utils.py:116-118) returns the
+    module's forward on the stored parameters (fql_module_forward).  Module names are the reference's without the `modules_` prefix."""
+
+    def __init__(self, agent):
+        self._agent = agent
+
+    def select(self, name):
+        mods = self._agent._modules
+        if name not in mods:
+            raise KeyError(f'{self._agent._name} has no module {name!r} (its modules: {", ".join(mods)})')
+        agent, family = self._agent, mods[name]
+        if family in ('pair', 'value'):
+            def module(observations, actions=None, params=None):   # utils/networks.py Value.__call__
+                return agent._module_forward(name, family, observations, actions, None, params)
+        else:
+            def module(observations, actions, times=None, is_encoded=False, params=None):   # ActorVectorField.__call__
+                return agent._module_forward(name, family, observations, actions, times, params)   # (is_encoded: no encoder on a state agent)
+        module.__name__ = name
+        return module
+
+
 class FQLAgent:
     """Flow Q-learning agent backed by the MI355X step engine."""
 
     _name = 'FQL'
     _loss_infos = 10          # infos fql_total_loss writes (the total-loss probe has no gradient statistics)
     _jax_sample_noise = True  # sample_actions(seed=<JAX key>) draws the reference's noise on the host
+    # network.select(name): the module's family.  'pair': Value(obs, actions) of the 2-member critic -> [2, n]; 'value': Value(obs) -> [n];
+    # 'field_t': ActorVectorField(obs, actions, times) -> [n, act]; 'field': ActorVectorField(obs, noises) -> [n, act]
+    _modules = {'critic': 'pair', 'target_critic': 'pair', 'actor_bc_flow': 'field_t', 'actor_onestep_flow': 'field'}
 
     def __init__(self, handle, config, seed):
         self._lib = _cabi.load()
@@ -466,6 +492,43 @@ class FQLAgent:
             return ((self._seed << 20) ^ self._sample_calls) & 0xFFFFFFFFFFFFFFFF
         return _seed_to_u64(seed) & 0xFFFFFFFFFFFFFFFF
 
+    # -- forward queries: agent.network.select(name)(...) -----------------------------------------
+    @property
+    def network(self):
+        """`agent.network.select('critic')(observations, actions=actions)` and the like (utils/flax_utils.py:116-118; 47 call sites in
+        agents/*.py): one module's forward on the stored parameters, on the caller's rows.  numpy in, numpy out; CUDA tensors in, a CUDA
+        tensor out on torch's current stream.  Parameters are read with get_params()."""
+        if not self._modules:
+            raise NotImplementedError(f"{self._name}: network.select is not available (the module's input carries host-built embeddings)")
+        if len(self.config['ob_dims']) == 3:
+            raise NotImplementedError(f"{self._name}: network.select is not available on visual agents (the module's encoder would run first)")
+        return _Network(self)
+
+    def _module_forward(self, name, family, observations, actions, times, params):
+        if params is not None:
+            raise NotImplementedError(f'network.select({name!r})(params=...) is jax.grad plumbing; the stored parameters are used')
+        od, ad = self.config['ob_dims'][0], self.config['action_dim']
+        oshape = tuple(np.shape(observations))
+        if not oshape or oshape[-1] != od:
+            raise ValueError(f'observations last dim must be {od}, got {oshape}')
+        lead = oshape[:-1]
+        n = int(np.prod(lead)) if lead else 1
+        if n < 1:
+            raise ValueError(f'observations hold no rows: {oshape}')
+        takes_actions, takes_times = family != 'value', family == 'field_t'
+        if takes_actions != (actions is not None):
+            raise ValueError(f'{name}: ' + ('actions are required' if takes_actions else 'a value module takes observations only (actions=None)'))
+        if actions is not None and tuple(np.shape(actions)) != lead + (ad,):
+            raise ValueError(f'{name}: actions must be {lead + (ad,)}, got {tuple(np.shape(actions))}')
+        if takes_times != (times is not None):
+            raise ValueError(f'{name}: ' + ('times are required' if takes_times else 'the module takes no times (times=None)'))
+        if times is not None and tuple(np.shape(times)) not in (lead, lead + (1,)):
+            raise ValueError(f'{name}: times must be {lead} or {lead + (1,)}, got {tuple(np.shape(times))}')
+        o, a, t = _Arg(observations, (n, od)), _Arg(actions, (n, ad)), _Arg(times, (n,))
+        out, optr = self._actions_out(observations, {'pair': (2,) + lead, 'value': lead}.get(family, lead + (ad,)))
+        self._check(self._lib.fql_module_forward(self._h, name.encode(), o.ptr, a.ptr, t.ptr, n, optr, self._stream([o, a, t])))
+        return out
+
     # -- device-resident dataset (utils/datasets.py Dataset/ReplayBuffer on the GPU) -------------
     def upload_dataset(self, dataset, capacity: Optional[int] = None, frame_stack: Optional[int] = None, p_aug: Optional[float] = None):
         """Dataset.create(...) arrays -> HBM.  Visual agents: `observations` / `next_observations` are the uint8 FRAMES
@@ -710,6 +773,7 @@ class KindAgent(FQLAgent):
 
     _refused = ()
     _update_fn = _update_dataset_fn = _sample_fn = None
+    _modules = {'critic': 'pair', 'target_critic': 'pair'}   # (a Gaussian actor returns a distribution object in the reference: not a query)
     _jax_sample_noise = False
 
     def __init_subclass__(cls, **kw):

@@ -70,6 +70,7 @@ class BCAgent(KindAgent):
     """Flow-matching BC agent backed by the MI355X step engine.  update: agents/bc.py:72-84, 4 infos (BC_INFO_KEYS)."""
 
     _name = 'BC'
+    _modules = {}   # network.select: the policy's input carries the host-built time embedding
     _refused = (('total_loss', 'total_loss (BCAgent has policy_loss)'),
                 ('compute_flow_actions', 'compute_flow_actions (sample_actions(noises=) is the flow)'),
                 ('create_replay_buffer', 'the replay ring'), ('update_balanced', 'balanced sampling'))

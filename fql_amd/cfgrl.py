@@ -76,6 +76,7 @@ class CFGRLAgent(KindAgent):
     """CFGRL agent backed by the MI355X step engine.  update: agents/cfgrl.py:58-68, 4 infos (CFGRL_INFO_KEYS)."""
 
     _name = 'CFGRL'
+    _modules = {}   # network.select: actor_flow's input carries the goals and the unc_embed row
     _refused = (('total_loss', 'total_loss (CFGRLAgent has policy_loss)'),
                 ('compute_flow_actions', 'compute_flow_actions (sample_actions(noises=) is the flow)'),
                 ('create_replay_buffer', 'the replay ring'), ('update_balanced', 'balanced sampling'),

@@ -90,3 +90,44 @@ __global__ __launch_bounds__(FQL_THREADS) void fql_jax_noise_kernel(const JaxNoi
     }
 }
 
+// ------------------------------------------------------------------------------------------------
+// Module queries (fql_module_forward: agent.network.select(module)(...), utils/flax_utils.py ModuleDict / TrainState.select).
+// ------------------------------------------------------------------------------------------------
+// The padded input rows of one chunk: row r = [obs_r | act_r | t_r | 0] (utils/networks.py Value.__call__ concatenates
+// [observations, actions], ActorVectorField.__call__ [observations, actions, times]); act and t may be null (the module takes none),
+// rows >= n and the pad columns are zero.  One wave per row, as fql_assemble_kernel; no RNG.
+struct QueryAssembleArgs {
+    const float *obs, *act, *t;   // [n, od], [n, ad] or null, [n] or null
+    float* X;                     // [n_pad, inp]
+    int n, n_pad, od, ad, inp;
+};
+__global__ __launch_bounds__(FQL_THREADS) void fql_query_assemble_kernel(const QueryAssembleArgs P) {
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int r = blockIdx.x * 4 + wave;
+    if (r >= P.n_pad) return;
+    const int a1 = P.od + (P.act ? P.ad : 0);   // first column behind the action block
+    for (int j = lane; j < P.inp; j += 64) {
+        float v = 0.f;
+        if (r < P.n) {
+            if (j < P.od) v = P.obs[(size_t)r * P.od + j];
+            else if (j < a1) v = P.act[(size_t)r * P.ad + (j - P.od)];
+            else if (j == a1 && P.t) v = P.t[r];
+        }
+        P.X[(size_t)r * P.inp + j] = v;
+    }
+}
+// The scalar heads of one chunk: out[e ld + r] = q_e[r, 0] for the `members` (1: value, 2: the critic pair) padded head outputs
+// [n_pad, 16], in one launch.  out points at the chunk's first row of member 0; ld is the member stride (the call's n for a device
+// `out`, the chunk's rows for the staging buffer).
+struct QueryHeadsArgs {
+    const float* q[2];   // [n_pad, 16] column 0; q[1] is null for one member
+    float* out;
+    int n, members;
+    size_t ld;
+};
+__global__ __launch_bounds__(FQL_THREADS) void fql_query_heads_kernel(const QueryHeadsArgs P) {
+    const int i = blockIdx.x * FQL_THREADS + threadIdx.x;
+    if (i >= P.n * P.members) return;
+    const int e = i >= P.n, r = i - e * P.n;
+    P.out[(size_t)e * P.ld + r] = (e ? P.q[1] : P.q[0])[(size_t)r * 16];
+}

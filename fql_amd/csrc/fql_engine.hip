@@ -693,6 +693,16 @@ struct fql_engine {
     };
     // (the bool: the sweep programs of the CFG samplers, workspaces of their own: get_eval)
     std::map<std::pair<int, bool>, std::unique_ptr<Eval>> evals;
+    // module queries (fql_module_forward): the workspace of one module's forward over n_pad padded rows, keyed by (index in modules(),
+    // n_pad).  Buffers and program are its own: no update, loss-probe or sampling workspace is read or written by a query.
+    struct Query {
+        std::vector<void*> allocs;
+        float* X = nullptr;        // [n_pad, in_p]: [obs | act | t | 0]
+        PassBuf p[2];              // one pass per member (the critic pairs: two nets on the same X)
+        Program prog;
+        float *st_obs = nullptr, *st_act = nullptr, *st_t = nullptr, *st_out = nullptr;   // staging of host rows / of a host result
+    };
+    std::map<std::pair<int, int>, std::unique_ptr<Query>> queries;
 
     // agent groups (fql_group_*): the group this engine is a member of, the event behind that group's last update and whether an entry
     // point of this engine has run since (then the next group update orders itself behind this engine's stream)
@@ -4393,6 +4403,92 @@ struct fql_engine {
             default: sample_actor(obs, noise, sd, temperature, n, out, s, own_stream); break;
         }
     }
+    // ---------------------------------------------------------------------------------------
+    // module queries: agent.network.select(module)(...) (utils/flax_utils.py ModuleDict / TrainState.select), DESIGN.md section 21
+    // ---------------------------------------------------------------------------------------
+    // The modules a handle of this kind answers for, under the reference's names without "modules_".  members 2: the stacked critic,
+    // nets `net` and `net + 1` on the same rows.  scalar: the head is one column (Value), the result [members, n]; else [n, act].
+    // Not here, and why (include/fql_amd.h): the Gaussian actors return a distribution object in the reference; IQL-diffusion's actor, BC's
+    // policy and CFGRL's actor_flow read host-built embeddings and the unc_embed row.
+    struct ModuleSpec { const char* name; int net, members; bool scalar, act, times; };
+    std::vector<ModuleSpec> modules() const {
+        std::vector<ModuleSpec> m;
+        if (kind == AgentKind::BC || kind == AgentKind::CFGRL) return m;
+        m.push_back({"critic", NET_C0, 2, true, true, false});
+        m.push_back({"target_critic", NET_T0, 2, true, true, false});
+        if (has_value_net()) m.push_back({"value", NET_OS, 1, true, false, false});
+        if (kind == AgentKind::FQL) {
+            m.push_back({"actor_bc_flow", NET_BC, 1, false, true, true});
+            m.push_back({"actor_onestep_flow", NET_OS, 1, false, true, false});
+        }
+        if (kind == AgentKind::IFQL) m.push_back({"actor_flow", NET_BC, 1, false, true, true});
+        return m;
+    }
+    // The workspace of module `mi` over n_pad rows: the padded input, one pass per member on lane 0 (the 16-row kernels of every sampling
+    // path: a row's result does not depend on the rows beside it) without saved activations, scheduled once.
+    Query& get_query(int mi, const ModuleSpec& sp, int n_pad) {
+        const std::pair<int, int> key{mi, n_pad};
+        auto it = queries.find(key);
+        if (it != queries.end()) return *it->second;
+        auto q = std::make_unique<Query>();
+        auto& W = q->allocs;
+        const int od = cfg.obs_dim, ad = cfg.act_dim;
+        q->X = dalloc(W, (size_t)n_pad * nets[sp.net].in_p());
+        q->st_obs = dalloc(W, (size_t)n_pad * od);
+        if (sp.act) q->st_act = dalloc(W, (size_t)n_pad * ad);
+        if (sp.times) q->st_t = dalloc(W, (size_t)n_pad);
+        q->st_out = dalloc(W, (size_t)n_pad * (sp.scalar ? sp.members : ad));
+        emit_lane = 0;
+        for (int e = 0; e < sp.members; ++e) {
+            q->p[e] = make_pass(W, sp.net + e, n_pad, q->X, false, false);
+            emit_forward(q->prog, q->p[e], false);
+        }
+        schedule(q->prog, W);
+        return *(queries[key] = std::move(q));
+    }
+    // One module's forward on the caller's rows, in chunks of <= 4096 as the samplers': stage, assemble [obs | act | t], the program, then
+    // the heads [members, n] (member-major at the chunk's offset) or the [m, act] rows.  A host result leaves through the staging buffer.
+    void module_forward(int mi, const ModuleSpec& sp, const float* obs, const float* act, const float* times, int n, float* out,
+                        hipStream_t s, bool own_stream) {
+        if (n <= 0) invalid("n must be positive (got %d)", n);
+        if (!obs || !out) invalid("observations/out must not be NULL");
+        if (sp.act && !act) invalid("module '%s' takes actions: actions must not be NULL", sp.name);
+        if (!sp.act && act) invalid("module '%s' takes observations only: actions must be NULL", sp.name);
+        if (sp.times && !times) invalid("module '%s' takes times: times must not be NULL", sp.name);
+        if (!sp.times && times) invalid("module '%s' takes no times: times must be NULL", sp.name);
+        const int od = cfg.obs_dim, ad = cfg.act_dim, ap = pad16(ad);
+        const bool dev_out = is_device_ptr(out);
+        for (int start = 0; start < n; start += 4096) {
+            const int m = std::min(4096, n - start), n_pad = pad16(m);
+            Query& q = get_query(mi, sp, n_pad);
+            const float* o = stage(obs + (size_t)start * od, q.st_obs, (size_t)m * od, s);
+            const float* a = act ? stage(act + (size_t)start * ad, q.st_act, (size_t)m * ad, s) : nullptr;
+            const float* t = times ? stage(times + start, q.st_t, (size_t)m, s) : nullptr;
+            drain_staging(s);
+            const QueryAssembleArgs aa{o, a, t, q.X, m, n_pad, od, ad, nets[sp.net].in_p()};
+            hipLaunchKernelGGL(fql_query_assemble_kernel, dim3((n_pad + 3) / 4), dim3(FQL_THREADS), 0, s, aa);
+            run_launches(q.prog, s);
+            if (sp.scalar) {
+                const QueryHeadsArgs ha{{q.p[0].out, sp.members == 2 ? q.p[1].out : nullptr}, dev_out ? out + start : q.st_out, m, sp.members,
+                                        dev_out ? (size_t)n : (size_t)m};
+                hipLaunchKernelGGL(fql_query_heads_kernel, dim3((m * sp.members + FQL_THREADS - 1) / FQL_THREADS), dim3(FQL_THREADS), 0, s, ha);
+            } else {
+                hipLaunchKernelGGL(fql_extract_kernel, dim3((m * ad + 255) / 256), dim3(256), 0, s, (const float*)q.p[0].out,
+                                   dev_out ? out + (size_t)start * ad : q.st_out, m, ad, ap);
+            }
+            HIP_CHECK(hipGetLastError());
+            if (!dev_out) {
+                if (sp.scalar)
+                    for (int e = 0; e < sp.members; ++e)
+                        HIP_CHECK(hipMemcpyAsync(out + (size_t)e * n + start, q.st_out + (size_t)e * m, (size_t)m * sizeof(float), hipMemcpyDeviceToHost, s));
+                else
+                    HIP_CHECK(hipMemcpyAsync(out + (size_t)start * ad, q.st_out, (size_t)m * ad * sizeof(float), hipMemcpyDeviceToHost, s));
+                HIP_CHECK(hipStreamSynchronize(s));
+            } else if (own_stream) {
+                HIP_CHECK(hipStreamSynchronize(s));   // a device result on the engine's private stream: finished before return, as the samplers'
+            }
+        }
+    }
     // ReBRAC host batches: the FQL ones plus next_actions [B, act] (source_from_dataset takes the dataset's actions one row on)
     void rebrac_source_from_batch(const float* obs, const float* act, const float* rew, const float* mask, const float* nobs, const float* nact,
                                   int batch, const fql_noise* nz, int advance, hipStream_t s) {
@@ -4435,6 +4531,7 @@ struct Admission {
     X(total_loss, -1, {OK_, OK_, "its batch has no next_actions: fql_rebrac_total_loss", NO_, NO_, NO_, "fql_iqld_total_loss", "fql_cfgrl_policy_loss"})                           \
     X(sample_actions, -1, {OK_, OK_, OK_, OK_, "fql_bc_sample_actions", OK_, "fql_iqld_sample_actions", "it takes goals: fql_cfgrl_sample_actions"})                                                      \
     X(flow_actions, -1, {OK_, OK_, "the actor is deterministic, there is no flow", NO_, NO_, NO_, NO_, NO_})                                 \
+    X(module_forward, -1, {OK_, OK_, OK_, OK_, "policy's input carries the host-built time embedding", OK_, OK_, "actor_flow's input carries the goals and the unc_embed row"})  \
     X(noise_from_jax_keys, -1, FQL_ALONE)                                                                                          \
     X(dataset_add_frames, -1, FQL_ALONE)                                                                                           \
     X(replay_create, -1, {OK_, NO_, NO_, OK_, NO_, NO_, NO_, NO_})                                                                           \
@@ -4845,6 +4942,8 @@ int fql_destroy(fql_handle h) {
     h->aql.shutdown();
     for (auto& kv : h->evals)
         for (void* p : kv.second->allocs) hipFree(p);
+    for (auto& kv : h->queries)
+        for (void* p : kv.second->allocs) hipFree(p);
     hipFree(h->P); hipFree(h->G); hipFree(h->Mu); hipFree(h->Nu); hipFree(h->d_chunks); hipFree(h->d_partials); hipFree(h->d_ticket); hipFree(h->d_leaf_range); hipFree(h->d_state); hipFree(h->d_src); hipFree(h->d_emb); hipFree(h->iql_info); hipFree(h->d_state_a);
     if (h->h_src_ring) hipHostFree(h->h_src_ring);
     hipFree(h->d_gsrc); hipFree(h->ds_final); hipFree(h->ds_reps);
@@ -5085,6 +5184,27 @@ int fql_flow_actions(fql_handle h, const float* obs, const float* noises, int n,
     FQL_ADMIT(h, EP_flow_actions);
     if (!h) return FQL_E_INVALID;
     FQL_TRY(h, h->eval_rows(true, obs, noises, 0, n, out, pick(h, stream), stream == nullptr));
+}
+int fql_module_forward(fql_handle h, const char* module, const float* obs, const float* act, const float* times, int n, float* out,
+                       void* stream) {
+    FQL_ADMIT(h, EP_module_forward);
+    if (!h) return FQL_E_INVALID;
+    if (h->visual) {
+        h->err = "fql_module_forward is not available on a visual agent (the reference runs the module's encoder first: state observations only)";
+        return FQL_E_STATE;
+    }
+    if (!module) { h->err = "fql_module_forward: module must not be NULL"; return FQL_E_INVALID; }
+    const auto mods = h->modules();
+    int mi = -1;
+    for (int i = 0; i < (int)mods.size(); ++i)
+        if (!std::strcmp(mods[i].name, module)) mi = i;
+    if (mi < 0) {
+        h->err = std::string("fql_module_forward: ") + h->desc().label + " has no module '" + module + "' (its modules:";
+        for (const auto& m : mods) h->err += std::string(" ") + m.name;
+        h->err += ")";
+        return FQL_E_NOTFOUND;
+    }
+    FQL_TRY(h, h->module_forward(mi, mods[mi], obs, act, times, n, out, pick(h, stream), stream == nullptr));
 }
 
 int fql_dataset_upload(fql_handle h, int64_t n, int64_t capacity, const float* obs, const float* act, const float* rew,

@@ -54,6 +54,7 @@ class IFQLAgent(FQLAgent):
     """Implicit flow Q-learning agent backed by the MI355X step engine."""
 
     _name = 'IFQL'
+    _modules = {'critic': 'pair', 'target_critic': 'pair', 'value': 'value', 'actor_flow': 'field_t'}
     _loss_infos = 9
     _jax_sample_noise = False
 

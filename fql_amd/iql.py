@@ -59,6 +59,7 @@ class IQLAgent(KindAgent):
     sample_actions: clip(mean + exp(log_stds) temperature N(0, 1), -1, 1)."""
 
     _name = 'IQL'
+    _modules = {'critic': 'pair', 'target_critic': 'pair', 'value': 'value'}
     _refused = (('compute_flow_actions', 'compute_flow_actions (the actor is a Gaussian, there is no flow)'),
                 ('update_balanced', 'balanced sampling (IQL trains offline from one dataset)'))
     _update_fn, _update_dataset_fn, _sample_fn = 'fql_iql_update', 'fql_iql_update_from_dataset', 'fql_iql_sample_actions'

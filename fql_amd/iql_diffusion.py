@@ -177,6 +177,7 @@ class IQLDiffusionAgent(KindAgent):
     """IQL-diffusion agent backed by the MI355X step engine."""
 
     _name = 'IQL-diffusion'
+    _modules = {'critic': 'pair', 'target_critic': 'pair', 'value': 'value'}   # (the actor's input carries host-built embeddings)
     _refused = (('compute_flow_actions', 'compute_flow_actions (sample_actions(noises=) is the flow)'),
                 ('create_replay_buffer', 'the replay ring'), ('update_balanced', 'balanced sampling'))
     _update_dataset_fn = 'fql_iqld_update_from_dataset'

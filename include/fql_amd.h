@@ -183,6 +183,26 @@ int fql_sample_actions(fql_handle h, const float* observations, int n, const flo
 /* FQLAgent.compute_flow_actions(observations, noises)  agents/fql.py:155-171 (Euler, then clip). */
 int fql_flow_actions(fql_handle h, const float* observations, const float* noises, int n, float* out,
                      void* stream);
+/* agent.network.select(module)(...)  utils/flax_utils.py ModuleDict / TrainState.select: forward of ONE module, stored parameters,
+ * caller rows.  No state change.  `module` is the reference's module name without "modules_":
+ *   "critic", "target_critic" (FQL, IFQL, ReBRAC, SAC, IQL, IQL-diffusion; utils/networks.py Value.__call__(observations, actions)):
+ *     observations [n, obs], actions [n, act], times NULL; out [2, n], the ensemble member first as in the reference;
+ *   "value" (IFQL, IQL, IQL-diffusion; Value.__call__(observations)): observations [n, obs], actions and times NULL; out [n];
+ *   "actor_bc_flow" (FQL), "actor_flow" (IFQL) (ActorVectorField.__call__(observations, actions, times)): the input row is
+ *     [obs | actions | times], times [n], any real t; out [n, act], NOT clipped (the clip is sample_actions' / compute_flow_actions');
+ *   "actor_onestep_flow" (FQL; ActorVectorField.__call__(observations, noises)): actions [n, act], times NULL; out [n, act], not clipped.
+ * n >= 1, any value: the rows run in chunks of <= 4096 on 16-row tiles, and row j of a call is bit for bit the single-row call on row j.
+ * Pointers are device or host; `stream` as elsewhere (NULL: the engine's own stream, a device `out` is finished before return).  Like
+ * every entry point the call first waits for the handle's updates on the engine's own queues and for its group's last update, so it
+ * sees the latest parameters.  A bf16x3 FQL handle runs the split forward its samplers run.  The query's buffers and programs are its
+ * own: no update, loss-probe or sampling workspace changes.
+ * FQL_E_NOTFOUND: a module the handle's kind does not have (fql_last_error lists the kind's modules).  FQL_E_INVALID: a NULL pointer the
+ * module needs, a non-NULL pointer it does not take, n <= 0.  FQL_E_STATE: BC and CFGRL handles, visual handles.
+ * Out of scope and refused: the Gaussian "actor" / "target_actor" of ReBRAC, SAC and IQL (the reference returns a distribution object;
+ * sample_actions with temperature 0 gives the clipped mode); IQL-diffusion's "actor", BC's policy and CFGRL's "actor_flow" (their inputs
+ * carry host-built embeddings and the unc_embed row); visual agents (the reference runs the module's encoder first); a params= override. */
+int fql_module_forward(fql_handle h, const char* module, const float* observations, const float* actions,
+                       const float* times, int n, float* out, void* stream);
 
 /* Dataset.create / ReplayBuffer (utils/datasets.py:36-62,435-495): the transition arrays live in HBM.
  * `capacity` >= n rows are allocated (main.py:112-114 uses max(2M, n+1) for online runs). */
