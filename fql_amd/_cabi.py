@@ -137,6 +137,9 @@ SYMBOLS = {
     'fql_group_destroy': (_I, [_VP]),
     'fql_group_update_from_dataset': (_I, [_VP, _VP, _I, _VP, _VP]),
     'fql_group_synchronize': (_I, [_VP]),
+    'fql_group_sample_actions': (_I, [_VP, _VP, _I, _VP, _VP, _VP, _VP]),
+    'fql_group_flow_actions': (_I, [_VP, _VP, _VP, _I, _VP, _VP]),
+    'fql_group_sample_stats': (_I, [_VP, _I, C.POINTER(_I64)]),
     'fql_ifql_default_config': (None, [C.POINTER(FqlIfqlConfig)]),
     'fql_ifql_create': (_I, [C.POINTER(FqlConfig), C.POINTER(FqlIfqlConfig), _U64, C.POINTER(_VP)]),
     'fql_num_info': (_I, [_VP]),

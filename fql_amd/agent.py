@@ -930,8 +930,81 @@ class FQLAgentGroup:
         self._keep = keep
         return [m._lazy_info(None) for m in self.members] if want_info else None
 
+    def sample_actions(self, observations, seed=None, temperature=1.0, noises=None):
+        """FQLAgent.sample_actions of every member in ONE fused call (fql_group_sample_actions): result[i] is bitwise what
+        members[i].sample_actions(observations[i], seed=..., noises=noises[i]) returns.
+
+        observations: [K, ..., od], one block of rows per member (each member acts in its own environments), or one block without the
+        leading K - [od], [n, od] - that every member acts on.  An array of three or more dims must lead with K; a 2-D array of exactly K
+        rows is read as one row per member.  noises: [K, ..., ad] or None.  seed: None, one seed (every member is keyed with it as its own
+        call would be) or a sequence of K; with neither seed nor noises each member's own sample counter advances as its own call would
+        advance it.  numpy in, numpy out; CUDA tensors in, a CUDA tensor out on torch's current stream.  `temperature` is accepted and
+        ignored, as in FQLAgent.  Returns [K, ..., ad]."""
+        return self._eval(observations, noises, seed, flow=False)
+
+    def compute_flow_actions(self, observations, noises):
+        """FQLAgent.compute_flow_actions of every member in one fused call (fql_group_flow_actions); shapes as in sample_actions."""
+        if noises is None:
+            raise ValueError('compute_flow_actions needs noises [K, ..., action_dim]')
+        return self._eval(observations, noises, None, flow=True)
+
+    def _eval(self, observations, noises, seed, flow):
+        K, cfg = len(self.members), self.members[0].config
+        od, ad = int(cfg['ob_dims'][0]), int(cfg['action_dim'])
+        is_t = hasattr(observations, 'data_ptr')
+        if not is_t:
+            observations = np.asarray(observations)
+        oshape = tuple(int(d) for d in observations.shape)
+        if not oshape or oshape[-1] != od:
+            raise ValueError(f'observations last dim must be {od}, got {oshape}')
+        zshape = None
+        if noises is not None:
+            if not hasattr(noises, 'data_ptr'):
+                noises = np.asarray(noises)
+            zshape = tuple(int(d) for d in noises.shape)
+        if len(oshape) >= 3:
+            if oshape[0] != K:
+                raise ValueError(f'observations must lead with the {K} members: [{K}, ..., {od}], got {oshape}')
+            shared = False
+        elif zshape is not None:
+            shared = len(zshape) == len(oshape) + 1
+        else:
+            shared = not (len(oshape) == 2 and oshape[0] == K)
+        lead = oshape[:-1] if shared else oshape[1:-1]
+        if zshape is not None and zshape != (K,) + lead + (ad,):
+            raise ValueError(f'noises must be {(K,) + lead + (ad,)} for observations {oshape}, got {zshape}')
+        n = int(np.prod(lead)) if lead else 1
+        if n < 1:
+            raise ValueError(f'observations hold no rows: {oshape}')
+        seeds = None
+        if not flow and noises is None:
+            if seed is None or np.ndim(seed) == 0:
+                vals = [m._sample_seed(seed, None) for m in self.members]
+            else:
+                if len(seed) != K:
+                    raise ValueError(f'{K} members but {len(seed)} seeds')
+                vals = [m._sample_seed(s, None) for m, s in zip(self.members, seed)]
+            seeds = (C.c_uint64 * K)(*vals)
+        if shared:   # the same rows for every member: broadcast here, the library takes one block per member
+            observations = (observations.unsqueeze(0).expand((K,) + oshape) if is_t else np.broadcast_to(observations, (K,) + oshape))
+        o = _Arg(observations, (K, n, od))
+        z = _Arg(noises, (K, n, ad))
+        out, optr = FQLAgent._actions_out(observations, (K,) + lead + (ad,))
+        stream = FQLAgent._stream([o, z])
+        if flow:
+            self._check(self._lib.fql_group_flow_actions(self._g, o.ptr, z.ptr, n, optr, stream))
+        else:
+            self._check(self._lib.fql_group_sample_actions(self._g, o.ptr, n, z.ptr, seeds, optr, stream))
+        return out
+
+    def sample_launches(self, flow=False):
+        """Kernel launches of one fused sampling call on a single chunk, counted from the built program (fql_group_sample_stats)."""
+        v = C.c_int64(0)
+        self._check(self._lib.fql_group_sample_stats(self._g, int(bool(flow)), C.byref(v)))
+        return int(v.value)
+
     def synchronize(self):
-        """Host wait for the group's last update."""
+        """Host wait for the group's last update or sampling call."""
         self._check(self._lib.fql_group_synchronize(self._g))
 
     def close(self):

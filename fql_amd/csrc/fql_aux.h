@@ -131,3 +131,17 @@ __global__ __launch_bounds__(FQL_THREADS) void fql_query_heads_kernel(const Quer
     const int e = i >= P.n, r = i - e * P.n;
     P.out[(size_t)e * P.ld + r] = (e ? P.q[1] : P.q[0])[(size_t)r * 16];
 }
+
+// ------------------------------------------------------------------------------------------------
+// A group's sampling call (fql_group_sample_actions, fql_group_flow_actions): multi-instance entry points of fql_assemble_kernel and
+// fql_extract_kernel (fql_kernels.h, bodies shared).  blockIdx.y picks the member, its argument struct comes from a device array, read
+// through the constant address space (scalar loads, as from the kernel-argument segment).
+// ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(FQL_THREADS) void fql_assemble_multi_kernel(const AssembleArgs* __restrict__ args) { const AssembleArgs P = ((const FQL_CONST_AS AssembleArgs*)args)[blockIdx.y]; fql_assemble_body(P); }
+// the single-instance kernel's arguments as a struct, one per member
+struct ExtractArgs {
+    const float* src;
+    float* out;
+    int n, ad, ap;
+};
+__global__ void fql_extract_multi_kernel(const ExtractArgs* __restrict__ args) { const ExtractArgs P = ((const FQL_CONST_AS ExtractArgs*)args)[blockIdx.y]; fql_extract_body(P.src, P.out, P.n, P.ad, P.ap); }

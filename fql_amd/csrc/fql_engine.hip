@@ -6294,6 +6294,7 @@ int fql_update_from_frames(fql_handle h, const int64_t* idx, const int32_t* crop
 // task tables (tile0 and the side kernel's sub-table offsets rebased, grid = the sum); an argument-struct launch becomes one launch of the
 // kernel's multi-instance entry point with blockIdx.y = member, reading the member's argument struct from a device array.  Every task keeps
 // the tile shape and arguments its member's program gave it, so each member computes exactly what it computes alone.
+// The members' sampling programs are zipped the same way (fql_group_s::Sample): one fused sample_actions / flow_actions call for all K.
 // ================================================================================================
 namespace {
 
@@ -6355,12 +6356,16 @@ struct fql_group_s {
     hipGraphExec_t exec = nullptr;
     std::vector<void*> allocs;
     int64_t* d_idx = nullptr;   // [K][B] staging of host row indices
-    hipStream_t last = nullptr; // the stream of the last update: an update on another stream waits for that update first
+    hipStream_t last = nullptr; // the stream of the last group call (update or sampling): a call on another stream waits for that one first
 
-    void* upload(const void* src, size_t bytes) {
+    void* galloc(size_t bytes) {
         void* d = nullptr;
         HIP_CHECK(hipMalloc(&d, std::max<size_t>(bytes, 16)));
         allocs.push_back(d);
+        return d;
+    }
+    void* upload(const void* src, size_t bytes) {
+        void* d = galloc(bytes);
         if (bytes) HIP_CHECK(hipMemcpy(d, src, bytes, hipMemcpyHostToDevice));
         return d;
     }
@@ -6376,9 +6381,10 @@ struct fql_group_s {
     template <typename T> static void rebase_tile0(T& t, int d) { t.tile0 += d; }
     static void rebase_tile0(MiscTask&, int) {}   // (indexed by workgroup - tile_m: concatenation is the rebase)
 
-    // one fused launch from launch `li` of every member's prog_full
-    GLaunch zip(int li) {
-        const Launch& L0 = m[0]->prog_full.launches[li];
+    // one fused launch from launch `li` of every member's program `prog(member)`: the update's prog_full, or a sampling workspace's
+    template <typename Sel>
+    GLaunch zip(int li, Sel&& prog) {
+        const Launch& L0 = prog(*m[0]).launches[li];
         GLaunch G;
         G.lane = L0.lane; G.waits = L0.waits; G.record_after = L0.record_after;
         if (is_table_launch(L0.type)) {
@@ -6392,7 +6398,7 @@ struct fql_group_s {
             std::vector<int> sg, sw, sl, sm;
             int cg = 0, cw = 0, cl = 0, cm = 0;
             for (int k = 0; k < K; ++k) {
-                const Launch& L = m[k]->prog_full.launches[li];
+                const Launch& L = prog(*m[k]).launches[li];
                 sg.push_back(cg); sw.push_back(cw); sl.push_back(cl); sm.push_back(0);
                 if (L0.type == OP_WFRAG) { tf.push_back(&m[k]->h_wfrag); cg += m[k]->wfrag_grid; }
                 else if (L0.type == OP_GEMM64) {
@@ -6428,14 +6434,174 @@ struct fql_group_s {
         if (it == multi_entries().end()) invalid("agent groups: launch %d (op type %d) has no multi-instance kernel", li, (int)L0.type);
         std::vector<uint8_t> args;
         for (int k = 0; k < K; ++k) {   // the structs are exactly what the member's own issue() passes
-            const Launch& L = m[k]->prog_full.launches[li];
+            const Launch& L = prog(*m[k]).launches[li];
             if (L.k.args.size() != it->second.arg_bytes) invalid("internal: launch %d binds %zu argument bytes, its struct has %zu", li, L.k.args.size(), it->second.arg_bytes);
             alignas(16) unsigned char a[FQL_BOUND_BYTES];
-            m[k]->issue_args(L, m[k]->tl_of(m[k]->prog_full, L), a);
+            m[k]->issue_args(L, m[k]->tl_of(prog(*m[k]), L), a);
             args.insert(args.end(), a, a + L.k.args.size());
         }
         G.k = it->second.bind(Geo(dim3(k0.grid[0], K), dim3(k0.block[0], k0.block[1], k0.block[2]), k0.lds), upload(args.data(), args.size()));
         return G;
+    }
+
+    // every launch of the members' programs `prog(member)` zipped: the sampling programs, which run on lane 0 alone
+    template <typename Sel>
+    std::vector<GLaunch> zip_lane0(Sel&& prog, const char* what) {
+        const Program& p0 = prog(*m[0]);
+        std::vector<GLaunch> out;
+        for (size_t li = 0; li < p0.launches.size(); ++li) {
+            const Launch& L0 = p0.launches[li];
+            if (L0.lane != 0 || !L0.waits.empty() || L0.k.grid[1] != 1 || L0.k.grid[2] != 1) invalid("agent groups: launch %zu of %s is not a plain lane-0 launch", li, what);
+            for (int k = 1; k < K; ++k) {
+                const Program& p = prog(*m[k]);
+                if (p.launches.size() != p0.launches.size() || p.launches[li].type != L0.type || p.launches[li].grid != L0.grid || p.launches[li].k.fn != L0.k.fn)
+                    invalid("agent groups: launch %zu of member %d's %s differs from member 0's", li, k, what);
+            }
+            out.push_back(zip((int)li, prog));
+        }
+        return out;
+    }
+
+    // ---- fused sampling (fql_group_sample_actions, fql_group_flow_actions): DESIGN.md section 12 ----
+    // The workspace of one chunk of n_pad padded rows per member, cached per n_pad like fql_engine::evals: the launches of every member's
+    // get_eval(n_pad).prog_os zipped (and of prog_flow, on the first flow call), the group's staging of host rows and of a host result,
+    // [K, m, .] packed by the chunk's m <= n_pad rows, and the [K] argument structs of the assemble and extract launches in device
+    // memory, rewritten by every chunk (the rows, the seed and the output are the call's).
+    struct Sample {
+        int n_pad = 0;
+        std::vector<GLaunch> os, flow;
+        float *st_obs = nullptr, *st_noise = nullptr, *st_out = nullptr;
+        unsigned char* d_args = nullptr;   // [K] AssembleArgs, then [K] ExtractArgs
+        Bound assemble, extract;           // the multi-instance launches over d_args, blockIdx.y = member
+    };
+    std::map<int, std::unique_ptr<Sample>> samples;
+    // The chunks' argument structs travel through a ring of pinned host slots (the copy reads the slot when the stream reaches it): a
+    // slot is reused once the event behind its copy has passed.  On the legacy default stream no event is recorded (fql_engine::grp_legacy):
+    // such a slot is reused after a device synchronise.
+    static constexpr int kArgRing = 32;
+    unsigned char* h_args = nullptr;
+    hipEvent_t arg_ev[kArgRing] = {};
+    char arg_state[kArgRing] = {};   // 0 = free, 1 = behind arg_ev, 2 = on the legacy stream
+    int arg_pos = 0;
+    size_t arg_bytes() const { return (size_t)K * (sizeof(AssembleArgs) + sizeof(ExtractArgs)); }
+
+    Sample& sample_ws(int n_pad, bool flow) {
+        std::unique_ptr<Sample>& slot = samples[n_pad];
+        if (!slot) {
+            auto w = std::make_unique<Sample>();
+            const int od = m[0]->cfg.obs_dim, ad = m[0]->cfg.act_dim;
+            w->n_pad = n_pad;
+            w->os = zip_lane0([&](fql_engine& e) -> Program& { return e.get_eval(n_pad).prog_os; }, "the one-step sampler");
+            w->st_obs = (float*)galloc((size_t)K * n_pad * od * sizeof(float));
+            w->st_noise = (float*)galloc((size_t)K * n_pad * ad * sizeof(float));
+            w->st_out = (float*)galloc((size_t)K * n_pad * ad * sizeof(float));
+            w->d_args = (unsigned char*)galloc(arg_bytes());
+            w->assemble = bind(fql_assemble_multi_kernel, Geo(dim3((n_pad + 3) / 4, K), dim3(FQL_THREADS), 0), (const AssembleArgs*)w->d_args);
+            w->extract = bind(fql_extract_multi_kernel, Geo(dim3((n_pad * ad + 255) / 256, K), dim3(256), 0),
+                              (const ExtractArgs*)(w->d_args + (size_t)K * sizeof(AssembleArgs)));
+            slot = std::move(w);
+        }
+        if (flow && slot->flow.empty())
+            slot->flow = zip_lane0([&](fql_engine& e) -> Program& { return e.get_eval(n_pad).prog_flow; }, "the flow sampler");
+        return *slot;
+    }
+    // launches of one fused sampling call on a single chunk, counted from the built program: assemble, the zipped launches, extract
+    int64_t sample_launches(bool flow) {
+        Sample& w = sample_ws(16, flow);
+        return 2 + (int64_t)(flow ? w.flow : w.os).size();
+    }
+    unsigned char* arg_slot() {
+        if (!h_args) {
+            HIP_CHECK(hipHostMalloc((void**)&h_args, kArgRing * arg_bytes()));
+            for (hipEvent_t& e : arg_ev) HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        }
+        arg_pos = (arg_pos + 1) % kArgRing;
+        if (arg_state[arg_pos] == 1) HIP_CHECK(hipEventSynchronize(arg_ev[arg_pos]));
+        else if (arg_state[arg_pos] == 2) {
+            HIP_CHECK(hipDeviceSynchronize());
+            for (char& st : arg_state) if (st == 2) st = 0;
+        }
+        arg_state[arg_pos] = 0;
+        return h_args + (size_t)arg_pos * arg_bytes();
+    }
+    // rows [start, start + mm) of every member's block of n rows of width w, as one copy over the member stride (a plain copy where
+    // both sides are packed)
+    void copy_rows(float* dst, size_t dstride, const float* src, size_t sstride, size_t width, hipMemcpyKind kind, hipStream_t s) {
+        if (dstride == width && sstride == width) HIP_CHECK(hipMemcpyAsync(dst, src, (size_t)K * width * sizeof(float), kind, s));
+        else HIP_CHECK(hipMemcpy2DAsync(dst, dstride * sizeof(float), src, sstride * sizeof(float), width * sizeof(float), (size_t)K, kind, s));
+    }
+    struct Rows { const float* p; size_t stride; };   // member i's rows of the chunk: p + i * stride
+    Rows chunk_rows(const float* src, bool dev, float* staging, int w, int n, int start, int mm, hipStream_t s) {
+        if (!src) return Rows{nullptr, 0};
+        if (dev) return Rows{src + (size_t)start * w, (size_t)n * w};   // device rows are read where they are
+        copy_rows(staging, (size_t)mm * w, src + (size_t)start * w, (size_t)n * w, (size_t)mm * w, hipMemcpyHostToDevice, s);
+        return Rows{staging, (size_t)mm * w};
+    }
+    // One fused sampling call (the caller has ordered `s`: enter()): per chunk of <= 4096 rows per member - the member's own chunks, so
+    // that a seeded draw is keyed as fql_engine::eval_rows keys it, (member's key, seed_i + start) - assemble-multi, the zipped launches of
+    // the members' program, extract-multi, as direct launches on s.  observations [K, n, od], noise [K, n, ad] or null, out [K, n, ad]:
+    // host or device each.  A host result is copied out and waited for per chunk.
+    void sample(bool flow, const float* obs, const float* noise, const uint64_t* seeds, int n, float* out, hipStream_t s) {
+        const int od = m[0]->cfg.obs_dim, ad = m[0]->cfg.act_dim, ap = pad16(ad);
+        const bool dev_obs = fql_engine::is_device_ptr(obs), dev_z = noise && fql_engine::is_device_ptr(noise), dev_out = fql_engine::is_device_ptr(out);
+        for (int start = 0; start < n; start += 4096) {
+            const int mm = std::min(4096, n - start);
+            Sample& w = sample_ws(pad16(mm), flow);
+            const Rows o = chunk_rows(obs, dev_obs, w.st_obs, od, n, start, mm, s);
+            const Rows z = chunk_rows(noise, dev_z, w.st_noise, ad, n, start, mm, s);
+            unsigned char* slot = arg_slot();
+            AssembleArgs* aa = (AssembleArgs*)slot;
+            ExtractArgs* ea = (ExtractArgs*)(slot + (size_t)K * sizeof(AssembleArgs));
+            for (int i = 0; i < K; ++i) {
+                fql_engine& e = *m[i];
+                fql_engine::Eval& ev = e.get_eval(w.n_pad);
+                aa[i] = AssembleArgs{o.p + i * o.stride, z.p ? z.p + i * z.stride : nullptr, flow ? ev.Xf : ev.X, e.seed,
+                                     (seeds ? seeds[i] : 0) + (uint64_t)start, mm, w.n_pad, od, ad, flow ? e.nets[NET_BC].in_p() : e.nets[NET_OS].in_p()};
+                ea[i] = ExtractArgs{flow ? ev.tgt : ev.p_os.out, dev_out ? out + ((size_t)i * n + start) * ad : w.st_out + (size_t)i * mm * ad, mm, ad, ap};
+            }
+            HIP_CHECK(hipMemcpyAsync(w.d_args, slot, arg_bytes(), hipMemcpyHostToDevice, s));
+            if (s == hipStreamLegacy) arg_state[arg_pos] = 2;
+            else { HIP_CHECK(hipEventRecord(arg_ev[arg_pos], s)); arg_state[arg_pos] = 1; }
+            if (!dev_obs || (noise && !dev_z)) HIP_CHECK(hipStreamSynchronize(s));   // (host rows are borrowed for the call only)
+            launch_bound(w.assemble, w.assemble.args.data(), s);
+            for (GLaunch& G : flow ? w.flow : w.os) launch_bound(G.k, G.k.args.data(), s);
+            launch_bound(w.extract, w.extract.args.data(), s);
+            HIP_CHECK(hipGetLastError());
+            if (!dev_out) {
+                copy_rows(out + (size_t)start * ad, (size_t)n * ad, w.st_out, (size_t)mm * ad, (size_t)mm * ad, hipMemcpyDeviceToHost, s);
+                HIP_CHECK(hipStreamSynchronize(s));
+            }
+        }
+    }
+
+    // ---- ordering of a group call (update or sampling) against the group's last call and against the members' own work ----
+    // The stream the call runs on, ordered (0) behind the group's last call where that ran on another stream (the caller's, then the
+    // group's own, or the reverse) and (1) behind everything submitted through a member since the last group call.
+    hipStream_t enter(void* stream) {
+        const hipStream_t s = stream ? (hipStream_t)stream : lanes[0];
+        if (last && last != s) HIP_CHECK(last == hipStreamLegacy ? hipDeviceSynchronize() : hipStreamWaitEvent(s, ev_done, 0));
+        last = s;
+        for (fql_handle h : m) {
+            if (!h->grp_touched) continue;
+            h->aql_drain();
+            HIP_CHECK(hipEventRecord(ev_in, h->stream));
+            HIP_CHECK(hipStreamWaitEvent(s, ev_in, 0));
+            h->grp_touched = false;
+        }
+        return s;
+    }
+    // The call is enqueued on s: every member entry point waits for it from here on (fql_engine::group_fence / group_order).  No event is
+    // recorded on the legacy default stream (fql_engine::grp_legacy): waits for such a call synchronise the device.  host_wait: the call
+    // hands a result to host memory and returns when it is there.
+    void leave(hipStream_t s, bool host_wait) {
+        const bool legacy = s == hipStreamLegacy;
+        if (!legacy) HIP_CHECK(hipEventRecord(ev_done, s));
+        for (fql_handle h : m) { h->grp_pending = true; h->grp_legacy = legacy; h->grp_touched = false; }
+        if (host_wait) HIP_CHECK(legacy ? hipDeviceSynchronize() : hipEventSynchronize(ev_done));
+    }
+    bool member_began() const {
+        for (fql_handle h : m) if (h->began) return true;
+        return false;
     }
 
     // the fused program as ONE graph with the lanes, forks, joins and cross-lane events of a member's own
@@ -6452,6 +6618,8 @@ struct fql_group_s {
         if (graph) hipGraphDestroy(graph);
         destroy_lane_events(*this);
         for (hipEvent_t e : {ev_in, ev_done}) if (e) hipEventDestroy(e);
+        for (hipEvent_t e : arg_ev) if (e) hipEventDestroy(e);
+        if (h_args) hipHostFree(h_args);
         for (void* p : allocs) hipFree(p);
         if (d_idx) hipFree(d_idx);
         for (hipStream_t s : lanes) if (s) hipStreamDestroy(s);
@@ -6517,7 +6685,7 @@ int fql_group_create(const fql_handle* members, int k, fql_group* out) {
         for (size_t li = 0; li < n; ++li) {
             const Bound& k0 = g->m[0]->prog_full.launches[li].k;
             if (k0.grid[1] != 1 || k0.grid[2] != 1) invalid("fql_group_create: launch %zu has a 2-D grid: not groupable", li);
-            g->launches.push_back(g->zip((int)li));
+            g->launches.push_back(g->zip((int)li, [](fql_engine& e) -> Program& { return e.prog_full; }));
             g->lane_used[g->launches.back().lane] = true;
         }
         for (int l = 0; l < FQL_LANES; ++l) HIP_CHECK(hipStreamCreateWithFlags(&g->lanes[l], hipStreamNonBlocking));
@@ -6564,21 +6732,8 @@ int fql_group_update_from_dataset(fql_group g, const int64_t* idx, int batch_siz
     if (!g) { g_create_error = "fql_group_update_from_dataset: NULL group"; return FQL_E_INVALID; }
     try {
         if (batch_size != g->B) invalid("fql_group_update_from_dataset: batch_size %d does not match the members' %d", batch_size, g->B);
-        for (int i = 0; i < g->K; ++i)
-            if (g->m[i]->began) { g_create_error = "fql_group_update_from_dataset: a member is between fql_update_begin and fql_update_end"; return FQL_E_STATE; }
-        const hipStream_t s = stream ? (hipStream_t)stream : g->lanes[0];
-        // behind the group's last update where that ran on another stream (the caller's, then the group's own, or the reverse)
-        if (g->last && g->last != s) HIP_CHECK(g->last == hipStreamLegacy ? hipDeviceSynchronize() : hipStreamWaitEvent(s, g->ev_done, 0));
-        g->last = s;
-        const bool legacy = s == hipStreamLegacy;   // no event there (fql_engine::grp_legacy): waits for this update synchronise the device
-        // ordering rule 1: behind everything submitted through a member since the last group update
-        for (fql_handle h : g->m) {
-            if (!h->grp_touched) continue;
-            h->aql_drain();
-            HIP_CHECK(hipEventRecord(g->ev_in, h->stream));
-            HIP_CHECK(hipStreamWaitEvent(s, g->ev_in, 0));
-            h->grp_touched = false;
-        }
+        if (g->member_began()) { g_create_error = "fql_group_update_from_dataset: a member is between fql_update_begin and fql_update_end"; return FQL_E_STATE; }
+        const hipStream_t s = g->enter(stream);
         const int64_t* rows = idx;
         if (idx && !fql_engine::is_device_ptr(idx)) {
             HIP_CHECK(hipMemcpyAsync(g->d_idx, idx, (size_t)g->K * g->B * sizeof(int64_t), hipMemcpyHostToDevice, s));
@@ -6591,9 +6746,48 @@ int fql_group_update_from_dataset(fql_group g, const int64_t* idx, int batch_siz
             for (int i = 0; i < g->K; ++i)
                 HIP_CHECK(hipMemcpyAsync(info13xk + (size_t)i * FQL_NUM_INFO, &g->m[i]->d_state->info[0], FQL_NUM_INFO * sizeof(float), hipMemcpyDefault, s));
         }
-        if (!legacy) HIP_CHECK(hipEventRecord(g->ev_done, s));
-        for (fql_handle h : g->m) { h->grp_pending = true; h->grp_legacy = legacy; h->grp_touched = false; }
-        if (info13xk && !fql_engine::is_device_ptr(info13xk)) HIP_CHECK(legacy ? hipDeviceSynchronize() : hipEventSynchronize(g->ev_done));
+        g->leave(s, info13xk && !fql_engine::is_device_ptr(info13xk));
+    } catch (const Invalid& e) {
+        g_create_error = e.msg; return FQL_E_INVALID;
+    } catch (const HipError& e) {
+        g_create_error = e.msg; return FQL_E_HIP;
+    }
+    return FQL_OK;
+}
+
+// The members' sample_actions (flow: compute_flow_actions) in one fused call: fql_group_s::sample between the update's ordering rules
+static int group_sample(fql_group g, const char* fn, bool flow, const float* obs, const float* noise, const uint64_t* seeds, int n, float* out, void* stream) {
+    if (!g) { g_create_error = std::string(fn) + ": NULL group"; return FQL_E_INVALID; }
+    try {
+        if (n <= 0) invalid("%s: n must be positive (got %d)", fn, n);
+        if (!obs || !out) invalid("%s: observations/out must not be NULL", fn);
+        if (flow && !noise) invalid("%s: noises must not be NULL", fn);
+        if (!noise && !seeds) invalid("%s: seeds must not be NULL when noises is NULL (one seed per member)", fn);
+        if (g->member_began()) { g_create_error = std::string(fn) + ": a member is between fql_update_begin and fql_update_end"; return FQL_E_STATE; }
+        const hipStream_t s = g->enter(stream);
+        g->sample(flow, obs, noise, seeds, n, out, s);
+        // a device result on the group's own stream: the caller has no handle to order its reads against, so finish here (as a member does)
+        g->leave(s, !stream && fql_engine::is_device_ptr(out));
+    } catch (const Invalid& e) {
+        g_create_error = e.msg; return FQL_E_INVALID;
+    } catch (const HipError& e) {
+        g_create_error = e.msg; return FQL_E_HIP;
+    } catch (const std::exception& e) {
+        g_create_error = e.what(); return FQL_E_HIP;
+    }
+    return FQL_OK;
+}
+int fql_group_sample_actions(fql_group g, const float* observations, int n, const float* noises, const uint64_t* seeds, float* out, void* stream) {
+    return group_sample(g, "fql_group_sample_actions", false, observations, noises, seeds, n, out, stream);
+}
+int fql_group_flow_actions(fql_group g, const float* observations, const float* noises, int n, float* out, void* stream) {
+    return group_sample(g, "fql_group_flow_actions", true, observations, noises, nullptr, n, out, stream);
+}
+int fql_group_sample_stats(fql_group g, int flow, int64_t* launches_per_call) {
+    if (!g) { g_create_error = "fql_group_sample_stats: NULL group"; return FQL_E_INVALID; }
+    if (!launches_per_call) { g_create_error = "fql_group_sample_stats: launches_per_call must not be NULL"; return FQL_E_INVALID; }
+    try {
+        *launches_per_call = g->sample_launches(flow != 0);
     } catch (const Invalid& e) {
         g_create_error = e.msg; return FQL_E_INVALID;
     } catch (const HipError& e) {

@@ -2451,7 +2451,7 @@ struct AssembleArgs {
     uint64_t key, seed;
     int n, n_pad, od, ad, inp;
 };
-__global__ __launch_bounds__(FQL_THREADS) void fql_assemble_kernel(AssembleArgs P) {
+__device__ __forceinline__ void fql_assemble_body(const AssembleArgs& P) {
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int b = blockIdx.x * 4 + wave;
     if (b >= P.n_pad) return;
@@ -2467,11 +2467,14 @@ __global__ __launch_bounds__(FQL_THREADS) void fql_assemble_kernel(AssembleArgs 
         P.X[(size_t)b * P.inp + j] = v;
     }
 }
+__global__ __launch_bounds__(FQL_THREADS) void fql_assemble_kernel(AssembleArgs P) { fql_assemble_body(P); }
+// (the multi-instance entry points of this kernel and the next, for a group's sampling call, are in fql_aux.h: off the update's path)
 // out[n, ad] = src[n, 16][:, :ad]
-__global__ void fql_extract_kernel(const float* src, float* out, int n, int ad, int ap) {
+__device__ __forceinline__ void fql_extract_body(const float* src, float* out, int n, int ad, int ap) {
     const int e = blockIdx.x * blockDim.x + threadIdx.x;
     if (e < n * ad) out[e] = src[(size_t)(e / ad) * ap + (e % ad)];
 }
+__global__ void fql_extract_kernel(const float* src, float* out, int n, int ad, int ap) { fql_extract_body(src, out, n, ad, ap); }
 // ReplayBuffer.add_transition (utils/datasets.py:483-491): one row into the ring
 __global__ void fql_dataset_add_kernel(float* obs, float* act, float* rew, float* mask, float* nobs,
                                        const float* row, int64_t pos, int od, int ad) {

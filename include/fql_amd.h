@@ -303,14 +303,31 @@ int fql_group_destroy(fql_group g);
 /* fql_update_from_dataset of every member in one fused update: member i samples its rows from ITS OWN uploaded dataset, idx + i * B
  * ([k][B] int64, device or host) or NULL = each member's device RNG; the noise always comes from each member's device RNG.
  * info13xk: [k][13] (device or host; host = synchronous) or NULL.  `stream` as elsewhere: NULL = the group's own stream.
- * Ordering: (0) the update is ordered after the group's previous update, also where that one ran on another stream.
+ * Ordering: (0) the update is ordered after the group's previous call (update or sampling), also where that one ran on another stream.
  * (1) the update is ordered after all work submitted earlier through any member: a member's queued engine-queue updates are
  * drained and the group's stream waits for the member's stream (work the caller enqueued on streams of its own is the caller's to order).
  * (2) every member entry point called afterwards sees this update's results without an explicit synchronise (fql_get_param /
  * fql_set_param included): it waits for the group's update first (fql_info_enqueue: a stream dependency, no host wait). */
 int fql_group_update_from_dataset(fql_group g, const int64_t* idx, int batch_size, float* info13xk, void* stream);
-/* Host wait for the group's last update. */
+/* Host wait for the group's last update or sampling call. */
 int fql_group_synchronize(fql_group g);
+/* fql_sample_actions of every member in one fused call: member i acts on ITS OWN rows, observations + i * n * obs_dim ([k][n][obs_dim]),
+ * with the noise noises + i * n * act_dim ([k][n][act_dim]) or, noises NULL, its device draw keyed by seeds[i] ([k], host; may be NULL
+ * only with noises); out [k][n][act_dim].  Pointers are device or host each (host out = synchronous; device out on a caller's stream =
+ * asynchronous; `stream` NULL = the group's own stream, finished before the call returns).  Every launch of a member's call carries
+ * all k members' rows (the assemble and extract launches with blockIdx.y = member, the layers over concatenated task tables), issued as
+ * direct launches: the launch count of a call does not depend on k.  Rows are chunked and seeded draws keyed exactly as the member's
+ * own call does it (<= 4096 rows per member and chunk, seeds[i] + first row of the chunk), so out[i] is bitwise what
+ * fql_sample_actions(member i, ..., seeds[i], ...) returns.  No state of a member changes.
+ * Ordering: as fql_group_update_from_dataset - after the group's last call, after everything submitted earlier through a member, and
+ * every member entry point called afterwards waits for this call.
+ * FQL_E_INVALID: NULL group, n <= 0, NULL observations or out, NULL seeds without noises. */
+int fql_group_sample_actions(fql_group g, const float* observations, int n, const float* noises, const uint64_t* seeds, float* out,
+                             void* stream);
+/* fql_flow_actions of every member likewise (the Euler flow of each member's BC actor on the caller's noises, which are required). */
+int fql_group_flow_actions(fql_group g, const float* observations, const float* noises, int n, float* out, void* stream);
+/* Kernel launches of one fused sampling call (flow != 0: of one flow call) on a single chunk, counted from the built program. */
+int fql_group_sample_stats(fql_group g, int flow, int64_t* launches_per_call);
 
 /* Introspection for tests / bench: per-update kernel-launch count, algorithmic MAC count per update
  * (SURVEY.md section 8d figure), and the engine's HIP stream. */
