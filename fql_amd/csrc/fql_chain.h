@@ -86,6 +86,7 @@ struct WfragTask {
                       // loads of one plane are 1 KB contiguous);
                       // 2 = split 16x16x16 operands dst[(k/4) N + n][hi 2 words | lo 2 words] (the 16-row rank-update block)
 };
+// (the source is the parameter arena as the update's Adam launches have just left it: read past the L1)
 __global__ __launch_bounds__(FQL_THREADS) void fql_wfrag_kernel(const WfragTask* __restrict__ tasks, int ntasks, int tl) {
     tl_enter(tl);
     const WfragTask& T = tasks[find_task(tasks, ntasks, blockIdx.x)];
@@ -96,7 +97,7 @@ __global__ __launch_bounds__(FQL_THREADS) void fql_wfrag_kernel(const WfragTask*
         if (j >= (T.K >> 5)) return;
         float v[8];
 #pragma unroll
-        for (int i = 0; i < 8; ++i) { const int k = 32 * j + 8 * q + i; v[i] = (k < T.kvalid) ? ldg(T.src + (size_t)k * T.ld + n) : 0.f; }
+        for (int i = 0; i < 8; ++i) { const int k = 32 * j + 8 * q + i; v[i] = (k < T.kvalid) ? ldx(T.src + (size_t)k * T.ld + n) : 0.f; }
         u32x4 hi, lo;
 #pragma unroll
         for (int i = 0; i < 4; ++i) { unsigned h, l; bsplit2(v[2 * i], v[2 * i + 1], h, l); hi[i] = h; lo[i] = l; }
@@ -110,7 +111,7 @@ __global__ __launch_bounds__(FQL_THREADS) void fql_wfrag_kernel(const WfragTask*
         if (k4 >= (T.K >> 2)) return;
         float v[4];
 #pragma unroll
-        for (int i = 0; i < 4; ++i) v[i] = (4 * k4 + i < T.kvalid) ? ldg(T.src + (size_t)(4 * k4 + i) * T.ld + n) : 0.f;
+        for (int i = 0; i < 4; ++i) v[i] = (4 * k4 + i < T.kvalid) ? ldx(T.src + (size_t)(4 * k4 + i) * T.ld + n) : 0.f;
         unsigned h0, l0, h1, l1;
         bsplit2(v[0], v[1], h0, l0);
         bsplit2(v[2], v[3], h1, l1);
@@ -121,7 +122,7 @@ __global__ __launch_bounds__(FQL_THREADS) void fql_wfrag_kernel(const WfragTask*
     if (k4 >= (T.K >> 2)) return;
     f32x4 v;
 #pragma unroll
-    for (int s = 0; s < 4; ++s) v[s] = (4 * k4 + s < T.kvalid) ? ldg(T.src + (size_t)(4 * k4 + s) * T.ld + n) : 0.f;
+    for (int s = 0; s < 4; ++s) v[s] = (4 * k4 + s < T.kvalid) ? ldx(T.src + (size_t)(4 * k4 + s) * T.ld + n) : 0.f;
     stg4(T.dst + ((size_t)k4 * T.N + n) * 4, v);
 }
 
@@ -168,7 +169,7 @@ __device__ __forceinline__ void chain_body(const ChainArgs& P) {
         }
     }
     // epilogue operand of this lane's output element (row 4q + kp, column n0 + c): the bias, or GELU'(z_prev) for variant D
-    const float bias = variant == 4 ? 0.f : variant == 3 ? ldg(P.Zprev + (size_t)(row0 + 4 * q + kp) * H + n0 + c) : ldg(P.bias + n0 + c);
+    const float bias = variant == 4 ? 0.f : variant == 3 ? ldx(P.Zprev + (size_t)(row0 + 4 * q + kp) * H + n0 + c) : ldg(P.bias + n0 + c);
     f32x4 bw4[2];
     if (variant == 2 && wave == 0) {
 #pragma unroll
@@ -180,7 +181,7 @@ __device__ __forceinline__ void chain_body(const ChainArgs& P) {
 #pragma unroll
         for (int t = 0; t < CT; ++t) {
             const int ct = wave + 8 * t;
-            cacc[t] = ldg4(P.A + ((size_t)((row0 >> 2) + q) * H + 16 * ct + c) * 4);   // C layout: rows 4q + i, column c
+            cacc[t] = ldx4(P.A + (size_t)(row0 >> 2) * H * 4, (unsigned)((q * H + 16 * ct + c) * 4));   // C layout: rows 4q + i, column c (C0 is built by this update)
             wf[t] = ldg4(P.W0f + ((size_t)q * H + 16 * ct + c) * 4);                   // k = 4q + s
         }
         {   // a_s = a_{s-1} + (sum of head partials + head bias) / flow_steps: two threads per element, fixed order
@@ -188,12 +189,12 @@ __device__ __forceinline__ void chain_body(const ChainArgs& P) {
             const int r = e >> 4, j = e & 15;
             float a = 0.f;
             if (j < P.ad) {
-                a = ldg(P.ea_in + (size_t)(row0 + r) * P.ea_ld + j);
+                a = ldx(P.ea_in + (size_t)(row0 + r) * P.ea_ld + j);
                 if (P.evp_in) {
                     float pv[NT / 2];
                     const float* pp = P.evp_in + ((size_t)(half * (NT / 2)) * P.M + row0 + r) * P.ap + j;
 #pragma unroll
-                    for (int tp = 0; tp < NT / 2; ++tp) pv[tp] = ldg(pp + (size_t)tp * P.M * P.ap);
+                    for (int tp = 0; tp < NT / 2; ++tp) pv[tp] = ldx(pp + (size_t)tp * P.M * P.ap);
                     float sum = 0.f;
 #pragma unroll
                     for (int tp = 0; tp < NT / 2; ++tp) sum += pv[tp];
@@ -238,14 +239,15 @@ __device__ __forceinline__ void chain_body(const ChainArgs& P) {
 #pragma unroll
         for (int r = 0; r < 2; ++r) {
             const size_t row = (size_t)(row0 + 2 * wave + r);
-            mean[r] = ldg(P.stats + 2 * row); rstd[r] = ldg(P.stats + 2 * row + 1);
-            const float dqr = P.A ? 0.f : ldg(P.dq + row * P.ldq);
+            mean[r] = ldx(P.stats + 2 * row); rstd[r] = ldx(P.stats + 2 * row + 1);
+            const float dqr = P.A ? 0.f : ldx(P.dq + row * P.ldq);
 #pragma unroll
             for (int i = 0; i < NV; ++i) {
                 const int k4 = 4 * (lane + 64 * i);
-                zz[r][i] = ldg4(P.Zprev + row * H + k4);
-                gq[r][i] = ldg4(P.Gv + row * H + k4);
-                if (P.A) dy[r][i] = ldg4(P.A + row * H + k4);
+                const unsigned ro = (unsigned)((2 * wave + r) * H + k4);   // in the workgroup's 16 rows
+                zz[r][i] = ldx4(P.Zprev + (size_t)row0 * H, ro);
+                gq[r][i] = ldx4(P.Gv + (size_t)row0 * H, ro);
+                if (P.A) dy[r][i] = ldx4(P.A + (size_t)row0 * H, ro);
                 else dy[r][i] = f32x4{dqr * wqv[i][0], dqr * wqv[i][1], dqr * wqv[i][2], dqr * wqv[i][3]};
             }
         }
@@ -277,7 +279,7 @@ __device__ __forceinline__ void chain_body(const ChainArgs& P) {
         f32x4 av[NA];
         const float* Ag = P.A + (size_t)row0 * H;
 #pragma unroll
-        for (int i = 0; i < NA; ++i) av[i] = ldg4(Ag + (size_t)(tid + i * FQL_CHAIN_THREADS) * 4);   // 16 rows of H floats are contiguous
+        for (int i = 0; i < NA; ++i) av[i] = ldx4(Ag, (unsigned)(tid + i * FQL_CHAIN_THREADS) * 4);   // 16 rows of H floats are contiguous
 #pragma unroll
         for (int i = 0; i < NA; ++i) {
             const int f = tid + i * FQL_CHAIN_THREADS;
@@ -359,13 +361,14 @@ __device__ __forceinline__ void fql_dgrad0_body(const Dgrad0Args& P) {
     const int ti = (int)blockIdx.x / ntm, tm = (int)blockIdx.x - ti * ntm;
     const GemmTask& T = P.t[ti];
     const int row0 = tm * 16, kq = T.K >> 2;           // contraction columns per wave (a multiple of 16)
-    const float* ap = T.A + (size_t)(row0 + c) * T.lda + kp * kq + 4 * q;          // dZ0[row c][k]
+    const float* ap = T.A + (size_t)row0 * T.lda;                                   // dZ0[row c][k]: written by this update, read from the tile's base
+    const unsigned ao = (unsigned)(c * T.lda + kp * kq + 4 * q);
     const float* bp = T.B + (size_t)(P.col0 + c) * T.ldb + kp * kq + 4 * q;        // W0[input col0 + c][k] (row-major [in][out]: contiguous in k)
     f32x4 acc = {0.f, 0.f, 0.f, 0.f}, acc2 = {0.f, 0.f, 0.f, 0.f};
     for (int g0 = 0; g0 < kq; g0 += 128) {             // (K is a multiple of 512.)  8 k-groups of 16 per round: 16 loads in flight, then 32 MFMAs on two accumulator chains
         f32x4 a[8], b[8];
 #pragma unroll
-        for (int g = 0; g < 8; ++g) { a[g] = ldg4(ap + g0 + 16 * g); b[g] = ldg4(bp + g0 + 16 * g); }
+        for (int g = 0; g < 8; ++g) { a[g] = ldx4(ap, ao, (unsigned)(g0 + 16 * g)); b[g] = ldg4(bp + g0 + 16 * g); }
 #pragma unroll
         for (int g = 0; g < 8; g += 2)
 #pragma unroll
@@ -402,27 +405,27 @@ __device__ __forceinline__ void fql_head_dgrad_body(const GemmTask& T) {
     const f32x4 b4 = ldg4(T.B + (size_t)(n0 + c) * T.ldb + 4 * q);
     float zp[4];
 #pragma unroll
-    for (int i = 0; i < 4; ++i) zp[i] = ldg(T.Zprev + (size_t)(row0 + 4 * q + i) * T.ldc + n0 + c);
+    for (int i = 0; i < 4; ++i) zp[i] = ldx(T.Zprev + (size_t)(row0 + 4 * q + i) * T.ldc + n0 + c);
     {
         const int r = tid >> 4, j = tid & 15;
         float g = 0.f;
         if (j < T.i2) {
-            const float ar = ldg(T.ea_in + (size_t)(row0 + r) * T.i0 + j);
+            const float ar = ldx(T.ea_in + (size_t)(row0 + r) * T.i0 + j);
             float tg;
             if (T.flags & GF_A_EULFIN) {
                 float pv[32];
 #pragma unroll
-                for (int tp = 0; tp < 32; ++tp) pv[tp] = ldg(T.aux2 + ((size_t)min(tp, T.ln_width - 1) * T.M + row0 + r) * T.i0 + j);
+                for (int tp = 0; tp < 32; ++tp) pv[tp] = ldx(T.aux2 + ((size_t)min(tp, T.ln_width - 1) * T.M + row0 + r) * T.i0 + j);
                 float sum = 0.f;
 #pragma unroll
                 for (int tp = 0; tp < 32; ++tp) sum += (tp < T.ln_width) ? pv[tp] : 0.f;
-                tg = clip1(ldg(T.aux + (size_t)(row0 + r) * T.i0 + j) + (sum + ldg(T.eb + j)) * T.f1);
+                tg = clip1(ldx(T.aux + (size_t)(row0 + r) * T.i0 + j) + (sum + ldg(T.eb + j)) * T.f1);
                 if (tn == 0) stg(const_cast<float*>(T.evp) + (size_t)(row0 + r) * T.i0 + j, tg);   // the actor-loss metrics read it
-            } else tg = ldg(T.evp + (size_t)(row0 + r) * T.i0 + j);
+            } else tg = ldx(T.evp + (size_t)(row0 + r) * T.i0 + j);
             g = T.f0 * (ar - tg);
             if (ar > -1.0f && ar < 1.0f) {
                 const size_t o = (size_t)(row0 + r) * T.e_ntp + T.i1 + j;
-                g += ldg(T.ew + o) + ldg(T.ew4 + o);
+                g += ldx(T.ew + o) + ldx(T.ew4 + o);
             }
             if (tn == 0 && T.ea_out) stg(T.ea_out + (size_t)(row0 + r) * T.i0 + j, g);   // the head's weight gradient reads it
         }
@@ -515,7 +518,7 @@ __global__ __launch_bounds__(FQL_CHAIN_THREADS, (V == 0 ? FQL_CHAIN_SPLIT_WAVES_
 #pragma unroll
         for (int t = 0; t < CT; ++t) {
             const int ct = wave + 8 * t;
-            cacc[t] = ldg4(P.A + (((size_t)(row0 >> 4) * (H / 16) + ct) * 64 + 16 * q + c) * 4);   // C0 in GF_C_FRAGT layout: row c, columns 16 ct + 4q .. + 3, 1 KB contiguous per tile
+            cacc[t] = ldx4(P.A + (size_t)(row0 >> 4) * (H / 16) * 256, (unsigned)((ct * 64 + 16 * q + c) * 4));   // C0 in GF_C_FRAGT layout: row c, columns 16 ct + 4q .. + 3, 1 KB contiguous per tile
             wf[t] = ldg4u(reinterpret_cast<const unsigned*>(P.W0f) + ((size_t)q * H + 16 * ct + c) * 4);
         }
         {   // a_s = a_{s-1} + (sum of head partials + head bias) / flow_steps: two threads per element, fixed order
@@ -523,12 +526,12 @@ __global__ __launch_bounds__(FQL_CHAIN_THREADS, (V == 0 ? FQL_CHAIN_SPLIT_WAVES_
             const int r = e >> 4, j = e & 15;
             float a = 0.f;
             if (j < P.ad) {
-                a = ldg(P.ea_in + (size_t)(row0 + r) * P.ea_ld + j);
+                a = ldx(P.ea_in + (size_t)(row0 + r) * P.ea_ld + j);
                 if (P.evp_in) {
                     float pv[NT / 2];
                     const float* pp = P.evp_in + ((size_t)(half * (NT / 2)) * P.M + row0 + r) * P.ap + j;
 #pragma unroll
-                    for (int tp = 0; tp < NT / 2; ++tp) pv[tp] = ldg(pp + (size_t)tp * P.M * P.ap);
+                    for (int tp = 0; tp < NT / 2; ++tp) pv[tp] = ldx(pp + (size_t)tp * P.M * P.ap);
                     float sum = 0.f;
 #pragma unroll
                     for (int tp = 0; tp < NT / 2; ++tp) sum += pv[tp];
@@ -578,7 +581,7 @@ __global__ __launch_bounds__(FQL_CHAIN_THREADS, (V == 0 ? FQL_CHAIN_SPLIT_WAVES_
 #pragma unroll
         for (int i = 0; i < NA; ++i) {
             const int pc = (tid + i * FQL_CHAIN_THREADS) & (4 * RS - 1);   // piece inside the plane: row pc / (RS / 4), slot pc % (RS / 4)
-            av[i] = ldg4u((i < NA / 2 ? Ah : Al) + (size_t)pc * 4);
+            av[i] = ldx4u(i < NA / 2 ? Ah : Al, (unsigned)pc * 4);
         }
 #pragma unroll
         for (int i = 0; i < NA; ++i) {

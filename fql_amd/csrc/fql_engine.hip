@@ -296,6 +296,37 @@ inline bool fused_tail_env() {
     const char* e = getenv("FQL_FUSED_TAIL");
     return !e || atoi(e) != 0;
 }
+// FQL_AQL_ACQUIRE=1: every kernel packet of every AQL program keeps its agent-scope acquire (the A/B switch and the fallback of build_aql's
+// L1-independent programs).  Read when an engine is created.
+inline bool aql_acquire_env() {
+    const char* e = getenv("FQL_AQL_ACQUIRE");
+    return e && atoi(e) != 0;
+}
+// The kernels that read everything an earlier launch of their program wrote past the L1 and the scalar cache (fql_kernels.h ldx: the audit
+// list is FQL_DUMP's "in-update reads"), with the twins that share their bodies.  A program all of whose launches bind one of these needs
+// no acquire between its packets (build_aql).  Not here: fql_finalize_kernel (its partials are plain loads: an update with FQL_FUSED_TAIL=0
+// keeps its acquires), the convolution family and every other agent kind's kernels.
+inline bool l1_independent_kernel(const void* fn) {
+#define FQL_L1_CHAIN(HH)                                                                                                                             \
+    (const void*)fql_chain_kernel<HH, 0>, (const void*)fql_chain_kernel<HH, 1>, (const void*)fql_chain_kernel<HH, 2>, (const void*)fql_chain_kernel<HH, 3>, \
+    (const void*)fql_chain_multi_kernel<HH, 0>, (const void*)fql_chain_multi_kernel<HH, 1>, (const void*)fql_chain_multi_kernel<HH, 2>,             \
+    (const void*)fql_chain_multi_kernel<HH, 3>, (const void*)fql_chain_split_kernel<HH, 0>, (const void*)fql_chain_split_kernel<HH, 1>,             \
+    (const void*)fql_chain_split_kernel<HH, 2>
+    static const void* const table[] = {
+        (const void*)fql_prep_kernel, (const void*)fql_prep_multi_kernel,
+        (const void*)fql_gemm16_kernel<false>, (const void*)fql_gemm16_kernel<true>,
+        (const void*)fql_gemm16_euler_kernel<false>, (const void*)fql_gemm16_euler_kernel<true>,
+        (const void*)fql_side_kernel, (const void*)fql_side_ka_kernel, (const void*)fql_side_big_kernel, (const void*)fql_side_big_ka_kernel,
+        (const void*)fql_side_split_kernel, (const void*)fql_side_split_ka_kernel,
+        FQL_L1_CHAIN(256), FQL_L1_CHAIN(512),
+        (const void*)fql_dgrad0_kernel, (const void*)fql_dgrad0_multi_kernel, (const void*)fql_head_dgrad_kernel, (const void*)fql_head_dgrad_multi_kernel,
+        (const void*)fql_loss_actor_kernel, (const void*)fql_loss_actor_multi_kernel,
+        (const void*)fql_euler_finish_kernel, (const void*)fql_euler_finish_multi_kernel,
+        (const void*)fql_adam_kernel, (const void*)fql_adam_multi_kernel, (const void*)fql_wfrag_kernel};
+#undef FQL_L1_CHAIN
+    for (const void* k : table) if (k == fn) return true;
+    return false;
+}
 // a side-lane launch's four host tables as SideArgs; null when a family exceeds its capacity
 inline std::unique_ptr<SideArgs> ka_side_args(const Launch& L) {
     const size_t ng = L.h_gemm.size(), nw = L.h_wgrad.size(), nl = L.h_ln.size(), nm = L.h_misc.size();
@@ -2342,6 +2373,46 @@ struct fql_engine {
         fprintf(stderr, "[fql] launches per lane:");
         for (int l = 0; l < FQL_LANES; ++l) fprintf(stderr, " %d", cnt[l]);
         fprintf(stderr, "\n");
+        dump_in_update_reads(pr);
+    }
+    // FQL_DUMP, second part: per launch, the buffers it reads that an earlier launch of the same program writes - the operands that must be read past
+    // the L1 (fql_kernels.h ldx) before the program may drop the acquires between its packets (build_aql).  A buffer is named by the task member that
+    // holds it where the op carries a payload, else by its place among the op's reads; `<- #n` is the last earlier launch that writes it.
+    void dump_in_update_reads(const Program& pr) const {
+        auto member = [](const Op& o, const void* p) -> std::string {
+            std::string s;
+            auto add = [&](const char* n, const void* q) { if (q == p) { if (!s.empty()) s += '/'; s += n; } };
+            if (o.type == OP_GEMM || o.type == OP_GEMM64 || o.type == OP_HEAD_DGRAD) {
+                const GemmTask& t = o.gemm;
+                add("A", t.A); add("B", t.B); add("bias", t.bias); add("Zprev", t.Zprev); add("aux", t.aux); add("aux2", t.aux2); add("ln_g", t.ln_g);
+                add("ln_b", t.ln_b); add("ea_in", t.ea_in); add("evp", t.evp); add("ew", t.ew); add("ew4", t.ew4); add("eb", t.eb);
+            } else if (o.type == OP_WGRAD) {
+                add("X", o.wgrad.X); add("dZ", o.wgrad.dZ);
+            } else if (o.type == OP_LNBWD) {
+                const LnBwdTask& t = o.ln;
+                add("dY", t.dY); add("Z", t.Z); add("Gv", t.Gv); add("stats", t.stats); add("gamma", t.gamma); add("dq", t.dq); add("wq", t.wq);
+            }
+            return s;
+        };
+        std::map<const void*, int> writer;   // buffer -> last launch, so far, that writes it
+        size_t oi = 0;
+        for (int li = 0; li < (int)pr.launches.size(); ++li) {
+            std::string line;
+            std::vector<const Op*> mine;
+            for (const Op& o : pr.ops) if (o.launch == li) mine.push_back(&o);
+            for (const Op* o : mine)
+                for (size_t ri = 0; ri < o->reads.size(); ++ri) {
+                    auto it = writer.find(o->reads[ri]);
+                    if (it == writer.end()) continue;
+                    char b[96];
+                    const std::string m = member(*o, o->reads[ri]);
+                    snprintf(b, sizeof b, " t%d.%s%s<-#%d", (int)o->type, m.empty() ? "r" : m.c_str(), m.empty() ? std::to_string(ri).c_str() : "", it->second);
+                    line += b;
+                }
+            for (const Op* o : mine) for (const void* w : o->writes) writer[w] = li;
+            fprintf(stderr, "[fql] #%2d type %2d in-update reads:%s\n", li, (int)pr.launches[li].type, line.empty() ? " none" : line.c_str());
+        }
+        (void)oi;
     }
     // Two FORKED lanes (>= 1; lane 0 is the capture's origin stream) must not wait on each other in both directions: the HIP
     // runtime bundled with torch 2.10 (ROCm 7.0) walks the resulting cycle of parallel capture streams forever in
@@ -2406,6 +2477,12 @@ struct fql_engine {
     // The program as AQL packet templates for the engine's own HSA queues (fql_aql.h): one queue per lane, the barrier bit inside a lane,
     // completion signal -> barrier-AND packet across lanes, into pr.aql.  Left off (pr.aql.ok = false, the captured graph runs) when the HSA
     // runtime does not come up or FQL_AQL=0.
+    const bool aql_acquire = aql_acquire_env();
+    static bool l1_independent(const Program& pr) {
+        for (const Launch& L : pr.launches)
+            if (!l1_independent_kernel(L.k.fn) || L.type == OP_IQLD_CFG) return false;   // (OP_IQLD_CFG: the one launch with an issue-time word)
+        return !pr.launches.empty();
+    }
     void build_aql(Program& pr) {
         static const bool off = getenv("FQL_AQL") && atoi(getenv("FQL_AQL")) == 0;
         static const bool trace_a = getenv("FQL_TRACE") != nullptr;
@@ -2446,7 +2523,11 @@ struct fql_engine {
             // fences between packets: agent scope both ways, as the HIP runtime sets them for kernels of one stream.  Measured (profiles/r03_aql.txt): system scope
             // 416 us per update, agent 355, acquire dropped 336 with the same results over 1300 updates (the invalidate is then left to eviction: not a guarantee,
             // not shipped), release dropped 332 and wrong.
+            // An L1-independent program - every launch binds a kernel that reads what earlier launches of the program wrote past the L1 and the
+            // scalar cache (l1_independent_kernel), none has words written at issue time - drops the acquire of every kernel packet but the first
+            // of each lane: there is nothing stale those caches could serve.  The release stays on every packet.  FQL_AQL_ACQUIRE=1 keeps them.
             constexpr int AG = HSA_FENCE_SCOPE_AGENT, SY = HSA_FENCE_SCOPE_SYSTEM, NO = HSA_FENCE_SCOPE_NONE;
+            const int interior = l1_independent(pr) && !aql_acquire ? NO : AG;
             for (int l = 1; l < FQL_AQL_LANES; ++l)
                 if (used[l]) {   // the previous update has finished on every lane
                     AqlPacket b = AqlRuntime::barrier_packet(false, NO, NO);
@@ -2461,7 +2542,7 @@ struct fql_engine {
                     for (size_t j = 0; j < 5 && w0 + j < L.waits.size(); ++j) b.deps[j] = sig[L.waits[w0 + j]];
                     ap.lane[L.lane].push_back(b);
                 }
-                AqlPacket k = AqlRuntime::kernel_packet(rec[i], *ki[i], (uint64_t)(uintptr_t)kargs + koff[i], true, first[L.lane] ? SY : AG, AG);
+                AqlPacket k = AqlRuntime::kernel_packet(rec[i], *ki[i], (uint64_t)(uintptr_t)kargs + koff[i], true, first[L.lane] ? SY : interior, AG);
                 first[L.lane] = false;
                 k.complete = sig[i];
                 ap.lane[L.lane].push_back(k);
@@ -6715,6 +6796,43 @@ int fql_debug_task_forms(fql_handle h, fql_group g, void* out, size_t bytes) {
     if (g) for (const GLaunch& G : g->launches) w.push_back(G.form);
     else for (const Launch& L : h->prog_full.launches) w.push_back(form(L));
     w[5] = (int32_t)w.size() - 6;
+    w[0] = (int32_t)w.size();
+    if (bytes > w.size() * sizeof(int32_t)) return FQL_E_INVALID;
+    if (bytes) std::memcpy(out, w.data(), bytes);
+    return FQL_OK;
+}
+
+// Diagnostic only (not in include/fql_amd.h, beside fql_debug_task_forms): the fences of the kernel packets of an update program on the engine's own
+// queues, as int32 words
+//   [words (this one included), 1 if every launch binds a kernel of l1_independent_kernel's table (and none has an issue-time word) else 0,
+//    1 if FQL_AQL_ACQUIRE was set when the engine was created else 0, kernel packets], then per kernel packet, lane by lane in queue order:
+//   lane, acquire scope, release scope (hsa_fence_scope_t: 0 none, 1 agent, 2 system) - read back from the packet headers build_aql wrote
+// of the handle's prog_full (no packets before its first update on the engine's own stream, or where the AQL path is off), or of the group `g`'s
+// fused program when g is given: a group runs its captured graph, so it has the table word and no packets.  Prefix reads as there.
+int fql_debug_aql_fences(fql_handle h, fql_group g, void* out, size_t bytes) {
+    if ((!h && !g) || (bytes && !out) || bytes % sizeof(int32_t)) return FQL_E_INVALID;
+    if (!g && (h->visual || !h->prog_full.exec || h->prog_full.launches.empty())) return FQL_E_STATE;
+    std::vector<int32_t> w{0, 0, 0, 0};
+    if (g) {
+        bool all = !g->launches.empty();
+        for (const GLaunch& G : g->launches) all = all && l1_independent_kernel(G.k.fn);
+        w[1] = all;
+        w[2] = g->m.empty() ? 0 : (int32_t)g->m[0]->aql_acquire;
+    } else {
+        w[1] = fql_engine::l1_independent(h->prog_full);
+        w[2] = h->aql_acquire;
+        const AqlProgram& ap = h->prog_full.aql;
+        if (ap.ok)
+            for (int l = 0; l < FQL_AQL_LANES; ++l)
+                for (const AqlPacket& p : ap.lane[l]) {
+                    if (p.barrier) continue;
+                    const uint32_t hdr = p.w[0] & 0xFFFFu;
+                    w.push_back(l);
+                    w.push_back((int32_t)((hdr >> HSA_PACKET_HEADER_SCACQUIRE_FENCE_SCOPE) & 3u));
+                    w.push_back((int32_t)((hdr >> HSA_PACKET_HEADER_SCRELEASE_FENCE_SCOPE) & 3u));
+                }
+    }
+    w[3] = ((int32_t)w.size() - 4) / 3;
     w[0] = (int32_t)w.size();
     if (bytes > w.size() * sizeof(int32_t)) return FQL_E_INVALID;
     if (bytes) std::memcpy(out, w.data(), bytes);

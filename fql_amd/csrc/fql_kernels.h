@@ -18,6 +18,31 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 #define FQL_GAS __attribute__((address_space(1)))
 __device__ __forceinline__ float ldg(const float* p) { return *(const FQL_GAS float*)p; }
 __device__ __forceinline__ f32x4 ldg4(const float* p) { return *(const FQL_GAS f32x4*)p; }
+// Two load families.  ldg / ldg4 / ldg4u: data no launch of the running update writes (parameters and their fragment-major copies, task tables, the
+// dataset, DevState words of the previous update); they may hit this CU's L1 and the scalar cache.  ldx / ldx4 / ldx4u: everything an earlier launch of
+// the same program wrote.  They go past the L1 (sc1) and are always vector loads (the scalar cache is no more coherent than the L1), so a program all
+// of whose in-update reads are ldx needs no acquire between its packets (the producer's release stays).  A word is an agent-scope
+// relaxed load (global_load_dword sc1).  16 bytes are a raw buffer load with the sc1 bit: `base` must be uniform over the wave (a task's pointer, or
+// that plus a workgroup's tile offset), `i` is the lane's offset and `s` a further uniform offset (the instruction's scalar offset), in elements, below 2^29.  (A non-temporal load is no substitute: it carries nt, not
+// sc1, and a uniform one becomes a scalar load.)  An operand that is a parameter in one launch and an activation in another is read with ldx.
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+// the buffer descriptor of a uniform base: the two halves go through v_readfirstlane (free where the compiler already holds them in SGPRs), so a base it
+// could not prove uniform - a task member reloaded behind a store - costs two moves and not a loop over the lanes' values
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t ldx_rsrc(const void* base) {
+    const uint64_t b = (uint64_t)base;
+    const uint64_t u = ((uint64_t)(unsigned)__builtin_amdgcn_readfirstlane((int)(b >> 32)) << 32) | (unsigned)__builtin_amdgcn_readfirstlane((int)b);
+    return __builtin_amdgcn_make_buffer_rsrc((void*)u, 0, 0x7FFFFFFF, 0x00020000);
+}
+__device__ __forceinline__ float ldx(const float* p) { return __hip_atomic_load((const FQL_GAS float*)p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ __forceinline__ u32x4 ldx4u(const unsigned* base, unsigned i, unsigned s = 0) {
+    return __builtin_amdgcn_raw_buffer_load_b128(ldx_rsrc(base), (int)(i * 4u), __builtin_amdgcn_readfirstlane((int)(s * 4u)), 16);   // aux 16 = sc1
+}
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ f32x2 ldx2(const float* base, unsigned i, unsigned s = 0) {   // 8 bytes, where the plain load was 8 bytes
+    return __builtin_bit_cast(f32x2, __builtin_amdgcn_raw_buffer_load_b64(ldx_rsrc(base), (int)(i * 4u), __builtin_amdgcn_readfirstlane((int)(s * 4u)), 16));
+}
+__device__ __forceinline__ f32x4 ldx4(const float* base, unsigned i, unsigned s = 0) { return __builtin_bit_cast(f32x4, ldx4u((const unsigned*)base, i, s)); }
 __device__ __forceinline__ void stg(float* p, float v) { *(FQL_GAS float*)p = v; }
 __device__ __forceinline__ void stg4(float* p, f32x4 v) { *(FQL_GAS f32x4*)p = v; }
 
@@ -623,7 +648,7 @@ __device__ __forceinline__ void gemm16_body(const GemmTask& T, float* lds) {
         for (int t = 0; t < CT; ++t) {
             const int ct = min(wave + 4 * t, (K >> 4) - 1);
 #pragma unroll
-            for (int i = 0; i < 4; ++i) cacc[t][i] = ldg(T.A + (size_t)(row0 + 4 * q + i) * T.lda + 16 * ct + c);
+            for (int i = 0; i < 4; ++i) cacc[t][i] = ldx(T.A + (size_t)(row0 + 4 * q + i) * T.lda + 16 * ct + c);
 #pragma unroll
             for (int s4 = 0; s4 < 4; ++s4) wf[t][s4] = ldg(T.ew + (size_t)(4 * q + s4) * K + 16 * ct + c);
         }
@@ -631,11 +656,11 @@ __device__ __forceinline__ void gemm16_body(const GemmTask& T, float* lds) {
             const int r = e >> 4, j = e & 15;
             float a = 0.f;
             if (j < ad) {
-                a = ldg(T.ea_in + (size_t)(row0 + r) * T.i0 + j);
+                a = ldx(T.ea_in + (size_t)(row0 + r) * T.i0 + j);
                 if (T.evp) {  // a_s = a_{s-1} + (sum of head partials + head bias) / flow_steps, fixed summation order
                     float pv[32];
 #pragma unroll
-                    for (int tp = 0; tp < 32; ++tp) pv[tp] = ldg(T.evp + ((size_t)min(tp, T.e_ntp - 1) * M + row0 + r) * apw + j);
+                    for (int tp = 0; tp < 32; ++tp) pv[tp] = ldx(T.evp + ((size_t)min(tp, T.e_ntp - 1) * M + row0 + r) * apw + j);
                     float sum = 0.f;
 #pragma unroll
                     for (int tp = 0; tp < 32; ++tp) sum += (tp < T.e_ntp) ? pv[tp] : 0.f;
@@ -670,22 +695,22 @@ __device__ __forceinline__ void gemm16_body(const GemmTask& T, float* lds) {
             const int r = sdiv(e, frcp(K)), j = e - r * K;
             float g = 0.f;
             if (j < T.i2) {
-                const float ar = ldg(T.ea_in + (size_t)(row0 + r) * T.i0 + j);
+                const float ar = ldx(T.ea_in + (size_t)(row0 + r) * T.i0 + j);
                 float tg;
                 if (flags & GF_A_EULFIN) {   // same loads, same summation order as fql_euler_finish_kernel: the target is bit-identical
                     float pv[32];
 #pragma unroll
-                    for (int tp = 0; tp < 32; ++tp) pv[tp] = ldg(T.aux2 + ((size_t)min(tp, T.ln_width - 1) * T.M + row0 + r) * T.i0 + j);
+                    for (int tp = 0; tp < 32; ++tp) pv[tp] = ldx(T.aux2 + ((size_t)min(tp, T.ln_width - 1) * T.M + row0 + r) * T.i0 + j);
                     float sum = 0.f;
 #pragma unroll
                     for (int tp = 0; tp < 32; ++tp) sum += (tp < T.ln_width) ? pv[tp] : 0.f;
-                    tg = clip1(ldg(T.aux + (size_t)(row0 + r) * T.i0 + j) + (sum + ldg(T.eb + j)) * T.f1);
+                    tg = clip1(ldx(T.aux + (size_t)(row0 + r) * T.i0 + j) + (sum + ldg(T.eb + j)) * T.f1);
                     if (tn == 0) stg(const_cast<float*>(T.evp) + (size_t)(row0 + r) * T.i0 + j, tg);   // the actor-loss metrics read it
-                } else tg = ldg(T.evp + (size_t)(row0 + r) * T.i0 + j);
+                } else tg = ldx(T.evp + (size_t)(row0 + r) * T.i0 + j);
                 g = T.f0 * (ar - tg);
                 if (ar > -1.0f && ar < 1.0f) {
                     const size_t o = (size_t)(row0 + r) * T.e_ntp + T.i1 + j;
-                    g += ldg(T.ew + o) + ldg(T.ew4 + o);
+                    g += ldx(T.ew + o) + ldx(T.ew4 + o);
                 }
                 if (tn == 0 && T.ea_out) stg(T.ea_out + (size_t)(row0 + r) * T.i0 + j, g);   // the head's wgrad reads it
             }
@@ -700,7 +725,7 @@ __device__ __forceinline__ void gemm16_body(const GemmTask& T, float* lds) {
         for (int i = 0; i < NA; ++i) {
             const int f = min(tid + i * FQL_THREADS, nA - 1);  // clamped, unconditional
             const int r = sdiv(f, rk4), kk = f - r * k4;
-            av[i] = ldg4(Ag + (size_t)r * T.lda + 4 * kk);
+            av[i] = ldx4(Ag, (unsigned)(r * T.lda + 4 * kk));
         }
         if (pass == 0) issue_b();
 #pragma unroll
@@ -779,7 +804,7 @@ __device__ __forceinline__ void gemm16_body(const GemmTask& T, float* lds) {
 #pragma unroll
         for (int rt = 0; rt < TMT; ++rt)
 #pragma unroll
-            for (int i = 0; i < 4; ++i) zpre[rt][i] = ldg(T.Zprev + (size_t)(row0 + 16 * rt + 4 * q + i) * T.ldc + n0 + c);
+            for (int i = 0; i < 4; ++i) zpre[rt][i] = ldx(T.Zprev + (size_t)(row0 + 16 * rt + 4 * q + i) * T.ldc + n0 + c);
     }
     f32x4 acc[TMT];
 #pragma unroll
@@ -861,7 +886,7 @@ __device__ __forceinline__ void gemm16_body(const GemmTask& T, float* lds) {
             // agents/fql.py:166-169: actions = actions + vels / flow_steps ; t = (i+1)/flow_steps
             float* xr = T.aux + (size_t)row * T.i0 + T.i1;
             if (n < T.i2) {
-                const float a = ldg(xr + n) + v * T.f0;
+                const float a = ldx(xr + n) + v * T.f0;
                 stg(xr + n, a);
                 if (flags & GF_EULER_LAST) stg(T.aux2 + (size_t)row * T.ldc + n, clip1(a));
             }
@@ -942,9 +967,9 @@ __device__ __forceinline__ void ln_fold_partials(const float* __restrict__ parti
         f32x4 pv[NR][4];
 #pragma unroll
         for (int i = 0; i < NR; ++i) {
-            const float* pp = partials + (size_t)(row_first + 16 * i) * rs;
+            const unsigned po = (unsigned)((row_first + 16 * i) * rs);
 #pragma unroll
-            for (int t = 0; t < 4; ++t) pv[i][t] = ldg4(pp + 4 * min(base + t, nf4 - 1));
+            for (int t = 0; t < 4; ++t) pv[i][t] = ldx4(partials, po + 4 * min(base + t, nf4 - 1));
         }
 #pragma unroll
         for (int i = 0; i < NR; ++i)
@@ -990,11 +1015,12 @@ __device__ __forceinline__ void gemm64_body(const GemmTask& T, float* lds) {
     // when a chunk is written to LDS, as in the 32-row body), and the first two chunks are requested before the statistics' partial sums are folded.
     f32x4 ra0[NRA], rb0[4], ra1[NRA], rb1[4], lg0, lb0, lg1, lb1;
     lg0 = lb0 = lg1 = lb1 = f32x4{0.f, 0.f, 0.f, 0.f};
-    const float* __restrict__ Ag = T.A + (size_t)(row0 + sr) * T.lda + 4 * sc4;
+    const float* __restrict__ Ag = T.A + (size_t)row0 * T.lda;   // (an activation: ldx4 from the tile's uniform base)
+    const unsigned ao = (unsigned)(sr * T.lda + 4 * sc4);
     const float* __restrict__ Bg = transb ? T.B + (size_t)(n0 + sr) * T.ldb + 4 * sc4 : T.B + (size_t)sr * T.ldb + n0 + 4 * sc4;
     auto load_chunk = [&](f32x4 (&ra)[NRA], f32x4 (&rb)[4], f32x4& lg, f32x4& lb, int k0) {  // K is a multiple of 64: no guards, unconditional loads
 #pragma unroll
-        for (int i = 0; i < NRA; ++i) ra[i] = ldg4(Ag + (size_t)(16 * i) * T.lda + k0);
+        for (int i = 0; i < NRA; ++i) ra[i] = ldx4(Ag, ao, (unsigned)(16 * i * T.lda + k0));
 #pragma unroll
         for (int i = 0; i < 4; ++i) rb[i] = transb ? ldg4(Bg + (size_t)(16 * i) * T.ldb + k0) : ldg4(Bg + (size_t)(k0 + 16 * i) * T.ldb);
         if (a_ln) { lg = ldg4(T.ln_g + k0 + 4 * sc4); lb = ldg4(T.ln_b + k0 + 4 * sc4); }
@@ -1116,8 +1142,8 @@ __device__ __forceinline__ void gemm64_body(const GemmTask& T, float* lds) {
                 float v = acc[i][j][r] + (j ? bias1 : bias0);
                 if (flags & GF_SAVE_Z) { float gg, dg; gelu_both(v, gg, dg); stg(T.Zout + o, dg); v = (flags & GF_GELU) ? gg : v; }
                 else if (flags & GF_GELU) v = gelu_f(v);
-                if (flags & GF_GELUGRAD) v *= ldg(T.Zprev + o);
-                if (flags & GF_RELUGRAD) v = (ldg(T.Zprev + o) > 0.f) ? v : 0.f;
+                if (flags & GF_GELUGRAD) v *= ldx(T.Zprev + o);
+                if (flags & GF_RELUGRAD) v = (ldx(T.Zprev + o) > 0.f) ? v : 0.f;
                 stg(T.C + o, v);
                 s1[i][r] += v; s2[i][r] += v * v;
             }
@@ -1197,13 +1223,14 @@ __device__ __forceinline__ void gemm32_body(const GemmTask& T, float* lds) {
     // B staging coordinates of float4 i (row of the LDS image, float offset inside the row)
     const int br0 = (transb || NJ == 2) ? sr : (tid >> 3), brs = (transb || NJ == 2) ? 16 : 32;
     const int bc4 = (transb || NJ == 2) ? sc4 : (tid & 7);
-    const float* __restrict__ Ag = T.A + (size_t)(row0 + sr) * T.lda + 4 * sc4;
+    const float* __restrict__ Ag = T.A + (size_t)row0 * T.lda;   // (an activation: ldx4 from the tile's uniform base)
+    const unsigned ao = (unsigned)(sr * T.lda + 4 * sc4);
     const float* __restrict__ Bg = transb ? T.B + (size_t)(n0 + br0) * T.ldb + 4 * bc4 : T.B + (size_t)br0 * T.ldb + n0 + 4 * bc4;
     f32x4 ra0[2], rb0[NB], ra1[2], rb1[NB], lg0, lb0, lg1, lb1;
     lg0 = lb0 = lg1 = lb1 = f32x4{0.f, 0.f, 0.f, 0.f};
     auto load_chunk = [&](f32x4 (&ra)[2], f32x4 (&rb)[NB], f32x4& lg, f32x4& lb, int k0) {   // K is a multiple of 64: no guards
 #pragma unroll
-        for (int i = 0; i < 2; ++i) ra[i] = ldg4(Ag + (size_t)(16 * i) * T.lda + k0);
+        for (int i = 0; i < 2; ++i) ra[i] = ldx4(Ag, ao, (unsigned)(16 * i * T.lda + k0));
 #pragma unroll
         for (int i = 0; i < NB; ++i) rb[i] = transb ? ldg4(Bg + (size_t)(brs * i) * T.ldb + k0) : ldg4(Bg + (size_t)(k0 + brs * i) * T.ldb);
         if (a_ln) { lg = ldg4(T.ln_g + k0 + 4 * sc4); lb = ldg4(T.ln_b + k0 + 4 * sc4); }
@@ -1319,9 +1346,9 @@ __device__ __forceinline__ void gemm32_body(const GemmTask& T, float* lds) {
 #pragma unroll
                 for (int r = 0; r < 4; ++r) v[r] = gelu_f(v[r]);
             }
-            if (flags & GF_GELUGRAD) v *= ldg4(T.Zprev + o);
+            if (flags & GF_GELUGRAD) v *= ldx4(T.Zprev + (size_t)row0 * T.ldc, (unsigned)((16 * wr + c) * T.ldc + n));
             if (flags & GF_RELUGRAD) {
-                const f32x4 zp = ldg4(T.Zprev + o);
+                const f32x4 zp = ldx4(T.Zprev + (size_t)row0 * T.ldc, (unsigned)((16 * wr + c) * T.ldc + n));
 #pragma unroll
                 for (int r = 0; r < 4; ++r) v[r] = (zp[r] > 0.f) ? v[r] : 0.f;
             }
@@ -1411,13 +1438,14 @@ __device__ __forceinline__ void gemm32s_body(const GemmTask& T, float* lds_f) {
     const int sr = tid >> 4, sc4 = tid & 15;      // A staging: rows sr, sr + 16; float4 column sc4 (k = 4 sc4 .. 4 sc4 + 3)
     const int br0 = (transb || NJ == 2) ? sr : (tid >> 3), brs = (transb || NJ == 2) ? 16 : 32;
     const int bc4 = (transb || NJ == 2) ? sc4 : (tid & 7);
-    const float* __restrict__ Ag = T.A + (size_t)(row0 + sr) * T.lda + 4 * sc4;
+    const float* __restrict__ Ag = T.A + (size_t)row0 * T.lda;   // (an activation: ldx4 from the tile's uniform base)
+    const unsigned ao = (unsigned)(sr * T.lda + 4 * sc4);
     const float* __restrict__ Bg = transb ? T.B + (size_t)(n0 + br0) * T.ldb + 4 * bc4 : T.B + (size_t)br0 * T.ldb + n0 + 4 * bc4;
     f32x4 ra0[2], rb0[NB], ra1[2], rb1[NB], lg0, lb0, lg1, lb1;
     lg0 = lb0 = lg1 = lb1 = f32x4{0.f, 0.f, 0.f, 0.f};
     auto load_chunk = [&](f32x4 (&ra)[2], f32x4 (&rb)[NB], f32x4& lg, f32x4& lb, int k0) {   // K is a multiple of 64: no guards
 #pragma unroll
-        for (int i = 0; i < 2; ++i) ra[i] = ldg4(Ag + (size_t)(16 * i) * T.lda + k0);
+        for (int i = 0; i < 2; ++i) ra[i] = ldx4(Ag, ao, (unsigned)(16 * i * T.lda + k0));
 #pragma unroll
         for (int i = 0; i < NB; ++i) rb[i] = transb ? ldg4(Bg + (size_t)(brs * i) * T.ldb + k0) : ldg4(Bg + (size_t)(k0 + brs * i) * T.ldb);
         if (a_ln) { lg = ldg4(T.ln_g + k0 + 4 * sc4); lb = ldg4(T.ln_b + k0 + 4 * sc4); }
@@ -1565,9 +1593,9 @@ __device__ __forceinline__ void gemm32s_body(const GemmTask& T, float* lds_f) {
 #pragma unroll
                 for (int r = 0; r < 4; ++r) v[r] = gelu_f(v[r]);
             }
-            if (flags & GF_GELUGRAD) v *= ldg4(T.Zprev + o);
+            if (flags & GF_GELUGRAD) v *= ldx4(T.Zprev + (size_t)row0 * T.ldc, (unsigned)((16 * wr + c) * T.ldc + n));
             if (flags & GF_RELUGRAD) {
-                const f32x4 zp = ldg4(T.Zprev + o);
+                const f32x4 zp = ldx4(T.Zprev + (size_t)row0 * T.ldc, (unsigned)((16 * wr + c) * T.ldc + n));
 #pragma unroll
                 for (int r = 0; r < 4; ++r) v[r] = (zp[r] > 0.f) ? v[r] : 0.f;
             }
@@ -1656,8 +1684,8 @@ __device__ __forceinline__ void wgrad_load_chunk(f32x2 (&a)[8], f32x4 (&b)[8], c
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
         const bool v = i < cnt;   // wave-uniform
-        a[i] = v ? *(const FQL_GAS f32x2*)(xp + i * sx + xo) : f32x2{0.f, 0.f};
-        b[i] = v ? ldg4(zp + i * sz + zo) : f32x4{0.f, 0.f, 0.f, 0.f};
+        a[i] = v ? ldx2(xp, xo, (unsigned)(i * sx)) : f32x2{0.f, 0.f};   // both operands are activations of this update; xp / zp are wave-uniform
+        b[i] = v ? ldx4(zp, zo, (unsigned)(i * sz)) : f32x4{0.f, 0.f, 0.f, 0.f};
     }
 }
 // the reduction over the 4 waves and the stores, shared by the fp32 and the split body
@@ -1765,8 +1793,8 @@ __device__ __forceinline__ void wgrad_split_body(const WgradTask& T, int bid, fl
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
             const int st = min(s0 + i, steps - 1);
-            a[i] = ldg(xp + st * sx + xo);
-            b[i] = ldg4(zp + st * sz + zo);
+            a[i] = ldx(xp + st * sx + xo);
+            b[i] = ldx4(zp, zo, (unsigned)(st * sz));
         }
     };
     auto mma = [&](const float (&a)[8], const f32x4 (&b)[8], int s0) {
@@ -1820,11 +1848,9 @@ __device__ __forceinline__ void lnbwd_body(const LnBwdTask& T, int bid, float (*
     if (local < T.ntiles_rows) {
         const int row = local * 4 + wave;
         if (row >= T.M) return;
-        const float mean = ldg(T.stats + 2 * row), rstd = ldg(T.stats + 2 * row + 1);
-        const float* dy = T.dY + (size_t)row * T.ld;
-        const float* z = T.Z + (size_t)row * T.ld;
-        const float* gv = T.Gv + (size_t)row * T.ld;
-        const float dqr = SYN ? ldg(T.dq + (size_t)row * T.ldq) : 0.f;
+        const float mean = ldx(T.stats + 2 * row), rstd = ldx(T.stats + 2 * row + 1);
+        const unsigned ro = (unsigned)(row * T.ld);   // everything but gamma and the head's weights was written by this update: ldx from the tasks' bases
+        const float dqr = SYN ? ldx(T.dq + (size_t)row * T.ldq) : 0.f;
         // H <= 1024 (a multiple of 16): <= 4 float4 per lane and tensor, columns 4 (lane + 64 i) ..; every load is issued first.  (Round 1 read 16
         // single floats per lane and tensor whatever H was - at H = 512 half of those 64 loads were clamped duplicates.)
         f32x4 zz[4], dd[4], gm[4], gq[4];
@@ -1832,13 +1858,13 @@ __device__ __forceinline__ void lnbwd_body(const LnBwdTask& T, int bid, float (*
         for (int i = 0; i < 4; ++i) {
             const int k4 = 4 * (lane + 64 * i);
             if (k4 < T.H) {
-                zz[i] = ldg4(z + k4);
-                gq[i] = ldg4(gv + k4);
+                zz[i] = ldx4(T.Z, ro + k4);
+                gq[i] = ldx4(T.Gv, ro + k4);
                 gm[i] = ldg4(T.gamma + k4);
                 if (SYN) {
 #pragma unroll
                     for (int e = 0; e < 4; ++e) dd[i][e] = dqr * ldg(T.wq + (size_t)(k4 + e) * T.ldw);
-                } else dd[i] = ldg4(dy + k4);
+                } else dd[i] = ldx4(T.dY, ro + k4);
             } else zz[i] = gq[i] = gm[i] = dd[i] = f32x4{0.f, 0.f, 0.f, 0.f};
         }
         f32x4 d[4], xh[4];
@@ -1882,9 +1908,9 @@ __device__ __forceinline__ void lnbwd_body(const LnBwdTask& T, int bid, float (*
 #pragma unroll
                 for (int u = 0; u < 16; ++u) {
                     const int m = min(m0 + 16 * u, T.M - 1);
-                    st[u] = *(const FQL_GAS f32x2*)(T.stats + 2 * m);
-                    dv[u] = SYN ? ldg(T.dq + (size_t)m * T.ldq) * wc : ldg(T.dY + (size_t)m * T.ld + col);
-                    zv[u] = ldg(T.Gv + (size_t)m * T.ld + col);
+                    st[u] = ldx2(T.stats, 2 * m);
+                    dv[u] = SYN ? ldx(T.dq + (size_t)m * T.ldq) * wc : ldx(T.dY + (size_t)m * T.ld + col);
+                    zv[u] = ldx(T.Gv + (size_t)m * T.ld + col);
                 }
 #pragma unroll
                 for (int u = 0; u < 16; ++u) {
@@ -2068,7 +2094,7 @@ __device__ __forceinline__ void fql_post_onestep_body(const PostOsArgs& P, float
     const int n = P.B * P.ad;
     for (int e = threadIdx.x; e < n; e += FQL_THREADS) {
         const int b = sdiv(e, frcp(P.ad)), a = e - b * P.ad;
-        const float d = clip1(P.A_os[(size_t)(2 * P.B + b) * P.ap + a]) - P.w_act[(size_t)b * P.ap + a];
+        const float d = clip1(ldx(P.A_os + (size_t)(2 * P.B + b) * P.ap + a)) - ldx(P.w_act + (size_t)b * P.ap + a);
         se += d * d;
     }
     const float tot = block_sum(se, sh);
@@ -2088,10 +2114,10 @@ __device__ __forceinline__ void fql_loss_critic_body(const LossCriticArgs& P, fl
     float sl = 0.f, sq = 0.f, mx = -INFINITY, mn = INFINITY;
     const float gs = 1.0f / (float)P.B;  // d/dq of mean over 2B of (q-y)^2 = 2 (q-y) / (2B)
     for (int b = threadIdx.x; b < P.B; b += FQL_THREADS) {
-        const float ta = P.tqa[(size_t)b * 16], tb = P.tqb[(size_t)b * 16];
+        const float ta = ldx(P.tqa + (size_t)b * 16), tb = ldx(P.tqb + (size_t)b * 16);
         const float nq = P.q_agg ? fminf(ta, tb) : 0.5f * (ta + tb);
-        const float y = P.w_rew[b] + P.discount * P.w_mask[b] * nq;
-        const float qa = P.q1a[(size_t)b * 16], qb = P.q1b[(size_t)b * 16];
+        const float y = ldx(P.w_rew + b) + P.discount * ldx(P.w_mask + b) * nq;
+        const float qa = ldx(P.q1a + (size_t)b * 16), qb = ldx(P.q1b + (size_t)b * 16);
         const float da = qa - y, db = qb - y;
         sl += da * da + db * db;
         sq += qa + qb;
@@ -2123,7 +2149,7 @@ struct LossQArgs {
 __device__ __forceinline__ void fql_loss_q_body(const LossQArgs& P, float* sh) {
     float s = 0.f, sa = 0.f;
     for (int b = threadIdx.x; b < P.B; b += FQL_THREADS) {
-        const float q = 0.5f * (P.q2a[(size_t)b * 16] + P.q2b[(size_t)b * 16]);
+        const float q = 0.5f * (ldx(P.q2a + (size_t)b * 16) + ldx(P.q2b + (size_t)b * 16));
         s += q; sa += fabsf(q);
     }
     const float ts = block_sum(s, sh), tsa = block_sum(sa, sh);
@@ -2156,7 +2182,7 @@ __device__ __forceinline__ void fql_loss_bc_body(const LossBcArgs& P, float* sh)
     float s = 0.f;
     for (int e = threadIdx.x; e < n; e += FQL_THREADS) {
         const int b = sdiv(e, frcp(P.ad)), a = e - b * P.ad;
-        const float d = P.pred[(size_t)b * P.ap + a] - P.vel[(size_t)b * P.ap + a];
+        const float d = ldx(P.pred + (size_t)b * P.ap + a) - ldx(P.vel + (size_t)b * P.ap + a);
         s += d * d;
         if (P.want_grad) P.dpred[(size_t)b * P.ap + a] = gs * d;
     }
@@ -2180,14 +2206,14 @@ __device__ __forceinline__ void fql_loss_actor_body(const LossActorArgs& P, floa
     float s = 0.f;
     for (int e = threadIdx.x; e < n; e += FQL_THREADS) {
         const int b = sdiv(e, frcp(P.ad)), a = e - b * P.ad;
-        const float ar = P.a_raw[(size_t)b * P.ap + a];
-        const float d = ar - P.tgt[(size_t)b * P.ap + a];
+        const float ar = ldx(P.a_raw + (size_t)b * P.ap + a);
+        const float d = ar - ldx(P.tgt + (size_t)b * P.ap + a);
         s += d * d;
         if (P.want_grad) {
             float g = gs * d;
             if (ar > -1.0f && ar < 1.0f) {
                 const size_t o = (size_t)b * P.inp_c + P.od + a;
-                g += P.dxa[o] + P.dxb[o];
+                g += ldx(P.dxa + o) + ldx(P.dxb + o);
             }
             P.da[(size_t)b * P.ap + a] = g;
         }
@@ -2196,7 +2222,7 @@ __device__ __forceinline__ void fql_loss_actor_body(const LossActorArgs& P, floa
     if (threadIdx.x == 0) {
         const float distill = t / (float)n;
         P.st->info[6] = distill;
-        P.st->info[4] = P.st->info[5] + P.alpha * distill + P.st->info[7];
+        P.st->info[4] = ldx(&P.st->info[5]) + P.alpha * distill + ldx(&P.st->info[7]);   // (the BC and Q loss tasks of this update wrote them)
     }
 }
 
@@ -2334,7 +2360,7 @@ __device__ __forceinline__ void fql_adam_body(const AdamArgs& A) {
         const int i = threadIdx.x + it * FQL_THREADS;
         if (i < n4) {
             const int o = ch.off + 4 * i;
-            f32x4 g = ldg4(A.G + o);
+            f32x4 g = ldx4(A.G, (unsigned)o);   // the gradient arena: written by this update
             const f32x4 p = ldg4(A.P + o);
             f32x4 m = ldg4(A.Mu + o);
             f32x4 v = ldg4(A.Nu + o);
@@ -2342,10 +2368,12 @@ __device__ __forceinline__ void fql_adam_body(const AdamArgs& A) {
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 const float ge = g[e] * gsc;
-                m[e] = 0.9f * m[e] + 0.1f * ge;
-                v[e] = 0.999f * v[e] + 0.001f * ge * ge;
+                // (the fused multiply-adds are spelled out: which product of a sum of two the compiler fuses is its choice, and it chose
+                // differently for the second moment once the gradient arrived through another kind of load - a last-bit change of every update)
+                m[e] = __builtin_fmaf(ge, 0.1f, 0.9f * m[e]);
+                v[e] = __builtin_fmaf(ge, 0.001f * ge, 0.999f * v[e]);
                 const float mh = m[e] / c1, vh = v[e] / c2;
-                pn[e] = p[e] - A.lr * (mh / (sqrtf(vh) + 1e-8f));
+                pn[e] = __builtin_fmaf(-A.lr, mh / (sqrtf(vh) + 1e-8f), p[e]);
                 ss += ge * ge; mx = fmaxf(mx, ge); mn = fminf(mn, ge);
             }
             stg4(A.Mu + o, m);
@@ -2354,7 +2382,7 @@ __device__ __forceinline__ void fql_adam_body(const AdamArgs& A) {
             if (o < A.critic_size) {
                 f32x4 t = ldg4(A.T + o);
 #pragma unroll
-                for (int e = 0; e < 4; ++e) t[e] = p[e] * A.tau + t[e] * (1.0f - A.tau);
+                for (int e = 0; e < 4; ++e) t[e] = __builtin_fmaf(p[e], A.tau, t[e] * (1.0f - A.tau));
                 stg4(A.T + o, t);
             }
         }
@@ -2418,11 +2446,11 @@ __device__ __forceinline__ void fql_euler_finish_body(const EulerFinishArgs& P) 
     const int r = sdiv(e, frcp(P.ad)), j = e - r * P.ad;
     float pv[32];
 #pragma unroll
-    for (int tp = 0; tp < 32; ++tp) pv[tp] = ldg(P.evp + ((size_t)min(tp, P.ntp - 1) * P.M + r) * P.ap + j);
+    for (int tp = 0; tp < 32; ++tp) pv[tp] = ldx(P.evp + ((size_t)min(tp, P.ntp - 1) * P.M + r) * P.ap + j);
     float sum = 0.f;
 #pragma unroll
     for (int tp = 0; tp < 32; ++tp) sum += (tp < P.ntp) ? pv[tp] : 0.f;
-    stg(P.tgt + (size_t)r * P.ap + j, clip1(ldg(P.a_in + (size_t)r * P.a_ld + j) + (sum + ldg(P.eb + j)) * P.scale));
+    stg(P.tgt + (size_t)r * P.ap + j, clip1(ldx(P.a_in + (size_t)r * P.a_ld + j) + (sum + ldg(P.eb + j)) * P.scale));
 }
 __global__ __launch_bounds__(FQL_THREADS) void fql_euler_finish_kernel(EulerFinishArgs P) { fql_euler_finish_body(P); }
 // multi-instance entry point (agent groups): blockIdx.y picks the member, its argument struct comes from a device array
