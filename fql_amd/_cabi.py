@@ -151,6 +151,10 @@ SYMBOLS = {
     'fql_rebrac_total_loss': (_I, [_VP] + _BATCH[:5] + [_VP, _I, C.POINTER(FqlNoise), _I, C.POINTER(_F), C.POINTER(_F), _VP]),
     'fql_rebrac_sample_actions': (_I, [_VP, _VP, _I, _VP, _U64, _F, _VP, _VP]),
     'fql_rebrac_stats': (_I, [_VP, _I, C.POINTER(_I64), C.POINTER(_I64)]),
+    'fql_rebrac_group_create': (_I, [_VP, _I, C.POINTER(_VP)]),
+    'fql_rebrac_group_update_from_dataset': (_I, [_VP, _VP, _I, _I, _VP, _VP]),
+    'fql_rebrac_group_sample_actions': (_I, [_VP, _VP, _I, _VP, _VP, _F, _VP, _VP]),
+    'fql_rebrac_group_stats': (_I, [_VP, C.POINTER(_I64), C.POINTER(_I64), C.POINTER(_I64)]),
     'fql_sac_default_config': (None, [C.POINTER(FqlSacConfig)]),
     'fql_sac_create': (_I, [C.POINTER(FqlConfig), C.POINTER(FqlSacConfig), _U64, C.POINTER(_VP)]),
     'fql_sac_update': (_I, [_VP] + _BATCH + [C.POINTER(FqlNoise), _VP, _VP]),

@@ -839,6 +839,81 @@ class KindAgent(FQLAgent):
         return out
 
 
+def _group_sample_args(members, observations, noises, seed, flow):
+    """The shape rules of a group's fused sampling call (FQLAgentGroup, ReBRACAgentGroup), checked before any library call: observations
+    [K, ..., od] or one shared block without the leading K, noises [K, ..., ad] or None, seed None / one / K.  Returns what the library
+    call takes: (observations _Arg [K, n, od], noises _Arg, seeds array or None, n, out, out pointer, stream)."""
+    K, cfg = len(members), members[0].config
+    od, ad = int(cfg['ob_dims'][0]), int(cfg['action_dim'])
+    is_t = hasattr(observations, 'data_ptr')
+    if not is_t:
+        observations = np.asarray(observations)
+    oshape = tuple(int(d) for d in observations.shape)
+    if not oshape or oshape[-1] != od:
+        raise ValueError(f'observations last dim must be {od}, got {oshape}')
+    zshape = None
+    if noises is not None:
+        if not hasattr(noises, 'data_ptr'):
+            noises = np.asarray(noises)
+        zshape = tuple(int(d) for d in noises.shape)
+    if len(oshape) >= 3:
+        if oshape[0] != K:
+            raise ValueError(f'observations must lead with the {K} members: [{K}, ..., {od}], got {oshape}')
+        shared = False
+    elif zshape is not None:
+        shared = len(zshape) == len(oshape) + 1
+    else:
+        shared = not (len(oshape) == 2 and oshape[0] == K)
+    lead = oshape[:-1] if shared else oshape[1:-1]
+    if zshape is not None and zshape != (K,) + lead + (ad,):
+        raise ValueError(f'noises must be {(K,) + lead + (ad,)} for observations {oshape}, got {zshape}')
+    n = int(np.prod(lead)) if lead else 1
+    if n < 1:
+        raise ValueError(f'observations hold no rows: {oshape}')
+    seeds = None
+    if not flow and noises is None:
+        if seed is None or np.ndim(seed) == 0:
+            vals = [m._sample_seed(seed, None) for m in members]
+        else:
+            if len(seed) != K:
+                raise ValueError(f'{K} members but {len(seed)} seeds')
+            vals = [m._sample_seed(s, None) for m, s in zip(members, seed)]
+        seeds = (C.c_uint64 * K)(*vals)
+    if shared:   # the same rows for every member: broadcast here, the library takes one block per member
+        observations = (observations.unsqueeze(0).expand((K,) + oshape) if is_t else np.broadcast_to(observations, (K,) + oshape))
+    o = _Arg(observations, (K, n, od))
+    z = _Arg(noises, (K, n, ad))
+    out, optr = FQLAgent._actions_out(observations, (K,) + lead + (ad,))
+    return o, z, seeds, n, out, optr, FQLAgent._stream([o, z])
+
+
+def _group_idx_arg(members, idxs, B):
+    """`idxs` [K, B] of a group update (host array or tensor, CUDA tensors on torch's current stream): (keep-alive, pointer, stream).
+    Host rows are range-checked against each member's dataset."""
+    K = len(members)
+    stream = None
+    if hasattr(idxs, 'data_ptr'):
+        keep = idxs.long().contiguous()
+        if tuple(keep.shape) != (K, B):
+            raise ValueError(f'idxs must be [{K}, {B}], got {tuple(keep.shape)}')
+        if keep.is_cuda:
+            h = _torch().cuda.current_stream().cuda_stream
+            stream = h if h else _cabi.FQL_STREAM_LEGACY
+        ip = keep.data_ptr()
+    else:
+        keep = np.ascontiguousarray(idxs, dtype=np.int64)
+        if keep.shape != (K, B):
+            raise ValueError(f'idxs must be [{K}, {B}], got {keep.shape}')
+        ip = keep.ctypes.data
+    if not (hasattr(keep, 'is_cuda') and keep.is_cuda):
+        a = keep.numpy() if hasattr(keep, 'numpy') else keep
+        for i, m in enumerate(members):
+            n = m.dataset_size()[0]
+            if B and (a[i].min() < 0 or a[i].max() >= n):
+                raise ValueError(f'idxs[{i}] out of range: [{int(a[i].min())}, {int(a[i].max())}] for {n} rows')
+    return keep, ip, stream
+
+
 class FQLAgentGroup:
     """K agents of one structure - the same config except `seed` and `alpha` - trained side by side by ONE fused update program
     (include/fql_amd.h, fql_group_*): every launch of the update carries all K members' tasks.  The seed / alpha sweeps the reference
@@ -902,30 +977,12 @@ class FQLAgentGroup:
     def update_from_dataset(self, batch_size=None, idxs=None, want_info=False):
         """One fused update of every member: rows from each member's dataset (`idxs` [K, B] int, host or device, or None = each member's
         device RNG), noise from each member's device RNG.  Returns a list of K LazyInfo (want_info) or None."""
-        K, B = len(self.members), int(batch_size or self.batch_size)
+        B = int(batch_size or self.batch_size)
         if B != self.batch_size:
             raise ValueError(f'batch_size {B}: the members of a group keep the batch size they were grouped with ({self.batch_size})')
         ip, keep, stream = None, None, None
         if idxs is not None:
-            if hasattr(idxs, 'data_ptr'):
-                keep = idxs.long().contiguous()
-                if tuple(keep.shape) != (K, B):
-                    raise ValueError(f'idxs must be [{K}, {B}], got {tuple(keep.shape)}')
-                if keep.is_cuda:
-                    h = _torch().cuda.current_stream().cuda_stream
-                    stream = h if h else _cabi.FQL_STREAM_LEGACY
-                ip = keep.data_ptr()
-            else:
-                keep = np.ascontiguousarray(idxs, dtype=np.int64)
-                if keep.shape != (K, B):
-                    raise ValueError(f'idxs must be [{K}, {B}], got {keep.shape}')
-                ip = keep.ctypes.data
-            if not (hasattr(keep, 'is_cuda') and keep.is_cuda):
-                a = keep.numpy() if hasattr(keep, 'numpy') else keep
-                for i, m in enumerate(self.members):
-                    n = m.dataset_size()[0]
-                    if B and (a[i].min() < 0 or a[i].max() >= n):
-                        raise ValueError(f'idxs[{i}] out of range: [{int(a[i].min())}, {int(a[i].max())}] for {n} rows')
+            keep, ip, stream = _group_idx_arg(self.members, idxs, B)
         self._check(self._lib.fql_group_update_from_dataset(self._g, ip, B, None, stream))
         self._keep = keep
         return [m._lazy_info(None) for m in self.members] if want_info else None
@@ -949,48 +1006,7 @@ class FQLAgentGroup:
         return self._eval(observations, noises, None, flow=True)
 
     def _eval(self, observations, noises, seed, flow):
-        K, cfg = len(self.members), self.members[0].config
-        od, ad = int(cfg['ob_dims'][0]), int(cfg['action_dim'])
-        is_t = hasattr(observations, 'data_ptr')
-        if not is_t:
-            observations = np.asarray(observations)
-        oshape = tuple(int(d) for d in observations.shape)
-        if not oshape or oshape[-1] != od:
-            raise ValueError(f'observations last dim must be {od}, got {oshape}')
-        zshape = None
-        if noises is not None:
-            if not hasattr(noises, 'data_ptr'):
-                noises = np.asarray(noises)
-            zshape = tuple(int(d) for d in noises.shape)
-        if len(oshape) >= 3:
-            if oshape[0] != K:
-                raise ValueError(f'observations must lead with the {K} members: [{K}, ..., {od}], got {oshape}')
-            shared = False
-        elif zshape is not None:
-            shared = len(zshape) == len(oshape) + 1
-        else:
-            shared = not (len(oshape) == 2 and oshape[0] == K)
-        lead = oshape[:-1] if shared else oshape[1:-1]
-        if zshape is not None and zshape != (K,) + lead + (ad,):
-            raise ValueError(f'noises must be {(K,) + lead + (ad,)} for observations {oshape}, got {zshape}')
-        n = int(np.prod(lead)) if lead else 1
-        if n < 1:
-            raise ValueError(f'observations hold no rows: {oshape}')
-        seeds = None
-        if not flow and noises is None:
-            if seed is None or np.ndim(seed) == 0:
-                vals = [m._sample_seed(seed, None) for m in self.members]
-            else:
-                if len(seed) != K:
-                    raise ValueError(f'{K} members but {len(seed)} seeds')
-                vals = [m._sample_seed(s, None) for m, s in zip(self.members, seed)]
-            seeds = (C.c_uint64 * K)(*vals)
-        if shared:   # the same rows for every member: broadcast here, the library takes one block per member
-            observations = (observations.unsqueeze(0).expand((K,) + oshape) if is_t else np.broadcast_to(observations, (K,) + oshape))
-        o = _Arg(observations, (K, n, od))
-        z = _Arg(noises, (K, n, ad))
-        out, optr = FQLAgent._actions_out(observations, (K,) + lead + (ad,))
-        stream = FQLAgent._stream([o, z])
+        o, z, seeds, n, out, optr, stream = _group_sample_args(self.members, observations, noises, seed, flow)
         if flow:
             self._check(self._lib.fql_group_flow_actions(self._g, o.ptr, z.ptr, n, optr, stream))
         else:

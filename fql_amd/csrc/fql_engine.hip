@@ -6376,20 +6376,23 @@ int fql_update_from_frames(fql_handle h, const int64_t* idx, const int32_t* crop
 // kernel's multi-instance entry point with blockIdx.y = member, reading the member's argument struct from a device array.  Every task keeps
 // the tile shape and arguments its member's program gave it, so each member computes exactly what it computes alone.
 // The members' sampling programs are zipped the same way (fql_group_s::Sample): one fused sample_actions / flow_actions call for all K.
+// A group has a kind: FQL members (fql_group_create), or ReBRAC members (fql_rebrac_group_create), whose group
+// holds a second fused program, the zip of the members' critic-only step, and a sampler that ends in ReBRAC's action kernel.
 // ================================================================================================
 namespace {
 
 typedef Bound (*MultiBind)(Geo g, const void* args);   // the multi-instance kernel bound over a device array of argument structs
 struct MultiEntry {
     MultiBind bind;
-    size_t arg_bytes;
+    size_t arg_bytes;   // what the single-instance launch binds (Bound::args)
+    size_t stride;      // the element of the multi-instance kernel's array: those bytes, padded to the struct's size
 };
 // single-instance kernel -> its multi-instance entry point
 const std::map<const void*, MultiEntry>& multi_entries() {
     static const std::map<const void*, MultiEntry> m = [] {
         std::map<const void*, MultiEntry> e;
 #define FQL_MULTI(single, multi, A) \
-    e[(const void*)(single)] = MultiEntry{[](Geo g, const void* a) { return bind(multi, g, (const A*)a); }, sizeof(A)}
+    e[(const void*)(single)] = MultiEntry{[](Geo g, const void* a) { return bind(multi, g, (const A*)a); }, sizeof(A), sizeof(A)}
         FQL_MULTI(fql_prep_kernel, fql_prep_multi_kernel, PrepArgs);
         FQL_MULTI(fql_loss_actor_kernel, fql_loss_actor_multi_kernel, LossActorArgs);
         FQL_MULTI(fql_euler_finish_kernel, fql_euler_finish_multi_kernel, EulerFinishArgs);
@@ -6405,6 +6408,15 @@ const std::map<const void*, MultiEntry>& multi_entries() {
         FQL_MULTI((fql_chain_kernel<256, 1>), (fql_chain_multi_kernel<256, 1>), ChainArgs);
         FQL_MULTI((fql_chain_kernel<256, 2>), (fql_chain_multi_kernel<256, 2>), ChainArgs);
         FQL_MULTI((fql_chain_kernel<256, 3>), (fql_chain_multi_kernel<256, 3>), ChainArgs);
+        // ReBRAC (fql_rebrac.h)
+        FQL_MULTI(fql_rebrac_prep_kernel, fql_rebrac_prep_multi_kernel, RebracPrepArgs);
+        FQL_MULTI(fql_rebrac_act_kernel, fql_rebrac_act_multi_kernel, RebracActArgs);
+        FQL_MULTI(fql_rebrac_loss_critic_kernel, fql_rebrac_loss_critic_multi_kernel, RebracCriticArgs);
+        FQL_MULTI(fql_rebrac_loss_actor_kernel, fql_rebrac_loss_actor_multi_kernel, RebracActorArgs);
+        FQL_MULTI(fql_rebrac_actor_grad_kernel, fql_rebrac_actor_grad_multi_kernel, RebracActorGradArgs);
+        // (FinalizeArgs, int full): the launch binds the two arguments packed, the array element is the struct that holds both
+        FQL_MULTI(fql_rebrac_finalize_kernel, fql_rebrac_finalize_multi_kernel, RebracFinalizeArgs);
+        e[(const void*)fql_rebrac_finalize_kernel].arg_bytes = packed_bytes<FinalizeArgs, int>();
 #undef FQL_MULTI
         return e;
     }();
@@ -6423,18 +6435,24 @@ struct GLaunch {
     // multi-instance entry point, grid y = member, over the [K] argument structs in device memory
     Bound k;
 };
+// one fused update program: the zip of one program of every member, captured as one graph (what issue_lanes needs of a launch list)
+struct GProgram {
+    std::vector<GLaunch> launches;
+    bool lane_used[FQL_LANES] = {};
+    hipEvent_t ev_fork = nullptr, ev_join[FQL_LANES] = {};
+    hipGraph_t graph = nullptr;
+    hipGraphExec_t exec = nullptr;
+};
 
 }  // namespace
 
 struct fql_group_s {
     std::vector<fql_handle> m;
+    AgentKind kind = AgentKind::FQL;     // the members' kind: FQL (fql_group_create) or ReBRAC (fql_rebrac_group_create)
     int K = 0, B = 0;
     hipStream_t lanes[FQL_LANES] = {};   // lane 0 = the group's own stream
-    std::vector<GLaunch> launches;
-    bool lane_used[FQL_LANES] = {};
-    hipEvent_t ev_fork = nullptr, ev_join[FQL_LANES] = {}, ev_in = nullptr, ev_done = nullptr;
-    hipGraph_t graph = nullptr;
-    hipGraphExec_t exec = nullptr;
+    GProgram full, critic;               // the members' prog_full zipped; a ReBRAC group's second program: their prog_critic zipped
+    hipEvent_t ev_in = nullptr, ev_done = nullptr;
     std::vector<void*> allocs;
     int64_t* d_idx = nullptr;   // [K][B] staging of host row indices
     hipStream_t last = nullptr; // the stream of the last group call (update or sampling): a call on another stream waits for that one first
@@ -6520,6 +6538,7 @@ struct fql_group_s {
             alignas(16) unsigned char a[FQL_BOUND_BYTES];
             m[k]->issue_args(L, m[k]->tl_of(prog(*m[k]), L), a);
             args.insert(args.end(), a, a + L.k.args.size());
+            args.resize((size_t)(k + 1) * it->second.stride, 0);
         }
         G.k = it->second.bind(Geo(dim3(k0.grid[0], K), dim3(k0.block[0], k0.block[1], k0.block[2]), k0.lds), upload(args.data(), args.size()));
         return G;
@@ -6552,8 +6571,9 @@ struct fql_group_s {
         int n_pad = 0;
         std::vector<GLaunch> os, flow;
         float *st_obs = nullptr, *st_noise = nullptr, *st_out = nullptr;
-        unsigned char* d_args = nullptr;   // [K] AssembleArgs, then [K] ExtractArgs
+        unsigned char* d_args = nullptr;   // [K] AssembleArgs, then [K] ExtractArgs (a ReBRAC group: [K] RebracActArgs)
         Bound assemble, extract;           // the multi-instance launches over d_args, blockIdx.y = member
+        Bound act;                         // a ReBRAC group: fql_rebrac_act_multi_kernel writes the actions, no extract launch
     };
     std::map<int, std::unique_ptr<Sample>> samples;
     // The chunks' argument structs travel through a ring of pinned host slots (the copy reads the slot when the stream reaches it): a
@@ -6564,7 +6584,8 @@ struct fql_group_s {
     hipEvent_t arg_ev[kArgRing] = {};
     char arg_state[kArgRing] = {};   // 0 = free, 1 = behind arg_ev, 2 = on the legacy stream
     int arg_pos = 0;
-    size_t arg_bytes() const { return (size_t)K * (sizeof(AssembleArgs) + sizeof(ExtractArgs)); }
+    // (a slot holds either layout: [K] AssembleArgs + [K] ExtractArgs, or [K] AssembleArgs + [K] RebracActArgs)
+    size_t arg_bytes() const { return (size_t)K * (sizeof(AssembleArgs) + std::max(sizeof(ExtractArgs), sizeof(RebracActArgs))); }
 
     Sample& sample_ws(int n_pad, bool flow) {
         std::unique_ptr<Sample>& slot = samples[n_pad];
@@ -6578,8 +6599,12 @@ struct fql_group_s {
             w->st_out = (float*)galloc((size_t)K * n_pad * ad * sizeof(float));
             w->d_args = (unsigned char*)galloc(arg_bytes());
             w->assemble = bind(fql_assemble_multi_kernel, Geo(dim3((n_pad + 3) / 4, K), dim3(FQL_THREADS), 0), (const AssembleArgs*)w->d_args);
-            w->extract = bind(fql_extract_multi_kernel, Geo(dim3((n_pad * ad + 255) / 256, K), dim3(256), 0),
-                              (const ExtractArgs*)(w->d_args + (size_t)K * sizeof(AssembleArgs)));
+            if (kind != AgentKind::REBRAC)
+                w->extract = bind(fql_extract_multi_kernel, Geo(dim3((n_pad * ad + 255) / 256, K), dim3(256), 0),
+                                  (const ExtractArgs*)(w->d_args + (size_t)K * sizeof(AssembleArgs)));
+            else
+                w->act = bind(fql_rebrac_act_multi_kernel, Geo(dim3((n_pad * ad + FQL_THREADS - 1) / FQL_THREADS, K), dim3(FQL_THREADS), 0),
+                          (const RebracActArgs*)(w->d_args + (size_t)K * sizeof(AssembleArgs)));
             slot = std::move(w);
         }
         if (flow && slot->flow.empty())
@@ -6622,8 +6647,11 @@ struct fql_group_s {
     // that a seeded draw is keyed as fql_engine::eval_rows keys it, (member's key, seed_i + start) - assemble-multi, the zipped launches of
     // the members' program, extract-multi, as direct launches on s.  observations [K, n, od], noise [K, n, ad] or null, out [K, n, ad]:
     // host or device each.  A host result is copied out and waited for per chunk.
-    void sample(bool flow, const float* obs, const float* noise, const uint64_t* seeds, int n, float* out, hipStream_t s) {
+    // A ReBRAC group (fql_rebrac_group_sample_actions): assemble-multi of [obs | 0], the zipped launches of the actor's forward, then
+    // fql_rebrac_act_multi_kernel, which writes the actions where extract-multi would - every argument as fql_engine::sample_actor fills it.
+    void sample(bool flow, const float* obs, const float* noise, const uint64_t* seeds, float temperature, int n, float* out, hipStream_t s) {
         const int od = m[0]->cfg.obs_dim, ad = m[0]->cfg.act_dim, ap = pad16(ad);
+        const bool rebrac = kind == AgentKind::REBRAC;
         const bool dev_obs = fql_engine::is_device_ptr(obs), dev_z = noise && fql_engine::is_device_ptr(noise), dev_out = fql_engine::is_device_ptr(out);
         for (int start = 0; start < n; start += 4096) {
             const int mm = std::min(4096, n - start);
@@ -6633,9 +6661,19 @@ struct fql_group_s {
             unsigned char* slot = arg_slot();
             AssembleArgs* aa = (AssembleArgs*)slot;
             ExtractArgs* ea = (ExtractArgs*)(slot + (size_t)K * sizeof(AssembleArgs));
+            RebracActArgs* ra = (RebracActArgs*)(slot + (size_t)K * sizeof(AssembleArgs));
             for (int i = 0; i < K; ++i) {
                 fql_engine& e = *m[i];
                 fql_engine::Eval& ev = e.get_eval(w.n_pad);
+                if (rebrac) {
+                    const uint64_t sd = seeds ? seeds[i] : 0;
+                    const float* zi = z.p ? z.p + i * z.stride : nullptr;
+                    float* dst = dev_out ? out + ((size_t)i * n + start) * ad : w.st_out + (size_t)i * mm * ad;
+                    aa[i] = AssembleArgs{o.p + i * o.stride, nullptr, ev.X, e.seed, sd, mm, w.n_pad, od, 0, e.nets[NET_BC].in_p()};   // [obs | 0]
+                    ra[i] = RebracActArgs{ev.p_os.out, zi, dst, e.seed, sd, mm, ad, ap, ad, ad, 0, start, zi ? 1 : 2, e.rcfg.tanh_squash, 1,
+                                          e.rcfg.actor_noise * temperature, e.rcfg.actor_noise_clip};
+                    continue;
+                }
                 aa[i] = AssembleArgs{o.p + i * o.stride, z.p ? z.p + i * z.stride : nullptr, flow ? ev.Xf : ev.X, e.seed,
                                      (seeds ? seeds[i] : 0) + (uint64_t)start, mm, w.n_pad, od, ad, flow ? e.nets[NET_BC].in_p() : e.nets[NET_OS].in_p()};
                 ea[i] = ExtractArgs{flow ? ev.tgt : ev.p_os.out, dev_out ? out + ((size_t)i * n + start) * ad : w.st_out + (size_t)i * mm * ad, mm, ad, ap};
@@ -6646,7 +6684,8 @@ struct fql_group_s {
             if (!dev_obs || (noise && !dev_z)) HIP_CHECK(hipStreamSynchronize(s));   // (host rows are borrowed for the call only)
             launch_bound(w.assemble, w.assemble.args.data(), s);
             for (GLaunch& G : flow ? w.flow : w.os) launch_bound(G.k, G.k.args.data(), s);
-            launch_bound(w.extract, w.extract.args.data(), s);
+            const Bound& fin = rebrac ? w.act : w.extract;
+            launch_bound(fin, fin.args.data(), s);
             HIP_CHECK(hipGetLastError());
             if (!dev_out) {
                 copy_rows(out + (size_t)start * ad, (size_t)n * ad, w.st_out, (size_t)mm * ad, (size_t)mm * ad, hipMemcpyDeviceToHost, s);
@@ -6686,8 +6725,8 @@ struct fql_group_s {
     }
 
     // the fused program as ONE graph with the lanes, forks, joins and cross-lane events of a member's own
-    void capture() {
-        capture_graph(lanes[0], [&] { issue_lanes(*this, lanes[0], lanes, true, [&](GLaunch& G, hipStream_t s) { launch_bound(G.k, G.k.args.data(), s); }); }, graph, exec);
+    void capture(GProgram& p) {
+        capture_graph(lanes[0], [&] { issue_lanes(p, lanes[0], lanes, true, [&](GLaunch& G, hipStream_t s) { launch_bound(G.k, G.k.args.data(), s); }); }, p.graph, p.exec);
     }
 
     void release() {
@@ -6695,9 +6734,11 @@ struct fql_group_s {
         if (last == hipStreamLegacy) hipDeviceSynchronize();
         if (ev_done) hipEventSynchronize(ev_done);
         for (fql_handle h : m) { h->group = nullptr; h->grp_pending = h->grp_legacy = false; h->grp_done = nullptr; h->grp_touched = true; }
-        if (exec) hipGraphExecDestroy(exec);
-        if (graph) hipGraphDestroy(graph);
-        destroy_lane_events(*this);
+        for (GProgram* p : {&full, &critic}) {
+            if (p->exec) hipGraphExecDestroy(p->exec);
+            if (p->graph) hipGraphDestroy(p->graph);
+            destroy_lane_events(*p);
+        }
         for (hipEvent_t e : {ev_in, ev_done}) if (e) hipEventDestroy(e);
         for (hipEvent_t e : arg_ev) if (e) hipEventDestroy(e);
         if (h_args) hipHostFree(h_args);
@@ -6708,71 +6749,90 @@ struct fql_group_s {
 };
 
 namespace {
-// the members' restrictions and the structural identity of their programs (fql_group_create)
-void group_check(const fql_handle* members, int k) {
-    if (!members || k <= 0) invalid("fql_group_create: members must be a non-empty array (k = %d)", k);
+// The update programs a group of `kind` fuses: every kind's prog_full, and ReBRAC's prog_critic (the critic-only step) behind it
+std::vector<Program fql_engine::*> group_programs(AgentKind kind) {
+    std::vector<Program fql_engine::*> p{&fql_engine::prog_full};
+    if (kind == AgentKind::REBRAC) p.push_back(&fql_engine::prog_critic);
+    return p;
+}
+// the members' restrictions and the structural identity of their programs (fql_group_create, fql_rebrac_group_create: `fn`).  What may
+// differ between members beside the create seed: FQL's alpha; ReBRAC's alpha_actor and alpha_critic - kernel arguments, not structure.
+void group_check(const char* fn, AgentKind kind, const fql_handle* members, int k) {
+    if (!members || k <= 0) invalid("%s: members must be a non-empty array (k = %d)", fn, k);
     for (int i = 0; i < k; ++i) {
         fql_handle h = members[i];
-        if (!h) invalid("fql_group_create: member %d is NULL", i);
-        for (int j = 0; j < i; ++j) if (members[j] == h) invalid("fql_group_create: member %d appears twice", i);
-        if (h->group) invalid("fql_group_create: member %d already belongs to a group", i);
-        if (h->visual) invalid("fql_group_create: member %d has an encoder (groups take state agents only)", i);
-        if (h->cfg.precision != 0) invalid("fql_group_create: member %d has precision %d (groups take fp32 members only)", i, h->cfg.precision);
-        if (h->began) invalid("fql_group_create: member %d is between fql_update_begin and fql_update_end", i);
-        require_graph(h->prog_full);
+        if (!h) invalid("%s: member %d is NULL", fn, i);
+        for (int j = 0; j < i; ++j) if (members[j] == h) invalid("%s: member %d appears twice", fn, i);
+        if (h->group) invalid("%s: member %d already belongs to a group", fn, i);
+        if (h->visual) invalid("%s: member %d has an encoder (groups take state agents only)", fn, i);
+        if (h->cfg.precision != 0) invalid("%s: member %d has precision %d (groups take fp32 members only)", fn, i, h->cfg.precision);
+        if (h->began) invalid("%s: member %d is between fql_update_begin and fql_update_end", fn, i);
         fql_config a = h->cfg, b = members[0]->cfg;
-        a.alpha = b.alpha = 0.f;
+        if (kind == AgentKind::FQL) a.alpha = b.alpha = 0.f;
         a.batch_size = b.batch_size = 0;
-        if (std::memcmp(&a, &b, sizeof a) != 0)
-            invalid("fql_group_create: member %d's config differs from member 0's in more than seed and alpha", i);
-        if (h->B != members[0]->B) invalid("fql_group_create: member %d has batch size %d, member 0 has %d", i, h->B, members[0]->B);
-        const Program& p = h->prog_full, &p0 = members[0]->prog_full;
-        if (p.launches.size() != p0.launches.size()) invalid("fql_group_create: member %d's update has %zu launches, member 0's %zu", i, p.launches.size(), p0.launches.size());
-        for (size_t li = 0; li < p.launches.size(); ++li) {
-            const Launch &L = p.launches[li], &L0 = p0.launches[li];
-            if (L.type != L0.type || L.lane != L0.lane || L.grid != L0.grid || L.waits != L0.waits || L.record_after != L0.record_after)
-                invalid("fql_group_create: launch %zu of member %d differs from member 0's (type %d/%d, lane %d/%d, grid %d/%d)", li, i, (int)L.type,
-                        (int)L0.type, L.lane, L0.lane, L.grid, L0.grid);
-            if (L.type == OP_WFRAG && h->wfrag_grid != members[0]->wfrag_grid) invalid("fql_group_create: member %d's weight-copy launch differs", i);
+        bool same = std::memcmp(&a, &b, sizeof a) == 0;
+        if (kind == AgentKind::REBRAC) {
+            fql_rebrac_config ra = h->rcfg, rb = members[0]->rcfg;
+            ra.alpha_actor = rb.alpha_actor = ra.alpha_critic = rb.alpha_critic = 0.f;
+            same = same && std::memcmp(&ra, &rb, sizeof ra) == 0;
+        }
+        if (!same)
+            invalid("%s: member %d's config differs from member 0's in more than seed and %s", fn, i, kind == AgentKind::REBRAC ? "alpha_actor / alpha_critic" : "alpha");
+        if (h->B != members[0]->B) invalid("%s: member %d has batch size %d, member 0 has %d", fn, i, h->B, members[0]->B);
+        for (Program fql_engine::* pp : group_programs(kind)) {
+            const Program& p = h->*pp, &p0 = members[0]->*pp;
+            require_graph(p);
+            if (p.launches.size() != p0.launches.size()) invalid("%s: member %d's update has %zu launches, member 0's %zu", fn, i, p.launches.size(), p0.launches.size());
+            for (size_t li = 0; li < p.launches.size(); ++li) {
+                const Launch &L = p.launches[li], &L0 = p0.launches[li];
+                if (L.type != L0.type || L.lane != L0.lane || L.grid != L0.grid || L.waits != L0.waits || L.record_after != L0.record_after)
+                    invalid("%s: launch %zu of member %d differs from member 0's (type %d/%d, lane %d/%d, grid %d/%d)", fn, li, i, (int)L.type,
+                            (int)L0.type, L.lane, L0.lane, L.grid, L0.grid);
+                if (L.type == OP_WFRAG && h->wfrag_grid != members[0]->wfrag_grid) invalid("%s: member %d's weight-copy launch differs", fn, i);
+            }
         }
     }
 }
-}  // namespace
 
-extern "C" {
-
-int fql_group_create(const fql_handle* members, int k, fql_group* out) {
-    if (!out) { g_create_error = "fql_group_create: out must not be NULL"; return FQL_E_INVALID; }
+// fql_group_create / fql_rebrac_group_create: a group of `kind` members, `want` what the refusal of another kind says the call takes
+int group_create(const char* fn, AgentKind kind, const char* want, const fql_handle* members, int k, fql_group* out) {
+    if (!out) { g_create_error = std::string(fn) + ": out must not be NULL"; return FQL_E_INVALID; }
     *out = nullptr;
     for (int i = 0; members && i < k; ++i)
-        if (members[i] && members[i]->kind != AgentKind::FQL) {
-            g_create_error = "fql_group_create: member " + std::to_string(i) + " is " + members[i]->desc().label + " (groups take FQL agents only)";
+        if (members[i] && members[i]->kind != kind) {
+            g_create_error = std::string(fn) + ": member " + std::to_string(i) + " is " + members[i]->desc().label + " (" + want + ")";
             return FQL_E_STATE;
         }
     auto* g = new fql_group_s();
     try {
-        group_check(members, k);
+        group_check(fn, kind, members, k);
         g->m.assign(members, members + k);
+        g->kind = kind;
         g->K = k;
         g->B = members[0]->B;
         for (fql_handle h : g->m) { h->aql_drain(); HIP_CHECK(hipStreamSynchronize(h->stream)); }
-        const size_t n = g->m[0]->prog_full.launches.size();
-        for (size_t li = 0; li < n; ++li)
-            for (int i = 1; i < k; ++i) {
-                const Bound &a = g->m[i]->prog_full.launches[li].k, &b = g->m[0]->prog_full.launches[li].k;
-                if (a.fn != b.fn || std::memcmp(a.grid, b.grid, sizeof a.grid) || std::memcmp(a.block, b.block, sizeof a.block) || a.lds != b.lds)
-                    invalid("fql_group_create: launch %zu of member %d runs another kernel or shape than member 0's", li, i);
+        auto fuse_program = [&](GProgram& gp, Program fql_engine::* pp) {
+            const size_t n = (g->m[0]->*pp).launches.size();
+            for (size_t li = 0; li < n; ++li)
+                for (int i = 1; i < k; ++i) {
+                    const Bound &a = (g->m[i]->*pp).launches[li].k, &b = (g->m[0]->*pp).launches[li].k;
+                    if (a.fn != b.fn || std::memcmp(a.grid, b.grid, sizeof a.grid) || std::memcmp(a.block, b.block, sizeof a.block) || a.lds != b.lds)
+                        invalid("%s: launch %zu of member %d runs another kernel or shape than member 0's", fn, li, i);
+                }
+            for (size_t li = 0; li < n; ++li) {
+                const Bound& k0 = (g->m[0]->*pp).launches[li].k;
+                if (k0.grid[1] != 1 || k0.grid[2] != 1) invalid("%s: launch %zu has a 2-D grid: not groupable", fn, li);
+                gp.launches.push_back(g->zip((int)li, [pp](fql_engine& e) -> Program& { return e.*pp; }));
+                gp.lane_used[gp.launches.back().lane] = true;
             }
-        for (size_t li = 0; li < n; ++li) {
-            const Bound& k0 = g->m[0]->prog_full.launches[li].k;
-            if (k0.grid[1] != 1 || k0.grid[2] != 1) invalid("fql_group_create: launch %zu has a 2-D grid: not groupable", li);
-            g->launches.push_back(g->zip((int)li, [](fql_engine& e) -> Program& { return e.prog_full; }));
-            g->lane_used[g->launches.back().lane] = true;
-        }
+        };
+        GProgram* const fused[] = {&g->full, &g->critic};
+        const std::vector<Program fql_engine::*> progs = group_programs(kind);
+        for (size_t p = 0; p < progs.size(); ++p) fuse_program(*fused[p], progs[p]);
         for (int l = 0; l < FQL_LANES; ++l) HIP_CHECK(hipStreamCreateWithFlags(&g->lanes[l], hipStreamNonBlocking));
         for (hipEvent_t* e : {&g->ev_in, &g->ev_done}) HIP_CHECK(hipEventCreateWithFlags(e, hipEventDisableTiming));
         HIP_CHECK(hipMalloc((void**)&g->d_idx, (size_t)k * g->B * sizeof(int64_t)));
-        g->capture();
+        for (size_t p = 0; p < progs.size(); ++p) g->capture(*fused[p]);
     } catch (const Invalid& e) {
         g_create_error = e.msg; g->release(); delete g; return FQL_E_INVALID;
     } catch (const HipError& e) {
@@ -6781,6 +6841,49 @@ int fql_group_create(const fql_handle* members, int k, fql_group* out) {
     for (fql_handle h : g->m) { h->group = g; h->grp_done = g->ev_done; h->grp_pending = false; h->grp_touched = true; }
     *out = g;
     return FQL_OK;
+}
+
+// One fused update of every member: `gp` is the group's program for the step's kind.  fn: the entry point, for its messages.
+int group_update(fql_group g, const char* fn, GProgram& gp, const int64_t* idx, int batch_size, float* info13xk, void* stream) {
+    try {
+        if (batch_size != g->B) invalid("%s: batch_size %d does not match the members' %d", fn, batch_size, g->B);
+        if (g->member_began()) { g_create_error = std::string(fn) + ": a member is between fql_update_begin and fql_update_end"; return FQL_E_STATE; }
+        const hipStream_t s = g->enter(stream);
+        const int64_t* rows = idx;
+        if (idx && !fql_engine::is_device_ptr(idx)) {
+            HIP_CHECK(hipMemcpyAsync(g->d_idx, idx, (size_t)g->K * g->B * sizeof(int64_t), hipMemcpyHostToDevice, s));
+            HIP_CHECK(hipStreamSynchronize(s));   // (host indices are borrowed for the call only)
+            rows = g->d_idx;
+        }
+        for (int i = 0; i < g->K; ++i) g->m[i]->source_from_dataset(rows ? rows + (size_t)i * g->B : nullptr, g->B, 0, 0, nullptr, s);
+        HIP_CHECK(hipGraphLaunch(gp.exec, s));
+        if (info13xk) {
+            for (int i = 0; i < g->K; ++i)
+                HIP_CHECK(hipMemcpyAsync(info13xk + (size_t)i * FQL_NUM_INFO, &g->m[i]->d_state->info[0], FQL_NUM_INFO * sizeof(float), hipMemcpyDefault, s));
+        }
+        g->leave(s, info13xk && !fql_engine::is_device_ptr(info13xk));
+    } catch (const Invalid& e) {
+        g_create_error = e.msg; return FQL_E_INVALID;
+    } catch (const HipError& e) {
+        g_create_error = e.msg; return FQL_E_HIP;
+    }
+    return FQL_OK;
+}
+// A group call on a group of the other kind: FQL_E_STATE, naming the call that serves it
+bool group_wrong_kind(fql_group g, AgentKind kind, const char* fn, const char* instead) {
+    if (g->kind == kind) return false;
+    g_create_error = std::string(fn) + " is not available on a group of " + g->m[0]->desc().name + " agents (" + instead + ")";
+    return true;
+}
+}  // namespace
+
+extern "C" {
+
+int fql_group_create(const fql_handle* members, int k, fql_group* out) {
+    return group_create("fql_group_create", AgentKind::FQL, "groups take FQL agents only", members, k, out);
+}
+int fql_rebrac_group_create(const fql_handle* members, int k, fql_group* out) {
+    return group_create("fql_rebrac_group_create", AgentKind::REBRAC, "ReBRAC groups take ReBRAC agents only", members, k, out);
 }
 
 // Diagnostic only (not in include/fql_amd.h, beside fql_debug_plan): where each launch of an update program takes its tasks from, as int32 words
@@ -6793,7 +6896,7 @@ int fql_debug_task_forms(fql_handle h, fql_group g, void* out, size_t bytes) {
     if (!g && (h->visual || !h->prog_full.exec || h->prog_full.launches.empty())) return FQL_E_STATE;
     auto form = [](const Launch& L) { return !is_table_launch(L.type) ? 0 : L.ka ? 2 : 1; };
     std::vector<int32_t> w{0, FQL_KA_GEMM, FQL_KA_WGRAD, FQL_KA_LN, FQL_KA_MISC, 0};
-    if (g) for (const GLaunch& G : g->launches) w.push_back(G.form);
+    if (g) for (const GLaunch& G : g->full.launches) w.push_back(G.form);
     else for (const Launch& L : h->prog_full.launches) w.push_back(form(L));
     w[5] = (int32_t)w.size() - 6;
     w[0] = (int32_t)w.size();
@@ -6814,8 +6917,8 @@ int fql_debug_aql_fences(fql_handle h, fql_group g, void* out, size_t bytes) {
     if (!g && (h->visual || !h->prog_full.exec || h->prog_full.launches.empty())) return FQL_E_STATE;
     std::vector<int32_t> w{0, 0, 0, 0};
     if (g) {
-        bool all = !g->launches.empty();
-        for (const GLaunch& G : g->launches) all = all && l1_independent_kernel(G.k.fn);
+        bool all = !g->full.launches.empty();
+        for (const GLaunch& G : g->full.launches) all = all && l1_independent_kernel(G.k.fn);
         w[1] = all;
         w[2] = g->m.empty() ? 0 : (int32_t)g->m[0]->aql_acquire;
     } else {
@@ -6847,43 +6950,33 @@ int fql_group_destroy(fql_group g) {
 }
 
 int fql_group_update_from_dataset(fql_group g, const int64_t* idx, int batch_size, float* info13xk, void* stream) {
-    if (!g) { g_create_error = "fql_group_update_from_dataset: NULL group"; return FQL_E_INVALID; }
-    try {
-        if (batch_size != g->B) invalid("fql_group_update_from_dataset: batch_size %d does not match the members' %d", batch_size, g->B);
-        if (g->member_began()) { g_create_error = "fql_group_update_from_dataset: a member is between fql_update_begin and fql_update_end"; return FQL_E_STATE; }
-        const hipStream_t s = g->enter(stream);
-        const int64_t* rows = idx;
-        if (idx && !fql_engine::is_device_ptr(idx)) {
-            HIP_CHECK(hipMemcpyAsync(g->d_idx, idx, (size_t)g->K * g->B * sizeof(int64_t), hipMemcpyHostToDevice, s));
-            HIP_CHECK(hipStreamSynchronize(s));   // (host indices are borrowed for the call only)
-            rows = g->d_idx;
-        }
-        for (int i = 0; i < g->K; ++i) g->m[i]->source_from_dataset(rows ? rows + (size_t)i * g->B : nullptr, g->B, 0, 0, nullptr, s);
-        HIP_CHECK(hipGraphLaunch(g->exec, s));
-        if (info13xk) {
-            for (int i = 0; i < g->K; ++i)
-                HIP_CHECK(hipMemcpyAsync(info13xk + (size_t)i * FQL_NUM_INFO, &g->m[i]->d_state->info[0], FQL_NUM_INFO * sizeof(float), hipMemcpyDefault, s));
-        }
-        g->leave(s, info13xk && !fql_engine::is_device_ptr(info13xk));
-    } catch (const Invalid& e) {
-        g_create_error = e.msg; return FQL_E_INVALID;
-    } catch (const HipError& e) {
-        g_create_error = e.msg; return FQL_E_HIP;
-    }
-    return FQL_OK;
+    const char* fn = "fql_group_update_from_dataset";
+    if (!g) { g_create_error = std::string(fn) + ": NULL group"; return FQL_E_INVALID; }
+    if (group_wrong_kind(g, AgentKind::FQL, fn, "the step kind is an argument: fql_rebrac_group_update_from_dataset")) return FQL_E_STATE;
+    return group_update(g, fn, g->full, idx, batch_size, info13xk, stream);
+}
+// fql_rebrac_update_from_dataset of every member in one fused update: the zip of their prog_full, or of their prog_critic
+int fql_rebrac_group_update_from_dataset(fql_group g, const int64_t* idx, int batch_size, int full_update, float* info13xk, void* stream) {
+    const char* fn = "fql_rebrac_group_update_from_dataset";
+    if (!g) { g_create_error = std::string(fn) + ": NULL group"; return FQL_E_INVALID; }
+    if (group_wrong_kind(g, AgentKind::REBRAC, fn, "fql_group_update_from_dataset")) return FQL_E_STATE;
+    return group_update(g, fn, full_update ? g->full : g->critic, idx, batch_size, info13xk, stream);
 }
 
 // The members' sample_actions (flow: compute_flow_actions) in one fused call: fql_group_s::sample between the update's ordering rules
-static int group_sample(fql_group g, const char* fn, bool flow, const float* obs, const float* noise, const uint64_t* seeds, int n, float* out, void* stream) {
+static int group_sample(fql_group g, const char* fn, AgentKind kind, const char* instead, bool flow, const float* obs, const float* noise,
+                        const uint64_t* seeds, float temperature, int n, float* out, void* stream) {
     if (!g) { g_create_error = std::string(fn) + ": NULL group"; return FQL_E_INVALID; }
+    if (group_wrong_kind(g, kind, fn, instead)) return FQL_E_STATE;
     try {
         if (n <= 0) invalid("%s: n must be positive (got %d)", fn, n);
         if (!obs || !out) invalid("%s: observations/out must not be NULL", fn);
         if (flow && !noise) invalid("%s: noises must not be NULL", fn);
         if (!noise && !seeds) invalid("%s: seeds must not be NULL when noises is NULL (one seed per member)", fn);
+        if (!(temperature >= 0.0f)) invalid("%s: temperature must be >= 0", fn);
         if (g->member_began()) { g_create_error = std::string(fn) + ": a member is between fql_update_begin and fql_update_end"; return FQL_E_STATE; }
         const hipStream_t s = g->enter(stream);
-        g->sample(flow, obs, noise, seeds, n, out, s);
+        g->sample(flow, obs, noise, seeds, temperature, n, out, s);
         // a device result on the group's own stream: the caller has no handle to order its reads against, so finish here (as a member does)
         g->leave(s, !stream && fql_engine::is_device_ptr(out));
     } catch (const Invalid& e) {
@@ -6896,16 +6989,36 @@ static int group_sample(fql_group g, const char* fn, bool flow, const float* obs
     return FQL_OK;
 }
 int fql_group_sample_actions(fql_group g, const float* observations, int n, const float* noises, const uint64_t* seeds, float* out, void* stream) {
-    return group_sample(g, "fql_group_sample_actions", false, observations, noises, seeds, n, out, stream);
+    return group_sample(g, "fql_group_sample_actions", AgentKind::FQL, "fql_rebrac_group_sample_actions", false, observations, noises, seeds, 1.0f, n, out, stream);
 }
 int fql_group_flow_actions(fql_group g, const float* observations, const float* noises, int n, float* out, void* stream) {
-    return group_sample(g, "fql_group_flow_actions", true, observations, noises, nullptr, n, out, stream);
+    return group_sample(g, "fql_group_flow_actions", AgentKind::FQL, "the actor is deterministic: fql_rebrac_group_sample_actions", true, observations, noises, nullptr, 1.0f, n, out, stream);
+}
+int fql_rebrac_group_sample_actions(fql_group g, const float* observations, int n, const float* noises, const uint64_t* seeds, float temperature,
+                                    float* out, void* stream) {
+    return group_sample(g, "fql_rebrac_group_sample_actions", AgentKind::REBRAC, "fql_group_sample_actions", false, observations, noises, seeds, temperature, n, out, stream);
 }
 int fql_group_sample_stats(fql_group g, int flow, int64_t* launches_per_call) {
     if (!g) { g_create_error = "fql_group_sample_stats: NULL group"; return FQL_E_INVALID; }
+    if (group_wrong_kind(g, AgentKind::FQL, "fql_group_sample_stats", "fql_rebrac_group_stats")) return FQL_E_STATE;
     if (!launches_per_call) { g_create_error = "fql_group_sample_stats: launches_per_call must not be NULL"; return FQL_E_INVALID; }
     try {
         *launches_per_call = g->sample_launches(flow != 0);
+    } catch (const Invalid& e) {
+        g_create_error = e.msg; return FQL_E_INVALID;
+    } catch (const HipError& e) {
+        g_create_error = e.msg; return FQL_E_HIP;
+    }
+    return FQL_OK;
+}
+// Launches of a ReBRAC group's two fused update programs and of one fused sampling call on a single chunk, counted from the built programs
+int fql_rebrac_group_stats(fql_group g, int64_t* launches_full, int64_t* launches_critic, int64_t* launches_sample) {
+    if (!g) { g_create_error = "fql_rebrac_group_stats: NULL group"; return FQL_E_INVALID; }
+    if (group_wrong_kind(g, AgentKind::REBRAC, "fql_rebrac_group_stats", "fql_group_sample_stats")) return FQL_E_STATE;
+    try {
+        if (launches_full) *launches_full = (int64_t)g->full.launches.size();
+        if (launches_critic) *launches_critic = (int64_t)g->critic.launches.size();
+        if (launches_sample) *launches_sample = g->sample_launches(false);
     } catch (const Invalid& e) {
         g_create_error = e.msg; return FQL_E_INVALID;
     } catch (const HipError& e) {

@@ -25,7 +25,7 @@ struct RebracPrepArgs {
 };
 // utils/datasets.py:64-100 (index draw, gather, next_actions = actions[min(idx + 1, size - 1)]), agents/rebrac.py:29-33 (the raw
 // N(0, 1) of the target-policy noise: Philox tensor 1, or fql_noise.eps1).  One wave per transition.
-__global__ __launch_bounds__(FQL_THREADS) void fql_rebrac_prep_kernel(RebracPrepArgs P) {
+__device__ __forceinline__ void fql_rebrac_prep_body(const RebracPrepArgs& P) {
     if (P.gz)
         for (int64_t i = (int64_t)blockIdx.x * FQL_THREADS + threadIdx.x; i < P.gz_n; i += (int64_t)gridDim.x * FQL_THREADS) P.gz[i] = 0.f;
     const SrcDesc& S = *P.src;
@@ -72,6 +72,10 @@ __global__ __launch_bounds__(FQL_THREADS) void fql_rebrac_prep_kernel(RebracPrep
         P.w_mask[b] = S.mask[src];
     }
 }
+__global__ __launch_bounds__(FQL_THREADS) void fql_rebrac_prep_kernel(RebracPrepArgs P) { fql_rebrac_prep_body(P); }
+// Multi-instance entry points (ReBRAC agent groups), here and below: blockIdx.y picks the member, its argument struct comes from a device
+// array, read through the constant address space (scalar loads, as from the kernel-argument segment; fql_kernels.h FQL_CONST_AS)
+__global__ __launch_bounds__(FQL_THREADS) void fql_rebrac_prep_multi_kernel(const RebracPrepArgs* __restrict__ args) { const RebracPrepArgs P = ((const FQL_CONST_AS RebracPrepArgs*)args)[blockIdx.y]; fql_rebrac_prep_body(P); }
 
 struct RebracActArgs {
     const float* mean;     // [n, ap]: mean_net output
@@ -86,7 +90,7 @@ struct RebracActArgs {
 // The deterministic actor's action (utils/networks.py:82-150, const_std): mode = tanh(mean) when squashed; plus clipped noise and the
 // [-1, 1] clip of the target policy (rebrac.py:28-34) and of sample_actions (rebrac.py:144-151); the actor loss's actions (rebrac.py:57-58)
 // take neither.  One thread per element.
-__global__ __launch_bounds__(FQL_THREADS) void fql_rebrac_act_kernel(RebracActArgs P) {
+__device__ __forceinline__ void fql_rebrac_act_body(const RebracActArgs& P) {
     const int e = blockIdx.x * FQL_THREADS + threadIdx.x;
     if (e >= P.n * P.ad) return;
     const int r = e / P.ad, a = e - r * P.ad;
@@ -99,6 +103,8 @@ __global__ __launch_bounds__(FQL_THREADS) void fql_rebrac_act_kernel(RebracActAr
     if (P.clip_out) v = clip1(v);
     P.out[(size_t)r * P.ldo + P.col0 + a] = v;
 }
+__global__ __launch_bounds__(FQL_THREADS) void fql_rebrac_act_kernel(RebracActArgs P) { fql_rebrac_act_body(P); }
+__global__ __launch_bounds__(FQL_THREADS) void fql_rebrac_act_multi_kernel(const RebracActArgs* __restrict__ args) { const RebracActArgs P = ((const FQL_CONST_AS RebracActArgs*)args)[blockIdx.y]; fql_rebrac_act_body(P); }
 
 struct RebracCriticArgs {
     const float *qa, *qb;      // [B, 16] column 0: critic members at (obs, act)
@@ -113,8 +119,7 @@ struct RebracCriticArgs {
 };
 // rebrac.py:36-53: next_q = min(target q1, q2) - alpha_critic sum((a' - next_actions)^2); y = r + discount mask next_q;
 // loss = mean over (2, B) of (q - y)^2; q_mean / q_max / q_min over all 2B values of q
-__global__ __launch_bounds__(FQL_THREADS) void fql_rebrac_loss_critic_kernel(RebracCriticArgs P) {
-    __shared__ float sh[4];
+__device__ __forceinline__ void fql_rebrac_loss_critic_body(const RebracCriticArgs& P, float* sh) {
     const float gs = 1.0f / (float)P.B;   // d/dq of mean over 2B of (q - y)^2
     float sl = 0.f, sq = 0.f, mx = -INFINITY, mn = INFINITY;
     for (int b = threadIdx.x; b < P.B; b += FQL_THREADS) {
@@ -147,6 +152,8 @@ __global__ __launch_bounds__(FQL_THREADS) void fql_rebrac_loss_critic_kernel(Reb
         in[3] = tmn;
     }
 }
+__global__ __launch_bounds__(FQL_THREADS) void fql_rebrac_loss_critic_kernel(RebracCriticArgs P) { __shared__ float sh[4]; fql_rebrac_loss_critic_body(P, sh); }
+__global__ __launch_bounds__(FQL_THREADS) void fql_rebrac_loss_critic_multi_kernel(const RebracCriticArgs* __restrict__ args) { __shared__ float sh[4]; const RebracCriticArgs P = ((const FQL_CONST_AS RebracCriticArgs*)args)[blockIdx.y]; fql_rebrac_loss_critic_body(P, sh); }
 
 struct RebracActorArgs {
     const float *qa, *qb;      // [B, 16] column 0: critic members (stored parameters) at (obs, a)
@@ -159,8 +166,7 @@ struct RebracActorArgs {
 };
 // rebrac.py:55-84: q = min(q1, q2), lam = 1 / mean|q| (no gradient), actor_loss = -mean(lam q), bc_loss = alpha_actor mean(sum((a - act)^2)),
 // std = 1 (const_std: log_std 0, temperature 1).  At a tie the gradient of min splits equally between the members, as jnp.min's does.
-__global__ __launch_bounds__(FQL_THREADS) void fql_rebrac_loss_actor_kernel(RebracActorArgs P) {
-    __shared__ float sh[4];
+__device__ __forceinline__ void fql_rebrac_loss_actor_body(const RebracActorArgs& P, float* sh) {
     float s = 0.f, sa = 0.f, se = 0.f;
     for (int b = threadIdx.x; b < P.B; b += FQL_THREADS) {
         const float q = fminf(P.qa[(size_t)b * 16], P.qb[(size_t)b * 16]);
@@ -194,6 +200,8 @@ __global__ __launch_bounds__(FQL_THREADS) void fql_rebrac_loss_actor_kernel(Rebr
         in[4] = mse;
     }
 }
+__global__ __launch_bounds__(FQL_THREADS) void fql_rebrac_loss_actor_kernel(RebracActorArgs P) { __shared__ float sh[4]; fql_rebrac_loss_actor_body(P, sh); }
+__global__ __launch_bounds__(FQL_THREADS) void fql_rebrac_loss_actor_multi_kernel(const RebracActorArgs* __restrict__ args) { __shared__ float sh[4]; const RebracActorArgs P = ((const FQL_CONST_AS RebracActorArgs*)args)[blockIdx.y]; fql_rebrac_loss_actor_body(P, sh); }
 
 struct RebracActorGradArgs {
     const float *dxa, *dxb;    // [B, inp_c]: the critic members' input gradients (columns od .. od + ad: dL/da through the Q term)
@@ -205,7 +213,7 @@ struct RebracActorGradArgs {
     int tanh_squash;
 };
 // dL/da = dQ-term/da + alpha_actor 2 (a - act) / B; through the tanh of the mode: dL/dmean = dL/da (1 - a^2)
-__global__ __launch_bounds__(FQL_THREADS) void fql_rebrac_actor_grad_kernel(RebracActorGradArgs P) {
+__device__ __forceinline__ void fql_rebrac_actor_grad_body(const RebracActorGradArgs& P) {
     const int e = blockIdx.x * FQL_THREADS + threadIdx.x;
     if (e >= P.B * P.ad) return;
     const int b = e / P.ad, a = e - b * P.ad;
@@ -215,9 +223,11 @@ __global__ __launch_bounds__(FQL_THREADS) void fql_rebrac_actor_grad_kernel(Rebr
     if (P.tanh_squash) g *= 1.0f - av * av;
     P.dmean[(size_t)b * P.ap + a] = g;
 }
+__global__ __launch_bounds__(FQL_THREADS) void fql_rebrac_actor_grad_kernel(RebracActorGradArgs P) { fql_rebrac_actor_grad_body(P); }
+__global__ __launch_bounds__(FQL_THREADS) void fql_rebrac_actor_grad_multi_kernel(const RebracActorGradArgs* __restrict__ args) { const RebracActorGradArgs P = ((const FQL_CONST_AS RebracActorGradArgs*)args)[blockIdx.y]; fql_rebrac_actor_grad_body(P); }
 
 // FQL's finalize (grad statistics into slots 10-12 and the step counters), then the reference's ReBRAC order for the step's kind
-__global__ __launch_bounds__(FQL_THREADS) void fql_rebrac_finalize_kernel(FinalizeArgs A, int full) {
+__device__ __forceinline__ void fql_rebrac_finalize_body(const FinalizeArgs& A, int full) {
     fql_finalize_body(A);
     if (threadIdx.x == 0 && A.do_grad_stats) {
         float* in = A.st->info;
@@ -227,3 +237,12 @@ __global__ __launch_bounds__(FQL_THREADS) void fql_rebrac_finalize_kernel(Finali
         for (int i = g0 + 3; i < 13; ++i) in[i] = 0.f;
     }
 }
+__global__ __launch_bounds__(FQL_THREADS) void fql_rebrac_finalize_kernel(FinalizeArgs A, int full) { fql_rebrac_finalize_body(A, full); }
+// The two arguments of the kernel above as one struct, laid out as its kernel-argument segment lays them out (A at 0, full behind it), so
+// that the bytes a member's launch binds are a prefix of its element of the multi-instance kernel's array
+struct RebracFinalizeArgs {
+    FinalizeArgs A;
+    int full;
+};
+static_assert(offsetof(RebracFinalizeArgs, full) == sizeof(FinalizeArgs) && alignof(FinalizeArgs) >= alignof(int), "RebracFinalizeArgs must match the (FinalizeArgs, int) kernel-argument layout");
+__global__ __launch_bounds__(FQL_THREADS) void fql_rebrac_finalize_multi_kernel(const RebracFinalizeArgs* __restrict__ args) { const RebracFinalizeArgs R = ((const FQL_CONST_AS RebracFinalizeArgs*)args)[blockIdx.y]; fql_rebrac_finalize_body(R.A, R.full); }

@@ -386,7 +386,8 @@ const char* fql_handle_info_name(fql_handle h, int i);
  * and fql_stream.  Refused: encoder != 0 or precision != 0 at create (FQL_E_INVALID); on a ReBRAC handle fql_update,
  * fql_update_from_dataset and fql_total_loss (no next_actions / step kind), fql_update_begin* / _end*, fql_grad_buckets, frame uploads /
  * updates, fql_noise_from_jax_keys, the replay ring, balanced sampling and fql_flow_actions return FQL_E_STATE, and fql_group_create
- * with a ReBRAC member returns FQL_E_STATE.  The fql_rebrac_* calls on another handle return FQL_E_STATE. */
+ * with a ReBRAC member still returns FQL_E_STATE: ReBRAC handles are grouped by fql_rebrac_group_create (below), whose groups hold two
+ * fused programs and take the step kind with every update.  The fql_rebrac_* calls on another handle return FQL_E_STATE. */
 #define FQL_REBRAC_NUM_INFO 12
 #define FQL_REBRAC_CRITIC_NUM_INFO 7
 typedef struct fql_rebrac_config {
@@ -419,6 +420,30 @@ int fql_rebrac_sample_actions(fql_handle h, const float* observations, int n, co
                               float* out, void* stream);
 /* launches and algorithmic MACs of one full (full_update != 0) or critic-only update */
 int fql_rebrac_stats(fql_handle h, int full_update, int64_t* launches_per_update, int64_t* macs_per_update);
+/* ---- ReBRAC agent groups: an alpha_actor x alpha_critic x seed sweep advanced by fused programs (agent groups, above) ----
+ * fql_rebrac_group_create: `members` [k], k >= 1, ReBRAC handles (another kind: FQL_E_STATE naming it), distinct, in no group, the same
+ * batch size and the same fql_config / fql_rebrac_config except alpha_actor, alpha_critic (and the create seed); anything else:
+ * FQL_E_INVALID naming the member, *out NULL.  The group holds TWO fused programs, each one graph with a member's lanes: the zip of
+ * every member's full step and the zip of every member's critic-only step (blockIdx.y = member in ReBRAC's own kernels, concatenated
+ * task tables in the layers).  A member's numbers are bitwise those it has alone.  fql_group_destroy and fql_group_synchronize serve
+ * these groups too; fql_set_batch_size and fql_destroy on a member return FQL_E_STATE while it is grouped.  Errors: fql_last_error(NULL).
+ * Across kinds: fql_group_update_from_dataset, fql_group_sample_actions, fql_group_flow_actions and fql_group_sample_stats on a ReBRAC
+ * group, and the three calls below that take a group on an FQL group, return FQL_E_STATE; a NULL group is FQL_E_INVALID. */
+int fql_rebrac_group_create(const fql_handle* members, int k, fql_group* out);
+/* fql_rebrac_update_from_dataset of every member in one fused update, full (full_update != 0) or critic-only.  idx: [k][B] int64, host or
+ * device, or NULL = each member's device RNG; next_actions are actions[min(idx + 1, size - 1)] of each member's own dataset.
+ * info13xk: [k][13] in fql_rebrac_update's layout for the step's kind (device or host; host = synchronous) or NULL.  Stream and ordering
+ * as fql_group_update_from_dataset. */
+int fql_rebrac_group_update_from_dataset(fql_group g, const int64_t* idx, int batch_size, int full_update, float* info13xk, void* stream);
+/* fql_rebrac_sample_actions of every member in one fused call; shapes, pointer kinds and ordering as fql_group_sample_actions.  Per
+ * chunk of <= 4096 rows per member: one assemble launch, the members' actor forward over concatenated task tables, and one launch of
+ * ReBRAC's action kernel that writes out[i] directly - the launch count does not depend on k.  out[i] is bitwise
+ * fql_rebrac_sample_actions(member i, ..., seeds[i], temperature, ...). */
+int fql_rebrac_group_sample_actions(fql_group g, const float* observations, int n, const float* noises, const uint64_t* seeds,
+                                    float temperature, float* out, void* stream);
+/* Launches of the group's full and critic-only programs and of one fused sampling call on a single chunk, counted from the built
+ * programs.  Any pointer may be NULL. */
+int fql_rebrac_group_stats(fql_group g, int64_t* launches_full, int64_t* launches_critic, int64_t* launches_sample);
 
 /* ---- SAC (agents/sac.py): soft actor-critic with a squashed Gaussian actor and a learned temperature; RLPD is this agent run online
  * from an empty replay ring with balanced sampling (main.py --offline_steps=0 --balanced_sampling=1).  State observations, fp32 only.
