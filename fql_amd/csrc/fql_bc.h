@@ -76,7 +76,7 @@ struct BcAssembleArgs {
     int n, n_pad, od, ad, inp, ap;
     int row0;                  // index of this chunk's first row in the call (keys the Philox draw: chunking does not change the noise)
 };
-__global__ __launch_bounds__(FQL_THREADS) void fql_bc_assemble_kernel(BcAssembleArgs P) {
+__device__ __forceinline__ void fql_bc_assemble_body(const BcAssembleArgs& P) {
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int r = blockIdx.x * 4 + wave;
     if (r >= P.n_pad) return;
@@ -87,6 +87,10 @@ __global__ __launch_bounds__(FQL_THREADS) void fql_bc_assemble_kernel(BcAssemble
         P.A[(size_t)r * P.ap + a] = v;
     }
 }
+__global__ __launch_bounds__(FQL_THREADS) void fql_bc_assemble_kernel(BcAssembleArgs P) { fql_bc_assemble_body(P); }
+// Multi-instance entry point (IQL-diffusion agent groups, whose sampler assembles its rows with this kernel): blockIdx.y picks the
+// member, its argument struct comes from a device array, read through the constant address space (fql_kernels.h FQL_CONST_AS)
+__global__ __launch_bounds__(FQL_THREADS) void fql_bc_assemble_multi_kernel(const BcAssembleArgs* __restrict__ args) { const BcAssembleArgs P = ((const FQL_CONST_AS BcAssembleArgs*)args)[blockIdx.y]; fql_bc_assemble_body(P); }
 
 // the [S, H] step-bias table: Cb[i][h] = sum_j emb[i][j] W0[od + ad + j][h], j in fixed order
 struct BcStepBiasArgs {

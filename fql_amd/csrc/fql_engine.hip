@@ -6377,7 +6377,9 @@ int fql_update_from_frames(fql_handle h, const int64_t* idx, const int32_t* crop
 // the tile shape and arguments its member's program gave it, so each member computes exactly what it computes alone.
 // The members' sampling programs are zipped the same way (fql_group_s::Sample): one fused sample_actions / flow_actions call for all K.
 // A group has a kind: FQL members (fql_group_create), or ReBRAC members (fql_rebrac_group_create), whose group
-// holds a second fused program, the zip of the members' critic-only step, and a sampler that ends in ReBRAC's action kernel.
+// holds a second fused program, the zip of the members' critic-only step, and a sampler that ends in ReBRAC's action kernel; or
+// IQL-diffusion members (fql_iqld_group_create), whose group holds one fused program per step kind (full,
+// critic-only, actor-only, neither) and a sampler that zips the members' sweep program: one guidance weight per row.
 // ================================================================================================
 namespace {
 
@@ -6417,6 +6419,19 @@ const std::map<const void*, MultiEntry>& multi_entries() {
         // (FinalizeArgs, int full): the launch binds the two arguments packed, the array element is the struct that holds both
         FQL_MULTI(fql_rebrac_finalize_kernel, fql_rebrac_finalize_multi_kernel, RebracFinalizeArgs);
         e[(const void*)fql_rebrac_finalize_kernel].arg_bytes = packed_bytes<FinalizeArgs, int>();
+        // IQL-diffusion (fql_iqld.h; its value loss is IFQL's, its sampler's row assembly BC's): the update programs, then the sweep sampler
+        FQL_MULTI(fql_iqld_prep_kernel, fql_iqld_prep_multi_kernel, IqldPrepArgs);
+        FQL_MULTI(fql_ifql_loss_value_kernel, fql_ifql_loss_value_multi_kernel, IfqlValueArgs);
+        FQL_MULTI(fql_iqld_loss_critic_kernel, fql_iqld_loss_critic_multi_kernel, IqldCriticArgs);
+        FQL_MULTI(fql_iqld_weight_kernel, fql_iqld_weight_multi_kernel, IqldWeightArgs);
+        FQL_MULTI(fql_iqld_loss_actor_kernel, fql_iqld_loss_actor_multi_kernel, IqldActorLossArgs);
+        FQL_MULTI(fql_iqld_embed_grad_kernel, fql_iqld_embed_grad_multi_kernel, IqldEmbedGradArgs);   // grid (2, members)
+        FQL_MULTI(fql_iqld_finalize_kernel, fql_iqld_finalize_multi_kernel, IqldFinalizeArgs);
+        FQL_MULTI(fql_bc_assemble_kernel, fql_bc_assemble_multi_kernel, BcAssembleArgs);
+        FQL_MULTI(fql_iqld_stepbias_kernel, fql_iqld_stepbias_multi_kernel, IqldStepBiasArgs);
+        FQL_MULTI(fql_iqld_layer0_kernel, fql_iqld_layer0_multi_kernel, IqldLayer0Args);
+        FQL_MULTI(fql_iqld_cfg_layer0_kernel, fql_iqld_cfg_layer0_multi_kernel, IqldCfgLayer0Args);
+        FQL_MULTI(fql_iqld_cfg_rows_step_kernel, fql_iqld_cfg_rows_step_multi_kernel, IqldCfgRowsStepArgs);
 #undef FQL_MULTI
         return e;
     }();
@@ -6448,10 +6463,13 @@ struct GProgram {
 
 struct fql_group_s {
     std::vector<fql_handle> m;
-    AgentKind kind = AgentKind::FQL;     // the members' kind: FQL (fql_group_create) or ReBRAC (fql_rebrac_group_create)
+    AgentKind kind = AgentKind::FQL;     // the members' kind: FQL (fql_group_create), ReBRAC (fql_rebrac_group_create) or IQL-diffusion (fql_iqld_group_create)
     int K = 0, B = 0;
     hipStream_t lanes[FQL_LANES] = {};   // lane 0 = the group's own stream
-    GProgram full, critic;               // the members' prog_full zipped; a ReBRAC group's second program: their prog_critic zipped
+    // One fused program per entry of group_programs(kind), in its order.  [0]: the members' prog_full zipped (every kind); [1]: their
+    // prog_critic (ReBRAC, IQL-diffusion); [2], [3]: their prog_actor and prog_none (IQL-diffusion)
+    enum { FULL = 0, CRITIC = 1, ACTOR = 2, NONE = 3, MAX_PROGS = 4 };
+    GProgram progs[MAX_PROGS];
     hipEvent_t ev_in = nullptr, ev_done = nullptr;
     std::vector<void*> allocs;
     int64_t* d_idx = nullptr;   // [K][B] staging of host row indices
@@ -6584,8 +6602,10 @@ struct fql_group_s {
     hipEvent_t arg_ev[kArgRing] = {};
     char arg_state[kArgRing] = {};   // 0 = free, 1 = behind arg_ev, 2 = on the legacy stream
     int arg_pos = 0;
-    // (a slot holds either layout: [K] AssembleArgs + [K] ExtractArgs, or [K] AssembleArgs + [K] RebracActArgs)
-    size_t arg_bytes() const { return (size_t)K * (sizeof(AssembleArgs) + std::max(sizeof(ExtractArgs), sizeof(RebracActArgs))); }
+    // (a slot holds the layout of the group's kind: [K] AssembleArgs + [K] ExtractArgs, [K] AssembleArgs + [K] RebracActArgs, or an
+    // IQL-diffusion group's [K] BcAssembleArgs + [K] ExtractArgs)
+    size_t asm_bytes() const { return kind == AgentKind::IQLD ? sizeof(BcAssembleArgs) : sizeof(AssembleArgs); }
+    size_t arg_bytes() const { return (size_t)K * (asm_bytes() + std::max(sizeof(ExtractArgs), sizeof(RebracActArgs))); }
 
     Sample& sample_ws(int n_pad, bool flow) {
         std::unique_ptr<Sample>& slot = samples[n_pad];
@@ -6611,8 +6631,31 @@ struct fql_group_s {
             slot->flow = zip_lane0([&](fql_engine& e) -> Program& { return e.get_eval(n_pad).prog_flow; }, "the flow sampler");
         return *slot;
     }
+    // An IQL-diffusion group's workspace of one chunk of `half` padded rows per member (Sample::n_pad holds the half): the launches of
+    // every member's SWEEP program get_eval(2 half, true).prog_flow zipped - it binds its per-row guidance weights from the member's
+    // workspace (Eval::cfgs) and takes no issue-time argument, which a device-resident argument array could not follow - between the
+    // multi-instance forms of the two launches fql_engine::sample_flow puts around it.
+    Sample& sample_ws_cfg(int half) {
+        std::unique_ptr<Sample>& slot = samples[half];
+        if (!slot) {
+            auto w = std::make_unique<Sample>();
+            const int od = m[0]->cfg.obs_dim, ad = m[0]->cfg.act_dim;
+            w->n_pad = half;
+            w->flow = zip_lane0([&](fql_engine& e) -> Program& { return e.get_eval(2 * half, true).prog_flow; }, "the guidance-sweep sampler");
+            w->st_obs = (float*)galloc((size_t)K * half * od * sizeof(float));
+            w->st_noise = (float*)galloc((size_t)K * half * ad * sizeof(float));
+            w->st_out = (float*)galloc((size_t)K * half * ad * sizeof(float));
+            w->d_args = (unsigned char*)galloc(arg_bytes());
+            w->assemble = bind(fql_bc_assemble_multi_kernel, Geo(dim3((half + 3) / 4, K), dim3(FQL_THREADS), 0), (const BcAssembleArgs*)w->d_args);
+            w->extract = bind(fql_extract_multi_kernel, Geo(dim3((half * ad + 255) / 256, K), dim3(256), 0),
+                              (const ExtractArgs*)(w->d_args + (size_t)K * sizeof(BcAssembleArgs)));
+            slot = std::move(w);
+        }
+        return *slot;
+    }
     // launches of one fused sampling call on a single chunk, counted from the built program: assemble, the zipped launches, extract
     int64_t sample_launches(bool flow) {
+        if (kind == AgentKind::IQLD) return 2 + (int64_t)sample_ws_cfg(16).flow.size();
         Sample& w = sample_ws(16, flow);
         return 2 + (int64_t)(flow ? w.flow : w.os).size();
     }
@@ -6678,19 +6721,58 @@ struct fql_group_s {
                                      (seeds ? seeds[i] : 0) + (uint64_t)start, mm, w.n_pad, od, ad, flow ? e.nets[NET_BC].in_p() : e.nets[NET_OS].in_p()};
                 ea[i] = ExtractArgs{flow ? ev.tgt : ev.p_os.out, dev_out ? out + ((size_t)i * n + start) * ad : w.st_out + (size_t)i * mm * ad, mm, ad, ap};
             }
-            HIP_CHECK(hipMemcpyAsync(w.d_args, slot, arg_bytes(), hipMemcpyHostToDevice, s));
-            if (s == hipStreamLegacy) arg_state[arg_pos] = 2;
-            else { HIP_CHECK(hipEventRecord(arg_ev[arg_pos], s)); arg_state[arg_pos] = 1; }
-            if (!dev_obs || (noise && !dev_z)) HIP_CHECK(hipStreamSynchronize(s));   // (host rows are borrowed for the call only)
-            launch_bound(w.assemble, w.assemble.args.data(), s);
-            for (GLaunch& G : flow ? w.flow : w.os) launch_bound(G.k, G.k.args.data(), s);
-            const Bound& fin = rebrac ? w.act : w.extract;
-            launch_bound(fin, fin.args.data(), s);
-            HIP_CHECK(hipGetLastError());
-            if (!dev_out) {
-                copy_rows(out + (size_t)start * ad, (size_t)n * ad, w.st_out, (size_t)mm * ad, (size_t)mm * ad, hipMemcpyDeviceToHost, s);
-                HIP_CHECK(hipStreamSynchronize(s));
+            issue_chunk(w, slot, flow ? w.flow : w.os, rebrac ? w.act : w.extract, !dev_obs || (noise && !dev_z), dev_out ? nullptr : out, n, start, mm, s);
+        }
+    }
+    // The tail of a chunk of either sampler: the slot's argument structs to the device with the ring's event behind them, the wait that
+    // ends the borrowing of host inputs (host rows - and weights - are the caller's again when the call returns), the assemble launch,
+    // the zipped launches, the finishing launch, and a host result (host_out: the call's `out`, [K, n, ad]) copied out and waited for.
+    void issue_chunk(Sample& w, const unsigned char* slot, std::vector<GLaunch>& zipped, const Bound& fin, bool host_inputs, float* host_out,
+                     int n, int start, int mm, hipStream_t s) {
+        const int ad = m[0]->cfg.act_dim;
+        HIP_CHECK(hipMemcpyAsync(w.d_args, slot, arg_bytes(), hipMemcpyHostToDevice, s));
+        if (s == hipStreamLegacy) arg_state[arg_pos] = 2;
+        else { HIP_CHECK(hipEventRecord(arg_ev[arg_pos], s)); arg_state[arg_pos] = 1; }
+        if (host_inputs) HIP_CHECK(hipStreamSynchronize(s));
+        launch_bound(w.assemble, w.assemble.args.data(), s);
+        for (GLaunch& G : zipped) launch_bound(G.k, G.k.args.data(), s);
+        launch_bound(fin, fin.args.data(), s);
+        HIP_CHECK(hipGetLastError());
+        if (host_out) {
+            copy_rows(host_out + (size_t)start * ad, (size_t)n * ad, w.st_out, (size_t)mm * ad, (size_t)mm * ad, hipMemcpyDeviceToHost, s);
+            HIP_CHECK(hipStreamSynchronize(s));
+        }
+    }
+
+    // An IQL-diffusion group (fql_iqld_group_sample_actions): fql_iqld_sample_actions_cfgs of every member in one fused call.  Per chunk
+    // of <= 2048 observations per member - the member's own chunks, row numbers and seed key (fql_engine::sample_flow) -
+    // fql_bc_assemble_multi_kernel, each member's chunk of `cfgs` [K, n] (host: checked finite here; or device) copied into the buffer
+    // its sweep program reads with 0 behind it, the zipped launches, extract-multi.
+    void sample_cfg(const float* obs, const float* noise, const uint64_t* seeds, const float* cfgs, int n, float* out, hipStream_t s) {
+        const int od = m[0]->cfg.obs_dim, ad = m[0]->cfg.act_dim, ap = pad16(ad);
+        const bool dev_obs = fql_engine::is_device_ptr(obs), dev_z = noise && fql_engine::is_device_ptr(noise), dev_out = fql_engine::is_device_ptr(out);
+        const bool dev_c = fql_engine::is_device_ptr(cfgs);
+        if (!dev_c)
+            for (size_t i = 0; i < (size_t)K * n; ++i)
+                if (!std::isfinite(cfgs[i])) invalid("cfgs[%zu][%zu] = %g: every guidance weight must be finite", i / n, i % n, (double)cfgs[i]);
+        for (int start = 0; start < n; start += 2048) {
+            const int mm = std::min(2048, n - start), half = pad16(mm);
+            Sample& w = sample_ws_cfg(half);
+            const Rows o = chunk_rows(obs, dev_obs, w.st_obs, od, n, start, mm, s);
+            const Rows z = chunk_rows(noise, dev_z, w.st_noise, ad, n, start, mm, s);
+            unsigned char* slot = arg_slot();
+            BcAssembleArgs* aa = (BcAssembleArgs*)slot;
+            ExtractArgs* ea = (ExtractArgs*)(slot + (size_t)K * sizeof(BcAssembleArgs));
+            for (int i = 0; i < K; ++i) {
+                fql_engine& e = *m[i];
+                fql_engine::Eval& ev = e.get_eval(2 * half, true);
+                aa[i] = BcAssembleArgs{o.p + i * o.stride, z.p ? z.p + i * z.stride : nullptr, ev.X, ev.Xf, e.seed, seeds ? seeds[i] : 0, mm, half, od, ad,
+                                       e.nets[NET_BC].in_p(), ap, start};
+                ea[i] = ExtractArgs{ev.tgt, dev_out ? out + ((size_t)i * n + start) * ad : w.st_out + (size_t)i * mm * ad, mm, ad, ap};
+                HIP_CHECK(hipMemcpyAsync(ev.cfgs, cfgs + (size_t)i * n + start, (size_t)mm * sizeof(float), hipMemcpyDefault, s));
+                if (half > mm) HIP_CHECK(hipMemsetAsync(ev.cfgs + mm, 0, (size_t)(half - mm) * sizeof(float), s));
             }
+            issue_chunk(w, slot, w.flow, w.extract, !dev_obs || (noise && !dev_z) || !dev_c, dev_out ? nullptr : out, n, start, mm, s);
         }
     }
 
@@ -6734,10 +6816,10 @@ struct fql_group_s {
         if (last == hipStreamLegacy) hipDeviceSynchronize();
         if (ev_done) hipEventSynchronize(ev_done);
         for (fql_handle h : m) { h->group = nullptr; h->grp_pending = h->grp_legacy = false; h->grp_done = nullptr; h->grp_touched = true; }
-        for (GProgram* p : {&full, &critic}) {
-            if (p->exec) hipGraphExecDestroy(p->exec);
-            if (p->graph) hipGraphDestroy(p->graph);
-            destroy_lane_events(*p);
+        for (GProgram& p : progs) {
+            if (p.exec) hipGraphExecDestroy(p.exec);
+            if (p.graph) hipGraphDestroy(p.graph);
+            destroy_lane_events(p);
         }
         for (hipEvent_t e : {ev_in, ev_done}) if (e) hipEventDestroy(e);
         for (hipEvent_t e : arg_ev) if (e) hipEventDestroy(e);
@@ -6749,14 +6831,17 @@ struct fql_group_s {
 };
 
 namespace {
-// The update programs a group of `kind` fuses: every kind's prog_full, and ReBRAC's prog_critic (the critic-only step) behind it
+// The update programs a group of `kind` fuses (fql_group_s::progs, in this order): every kind's prog_full; ReBRAC's prog_critic (the
+// critic-only step) behind it; IQL-diffusion's four step kinds
 std::vector<Program fql_engine::*> group_programs(AgentKind kind) {
     std::vector<Program fql_engine::*> p{&fql_engine::prog_full};
-    if (kind == AgentKind::REBRAC) p.push_back(&fql_engine::prog_critic);
+    if (kind == AgentKind::REBRAC || kind == AgentKind::IQLD) p.push_back(&fql_engine::prog_critic);
+    if (kind == AgentKind::IQLD) { p.push_back(&fql_engine::prog_actor); p.push_back(&fql_engine::prog_none); }
     return p;
 }
 // the members' restrictions and the structural identity of their programs (fql_group_create, fql_rebrac_group_create: `fn`).  What may
-// differ between members beside the create seed: FQL's alpha; ReBRAC's alpha_actor and alpha_critic - kernel arguments, not structure.
+// differ between members beside the create seed: FQL's alpha; ReBRAC's alpha_actor and alpha_critic; IQL-diffusion's awr_temperature and
+// softmax_beta (both reach the device as IqldWeightArgs::temp alone) - kernel arguments, not structure.
 void group_check(const char* fn, AgentKind kind, const fql_handle* members, int k) {
     if (!members || k <= 0) invalid("%s: members must be a non-empty array (k = %d)", fn, k);
     for (int i = 0; i < k; ++i) {
@@ -6776,8 +6861,14 @@ void group_check(const char* fn, AgentKind kind, const fql_handle* members, int 
             ra.alpha_actor = rb.alpha_actor = ra.alpha_critic = rb.alpha_critic = 0.f;
             same = same && std::memcmp(&ra, &rb, sizeof ra) == 0;
         }
+        if (kind == AgentKind::IQLD) {
+            fql_iqld_config da = h->dcfg, db = members[0]->dcfg;
+            da.awr_temperature = db.awr_temperature = da.softmax_beta = db.softmax_beta = 0.f;
+            same = same && std::memcmp(&da, &db, sizeof da) == 0;
+        }
         if (!same)
-            invalid("%s: member %d's config differs from member 0's in more than seed and %s", fn, i, kind == AgentKind::REBRAC ? "alpha_actor / alpha_critic" : "alpha");
+            invalid("%s: member %d's config differs from member 0's in more than seed and %s", fn, i,
+                    kind == AgentKind::REBRAC ? "alpha_actor / alpha_critic" : kind == AgentKind::IQLD ? "awr_temperature / softmax_beta" : "alpha");
         if (h->B != members[0]->B) invalid("%s: member %d has batch size %d, member 0 has %d", fn, i, h->B, members[0]->B);
         for (Program fql_engine::* pp : group_programs(kind)) {
             const Program& p = h->*pp, &p0 = members[0]->*pp;
@@ -6821,18 +6912,17 @@ int group_create(const char* fn, AgentKind kind, const char* want, const fql_han
                 }
             for (size_t li = 0; li < n; ++li) {
                 const Bound& k0 = (g->m[0]->*pp).launches[li].k;
-                if (k0.grid[1] != 1 || k0.grid[2] != 1) invalid("%s: launch %zu has a 2-D grid: not groupable", fn, li);
+                if (k0.grid[1] != 1 || k0.grid[2] != 1) invalid("%s: launch %zu has a 2-D grid: not groupable", fn, li);   // (grid y is the member)
                 gp.launches.push_back(g->zip((int)li, [pp](fql_engine& e) -> Program& { return e.*pp; }));
                 gp.lane_used[gp.launches.back().lane] = true;
             }
         };
-        GProgram* const fused[] = {&g->full, &g->critic};
         const std::vector<Program fql_engine::*> progs = group_programs(kind);
-        for (size_t p = 0; p < progs.size(); ++p) fuse_program(*fused[p], progs[p]);
+        for (size_t p = 0; p < progs.size(); ++p) fuse_program(g->progs[p], progs[p]);
         for (int l = 0; l < FQL_LANES; ++l) HIP_CHECK(hipStreamCreateWithFlags(&g->lanes[l], hipStreamNonBlocking));
         for (hipEvent_t* e : {&g->ev_in, &g->ev_done}) HIP_CHECK(hipEventCreateWithFlags(e, hipEventDisableTiming));
         HIP_CHECK(hipMalloc((void**)&g->d_idx, (size_t)k * g->B * sizeof(int64_t)));
-        for (size_t p = 0; p < progs.size(); ++p) g->capture(*fused[p]);
+        for (size_t p = 0; p < progs.size(); ++p) g->capture(g->progs[p]);
     } catch (const Invalid& e) {
         g_create_error = e.msg; g->release(); delete g; return FQL_E_INVALID;
     } catch (const HipError& e) {
@@ -6844,7 +6934,8 @@ int group_create(const char* fn, AgentKind kind, const char* want, const fql_han
 }
 
 // One fused update of every member: `gp` is the group's program for the step's kind.  fn: the entry point, for its messages.
-int group_update(fql_group g, const char* fn, GProgram& gp, const int64_t* idx, int batch_size, float* info13xk, void* stream) {
+// infos: [k][n_info] - 13 floats of DevState::info, or an IQL-diffusion member's 21 of its own buffer (fql_engine::info_src).
+int group_update(fql_group g, const char* fn, GProgram& gp, const int64_t* idx, int batch_size, float* info13xk, void* stream, int n_info = FQL_NUM_INFO) {
     try {
         if (batch_size != g->B) invalid("%s: batch_size %d does not match the members' %d", fn, batch_size, g->B);
         if (g->member_began()) { g_create_error = std::string(fn) + ": a member is between fql_update_begin and fql_update_end"; return FQL_E_STATE; }
@@ -6859,7 +6950,7 @@ int group_update(fql_group g, const char* fn, GProgram& gp, const int64_t* idx, 
         HIP_CHECK(hipGraphLaunch(gp.exec, s));
         if (info13xk) {
             for (int i = 0; i < g->K; ++i)
-                HIP_CHECK(hipMemcpyAsync(info13xk + (size_t)i * FQL_NUM_INFO, &g->m[i]->d_state->info[0], FQL_NUM_INFO * sizeof(float), hipMemcpyDefault, s));
+                HIP_CHECK(hipMemcpyAsync(info13xk + (size_t)i * n_info, g->m[i]->info_src(), (size_t)n_info * sizeof(float), hipMemcpyDefault, s));
         }
         g->leave(s, info13xk && !fql_engine::is_device_ptr(info13xk));
     } catch (const Invalid& e) {
@@ -6869,9 +6960,19 @@ int group_update(fql_group g, const char* fn, GProgram& gp, const int64_t* idx, 
     }
     return FQL_OK;
 }
-// A group call on a group of the other kind: FQL_E_STATE, naming the call that serves it
-bool group_wrong_kind(fql_group g, AgentKind kind, const char* fn, const char* instead) {
+// What a group call does, and the call of each kind of group that does it
+enum GroupCall { GC_UPDATE, GC_SAMPLE, GC_STATS };
+const char* group_call_of(AgentKind kind, GroupCall c) {
+    static const char* const fql[] = {"fql_group_update_from_dataset", "fql_group_sample_actions", "fql_group_sample_stats"};
+    static const char* const rebrac[] = {"the step kind is an argument: fql_rebrac_group_update_from_dataset", "fql_rebrac_group_sample_actions", "fql_rebrac_group_stats"};
+    static const char* const iqld[] = {"the step kind is two arguments: fql_iqld_group_update_from_dataset", "it takes guidance weights: fql_iqld_group_sample_actions", "fql_iqld_group_stats"};
+    return (kind == AgentKind::IQLD ? iqld : kind == AgentKind::REBRAC ? rebrac : fql)[c];
+}
+// A group call on a group of another kind: FQL_E_STATE, naming the call that serves it.  `kind`: the groups `fn` serves; `instead`: what
+// an FQL call says on a ReBRAC group and the reverse; with an IQL-diffusion group on either side, the group's own call for `c`.
+bool group_wrong_kind(fql_group g, AgentKind kind, const char* fn, const char* instead, GroupCall c) {
     if (g->kind == kind) return false;
+    if (g->kind == AgentKind::IQLD || kind == AgentKind::IQLD) instead = group_call_of(g->kind, c);
     g_create_error = std::string(fn) + " is not available on a group of " + g->m[0]->desc().name + " agents (" + instead + ")";
     return true;
 }
@@ -6885,6 +6986,9 @@ int fql_group_create(const fql_handle* members, int k, fql_group* out) {
 int fql_rebrac_group_create(const fql_handle* members, int k, fql_group* out) {
     return group_create("fql_rebrac_group_create", AgentKind::REBRAC, "ReBRAC groups take ReBRAC agents only", members, k, out);
 }
+int fql_iqld_group_create(const fql_handle* members, int k, fql_group* out) {
+    return group_create("fql_iqld_group_create", AgentKind::IQLD, "IQL-diffusion groups take IQL-diffusion agents only", members, k, out);
+}
 
 // Diagnostic only (not in include/fql_amd.h, beside fql_debug_plan): where each launch of an update program takes its tasks from, as int32 words
 //   [words (this one included), capacities of the argument form of a side-lane launch: GEMM-tile, weight-gradient, LayerNorm-backward, loss / metric
@@ -6896,7 +7000,7 @@ int fql_debug_task_forms(fql_handle h, fql_group g, void* out, size_t bytes) {
     if (!g && (h->visual || !h->prog_full.exec || h->prog_full.launches.empty())) return FQL_E_STATE;
     auto form = [](const Launch& L) { return !is_table_launch(L.type) ? 0 : L.ka ? 2 : 1; };
     std::vector<int32_t> w{0, FQL_KA_GEMM, FQL_KA_WGRAD, FQL_KA_LN, FQL_KA_MISC, 0};
-    if (g) for (const GLaunch& G : g->full.launches) w.push_back(G.form);
+    if (g) for (const GLaunch& G : g->progs[fql_group_s::FULL].launches) w.push_back(G.form);
     else for (const Launch& L : h->prog_full.launches) w.push_back(form(L));
     w[5] = (int32_t)w.size() - 6;
     w[0] = (int32_t)w.size();
@@ -6917,8 +7021,8 @@ int fql_debug_aql_fences(fql_handle h, fql_group g, void* out, size_t bytes) {
     if (!g && (h->visual || !h->prog_full.exec || h->prog_full.launches.empty())) return FQL_E_STATE;
     std::vector<int32_t> w{0, 0, 0, 0};
     if (g) {
-        bool all = !g->full.launches.empty();
-        for (const GLaunch& G : g->full.launches) all = all && l1_independent_kernel(G.k.fn);
+        bool all = !g->progs[fql_group_s::FULL].launches.empty();
+        for (const GLaunch& G : g->progs[fql_group_s::FULL].launches) all = all && l1_independent_kernel(G.k.fn);
         w[1] = all;
         w[2] = g->m.empty() ? 0 : (int32_t)g->m[0]->aql_acquire;
     } else {
@@ -6952,22 +7056,31 @@ int fql_group_destroy(fql_group g) {
 int fql_group_update_from_dataset(fql_group g, const int64_t* idx, int batch_size, float* info13xk, void* stream) {
     const char* fn = "fql_group_update_from_dataset";
     if (!g) { g_create_error = std::string(fn) + ": NULL group"; return FQL_E_INVALID; }
-    if (group_wrong_kind(g, AgentKind::FQL, fn, "the step kind is an argument: fql_rebrac_group_update_from_dataset")) return FQL_E_STATE;
-    return group_update(g, fn, g->full, idx, batch_size, info13xk, stream);
+    if (group_wrong_kind(g, AgentKind::FQL, fn, "the step kind is an argument: fql_rebrac_group_update_from_dataset", GC_UPDATE)) return FQL_E_STATE;
+    return group_update(g, fn, g->progs[fql_group_s::FULL], idx, batch_size, info13xk, stream);
 }
 // fql_rebrac_update_from_dataset of every member in one fused update: the zip of their prog_full, or of their prog_critic
 int fql_rebrac_group_update_from_dataset(fql_group g, const int64_t* idx, int batch_size, int full_update, float* info13xk, void* stream) {
     const char* fn = "fql_rebrac_group_update_from_dataset";
     if (!g) { g_create_error = std::string(fn) + ": NULL group"; return FQL_E_INVALID; }
-    if (group_wrong_kind(g, AgentKind::REBRAC, fn, "fql_group_update_from_dataset")) return FQL_E_STATE;
-    return group_update(g, fn, full_update ? g->full : g->critic, idx, batch_size, info13xk, stream);
+    if (group_wrong_kind(g, AgentKind::REBRAC, fn, "fql_group_update_from_dataset", GC_UPDATE)) return FQL_E_STATE;
+    return group_update(g, fn, g->progs[full_update ? fql_group_s::FULL : fql_group_s::CRITIC], idx, batch_size, info13xk, stream);
+}
+
+// fql_iqld_update_from_dataset of every member in one fused update: the zip of their program of that step kind
+int fql_iqld_group_update_from_dataset(fql_group g, const int64_t* idx, int batch_size, int update_critic, int update_actor, float* info21xk, void* stream) {
+    const char* fn = "fql_iqld_group_update_from_dataset";
+    if (!g) { g_create_error = std::string(fn) + ": NULL group"; return FQL_E_INVALID; }
+    if (group_wrong_kind(g, AgentKind::IQLD, fn, nullptr, GC_UPDATE)) return FQL_E_STATE;
+    const int kind = update_critic ? (update_actor ? fql_group_s::FULL : fql_group_s::CRITIC) : (update_actor ? fql_group_s::ACTOR : fql_group_s::NONE);
+    return group_update(g, fn, g->progs[kind], idx, batch_size, info21xk, stream, FQL_IQLD_NUM_INFO);
 }
 
 // The members' sample_actions (flow: compute_flow_actions) in one fused call: fql_group_s::sample between the update's ordering rules
 static int group_sample(fql_group g, const char* fn, AgentKind kind, const char* instead, bool flow, const float* obs, const float* noise,
                         const uint64_t* seeds, float temperature, int n, float* out, void* stream) {
     if (!g) { g_create_error = std::string(fn) + ": NULL group"; return FQL_E_INVALID; }
-    if (group_wrong_kind(g, kind, fn, instead)) return FQL_E_STATE;
+    if (group_wrong_kind(g, kind, fn, instead, GC_SAMPLE)) return FQL_E_STATE;
     try {
         if (n <= 0) invalid("%s: n must be positive (got %d)", fn, n);
         if (!obs || !out) invalid("%s: observations/out must not be NULL", fn);
@@ -6998,9 +7111,33 @@ int fql_rebrac_group_sample_actions(fql_group g, const float* observations, int 
                                     float* out, void* stream) {
     return group_sample(g, "fql_rebrac_group_sample_actions", AgentKind::REBRAC, "fql_group_sample_actions", false, observations, noises, seeds, temperature, n, out, stream);
 }
+// fql_iqld_sample_actions_cfgs of every member in one fused call: fql_group_s::sample_cfg between the update's ordering rules
+int fql_iqld_group_sample_actions(fql_group g, const float* observations, int n, const float* noises, const uint64_t* seeds, const float* cfgs,
+                                  float* out, void* stream) {
+    const char* fn = "fql_iqld_group_sample_actions";
+    if (!g) { g_create_error = std::string(fn) + ": NULL group"; return FQL_E_INVALID; }
+    if (group_wrong_kind(g, AgentKind::IQLD, fn, nullptr, GC_SAMPLE)) return FQL_E_STATE;
+    try {
+        if (n <= 0) invalid("%s: n must be positive (got %d)", fn, n);
+        if (!observations || !out) invalid("%s: observations/out must not be NULL", fn);
+        if (!cfgs) invalid("%s: cfgs must not be NULL (one guidance weight per member and row)", fn);
+        if (!noises && !seeds) invalid("%s: seeds must not be NULL when noises is NULL (one seed per member)", fn);
+        if (g->member_began()) { g_create_error = std::string(fn) + ": a member is between fql_update_begin and fql_update_end"; return FQL_E_STATE; }
+        const hipStream_t s = g->enter(stream);
+        g->sample_cfg(observations, noises, seeds, cfgs, n, out, s);
+        g->leave(s, !stream && fql_engine::is_device_ptr(out));
+    } catch (const Invalid& e) {
+        g_create_error = e.msg; return FQL_E_INVALID;
+    } catch (const HipError& e) {
+        g_create_error = e.msg; return FQL_E_HIP;
+    } catch (const std::exception& e) {
+        g_create_error = e.what(); return FQL_E_HIP;
+    }
+    return FQL_OK;
+}
 int fql_group_sample_stats(fql_group g, int flow, int64_t* launches_per_call) {
     if (!g) { g_create_error = "fql_group_sample_stats: NULL group"; return FQL_E_INVALID; }
-    if (group_wrong_kind(g, AgentKind::FQL, "fql_group_sample_stats", "fql_rebrac_group_stats")) return FQL_E_STATE;
+    if (group_wrong_kind(g, AgentKind::FQL, "fql_group_sample_stats", "fql_rebrac_group_stats", GC_STATS)) return FQL_E_STATE;
     if (!launches_per_call) { g_create_error = "fql_group_sample_stats: launches_per_call must not be NULL"; return FQL_E_INVALID; }
     try {
         *launches_per_call = g->sample_launches(flow != 0);
@@ -7014,11 +7151,27 @@ int fql_group_sample_stats(fql_group g, int flow, int64_t* launches_per_call) {
 // Launches of a ReBRAC group's two fused update programs and of one fused sampling call on a single chunk, counted from the built programs
 int fql_rebrac_group_stats(fql_group g, int64_t* launches_full, int64_t* launches_critic, int64_t* launches_sample) {
     if (!g) { g_create_error = "fql_rebrac_group_stats: NULL group"; return FQL_E_INVALID; }
-    if (group_wrong_kind(g, AgentKind::REBRAC, "fql_rebrac_group_stats", "fql_group_sample_stats")) return FQL_E_STATE;
+    if (group_wrong_kind(g, AgentKind::REBRAC, "fql_rebrac_group_stats", "fql_group_sample_stats", GC_STATS)) return FQL_E_STATE;
     try {
-        if (launches_full) *launches_full = (int64_t)g->full.launches.size();
-        if (launches_critic) *launches_critic = (int64_t)g->critic.launches.size();
+        if (launches_full) *launches_full = (int64_t)g->progs[fql_group_s::FULL].launches.size();
+        if (launches_critic) *launches_critic = (int64_t)g->progs[fql_group_s::CRITIC].launches.size();
         if (launches_sample) *launches_sample = g->sample_launches(false);
+    } catch (const Invalid& e) {
+        g_create_error = e.msg; return FQL_E_INVALID;
+    } catch (const HipError& e) {
+        g_create_error = e.msg; return FQL_E_HIP;
+    }
+    return FQL_OK;
+}
+
+// Launches of an IQL-diffusion group's four fused update programs (full, critic-only, actor-only, neither) and of one fused sampling
+// call on a single chunk, counted from the built programs
+int fql_iqld_group_stats(fql_group g, int64_t launches[4], int64_t* launches_sample) {
+    if (!g) { g_create_error = "fql_iqld_group_stats: NULL group"; return FQL_E_INVALID; }
+    if (group_wrong_kind(g, AgentKind::IQLD, "fql_iqld_group_stats", nullptr, GC_STATS)) return FQL_E_STATE;
+    try {
+        if (launches) for (int p = 0; p < fql_group_s::MAX_PROGS; ++p) launches[p] = (int64_t)g->progs[p].launches.size();
+        if (launches_sample) *launches_sample = g->sample_launches(true);
     } catch (const Invalid& e) {
         g_create_error = e.msg; return FQL_E_INVALID;
     } catch (const HipError& e) {

@@ -69,8 +69,7 @@ struct IfqlValueArgs {
     float expectile;
 };
 // agents/ifql.py:25-43: q = min(target q1, q2); loss = mean(w (q - v)^2), w = expectile where q - v >= 0, else 1 - expectile
-__global__ __launch_bounds__(FQL_THREADS) void fql_ifql_loss_value_kernel(IfqlValueArgs P) {
-    __shared__ float sh[4];
+__device__ __forceinline__ void fql_ifql_loss_value_body(const IfqlValueArgs& P, float* sh) {
     const float gs = 2.0f / (float)P.B;
     float sl = 0.f, sv = 0.f, mx = -INFINITY, mn = INFINITY;
     for (int b = threadIdx.x; b < P.B; b += FQL_THREADS) {
@@ -94,6 +93,10 @@ __global__ __launch_bounds__(FQL_THREADS) void fql_ifql_loss_value_kernel(IfqlVa
         in[3] = tmn;
     }
 }
+__global__ __launch_bounds__(FQL_THREADS) void fql_ifql_loss_value_kernel(IfqlValueArgs P) { __shared__ float sh[4]; fql_ifql_loss_value_body(P, sh); }
+// Multi-instance entry point (IQL-diffusion agent groups, whose value loss this is): blockIdx.y picks the member, its argument struct
+// comes from a device array, read through the constant address space (fql_kernels.h FQL_CONST_AS)
+__global__ __launch_bounds__(FQL_THREADS) void fql_ifql_loss_value_multi_kernel(const IfqlValueArgs* __restrict__ args) { __shared__ float sh[4]; const IfqlValueArgs P = ((const FQL_CONST_AS IfqlValueArgs*)args)[blockIdx.y]; fql_ifql_loss_value_body(P, sh); }
 
 struct IfqlCriticArgs {
     const float* nv;           // [B, 16] column 0: value(next_obs) with the stored parameters (rows B..2B-1 of the value pass)

@@ -5,6 +5,8 @@
 // the GEMM bodies, weight gradients, LayerNorm backward, Adam + Polyak and the sampler's row assembly (fql_bc_assemble_kernel) are
 // FQL's and BC's.  Every reduction runs in one workgroup in a fixed order (no float atomics).  At the end of the file: the two kernels
 // of the sweep programs (one guidance weight per row), the guidance step folded into the next step's layer 0 and the last step alone.
+// Every kernel an IQL-diffusion agent group fuses (fql_iqld_group_*) comes in three parts: a __device__ body, the
+// by-value entry a single handle launches, and a *_multi_kernel that takes a device array of the same argument struct, one per member.
 //
 // The actor (DiffusionPolicy) is MLP(hidden, GELU, LayerNorm) + Dense(act) on [obs | x_t | emb(t) | Embed[is_positive]]: BC's policy
 // with 32 more input columns.  The positive and the unconditional pass of a batch share obs, x_t, t and vel, so they run as ONE pass
@@ -34,7 +36,7 @@ struct IqldPrepArgs {
 };
 // utils/datasets.py:64-100 (index draw + gather), agents/iql_diffusion.py:172-186 (x_0, k, x_t, vel and the two actor inputs): one wave
 // per transition.  x_0 is Philox tensor 2 and k = floor(u32 (S + 1) / 2^32) of tensor 3, as BC's; explicit tensors replace them.
-__global__ __launch_bounds__(FQL_THREADS) void fql_iqld_prep_kernel(IqldPrepArgs P) {
+__device__ __forceinline__ void fql_iqld_prep_body(const IqldPrepArgs& P) {
     const SrcDesc& S = *P.src;
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int b = blockIdx.x * 4 + wave;
@@ -85,6 +87,11 @@ __global__ __launch_bounds__(FQL_THREADS) void fql_iqld_prep_kernel(IqldPrepArgs
         P.w_mask[b] = S.mask[src];
     }
 }
+__global__ __launch_bounds__(FQL_THREADS) void fql_iqld_prep_kernel(IqldPrepArgs P) { fql_iqld_prep_body(P); }
+// Multi-instance entry points (IQL-diffusion agent groups), here and below: blockIdx.y picks the member, its argument struct comes from a
+// device array, read through the constant address space (scalar loads, as from the kernel-argument segment; fql_kernels.h FQL_CONST_AS).
+// Shared-memory arrays are declared in the entries and handed to the body.
+__global__ __launch_bounds__(FQL_THREADS) void fql_iqld_prep_multi_kernel(const IqldPrepArgs* __restrict__ args) { const IqldPrepArgs P = ((const FQL_CONST_AS IqldPrepArgs*)args)[blockIdx.y]; fql_iqld_prep_body(P); }
 
 struct IqldCriticArgs {
     const float* nv;           // [B, 16] column 0: value(next_obs), stored parameters (rows B..2B-1 of the value pass)
@@ -97,8 +104,7 @@ struct IqldCriticArgs {
 };
 // agents/iql_diffusion.py:94-103: y = r + discount mask v(next_obs); loss = mean over BOTH members and the batch of (q_e - y)^2, i.e.
 // 1 / (2B) where agents/iql.py sums the members; q = mean of member 0
-__global__ __launch_bounds__(FQL_THREADS) void fql_iqld_loss_critic_kernel(IqldCriticArgs P) {
-    __shared__ float sh[4];
+__device__ __forceinline__ void fql_iqld_loss_critic_body(const IqldCriticArgs& P, float* sh) {
     const float gs = 1.0f / (float)P.B;   // 2 / (2B)
     float sl = 0.f, sq = 0.f;
     for (int b = threadIdx.x; b < P.B; b += FQL_THREADS) {
@@ -118,6 +124,8 @@ __global__ __launch_bounds__(FQL_THREADS) void fql_iqld_loss_critic_kernel(IqldC
         P.info[IQLD_I_CRITIC + 1] = tq / (float)P.B;
     }
 }
+__global__ __launch_bounds__(FQL_THREADS) void fql_iqld_loss_critic_kernel(IqldCriticArgs P) { __shared__ float sh[4]; fql_iqld_loss_critic_body(P, sh); }
+__global__ __launch_bounds__(FQL_THREADS) void fql_iqld_loss_critic_multi_kernel(const IqldCriticArgs* __restrict__ args) { __shared__ float sh[4]; const IqldCriticArgs P = ((const FQL_CONST_AS IqldCriticArgs*)args)[blockIdx.y]; fql_iqld_loss_critic_body(P, sh); }
 
 struct IqldWeightArgs {
     const float *qa, *qb;      // [B, 16] column 0: the pair (target or online, stored parameters) at (obs, act)
@@ -134,9 +142,8 @@ struct IqldWeightArgs {
 // weights over (sum w + 1e-8).  The largest are selected by rank: rank(b) = #{j : w_j > w_b or (w_j == w_b and j < b)}, so exactly topk
 // rows are taken whatever the ties (equal weights contribute equal amounts: the sum is the sorted array's).  topk == 0 takes every row,
 // as sorted[-0:] does.  o is all ones in this family: o_mean, o_std, o_min, o_max = 1, 0, 1, 1.
-__global__ __launch_bounds__(FQL_THREADS) void fql_iqld_weight_kernel(IqldWeightArgs P) {
-    __shared__ float sh[4];
-    __shared__ float ws[2048];   // the weights of a batch of <= 2048 rows: the rank loop below reads each of them B times
+// ws: [2048] in LDS, the weights of a batch of <= 2048 rows: the rank loop below reads each of them B times
+__device__ __forceinline__ void fql_iqld_weight_body(const IqldWeightArgs& P, float* sh, float* ws) {
     const int B = P.B;
     float sq = 0.f, sp = 0.f, se = 0.f;
     for (int b = threadIdx.x; b < B; b += FQL_THREADS) {
@@ -194,6 +201,8 @@ __global__ __launch_bounds__(FQL_THREADS) void fql_iqld_weight_kernel(IqldWeight
         in[11] = tmx;                       // loss_weights_max
     }
 }
+__global__ __launch_bounds__(FQL_THREADS) void fql_iqld_weight_kernel(IqldWeightArgs P) { __shared__ float sh[4]; __shared__ float ws[2048]; fql_iqld_weight_body(P, sh, ws); }
+__global__ __launch_bounds__(FQL_THREADS) void fql_iqld_weight_multi_kernel(const IqldWeightArgs* __restrict__ args) { __shared__ float sh[4]; __shared__ float ws[2048]; const IqldWeightArgs P = ((const FQL_CONST_AS IqldWeightArgs*)args)[blockIdx.y]; fql_iqld_weight_body(P, sh, ws); }
 
 struct IqldActorLossArgs {
     const float* pred;         // [2B, ap]: rows [0, B) positive, [B, 2B) unconditional
@@ -206,8 +215,7 @@ struct IqldActorLossArgs {
 };
 // agents/iql_diffusion.py:180-189: lp_b = mean_a((vel - pred_pos)^2) w_b, lu_b = mean_a((vel - pred_unc)^2), loss = mean_b(lp + 0.1 lu).
 // dL/dpred_pos = -2 w_b (vel - pred) / (B act), dL/dpred_unc = -0.2 (vel - pred) / (B act).  One thread per row.
-__global__ __launch_bounds__(FQL_THREADS) void fql_iqld_loss_actor_kernel(IqldActorLossArgs P) {
-    __shared__ float sh[4];
+__device__ __forceinline__ void fql_iqld_loss_actor_body(const IqldActorLossArgs& P, float* sh) {
     const int B = P.B;
     const float gs = 2.0f / ((float)B * (float)P.ad);
     float sp = 0.f, su = 0.f, sl = 0.f;
@@ -238,6 +246,8 @@ __global__ __launch_bounds__(FQL_THREADS) void fql_iqld_loss_actor_kernel(IqldAc
         in[4] = tu / (float)B;   // actor_loss_uncond
     }
 }
+__global__ __launch_bounds__(FQL_THREADS) void fql_iqld_loss_actor_kernel(IqldActorLossArgs P) { __shared__ float sh[4]; fql_iqld_loss_actor_body(P, sh); }
+__global__ __launch_bounds__(FQL_THREADS) void fql_iqld_loss_actor_multi_kernel(const IqldActorLossArgs* __restrict__ args) { __shared__ float sh[4]; const IqldActorLossArgs P = ((const FQL_CONST_AS IqldActorLossArgs*)args)[blockIdx.y]; fql_iqld_loss_actor_body(P, sh); }
 
 struct IqldEmbedGradArgs {
     const float* dZ0;          // [2B, H]: gradient at layer 0's pre-activation
@@ -247,9 +257,8 @@ struct IqldEmbedGradArgs {
 };
 // The 32 embedding columns of a half are one constant row, so dEmbed[r] = (column sum over that half of dZ0) W0[embed rows]^T.
 // Workgroup 0 takes rows [0, B) (Embed[1]), workgroup 1 rows [B, 2B) (Embed[0]); the column sums run over b in rising order per thread,
-// the products over h in rising order.  H <= 1024.
-__global__ __launch_bounds__(FQL_THREADS) void fql_iqld_embed_grad_kernel(IqldEmbedGradArgs P) {
-    __shared__ float cs[1024];
+// the products over h in rising order.  H <= 1024.  cs: [1024] in LDS.  (The multi-instance grid is (2, members): blockIdx.x stays the half.)
+__device__ __forceinline__ void fql_iqld_embed_grad_body(const IqldEmbedGradArgs& P, float* cs) {
     const int half = blockIdx.x;
     const float* dz = P.dZ0 + (size_t)half * P.B * P.H;
     for (int h = threadIdx.x; h < P.H; h += FQL_THREADS) {
@@ -265,6 +274,8 @@ __global__ __launch_bounds__(FQL_THREADS) void fql_iqld_embed_grad_kernel(IqldEm
         P.g[(half == 0 ? IQLD_EMBED : 0) + threadIdx.x] = s;
     }
 }
+__global__ __launch_bounds__(FQL_THREADS) void fql_iqld_embed_grad_kernel(IqldEmbedGradArgs P) { __shared__ float cs[1024]; fql_iqld_embed_grad_body(P, cs); }
+__global__ __launch_bounds__(FQL_THREADS) void fql_iqld_embed_grad_multi_kernel(const IqldEmbedGradArgs* __restrict__ args) { __shared__ float cs[1024]; const IqldEmbedGradArgs P = ((const FQL_CONST_AS IqldEmbedGradArgs*)args)[blockIdx.y]; fql_iqld_embed_grad_body(P, cs); }
 
 struct IqldFinalizeArgs {
     DevState* st;              // the handle's state: the RNG step, and the counters of the critic and value TrainStates
@@ -280,9 +291,8 @@ struct IqldFinalizeArgs {
 // grad/max, grad/min, grad/norm over ONE TrainState's leaves (the reference merges {**critic_info, **value_info, **actor_info}: the
 // actor's statistics when it stepped, otherwise the value net's), from the per-chunk partials of that TrainState's Adam launch; the value
 // infos in the reference's order (value_loss, v, v_min, v_max); the per-TrainState counters and the RNG step.
-__global__ __launch_bounds__(FQL_THREADS) void fql_iqld_finalize_kernel(IqldFinalizeArgs A) {
-    __shared__ float sh[4];
-    __shared__ float leafn[256];
+// leafn: [256] in LDS.
+__device__ __forceinline__ void fql_iqld_finalize_body(const IqldFinalizeArgs& A, float* sh, float* leafn) {
     const int nl = A.leaf_hi - A.leaf_lo;
     float mx = -INFINITY, mn = INFINITY;
     if (nl > 0) {
@@ -324,6 +334,8 @@ __global__ __launch_bounds__(FQL_THREADS) void fql_iqld_finalize_kernel(IqldFina
         A.st_a->b1pow *= 0.9; A.st_a->b2pow *= 0.999;
     }
 }
+__global__ __launch_bounds__(FQL_THREADS) void fql_iqld_finalize_kernel(IqldFinalizeArgs A) { __shared__ float sh[4]; __shared__ float leafn[256]; fql_iqld_finalize_body(A, sh, leafn); }
+__global__ __launch_bounds__(FQL_THREADS) void fql_iqld_finalize_multi_kernel(const IqldFinalizeArgs* __restrict__ args) { __shared__ float sh[4]; __shared__ float leafn[256]; const IqldFinalizeArgs A = ((const FQL_CONST_AS IqldFinalizeArgs*)args)[blockIdx.y]; fql_iqld_finalize_body(A, sh, leafn); }
 
 // ---- sample_actions (agents/iql_diffusion.py:249-270) ----------------------------------------------------------------------------
 // BC's hoisted form with two halves: z0 = C0 + x W0[act rows] + c[i][half], C0 = obs W0[obs rows] + b0 shared by both halves, and
@@ -335,7 +347,7 @@ struct IqldStepBiasArgs {
     float* Cb;                 // [S, 2, H]
     int S, H;
 };
-__global__ __launch_bounds__(FQL_THREADS) void fql_iqld_stepbias_kernel(IqldStepBiasArgs P) {
+__device__ __forceinline__ void fql_iqld_stepbias_body(const IqldStepBiasArgs& P) {
     const int e = blockIdx.x * FQL_THREADS + threadIdx.x;
     if (e >= P.S * 2 * P.H) return;
     const int h = e % P.H, half = (e / P.H) & 1, i = e / (2 * P.H);
@@ -346,6 +358,8 @@ __global__ __launch_bounds__(FQL_THREADS) void fql_iqld_stepbias_kernel(IqldStep
     for (int j = 0; j < IQLD_EMBED; ++j) s = fmaf(row[j], P.W0e[(size_t)(BC_EMB + j) * P.H + h], s);
     P.Cb[e] = s;
 }
+__global__ __launch_bounds__(FQL_THREADS) void fql_iqld_stepbias_kernel(IqldStepBiasArgs P) { fql_iqld_stepbias_body(P); }
+__global__ __launch_bounds__(FQL_THREADS) void fql_iqld_stepbias_multi_kernel(const IqldStepBiasArgs* __restrict__ args) { const IqldStepBiasArgs P = ((const FQL_CONST_AS IqldStepBiasArgs*)args)[blockIdx.y]; fql_iqld_stepbias_body(P); }
 
 struct IqldLayer0Args {
     const float *C0, *A, *W0a, *cb;   // C0 [n_pad, H]; A [n_pad, ap]; W0a = row od of W0 (ad rows); cb = rows (i, 0) and (i, 1) of the step-bias table [2, H]
@@ -353,7 +367,7 @@ struct IqldLayer0Args {
     int n_pad, H, ad, ap;
 };
 // layer 0 of one Euler step for both halves: one thread per (row, column), the act terms in fixed order (as fql_bc_layer0_kernel)
-__global__ __launch_bounds__(FQL_THREADS) void fql_iqld_layer0_kernel(IqldLayer0Args P) {
+__device__ __forceinline__ void fql_iqld_layer0_body(const IqldLayer0Args& P) {
     const int e = blockIdx.x * FQL_THREADS + threadIdx.x;
     if (e >= 2 * P.n_pad * P.H) return;
     const int r = e / P.H, h = e - r * P.H;
@@ -363,6 +377,8 @@ __global__ __launch_bounds__(FQL_THREADS) void fql_iqld_layer0_kernel(IqldLayer0
     for (int a = 0; a < P.ad; ++a) s = fmaf(x[a], P.W0a[(size_t)a * P.H + h], s);
     P.G0[e] = gelu_f(s);
 }
+__global__ __launch_bounds__(FQL_THREADS) void fql_iqld_layer0_kernel(IqldLayer0Args P) { fql_iqld_layer0_body(P); }
+__global__ __launch_bounds__(FQL_THREADS) void fql_iqld_layer0_multi_kernel(const IqldLayer0Args* __restrict__ args) { const IqldLayer0Args P = ((const FQL_CONST_AS IqldLayer0Args*)args)[blockIdx.y]; fql_iqld_layer0_body(P); }
 
 struct IqldCfgStepArgs {
     const float* V;            // [2 n_pad, ap]: the head's output, positive half then unconditional half
@@ -403,13 +419,15 @@ struct IqldCfgRowsStepArgs {
     float dt;
 };
 // the last Euler step of a sweep program: fql_iqld_cfg_step_kernel with the row's own weight; x itself is not written back
-__global__ __launch_bounds__(FQL_THREADS) void fql_iqld_cfg_rows_step_kernel(IqldCfgRowsStepArgs P) {
+__device__ __forceinline__ void fql_iqld_cfg_rows_step_body(const IqldCfgRowsStepArgs& P) {
     const int e = blockIdx.x * FQL_THREADS + threadIdx.x;
     if (e >= P.n_pad * P.ad) return;
     const int r = e / P.ad, a = e - r * P.ad;
     const size_t o = (size_t)r * P.ap + a;
     P.tgt[o] = clip1(iqld_cfg_euler(P.X[o], P.V[o], P.V[(size_t)P.n_pad * P.ap + o], P.cfg[r], P.dt));
 }
+__global__ __launch_bounds__(FQL_THREADS) void fql_iqld_cfg_rows_step_kernel(IqldCfgRowsStepArgs P) { fql_iqld_cfg_rows_step_body(P); }
+__global__ __launch_bounds__(FQL_THREADS) void fql_iqld_cfg_rows_step_multi_kernel(const IqldCfgRowsStepArgs* __restrict__ args) { const IqldCfgRowsStepArgs P = ((const FQL_CONST_AS IqldCfgRowsStepArgs*)args)[blockIdx.y]; fql_iqld_cfg_rows_step_body(P); }
 
 struct IqldCfgLayer0Args {
     const float *C0, *V, *Xin, *cfg, *W0a, *cb;   // C0 [n_pad, H]; V [2 n_pad, ap]: the previous step's head output; Xin [n_pad, ap]; cfg [n_pad];
@@ -423,7 +441,7 @@ struct IqldCfgLayer0Args {
 // order, GELU).  One thread per (row, column) as there; every thread forms the ad values x_new[src][.] it multiplies (a wave reads one
 // row: the loads are broadcasts).  Xin is read and Xout written, so no thread reads what another writes; the positive half's threads
 // h, h + H, .. < ap store x_new (0 in the padding columns) for the next launch.
-__global__ __launch_bounds__(FQL_THREADS) void fql_iqld_cfg_layer0_kernel(IqldCfgLayer0Args P) {
+__device__ __forceinline__ void fql_iqld_cfg_layer0_body(const IqldCfgLayer0Args& P) {
     const int e = blockIdx.x * FQL_THREADS + threadIdx.x;
     if (e >= 2 * P.n_pad * P.H) return;
     const int r = e / P.H, h = e - r * P.H;
@@ -439,3 +457,5 @@ __global__ __launch_bounds__(FQL_THREADS) void fql_iqld_cfg_layer0_kernel(IqldCf
         for (int a = h; a < P.ap; a += P.H)
             P.Xout[(size_t)src * P.ap + a] = a < P.ad ? iqld_cfg_euler(x[a], vp[a], vu[a], c, P.dt) : 0.f;
 }
+__global__ __launch_bounds__(FQL_THREADS) void fql_iqld_cfg_layer0_kernel(IqldCfgLayer0Args P) { fql_iqld_cfg_layer0_body(P); }
+__global__ __launch_bounds__(FQL_THREADS) void fql_iqld_cfg_layer0_multi_kernel(const IqldCfgLayer0Args* __restrict__ args) { const IqldCfgLayer0Args P = ((const FQL_CONST_AS IqldCfgLayer0Args*)args)[blockIdx.y]; fql_iqld_cfg_layer0_body(P); }

@@ -12,6 +12,9 @@ Refused here, before the library is called: optimal_var 'softmax' / 'sampled_adv
 bc_agent), opt_decay_schedule 'cosine', an encoder, precision other than fp32, an activation other than GELU, goal conditioning and rng
 other than 'engine'.  Datasets, get/set_params and synchronize are FQLAgent's plumbing on the handle; checkpoints carry the reference's
 fields rng / critic / target_critic / value / actor (fql_amd/checkpoint.py).
+
+IQLDiffusionAgentGroup advances K such agents - one config but for seed, awr_temperature and softmax_beta - with one fused program per
+step kind and samples them in one fused call (fql_iqld_group_*).
 """
 from __future__ import annotations
 
@@ -20,7 +23,7 @@ import ctypes as C
 import numpy as np
 
 from . import _cabi
-from .agent import KindAgent, LazyInfo, _Arg, _PendingN
+from .agent import FQLAgent, KindAgent, LazyInfo, _Arg, _PendingN, _group_idx_arg, _group_sample_args
 from .bc import grid_index
 from .config import ConfigDict
 
@@ -378,4 +381,129 @@ class IQLDiffusionAgent(KindAgent):
         return int(la.value), int(ma.value), int(ls.value)
 
 
-__all__ = ['IQLDiffusionAgent', 'IQLD_INFO_KEYS', 'IQLD_ROW_KEYS', 'IQLD_NOISE_KEYS', 'OPTIMAL_VARS', 'info_keys', 'get_config']
+def group_cfgs(cfg, K, lead):
+    """The guidance weights of a group's fused sampling call as [K, n] (n = prod(lead)), checked before any library call: a scalar (every
+    member, every row), [K] (one per member) or [K, *lead] (one per member and row); every weight finite (check_cfgs)."""
+    n = int(np.prod(lead)) if lead else 1
+    c = as_array(cfg)
+    is_t = hasattr(c, 'data_ptr')
+    sh = tuple(int(d) for d in c.shape)
+    if sh == ():
+        c = c.reshape(1, 1).expand(K, n) if is_t else np.broadcast_to(np.asarray(c, dtype=np.float32).reshape(1, 1), (K, n))
+    elif sh == (K,) and sh != (K,) + tuple(lead):
+        c = c.reshape(K, 1).expand(K, n) if is_t else np.broadcast_to(np.asarray(c, dtype=np.float32).reshape(K, 1), (K, n))
+    elif sh != (K,) + tuple(lead):
+        raise ValueError(f'cfg must be a scalar, [{K}] (one guidance weight per member) or {(K,) + tuple(lead)} (one per row), got {sh}')
+    c = c.float() if is_t else np.asarray(c, dtype=np.float32)
+    return check_cfgs(c.reshape(K * n), K * n, 'member and row').reshape(K, n)
+
+
+class IQLDiffusionAgentGroup:
+    """K IQL-diffusion agents of one structure - the same config except `seed`, `awr_temperature` and `softmax_beta` - advanced by fused
+    update programs (include/fql_amd.h, fql_iqld_group_*): one per step kind, every launch carrying all K members' tasks.  The
+    softmax_beta x seed sweep of the reference's scripts on one device:
+
+        group = IQLDiffusionAgentGroup.create(seeds, ex_obs, ex_act, config, softmax_betas=[...])
+        group.upload_dataset(train_dataset)
+        for i in range(1, n + 1):
+            infos = group.update_from_dataset(update_critic=..., update_actor=..., want_info=(i % log_every == 0))
+        actions = group.sample_actions(observations, seed=i, cfg=3.0)   # [K, ..., act], one fused call
+
+    `members` are ordinary IQLDiffusionAgent objects; a member's trajectory is bitwise the one it has when trained alone with the same
+    seed, coefficients, rows and noise.  Members are state agents with precision 'fp32' and the engine's device RNG; while grouped their
+    batch size is fixed.  FQL agents are grouped by FQLAgentGroup, ReBRAC agents by ReBRACAgentGroup."""
+
+    def __init__(self, handle, members):
+        self._lib = _cabi.load()
+        self._g = handle
+        self.members = members
+        self.batch_size = int(members[0].config['batch_size'])
+        self._keep = None
+
+    @classmethod
+    def create(cls, seeds, ex_observations, ex_actions, config, awr_temperatures=None, softmax_betas=None):
+        seeds = [int(s) for s in seeds]
+        if not seeds:
+            raise ValueError('an agent group needs at least one seed')
+        cfg = get_config()
+        cfg.update(dict(config))
+        coef = {}
+        for key, vals, name in (('awr_temperature', awr_temperatures, 'awr_temperatures'), ('softmax_beta', softmax_betas, 'softmax_betas')):
+            coef[key] = [float(cfg[key])] * len(seeds) if vals is None else [float(a) for a in vals]
+            if len(coef[key]) != len(seeds):
+                raise ValueError(f'{len(seeds)} seeds but {len(coef[key])} {name}')
+        IQLDiffusionAgent._refuse_config(cfg)   # encoder, precision, rng: NotImplementedError before any library call
+        lib = _cabi.load()
+        members = []
+        for s, t, b in zip(seeds, coef['awr_temperature'], coef['softmax_beta']):
+            c = dict(cfg)
+            c['awr_temperature'], c['softmax_beta'] = t, b
+            members.append(IQLDiffusionAgent.create(s, ex_observations, ex_actions, c))
+        arr = (C.c_void_p * len(members))(*[m._h for m in members])
+        g = C.c_void_p()
+        _cabi.check(lib, None, lib.fql_iqld_group_create(arr, len(members), C.byref(g)))
+        return cls(g, members)
+
+    def _check(self, rc):
+        _cabi.check(self._lib, None, rc)
+
+    def upload_dataset(self, dataset, capacity=None):
+        """Every member gets its own device copy of `dataset` (IQLDiffusionAgent.upload_dataset)."""
+        for m in self.members:
+            m.upload_dataset(dataset, capacity=capacity)
+
+    def update_from_dataset(self, batch_size=None, idxs=None, want_info=False, update_critic=True, update_actor=True):
+        """One fused update of every member of the step kind (update_critic, update_actor): rows from each member's dataset (`idxs`
+        [K, B] int, host or device, or None = each member's device RNG), x_0 and t from each member's device RNG.  Returns a list of K
+        StepInfo keyed by info_keys(update_critic, update_actor) (want_info) or None."""
+        B = int(batch_size or self.batch_size)
+        if B != self.batch_size:
+            raise ValueError(f'batch_size {B}: the members of a group keep the batch size they were grouped with ({self.batch_size})')
+        ip, keep, stream = None, None, None
+        if idxs is not None:
+            keep, ip, stream = _group_idx_arg(self.members, idxs, B)
+        uc, ua = bool(update_critic), bool(update_actor)
+        self._check(self._lib.fql_iqld_group_update_from_dataset(self._g, ip, B, int(uc), int(ua), None, stream))
+        self._keep = keep
+        for m in self.members:
+            m._actor_steps += int(ua)
+        return [m._step_info(None, uc, ua, B) for m in self.members] if want_info else None
+
+    def sample_actions(self, observations, seed=None, cfg=1.0, noises=None):
+        """IQLDiffusionAgent.sample_actions of every member in ONE fused call (fql_iqld_group_sample_actions): result[i] is bitwise
+        what members[i].sample_actions(observations[i], seed=..., cfg=..., noises=noises[i]) returns.  `cfg`: a scalar, [K] (one
+        guidance weight per member) or [K, ...] (one per row: members[i].sample_actions_rows); every weight finite.  Shapes and seeds as
+        in FQLAgentGroup.sample_actions: observations [K, ..., od] or one shared block, noises [K, ..., ad] or None, seed None (each
+        member's own counter advances), one seed or K seeds.  Returns [K, ..., ad]."""
+        K = len(self.members)
+        c = as_array(cfg)
+        check_cfgs(c.reshape(-1), int(np.prod(c.shape)), 'entry')   # finite, whatever the shape: before a member's seed counter moves
+        o, z, seeds, n, out, optr, stream = _group_sample_args(self.members, observations, noises, seed, False)
+        w = _Arg(group_cfgs(c, K, tuple(int(d) for d in out.shape[1:-1])), (K, n))
+        self._check(self._lib.fql_iqld_group_sample_actions(self._g, o.ptr, n, z.ptr, seeds, w.ptr, optr, FQLAgent._stream([o, z, w])))
+        return out
+
+    def launches(self):
+        """Kernel launches of (the full, critic-only, actor-only and neither program, one fused sampling call on a single chunk)."""
+        la, s = (C.c_int64 * 4)(), C.c_int64(0)
+        self._check(self._lib.fql_iqld_group_stats(self._g, la, C.byref(s)))
+        return int(la[0]), int(la[1]), int(la[2]), int(la[3]), int(s.value)
+
+    def synchronize(self):
+        """Host wait for the group's last update or sampling call."""
+        self._check(self._lib.fql_group_synchronize(self._g))
+
+    def close(self):
+        """Destroy the fused programs; the members stay usable as standalone agents."""
+        if getattr(self, '_g', None):
+            self._lib.fql_group_destroy(self._g)
+            self._g = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+__all__ = ['IQLDiffusionAgent', 'IQLDiffusionAgentGroup', 'IQLD_INFO_KEYS', 'IQLD_ROW_KEYS', 'IQLD_NOISE_KEYS', 'OPTIMAL_VARS', 'info_keys', 'get_config']

@@ -636,7 +636,8 @@ int fql_iql_stats(fql_handle h, int64_t* launches_per_update, int64_t* macs_per_
  * fql_sample_actions, fql_flow_actions, fql_grad_buckets, frame uploads / updates, fql_replay_*, fql_update_balanced,
  * fql_noise_from_jax_keys, fql_read_info, fql_info_wait, fql_set_step (fql_iqld_set_steps writes both counter blocks), fql_set_grad_scale
  * and every other kind's calls return FQL_E_STATE, and fql_group_create with such a
- * member returns FQL_E_STATE.  The fql_iqld_* calls on another handle return FQL_E_STATE. */
+ * member still returns FQL_E_STATE: IQL-diffusion handles are grouped by fql_iqld_group_create (below), whose groups hold one fused
+ * program per step kind.  The fql_iqld_* calls on another handle return FQL_E_STATE. */
 #define FQL_IQLD_NUM_INFO 21
 typedef struct fql_iqld_config {
     float actor_lr, value_lr, critic_lr;  /* 3e-4 each                                                          */
@@ -679,6 +680,39 @@ int fql_iqld_set_steps(fql_handle h, const int64_t steps[3]);
 /* launches and algorithmic MACs of one update of that step kind; launches of one sampling call of <= 2048 observations */
 int fql_iqld_stats(fql_handle h, int update_critic, int update_actor, int64_t* launches_per_update, int64_t* macs_per_update,
                    int64_t* launches_per_sample);
+/* ---- IQL-diffusion agent groups: a softmax_beta / awr_temperature x seed sweep advanced by fused programs (agent groups, above) ----
+ * fql_iqld_group_create: `members` [k], k >= 1, IQL-diffusion handles (another kind: FQL_E_STATE naming it), distinct, in no group, the
+ * same batch size and the same fql_config / fql_iqld_config except awr_temperature, softmax_beta (and the create seed); anything else -
+ * optimal_var, expectile, target_extraction, a learning rate, a hidden size - is FQL_E_INVALID naming the member, *out NULL.  The group
+ * holds FOUR fused programs, each one graph with a member's lanes: the zip of every member's program of one step kind (full, critic-only,
+ * actor-only, neither; blockIdx.y = member in the agent's own kernels, concatenated task tables in the layers).  A member's numbers are
+ * bitwise those it has alone, and after a group update it behaves as after its own: fql_iqld_read_rows, fql_iqld_get_steps,
+ * fql_read_info_n, its own updates and sampling calls, module queries and checkpoints.  fql_group_destroy and fql_group_synchronize serve
+ * these groups too; fql_set_batch_size and fql_destroy on a member return FQL_E_STATE while it is grouped.  fql_group_create keeps
+ * refusing IQL-diffusion handles.  Errors: fql_last_error(NULL).
+ * Across kinds: the fql_group_* and fql_rebrac_group_* calls that take a group return FQL_E_STATE on an IQL-diffusion group, and the three
+ * calls below that take a group return it on an FQL or ReBRAC group, each naming the call that serves the group; a NULL group is
+ * FQL_E_INVALID. */
+int fql_iqld_group_create(const fql_handle* members, int k, fql_group* out);
+/* fql_iqld_update_from_dataset of every member in one fused update of the step kind (update_critic, update_actor).  idx: [k][B] int64,
+ * host or device, or NULL = each member's device RNG; x_0 and t are each member's Philox.  info21xk: [k][21] in fql_read_info_n's layout
+ * (the slots of a net that did not step are 0; device or host; host = synchronous) or NULL.  Every step kind advances each member's
+ * update counter, and only the Adam counts that kind advances alone; (0, 0) moves the RNG step and nothing else.  Stream and ordering
+ * as fql_group_update_from_dataset. */
+int fql_iqld_group_update_from_dataset(fql_group g, const int64_t* idx, int batch_size, int update_critic, int update_actor,
+                                       float* info21xk, void* stream);
+/* fql_iqld_sample_actions_cfgs of every member in one fused call.  observations [k][n][od], noises [k][n][act] or NULL (then seeds [k],
+ * each member's Philox), cfgs [k][n] (one guidance weight per member and row: a scalar cfg or one per member is that value repeated;
+ * host: every weight finite, else FQL_E_INVALID; or device), out [k][n][act]; host or device each.  Per chunk of <= 2048 observations
+ * per member: one assemble launch, the members' sweep program over concatenated task tables and [k] argument structs, one extract
+ * launch - the launch count of fql_sample_cfgs_stats, whatever k is.  out[i] is bitwise
+ * fql_iqld_sample_actions_cfgs(member i, ..., seeds[i], cfgs[i], ...), whose row j is fql_iqld_sample_actions at cfg = cfgs[i][j].
+ * Pointer kinds and ordering as fql_group_sample_actions. */
+int fql_iqld_group_sample_actions(fql_group g, const float* observations, int n, const float* noises, const uint64_t* seeds,
+                                  const float* cfgs, float* out, void* stream);
+/* Launches of the group's four programs - [0] full, [1] critic-only, [2] actor-only, [3] neither - and of one fused sampling call on a
+ * single chunk, counted from the built programs.  Either pointer may be NULL. */
+int fql_iqld_group_stats(fql_group g, int64_t launches[4], int64_t* launches_sample);
 
 /* ---- CFGRL (agents/cfgrl.py): classifier-free-guidance RL, a goal-conditioned flow policy.  State observations, fp32, GELU.
  * One ModuleDict TrainState (`network`), leaves in jax dict order:
