@@ -8,7 +8,7 @@ reference's eight keys.
 from .agent import FQLAgent, FQLAgentGroup, INFO_KEYS, NOISE_KEYS
 from .config import get_config
 from .datasets import Dataset, ReplayBuffer
-from .ifql import IFQLAgent, IFQL_INFO_KEYS
+from .ifql import IFQLAgent, IFQLAgentGroup, IFQL_INFO_KEYS
 from .rebrac import ReBRACAgent, ReBRACAgentGroup, REBRAC_INFO_KEYS, REBRAC_CRITIC_INFO_KEYS
 from .sac import SACAgent, SAC_INFO_KEYS
 from .bc import BCAgent, BC_INFO_KEYS, train_bc
@@ -19,5 +19,5 @@ from .cfgrl import CFGRLAgent, CFGRL_INFO_KEYS
 agents = dict(fql=FQLAgent, ifql=IFQLAgent, rebrac=ReBRACAgent, sac=SACAgent, bc=BCAgent, iql=IQLAgent,
               iql_diffusion=IQLDiffusionAgent, cfgrl=CFGRLAgent)
 
-__all__ = ['FQLAgent', 'FQLAgentGroup', 'IFQLAgent', 'ReBRACAgent', 'ReBRACAgentGroup', 'SACAgent', 'BCAgent', 'IQLAgent', 'IQLDiffusionAgent', 'IQLDiffusionAgentGroup', 'CFGRLAgent', 'train_bc', 'get_config', 'agents', 'INFO_KEYS', 'IFQL_INFO_KEYS',
+__all__ = ['FQLAgent', 'FQLAgentGroup', 'IFQLAgent', 'IFQLAgentGroup', 'ReBRACAgent', 'ReBRACAgentGroup', 'SACAgent', 'BCAgent', 'IQLAgent', 'IQLDiffusionAgent', 'IQLDiffusionAgentGroup', 'CFGRLAgent', 'train_bc', 'get_config', 'agents', 'INFO_KEYS', 'IFQL_INFO_KEYS',
            'REBRAC_INFO_KEYS', 'REBRAC_CRITIC_INFO_KEYS', 'SAC_INFO_KEYS', 'BC_INFO_KEYS', 'IQL_INFO_KEYS', 'IQLD_INFO_KEYS', 'CFGRL_INFO_KEYS', 'NOISE_KEYS', 'Dataset', 'ReplayBuffer']

@@ -839,10 +839,12 @@ class KindAgent(FQLAgent):
         return out
 
 
-def _group_sample_args(members, observations, noises, seed, flow):
-    """The shape rules of a group's fused sampling call (FQLAgentGroup, ReBRACAgentGroup), checked before any library call: observations
-    [K, ..., od] or one shared block without the leading K, noises [K, ..., ad] or None, seed None / one / K.  Returns what the library
+def _group_sample_args(members, observations, noises, seed, flow, per=()):
+    """The shape rules of a group's fused sampling call (FQLAgentGroup, ReBRACAgentGroup, ...), checked before any library call:
+    observations [K, ..., od] or one shared block without the leading K, noises [K, ..., ad] or None, seed None / one / K.  `per`: the
+    dims of a row's noise in front of ad (IFQLAgentGroup's best of N: (num_samples,), noises [K, ..., N, ad]).  Returns what the library
     call takes: (observations _Arg [K, n, od], noises _Arg, seeds array or None, n, out, out pointer, stream)."""
+    per = tuple(int(d) for d in per)
     K, cfg = len(members), members[0].config
     od, ad = int(cfg['ob_dims'][0]), int(cfg['action_dim'])
     is_t = hasattr(observations, 'data_ptr')
@@ -861,12 +863,12 @@ def _group_sample_args(members, observations, noises, seed, flow):
             raise ValueError(f'observations must lead with the {K} members: [{K}, ..., {od}], got {oshape}')
         shared = False
     elif zshape is not None:
-        shared = len(zshape) == len(oshape) + 1
+        shared = len(zshape) - len(per) == len(oshape) + 1
     else:
         shared = not (len(oshape) == 2 and oshape[0] == K)
     lead = oshape[:-1] if shared else oshape[1:-1]
-    if zshape is not None and zshape != (K,) + lead + (ad,):
-        raise ValueError(f'noises must be {(K,) + lead + (ad,)} for observations {oshape}, got {zshape}')
+    if zshape is not None and zshape != (K,) + lead + per + (ad,):
+        raise ValueError(f'noises must be {(K,) + lead + per + (ad,)} for observations {oshape}, got {zshape}')
     n = int(np.prod(lead)) if lead else 1
     if n < 1:
         raise ValueError(f'observations hold no rows: {oshape}')
@@ -882,7 +884,7 @@ def _group_sample_args(members, observations, noises, seed, flow):
     if shared:   # the same rows for every member: broadcast here, the library takes one block per member
         observations = (observations.unsqueeze(0).expand((K,) + oshape) if is_t else np.broadcast_to(observations, (K,) + oshape))
     o = _Arg(observations, (K, n, od))
-    z = _Arg(noises, (K, n, ad))
+    z = _Arg(noises, (K, n) + per + (ad,))
     out, optr = FQLAgent._actions_out(observations, (K,) + lead + (ad,))
     return o, z, seeds, n, out, optr, FQLAgent._stream([o, z])
 

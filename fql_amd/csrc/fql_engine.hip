@@ -6379,7 +6379,9 @@ int fql_update_from_frames(fql_handle h, const int64_t* idx, const int32_t* crop
 // A group has a kind: FQL members (fql_group_create), or ReBRAC members (fql_rebrac_group_create), whose group
 // holds a second fused program, the zip of the members' critic-only step, and a sampler that ends in ReBRAC's action kernel; or
 // IQL-diffusion members (fql_iqld_group_create), whose group holds one fused program per step kind (full,
-// critic-only, actor-only, neither) and a sampler that zips the members' sweep program: one guidance weight per row.
+// critic-only, actor-only, neither) and a sampler that zips the members' sweep program: one guidance weight per row; or IFQL members
+// (fql_ifql_group_create), whose group holds the one fused program and a best-of-N sampler that zips the members'
+// Euler flow and critic pair between the multi-instance forms of IFQL's three sampling kernels.
 // ================================================================================================
 namespace {
 
@@ -6432,6 +6434,10 @@ const std::map<const void*, MultiEntry>& multi_entries() {
         FQL_MULTI(fql_iqld_layer0_kernel, fql_iqld_layer0_multi_kernel, IqldLayer0Args);
         FQL_MULTI(fql_iqld_cfg_layer0_kernel, fql_iqld_cfg_layer0_multi_kernel, IqldCfgLayer0Args);
         FQL_MULTI(fql_iqld_cfg_rows_step_kernel, fql_iqld_cfg_rows_step_multi_kernel, IqldCfgRowsStepArgs);
+        // IFQL (fql_ifql.h): the update program (its value loss is entered above; the sampler's three kernels are bound by sample_ws_bon)
+        FQL_MULTI(fql_ifql_prep_kernel, fql_ifql_prep_multi_kernel, IfqlPrepArgs);
+        FQL_MULTI(fql_ifql_loss_critic_kernel, fql_ifql_loss_critic_multi_kernel, IfqlCriticArgs);
+        FQL_MULTI(fql_ifql_finalize_kernel, fql_ifql_finalize_multi_kernel, FinalizeArgs);
 #undef FQL_MULTI
         return e;
     }();
@@ -6463,7 +6469,7 @@ struct GProgram {
 
 struct fql_group_s {
     std::vector<fql_handle> m;
-    AgentKind kind = AgentKind::FQL;     // the members' kind: FQL (fql_group_create), ReBRAC (fql_rebrac_group_create) or IQL-diffusion (fql_iqld_group_create)
+    AgentKind kind = AgentKind::FQL;     // the members' kind: FQL (fql_group_create), ReBRAC (fql_rebrac_group_create), IQL-diffusion (fql_iqld_group_create) or IFQL (fql_ifql_group_create)
     int K = 0, B = 0;
     hipStream_t lanes[FQL_LANES] = {};   // lane 0 = the group's own stream
     // One fused program per entry of group_programs(kind), in its order.  [0]: the members' prog_full zipped (every kind); [1]: their
@@ -6588,10 +6594,13 @@ struct fql_group_s {
     struct Sample {
         int n_pad = 0;
         std::vector<GLaunch> os, flow;
+        std::vector<GLaunch> q;            // an IFQL group's best-of-N sampler: the members' critic pair (Eval::prog_q) zipped
         float *st_obs = nullptr, *st_noise = nullptr, *st_out = nullptr;
         unsigned char* d_args = nullptr;   // [K] AssembleArgs, then [K] ExtractArgs (a ReBRAC group: [K] RebracActArgs)
         Bound assemble, extract;           // the multi-instance launches over d_args, blockIdx.y = member
         Bound act;                         // a ReBRAC group: fql_rebrac_act_multi_kernel writes the actions, no extract launch
+        // an IFQL group's best-of-N sampler, over the other layout of d_args: [K] IfqlRepeatArgs, [K] IfqlQinArgs, [K] IfqlSelectArgs
+        Bound repeat, qin, select;
     };
     std::map<int, std::unique_ptr<Sample>> samples;
     // The chunks' argument structs travel through a ring of pinned host slots (the copy reads the slot when the stream reaches it): a
@@ -6603,9 +6612,11 @@ struct fql_group_s {
     char arg_state[kArgRing] = {};   // 0 = free, 1 = behind arg_ev, 2 = on the legacy stream
     int arg_pos = 0;
     // (a slot holds the layout of the group's kind: [K] AssembleArgs + [K] ExtractArgs, [K] AssembleArgs + [K] RebracActArgs, or an
-    // IQL-diffusion group's [K] BcAssembleArgs + [K] ExtractArgs)
+    // IQL-diffusion group's [K] BcAssembleArgs + [K] ExtractArgs; an IFQL group's flow call uses the first, its best-of-N call
+    // [K] IfqlRepeatArgs + [K] IfqlQinArgs + [K] IfqlSelectArgs)
     size_t asm_bytes() const { return kind == AgentKind::IQLD ? sizeof(BcAssembleArgs) : sizeof(AssembleArgs); }
-    size_t arg_bytes() const { return (size_t)K * (asm_bytes() + std::max(sizeof(ExtractArgs), sizeof(RebracActArgs))); }
+    size_t bon_bytes() const { return kind == AgentKind::IFQL ? sizeof(IfqlRepeatArgs) + sizeof(IfqlQinArgs) + sizeof(IfqlSelectArgs) : 0; }
+    size_t arg_bytes() const { return (size_t)K * std::max(asm_bytes() + std::max(sizeof(ExtractArgs), sizeof(RebracActArgs)), bon_bytes()); }
 
     Sample& sample_ws(int n_pad, bool flow) {
         std::unique_ptr<Sample>& slot = samples[n_pad];
@@ -6613,7 +6624,8 @@ struct fql_group_s {
             auto w = std::make_unique<Sample>();
             const int od = m[0]->cfg.obs_dim, ad = m[0]->cfg.act_dim;
             w->n_pad = n_pad;
-            w->os = zip_lane0([&](fql_engine& e) -> Program& { return e.get_eval(n_pad).prog_os; }, "the one-step sampler");
+            if (kind != AgentKind::IFQL)   // (an IFQL member's workspace has no one-step actor: its calls are the flow and best of N)
+                w->os = zip_lane0([&](fql_engine& e) -> Program& { return e.get_eval(n_pad).prog_os; }, "the one-step sampler");
             w->st_obs = (float*)galloc((size_t)K * n_pad * od * sizeof(float));
             w->st_noise = (float*)galloc((size_t)K * n_pad * ad * sizeof(float));
             w->st_out = (float*)galloc((size_t)K * n_pad * ad * sizeof(float));
@@ -6653,9 +6665,33 @@ struct fql_group_s {
         }
         return *slot;
     }
+    // An IFQL group's workspace of one chunk of n_pad padded SAMPLE rows per member (num_samples rows per observation): the flow
+    // workspace above - the same member workspace get_eval(n_pad) serves both calls - with the members' critic pair zipped and the
+    // multi-instance forms of the three launches fql_engine::sample_best_of_n puts around the two programs.  The staging blocks hold
+    // what a chunk needs: <= n_pad / N observations, <= n_pad noise rows.  select's grid covers the most observations a chunk of
+    // n_pad sample rows can hold; its workgroups past a chunk's own count return at once.
+    Sample& sample_ws_bon(int n_pad) {
+        Sample& w = sample_ws(n_pad, true);
+        if (w.q.empty()) {
+            const int N = m[0]->num_samples;
+            w.q = zip_lane0([&](fql_engine& e) -> Program& { return e.get_eval(n_pad).prog_q; }, "the best-of-N critic pair");
+            const unsigned char* d = w.d_args;
+            w.repeat = bind(fql_ifql_repeat_multi_kernel, Geo(dim3((n_pad + 3) / 4, K), dim3(FQL_THREADS), 0), (const IfqlRepeatArgs*)d);
+            d += (size_t)K * sizeof(IfqlRepeatArgs);
+            w.qin = bind(fql_ifql_qin_multi_kernel, Geo(dim3((n_pad + 3) / 4, K), dim3(FQL_THREADS), 0), (const IfqlQinArgs*)d);
+            d += (size_t)K * sizeof(IfqlQinArgs);
+            w.select = bind(fql_ifql_select_multi_kernel, Geo(dim3((std::max(1, n_pad / N) + 3) / 4, K), dim3(FQL_THREADS), 0), (const IfqlSelectArgs*)d);
+        }
+        return w;
+    }
     // launches of one fused sampling call on a single chunk, counted from the built program: assemble, the zipped launches, extract
+    // (an IFQL group's best-of-N call: repeat, the flow, qin, the critic pair, select)
     int64_t sample_launches(bool flow) {
         if (kind == AgentKind::IQLD) return 2 + (int64_t)sample_ws_cfg(16).flow.size();
+        if (kind == AgentKind::IFQL && !flow) {
+            Sample& w = sample_ws_bon(pad16(m[0]->num_samples));
+            return 3 + (int64_t)w.flow.size() + (int64_t)w.q.size();
+        }
         Sample& w = sample_ws(16, flow);
         return 2 + (int64_t)(flow ? w.flow : w.os).size();
     }
@@ -6729,14 +6765,21 @@ struct fql_group_s {
     // the zipped launches, the finishing launch, and a host result (host_out: the call's `out`, [K, n, ad]) copied out and waited for.
     void issue_chunk(Sample& w, const unsigned char* slot, std::vector<GLaunch>& zipped, const Bound& fin, bool host_inputs, float* host_out,
                      int n, int start, int mm, hipStream_t s) {
+        issue_chunk(w, slot, host_inputs, host_out, n, start, mm, s, [&] {
+            launch_bound(w.assemble, w.assemble.args.data(), s);
+            for (GLaunch& G : zipped) launch_bound(G.k, G.k.args.data(), s);
+            launch_bound(fin, fin.args.data(), s);
+        });
+    }
+    // (the same with the chunk's launches as a callable: an IFQL group's best-of-N chunk is five groups of launches, not three)
+    template <typename Launches>
+    void issue_chunk(Sample& w, const unsigned char* slot, bool host_inputs, float* host_out, int n, int start, int mm, hipStream_t s, Launches&& launches) {
         const int ad = m[0]->cfg.act_dim;
         HIP_CHECK(hipMemcpyAsync(w.d_args, slot, arg_bytes(), hipMemcpyHostToDevice, s));
         if (s == hipStreamLegacy) arg_state[arg_pos] = 2;
         else { HIP_CHECK(hipEventRecord(arg_ev[arg_pos], s)); arg_state[arg_pos] = 1; }
         if (host_inputs) HIP_CHECK(hipStreamSynchronize(s));
-        launch_bound(w.assemble, w.assemble.args.data(), s);
-        for (GLaunch& G : zipped) launch_bound(G.k, G.k.args.data(), s);
-        launch_bound(fin, fin.args.data(), s);
+        launches();
         HIP_CHECK(hipGetLastError());
         if (host_out) {
             copy_rows(host_out + (size_t)start * ad, (size_t)n * ad, w.st_out, (size_t)mm * ad, (size_t)mm * ad, hipMemcpyDeviceToHost, s);
@@ -6773,6 +6816,44 @@ struct fql_group_s {
                 if (half > mm) HIP_CHECK(hipMemsetAsync(ev.cfgs + mm, 0, (size_t)(half - mm) * sizeof(float), s));
             }
             issue_chunk(w, slot, w.flow, w.extract, !dev_obs || (noise && !dev_z) || !dev_c, dev_out ? nullptr : out, n, start, mm, s);
+        }
+    }
+
+    // An IFQL group (fql_ifql_group_sample_actions): fql_sample_actions of every member - best of num_samples - in one fused call.  Per
+    // chunk of <= 4096 SAMPLE rows per member - the member's own chunks (fql_engine::sample_chunks with SampleSpec{0, N}), its row numbers
+    // (row0 = start N) and its seed key, so a seeded draw is the member's own - repeat-multi, the zipped launches of the members' Euler
+    // flow, qin-multi, the zipped launches of their critic pair, select-multi, which writes the chunk's actions where the caller's `out`
+    // is device memory and into the staging block where it is not.  noise: [K, n, N, ad] or null.
+    void sample_bon(const float* obs, const float* noise, const uint64_t* seeds, int n, float* out, hipStream_t s) {
+        const int od = m[0]->cfg.obs_dim, ad = m[0]->cfg.act_dim, ap = pad16(ad), N = m[0]->num_samples;
+        const bool dev_obs = fql_engine::is_device_ptr(obs), dev_z = noise && fql_engine::is_device_ptr(noise), dev_out = fql_engine::is_device_ptr(out);
+        const int per = std::max(1, 4096 / N);
+        for (int start = 0; start < n; start += per) {
+            const int mm = std::min(per, n - start);
+            Sample& w = sample_ws_bon(pad16(mm * N));
+            const Rows o = chunk_rows(obs, dev_obs, w.st_obs, od, n, start, mm, s);
+            const Rows z = chunk_rows(noise, dev_z, w.st_noise, N * ad, n, start, mm, s);
+            unsigned char* slot = arg_slot();
+            IfqlRepeatArgs* ra = (IfqlRepeatArgs*)slot;
+            IfqlQinArgs* qa = (IfqlQinArgs*)(slot + (size_t)K * sizeof(IfqlRepeatArgs));
+            IfqlSelectArgs* sa = (IfqlSelectArgs*)(slot + (size_t)K * (sizeof(IfqlRepeatArgs) + sizeof(IfqlQinArgs)));
+            for (int i = 0; i < K; ++i) {
+                fql_engine& e = *m[i];
+                fql_engine::Eval& ev = e.get_eval(w.n_pad);
+                const float* oi = o.p + i * o.stride;
+                ra[i] = IfqlRepeatArgs{oi, z.p ? z.p + i * z.stride : nullptr, ev.Xf, e.seed, seeds ? seeds[i] : 0, mm, N, w.n_pad, od, ad,
+                                       e.nets[NET_BC].in_p(), start * N};
+                qa[i] = IfqlQinArgs{oi, ev.tgt, ev.Xq, mm, N, w.n_pad, od, ad, ap, e.nets[NET_C0].in_p()};
+                sa[i] = IfqlSelectArgs{ev.p_q[0].out, ev.p_q[1].out, ev.tgt, dev_out ? out + ((size_t)i * n + start) * ad : w.st_out + (size_t)i * mm * ad,
+                                       mm, N, ad, ap};
+            }
+            issue_chunk(w, slot, !dev_obs || (noise && !dev_z), dev_out ? nullptr : out, n, start, mm, s, [&] {
+                launch_bound(w.repeat, w.repeat.args.data(), s);
+                for (GLaunch& G : w.flow) launch_bound(G.k, G.k.args.data(), s);
+                launch_bound(w.qin, w.qin.args.data(), s);
+                for (GLaunch& G : w.q) launch_bound(G.k, G.k.args.data(), s);
+                launch_bound(w.select, w.select.args.data(), s);
+            });
         }
     }
 
@@ -6832,7 +6913,7 @@ struct fql_group_s {
 
 namespace {
 // The update programs a group of `kind` fuses (fql_group_s::progs, in this order): every kind's prog_full; ReBRAC's prog_critic (the
-// critic-only step) behind it; IQL-diffusion's four step kinds
+// critic-only step) behind it; IQL-diffusion's four step kinds.  IFQL has the one program.
 std::vector<Program fql_engine::*> group_programs(AgentKind kind) {
     std::vector<Program fql_engine::*> p{&fql_engine::prog_full};
     if (kind == AgentKind::REBRAC || kind == AgentKind::IQLD) p.push_back(&fql_engine::prog_critic);
@@ -6841,7 +6922,8 @@ std::vector<Program fql_engine::*> group_programs(AgentKind kind) {
 }
 // the members' restrictions and the structural identity of their programs (fql_group_create, fql_rebrac_group_create: `fn`).  What may
 // differ between members beside the create seed: FQL's alpha; ReBRAC's alpha_actor and alpha_critic; IQL-diffusion's awr_temperature and
-// softmax_beta (both reach the device as IqldWeightArgs::temp alone) - kernel arguments, not structure.
+// softmax_beta (both reach the device as IqldWeightArgs::temp alone); IFQL's expectile (IfqlValueArgs::expectile alone) - kernel arguments,
+// not structure.  An IFQL member's num_samples is structure: it sets the row count of the sampler's workspaces.
 void group_check(const char* fn, AgentKind kind, const fql_handle* members, int k) {
     if (!members || k <= 0) invalid("%s: members must be a non-empty array (k = %d)", fn, k);
     for (int i = 0; i < k; ++i) {
@@ -6866,9 +6948,11 @@ void group_check(const char* fn, AgentKind kind, const fql_handle* members, int 
             da.awr_temperature = db.awr_temperature = da.softmax_beta = db.softmax_beta = 0.f;
             same = same && std::memcmp(&da, &db, sizeof da) == 0;
         }
+        if (kind == AgentKind::IFQL) same = same && h->num_samples == members[0]->num_samples;
         if (!same)
             invalid("%s: member %d's config differs from member 0's in more than seed and %s", fn, i,
-                    kind == AgentKind::REBRAC ? "alpha_actor / alpha_critic" : kind == AgentKind::IQLD ? "awr_temperature / softmax_beta" : "alpha");
+                    kind == AgentKind::REBRAC ? "alpha_actor / alpha_critic" : kind == AgentKind::IQLD ? "awr_temperature / softmax_beta" :
+                    kind == AgentKind::IFQL ? "expectile" : "alpha");
         if (h->B != members[0]->B) invalid("%s: member %d has batch size %d, member 0 has %d", fn, i, h->B, members[0]->B);
         for (Program fql_engine::* pp : group_programs(kind)) {
             const Program& p = h->*pp, &p0 = members[0]->*pp;
@@ -6961,18 +7045,22 @@ int group_update(fql_group g, const char* fn, GProgram& gp, const int64_t* idx, 
     return FQL_OK;
 }
 // What a group call does, and the call of each kind of group that does it
-enum GroupCall { GC_UPDATE, GC_SAMPLE, GC_STATS };
+enum GroupCall { GC_UPDATE, GC_SAMPLE, GC_STATS, GC_FLOW };
 const char* group_call_of(AgentKind kind, GroupCall c) {
-    static const char* const fql[] = {"fql_group_update_from_dataset", "fql_group_sample_actions", "fql_group_sample_stats"};
-    static const char* const rebrac[] = {"the step kind is an argument: fql_rebrac_group_update_from_dataset", "fql_rebrac_group_sample_actions", "fql_rebrac_group_stats"};
-    static const char* const iqld[] = {"the step kind is two arguments: fql_iqld_group_update_from_dataset", "it takes guidance weights: fql_iqld_group_sample_actions", "fql_iqld_group_stats"};
-    return (kind == AgentKind::IQLD ? iqld : kind == AgentKind::REBRAC ? rebrac : fql)[c];
+    static const char* const fql[] = {"fql_group_update_from_dataset", "fql_group_sample_actions", "fql_group_sample_stats", "fql_group_flow_actions"};
+    static const char* const rebrac[] = {"the step kind is an argument: fql_rebrac_group_update_from_dataset", "fql_rebrac_group_sample_actions", "fql_rebrac_group_stats",
+                                         "the actor is deterministic: fql_rebrac_group_sample_actions"};
+    static const char* const iqld[] = {"the step kind is two arguments: fql_iqld_group_update_from_dataset", "it takes guidance weights: fql_iqld_group_sample_actions", "fql_iqld_group_stats",
+                                       "it takes guidance weights: fql_iqld_group_sample_actions"};
+    static const char* const ifql[] = {"fql_ifql_group_update_from_dataset", "best of num_samples: fql_ifql_group_sample_actions", "fql_ifql_group_stats", "fql_ifql_group_flow_actions"};
+    return (kind == AgentKind::IFQL ? ifql : kind == AgentKind::IQLD ? iqld : kind == AgentKind::REBRAC ? rebrac : fql)[c];
 }
 // A group call on a group of another kind: FQL_E_STATE, naming the call that serves it.  `kind`: the groups `fn` serves; `instead`: what
-// an FQL call says on a ReBRAC group and the reverse; with an IQL-diffusion group on either side, the group's own call for `c`.
+// an FQL call says on a ReBRAC group and the reverse; with an IQL-diffusion or IFQL group on either side, the group's own call for `c`.
 bool group_wrong_kind(fql_group g, AgentKind kind, const char* fn, const char* instead, GroupCall c) {
     if (g->kind == kind) return false;
-    if (g->kind == AgentKind::IQLD || kind == AgentKind::IQLD) instead = group_call_of(g->kind, c);
+    const auto later = [](AgentKind k) { return k == AgentKind::IQLD || k == AgentKind::IFQL; };
+    if (later(g->kind) || later(kind) || !instead) instead = group_call_of(g->kind, c);
     g_create_error = std::string(fn) + " is not available on a group of " + g->m[0]->desc().name + " agents (" + instead + ")";
     return true;
 }
@@ -6988,6 +7076,9 @@ int fql_rebrac_group_create(const fql_handle* members, int k, fql_group* out) {
 }
 int fql_iqld_group_create(const fql_handle* members, int k, fql_group* out) {
     return group_create("fql_iqld_group_create", AgentKind::IQLD, "IQL-diffusion groups take IQL-diffusion agents only", members, k, out);
+}
+int fql_ifql_group_create(const fql_handle* members, int k, fql_group* out) {
+    return group_create("fql_ifql_group_create", AgentKind::IFQL, "IFQL groups take IFQL agents only", members, k, out);
 }
 
 // Diagnostic only (not in include/fql_amd.h, beside fql_debug_plan): where each launch of an update program takes its tasks from, as int32 words
@@ -7076,11 +7167,20 @@ int fql_iqld_group_update_from_dataset(fql_group g, const int64_t* idx, int batc
     return group_update(g, fn, g->progs[kind], idx, batch_size, info21xk, stream, FQL_IQLD_NUM_INFO);
 }
 
+// fql_update_from_dataset of every IFQL member in one fused update: the zip of their prog_full; 12 infos per member
+int fql_ifql_group_update_from_dataset(fql_group g, const int64_t* idx, int batch_size, float* info12xk, void* stream) {
+    const char* fn = "fql_ifql_group_update_from_dataset";
+    if (!g) { g_create_error = std::string(fn) + ": NULL group"; return FQL_E_INVALID; }
+    if (group_wrong_kind(g, AgentKind::IFQL, fn, nullptr, GC_UPDATE)) return FQL_E_STATE;
+    return group_update(g, fn, g->progs[fql_group_s::FULL], idx, batch_size, info12xk, stream, FQL_IFQL_NUM_INFO);
+}
+
 // The members' sample_actions (flow: compute_flow_actions) in one fused call: fql_group_s::sample between the update's ordering rules
+// (an IFQL group's sample_actions is best of num_samples: fql_group_s::sample_bon)
 static int group_sample(fql_group g, const char* fn, AgentKind kind, const char* instead, bool flow, const float* obs, const float* noise,
                         const uint64_t* seeds, float temperature, int n, float* out, void* stream) {
     if (!g) { g_create_error = std::string(fn) + ": NULL group"; return FQL_E_INVALID; }
-    if (group_wrong_kind(g, kind, fn, instead, GC_SAMPLE)) return FQL_E_STATE;
+    if (group_wrong_kind(g, kind, fn, instead, flow ? GC_FLOW : GC_SAMPLE)) return FQL_E_STATE;
     try {
         if (n <= 0) invalid("%s: n must be positive (got %d)", fn, n);
         if (!obs || !out) invalid("%s: observations/out must not be NULL", fn);
@@ -7089,7 +7189,8 @@ static int group_sample(fql_group g, const char* fn, AgentKind kind, const char*
         if (!(temperature >= 0.0f)) invalid("%s: temperature must be >= 0", fn);
         if (g->member_began()) { g_create_error = std::string(fn) + ": a member is between fql_update_begin and fql_update_end"; return FQL_E_STATE; }
         const hipStream_t s = g->enter(stream);
-        g->sample(flow, obs, noise, seeds, temperature, n, out, s);
+        if (kind == AgentKind::IFQL && !flow) g->sample_bon(obs, noise, seeds, n, out, s);
+        else g->sample(flow, obs, noise, seeds, temperature, n, out, s);
         // a device result on the group's own stream: the caller has no handle to order its reads against, so finish here (as a member does)
         g->leave(s, !stream && fql_engine::is_device_ptr(out));
     } catch (const Invalid& e) {
@@ -7110,6 +7211,12 @@ int fql_group_flow_actions(fql_group g, const float* observations, const float* 
 int fql_rebrac_group_sample_actions(fql_group g, const float* observations, int n, const float* noises, const uint64_t* seeds, float temperature,
                                     float* out, void* stream) {
     return group_sample(g, "fql_rebrac_group_sample_actions", AgentKind::REBRAC, "fql_group_sample_actions", false, observations, noises, seeds, temperature, n, out, stream);
+}
+int fql_ifql_group_sample_actions(fql_group g, const float* observations, int n, const float* noises, const uint64_t* seeds, float* out, void* stream) {
+    return group_sample(g, "fql_ifql_group_sample_actions", AgentKind::IFQL, nullptr, false, observations, noises, seeds, 1.0f, n, out, stream);
+}
+int fql_ifql_group_flow_actions(fql_group g, const float* observations, const float* noises, int n, float* out, void* stream) {
+    return group_sample(g, "fql_ifql_group_flow_actions", AgentKind::IFQL, nullptr, true, observations, noises, nullptr, 1.0f, n, out, stream);
 }
 // fql_iqld_sample_actions_cfgs of every member in one fused call: fql_group_s::sample_cfg between the update's ordering rules
 int fql_iqld_group_sample_actions(fql_group g, const float* observations, int n, const float* noises, const uint64_t* seeds, const float* cfgs,
@@ -7172,6 +7279,23 @@ int fql_iqld_group_stats(fql_group g, int64_t launches[4], int64_t* launches_sam
     try {
         if (launches) for (int p = 0; p < fql_group_s::MAX_PROGS; ++p) launches[p] = (int64_t)g->progs[p].launches.size();
         if (launches_sample) *launches_sample = g->sample_launches(true);
+    } catch (const Invalid& e) {
+        g_create_error = e.msg; return FQL_E_INVALID;
+    } catch (const HipError& e) {
+        g_create_error = e.msg; return FQL_E_HIP;
+    }
+    return FQL_OK;
+}
+
+// Launches of an IFQL group's fused update program and of one fused best-of-N and one fused flow call on a single chunk, counted from
+// the built programs
+int fql_ifql_group_stats(fql_group g, int64_t* launches_update, int64_t* launches_sample, int64_t* launches_flow) {
+    if (!g) { g_create_error = "fql_ifql_group_stats: NULL group"; return FQL_E_INVALID; }
+    if (group_wrong_kind(g, AgentKind::IFQL, "fql_ifql_group_stats", nullptr, GC_STATS)) return FQL_E_STATE;
+    try {
+        if (launches_update) *launches_update = (int64_t)g->progs[fql_group_s::FULL].launches.size();
+        if (launches_sample) *launches_sample = g->sample_launches(false);
+        if (launches_flow) *launches_flow = g->sample_launches(true);
     } catch (const Invalid& e) {
         g_create_error = e.msg; return FQL_E_INVALID;
     } catch (const HipError& e) {

@@ -1,6 +1,8 @@
 // fql_ifql.h -- the kernels of the IFQL agent (agents/ifql.py) that FQL's kernels do not cover: batch assembly, the IQL value and
 // critic losses, the info layout of the finalize step, and best-of-N action selection.  The GEMM bodies, weight gradients,
 // LayerNorm backward, the flow-matching loss (fql_loss_bc_body), Adam + Polyak and the grad statistics are FQL's.
+// Every kernel an IFQL agent group fuses (fql_ifql_group_*) comes in three parts: a __device__ body, the by-value
+// entry a single handle launches, and a *_multi_kernel that takes a device array of the same argument struct, one per member.
 #pragma once
 #include "fql_kernels.h"
 
@@ -20,7 +22,7 @@ struct IfqlPrepArgs {
 // utils/datasets.py:64-100 (index draw + gather), agents/ifql.py:62-69 (x_0, t, x_t, vel): one wave per transition builds
 // X_v = [obs ; next_obs] (2B rows), X_c = [obs | act], X_bc = [obs | x_t | t], vel = act - x_0.  x_0 and t are the same Philox tensors
 // (2, 3) as FQL's BC-flow noise; explicit tensors replace them.
-__global__ __launch_bounds__(FQL_THREADS) void fql_ifql_prep_kernel(IfqlPrepArgs P) {
+__device__ __forceinline__ void fql_ifql_prep_body(const IfqlPrepArgs& P) {
     const SrcDesc& S = *P.src;
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int b = blockIdx.x * 4 + wave;
@@ -59,6 +61,11 @@ __global__ __launch_bounds__(FQL_THREADS) void fql_ifql_prep_kernel(IfqlPrepArgs
         P.w_mask[b] = S.mask[src];
     }
 }
+__global__ __launch_bounds__(FQL_THREADS) void fql_ifql_prep_kernel(IfqlPrepArgs P) { fql_ifql_prep_body(P); }
+// Multi-instance entry points (IFQL agent groups; the value loss below also IQL-diffusion's), here and below: blockIdx.y picks the member,
+// its argument struct comes from a device array, read through the constant address space (scalar loads, as from the kernel-argument
+// segment; fql_kernels.h FQL_CONST_AS).  Shared-memory arrays are declared in the entries and handed to the body.  Grid x = rows / 4.
+__global__ __launch_bounds__(FQL_THREADS) void fql_ifql_prep_multi_kernel(const IfqlPrepArgs* __restrict__ args) { const IfqlPrepArgs P = ((const FQL_CONST_AS IfqlPrepArgs*)args)[blockIdx.y]; fql_ifql_prep_body(P); }
 
 struct IfqlValueArgs {
     const float* v;            // [B, 16] column 0: value(obs) (rows 0..B-1 of the [obs ; next_obs] pass)
@@ -94,8 +101,6 @@ __device__ __forceinline__ void fql_ifql_loss_value_body(const IfqlValueArgs& P,
     }
 }
 __global__ __launch_bounds__(FQL_THREADS) void fql_ifql_loss_value_kernel(IfqlValueArgs P) { __shared__ float sh[4]; fql_ifql_loss_value_body(P, sh); }
-// Multi-instance entry point (IQL-diffusion agent groups, whose value loss this is): blockIdx.y picks the member, its argument struct
-// comes from a device array, read through the constant address space (fql_kernels.h FQL_CONST_AS)
 __global__ __launch_bounds__(FQL_THREADS) void fql_ifql_loss_value_multi_kernel(const IfqlValueArgs* __restrict__ args) { __shared__ float sh[4]; const IfqlValueArgs P = ((const FQL_CONST_AS IfqlValueArgs*)args)[blockIdx.y]; fql_ifql_loss_value_body(P, sh); }
 
 struct IfqlCriticArgs {
@@ -109,8 +114,7 @@ struct IfqlCriticArgs {
 };
 // agents/ifql.py:45-58: y = r + discount mask v(next_obs); loss = mean((q1 - y)^2 + (q2 - y)^2) (a SUM over the two members);
 // q_mean / q_max / q_min are statistics of y
-__global__ __launch_bounds__(FQL_THREADS) void fql_ifql_loss_critic_kernel(IfqlCriticArgs P) {
-    __shared__ float sh[4];
+__device__ __forceinline__ void fql_ifql_loss_critic_body(const IfqlCriticArgs& P, float* sh) {
     const float gs = 2.0f / (float)P.B;
     float sl = 0.f, sy = 0.f, mx = -INFINITY, mn = INFINITY;
     for (int b = threadIdx.x; b < P.B; b += FQL_THREADS) {
@@ -134,9 +138,12 @@ __global__ __launch_bounds__(FQL_THREADS) void fql_ifql_loss_critic_kernel(IfqlC
         P.st->info[IFQL_I_Q + 2] = tmn;
     }
 }
+__global__ __launch_bounds__(FQL_THREADS) void fql_ifql_loss_critic_kernel(IfqlCriticArgs P) { __shared__ float sh[4]; fql_ifql_loss_critic_body(P, sh); }
+__global__ __launch_bounds__(FQL_THREADS) void fql_ifql_loss_critic_multi_kernel(const IfqlCriticArgs* __restrict__ args) { __shared__ float sh[4]; const IfqlCriticArgs P = ((const FQL_CONST_AS IfqlCriticArgs*)args)[blockIdx.y]; fql_ifql_loss_critic_body(P, sh); }
 
 // FQL's finalize (grad statistics into slots 10-12 and the step counters when A.do_grad_stats), then the reference's IFQL order
-__global__ __launch_bounds__(FQL_THREADS) void fql_ifql_finalize_kernel(FinalizeArgs A) {
+// (fql_finalize_body declares the LDS it needs itself, sh[4] and leafn[256]: both entries get it through the inlined body)
+__device__ __forceinline__ void fql_ifql_finalize_body(const FinalizeArgs& A) {
     fql_finalize_body(A);
     if (threadIdx.x == 0) {
         float* in = A.st->info;
@@ -146,6 +153,8 @@ __global__ __launch_bounds__(FQL_THREADS) void fql_ifql_finalize_kernel(Finalize
         in[9] = gmax; in[10] = gmin; in[11] = gn; in[12] = 0.f;
     }
 }
+__global__ __launch_bounds__(FQL_THREADS) void fql_ifql_finalize_kernel(FinalizeArgs A) { fql_ifql_finalize_body(A); }
+__global__ __launch_bounds__(FQL_THREADS) void fql_ifql_finalize_multi_kernel(const FinalizeArgs* __restrict__ args) { const FinalizeArgs A = ((const FQL_CONST_AS FinalizeArgs*)args)[blockIdx.y]; fql_ifql_finalize_body(A); }
 
 // ---- sample_actions (agents/ifql.py:123-155) ------------------------------------------------------------------------------------
 struct IfqlRepeatArgs {
@@ -155,7 +164,7 @@ struct IfqlRepeatArgs {
     int n, N, n_pad, od, ad, inp;
     int row0;                  // index of this chunk's first row in the call (keys the Philox draw: chunking does not change the noise)
 };
-__global__ __launch_bounds__(FQL_THREADS) void fql_ifql_repeat_kernel(IfqlRepeatArgs P) {
+__device__ __forceinline__ void fql_ifql_repeat_body(const IfqlRepeatArgs& P) {
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int r = blockIdx.x * 4 + wave;
     if (r >= P.n_pad) return;
@@ -172,13 +181,15 @@ __global__ __launch_bounds__(FQL_THREADS) void fql_ifql_repeat_kernel(IfqlRepeat
         P.X[(size_t)r * P.inp + j] = v;
     }
 }
+__global__ __launch_bounds__(FQL_THREADS) void fql_ifql_repeat_kernel(IfqlRepeatArgs P) { fql_ifql_repeat_body(P); }
+__global__ __launch_bounds__(FQL_THREADS) void fql_ifql_repeat_multi_kernel(const IfqlRepeatArgs* __restrict__ args) { const IfqlRepeatArgs P = ((const FQL_CONST_AS IfqlRepeatArgs*)args)[blockIdx.y]; fql_ifql_repeat_body(P); }
 // critic input [obs_i | clip(flow action)] of every sample row
 struct IfqlQinArgs {
     const float *obs, *act;    // obs [n, od]; act [n_pad, ap] (clipped Euler result)
     float* X;                  // [n_pad, inp]
     int n, N, n_pad, od, ad, ap, inp;
 };
-__global__ __launch_bounds__(FQL_THREADS) void fql_ifql_qin_kernel(IfqlQinArgs P) {
+__device__ __forceinline__ void fql_ifql_qin_body(const IfqlQinArgs& P) {
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int r = blockIdx.x * 4 + wave;
     if (r >= P.n_pad) return;
@@ -192,6 +203,8 @@ __global__ __launch_bounds__(FQL_THREADS) void fql_ifql_qin_kernel(IfqlQinArgs P
         P.X[(size_t)r * P.inp + j] = v;
     }
 }
+__global__ __launch_bounds__(FQL_THREADS) void fql_ifql_qin_kernel(IfqlQinArgs P) { fql_ifql_qin_body(P); }
+__global__ __launch_bounds__(FQL_THREADS) void fql_ifql_qin_multi_kernel(const IfqlQinArgs* __restrict__ args) { const IfqlQinArgs P = ((const FQL_CONST_AS IfqlQinArgs*)args)[blockIdx.y]; fql_ifql_qin_body(P); }
 // best of N: q = min over the two critic members, the FIRST index of the largest q (jnp.argmax), its action.  One wave per observation
 // (wave64: the butterfly covers offsets 32 .. 1, cdna_hip_programming.md section 1); ties resolve to the lower index at every step.
 struct IfqlSelectArgs {
@@ -200,7 +213,7 @@ struct IfqlSelectArgs {
     float* out;                // [n, ad]
     int n, N, ad, ap;
 };
-__global__ __launch_bounds__(FQL_THREADS) void fql_ifql_select_kernel(IfqlSelectArgs P) {
+__device__ __forceinline__ void fql_ifql_select_body(const IfqlSelectArgs& P) {
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int i = blockIdx.x * 4 + wave;
     if (i >= P.n) return;
@@ -220,3 +233,5 @@ __global__ __launch_bounds__(FQL_THREADS) void fql_ifql_select_kernel(IfqlSelect
     if (bi == 0x7FFFFFFF) bi = 0;
     for (int a = lane; a < P.ad; a += 64) P.out[(size_t)i * P.ad + a] = P.act[((size_t)i * P.N + bi) * P.ap + a];
 }
+__global__ __launch_bounds__(FQL_THREADS) void fql_ifql_select_kernel(IfqlSelectArgs P) { fql_ifql_select_body(P); }
+__global__ __launch_bounds__(FQL_THREADS) void fql_ifql_select_multi_kernel(const IfqlSelectArgs* __restrict__ args) { const IfqlSelectArgs P = ((const FQL_CONST_AS IfqlSelectArgs*)args)[blockIdx.y]; fql_ifql_select_body(P); }

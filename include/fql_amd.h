@@ -350,7 +350,7 @@ void* fql_stream(fql_handle h);
  *   - alpha, q_agg and normalize_q_loss of fql_config are ignored.
  * Refused: encoder != 0 or precision != 0 at create (FQL_E_INVALID); on an IFQL handle fql_update_begin* / _end*, fql_grad_buckets, frame
  * uploads / updates, fql_noise_from_jax_keys, the replay ring and balanced sampling return FQL_E_STATE, and fql_group_create with an IFQL
- * member returns FQL_E_STATE. */
+ * member still returns FQL_E_STATE: IFQL handles are grouped by fql_ifql_group_create (below). */
 #define FQL_IFQL_NUM_INFO 12
 typedef struct fql_ifql_config {
     float expectile;      /* IQL expectile (0.9) */
@@ -359,6 +359,36 @@ typedef struct fql_ifql_config {
 } fql_ifql_config;
 void fql_ifql_default_config(fql_ifql_config* c);
 int fql_ifql_create(const fql_config* cfg, const fql_ifql_config* icfg, uint64_t seed, fql_handle* out);
+/* ---- IFQL agent groups: the seeds of one task, or an expectile x seed sweep, advanced by one fused program (agent groups, above) ----
+ * fql_ifql_group_create: `members` [k], k >= 1, IFQL handles (another kind: FQL_E_STATE naming it), distinct, in no group, the same batch
+ * size and the same fql_config / fql_ifql_config except expectile (and the create seed); anything else - num_samples, flow_steps, a
+ * hidden size, lr - is FQL_E_INVALID naming the member, *out NULL.  The group holds ONE fused program, one graph with a member's lanes:
+ * the zip of every member's update (blockIdx.y = member in IFQL's own kernels, concatenated task tables in the layers).  A member's
+ * numbers are bitwise those it has alone, and after a group update it behaves as after its own: fql_read_info, its own updates and
+ * sampling calls, fql_total_loss, module queries, parameter access and checkpoints.  fql_group_destroy and fql_group_synchronize serve
+ * these groups too; fql_set_batch_size and fql_destroy on a member return FQL_E_STATE while it is grouped.  fql_group_create keeps
+ * refusing IFQL handles.  Errors: fql_last_error(NULL).
+ * Across kinds: the fql_group_*, fql_rebrac_group_* and fql_iqld_group_* calls that take a group return FQL_E_STATE on an IFQL group, and
+ * the four calls below that take a group return it on a group of another kind, each naming the call that serves the group; a NULL group
+ * is FQL_E_INVALID. */
+int fql_ifql_group_create(const fql_handle* members, int k, fql_group* out);
+/* fql_update_from_dataset of every member in one fused update.  idx: [k][B] int64, host or device, or NULL = each member's device RNG;
+ * x_0 and t are each member's Philox.  info12xk: [k][12] in fql_handle_info_name's order (device or host; host = synchronous) or NULL.
+ * Stream and ordering as fql_group_update_from_dataset. */
+int fql_ifql_group_update_from_dataset(fql_group g, const int64_t* idx, int batch_size, float* info12xk, void* stream);
+/* fql_sample_actions of every member - best of num_samples - in one fused call.  observations [k][n][od], noises
+ * [k][n][num_samples][act] or NULL (then seeds [k], each member's Philox), out [k][n][act]; host or device each.  Per chunk of <= 4096
+ * sample rows per member (the member's own chunks and row numbers): one repeat launch, the members' Euler flow over concatenated task
+ * tables, one critic-input launch, the members' critic pair, one select launch, which writes the actions - 3 launches more than the two
+ * programs have, whatever k is.  out[i] is bitwise fql_sample_actions(member i, ..., seeds[i], ...).  Pointer kinds and ordering as
+ * fql_group_sample_actions. */
+int fql_ifql_group_sample_actions(fql_group g, const float* observations, int n, const float* noises, const uint64_t* seeds, float* out,
+                                  void* stream);
+/* fql_flow_actions of every member in one fused call: noises [k][n][act], required; everything else as fql_group_flow_actions. */
+int fql_ifql_group_flow_actions(fql_group g, const float* observations, const float* noises, int n, float* out, void* stream);
+/* Launches of the group's fused update program and of one fused best-of-N call and one fused flow call on a single chunk, counted from
+ * the built programs.  Any pointer may be NULL. */
+int fql_ifql_group_stats(fql_group g, int64_t* launches_update, int64_t* launches_sample, int64_t* launches_flow);
 /* infos per update of this handle: 13 (FQL) or 12 (IFQL); their names, NULL past fql_num_info */
 int fql_num_info(fql_handle h);
 const char* fql_handle_info_name(fql_handle h, int i);
