@@ -40,6 +40,10 @@ PATHS = {
     # act == the padded width 16: no padding column, no task 32 wide
     'act16': (29, 16, 256, H512, H512, {}, 180),
     'b16': (7, 3, 16, H64, H64, {}, 190),
+    # hidden widths that are no multiple of 16: out 50 of out_p 64, the value pass (M 64) on 32-row tiles and the B-row passes on the
+    # 16-row kernel; out 500 of out_p 512 (the width class of the best-of-N sampler's nets), LayerNorm over 500 of 512 columns
+    'w50_padded': (29, 8, 32, (50,) * 3, (50,) * 3, {}, 210),
+    'w500_padded': (29, 8, 64, (500,) * 4, (500,) * 4, {}, 220),
 }
 # one hidden-512 handle through these batch sizes: 32-row tiles, the mixed 64 / 32-row launch, the 16-row kernel, one tile, and back
 WALK = (29, 8, (256, 512, 272, 16, 256), 200)

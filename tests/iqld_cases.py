@@ -40,6 +40,7 @@ SHAPES = {
     'ad17-nh2': case(ad=17, nh=2, B=32, seed=43, te=0),
     'od5-S4': case(od=5, S=4, B=32, seed=44),
     'actor-hidden': case(B=32, seed=45, actor_hidden=(128, 64)),
+    'w50-padded': case(B=32, seed=46, hidden=(50, 50, 50)),   # widths that are no multiple of 16: out 50 of out_p 64 in all three nets
 }
 STEP_KINDS = case(seed=50)
 SWITCH = [case(B=64, seed=60), case(B=16, seed=61), case(B=256, seed=62)]   # one agent, the batch and noise of each size

@@ -39,6 +39,8 @@ PATHS = {
     # no LayerNorm anywhere, no tanh; OP_DGRAD0 with all 16 columns live
     'no_ln_h512_no_tanh': (29, 16, 256, H512, H512, dict(layer_norm=False, actor_layer_norm=False, tanh_squash=False), 7),
     'b16': (7, 3, 16, H64, H64, {}, 0),
+    # hidden widths that are no multiple of 16: out 50 of out_p 64, the 16-row kernel everywhere, the generic dgrad (K 64)
+    'w50_padded': (29, 8, 32, (50,) * 3, (50,) * 3, {}, 0),
 }
 # one hidden-512 handle through these batch sizes, full and critic-only steps in turn; the data seed of the walk
 WALK = (29, 8, (256, 512, 272, 16, 256), 1)

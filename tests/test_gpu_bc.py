@@ -376,6 +376,13 @@ def _p_wide1024(plan, B):
     assert _has(kbig, B, 1024, 1024) and _has(kbig, B, 16, 1024) and (B, 1024, 1024) in _wgrad(plan)
 
 
+def _p_w50_padded(plan, B):
+    g = _gemm(plan)
+    assert not [L for L in plan if L['type'] == OP_DGRAD0]
+    assert g and all(t['M'] == B and t['rows'] == 16 and t['kernel'] == K_GEMM16 and t['type'] == OP_GEMM for t in g)
+    assert _has(g, B, 64, 64) and (B, 64, 64) in _wgrad(plan) and B in {m for L in plan for m in L['ln']}   # out 50 of out_p 64
+
+
 H512_CASES = {   # id -> (od, ad, hidden, B, S, use_layer_norm, plan assertion)
     'humanoidmaze': (69, 21, (512,) * 4, 256, 16, 1, _p_humanoidmaze),
     'act16': (29, 16, (512,) * 4, 256, 16, 1, _p_act16),
@@ -383,6 +390,7 @@ H512_CASES = {   # id -> (od, ad, hidden, B, S, use_layer_norm, plan assertion)
     'b272': (29, 8, (512,) * 4, 272, 16, 1, _p_b272),
     'wide1024': (29, 8, (1024,) * 2, 48, 16, 1, _p_wide1024),
     'humanoidmaze-no-ln': (69, 21, (512,) * 4, 256, 16, 0, _p_humanoidmaze),
+    'w50-padded': (29, 8, (50, 50, 50), 32, 16, 1, _p_w50_padded),   # hidden widths that are no multiple of 16: LayerNorm over 50 of 64 columns
 }
 
 

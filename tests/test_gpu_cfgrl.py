@@ -285,6 +285,13 @@ def _p_ragged(plan, B):
     assert {(B, 128, 128), (B, 128, 64), (B, 64, 96), (B, 96, 16)} <= _wgrad(plan)
 
 
+def _p_w50_padded(plan, B):
+    g = _gemm(plan)
+    _no_input_gradient(plan, 128, 64)                            # 29 + 29 + 8 + 1 = 67
+    assert g and all(t['M'] == B and t['rows'] == 16 and t['kernel'] == K_GEMM16 and t['type'] == OP_GEMM for t in g)
+    assert _has(g, B, 64, 64) and (B, 64, 64) in _wgrad(plan) and B in {m for L in plan for m in L['ln']}   # out 50 of out_p 64
+
+
 H512_CASES = {   # id -> (od, gd, ad, hidden, B, actor_layer_norm, plan assertion)
     'humanoidmaze': (69, 69, 21, (512,) * 4, 256, True, _p_humanoidmaze),
     'humanoidmaze-no-ln': (69, 69, 21, (512,) * 4, 256, False, _p_humanoidmaze),
@@ -294,6 +301,7 @@ H512_CASES = {   # id -> (od, gd, ad, hidden, B, actor_layer_norm, plan assertio
     'b272': (29, 29, 8, (512,) * 4, 272, False, _p_b272),
     'wide1024': (29, 29, 8, (1024,) * 2, 48, False, _p_wide1024),
     'ragged': (29, 29, 8, (128, 64, 96), 32, True, _p_ragged),
+    'w50-padded': (29, 29, 8, (50, 50, 50), 32, True, _p_w50_padded),   # hidden widths that are no multiple of 16: LayerNorm over 50 of 64 columns
 }
 
 

@@ -81,6 +81,7 @@ PATHS = [
     pytest.param(17, 6, 16, (32,) * 4, dict(layer_norm=False), 4, 5, id='no_ln_b16'),        # empty LayerNorm-backward sub-table, minimum batch
     pytest.param(29, 8, 64, (256,) * 4, {}, 8, 5, id='k8'),                                  # eight members per table, blockIdx.y up to 7
     pytest.param(29, 8, 32, (1024,) * 3, {}, 2, 3, id='wide1024'),                           # fused tables through the K > 512 kernels
+    pytest.param(29, 8, 32, (50, 50, 50), {}, 2, 5, id='w50_padded'),                        # out 50 of out_p 64: LayerNorm widths and zeroed padding in fused tables
 ]
 
 

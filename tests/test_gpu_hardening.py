@@ -16,7 +16,7 @@ import numpy as np
 import pytest
 
 from oracle import fql_oracle as O
-from tests.util import assert_info_close, leaf_dict, make_problem, randomize_params
+from tests.util import assert_info_close, assert_initialised_like_the_reference, leaf_dict, make_problem, randomize_params
 
 pytestmark = pytest.mark.gpu
 
@@ -45,33 +45,7 @@ def test_create_initialises_like_the_reference():
     agents/fql.py:241-242 target_critic := critic; different seeds give different kernels."""
     cfg, ds, batch, noise = make_problem(29, 8, 256, (512, 512, 512, 512), seed=1)
     a0, a1 = _agent(cfg, batch, seed=0), _agent(cfg, batch, seed=1)
-    p0, p1 = a0.get_params(), a1.get_params()
-    n_kernel = 0
-    for path, w in O.tree_leaves_with_path(p0):
-        if path.endswith('/kernel'):
-            fan_in, fan_out = w.shape[-2], w.shape[-1]
-            lim = np.sqrt(6.0 / (fan_in + fan_out))
-            assert np.abs(w).max() <= lim * (1 + 1e-6), path
-            if w.size >= 4096:
-                assert np.abs(w).max() >= 0.98 * lim, path                       # the bound is attained, not a smaller box
-                assert abs(w.var() / (lim * lim / 3.0) - 1.0) < 0.05, (path, w.var())  # U(-lim, lim): variance lim^2 / 3
-                assert abs(w.mean()) < 4 * lim / np.sqrt(3 * w.size), path
-            if w.ndim == 3:   # ensemble members are drawn independently
-                assert np.abs(w[0] - w[1]).max() > 0.1 * lim, path
-            n_kernel += 1
-        elif 'LayerNorm' in path and path.endswith('/scale'):
-            np.testing.assert_array_equal(w, 1.0, err_msg=path)
-        else:   # Dense bias, LayerNorm bias
-            np.testing.assert_array_equal(w, 0.0, err_msg=path)
-    assert n_kernel == 20
-    for (path, a), (_, b) in zip(O.tree_leaves_with_path(p0['modules_critic']), O.tree_leaves_with_path(p0['modules_target_critic'])):
-        np.testing.assert_array_equal(a, b, err_msg=path)
-    k = 'modules_actor_bc_flow'
-    assert np.abs(leaf_dict(p0[k])['mlp/Dense_1/kernel'] - leaf_dict(p1[k])['mlp/Dense_1/kernel']).max() > 0.01
-    opt = a0.get_opt_state()
-    assert opt['count'] == 0 and opt['step'] == 1           # utils/flax_utils.py:81: TrainState.step starts at 1
-    for path, m in O.tree_leaves_with_path(opt['mu']):
-        assert not m.any(), path
+    assert_initialised_like_the_reference(a0.get_params(), a1.get_params(), a0.get_opt_state(), n_kernel=20)   # (tests/util.py: shared with the padded widths)
 
 
 def _workspace(agent, which, dtype=np.float32):

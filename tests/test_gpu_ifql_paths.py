@@ -137,8 +137,25 @@ def _p_b16(plan, B):
     assert B == 16
 
 
+def _p_w50_padded(plan, B):
+    g = _common(plan, B)
+    # out 50 of out_p 64: the value net's 2B = 64 rows on fql_side_kernel's 32-row tiles (LayerNorm partial sums over 50 of 64 columns),
+    # every B-row task on the 16-row kernel
+    assert plan_has(plan_gemm(plan, (K_SIDE,)), 2 * B, 64, 64, rows=32) and B in plan_ln(plan)
+    assert plan_has(g, B, 64, 64) and all(t['rows'] == 16 and t['kernel'] == K_GEMM16 for t in g if t['M'] == B)
+    assert (B, 64, 64) in {(t['M'], t['Kin'], t['N']) for t in plan_wgrad(plan)}
+
+
+def _p_w500_padded(plan, B):
+    g = _common(plan, B)
+    assert plan_has(g, 2 * B, 512, 512) and plan_has(g, B, 512, 512) and B in plan_ln(plan)   # out 500 of out_p 512
+    assert plan_has(plan_gemm(plan, (K_SIDE,)), 2 * B, 512, 512, rows=32)                 # LayerNorm partial sums over 500 valid columns
+    assert (B, 512, 512) in {(t['M'], t['Kin'], t['N']) for t in plan_wgrad(plan)}
+
+
 PROPERTY = {'b512_mixed': _p_b512_mixed, 'b272': _p_b272, 'b544_h64': _p_b544_h64, 'b1040_h64': _p_b1040_h64, 'b2048_h64': _p_b2048_h64,
-            'wide1024': _p_wide1024, 'obs600': _p_obs600, 'no_ln_h512': _p_no_ln_h512, 'act16': _p_act16, 'b16': _p_b16}
+            'wide1024': _p_wide1024, 'obs600': _p_obs600, 'no_ln_h512': _p_no_ln_h512, 'act16': _p_act16, 'b16': _p_b16,
+            'w50_padded': _p_w50_padded, 'w500_padded': _p_w500_padded}
 
 
 def _recorded(ref):

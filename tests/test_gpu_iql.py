@@ -174,6 +174,8 @@ SHAPE_CASES = {
     'ragged_depths': ((45, 24, 48, ((64, 64), (80, 48, 64))), {}, 2),
     # 256 + 16 rows: threads 0..15 take two rows, the rest one; two head-kernel blocks, the second 16 rows; M no multiple of 64
     'b272': ((11, 5, 272, ((64,) * 4, (64,) * 4)), {}, 2),
+    # hidden widths that are no multiple of 16: out 50 of out_p 64 in the value, critic and actor nets (LayerNorm over 50 of 64 columns)
+    'w50_padded': ((29, 8, 32, ((50,) * 3, (50,) * 3)), {}, 2),
 }
 
 # (case, actor_loss, const_std, seed).  Under ddpgbc with log_stds the |x| = 1 kink is cleared by IO.clear_of_unit_clip at the state
@@ -191,6 +193,7 @@ SHAPE_COMBOS = [
     ('obs50', 'awr', False, 0), ('obs50', 'ddpgbc', False, 0),
     ('ragged_depths', 'awr', False, 0), ('ragged_depths', 'ddpgbc', False, 0),
     ('b272', 'awr', False, 1), ('b272', 'ddpgbc', False, 2),
+    ('w50_padded', 'awr', False, 0), ('w50_padded', 'ddpgbc', False, 0),
 ]
 # the batch-size switch: one ddpgbc agent with log_stds, these batch sizes in turn (data seed SWITCH_SEED + step)
 SWITCH_SHAPE, SWITCH_BATCHES, SWITCH_SEED = (29, 8, 64, 64), (64, 16, 272, 64), 0

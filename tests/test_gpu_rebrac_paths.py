@@ -115,8 +115,15 @@ def _p_b16(plan, B):
     assert B == 16
 
 
+def _p_w50_padded(plan, B):
+    g = _common(plan, B)
+    _rows16_only(plan)
+    _dgrad0(plan, B, False)
+    assert plan_has(g, B, 64, 64) and B in plan_ln(plan)   # out 50 of out_p 64
+
+
 PROPERTY = {'b272': _p_b272, 'obs50': _p_obs50, 'b1040_h64': _p_b1040_h64, 'b2048_h64': _p_b2048_h64, 'wide1024': _p_wide1024,
-            'obs600': _p_obs600, 'no_ln_h512_no_tanh': _p_no_ln, 'b16': _p_b16}
+            'obs600': _p_obs600, 'no_ln_h512_no_tanh': _p_no_ln, 'b16': _p_b16, 'w50_padded': _p_w50_padded}
 
 
 def _recorded(ref):

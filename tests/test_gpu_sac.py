@@ -167,6 +167,8 @@ SHAPE_CASES = {
     'ragged_depths': (45, 24, 48, (64, 64), (80, 48, 64), dict(backup_entropy=True), 2, 1, 5),
     # 256 + 16 rows, 544 actor rows: M no multiple of 64; no tanh
     'b272': (11, 5, 272, (64,) * 4, (64,) * 4, dict(tanh_squash=False), 2, 1, 5),
+    # hidden widths that are no multiple of 16: out 50 of out_p 64 in the actor and the critics (LayerNorm over 50 of 64 columns)
+    'w50_padded': (29, 8, 32, (50,) * 3, (50,) * 3, {}, 2, 1, 5),
 }
 
 

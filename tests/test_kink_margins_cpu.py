@@ -95,7 +95,7 @@ def test_sac_shape_cases_keep_their_margins(case):
 def test_sac_shape_cases_cover_the_configurations_asked_for():
     kws = [c[5] for c in TS.SHAPE_CASES.values()]
     assert sum(kw.get('backup_entropy', False) for kw in kws) == 1 and sum(not kw.get('tanh_squash', True) for kw in kws) == 1
-    assert set(TS.SHAPE_CASES) == {'act16', 'humanoidmaze', 'b1024', 'ragged_depths', 'b272'}
+    assert set(TS.SHAPE_CASES) == {'act16', 'humanoidmaze', 'b1024', 'ragged_depths', 'b272', 'w50_padded'}
 
 
 # ---- ReBRAC: q1 = q2 at (obs, actor action) --------------------------------------------------------------------------------------------
@@ -167,8 +167,9 @@ def test_ifql_sampler_problems_at_hidden_512_have_clear_winners(N, n):
 
 
 def test_ifql_and_rebrac_case_tables_hold_the_cases_asked_for():
-    assert list(FC.PATHS) == ['b512_mixed', 'b272', 'b544_h64', 'b1040_h64', 'b2048_h64', 'wide1024', 'obs600', 'no_ln_h512', 'act16', 'b16']
-    assert list(RC.PATHS) == ['b272', 'obs50', 'b1040_h64', 'b2048_h64', 'wide1024', 'obs600', 'no_ln_h512_no_tanh', 'b16']
+    assert list(FC.PATHS) == ['b512_mixed', 'b272', 'b544_h64', 'b1040_h64', 'b2048_h64', 'wide1024', 'obs600', 'no_ln_h512', 'act16', 'b16',
+                              'w50_padded', 'w500_padded']
+    assert list(RC.PATHS) == ['b272', 'obs50', 'b1040_h64', 'b2048_h64', 'wide1024', 'obs600', 'no_ln_h512_no_tanh', 'b16', 'w50_padded']
     assert list(FC.SAMPLER_CASES) == [(1, 37), (7, 590), (65, 64)] and FC.SAMPLER_SHAPE[:2] == (69, 21)
     big = 1024 * 512 ** 2   # no new case costs more than the existing b1024 cases: B x H^2
     for table in (FC.PATHS, RC.PATHS):

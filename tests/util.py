@@ -49,6 +49,37 @@ def assert_same_state(a, b):
             np.testing.assert_array_equal(la[k], lb[k], err_msg=f'{part} {k}')
 
 
+def assert_initialised_like_the_reference(p0, p1, opt, n_kernel):
+    """get_params of two FQL agents created from seeds 0 and 1, and the first one's optimizer state: Glorot-uniform kernels from the real
+    fan-in and fan-out (the bound attained, the variance of U(-lim, lim)), ensemble members drawn independently, Dense biases 0,
+    LayerNorm (1, 0), target_critic := critic, different seeds different kernels, zero moments and the counters of a fresh TrainState."""
+    n = 0
+    for path, w in O.tree_leaves_with_path(p0):
+        if path.endswith('/kernel'):
+            fan_in, fan_out = w.shape[-2], w.shape[-1]
+            lim = np.sqrt(6.0 / (fan_in + fan_out))
+            assert np.abs(w).max() <= lim * (1 + 1e-6), path
+            if w.size >= 4096:
+                assert np.abs(w).max() >= 0.98 * lim, path                       # the bound is attained, not a smaller box
+                assert abs(w.var() / (lim * lim / 3.0) - 1.0) < 0.05, (path, w.var())  # U(-lim, lim): variance lim^2 / 3
+                assert abs(w.mean()) < 4 * lim / np.sqrt(3 * w.size), path
+            if w.ndim == 3:   # ensemble members are drawn independently
+                assert np.abs(w[0] - w[1]).max() > 0.1 * lim, path
+            n += 1
+        elif 'LayerNorm' in path and path.endswith('/scale'):
+            np.testing.assert_array_equal(w, 1.0, err_msg=path)
+        else:   # Dense bias, LayerNorm bias
+            np.testing.assert_array_equal(w, 0.0, err_msg=path)
+    assert n == n_kernel
+    for (path, a), (_, b) in zip(O.tree_leaves_with_path(p0['modules_critic']), O.tree_leaves_with_path(p0['modules_target_critic'])):
+        np.testing.assert_array_equal(a, b, err_msg=path)
+    k = 'modules_actor_bc_flow'
+    assert np.abs(leaf_dict(p0[k])['mlp/Dense_1/kernel'] - leaf_dict(p1[k])['mlp/Dense_1/kernel']).max() > 0.01
+    assert opt['count'] == 0 and opt['step'] == 1           # utils/flax_utils.py:81: TrainState.step starts at 1
+    for path, m in O.tree_leaves_with_path(opt['mu']):
+        assert not m.any(), path
+
+
 def assert_info_close(got, want, rtol=2e-5, atol=2e-6, keys=None):
     for k in (keys or O.INFO_KEYS):
         g, w = float(got[k]), float(want[k])
