@@ -950,7 +950,7 @@ class FQLAgentGroup:
         if cfg.get('agent_name') == 'sac':
             raise NotImplementedError('agent groups take FQL agents only (SAC groups are not available)')
         if cfg.get('agent_name') == 'iql':
-            raise NotImplementedError('agent groups take FQL agents only (IQL groups are not available)')
+            raise NotImplementedError('agent groups take FQL agents only (IQL agents are grouped by IQLAgentGroup)')
         if cfg.get('encoder') is not None:
             raise NotImplementedError('agent groups take state agents only (encoder=None)')
         if cfg.get('precision', 'fp32') not in ('fp32', 0):

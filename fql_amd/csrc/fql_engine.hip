@@ -6381,7 +6381,9 @@ int fql_update_from_frames(fql_handle h, const int64_t* idx, const int32_t* crop
 // IQL-diffusion members (fql_iqld_group_create), whose group holds one fused program per step kind (full,
 // critic-only, actor-only, neither) and a sampler that zips the members' sweep program: one guidance weight per row; or IFQL members
 // (fql_ifql_group_create), whose group holds the one fused program and a best-of-N sampler that zips the members'
-// Euler flow and critic pair between the multi-instance forms of IFQL's three sampling kernels.
+// Euler flow and critic pair between the multi-instance forms of IFQL's three sampling kernels; or IQL members (fql_iql_group_create;
+// DESIGN.md section 25), whose group holds the one fused program - IFQL's value and critic lanes beside the Gaussian actor's own
+// kernels - and a sampler that ends in the multi-instance form of IQL's sampling head.
 // ================================================================================================
 namespace {
 
@@ -6438,6 +6440,13 @@ const std::map<const void*, MultiEntry>& multi_entries() {
         FQL_MULTI(fql_ifql_prep_kernel, fql_ifql_prep_multi_kernel, IfqlPrepArgs);
         FQL_MULTI(fql_ifql_loss_critic_kernel, fql_ifql_loss_critic_multi_kernel, IfqlCriticArgs);
         FQL_MULTI(fql_ifql_finalize_kernel, fql_ifql_finalize_multi_kernel, FinalizeArgs);
+        // IQL (fql_iql.h; its value and critic losses are IFQL's, entered above; the sampler's head is bound by sample_ws)
+        FQL_MULTI(fql_iql_prep_kernel, fql_iql_prep_multi_kernel, IqlPrepArgs);
+        FQL_MULTI(fql_iql_head_kernel, fql_iql_head_multi_kernel, IqlHeadArgs);
+        FQL_MULTI(fql_iql_loss_awr_kernel, fql_iql_loss_awr_multi_kernel, IqlAwrArgs);
+        FQL_MULTI(fql_iql_loss_ddpgbc_kernel, fql_iql_loss_ddpgbc_multi_kernel, IqlDdpgArgs);
+        FQL_MULTI(fql_iql_actor_grad_kernel, fql_iql_actor_grad_multi_kernel, IqlActorGradArgs);
+        FQL_MULTI(fql_iql_finalize_kernel, fql_iql_finalize_multi_kernel, IqlFinalizeArgs);
 #undef FQL_MULTI
         return e;
     }();
@@ -6469,7 +6478,7 @@ struct GProgram {
 
 struct fql_group_s {
     std::vector<fql_handle> m;
-    AgentKind kind = AgentKind::FQL;     // the members' kind: FQL (fql_group_create), ReBRAC (fql_rebrac_group_create), IQL-diffusion (fql_iqld_group_create) or IFQL (fql_ifql_group_create)
+    AgentKind kind = AgentKind::FQL;     // the members' kind: FQL (fql_group_create), ReBRAC (fql_rebrac_group_create), IQL-diffusion (fql_iqld_group_create), IFQL (fql_ifql_group_create) or IQL (fql_iql_group_create)
     int K = 0, B = 0;
     hipStream_t lanes[FQL_LANES] = {};   // lane 0 = the group's own stream
     // One fused program per entry of group_programs(kind), in its order.  [0]: the members' prog_full zipped (every kind); [1]: their
@@ -6596,9 +6605,9 @@ struct fql_group_s {
         std::vector<GLaunch> os, flow;
         std::vector<GLaunch> q;            // an IFQL group's best-of-N sampler: the members' critic pair (Eval::prog_q) zipped
         float *st_obs = nullptr, *st_noise = nullptr, *st_out = nullptr;
-        unsigned char* d_args = nullptr;   // [K] AssembleArgs, then [K] ExtractArgs (a ReBRAC group: [K] RebracActArgs)
+        unsigned char* d_args = nullptr;   // [K] AssembleArgs, then [K] ExtractArgs (a ReBRAC group: [K] RebracActArgs; an IQL group: [K] IqlSampleArgs)
         Bound assemble, extract;           // the multi-instance launches over d_args, blockIdx.y = member
-        Bound act;                         // a ReBRAC group: fql_rebrac_act_multi_kernel writes the actions, no extract launch
+        Bound act;                         // a ReBRAC group: fql_rebrac_act_multi_kernel writes the actions, no extract launch; an IQL group: fql_iql_sample_multi_kernel
         // an IFQL group's best-of-N sampler, over the other layout of d_args: [K] IfqlRepeatArgs, [K] IfqlQinArgs, [K] IfqlSelectArgs
         Bound repeat, qin, select;
     };
@@ -6611,12 +6620,12 @@ struct fql_group_s {
     hipEvent_t arg_ev[kArgRing] = {};
     char arg_state[kArgRing] = {};   // 0 = free, 1 = behind arg_ev, 2 = on the legacy stream
     int arg_pos = 0;
-    // (a slot holds the layout of the group's kind: [K] AssembleArgs + [K] ExtractArgs, [K] AssembleArgs + [K] RebracActArgs, or an
-    // IQL-diffusion group's [K] BcAssembleArgs + [K] ExtractArgs; an IFQL group's flow call uses the first, its best-of-N call
-    // [K] IfqlRepeatArgs + [K] IfqlQinArgs + [K] IfqlSelectArgs)
+    // (a slot holds the layout of the group's kind: [K] AssembleArgs + [K] ExtractArgs, [K] AssembleArgs + [K] RebracActArgs, an IQL
+    // group's [K] AssembleArgs + [K] IqlSampleArgs, or an IQL-diffusion group's [K] BcAssembleArgs + [K] ExtractArgs; an IFQL group's
+    // flow call uses the first, its best-of-N call [K] IfqlRepeatArgs + [K] IfqlQinArgs + [K] IfqlSelectArgs)
     size_t asm_bytes() const { return kind == AgentKind::IQLD ? sizeof(BcAssembleArgs) : sizeof(AssembleArgs); }
     size_t bon_bytes() const { return kind == AgentKind::IFQL ? sizeof(IfqlRepeatArgs) + sizeof(IfqlQinArgs) + sizeof(IfqlSelectArgs) : 0; }
-    size_t arg_bytes() const { return (size_t)K * std::max(asm_bytes() + std::max(sizeof(ExtractArgs), sizeof(RebracActArgs)), bon_bytes()); }
+    size_t arg_bytes() const { return (size_t)K * std::max(asm_bytes() + std::max({sizeof(ExtractArgs), sizeof(RebracActArgs), sizeof(IqlSampleArgs)}), bon_bytes()); }
 
     Sample& sample_ws(int n_pad, bool flow) {
         std::unique_ptr<Sample>& slot = samples[n_pad];
@@ -6631,7 +6640,10 @@ struct fql_group_s {
             w->st_out = (float*)galloc((size_t)K * n_pad * ad * sizeof(float));
             w->d_args = (unsigned char*)galloc(arg_bytes());
             w->assemble = bind(fql_assemble_multi_kernel, Geo(dim3((n_pad + 3) / 4, K), dim3(FQL_THREADS), 0), (const AssembleArgs*)w->d_args);
-            if (kind != AgentKind::REBRAC)
+            if (kind == AgentKind::IQL)   // (grid x over the padded rows: a chunk's m <= n_pad, elements past m * ad return at once)
+                w->act = bind(fql_iql_sample_multi_kernel, Geo(dim3((n_pad * ad + FQL_THREADS - 1) / FQL_THREADS, K), dim3(FQL_THREADS), 0),
+                              (const IqlSampleArgs*)(w->d_args + (size_t)K * sizeof(AssembleArgs)));
+            else if (kind != AgentKind::REBRAC)
                 w->extract = bind(fql_extract_multi_kernel, Geo(dim3((n_pad * ad + 255) / 256, K), dim3(256), 0),
                                   (const ExtractArgs*)(w->d_args + (size_t)K * sizeof(AssembleArgs)));
             else
@@ -6685,7 +6697,8 @@ struct fql_group_s {
         return w;
     }
     // launches of one fused sampling call on a single chunk, counted from the built program: assemble, the zipped launches, extract
-    // (an IFQL group's best-of-N call: repeat, the flow, qin, the critic pair, select)
+    // (a ReBRAC or IQL group: the kind's action kernel in extract's place; an IFQL group's best-of-N call: repeat, the flow, qin, the
+    // critic pair, select)
     int64_t sample_launches(bool flow) {
         if (kind == AgentKind::IQLD) return 2 + (int64_t)sample_ws_cfg(16).flow.size();
         if (kind == AgentKind::IFQL && !flow) {
@@ -6728,9 +6741,11 @@ struct fql_group_s {
     // host or device each.  A host result is copied out and waited for per chunk.
     // A ReBRAC group (fql_rebrac_group_sample_actions): assemble-multi of [obs | 0], the zipped launches of the actor's forward, then
     // fql_rebrac_act_multi_kernel, which writes the actions where extract-multi would - every argument as fql_engine::sample_actor fills it.
+    // An IQL group (fql_iql_group_sample_actions): the same two launches around the actor's forward, then fql_iql_sample_multi_kernel on the
+    // means - each member's own row numbers (row0 = start), seed, key and log_stds (P + ls_off, null under const_std), one temperature.
     void sample(bool flow, const float* obs, const float* noise, const uint64_t* seeds, float temperature, int n, float* out, hipStream_t s) {
         const int od = m[0]->cfg.obs_dim, ad = m[0]->cfg.act_dim, ap = pad16(ad);
-        const bool rebrac = kind == AgentKind::REBRAC;
+        const bool rebrac = kind == AgentKind::REBRAC, iql = kind == AgentKind::IQL;
         const bool dev_obs = fql_engine::is_device_ptr(obs), dev_z = noise && fql_engine::is_device_ptr(noise), dev_out = fql_engine::is_device_ptr(out);
         for (int start = 0; start < n; start += 4096) {
             const int mm = std::min(4096, n - start);
@@ -6741,23 +6756,27 @@ struct fql_group_s {
             AssembleArgs* aa = (AssembleArgs*)slot;
             ExtractArgs* ea = (ExtractArgs*)(slot + (size_t)K * sizeof(AssembleArgs));
             RebracActArgs* ra = (RebracActArgs*)(slot + (size_t)K * sizeof(AssembleArgs));
+            IqlSampleArgs* qa = (IqlSampleArgs*)(slot + (size_t)K * sizeof(AssembleArgs));
             for (int i = 0; i < K; ++i) {
                 fql_engine& e = *m[i];
                 fql_engine::Eval& ev = e.get_eval(w.n_pad);
-                if (rebrac) {
+                if (rebrac || iql) {
                     const uint64_t sd = seeds ? seeds[i] : 0;
                     const float* zi = z.p ? z.p + i * z.stride : nullptr;
                     float* dst = dev_out ? out + ((size_t)i * n + start) * ad : w.st_out + (size_t)i * mm * ad;
                     aa[i] = AssembleArgs{o.p + i * o.stride, nullptr, ev.X, e.seed, sd, mm, w.n_pad, od, 0, e.nets[NET_BC].in_p()};   // [obs | 0]
-                    ra[i] = RebracActArgs{ev.p_os.out, zi, dst, e.seed, sd, mm, ad, ap, ad, ad, 0, start, zi ? 1 : 2, e.rcfg.tanh_squash, 1,
-                                          e.rcfg.actor_noise * temperature, e.rcfg.actor_noise_clip};
+                    if (iql)
+                        qa[i] = IqlSampleArgs{ev.p_os.out, e.qcfg.const_std ? nullptr : e.P + e.ls_off, zi, dst, e.seed, sd, mm, ad, ap, start, temperature};
+                    else
+                        ra[i] = RebracActArgs{ev.p_os.out, zi, dst, e.seed, sd, mm, ad, ap, ad, ad, 0, start, zi ? 1 : 2, e.rcfg.tanh_squash, 1,
+                                              e.rcfg.actor_noise * temperature, e.rcfg.actor_noise_clip};
                     continue;
                 }
                 aa[i] = AssembleArgs{o.p + i * o.stride, z.p ? z.p + i * z.stride : nullptr, flow ? ev.Xf : ev.X, e.seed,
                                      (seeds ? seeds[i] : 0) + (uint64_t)start, mm, w.n_pad, od, ad, flow ? e.nets[NET_BC].in_p() : e.nets[NET_OS].in_p()};
                 ea[i] = ExtractArgs{flow ? ev.tgt : ev.p_os.out, dev_out ? out + ((size_t)i * n + start) * ad : w.st_out + (size_t)i * mm * ad, mm, ad, ap};
             }
-            issue_chunk(w, slot, flow ? w.flow : w.os, rebrac ? w.act : w.extract, !dev_obs || (noise && !dev_z), dev_out ? nullptr : out, n, start, mm, s);
+            issue_chunk(w, slot, flow ? w.flow : w.os, rebrac || iql ? w.act : w.extract, !dev_obs || (noise && !dev_z), dev_out ? nullptr : out, n, start, mm, s);
         }
     }
     // The tail of a chunk of either sampler: the slot's argument structs to the device with the ring's event behind them, the wait that
@@ -6913,7 +6932,7 @@ struct fql_group_s {
 
 namespace {
 // The update programs a group of `kind` fuses (fql_group_s::progs, in this order): every kind's prog_full; ReBRAC's prog_critic (the
-// critic-only step) behind it; IQL-diffusion's four step kinds.  IFQL has the one program.
+// critic-only step) behind it; IQL-diffusion's four step kinds.  IFQL and IQL have the one program.
 std::vector<Program fql_engine::*> group_programs(AgentKind kind) {
     std::vector<Program fql_engine::*> p{&fql_engine::prog_full};
     if (kind == AgentKind::REBRAC || kind == AgentKind::IQLD) p.push_back(&fql_engine::prog_critic);
@@ -6923,7 +6942,9 @@ std::vector<Program fql_engine::*> group_programs(AgentKind kind) {
 // the members' restrictions and the structural identity of their programs (fql_group_create, fql_rebrac_group_create: `fn`).  What may
 // differ between members beside the create seed: FQL's alpha; ReBRAC's alpha_actor and alpha_critic; IQL-diffusion's awr_temperature and
 // softmax_beta (both reach the device as IqldWeightArgs::temp alone); IFQL's expectile (IfqlValueArgs::expectile alone) - kernel arguments,
-// not structure.  An IFQL member's num_samples is structure: it sets the row count of the sampler's workspaces.
+// not structure.  An IFQL member's num_samples is structure: it sets the row count of the sampler's workspaces.  IQL's expectile and
+// alpha are arguments (IfqlValueArgs::expectile; IqlAwrArgs / IqlDdpgArgs / IqlActorGradArgs::alpha); its actor_loss and const_std are
+// structure: they choose the launches and the log_stds leaf.
 void group_check(const char* fn, AgentKind kind, const fql_handle* members, int k) {
     if (!members || k <= 0) invalid("%s: members must be a non-empty array (k = %d)", fn, k);
     for (int i = 0; i < k; ++i) {
@@ -6949,10 +6970,15 @@ void group_check(const char* fn, AgentKind kind, const fql_handle* members, int 
             same = same && std::memcmp(&da, &db, sizeof da) == 0;
         }
         if (kind == AgentKind::IFQL) same = same && h->num_samples == members[0]->num_samples;
+        if (kind == AgentKind::IQL) {
+            fql_iql_config qa = h->qcfg, qb = members[0]->qcfg;
+            qa.expectile = qb.expectile = qa.alpha = qb.alpha = 0.f;
+            same = same && std::memcmp(&qa, &qb, sizeof qa) == 0;
+        }
         if (!same)
             invalid("%s: member %d's config differs from member 0's in more than seed and %s", fn, i,
                     kind == AgentKind::REBRAC ? "alpha_actor / alpha_critic" : kind == AgentKind::IQLD ? "awr_temperature / softmax_beta" :
-                    kind == AgentKind::IFQL ? "expectile" : "alpha");
+                    kind == AgentKind::IFQL ? "expectile" : kind == AgentKind::IQL ? "expectile / alpha" : "alpha");
         if (h->B != members[0]->B) invalid("%s: member %d has batch size %d, member 0 has %d", fn, i, h->B, members[0]->B);
         for (Program fql_engine::* pp : group_programs(kind)) {
             const Program& p = h->*pp, &p0 = members[0]->*pp;
@@ -7018,7 +7044,8 @@ int group_create(const char* fn, AgentKind kind, const char* want, const fql_han
 }
 
 // One fused update of every member: `gp` is the group's program for the step's kind.  fn: the entry point, for its messages.
-// infos: [k][n_info] - 13 floats of DevState::info, or an IQL-diffusion member's 21 of its own buffer (fql_engine::info_src).
+// infos: [k][n_info] - 13 floats of DevState::info, or an IQL-diffusion member's 21 or an IQL member's 16 or 19 of its own buffer
+// (fql_engine::info_src).
 int group_update(fql_group g, const char* fn, GProgram& gp, const int64_t* idx, int batch_size, float* info13xk, void* stream, int n_info = FQL_NUM_INFO) {
     try {
         if (batch_size != g->B) invalid("%s: batch_size %d does not match the members' %d", fn, batch_size, g->B);
@@ -7053,13 +7080,15 @@ const char* group_call_of(AgentKind kind, GroupCall c) {
     static const char* const iqld[] = {"the step kind is two arguments: fql_iqld_group_update_from_dataset", "it takes guidance weights: fql_iqld_group_sample_actions", "fql_iqld_group_stats",
                                        "it takes guidance weights: fql_iqld_group_sample_actions"};
     static const char* const ifql[] = {"fql_ifql_group_update_from_dataset", "best of num_samples: fql_ifql_group_sample_actions", "fql_ifql_group_stats", "fql_ifql_group_flow_actions"};
-    return (kind == AgentKind::IFQL ? ifql : kind == AgentKind::IQLD ? iqld : kind == AgentKind::REBRAC ? rebrac : fql)[c];
+    static const char* const iql[] = {"fql_iql_group_update_from_dataset", "it takes a temperature: fql_iql_group_sample_actions", "fql_iql_group_stats",
+                                      "the actor is a Gaussian, there is no flow: fql_iql_group_sample_actions"};
+    return (kind == AgentKind::IQL ? iql : kind == AgentKind::IFQL ? ifql : kind == AgentKind::IQLD ? iqld : kind == AgentKind::REBRAC ? rebrac : fql)[c];
 }
 // A group call on a group of another kind: FQL_E_STATE, naming the call that serves it.  `kind`: the groups `fn` serves; `instead`: what
-// an FQL call says on a ReBRAC group and the reverse; with an IQL-diffusion or IFQL group on either side, the group's own call for `c`.
+// an FQL call says on a ReBRAC group and the reverse; with an IQL-diffusion, IFQL or IQL group on either side, the group's own call for `c`.
 bool group_wrong_kind(fql_group g, AgentKind kind, const char* fn, const char* instead, GroupCall c) {
     if (g->kind == kind) return false;
-    const auto later = [](AgentKind k) { return k == AgentKind::IQLD || k == AgentKind::IFQL; };
+    const auto later = [](AgentKind k) { return k == AgentKind::IQLD || k == AgentKind::IFQL || k == AgentKind::IQL; };
     if (later(g->kind) || later(kind) || !instead) instead = group_call_of(g->kind, c);
     g_create_error = std::string(fn) + " is not available on a group of " + g->m[0]->desc().name + " agents (" + instead + ")";
     return true;
@@ -7079,6 +7108,9 @@ int fql_iqld_group_create(const fql_handle* members, int k, fql_group* out) {
 }
 int fql_ifql_group_create(const fql_handle* members, int k, fql_group* out) {
     return group_create("fql_ifql_group_create", AgentKind::IFQL, "IFQL groups take IFQL agents only", members, k, out);
+}
+int fql_iql_group_create(const fql_handle* members, int k, fql_group* out) {
+    return group_create("fql_iql_group_create", AgentKind::IQL, "IQL groups take IQL agents only", members, k, out);
 }
 
 // Diagnostic only (not in include/fql_amd.h, beside fql_debug_plan): where each launch of an update program takes its tasks from, as int32 words
@@ -7175,6 +7207,15 @@ int fql_ifql_group_update_from_dataset(fql_group g, const int64_t* idx, int batc
     return group_update(g, fn, g->progs[fql_group_s::FULL], idx, batch_size, info12xk, stream, FQL_IFQL_NUM_INFO);
 }
 
+// fql_iql_update_from_dataset of every IQL member in one fused update: the zip of their prog_full; 16 (awr) or 19 (ddpgbc) infos per
+// member, out of each member's own info buffer (fql_engine::info_src)
+int fql_iql_group_update_from_dataset(fql_group g, const int64_t* idx, int batch_size, float* infoNxk, void* stream) {
+    const char* fn = "fql_iql_group_update_from_dataset";
+    if (!g) { g_create_error = std::string(fn) + ": NULL group"; return FQL_E_INVALID; }
+    if (group_wrong_kind(g, AgentKind::IQL, fn, nullptr, GC_UPDATE)) return FQL_E_STATE;
+    return group_update(g, fn, g->progs[fql_group_s::FULL], idx, batch_size, infoNxk, stream, g->m[0]->num_info());
+}
+
 // The members' sample_actions (flow: compute_flow_actions) in one fused call: fql_group_s::sample between the update's ordering rules
 // (an IFQL group's sample_actions is best of num_samples: fql_group_s::sample_bon)
 static int group_sample(fql_group g, const char* fn, AgentKind kind, const char* instead, bool flow, const float* obs, const float* noise,
@@ -7217,6 +7258,10 @@ int fql_ifql_group_sample_actions(fql_group g, const float* observations, int n,
 }
 int fql_ifql_group_flow_actions(fql_group g, const float* observations, const float* noises, int n, float* out, void* stream) {
     return group_sample(g, "fql_ifql_group_flow_actions", AgentKind::IFQL, nullptr, true, observations, noises, nullptr, 1.0f, n, out, stream);
+}
+int fql_iql_group_sample_actions(fql_group g, const float* observations, int n, const float* noises, const uint64_t* seeds, float temperature,
+                                 float* out, void* stream) {
+    return group_sample(g, "fql_iql_group_sample_actions", AgentKind::IQL, nullptr, false, observations, noises, seeds, temperature, n, out, stream);
 }
 // fql_iqld_sample_actions_cfgs of every member in one fused call: fql_group_s::sample_cfg between the update's ordering rules
 int fql_iqld_group_sample_actions(fql_group g, const float* observations, int n, const float* noises, const uint64_t* seeds, const float* cfgs,
@@ -7296,6 +7341,21 @@ int fql_ifql_group_stats(fql_group g, int64_t* launches_update, int64_t* launche
         if (launches_update) *launches_update = (int64_t)g->progs[fql_group_s::FULL].launches.size();
         if (launches_sample) *launches_sample = g->sample_launches(false);
         if (launches_flow) *launches_flow = g->sample_launches(true);
+    } catch (const Invalid& e) {
+        g_create_error = e.msg; return FQL_E_INVALID;
+    } catch (const HipError& e) {
+        g_create_error = e.msg; return FQL_E_HIP;
+    }
+    return FQL_OK;
+}
+
+// Launches of an IQL group's fused update program and of one fused sampling call on a single chunk, counted from the built programs
+int fql_iql_group_stats(fql_group g, int64_t* launches_update, int64_t* launches_sample) {
+    if (!g) { g_create_error = "fql_iql_group_stats: NULL group"; return FQL_E_INVALID; }
+    if (group_wrong_kind(g, AgentKind::IQL, "fql_iql_group_stats", nullptr, GC_STATS)) return FQL_E_STATE;
+    try {
+        if (launches_update) *launches_update = (int64_t)g->progs[fql_group_s::FULL].launches.size();
+        if (launches_sample) *launches_sample = g->sample_launches(false);
     } catch (const Invalid& e) {
         g_create_error = e.msg; return FQL_E_INVALID;
     } catch (const HipError& e) {

@@ -4,6 +4,8 @@
 // (fql_ifql_loss_value_kernel, fql_ifql_loss_critic_kernel: agents/iql.py:28-55 is agents/ifql.py:31-58 term for term); the GEMM bodies,
 // weight gradients, LayerNorm backward, the critic's input gradient, Adam + Polyak and the grad statistics are FQL's.  Every reduction
 // runs in one workgroup in a fixed order (no float atomics).
+// Every kernel an IQL agent group fuses (fql_iql_group_*) comes in three parts: a __device__ body, the by-value
+// entry a single handle launches, and a *_multi_kernel that takes a device array of the same argument struct, one per member.
 //
 // The actor (utils/networks.py:82-150 with state_dependent_std=False) is actor_net + mean_net as one MLP obs -> [B, ap]; log_stds is a
 // vector leaf [act] of the arena (const_std=False) or absent (const_std=True: log-std 0).  No tanh squash.
@@ -39,7 +41,9 @@ struct IqlPrepArgs {
 };
 // utils/datasets.py:64-100 (index draw + gather) and the network inputs of agents/iql.py; eps is fql_noise.eps1 or Philox tensor 1.
 // One wave per transition.
-__global__ __launch_bounds__(FQL_THREADS) void fql_iql_prep_kernel(IqlPrepArgs P) {
+// (the body takes the struct by value: through a reference the by-value entry compiles to 66 VGPRs and 7 waves per SIMD, this way to the
+// 63 and 8 it had as one function)
+__device__ __forceinline__ void fql_iql_prep_body(const IqlPrepArgs P) {
     const SrcDesc& S = *P.src;
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int b = blockIdx.x * 4 + wave;
@@ -79,6 +83,12 @@ __global__ __launch_bounds__(FQL_THREADS) void fql_iql_prep_kernel(IqlPrepArgs P
         P.w_mask[b] = S.mask[src];
     }
 }
+__global__ __launch_bounds__(FQL_THREADS) void fql_iql_prep_kernel(IqlPrepArgs P) { fql_iql_prep_body(P); }
+// Multi-instance entry points (IQL agent groups), here and below: blockIdx.y picks the member, its argument struct comes from a device
+// array, read through the constant address space (scalar loads, as from the kernel-argument segment; fql_kernels.h FQL_CONST_AS).
+// Shared-memory arrays are declared in the entries and handed to the body: the single-workgroup kernels run as grid (1, members), each
+// workgroup the member's own fixed-order reduction.  Grid x = rows / 4.
+__global__ __launch_bounds__(FQL_THREADS) void fql_iql_prep_multi_kernel(const IqlPrepArgs* __restrict__ args) { const IqlPrepArgs P = ((const FQL_CONST_AS IqlPrepArgs*)args)[blockIdx.y]; fql_iql_prep_body(P); }
 
 struct IqlHeadArgs {
     const float* mean;         // [B, ap]: the actor's output
@@ -91,7 +101,7 @@ struct IqlHeadArgs {
 };
 // The Gaussian head (distrax.MultivariateNormalDiag, temperature 1): log_prob(a) = sum_j(-((a_j - mean_j) / s_j)^2 / 2 - ls_j -
 // log(2 pi) / 2), s = exp(clip(log_stds, -5, 2)).  One thread per row; accurate transcendentals.
-__global__ __launch_bounds__(FQL_THREADS) void fql_iql_head_kernel(IqlHeadArgs P) {
+__device__ __forceinline__ void fql_iql_head_body(const IqlHeadArgs& P) {
     const int b = blockIdx.x * FQL_THREADS + threadIdx.x;
     if (b >= P.B) return;
     const float half_log_2pi = 0.91893853320467274f;
@@ -113,6 +123,8 @@ __global__ __launch_bounds__(FQL_THREADS) void fql_iql_head_kernel(IqlHeadArgs P
     P.lp[b] = lp;
     P.se[b] = se;
 }
+__global__ __launch_bounds__(FQL_THREADS) void fql_iql_head_kernel(IqlHeadArgs P) { fql_iql_head_body(P); }
+__global__ __launch_bounds__(FQL_THREADS) void fql_iql_head_multi_kernel(const IqlHeadArgs* __restrict__ args) { const IqlHeadArgs P = ((const FQL_CONST_AS IqlHeadArgs*)args)[blockIdx.y]; fql_iql_head_body(P); }
 
 // dL/dlog_stds[a] = mask(raw_a) sum_b part[b, a], rows summed by thread-strided partials and a fixed block tree.  Called by the whole
 // workgroup after a __syncthreads() behind the writes of `part`.
@@ -148,8 +160,7 @@ struct IqlAwrArgs {
 };
 // agents/iql.py:59-82: adv = min(q1, q2) - v, w = min(exp(alpha adv), 100) (a constant under the gradient: every input is a stored
 // parameter's), loss = -mean(w log_prob(actions)).  dL/dmean_j = -(w / B) (a_j - mean_j) / s_j^2, dL/dls_j = -(w / B) (u_j^2 - 1).
-__global__ __launch_bounds__(FQL_THREADS) void fql_iql_loss_awr_kernel(IqlAwrArgs P) {
-    __shared__ float sh[4];
+__device__ __forceinline__ void fql_iql_loss_awr_body(const IqlAwrArgs& P, float* sh) {
     float swl = 0.f, sadv = 0.f, slp = 0.f, sse = 0.f;
     for (int b = threadIdx.x; b < P.B; b += FQL_THREADS) {
         const float adv = fminf(P.qa[(size_t)b * 16], P.qb[(size_t)b * 16]) - P.v[(size_t)b * 16];
@@ -185,6 +196,8 @@ __global__ __launch_bounds__(FQL_THREADS) void fql_iql_loss_awr_kernel(IqlAwrArg
     __syncthreads();
     iql_reduce_log_stds(P.ls_part, P.log_stds, P.g_ls, P.B, P.ad, P.ap, sh);
 }
+__global__ __launch_bounds__(FQL_THREADS) void fql_iql_loss_awr_kernel(IqlAwrArgs P) { __shared__ float sh[4]; fql_iql_loss_awr_body(P, sh); }
+__global__ __launch_bounds__(FQL_THREADS) void fql_iql_loss_awr_multi_kernel(const IqlAwrArgs* __restrict__ args) { __shared__ float sh[4]; const IqlAwrArgs P = ((const FQL_CONST_AS IqlAwrArgs*)args)[blockIdx.y]; fql_iql_loss_awr_body(P, sh); }
 
 struct IqlDdpgArgs {
     const float *qa, *qb;      // [B, 16] column 0: critic members (stored parameters) at (obs, q_actions)
@@ -197,8 +210,7 @@ struct IqlDdpgArgs {
 };
 // agents/iql.py:83-110: q = min(q1, q2), q_loss = -mean(q) / stop_gradient(mean |q|), bc_loss = -alpha mean(log_prob(actions)).
 // dL/dq_e = -(1 / B) / mean|q| to the smaller member (1/2 each at an exact tie, as jnp.minimum's gradient).
-__global__ __launch_bounds__(FQL_THREADS) void fql_iql_loss_ddpgbc_kernel(IqlDdpgArgs P) {
-    __shared__ float sh[4];
+__device__ __forceinline__ void fql_iql_loss_ddpgbc_body(const IqlDdpgArgs& P, float* sh) {
     float sq = 0.f, sa = 0.f, slp = 0.f, sse = 0.f;
     for (int b = threadIdx.x; b < P.B; b += FQL_THREADS) {
         const float q = fminf(P.qa[(size_t)b * 16], P.qb[(size_t)b * 16]);
@@ -231,6 +243,8 @@ __global__ __launch_bounds__(FQL_THREADS) void fql_iql_loss_ddpgbc_kernel(IqlDdp
         P.dqb[(size_t)b * 16] = g * (1.0f - ra);
     }
 }
+__global__ __launch_bounds__(FQL_THREADS) void fql_iql_loss_ddpgbc_kernel(IqlDdpgArgs P) { __shared__ float sh[4]; fql_iql_loss_ddpgbc_body(P, sh); }
+__global__ __launch_bounds__(FQL_THREADS) void fql_iql_loss_ddpgbc_multi_kernel(const IqlDdpgArgs* __restrict__ args) { __shared__ float sh[4]; const IqlDdpgArgs P = ((const FQL_CONST_AS IqlDdpgArgs*)args)[blockIdx.y]; fql_iql_loss_ddpgbc_body(P, sh); }
 
 struct IqlActorGradArgs {
     const float *dxa, *dxb;    // [B, inp_c]: the critic members' input gradients (columns od .. od + ad: dL/dq_actions through q_loss)
@@ -248,8 +262,7 @@ struct IqlActorGradArgs {
 // jnp.clip); g = c dL/dq_actions.  With u = (a - mean) / s:
 //   dL/dmean_j = g_j - (alpha / B) u_j / s_j,   dL/dls_j = mask(raw_j) sum_b (g_j s_j eps_j - (alpha / B) (u_j^2 - 1)).
 // One workgroup: the reduction over B of the log_stds gradient runs in a fixed order.
-__global__ __launch_bounds__(FQL_THREADS) void fql_iql_actor_grad_kernel(IqlActorGradArgs P) {
-    __shared__ float sh[4];
+__device__ __forceinline__ void fql_iql_actor_grad_body(const IqlActorGradArgs& P, float* sh) {
     const float ab = P.alpha / (float)P.B;
     for (int e = threadIdx.x; e < P.B * P.ad; e += FQL_THREADS) {
         const int b = e / P.ad, a = e - b * P.ad;
@@ -269,6 +282,8 @@ __global__ __launch_bounds__(FQL_THREADS) void fql_iql_actor_grad_kernel(IqlActo
     __syncthreads();
     iql_reduce_log_stds(P.ls_part, P.log_stds, P.g_ls, P.B, P.ad, P.ap, sh);
 }
+__global__ __launch_bounds__(FQL_THREADS) void fql_iql_actor_grad_kernel(IqlActorGradArgs P) { __shared__ float sh[4]; fql_iql_actor_grad_body(P, sh); }
+__global__ __launch_bounds__(FQL_THREADS) void fql_iql_actor_grad_multi_kernel(const IqlActorGradArgs* __restrict__ args) { __shared__ float sh[4]; const IqlActorGradArgs P = ((const FQL_CONST_AS IqlActorGradArgs*)args)[blockIdx.y]; fql_iql_actor_grad_body(P, sh); }
 
 struct IqlFinalizeArgs {
     FinalizeArgs fin;
@@ -276,7 +291,8 @@ struct IqlFinalizeArgs {
     int n_actor;       // IQL_N_AWR or IQL_N_DDPGBC
 };
 // FQL's finalize (grad statistics into DevState::info 10-12 and the step counters when do_grad_stats), then the reference's IQL order
-__global__ __launch_bounds__(FQL_THREADS) void fql_iql_finalize_kernel(IqlFinalizeArgs A) {
+// (fql_finalize_body declares the LDS it needs itself, sh[4] and leafn[256]: both entries get it through the inlined body)
+__device__ __forceinline__ void fql_iql_finalize_body(const IqlFinalizeArgs& A) {
     fql_finalize_body(A.fin);
     if (threadIdx.x == 0) {
         const float* in = A.fin.st->info;
@@ -288,6 +304,8 @@ __global__ __launch_bounds__(FQL_THREADS) void fql_iql_finalize_kernel(IqlFinali
         for (int i = 0; i < 3; ++i) g[i] = A.fin.do_grad_stats ? in[10 + i] : 0.f;
     }
 }
+__global__ __launch_bounds__(FQL_THREADS) void fql_iql_finalize_kernel(IqlFinalizeArgs A) { fql_iql_finalize_body(A); }
+__global__ __launch_bounds__(FQL_THREADS) void fql_iql_finalize_multi_kernel(const IqlFinalizeArgs* __restrict__ args) { const IqlFinalizeArgs A = ((const FQL_CONST_AS IqlFinalizeArgs*)args)[blockIdx.y]; fql_iql_finalize_body(A); }
 
 struct IqlSampleArgs {
     const float* mean;         // [n, ap]
@@ -299,7 +317,7 @@ struct IqlSampleArgs {
     float temperature;
 };
 // agents/iql.py:158-169: clip(mean + exp(clip(log_stds)) temperature eps, -1, 1); temperature 0 is clip(mean) exactly
-__global__ __launch_bounds__(FQL_THREADS) void fql_iql_sample_kernel(IqlSampleArgs P) {
+__device__ __forceinline__ void fql_iql_sample_body(const IqlSampleArgs& P) {
     const int e = blockIdx.x * FQL_THREADS + threadIdx.x;
     if (e >= P.n * P.ad) return;
     const int r = e / P.ad, a = e - r * P.ad;
@@ -312,3 +330,6 @@ __global__ __launch_bounds__(FQL_THREADS) void fql_iql_sample_kernel(IqlSampleAr
     }
     P.out[e] = clip1(x);
 }
+__global__ __launch_bounds__(FQL_THREADS) void fql_iql_sample_kernel(IqlSampleArgs P) { fql_iql_sample_body(P); }
+// (an IQL group's sampler: grid x covers the chunk's padded rows, elements past the member's n * ad return at once)
+__global__ __launch_bounds__(FQL_THREADS) void fql_iql_sample_multi_kernel(const IqlSampleArgs* __restrict__ args) { const IqlSampleArgs P = ((const FQL_CONST_AS IqlSampleArgs*)args)[blockIdx.y]; fql_iql_sample_body(P); }

@@ -600,8 +600,8 @@ int fql_bc_stats(fql_handle h, int64_t* launches_per_update, int64_t* macs_per_u
  * reserve / size, fql_sample_actions (temperature 1), info enqueue / fql_info_wait_n / fql_read_info_n, fql_synchronize, fql_stats and
  * fql_stream.  Refused: encoder != 0 or precision != 0 at create (FQL_E_INVALID); on an IQL handle fql_update*, fql_update_begin* /
  * _end*, fql_total_loss, fql_flow_actions, fql_grad_buckets, frame uploads / updates, fql_replay_*, fql_update_balanced,
- * fql_noise_from_jax_keys, fql_read_info and fql_info_wait return FQL_E_STATE, and fql_group_create with an IQL member returns
- * FQL_E_STATE.  The fql_iql_* calls on another handle return FQL_E_STATE. */
+ * fql_noise_from_jax_keys, fql_read_info and fql_info_wait return FQL_E_STATE, and fql_group_create with an IQL member still returns
+ * FQL_E_STATE: IQL handles are grouped by fql_iql_group_create (below).  The fql_iql_* calls on another handle return FQL_E_STATE. */
 #define FQL_IQL_AWR_NUM_INFO 16
 #define FQL_IQL_DDPGBC_NUM_INFO 19
 typedef struct fql_iql_config {
@@ -632,6 +632,35 @@ int fql_iql_sample_actions(fql_handle h, const float* observations, int n, const
                            float* out, void* stream);
 /* launches and algorithmic MACs of one update */
 int fql_iql_stats(fql_handle h, int64_t* launches_per_update, int64_t* macs_per_update);
+/* ---- IQL agent groups: the seeds of one task, or an alpha x expectile x seed sweep, advanced by one fused program (agent groups, above) ----
+ * fql_iql_group_create: `members` [k], k >= 1, IQL handles (another kind: FQL_E_STATE naming it), distinct, in no group, the same batch
+ * size and the same fql_config / fql_iql_config except expectile and alpha (and the create seed); anything else - actor_loss, const_std,
+ * a hidden size, lr - is FQL_E_INVALID naming the member, *out NULL.  The group holds ONE fused program, one graph with a member's lanes:
+ * the zip of every member's update (blockIdx.y = member in IQL's own kernels and in IFQL's two losses, concatenated task tables in the
+ * layers), a member's launch count whatever k is.  A member's numbers are bitwise those it has alone, and after a group update it behaves
+ * as after its own: fql_read_info_n (its own 16 or 19 infos), its own updates and sampling calls, fql_iql_total_loss, parameter access
+ * and checkpoints.  fql_group_destroy and fql_group_synchronize serve these groups too; fql_set_batch_size and fql_destroy on a member
+ * return FQL_E_STATE while it is grouped.  fql_group_create and the other kinds' creates keep refusing IQL handles.  Errors:
+ * fql_last_error(NULL).
+ * Across kinds: the fql_group_*, fql_rebrac_group_*, fql_iqld_group_* and fql_ifql_group_* calls that take a group return FQL_E_STATE on
+ * an IQL group, and the three calls below that take a group return it on a group of another kind, each naming the call that serves the
+ * group; a NULL group is FQL_E_INVALID. */
+int fql_iql_group_create(const fql_handle* members, int k, fql_group* out);
+/* fql_iql_update_from_dataset of every member in one fused update.  idx: [k][B] int64, host or device, or NULL = each member's device
+ * RNG; eps is each member's Philox.  infoNxk: [k][fql_num_info] - 16 (awr) or 19 (ddpgbc) per member, as fql_read_info_n gives them -
+ * device or host (host = synchronous), or NULL.  Stream and ordering as fql_group_update_from_dataset. */
+int fql_iql_group_update_from_dataset(fql_group g, const int64_t* idx, int batch_size, float* infoNxk, void* stream);
+/* fql_iql_sample_actions of every member in one fused call.  observations [k][n][od], noises [k][n][act] raw N(0, 1) or NULL (then seeds
+ * [k], each member's Philox keyed by its own seed and the row's number in the call), one temperature for the call, out [k][n][act]; host
+ * or device each.  Per chunk of <= 4096 rows per member: one assemble launch, the members' actor over concatenated task tables, one
+ * sampling-head launch with each member's own log_stds, which writes the actions - 2 launches more than the actor has layers, whatever k
+ * is.  out[i] is bitwise fql_iql_sample_actions(member i, ..., seeds[i], temperature, ...).  Pointer kinds and ordering as
+ * fql_group_sample_actions. */
+int fql_iql_group_sample_actions(fql_group g, const float* observations, int n, const float* noises, const uint64_t* seeds,
+                                 float temperature, float* out, void* stream);
+/* Launches of the group's fused update program and of one fused sampling call on a single chunk, counted from the built programs.
+ * Either pointer may be NULL. */
+int fql_iql_group_stats(fql_group g, int64_t* launches_update, int64_t* launches_sample);
 
 /* ---- IQL-diffusion (agents/iql_diffusion.py): IQL critics with an optimality-conditioned flow actor and classifier-free guidance, the
  * agent the CFGRL training script defaults to.  The BINARY optimality family only: optimal_var in {binary, binary_awr_loss,
