@@ -951,6 +951,8 @@ class FQLAgentGroup:
             raise NotImplementedError('agent groups take FQL agents only (SAC groups are not available)')
         if cfg.get('agent_name') == 'iql':
             raise NotImplementedError('agent groups take FQL agents only (IQL agents are grouped by IQLAgentGroup)')
+        if cfg.get('agent_name') == 'cfgrl':
+            raise NotImplementedError('agent groups take FQL agents only (CFGRL agents are grouped by CFGRLAgentGroup)')
         if cfg.get('encoder') is not None:
             raise NotImplementedError('agent groups take state agents only (encoder=None)')
         if cfg.get('precision', 'fp32') not in ('fp32', 0):

@@ -16,6 +16,9 @@ mask there.  read_rows() returns the raw 32-bit draws of the last update, so the
 State observations, fp32 and GELU only: `encoder`, precision 'bf16x3', rng other than 'engine', frame stacking and actor_geom_sample
 are refused here, before the library is called.  Checkpoints (TrainState key 'network'), get/set_params and synchronize are FQLAgent's
 plumbing on a CFGRL handle.
+
+CFGRLAgentGroup advances K such agents - one config but for seed, cfg and the actor's goal mixture - with one fused update program and
+samples them in one fused call (fql_cfgrl_group_*).
 """
 from __future__ import annotations
 
@@ -24,9 +27,9 @@ import ctypes as C
 import numpy as np
 
 from . import _cabi
-from .agent import KindAgent, _Arg, _PendingN
+from .agent import FQLAgent, KindAgent, _Arg, _PendingN, _group_idx_arg, _group_sample_args
 from .config import ConfigDict
-from .iql_diffusion import as_array, check_cfgs, sweep_inputs
+from .iql_diffusion import as_array, check_cfgs, group_cfgs, sweep_inputs
 
 CFGRL_INFO_KEYS = ('actor/actor_loss', 'grad/max', 'grad/min', 'grad/norm')
 CFGRL_NOISE_KEYS = ('x0', 't')
@@ -91,19 +94,7 @@ class CFGRLAgent(KindAgent):
         """agents/cfgrl.py:102-159.  `example_batch`: observations, actions and value_goals (goal_dim is its last axis)."""
         cfg = get_config()
         cfg.update(dict(config))
-        cls._refuse_config(cfg)
-        if cfg.get('actor_geom_sample'):
-            raise NotImplementedError('CFGRL: actor_geom_sample=True is not built (uniform trajectory goals only)')
-        if cfg.get('frame_stack') is not None:
-            raise NotImplementedError('CFGRL: frame_stack is not built (state observations only)')
-        if int(cfg['flow_steps']) < 1:
-            raise ValueError('flow_steps must be >= 1')
-        psum = float(cfg['actor_p_curgoal']) + float(cfg['actor_p_trajgoal']) + float(cfg['actor_p_randomgoal'])
-        if not np.isclose(psum, 1.0):   # utils/datasets.py:159-161
-            raise ValueError('actor_p_curgoal + actor_p_trajgoal + actor_p_randomgoal must be 1')
-        for k in ('observations', 'actions', 'value_goals'):
-            if k not in example_batch:
-                raise KeyError(f'example_batch is missing {k!r}')
+        cls._check_create(cfg, example_batch)
         lib = _cabi.load()
         # fql_config mapping (include/fql_amd.h): actor_hidden_dims -> actor_hidden, actor_layer_norm, lr
         ec = dict(actor_hidden_dims=tuple(cfg['actor_hidden_dims']), value_hidden_dims=tuple(cfg['actor_hidden_dims']), layer_norm=False,
@@ -122,6 +113,23 @@ class CFGRLAgent(KindAgent):
         cfg['action_dim'] = action_dim
         cfg['goal_dim'] = int(gc.goal_dim)
         return cls(h, cfg, int(seed))
+
+    @classmethod
+    def _check_create(cls, cfg, example_batch):
+        """The refusals of create (and of CFGRLAgentGroup.create, per member), before any library call."""
+        cls._refuse_config(cfg)
+        if cfg.get('actor_geom_sample'):
+            raise NotImplementedError('CFGRL: actor_geom_sample=True is not built (uniform trajectory goals only)')
+        if cfg.get('frame_stack') is not None:
+            raise NotImplementedError('CFGRL: frame_stack is not built (state observations only)')
+        if int(cfg['flow_steps']) < 1:
+            raise ValueError('flow_steps must be >= 1')
+        psum = float(cfg['actor_p_curgoal']) + float(cfg['actor_p_trajgoal']) + float(cfg['actor_p_randomgoal'])
+        if not np.isclose(psum, 1.0):   # utils/datasets.py:159-161
+            raise ValueError('actor_p_curgoal + actor_p_trajgoal + actor_p_randomgoal must be 1')
+        for k in ('observations', 'actions', 'value_goals'):
+            if k not in example_batch:
+                raise KeyError(f'example_batch is missing {k!r}')
 
     def _batch_args(self, batch):   # CFGRL reads observations, actions and actor_goals of the goal-conditioned batch
         for k in ('observations', 'actions', 'actor_goals'):
@@ -282,4 +290,146 @@ class CFGRLAgent(KindAgent):
         return int(la.value), int(ma.value), int(ls.value)
 
 
-__all__ = ['CFGRLAgent', 'CFGRL_INFO_KEYS', 'CFGRL_NOISE_KEYS', 'CFGRL_DRAW_KEYS', 'get_config', 'final_indices']
+MIX_KEYS = ('actor_p_curgoal', 'actor_p_trajgoal', 'actor_p_randomgoal')
+
+
+class CFGRLAgentGroup:
+    """K CFGRL agents of one structure - the same config except `seed`, `cfg` and the actor's goal mixture (actor_p_curgoal /
+    actor_p_trajgoal / actor_p_randomgoal) - advanced by ONE fused update program (include/fql_amd.h, fql_cfgrl_group_*): every launch of
+    the update's single lane carries all K members' tasks.  The seed x goal-mixture x guidance-weight sweeps of the goal-conditioned
+    benchmarks on one device:
+
+        group = CFGRLAgentGroup.create(seeds, example_batch, config, cfgs=[1.5, 3, 5], goal_mixes=[(0, 1, 0), (0, .5, .5), (.2, .5, .3)])
+        group.upload_dataset(train_dataset)
+        for i in range(1, n + 1):
+            infos = group.update_from_dataset(want_info=(i % log_every == 0))
+        actions = group.sample_actions(observations, goals, seed=i)   # [K, ..., act], one fused call, each member's own cfg
+
+    `members` are ordinary CFGRLAgent objects; a member's trajectory is bitwise the one it has when trained alone with the same seed,
+    mixture, rows, mask and noise.  Members are state agents with precision 'fp32' and the engine's device RNG; while grouped their batch
+    size is fixed.  The other kinds have groups of their own (FQLAgentGroup, ReBRACAgentGroup, IQLDiffusionAgentGroup, IFQLAgentGroup,
+    IQLAgentGroup)."""
+
+    def __init__(self, handle, members):
+        self._lib = _cabi.load()
+        self._g = handle
+        self.members = members
+        self.batch_size = int(members[0].config['batch_size'])
+        self._keep = None
+
+    @classmethod
+    def create(cls, seeds, example_batch, config, cfgs=None, goal_mixes=None):
+        """`cfgs`: K default guidance weights (None: the config's).  `goal_mixes`: K triples (p_cur, p_traj, p_random), each summing to
+        1 (None: the config's mixture for every member)."""
+        seeds = [int(s) for s in seeds]
+        if not seeds:
+            raise ValueError('an agent group needs at least one seed')
+        cfg = get_config()
+        cfg.update(dict(config))
+        cfgs = [float(cfg['cfg'])] * len(seeds) if cfgs is None else [float(c) for c in cfgs]
+        if len(cfgs) != len(seeds):
+            raise ValueError(f'{len(seeds)} seeds but {len(cfgs)} cfgs')
+        if not np.isfinite(cfgs).all():
+            raise ValueError('cfgs: every guidance weight must be finite')
+        if goal_mixes is None:
+            goal_mixes = [tuple(float(cfg[k]) for k in MIX_KEYS)] * len(seeds)
+        goal_mixes = [tuple(float(p) for p in mix) for mix in goal_mixes]
+        if len(goal_mixes) != len(seeds):
+            raise ValueError(f'{len(seeds)} seeds but {len(goal_mixes)} goal_mixes')
+        for i, mix in enumerate(goal_mixes):
+            if len(mix) != 3 or min(mix) < 0.0 or not np.isclose(sum(mix), 1.0):
+                raise ValueError(f'goal_mixes[{i}] = {mix}: three probabilities (p_cur, p_traj, p_random) that sum to 1')
+        per_member = []
+        for c, mix in zip(cfgs, goal_mixes):
+            mc = dict(cfg, cfg=c, **dict(zip(MIX_KEYS, mix)))
+            CFGRLAgent._check_create(mc, example_batch)   # encoder, precision, rng, actor_geom_sample, frame_stack, flow_steps, the example's keys
+            per_member.append(mc)
+        lib = _cabi.load()
+        members = [CFGRLAgent.create(s, example_batch, mc) for s, mc in zip(seeds, per_member)]
+        arr = (C.c_void_p * len(members))(*[m._h for m in members])
+        g = C.c_void_p()
+        _cabi.check(lib, None, lib.fql_cfgrl_group_create(arr, len(members), C.byref(g)))
+        return cls(g, members)
+
+    def _check(self, rc):
+        _cabi.check(self._lib, None, rc)
+
+    def upload_dataset(self, dataset, capacity=None):
+        """Every member gets its own device copy of `dataset` and its own goal table (CFGRLAgent.upload_dataset)."""
+        for m in self.members:
+            m.upload_dataset(dataset, capacity=capacity)
+
+    def update_from_dataset(self, batch_size=None, idxs=None, do_cfg=None, want_info=False):
+        """One fused update of every member: rows from each member's dataset (`idxs` [K, B] int, host or device, or None = each member's
+        device RNG), the goal of each row drawn with the member's own mixture, `do_cfg` [K, B] booleans (host or device) or None = each
+        member's own mask draw; x_0 and t from each member's device RNG.  Returns a list of K LazyInfo over CFGRL_INFO_KEYS (want_info)
+        or None."""
+        K = len(self.members)
+        B = int(batch_size or self.batch_size)
+        if B != self.batch_size:
+            raise ValueError(f'batch_size {B}: the members of a group keep the batch size they were grouped with ({self.batch_size})')
+        mask = _Arg(None)
+        if do_cfg is not None:
+            do_cfg = do_cfg if hasattr(do_cfg, 'data_ptr') else np.asarray(do_cfg)
+            if tuple(int(d) for d in do_cfg.shape) != (K, B):
+                raise ValueError(f'do_cfg must be [{K}, {B}], got {tuple(do_cfg.shape)}')
+            mask = _Arg(do_cfg != 0, (K, B), u8=True)
+        ip, keep, stream = None, None, None
+        if idxs is not None:
+            keep, ip, stream = _group_idx_arg(self.members, idxs, B)
+        if stream is None:
+            stream = FQLAgent._stream([mask])
+        self._check(self._lib.fql_cfgrl_group_update_from_dataset(self._g, ip, B, mask.ptr, None, stream))
+        self._keep = (keep, mask)
+        return [m._lazy_info(None) for m in self.members] if want_info else None
+
+    def sample_actions(self, observations, goals, seed=None, cfg=None, noises=None):
+        """CFGRLAgent.sample_actions of every member in ONE fused call (fql_cfgrl_group_sample_actions): result[i] is bitwise what
+        members[i].sample_actions(observations[i], goals[i], seed=..., cfg=..., noises=noises[i]) returns.  `cfg`: None (each member's
+        configured default), a scalar, [K] (one guidance weight per member) or [K, ...] (one per row: members[i].sample_actions_rows);
+        every weight finite.  observations [K, ..., od] or one shared block; goals [K, ..., G], one shared block [..., G] or one [G] for
+        every member and row; noises [K, ..., ad] or None; seed None (each member's own counter advances), one seed or K seeds, as in
+        FQLAgentGroup.sample_actions.  Returns [K, ..., ad]."""
+        if goals is None:
+            raise ValueError('CFGRL: sample_actions needs goals (the conditional pass reads them, agents/cfgrl.py:93)')
+        K, G = len(self.members), int(self.members[0].config['goal_dim'])
+        c = as_array([float(m.config['cfg']) for m in self.members] if cfg is None else cfg)
+        check_cfgs(c.reshape(-1), int(np.prod(c.shape)), 'entry')   # finite, whatever the shape: before a member's seed counter moves
+        goals = as_array(goals)
+        # (flow=True: the shape rules alone - no seed is drawn, no counter moves before the goals and the weights are checked)
+        lead = tuple(int(d) for d in _group_sample_args(self.members, observations, noises, seed, True)[4].shape[1:-1])
+        gs = tuple(int(d) for d in goals.shape)
+        if gs not in ((K,) + lead + (G,), lead + (G,), (G,)):
+            raise ValueError(f'goals must be {(K,) + lead + (G,)}, one shared block {lead + (G,)} or one [{G}], got {gs}')
+        if gs != (K,) + lead + (G,):   # shared: broadcast here, the library takes one block per member
+            goals = goals.expand((K,) + lead + (G,)) if hasattr(goals, 'data_ptr') else np.broadcast_to(goals, (K,) + lead + (G,))
+        w = group_cfgs(c, K, lead)
+        o, z, seeds, n, out, optr, _ = _group_sample_args(self.members, observations, noises, seed, False)
+        g, w = _Arg(goals, (K, n, G)), _Arg(w, (K, n))
+        self._check(self._lib.fql_cfgrl_group_sample_actions(self._g, o.ptr, g.ptr, n, z.ptr, seeds, w.ptr, optr, FQLAgent._stream([o, g, z, w])))
+        return out
+
+    def launches(self):
+        """Kernel launches of (the fused update program, one fused sampling call on a single chunk)."""
+        u, s = C.c_int64(0), C.c_int64(0)
+        self._check(self._lib.fql_cfgrl_group_stats(self._g, C.byref(u), C.byref(s)))
+        return int(u.value), int(s.value)
+
+    def synchronize(self):
+        """Host wait for the group's last update or sampling call."""
+        self._check(self._lib.fql_group_synchronize(self._g))
+
+    def close(self):
+        """Destroy the fused program; the members stay usable as standalone agents.  A second close is a no-op."""
+        if getattr(self, '_g', None):
+            self._lib.fql_group_destroy(self._g)
+            self._g = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+__all__ = ['CFGRLAgent', 'CFGRLAgentGroup', 'CFGRL_INFO_KEYS', 'CFGRL_NOISE_KEYS', 'CFGRL_DRAW_KEYS', 'get_config', 'final_indices']

@@ -4,6 +4,8 @@
 // weight gradients, LayerNorm backward, the flow-matching loss (fql_loss_bc_body: its 2 / (B act) scaling is this loss's), Adam and the
 // grad statistics are FQL's; the sampler's CFG combine, Euler add and final clip are IQL-diffusion's fql_iqld_cfg_step_kernel, unchanged.
 // The sweep program (one guidance weight per row) adds fql_cfgrl_cfg_layer0_kernel and ends on IQL-diffusion's rows step kernel.
+// Every kernel a CFGRL agent group fuses (fql_cfgrl_group_*) comes in three parts: a __device__ body, the by-value
+// entry a single handle launches, and a *_multi_kernel that takes a device array of the same argument struct, one per member.
 //
 // actor_flow is GCActorVectorField: MLP((*hidden, act), GELU, LayerNorm optional) on [obs | goal | x_t | t], t one column.
 #pragma once
@@ -69,7 +71,7 @@ struct CfgrlPrepArgs {
 // utils/datasets.py:64-100 (index draw + gather) and :224-255 (goal), agents/cfgrl.py:24-37 (x_0, t, x_t, vel, do_cfg, goals): one wave
 // per transition writes X = [obs | goal or unc_embed | x_t | t | 0] and vel = act - x_0.  x_0 is Philox tensor 2 and t tensor 3 (continuous,
 // as IFQL's); explicit tensors replace them.
-__global__ __launch_bounds__(FQL_THREADS) void fql_cfgrl_prep_kernel(CfgrlPrepArgs P) {
+__device__ __forceinline__ void fql_cfgrl_prep_body(const CfgrlPrepArgs& P) {
     const SrcDesc& S = *P.src;
     const CfgrlSrc& Gs = *P.gsrc;
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -134,6 +136,12 @@ __global__ __launch_bounds__(FQL_THREADS) void fql_cfgrl_prep_kernel(CfgrlPrepAr
         P.draws[(size_t)lane * P.B + b] = v;
     }
 }
+__global__ __launch_bounds__(FQL_THREADS) void fql_cfgrl_prep_kernel(CfgrlPrepArgs P) { fql_cfgrl_prep_body(P); }
+// Multi-instance entry points (CFGRL agent groups), here and below: blockIdx.y picks the member, its argument struct comes from a device
+// array, read through the constant address space (scalar loads, as from the kernel-argument segment; fql_kernels.h FQL_CONST_AS).
+// Shared-memory arrays are declared in the entries and handed to the body: the single-workgroup kernels run as grid (1, members), each
+// workgroup the member's own fixed-order reduction.
+__global__ __launch_bounds__(FQL_THREADS) void fql_cfgrl_prep_multi_kernel(const CfgrlPrepArgs* __restrict__ args) { const CfgrlPrepArgs P = ((const FQL_CONST_AS CfgrlPrepArgs*)args)[blockIdx.y]; fql_cfgrl_prep_body(P); }
 
 struct CfgrlEmbedGradArgs {
     const float* dZ0;          // [B, H]: gradient at layer 0's pre-activation
@@ -148,11 +156,8 @@ struct CfgrlEmbedGradArgs {
 // load of the mask inside the sum: a loop over every row that tests mask[b] first costs one dependent global load per row (measured: 80 us
 // at B 256).  Each thread owns columns threadIdx.x + 256 i, i < 4 (H <= 1024), and adds the rows in rising b, eight loads in flight.  Then one wave per goal
 // column, the products over h in rising order per lane and a fixed shuffle tree over the lanes.  No dropped row: every sum stays 0.f, dU
-// is exactly zero.
-__global__ __launch_bounds__(FQL_THREADS) void fql_cfgrl_embed_grad_kernel(CfgrlEmbedGradArgs P) {
-    __shared__ float cs[1024];
-    __shared__ int rows[FQL_THREADS];
-    __shared__ int cnt[FQL_THREADS / 64];
+// is exactly zero.  cs: [1024], rows: [FQL_THREADS], cnt: [FQL_THREADS / 64] in LDS.
+__device__ __forceinline__ void fql_cfgrl_embed_grad_body(const CfgrlEmbedGradArgs& P, float* cs, int* rows, int* cnt) {
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     float s[4] = {0.f, 0.f, 0.f, 0.f};
     for (int b0 = 0; b0 < P.B; b0 += FQL_THREADS) {
@@ -203,9 +208,11 @@ __global__ __launch_bounds__(FQL_THREADS) void fql_cfgrl_embed_grad_kernel(Cfgrl
         if (lane == 0) P.g[j] = t;
     }
 }
+__global__ __launch_bounds__(FQL_THREADS) void fql_cfgrl_embed_grad_kernel(CfgrlEmbedGradArgs P) { __shared__ float cs[1024]; __shared__ int rows[FQL_THREADS]; __shared__ int cnt[FQL_THREADS / 64]; fql_cfgrl_embed_grad_body(P, cs, rows, cnt); }
+__global__ __launch_bounds__(FQL_THREADS) void fql_cfgrl_embed_grad_multi_kernel(const CfgrlEmbedGradArgs* __restrict__ args) { __shared__ float cs[1024]; __shared__ int rows[FQL_THREADS]; __shared__ int cnt[FQL_THREADS / 64]; const CfgrlEmbedGradArgs P = ((const FQL_CONST_AS CfgrlEmbedGradArgs*)args)[blockIdx.y]; fql_cfgrl_embed_grad_body(P, cs, rows, cnt); }
 
 // FQL's finalize (grad statistics into slots 10-12 and the step counters), then the reference's order in slots 0-3
-__global__ __launch_bounds__(FQL_THREADS) void fql_cfgrl_finalize_kernel(FinalizeArgs A) {
+__device__ __forceinline__ void fql_cfgrl_finalize_body(const FinalizeArgs& A) {
     fql_finalize_body(A);
     if (threadIdx.x == 0) {
         float* in = A.st->info;
@@ -213,6 +220,8 @@ __global__ __launch_bounds__(FQL_THREADS) void fql_cfgrl_finalize_kernel(Finaliz
         in[0] = loss; in[1] = gmax; in[2] = gmin; in[3] = gn;
     }
 }
+__global__ __launch_bounds__(FQL_THREADS) void fql_cfgrl_finalize_kernel(FinalizeArgs A) { fql_cfgrl_finalize_body(A); }
+__global__ __launch_bounds__(FQL_THREADS) void fql_cfgrl_finalize_multi_kernel(const FinalizeArgs* __restrict__ args) { const FinalizeArgs A = ((const FQL_CONST_AS FinalizeArgs*)args)[blockIdx.y]; fql_cfgrl_finalize_body(A); }
 
 // ---- sample_actions (agents/cfgrl.py:70-100) ---------------------------------------------------------------------------------------
 // IQL-diffusion's two-half form: rows [0, n_pad) are the conditional pass ([obs | goal]), rows [n_pad, 2 n_pad) the unconditional one
@@ -226,7 +235,7 @@ struct CfgrlAssembleArgs {
     int n, n_pad, od, G, ad, inp, ap;
     int row0;                  // index of this chunk's first row in the call (keys the Philox draw: chunking does not change the noise)
 };
-__global__ __launch_bounds__(FQL_THREADS) void fql_cfgrl_assemble_kernel(CfgrlAssembleArgs P) {
+__device__ __forceinline__ void fql_cfgrl_assemble_body(const CfgrlAssembleArgs& P) {
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int r = blockIdx.x * 4 + wave;
     if (r >= P.n_pad) return;
@@ -245,6 +254,8 @@ __global__ __launch_bounds__(FQL_THREADS) void fql_cfgrl_assemble_kernel(CfgrlAs
         P.A[(size_t)r * P.ap + a] = v;
     }
 }
+__global__ __launch_bounds__(FQL_THREADS) void fql_cfgrl_assemble_kernel(CfgrlAssembleArgs P) { fql_cfgrl_assemble_body(P); }
+__global__ __launch_bounds__(FQL_THREADS) void fql_cfgrl_assemble_multi_kernel(const CfgrlAssembleArgs* __restrict__ args) { const CfgrlAssembleArgs P = ((const FQL_CONST_AS CfgrlAssembleArgs*)args)[blockIdx.y]; fql_cfgrl_assemble_body(P); }
 
 struct CfgrlLayer0Args {
     const float *C0, *A, *W0a;   // C0 [2 n_pad, H]; A [n_pad, ap]; W0a = row od + G of W0 [in_p, H]: ad action rows, then the t row
@@ -253,7 +264,7 @@ struct CfgrlLayer0Args {
     float t;                     // i / flow_steps
 };
 // layer 0 of one Euler step for both halves: one thread per (row, column), the act terms in fixed order, then the t term
-__global__ __launch_bounds__(FQL_THREADS) void fql_cfgrl_layer0_kernel(CfgrlLayer0Args P) {
+__device__ __forceinline__ void fql_cfgrl_layer0_body(const CfgrlLayer0Args& P) {
     const int e = blockIdx.x * FQL_THREADS + threadIdx.x;
     if (e >= 2 * P.n_pad * P.H) return;
     const int r = e / P.H, h = e - r * P.H;
@@ -264,6 +275,8 @@ __global__ __launch_bounds__(FQL_THREADS) void fql_cfgrl_layer0_kernel(CfgrlLaye
     s = fmaf(P.t, P.W0a[(size_t)P.ad * P.H + h], s);
     P.G0[e] = gelu_f(s);
 }
+__global__ __launch_bounds__(FQL_THREADS) void fql_cfgrl_layer0_kernel(CfgrlLayer0Args P) { fql_cfgrl_layer0_body(P); }
+__global__ __launch_bounds__(FQL_THREADS) void fql_cfgrl_layer0_multi_kernel(const CfgrlLayer0Args* __restrict__ args) { const CfgrlLayer0Args P = ((const FQL_CONST_AS CfgrlLayer0Args*)args)[blockIdx.y]; fql_cfgrl_layer0_body(P); }
 
 struct CfgrlCfgLayer0Args {
     const float *C0, *V, *Xin, *cfg, *W0a;   // C0 [2 n_pad, H]; V [2 n_pad, ap]: the previous step's head output; Xin [n_pad, ap]; cfg [n_pad];
@@ -274,7 +287,9 @@ struct CfgrlCfgLayer0Args {
 };
 // Euler step i >= 1 of a sweep program (sample_actions_cfgs) in one launch: fql_iqld_cfg_layer0_kernel around fql_cfgrl_layer0_kernel's
 // layer 0 (C0 spans both halves; the act terms in rising order, then the t term)
-__global__ __launch_bounds__(FQL_THREADS) void fql_cfgrl_cfg_layer0_kernel(CfgrlCfgLayer0Args P) {
+// (the body takes the struct by value: through a reference the by-value entry compiles to 28 SGPRs, this way to the 26 it had as one
+// function)
+__device__ __forceinline__ void fql_cfgrl_cfg_layer0_body(const CfgrlCfgLayer0Args P) {
     const int e = blockIdx.x * FQL_THREADS + threadIdx.x;
     if (e >= 2 * P.n_pad * P.H) return;
     const int r = e / P.H, h = e - r * P.H;
@@ -291,3 +306,5 @@ __global__ __launch_bounds__(FQL_THREADS) void fql_cfgrl_cfg_layer0_kernel(Cfgrl
         for (int a = h; a < P.ap; a += P.H)
             P.Xout[(size_t)src * P.ap + a] = a < P.ad ? iqld_cfg_euler(x[a], vp[a], vu[a], c, P.dt) : 0.f;
 }
+__global__ __launch_bounds__(FQL_THREADS) void fql_cfgrl_cfg_layer0_kernel(CfgrlCfgLayer0Args P) { fql_cfgrl_cfg_layer0_body(P); }
+__global__ __launch_bounds__(FQL_THREADS) void fql_cfgrl_cfg_layer0_multi_kernel(const CfgrlCfgLayer0Args* __restrict__ args) { const CfgrlCfgLayer0Args P = ((const FQL_CONST_AS CfgrlCfgLayer0Args*)args)[blockIdx.y]; fql_cfgrl_cfg_layer0_body(P); }

@@ -6383,7 +6383,9 @@ int fql_update_from_frames(fql_handle h, const int64_t* idx, const int32_t* crop
 // (fql_ifql_group_create), whose group holds the one fused program and a best-of-N sampler that zips the members'
 // Euler flow and critic pair between the multi-instance forms of IFQL's three sampling kernels; or IQL members (fql_iql_group_create;
 // DESIGN.md section 25), whose group holds the one fused program - IFQL's value and critic lanes beside the Gaussian actor's own
-// kernels - and a sampler that ends in the multi-instance form of IQL's sampling head.
+// kernels - and a sampler that ends in the multi-instance form of IQL's sampling head; or CFGRL members (fql_cfgrl_group_create;
+// DESIGN.md section 26), whose group holds the one fused program - BC's single lane, each member's goal source (CfgrlSrc) set per
+// update - and a sampler that zips the members' sweep program behind the multi-instance form of CFGRL's two-half row assembly.
 // ================================================================================================
 namespace {
 
@@ -6447,6 +6449,14 @@ const std::map<const void*, MultiEntry>& multi_entries() {
         FQL_MULTI(fql_iql_loss_ddpgbc_kernel, fql_iql_loss_ddpgbc_multi_kernel, IqlDdpgArgs);
         FQL_MULTI(fql_iql_actor_grad_kernel, fql_iql_actor_grad_multi_kernel, IqlActorGradArgs);
         FQL_MULTI(fql_iql_finalize_kernel, fql_iql_finalize_multi_kernel, IqlFinalizeArgs);
+        // CFGRL (fql_cfgrl.h): the update program, then the sweep sampler, which ends on IQL-diffusion's rows step kernel, entered above
+        // (the sampler's row assembly is bound by sample_ws_cfg)
+        FQL_MULTI(fql_cfgrl_prep_kernel, fql_cfgrl_prep_multi_kernel, CfgrlPrepArgs);
+        FQL_MULTI(fql_cfgrl_embed_grad_kernel, fql_cfgrl_embed_grad_multi_kernel, CfgrlEmbedGradArgs);   // grid (1, members)
+        FQL_MULTI(fql_cfgrl_finalize_kernel, fql_cfgrl_finalize_multi_kernel, FinalizeArgs);
+        FQL_MULTI(fql_cfgrl_assemble_kernel, fql_cfgrl_assemble_multi_kernel, CfgrlAssembleArgs);
+        FQL_MULTI(fql_cfgrl_layer0_kernel, fql_cfgrl_layer0_multi_kernel, CfgrlLayer0Args);
+        FQL_MULTI(fql_cfgrl_cfg_layer0_kernel, fql_cfgrl_cfg_layer0_multi_kernel, CfgrlCfgLayer0Args);
 #undef FQL_MULTI
         return e;
     }();
@@ -6478,7 +6488,7 @@ struct GProgram {
 
 struct fql_group_s {
     std::vector<fql_handle> m;
-    AgentKind kind = AgentKind::FQL;     // the members' kind: FQL (fql_group_create), ReBRAC (fql_rebrac_group_create), IQL-diffusion (fql_iqld_group_create), IFQL (fql_ifql_group_create) or IQL (fql_iql_group_create)
+    AgentKind kind = AgentKind::FQL;     // the members' kind: FQL (fql_group_create), ReBRAC (fql_rebrac_group_create), IQL-diffusion (fql_iqld_group_create), IFQL (fql_ifql_group_create), IQL (fql_iql_group_create) or CFGRL (fql_cfgrl_group_create)
     int K = 0, B = 0;
     hipStream_t lanes[FQL_LANES] = {};   // lane 0 = the group's own stream
     // One fused program per entry of group_programs(kind), in its order.  [0]: the members' prog_full zipped (every kind); [1]: their
@@ -6488,6 +6498,7 @@ struct fql_group_s {
     hipEvent_t ev_in = nullptr, ev_done = nullptr;
     std::vector<void*> allocs;
     int64_t* d_idx = nullptr;   // [K][B] staging of host row indices
+    unsigned char* d_mask = nullptr;   // a CFGRL group: [K][B] staging of a host do_cfg mask
     hipStream_t last = nullptr; // the stream of the last group call (update or sampling): a call on another stream waits for that one first
 
     void* galloc(size_t bytes) {
@@ -6605,6 +6616,7 @@ struct fql_group_s {
         std::vector<GLaunch> os, flow;
         std::vector<GLaunch> q;            // an IFQL group's best-of-N sampler: the members' critic pair (Eval::prog_q) zipped
         float *st_obs = nullptr, *st_noise = nullptr, *st_out = nullptr;
+        float* st_goal = nullptr;          // a CFGRL group: staging of host goals
         unsigned char* d_args = nullptr;   // [K] AssembleArgs, then [K] ExtractArgs (a ReBRAC group: [K] RebracActArgs; an IQL group: [K] IqlSampleArgs)
         Bound assemble, extract;           // the multi-instance launches over d_args, blockIdx.y = member
         Bound act;                         // a ReBRAC group: fql_rebrac_act_multi_kernel writes the actions, no extract launch; an IQL group: fql_iql_sample_multi_kernel
@@ -6622,8 +6634,9 @@ struct fql_group_s {
     int arg_pos = 0;
     // (a slot holds the layout of the group's kind: [K] AssembleArgs + [K] ExtractArgs, [K] AssembleArgs + [K] RebracActArgs, an IQL
     // group's [K] AssembleArgs + [K] IqlSampleArgs, or an IQL-diffusion group's [K] BcAssembleArgs + [K] ExtractArgs; an IFQL group's
-    // flow call uses the first, its best-of-N call [K] IfqlRepeatArgs + [K] IfqlQinArgs + [K] IfqlSelectArgs)
-    size_t asm_bytes() const { return kind == AgentKind::IQLD ? sizeof(BcAssembleArgs) : sizeof(AssembleArgs); }
+    // flow call uses the first, its best-of-N call [K] IfqlRepeatArgs + [K] IfqlQinArgs + [K] IfqlSelectArgs; a CFGRL group's
+    // [K] CfgrlAssembleArgs + [K] ExtractArgs)
+    size_t asm_bytes() const { return kind == AgentKind::IQLD ? sizeof(BcAssembleArgs) : kind == AgentKind::CFGRL ? sizeof(CfgrlAssembleArgs) : sizeof(AssembleArgs); }
     size_t bon_bytes() const { return kind == AgentKind::IFQL ? sizeof(IfqlRepeatArgs) + sizeof(IfqlQinArgs) + sizeof(IfqlSelectArgs) : 0; }
     size_t arg_bytes() const { return (size_t)K * std::max(asm_bytes() + std::max({sizeof(ExtractArgs), sizeof(RebracActArgs), sizeof(IqlSampleArgs)}), bon_bytes()); }
 
@@ -6658,7 +6671,8 @@ struct fql_group_s {
     // An IQL-diffusion group's workspace of one chunk of `half` padded rows per member (Sample::n_pad holds the half): the launches of
     // every member's SWEEP program get_eval(2 half, true).prog_flow zipped - it binds its per-row guidance weights from the member's
     // workspace (Eval::cfgs) and takes no issue-time argument, which a device-resident argument array could not follow - between the
-    // multi-instance forms of the two launches fql_engine::sample_flow puts around it.
+    // multi-instance forms of the two launches fql_engine::sample_flow puts around it.  A CFGRL group's is the same with CFGRL's row
+    // assembly, which writes both halves - [obs | goal] and [obs | the member's unc_embed row] - and a staging block for host goals.
     Sample& sample_ws_cfg(int half) {
         std::unique_ptr<Sample>& slot = samples[half];
         if (!slot) {
@@ -6670,9 +6684,13 @@ struct fql_group_s {
             w->st_noise = (float*)galloc((size_t)K * half * ad * sizeof(float));
             w->st_out = (float*)galloc((size_t)K * half * ad * sizeof(float));
             w->d_args = (unsigned char*)galloc(arg_bytes());
-            w->assemble = bind(fql_bc_assemble_multi_kernel, Geo(dim3((half + 3) / 4, K), dim3(FQL_THREADS), 0), (const BcAssembleArgs*)w->d_args);
+            if (kind == AgentKind::CFGRL) {
+                w->st_goal = (float*)galloc((size_t)K * half * m[0]->gcfg.goal_dim * sizeof(float));
+                w->assemble = bind(fql_cfgrl_assemble_multi_kernel, Geo(dim3((half + 3) / 4, K), dim3(FQL_THREADS), 0), (const CfgrlAssembleArgs*)w->d_args);
+            } else
+                w->assemble = bind(fql_bc_assemble_multi_kernel, Geo(dim3((half + 3) / 4, K), dim3(FQL_THREADS), 0), (const BcAssembleArgs*)w->d_args);
             w->extract = bind(fql_extract_multi_kernel, Geo(dim3((half * ad + 255) / 256, K), dim3(256), 0),
-                              (const ExtractArgs*)(w->d_args + (size_t)K * sizeof(BcAssembleArgs)));
+                              (const ExtractArgs*)(w->d_args + (size_t)K * asm_bytes()));
             slot = std::move(w);
         }
         return *slot;
@@ -6700,7 +6718,7 @@ struct fql_group_s {
     // (a ReBRAC or IQL group: the kind's action kernel in extract's place; an IFQL group's best-of-N call: repeat, the flow, qin, the
     // critic pair, select)
     int64_t sample_launches(bool flow) {
-        if (kind == AgentKind::IQLD) return 2 + (int64_t)sample_ws_cfg(16).flow.size();
+        if (kind == AgentKind::IQLD || kind == AgentKind::CFGRL) return 2 + (int64_t)sample_ws_cfg(16).flow.size();
         if (kind == AgentKind::IFQL && !flow) {
             Sample& w = sample_ws_bon(pad16(m[0]->num_samples));
             return 3 + (int64_t)w.flow.size() + (int64_t)w.q.size();
@@ -6810,10 +6828,12 @@ struct fql_group_s {
     // of <= 2048 observations per member - the member's own chunks, row numbers and seed key (fql_engine::sample_flow) -
     // fql_bc_assemble_multi_kernel, each member's chunk of `cfgs` [K, n] (host: checked finite here; or device) copied into the buffer
     // its sweep program reads with 0 behind it, the zipped launches, extract-multi.
-    void sample_cfg(const float* obs, const float* noise, const uint64_t* seeds, const float* cfgs, int n, float* out, hipStream_t s) {
-        const int od = m[0]->cfg.obs_dim, ad = m[0]->cfg.act_dim, ap = pad16(ad);
+    // A CFGRL group (fql_cfgrl_group_sample_actions): fql_cfgrl_sample_actions_cfgs of every member the same way, with `goals` [K, n, G]
+    // beside the observations and fql_cfgrl_assemble_multi_kernel, whose unconditional half reads each member's own unc_embed leaf.
+    void sample_cfg(const float* obs, const float* goals, const float* noise, const uint64_t* seeds, const float* cfgs, int n, float* out, hipStream_t s) {
+        const int od = m[0]->cfg.obs_dim, ad = m[0]->cfg.act_dim, ap = pad16(ad), Gd = kind == AgentKind::CFGRL ? m[0]->gcfg.goal_dim : 0;
         const bool dev_obs = fql_engine::is_device_ptr(obs), dev_z = noise && fql_engine::is_device_ptr(noise), dev_out = fql_engine::is_device_ptr(out);
-        const bool dev_c = fql_engine::is_device_ptr(cfgs);
+        const bool dev_c = fql_engine::is_device_ptr(cfgs), dev_g = !Gd || fql_engine::is_device_ptr(goals);
         if (!dev_c)
             for (size_t i = 0; i < (size_t)K * n; ++i)
                 if (!std::isfinite(cfgs[i])) invalid("cfgs[%zu][%zu] = %g: every guidance weight must be finite", i / n, i % n, (double)cfgs[i]);
@@ -6822,19 +6842,25 @@ struct fql_group_s {
             Sample& w = sample_ws_cfg(half);
             const Rows o = chunk_rows(obs, dev_obs, w.st_obs, od, n, start, mm, s);
             const Rows z = chunk_rows(noise, dev_z, w.st_noise, ad, n, start, mm, s);
+            const Rows gl = Gd ? chunk_rows(goals, dev_g, w.st_goal, Gd, n, start, mm, s) : Rows{nullptr, 0};
             unsigned char* slot = arg_slot();
             BcAssembleArgs* aa = (BcAssembleArgs*)slot;
-            ExtractArgs* ea = (ExtractArgs*)(slot + (size_t)K * sizeof(BcAssembleArgs));
+            CfgrlAssembleArgs* ga = (CfgrlAssembleArgs*)slot;
+            ExtractArgs* ea = (ExtractArgs*)(slot + (size_t)K * asm_bytes());
             for (int i = 0; i < K; ++i) {
                 fql_engine& e = *m[i];
                 fql_engine::Eval& ev = e.get_eval(2 * half, true);
-                aa[i] = BcAssembleArgs{o.p + i * o.stride, z.p ? z.p + i * z.stride : nullptr, ev.X, ev.Xf, e.seed, seeds ? seeds[i] : 0, mm, half, od, ad,
-                                       e.nets[NET_BC].in_p(), ap, start};
+                const float* zi = z.p ? z.p + i * z.stride : nullptr;
+                if (Gd)
+                    ga[i] = CfgrlAssembleArgs{o.p + i * o.stride, gl.p + i * gl.stride, e.P + e.emb_off, zi, ev.X, ev.Xf, e.seed, seeds ? seeds[i] : 0, mm, half,
+                                              od, Gd, ad, e.nets[NET_BC].in_p(), ap, start};
+                else
+                    aa[i] = BcAssembleArgs{o.p + i * o.stride, zi, ev.X, ev.Xf, e.seed, seeds ? seeds[i] : 0, mm, half, od, ad, e.nets[NET_BC].in_p(), ap, start};
                 ea[i] = ExtractArgs{ev.tgt, dev_out ? out + ((size_t)i * n + start) * ad : w.st_out + (size_t)i * mm * ad, mm, ad, ap};
                 HIP_CHECK(hipMemcpyAsync(ev.cfgs, cfgs + (size_t)i * n + start, (size_t)mm * sizeof(float), hipMemcpyDefault, s));
                 if (half > mm) HIP_CHECK(hipMemsetAsync(ev.cfgs + mm, 0, (size_t)(half - mm) * sizeof(float), s));
             }
-            issue_chunk(w, slot, w.flow, w.extract, !dev_obs || (noise && !dev_z) || !dev_c, dev_out ? nullptr : out, n, start, mm, s);
+            issue_chunk(w, slot, w.flow, w.extract, !dev_obs || (noise && !dev_z) || !dev_c || !dev_g, dev_out ? nullptr : out, n, start, mm, s);
         }
     }
 
@@ -6932,7 +6958,7 @@ struct fql_group_s {
 
 namespace {
 // The update programs a group of `kind` fuses (fql_group_s::progs, in this order): every kind's prog_full; ReBRAC's prog_critic (the
-// critic-only step) behind it; IQL-diffusion's four step kinds.  IFQL and IQL have the one program.
+// critic-only step) behind it; IQL-diffusion's four step kinds.  IFQL, IQL and CFGRL have the one program.
 std::vector<Program fql_engine::*> group_programs(AgentKind kind) {
     std::vector<Program fql_engine::*> p{&fql_engine::prog_full};
     if (kind == AgentKind::REBRAC || kind == AgentKind::IQLD) p.push_back(&fql_engine::prog_critic);
@@ -6944,7 +6970,9 @@ std::vector<Program fql_engine::*> group_programs(AgentKind kind) {
 // softmax_beta (both reach the device as IqldWeightArgs::temp alone); IFQL's expectile (IfqlValueArgs::expectile alone) - kernel arguments,
 // not structure.  An IFQL member's num_samples is structure: it sets the row count of the sampler's workspaces.  IQL's expectile and
 // alpha are arguments (IfqlValueArgs::expectile; IqlAwrArgs / IqlDdpgArgs / IqlActorGradArgs::alpha); its actor_loss and const_std are
-// structure: they choose the launches and the log_stds leaf.
+// structure: they choose the launches and the log_stds leaf.  CFGRL's cfg is the sampler's default guidance weight, an argument of the
+// sampling calls, and its three goal-mixture probabilities reach the device only as CfgrlSrc::thr_traj, p_cur and all_cur, which every
+// update writes per member: arguments too.  goal_dim, flow_steps and p_uncond are structure or shared constants.
 void group_check(const char* fn, AgentKind kind, const fql_handle* members, int k) {
     if (!members || k <= 0) invalid("%s: members must be a non-empty array (k = %d)", fn, k);
     for (int i = 0; i < k; ++i) {
@@ -6975,8 +7003,15 @@ void group_check(const char* fn, AgentKind kind, const fql_handle* members, int 
             qa.expectile = qb.expectile = qa.alpha = qb.alpha = 0.f;
             same = same && std::memcmp(&qa, &qb, sizeof qa) == 0;
         }
+        if (kind == AgentKind::CFGRL) {
+            fql_cfgrl_config ga = h->gcfg, gb = members[0]->gcfg;
+            ga.cfg = gb.cfg = 0.f;
+            ga.actor_p_curgoal = gb.actor_p_curgoal = ga.actor_p_trajgoal = gb.actor_p_trajgoal = ga.actor_p_randomgoal = gb.actor_p_randomgoal = 0;
+            same = same && std::memcmp(&ga, &gb, sizeof ga) == 0;
+        }
         if (!same)
             invalid("%s: member %d's config differs from member 0's in more than seed and %s", fn, i,
+                    kind == AgentKind::CFGRL ? "cfg / actor_p_curgoal / actor_p_trajgoal / actor_p_randomgoal" :
                     kind == AgentKind::REBRAC ? "alpha_actor / alpha_critic" : kind == AgentKind::IQLD ? "awr_temperature / softmax_beta" :
                     kind == AgentKind::IFQL ? "expectile" : kind == AgentKind::IQL ? "expectile / alpha" : "alpha");
         if (h->B != members[0]->B) invalid("%s: member %d has batch size %d, member 0 has %d", fn, i, h->B, members[0]->B);
@@ -7001,7 +7036,8 @@ int group_create(const char* fn, AgentKind kind, const char* want, const fql_han
     *out = nullptr;
     for (int i = 0; members && i < k; ++i)
         if (members[i] && members[i]->kind != kind) {
-            g_create_error = std::string(fn) + ": member " + std::to_string(i) + " is " + members[i]->desc().label + " (" + want + ")";
+            g_create_error = std::string(fn) + ": member " + std::to_string(i) + " is " + members[i]->desc().label + " (" + want +
+                             (members[i]->kind == AgentKind::CFGRL ? "; CFGRL agents are grouped by fql_cfgrl_group_create" : "") + ")";
             return FQL_E_STATE;
         }
     auto* g = new fql_group_s();
@@ -7032,6 +7068,7 @@ int group_create(const char* fn, AgentKind kind, const char* want, const fql_han
         for (int l = 0; l < FQL_LANES; ++l) HIP_CHECK(hipStreamCreateWithFlags(&g->lanes[l], hipStreamNonBlocking));
         for (hipEvent_t* e : {&g->ev_in, &g->ev_done}) HIP_CHECK(hipEventCreateWithFlags(e, hipEventDisableTiming));
         HIP_CHECK(hipMalloc((void**)&g->d_idx, (size_t)k * g->B * sizeof(int64_t)));
+        if (kind == AgentKind::CFGRL) g->d_mask = (unsigned char*)g->galloc((size_t)k * g->B);
         for (size_t p = 0; p < progs.size(); ++p) g->capture(g->progs[p]);
     } catch (const Invalid& e) {
         g_create_error = e.msg; g->release(); delete g; return FQL_E_INVALID;
@@ -7045,19 +7082,35 @@ int group_create(const char* fn, AgentKind kind, const char* want, const fql_han
 
 // One fused update of every member: `gp` is the group's program for the step's kind.  fn: the entry point, for its messages.
 // infos: [k][n_info] - 13 floats of DevState::info, or an IQL-diffusion member's 21 or an IQL member's 16 or 19 of its own buffer
-// (fql_engine::info_src).
-int group_update(fql_group g, const char* fn, GProgram& gp, const int64_t* idx, int batch_size, float* info13xk, void* stream, int n_info = FQL_NUM_INFO) {
+// (fql_engine::info_src).  A CFGRL group: every member's goal source (CfgrlSrc: its goal table, its mixture thresholds and its rows of
+// `do_cfg`, [k][B] bytes, host or device, or NULL = each member's Philox mask) is set beside its dataset source, as
+// fql_cfgrl_update_from_dataset sets them.
+int group_update(fql_group g, const char* fn, GProgram& gp, const int64_t* idx, int batch_size, float* info13xk, void* stream, int n_info = FQL_NUM_INFO,
+                 const unsigned char* do_cfg = nullptr) {
     try {
+        const bool cfgrl = g->kind == AgentKind::CFGRL;
         if (batch_size != g->B) invalid("%s: batch_size %d does not match the members' %d", fn, batch_size, g->B);
         if (g->member_began()) { g_create_error = std::string(fn) + ": a member is between fql_update_begin and fql_update_end"; return FQL_E_STATE; }
+        for (int i = 0; cfgrl && i < g->K; ++i)
+            if (!g->m[i]->ds_final) invalid("%s: member %d has no goal table (fql_cfgrl_dataset_goals after fql_dataset_upload)", fn, i);
         const hipStream_t s = g->enter(stream);
+        const unsigned char* mask = do_cfg;
+        if (do_cfg && !fql_engine::is_device_ptr(do_cfg)) {   // (borrowed for the call only: the wait is the indices' below, or its own)
+            HIP_CHECK(hipMemcpyAsync(g->d_mask, do_cfg, (size_t)g->K * g->B, hipMemcpyHostToDevice, s));
+            if (!idx || fql_engine::is_device_ptr(idx)) HIP_CHECK(hipStreamSynchronize(s));
+            mask = g->d_mask;
+        }
         const int64_t* rows = idx;
         if (idx && !fql_engine::is_device_ptr(idx)) {
             HIP_CHECK(hipMemcpyAsync(g->d_idx, idx, (size_t)g->K * g->B * sizeof(int64_t), hipMemcpyHostToDevice, s));
             HIP_CHECK(hipStreamSynchronize(s));   // (host indices are borrowed for the call only)
             rows = g->d_idx;
         }
-        for (int i = 0; i < g->K; ++i) g->m[i]->source_from_dataset(rows ? rows + (size_t)i * g->B : nullptr, g->B, 0, 0, nullptr, s);
+        for (int i = 0; i < g->K; ++i) {
+            const int64_t* ri = rows ? rows + (size_t)i * g->B : nullptr;
+            if (cfgrl) g->m[i]->cfgrl_source_from_dataset(ri, g->B, 0, 0, nullptr, mask ? mask + (size_t)i * g->B : nullptr, s);
+            else g->m[i]->source_from_dataset(ri, g->B, 0, 0, nullptr, s);
+        }
         HIP_CHECK(hipGraphLaunch(gp.exec, s));
         if (info13xk) {
             for (int i = 0; i < g->K; ++i)
@@ -7082,13 +7135,16 @@ const char* group_call_of(AgentKind kind, GroupCall c) {
     static const char* const ifql[] = {"fql_ifql_group_update_from_dataset", "best of num_samples: fql_ifql_group_sample_actions", "fql_ifql_group_stats", "fql_ifql_group_flow_actions"};
     static const char* const iql[] = {"fql_iql_group_update_from_dataset", "it takes a temperature: fql_iql_group_sample_actions", "fql_iql_group_stats",
                                       "the actor is a Gaussian, there is no flow: fql_iql_group_sample_actions"};
+    static const char* const cfgrl[] = {"it sets each member's goal source: fql_cfgrl_group_update_from_dataset", "it takes goals and guidance weights: fql_cfgrl_group_sample_actions",
+                                        "fql_cfgrl_group_stats", "it takes goals and guidance weights: fql_cfgrl_group_sample_actions"};
+    if (kind == AgentKind::CFGRL) return cfgrl[c];
     return (kind == AgentKind::IQL ? iql : kind == AgentKind::IFQL ? ifql : kind == AgentKind::IQLD ? iqld : kind == AgentKind::REBRAC ? rebrac : fql)[c];
 }
 // A group call on a group of another kind: FQL_E_STATE, naming the call that serves it.  `kind`: the groups `fn` serves; `instead`: what
-// an FQL call says on a ReBRAC group and the reverse; with an IQL-diffusion, IFQL or IQL group on either side, the group's own call for `c`.
+// an FQL call says on a ReBRAC group and the reverse; with an IQL-diffusion, IFQL, IQL or CFGRL group on either side, the group's own call for `c`.
 bool group_wrong_kind(fql_group g, AgentKind kind, const char* fn, const char* instead, GroupCall c) {
     if (g->kind == kind) return false;
-    const auto later = [](AgentKind k) { return k == AgentKind::IQLD || k == AgentKind::IFQL || k == AgentKind::IQL; };
+    const auto later = [](AgentKind k) { return k == AgentKind::IQLD || k == AgentKind::IFQL || k == AgentKind::IQL || k == AgentKind::CFGRL; };
     if (later(g->kind) || later(kind) || !instead) instead = group_call_of(g->kind, c);
     g_create_error = std::string(fn) + " is not available on a group of " + g->m[0]->desc().name + " agents (" + instead + ")";
     return true;
@@ -7111,6 +7167,9 @@ int fql_ifql_group_create(const fql_handle* members, int k, fql_group* out) {
 }
 int fql_iql_group_create(const fql_handle* members, int k, fql_group* out) {
     return group_create("fql_iql_group_create", AgentKind::IQL, "IQL groups take IQL agents only", members, k, out);
+}
+int fql_cfgrl_group_create(const fql_handle* members, int k, fql_group* out) {
+    return group_create("fql_cfgrl_group_create", AgentKind::CFGRL, "CFGRL groups take CFGRL agents only", members, k, out);
 }
 
 // Diagnostic only (not in include/fql_amd.h, beside fql_debug_plan): where each launch of an update program takes its tasks from, as int32 words
@@ -7216,6 +7275,15 @@ int fql_iql_group_update_from_dataset(fql_group g, const int64_t* idx, int batch
     return group_update(g, fn, g->progs[fql_group_s::FULL], idx, batch_size, infoNxk, stream, g->m[0]->num_info());
 }
 
+// fql_cfgrl_update_from_dataset of every CFGRL member in one fused update: the zip of their prog_full behind each member's dataset
+// source and goal source; 4 infos per member
+int fql_cfgrl_group_update_from_dataset(fql_group g, const int64_t* idx, int batch_size, const uint8_t* do_cfg, float* info4xk, void* stream) {
+    const char* fn = "fql_cfgrl_group_update_from_dataset";
+    if (!g) { g_create_error = std::string(fn) + ": NULL group"; return FQL_E_INVALID; }
+    if (group_wrong_kind(g, AgentKind::CFGRL, fn, nullptr, GC_UPDATE)) return FQL_E_STATE;
+    return group_update(g, fn, g->progs[fql_group_s::FULL], idx, batch_size, info4xk, stream, FQL_CFGRL_NUM_INFO, do_cfg);
+}
+
 // The members' sample_actions (flow: compute_flow_actions) in one fused call: fql_group_s::sample between the update's ordering rules
 // (an IFQL group's sample_actions is best of num_samples: fql_group_s::sample_bon)
 static int group_sample(fql_group g, const char* fn, AgentKind kind, const char* instead, bool flow, const float* obs, const float* noise,
@@ -7263,20 +7331,21 @@ int fql_iql_group_sample_actions(fql_group g, const float* observations, int n, 
                                  float* out, void* stream) {
     return group_sample(g, "fql_iql_group_sample_actions", AgentKind::IQL, nullptr, false, observations, noises, seeds, temperature, n, out, stream);
 }
-// fql_iqld_sample_actions_cfgs of every member in one fused call: fql_group_s::sample_cfg between the update's ordering rules
-int fql_iqld_group_sample_actions(fql_group g, const float* observations, int n, const float* noises, const uint64_t* seeds, const float* cfgs,
-                                  float* out, void* stream) {
-    const char* fn = "fql_iqld_group_sample_actions";
+// fql_iqld_sample_actions_cfgs / fql_cfgrl_sample_actions_cfgs of every member in one fused call: fql_group_s::sample_cfg between the
+// update's ordering rules.  goals: a CFGRL group's [k][n][G], which its conditional pass reads
+static int group_sample_cfg(fql_group g, const char* fn, AgentKind kind, const float* observations, const float* goals, int n, const float* noises,
+                            const uint64_t* seeds, const float* cfgs, float* out, void* stream) {
     if (!g) { g_create_error = std::string(fn) + ": NULL group"; return FQL_E_INVALID; }
-    if (group_wrong_kind(g, AgentKind::IQLD, fn, nullptr, GC_SAMPLE)) return FQL_E_STATE;
+    if (group_wrong_kind(g, kind, fn, nullptr, GC_SAMPLE)) return FQL_E_STATE;
     try {
         if (n <= 0) invalid("%s: n must be positive (got %d)", fn, n);
         if (!observations || !out) invalid("%s: observations/out must not be NULL", fn);
+        if (kind == AgentKind::CFGRL && !goals) invalid("%s: goals must not be NULL (the conditional pass reads them: agents/cfgrl.py:93)", fn);
         if (!cfgs) invalid("%s: cfgs must not be NULL (one guidance weight per member and row)", fn);
         if (!noises && !seeds) invalid("%s: seeds must not be NULL when noises is NULL (one seed per member)", fn);
         if (g->member_began()) { g_create_error = std::string(fn) + ": a member is between fql_update_begin and fql_update_end"; return FQL_E_STATE; }
         const hipStream_t s = g->enter(stream);
-        g->sample_cfg(observations, noises, seeds, cfgs, n, out, s);
+        g->sample_cfg(observations, goals, noises, seeds, cfgs, n, out, s);
         g->leave(s, !stream && fql_engine::is_device_ptr(out));
     } catch (const Invalid& e) {
         g_create_error = e.msg; return FQL_E_INVALID;
@@ -7286,6 +7355,14 @@ int fql_iqld_group_sample_actions(fql_group g, const float* observations, int n,
         g_create_error = e.what(); return FQL_E_HIP;
     }
     return FQL_OK;
+}
+int fql_iqld_group_sample_actions(fql_group g, const float* observations, int n, const float* noises, const uint64_t* seeds, const float* cfgs,
+                                  float* out, void* stream) {
+    return group_sample_cfg(g, "fql_iqld_group_sample_actions", AgentKind::IQLD, observations, nullptr, n, noises, seeds, cfgs, out, stream);
+}
+int fql_cfgrl_group_sample_actions(fql_group g, const float* observations, const float* goals, int n, const float* noises, const uint64_t* seeds,
+                                   const float* cfgs, float* out, void* stream) {
+    return group_sample_cfg(g, "fql_cfgrl_group_sample_actions", AgentKind::CFGRL, observations, goals, n, noises, seeds, cfgs, out, stream);
 }
 int fql_group_sample_stats(fql_group g, int flow, int64_t* launches_per_call) {
     if (!g) { g_create_error = "fql_group_sample_stats: NULL group"; return FQL_E_INVALID; }
@@ -7356,6 +7433,21 @@ int fql_iql_group_stats(fql_group g, int64_t* launches_update, int64_t* launches
     try {
         if (launches_update) *launches_update = (int64_t)g->progs[fql_group_s::FULL].launches.size();
         if (launches_sample) *launches_sample = g->sample_launches(false);
+    } catch (const Invalid& e) {
+        g_create_error = e.msg; return FQL_E_INVALID;
+    } catch (const HipError& e) {
+        g_create_error = e.msg; return FQL_E_HIP;
+    }
+    return FQL_OK;
+}
+
+// Launches of a CFGRL group's fused update program and of one fused sampling call on a single chunk, counted from the built programs
+int fql_cfgrl_group_stats(fql_group g, int64_t* launches_update, int64_t* launches_sample) {
+    if (!g) { g_create_error = "fql_cfgrl_group_stats: NULL group"; return FQL_E_INVALID; }
+    if (group_wrong_kind(g, AgentKind::CFGRL, "fql_cfgrl_group_stats", nullptr, GC_STATS)) return FQL_E_STATE;
+    try {
+        if (launches_update) *launches_update = (int64_t)g->progs[fql_group_s::FULL].launches.size();
+        if (launches_sample) *launches_sample = g->sample_launches(true);
     } catch (const Invalid& e) {
         g_create_error = e.msg; return FQL_E_INVALID;
     } catch (const HipError& e) {

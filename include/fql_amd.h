@@ -798,7 +798,8 @@ int fql_iqld_group_stats(fql_group g, int64_t launches[4], int64_t* launches_sam
  * precision != 0, goal_dim outside [1, 1024], probabilities that do not sum to 1.  On a CFGRL handle fql_update*, fql_update_begin* /
  * _end*, fql_total_loss, fql_sample_actions, fql_flow_actions, fql_grad_buckets, frame uploads / updates, fql_replay_*,
  * fql_update_balanced, fql_noise_from_jax_keys, fql_read_info, fql_info_wait and every other kind's calls return FQL_E_STATE, and
- * fql_group_create with such a member returns FQL_E_STATE.  The fql_cfgrl_* calls on another handle return FQL_E_STATE. */
+ * fql_group_create with such a member still returns FQL_E_STATE: CFGRL handles are grouped by fql_cfgrl_group_create (below the guidance
+ * sweeps).  The fql_cfgrl_* calls on another handle return FQL_E_STATE. */
 #define FQL_CFGRL_NUM_INFO 4
 typedef struct fql_cfgrl_config {
     int32_t goal_dim;                 /* G: last axis of example_batch['value_goals']; need not equal obs_dim   */
@@ -854,6 +855,43 @@ int fql_cfgrl_sample_actions_cfgs(fql_handle h, const float* observations, const
 /* launches of one such call of <= 2048 rows, counted from the built program: 4 + S nl + 1 (IQL-diffusion), 3 + S nl + 1 (CFGRL), where
  * fql_iqld_stats / fql_cfgrl_stats report 4 + S (nl + 1) / 3 + S (nl + 1) for the scalar call.  IQL-diffusion and CFGRL handles only. */
 int fql_sample_cfgs_stats(fql_handle h, int64_t* launches_per_call);
+
+/* ---- CFGRL agent groups: a seed x goal-mixture x guidance-weight sweep advanced by one fused program (agent groups, above) ----
+ * fql_cfgrl_group_create: `members` [k], k >= 1, CFGRL handles (another kind: FQL_E_STATE naming it), distinct, in no group, the same
+ * batch size and the same fql_config / fql_cfgrl_config except cfg, actor_p_curgoal, actor_p_trajgoal, actor_p_randomgoal (and the create
+ * seed); anything else - goal_dim, flow_steps, p_uncond, actor_layer_norm, a hidden size, lr - is FQL_E_INVALID naming the member and
+ * the fields that may differ, *out NULL.  cfg is the default guidance weight, an argument of the sampling calls; the three probabilities
+ * reach the device only through each member's goal source, which every update writes.  The group holds ONE fused program, one graph on a
+ * member's single lane: the zip of every member's update (blockIdx.y = member in CFGRL's own kernels, concatenated task tables in the
+ * layers, the weight gradients and Adam).  A member's numbers are bitwise those it has alone, and after a group update it behaves as
+ * after its own: fql_cfgrl_read_rows(probe = 0), fql_read_info_n, fql_cfgrl_policy_loss, its own updates and sampling calls, parameter
+ * access and checkpoints.  fql_group_destroy and fql_group_synchronize serve these groups too; fql_set_batch_size and fql_destroy on a
+ * member return FQL_E_STATE while it is grouped.  fql_group_create and the other kinds' group creates keep refusing CFGRL handles and name
+ * this call.  Errors: fql_last_error(NULL).
+ * Across kinds: every other kind's call that takes a group returns FQL_E_STATE on a CFGRL group, and the three calls below that take a
+ * group return it on a group of another kind, each naming the call that serves the group; a NULL group is FQL_E_INVALID. */
+int fql_cfgrl_group_create(const fql_handle* members, int k, fql_group* out);
+/* fql_cfgrl_update_from_dataset of every member in one fused update.  idx: [k][B] int64, host or device, or NULL = each member's device
+ * RNG.  do_cfg: [k][B] bytes (non-zero = the row's goal is dropped), host or device, or NULL = each member's own Philox mask.  Per
+ * member the call sets the dataset source and the goal source - its goal table (required: without one FQL_E_INVALID naming the member),
+ * its mixture thresholds, its rows of do_cfg - then launches the one graph.  x_0, t, the index draw and the four goal draws are each
+ * member's own Philox.  info4xk: [k][4] in fql_read_info_n's layout (device or host; host = synchronous) or NULL.  Stream and ordering
+ * as fql_group_update_from_dataset. */
+int fql_cfgrl_group_update_from_dataset(fql_group g, const int64_t* idx, int batch_size, const uint8_t* do_cfg, float* info4xk,
+                                        void* stream);
+/* fql_cfgrl_sample_actions_cfgs of every member in one fused call.  observations [k][n][od], goals [k][n][goal_dim] (NULL:
+ * FQL_E_INVALID), noises [k][n][act] or NULL (then seeds [k], each member's Philox), cfgs [k][n] (one guidance weight per member and
+ * row: a scalar cfg or one per member is that value repeated; host: every weight finite, else FQL_E_INVALID; or device), out
+ * [k][n][act]; host or device each.  Per chunk of <= 2048 observations per member: one assemble launch (both halves; the unconditional
+ * half reads each member's own unc_embed leaf), the members' sweep program over concatenated task tables and [k] argument structs, one
+ * extract launch - the launch count of fql_sample_cfgs_stats, whatever k is.  out[i] is bitwise
+ * fql_cfgrl_sample_actions_cfgs(member i, ..., seeds[i], cfgs[i], ...), whose row j is fql_cfgrl_sample_actions at cfg = cfgs[i][j].
+ * Pointer kinds and ordering as fql_group_sample_actions. */
+int fql_cfgrl_group_sample_actions(fql_group g, const float* observations, const float* goals, int n, const float* noises,
+                                   const uint64_t* seeds, const float* cfgs, float* out, void* stream);
+/* Launches of the group's fused update program and of one fused sampling call on a single chunk, counted from the built programs.
+ * Either pointer may be NULL. */
+int fql_cfgrl_group_stats(fql_group g, int64_t* launches_update, int64_t* launches_sample);
 
 #ifdef __cplusplus
 }
