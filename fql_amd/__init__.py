@@ -10,7 +10,7 @@ from .config import get_config
 from .datasets import Dataset, ReplayBuffer
 from .ifql import IFQLAgent, IFQLAgentGroup, IFQL_INFO_KEYS
 from .rebrac import ReBRACAgent, ReBRACAgentGroup, REBRAC_INFO_KEYS, REBRAC_CRITIC_INFO_KEYS
-from .sac import SACAgent, SAC_INFO_KEYS
+from .sac import SACAgent, SACAgentGroup, SAC_INFO_KEYS
 from .bc import BCAgent, BC_INFO_KEYS, train_bc
 from .iql import IQLAgent, IQLAgentGroup, IQL_INFO_KEYS
 from .iql_diffusion import IQLDiffusionAgent, IQLDiffusionAgentGroup, IQLD_INFO_KEYS
@@ -19,5 +19,5 @@ from .cfgrl import CFGRLAgent, CFGRLAgentGroup, CFGRL_INFO_KEYS
 agents = dict(fql=FQLAgent, ifql=IFQLAgent, rebrac=ReBRACAgent, sac=SACAgent, bc=BCAgent, iql=IQLAgent,
               iql_diffusion=IQLDiffusionAgent, cfgrl=CFGRLAgent)
 
-__all__ = ['FQLAgent', 'FQLAgentGroup', 'IFQLAgent', 'IFQLAgentGroup', 'ReBRACAgent', 'ReBRACAgentGroup', 'SACAgent', 'BCAgent', 'IQLAgent', 'IQLAgentGroup', 'IQLDiffusionAgent', 'IQLDiffusionAgentGroup', 'CFGRLAgent', 'CFGRLAgentGroup', 'train_bc', 'get_config', 'agents', 'INFO_KEYS', 'IFQL_INFO_KEYS',
+__all__ = ['FQLAgent', 'FQLAgentGroup', 'IFQLAgent', 'IFQLAgentGroup', 'ReBRACAgent', 'ReBRACAgentGroup', 'SACAgent', 'SACAgentGroup', 'BCAgent', 'IQLAgent', 'IQLAgentGroup', 'IQLDiffusionAgent', 'IQLDiffusionAgentGroup', 'CFGRLAgent', 'CFGRLAgentGroup', 'train_bc', 'get_config', 'agents', 'INFO_KEYS', 'IFQL_INFO_KEYS',
            'REBRAC_INFO_KEYS', 'REBRAC_CRITIC_INFO_KEYS', 'SAC_INFO_KEYS', 'BC_INFO_KEYS', 'IQL_INFO_KEYS', 'IQLD_INFO_KEYS', 'CFGRL_INFO_KEYS', 'NOISE_KEYS', 'Dataset', 'ReplayBuffer']

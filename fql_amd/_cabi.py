@@ -204,6 +204,11 @@ SYMBOLS = {
     'fql_cfgrl_group_update_from_dataset': (_I, [_VP, _VP, _I, _VP, _VP, _VP]),
     'fql_cfgrl_group_sample_actions': (_I, [_VP, _VP, _VP, _I, _VP, _VP, _VP, _VP, _VP]),
     'fql_cfgrl_group_stats': (_I, [_VP, C.POINTER(_I64), C.POINTER(_I64)]),
+    'fql_sac_group_create': (_I, [_VP, _I, C.POINTER(_VP)]),
+    'fql_sac_group_update_from_dataset': (_I, [_VP, _VP, _I, _VP, _VP]),
+    'fql_sac_group_update_balanced': (_I, [_VP, _VP, _VP, _I, _VP, _VP]),
+    'fql_sac_group_sample_actions': (_I, [_VP, _VP, _I, _VP, _VP, _F, _VP, _VP]),
+    'fql_sac_group_stats': (_I, [_VP, C.POINTER(_I64), C.POINTER(_I64)]),
     'fql_cfgrl_default_config': (None, [C.POINTER(FqlCfgrlConfig)]),
     'fql_cfgrl_create': (_I, [C.POINTER(FqlConfig), C.POINTER(FqlCfgrlConfig), _U64, C.POINTER(_VP)]),
     'fql_cfgrl_update': (_I, [_VP, _VP, _VP, _VP, _I, C.POINTER(FqlNoise), _VP, _VP, _VP]),

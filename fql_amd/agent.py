@@ -948,7 +948,7 @@ class FQLAgentGroup:
         if len(alphas) != len(seeds):
             raise ValueError(f'{len(seeds)} seeds but {len(alphas)} alphas')
         if cfg.get('agent_name') == 'sac':
-            raise NotImplementedError('agent groups take FQL agents only (SAC groups are not available)')
+            raise NotImplementedError('agent groups take FQL agents only (SAC agents are grouped by SACAgentGroup)')
         if cfg.get('agent_name') == 'iql':
             raise NotImplementedError('agent groups take FQL agents only (IQL agents are grouped by IQLAgentGroup)')
         if cfg.get('agent_name') == 'cfgrl':

@@ -6385,7 +6385,9 @@ int fql_update_from_frames(fql_handle h, const int64_t* idx, const int32_t* crop
 // DESIGN.md section 25), whose group holds the one fused program - IFQL's value and critic lanes beside the Gaussian actor's own
 // kernels - and a sampler that ends in the multi-instance form of IQL's sampling head; or CFGRL members (fql_cfgrl_group_create;
 // DESIGN.md section 26), whose group holds the one fused program - BC's single lane, each member's goal source (CfgrlSrc) set per
-// update - and a sampler that zips the members' sweep program behind the multi-instance form of CFGRL's two-half row assembly.
+// update - and a sampler that zips the members' sweep program behind the multi-instance form of CFGRL's two-half row assembly; or SAC
+// members (fql_sac_group_create), whose group holds the one fused program, entered with each member's dataset
+// source or with its two-source balanced one (the member's own replay ring), and a sampler that ends in SAC's action kernel.
 // ================================================================================================
 namespace {
 
@@ -6457,6 +6459,13 @@ const std::map<const void*, MultiEntry>& multi_entries() {
         FQL_MULTI(fql_cfgrl_assemble_kernel, fql_cfgrl_assemble_multi_kernel, CfgrlAssembleArgs);
         FQL_MULTI(fql_cfgrl_layer0_kernel, fql_cfgrl_layer0_multi_kernel, CfgrlLayer0Args);
         FQL_MULTI(fql_cfgrl_cfg_layer0_kernel, fql_cfgrl_cfg_layer0_multi_kernel, CfgrlCfgLayer0Args);
+        // SAC (fql_sac.h): the update program; the sampler's last launch is the act kernel's multi-instance entry, bound by sample_ws
+        FQL_MULTI(fql_sac_prep_kernel, fql_sac_prep_multi_kernel, SacPrepArgs);
+        FQL_MULTI(fql_sac_act_kernel, fql_sac_act_multi_kernel, SacActArgs);
+        FQL_MULTI(fql_sac_loss_critic_kernel, fql_sac_loss_critic_multi_kernel, SacCriticArgs);
+        FQL_MULTI(fql_sac_loss_actor_kernel, fql_sac_loss_actor_multi_kernel, SacActorArgs);
+        FQL_MULTI(fql_sac_actor_grad_kernel, fql_sac_actor_grad_multi_kernel, SacActorGradArgs);
+        FQL_MULTI(fql_sac_finalize_kernel, fql_sac_finalize_multi_kernel, FinalizeArgs);
 #undef FQL_MULTI
         return e;
     }();
@@ -6488,7 +6497,7 @@ struct GProgram {
 
 struct fql_group_s {
     std::vector<fql_handle> m;
-    AgentKind kind = AgentKind::FQL;     // the members' kind: FQL (fql_group_create), ReBRAC (fql_rebrac_group_create), IQL-diffusion (fql_iqld_group_create), IFQL (fql_ifql_group_create), IQL (fql_iql_group_create) or CFGRL (fql_cfgrl_group_create)
+    AgentKind kind = AgentKind::FQL;     // the members' kind: FQL (fql_group_create), ReBRAC (fql_rebrac_group_create), IQL-diffusion (fql_iqld_group_create), IFQL (fql_ifql_group_create), IQL (fql_iql_group_create), CFGRL (fql_cfgrl_group_create) or SAC (fql_sac_group_create)
     int K = 0, B = 0;
     hipStream_t lanes[FQL_LANES] = {};   // lane 0 = the group's own stream
     // One fused program per entry of group_programs(kind), in its order.  [0]: the members' prog_full zipped (every kind); [1]: their
@@ -6617,9 +6626,9 @@ struct fql_group_s {
         std::vector<GLaunch> q;            // an IFQL group's best-of-N sampler: the members' critic pair (Eval::prog_q) zipped
         float *st_obs = nullptr, *st_noise = nullptr, *st_out = nullptr;
         float* st_goal = nullptr;          // a CFGRL group: staging of host goals
-        unsigned char* d_args = nullptr;   // [K] AssembleArgs, then [K] ExtractArgs (a ReBRAC group: [K] RebracActArgs; an IQL group: [K] IqlSampleArgs)
+        unsigned char* d_args = nullptr;   // [K] AssembleArgs, then [K] ExtractArgs (a ReBRAC group: [K] RebracActArgs; an IQL group: [K] IqlSampleArgs; a SAC group: [K] SacActArgs)
         Bound assemble, extract;           // the multi-instance launches over d_args, blockIdx.y = member
-        Bound act;                         // a ReBRAC group: fql_rebrac_act_multi_kernel writes the actions, no extract launch; an IQL group: fql_iql_sample_multi_kernel
+        Bound act;                         // a ReBRAC group: fql_rebrac_act_multi_kernel writes the actions, no extract launch; an IQL group: fql_iql_sample_multi_kernel; a SAC group: fql_sac_act_multi_kernel
         // an IFQL group's best-of-N sampler, over the other layout of d_args: [K] IfqlRepeatArgs, [K] IfqlQinArgs, [K] IfqlSelectArgs
         Bound repeat, qin, select;
     };
@@ -6633,12 +6642,12 @@ struct fql_group_s {
     char arg_state[kArgRing] = {};   // 0 = free, 1 = behind arg_ev, 2 = on the legacy stream
     int arg_pos = 0;
     // (a slot holds the layout of the group's kind: [K] AssembleArgs + [K] ExtractArgs, [K] AssembleArgs + [K] RebracActArgs, an IQL
-    // group's [K] AssembleArgs + [K] IqlSampleArgs, or an IQL-diffusion group's [K] BcAssembleArgs + [K] ExtractArgs; an IFQL group's
+    // group's [K] AssembleArgs + [K] IqlSampleArgs, a SAC group's [K] AssembleArgs + [K] SacActArgs, or an IQL-diffusion group's [K] BcAssembleArgs + [K] ExtractArgs; an IFQL group's
     // flow call uses the first, its best-of-N call [K] IfqlRepeatArgs + [K] IfqlQinArgs + [K] IfqlSelectArgs; a CFGRL group's
     // [K] CfgrlAssembleArgs + [K] ExtractArgs)
     size_t asm_bytes() const { return kind == AgentKind::IQLD ? sizeof(BcAssembleArgs) : kind == AgentKind::CFGRL ? sizeof(CfgrlAssembleArgs) : sizeof(AssembleArgs); }
     size_t bon_bytes() const { return kind == AgentKind::IFQL ? sizeof(IfqlRepeatArgs) + sizeof(IfqlQinArgs) + sizeof(IfqlSelectArgs) : 0; }
-    size_t arg_bytes() const { return (size_t)K * std::max(asm_bytes() + std::max({sizeof(ExtractArgs), sizeof(RebracActArgs), sizeof(IqlSampleArgs)}), bon_bytes()); }
+    size_t arg_bytes() const { return (size_t)K * std::max(asm_bytes() + std::max({sizeof(ExtractArgs), sizeof(RebracActArgs), sizeof(IqlSampleArgs), sizeof(SacActArgs)}), bon_bytes()); }
 
     Sample& sample_ws(int n_pad, bool flow) {
         std::unique_ptr<Sample>& slot = samples[n_pad];
@@ -6656,6 +6665,9 @@ struct fql_group_s {
             if (kind == AgentKind::IQL)   // (grid x over the padded rows: a chunk's m <= n_pad, elements past m * ad return at once)
                 w->act = bind(fql_iql_sample_multi_kernel, Geo(dim3((n_pad * ad + FQL_THREADS - 1) / FQL_THREADS, K), dim3(FQL_THREADS), 0),
                               (const IqlSampleArgs*)(w->d_args + (size_t)K * sizeof(AssembleArgs)));
+            else if (kind == AgentKind::SAC)   // (one thread per row; rows past a chunk's m return at once)
+                w->act = bind(fql_sac_act_multi_kernel, Geo(dim3((n_pad + FQL_THREADS - 1) / FQL_THREADS, K), dim3(FQL_THREADS), 0),
+                              (const SacActArgs*)(w->d_args + (size_t)K * sizeof(AssembleArgs)));
             else if (kind != AgentKind::REBRAC)
                 w->extract = bind(fql_extract_multi_kernel, Geo(dim3((n_pad * ad + 255) / 256, K), dim3(256), 0),
                                   (const ExtractArgs*)(w->d_args + (size_t)K * sizeof(AssembleArgs)));
@@ -6715,7 +6727,7 @@ struct fql_group_s {
         return w;
     }
     // launches of one fused sampling call on a single chunk, counted from the built program: assemble, the zipped launches, extract
-    // (a ReBRAC or IQL group: the kind's action kernel in extract's place; an IFQL group's best-of-N call: repeat, the flow, qin, the
+    // (a ReBRAC, IQL or SAC group: the kind's action kernel in extract's place; an IFQL group's best-of-N call: repeat, the flow, qin, the
     // critic pair, select)
     int64_t sample_launches(bool flow) {
         if (kind == AgentKind::IQLD || kind == AgentKind::CFGRL) return 2 + (int64_t)sample_ws_cfg(16).flow.size();
@@ -6761,9 +6773,11 @@ struct fql_group_s {
     // fql_rebrac_act_multi_kernel, which writes the actions where extract-multi would - every argument as fql_engine::sample_actor fills it.
     // An IQL group (fql_iql_group_sample_actions): the same two launches around the actor's forward, then fql_iql_sample_multi_kernel on the
     // means - each member's own row numbers (row0 = start), seed, key and log_stds (P + ls_off, null under const_std), one temperature.
+    // A SAC group (fql_sac_group_sample_actions): the same again around the actor's forward, whose last layer is the [H, 2 ap] head layer,
+    // then fql_sac_act_multi_kernel on the heads - noise_mode 1 or 2, clip_out 1, no lp, row0 and seed as fql_engine::sample_actor sets them.
     void sample(bool flow, const float* obs, const float* noise, const uint64_t* seeds, float temperature, int n, float* out, hipStream_t s) {
         const int od = m[0]->cfg.obs_dim, ad = m[0]->cfg.act_dim, ap = pad16(ad);
-        const bool rebrac = kind == AgentKind::REBRAC, iql = kind == AgentKind::IQL;
+        const bool rebrac = kind == AgentKind::REBRAC, iql = kind == AgentKind::IQL, sac = kind == AgentKind::SAC;
         const bool dev_obs = fql_engine::is_device_ptr(obs), dev_z = noise && fql_engine::is_device_ptr(noise), dev_out = fql_engine::is_device_ptr(out);
         for (int start = 0; start < n; start += 4096) {
             const int mm = std::min(4096, n - start);
@@ -6775,16 +6789,19 @@ struct fql_group_s {
             ExtractArgs* ea = (ExtractArgs*)(slot + (size_t)K * sizeof(AssembleArgs));
             RebracActArgs* ra = (RebracActArgs*)(slot + (size_t)K * sizeof(AssembleArgs));
             IqlSampleArgs* qa = (IqlSampleArgs*)(slot + (size_t)K * sizeof(AssembleArgs));
+            SacActArgs* sa = (SacActArgs*)(slot + (size_t)K * sizeof(AssembleArgs));
             for (int i = 0; i < K; ++i) {
                 fql_engine& e = *m[i];
                 fql_engine::Eval& ev = e.get_eval(w.n_pad);
-                if (rebrac || iql) {
+                if (rebrac || iql || sac) {
                     const uint64_t sd = seeds ? seeds[i] : 0;
                     const float* zi = z.p ? z.p + i * z.stride : nullptr;
                     float* dst = dev_out ? out + ((size_t)i * n + start) * ad : w.st_out + (size_t)i * mm * ad;
                     aa[i] = AssembleArgs{o.p + i * o.stride, nullptr, ev.X, e.seed, sd, mm, w.n_pad, od, 0, e.nets[NET_BC].in_p()};   // [obs | 0]
                     if (iql)
                         qa[i] = IqlSampleArgs{ev.p_os.out, e.qcfg.const_std ? nullptr : e.P + e.ls_off, zi, dst, e.seed, sd, mm, ad, ap, start, temperature};
+                    else if (sac)
+                        sa[i] = SacActArgs{ev.p_os.out, zi, dst, dst, nullptr, e.seed, sd, mm, ad, ap, ad, ad, 0, start, mm, zi ? 1 : 2, e.scfg.tanh_squash, 1, temperature};
                     else
                         ra[i] = RebracActArgs{ev.p_os.out, zi, dst, e.seed, sd, mm, ad, ap, ad, ad, 0, start, zi ? 1 : 2, e.rcfg.tanh_squash, 1,
                                               e.rcfg.actor_noise * temperature, e.rcfg.actor_noise_clip};
@@ -6794,7 +6811,7 @@ struct fql_group_s {
                                      (seeds ? seeds[i] : 0) + (uint64_t)start, mm, w.n_pad, od, ad, flow ? e.nets[NET_BC].in_p() : e.nets[NET_OS].in_p()};
                 ea[i] = ExtractArgs{flow ? ev.tgt : ev.p_os.out, dev_out ? out + ((size_t)i * n + start) * ad : w.st_out + (size_t)i * mm * ad, mm, ad, ap};
             }
-            issue_chunk(w, slot, flow ? w.flow : w.os, rebrac || iql ? w.act : w.extract, !dev_obs || (noise && !dev_z), dev_out ? nullptr : out, n, start, mm, s);
+            issue_chunk(w, slot, flow ? w.flow : w.os, rebrac || iql || sac ? w.act : w.extract, !dev_obs || (noise && !dev_z), dev_out ? nullptr : out, n, start, mm, s);
         }
     }
     // The tail of a chunk of either sampler: the slot's argument structs to the device with the ring's event behind them, the wait that
@@ -6958,7 +6975,7 @@ struct fql_group_s {
 
 namespace {
 // The update programs a group of `kind` fuses (fql_group_s::progs, in this order): every kind's prog_full; ReBRAC's prog_critic (the
-// critic-only step) behind it; IQL-diffusion's four step kinds.  IFQL, IQL and CFGRL have the one program.
+// critic-only step) behind it; IQL-diffusion's four step kinds.  IFQL, IQL, CFGRL and SAC have the one program.
 std::vector<Program fql_engine::*> group_programs(AgentKind kind) {
     std::vector<Program fql_engine::*> p{&fql_engine::prog_full};
     if (kind == AgentKind::REBRAC || kind == AgentKind::IQLD) p.push_back(&fql_engine::prog_critic);
@@ -6972,7 +6989,9 @@ std::vector<Program fql_engine::*> group_programs(AgentKind kind) {
 // alpha are arguments (IfqlValueArgs::expectile; IqlAwrArgs / IqlDdpgArgs / IqlActorGradArgs::alpha); its actor_loss and const_std are
 // structure: they choose the launches and the log_stds leaf.  CFGRL's cfg is the sampler's default guidance weight, an argument of the
 // sampling calls, and its three goal-mixture probabilities reach the device only as CfgrlSrc::thr_traj, p_cur and all_cur, which every
-// update writes per member: arguments too.  goal_dim, flow_steps and p_uncond are structure or shared constants.
+// update writes per member: arguments too.  goal_dim, flow_steps and p_uncond are structure or shared constants.  SAC's target_entropy
+// (and the multiplier it is derived from when NaN) reaches the device as SacActorArgs::target_entropy alone: an argument; tanh_squash,
+// backup_entropy, q_agg and the rest choose kernel arguments every member shares.
 void group_check(const char* fn, AgentKind kind, const fql_handle* members, int k) {
     if (!members || k <= 0) invalid("%s: members must be a non-empty array (k = %d)", fn, k);
     for (int i = 0; i < k; ++i) {
@@ -7009,8 +7028,14 @@ void group_check(const char* fn, AgentKind kind, const fql_handle* members, int 
             ga.actor_p_curgoal = gb.actor_p_curgoal = ga.actor_p_trajgoal = gb.actor_p_trajgoal = ga.actor_p_randomgoal = gb.actor_p_randomgoal = 0;
             same = same && std::memcmp(&ga, &gb, sizeof ga) == 0;
         }
+        if (kind == AgentKind::SAC) {   // (target_entropy may be NaN = automatic: zeroed before the compare, like the multiplier)
+            fql_sac_config sa = h->scfg, sb = members[0]->scfg;
+            sa.target_entropy = sb.target_entropy = sa.target_entropy_multiplier = sb.target_entropy_multiplier = 0.f;
+            same = same && std::memcmp(&sa, &sb, sizeof sa) == 0;
+        }
         if (!same)
             invalid("%s: member %d's config differs from member 0's in more than seed and %s", fn, i,
+                    kind == AgentKind::SAC ? "target_entropy / target_entropy_multiplier" :
                     kind == AgentKind::CFGRL ? "cfg / actor_p_curgoal / actor_p_trajgoal / actor_p_randomgoal" :
                     kind == AgentKind::REBRAC ? "alpha_actor / alpha_critic" : kind == AgentKind::IQLD ? "awr_temperature / softmax_beta" :
                     kind == AgentKind::IFQL ? "expectile" : kind == AgentKind::IQL ? "expectile / alpha" : "alpha");
@@ -7084,13 +7109,26 @@ int group_create(const char* fn, AgentKind kind, const char* want, const fql_han
 // infos: [k][n_info] - 13 floats of DevState::info, or an IQL-diffusion member's 21 or an IQL member's 16 or 19 of its own buffer
 // (fql_engine::info_src).  A CFGRL group: every member's goal source (CfgrlSrc: its goal table, its mixture thresholds and its rows of
 // `do_cfg`, [k][B] bytes, host or device, or NULL = each member's Philox mask) is set beside its dataset source, as
-// fql_cfgrl_update_from_dataset sets them.
+// fql_cfgrl_update_from_dataset sets them.  balanced (a SAC group's fql_sac_group_update_balanced): every member's source is its
+// two-source one (fql_engine::source_balanced: B / 2 rows of its dataset, B / 2 of its own replay ring); idx and idx_rb are [k][B / 2]
+// each, both or neither, host or device, staged into each member's index buffer as its own call stages them.  Every member is checked
+// before any member's source is written: a refusal leaves every member where it was.
 int group_update(fql_group g, const char* fn, GProgram& gp, const int64_t* idx, int batch_size, float* info13xk, void* stream, int n_info = FQL_NUM_INFO,
-                 const unsigned char* do_cfg = nullptr) {
+                 const unsigned char* do_cfg = nullptr, bool balanced = false, const int64_t* idx_rb = nullptr) {
     try {
         const bool cfgrl = g->kind == AgentKind::CFGRL;
         if (batch_size != g->B) invalid("%s: batch_size %d does not match the members' %d", fn, batch_size, g->B);
         if (g->member_began()) { g_create_error = std::string(fn) + ": a member is between fql_update_begin and fql_update_end"; return FQL_E_STATE; }
+        if (balanced) {
+            if (g->B % 2) invalid("%s: balanced sampling draws batch_size // 2 rows from each source: batch_size %d must be even", fn, g->B);
+            if (!idx != !idx_rb) invalid("%s: balanced sampling: give both index arrays or neither", fn);
+            for (int i = 0; i < g->K; ++i) {
+                const fql_engine& e = *g->m[i];
+                if (e.ds_size <= 0 || !e.ds_obs) invalid("%s: member %d has no training dataset uploaded", fn, i);
+                if (e.rb_cap <= 0) invalid("%s: member %d has no replay ring (fql_replay_create)", fn, i);
+                if (e.rb_size <= 0) invalid("%s: member %d's replay ring is empty (the reference would draw randint(0), a ValueError)", fn, i);
+            }
+        }
         for (int i = 0; cfgrl && i < g->K; ++i)
             if (!g->m[i]->ds_final) invalid("%s: member %d has no goal table (fql_cfgrl_dataset_goals after fql_dataset_upload)", fn, i);
         const hipStream_t s = g->enter(stream);
@@ -7101,7 +7139,7 @@ int group_update(fql_group g, const char* fn, GProgram& gp, const int64_t* idx, 
             mask = g->d_mask;
         }
         const int64_t* rows = idx;
-        if (idx && !fql_engine::is_device_ptr(idx)) {
+        if (idx && !balanced && !fql_engine::is_device_ptr(idx)) {
             HIP_CHECK(hipMemcpyAsync(g->d_idx, idx, (size_t)g->K * g->B * sizeof(int64_t), hipMemcpyHostToDevice, s));
             HIP_CHECK(hipStreamSynchronize(s));   // (host indices are borrowed for the call only)
             rows = g->d_idx;
@@ -7109,6 +7147,7 @@ int group_update(fql_group g, const char* fn, GProgram& gp, const int64_t* idx, 
         for (int i = 0; i < g->K; ++i) {
             const int64_t* ri = rows ? rows + (size_t)i * g->B : nullptr;
             if (cfgrl) g->m[i]->cfgrl_source_from_dataset(ri, g->B, 0, 0, nullptr, mask ? mask + (size_t)i * g->B : nullptr, s);
+            else if (balanced) g->m[i]->source_balanced(idx ? idx + (size_t)i * (g->B / 2) : nullptr, idx_rb ? idx_rb + (size_t)i * (g->B / 2) : nullptr, nullptr, g->B, nullptr, s);
             else g->m[i]->source_from_dataset(ri, g->B, 0, 0, nullptr, s);
         }
         HIP_CHECK(hipGraphLaunch(gp.exec, s));
@@ -7137,14 +7176,17 @@ const char* group_call_of(AgentKind kind, GroupCall c) {
                                       "the actor is a Gaussian, there is no flow: fql_iql_group_sample_actions"};
     static const char* const cfgrl[] = {"it sets each member's goal source: fql_cfgrl_group_update_from_dataset", "it takes goals and guidance weights: fql_cfgrl_group_sample_actions",
                                         "fql_cfgrl_group_stats", "it takes goals and guidance weights: fql_cfgrl_group_sample_actions"};
+    static const char* const sac[] = {"fql_sac_group_update_from_dataset (or fql_sac_group_update_balanced)", "it takes a temperature: fql_sac_group_sample_actions", "fql_sac_group_stats",
+                                      "the actor is a Gaussian, there is no flow: fql_sac_group_sample_actions"};
     if (kind == AgentKind::CFGRL) return cfgrl[c];
+    if (kind == AgentKind::SAC) return sac[c];
     return (kind == AgentKind::IQL ? iql : kind == AgentKind::IFQL ? ifql : kind == AgentKind::IQLD ? iqld : kind == AgentKind::REBRAC ? rebrac : fql)[c];
 }
 // A group call on a group of another kind: FQL_E_STATE, naming the call that serves it.  `kind`: the groups `fn` serves; `instead`: what
-// an FQL call says on a ReBRAC group and the reverse; with an IQL-diffusion, IFQL, IQL or CFGRL group on either side, the group's own call for `c`.
+// an FQL call says on a ReBRAC group and the reverse; with an IQL-diffusion, IFQL, IQL, CFGRL or SAC group on either side, the group's own call for `c`.
 bool group_wrong_kind(fql_group g, AgentKind kind, const char* fn, const char* instead, GroupCall c) {
     if (g->kind == kind) return false;
-    const auto later = [](AgentKind k) { return k == AgentKind::IQLD || k == AgentKind::IFQL || k == AgentKind::IQL || k == AgentKind::CFGRL; };
+    const auto later = [](AgentKind k) { return k == AgentKind::IQLD || k == AgentKind::IFQL || k == AgentKind::IQL || k == AgentKind::CFGRL || k == AgentKind::SAC; };
     if (later(g->kind) || later(kind) || !instead) instead = group_call_of(g->kind, c);
     g_create_error = std::string(fn) + " is not available on a group of " + g->m[0]->desc().name + " agents (" + instead + ")";
     return true;
@@ -7170,6 +7212,9 @@ int fql_iql_group_create(const fql_handle* members, int k, fql_group* out) {
 }
 int fql_cfgrl_group_create(const fql_handle* members, int k, fql_group* out) {
     return group_create("fql_cfgrl_group_create", AgentKind::CFGRL, "CFGRL groups take CFGRL agents only", members, k, out);
+}
+int fql_sac_group_create(const fql_handle* members, int k, fql_group* out) {
+    return group_create("fql_sac_group_create", AgentKind::SAC, "SAC groups take SAC agents only", members, k, out);
 }
 
 // Diagnostic only (not in include/fql_amd.h, beside fql_debug_plan): where each launch of an update program takes its tasks from, as int32 words
@@ -7284,6 +7329,21 @@ int fql_cfgrl_group_update_from_dataset(fql_group g, const int64_t* idx, int bat
     return group_update(g, fn, g->progs[fql_group_s::FULL], idx, batch_size, info4xk, stream, FQL_CFGRL_NUM_INFO, do_cfg);
 }
 
+// fql_sac_update_from_dataset of every SAC member in one fused update: the zip of their prog_full; 14 infos per member
+int fql_sac_group_update_from_dataset(fql_group g, const int64_t* idx, int batch_size, float* info14xk, void* stream) {
+    const char* fn = "fql_sac_group_update_from_dataset";
+    if (!g) { g_create_error = std::string(fn) + ": NULL group"; return FQL_E_INVALID; }
+    if (group_wrong_kind(g, AgentKind::SAC, fn, nullptr, GC_UPDATE)) return FQL_E_STATE;
+    return group_update(g, fn, g->progs[fql_group_s::FULL], idx, batch_size, info14xk, stream, FQL_SAC_NUM_INFO);
+}
+// fql_sac_update_balanced of every SAC member in one fused update: the same program behind each member's two-source descriptor
+int fql_sac_group_update_balanced(fql_group g, const int64_t* idx_dataset, const int64_t* idx_replay, int batch_size, float* info14xk, void* stream) {
+    const char* fn = "fql_sac_group_update_balanced";
+    if (!g) { g_create_error = std::string(fn) + ": NULL group"; return FQL_E_INVALID; }
+    if (group_wrong_kind(g, AgentKind::SAC, fn, nullptr, GC_UPDATE)) return FQL_E_STATE;
+    return group_update(g, fn, g->progs[fql_group_s::FULL], idx_dataset, batch_size, info14xk, stream, FQL_SAC_NUM_INFO, nullptr, true, idx_replay);
+}
+
 // The members' sample_actions (flow: compute_flow_actions) in one fused call: fql_group_s::sample between the update's ordering rules
 // (an IFQL group's sample_actions is best of num_samples: fql_group_s::sample_bon)
 static int group_sample(fql_group g, const char* fn, AgentKind kind, const char* instead, bool flow, const float* obs, const float* noise,
@@ -7330,6 +7390,10 @@ int fql_ifql_group_flow_actions(fql_group g, const float* observations, const fl
 int fql_iql_group_sample_actions(fql_group g, const float* observations, int n, const float* noises, const uint64_t* seeds, float temperature,
                                  float* out, void* stream) {
     return group_sample(g, "fql_iql_group_sample_actions", AgentKind::IQL, nullptr, false, observations, noises, seeds, temperature, n, out, stream);
+}
+int fql_sac_group_sample_actions(fql_group g, const float* observations, int n, const float* noises, const uint64_t* seeds, float temperature,
+                                 float* out, void* stream) {
+    return group_sample(g, "fql_sac_group_sample_actions", AgentKind::SAC, nullptr, false, observations, noises, seeds, temperature, n, out, stream);
 }
 // fql_iqld_sample_actions_cfgs / fql_cfgrl_sample_actions_cfgs of every member in one fused call: fql_group_s::sample_cfg between the
 // update's ordering rules.  goals: a CFGRL group's [k][n][G], which its conditional pass reads
@@ -7448,6 +7512,21 @@ int fql_cfgrl_group_stats(fql_group g, int64_t* launches_update, int64_t* launch
     try {
         if (launches_update) *launches_update = (int64_t)g->progs[fql_group_s::FULL].launches.size();
         if (launches_sample) *launches_sample = g->sample_launches(true);
+    } catch (const Invalid& e) {
+        g_create_error = e.msg; return FQL_E_INVALID;
+    } catch (const HipError& e) {
+        g_create_error = e.msg; return FQL_E_HIP;
+    }
+    return FQL_OK;
+}
+
+// Launches of a SAC group's fused update program and of one fused sampling call on a single chunk, counted from the built programs
+int fql_sac_group_stats(fql_group g, int64_t* launches_update, int64_t* launches_sample) {
+    if (!g) { g_create_error = "fql_sac_group_stats: NULL group"; return FQL_E_INVALID; }
+    if (group_wrong_kind(g, AgentKind::SAC, "fql_sac_group_stats", nullptr, GC_STATS)) return FQL_E_STATE;
+    try {
+        if (launches_update) *launches_update = (int64_t)g->progs[fql_group_s::FULL].launches.size();
+        if (launches_sample) *launches_sample = g->sample_launches(false);
     } catch (const Invalid& e) {
         g_create_error = e.msg; return FQL_E_INVALID;
     } catch (const HipError& e) {

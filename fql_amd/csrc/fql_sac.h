@@ -3,6 +3,8 @@
 // actor losses (with the temperature's own loss and gradient), the gradient handed to the actor's two heads and the info layout of the
 // finalize step.  The GEMM bodies, weight gradients, LayerNorm backward, the critic's input gradient, Adam + Polyak and the grad
 // statistics are FQL's.  Every reduction runs in one workgroup in a fixed order (no float atomics).
+// Every kernel a SAC agent group fuses (fql_sac_group_*) comes in three parts: a __device__ body, the by-value
+// entry a single handle launches, and a *_multi_kernel that takes a device array of the same argument struct, one per member.
 //
 // The actor's two heads (mean_net, log_std_net) are one [H, 2 ap] layer of the arena: columns [0, ap) the mean, [ap, 2 ap) the raw
 // log-std (the leaves read back as separate [H, act] / [act] arrays, build_leaves()).
@@ -31,7 +33,7 @@ struct SacPrepArgs {
 // utils/datasets.py:64-100 (index draw and gather, from one source or the two of a balanced batch, main.py:255-259) and the raw N(0, 1) of
 // the two samples (agents/sac.py:27,62): eps_n = fql_noise.eps1 or Philox tensor 1, eps_c = fql_noise.eps2 or Philox tensor 5.  One wave
 // per transition.
-__global__ __launch_bounds__(FQL_THREADS) void fql_sac_prep_kernel(SacPrepArgs P) {
+__device__ __forceinline__ void fql_sac_prep_body(const SacPrepArgs P) {
     const SrcDesc& S = *P.src;
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int b = blockIdx.x * 4 + wave;
@@ -74,6 +76,12 @@ __global__ __launch_bounds__(FQL_THREADS) void fql_sac_prep_kernel(SacPrepArgs P
         P.w_mask[b] = (second ? S.mask2 : S.mask)[src];
     }
 }
+__global__ __launch_bounds__(FQL_THREADS) void fql_sac_prep_kernel(SacPrepArgs P) { fql_sac_prep_body(P); }
+// Multi-instance entry points (SAC agent groups), here and below: blockIdx.y picks the member, its argument struct comes from a device
+// array, read through the constant address space (scalar loads, as from the kernel-argument segment; fql_kernels.h FQL_CONST_AS).
+// Shared-memory arrays are declared in the entries and handed to the body: the single-workgroup kernels run as grid (1, members), each
+// workgroup the member's own fixed-order reduction.  Grid x = rows / 4.
+__global__ __launch_bounds__(FQL_THREADS) void fql_sac_prep_multi_kernel(const SacPrepArgs* __restrict__ args) { const SacPrepArgs P = ((const FQL_CONST_AS SacPrepArgs*)args)[blockIdx.y]; fql_sac_prep_body(P); }
 
 // softplus(y) = log(1 + e^y) without overflow for large |y|
 __device__ __forceinline__ float sac_softplus(float y) { return fmaxf(y, 0.0f) + log1pf(expf(-fabsf(y))); }
@@ -94,7 +102,7 @@ struct SacActArgs {
 // temperature eps, a = tanh(x) (or x); distrax's sample_and_log_prob: log_prob = sum_j (-eps_j^2 / 2 - log(exp(ls_j) temperature) -
 // log(2 pi) / 2) - [tanh] sum_j 2 (log 2 - x_j - softplus(-2 x_j)).  sample_actions (sac.py:136-149) adds the [-1, 1] clip.  One thread
 // per row; accurate transcendentals.
-__global__ __launch_bounds__(FQL_THREADS) void fql_sac_act_kernel(SacActArgs P) {
+__device__ __forceinline__ void fql_sac_act_body(const SacActArgs& P) {
     const int r = blockIdx.x * FQL_THREADS + threadIdx.x;
     if (r >= P.n) return;
     const float* h = P.head + (size_t)r * 2 * P.ap;
@@ -117,6 +125,9 @@ __global__ __launch_bounds__(FQL_THREADS) void fql_sac_act_kernel(SacActArgs P) 
     }
     if (P.lp) P.lp[r] = lp;
 }
+__global__ __launch_bounds__(FQL_THREADS) void fql_sac_act_kernel(SacActArgs P) { fql_sac_act_body(P); }
+// (a SAC group's sampler binds this one too: grid x covers the chunk's padded rows, rows past the member's n return at once)
+__global__ __launch_bounds__(FQL_THREADS) void fql_sac_act_multi_kernel(const SacActArgs* __restrict__ args) { const SacActArgs P = ((const FQL_CONST_AS SacActArgs*)args)[blockIdx.y]; fql_sac_act_body(P); }
 
 struct SacCriticArgs {
     const float *qa, *qb;      // [B, 16] column 0: critic members at (obs, act)
@@ -131,8 +142,7 @@ struct SacCriticArgs {
 };
 // sac.py:23-56: next_q = min (or mean) of the target pair; y = r + discount mask next_q (- discount mask lp' alpha with backup_entropy);
 // loss = mean over (2, B) of (q - y)^2; q_mean / q_max / q_min over all 2B values of q
-__global__ __launch_bounds__(FQL_THREADS) void fql_sac_loss_critic_kernel(SacCriticArgs P) {
-    __shared__ float sh[4];
+__device__ __forceinline__ void fql_sac_loss_critic_body(const SacCriticArgs& P, float* sh) {
     const float gs = 1.0f / (float)P.B;   // d/dq of mean over 2B of (q - y)^2
     const float alpha = expf(P.log_alpha[0]);
     float sl = 0.f, sq = 0.f, mx = -INFINITY, mn = INFINITY;
@@ -163,6 +173,8 @@ __global__ __launch_bounds__(FQL_THREADS) void fql_sac_loss_critic_kernel(SacCri
         in[3] = tmn;
     }
 }
+__global__ __launch_bounds__(FQL_THREADS) void fql_sac_loss_critic_kernel(SacCriticArgs P) { __shared__ float sh[4]; fql_sac_loss_critic_body(P, sh); }
+__global__ __launch_bounds__(FQL_THREADS) void fql_sac_loss_critic_multi_kernel(const SacCriticArgs* __restrict__ args) { __shared__ float sh[4]; const SacCriticArgs P = ((const FQL_CONST_AS SacCriticArgs*)args)[blockIdx.y]; fql_sac_loss_critic_body(P, sh); }
 
 struct SacActorArgs {
     const float *qa, *qb;      // [B, 16] column 0: critic members (stored parameters) at (obs, a)
@@ -177,8 +189,7 @@ struct SacActorArgs {
 };
 // sac.py:58-92: qbar = mean of the pair, actor_loss = mean(alpha lp - qbar) (alpha held constant), entropy = -mean(lp),
 // alpha_loss = alpha (entropy - target_entropy) with d/dlog_value = alpha (entropy - target_entropy), std = mean of exp(ls) over [B, act]
-__global__ __launch_bounds__(FQL_THREADS) void fql_sac_loss_actor_kernel(SacActorArgs P) {
-    __shared__ float sh[4];
+__device__ __forceinline__ void fql_sac_loss_actor_body(const SacActorArgs& P, float* sh) {
     float slp = 0.f, sq = 0.f, ss = 0.f;
     for (int b = threadIdx.x; b < P.B; b += FQL_THREADS) {
         slp += P.lp[b];
@@ -209,6 +220,8 @@ __global__ __launch_bounds__(FQL_THREADS) void fql_sac_loss_actor_kernel(SacActo
         in[SAC_I_Q] = q;
     }
 }
+__global__ __launch_bounds__(FQL_THREADS) void fql_sac_loss_actor_kernel(SacActorArgs P) { __shared__ float sh[4]; fql_sac_loss_actor_body(P, sh); }
+__global__ __launch_bounds__(FQL_THREADS) void fql_sac_loss_actor_multi_kernel(const SacActorArgs* __restrict__ args) { __shared__ float sh[4]; const SacActorArgs P = ((const FQL_CONST_AS SacActorArgs*)args)[blockIdx.y]; fql_sac_loss_actor_body(P, sh); }
 
 struct SacActorGradArgs {
     const float *dxa, *dxb;    // [B, inp_c]: the critic members' input gradients (columns od .. od + ad: dL/da through the Q term)
@@ -223,7 +236,9 @@ struct SacActorGradArgs {
 // Through sample_and_log_prob (x = mean + s eps, the Gaussian term of lp depends on mean only through x and cancels):
 //   g_x = alpha 2 a / B + (1 - a^2) dL_Q/da with tanh, dL_Q/da without; dL/dmean = g_x;
 //   dL/dls_raw = clipmask (g_x s eps - alpha / B), clipmask 1 inside (-5, 2), 0 outside, 1/2 at a bound (jnp.clip's max / min).
-__global__ __launch_bounds__(FQL_THREADS) void fql_sac_actor_grad_kernel(SacActorGradArgs P) {
+// (the body takes the struct by value: through a reference the by-value entry compiles to 17 VGPRs and 1028 bytes, this way to the 16
+// and 956 it had as one function)
+__device__ __forceinline__ void fql_sac_actor_grad_body(const SacActorGradArgs P) {
     const int e = blockIdx.x * FQL_THREADS + threadIdx.x;
     if (e >= P.B * P.ad) return;
     const int b = e / P.ad, a = e - b * P.ad;
@@ -241,14 +256,14 @@ __global__ __launch_bounds__(FQL_THREADS) void fql_sac_actor_grad_kernel(SacActo
     d[a] = gx;
     d[P.ap + a] = cm * (gx * s * P.eps[(size_t)b * P.ap + a] - alpha * invB);
 }
+__global__ __launch_bounds__(FQL_THREADS) void fql_sac_actor_grad_kernel(SacActorGradArgs P) { fql_sac_actor_grad_body(P); }
+__global__ __launch_bounds__(FQL_THREADS) void fql_sac_actor_grad_multi_kernel(const SacActorGradArgs* __restrict__ args) { const SacActorGradArgs P = ((const FQL_CONST_AS SacActorGradArgs*)args)[blockIdx.y]; fql_sac_actor_grad_body(P); }
 
 // FQL's finalize (grad statistics, then the step counters) with one change: a leaf's chunk partials are folded by a whole wave (lane-strided
 // sums, then a fixed xor tree), not by 4 threads.  SAC's head leaves have one Adam chunk per padded row (build_leaves: 2 x H chunks), which
 // FQL's 4-threads-per-leaf loop walks sequentially on the update's serial tail (14.5 us per update at H = 512, against 5.7 us for FQL's
 // finalize).  Fixed order throughout: bitwise reproducible.  Then the reference's SAC order (14 infos).
-__global__ __launch_bounds__(FQL_THREADS) void fql_sac_finalize_kernel(FinalizeArgs A) {
-    __shared__ float sh[4];
-    __shared__ float leafn[256];
+__device__ __forceinline__ void fql_sac_finalize_body(const FinalizeArgs& A, float* sh, float* leafn) {
     DevState* st = A.st;
     tl_enter(A.tl);
     if (!A.do_grad_stats) return;
@@ -282,3 +297,5 @@ __global__ __launch_bounds__(FQL_THREADS) void fql_sac_finalize_kernel(FinalizeA
         st->b2pow *= 0.999;
     }
 }
+__global__ __launch_bounds__(FQL_THREADS) void fql_sac_finalize_kernel(FinalizeArgs A) { __shared__ float sh[4]; __shared__ float leafn[256]; fql_sac_finalize_body(A, sh, leafn); }
+__global__ __launch_bounds__(FQL_THREADS) void fql_sac_finalize_multi_kernel(const FinalizeArgs* __restrict__ args) { __shared__ float sh[4]; __shared__ float leafn[256]; const FinalizeArgs A = ((const FQL_CONST_AS FinalizeArgs*)args)[blockIdx.y]; fql_sac_finalize_body(A, sh, leafn); }

@@ -294,8 +294,10 @@ int fql_info_wait(fql_handle h, uint64_t ticket, float* info13_host);
  * fql_group_create: `members` [k], k >= 1, distinct, in no other group.  Members are state agents (encoder 0) with precision 0, the same
  * config except alpha (and the create seed), the same batch size, and structurally identical update programs (launch count, kernels,
  * grids, lanes, waits).  Anything else: FQL_E_INVALID.
- * Out of scope and refused: visual or bf16x3 members, members that differ in anything but seed and alpha.  Data-parallel halves,
- * balanced sampling, replay rings and the engine's own queues (stream = NULL updates of a single agent) are not group paths.
+ * Out of scope and refused: visual or bf16x3 members, members that differ in anything but seed and alpha.  Data-parallel halves and
+ * the engine's own queues (stream = NULL updates of a single agent) are not group paths.  Balanced sampling is a group path for SAC
+ * groups alone (fql_sac_group_update_balanced, below): a member's replay ring stays the member's own, filled through the member's
+ * fql_replay_add; no group call inserts into a ring.
  * While a handle belongs to a group, fql_set_batch_size and fql_destroy on it return FQL_E_STATE. */
 int fql_group_create(const fql_handle* members, int k, fql_group* out);
 /* Waits for the group's last update and releases the members (they are plain handles again; nothing is freed of them). */
@@ -492,8 +494,8 @@ int fql_rebrac_group_stats(fql_group g, int64_t* launches_full, int64_t* launche
  * reserve / size, replay create / add / size, fql_sample_actions (temperature 1), info enqueue / fql_info_wait_n / fql_read_info_n,
  * fql_synchronize, fql_stats and fql_stream.  Refused: encoder != 0, precision != 0 or state_dependent_std == 0 at create
  * (FQL_E_INVALID); on a SAC handle fql_update*, fql_update_begin* / _end*, fql_total_loss, fql_grad_buckets, frame uploads / updates,
- * fql_noise_from_jax_keys and fql_flow_actions return FQL_E_STATE, and fql_group_create with a SAC member returns FQL_E_STATE.  The
- * fql_sac_* calls on another handle return FQL_E_STATE. */
+ * fql_noise_from_jax_keys and fql_flow_actions return FQL_E_STATE, and fql_group_create with a SAC member still returns FQL_E_STATE:
+ * SAC handles are grouped by fql_sac_group_create (below the CFGRL groups).  The fql_sac_* calls on another handle return FQL_E_STATE. */
 #define FQL_SAC_NUM_INFO 14
 typedef struct fql_sac_config {
     float target_entropy;             /* NaN = automatic: -target_entropy_multiplier * act_dim (NaN)  */
@@ -892,6 +894,47 @@ int fql_cfgrl_group_sample_actions(fql_group g, const float* observations, const
 /* Launches of the group's fused update program and of one fused sampling call on a single chunk, counted from the built programs.
  * Either pointer may be NULL. */
 int fql_cfgrl_group_stats(fql_group g, int64_t* launches_update, int64_t* launches_sample);
+
+/* ---- SAC agent groups: the seeds of one RLPD run, or a target-entropy x seed sweep, advanced by one fused program (agent groups, above) ----
+ * fql_sac_group_create: `members` [k], k >= 1, SAC handles (another kind: FQL_E_STATE naming it), distinct, in no group, the same batch
+ * size and the same fql_config / fql_sac_config except target_entropy and target_entropy_multiplier (and the create seed); anything
+ * else - tanh_squash, backup_entropy, q_agg, discount, a hidden size, a LayerNorm flag, lr - is FQL_E_INVALID naming the member and
+ * target_entropy, *out NULL.  The group holds ONE fused program, one graph with a member's three lanes: the zip of every member's update
+ * (blockIdx.y = member in SAC's own six kernels, concatenated task tables in the layers), a member's launch count whatever k is.  Each
+ * member's target_entropy and modules_alpha/log_value stay in its own argument structs.  A member's numbers are bitwise those it has
+ * alone, and after a group update it behaves as after its own: fql_read_info_n (its own 14 infos), its own updates and sampling calls,
+ * fql_sac_total_loss, parameter access and checkpoints.
+ * Online use: a member's replay ring is its own.  While grouped, fql_replay_create, fql_replay_add, fql_replay_size, fql_dataset_add,
+ * fql_sac_sample_actions and fql_sac_total_loss on a member keep working and wait for the group's last call, as every member entry
+ * point does; no group call inserts into a ring.  fql_group_destroy and fql_group_synchronize serve these groups too;
+ * fql_set_batch_size and fql_destroy on a member return FQL_E_STATE while it is grouped.  fql_group_create and the other kinds' group
+ * creates keep refusing SAC handles (FQL_E_STATE).  Errors: fql_last_error(NULL).
+ * Across kinds: every other kind's call that takes a group returns FQL_E_STATE on a SAC group, and the four calls below that take a
+ * group return it on a group of another kind, each naming the call that serves the group; a NULL group is FQL_E_INVALID. */
+int fql_sac_group_create(const fql_handle* members, int k, fql_group* out);
+/* fql_sac_update_from_dataset of every member in one fused update.  idx: [k][B] int64, host or device, or NULL = each member's device
+ * RNG; eps_n and eps_c are each member's Philox.  info14xk: [k][14] in fql_sac_update's order (device or host; host = synchronous) or
+ * NULL.  Stream and ordering as fql_group_update_from_dataset. */
+int fql_sac_group_update_from_dataset(fql_group g, const int64_t* idx, int batch_size, float* info14xk, void* stream);
+/* fql_sac_update_balanced of every member in one fused update (RLPD's step for k seeds): member i draws B / 2 rows of ITS OWN dataset
+ * and B / 2 of ITS OWN replay ring.  idx_dataset, idx_replay: [k][B / 2] int64 each, both or neither (NULL = each member's device RNG
+ * over its dataset's and its ring's current sizes), host or device; they are staged into each member's index buffer as
+ * fql_sac_update_balanced stages them.  Every member is checked before any member's source is written or the graph is launched: B even,
+ * a dataset uploaded, a ring created, the ring not empty - else FQL_E_INVALID naming the member, and no member's parameters, Adam
+ * counts or RNG step have moved.  info14xk, stream and ordering as above. */
+int fql_sac_group_update_balanced(fql_group g, const int64_t* idx_dataset, const int64_t* idx_replay, int batch_size,
+                                  float* info14xk, void* stream);
+/* fql_sac_sample_actions of every member in one fused call.  observations [k][n][od], noises [k][n][act] raw N(0, 1) or NULL (then seeds
+ * [k], each member's Philox keyed by its own seed and the row's number in the call), one temperature for the call, out [k][n][act]; host
+ * or device each.  Per chunk of <= 4096 rows per member: one assemble launch, the members' actor over concatenated task tables (its last
+ * layer the [H, 2 act] head layer), one launch of SAC's action kernel, which writes the actions - 2 launches more than the actor has
+ * layers, whatever k is.  out[i] is bitwise fql_sac_sample_actions(member i, ..., seeds[i], temperature, ...).  Pointer kinds and
+ * ordering as fql_group_sample_actions. */
+int fql_sac_group_sample_actions(fql_group g, const float* observations, int n, const float* noises, const uint64_t* seeds,
+                                 float temperature, float* out, void* stream);
+/* Launches of the group's fused update program and of one fused sampling call on a single chunk, counted from the built programs.
+ * Either pointer may be NULL. */
+int fql_sac_group_stats(fql_group g, int64_t* launches_update, int64_t* launches_sample);
 
 #ifdef __cplusplus
 }
