@@ -13,7 +13,14 @@ Jobs: `kinds`: FQL, IFQL, ReBRAC, SAC, IQL ddpgbc and awr, BC, IQL-diffusion, CF
 critic-only and full steps, IQL-diffusion runs its four step kinds; one sample_actions of 5 rows each, cfg 3 and one per-row sweep call for
 the two CFG kinds).  `h512_<precision>`: FQL at hidden 512 x 4, batch 256, then one update_begin_split / update_end_split pair.
 `edges_<precision>`: the FQL shapes of tests/test_gpu_batch_edges.py CASES.  `frames`: a 32 x 32 x 3 frames handle in both precisions (no
-plan: the read-out refuses visual handles).  `group`: the two members of a K = 2 group at hidden 256 x 4, batch 64."""
+plan: the read-out refuses visual handles).  `group`: the two members of a K = 2 FQL group at hidden 256 x 4, batch 64.
+`group_<kind>` (rebrac, iqld, ifql, iql_ddpgbc, iql_awr, cfgrl, sac): a K = 2 group of that kind at hidden 64 x 2, batch 32, its free fields
+differing - launches() and the fused program's task forms; 8 fused updates (ReBRAC alternates its step kinds, IQL-diffusion runs its four,
+SAC runs four from the dataset and four balanced over rings of 64 rows); one fused sample_actions of 5 host rows per member with explicit
+noises and one with a seed (the CFG kinds: cfg 3 and one per-row weight array; IFQL: compute_flow_actions too); every member's state; the
+infos of one more update per update call of the kind, read through the C ABI into a NaN-filled host buffer; and, as uint8, the
+fql_last_error text of every other kind's group entry points called on this group and of the creates it refuses (another kind's member,
+a member of another structure, a member listed twice, a member already grouped)."""
 import ctypes as C
 import os
 import subprocess
@@ -27,7 +34,8 @@ sys.path.insert(0, ROOT)
 OD, AD, UPDATES = 29, 8, 8
 PRECISIONS = ('fp32', 'bf16x3')
 # job -> its time limit in seconds (each takes 1 - 3 s on an MI355X; a cold start of the runtime can add several)
-JOBS = {'kinds': 30, 'h512_fp32': 30, 'h512_bf16x3': 30, 'edges_fp32': 30, 'edges_bf16x3': 30, 'frames': 20, 'group': 20}
+JOBS = {'kinds': 30, 'h512_fp32': 30, 'h512_bf16x3': 30, 'edges_fp32': 30, 'edges_bf16x3': 30, 'frames': 20, 'group': 20,
+        'group_rebrac': 30, 'group_iqld': 30, 'group_ifql': 30, 'group_iql_ddpgbc': 30, 'group_iql_awr': 30, 'group_cfgrl': 30, 'group_sac': 30}
 
 
 # ---- child: one job on one library ---------------------------------------------------------------------------------------------------
@@ -196,10 +204,128 @@ def job_group(out):
     g.close()
 
 
+# every group entry point but the creates, with arguments its kind check never reads: (name, arguments behind the group handle)
+GROUP_CALLS = {
+    'fql': [('fql_group_update_from_dataset', (None, 32, None, None)), ('fql_group_sample_actions', (None, 1, None, None, None, None)),
+            ('fql_group_flow_actions', (None, None, 1, None, None)), ('fql_group_sample_stats', (0, None))],
+    'rebrac': [('fql_rebrac_group_update_from_dataset', (None, 32, 1, None, None)),
+               ('fql_rebrac_group_sample_actions', (None, 1, None, None, 1.0, None, None)), ('fql_rebrac_group_stats', (None, None, None))],
+    'iqld': [('fql_iqld_group_update_from_dataset', (None, 32, 1, 1, None, None)),
+             ('fql_iqld_group_sample_actions', (None, 1, None, None, None, None, None)), ('fql_iqld_group_stats', (None, None))],
+    'ifql': [('fql_ifql_group_update_from_dataset', (None, 32, None, None)), ('fql_ifql_group_sample_actions', (None, 1, None, None, None, None)),
+             ('fql_ifql_group_flow_actions', (None, None, 1, None, None)), ('fql_ifql_group_stats', (None, None, None))],
+    'iql': [('fql_iql_group_update_from_dataset', (None, 32, None, None)), ('fql_iql_group_sample_actions', (None, 1, None, None, 1.0, None, None)),
+            ('fql_iql_group_stats', (None, None))],
+    'cfgrl': [('fql_cfgrl_group_update_from_dataset', (None, 32, None, None, None)),
+              ('fql_cfgrl_group_sample_actions', (None, None, 1, None, None, None, None, None)), ('fql_cfgrl_group_stats', (None, None))],
+    'sac': [('fql_sac_group_update_from_dataset', (None, 32, None, None)), ('fql_sac_group_update_balanced', (None, None, 32, None, None)),
+            ('fql_sac_group_sample_actions', (None, 1, None, None, 1.0, None, None)), ('fql_sac_group_stats', (None, None))],
+}
+
+
+def refusal(out, tag, lib, rc):
+    """The code and the full fql_last_error text of a refused group call, as uint8."""
+    assert rc != 0, tag
+    out[f'{tag}/rc'] = np.array([rc], np.int32)
+    out[f'{tag}/text'] = np.frombuffer(lib.fql_last_error(None), np.uint8)
+
+
+def job_group_kind(out, job):
+    """A K = 2 group of one kind at hidden 64 x 2, batch 32, its free fields differing: launches and task forms, 8 fused updates, fused
+    sampling with explicit noises and with a seed, every member's state, and what the library says to every other kind's group calls on
+    this group and to the creates it refuses."""
+    import fql_amd
+    import fql_amd.cfgrl
+    from fql_amd import _cabi
+    kind = job.split('_')[0]
+    ds = dataset(256, seed=3)
+    ex = (ds['observations'][:1], ds['actions'][:1])
+    gex = ({'observations': ex[0], 'actions': ex[1], 'value_goals': ds['next_observations'][:1]},)
+    hid = dict(actor_hidden_dims=(64, 64), value_hidden_dims=(64, 64), hidden_dims=(64, 64), batch_size=32)
+    mod, cls, member, create_fn, sweep, example = {
+        'rebrac': (fql_amd.rebrac, fql_amd.ReBRACAgentGroup, fql_amd.ReBRACAgent, 'fql_rebrac_group_create', dict(alpha_actors=[0.01, 0.1], alpha_critics=[0.0, 0.01]), ex),
+        'iqld': (fql_amd.iql_diffusion, fql_amd.IQLDiffusionAgentGroup, fql_amd.IQLDiffusionAgent, 'fql_iqld_group_create',
+                 dict(awr_temperatures=[1.0, 3.0], softmax_betas=[1.0, 10.0]), ex),
+        'ifql': (fql_amd.ifql, fql_amd.IFQLAgentGroup, fql_amd.IFQLAgent, 'fql_ifql_group_create', dict(expectiles=[0.7, 0.9]), ex),
+        'iql': (fql_amd.iql, fql_amd.IQLAgentGroup, fql_amd.IQLAgent, 'fql_iql_group_create', dict(expectiles=[0.7, 0.9], alphas=[1.0, 10.0]), ex),
+        'cfgrl': (fql_amd.cfgrl, fql_amd.CFGRLAgentGroup, fql_amd.CFGRLAgent, 'fql_cfgrl_group_create',
+                  dict(cfgs=[1.5, 3.0], goal_mixes=[(0.0, 1.0, 0.0), (0.2, 0.5, 0.3)]), gex),
+        'sac': (fql_amd.sac, fql_amd.SACAgentGroup, fql_amd.SACAgent, 'fql_sac_group_create', dict(target_entropies=[-4.0, None]), ex),
+    }[kind]
+    cfg = dict(mod.get_config(), **hid)
+    if kind == 'iql':
+        cfg['actor_loss'] = job.split('_')[1]
+    g = cls.create([0, 1], *example, cfg, **sweep)
+    out['launches'] = np.array(g.launches(), np.int64)
+    plan_and_forms(out, 'group', group=g)
+    g.upload_dataset(ds)
+    if kind == 'sac':
+        g.create_replay_buffers(64)
+        for j in range(64):
+            g.add_transitions([{k: ds[k][(j + 64 * i) % 256] for k in ('observations', 'actions', 'rewards', 'masks', 'next_observations')} for i in range(2)])
+    for i in range(UPDATES):
+        if kind == 'rebrac':
+            g.update_from_dataset(full_update=bool(i % 2))
+        elif kind == 'iqld':
+            g.update_from_dataset(update_critic=i % 4 < 2, update_actor=i % 2 == 0)
+        elif kind == 'sac' and i >= UPDATES // 2:
+            g.update_balanced()
+        else:
+            g.update_from_dataset()
+    g.synchronize()
+    rng = np.random.default_rng(1)
+    obs = np.stack([ds['observations'][:5], ds['observations'][5:10]])
+    z = rng.standard_normal((2, 5, AD)).astype(np.float32)
+    if kind in ('iqld', 'cfgrl'):
+        goals = (np.stack([ds['next_observations'][:5], ds['next_observations'][5:10]]),) if kind == 'cfgrl' else ()
+        w = np.array([[1.0, 1.5, 3.0, 5.0, 3.0], [0.0, 3.0, 1.0, 2.5, 7.0]], np.float32)
+        out['sample'] = g.sample_actions(obs, *goals, noises=z, cfg=3.0)
+        out['sample_rows'] = g.sample_actions(obs, *goals, noises=z, cfg=w)
+        out['sample_seed'] = g.sample_actions(obs, *goals, seed=7, cfg=3.0)
+    elif kind == 'ifql':
+        N = int(cfg['num_samples'])
+        out['sample'] = g.sample_actions(obs, noises=rng.standard_normal((2, 5, N, AD)).astype(np.float32))
+        out['sample_seed'] = g.sample_actions(obs, seed=7)
+        out['flow'] = g.compute_flow_actions(obs, z)
+    else:
+        out['sample'] = g.sample_actions(obs, noises=z)
+        out['sample_seed'] = g.sample_actions(obs, seed=7)
+    for i, m in enumerate(g.members):
+        state(out, f'member{i}', m)
+    # one more fused update per update call of the kind, through the C ABI into a NaN-filled host buffer: the infos' stride and extent
+    lib = _cabi.load()
+    for fn, args in [c for c in GROUP_CALLS[kind] if 'update' in c[0]]:
+        infos = np.full(64, np.nan, np.float32)
+        assert getattr(lib, fn)(g._g, *args[:-2], infos.ctypes.data, None) == 0, lib.fql_last_error(None)
+        out[f'infos/{fn}'] = infos
+    # every other kind's group calls on this group
+    for other, calls in GROUP_CALLS.items():
+        for fn, args in calls if other != kind else ():
+            refusal(out, f'on_this_group/{fn}', lib, getattr(lib, fn)(g._g, *args))
+    # the creates this kind refuses: another kind's member (an FQL agent; a CFGRL agent), a member of another structure, a member twice, a
+    # member already grouped
+    create = getattr(lib, create_fn)
+    fresh = [member.create(2 + i, *example, c) for i, c in enumerate((cfg, dict(cfg, discount=0.9)))]
+    strangers = [fql_amd.FQLAgent.create(4, *ex, dict(fql_amd.get_config(), **hid))]
+    if kind != 'cfgrl':
+        strangers.append(fql_amd.CFGRLAgent.create(5, *gex, dict(fql_amd.cfgrl.get_config(), **hid)))
+    refused = [(f'stranger{i}', [fresh[0], s]) for i, s in enumerate(strangers)]
+    refused += [('structure', fresh), ('twice', [fresh[0], fresh[0]]), ('grouped', [fresh[0], g.members[0]])]
+    for tag, members in refused:
+        h = C.c_void_p()
+        refusal(out, f'create/{tag}', lib, create((C.c_void_p * len(members))(*[m._h for m in members]), len(members), C.byref(h)))
+        assert not h.value, tag
+    g.close()
+    for a in fresh + strangers:
+        a.close()
+
+
 def child(job, where):
     out = {}
     name, _, precision = job.partition('_')
-    if precision:
+    if name == 'group' and precision:
+        job_group_kind(out, precision)
+    elif precision:
         {'h512': job_h512, 'edges': job_edges}[name](out, precision)
     else:
         {'kinds': job_kinds, 'frames': job_frames, 'group': job_group}[name](out)

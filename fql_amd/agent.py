@@ -889,15 +889,16 @@ def _group_sample_args(members, observations, noises, seed, flow, per=()):
     return o, z, seeds, n, out, optr, FQLAgent._stream([o, z])
 
 
-def _group_idx_arg(members, idxs, B):
+def _group_idx_arg(members, idxs, B, what='idxs', rows=lambda m: m.dataset_size()[0]):
     """`idxs` [K, B] of a group update (host array or tensor, CUDA tensors on torch's current stream): (keep-alive, pointer, stream).
-    Host rows are range-checked against each member's dataset."""
+    Host rows are range-checked against `rows(member)`, each member's dataset (or, `what` = 'replay idxs', its replay ring): an
+    out-of-range row never reaches the device."""
     K = len(members)
     stream = None
     if hasattr(idxs, 'data_ptr'):
         keep = idxs.long().contiguous()
         if tuple(keep.shape) != (K, B):
-            raise ValueError(f'idxs must be [{K}, {B}], got {tuple(keep.shape)}')
+            raise ValueError(f'{what} must be [{K}, {B}], got {tuple(keep.shape)}')
         if keep.is_cuda:
             h = _torch().cuda.current_stream().cuda_stream
             stream = h if h else _cabi.FQL_STREAM_LEGACY
@@ -905,18 +906,162 @@ def _group_idx_arg(members, idxs, B):
     else:
         keep = np.ascontiguousarray(idxs, dtype=np.int64)
         if keep.shape != (K, B):
-            raise ValueError(f'idxs must be [{K}, {B}], got {keep.shape}')
+            raise ValueError(f'{what} must be [{K}, {B}], got {keep.shape}')
         ip = keep.ctypes.data
     if not (hasattr(keep, 'is_cuda') and keep.is_cuda):
         a = keep.numpy() if hasattr(keep, 'numpy') else keep
         for i, m in enumerate(members):
-            n = m.dataset_size()[0]
+            n = rows(m)
             if B and (a[i].min() < 0 or a[i].max() >= n):
-                raise ValueError(f'idxs[{i}] out of range: [{int(a[i].min())}, {int(a[i].max())}] for {n} rows')
+                raise ValueError(f'{what}[{i}] out of range: [{int(a[i].min())}, {int(a[i].max())}] for {n} rows')
     return keep, ip, stream
 
 
-class FQLAgentGroup:
+class AgentGroup:
+    """What the agent groups share: K members of one structure behind one group handle of the library.  A subclass names its members'
+    class (`_member`), its module's get_config (`_get_config`) and its library calls (`_create_fn`, `_update_fn`, `_sample_fn`,
+    `_stats_fn` with `_stats_outs` out-values), and keeps the methods whose signature or result is its kind's own."""
+
+    _member = _get_config = None
+    _create_fn = _update_fn = _balanced_fn = _sample_fn = _flow_fn = _stats_fn = None
+    _stats_outs = 2
+    _sample_temperature = True   # the kind's sampling call takes a temperature
+
+    def __init__(self, handle, members):
+        self._lib = _cabi.load()
+        self._g = handle
+        self.members = members
+        self.batch_size = int(members[0].config['batch_size'])
+        self._keep = None
+
+    @classmethod
+    def _refuse(cls, cfg, *example):
+        """A member config's refusals before any library call (encoder, precision, rng and the member class's own)."""
+        cls._member._refuse_config(cfg)
+
+    @classmethod
+    def _create(cls, seeds, config, sweeps, *example, more=None):
+        """The group of one member per seed.  `sweeps`: {config key: (K values or None = the config's for every member, plural name,
+        conversion = float)}, what differs between members beside the seed; `more(cfg, K, lists)` checks and adds a kind's further
+        per-member keys.  Every check runs before the library is loaded."""
+        seeds = [int(s) for s in seeds]
+        if not seeds:
+            raise ValueError('an agent group needs at least one seed')
+        cfg = cls._get_config()
+        cfg.update(dict(config))
+        lists = {}
+        for key, (vals, name, *conv) in sweeps.items():
+            conv = conv[0] if conv else float
+            lists[key] = [conv(v) for v in ([cfg[key]] * len(seeds) if vals is None else vals)]
+            if len(lists[key]) != len(seeds):
+                raise ValueError(f'{len(seeds)} seeds but {len(lists[key])} {name}')
+        if more is not None:
+            more(cfg, len(seeds), lists)
+        cfgs = [dict(cfg, **{key: vals[i] for key, vals in lists.items()}) for i in range(len(seeds))]
+        for c in cfgs:
+            cls._refuse(c, *example)
+        lib = _cabi.load()
+        members = [cls._member.create(s, *example, c) for s, c in zip(seeds, cfgs)]
+        arr = (C.c_void_p * len(members))(*[m._h for m in members])
+        g = C.c_void_p()
+        _cabi.check(lib, None, getattr(lib, cls._create_fn)(arr, len(members), C.byref(g)))
+        return cls(g, members)
+
+    def _check(self, rc):
+        _cabi.check(self._lib, None, rc)
+
+    def _batch(self, batch_size):
+        B = int(batch_size or self.batch_size)
+        if B != self.batch_size:
+            raise ValueError(f'batch_size {B}: the members of a group keep the batch size they were grouped with ({self.batch_size})')
+        return B
+
+    def upload_dataset(self, dataset, capacity: Optional[int] = None):
+        """Every member gets its own device copy of `dataset` (the member class's upload_dataset)."""
+        for m in self.members:
+            m.upload_dataset(dataset, capacity=capacity)
+
+    def _update(self, B, idxs, want_info, extra=(), hold=None, after=None, info=None, balanced=False):
+        """One fused update.  `extra`: what the kind's call takes between the batch size and the info pointer; `hold`: an _Arg behind
+        one of them, kept alive (and, without device rows, the stream the call runs on); `after(member)`: what the step leaves in a
+        member; `info(member)`: its infos, where they are not the member's _lazy_info."""
+        ptrs = (None, None) if balanced else (None,)
+        keep = stream = None
+        if idxs is not None and balanced:
+            if len(idxs) != 2:
+                raise ValueError('idxs must be (dataset_idxs, replay_idxs)')
+            ka, ia, sa = _group_idx_arg(self.members, idxs[0], B // 2, 'dataset idxs')
+            kb, ib, sb = _group_idx_arg(self.members, idxs[1], B // 2, 'replay idxs', lambda m: m.replay_size()[0])
+            ptrs, keep, stream = (ia, ib), (ka, kb), (sb if sb is not None else sa)
+        elif idxs is not None:
+            keep, ip, stream = _group_idx_arg(self.members, idxs, B)
+            ptrs = (ip,)
+        if stream is None and hold is not None:
+            stream = FQLAgent._stream([hold])
+        fn = getattr(self._lib, self._balanced_fn if balanced else self._update_fn)
+        self._check(fn(self._g, *ptrs, B, *extra, None, stream))
+        self._keep = keep if hold is None else (keep, hold)
+        if after is not None:
+            for m in self.members:
+                after(m)
+        if not want_info:
+            return None
+        return [info(m) if info is not None else m._lazy_info(None) for m in self.members]
+
+    def update_from_dataset(self, batch_size=None, idxs=None, want_info=False):
+        """One fused update of every member: rows from each member's dataset (`idxs` [K, B] int, host or device, or None = each member's
+        device RNG), noise from each member's device RNG.  Returns a list of K LazyInfo with the members' info keys (want_info) or None."""
+        return self._update(self._batch(batch_size), idxs, want_info)
+
+    def _noise_per(self):
+        """The dims of a row's sampling noise in front of the action dim."""
+        return ()
+
+    def sample_actions(self, observations, seed=None, temperature=1.0, noises=None):
+        """The member class's sample_actions of every member in ONE fused call: result[i] is bitwise what
+        members[i].sample_actions(observations[i], seed=..., temperature=..., noises=noises[i]) returns.  Shapes and seeds as in
+        FQLAgentGroup.sample_actions: observations [K, ..., od] or one shared block, noises [K, ..., ad] or None, seed None (each
+        member's own counter advances), one seed or K seeds.  Returns [K, ..., ad]."""
+        o, z, seeds, n, out, optr, stream = _group_sample_args(self.members, observations, noises, seed, False, per=self._noise_per())
+        t = (float(temperature),) if self._sample_temperature else ()
+        self._check(getattr(self._lib, self._sample_fn)(self._g, o.ptr, n, z.ptr, seeds, *t, optr, stream))
+        return out
+
+    def _flow_actions(self, observations, noises):
+        """compute_flow_actions of every member in one fused call (`_flow_fn`): noises [K, ..., ad]."""
+        if noises is None:
+            raise ValueError('compute_flow_actions needs noises [K, ..., action_dim]')
+        o, z, _, n, out, optr, stream = _group_sample_args(self.members, observations, noises, None, True)
+        self._check(getattr(self._lib, self._flow_fn)(self._g, o.ptr, z.ptr, n, optr, stream))
+        return out
+
+    def launches(self):
+        """Kernel launches of the group's fused update program(s), then of its fused sampling call(s) on a single chunk, as the
+        kind's stats call counts them from the built programs."""
+        if self._stats_fn is None:
+            raise NotImplementedError(f'{type(self).__name__} counts its sampling launches with sample_launches()')
+        outs = [C.c_int64(0) for _ in range(self._stats_outs)]
+        self._check(getattr(self._lib, self._stats_fn)(self._g, *[C.byref(v) for v in outs]))
+        return tuple(int(v.value) for v in outs)
+
+    def synchronize(self):
+        """Host wait for the group's last update or sampling call."""
+        self._check(self._lib.fql_group_synchronize(self._g))
+
+    def close(self):
+        """Destroy the fused program(s); the members stay usable as standalone agents.  A second close is a no-op."""
+        if getattr(self, '_g', None):
+            self._lib.fql_group_destroy(self._g)
+            self._g = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class FQLAgentGroup(AgentGroup):
     """K agents of one structure - the same config except `seed` and `alpha` - trained side by side by ONE fused update program
     (include/fql_amd.h, fql_group_*): every launch of the update carries all K members' tasks.  The seed / alpha sweeps the reference
     recommends (README "Tips for hyperparameter tuning") on one device:
@@ -930,66 +1075,26 @@ class FQLAgentGroup:
     bitwise the one it has when trained alone with the same seed, alpha, rows and noise.  Members are state agents with precision 'fp32'
     and the engine's device RNG; while grouped their batch size is fixed."""
 
-    def __init__(self, handle, members):
-        self._lib = _cabi.load()
-        self._g = handle
-        self.members = members
-        self.batch_size = int(members[0].config['batch_size'])
-        self._keep = None
+    _member, _get_config = FQLAgent, staticmethod(get_config)
+    _create_fn, _update_fn, _sample_fn, _flow_fn = 'fql_group_create', 'fql_group_update_from_dataset', 'fql_group_sample_actions', 'fql_group_flow_actions'
+    _sample_temperature = False
+    _other_groups = {'sac': 'SAC', 'iql': 'IQL', 'cfgrl': 'CFGRL'}   # agent_name -> the kind whose own group class takes such a config
 
     @classmethod
     def create(cls, seeds, ex_observations, ex_actions, config, alphas=None):
-        seeds = [int(s) for s in seeds]
-        if not seeds:
-            raise ValueError('an agent group needs at least one seed')
-        cfg = get_config()
-        cfg.update(dict(config))
-        alphas = [float(cfg['alpha'])] * len(seeds) if alphas is None else [float(a) for a in alphas]
-        if len(alphas) != len(seeds):
-            raise ValueError(f'{len(seeds)} seeds but {len(alphas)} alphas')
-        if cfg.get('agent_name') == 'sac':
-            raise NotImplementedError('agent groups take FQL agents only (SAC agents are grouped by SACAgentGroup)')
-        if cfg.get('agent_name') == 'iql':
-            raise NotImplementedError('agent groups take FQL agents only (IQL agents are grouped by IQLAgentGroup)')
-        if cfg.get('agent_name') == 'cfgrl':
-            raise NotImplementedError('agent groups take FQL agents only (CFGRL agents are grouped by CFGRLAgentGroup)')
+        return cls._create(seeds, config, {'alpha': (alphas, 'alphas')}, ex_observations, ex_actions)
+
+    @classmethod
+    def _refuse(cls, cfg, *example):
+        kind = cls._other_groups.get(cfg.get('agent_name'))
+        if kind:
+            raise NotImplementedError(f'agent groups take FQL agents only ({kind} agents are grouped by {kind}AgentGroup)')
         if cfg.get('encoder') is not None:
             raise NotImplementedError('agent groups take state agents only (encoder=None)')
         if cfg.get('precision', 'fp32') not in ('fp32', 0):
             raise NotImplementedError("agent groups take precision='fp32' members only")
         if cfg.get('rng') is not None and cfg.get('rng') != 'engine':
             raise NotImplementedError(f"agent groups draw rows and noise from the engine's device RNG; rng={cfg.get('rng')!r} is not supported")
-        lib = _cabi.load()
-        members = []
-        for s, a in zip(seeds, alphas):
-            c = dict(cfg)
-            c['alpha'] = a
-            members.append(FQLAgent.create(s, ex_observations, ex_actions, c))
-        arr = (C.c_void_p * len(members))(*[m._h for m in members])
-        g = C.c_void_p()
-        _cabi.check(lib, None, lib.fql_group_create(arr, len(members), C.byref(g)))
-        return cls(g, members)
-
-    def _check(self, rc):
-        _cabi.check(self._lib, None, rc)
-
-    def upload_dataset(self, dataset, capacity: Optional[int] = None):
-        """Every member gets its own device copy of `dataset` (FQLAgent.upload_dataset)."""
-        for m in self.members:
-            m.upload_dataset(dataset, capacity=capacity)
-
-    def update_from_dataset(self, batch_size=None, idxs=None, want_info=False):
-        """One fused update of every member: rows from each member's dataset (`idxs` [K, B] int, host or device, or None = each member's
-        device RNG), noise from each member's device RNG.  Returns a list of K LazyInfo (want_info) or None."""
-        B = int(batch_size or self.batch_size)
-        if B != self.batch_size:
-            raise ValueError(f'batch_size {B}: the members of a group keep the batch size they were grouped with ({self.batch_size})')
-        ip, keep, stream = None, None, None
-        if idxs is not None:
-            keep, ip, stream = _group_idx_arg(self.members, idxs, B)
-        self._check(self._lib.fql_group_update_from_dataset(self._g, ip, B, None, stream))
-        self._keep = keep
-        return [m._lazy_info(None) for m in self.members] if want_info else None
 
     def sample_actions(self, observations, seed=None, temperature=1.0, noises=None):
         """FQLAgent.sample_actions of every member in ONE fused call (fql_group_sample_actions): result[i] is bitwise what
@@ -1001,40 +1106,14 @@ class FQLAgentGroup:
         call would be) or a sequence of K; with neither seed nor noises each member's own sample counter advances as its own call would
         advance it.  numpy in, numpy out; CUDA tensors in, a CUDA tensor out on torch's current stream.  `temperature` is accepted and
         ignored, as in FQLAgent.  Returns [K, ..., ad]."""
-        return self._eval(observations, noises, seed, flow=False)
+        return super().sample_actions(observations, seed, temperature, noises)
 
     def compute_flow_actions(self, observations, noises):
         """FQLAgent.compute_flow_actions of every member in one fused call (fql_group_flow_actions); shapes as in sample_actions."""
-        if noises is None:
-            raise ValueError('compute_flow_actions needs noises [K, ..., action_dim]')
-        return self._eval(observations, noises, None, flow=True)
-
-    def _eval(self, observations, noises, seed, flow):
-        o, z, seeds, n, out, optr, stream = _group_sample_args(self.members, observations, noises, seed, flow)
-        if flow:
-            self._check(self._lib.fql_group_flow_actions(self._g, o.ptr, z.ptr, n, optr, stream))
-        else:
-            self._check(self._lib.fql_group_sample_actions(self._g, o.ptr, n, z.ptr, seeds, optr, stream))
-        return out
+        return self._flow_actions(observations, noises)
 
     def sample_launches(self, flow=False):
         """Kernel launches of one fused sampling call on a single chunk, counted from the built program (fql_group_sample_stats)."""
         v = C.c_int64(0)
         self._check(self._lib.fql_group_sample_stats(self._g, int(bool(flow)), C.byref(v)))
         return int(v.value)
-
-    def synchronize(self):
-        """Host wait for the group's last update or sampling call."""
-        self._check(self._lib.fql_group_synchronize(self._g))
-
-    def close(self):
-        """Destroy the fused program; the members stay usable as standalone agents."""
-        if getattr(self, '_g', None):
-            self._lib.fql_group_destroy(self._g)
-            self._g = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

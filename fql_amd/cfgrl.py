@@ -27,7 +27,7 @@ import ctypes as C
 import numpy as np
 
 from . import _cabi
-from .agent import FQLAgent, KindAgent, _Arg, _PendingN, _group_idx_arg, _group_sample_args
+from .agent import AgentGroup, FQLAgent, KindAgent, _Arg, _PendingN, _group_sample_args
 from .config import ConfigDict
 from .iql_diffusion import as_array, check_cfgs, group_cfgs, sweep_inputs
 
@@ -293,7 +293,7 @@ class CFGRLAgent(KindAgent):
 MIX_KEYS = ('actor_p_curgoal', 'actor_p_trajgoal', 'actor_p_randomgoal')
 
 
-class CFGRLAgentGroup:
+class CFGRLAgentGroup(AgentGroup):
     """K CFGRL agents of one structure - the same config except `seed`, `cfg` and the actor's goal mixture (actor_p_curgoal /
     actor_p_trajgoal / actor_p_randomgoal) - advanced by ONE fused update program (include/fql_amd.h, fql_cfgrl_group_*): every launch of
     the update's single lane carries all K members' tasks.  The seed x goal-mixture x guidance-weight sweeps of the goal-conditioned
@@ -310,54 +310,29 @@ class CFGRLAgentGroup:
     size is fixed.  The other kinds have groups of their own (FQLAgentGroup, ReBRACAgentGroup, IQLDiffusionAgentGroup, IFQLAgentGroup,
     IQLAgentGroup)."""
 
-    def __init__(self, handle, members):
-        self._lib = _cabi.load()
-        self._g = handle
-        self.members = members
-        self.batch_size = int(members[0].config['batch_size'])
-        self._keep = None
+    _member, _get_config = CFGRLAgent, staticmethod(get_config)
+    _create_fn, _update_fn = 'fql_cfgrl_group_create', 'fql_cfgrl_group_update_from_dataset'
+    _sample_fn, _stats_fn = 'fql_cfgrl_group_sample_actions', 'fql_cfgrl_group_stats'   # launches(): (the update program, one sampling call)
 
     @classmethod
     def create(cls, seeds, example_batch, config, cfgs=None, goal_mixes=None):
         """`cfgs`: K default guidance weights (None: the config's).  `goal_mixes`: K triples (p_cur, p_traj, p_random), each summing to
         1 (None: the config's mixture for every member)."""
-        seeds = [int(s) for s in seeds]
-        if not seeds:
-            raise ValueError('an agent group needs at least one seed')
-        cfg = get_config()
-        cfg.update(dict(config))
-        cfgs = [float(cfg['cfg'])] * len(seeds) if cfgs is None else [float(c) for c in cfgs]
-        if len(cfgs) != len(seeds):
-            raise ValueError(f'{len(seeds)} seeds but {len(cfgs)} cfgs')
-        if not np.isfinite(cfgs).all():
-            raise ValueError('cfgs: every guidance weight must be finite')
-        if goal_mixes is None:
-            goal_mixes = [tuple(float(cfg[k]) for k in MIX_KEYS)] * len(seeds)
-        goal_mixes = [tuple(float(p) for p in mix) for mix in goal_mixes]
-        if len(goal_mixes) != len(seeds):
-            raise ValueError(f'{len(seeds)} seeds but {len(goal_mixes)} goal_mixes')
-        for i, mix in enumerate(goal_mixes):
-            if len(mix) != 3 or min(mix) < 0.0 or not np.isclose(sum(mix), 1.0):
-                raise ValueError(f'goal_mixes[{i}] = {mix}: three probabilities (p_cur, p_traj, p_random) that sum to 1')
-        per_member = []
-        for c, mix in zip(cfgs, goal_mixes):
-            mc = dict(cfg, cfg=c, **dict(zip(MIX_KEYS, mix)))
-            CFGRLAgent._check_create(mc, example_batch)   # encoder, precision, rng, actor_geom_sample, frame_stack, flow_steps, the example's keys
-            per_member.append(mc)
-        lib = _cabi.load()
-        members = [CFGRLAgent.create(s, example_batch, mc) for s, mc in zip(seeds, per_member)]
-        arr = (C.c_void_p * len(members))(*[m._h for m in members])
-        g = C.c_void_p()
-        _cabi.check(lib, None, lib.fql_cfgrl_group_create(arr, len(members), C.byref(g)))
-        return cls(g, members)
+        def mixtures(cfg, K, lists):
+            if not np.isfinite(lists['cfg']).all():
+                raise ValueError('cfgs: every guidance weight must be finite')
+            mixes = [tuple(float(cfg[k]) for k in MIX_KEYS)] * K if goal_mixes is None else [tuple(float(p) for p in mix) for mix in goal_mixes]
+            if len(mixes) != K:
+                raise ValueError(f'{K} seeds but {len(mixes)} goal_mixes')
+            for i, mix in enumerate(mixes):
+                if len(mix) != 3 or min(mix) < 0.0 or not np.isclose(sum(mix), 1.0):
+                    raise ValueError(f'goal_mixes[{i}] = {mix}: three probabilities (p_cur, p_traj, p_random) that sum to 1')
+            lists.update((k, [mix[j] for mix in mixes]) for j, k in enumerate(MIX_KEYS))
+        return cls._create(seeds, config, {'cfg': (cfgs, 'cfgs')}, example_batch, more=mixtures)
 
-    def _check(self, rc):
-        _cabi.check(self._lib, None, rc)
-
-    def upload_dataset(self, dataset, capacity=None):
-        """Every member gets its own device copy of `dataset` and its own goal table (CFGRLAgent.upload_dataset)."""
-        for m in self.members:
-            m.upload_dataset(dataset, capacity=capacity)
+    @classmethod
+    def _refuse(cls, cfg, example_batch):   # encoder, precision, rng, actor_geom_sample, frame_stack, flow_steps, the example's keys
+        CFGRLAgent._check_create(cfg, example_batch)
 
     def update_from_dataset(self, batch_size=None, idxs=None, do_cfg=None, want_info=False):
         """One fused update of every member: rows from each member's dataset (`idxs` [K, B] int, host or device, or None = each member's
@@ -365,23 +340,14 @@ class CFGRLAgentGroup:
         member's own mask draw; x_0 and t from each member's device RNG.  Returns a list of K LazyInfo over CFGRL_INFO_KEYS (want_info)
         or None."""
         K = len(self.members)
-        B = int(batch_size or self.batch_size)
-        if B != self.batch_size:
-            raise ValueError(f'batch_size {B}: the members of a group keep the batch size they were grouped with ({self.batch_size})')
+        B = self._batch(batch_size)
         mask = _Arg(None)
         if do_cfg is not None:
             do_cfg = do_cfg if hasattr(do_cfg, 'data_ptr') else np.asarray(do_cfg)
             if tuple(int(d) for d in do_cfg.shape) != (K, B):
                 raise ValueError(f'do_cfg must be [{K}, {B}], got {tuple(do_cfg.shape)}')
             mask = _Arg(do_cfg != 0, (K, B), u8=True)
-        ip, keep, stream = None, None, None
-        if idxs is not None:
-            keep, ip, stream = _group_idx_arg(self.members, idxs, B)
-        if stream is None:
-            stream = FQLAgent._stream([mask])
-        self._check(self._lib.fql_cfgrl_group_update_from_dataset(self._g, ip, B, mask.ptr, None, stream))
-        self._keep = (keep, mask)
-        return [m._lazy_info(None) for m in self.members] if want_info else None
+        return self._update(B, idxs, want_info, extra=(mask.ptr,), hold=mask)
 
     def sample_actions(self, observations, goals, seed=None, cfg=None, noises=None):
         """CFGRLAgent.sample_actions of every member in ONE fused call (fql_cfgrl_group_sample_actions): result[i] is bitwise what
@@ -406,30 +372,8 @@ class CFGRLAgentGroup:
         w = group_cfgs(c, K, lead)
         o, z, seeds, n, out, optr, _ = _group_sample_args(self.members, observations, noises, seed, False)
         g, w = _Arg(goals, (K, n, G)), _Arg(w, (K, n))
-        self._check(self._lib.fql_cfgrl_group_sample_actions(self._g, o.ptr, g.ptr, n, z.ptr, seeds, w.ptr, optr, FQLAgent._stream([o, g, z, w])))
+        self._check(getattr(self._lib, self._sample_fn)(self._g, o.ptr, g.ptr, n, z.ptr, seeds, w.ptr, optr, FQLAgent._stream([o, g, z, w])))
         return out
-
-    def launches(self):
-        """Kernel launches of (the fused update program, one fused sampling call on a single chunk)."""
-        u, s = C.c_int64(0), C.c_int64(0)
-        self._check(self._lib.fql_cfgrl_group_stats(self._g, C.byref(u), C.byref(s)))
-        return int(u.value), int(s.value)
-
-    def synchronize(self):
-        """Host wait for the group's last update or sampling call."""
-        self._check(self._lib.fql_group_synchronize(self._g))
-
-    def close(self):
-        """Destroy the fused program; the members stay usable as standalone agents.  A second close is a no-op."""
-        if getattr(self, '_g', None):
-            self._lib.fql_group_destroy(self._g)
-            self._g = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 __all__ = ['CFGRLAgent', 'CFGRLAgentGroup', 'CFGRL_INFO_KEYS', 'CFGRL_NOISE_KEYS', 'CFGRL_DRAW_KEYS', 'get_config', 'final_indices']

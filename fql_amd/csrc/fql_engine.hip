@@ -6375,19 +6375,9 @@ int fql_update_from_frames(fql_handle h, const int64_t* idx, const int32_t* crop
 // task tables (tile0 and the side kernel's sub-table offsets rebased, grid = the sum); an argument-struct launch becomes one launch of the
 // kernel's multi-instance entry point with blockIdx.y = member, reading the member's argument struct from a device array.  Every task keeps
 // the tile shape and arguments its member's program gave it, so each member computes exactly what it computes alone.
-// The members' sampling programs are zipped the same way (fql_group_s::Sample): one fused sample_actions / flow_actions call for all K.
-// A group has a kind: FQL members (fql_group_create), or ReBRAC members (fql_rebrac_group_create), whose group
-// holds a second fused program, the zip of the members' critic-only step, and a sampler that ends in ReBRAC's action kernel; or
-// IQL-diffusion members (fql_iqld_group_create), whose group holds one fused program per step kind (full,
-// critic-only, actor-only, neither) and a sampler that zips the members' sweep program: one guidance weight per row; or IFQL members
-// (fql_ifql_group_create), whose group holds the one fused program and a best-of-N sampler that zips the members'
-// Euler flow and critic pair between the multi-instance forms of IFQL's three sampling kernels; or IQL members (fql_iql_group_create;
-// DESIGN.md section 25), whose group holds the one fused program - IFQL's value and critic lanes beside the Gaussian actor's own
-// kernels - and a sampler that ends in the multi-instance form of IQL's sampling head; or CFGRL members (fql_cfgrl_group_create;
-// DESIGN.md section 26), whose group holds the one fused program - BC's single lane, each member's goal source (CfgrlSrc) set per
-// update - and a sampler that zips the members' sweep program behind the multi-instance form of CFGRL's two-half row assembly; or SAC
-// members (fql_sac_group_create), whose group holds the one fused program, entered with each member's dataset
-// source or with its two-source balanced one (the member's own replay ring), and a sampler that ends in SAC's action kernel.
+// The members' sampling programs are zipped the same way (fql_group_s::Sample): one fused sampling call for all K.
+// A group has a kind, its members': what a kind's group fuses, what may differ between its members and how it samples is the kind's row
+// of k_group_kinds, below.  A new group kind adds its row, the multi-instance entries of its kernels and its C entry points.
 // ================================================================================================
 namespace {
 
@@ -6493,15 +6483,189 @@ struct GProgram {
     hipGraphExec_t exec = nullptr;
 };
 
+// ---- one row per group kind ----
+// What may differ between the members of a group beside the create seed are kernel ARGUMENTS; everything else is structure, or a constant
+// every member shares.  same_structure: the members' configs with those free fields (and the batch size, which the members' B answers)
+// zeroed, compared byte by byte.
+template <typename C, typename Zero>
+bool same_but(C a, C b, Zero zero) { zero(a); zero(b); return std::memcmp(&a, &b, sizeof a) == 0; }
+bool same_base(const fql_engine& a, const fql_engine& b) { return same_but(a.cfg, b.cfg, [](fql_config& c) { c.batch_size = 0; }); }
+bool same_fql(const fql_engine& a, const fql_engine& b) { return same_but(a.cfg, b.cfg, [](fql_config& c) { c.alpha = 0.f; c.batch_size = 0; }); }
+bool same_rebrac(const fql_engine& a, const fql_engine& b) {
+    return same_base(a, b) && same_but(a.rcfg, b.rcfg, [](fql_rebrac_config& c) { c.alpha_actor = c.alpha_critic = 0.f; });
+}
+// (both reach the device as IqldWeightArgs::temp alone)
+bool same_iqld(const fql_engine& a, const fql_engine& b) {
+    return same_base(a, b) && same_but(a.dcfg, b.dcfg, [](fql_iqld_config& c) { c.awr_temperature = c.softmax_beta = 0.f; });
+}
+// (IfqlValueArgs::expectile alone; num_samples is structure: it sets the row count of the sampler's workspaces)
+bool same_ifql(const fql_engine& a, const fql_engine& b) { return same_base(a, b) && a.num_samples == b.num_samples; }
+// (IfqlValueArgs::expectile; IqlAwrArgs / IqlDdpgArgs / IqlActorGradArgs::alpha; actor_loss and const_std are structure: they choose the
+// launches and the log_stds leaf)
+bool same_iql(const fql_engine& a, const fql_engine& b) {
+    return same_base(a, b) && same_but(a.qcfg, b.qcfg, [](fql_iql_config& c) { c.expectile = c.alpha = 0.f; });
+}
+// (cfg is the sampler's default guidance weight, an argument of the sampling calls; the three goal-mixture probabilities reach the
+// device only as CfgrlSrc::thr_traj, p_cur and all_cur, which every update writes per member; goal_dim, flow_steps and p_uncond are
+// structure or shared constants)
+bool same_cfgrl(const fql_engine& a, const fql_engine& b) {
+    return same_base(a, b) && same_but(a.gcfg, b.gcfg, [](fql_cfgrl_config& c) {
+               c.cfg = 0.f;
+               c.actor_p_curgoal = c.actor_p_trajgoal = c.actor_p_randomgoal = 0;
+           });
+}
+// (target_entropy - NaN = automatic - and the multiplier it is then derived from reach the device as SacActorArgs::target_entropy alone;
+// tanh_squash, backup_entropy, q_agg and the rest choose kernel arguments every member shares)
+bool same_sac(const fql_engine& a, const fql_engine& b) {
+    return same_base(a, b) && same_but(a.scfg, b.scfg, [](fql_sac_config& c) { c.target_entropy = c.target_entropy_multiplier = 0.f; });
+}
+
+// The launch that ends a chunk of the plain chunk loop (fql_group_s::sample), over the [K] argument structs behind the chunk's [K]
+// AssembleArgs.  bind: the multi-instance kernel over `n_pad` padded rows per member (a chunk's m <= n_pad: what lies past m returns at
+// once); fill: member i's struct of a chunk of `mm` rows from row `start`, every argument as the member's own call fills it
+// (fql_engine::eval_rows, fql_engine::sample_actor): its noise rows z or null, where its actions go, its seed.
+struct ChunkRows { const float* z; float* dst; uint64_t seed; int mm, start; float temperature; };
+struct SampleFinish {
+    Bound (*bind)(int n_pad, int ad, int K, const void* d);
+    void (*fill)(void* a, int i, const fql_engine& e, const fql_engine::Eval& ev, bool flow, const ChunkRows& r);
+    size_t bytes;
+};
+Geo per_element(int n, int threads, int K) { return Geo(dim3((n + threads - 1) / threads, K), dim3(threads), 0); }
+const SampleFinish k_finish_extract = {
+    [](int n_pad, int ad, int K, const void* d) { return bind(fql_extract_multi_kernel, per_element(n_pad * ad, 256, K), (const ExtractArgs*)d); },
+    [](void* a, int i, const fql_engine& e, const fql_engine::Eval& ev, bool flow, const ChunkRows& r) {
+        ((ExtractArgs*)a)[i] = ExtractArgs{flow ? ev.tgt : ev.p_os.out, r.dst, r.mm, e.cfg.act_dim, pad16(e.cfg.act_dim)};
+    },
+    sizeof(ExtractArgs)};
+// ReBRAC: fql_rebrac_act_multi_kernel on the actor's forward writes the actions where extract-multi would
+const SampleFinish k_finish_rebrac = {
+    [](int n_pad, int ad, int K, const void* d) { return bind(fql_rebrac_act_multi_kernel, per_element(n_pad * ad, FQL_THREADS, K), (const RebracActArgs*)d); },
+    [](void* a, int i, const fql_engine& e, const fql_engine::Eval& ev, bool, const ChunkRows& r) {
+        const int ad = e.cfg.act_dim;
+        ((RebracActArgs*)a)[i] = RebracActArgs{ev.p_os.out, r.z, r.dst, e.seed, r.seed, r.mm, ad, pad16(ad), ad, ad, 0, r.start, r.z ? 1 : 2, e.rcfg.tanh_squash, 1,
+                                               e.rcfg.actor_noise * r.temperature, e.rcfg.actor_noise_clip};
+    },
+    sizeof(RebracActArgs)};
+// IQL: fql_iql_sample_multi_kernel on the means - each member's own row numbers (row0 = start), seed, key and log_stds (P + ls_off, null
+// under const_std), one temperature
+const SampleFinish k_finish_iql = {
+    [](int n_pad, int ad, int K, const void* d) { return bind(fql_iql_sample_multi_kernel, per_element(n_pad * ad, FQL_THREADS, K), (const IqlSampleArgs*)d); },
+    [](void* a, int i, const fql_engine& e, const fql_engine::Eval& ev, bool, const ChunkRows& r) {
+        const int ad = e.cfg.act_dim;
+        ((IqlSampleArgs*)a)[i] = IqlSampleArgs{ev.p_os.out, e.qcfg.const_std ? nullptr : e.P + e.ls_off, r.z, r.dst, e.seed, r.seed, r.mm, ad, pad16(ad), r.start, r.temperature};
+    },
+    sizeof(IqlSampleArgs)};
+// SAC: fql_sac_act_multi_kernel, one thread per row, on the actor's forward, whose last layer is the [H, 2 ap] head layer - noise_mode 1
+// or 2, clip_out 1, no lp
+const SampleFinish k_finish_sac = {
+    [](int n_pad, int, int K, const void* d) { return bind(fql_sac_act_multi_kernel, per_element(n_pad, FQL_THREADS, K), (const SacActArgs*)d); },
+    [](void* a, int i, const fql_engine& e, const fql_engine::Eval& ev, bool, const ChunkRows& r) {
+        const int ad = e.cfg.act_dim;
+        ((SacActArgs*)a)[i] = SacActArgs{ev.p_os.out, r.z, r.dst, r.dst, nullptr, e.seed, r.seed, r.mm, ad, pad16(ad), ad, ad, 0, r.start, r.mm, r.z ? 1 : 2, e.scfg.tanh_squash, 1,
+                                         r.temperature};
+    },
+    sizeof(SacActArgs)};
+
+// The row assembly that opens a chunk of the guidance-sweep loop (fql_group_s::sample_cfg), over the chunk's [K] argument structs; its
+// [K] ExtractArgs lie behind them.  goals: member i's goal rows of the chunk, where the kind has them.
+struct SweepAssemble {
+    Bound (*bind)(int half, int K, const void* d);
+    void (*fill)(void* a, int i, const fql_engine& e, const fql_engine::Eval& ev, const float* obs, const float* goals, int half, const ChunkRows& r);
+    size_t bytes;
+};
+const SweepAssemble k_assemble_bc = {
+    [](int half, int K, const void* d) { return bind(fql_bc_assemble_multi_kernel, Geo(dim3((half + 3) / 4, K), dim3(FQL_THREADS), 0), (const BcAssembleArgs*)d); },
+    [](void* a, int i, const fql_engine& e, const fql_engine::Eval& ev, const float* obs, const float*, int half, const ChunkRows& r) {
+        const int ad = e.cfg.act_dim;
+        ((BcAssembleArgs*)a)[i] = BcAssembleArgs{obs, r.z, ev.X, ev.Xf, e.seed, r.seed, r.mm, half, e.cfg.obs_dim, ad, e.nets[NET_BC].in_p(), pad16(ad), r.start};
+    },
+    sizeof(BcAssembleArgs)};
+// CFGRL's writes both halves - [obs | goal] and [obs | the member's own unc_embed leaf]
+const SweepAssemble k_assemble_cfgrl = {
+    [](int half, int K, const void* d) { return bind(fql_cfgrl_assemble_multi_kernel, Geo(dim3((half + 3) / 4, K), dim3(FQL_THREADS), 0), (const CfgrlAssembleArgs*)d); },
+    [](void* a, int i, const fql_engine& e, const fql_engine::Eval& ev, const float* obs, const float* goals, int half, const ChunkRows& r) {
+        const int ad = e.cfg.act_dim;
+        ((CfgrlAssembleArgs*)a)[i] = CfgrlAssembleArgs{obs, goals, e.P + e.emb_off, r.z, ev.X, ev.Xf, e.seed, r.seed, r.mm, half, e.cfg.obs_dim, e.gcfg.goal_dim, ad,
+                                                       e.nets[NET_BC].in_p(), pad16(ad), r.start};
+    },
+    sizeof(CfgrlAssembleArgs)};
+
+// What a group call does; GroupKind::calls names the call of each kind of group that does it, as the refusal on a group of that kind
+// says it: "<fn> is not available on a group of <kind> agents (<hint>)"
+enum GroupCall { GC_UPDATE, GC_SAMPLE, GC_STATS, GC_FLOW };
+enum GroupSampler { GS_PLAIN, GS_SWEEP, GS_BEST_OF_N };
+struct GroupKind {
+    AgentKind kind;        // the row's index
+    const char* create;    // its create call; nullptr: the kind has no groups
+    const char* takes;     // what that call's refusal of another kind's member says
+    const char* grouped_by;   // what the other creates' refusal of a member of THIS kind adds, or nullptr
+    const char* free_fields;  // what may differ between members beside the create seed ...
+    bool (*same_structure)(const fql_engine&, const fql_engine&);   // ... and the compare that lets exactly that differ
+    int programs;          // fused update programs (fql_group_s::progs): prog_full; + prog_critic; + prog_actor, prog_none
+    int infos;             // floats per member of an update's infos where that is not the members' num_info(), else 0
+    bool goals;            // every update sets each member's goal source (CfgrlSrc) beside its dataset source, and the sampler takes goals
+    const char* calls[4];  // by GroupCall
+    GroupSampler sampler;  // the chunk loop of its sample_actions
+    const SampleFinish* finish;      // GS_PLAIN, and GS_BEST_OF_N's flow call: assemble-multi, the members' program, this launch
+    const SweepAssemble* assemble;   // GS_SWEEP: this launch, the members' sweep program, extract-multi
+};
+constexpr GroupKind k_group_kinds[kNumKinds] = {
+    {AgentKind::FQL, "fql_group_create", "groups take FQL agents only", nullptr, "alpha", same_fql, 1, 0, false,
+     {"fql_group_update_from_dataset", "fql_group_sample_actions", "fql_group_sample_stats", "fql_group_flow_actions"}, GS_PLAIN, &k_finish_extract, nullptr},
+    // the one fused program; sample_actions zips the members' Euler flow and critic pair between the multi-instance
+    // forms of IFQL's three sampling kernels (fql_group_s::sample_bon); the members have no one-step actor
+    {AgentKind::IFQL, "fql_ifql_group_create", "IFQL groups take IFQL agents only", nullptr, "expectile", same_ifql, 1, 0, false,
+     {"fql_ifql_group_update_from_dataset", "best of num_samples: fql_ifql_group_sample_actions", "fql_ifql_group_stats", "fql_ifql_group_flow_actions"},
+     GS_BEST_OF_N, &k_finish_extract, nullptr},
+    // a second fused program, the zip of the members' critic-only step; infos in fql_rebrac_update's layout, the
+    // 13 floats of DevState::info per member (12 or 7 by the step's kind, zeros behind them)
+    {AgentKind::REBRAC, "fql_rebrac_group_create", "ReBRAC groups take ReBRAC agents only", nullptr, "alpha_actor / alpha_critic", same_rebrac, 2, FQL_NUM_INFO, false,
+     {"the step kind is an argument: fql_rebrac_group_update_from_dataset", "fql_rebrac_group_sample_actions", "fql_rebrac_group_stats",
+      "the actor is deterministic: fql_rebrac_group_sample_actions"},
+     GS_PLAIN, &k_finish_rebrac, nullptr},
+    // the one fused program, entered with each member's dataset source or with its two-source balanced one (the
+    // member's own replay ring)
+    {AgentKind::SAC, "fql_sac_group_create", "SAC groups take SAC agents only", nullptr, "target_entropy / target_entropy_multiplier", same_sac, 1, 0, false,
+     {"fql_sac_group_update_from_dataset (or fql_sac_group_update_balanced)", "it takes a temperature: fql_sac_group_sample_actions", "fql_sac_group_stats",
+      "the actor is a Gaussian, there is no flow: fql_sac_group_sample_actions"},
+     GS_PLAIN, &k_finish_sac, nullptr},
+    {AgentKind::BC, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, false, {}, GS_PLAIN, nullptr, nullptr},
+    // the one fused program - IFQL's value and critic lanes beside the Gaussian actor's own kernels
+    {AgentKind::IQL, "fql_iql_group_create", "IQL groups take IQL agents only", nullptr, "expectile / alpha", same_iql, 1, 0, false,
+     {"fql_iql_group_update_from_dataset", "it takes a temperature: fql_iql_group_sample_actions", "fql_iql_group_stats",
+      "the actor is a Gaussian, there is no flow: fql_iql_group_sample_actions"},
+     GS_PLAIN, &k_finish_iql, nullptr},
+    // one fused program per step kind (full, critic-only, actor-only, neither); the sampler zips the members' sweep
+    // program: one guidance weight per row
+    {AgentKind::IQLD, "fql_iqld_group_create", "IQL-diffusion groups take IQL-diffusion agents only", nullptr, "awr_temperature / softmax_beta", same_iqld, 4, 0, false,
+     {"the step kind is two arguments: fql_iqld_group_update_from_dataset", "it takes guidance weights: fql_iqld_group_sample_actions", "fql_iqld_group_stats",
+      "it takes guidance weights: fql_iqld_group_sample_actions"},
+     GS_SWEEP, nullptr, &k_assemble_bc},
+    // the one fused program - BC's single lane; the sampler zips the members' sweep program behind CFGRL's two-half
+    // row assembly
+    {AgentKind::CFGRL, "fql_cfgrl_group_create", "CFGRL groups take CFGRL agents only", "; CFGRL agents are grouped by fql_cfgrl_group_create",
+     "cfg / actor_p_curgoal / actor_p_trajgoal / actor_p_randomgoal", same_cfgrl, 1, 0, true,
+     {"it sets each member's goal source: fql_cfgrl_group_update_from_dataset", "it takes goals and guidance weights: fql_cfgrl_group_sample_actions",
+      "fql_cfgrl_group_stats", "it takes goals and guidance weights: fql_cfgrl_group_sample_actions"},
+     GS_SWEEP, nullptr, &k_assemble_cfgrl},
+};
+constexpr bool group_rows_in_order() {
+    for (int i = 0; i < kNumKinds; ++i) if ((int)k_group_kinds[i].kind != i) return false;
+    return true;
+}
+static_assert(group_rows_in_order(), "k_group_kinds is indexed by AgentKind");
+// the update programs a group fuses, in the order of fql_group_s::progs: the first GroupKind::programs of these
+constexpr Program fql_engine::* k_group_programs[] = {&fql_engine::prog_full, &fql_engine::prog_critic, &fql_engine::prog_actor, &fql_engine::prog_none};
+
 }  // namespace
 
 struct fql_group_s {
     std::vector<fql_handle> m;
-    AgentKind kind = AgentKind::FQL;     // the members' kind: FQL (fql_group_create), ReBRAC (fql_rebrac_group_create), IQL-diffusion (fql_iqld_group_create), IFQL (fql_ifql_group_create), IQL (fql_iql_group_create), CFGRL (fql_cfgrl_group_create) or SAC (fql_sac_group_create)
+    const GroupKind* kind = nullptr;     // the members' kind: its row of k_group_kinds
     int K = 0, B = 0;
     hipStream_t lanes[FQL_LANES] = {};   // lane 0 = the group's own stream
-    // One fused program per entry of group_programs(kind), in its order.  [0]: the members' prog_full zipped (every kind); [1]: their
-    // prog_critic (ReBRAC, IQL-diffusion); [2], [3]: their prog_actor and prog_none (IQL-diffusion)
+    // One fused program per entry of k_group_programs, the first kind->programs of them: the members' prog_full zipped, their
+    // prog_critic, their prog_actor and prog_none
     enum { FULL = 0, CRITIC = 1, ACTOR = 2, NONE = 3, MAX_PROGS = 4 };
     GProgram progs[MAX_PROGS];
     hipEvent_t ev_in = nullptr, ev_done = nullptr;
@@ -6626,9 +6790,8 @@ struct fql_group_s {
         std::vector<GLaunch> q;            // an IFQL group's best-of-N sampler: the members' critic pair (Eval::prog_q) zipped
         float *st_obs = nullptr, *st_noise = nullptr, *st_out = nullptr;
         float* st_goal = nullptr;          // a CFGRL group: staging of host goals
-        unsigned char* d_args = nullptr;   // [K] AssembleArgs, then [K] ExtractArgs (a ReBRAC group: [K] RebracActArgs; an IQL group: [K] IqlSampleArgs; a SAC group: [K] SacActArgs)
-        Bound assemble, extract;           // the multi-instance launches over d_args, blockIdx.y = member
-        Bound act;                         // a ReBRAC group: fql_rebrac_act_multi_kernel writes the actions, no extract launch; an IQL group: fql_iql_sample_multi_kernel; a SAC group: fql_sac_act_multi_kernel
+        unsigned char* d_args = nullptr;   // [K] argument structs of the chunk's first launch, then those of its last (arg_bytes())
+        Bound assemble, finish;            // those two multi-instance launches over d_args, blockIdx.y = member
         // an IFQL group's best-of-N sampler, over the other layout of d_args: [K] IfqlRepeatArgs, [K] IfqlQinArgs, [K] IfqlSelectArgs
         Bound repeat, qin, select;
     };
@@ -6641,13 +6804,13 @@ struct fql_group_s {
     hipEvent_t arg_ev[kArgRing] = {};
     char arg_state[kArgRing] = {};   // 0 = free, 1 = behind arg_ev, 2 = on the legacy stream
     int arg_pos = 0;
-    // (a slot holds the layout of the group's kind: [K] AssembleArgs + [K] ExtractArgs, [K] AssembleArgs + [K] RebracActArgs, an IQL
-    // group's [K] AssembleArgs + [K] IqlSampleArgs, a SAC group's [K] AssembleArgs + [K] SacActArgs, or an IQL-diffusion group's [K] BcAssembleArgs + [K] ExtractArgs; an IFQL group's
-    // flow call uses the first, its best-of-N call [K] IfqlRepeatArgs + [K] IfqlQinArgs + [K] IfqlSelectArgs; a CFGRL group's
-    // [K] CfgrlAssembleArgs + [K] ExtractArgs)
-    size_t asm_bytes() const { return kind == AgentKind::IQLD ? sizeof(BcAssembleArgs) : kind == AgentKind::CFGRL ? sizeof(CfgrlAssembleArgs) : sizeof(AssembleArgs); }
-    size_t bon_bytes() const { return kind == AgentKind::IFQL ? sizeof(IfqlRepeatArgs) + sizeof(IfqlQinArgs) + sizeof(IfqlSelectArgs) : 0; }
-    size_t arg_bytes() const { return (size_t)K * std::max(asm_bytes() + std::max({sizeof(ExtractArgs), sizeof(RebracActArgs), sizeof(IqlSampleArgs), sizeof(SacActArgs)}), bon_bytes()); }
+    // (a slot holds the layout of the group's kind: [K] AssembleArgs and its finishing launch's [K] structs, or its sweep assembly's
+    // [K] structs and [K] ExtractArgs; a best-of-N call [K] IfqlRepeatArgs + [K] IfqlQinArgs + [K] IfqlSelectArgs)
+    size_t asm_bytes() const { return kind->sampler == GS_SWEEP ? kind->assemble->bytes : sizeof(AssembleArgs); }
+    size_t arg_bytes() const {
+        const size_t bon = kind->sampler == GS_BEST_OF_N ? sizeof(IfqlRepeatArgs) + sizeof(IfqlQinArgs) + sizeof(IfqlSelectArgs) : 0;
+        return (size_t)K * std::max(asm_bytes() + (kind->sampler == GS_SWEEP ? sizeof(ExtractArgs) : kind->finish->bytes), bon);
+    }
 
     Sample& sample_ws(int n_pad, bool flow) {
         std::unique_ptr<Sample>& slot = samples[n_pad];
@@ -6655,25 +6818,14 @@ struct fql_group_s {
             auto w = std::make_unique<Sample>();
             const int od = m[0]->cfg.obs_dim, ad = m[0]->cfg.act_dim;
             w->n_pad = n_pad;
-            if (kind != AgentKind::IFQL)   // (an IFQL member's workspace has no one-step actor: its calls are the flow and best of N)
+            if (kind->sampler != GS_BEST_OF_N)   // (a best-of-N member's workspace has no one-step actor: its calls are the flow and best of N)
                 w->os = zip_lane0([&](fql_engine& e) -> Program& { return e.get_eval(n_pad).prog_os; }, "the one-step sampler");
             w->st_obs = (float*)galloc((size_t)K * n_pad * od * sizeof(float));
             w->st_noise = (float*)galloc((size_t)K * n_pad * ad * sizeof(float));
             w->st_out = (float*)galloc((size_t)K * n_pad * ad * sizeof(float));
             w->d_args = (unsigned char*)galloc(arg_bytes());
             w->assemble = bind(fql_assemble_multi_kernel, Geo(dim3((n_pad + 3) / 4, K), dim3(FQL_THREADS), 0), (const AssembleArgs*)w->d_args);
-            if (kind == AgentKind::IQL)   // (grid x over the padded rows: a chunk's m <= n_pad, elements past m * ad return at once)
-                w->act = bind(fql_iql_sample_multi_kernel, Geo(dim3((n_pad * ad + FQL_THREADS - 1) / FQL_THREADS, K), dim3(FQL_THREADS), 0),
-                              (const IqlSampleArgs*)(w->d_args + (size_t)K * sizeof(AssembleArgs)));
-            else if (kind == AgentKind::SAC)   // (one thread per row; rows past a chunk's m return at once)
-                w->act = bind(fql_sac_act_multi_kernel, Geo(dim3((n_pad + FQL_THREADS - 1) / FQL_THREADS, K), dim3(FQL_THREADS), 0),
-                              (const SacActArgs*)(w->d_args + (size_t)K * sizeof(AssembleArgs)));
-            else if (kind != AgentKind::REBRAC)
-                w->extract = bind(fql_extract_multi_kernel, Geo(dim3((n_pad * ad + 255) / 256, K), dim3(256), 0),
-                                  (const ExtractArgs*)(w->d_args + (size_t)K * sizeof(AssembleArgs)));
-            else
-                w->act = bind(fql_rebrac_act_multi_kernel, Geo(dim3((n_pad * ad + FQL_THREADS - 1) / FQL_THREADS, K), dim3(FQL_THREADS), 0),
-                          (const RebracActArgs*)(w->d_args + (size_t)K * sizeof(AssembleArgs)));
+            w->finish = kind->finish->bind(n_pad, ad, K, w->d_args + (size_t)K * sizeof(AssembleArgs));
             slot = std::move(w);
         }
         if (flow && slot->flow.empty())
@@ -6696,13 +6848,9 @@ struct fql_group_s {
             w->st_noise = (float*)galloc((size_t)K * half * ad * sizeof(float));
             w->st_out = (float*)galloc((size_t)K * half * ad * sizeof(float));
             w->d_args = (unsigned char*)galloc(arg_bytes());
-            if (kind == AgentKind::CFGRL) {
-                w->st_goal = (float*)galloc((size_t)K * half * m[0]->gcfg.goal_dim * sizeof(float));
-                w->assemble = bind(fql_cfgrl_assemble_multi_kernel, Geo(dim3((half + 3) / 4, K), dim3(FQL_THREADS), 0), (const CfgrlAssembleArgs*)w->d_args);
-            } else
-                w->assemble = bind(fql_bc_assemble_multi_kernel, Geo(dim3((half + 3) / 4, K), dim3(FQL_THREADS), 0), (const BcAssembleArgs*)w->d_args);
-            w->extract = bind(fql_extract_multi_kernel, Geo(dim3((half * ad + 255) / 256, K), dim3(256), 0),
-                              (const ExtractArgs*)(w->d_args + (size_t)K * asm_bytes()));
+            if (kind->goals) w->st_goal = (float*)galloc((size_t)K * half * m[0]->gcfg.goal_dim * sizeof(float));
+            w->assemble = kind->assemble->bind(half, K, w->d_args);
+            w->finish = k_finish_extract.bind(half, ad, K, w->d_args + (size_t)K * asm_bytes());
             slot = std::move(w);
         }
         return *slot;
@@ -6726,12 +6874,11 @@ struct fql_group_s {
         }
         return w;
     }
-    // launches of one fused sampling call on a single chunk, counted from the built program: assemble, the zipped launches, extract
-    // (a ReBRAC, IQL or SAC group: the kind's action kernel in extract's place; an IFQL group's best-of-N call: repeat, the flow, qin, the
-    // critic pair, select)
+    // launches of one fused sampling call on a single chunk, counted from the built program: assemble, the zipped launches, the
+    // finishing launch (a best-of-N call: repeat, the flow, qin, the critic pair, select)
     int64_t sample_launches(bool flow) {
-        if (kind == AgentKind::IQLD || kind == AgentKind::CFGRL) return 2 + (int64_t)sample_ws_cfg(16).flow.size();
-        if (kind == AgentKind::IFQL && !flow) {
+        if (kind->sampler == GS_SWEEP) return 2 + (int64_t)sample_ws_cfg(16).flow.size();
+        if (kind->sampler == GS_BEST_OF_N && !flow) {
             Sample& w = sample_ws_bon(pad16(m[0]->num_samples));
             return 3 + (int64_t)w.flow.size() + (int64_t)w.q.size();
         }
@@ -6769,15 +6916,12 @@ struct fql_group_s {
     // that a seeded draw is keyed as fql_engine::eval_rows keys it, (member's key, seed_i + start) - assemble-multi, the zipped launches of
     // the members' program, extract-multi, as direct launches on s.  observations [K, n, od], noise [K, n, ad] or null, out [K, n, ad]:
     // host or device each.  A host result is copied out and waited for per chunk.
-    // A ReBRAC group (fql_rebrac_group_sample_actions): assemble-multi of [obs | 0], the zipped launches of the actor's forward, then
-    // fql_rebrac_act_multi_kernel, which writes the actions where extract-multi would - every argument as fql_engine::sample_actor fills it.
-    // An IQL group (fql_iql_group_sample_actions): the same two launches around the actor's forward, then fql_iql_sample_multi_kernel on the
-    // means - each member's own row numbers (row0 = start), seed, key and log_stds (P + ls_off, null under const_std), one temperature.
-    // A SAC group (fql_sac_group_sample_actions): the same again around the actor's forward, whose last layer is the [H, 2 ap] head layer,
-    // then fql_sac_act_multi_kernel on the heads - noise_mode 1 or 2, clip_out 1, no lp, row0 and seed as fql_engine::sample_actor sets them.
+    // Members whose actor reads the observation alone (fql_engine::actor_on_obs): assemble-multi of [obs | 0] with the seed unshifted, the
+    // zipped launches of the actor's forward, then the kind's finishing launch (SampleFinish), which draws the noise under the member's
+    // own row numbers (row0 = start) and writes the actions where extract-multi would.
     void sample(bool flow, const float* obs, const float* noise, const uint64_t* seeds, float temperature, int n, float* out, hipStream_t s) {
-        const int od = m[0]->cfg.obs_dim, ad = m[0]->cfg.act_dim, ap = pad16(ad);
-        const bool rebrac = kind == AgentKind::REBRAC, iql = kind == AgentKind::IQL, sac = kind == AgentKind::SAC;
+        const int od = m[0]->cfg.obs_dim, ad = m[0]->cfg.act_dim;
+        const bool on_obs = m[0]->actor_on_obs();
         const bool dev_obs = fql_engine::is_device_ptr(obs), dev_z = noise && fql_engine::is_device_ptr(noise), dev_out = fql_engine::is_device_ptr(out);
         for (int start = 0; start < n; start += 4096) {
             const int mm = std::min(4096, n - start);
@@ -6786,43 +6930,30 @@ struct fql_group_s {
             const Rows z = chunk_rows(noise, dev_z, w.st_noise, ad, n, start, mm, s);
             unsigned char* slot = arg_slot();
             AssembleArgs* aa = (AssembleArgs*)slot;
-            ExtractArgs* ea = (ExtractArgs*)(slot + (size_t)K * sizeof(AssembleArgs));
-            RebracActArgs* ra = (RebracActArgs*)(slot + (size_t)K * sizeof(AssembleArgs));
-            IqlSampleArgs* qa = (IqlSampleArgs*)(slot + (size_t)K * sizeof(AssembleArgs));
-            SacActArgs* sa = (SacActArgs*)(slot + (size_t)K * sizeof(AssembleArgs));
             for (int i = 0; i < K; ++i) {
                 fql_engine& e = *m[i];
                 fql_engine::Eval& ev = e.get_eval(w.n_pad);
-                if (rebrac || iql || sac) {
-                    const uint64_t sd = seeds ? seeds[i] : 0;
-                    const float* zi = z.p ? z.p + i * z.stride : nullptr;
-                    float* dst = dev_out ? out + ((size_t)i * n + start) * ad : w.st_out + (size_t)i * mm * ad;
-                    aa[i] = AssembleArgs{o.p + i * o.stride, nullptr, ev.X, e.seed, sd, mm, w.n_pad, od, 0, e.nets[NET_BC].in_p()};   // [obs | 0]
-                    if (iql)
-                        qa[i] = IqlSampleArgs{ev.p_os.out, e.qcfg.const_std ? nullptr : e.P + e.ls_off, zi, dst, e.seed, sd, mm, ad, ap, start, temperature};
-                    else if (sac)
-                        sa[i] = SacActArgs{ev.p_os.out, zi, dst, dst, nullptr, e.seed, sd, mm, ad, ap, ad, ad, 0, start, mm, zi ? 1 : 2, e.scfg.tanh_squash, 1, temperature};
-                    else
-                        ra[i] = RebracActArgs{ev.p_os.out, zi, dst, e.seed, sd, mm, ad, ap, ad, ad, 0, start, zi ? 1 : 2, e.rcfg.tanh_squash, 1,
-                                              e.rcfg.actor_noise * temperature, e.rcfg.actor_noise_clip};
-                    continue;
-                }
-                aa[i] = AssembleArgs{o.p + i * o.stride, z.p ? z.p + i * z.stride : nullptr, flow ? ev.Xf : ev.X, e.seed,
-                                     (seeds ? seeds[i] : 0) + (uint64_t)start, mm, w.n_pad, od, ad, flow ? e.nets[NET_BC].in_p() : e.nets[NET_OS].in_p()};
-                ea[i] = ExtractArgs{flow ? ev.tgt : ev.p_os.out, dev_out ? out + ((size_t)i * n + start) * ad : w.st_out + (size_t)i * mm * ad, mm, ad, ap};
+                const ChunkRows r{z.p ? z.p + i * z.stride : nullptr, dev_out ? out + ((size_t)i * n + start) * ad : w.st_out + (size_t)i * mm * ad,
+                                  seeds ? seeds[i] : 0, mm, start, temperature};
+                if (on_obs)
+                    aa[i] = AssembleArgs{o.p + i * o.stride, nullptr, ev.X, e.seed, r.seed, mm, w.n_pad, od, 0, e.nets[NET_BC].in_p()};   // [obs | 0]
+                else
+                    aa[i] = AssembleArgs{o.p + i * o.stride, r.z, flow ? ev.Xf : ev.X, e.seed, r.seed + (uint64_t)start, mm, w.n_pad, od, ad,
+                                         flow ? e.nets[NET_BC].in_p() : e.nets[NET_OS].in_p()};
+                kind->finish->fill(slot + (size_t)K * sizeof(AssembleArgs), i, e, ev, flow, r);
             }
-            issue_chunk(w, slot, flow ? w.flow : w.os, rebrac || iql || sac ? w.act : w.extract, !dev_obs || (noise && !dev_z), dev_out ? nullptr : out, n, start, mm, s);
+            issue_chunk(w, slot, flow ? w.flow : w.os, !dev_obs || (noise && !dev_z), dev_out ? nullptr : out, n, start, mm, s);
         }
     }
     // The tail of a chunk of either sampler: the slot's argument structs to the device with the ring's event behind them, the wait that
     // ends the borrowing of host inputs (host rows - and weights - are the caller's again when the call returns), the assemble launch,
     // the zipped launches, the finishing launch, and a host result (host_out: the call's `out`, [K, n, ad]) copied out and waited for.
-    void issue_chunk(Sample& w, const unsigned char* slot, std::vector<GLaunch>& zipped, const Bound& fin, bool host_inputs, float* host_out,
-                     int n, int start, int mm, hipStream_t s) {
+    void issue_chunk(Sample& w, const unsigned char* slot, std::vector<GLaunch>& zipped, bool host_inputs, float* host_out, int n, int start, int mm,
+                     hipStream_t s) {
         issue_chunk(w, slot, host_inputs, host_out, n, start, mm, s, [&] {
             launch_bound(w.assemble, w.assemble.args.data(), s);
             for (GLaunch& G : zipped) launch_bound(G.k, G.k.args.data(), s);
-            launch_bound(fin, fin.args.data(), s);
+            launch_bound(w.finish, w.finish.args.data(), s);
         });
     }
     // (the same with the chunk's launches as a callable: an IFQL group's best-of-N chunk is five groups of launches, not three)
@@ -6848,7 +6979,7 @@ struct fql_group_s {
     // A CFGRL group (fql_cfgrl_group_sample_actions): fql_cfgrl_sample_actions_cfgs of every member the same way, with `goals` [K, n, G]
     // beside the observations and fql_cfgrl_assemble_multi_kernel, whose unconditional half reads each member's own unc_embed leaf.
     void sample_cfg(const float* obs, const float* goals, const float* noise, const uint64_t* seeds, const float* cfgs, int n, float* out, hipStream_t s) {
-        const int od = m[0]->cfg.obs_dim, ad = m[0]->cfg.act_dim, ap = pad16(ad), Gd = kind == AgentKind::CFGRL ? m[0]->gcfg.goal_dim : 0;
+        const int od = m[0]->cfg.obs_dim, ad = m[0]->cfg.act_dim, Gd = kind->goals ? m[0]->gcfg.goal_dim : 0;
         const bool dev_obs = fql_engine::is_device_ptr(obs), dev_z = noise && fql_engine::is_device_ptr(noise), dev_out = fql_engine::is_device_ptr(out);
         const bool dev_c = fql_engine::is_device_ptr(cfgs), dev_g = !Gd || fql_engine::is_device_ptr(goals);
         if (!dev_c)
@@ -6861,23 +6992,17 @@ struct fql_group_s {
             const Rows z = chunk_rows(noise, dev_z, w.st_noise, ad, n, start, mm, s);
             const Rows gl = Gd ? chunk_rows(goals, dev_g, w.st_goal, Gd, n, start, mm, s) : Rows{nullptr, 0};
             unsigned char* slot = arg_slot();
-            BcAssembleArgs* aa = (BcAssembleArgs*)slot;
-            CfgrlAssembleArgs* ga = (CfgrlAssembleArgs*)slot;
-            ExtractArgs* ea = (ExtractArgs*)(slot + (size_t)K * asm_bytes());
             for (int i = 0; i < K; ++i) {
                 fql_engine& e = *m[i];
                 fql_engine::Eval& ev = e.get_eval(2 * half, true);
-                const float* zi = z.p ? z.p + i * z.stride : nullptr;
-                if (Gd)
-                    ga[i] = CfgrlAssembleArgs{o.p + i * o.stride, gl.p + i * gl.stride, e.P + e.emb_off, zi, ev.X, ev.Xf, e.seed, seeds ? seeds[i] : 0, mm, half,
-                                              od, Gd, ad, e.nets[NET_BC].in_p(), ap, start};
-                else
-                    aa[i] = BcAssembleArgs{o.p + i * o.stride, zi, ev.X, ev.Xf, e.seed, seeds ? seeds[i] : 0, mm, half, od, ad, e.nets[NET_BC].in_p(), ap, start};
-                ea[i] = ExtractArgs{ev.tgt, dev_out ? out + ((size_t)i * n + start) * ad : w.st_out + (size_t)i * mm * ad, mm, ad, ap};
+                const ChunkRows r{z.p ? z.p + i * z.stride : nullptr, dev_out ? out + ((size_t)i * n + start) * ad : w.st_out + (size_t)i * mm * ad,
+                                  seeds ? seeds[i] : 0, mm, start, 1.0f};
+                kind->assemble->fill(slot, i, e, ev, o.p + i * o.stride, Gd ? gl.p + i * gl.stride : nullptr, half, r);
+                k_finish_extract.fill(slot + (size_t)K * asm_bytes(), i, e, ev, true, r);
                 HIP_CHECK(hipMemcpyAsync(ev.cfgs, cfgs + (size_t)i * n + start, (size_t)mm * sizeof(float), hipMemcpyDefault, s));
                 if (half > mm) HIP_CHECK(hipMemsetAsync(ev.cfgs + mm, 0, (size_t)(half - mm) * sizeof(float), s));
             }
-            issue_chunk(w, slot, w.flow, w.extract, !dev_obs || (noise && !dev_z) || !dev_c || !dev_g, dev_out ? nullptr : out, n, start, mm, s);
+            issue_chunk(w, slot, w.flow, !dev_obs || (noise && !dev_z) || !dev_c || !dev_g, dev_out ? nullptr : out, n, start, mm, s);
         }
     }
 
@@ -6974,25 +7099,36 @@ struct fql_group_s {
 };
 
 namespace {
-// The update programs a group of `kind` fuses (fql_group_s::progs, in this order): every kind's prog_full; ReBRAC's prog_critic (the
-// critic-only step) behind it; IQL-diffusion's four step kinds.  IFQL, IQL, CFGRL and SAC have the one program.
-std::vector<Program fql_engine::*> group_programs(AgentKind kind) {
-    std::vector<Program fql_engine::*> p{&fql_engine::prog_full};
-    if (kind == AgentKind::REBRAC || kind == AgentKind::IQLD) p.push_back(&fql_engine::prog_critic);
-    if (kind == AgentKind::IQLD) { p.push_back(&fql_engine::prog_actor); p.push_back(&fql_engine::prog_none); }
-    return p;
+// The body of a group entry point: FQL_OK, or the code of what it threw with the message where fql_last_error(NULL) reads it
+#define GROUP_TRY(...)                                     \
+    try {                                                  \
+        __VA_ARGS__;                                       \
+        return FQL_OK;                                     \
+    } catch (const Invalid& e) {                           \
+        g_create_error = e.msg;                            \
+        return FQL_E_INVALID;                              \
+    } catch (const HipError& e) {                          \
+        g_create_error = e.msg;                            \
+        return FQL_E_HIP;                                  \
+    } catch (const std::exception& e) {                    \
+        g_create_error = e.what();                         \
+        return FQL_E_HIP;                                  \
+    }
+// A group call on a group of another kind: FQL_E_STATE, naming the call of the group's own kind that serves it
+bool group_wrong_kind(fql_group g, AgentKind kind, const char* fn, GroupCall c) {
+    if (g->kind->kind == kind) return false;
+    g_create_error = std::string(fn) + " is not available on a group of " + g->m[0]->desc().name + " agents (" + g->kind->calls[c] + ")";
+    return true;
 }
-// the members' restrictions and the structural identity of their programs (fql_group_create, fql_rebrac_group_create: `fn`).  What may
-// differ between members beside the create seed: FQL's alpha; ReBRAC's alpha_actor and alpha_critic; IQL-diffusion's awr_temperature and
-// softmax_beta (both reach the device as IqldWeightArgs::temp alone); IFQL's expectile (IfqlValueArgs::expectile alone) - kernel arguments,
-// not structure.  An IFQL member's num_samples is structure: it sets the row count of the sampler's workspaces.  IQL's expectile and
-// alpha are arguments (IfqlValueArgs::expectile; IqlAwrArgs / IqlDdpgArgs / IqlActorGradArgs::alpha); its actor_loss and const_std are
-// structure: they choose the launches and the log_stds leaf.  CFGRL's cfg is the sampler's default guidance weight, an argument of the
-// sampling calls, and its three goal-mixture probabilities reach the device only as CfgrlSrc::thr_traj, p_cur and all_cur, which every
-// update writes per member: arguments too.  goal_dim, flow_steps and p_uncond are structure or shared constants.  SAC's target_entropy
-// (and the multiplier it is derived from when NaN) reaches the device as SacActorArgs::target_entropy alone: an argument; tanh_squash,
-// backup_entropy, q_agg and the rest choose kernel arguments every member shares.
-void group_check(const char* fn, AgentKind kind, const fql_handle* members, int k) {
+// the first line of an entry point `fn` that serves groups of `kind`
+#define GROUP_ENTER(g, kind, fn, call)                                                                \
+    do {                                                                                              \
+        if (!(g)) { g_create_error = std::string(fn) + ": NULL group"; return FQL_E_INVALID; }        \
+        if (group_wrong_kind((g), (kind), (fn), (call))) return FQL_E_STATE;                          \
+    } while (0)
+
+// the members' restrictions and the structural identity of their programs (`fn`: the create call)
+void group_check(const char* fn, const GroupKind& kind, const fql_handle* members, int k) {
     if (!members || k <= 0) invalid("%s: members must be a non-empty array (k = %d)", fn, k);
     for (int i = 0; i < k; ++i) {
         fql_handle h = members[i];
@@ -7002,46 +7138,10 @@ void group_check(const char* fn, AgentKind kind, const fql_handle* members, int 
         if (h->visual) invalid("%s: member %d has an encoder (groups take state agents only)", fn, i);
         if (h->cfg.precision != 0) invalid("%s: member %d has precision %d (groups take fp32 members only)", fn, i, h->cfg.precision);
         if (h->began) invalid("%s: member %d is between fql_update_begin and fql_update_end", fn, i);
-        fql_config a = h->cfg, b = members[0]->cfg;
-        if (kind == AgentKind::FQL) a.alpha = b.alpha = 0.f;
-        a.batch_size = b.batch_size = 0;
-        bool same = std::memcmp(&a, &b, sizeof a) == 0;
-        if (kind == AgentKind::REBRAC) {
-            fql_rebrac_config ra = h->rcfg, rb = members[0]->rcfg;
-            ra.alpha_actor = rb.alpha_actor = ra.alpha_critic = rb.alpha_critic = 0.f;
-            same = same && std::memcmp(&ra, &rb, sizeof ra) == 0;
-        }
-        if (kind == AgentKind::IQLD) {
-            fql_iqld_config da = h->dcfg, db = members[0]->dcfg;
-            da.awr_temperature = db.awr_temperature = da.softmax_beta = db.softmax_beta = 0.f;
-            same = same && std::memcmp(&da, &db, sizeof da) == 0;
-        }
-        if (kind == AgentKind::IFQL) same = same && h->num_samples == members[0]->num_samples;
-        if (kind == AgentKind::IQL) {
-            fql_iql_config qa = h->qcfg, qb = members[0]->qcfg;
-            qa.expectile = qb.expectile = qa.alpha = qb.alpha = 0.f;
-            same = same && std::memcmp(&qa, &qb, sizeof qa) == 0;
-        }
-        if (kind == AgentKind::CFGRL) {
-            fql_cfgrl_config ga = h->gcfg, gb = members[0]->gcfg;
-            ga.cfg = gb.cfg = 0.f;
-            ga.actor_p_curgoal = gb.actor_p_curgoal = ga.actor_p_trajgoal = gb.actor_p_trajgoal = ga.actor_p_randomgoal = gb.actor_p_randomgoal = 0;
-            same = same && std::memcmp(&ga, &gb, sizeof ga) == 0;
-        }
-        if (kind == AgentKind::SAC) {   // (target_entropy may be NaN = automatic: zeroed before the compare, like the multiplier)
-            fql_sac_config sa = h->scfg, sb = members[0]->scfg;
-            sa.target_entropy = sb.target_entropy = sa.target_entropy_multiplier = sb.target_entropy_multiplier = 0.f;
-            same = same && std::memcmp(&sa, &sb, sizeof sa) == 0;
-        }
-        if (!same)
-            invalid("%s: member %d's config differs from member 0's in more than seed and %s", fn, i,
-                    kind == AgentKind::SAC ? "target_entropy / target_entropy_multiplier" :
-                    kind == AgentKind::CFGRL ? "cfg / actor_p_curgoal / actor_p_trajgoal / actor_p_randomgoal" :
-                    kind == AgentKind::REBRAC ? "alpha_actor / alpha_critic" : kind == AgentKind::IQLD ? "awr_temperature / softmax_beta" :
-                    kind == AgentKind::IFQL ? "expectile" : kind == AgentKind::IQL ? "expectile / alpha" : "alpha");
+        if (!kind.same_structure(*h, *members[0])) invalid("%s: member %d's config differs from member 0's in more than seed and %s", fn, i, kind.free_fields);
         if (h->B != members[0]->B) invalid("%s: member %d has batch size %d, member 0 has %d", fn, i, h->B, members[0]->B);
-        for (Program fql_engine::* pp : group_programs(kind)) {
-            const Program& p = h->*pp, &p0 = members[0]->*pp;
+        for (int pi = 0; pi < kind.programs; ++pi) {
+            const Program& p = h->*k_group_programs[pi], &p0 = members[0]->*k_group_programs[pi];
             require_graph(p);
             if (p.launches.size() != p0.launches.size()) invalid("%s: member %d's update has %zu launches, member 0's %zu", fn, i, p.launches.size(), p0.launches.size());
             for (size_t li = 0; li < p.launches.size(); ++li) {
@@ -7055,25 +7155,30 @@ void group_check(const char* fn, AgentKind kind, const fql_handle* members, int 
     }
 }
 
-// fql_group_create / fql_rebrac_group_create: a group of `kind` members, `want` what the refusal of another kind says the call takes
-int group_create(const char* fn, AgentKind kind, const char* want, const fql_handle* members, int k, fql_group* out) {
+// a group of `which` members: the kind's create call
+int group_create(AgentKind which, const fql_handle* members, int k, fql_group* out) {
+    const GroupKind& kind = k_group_kinds[(int)which];
+    const char* fn = kind.create;
     if (!out) { g_create_error = std::string(fn) + ": out must not be NULL"; return FQL_E_INVALID; }
     *out = nullptr;
     for (int i = 0; members && i < k; ++i)
-        if (members[i] && members[i]->kind != kind) {
-            g_create_error = std::string(fn) + ": member " + std::to_string(i) + " is " + members[i]->desc().label + " (" + want +
-                             (members[i]->kind == AgentKind::CFGRL ? "; CFGRL agents are grouped by fql_cfgrl_group_create" : "") + ")";
+        if (members[i] && members[i]->kind != which) {
+            const char* grouped_by = k_group_kinds[(int)members[i]->kind].grouped_by;
+            g_create_error = std::string(fn) + ": member " + std::to_string(i) + " is " + members[i]->desc().label + " (" + kind.takes + (grouped_by ? grouped_by : "") + ")";
             return FQL_E_STATE;
         }
-    auto* g = new fql_group_s();
-    try {
+    struct Release { void operator()(fql_group_s* g) const { g->release(); delete g; } };
+    GROUP_TRY({
+        std::unique_ptr<fql_group_s, Release> g(new fql_group_s());
         group_check(fn, kind, members, k);
         g->m.assign(members, members + k);
-        g->kind = kind;
+        g->kind = &kind;
         g->K = k;
         g->B = members[0]->B;
         for (fql_handle h : g->m) { h->aql_drain(); HIP_CHECK(hipStreamSynchronize(h->stream)); }
-        auto fuse_program = [&](GProgram& gp, Program fql_engine::* pp) {
+        for (int pi = 0; pi < kind.programs; ++pi) {
+            GProgram& gp = g->progs[pi];
+            Program fql_engine::* pp = k_group_programs[pi];
             const size_t n = (g->m[0]->*pp).launches.size();
             for (size_t li = 0; li < n; ++li)
                 for (int i = 1; i < k; ++i) {
@@ -7087,41 +7192,38 @@ int group_create(const char* fn, AgentKind kind, const char* want, const fql_han
                 gp.launches.push_back(g->zip((int)li, [pp](fql_engine& e) -> Program& { return e.*pp; }));
                 gp.lane_used[gp.launches.back().lane] = true;
             }
-        };
-        const std::vector<Program fql_engine::*> progs = group_programs(kind);
-        for (size_t p = 0; p < progs.size(); ++p) fuse_program(g->progs[p], progs[p]);
+        }
         for (int l = 0; l < FQL_LANES; ++l) HIP_CHECK(hipStreamCreateWithFlags(&g->lanes[l], hipStreamNonBlocking));
         for (hipEvent_t* e : {&g->ev_in, &g->ev_done}) HIP_CHECK(hipEventCreateWithFlags(e, hipEventDisableTiming));
         HIP_CHECK(hipMalloc((void**)&g->d_idx, (size_t)k * g->B * sizeof(int64_t)));
-        if (kind == AgentKind::CFGRL) g->d_mask = (unsigned char*)g->galloc((size_t)k * g->B);
-        for (size_t p = 0; p < progs.size(); ++p) g->capture(g->progs[p]);
-    } catch (const Invalid& e) {
-        g_create_error = e.msg; g->release(); delete g; return FQL_E_INVALID;
-    } catch (const HipError& e) {
-        g_create_error = e.msg; g->release(); delete g; return FQL_E_HIP;
-    }
-    for (fql_handle h : g->m) { h->group = g; h->grp_done = g->ev_done; h->grp_pending = false; h->grp_touched = true; }
-    *out = g;
-    return FQL_OK;
+        if (kind.goals) g->d_mask = (unsigned char*)g->galloc((size_t)k * g->B);
+        for (int pi = 0; pi < kind.programs; ++pi) g->capture(g->progs[pi]);
+        for (fql_handle h : g->m) { h->group = g.get(); h->grp_done = g->ev_done; h->grp_pending = false; h->grp_touched = true; }
+        *out = g.release();
+    });
 }
 
-// One fused update of every member: `gp` is the group's program for the step's kind.  fn: the entry point, for its messages.
-// infos: [k][n_info] - 13 floats of DevState::info, or an IQL-diffusion member's 21 or an IQL member's 16 or 19 of its own buffer
-// (fql_engine::info_src).  A CFGRL group: every member's goal source (CfgrlSrc: its goal table, its mixture thresholds and its rows of
-// `do_cfg`, [k][B] bytes, host or device, or NULL = each member's Philox mask) is set beside its dataset source, as
-// fql_cfgrl_update_from_dataset sets them.  balanced (a SAC group's fql_sac_group_update_balanced): every member's source is its
-// two-source one (fql_engine::source_balanced: B / 2 rows of its dataset, B / 2 of its own replay ring); idx and idx_rb are [k][B / 2]
-// each, both or neither, host or device, staged into each member's index buffer as its own call stages them.  Every member is checked
-// before any member's source is written: a refusal leaves every member where it was.
-int group_update(fql_group g, const char* fn, GProgram& gp, const int64_t* idx, int batch_size, float* info13xk, void* stream, int n_info = FQL_NUM_INFO,
-                 const unsigned char* do_cfg = nullptr, bool balanced = false, const int64_t* idx_rb = nullptr) {
-    try {
-        const bool cfgrl = g->kind == AgentKind::CFGRL;
+// What one fused update runs beside its rows: the group's program for the step's kind; a goal kind's `do_cfg`, [k][B] bytes, host or
+// device, or NULL = each member's Philox mask; balanced (fql_sac_group_update_balanced): every member's source is its two-source one
+// (fql_engine::source_balanced: B / 2 rows of its dataset, B / 2 of its own replay ring), idx and idx_rb [k][B / 2] each, both or
+// neither, host or device, staged into each member's index buffer as its own call stages them.
+struct GroupStep {
+    int prog = fql_group_s::FULL;
+    const unsigned char* do_cfg = nullptr;
+    bool balanced = false;
+    const int64_t* idx_rb = nullptr;
+};
+// One fused update of every member.  fn: the entry point, for its messages.  infos: [k][the members' num_info(), or GroupKind::infos] out of each
+// member's info buffer (fql_engine::info_src).  A goal kind: every member's goal source (CfgrlSrc: its goal table, its mixture thresholds and its
+// rows of do_cfg) is set beside its dataset source, as fql_cfgrl_update_from_dataset sets them.  Every member is checked before any
+// member's source is written: a refusal leaves every member where it was.
+int group_update(fql_group g, const char* fn, const int64_t* idx, int batch_size, float* infos, void* stream, const GroupStep& st = GroupStep()) {
+    GROUP_TRY({
         if (batch_size != g->B) invalid("%s: batch_size %d does not match the members' %d", fn, batch_size, g->B);
         if (g->member_began()) { g_create_error = std::string(fn) + ": a member is between fql_update_begin and fql_update_end"; return FQL_E_STATE; }
-        if (balanced) {
+        if (st.balanced) {
             if (g->B % 2) invalid("%s: balanced sampling draws batch_size // 2 rows from each source: batch_size %d must be even", fn, g->B);
-            if (!idx != !idx_rb) invalid("%s: balanced sampling: give both index arrays or neither", fn);
+            if (!idx != !st.idx_rb) invalid("%s: balanced sampling: give both index arrays or neither", fn);
             for (int i = 0; i < g->K; ++i) {
                 const fql_engine& e = *g->m[i];
                 if (e.ds_size <= 0 || !e.ds_obs) invalid("%s: member %d has no training dataset uploaded", fn, i);
@@ -7129,93 +7231,96 @@ int group_update(fql_group g, const char* fn, GProgram& gp, const int64_t* idx, 
                 if (e.rb_size <= 0) invalid("%s: member %d's replay ring is empty (the reference would draw randint(0), a ValueError)", fn, i);
             }
         }
-        for (int i = 0; cfgrl && i < g->K; ++i)
+        for (int i = 0; g->kind->goals && i < g->K; ++i)
             if (!g->m[i]->ds_final) invalid("%s: member %d has no goal table (fql_cfgrl_dataset_goals after fql_dataset_upload)", fn, i);
         const hipStream_t s = g->enter(stream);
-        const unsigned char* mask = do_cfg;
-        if (do_cfg && !fql_engine::is_device_ptr(do_cfg)) {   // (borrowed for the call only: the wait is the indices' below, or its own)
-            HIP_CHECK(hipMemcpyAsync(g->d_mask, do_cfg, (size_t)g->K * g->B, hipMemcpyHostToDevice, s));
+        const unsigned char* mask = st.do_cfg;
+        if (mask && !fql_engine::is_device_ptr(mask)) {   // (borrowed for the call only: the wait is the indices' below, or its own)
+            HIP_CHECK(hipMemcpyAsync(g->d_mask, mask, (size_t)g->K * g->B, hipMemcpyHostToDevice, s));
             if (!idx || fql_engine::is_device_ptr(idx)) HIP_CHECK(hipStreamSynchronize(s));
             mask = g->d_mask;
         }
         const int64_t* rows = idx;
-        if (idx && !balanced && !fql_engine::is_device_ptr(idx)) {
+        if (idx && !st.balanced && !fql_engine::is_device_ptr(idx)) {
             HIP_CHECK(hipMemcpyAsync(g->d_idx, idx, (size_t)g->K * g->B * sizeof(int64_t), hipMemcpyHostToDevice, s));
             HIP_CHECK(hipStreamSynchronize(s));   // (host indices are borrowed for the call only)
             rows = g->d_idx;
         }
         for (int i = 0; i < g->K; ++i) {
             const int64_t* ri = rows ? rows + (size_t)i * g->B : nullptr;
-            if (cfgrl) g->m[i]->cfgrl_source_from_dataset(ri, g->B, 0, 0, nullptr, mask ? mask + (size_t)i * g->B : nullptr, s);
-            else if (balanced) g->m[i]->source_balanced(idx ? idx + (size_t)i * (g->B / 2) : nullptr, idx_rb ? idx_rb + (size_t)i * (g->B / 2) : nullptr, nullptr, g->B, nullptr, s);
+            if (g->kind->goals) g->m[i]->cfgrl_source_from_dataset(ri, g->B, 0, 0, nullptr, mask ? mask + (size_t)i * g->B : nullptr, s);
+            else if (st.balanced) g->m[i]->source_balanced(idx ? idx + (size_t)i * (g->B / 2) : nullptr, st.idx_rb ? st.idx_rb + (size_t)i * (g->B / 2) : nullptr, nullptr, g->B, nullptr, s);
             else g->m[i]->source_from_dataset(ri, g->B, 0, 0, nullptr, s);
         }
-        HIP_CHECK(hipGraphLaunch(gp.exec, s));
-        if (info13xk) {
-            for (int i = 0; i < g->K; ++i)
-                HIP_CHECK(hipMemcpyAsync(info13xk + (size_t)i * n_info, g->m[i]->info_src(), (size_t)n_info * sizeof(float), hipMemcpyDefault, s));
+        HIP_CHECK(hipGraphLaunch(g->progs[st.prog].exec, s));
+        const size_t n_info = (size_t)(g->kind->infos ? g->kind->infos : g->m[0]->num_info());
+        for (int i = 0; infos && i < g->K; ++i)
+            HIP_CHECK(hipMemcpyAsync(infos + i * n_info, g->m[i]->info_src(), n_info * sizeof(float), hipMemcpyDefault, s));
+        g->leave(s, infos && !fql_engine::is_device_ptr(infos));
+    });
+}
+
+// Launches counted from the built programs, each where its out-pointer is given: of the group's fused update programs, in their order,
+// and of one fused sampling call and one fused flow call (a sweep kind: its one sampler answers either) on a single chunk
+int group_stats(fql_group g, std::initializer_list<int64_t*> programs, int64_t* sample, int64_t* flow) {
+    GROUP_TRY({
+        int pi = 0;
+        for (int64_t* out : programs) {
+            if (out) *out = (int64_t)g->progs[pi].launches.size();
+            ++pi;
         }
-        g->leave(s, info13xk && !fql_engine::is_device_ptr(info13xk));
-    } catch (const Invalid& e) {
-        g_create_error = e.msg; return FQL_E_INVALID;
-    } catch (const HipError& e) {
-        g_create_error = e.msg; return FQL_E_HIP;
-    }
-    return FQL_OK;
+        if (sample) *sample = g->sample_launches(false);
+        if (flow) *flow = g->sample_launches(true);
+    });
 }
-// What a group call does, and the call of each kind of group that does it
-enum GroupCall { GC_UPDATE, GC_SAMPLE, GC_STATS, GC_FLOW };
-const char* group_call_of(AgentKind kind, GroupCall c) {
-    static const char* const fql[] = {"fql_group_update_from_dataset", "fql_group_sample_actions", "fql_group_sample_stats", "fql_group_flow_actions"};
-    static const char* const rebrac[] = {"the step kind is an argument: fql_rebrac_group_update_from_dataset", "fql_rebrac_group_sample_actions", "fql_rebrac_group_stats",
-                                         "the actor is deterministic: fql_rebrac_group_sample_actions"};
-    static const char* const iqld[] = {"the step kind is two arguments: fql_iqld_group_update_from_dataset", "it takes guidance weights: fql_iqld_group_sample_actions", "fql_iqld_group_stats",
-                                       "it takes guidance weights: fql_iqld_group_sample_actions"};
-    static const char* const ifql[] = {"fql_ifql_group_update_from_dataset", "best of num_samples: fql_ifql_group_sample_actions", "fql_ifql_group_stats", "fql_ifql_group_flow_actions"};
-    static const char* const iql[] = {"fql_iql_group_update_from_dataset", "it takes a temperature: fql_iql_group_sample_actions", "fql_iql_group_stats",
-                                      "the actor is a Gaussian, there is no flow: fql_iql_group_sample_actions"};
-    static const char* const cfgrl[] = {"it sets each member's goal source: fql_cfgrl_group_update_from_dataset", "it takes goals and guidance weights: fql_cfgrl_group_sample_actions",
-                                        "fql_cfgrl_group_stats", "it takes goals and guidance weights: fql_cfgrl_group_sample_actions"};
-    static const char* const sac[] = {"fql_sac_group_update_from_dataset (or fql_sac_group_update_balanced)", "it takes a temperature: fql_sac_group_sample_actions", "fql_sac_group_stats",
-                                      "the actor is a Gaussian, there is no flow: fql_sac_group_sample_actions"};
-    if (kind == AgentKind::CFGRL) return cfgrl[c];
-    if (kind == AgentKind::SAC) return sac[c];
-    return (kind == AgentKind::IQL ? iql : kind == AgentKind::IFQL ? ifql : kind == AgentKind::IQLD ? iqld : kind == AgentKind::REBRAC ? rebrac : fql)[c];
+
+// The members' sample_actions (flow: compute_flow_actions) in one fused call, between the update's ordering rules: the chunk loop of
+// the group's kind (fql_group_s::sample; best of N: fql_group_s::sample_bon, whose flow call is the plain loop's)
+int group_sample(fql_group g, const char* fn, AgentKind kind, bool flow, const float* obs, const float* noise, const uint64_t* seeds, float temperature, int n,
+                 float* out, void* stream) {
+    GROUP_ENTER(g, kind, fn, flow ? GC_FLOW : GC_SAMPLE);
+    GROUP_TRY({
+        if (n <= 0) invalid("%s: n must be positive (got %d)", fn, n);
+        if (!obs || !out) invalid("%s: observations/out must not be NULL", fn);
+        if (flow && !noise) invalid("%s: noises must not be NULL", fn);
+        if (!noise && !seeds) invalid("%s: seeds must not be NULL when noises is NULL (one seed per member)", fn);
+        if (!(temperature >= 0.0f)) invalid("%s: temperature must be >= 0", fn);
+        if (g->member_began()) { g_create_error = std::string(fn) + ": a member is between fql_update_begin and fql_update_end"; return FQL_E_STATE; }
+        const hipStream_t s = g->enter(stream);
+        if (g->kind->sampler == GS_BEST_OF_N && !flow) g->sample_bon(obs, noise, seeds, n, out, s);
+        else g->sample(flow, obs, noise, seeds, temperature, n, out, s);
+        // a device result on the group's own stream: the caller has no handle to order its reads against, so finish here (as a member does)
+        g->leave(s, !stream && fql_engine::is_device_ptr(out));
+    });
 }
-// A group call on a group of another kind: FQL_E_STATE, naming the call that serves it.  `kind`: the groups `fn` serves; `instead`: what
-// an FQL call says on a ReBRAC group and the reverse; with an IQL-diffusion, IFQL, IQL, CFGRL or SAC group on either side, the group's own call for `c`.
-bool group_wrong_kind(fql_group g, AgentKind kind, const char* fn, const char* instead, GroupCall c) {
-    if (g->kind == kind) return false;
-    const auto later = [](AgentKind k) { return k == AgentKind::IQLD || k == AgentKind::IFQL || k == AgentKind::IQL || k == AgentKind::CFGRL || k == AgentKind::SAC; };
-    if (later(g->kind) || later(kind) || !instead) instead = group_call_of(g->kind, c);
-    g_create_error = std::string(fn) + " is not available on a group of " + g->m[0]->desc().name + " agents (" + instead + ")";
-    return true;
+// The members' per-row guidance sweep (fql_iqld_sample_actions_cfgs, fql_cfgrl_sample_actions_cfgs) in one fused call:
+// fql_group_s::sample_cfg between the update's ordering rules.  goals: a goal kind's [k][n][G], which its conditional pass reads
+int group_sample_cfg(fql_group g, const char* fn, AgentKind kind, const float* observations, const float* goals, int n, const float* noises,
+                     const uint64_t* seeds, const float* cfgs, float* out, void* stream) {
+    GROUP_ENTER(g, kind, fn, GC_SAMPLE);
+    GROUP_TRY({
+        if (n <= 0) invalid("%s: n must be positive (got %d)", fn, n);
+        if (!observations || !out) invalid("%s: observations/out must not be NULL", fn);
+        if (g->kind->goals && !goals) invalid("%s: goals must not be NULL (the conditional pass reads them: agents/cfgrl.py:93)", fn);
+        if (!cfgs) invalid("%s: cfgs must not be NULL (one guidance weight per member and row)", fn);
+        if (!noises && !seeds) invalid("%s: seeds must not be NULL when noises is NULL (one seed per member)", fn);
+        if (g->member_began()) { g_create_error = std::string(fn) + ": a member is between fql_update_begin and fql_update_end"; return FQL_E_STATE; }
+        const hipStream_t s = g->enter(stream);
+        g->sample_cfg(observations, goals, noises, seeds, cfgs, n, out, s);
+        g->leave(s, !stream && fql_engine::is_device_ptr(out));
+    });
 }
 }  // namespace
 
 extern "C" {
 
-int fql_group_create(const fql_handle* members, int k, fql_group* out) {
-    return group_create("fql_group_create", AgentKind::FQL, "groups take FQL agents only", members, k, out);
-}
-int fql_rebrac_group_create(const fql_handle* members, int k, fql_group* out) {
-    return group_create("fql_rebrac_group_create", AgentKind::REBRAC, "ReBRAC groups take ReBRAC agents only", members, k, out);
-}
-int fql_iqld_group_create(const fql_handle* members, int k, fql_group* out) {
-    return group_create("fql_iqld_group_create", AgentKind::IQLD, "IQL-diffusion groups take IQL-diffusion agents only", members, k, out);
-}
-int fql_ifql_group_create(const fql_handle* members, int k, fql_group* out) {
-    return group_create("fql_ifql_group_create", AgentKind::IFQL, "IFQL groups take IFQL agents only", members, k, out);
-}
-int fql_iql_group_create(const fql_handle* members, int k, fql_group* out) {
-    return group_create("fql_iql_group_create", AgentKind::IQL, "IQL groups take IQL agents only", members, k, out);
-}
-int fql_cfgrl_group_create(const fql_handle* members, int k, fql_group* out) {
-    return group_create("fql_cfgrl_group_create", AgentKind::CFGRL, "CFGRL groups take CFGRL agents only", members, k, out);
-}
-int fql_sac_group_create(const fql_handle* members, int k, fql_group* out) {
-    return group_create("fql_sac_group_create", AgentKind::SAC, "SAC groups take SAC agents only", members, k, out);
-}
+int fql_group_create(const fql_handle* members, int k, fql_group* out) { return group_create(AgentKind::FQL, members, k, out); }
+int fql_rebrac_group_create(const fql_handle* members, int k, fql_group* out) { return group_create(AgentKind::REBRAC, members, k, out); }
+int fql_iqld_group_create(const fql_handle* members, int k, fql_group* out) { return group_create(AgentKind::IQLD, members, k, out); }
+int fql_ifql_group_create(const fql_handle* members, int k, fql_group* out) { return group_create(AgentKind::IFQL, members, k, out); }
+int fql_iql_group_create(const fql_handle* members, int k, fql_group* out) { return group_create(AgentKind::IQL, members, k, out); }
+int fql_cfgrl_group_create(const fql_handle* members, int k, fql_group* out) { return group_create(AgentKind::CFGRL, members, k, out); }
+int fql_sac_group_create(const fql_handle* members, int k, fql_group* out) { return group_create(AgentKind::SAC, members, k, out); }
 
 // Diagnostic only (not in include/fql_amd.h, beside fql_debug_plan): where each launch of an update program takes its tasks from, as int32 words
 //   [words (this one included), capacities of the argument form of a side-lane launch: GEMM-tile, weight-gradient, LayerNorm-backward, loss / metric
@@ -7280,145 +7385,83 @@ int fql_group_destroy(fql_group g) {
     return FQL_OK;
 }
 
+// The kind's update_from_dataset of every member in one fused update: the zip of their program of the step's kind
 int fql_group_update_from_dataset(fql_group g, const int64_t* idx, int batch_size, float* info13xk, void* stream) {
     const char* fn = "fql_group_update_from_dataset";
-    if (!g) { g_create_error = std::string(fn) + ": NULL group"; return FQL_E_INVALID; }
-    if (group_wrong_kind(g, AgentKind::FQL, fn, "the step kind is an argument: fql_rebrac_group_update_from_dataset", GC_UPDATE)) return FQL_E_STATE;
-    return group_update(g, fn, g->progs[fql_group_s::FULL], idx, batch_size, info13xk, stream);
+    GROUP_ENTER(g, AgentKind::FQL, fn, GC_UPDATE);
+    return group_update(g, fn, idx, batch_size, info13xk, stream);
 }
-// fql_rebrac_update_from_dataset of every member in one fused update: the zip of their prog_full, or of their prog_critic
 int fql_rebrac_group_update_from_dataset(fql_group g, const int64_t* idx, int batch_size, int full_update, float* info13xk, void* stream) {
     const char* fn = "fql_rebrac_group_update_from_dataset";
-    if (!g) { g_create_error = std::string(fn) + ": NULL group"; return FQL_E_INVALID; }
-    if (group_wrong_kind(g, AgentKind::REBRAC, fn, "fql_group_update_from_dataset", GC_UPDATE)) return FQL_E_STATE;
-    return group_update(g, fn, g->progs[full_update ? fql_group_s::FULL : fql_group_s::CRITIC], idx, batch_size, info13xk, stream);
+    GROUP_ENTER(g, AgentKind::REBRAC, fn, GC_UPDATE);
+    GroupStep st;
+    st.prog = full_update ? fql_group_s::FULL : fql_group_s::CRITIC;
+    return group_update(g, fn, idx, batch_size, info13xk, stream, st);
 }
-
-// fql_iqld_update_from_dataset of every member in one fused update: the zip of their program of that step kind
 int fql_iqld_group_update_from_dataset(fql_group g, const int64_t* idx, int batch_size, int update_critic, int update_actor, float* info21xk, void* stream) {
     const char* fn = "fql_iqld_group_update_from_dataset";
-    if (!g) { g_create_error = std::string(fn) + ": NULL group"; return FQL_E_INVALID; }
-    if (group_wrong_kind(g, AgentKind::IQLD, fn, nullptr, GC_UPDATE)) return FQL_E_STATE;
-    const int kind = update_critic ? (update_actor ? fql_group_s::FULL : fql_group_s::CRITIC) : (update_actor ? fql_group_s::ACTOR : fql_group_s::NONE);
-    return group_update(g, fn, g->progs[kind], idx, batch_size, info21xk, stream, FQL_IQLD_NUM_INFO);
+    GROUP_ENTER(g, AgentKind::IQLD, fn, GC_UPDATE);
+    GroupStep st;
+    st.prog = update_critic ? (update_actor ? fql_group_s::FULL : fql_group_s::CRITIC) : (update_actor ? fql_group_s::ACTOR : fql_group_s::NONE);
+    return group_update(g, fn, idx, batch_size, info21xk, stream, st);
 }
-
-// fql_update_from_dataset of every IFQL member in one fused update: the zip of their prog_full; 12 infos per member
 int fql_ifql_group_update_from_dataset(fql_group g, const int64_t* idx, int batch_size, float* info12xk, void* stream) {
     const char* fn = "fql_ifql_group_update_from_dataset";
-    if (!g) { g_create_error = std::string(fn) + ": NULL group"; return FQL_E_INVALID; }
-    if (group_wrong_kind(g, AgentKind::IFQL, fn, nullptr, GC_UPDATE)) return FQL_E_STATE;
-    return group_update(g, fn, g->progs[fql_group_s::FULL], idx, batch_size, info12xk, stream, FQL_IFQL_NUM_INFO);
+    GROUP_ENTER(g, AgentKind::IFQL, fn, GC_UPDATE);
+    return group_update(g, fn, idx, batch_size, info12xk, stream);
 }
-
-// fql_iql_update_from_dataset of every IQL member in one fused update: the zip of their prog_full; 16 (awr) or 19 (ddpgbc) infos per
-// member, out of each member's own info buffer (fql_engine::info_src)
+// (16 infos per member under awr, 19 under ddpgbc)
 int fql_iql_group_update_from_dataset(fql_group g, const int64_t* idx, int batch_size, float* infoNxk, void* stream) {
     const char* fn = "fql_iql_group_update_from_dataset";
-    if (!g) { g_create_error = std::string(fn) + ": NULL group"; return FQL_E_INVALID; }
-    if (group_wrong_kind(g, AgentKind::IQL, fn, nullptr, GC_UPDATE)) return FQL_E_STATE;
-    return group_update(g, fn, g->progs[fql_group_s::FULL], idx, batch_size, infoNxk, stream, g->m[0]->num_info());
+    GROUP_ENTER(g, AgentKind::IQL, fn, GC_UPDATE);
+    return group_update(g, fn, idx, batch_size, infoNxk, stream);
 }
-
-// fql_cfgrl_update_from_dataset of every CFGRL member in one fused update: the zip of their prog_full behind each member's dataset
-// source and goal source; 4 infos per member
+// (behind each member's dataset source and goal source)
 int fql_cfgrl_group_update_from_dataset(fql_group g, const int64_t* idx, int batch_size, const uint8_t* do_cfg, float* info4xk, void* stream) {
     const char* fn = "fql_cfgrl_group_update_from_dataset";
-    if (!g) { g_create_error = std::string(fn) + ": NULL group"; return FQL_E_INVALID; }
-    if (group_wrong_kind(g, AgentKind::CFGRL, fn, nullptr, GC_UPDATE)) return FQL_E_STATE;
-    return group_update(g, fn, g->progs[fql_group_s::FULL], idx, batch_size, info4xk, stream, FQL_CFGRL_NUM_INFO, do_cfg);
+    GROUP_ENTER(g, AgentKind::CFGRL, fn, GC_UPDATE);
+    GroupStep st;
+    st.do_cfg = do_cfg;
+    return group_update(g, fn, idx, batch_size, info4xk, stream, st);
 }
-
-// fql_sac_update_from_dataset of every SAC member in one fused update: the zip of their prog_full; 14 infos per member
 int fql_sac_group_update_from_dataset(fql_group g, const int64_t* idx, int batch_size, float* info14xk, void* stream) {
     const char* fn = "fql_sac_group_update_from_dataset";
-    if (!g) { g_create_error = std::string(fn) + ": NULL group"; return FQL_E_INVALID; }
-    if (group_wrong_kind(g, AgentKind::SAC, fn, nullptr, GC_UPDATE)) return FQL_E_STATE;
-    return group_update(g, fn, g->progs[fql_group_s::FULL], idx, batch_size, info14xk, stream, FQL_SAC_NUM_INFO);
+    GROUP_ENTER(g, AgentKind::SAC, fn, GC_UPDATE);
+    return group_update(g, fn, idx, batch_size, info14xk, stream);
 }
 // fql_sac_update_balanced of every SAC member in one fused update: the same program behind each member's two-source descriptor
 int fql_sac_group_update_balanced(fql_group g, const int64_t* idx_dataset, const int64_t* idx_replay, int batch_size, float* info14xk, void* stream) {
     const char* fn = "fql_sac_group_update_balanced";
-    if (!g) { g_create_error = std::string(fn) + ": NULL group"; return FQL_E_INVALID; }
-    if (group_wrong_kind(g, AgentKind::SAC, fn, nullptr, GC_UPDATE)) return FQL_E_STATE;
-    return group_update(g, fn, g->progs[fql_group_s::FULL], idx_dataset, batch_size, info14xk, stream, FQL_SAC_NUM_INFO, nullptr, true, idx_replay);
+    GROUP_ENTER(g, AgentKind::SAC, fn, GC_UPDATE);
+    GroupStep st;
+    st.balanced = true;
+    st.idx_rb = idx_replay;
+    return group_update(g, fn, idx_dataset, batch_size, info14xk, stream, st);
 }
 
-// The members' sample_actions (flow: compute_flow_actions) in one fused call: fql_group_s::sample between the update's ordering rules
-// (an IFQL group's sample_actions is best of num_samples: fql_group_s::sample_bon)
-static int group_sample(fql_group g, const char* fn, AgentKind kind, const char* instead, bool flow, const float* obs, const float* noise,
-                        const uint64_t* seeds, float temperature, int n, float* out, void* stream) {
-    if (!g) { g_create_error = std::string(fn) + ": NULL group"; return FQL_E_INVALID; }
-    if (group_wrong_kind(g, kind, fn, instead, flow ? GC_FLOW : GC_SAMPLE)) return FQL_E_STATE;
-    try {
-        if (n <= 0) invalid("%s: n must be positive (got %d)", fn, n);
-        if (!obs || !out) invalid("%s: observations/out must not be NULL", fn);
-        if (flow && !noise) invalid("%s: noises must not be NULL", fn);
-        if (!noise && !seeds) invalid("%s: seeds must not be NULL when noises is NULL (one seed per member)", fn);
-        if (!(temperature >= 0.0f)) invalid("%s: temperature must be >= 0", fn);
-        if (g->member_began()) { g_create_error = std::string(fn) + ": a member is between fql_update_begin and fql_update_end"; return FQL_E_STATE; }
-        const hipStream_t s = g->enter(stream);
-        if (kind == AgentKind::IFQL && !flow) g->sample_bon(obs, noise, seeds, n, out, s);
-        else g->sample(flow, obs, noise, seeds, temperature, n, out, s);
-        // a device result on the group's own stream: the caller has no handle to order its reads against, so finish here (as a member does)
-        g->leave(s, !stream && fql_engine::is_device_ptr(out));
-    } catch (const Invalid& e) {
-        g_create_error = e.msg; return FQL_E_INVALID;
-    } catch (const HipError& e) {
-        g_create_error = e.msg; return FQL_E_HIP;
-    } catch (const std::exception& e) {
-        g_create_error = e.what(); return FQL_E_HIP;
-    }
-    return FQL_OK;
-}
 int fql_group_sample_actions(fql_group g, const float* observations, int n, const float* noises, const uint64_t* seeds, float* out, void* stream) {
-    return group_sample(g, "fql_group_sample_actions", AgentKind::FQL, "fql_rebrac_group_sample_actions", false, observations, noises, seeds, 1.0f, n, out, stream);
+    return group_sample(g, "fql_group_sample_actions", AgentKind::FQL, false, observations, noises, seeds, 1.0f, n, out, stream);
 }
 int fql_group_flow_actions(fql_group g, const float* observations, const float* noises, int n, float* out, void* stream) {
-    return group_sample(g, "fql_group_flow_actions", AgentKind::FQL, "the actor is deterministic: fql_rebrac_group_sample_actions", true, observations, noises, nullptr, 1.0f, n, out, stream);
+    return group_sample(g, "fql_group_flow_actions", AgentKind::FQL, true, observations, noises, nullptr, 1.0f, n, out, stream);
 }
 int fql_rebrac_group_sample_actions(fql_group g, const float* observations, int n, const float* noises, const uint64_t* seeds, float temperature,
                                     float* out, void* stream) {
-    return group_sample(g, "fql_rebrac_group_sample_actions", AgentKind::REBRAC, "fql_group_sample_actions", false, observations, noises, seeds, temperature, n, out, stream);
+    return group_sample(g, "fql_rebrac_group_sample_actions", AgentKind::REBRAC, false, observations, noises, seeds, temperature, n, out, stream);
 }
 int fql_ifql_group_sample_actions(fql_group g, const float* observations, int n, const float* noises, const uint64_t* seeds, float* out, void* stream) {
-    return group_sample(g, "fql_ifql_group_sample_actions", AgentKind::IFQL, nullptr, false, observations, noises, seeds, 1.0f, n, out, stream);
+    return group_sample(g, "fql_ifql_group_sample_actions", AgentKind::IFQL, false, observations, noises, seeds, 1.0f, n, out, stream);
 }
 int fql_ifql_group_flow_actions(fql_group g, const float* observations, const float* noises, int n, float* out, void* stream) {
-    return group_sample(g, "fql_ifql_group_flow_actions", AgentKind::IFQL, nullptr, true, observations, noises, nullptr, 1.0f, n, out, stream);
+    return group_sample(g, "fql_ifql_group_flow_actions", AgentKind::IFQL, true, observations, noises, nullptr, 1.0f, n, out, stream);
 }
 int fql_iql_group_sample_actions(fql_group g, const float* observations, int n, const float* noises, const uint64_t* seeds, float temperature,
                                  float* out, void* stream) {
-    return group_sample(g, "fql_iql_group_sample_actions", AgentKind::IQL, nullptr, false, observations, noises, seeds, temperature, n, out, stream);
+    return group_sample(g, "fql_iql_group_sample_actions", AgentKind::IQL, false, observations, noises, seeds, temperature, n, out, stream);
 }
 int fql_sac_group_sample_actions(fql_group g, const float* observations, int n, const float* noises, const uint64_t* seeds, float temperature,
                                  float* out, void* stream) {
-    return group_sample(g, "fql_sac_group_sample_actions", AgentKind::SAC, nullptr, false, observations, noises, seeds, temperature, n, out, stream);
-}
-// fql_iqld_sample_actions_cfgs / fql_cfgrl_sample_actions_cfgs of every member in one fused call: fql_group_s::sample_cfg between the
-// update's ordering rules.  goals: a CFGRL group's [k][n][G], which its conditional pass reads
-static int group_sample_cfg(fql_group g, const char* fn, AgentKind kind, const float* observations, const float* goals, int n, const float* noises,
-                            const uint64_t* seeds, const float* cfgs, float* out, void* stream) {
-    if (!g) { g_create_error = std::string(fn) + ": NULL group"; return FQL_E_INVALID; }
-    if (group_wrong_kind(g, kind, fn, nullptr, GC_SAMPLE)) return FQL_E_STATE;
-    try {
-        if (n <= 0) invalid("%s: n must be positive (got %d)", fn, n);
-        if (!observations || !out) invalid("%s: observations/out must not be NULL", fn);
-        if (kind == AgentKind::CFGRL && !goals) invalid("%s: goals must not be NULL (the conditional pass reads them: agents/cfgrl.py:93)", fn);
-        if (!cfgs) invalid("%s: cfgs must not be NULL (one guidance weight per member and row)", fn);
-        if (!noises && !seeds) invalid("%s: seeds must not be NULL when noises is NULL (one seed per member)", fn);
-        if (g->member_began()) { g_create_error = std::string(fn) + ": a member is between fql_update_begin and fql_update_end"; return FQL_E_STATE; }
-        const hipStream_t s = g->enter(stream);
-        g->sample_cfg(observations, goals, noises, seeds, cfgs, n, out, s);
-        g->leave(s, !stream && fql_engine::is_device_ptr(out));
-    } catch (const Invalid& e) {
-        g_create_error = e.msg; return FQL_E_INVALID;
-    } catch (const HipError& e) {
-        g_create_error = e.msg; return FQL_E_HIP;
-    } catch (const std::exception& e) {
-        g_create_error = e.what(); return FQL_E_HIP;
-    }
-    return FQL_OK;
+    return group_sample(g, "fql_sac_group_sample_actions", AgentKind::SAC, false, observations, noises, seeds, temperature, n, out, stream);
 }
 int fql_iqld_group_sample_actions(fql_group g, const float* observations, int n, const float* noises, const uint64_t* seeds, const float* cfgs,
                                   float* out, void* stream) {
@@ -7428,111 +7471,39 @@ int fql_cfgrl_group_sample_actions(fql_group g, const float* observations, const
                                    const float* cfgs, float* out, void* stream) {
     return group_sample_cfg(g, "fql_cfgrl_group_sample_actions", AgentKind::CFGRL, observations, goals, n, noises, seeds, cfgs, out, stream);
 }
+
+// Launches of the group's fused update programs and of one fused sampling call on a single chunk, counted from the built programs
 int fql_group_sample_stats(fql_group g, int flow, int64_t* launches_per_call) {
-    if (!g) { g_create_error = "fql_group_sample_stats: NULL group"; return FQL_E_INVALID; }
-    if (group_wrong_kind(g, AgentKind::FQL, "fql_group_sample_stats", "fql_rebrac_group_stats", GC_STATS)) return FQL_E_STATE;
+    GROUP_ENTER(g, AgentKind::FQL, "fql_group_sample_stats", GC_STATS);
     if (!launches_per_call) { g_create_error = "fql_group_sample_stats: launches_per_call must not be NULL"; return FQL_E_INVALID; }
-    try {
-        *launches_per_call = g->sample_launches(flow != 0);
-    } catch (const Invalid& e) {
-        g_create_error = e.msg; return FQL_E_INVALID;
-    } catch (const HipError& e) {
-        g_create_error = e.msg; return FQL_E_HIP;
-    }
-    return FQL_OK;
+    return group_stats(g, {}, flow ? nullptr : launches_per_call, flow ? launches_per_call : nullptr);
 }
-// Launches of a ReBRAC group's two fused update programs and of one fused sampling call on a single chunk, counted from the built programs
 int fql_rebrac_group_stats(fql_group g, int64_t* launches_full, int64_t* launches_critic, int64_t* launches_sample) {
-    if (!g) { g_create_error = "fql_rebrac_group_stats: NULL group"; return FQL_E_INVALID; }
-    if (group_wrong_kind(g, AgentKind::REBRAC, "fql_rebrac_group_stats", "fql_group_sample_stats", GC_STATS)) return FQL_E_STATE;
-    try {
-        if (launches_full) *launches_full = (int64_t)g->progs[fql_group_s::FULL].launches.size();
-        if (launches_critic) *launches_critic = (int64_t)g->progs[fql_group_s::CRITIC].launches.size();
-        if (launches_sample) *launches_sample = g->sample_launches(false);
-    } catch (const Invalid& e) {
-        g_create_error = e.msg; return FQL_E_INVALID;
-    } catch (const HipError& e) {
-        g_create_error = e.msg; return FQL_E_HIP;
-    }
-    return FQL_OK;
+    GROUP_ENTER(g, AgentKind::REBRAC, "fql_rebrac_group_stats", GC_STATS);
+    return group_stats(g, {launches_full, launches_critic}, launches_sample, nullptr);
 }
-
-// Launches of an IQL-diffusion group's four fused update programs (full, critic-only, actor-only, neither) and of one fused sampling
-// call on a single chunk, counted from the built programs
+// (full, critic-only, actor-only, neither)
 int fql_iqld_group_stats(fql_group g, int64_t launches[4], int64_t* launches_sample) {
-    if (!g) { g_create_error = "fql_iqld_group_stats: NULL group"; return FQL_E_INVALID; }
-    if (group_wrong_kind(g, AgentKind::IQLD, "fql_iqld_group_stats", nullptr, GC_STATS)) return FQL_E_STATE;
-    try {
-        if (launches) for (int p = 0; p < fql_group_s::MAX_PROGS; ++p) launches[p] = (int64_t)g->progs[p].launches.size();
-        if (launches_sample) *launches_sample = g->sample_launches(true);
-    } catch (const Invalid& e) {
-        g_create_error = e.msg; return FQL_E_INVALID;
-    } catch (const HipError& e) {
-        g_create_error = e.msg; return FQL_E_HIP;
-    }
-    return FQL_OK;
+    GROUP_ENTER(g, AgentKind::IQLD, "fql_iqld_group_stats", GC_STATS);
+    if (!launches) return group_stats(g, {}, launches_sample, nullptr);
+    return group_stats(g, {launches, launches + 1, launches + 2, launches + 3}, launches_sample, nullptr);
 }
-
-// Launches of an IFQL group's fused update program and of one fused best-of-N and one fused flow call on a single chunk, counted from
-// the built programs
+// (one fused best-of-N and one fused flow call)
 int fql_ifql_group_stats(fql_group g, int64_t* launches_update, int64_t* launches_sample, int64_t* launches_flow) {
-    if (!g) { g_create_error = "fql_ifql_group_stats: NULL group"; return FQL_E_INVALID; }
-    if (group_wrong_kind(g, AgentKind::IFQL, "fql_ifql_group_stats", nullptr, GC_STATS)) return FQL_E_STATE;
-    try {
-        if (launches_update) *launches_update = (int64_t)g->progs[fql_group_s::FULL].launches.size();
-        if (launches_sample) *launches_sample = g->sample_launches(false);
-        if (launches_flow) *launches_flow = g->sample_launches(true);
-    } catch (const Invalid& e) {
-        g_create_error = e.msg; return FQL_E_INVALID;
-    } catch (const HipError& e) {
-        g_create_error = e.msg; return FQL_E_HIP;
-    }
-    return FQL_OK;
+    GROUP_ENTER(g, AgentKind::IFQL, "fql_ifql_group_stats", GC_STATS);
+    return group_stats(g, {launches_update}, launches_sample, launches_flow);
 }
-
-// Launches of an IQL group's fused update program and of one fused sampling call on a single chunk, counted from the built programs
 int fql_iql_group_stats(fql_group g, int64_t* launches_update, int64_t* launches_sample) {
-    if (!g) { g_create_error = "fql_iql_group_stats: NULL group"; return FQL_E_INVALID; }
-    if (group_wrong_kind(g, AgentKind::IQL, "fql_iql_group_stats", nullptr, GC_STATS)) return FQL_E_STATE;
-    try {
-        if (launches_update) *launches_update = (int64_t)g->progs[fql_group_s::FULL].launches.size();
-        if (launches_sample) *launches_sample = g->sample_launches(false);
-    } catch (const Invalid& e) {
-        g_create_error = e.msg; return FQL_E_INVALID;
-    } catch (const HipError& e) {
-        g_create_error = e.msg; return FQL_E_HIP;
-    }
-    return FQL_OK;
+    GROUP_ENTER(g, AgentKind::IQL, "fql_iql_group_stats", GC_STATS);
+    return group_stats(g, {launches_update}, launches_sample, nullptr);
 }
-
-// Launches of a CFGRL group's fused update program and of one fused sampling call on a single chunk, counted from the built programs
 int fql_cfgrl_group_stats(fql_group g, int64_t* launches_update, int64_t* launches_sample) {
-    if (!g) { g_create_error = "fql_cfgrl_group_stats: NULL group"; return FQL_E_INVALID; }
-    if (group_wrong_kind(g, AgentKind::CFGRL, "fql_cfgrl_group_stats", nullptr, GC_STATS)) return FQL_E_STATE;
-    try {
-        if (launches_update) *launches_update = (int64_t)g->progs[fql_group_s::FULL].launches.size();
-        if (launches_sample) *launches_sample = g->sample_launches(true);
-    } catch (const Invalid& e) {
-        g_create_error = e.msg; return FQL_E_INVALID;
-    } catch (const HipError& e) {
-        g_create_error = e.msg; return FQL_E_HIP;
-    }
-    return FQL_OK;
+    GROUP_ENTER(g, AgentKind::CFGRL, "fql_cfgrl_group_stats", GC_STATS);
+    return group_stats(g, {launches_update}, launches_sample, nullptr);
 }
-
-// Launches of a SAC group's fused update program and of one fused sampling call on a single chunk, counted from the built programs
 int fql_sac_group_stats(fql_group g, int64_t* launches_update, int64_t* launches_sample) {
-    if (!g) { g_create_error = "fql_sac_group_stats: NULL group"; return FQL_E_INVALID; }
-    if (group_wrong_kind(g, AgentKind::SAC, "fql_sac_group_stats", nullptr, GC_STATS)) return FQL_E_STATE;
-    try {
-        if (launches_update) *launches_update = (int64_t)g->progs[fql_group_s::FULL].launches.size();
-        if (launches_sample) *launches_sample = g->sample_launches(false);
-    } catch (const Invalid& e) {
-        g_create_error = e.msg; return FQL_E_INVALID;
-    } catch (const HipError& e) {
-        g_create_error = e.msg; return FQL_E_HIP;
-    }
-    return FQL_OK;
+    GROUP_ENTER(g, AgentKind::SAC, "fql_sac_group_stats", GC_STATS);
+    return group_stats(g, {launches_update}, launches_sample, nullptr);
 }
 
 int fql_group_synchronize(fql_group g) {

@@ -19,7 +19,7 @@ from __future__ import annotations
 import ctypes as C
 
 from . import _cabi
-from .agent import FQLAgent, _group_idx_arg, _group_sample_args
+from .agent import AgentGroup, FQLAgent
 from .config import ConfigDict
 
 IFQL_INFO_KEYS = (
@@ -101,7 +101,7 @@ class IFQLAgent(FQLAgent):
         return self._eval(observations, noises, seed, flow=False)
 
 
-class IFQLAgentGroup:
+class IFQLAgentGroup(AgentGroup):
     """K IFQL agents of one structure - the same config except `seed` and `expectile` - advanced by ONE fused update program
     (include/fql_amd.h, fql_ifql_group_*): every launch of the update carries all K members' tasks.  The seeds of one task, or an
     expectile x seed sweep, on one device:
@@ -117,55 +117,17 @@ class IFQLAgentGroup:
     size is fixed.  FQL agents are grouped by FQLAgentGroup, ReBRAC agents by ReBRACAgentGroup, IQL-diffusion agents by
     IQLDiffusionAgentGroup."""
 
-    def __init__(self, handle, members):
-        self._lib = _cabi.load()
-        self._g = handle
-        self.members = members
-        self.batch_size = int(members[0].config['batch_size'])
-        self._keep = None
+    _member, _get_config = IFQLAgent, staticmethod(get_config)
+    _create_fn, _update_fn = 'fql_ifql_group_create', 'fql_ifql_group_update_from_dataset'
+    _sample_fn, _flow_fn, _sample_temperature = 'fql_ifql_group_sample_actions', 'fql_ifql_group_flow_actions', False
+    _stats_fn, _stats_outs = 'fql_ifql_group_stats', 3   # launches(): (the update program, one best-of-N call, one flow call)
 
     @classmethod
     def create(cls, seeds, ex_observations, ex_actions, config, expectiles=None):
-        seeds = [int(s) for s in seeds]
-        if not seeds:
-            raise ValueError('an agent group needs at least one seed')
-        cfg = get_config()
-        cfg.update(dict(config))
-        expectiles = [float(cfg['expectile'])] * len(seeds) if expectiles is None else [float(e) for e in expectiles]
-        if len(expectiles) != len(seeds):
-            raise ValueError(f'{len(seeds)} seeds but {len(expectiles)} expectiles')
-        IFQLAgent._refuse_config(cfg)   # encoder, precision, rng: NotImplementedError before any library call
-        lib = _cabi.load()
-        members = []
-        for s, e in zip(seeds, expectiles):
-            c = dict(cfg)
-            c['expectile'] = e
-            members.append(IFQLAgent.create(s, ex_observations, ex_actions, c))
-        arr = (C.c_void_p * len(members))(*[m._h for m in members])
-        g = C.c_void_p()
-        _cabi.check(lib, None, lib.fql_ifql_group_create(arr, len(members), C.byref(g)))
-        return cls(g, members)
+        return cls._create(seeds, config, {'expectile': (expectiles, 'expectiles')}, ex_observations, ex_actions)
 
-    def _check(self, rc):
-        _cabi.check(self._lib, None, rc)
-
-    def upload_dataset(self, dataset, capacity=None):
-        """Every member gets its own device copy of `dataset` (IFQLAgent.upload_dataset)."""
-        for m in self.members:
-            m.upload_dataset(dataset, capacity=capacity)
-
-    def update_from_dataset(self, batch_size=None, idxs=None, want_info=False):
-        """One fused update of every member: rows from each member's dataset (`idxs` [K, B] int, host or device, or None = each member's
-        device RNG), x_0 and t from each member's device RNG.  Returns a list of K LazyInfo keyed by IFQL_INFO_KEYS (want_info) or None."""
-        B = int(batch_size or self.batch_size)
-        if B != self.batch_size:
-            raise ValueError(f'batch_size {B}: the members of a group keep the batch size they were grouped with ({self.batch_size})')
-        ip, keep, stream = None, None, None
-        if idxs is not None:
-            keep, ip, stream = _group_idx_arg(self.members, idxs, B)
-        self._check(self._lib.fql_ifql_group_update_from_dataset(self._g, ip, B, None, stream))
-        self._keep = keep
-        return [m._lazy_info(None) for m in self.members] if want_info else None
+    def _noise_per(self):   # best of N: noises [K, ..., num_samples, ad]
+        return (int(self.members[0].config['num_samples']),)
 
     def sample_actions(self, observations, seed=None, temperature=1.0, noises=None):
         """IFQLAgent.sample_actions of every member - best of `num_samples` - in ONE fused call (fql_ifql_group_sample_actions):
@@ -173,40 +135,11 @@ class IFQLAgentGroup:
         FQLAgentGroup.sample_actions: observations [K, ..., od] or one shared block, noises [K, ..., num_samples, ad] or None, seed None
         (each member's own counter advances), one seed or K seeds.  `temperature` is accepted and ignored, as in IFQLAgent.  Returns
         [K, ..., ad]."""
-        N = int(self.members[0].config['num_samples'])
-        o, z, seeds, n, out, optr, stream = _group_sample_args(self.members, observations, noises, seed, False, per=(N,))
-        self._check(self._lib.fql_ifql_group_sample_actions(self._g, o.ptr, n, z.ptr, seeds, optr, stream))
-        return out
+        return super().sample_actions(observations, seed, temperature, noises)
 
     def compute_flow_actions(self, observations, noises):
         """IFQLAgent.compute_flow_actions of every member in one fused call (fql_ifql_group_flow_actions): noises [K, ..., ad]."""
-        if noises is None:
-            raise ValueError('compute_flow_actions needs noises [K, ..., action_dim]')
-        o, z, _, n, out, optr, stream = _group_sample_args(self.members, observations, noises, None, True)
-        self._check(self._lib.fql_ifql_group_flow_actions(self._g, o.ptr, z.ptr, n, optr, stream))
-        return out
-
-    def launches(self):
-        """Kernel launches of (the fused update program, one fused best-of-N call, one fused flow call - each on a single chunk)."""
-        u, s, f = C.c_int64(0), C.c_int64(0), C.c_int64(0)
-        self._check(self._lib.fql_ifql_group_stats(self._g, C.byref(u), C.byref(s), C.byref(f)))
-        return int(u.value), int(s.value), int(f.value)
-
-    def synchronize(self):
-        """Host wait for the group's last update or sampling call."""
-        self._check(self._lib.fql_group_synchronize(self._g))
-
-    def close(self):
-        """Destroy the fused program; the members stay usable as standalone agents."""
-        if getattr(self, '_g', None):
-            self._lib.fql_group_destroy(self._g)
-            self._g = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        return self._flow_actions(observations, noises)
 
 
 __all__ = ['IFQLAgent', 'IFQLAgentGroup', 'IFQL_INFO_KEYS', 'IFQL_NOISE_KEYS', 'get_config']

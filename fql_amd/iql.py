@@ -17,7 +17,7 @@ from __future__ import annotations
 import ctypes as C
 
 from . import _cabi
-from .agent import KindAgent, _Arg, _PendingN, _group_idx_arg, _group_sample_args
+from .agent import AgentGroup, KindAgent, _Arg, _PendingN
 from .config import ConfigDict
 
 _IQL_HEAD_KEYS = (
@@ -131,7 +131,7 @@ class IQLAgent(KindAgent):
         return int(la.value), int(ma.value)
 
 
-class IQLAgentGroup:
+class IQLAgentGroup(AgentGroup):
     """K IQL agents of one structure - the same config except `seed`, `expectile` and `alpha` - advanced by ONE fused update program
     (include/fql_amd.h, fql_iql_group_*): every launch of the update carries all K members' tasks.  The alpha x expectile x seed sweep
     every table of the reference's papers runs for this baseline, on one device:
@@ -147,89 +147,13 @@ class IQLAgentGroup:
     state agents with precision 'fp32' and the engine's device RNG; while grouped their batch size is fixed.  FQL agents are grouped by
     FQLAgentGroup, ReBRAC agents by ReBRACAgentGroup, IQL-diffusion agents by IQLDiffusionAgentGroup, IFQL agents by IFQLAgentGroup."""
 
-    def __init__(self, handle, members):
-        self._lib = _cabi.load()
-        self._g = handle
-        self.members = members
-        self.batch_size = int(members[0].config['batch_size'])
-        self._keep = None
+    _member, _get_config = IQLAgent, staticmethod(get_config)
+    _create_fn, _update_fn = 'fql_iql_group_create', 'fql_iql_group_update_from_dataset'
+    _sample_fn, _stats_fn = 'fql_iql_group_sample_actions', 'fql_iql_group_stats'   # launches(): (the update program, one sampling call)
 
     @classmethod
     def create(cls, seeds, ex_observations, ex_actions, config, expectiles=None, alphas=None):
-        seeds = [int(s) for s in seeds]
-        if not seeds:
-            raise ValueError('an agent group needs at least one seed')
-        cfg = get_config()
-        cfg.update(dict(config))
-        coef = {}
-        for key, vals, name in (('expectile', expectiles, 'expectiles'), ('alpha', alphas, 'alphas')):
-            coef[key] = [float(cfg[key])] * len(seeds) if vals is None else [float(a) for a in vals]
-            if len(coef[key]) != len(seeds):
-                raise ValueError(f'{len(seeds)} seeds but {len(coef[key])} {name}')
-        IQLAgent._refuse_config(cfg)   # encoder, precision, rng, actor_loss: before any library call
-        lib = _cabi.load()
-        members = []
-        for s, e, a in zip(seeds, coef['expectile'], coef['alpha']):
-            c = dict(cfg)
-            c['expectile'], c['alpha'] = e, a
-            members.append(IQLAgent.create(s, ex_observations, ex_actions, c))
-        arr = (C.c_void_p * len(members))(*[m._h for m in members])
-        g = C.c_void_p()
-        _cabi.check(lib, None, lib.fql_iql_group_create(arr, len(members), C.byref(g)))
-        return cls(g, members)
-
-    def _check(self, rc):
-        _cabi.check(self._lib, None, rc)
-
-    def upload_dataset(self, dataset, capacity=None):
-        """Every member gets its own device copy of `dataset` (IQLAgent.upload_dataset)."""
-        for m in self.members:
-            m.upload_dataset(dataset, capacity=capacity)
-
-    def update_from_dataset(self, batch_size=None, idxs=None, want_info=False):
-        """One fused update of every member: rows from each member's dataset (`idxs` [K, B] int, host or device, or None = each member's
-        device RNG), eps from each member's device RNG.  Returns a list of K LazyInfo keyed by IQL_INFO_KEYS[actor_loss] (want_info) or
-        None."""
-        B = int(batch_size or self.batch_size)
-        if B != self.batch_size:
-            raise ValueError(f'batch_size {B}: the members of a group keep the batch size they were grouped with ({self.batch_size})')
-        ip, keep, stream = None, None, None
-        if idxs is not None:
-            keep, ip, stream = _group_idx_arg(self.members, idxs, B)
-        self._check(self._lib.fql_iql_group_update_from_dataset(self._g, ip, B, None, stream))
-        self._keep = keep
-        return [m._lazy_info(None) for m in self.members] if want_info else None
-
-    def sample_actions(self, observations, seed=None, temperature=1.0, noises=None):
-        """IQLAgent.sample_actions of every member in ONE fused call (fql_iql_group_sample_actions): result[i] is bitwise what
-        members[i].sample_actions(observations[i], seed=..., temperature=..., noises=noises[i]) returns.  Shapes and seeds as in
-        FQLAgentGroup.sample_actions: observations [K, ..., od] or one shared block, noises [K, ..., ad] or None, seed None (each
-        member's own counter advances), one seed or K seeds.  Returns [K, ..., ad]."""
-        o, z, seeds, n, out, optr, stream = _group_sample_args(self.members, observations, noises, seed, False)
-        self._check(self._lib.fql_iql_group_sample_actions(self._g, o.ptr, n, z.ptr, seeds, float(temperature), optr, stream))
-        return out
-
-    def launches(self):
-        """Kernel launches of (the fused update program, one fused sampling call on a single chunk)."""
-        u, s = C.c_int64(0), C.c_int64(0)
-        self._check(self._lib.fql_iql_group_stats(self._g, C.byref(u), C.byref(s)))
-        return int(u.value), int(s.value)
-
-    def synchronize(self):
-        """Host wait for the group's last update or sampling call."""
-        self._check(self._lib.fql_group_synchronize(self._g))
-
-    def close(self):
-        """Destroy the fused program; the members stay usable as standalone agents."""
-        if getattr(self, '_g', None):
-            self._lib.fql_group_destroy(self._g)
-            self._g = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        return cls._create(seeds, config, {'expectile': (expectiles, 'expectiles'), 'alpha': (alphas, 'alphas')}, ex_observations, ex_actions)
 
 
 __all__ = ['IQLAgent', 'IQLAgentGroup', 'IQL_INFO_KEYS', 'IQL_AWR_INFO_KEYS', 'IQL_DDPGBC_INFO_KEYS', 'IQL_NOISE_KEYS', 'get_config']

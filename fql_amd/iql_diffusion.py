@@ -23,7 +23,7 @@ import ctypes as C
 import numpy as np
 
 from . import _cabi
-from .agent import FQLAgent, KindAgent, LazyInfo, _Arg, _PendingN, _group_idx_arg, _group_sample_args
+from .agent import AgentGroup, FQLAgent, KindAgent, LazyInfo, _Arg, _PendingN, _group_sample_args
 from .bc import grid_index
 from .config import ConfigDict
 
@@ -398,7 +398,7 @@ def group_cfgs(cfg, K, lead):
     return check_cfgs(c.reshape(K * n), K * n, 'member and row').reshape(K, n)
 
 
-class IQLDiffusionAgentGroup:
+class IQLDiffusionAgentGroup(AgentGroup):
     """K IQL-diffusion agents of one structure - the same config except `seed`, `awr_temperature` and `softmax_beta` - advanced by fused
     update programs (include/fql_amd.h, fql_iqld_group_*): one per step kind, every launch carrying all K members' tasks.  The
     softmax_beta x seed sweep of the reference's scripts on one device:
@@ -413,61 +413,25 @@ class IQLDiffusionAgentGroup:
     seed, coefficients, rows and noise.  Members are state agents with precision 'fp32' and the engine's device RNG; while grouped their
     batch size is fixed.  FQL agents are grouped by FQLAgentGroup, ReBRAC agents by ReBRACAgentGroup."""
 
-    def __init__(self, handle, members):
-        self._lib = _cabi.load()
-        self._g = handle
-        self.members = members
-        self.batch_size = int(members[0].config['batch_size'])
-        self._keep = None
+    _member, _get_config = IQLDiffusionAgent, staticmethod(get_config)
+    _create_fn, _update_fn = 'fql_iqld_group_create', 'fql_iqld_group_update_from_dataset'
+    _sample_fn, _stats_fn = 'fql_iqld_group_sample_actions', 'fql_iqld_group_stats'
 
     @classmethod
     def create(cls, seeds, ex_observations, ex_actions, config, awr_temperatures=None, softmax_betas=None):
-        seeds = [int(s) for s in seeds]
-        if not seeds:
-            raise ValueError('an agent group needs at least one seed')
-        cfg = get_config()
-        cfg.update(dict(config))
-        coef = {}
-        for key, vals, name in (('awr_temperature', awr_temperatures, 'awr_temperatures'), ('softmax_beta', softmax_betas, 'softmax_betas')):
-            coef[key] = [float(cfg[key])] * len(seeds) if vals is None else [float(a) for a in vals]
-            if len(coef[key]) != len(seeds):
-                raise ValueError(f'{len(seeds)} seeds but {len(coef[key])} {name}')
-        IQLDiffusionAgent._refuse_config(cfg)   # encoder, precision, rng: NotImplementedError before any library call
-        lib = _cabi.load()
-        members = []
-        for s, t, b in zip(seeds, coef['awr_temperature'], coef['softmax_beta']):
-            c = dict(cfg)
-            c['awr_temperature'], c['softmax_beta'] = t, b
-            members.append(IQLDiffusionAgent.create(s, ex_observations, ex_actions, c))
-        arr = (C.c_void_p * len(members))(*[m._h for m in members])
-        g = C.c_void_p()
-        _cabi.check(lib, None, lib.fql_iqld_group_create(arr, len(members), C.byref(g)))
-        return cls(g, members)
-
-    def _check(self, rc):
-        _cabi.check(self._lib, None, rc)
-
-    def upload_dataset(self, dataset, capacity=None):
-        """Every member gets its own device copy of `dataset` (IQLDiffusionAgent.upload_dataset)."""
-        for m in self.members:
-            m.upload_dataset(dataset, capacity=capacity)
+        return cls._create(seeds, config, {'awr_temperature': (awr_temperatures, 'awr_temperatures'), 'softmax_beta': (softmax_betas, 'softmax_betas')},
+                           ex_observations, ex_actions)
 
     def update_from_dataset(self, batch_size=None, idxs=None, want_info=False, update_critic=True, update_actor=True):
         """One fused update of every member of the step kind (update_critic, update_actor): rows from each member's dataset (`idxs`
         [K, B] int, host or device, or None = each member's device RNG), x_0 and t from each member's device RNG.  Returns a list of K
         StepInfo keyed by info_keys(update_critic, update_actor) (want_info) or None."""
-        B = int(batch_size or self.batch_size)
-        if B != self.batch_size:
-            raise ValueError(f'batch_size {B}: the members of a group keep the batch size they were grouped with ({self.batch_size})')
-        ip, keep, stream = None, None, None
-        if idxs is not None:
-            keep, ip, stream = _group_idx_arg(self.members, idxs, B)
+        B = self._batch(batch_size)
         uc, ua = bool(update_critic), bool(update_actor)
-        self._check(self._lib.fql_iqld_group_update_from_dataset(self._g, ip, B, int(uc), int(ua), None, stream))
-        self._keep = keep
-        for m in self.members:
+
+        def after(m):
             m._actor_steps += int(ua)
-        return [m._step_info(None, uc, ua, B) for m in self.members] if want_info else None
+        return self._update(B, idxs, want_info, extra=(int(uc), int(ua)), after=after, info=lambda m: m._step_info(None, uc, ua, B))
 
     def sample_actions(self, observations, seed=None, cfg=1.0, noises=None):
         """IQLDiffusionAgent.sample_actions of every member in ONE fused call (fql_iqld_group_sample_actions): result[i] is bitwise
@@ -480,30 +444,14 @@ class IQLDiffusionAgentGroup:
         check_cfgs(c.reshape(-1), int(np.prod(c.shape)), 'entry')   # finite, whatever the shape: before a member's seed counter moves
         o, z, seeds, n, out, optr, stream = _group_sample_args(self.members, observations, noises, seed, False)
         w = _Arg(group_cfgs(c, K, tuple(int(d) for d in out.shape[1:-1])), (K, n))
-        self._check(self._lib.fql_iqld_group_sample_actions(self._g, o.ptr, n, z.ptr, seeds, w.ptr, optr, FQLAgent._stream([o, z, w])))
+        self._check(getattr(self._lib, self._sample_fn)(self._g, o.ptr, n, z.ptr, seeds, w.ptr, optr, FQLAgent._stream([o, z, w])))
         return out
 
     def launches(self):
         """Kernel launches of (the full, critic-only, actor-only and neither program, one fused sampling call on a single chunk)."""
         la, s = (C.c_int64 * 4)(), C.c_int64(0)
-        self._check(self._lib.fql_iqld_group_stats(self._g, la, C.byref(s)))
+        self._check(getattr(self._lib, self._stats_fn)(self._g, la, C.byref(s)))
         return int(la[0]), int(la[1]), int(la[2]), int(la[3]), int(s.value)
-
-    def synchronize(self):
-        """Host wait for the group's last update or sampling call."""
-        self._check(self._lib.fql_group_synchronize(self._g))
-
-    def close(self):
-        """Destroy the fused programs; the members stay usable as standalone agents."""
-        if getattr(self, '_g', None):
-            self._lib.fql_group_destroy(self._g)
-            self._g = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 __all__ = ['IQLDiffusionAgent', 'IQLDiffusionAgentGroup', 'IQLD_INFO_KEYS', 'IQLD_ROW_KEYS', 'IQLD_NOISE_KEYS', 'OPTIMAL_VARS', 'info_keys', 'get_config']

@@ -19,7 +19,7 @@ from __future__ import annotations
 import ctypes as C
 
 from . import _cabi
-from .agent import KindAgent, LazyInfo, _Arg, _group_idx_arg, _group_sample_args
+from .agent import AgentGroup, KindAgent, LazyInfo, _Arg
 from .config import ConfigDict
 
 REBRAC_INFO_KEYS = (
@@ -153,7 +153,7 @@ class ReBRACAgent(KindAgent):
         return int(la.value), int(ma.value)
 
 
-class ReBRACAgentGroup:
+class ReBRACAgentGroup(AgentGroup):
     """K ReBRAC agents of one structure - the same config except `seed`, `alpha_actor` and `alpha_critic` - advanced by fused update
     programs (include/fql_amd.h, fql_rebrac_group_*): one for the full step, one for the critic-only step, every launch carrying all K
     members' tasks.  The alpha_actor x alpha_critic x seed sweep of the reference's protocol on one device:
@@ -168,92 +168,25 @@ class ReBRACAgentGroup:
     alphas, rows and noise.  Members are state agents with precision 'fp32' and the engine's device RNG; while grouped their batch size
     is fixed.  FQL agents are grouped by FQLAgentGroup."""
 
-    def __init__(self, handle, members):
-        self._lib = _cabi.load()
-        self._g = handle
-        self.members = members
-        self.batch_size = int(members[0].config['batch_size'])
-        self._keep = None
+    _member, _get_config = ReBRACAgent, staticmethod(get_config)
+    _create_fn, _update_fn = 'fql_rebrac_group_create', 'fql_rebrac_group_update_from_dataset'
+    _sample_fn = 'fql_rebrac_group_sample_actions'
+    _stats_fn, _stats_outs = 'fql_rebrac_group_stats', 3   # launches(): (the full program, the critic-only program, one sampling call)
 
     @classmethod
     def create(cls, seeds, ex_observations, ex_actions, config, alpha_actors=None, alpha_critics=None):
-        seeds = [int(s) for s in seeds]
-        if not seeds:
-            raise ValueError('an agent group needs at least one seed')
-        cfg = get_config()
-        cfg.update(dict(config))
-        alphas = {}
-        for key, vals in (('alpha_actor', alpha_actors), ('alpha_critic', alpha_critics)):
-            alphas[key] = [float(cfg[key])] * len(seeds) if vals is None else [float(a) for a in vals]
-            if len(alphas[key]) != len(seeds):
-                raise ValueError(f'{len(seeds)} seeds but {len(alphas[key])} {key}s')
-        ReBRACAgent._refuse_config(cfg)   # encoder, precision, rng: NotImplementedError before any library call
-        lib = _cabi.load()
-        members = []
-        for s, aa, ac in zip(seeds, alphas['alpha_actor'], alphas['alpha_critic']):
-            c = dict(cfg)
-            c['alpha_actor'], c['alpha_critic'] = aa, ac
-            members.append(ReBRACAgent.create(s, ex_observations, ex_actions, c))
-        arr = (C.c_void_p * len(members))(*[m._h for m in members])
-        g = C.c_void_p()
-        _cabi.check(lib, None, lib.fql_rebrac_group_create(arr, len(members), C.byref(g)))
-        return cls(g, members)
-
-    def _check(self, rc):
-        _cabi.check(self._lib, None, rc)
-
-    def upload_dataset(self, dataset, capacity=None):
-        """Every member gets its own device copy of `dataset` (ReBRACAgent.upload_dataset)."""
-        for m in self.members:
-            m.upload_dataset(dataset, capacity=capacity)
+        return cls._create(seeds, config, {'alpha_actor': (alpha_actors, 'alpha_actors'), 'alpha_critic': (alpha_critics, 'alpha_critics')},
+                           ex_observations, ex_actions)
 
     def update_from_dataset(self, batch_size=None, idxs=None, want_info=False, full_update=True):
         """One fused update of every member, full or critic-only: rows from each member's dataset (`idxs` [K, B] int, host or device, or
         None = each member's device RNG) with next_actions = actions[min(idx + 1, size - 1)], noise from each member's device RNG.
         Returns a list of K LazyInfo (want_info; 12 or 7 keys by the step's kind) or None."""
-        B = int(batch_size or self.batch_size)
-        if B != self.batch_size:
-            raise ValueError(f'batch_size {B}: the members of a group keep the batch size they were grouped with ({self.batch_size})')
-        ip, keep, stream = None, None, None
-        if idxs is not None:
-            keep, ip, stream = _group_idx_arg(self.members, idxs, B)
         full = bool(full_update)
-        self._check(self._lib.fql_rebrac_group_update_from_dataset(self._g, ip, B, int(full), None, stream))
-        self._keep = keep
-        for m in self.members:
+
+        def after(m):
             m._last_full = full
-        return [m._lazy_info(None) for m in self.members] if want_info else None
-
-    def sample_actions(self, observations, seed=None, temperature=1.0, noises=None):
-        """ReBRACAgent.sample_actions of every member in ONE fused call (fql_rebrac_group_sample_actions): result[i] is bitwise what
-        members[i].sample_actions(observations[i], seed=..., temperature=..., noises=noises[i]) returns.  Shapes and seeds as in
-        FQLAgentGroup.sample_actions: observations [K, ..., od] or one shared block, noises [K, ..., ad] or None, seed None (each
-        member's own counter advances), one seed or K seeds.  Returns [K, ..., ad]."""
-        o, z, seeds, n, out, optr, stream = _group_sample_args(self.members, observations, noises, seed, False)
-        self._check(self._lib.fql_rebrac_group_sample_actions(self._g, o.ptr, n, z.ptr, seeds, float(temperature), optr, stream))
-        return out
-
-    def launches(self):
-        """Kernel launches of (the full program, the critic-only program, one fused sampling call on a single chunk)."""
-        f, c, s = C.c_int64(0), C.c_int64(0), C.c_int64(0)
-        self._check(self._lib.fql_rebrac_group_stats(self._g, C.byref(f), C.byref(c), C.byref(s)))
-        return int(f.value), int(c.value), int(s.value)
-
-    def synchronize(self):
-        """Host wait for the group's last update or sampling call."""
-        self._check(self._lib.fql_group_synchronize(self._g))
-
-    def close(self):
-        """Destroy the fused programs; the members stay usable as standalone agents."""
-        if getattr(self, '_g', None):
-            self._lib.fql_group_destroy(self._g)
-            self._g = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        return self._update(self._batch(batch_size), idxs, want_info, extra=(int(full),), after=after)
 
 
 __all__ = ['ReBRACAgent', 'ReBRACAgentGroup', 'REBRAC_INFO_KEYS', 'REBRAC_CRITIC_INFO_KEYS', 'REBRAC_NOISE_KEYS', 'get_config']

@@ -21,10 +21,8 @@ from __future__ import annotations
 import ctypes as C
 import math
 
-import numpy as np
-
 from . import _cabi
-from .agent import KindAgent, _Arg, _PendingN, _group_idx_arg, _group_sample_args, _torch
+from .agent import AgentGroup, KindAgent, _Arg, _PendingN
 from .config import ConfigDict
 
 SAC_INFO_KEYS = (
@@ -152,38 +150,7 @@ class SACAgent(KindAgent):
         return int(la.value), int(ma.value)
 
 
-def _group_balanced_idx(members, idxs, B):
-    """`idxs` = (dataset_idxs [K, B // 2], replay_idxs [K, B // 2]) of a balanced group update, host arrays or tensors (CUDA tensors on
-    torch's current stream): (keep-alive, dataset pointer, replay pointer, stream).  Host rows are range-checked against each member's
-    dataset_size() and replay_size(): an out-of-range row never reaches the device."""
-    K, half = len(members), B // 2
-    if len(idxs) != 2:
-        raise ValueError('idxs must be (dataset_idxs, replay_idxs)')
-    keeps, ptrs, stream = [], [], None
-    for part, what, rows in ((idxs[0], 'dataset idxs', lambda m: m.dataset_size()[0]), (idxs[1], 'replay idxs', lambda m: m.replay_size()[0])):
-        if hasattr(part, 'data_ptr'):
-            keep = part.long().contiguous()
-            shape, ptr = tuple(keep.shape), keep.data_ptr()
-            host = None if keep.is_cuda else keep.numpy()
-            if keep.is_cuda:
-                h = _torch().cuda.current_stream().cuda_stream
-                stream = h if h else _cabi.FQL_STREAM_LEGACY
-        else:
-            keep = np.ascontiguousarray(part, dtype=np.int64)
-            shape, ptr, host = keep.shape, keep.ctypes.data, keep
-        if shape != (K, half):
-            raise ValueError(f'{what} must be [{K}, {half}], got {tuple(shape)}')
-        if host is not None and half:
-            for i, m in enumerate(members):
-                n = rows(m)
-                if host[i].min() < 0 or host[i].max() >= n:
-                    raise ValueError(f'{what}[{i}] out of range: [{int(host[i].min())}, {int(host[i].max())}] for {n} rows')
-        keeps.append(keep)
-        ptrs.append(ptr)
-    return tuple(keeps), ptrs[0], ptrs[1], stream
-
-
-class SACAgentGroup:
+class SACAgentGroup(AgentGroup):
     """K SAC agents of one structure - the same config except `seed` and `target_entropy` - advanced by ONE fused update program
     (include/fql_amd.h, fql_sac_group_*): every launch of the update carries all K members' tasks.  The seeds of an RLPD run on one
     device:
@@ -200,48 +167,14 @@ class SACAgentGroup:
     with precision 'fp32' and the engine's device RNG; while grouped their batch size is fixed.  Ring inserts are not fused: a member's
     ring is filled through the member."""
 
-    def __init__(self, handle, members):
-        self._lib = _cabi.load()
-        self._g = handle
-        self.members = members
-        self.batch_size = int(members[0].config['batch_size'])
-        self._keep = None
+    _member, _get_config = SACAgent, staticmethod(get_config)
+    _create_fn, _update_fn, _balanced_fn = 'fql_sac_group_create', 'fql_sac_group_update_from_dataset', 'fql_sac_group_update_balanced'
+    _sample_fn, _stats_fn = 'fql_sac_group_sample_actions', 'fql_sac_group_stats'   # launches(): (the update program, one sampling call)
 
     @classmethod
     def create(cls, seeds, ex_observations, ex_actions, config, target_entropies=None):
-        seeds = [int(s) for s in seeds]
-        if not seeds:
-            raise ValueError('an agent group needs at least one seed')
-        cfg = get_config()
-        cfg.update(dict(config))
-        tes = [cfg['target_entropy']] * len(seeds) if target_entropies is None else [None if t is None else float(t) for t in target_entropies]
-        if len(tes) != len(seeds):
-            raise ValueError(f'{len(seeds)} seeds but {len(tes)} target_entropies')
-        SACAgent._refuse_config(cfg)   # encoder, precision, rng, state_dependent_std: before any library call
-        lib = _cabi.load()
-        members = []
-        for s, t in zip(seeds, tes):
-            c = dict(cfg)
-            c['target_entropy'] = t
-            members.append(SACAgent.create(s, ex_observations, ex_actions, c))
-        arr = (C.c_void_p * len(members))(*[m._h for m in members])
-        g = C.c_void_p()
-        _cabi.check(lib, None, lib.fql_sac_group_create(arr, len(members), C.byref(g)))
-        return cls(g, members)
-
-    def _check(self, rc):
-        _cabi.check(self._lib, None, rc)
-
-    def _batch(self, batch_size):
-        B = int(batch_size or self.batch_size)
-        if B != self.batch_size:
-            raise ValueError(f'batch_size {B}: the members of a group keep the batch size they were grouped with ({self.batch_size})')
-        return B
-
-    def upload_dataset(self, dataset, capacity=None):
-        """Every member gets its own device copy of `dataset` (SACAgent.upload_dataset)."""
-        for m in self.members:
-            m.upload_dataset(dataset, capacity=capacity)
+        tes = None if target_entropies is None else [None if t is None else float(t) for t in target_entropies]   # (None: automatic)
+        return cls._create(seeds, config, {'target_entropy': (tes, 'target_entropies', lambda t: t)}, ex_observations, ex_actions)
 
     def create_replay_buffers(self, capacity):
         """Every member gets its own empty replay ring of `capacity` rows (SACAgent.create_replay_buffer)."""
@@ -255,60 +188,11 @@ class SACAgentGroup:
         for m, t in zip(self.members, transitions):
             m.add_transition(t, replay=True)
 
-    def update_from_dataset(self, batch_size=None, idxs=None, want_info=False):
-        """One fused update of every member: rows from each member's dataset (`idxs` [K, B] int, host or device, or None = each member's
-        device RNG), eps_n and eps_c from each member's device RNG.  Returns a list of K LazyInfo keyed by SAC_INFO_KEYS (want_info) or
-        None."""
-        B = self._batch(batch_size)
-        ip, keep, stream = None, None, None
-        if idxs is not None:
-            keep, ip, stream = _group_idx_arg(self.members, idxs, B)
-        self._check(self._lib.fql_sac_group_update_from_dataset(self._g, ip, B, None, stream))
-        self._keep = keep
-        return [m._lazy_info(None) for m in self.members] if want_info else None
-
     def update_balanced(self, batch_size=None, idxs=None, want_info=False):
-        """RLPD's step for every member in one fused update: member i trains on concat(its dataset.sample(B // 2), its replay
-        ring.sample(B // 2)).  `idxs` = (dataset_idxs [K, B // 2], replay_idxs [K, B // 2]), host or device, or None = each member's
-        device RNG.  Returns as update_from_dataset."""
-        B = self._batch(batch_size)
-        ia, ib, keep, stream = None, None, None, None
-        if idxs is not None:
-            keep, ia, ib, stream = _group_balanced_idx(self.members, idxs, B)
-        self._check(self._lib.fql_sac_group_update_balanced(self._g, ia, ib, B, None, stream))
-        self._keep = keep
-        return [m._lazy_info(None) for m in self.members] if want_info else None
-
-    def sample_actions(self, observations, seed=None, temperature=1.0, noises=None):
-        """SACAgent.sample_actions of every member in ONE fused call (fql_sac_group_sample_actions): result[i] is bitwise what
-        members[i].sample_actions(observations[i], seed=..., temperature=..., noises=noises[i]) returns.  Shapes and seeds as in
-        IQLAgentGroup.sample_actions: observations [K, ..., od] or one shared block, noises [K, ..., ad] or None, seed None (each
-        member's own counter advances), one seed or K seeds.  Returns [K, ..., ad]."""
-        o, z, seeds, n, out, optr, stream = _group_sample_args(self.members, observations, noises, seed, False)
-        self._check(self._lib.fql_sac_group_sample_actions(self._g, o.ptr, n, z.ptr, seeds, float(temperature), optr, stream))
-        return out
-
-    def launches(self):
-        """Kernel launches of (the fused update program, one fused sampling call on a single chunk)."""
-        u, s = C.c_int64(0), C.c_int64(0)
-        self._check(self._lib.fql_sac_group_stats(self._g, C.byref(u), C.byref(s)))
-        return int(u.value), int(s.value)
-
-    def synchronize(self):
-        """Host wait for the group's last update or sampling call."""
-        self._check(self._lib.fql_group_synchronize(self._g))
-
-    def close(self):
-        """Destroy the fused program; the members stay usable as standalone agents."""
-        if getattr(self, '_g', None):
-            self._lib.fql_group_destroy(self._g)
-            self._g = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        """RLPD's step for every member in one fused update (fql_sac_group_update_balanced): member i trains on concat(its
+        dataset.sample(B // 2), its replay ring.sample(B // 2)).  `idxs` = (dataset_idxs [K, B // 2], replay_idxs [K, B // 2]), host or
+        device, or None = each member's device RNG.  Returns as update_from_dataset."""
+        return self._update(self._batch(batch_size), idxs, want_info, balanced=True)
 
 
 __all__ = ['SACAgent', 'SACAgentGroup', 'SAC_INFO_KEYS', 'SAC_NOISE_KEYS', 'get_config']
