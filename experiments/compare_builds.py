@@ -9,9 +9,14 @@ the counters) and dump.txt (its stderr: the FQL_DUMP lines of every program the 
 non-zero exit or time-out stops the script.  This process never opens the GPU: it compares the two directories, prints the first
 difference and the number of arrays and lines compared, and exits 1 on a difference.
 
-Jobs: `kinds`: FQL, IFQL, ReBRAC, SAC, IQL ddpgbc and awr, BC, IQL-diffusion, CFGRL at hidden 64 x 2, batch 32 (ReBRAC alternates
-critic-only and full steps, IQL-diffusion runs its four step kinds; one sample_actions of 5 rows each, cfg 3 and one per-row sweep call for
-the two CFG kinds).  `h512_<precision>`: FQL at hidden 512 x 4, batch 256, then one update_begin_split / update_end_split pair.
+Jobs: `kinds`: FQL, IFQL, ReBRAC, SAC with and without tanh_squash, IQL ddpgbc and awr with const_std and with the log_stds leaf, BC,
+IQL-diffusion, CFGRL at hidden 64 x 2, batch 32 (ReBRAC alternates critic-only and full steps, IQL-diffusion runs its four step kinds; one
+sample_actions of 5 rows each, cfg 3 and one per-row sweep call for the two CFG kinds).  Around that, what a handle's kind decides on the
+host: right after create every parameter leaf, fql_num_info and every fql_handle_info_name; behind the state read-out a total_loss /
+policy_loss probe on one fixed batch with explicit noise (loss and infos), one network.select query of 5 rows per module the kind answers
+for, the fql_last_error text of a query of a module it does not have and of an update whose explicit noise carries a field it does not
+read, and a second sampling call (explicit noises where the first used a seed, and the reverse; temperature 0.5 for ReBRAC, SAC and IQL).
+`h512_<precision>`: FQL at hidden 512 x 4, batch 256, then one update_begin_split / update_end_split pair.
 `edges_<precision>`: the FQL shapes of tests/test_gpu_batch_edges.py CASES.  `frames`: a 32 x 32 x 3 frames handle in both precisions (no
 plan: the read-out refuses visual handles).  `group`: the two members of a K = 2 FQL group at hidden 256 x 4, batch 64.
 `group_<kind>` (rebrac, iqld, ifql, iql_ddpgbc, iql_awr, cfgrl, sac): a K = 2 group of that kind at hidden 64 x 2, batch 32, its free fields
@@ -91,6 +96,7 @@ def fql_handle(out, tag, B, hidden, precision):
     cfg.update(actor_hidden_dims=tuple(hidden), value_hidden_dims=tuple(hidden), alpha=10.0, batch_size=B, precision=precision)
     ds = dataset(max(4 * B, 64), seed=3)
     a = fql_amd.FQLAgent.create(0, ds['observations'][:1], ds['actions'][:1], cfg)
+    created(out, tag, a)
     plan_and_forms(out, tag, agent=a)
     out[f'{tag}/stats'] = np.array([v for _, v in sorted(a.stats().items())], np.int64)
     a.upload_dataset(ds)
@@ -103,6 +109,90 @@ def fql_handle(out, tag, B, hidden, precision):
     return a
 
 
+def loss_noise(kind, B):
+    """The explicit noise of one loss probe: the fields the kind reads, from one fixed draw (t on the grid k / 16 for BC and IQL-diffusion)."""
+    rng = np.random.default_rng(5)
+    n = {k: rng.standard_normal((B, AD)).astype(np.float32) for k in ('eps1', 'x0', 'z', 'eps2')}
+    n['t'] = rng.uniform(size=B).astype(np.float32)
+    grid = (rng.integers(0, 17, size=B) / 16.0).astype(np.float32)
+    return {'fql': n, 'ifql': {k: n[k] for k in ('x0', 't')}, 'rebrac': {'eps1': n['eps1']}, 'sac': {k: n[k] for k in ('eps1', 'eps2')},
+            'iql': {'eps': n['eps1']}, 'bc': {'x0': n['x0'], 't': grid}, 'iqld': {'x0': n['x0'], 't': grid},
+            'cfgrl': {k: n[k] for k in ('x0', 't')}}[kind]
+
+
+def created(out, tag, a):
+    """Right after create: every parameter leaf (the initialisers), the info count and every info name as bytes."""
+    from fql_amd import _cabi
+    lib = _cabi.load()
+    out.update(flat(a.get_params(), f'{tag}/init'))
+    n = lib.fql_num_info(a._h)
+    out[f'{tag}/num_info'] = np.array([n], np.int32)
+    for i in range(n):
+        out[f'{tag}/info_name/{i:02d}'] = np.frombuffer(lib.fql_handle_info_name(a._h, i), np.uint8)
+
+
+def refusal_text(out, tag, lib, a, rc):
+    out[f'{tag}/rc'] = np.array([rc], np.int32)
+    out[f'{tag}/text'] = np.frombuffer(lib.fql_last_error(a._h), np.uint8)
+
+
+def probes(out, tag, a, ds, goals=None):
+    """Behind the updates and the state read-out, what the handle's kind decides on the host: a loss probe on one fixed batch with explicit
+    noise, one query of every module the kind answers for, the refusal of a module it does not have and of a noise field it does not
+    read, and a second sampling call (explicit noises where the first used a seed, and the reverse; temperature 0.5 where the kind has one)."""
+    import fql_amd
+    from fql_amd import _cabi
+    lib = _cabi.load()
+    kind, B = tag.split('_')[0], 32
+    batch = {k: ds[k][:B] for k in ('observations', 'actions', 'rewards', 'masks', 'next_observations')}
+    batch['next_actions'] = ds['actions'][1:B + 1]
+    batch['actor_goals'] = ds['next_observations'][:B]
+    noise = loss_noise(kind, B)
+    if kind == 'rebrac':
+        losses = [(f'loss{f}', a.total_loss(batch, noise=noise, full_update=bool(f))) for f in (1, 0)]
+    elif kind == 'bc':
+        losses = [('loss', a.policy_loss(batch, noise=noise))]
+    elif kind == 'cfgrl':
+        losses = [('loss', a.policy_loss(batch, noise=noise, do_cfg=np.arange(B) % 3 == 0))]
+    else:
+        losses = [('loss', a.total_loss(batch, noise=noise))]
+    for name, (loss, info) in losses:
+        out[f'{tag}/{name}'] = np.array([loss], np.float32)
+        for k, v in info.items():
+            out[f'{tag}/{name}/{k}'] = np.asarray(v)
+    rng = np.random.default_rng(6)
+    obs, act = ds['observations'][:5], ds['actions'][:5]
+    z, t = rng.standard_normal((5, AD)).astype(np.float32), rng.uniform(size=5).astype(np.float32)
+    for name, family in a._modules.items():
+        m = a.network.select(name)
+        out[f'{tag}/module/{name}'] = {'pair': lambda: m(obs, actions=act), 'value': lambda: m(obs), 'field_t': lambda: m(obs, act, t),
+                                       'field': lambda: m(obs, z)}[family]()
+    missing = 'value' if 'value' not in a._modules else 'actor_onestep_flow'
+    refusal_text(out, f'{tag}/no_module', lib, a, lib.fql_module_forward(a._h, missing.encode(), None, None, None, 5, None, None))
+    if kind in ('rebrac', 'sac', 'iql'):
+        out[f'{tag}/sample2'] = a.sample_actions(obs, noises=z, temperature=0.5)
+    elif kind == 'ifql':
+        out[f'{tag}/sample2'] = a.sample_actions(obs, noises=rng.standard_normal((5, int(a.config['num_samples']), AD)).astype(np.float32))
+    elif kind == 'bc':
+        out[f'{tag}/sample2'] = a.sample_actions(obs, noises=z)
+    elif kind == 'cfgrl':
+        out[f'{tag}/sample2'] = a.sample_actions(obs, goals, seed=7, cfg=3.0)
+    elif kind == 'iqld':
+        out[f'{tag}/sample2'] = a.sample_actions(obs, seed=7, cfg=3.0)
+    else:
+        out[f'{tag}/sample2'] = a.sample_actions(obs, seed=7)
+    if kind != 'fql':   # a field the kind does not read (z is FQL's alone), past the Python layer's own check of the dict
+        a._noise_args = lambda noise, B: fql_amd.FQLAgent._noise_args(a, noise, B)
+        try:
+            a.update_from_dataset(B, noise={'z': rng.standard_normal((B, AD)).astype(np.float32)})
+            rc = 0
+        except (ValueError, KeyError, _cabi.FqlError) as e:
+            rc = {ValueError: _cabi.FQL_E_INVALID, KeyError: _cabi.FQL_E_NOTFOUND}.get(type(e), _cabi.FQL_E_STATE)
+        del a._noise_args
+        assert rc != 0, tag
+        refusal_text(out, f'{tag}/noise_refusal', lib, a, rc)
+
+
 def job_kinds(out):
     import fql_amd
     import fql_amd.cfgrl
@@ -110,19 +200,26 @@ def job_kinds(out):
     obs, z = ds['observations'][:5], np.random.default_rng(1).standard_normal((5, AD)).astype(np.float32)
     w = np.array([1.0, 1.5, 3.0, 5.0, 3.0], np.float32)
     hid = dict(actor_hidden_dims=(64, 64), value_hidden_dims=(64, 64), hidden_dims=(64, 64), batch_size=32)
-    fql_handle(out, 'fql', 32, (64, 64), 'fp32').close()
+    f = fql_handle(out, 'fql', 32, (64, 64), 'fp32')
+    probes(out, 'fql', f, dataset(max(4 * 32, 64), seed=3))
+    f.close()
     ex = (ds['observations'][:1], ds['actions'][:1])
+    iql, sac = fql_amd.iql.get_config(), fql_amd.sac.get_config()
     kinds = [('ifql', fql_amd.IFQLAgent, fql_amd.ifql.get_config(), lambda a: a.stats().values()),
              ('rebrac', fql_amd.ReBRACAgent, fql_amd.rebrac.get_config(), lambda a: a.rebrac_stats(True) + a.rebrac_stats(False)),
-             ('sac', fql_amd.SACAgent, fql_amd.sac.get_config(), lambda a: a.sac_stats()),
-             ('iql_ddpgbc', fql_amd.IQLAgent, dict(fql_amd.iql.get_config(), actor_loss='ddpgbc'), lambda a: a.iql_stats()),
-             ('iql_awr', fql_amd.IQLAgent, dict(fql_amd.iql.get_config(), actor_loss='awr'), lambda a: a.iql_stats()),
+             ('sac', fql_amd.SACAgent, sac, lambda a: a.sac_stats()),
+             ('sac_nosquash', fql_amd.SACAgent, dict(sac, tanh_squash=False), lambda a: a.sac_stats()),
+             ('iql_ddpgbc', fql_amd.IQLAgent, dict(iql, actor_loss='ddpgbc'), lambda a: a.iql_stats()),
+             ('iql_awr', fql_amd.IQLAgent, dict(iql, actor_loss='awr'), lambda a: a.iql_stats()),
+             ('iql_ddpgbc_logstds', fql_amd.IQLAgent, dict(iql, actor_loss='ddpgbc', const_std=False), lambda a: a.iql_stats()),
+             ('iql_awr_logstds', fql_amd.IQLAgent, dict(iql, actor_loss='awr', const_std=False), lambda a: a.iql_stats()),
              ('bc', fql_amd.BCAgent, fql_amd.bc.get_config(), lambda a: a.bc_stats()),
              ('iqld', fql_amd.IQLDiffusionAgent, fql_amd.iql_diffusion.get_config(),
               lambda a: sum((a.iqld_stats(c, p) for c in (1, 0) for p in (1, 0)), ()) + (a.sample_cfgs_stats(),))]
     for tag, cls, cfg, stats in kinds:
         cfg = dict(cfg, **hid)
         a = cls.create(0, *ex, cfg)
+        created(out, tag, a)
         plan_and_forms(out, tag, agent=a)
         out[f'{tag}/stats'] = np.array([int(v) for v in stats(a)], np.int64)
         a.upload_dataset(ds)
@@ -139,9 +236,11 @@ def job_kinds(out):
             else:
                 a.update_from_dataset(32)
         state(out, tag, a)
+        probes(out, tag, a, ds)
         a.close()
     goals = ds['next_observations'][:5]
     g = fql_amd.CFGRLAgent.create(0, {'observations': ex[0], 'actions': ex[1], 'value_goals': goals[:1]}, dict(fql_amd.cfgrl.get_config(), **hid))
+    created(out, 'cfgrl', g)
     plan_and_forms(out, 'cfgrl', agent=g)
     out['cfgrl/stats'] = np.array(g.cfgrl_stats() + (g.sample_cfgs_stats(),), np.int64)
     g.upload_dataset(ds)
@@ -150,6 +249,7 @@ def job_kinds(out):
     for _ in range(UPDATES):
         g.update_from_dataset(32)
     state(out, 'cfgrl', g)
+    probes(out, 'cfgrl', g, ds, goals)
     g.close()
 
 

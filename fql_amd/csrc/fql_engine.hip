@@ -494,32 +494,83 @@ const char* const k_iqld_info_names[FQL_IQLD_NUM_INFO] = {
 const char* const k_cfgrl_info_names[FQL_CFGRL_NUM_INFO] = {"actor/actor_loss", "grad/max", "grad/min", "grad/norm"};
 
 enum { NZ_EPS1 = 1, NZ_X0 = 2, NZ_T = 4, NZ_Z = 8, NZ_EPS2 = 16 };   // the fields of fql_noise
-// One row per kind, indexed by AgentKind.  A new agent adds a row here and a column to k_admission (C ABI, below).
+
+// What a kind's row is made of (KindDesc, below).
+// A module of the parameter tree: its nets (n1 >= 0: the stacked pair), whether it trains, its encoder on a visual handle.  n0 < 0: a
+// module without a net (SAC's 0-d LogParam).  actor: an Actor module, whose last layer is read back as mean_net behind actor_net.
+struct Mod { const char* name; const char* sub; int n0, n1; bool train; int enc; bool actor = false; };
+// Where a kind's special leaves sort among the generic ones (KindDesc::special_leaves is called at each of these places)
+enum LeafSite { LS_BARE_HEAD, LS_NO_NET, LS_ACTOR_HEAD, LS_LAST };   // behind a bare net's Dense_0; a module without a net; behind an Actor's actor_net; behind every module
+enum HeadInit { HI_GLOROT, HI_LECUN_TRUNC, HI_TWO_HEADS };   // the actor head's initialiser (init_params)
+struct EmbedInit { int n, fan_in; };                          // the embedding at emb_off: n floats of the untruncated N(0, 1 / fan_in)
+struct InfoSet { const char* const* names; int n; };
+enum Sampler { SMP_ONESTEP, SMP_BEST_OF_N, SMP_ACTOR, SMP_FLOW };   // sample_actions: FQL's one-step actor, IFQL's best of N, an actor on obs, a flow policy
+// One chunk of an actor kind's sampling call behind the actor's forward: mean [m, out_p] -> out [m, act]; z: the caller's noise or null
+struct ActChunk { const float *mean, *z; float* out; uint64_t sd; int m, start; float temperature; };
+// What differs between the hoisted flow samplers (DESIGN.md sections 16 and 18-20): BC's, and the two CFG kinds' with a scalar cfg
+// or, as a sweep, with one guidance weight per row.  A row holds halves, shared_x and tables; flow_shape() fills in the handle's rest.
+struct FlowShape {
+    int halves;      // 1: BC, one block of n_pad rows.  2: the CFG kinds, rows [0, half) the positive / conditional pass, [half, n_pad) the unconditional one
+    bool shared_x;   // the halves share X = [obs | 0] and C0 (IQL-diffusion); CFGRL's differ in the goal columns
+    int tables;      // step-bias rows per step: 1 BC [S, H], 2 IQL-diffusion [S, 2, H], 0 CFGRL (t is an argument of its layer-0 kernels)
+    int S;           // Euler steps
+    int goal_dim;    // CFGRL: the goal block in front of the action rows of W0, and goals to stage; else 0
+    bool sweep;      // the weights come per row from the workspace (cfgs), and the combine of step i - 1 rides in front of layer 0 of step i
+};
+// A module a handle answers for in fql_module_forward, under the reference's name without "modules_".  members 2: the stacked critic,
+// nets `net` and `net + 1` on the same rows.  scalar: the head is one column (Value), the result [members, n]; else [n, act].
+struct ModuleSpec { const char* name; int net, members; bool scalar, act, times; };
+enum : unsigned {   // traits of a kind
+    K_CRITIC = 1,         // a critic pair and its target (NET_C0..NET_T1)
+    K_OWN_INFO = 2,       // the infos live in iql_info, not in DevState::info
+    K_POLYAK_ALL = 4,     // Polyak moves the whole trained range: critic_size = n_train (rebrac.py:131-133: critic pair and actor)
+    K_CHAIN = 8,          // the Euler-chain kernel is admitted (build_chain_weights)
+    K_TIME_TABLE = 16,    // the timestep-embedding table d_emb; an explicit t is read on the grid {0, 1/S, ..., 1}
+    K_NEXT_ACTIONS = 32,  // update_from_dataset takes next_actions from the dataset (utils/datasets.py:96-100)
+    K_ACTOR_STATE = 64,   // a second DevState, d_state_a: the actor TrainState's own counters
+    K_GOALS = 128,        // a goal source (d_gsrc), a goal block in the actor's rows; the goal config holds the sampler's steps
+    K_VISUAL = 256,       // visual encoders and the bf16 x 3 precision are available
+};
+// One row per kind, indexed by AgentKind: everything the single-handle layer decides by the kind.  The table, k_kinds, stands behind
+// fql_engine, whose members its rows name.  A new agent adds an enumerator, a row and its hooks there, and a column to EP_TABLE (C ABI).
 struct KindDesc {
     const char* name;               // "IFQL": create-time messages
     const char* label;              // "an IFQL handle": entry-point messages
     const char* create;             // its create call
-    const char* const* info_names;  // nullptr: depends on the handle's config (IQL: by actor_loss)
+    unsigned traits;                // K_*
+    const char* const* info_names;
     int num_info;
+    InfoSet (*infos)(const fql_engine&);   // where names and count depend on the handle's config (IQL: by actor_loss); else null
+    int probe_infos, probe_terms[3];       // fql_total_loss: the infos it returns, the info slots whose sum is the loss (-1: none)
     int noise_reads;                // NZ_* fields of fql_noise the kind reads; any other must be NULL ...
     const char* noise_refusal;      // ... or fill_noise refuses with this
-};
-const KindDesc k_kinds[kNumKinds] = {
-    {"FQL", "an FQL handle", "fql_create", k_info_names, FQL_NUM_INFO, NZ_EPS1 | NZ_X0 | NZ_T | NZ_Z | NZ_EPS2, nullptr},
-    {"IFQL", "an IFQL handle", "fql_ifql_create", k_ifql_info_names, FQL_IFQL_NUM_INFO, NZ_X0 | NZ_T,
-     "IFQL reads only x0 and t of fql_noise (eps1, z and eps2 must be NULL)"},
-    {"ReBRAC", "a ReBRAC handle", "fql_rebrac_create", k_rebrac_info_names, FQL_REBRAC_NUM_INFO, NZ_EPS1,
-     "ReBRAC reads only eps1 of fql_noise (x0, t, z and eps2 must be NULL)"},
-    {"SAC", "a SAC handle", "fql_sac_create", k_sac_info_names, FQL_SAC_NUM_INFO, NZ_EPS1 | NZ_EPS2,
-     "SAC reads only eps1 and eps2 of fql_noise (x0, t and z must be NULL)"},
-    {"BC", "a BC handle", "fql_bc_create", k_bc_info_names, FQL_BC_NUM_INFO, NZ_X0 | NZ_T,
-     "BC reads only x0 and t of fql_noise (eps1, z and eps2 must be NULL)"},
-    {"IQL", "an IQL handle", "fql_iql_create", nullptr, 0, NZ_EPS1,
-     "IQL reads only eps1 of fql_noise (x0, t, z and eps2 must be NULL)"},
-    {"IQL-diffusion", "an IQL-diffusion handle", "fql_iqld_create", k_iqld_info_names, FQL_IQLD_NUM_INFO, NZ_X0 | NZ_T,
-     "IQL-diffusion reads only x0 and t of fql_noise (eps1, z and eps2 must be NULL)"},
-    {"CFGRL", "a CFGRL handle", "fql_cfgrl_create", k_cfgrl_info_names, FQL_CFGRL_NUM_INFO, NZ_X0 | NZ_T,
-     "CFGRL reads only x0 and t of fql_noise (eps1, z and eps2 must be NULL)"},
+    // create: the refusal of a kind config or null; the copy of the config into the engine
+    const char* (*check)(const void* kind_cfg);
+    void (*adopt)(fql_engine&, const void* kind_cfg);
+    // the arena: NET_BC / NET_OS / NET_TA over (obs, act) widths; the trained floats a kind keeps behind NET_OS and the member that holds their offset
+    void (*nets)(fql_engine&, int od, int ad);
+    size_t fql_engine::* extra_off;
+    size_t (*extra_floats)(const fql_engine&);
+    // leaves: the modules in the parameter tree's order, the prefix of a bare policy net's leaves (null: none), the prefixes of the three
+    // trained modules in chunk order (all null: one module, every chunk), the kind's special leaves (returns true where it wrote an Actor's heads itself)
+    const Mod* mods;
+    int nmods;
+    const char* bare;
+    const char* trained[3];
+    bool (*special_leaves)(fql_engine&, LeafSite, const Mod*);
+    // initialisers: the actor head's, the Glorot scale of HI_GLOROT / HI_TWO_HEADS (null: 1), the embedding's (null: none)
+    HeadInit head_init;
+    double (*head_scale)(const fql_engine&);
+    EmbedInit (*embed_init)(const fql_engine&);
+    // per batch size: the update workspace and programs; the multiply-accumulates of one update
+    void (fql_engine::*workspace)();
+    int64_t (*macs)(const fql_engine&);
+    // sampling and queries: the sampler; SMP_ACTOR: the launch behind the actor's forward; SMP_FLOW: halves, shared_x, tables; fql_module_forward's modules
+    Sampler sampler;
+    void (*act)(const fql_engine&, const ActChunk&, hipStream_t);
+    FlowShape flow;
+    const ModuleSpec* modules;
+    int nmodules;
 };
 
 }  // namespace
@@ -528,14 +579,14 @@ struct fql_group_s;
 struct fql_engine {
     fql_config cfg{};
     AgentKind kind = AgentKind::FQL;
-    const KindDesc& desc() const { return k_kinds[(int)kind]; }
-    bool has_value_net() const { return kind == AgentKind::IFQL || kind == AgentKind::IQL || kind == AgentKind::IQLD; }      // NET_OS holds V(obs)
-    bool actor_on_obs() const { return kind == AgentKind::REBRAC || kind == AgentKind::SAC || kind == AgentKind::IQL; }   // NET_BC is actor(obs), no flow
-    int num_info() const {
-        if (kind == AgentKind::IQL) return qcfg.actor_loss == 1 ? FQL_IQL_DDPGBC_NUM_INFO : FQL_IQL_AWR_NUM_INFO;
-        return desc().num_info;
-    }
-    const char* const* info_names() const { return kind == AgentKind::IQL ? k_iql_info_names[qcfg.actor_loss == 1 ? 1 : 0] : desc().info_names; }
+    const KindDesc& desc() const;
+    bool has(unsigned trait) const { return (desc().traits & trait) != 0; }
+    bool actor_on_obs() const { return desc().sampler == SMP_ACTOR; }   // NET_BC is actor(obs), no flow
+    bool flow_sampler() const { return desc().sampler == SMP_FLOW; }
+    bool own_info() const { return has(K_OWN_INFO); }
+    InfoSet infos() const { return desc().infos ? desc().infos(*this) : InfoSet{desc().info_names, desc().num_info}; }
+    int num_info() const { return infos().n; }
+    const char* const* info_names() const { return infos().names; }
     // IFQL agent (agents/ifql.py; fql_ifql_create): the arena's NET_OS slot holds the value net (obs -> 1, LayerNorm like the critic),
     // NET_BC is actor_flow; critic, target and their place in the arena are FQL's.  The update is build_ifql_program.
     float expectile = 0.9f;
@@ -601,7 +652,6 @@ struct fql_engine {
     unsigned char *in_cfg = nullptr, *cf_mask = nullptr;   // [B] staging of a host mask; [2][B] do_cfg
     int64_t* cf_rows = nullptr;                   // [2][2][B]
     uint32_t* cf_draws = nullptr;                 // [2][CFGRL_NUM_DRAWS][B]
-    bool own_info() const { return kind == AgentKind::IQL || kind == AgentKind::IQLD; }
     uint64_t seed = 0;
     int device = 0;
     hipStream_t stream = nullptr;
@@ -771,37 +821,29 @@ struct fql_engine {
         return (float*)p;
     }
 
+    static Net make_net(int in, const int32_t* hid, int nh, int out, bool ln) {
+        Net n;
+        int prev = in;
+        for (int i = 0; i <= nh; ++i) {
+            Layer L{};
+            L.in = prev;
+            L.out = (i < nh) ? hid[i] : out;
+            L.in_p = (i == 0) ? ((L.in + 63) & ~63) : pad16(L.in);
+            L.out_p = pad16(L.out);
+            L.ln = ln && i < nh;
+            n.layers.push_back(L);
+            prev = L.out;
+        }
+        return n;
+    }
+    Net actor_net(int in, int out) const { return make_net(in, cfg.actor_hidden, cfg.num_actor_hidden, out, cfg.actor_layer_norm != 0); }
+    Net value_net(int in) const { return make_net(in, cfg.value_hidden, cfg.num_value_hidden, 1, cfg.layer_norm != 0); }
     void build_nets() {
         const int od = cfg.obs_dim, ad = cfg.act_dim;
-        auto make = [&](int in, const int32_t* hid, int nh, int out, bool ln) {
-            Net n;
-            int prev = in;
-            for (int i = 0; i <= nh; ++i) {
-                Layer L{};
-                L.in = prev;
-                L.out = (i < nh) ? hid[i] : out;
-                L.in_p = (i == 0) ? ((L.in + 63) & ~63) : pad16(L.in);
-                L.out_p = pad16(L.out);
-                L.ln = ln && i < nh;
-                n.layers.push_back(L);
-                prev = L.out;
-            }
-            return n;
-        };
-        auto actor = [&](int in, int out) { return make(in, cfg.actor_hidden, cfg.num_actor_hidden, out, cfg.actor_layer_norm != 0); };
-        auto value = [&](int in) { return make(in, cfg.value_hidden, cfg.num_value_hidden, 1, cfg.layer_norm != 0); };
+        const KindDesc& kd = desc();
         for (Net& n : nets) n = Net{};
-        if (kind != AgentKind::BC && kind != AgentKind::CFGRL) nets[NET_C0] = value(od + ad);
-        switch (kind) {
-            case AgentKind::FQL: nets[NET_BC] = actor(od + ad + 1, ad); nets[NET_OS] = actor(od + ad, ad); break;
-            case AgentKind::IFQL: nets[NET_BC] = actor(od + ad + 1, ad); nets[NET_OS] = value(od); break;   // value (agents/ifql.py:188-193)
-            case AgentKind::REBRAC: nets[NET_BC] = nets[NET_TA] = actor(od, ad); break;                      // actor (utils/networks.py:82-150)
-            case AgentKind::SAC: nets[NET_BC] = actor(od, 2 * pad16(ad)); break;                             // actor_net + [mean_net | log_std_net]
-            case AgentKind::BC: nets[NET_BC] = actor(od + ad + BC_EMB, ad); break;                           // policy(obs, x_t, emb(t)) (agents/bc.py:26-44)
-            case AgentKind::IQL: nets[NET_BC] = actor(od, ad); nets[NET_OS] = value(od); break;
-            case AgentKind::IQLD: nets[NET_BC] = actor(od + ad + BC_EMB + IQLD_EMBED, ad); nets[NET_OS] = value(od); break;   // iql_diffusion.py:54-67
-            case AgentKind::CFGRL: nets[NET_BC] = actor(od + gcfg.goal_dim + ad + 1, ad); break;               // actor_flow(obs, goals, x_t, t) (utils/networks.py:237-284)
-        }
+        if (has(K_CRITIC)) nets[NET_C0] = value_net(od + ad);
+        kd.nets(*this, od, ad);
         nets[NET_C1] = nets[NET_T0] = nets[NET_T1] = nets[NET_C0];
         size_t off = 0;
         auto place_enc = [&](int ei) {
@@ -851,16 +893,13 @@ struct fql_engine {
             if (ni == NET_BC) place_enc(ENC_BC);
             if (ni == NET_OS) {
                 place_enc(ENC_OS);
-                if (kind == AgentKind::SAC) { alpha_off = off; off += 4; }   // modules_alpha/log_value: one float, padded to an Adam quad
-                if (kind == AgentKind::IQL && !qcfg.const_std) { ls_off = off; off += pad16(ad); }   // modules_actor/log_stds: [act], padded to ap
-                if (kind == AgentKind::IQLD) { emb_off = off; off += 2 * IQLD_EMBED; }               // actor/Embed_0/embedding: [2, 32]
-                if (kind == AgentKind::CFGRL) { emb_off = off; off += pad16(gcfg.goal_dim); }        // modules_unc_embed/Embed_0/embedding: [1, G], padded
+                if (const size_t extra = kd.extra_off ? kd.extra_floats(*this) : 0) { this->*kd.extra_off = off; off += extra; }
                 n_train = off;
             }
             if (ni == NET_T1) place_enc(ENC_T);
         }
         n_total = off;
-        if (kind == AgentKind::REBRAC) critic_size = n_train;   // Polyak moves the critic pair and the actor (rebrac.py:131-133)
+        if (has(K_POLYAK_ALL)) critic_size = n_train;
         for (int ni = 0; ni < NUM_NETS; ++ni)
             for (const Layer& L : nets[ni].layers)
                 if (L.in_p > 1024 || L.out_p > 1024) invalid("layer widths above 1024 are not supported (got %d -> %d)", L.in, L.out);
@@ -909,7 +948,7 @@ struct fql_engine {
         const Net& n = nets[NET_BC];
         const int nh = n.nl() - 1;
         const int H = n.layers[0].out_p;
-        bool ok = kind == AgentKind::FQL && !cfg.actor_layer_norm && cfg.act_dim <= 15 && nh >= 3 && (H == 256 || H == 512);   // (the Euler chain is FQL's)
+        bool ok = has(K_CHAIN) && !cfg.actor_layer_norm && cfg.act_dim <= 15 && nh >= 3 && (H == 256 || H == 512);
         for (int l = 0; l < nh && ok; ++l) ok = n.layers[l].out == H && n.layers[l].out_p == H;
         use_chain = ok;
         if (!ok) return;
@@ -941,72 +980,36 @@ struct fql_engine {
         HIP_CHECK(hipStreamSynchronize(s));
     }
 
+    // A trainable leaf of one segment: a vector [cols] or a matrix [rows, cols] at `off`, padded to rp x cp.  It takes the next train id
+    // (n_train_leaves counts them while build_leaves runs).
+    void add_leaf(const std::string& name, bool matrix, int rows, int cols, size_t off, int rp, int cp) {
+        Leaf lf;
+        lf.name = name;
+        int d = 0;
+        if (matrix) lf.shape[d++] = rows;
+        lf.shape[d++] = cols;
+        lf.ndim = d;
+        for (int k = d; k < 4; ++k) lf.shape[k] = 1;
+        lf.segs.push_back(Segment{off, matrix ? rows : 1, cols, matrix ? rp : 1, cp});
+        lf.trainable = true;
+        lf.train_id = n_train_leaves++;
+        leaves.push_back(lf);
+    }
     void build_leaves() {
         leaves.clear();
-        struct Mod { const char* name; const char* sub; int n0, n1; bool train; int enc; bool actor = false; };
-        const Mod fql_mods[4] = {{"modules_actor_bc_flow", "mlp", NET_BC, -1, true, ENC_BC},
-                                 {"modules_actor_onestep_flow", "mlp", NET_OS, -1, true, ENC_OS},
-                                 {"modules_critic", "value_net", NET_C0, NET_C1, true, ENC_C},
-                                 {"modules_target_critic", "value_net", NET_T0, NET_T1, false, ENC_T}};
-        // IFQL (agents/ifql.py:215-225): the value net is a 1-member Value, so its leaves are unstacked
-        const Mod ifql_mods[4] = {{"modules_actor_flow", "mlp", NET_BC, -1, true, ENC_BC},
-                                  {"modules_critic", "value_net", NET_C0, NET_C1, true, ENC_C},
-                                  {"modules_target_critic", "value_net", NET_T0, NET_T1, false, ENC_T},
-                                  {"modules_value", "value_net", NET_OS, -1, true, ENC_OS}};
-        // ReBRAC (agents/rebrac.py:199-213): Actor modules hold actor_net/Dense_0..nh-1 (+ LayerNorm_i) and mean_net (the last layer)
-        const Mod rebrac_mods[4] = {{"modules_actor", "actor_net", NET_BC, -1, true, ENC_BC, true},
-                                    {"modules_critic", "value_net", NET_C0, NET_C1, true, ENC_C},
-                                    {"modules_target_actor", "actor_net", NET_TA, -1, false, ENC_BC, true},
-                                    {"modules_target_critic", "value_net", NET_T0, NET_T1, false, ENC_T}};
-        // SAC (agents/sac.py:170-196): Actor (actor_net, log_std_net, mean_net), the 0-d LogParam (n0 = -1), critic, target critic
-        const Mod sac_mods[4] = {{"modules_actor", "actor_net", NET_BC, -1, true, ENC_BC, true},
-                                 {"modules_alpha", "", -1, -1, true, ENC_BC},
-                                 {"modules_critic", "value_net", NET_C0, NET_C1, true, ENC_C},
-                                 {"modules_target_critic", "value_net", NET_T0, NET_T1, false, ENC_T}};
-        // IQL (agents/iql.py:222-227): Actor (actor_net, log_stds with const_std = 0, mean_net), critic, target critic, the 1-member value
-        const Mod iql_mods[4] = {{"modules_actor", "actor_net", NET_BC, -1, true, ENC_BC, true},
-                                 {"modules_critic", "value_net", NET_C0, NET_C1, true, ENC_C},
-                                 {"modules_target_critic", "value_net", NET_T0, NET_T1, false, ENC_T},
-                                 {"modules_value", "value_net", NET_OS, -1, true, ENC_OS}};
-        // IQL-diffusion (agents/iql_diffusion.py:87-91): four bare TrainStates, no ModuleDict; the actor's leaves are BC's plus the embedding
-        const Mod iqld_mods[3] = {{"critic", "value_net", NET_C0, NET_C1, true, ENC_C},
-                                  {"target_critic", "value_net", NET_T0, NET_T1, false, ENC_T},
-                                  {"value", "value_net", NET_OS, -1, true, ENC_OS}};
-        // CFGRL (agents/cfgrl.py:143-156): one ModuleDict, actor_flow and the [1, G] embedding behind it
-        const Mod cfgrl_mods[1] = {{"modules_actor_flow", "mlp", NET_BC, -1, true, ENC_BC}};
-        const Mod* mods = nullptr;   // BC: no modules, the leaves of one bare net
-        int nmods = 4;
-        const char* bare = nullptr;  // prefix of the bare policy net's leaves (BC: none, IQL-diffusion: its `actor` field)
-        switch (kind) {
-            case AgentKind::FQL: mods = fql_mods; break;
-            case AgentKind::IFQL: mods = ifql_mods; break;
-            case AgentKind::REBRAC: mods = rebrac_mods; break;
-            case AgentKind::SAC: mods = sac_mods; break;
-            case AgentKind::BC: bare = ""; nmods = 0; break;
-            case AgentKind::IQL: mods = iql_mods; break;
-            case AgentKind::IQLD: bare = "actor/"; mods = iqld_mods; nmods = 3; break;
-            case AgentKind::CFGRL: mods = cfgrl_mods; nmods = 1; break;
-        }
-        int tid = 0;
+        const KindDesc& kd = desc();
+        const char* bare = kd.bare;
+        auto special = [&](LeafSite at, const Mod* m) { return kd.special_leaves && kd.special_leaves(*this, at, m); };
+        n_train_leaves = 0;
         if (bare) {   // agents/bc.py:26-44: a bare TrainState: Dense_0 (the head), then MLP_0/Dense_i and MLP_0/LayerNorm_i (jax dict order)
             const Net& n0 = nets[NET_BC];
             auto add = [&](const std::string& name, bool matrix, int rows, int cols, size_t o0, int rp, int cp) {
-                Leaf lf;
-                lf.name = bare + name;
-                int d = 0;
-                if (matrix) lf.shape[d++] = rows;
-                lf.shape[d++] = cols;
-                lf.ndim = d;
-                for (int k = d; k < 4; ++k) lf.shape[k] = 1;
-                lf.segs.push_back(Segment{o0, matrix ? rows : 1, cols, matrix ? rp : 1, cp});
-                lf.trainable = true;
-                lf.train_id = tid++;
-                leaves.push_back(lf);
+                add_leaf(bare + name, matrix, rows, cols, o0, rp, cp);
             };
             const Layer& hd = n0.layers.back();
             add("Dense_0/bias", false, 1, hd.out, hd.b, 1, hd.out_p);
             add("Dense_0/kernel", true, hd.in, hd.out, hd.w, hd.in_p, hd.out_p);
-            if (kind == AgentKind::IQLD) add("Embed_0/embedding", true, 2, IQLD_EMBED, emb_off, 2, IQLD_EMBED);   // nn.Embed(2, 32): sorts behind Dense_0
+            special(LS_BARE_HEAD, nullptr);
             for (int i = 0; i + 1 < n0.nl(); ++i) {
                 const Layer& a = n0.layers[i];
                 add("MLP_0/Dense_" + std::to_string(i) + "/bias", false, 1, a.out, a.b, 1, a.out_p);
@@ -1019,19 +1022,9 @@ struct fql_engine {
                 add("MLP_0/LayerNorm_" + std::to_string(i) + "/scale", false, 1, a.out, a.g, 1, a.out_p);
             }
         }
-        for (int mi = 0; mi < (mods ? nmods : 0); ++mi) {
-            const Mod& m = mods[mi];
-            if (m.n0 < 0) {   // modules_alpha/log_value: shape ()
-                Leaf lf;
-                lf.name = std::string(m.name) + "/log_value";
-                lf.ndim = 0;
-                for (int k = 0; k < 4; ++k) lf.shape[k] = 1;
-                lf.segs.push_back(Segment{alpha_off, 1, 1, 1, 4});
-                lf.trainable = true;
-                lf.train_id = tid++;
-                leaves.push_back(lf);
-                continue;
-            }
+        for (int mi = 0; mi < kd.nmods; ++mi) {
+            const Mod& m = kd.mods[mi];
+            if (m.n0 < 0) { special(LS_NO_NET, &m); continue; }
             const Net& n0 = nets[m.n0];
             const bool ens = m.n1 >= 0;
             if (visual) {
@@ -1045,7 +1038,7 @@ struct fql_engine {
                     for (int k = 0; k < 4; ++k) lf.shape[k] = k < lf.ndim ? shape[k] : 1;
                     lf.segs.push_back(Segment{off, rows, cols, rows, cols});
                     lf.trainable = m.train;
-                    lf.train_id = m.train ? tid++ : -1;
+                    lf.train_id = m.train ? n_train_leaves++ : -1;
                     leaves.push_back(lf);
                 };
                 const std::string eb = std::string(m.name) + "/encoder/";
@@ -1071,7 +1064,7 @@ struct fql_engine {
                 lf.segs.push_back(Segment{o0, matrix ? rows : 1, cols, matrix ? rp : 1, cp});
                 if (ens) lf.segs.push_back(Segment{o1, matrix ? rows : 1, cols, matrix ? rp : 1, cp});
                 lf.trainable = m.train;
-                lf.train_id = m.train ? tid++ : -1;
+                lf.train_id = m.train ? n_train_leaves++ : -1;
                 leaves.push_back(lf);
             };
             const std::string base = std::string(m.name) + "/" + m.sub + "/";
@@ -1089,36 +1082,14 @@ struct fql_engine {
                 add(base + "LayerNorm_" + std::to_string(i) + "/bias", false, 1, a.out, a.be, b ? b->be : 0, 1, a.out_p);
                 add(base + "LayerNorm_" + std::to_string(i) + "/scale", false, 1, a.out, a.g, b ? b->g : 0, 1, a.out_p);
             }
-            if (m.actor && kind == AgentKind::SAC) {   // the two heads: column blocks [0, ap) and [ap, 2 ap) of the last layer, each read back as [H, act] / [act]
-                const Layer& a = n0.layers.back();
-                const int ad = cfg.act_dim, ap = pad16(ad);
-                for (const char* head : {"log_std_net", "mean_net"}) {
-                    const size_t c0 = std::strcmp(head, "mean_net") == 0 ? 0 : (size_t)ap;
-                    const std::string hb = std::string(m.name) + "/" + head + "/";
-                    add(hb + "bias", false, 1, ad, a.b + c0, 0, 1, ap);
-                    add(hb + "kernel", true, a.in, ad, a.w + c0, 0, a.in_p, a.out_p);
-                    leaves.back().segs[0].chunk_w = ap;
-                }
-            } else if (m.actor) {
-                if (kind == AgentKind::IQL && !qcfg.const_std)   // "log_stds" sorts between actor_net and mean_net
-                    add(std::string(m.name) + "/log_stds", false, 1, cfg.act_dim, ls_off, 0, 1, pad16(cfg.act_dim));
+            if (m.actor && !special(LS_ACTOR_HEAD, &m)) {
                 const Layer& a = n0.layers.back();
                 const std::string hb = std::string(m.name) + "/mean_net/";
                 add(hb + "bias", false, 1, a.out, a.b, 0, 1, a.out_p);
                 add(hb + "kernel", true, a.in, a.out, a.w, 0, a.in_p, a.out_p);
             }
         }
-        if (kind == AgentKind::CFGRL) {   // nn.Embed(1, goal_dim): "modules_unc_embed" sorts behind "modules_actor_flow"
-            Leaf lf;
-            lf.name = "modules_unc_embed/Embed_0/embedding";
-            lf.ndim = 2;
-            lf.shape[0] = 1; lf.shape[1] = gcfg.goal_dim; lf.shape[2] = lf.shape[3] = 1;
-            lf.segs.push_back(Segment{emb_off, 1, gcfg.goal_dim, 1, pad16(gcfg.goal_dim)});
-            lf.trainable = true;
-            lf.train_id = tid++;
-            leaves.push_back(lf);
-        }
-        n_train_leaves = tid;
+        special(LS_LAST, nullptr);
         if (n_train_leaves > 256) invalid("too many trainable leaves (%d)", n_train_leaves);
         // Adam chunks: contiguous pieces of one leaf, <= 4096 elements
         std::vector<AdamChunk> ch;
@@ -1141,16 +1112,7 @@ struct fql_engine {
         for (const AdamChunk& c : ch) range[c.leaf + 1]++;
         for (int i = 0; i < n_train_leaves; ++i) range[i + 1] += range[i];
         {   // leaves (and so chunks) are ordered module by module: actor_bc_flow, actor_onestep_flow, critic
-            static const char* const trained[kNumKinds][3] = {
-                {"modules_actor_bc_flow/", "modules_actor_onestep_flow/", "modules_critic/"},
-                {"modules_actor_flow/", "modules_value/", "modules_critic/"},
-                {"modules_actor/", "modules_critic/", "modules_critic/"},   // (ReBRAC, two trained modules: the critic's range twice)
-                {"modules_actor/", "modules_alpha/", "modules_critic/"},
-                {nullptr, nullptr, nullptr},                                // (BC, one module: every chunk)
-                {"modules_actor/", "modules_value/", "modules_critic/"},
-                {"actor/", "value/", "critic/"},
-                {nullptr, nullptr, nullptr}};                               // (CFGRL, one TrainState: every chunk)
-            const char* const* mods = trained[(int)kind];
+            const char* const* mods = kd.trained;
             for (int m = 0; m < 3; ++m) {
                 if (!mods[m]) { mod_chunk0[m] = 0; mod_chunkn[m] = n_chunks; continue; }
                 int lo = 1 << 30, hi = -1;
@@ -1194,17 +1156,16 @@ struct fql_engine {
     void init_params() {
         // utils/networks.py:9-11 Glorot-uniform kernels; flax Dense bias 0; LayerNorm scale 1 / bias 0;
         // agents/fql.py:241-242 target := critic.  (Host RNG: JAX's threefry init is not reproducible.)
+        const KindDesc& kd = desc();
         std::vector<float> h(n_total, 0.f);
         std::mt19937_64 gen(seed * 0x9E3779B97F4A7C15ull + 0x1234567ull);
         for (int ni = 0; ni <= NET_OS; ++ni)
             for (const Layer& L : nets[ni].layers) {
-                // ReBRAC's mean_net: variance_scaling(actor_fc_scale, fan_avg, uniform) (utils/networks.py:9-11,117)
+                // an Actor's mean_net: variance_scaling(the row's scale, fan_avg, uniform) (utils/networks.py:9-11,117)
                 const bool actor_head = ni == NET_BC && &L == &nets[ni].layers.back();
-                const double scale = !actor_head ? 1.0 : kind == AgentKind::REBRAC ? (double)rcfg.actor_fc_scale
-                                     : kind == AgentKind::IQL ? 1e-2   // Actor.final_fc_init_scale (utils/networks.py:106)
-                                                              : 1.0;
-                if ((kind == AgentKind::BC || kind == AgentKind::IQLD) && actor_head) {
-                    // BC's Dense_0 is a bare nn.Dense (agents/bc.py:43): flax's default lecun_normal = variance_scaling(1, fan_in,
+                const double scale = actor_head && kd.head_scale ? kd.head_scale(*this) : 1.0;
+                if (actor_head && kd.head_init == HI_LECUN_TRUNC) {
+                    // a bare nn.Dense (agents/bc.py:43): flax's default lecun_normal = variance_scaling(1, fan_in,
                     // truncated_normal): N(0, 1) truncated to [-2, 2], scaled by sqrt(1 / fan_in) / 0.87962566103423978
                     const double sd = std::sqrt(1.0 / (double)L.in) / 0.87962566103423978;
                     std::normal_distribution<double> Nd(0.0, 1.0);
@@ -1216,10 +1177,10 @@ struct fql_engine {
                         }
                     continue;
                 }
-                if (kind == AgentKind::SAC && actor_head) {
+                if (actor_head && kd.head_init == HI_TWO_HEADS) {
                     // SAC's mean_net and log_std_net: variance_scaling(actor_fc_scale, fan_avg, uniform), [H, act] each (utils/networks.py:9-11,111-113)
                     const int ad = cfg.act_dim, ap = pad16(ad);
-                    const double lim = std::sqrt(6.0 * (double)scfg.actor_fc_scale / (double)(L.in + ad));
+                    const double lim = std::sqrt(6.0 * scale / (double)(L.in + ad));
                     std::uniform_real_distribution<double> U(-lim, lim);
                     for (int c0 : {0, ap})
                         for (int r = 0; r < L.in; ++r)
@@ -1247,18 +1208,10 @@ struct fql_engine {
                 std::uniform_real_distribution<double> U(-lim, lim);
                 for (size_t i = 0; i < (size_t)D.in * D.out; ++i) h[D.w + i] = (float)U(gen);
             }
-        if (kind == AgentKind::IQLD) {
-            // nn.Embed's default init: variance_scaling(1.0, 'fan_in', 'normal', out_axis=0) on [2, 32].  With in_axis = -2 and out_axis = 0
-            // both name axis 0: in_size = out_size = 2, receptive field = 64 / (2 * 2) = 16, fan_in = 2 * 16 = 32 (the feature count);
-            // 'normal' is the untruncated N(0, 1 / fan_in)
-            std::normal_distribution<double> Nd(0.0, std::sqrt(1.0 / (double)IQLD_EMBED));
-            for (int i = 0; i < 2 * IQLD_EMBED; ++i) h[emb_off + i] = (float)Nd(gen);
-        }
-        if (kind == AgentKind::CFGRL) {
-            // nn.Embed(1, G): variance_scaling(1.0, 'fan_in', 'normal', out_axis=0) on [1, G].  By the derivation above in_size = out_size = 1,
-            // receptive field = G, fan_in = G: the untruncated N(0, 1 / G)
-            std::normal_distribution<double> Nd(0.0, std::sqrt(1.0 / (double)gcfg.goal_dim));
-            for (int i = 0; i < gcfg.goal_dim; ++i) h[emb_off + i] = (float)Nd(gen);
+        if (kd.embed_init) {   // nn.Embed's default init, variance_scaling(1.0, 'fan_in', 'normal', out_axis=0): the untruncated N(0, 1 / fan_in)
+            const EmbedInit em = kd.embed_init(*this);
+            std::normal_distribution<double> Nd(0.0, std::sqrt(1.0 / (double)em.fan_in));
+            for (int i = 0; i < em.n; ++i) h[emb_off + i] = (float)Nd(gen);
         }
         std::memcpy(h.data() + n_train, h.data(), critic_size * sizeof(float));
         HIP_CHECK(hipMemcpy(P, h.data(), n_total * sizeof(float), hipMemcpyHostToDevice));
@@ -3116,8 +3069,6 @@ struct fql_engine {
         X_bc = dalloc(W, (size_t)B * nets[NET_BC].in_p());
         vel = dalloc(W, (size_t)B * ap);
         w_rew = dalloc(W, B); w_mask = dalloc(W, B);
-        X_os = X_eu = X_c2 = X_ct = X_e0 = C0 = Vpart = w_act = tgt = nullptr;
-        fused_euler = euler_finish_fused = false;
         p_v = make_pass(W, NET_OS, 2 * B, X_v, true, false);
         p_bc = make_pass(W, NET_BC, B, X_bc, true, false);
         for (int e = 0; e < 2; ++e) {
@@ -3213,12 +3164,11 @@ struct fql_engine {
         const int ap = pad16(cfg.act_dim);
         const int inp_a = nets[NET_BC].in_p(), inp_c = nets[NET_C0].in_p();
         auto& W = ws_allocs;
+        in_nact = dalloc(W, (size_t)B * cfg.act_dim);   // staging of a host batch's next_actions
         X_c1 = dalloc(W, (size_t)B * inp_c); X_t = dalloc(W, (size_t)B * inp_c); X_q = dalloc(W, (size_t)B * inp_c);
         X_a = dalloc(W, (size_t)B * inp_a); X_ta = dalloc(W, (size_t)B * inp_a);
         w_act = dalloc(W, (size_t)B * ap); w_nact = dalloc(W, (size_t)B * ap); w_noise = dalloc(W, (size_t)B * ap);
         w_rew = dalloc(W, B); w_mask = dalloc(W, B);
-        X_os = X_bc = X_eu = X_c2 = X_ct = X_e0 = C0 = Vpart = vel = tgt = X_v = nullptr;
-        fused_euler = euler_finish_fused = false;
         p_a = make_pass(W, NET_BC, B, X_a, true, false);
         p_ta = make_pass(W, NET_TA, B, X_ta, false, false);
         for (int e = 0; e < 2; ++e) {
@@ -3301,8 +3251,6 @@ struct fql_engine {
         X_a = dalloc(W, (size_t)2 * B * inp_a);
         w_eps = dalloc(W, (size_t)2 * B * ap); lp_buf = dalloc(W, (size_t)2 * B);
         w_rew = dalloc(W, B); w_mask = dalloc(W, B);
-        X_os = X_bc = X_eu = X_c2 = X_ct = X_e0 = C0 = Vpart = vel = tgt = X_v = X_ta = w_act = nullptr;
-        fused_euler = euler_finish_fused = false;
         p_a = make_pass(W, NET_BC, 2 * B, X_a, true, false);
         for (int e = 0; e < 2; ++e) {
             p_c1[e] = make_pass(W, NET_C0 + e, B, X_c1, true, false);
@@ -3346,8 +3294,6 @@ struct fql_engine {
         auto& W = ws_allocs;
         X_bc = dalloc(W, (size_t)B * nets[NET_BC].in_p());
         vel = dalloc(W, (size_t)B * ap);
-        X_os = X_eu = X_c1 = X_c2 = X_ct = X_e0 = C0 = Vpart = w_act = tgt = w_rew = w_mask = nullptr;
-        fused_euler = euler_finish_fused = false;
         p_bc = make_pass(W, NET_BC, B, X_bc, true, false);
         build_bc_program(prog_full, true);
         build_bc_program(prog_loss, false);
@@ -3401,34 +3347,28 @@ struct fql_engine {
         cf_mask = (unsigned char*)dalloc(W, (size_t)(2 * B + 3) / 4);
         cf_rows = (int64_t*)dalloc(W, (size_t)2 * 2 * B * 2);
         cf_draws = (uint32_t*)dalloc(W, (size_t)2 * CFGRL_NUM_DRAWS * B);
-        X_os = X_eu = X_c1 = X_c2 = X_ct = X_e0 = C0 = Vpart = w_act = tgt = w_rew = w_mask = nullptr;
-        fused_euler = euler_finish_fused = false;
         p_bc = make_pass(W, NET_BC, B, X_bc, true, false);
         build_cfgrl_program(prog_full, true);
         build_cfgrl_program(prog_loss, false);
         finish_programs({&prog_full, &prog_loss});
     }
 
-    // multiply-accumulates of one BC update per batch row, algorithmic: forward + backward without the input gradient
-    int64_t bc_macs() const {
-        int64_t m = 0;
-        for (const Layer& L : nets[NET_BC].layers) m += (int64_t)L.in * L.out;
-        return (3 * m - (int64_t)nets[NET_BC].layers[0].in * nets[NET_BC].layers[0].out) * (int64_t)B;
-    }
+    // multiply-accumulates per row of a net's forward, algorithmic (full GEMM shapes at the logical widths), and of its first layer alone
+    // (a backward pass without the input gradient costs 2 net_macs - first_macs)
+    static int64_t net_macs(const Net& n) { int64_t m = 0; for (const Layer& L : n.layers) m += (int64_t)L.in * L.out; return m; }
+    static int64_t first_macs(const Net& n) { return (int64_t)n.layers[0].in * n.layers[0].out; }
 
-    // multiply-accumulates of one SAC update per batch row, algorithmic (full GEMM shapes at the logical widths; the heads are H x 2 act)
+    // multiply-accumulates of one BC update per batch row, algorithmic: forward + backward without the input gradient
+    int64_t bc_macs() const { return (3 * net_macs(nets[NET_BC]) - first_macs(nets[NET_BC])) * (int64_t)B; }
+
+    // multiply-accumulates of one SAC update per batch row, algorithmic (the heads are H x 2 act, not the padded 2 ap of the stored layer)
     int64_t sac_macs() const {
-        auto macs = [&](const Net& n) {
-            int64_t m = 0;
-            for (const Layer& L : n.layers) m += (int64_t)L.in * (&L == &n.layers.back() && &n == &nets[NET_BC] ? 2 * cfg.act_dim : L.out);
-            return m;
-        };
-        auto first = [&](const Net& n) { return (int64_t)n.layers[0].in * n.layers[0].out; };
-        const int64_t ac = macs(nets[NET_BC]), cr = macs(nets[NET_C0]);
+        const Layer& heads = nets[NET_BC].layers.back();
+        const int64_t ac = net_macs(nets[NET_BC]) - (int64_t)heads.in * (heads.out - 2 * cfg.act_dim), cr = net_macs(nets[NET_C0]);
         // actor on 2B rows; target pair; critic pair forward + backward without the input gradient
-        int64_t m = 2 * ac + 2 * cr + 2 * cr + 2 * (2 * cr - first(nets[NET_C0]));
+        int64_t m = 2 * ac + 2 * cr + 2 * cr + 2 * (2 * cr - first_macs(nets[NET_C0]));
         // the pair on [obs | a] forward + input gradient; actor backward on the obs rows without the input gradient
-        m += 2 * cr + 2 * cr + (2 * ac - first(nets[NET_BC]));
+        m += 2 * cr + 2 * cr + (2 * ac - first_macs(nets[NET_BC]));
         return m * (int64_t)B;
     }
 
@@ -3540,8 +3480,6 @@ struct fql_engine {
         w_act = dalloc(W, (size_t)B * ap); w_eps = dalloc(W, (size_t)B * ap); ls_part = dalloc(W, (size_t)B * ap);
         lp_buf = dalloc(W, B); se_buf = dalloc(W, B);
         w_rew = dalloc(W, B); w_mask = dalloc(W, B);
-        X_os = X_bc = X_eu = X_c2 = X_ct = X_e0 = C0 = Vpart = vel = tgt = X_t = X_ta = nullptr;
-        fused_euler = euler_finish_fused = false;
         p_v = make_pass(W, NET_OS, 2 * B, X_v, true, false);
         p_a = make_pass(W, NET_BC, B, X_a, true, false);
         for (int e = 0; e < 2; ++e) {
@@ -3555,11 +3493,9 @@ struct fql_engine {
     }
     // multiply-accumulates of one IQL update per batch row, algorithmic (full GEMM shapes at the logical widths)
     int64_t iql_macs() const {
-        auto macs = [&](const Net& n) { int64_t m = 0; for (const Layer& L : n.layers) m += (int64_t)L.in * L.out; return m; };
-        auto first = [&](const Net& n) { return (int64_t)n.layers[0].in * n.layers[0].out; };
-        const int64_t va = macs(nets[NET_OS]), ac = macs(nets[NET_BC]), cr = macs(nets[NET_C0]);
+        const int64_t va = net_macs(nets[NET_OS]), ac = net_macs(nets[NET_BC]), cr = net_macs(nets[NET_C0]);
         // value on 2B rows + its backward on B; target pair; critic pair forward + backward (no input gradient); actor forward + backward
-        int64_t m = 2 * va + (2 * va - first(nets[NET_OS])) + 2 * cr + 2 * cr + 2 * (2 * cr - first(nets[NET_C0])) + ac + (2 * ac - first(nets[NET_BC]));
+        int64_t m = 2 * va + (2 * va - first_macs(nets[NET_OS])) + 2 * cr + 2 * cr + 2 * (2 * cr - first_macs(nets[NET_C0])) + ac + (2 * ac - first_macs(nets[NET_BC]));
         if (qcfg.actor_loss == 1) m += 2 * cr + 2 * cr;   // ddpgbc: the pair on [obs | q_actions] forward + input gradient
         return m * (int64_t)B;
     }
@@ -3672,8 +3608,6 @@ struct fql_engine {
         vel = dalloc(W, (size_t)B * ap);
         w_rew = dalloc(W, B); w_mask = dalloc(W, B); w_lw = dalloc(W, B);
         rows_buf = dalloc(W, (size_t)6 * B);
-        X_os = X_eu = X_c2 = X_ct = X_e0 = C0 = Vpart = w_act = tgt = nullptr;
-        fused_euler = euler_finish_fused = false;
         p_v = make_pass(W, NET_OS, 2 * B, X_v, true, false);
         p_bc = make_pass(W, NET_BC, 2 * B, X_bc, true, false);
         for (int e = 0; e < 2; ++e) {
@@ -3692,50 +3626,40 @@ struct fql_engine {
     }
     // multiply-accumulates of one IQL-diffusion update per batch row, algorithmic (full GEMM shapes at the logical widths)
     int64_t iqld_macs(bool upd_critic, bool upd_actor) const {
-        auto macs = [&](const Net& n) { int64_t m = 0; for (const Layer& L : n.layers) m += (int64_t)L.in * L.out; return m; };
-        auto first = [&](const Net& n) { return (int64_t)n.layers[0].in * n.layers[0].out; };
-        const int64_t va = macs(nets[NET_OS]), ac = macs(nets[NET_BC]), cr = macs(nets[NET_C0]);
+        const int64_t va = net_macs(nets[NET_OS]), ac = net_macs(nets[NET_BC]), cr = net_macs(nets[NET_C0]);
         const bool te = dcfg.target_extraction != 0;
         int64_t m = 0;
         if (upd_critic || upd_actor) m += 2 * va;                                  // value on 2B rows
         if (upd_critic || (upd_actor && te)) m += 2 * cr;                          // target pair
         if (upd_critic || (upd_actor && !te)) m += 2 * cr;                         // critic pair
-        if (upd_critic) m += (2 * va - first(nets[NET_OS])) + 2 * (2 * cr - first(nets[NET_C0]));
-        if (upd_actor) m += 2 * ac + 2 * (2 * ac - first(nets[NET_BC]));           // the policy on 2B rows, forward + backward
+        if (upd_critic) m += (2 * va - first_macs(nets[NET_OS])) + 2 * (2 * cr - first_macs(nets[NET_C0]));
+        if (upd_actor) m += 2 * ac + 2 * (2 * ac - first_macs(nets[NET_BC]));      // the policy on 2B rows, forward + backward
         return m * (int64_t)B;
     }
 
     // multiply-accumulates of one ReBRAC update per batch row, algorithmic (full GEMM shapes)
     int64_t rebrac_macs(bool full_update) const {
-        auto macs = [&](const Net& n) { int64_t m = 0; for (const Layer& L : n.layers) m += (int64_t)L.in * L.out; return m; };
-        auto first = [&](const Net& n) { return (int64_t)n.layers[0].in * n.layers[0].out; };
-        const int64_t ac = macs(nets[NET_BC]), cr = macs(nets[NET_C0]);
+        const int64_t ac = net_macs(nets[NET_BC]), cr = net_macs(nets[NET_C0]);
         // target actor + target pair forward; critic pair forward + backward without the input gradient
-        int64_t m = ac + 2 * cr + 2 * cr + 2 * (2 * cr - first(nets[NET_C0]));
+        int64_t m = ac + 2 * cr + 2 * cr + 2 * (2 * cr - first_macs(nets[NET_C0]));
         // actor forward; the pair on [obs | a] forward + input gradient; actor backward without the input gradient
-        if (full_update) m += ac + 2 * cr + 2 * cr + (2 * ac - first(nets[NET_BC]));
+        if (full_update) m += ac + 2 * cr + 2 * cr + (2 * ac - first_macs(nets[NET_BC]));
         return m * (int64_t)B;
     }
 
-    int64_t macs_per_update() const {
-        auto macs = [&](const Net& n) { int64_t m = 0; for (const Layer& L : n.layers) m += (int64_t)L.in * L.out; return m; };
-        auto first = [&](const Net& n) { return (int64_t)n.layers[0].in * n.layers[0].out; };
-        switch (kind) {
-            case AgentKind::REBRAC: return rebrac_macs(true);
-            case AgentKind::SAC: return sac_macs();
-            case AgentKind::BC: case AgentKind::CFGRL: return bc_macs();
-            case AgentKind::IQL: return iql_macs();
-            case AgentKind::IQLD: return iqld_macs(true, true);
-            default: break;
-        }
-        const int64_t os = macs(nets[NET_OS]), bc = macs(nets[NET_BC]), cr = macs(nets[NET_C0]);
-        if (kind == AgentKind::IFQL) {   // value on 2B rows + its backward on B; target pair; critic pair forward + backward (no input gradient); actor_flow forward + backward
-            const int64_t fwd = 2 * os + 4 * cr + bc;
-            const int64_t bwd = (2 * os - first(nets[NET_OS])) + 2 * (2 * cr - first(nets[NET_C0])) + (2 * bc - first(nets[NET_BC]));
-            return (fwd + bwd) * (int64_t)B;
-        }
+    int64_t macs_per_update() const { return desc().macs(*this); }   // (of the kind's full update)
+    // multiply-accumulates of one IFQL update: value on 2B rows + its backward on B; target pair; critic pair forward + backward (no input
+    // gradient); actor_flow forward + backward
+    int64_t ifql_macs() const {
+        const int64_t os = net_macs(nets[NET_OS]), bc = net_macs(nets[NET_BC]), cr = net_macs(nets[NET_C0]);
+        const int64_t fwd = 2 * os + 4 * cr + bc;
+        const int64_t bwd = (2 * os - first_macs(nets[NET_OS])) + 2 * (2 * cr - first_macs(nets[NET_C0])) + (2 * bc - first_macs(nets[NET_BC]));
+        return (fwd + bwd) * (int64_t)B;
+    }
+    int64_t fql_macs() const {
+        const int64_t os = net_macs(nets[NET_OS]), bc = net_macs(nets[NET_BC]), cr = net_macs(nets[NET_C0]);
         const int64_t fwd = 3 * os + (cfg.flow_steps + 1) * bc + 6 * cr;
-        const int64_t bwd = 2 * (2 * cr - first(nets[NET_C0])) + (2 * bc - first(nets[NET_BC])) + (2 * os - first(nets[NET_OS])) + 2 * cr;
+        const int64_t bwd = 2 * (2 * cr - first_macs(nets[NET_C0])) + (2 * bc - first_macs(nets[NET_BC])) + (2 * os - first_macs(nets[NET_OS])) + 2 * cr;
         int64_t total = (fwd + bwd) * (int64_t)B;
         if (visual) {
             // encoder: 5 distinct forward image-batches per update (onestep on obs and next_obs, critic, target, bc_flow; the
@@ -3783,16 +3707,11 @@ struct fql_engine {
         in_act = dalloc(W, (size_t)B * ad); in_rew = dalloc(W, B); in_mask = dalloc(W, B);
         for (int i = 0; i < 5; ++i) in_noise[i] = dalloc(W, (size_t)B * ad);
         in_idx = (int64_t*)dalloc(W, (size_t)B * 4);   // [2][B]: indices in use, staging of host indices (frames path)
-        switch (kind) {
-            case AgentKind::FQL: break;   // below
-            case AgentKind::IFQL: build_ifql_workspace(); return;
-            case AgentKind::REBRAC: in_nact = dalloc(W, (size_t)B * ad); build_rebrac_workspace(); return;
-            case AgentKind::SAC: build_sac_workspace(); return;
-            case AgentKind::BC: build_bc_workspace(); return;
-            case AgentKind::IQL: build_iql_workspace(); return;
-            case AgentKind::IQLD: build_iqld_workspace(); return;
-            case AgentKind::CFGRL: build_cfgrl_workspace(); return;
-        }
+        (this->*desc().workspace)();
+    }
+    void build_fql_workspace() {
+        const int ad = cfg.act_dim;
+        auto& W = ws_allocs;
         const int inp_c = nets[NET_OS].in_p(), inp_b = nets[NET_BC].in_p();
         X_os = dalloc(W, (size_t)3 * B * inp_c); X_bc = dalloc(W, (size_t)B * inp_b); X_eu = dalloc(W, (size_t)B * inp_b);
         X_c1 = dalloc(W, (size_t)B * inp_c); X_c2 = dalloc(W, (size_t)B * inp_c); X_ct = dalloc(W, (size_t)B * inp_c);
@@ -4008,7 +3927,7 @@ struct fql_engine {
         if (!nz) return;
         const int given = (nz->eps1 ? NZ_EPS1 : 0) | (nz->x0 ? NZ_X0 : 0) | (nz->t ? NZ_T : 0) | (nz->z ? NZ_Z : 0) | (nz->eps2 ? NZ_EPS2 : 0);
         if (given & ~desc().noise_reads) invalid("%s", desc().noise_refusal);
-        if ((kind == AgentKind::BC || kind == AgentKind::IQLD) && nz->t && !is_device_ptr(nz->t))   // t = k / S on the grid (device pointers are the caller's to keep on it: read as round(t S))
+        if (has(K_TIME_TABLE) && nz->t && !is_device_ptr(nz->t))   // t = k / S on the grid (device pointers are the caller's to keep on it: read as round(t S))
             for (int b = 0; b < B; ++b) {
                 const float ts = nz->t[b] * (float)bc_steps;
                 if (!(ts >= -1e-3f && ts <= (float)bc_steps + 1e-3f) || std::fabs(ts - std::nearbyint(ts)) > 1e-3f)
@@ -4028,7 +3947,7 @@ struct fql_engine {
         if (lo < 0 || hi > ds_size || lo >= hi) invalid("bad sampling range [%lld, %lld) for dataset of %lld rows", (long long)lo, (long long)hi, (long long)ds_size);
         SrcDesc d{};
         d.obs = ds_obs; d.act = ds_act; d.rew = ds_rew; d.mask = ds_mask; d.nobs = ds_nobs;
-        if (kind == AgentKind::REBRAC) { d.nact = ds_act; d.nact_rows = ds_size; }   // utils/datasets.py:96-100: actions[min(idx + 1, size - 1)], the whole dataset's size
+        if (has(K_NEXT_ACTIONS)) { d.nact = ds_act; d.nact_rows = ds_size; }   // utils/datasets.py:96-100: actions[min(idx + 1, size - 1)], the whole dataset's size
         if (idx) {
             if (is_device_ptr(idx)) d.idx = idx;
             else {
@@ -4137,21 +4056,13 @@ struct fql_engine {
     // ---------------------------------------------------------------------------------------
     // eval paths
     // ---------------------------------------------------------------------------------------
-    // What differs between the hoisted flow samplers (DESIGN.md sections 16 and 18-20): BC's, and the two CFG kinds' with a scalar cfg
-    // or, as a sweep, with one guidance weight per row.
-    struct FlowShape {
-        int halves;      // 1: BC, one block of n_pad rows.  2: the CFG kinds, rows [0, half) the positive / conditional pass, [half, n_pad) the unconditional one
-        bool shared_x;   // the halves share X = [obs | 0] and C0 (IQL-diffusion); CFGRL's differ in the goal columns
-        int tables;      // step-bias rows per step: 1 BC [S, H], 2 IQL-diffusion [S, 2, H], 0 CFGRL (t is an argument of its layer-0 kernels)
-        int S;           // Euler steps
-        int goal_dim;    // CFGRL: the goal block in front of the action rows of W0, and goals to stage; else 0
-        bool sweep;      // the weights come per row from the workspace (cfgs), and the combine of step i - 1 rides in front of layer 0 of step i
-    };
-    bool flow_sampler() const { return kind == AgentKind::BC || kind == AgentKind::IQLD || kind == AgentKind::CFGRL; }
+    // the kind's FlowShape on this handle: the row's halves, shared_x and tables; the steps and the goal block; a sweep where there is a guidance weight
     FlowShape flow_shape(bool sweep) const {
-        if (kind == AgentKind::BC) return {1, true, 1, bc_steps, 0, false};
-        if (kind == AgentKind::IQLD) return {2, true, 2, bc_steps, 0, sweep};
-        return {2, false, 0, gcfg.flow_steps, gcfg.goal_dim, sweep};   // CFGRL
+        FlowShape sh = desc().flow;
+        sh.S = has(K_GOALS) ? gcfg.flow_steps : bc_steps;
+        sh.goal_dim = has(K_GOALS) ? gcfg.goal_dim : 0;
+        sh.sweep = sweep && sh.halves == 2;
+        return sh;
     }
     // the loop-invariant layer-0 term of a hoisted flow sampler: C0 = X W0 + b0 over `rows` rows
     void emit_c0(Program& pr, const float* X, int rows, float* C0e) {
@@ -4288,7 +4199,7 @@ struct fql_engine {
                          1.0f / (float)fs, (float)(s + 1) / (float)fs);
         schedule(ev.prog_os, W);
         schedule(ev.prog_flow, W);
-        if (kind == AgentKind::IFQL) {   // best-of-N scoring: the critic pair on every sample row
+        if (desc().sampler == SMP_BEST_OF_N) {   // the scoring pass: the critic pair on every sample row
             ev.Xq = dalloc(W, (size_t)n_pad * nets[NET_C0].in_p());
             for (int e = 0; e < 2; ++e) {
                 ev.p_q[e] = make_pass(W, NET_C0 + e, n_pad, ev.Xq, false, false);
@@ -4317,9 +4228,11 @@ struct fql_engine {
         if (it != evals.end()) return *it->second;
         auto ev = std::make_unique<Eval>();
         ev->n_pad = n_pad;
-        if (flow_sampler()) build_flow_sampler(*ev, flow_shape(sweep));
-        else if (actor_on_obs()) build_actor_eval(*ev);
-        else build_fql_eval(*ev);
+        switch (desc().sampler) {
+            case SMP_FLOW: build_flow_sampler(*ev, flow_shape(sweep)); break;
+            case SMP_ACTOR: build_actor_eval(*ev); break;
+            case SMP_ONESTEP: case SMP_BEST_OF_N: build_fql_eval(*ev); break;
+        }
         return *(evals[key] = std::move(ev));
     }
     // The row-chunk loop of every sampling path.  A chunk is <= 4096 rows (256 image rows) of rows_per_obs rows per observation: its
@@ -4377,31 +4290,15 @@ struct fql_engine {
             hipLaunchKernelGGL(fql_extract_kernel, dim3((c.m * ad + 255) / 256), dim3(256), 0, s, src16, c.out, c.m, ad, pad16(ad));
         });
     }
-    // The actors on obs: the actor's forward over the rows, then the kind's own kernel on its output.  noise: [n, act] raw N(0, 1) or null
-    // (Philox keyed by (seed, sd) and the row number of the call: chunking does not change the draw).
-    //   ReBRAC (agents/rebrac.py:136-152): clip(mode(actor(obs)) + clip(N(0, 1) actor_noise temperature, +-actor_noise_clip), -1, 1)
-    //   SAC (agents/sac.py:125-136): clip(tanh(mean + exp(ls) temperature eps), -1, 1) (no tanh without tanh_squash)
-    //   IQL (agents/iql.py:158-169): clip(mean + exp(clip(log_stds)) temperature eps, -1, 1)
+    // The actors on obs: the actor's forward over the rows, then the kind's own launch on its output (KindDesc::act).  noise: [n, act] raw
+    // N(0, 1) or null (Philox keyed by (seed, sd) and the row number of the call: chunking does not change the draw).
     void sample_actor(const float* obs, const float* noise, uint64_t sd, float temperature, int n, float* out, hipStream_t s, bool own_stream) {
-        const int od = cfg.obs_dim, ad = cfg.act_dim, ap = pad16(ad);
+        const int od = cfg.obs_dim;
         sample_chunks(obs, noise, n, out, s, own_stream, SampleSpec{temperature}, [&](const SampleChunk& c) {
-            const int m = c.m, start = c.start;
-            const float* z = c.z;
-            AssembleArgs aa{c.o, nullptr, c.ev.X, seed, sd, m, c.ev.n_pad, od, 0, nets[NET_BC].in_p()};   // [obs | 0]
+            AssembleArgs aa{c.o, nullptr, c.ev.X, seed, sd, c.m, c.ev.n_pad, od, 0, nets[NET_BC].in_p()};   // [obs | 0]
             hipLaunchKernelGGL(fql_assemble_kernel, dim3((c.ev.n_pad + 3) / 4), dim3(FQL_THREADS), 0, s, aa);
             run_launches(c.ev.prog_os, s);
-            const float* mean = c.ev.p_os.out;
-            if (kind == AgentKind::REBRAC) {
-                RebracActArgs ra{mean, z, c.out, seed, sd, m, ad, ap, ad, ad, 0, start, z ? 1 : 2, rcfg.tanh_squash, 1,
-                                 rcfg.actor_noise * temperature, rcfg.actor_noise_clip};
-                hipLaunchKernelGGL(fql_rebrac_act_kernel, dim3((m * ad + FQL_THREADS - 1) / FQL_THREADS), dim3(FQL_THREADS), 0, s, ra);
-            } else if (kind == AgentKind::SAC) {
-                SacActArgs sa{mean, z, c.out, c.out, nullptr, seed, sd, m, ad, ap, ad, ad, 0, start, m, z ? 1 : 2, scfg.tanh_squash, 1, temperature};
-                hipLaunchKernelGGL(fql_sac_act_kernel, dim3((m + FQL_THREADS - 1) / FQL_THREADS), dim3(FQL_THREADS), 0, s, sa);
-            } else {
-                IqlSampleArgs sa{mean, qcfg.const_std ? nullptr : P + ls_off, z, c.out, seed, sd, m, ad, ap, start, temperature};
-                hipLaunchKernelGGL(fql_iql_sample_kernel, dim3((m * ad + FQL_THREADS - 1) / FQL_THREADS), dim3(FQL_THREADS), 0, s, sa);
-            }
+            desc().act(*this, ActChunk{c.ev.p_os.out, c.z, c.out, sd, c.m, c.start, temperature}, s);
         });
     }
     // sample_actions of the flow policies (build_flow_sampler's program between the kind's assemble launch and the extract launch):
@@ -4477,34 +4374,20 @@ struct fql_engine {
     }
     // sample_actions of the handle's kind (the temperature is ReBRAC's, SAC's and IQL's)
     void sample(const float* obs, const float* noise, uint64_t sd, float temperature, int n, float* out, hipStream_t s, bool own_stream) {
-        switch (kind) {
-            case AgentKind::FQL: eval_rows(false, obs, noise, sd, n, out, s, own_stream); break;
-            case AgentKind::IFQL: sample_best_of_n(obs, noise, sd, n, out, s, own_stream); break;
-            case AgentKind::BC: sample_flow(obs, noise, sd, n, out, s, own_stream, FlowCall{}); break;
-            default: sample_actor(obs, noise, sd, temperature, n, out, s, own_stream); break;
+        switch (desc().sampler) {
+            case SMP_ONESTEP: eval_rows(false, obs, noise, sd, n, out, s, own_stream); break;
+            case SMP_BEST_OF_N: sample_best_of_n(obs, noise, sd, n, out, s, own_stream); break;
+            case SMP_FLOW: sample_flow(obs, noise, sd, n, out, s, own_stream, FlowCall{}); break;   // (BC: the CFG kinds' calls pass their cfg and goals to sample_flow)
+            case SMP_ACTOR: sample_actor(obs, noise, sd, temperature, n, out, s, own_stream); break;
         }
     }
     // ---------------------------------------------------------------------------------------
     // module queries: agent.network.select(module)(...) (utils/flax_utils.py ModuleDict / TrainState.select), DESIGN.md section 21
     // ---------------------------------------------------------------------------------------
-    // The modules a handle of this kind answers for, under the reference's names without "modules_".  members 2: the stacked critic,
-    // nets `net` and `net + 1` on the same rows.  scalar: the head is one column (Value), the result [members, n]; else [n, act].
-    // Not here, and why (include/fql_amd.h): the Gaussian actors return a distribution object in the reference; IQL-diffusion's actor, BC's
+    // The modules a handle of this kind answers for (the row's ModuleSpec list).
+    // Not there, and why (include/fql_amd.h): the Gaussian actors return a distribution object in the reference; IQL-diffusion's actor, BC's
     // policy and CFGRL's actor_flow read host-built embeddings and the unc_embed row.
-    struct ModuleSpec { const char* name; int net, members; bool scalar, act, times; };
-    std::vector<ModuleSpec> modules() const {
-        std::vector<ModuleSpec> m;
-        if (kind == AgentKind::BC || kind == AgentKind::CFGRL) return m;
-        m.push_back({"critic", NET_C0, 2, true, true, false});
-        m.push_back({"target_critic", NET_T0, 2, true, true, false});
-        if (has_value_net()) m.push_back({"value", NET_OS, 1, true, false, false});
-        if (kind == AgentKind::FQL) {
-            m.push_back({"actor_bc_flow", NET_BC, 1, false, true, true});
-            m.push_back({"actor_onestep_flow", NET_OS, 1, false, true, false});
-        }
-        if (kind == AgentKind::IFQL) m.push_back({"actor_flow", NET_BC, 1, false, true, true});
-        return m;
-    }
+    std::vector<ModuleSpec> modules() const { return {desc().modules, desc().modules + desc().nmodules}; }
     // The workspace of module `mi` over n_pad rows: the padded input, one pass per member on lane 0 (the 16-row kernels of every sampling
     // path: a row's result does not depend on the rows beside it) without saved activations, scheduled once.
     Query& get_query(int mi, const ModuleSpec& sp, int n_pad) {
@@ -4589,6 +4472,273 @@ struct fql_engine {
         set_source(d, s);
     }
 };
+
+// ================================================================================================
+// k_kinds: one row per kind (KindDesc, above), each kind's hooks in front of the table
+// ================================================================================================
+namespace {
+
+// ---- FQL (agents/fql.py) ----
+const Mod k_fql_mods[4] = {{"modules_actor_bc_flow", "mlp", NET_BC, -1, true, ENC_BC},
+                           {"modules_actor_onestep_flow", "mlp", NET_OS, -1, true, ENC_OS},
+                           {"modules_critic", "value_net", NET_C0, NET_C1, true, ENC_C},
+                           {"modules_target_critic", "value_net", NET_T0, NET_T1, false, ENC_T}};
+const ModuleSpec k_fql_modules[4] = {{"critic", NET_C0, 2, true, true, false}, {"target_critic", NET_T0, 2, true, true, false},
+                                     {"actor_bc_flow", NET_BC, 1, false, true, true}, {"actor_onestep_flow", NET_OS, 1, false, true, false}};
+// the kinds with a value net answer for the first three of these, IFQL for its actor_flow too; the other critic kinds for the pair alone
+const ModuleSpec k_value_modules[4] = {{"critic", NET_C0, 2, true, true, false}, {"target_critic", NET_T0, 2, true, true, false},
+                                       {"value", NET_OS, 1, true, false, false}, {"actor_flow", NET_BC, 1, false, true, true}};
+void fql_nets(fql_engine& e, int od, int ad) { e.nets[NET_BC] = e.actor_net(od + ad + 1, ad); e.nets[NET_OS] = e.actor_net(od + ad, ad); }
+
+// ---- IFQL (agents/ifql.py:215-225): the value net is a 1-member Value, so its leaves are unstacked ----
+const Mod k_ifql_mods[4] = {{"modules_actor_flow", "mlp", NET_BC, -1, true, ENC_BC},
+                            {"modules_critic", "value_net", NET_C0, NET_C1, true, ENC_C},
+                            {"modules_target_critic", "value_net", NET_T0, NET_T1, false, ENC_T},
+                            {"modules_value", "value_net", NET_OS, -1, true, ENC_OS}};
+void ifql_nets(fql_engine& e, int od, int ad) { e.nets[NET_BC] = e.actor_net(od + ad + 1, ad); e.nets[NET_OS] = e.value_net(od); }   // value (agents/ifql.py:188-193)
+const char* ifql_check(const void* kind_cfg) {
+    const auto* c = static_cast<const fql_ifql_config*>(kind_cfg);
+    if (!(c->expectile > 0.0f && c->expectile < 1.0f)) return "expectile must be in (0, 1)";
+    if (c->num_samples < 1 || c->num_samples > 4096) return "num_samples must be in [1, 4096]";
+    return nullptr;
+}
+void ifql_adopt(fql_engine& e, const void* kind_cfg) {
+    const auto* c = static_cast<const fql_ifql_config*>(kind_cfg);
+    e.expectile = c->expectile; e.num_samples = c->num_samples;
+}
+
+// ---- ReBRAC (agents/rebrac.py:199-213): Actor modules hold actor_net/Dense_0..nh-1 (+ LayerNorm_i) and mean_net (the last layer) ----
+const Mod k_rebrac_mods[4] = {{"modules_actor", "actor_net", NET_BC, -1, true, ENC_BC, true},
+                              {"modules_critic", "value_net", NET_C0, NET_C1, true, ENC_C},
+                              {"modules_target_actor", "actor_net", NET_TA, -1, false, ENC_BC, true},
+                              {"modules_target_critic", "value_net", NET_T0, NET_T1, false, ENC_T}};
+void rebrac_nets(fql_engine& e, int od, int ad) { e.nets[NET_BC] = e.nets[NET_TA] = e.actor_net(od, ad); }   // actor (utils/networks.py:82-150)
+const char* rebrac_check(const void* kind_cfg) {
+    const auto* c = static_cast<const fql_rebrac_config*>(kind_cfg);
+    if (!(c->actor_noise >= 0.0f) || !(c->actor_noise_clip >= 0.0f)) return "actor_noise and actor_noise_clip must be >= 0";
+    if (!(c->actor_fc_scale > 0.0f)) return "actor_fc_scale must be > 0";
+    if (!std::isfinite(c->alpha_actor) || !std::isfinite(c->alpha_critic)) return "alpha_actor and alpha_critic must be finite";
+    if (c->tanh_squash != 0 && c->tanh_squash != 1) return "tanh_squash must be 0 or 1";
+    return nullptr;
+}
+void rebrac_adopt(fql_engine& e, const void* kind_cfg) { e.rcfg = *static_cast<const fql_rebrac_config*>(kind_cfg); }
+// agents/rebrac.py:136-152: clip(mode(actor(obs)) + clip(N(0, 1) actor_noise temperature, +-actor_noise_clip), -1, 1)
+void rebrac_act(const fql_engine& e, const ActChunk& c, hipStream_t s) {
+    const int ad = e.cfg.act_dim, ap = pad16(ad);
+    RebracActArgs ra{c.mean, c.z, c.out, e.seed, c.sd, c.m, ad, ap, ad, ad, 0, c.start, c.z ? 1 : 2, e.rcfg.tanh_squash, 1,
+                     e.rcfg.actor_noise * c.temperature, e.rcfg.actor_noise_clip};
+    hipLaunchKernelGGL(fql_rebrac_act_kernel, dim3((c.m * ad + FQL_THREADS - 1) / FQL_THREADS), dim3(FQL_THREADS), 0, s, ra);
+}
+
+// ---- SAC (agents/sac.py:170-196): Actor (actor_net, log_std_net, mean_net), the 0-d LogParam (n0 = -1), critic, target critic ----
+const Mod k_sac_mods[4] = {{"modules_actor", "actor_net", NET_BC, -1, true, ENC_BC, true},
+                           {"modules_alpha", "", -1, -1, true, ENC_BC},
+                           {"modules_critic", "value_net", NET_C0, NET_C1, true, ENC_C},
+                           {"modules_target_critic", "value_net", NET_T0, NET_T1, false, ENC_T}};
+void sac_nets(fql_engine& e, int od, int ad) { e.nets[NET_BC] = e.actor_net(od, 2 * pad16(ad)); }   // actor_net + [mean_net | log_std_net]
+const char* sac_check(const void* kind_cfg) {
+    const auto* c = static_cast<const fql_sac_config*>(kind_cfg);
+    if (c->state_dependent_std != 1) return "only state_dependent_std = 1 is available (the const_std=False vector form is not)";
+    if (c->tanh_squash != 0 && c->tanh_squash != 1) return "tanh_squash must be 0 or 1";
+    if (!(c->actor_fc_scale > 0.0f)) return "actor_fc_scale must be > 0";
+    if (!std::isnan(c->target_entropy) && !std::isfinite(c->target_entropy)) return "target_entropy must be finite or NaN (automatic)";
+    if (std::isnan(c->target_entropy) && !std::isfinite(c->target_entropy_multiplier)) return "target_entropy_multiplier must be finite";
+    return nullptr;
+}
+void sac_adopt(fql_engine& e, const void* kind_cfg) {   // sac.py create: target_entropy = -target_entropy_multiplier * action_dim when None
+    e.scfg = *static_cast<const fql_sac_config*>(kind_cfg);
+    e.target_entropy = std::isnan(e.scfg.target_entropy) ? -e.scfg.target_entropy_multiplier * (float)e.cfg.act_dim : e.scfg.target_entropy;
+}
+bool sac_leaves(fql_engine& e, LeafSite at, const Mod* m) {
+    if (at == LS_NO_NET) {   // modules_alpha/log_value: shape (), one float padded to an Adam quad
+        e.add_leaf(std::string(m->name) + "/log_value", false, 1, 1, e.alpha_off, 1, 4);
+        e.leaves.back().ndim = 0;
+        return true;
+    }
+    if (at != LS_ACTOR_HEAD) return false;
+    // the two heads: column blocks [0, ap) and [ap, 2 ap) of the last layer, each read back as [H, act] / [act]
+    const Layer& a = e.nets[m->n0].layers.back();
+    const int ad = e.cfg.act_dim, ap = pad16(ad);
+    for (const char* head : {"log_std_net", "mean_net"}) {
+        const size_t c0 = std::strcmp(head, "mean_net") == 0 ? 0 : (size_t)ap;
+        const std::string hb = std::string(m->name) + "/" + head + "/";
+        e.add_leaf(hb + "bias", false, 1, ad, a.b + c0, 1, ap);
+        e.add_leaf(hb + "kernel", true, a.in, ad, a.w + c0, a.in_p, a.out_p);
+        e.leaves.back().segs[0].chunk_w = ap;
+    }
+    return true;
+}
+// agents/sac.py:125-136: clip(tanh(mean + exp(ls) temperature eps), -1, 1) (no tanh without tanh_squash)
+void sac_act(const fql_engine& e, const ActChunk& c, hipStream_t s) {
+    const int ad = e.cfg.act_dim, ap = pad16(ad);
+    SacActArgs sa{c.mean, c.z, c.out, c.out, nullptr, e.seed, c.sd, c.m, ad, ap, ad, ad, 0, c.start, c.m, c.z ? 1 : 2, e.scfg.tanh_squash, 1, c.temperature};
+    hipLaunchKernelGGL(fql_sac_act_kernel, dim3((c.m + FQL_THREADS - 1) / FQL_THREADS), dim3(FQL_THREADS), 0, s, sa);
+}
+
+// ---- BC (agents/bc.py:26-44): no modules, the leaves of one bare net, policy(obs, x_t, emb(t)) ----
+void bc_nets(fql_engine& e, int od, int ad) { e.nets[NET_BC] = e.actor_net(od + ad + BC_EMB, ad); }
+const char* bc_check(const void* kind_cfg) {
+    const auto* c = static_cast<const fql_bc_config*>(kind_cfg);
+    return c->denoise_steps < 1 || c->denoise_steps > 1024 ? "denoise_steps must be in [1, 1024]" : nullptr;
+}
+void bc_adopt(fql_engine& e, const void* kind_cfg) { e.bc_steps = static_cast<const fql_bc_config*>(kind_cfg)->denoise_steps; }
+
+// ---- IQL (agents/iql.py:222-227): Actor (actor_net, log_stds with const_std = 0, mean_net), critic, target critic, the 1-member value ----
+const Mod k_iql_mods[4] = {{"modules_actor", "actor_net", NET_BC, -1, true, ENC_BC, true},
+                           {"modules_critic", "value_net", NET_C0, NET_C1, true, ENC_C},
+                           {"modules_target_critic", "value_net", NET_T0, NET_T1, false, ENC_T},
+                           {"modules_value", "value_net", NET_OS, -1, true, ENC_OS}};
+void iql_nets(fql_engine& e, int od, int ad) { e.nets[NET_BC] = e.actor_net(od, ad); e.nets[NET_OS] = e.value_net(od); }
+const char* iql_check(const void* kind_cfg) {
+    const auto* c = static_cast<const fql_iql_config*>(kind_cfg);
+    if (!(c->expectile > 0.0f && c->expectile < 1.0f)) return "expectile must be in (0, 1)";
+    if (!std::isfinite(c->alpha)) return "alpha must be finite";
+    if (c->actor_loss != 0 && c->actor_loss != 1) return "actor_loss must be 0 (awr) or 1 (ddpgbc)";
+    if (c->const_std != 0 && c->const_std != 1) return "const_std must be 0 or 1";
+    return nullptr;
+}
+void iql_adopt(fql_engine& e, const void* kind_cfg) { e.qcfg = *static_cast<const fql_iql_config*>(kind_cfg); }
+InfoSet iql_infos(const fql_engine& e) {
+    const bool ddpg = e.qcfg.actor_loss == 1;
+    return {k_iql_info_names[ddpg ? 1 : 0], ddpg ? FQL_IQL_DDPGBC_NUM_INFO : FQL_IQL_AWR_NUM_INFO};
+}
+size_t iql_extra(const fql_engine& e) { return e.qcfg.const_std ? 0 : pad16(e.cfg.act_dim); }   // modules_actor/log_stds: [act], padded to ap
+bool iql_leaves(fql_engine& e, LeafSite at, const Mod* m) {   // "log_stds" sorts between actor_net and mean_net
+    if (at == LS_ACTOR_HEAD && !e.qcfg.const_std)
+        e.add_leaf(std::string(m->name) + "/log_stds", false, 1, e.cfg.act_dim, e.ls_off, 1, pad16(e.cfg.act_dim));
+    return false;
+}
+// agents/iql.py:158-169: clip(mean + exp(clip(log_stds)) temperature eps, -1, 1)
+void iql_act(const fql_engine& e, const ActChunk& c, hipStream_t s) {
+    const int ad = e.cfg.act_dim, ap = pad16(ad);
+    IqlSampleArgs sa{c.mean, e.qcfg.const_std ? nullptr : e.P + e.ls_off, c.z, c.out, e.seed, c.sd, c.m, ad, ap, c.start, c.temperature};
+    hipLaunchKernelGGL(fql_iql_sample_kernel, dim3((c.m * ad + FQL_THREADS - 1) / FQL_THREADS), dim3(FQL_THREADS), 0, s, sa);
+}
+
+// ---- IQL-diffusion (agents/iql_diffusion.py:87-91): four bare TrainStates, no ModuleDict; the actor's leaves are BC's plus the embedding ----
+const Mod k_iqld_mods[3] = {{"critic", "value_net", NET_C0, NET_C1, true, ENC_C},
+                            {"target_critic", "value_net", NET_T0, NET_T1, false, ENC_T},
+                            {"value", "value_net", NET_OS, -1, true, ENC_OS}};
+void iqld_nets(fql_engine& e, int od, int ad) {   // iql_diffusion.py:54-67
+    e.nets[NET_BC] = e.actor_net(od + ad + BC_EMB + IQLD_EMBED, ad); e.nets[NET_OS] = e.value_net(od);
+}
+const char* iqld_check(const void* kind_cfg) {
+    const auto* c = static_cast<const fql_iqld_config*>(kind_cfg);
+    if (c->optimal_var == 3 || c->optimal_var == 4)
+        return "optimal_var 'softmax' / 'sampled_adv_softmax' (the continuous policy with an external bc_agent) is not available: "
+               "the binary family only (0 binary, 1 binary_awr_loss, 2 binary_softmax_loss)";
+    if (c->optimal_var < 0 || c->optimal_var > 4) return "optimal_var must be 0 (binary), 1 (binary_awr_loss) or 2 (binary_softmax_loss)";
+    if (c->opt_decay_schedule != 0) return "opt_decay_schedule 'cosine' is not available (a constant actor_lr only)";
+    if (!(c->expectile > 0.0f && c->expectile < 1.0f)) return "expectile must be in (0, 1)";
+    if (!(c->actor_lr > 0.0f) || !(c->value_lr > 0.0f) || !(c->critic_lr > 0.0f)) return "actor_lr, value_lr and critic_lr must be > 0";
+    if (!std::isfinite(c->awr_temperature) || !std::isfinite(c->softmax_beta)) return "awr_temperature and softmax_beta must be finite";
+    if (c->target_extraction != 0 && c->target_extraction != 1) return "target_extraction must be 0 or 1";
+    if (c->denoise_steps < 1 || c->denoise_steps > 1024) return "denoise_steps must be in [1, 1024]";
+    return nullptr;
+}
+void iqld_adopt(fql_engine& e, const void* kind_cfg) { e.dcfg = *static_cast<const fql_iqld_config*>(kind_cfg); e.bc_steps = e.dcfg.denoise_steps; }
+bool iqld_leaves(fql_engine& e, LeafSite at, const Mod*) {   // nn.Embed(2, 32): sorts behind Dense_0
+    if (at == LS_BARE_HEAD) e.add_leaf("actor/Embed_0/embedding", true, 2, IQLD_EMBED, e.emb_off, 2, IQLD_EMBED);
+    return false;
+}
+// nn.Embed(2, 32): with in_axis = -2 and out_axis = 0 both name axis 0: in_size = out_size = 2, receptive field = 64 / (2 * 2) = 16,
+// fan_in = 2 * 16 = 32 (the feature count)
+EmbedInit iqld_embed_init(const fql_engine&) { return {2 * IQLD_EMBED, IQLD_EMBED}; }
+
+// ---- CFGRL (agents/cfgrl.py:143-156): one ModuleDict, actor_flow and the [1, G] embedding behind it ----
+const Mod k_cfgrl_mods[1] = {{"modules_actor_flow", "mlp", NET_BC, -1, true, ENC_BC}};
+void cfgrl_nets(fql_engine& e, int od, int ad) { e.nets[NET_BC] = e.actor_net(od + e.gcfg.goal_dim + ad + 1, ad); }   // actor_flow(obs, goals, x_t, t) (utils/networks.py:237-284)
+const char* cfgrl_check(const void* kind_cfg) {
+    const auto* c = static_cast<const fql_cfgrl_config*>(kind_cfg);
+    if (c->actor_geom_sample != 0)
+        return "actor_geom_sample = True is not available: the geometric offset is a ceil of a ratio of logarithms, which the device's "
+               "log and numpy's may round to different integers (uniform trajectory goals only)";
+    if (c->goal_dim < 1 || c->goal_dim > 1024) return "goal_dim must be in [1, 1024] (layer 0 is obs + goal_dim + act + 1 wide)";
+    if (c->flow_steps < 1 || c->flow_steps > 1024) return "flow_steps must be in [1, 1024]";
+    if (!std::isfinite(c->cfg)) return "cfg must be finite";
+    if (!(c->p_uncond >= 0.0 && c->p_uncond <= 1.0)) return "p_uncond must be in [0, 1]";
+    const double pc = c->actor_p_curgoal, pt = c->actor_p_trajgoal, pr = c->actor_p_randomgoal;
+    if (!(pc >= 0.0 && pt >= 0.0 && pr >= 0.0) || std::fabs(pc + pt + pr - 1.0) > 1e-8)   // utils/datasets.py:159-161
+        return "actor_p_curgoal + actor_p_trajgoal + actor_p_randomgoal must be 1, each >= 0";
+    return nullptr;
+}
+void cfgrl_adopt(fql_engine& e, const void* kind_cfg) { e.gcfg = *static_cast<const fql_cfgrl_config*>(kind_cfg); }
+bool cfgrl_leaves(fql_engine& e, LeafSite at, const Mod*) {   // nn.Embed(1, goal_dim): "modules_unc_embed" sorts behind "modules_actor_flow"
+    if (at == LS_LAST) e.add_leaf("modules_unc_embed/Embed_0/embedding", true, 1, e.gcfg.goal_dim, e.emb_off, 1, pad16(e.gcfg.goal_dim));
+    return false;
+}
+// nn.Embed(1, G): by the derivation at iqld_embed_init in_size = out_size = 1, receptive field = G, fan_in = G
+EmbedInit cfgrl_embed_init(const fql_engine& e) { return {e.gcfg.goal_dim, e.gcfg.goal_dim}; }
+
+const KindDesc k_kinds[kNumKinds] = {
+    {"FQL", "an FQL handle", "fql_create", K_CRITIC | K_CHAIN | K_VISUAL,
+     k_info_names, FQL_NUM_INFO, nullptr, 10, {0, 4, -1},
+     NZ_EPS1 | NZ_X0 | NZ_T | NZ_Z | NZ_EPS2, nullptr,
+     nullptr, nullptr, fql_nets, nullptr, nullptr,
+     k_fql_mods, 4, nullptr, {"modules_actor_bc_flow/", "modules_actor_onestep_flow/", "modules_critic/"}, nullptr,
+     HI_GLOROT, nullptr, nullptr,
+     &fql_engine::build_fql_workspace, [](const fql_engine& e) { return e.fql_macs(); },
+     SMP_ONESTEP, nullptr, {}, k_fql_modules, 4},
+    {"IFQL", "an IFQL handle", "fql_ifql_create", K_CRITIC,
+     k_ifql_info_names, FQL_IFQL_NUM_INFO, nullptr, 9, {0, 4, 8},   // agents/ifql.py:79-98: value + critic + actor; nine infos
+     NZ_X0 | NZ_T, "IFQL reads only x0 and t of fql_noise (eps1, z and eps2 must be NULL)",
+     ifql_check, ifql_adopt, ifql_nets, nullptr, nullptr,
+     k_ifql_mods, 4, nullptr, {"modules_actor_flow/", "modules_value/", "modules_critic/"}, nullptr,
+     HI_GLOROT, nullptr, nullptr,
+     &fql_engine::build_ifql_workspace, [](const fql_engine& e) { return e.ifql_macs(); },
+     SMP_BEST_OF_N, nullptr, {}, k_value_modules, 4},
+    {"ReBRAC", "a ReBRAC handle", "fql_rebrac_create", K_CRITIC | K_POLYAK_ALL | K_NEXT_ACTIONS,
+     k_rebrac_info_names, FQL_REBRAC_NUM_INFO, nullptr, 0, {-1, -1, -1},
+     NZ_EPS1, "ReBRAC reads only eps1 of fql_noise (x0, t, z and eps2 must be NULL)",
+     rebrac_check, rebrac_adopt, rebrac_nets, nullptr, nullptr,
+     k_rebrac_mods, 4, nullptr, {"modules_actor/", "modules_critic/", "modules_critic/"}, nullptr,   // (two trained modules: the critic's range twice)
+     HI_GLOROT, [](const fql_engine& e) { return (double)e.rcfg.actor_fc_scale; }, nullptr,
+     &fql_engine::build_rebrac_workspace, [](const fql_engine& e) { return e.rebrac_macs(true); },
+     SMP_ACTOR, rebrac_act, {}, k_value_modules, 2},
+    {"SAC", "a SAC handle", "fql_sac_create", K_CRITIC,
+     k_sac_info_names, FQL_SAC_NUM_INFO, nullptr, 0, {-1, -1, -1},
+     NZ_EPS1 | NZ_EPS2, "SAC reads only eps1 and eps2 of fql_noise (x0, t and z must be NULL)",
+     sac_check, sac_adopt, sac_nets, &fql_engine::alpha_off, [](const fql_engine&) { return (size_t)4; },   // modules_alpha/log_value: one float, padded to an Adam quad
+     k_sac_mods, 4, nullptr, {"modules_actor/", "modules_alpha/", "modules_critic/"}, sac_leaves,
+     HI_TWO_HEADS, [](const fql_engine& e) { return (double)e.scfg.actor_fc_scale; }, nullptr,
+     &fql_engine::build_sac_workspace, [](const fql_engine& e) { return e.sac_macs(); },
+     SMP_ACTOR, sac_act, {}, k_value_modules, 2},
+    {"BC", "a BC handle", "fql_bc_create", K_TIME_TABLE,
+     k_bc_info_names, FQL_BC_NUM_INFO, nullptr, 0, {-1, -1, -1},
+     NZ_X0 | NZ_T, "BC reads only x0 and t of fql_noise (eps1, z and eps2 must be NULL)",
+     bc_check, bc_adopt, bc_nets, nullptr, nullptr,
+     nullptr, 0, "", {nullptr, nullptr, nullptr}, nullptr,   // (one module: every chunk)
+     HI_LECUN_TRUNC, nullptr, nullptr,
+     &fql_engine::build_bc_workspace, [](const fql_engine& e) { return e.bc_macs(); },
+     SMP_FLOW, nullptr, {1, true, 1}, nullptr, 0},
+    {"IQL", "an IQL handle", "fql_iql_create", K_CRITIC | K_OWN_INFO,
+     nullptr, 0, iql_infos, 0, {-1, -1, -1},
+     NZ_EPS1, "IQL reads only eps1 of fql_noise (x0, t, z and eps2 must be NULL)",
+     iql_check, iql_adopt, iql_nets, &fql_engine::ls_off, iql_extra,
+     k_iql_mods, 4, nullptr, {"modules_actor/", "modules_value/", "modules_critic/"}, iql_leaves,
+     HI_GLOROT, [](const fql_engine&) { return 1e-2; }, nullptr,   // Actor.final_fc_init_scale (utils/networks.py:106)
+     &fql_engine::build_iql_workspace, [](const fql_engine& e) { return e.iql_macs(); },
+     SMP_ACTOR, iql_act, {}, k_value_modules, 3},
+    {"IQL-diffusion", "an IQL-diffusion handle", "fql_iqld_create", K_CRITIC | K_OWN_INFO | K_TIME_TABLE | K_ACTOR_STATE,
+     k_iqld_info_names, FQL_IQLD_NUM_INFO, nullptr, 0, {-1, -1, -1},
+     NZ_X0 | NZ_T, "IQL-diffusion reads only x0 and t of fql_noise (eps1, z and eps2 must be NULL)",
+     iqld_check, iqld_adopt, iqld_nets, &fql_engine::emb_off, [](const fql_engine&) { return (size_t)2 * IQLD_EMBED; },   // actor/Embed_0/embedding: [2, 32]
+     k_iqld_mods, 3, "actor/", {"actor/", "value/", "critic/"}, iqld_leaves,   // (bare: the policy net is the `actor` field)
+     HI_LECUN_TRUNC, nullptr, iqld_embed_init,
+     &fql_engine::build_iqld_workspace, [](const fql_engine& e) { return e.iqld_macs(true, true); },
+     SMP_FLOW, nullptr, {2, true, 2}, k_value_modules, 3},
+    {"CFGRL", "a CFGRL handle", "fql_cfgrl_create", K_GOALS,
+     k_cfgrl_info_names, FQL_CFGRL_NUM_INFO, nullptr, 0, {-1, -1, -1},
+     NZ_X0 | NZ_T, "CFGRL reads only x0 and t of fql_noise (eps1, z and eps2 must be NULL)",
+     cfgrl_check, cfgrl_adopt, cfgrl_nets, &fql_engine::emb_off, [](const fql_engine& e) { return (size_t)pad16(e.gcfg.goal_dim); },   // modules_unc_embed/Embed_0/embedding: [1, G], padded
+     k_cfgrl_mods, 1, nullptr, {nullptr, nullptr, nullptr}, cfgrl_leaves,   // (one TrainState: every chunk)
+     HI_GLOROT, nullptr, cfgrl_embed_init,
+     &fql_engine::build_cfgrl_workspace, [](const fql_engine& e) { return e.bc_macs(); },
+     SMP_FLOW, nullptr, {2, false, 0}, nullptr, 0},
+};
+
+}  // namespace
+const KindDesc& fql_engine::desc() const { return k_kinds[(int)kind]; }
 
 // ================================================================================================
 // C ABI
@@ -4825,72 +4975,12 @@ static int create_engine(const fql_config* cfg, AgentSpec agent, uint64_t seed, 
     *out = nullptr;
     const AgentKind kind = agent.kind;
     const KindDesc& kd = k_kinds[(int)kind];
-    const auto* icfg = static_cast<const fql_ifql_config*>(agent.cfg);
-    const auto* rcfg = static_cast<const fql_rebrac_config*>(agent.cfg);
-    const auto* scfg = static_cast<const fql_sac_config*>(agent.cfg);
-    const auto* bcfg = static_cast<const fql_bc_config*>(agent.cfg);
-    const auto* qcfg = static_cast<const fql_iql_config*>(agent.cfg);
-    const auto* dcfg = static_cast<const fql_iqld_config*>(agent.cfg);
-    const auto* gcfg = static_cast<const fql_cfgrl_config*>(agent.cfg);
     auto refuse = [&](const std::string& why) { g_create_error = std::string(kd.create) + ": " + why; return FQL_E_INVALID; };
-    if (kind != AgentKind::FQL) {   // every other kind: state observations and fp32 only
+    if (!(kd.traits & K_VISUAL)) {   // state observations and fp32 only
         if (cfg->encoder != 0) return refuse(std::string("visual encoders are not available for ") + kd.name + " (encoder must be 0)");
         if (cfg->precision != 0) return refuse(std::string(kd.name) + " runs in fp32 only (precision must be 0)");
     }
-    switch (kind) {
-        case AgentKind::FQL: break;
-        case AgentKind::IFQL:
-            if (!(icfg->expectile > 0.0f && icfg->expectile < 1.0f)) return refuse("expectile must be in (0, 1)");
-            if (icfg->num_samples < 1 || icfg->num_samples > 4096) return refuse("num_samples must be in [1, 4096]");
-            break;
-        case AgentKind::REBRAC:
-            if (!(rcfg->actor_noise >= 0.0f) || !(rcfg->actor_noise_clip >= 0.0f)) return refuse("actor_noise and actor_noise_clip must be >= 0");
-            if (!(rcfg->actor_fc_scale > 0.0f)) return refuse("actor_fc_scale must be > 0");
-            if (!std::isfinite(rcfg->alpha_actor) || !std::isfinite(rcfg->alpha_critic)) return refuse("alpha_actor and alpha_critic must be finite");
-            if (rcfg->tanh_squash != 0 && rcfg->tanh_squash != 1) return refuse("tanh_squash must be 0 or 1");
-            break;
-        case AgentKind::SAC:
-            if (scfg->state_dependent_std != 1) return refuse("only state_dependent_std = 1 is available (the const_std=False vector form is not)");
-            if (scfg->tanh_squash != 0 && scfg->tanh_squash != 1) return refuse("tanh_squash must be 0 or 1");
-            if (!(scfg->actor_fc_scale > 0.0f)) return refuse("actor_fc_scale must be > 0");
-            if (!std::isnan(scfg->target_entropy) && !std::isfinite(scfg->target_entropy)) return refuse("target_entropy must be finite or NaN (automatic)");
-            if (std::isnan(scfg->target_entropy) && !std::isfinite(scfg->target_entropy_multiplier)) return refuse("target_entropy_multiplier must be finite");
-            break;
-        case AgentKind::BC:
-            if (bcfg->denoise_steps < 1 || bcfg->denoise_steps > 1024) return refuse("denoise_steps must be in [1, 1024]");
-            break;
-        case AgentKind::IQL:
-            if (!(qcfg->expectile > 0.0f && qcfg->expectile < 1.0f)) return refuse("expectile must be in (0, 1)");
-            if (!std::isfinite(qcfg->alpha)) return refuse("alpha must be finite");
-            if (qcfg->actor_loss != 0 && qcfg->actor_loss != 1) return refuse("actor_loss must be 0 (awr) or 1 (ddpgbc)");
-            if (qcfg->const_std != 0 && qcfg->const_std != 1) return refuse("const_std must be 0 or 1");
-            break;
-        case AgentKind::IQLD:
-            if (dcfg->optimal_var == 3 || dcfg->optimal_var == 4)
-                return refuse("optimal_var 'softmax' / 'sampled_adv_softmax' (the continuous policy with an external bc_agent) is not available: "
-                              "the binary family only (0 binary, 1 binary_awr_loss, 2 binary_softmax_loss)");
-            if (dcfg->optimal_var < 0 || dcfg->optimal_var > 4) return refuse("optimal_var must be 0 (binary), 1 (binary_awr_loss) or 2 (binary_softmax_loss)");
-            if (dcfg->opt_decay_schedule != 0) return refuse("opt_decay_schedule 'cosine' is not available (a constant actor_lr only)");
-            if (!(dcfg->expectile > 0.0f && dcfg->expectile < 1.0f)) return refuse("expectile must be in (0, 1)");
-            if (!(dcfg->actor_lr > 0.0f) || !(dcfg->value_lr > 0.0f) || !(dcfg->critic_lr > 0.0f)) return refuse("actor_lr, value_lr and critic_lr must be > 0");
-            if (!std::isfinite(dcfg->awr_temperature) || !std::isfinite(dcfg->softmax_beta)) return refuse("awr_temperature and softmax_beta must be finite");
-            if (dcfg->target_extraction != 0 && dcfg->target_extraction != 1) return refuse("target_extraction must be 0 or 1");
-            if (dcfg->denoise_steps < 1 || dcfg->denoise_steps > 1024) return refuse("denoise_steps must be in [1, 1024]");
-            break;
-        case AgentKind::CFGRL: {
-            if (gcfg->actor_geom_sample != 0)
-                return refuse("actor_geom_sample = True is not available: the geometric offset is a ceil of a ratio of logarithms, which the device's "
-                              "log and numpy's may round to different integers (uniform trajectory goals only)");
-            if (gcfg->goal_dim < 1 || gcfg->goal_dim > 1024) return refuse("goal_dim must be in [1, 1024] (layer 0 is obs + goal_dim + act + 1 wide)");
-            if (gcfg->flow_steps < 1 || gcfg->flow_steps > 1024) return refuse("flow_steps must be in [1, 1024]");
-            if (!std::isfinite(gcfg->cfg)) return refuse("cfg must be finite");
-            if (!(gcfg->p_uncond >= 0.0 && gcfg->p_uncond <= 1.0)) return refuse("p_uncond must be in [0, 1]");
-            const double pc = gcfg->actor_p_curgoal, pt = gcfg->actor_p_trajgoal, pr = gcfg->actor_p_randomgoal;
-            if (!(pc >= 0.0 && pt >= 0.0 && pr >= 0.0) || std::fabs(pc + pt + pr - 1.0) > 1e-8)   // utils/datasets.py:159-161
-                return refuse("actor_p_curgoal + actor_p_trajgoal + actor_p_randomgoal must be 1, each >= 0");
-            break;
-        }
-    }
+    if (const char* why = kd.check ? kd.check(agent.cfg) : nullptr) return refuse(why);
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
         (void)hipGetLastError();
@@ -4902,19 +4992,7 @@ static int create_engine(const fql_config* cfg, AgentSpec agent, uint64_t seed, 
         h->cfg = *cfg;
         h->seed = seed;
         h->kind = kind;
-        switch (kind) {
-            case AgentKind::FQL: break;
-            case AgentKind::IFQL: h->expectile = icfg->expectile; h->num_samples = icfg->num_samples; break;
-            case AgentKind::REBRAC: h->rcfg = *rcfg; break;
-            case AgentKind::SAC:   // sac.py create: target_entropy = -target_entropy_multiplier * action_dim when None
-                h->scfg = *scfg;
-                h->target_entropy = std::isnan(scfg->target_entropy) ? -scfg->target_entropy_multiplier * (float)cfg->act_dim : scfg->target_entropy;
-                break;
-            case AgentKind::BC: h->bc_steps = bcfg->denoise_steps; break;
-            case AgentKind::IQL: h->qcfg = *qcfg; break;
-            case AgentKind::IQLD: h->dcfg = *dcfg; h->bc_steps = dcfg->denoise_steps; break;
-            case AgentKind::CFGRL: h->gcfg = *gcfg; break;
-        }
+        if (kd.adopt) kd.adopt(*h, agent.cfg);
         if (cfg->encoder != 0) {   // visual agent (agents/fql.py:196-202): the MLPs see the 512-wide encoding instead of obs
             if (cfg->encoder != 1 && cfg->encoder != 2) invalid("encoder %d not available (0 = none, 1 = impala_small, 2 = impala)", cfg->encoder);
             if (cfg->img_h <= 0 || cfg->img_w <= 0 || cfg->img_h % 32 || cfg->img_w % 32 || cfg->img_w > 128 || cfg->img_c <= 0 || cfg->img_c > 16)
@@ -4950,7 +5028,7 @@ static int create_engine(const fql_config* cfg, AgentSpec agent, uint64_t seed, 
         HIP_CHECK(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
         for (int l = 1; l < FQL_LANES; ++l) HIP_CHECK(hipStreamCreateWithFlags(&h->lane_streams[l], hipStreamNonBlocking));
         h->build_nets();
-        if (kind == AgentKind::BC || kind == AgentKind::IQLD) {   // the timestep-embedding table, rows k = 0..S: freq_i = float32(exp_f64(-ln(10000) i / 8)),
+        if (h->has(K_TIME_TABLE)) {   // the timestep-embedding table, rows k = 0..S: freq_i = float32(exp_f64(-ln(10000) i / 8)),
                        // arg = float32(float32(t 10000) freq_i), [cos | sin] in fp64 of that fp32 argument, rounded to fp32
             const int S = h->bc_steps;
             std::vector<float> tab((size_t)(S + 1) * BC_EMB);
@@ -4994,11 +5072,11 @@ static int create_engine(const fql_config* cfg, AgentSpec agent, uint64_t seed, 
         int bi; std::memcpy(&bi, &ninf, 4); st.gmax = bi >= 0 ? bi : bi ^ 0x7FFFFFFF;
         std::memcpy(&bi, &pinf, 4); st.gmin = bi >= 0 ? bi : bi ^ 0x7FFFFFFF;
         HIP_CHECK(hipMemcpy(h->d_state, &st, sizeof st, hipMemcpyHostToDevice));
-        if (kind == AgentKind::IQLD) {   // the actor TrainState's counters (the same initial values)
+        if (h->has(K_ACTOR_STATE)) {   // the actor TrainState's counters (the same initial values)
             HIP_CHECK(hipMalloc((void**)&h->d_state_a, sizeof(DevState)));
             HIP_CHECK(hipMemcpy(h->d_state_a, &st, sizeof st, hipMemcpyHostToDevice));
         }
-        if (kind == AgentKind::CFGRL) {
+        if (h->has(K_GOALS)) {
             HIP_CHECK(hipMalloc((void**)&h->d_gsrc, sizeof(CfgrlSrc)));
             HIP_CHECK(hipMemset(h->d_gsrc, 0, sizeof(CfgrlSrc)));
             HIP_CHECK(hipHostMalloc((void**)&h->h_gsrc_ring, 64 * sizeof(CfgrlSrc), hipHostMallocDefault));
@@ -5246,13 +5324,11 @@ int fql_total_loss(fql_handle h, const float* obs, const float* act, const float
         float tmp[10];
         HIP_CHECK(hipMemcpyAsync(tmp, &h->d_state->info[0], sizeof tmp, hipMemcpyDeviceToHost, s));
         HIP_CHECK(hipStreamSynchronize(s));
-        if (h->kind == AgentKind::IFQL) {   // agents/ifql.py:79-98: value + critic + actor; nine infos
-            if (loss) *loss = tmp[0] + tmp[4] + tmp[8];
-            if (info10) std::memcpy(info10, tmp, 9 * sizeof(float));
-        } else {
-        if (loss) *loss = tmp[0] + tmp[4];
-        if (info10) std::memcpy(info10, tmp, sizeof tmp);
-        }
+        const KindDesc& kd = h->desc();   // (FQL: critic + actor, ten infos; IFQL: value + critic + actor, nine)
+        float sum = tmp[kd.probe_terms[0]];
+        for (int i = 1; i < 3 && kd.probe_terms[i] >= 0; ++i) sum += tmp[kd.probe_terms[i]];
+        if (loss) *loss = sum;
+        if (info10) std::memcpy(info10, tmp, (size_t)kd.probe_infos * sizeof(float));
     });
 }
 
@@ -5590,10 +5666,14 @@ int fql_read_info_n(fql_handle h, float* out, int n) {
     });
 }
 
+// what every *_stats entry point says of an update: the launches of its program and its multiply-accumulates
+static void update_stats(const Program& pr, int64_t macs, int64_t* launches_per_update, int64_t* macs_per_update) {
+    if (launches_per_update) *launches_per_update = (int64_t)pr.launches.size();
+    if (macs_per_update) *macs_per_update = macs;
+}
 int fql_stats(fql_handle h, int64_t* launches_per_update, int64_t* macs_per_update, int64_t* param_count) {
     if (!h) return FQL_E_INVALID;
-    if (launches_per_update) *launches_per_update = (int64_t)h->prog_full.launches.size();
-    if (macs_per_update) *macs_per_update = h->macs_per_update();
+    update_stats(h->prog_full, h->macs_per_update(), launches_per_update, macs_per_update);
     if (param_count) {
         int64_t n = 0;
         for (const Leaf& l : h->leaves) n += (int64_t)fql_engine::leaf_count(l);
@@ -5647,8 +5727,7 @@ int fql_rebrac_sample_actions(fql_handle h, const float* obs, int n, const float
 int fql_rebrac_stats(fql_handle h, int full_update, int64_t* launches_per_update, int64_t* macs_per_update) {
     if (!h) return FQL_E_INVALID;
     FQL_ADMIT(h, EP_rebrac_stats);
-    if (launches_per_update) *launches_per_update = (int64_t)(full_update ? h->prog_full : h->prog_critic).launches.size();
-    if (macs_per_update) *macs_per_update = full_update ? h->macs_per_update() : h->rebrac_macs(false);
+    update_stats(full_update ? h->prog_full : h->prog_critic, h->rebrac_macs(full_update != 0), launches_per_update, macs_per_update);
     return FQL_OK;
 }
 
@@ -5707,8 +5786,7 @@ int fql_sac_sample_actions(fql_handle h, const float* obs, int n, const float* n
 int fql_sac_stats(fql_handle h, int64_t* launches_per_update, int64_t* macs_per_update) {
     if (!h) return FQL_E_INVALID;
     FQL_ADMIT(h, EP_sac_stats);
-    if (launches_per_update) *launches_per_update = (int64_t)h->prog_full.launches.size();
-    if (macs_per_update) *macs_per_update = h->macs_per_update();
+    update_stats(h->prog_full, h->macs_per_update(), launches_per_update, macs_per_update);
     return FQL_OK;
 }
 
@@ -5766,8 +5844,7 @@ int fql_iql_sample_actions(fql_handle h, const float* obs, int n, const float* n
 int fql_iql_stats(fql_handle h, int64_t* launches_per_update, int64_t* macs_per_update) {
     if (!h) return FQL_E_INVALID;
     FQL_ADMIT(h, EP_iql_stats);
-    if (launches_per_update) *launches_per_update = (int64_t)h->prog_full.launches.size();
-    if (macs_per_update) *macs_per_update = h->macs_per_update();
+    update_stats(h->prog_full, h->macs_per_update(), launches_per_update, macs_per_update);
     return FQL_OK;
 }
 
@@ -5818,8 +5895,7 @@ int fql_bc_stats(fql_handle h, int64_t* launches_per_update, int64_t* macs_per_u
     if (!h) return FQL_E_INVALID;
     FQL_ADMIT(h, EP_bc_stats);
     FQL_TRY(h, {
-        if (launches_per_update) *launches_per_update = (int64_t)h->prog_full.launches.size();
-        if (macs_per_update) *macs_per_update = h->macs_per_update();
+        update_stats(h->prog_full, h->macs_per_update(), launches_per_update, macs_per_update);
         if (launches_per_sample) *launches_per_sample = h->sample_flow_launches(false);   // assemble, step-bias table, C0, S (layer 0 + nh GEMMs), extract
     });
 }
@@ -5928,8 +6004,7 @@ int fql_iqld_stats(fql_handle h, int update_critic, int update_actor, int64_t* l
     if (!h) return FQL_E_INVALID;
     FQL_ADMIT(h, EP_iqld_stats);
     FQL_TRY(h, {
-        if (launches_per_update) *launches_per_update = (int64_t)h->iqld_program(update_critic != 0, update_actor != 0).launches.size();
-        if (macs_per_update) *macs_per_update = h->iqld_macs(update_critic != 0, update_actor != 0);
+        update_stats(h->iqld_program(update_critic != 0, update_actor != 0), h->iqld_macs(update_critic != 0, update_actor != 0), launches_per_update, macs_per_update);
         // assemble, step-bias table, C0, S (layer 0 + nh GEMMs + the CFG step), extract
         if (launches_per_sample) *launches_per_sample = h->sample_flow_launches(false);
     });
@@ -6036,8 +6111,7 @@ int fql_cfgrl_stats(fql_handle h, int64_t* launches_per_update, int64_t* macs_pe
     if (!h) return FQL_E_INVALID;
     FQL_ADMIT(h, EP_cfgrl_stats);
     FQL_TRY(h, {
-        if (launches_per_update) *launches_per_update = (int64_t)h->prog_full.launches.size();
-        if (macs_per_update) *macs_per_update = h->macs_per_update();
+        update_stats(h->prog_full, h->macs_per_update(), launches_per_update, macs_per_update);
         // assemble, C0, S (layer 0 + nh GEMMs + the CFG step), extract
         if (launches_per_sample) *launches_per_sample = h->sample_flow_launches(false);
     });
