@@ -65,7 +65,7 @@ def test_group_equals_standalone_twins_device_rng(K, B, H, n):
     group.close()
 
 
-# The shapes at which the fused program is built differently (fql_group_s::zip / fuse, fql_amd/csrc/fql_engine.hip).  Each is pinned to the
+# The shapes at which the fused program is built differently (fql_group_s::zip / fuse, fql_amd/csrc/fql_engine_groups.h).  Each is pinned to the
 # fp64 restatement for a single agent (test_gpu_parity.py, test_gpu_shapes.py, test_gpu_hardening.py; k8 is a shape of the cases above),
 # so the twin is a checked reference.
 PATHS = [
